@@ -15,14 +15,17 @@ this process is one rank; a plain `python bench.py --gpus N` starts the N ranks 
 rendezvous on 127.0.0.1) and rank 0 prints the line.  --shape shard is BASELINE configs[4] literally: 32 captures
 of sixteen back-to-back frames per GPU (256 concurrent captures over 8 GPUs) instead of 4096 captures of one frame.
 
-The timed region: the K-step block (--steps) is repeated until at least --min-seconds have passed; every step is a
-process call whose dense result rows AND MPDU array are delivered to page-locked host memory behind the kernels, and the
+The timed region is exactly --steps steps (with --min-seconds S > 0 the K-step block is repeated until S seconds have passed); every
+step is a process call whose dense result rows AND MPDU array are delivered to page-locked host memory behind the kernels, and the
 oldest call in flight is waited for and its rows compared with the verified ones.  Before anything is timed, the first
 call's rows are compared, capture by capture, with what the compiled reference graph reports (--check 0 = all captures).
+--dump-outputs DIR writes what the last timed step delivered (rows and MPDU bytes, see dump_outputs) as DIR/<name>.npy.
 
-Prints ONE JSON line on rank 0 (see the contract in the task description), with `roofline` for the dominant kernel (HIP
-events on the library's own streams, one call in flight) and `cpu_baseline` (the reference's SSE graph compiled from its
-sources, on all usable host cores; the scalar restatement where that library is absent).
+Prints ONE JSON line on rank 0, with `ms_per_step` (one timed step), `roofline` for the dominant kernel (HIP events on the
+library's own streams, one call in flight) and `cpu_baseline` (the reference's SSE graph compiled from its sources, on all
+usable host cores; the scalar restatement where that library is absent).  The side sections (plain host, latency, stages,
+ingest, tx, 11b, 11n, HT40, shard shape) are measured only with --sections-out FILE, which receives the whole object: the line
+itself stays a few KB.
 """
 import argparse
 import json
@@ -66,6 +69,33 @@ from benchlib.cpu import _cpu_worker, _cpu_worker_11b, _cpu_worker_11n, cpu_base
 from benchlib.stages import bench_ingest, bench_stages, bench_tx  # noqa: E402,F401
 from benchlib.latency import bench_e2e, bench_large_call, bench_latency  # noqa: E402,F401
 from benchlib.rows import bench_11b, bench_11n, bench_ht40, bench_shard_shape  # noqa: E402,F401
+
+
+DUMP_LIMIT = 60 * 10 ** 6  # array bytes written by --dump-outputs at most (the .npy headers included, under 64 MB)
+SETTLE_STEPS = 100         # untimed steps at least between the warm-up and the timed region
+SIDE_SECTIONS = ("plain_host", "latency", "e2e", "stages", "ingest", "tx", "rx11b", "rx11b_cck", "rx11n", "rx11n_40", "shard_32x16")   # --sections-out only
+
+
+def dump_outputs(out_dir, sora_amd, rows, mpdu, prefix=""):
+    """--dump-outputs: what a caller of the timed path receives from one step, as <out_dir>/<prefix><name>.npy -- the delivered result
+    rows, one float64 file per field (row_<field>.npy, row_index.npy = the rows' places in the table), and mpdu.npy, the MPDU bytes
+    of every row that carries some (frame OK or FCS failure) in row order, as float32.  A table beyond DUMP_LIMIT is cut to a fixed
+    seeded sample of rows.  Row order and MPDU offsets are the library's own, deterministic for a given input."""
+    os.makedirs(out_dir, exist_ok=True)
+    has = np.isin(rows["error_code"], (sora_amd.E_FRAME_OK, sora_amd.E_CRC32_FAIL))
+    ln = np.where(has, np.minimum(rows["length"], 4096), 0).astype(np.int64)
+    per_row = 8 * (len(rows.dtype.names) + 1) + 4 * ln
+    idx = np.arange(len(rows))
+    if per_row.sum() > DUMP_LIMIT:
+        perm = np.random.default_rng(0).permutation(len(rows))
+        idx = np.sort(perm[:np.searchsorted(np.cumsum(per_row[perm]), DUMP_LIMIT, side="right")])
+    np.save(os.path.join(out_dir, prefix + "row_index.npy"), idx.astype(np.float64))
+    for f in rows.dtype.names:
+        np.save(os.path.join(out_dir, prefix + "row_%s.npy" % f), rows[f][idx].astype(np.float64))
+    off = rows["mpdu_offset"].astype(np.int64)
+    assert all(off[i] + ln[i] <= len(mpdu) for i in idx if ln[i]), "a row's MPDU lies beyond the delivered MPDU array"
+    parts = [mpdu[off[i]:off[i] + ln[i]] for i in idx if ln[i]]
+    np.save(os.path.join(out_dir, prefix + "mpdu.npy"), (np.concatenate(parts) if parts else np.zeros(0, np.uint8)).astype(np.float32))
 
 
 def _free_port():
@@ -135,7 +165,11 @@ def main():
     ap.add_argument("--depth", type=int, default=0, help="process calls in flight on the handle's internal pipelines (0 = library default)")
     ap.add_argument("--trellis", type=int, default=-1, help="trellis kernel: 64 = k_viterbi, 16 = k_viterbi16, 0 = the library's choice from the depth (default: leave the handle as created)")
     ap.add_argument("--check", type=int, default=0, help="captures compared with the reference after the timed region (0 = all)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="the timed region repeats the K-step block until it has lasted this long")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="0 (default): the timed region is exactly --steps steps; > 0: the K-step block is repeated "
+                    "until it has lasted this long")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one delivered (result rows, MPDU bytes) as DIR/<name>.npy")
+    ap.add_argument("--sections-out", metavar="FILE", help="also measure the side sections (plain host, latency, stages, ingest, tx, 11b, 11n, HT40, shard shape) "
+                    "and write the whole result object, them included, to FILE as JSON")
     ap.add_argument("--no-deliver", action="store_true", help="do not deliver rows + MPDUs to the host inside the timed region (round-1 behaviour)")
     ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES for this process (read before HIP starts); 0 = leave the runtime default")
     ap.add_argument("--shape", default="batch", choices=["batch", "shard"], help="batch: --frames captures of one frame per GPU (BASELINE configs[2], the headline); "
@@ -249,6 +283,7 @@ def main():
     inflight = {}                                                   # ticket -> index of the buffer it is delivered into
     free = collections.deque(range(nb))
     order = {"any": not args.wait_oldest}
+    last = {}                                                       # the latest step's ticket and buffer (--dump-outputs)
 
     def consume_one():
         ta = time.perf_counter()
@@ -275,8 +310,9 @@ def main():
                 if bound:
                     rx.bind_mpdu(bufs[bi])                          # sora_rx_bind_mpdu: the call's frame sink writes its MPDUs into this buffer itself; deliver_async copies rows only
             tk = rx.process_dev(d_iqs[(rx.ticket() + 1) % NCOPIES], descs)
+            last["tk"] = tk
             if deliver:
-                rx.deliver_async(tk, bufs[bi]); inflight[tk] = bi
+                rx.deliver_async(tk, bufs[bi]); inflight[tk] = bi; last["bi"] = bi
             stats["t_submit"] += time.perf_counter() - ta
             if deliver and len(inflight) >= dep:
                 consume_one()
@@ -287,13 +323,17 @@ def main():
     run_block(args.warmup, deliver)
     rx.flush()
     barrier()
-    run_block(args.steps, deliver); rx.flush()                       # (the first block after the warm-up still pays first-use costs: size the region from the second)
-    t0 = time.perf_counter()
-    run_block(args.steps, deliver); rx.flush()
-    probe = time.perf_counter() - t0
-    repeats = max(1, int(np.ceil(args.min_seconds / max(probe, 1e-6))))
-    if world > 1:                                  # every rank runs the same number of blocks
-        r_t = torch.tensor([repeats], device=dev, dtype=torch.int64); dist.all_reduce(r_t, op=dist.ReduceOp.MAX); repeats = int(r_t.item())
+    # the first block after the warm-up still pays first-use costs -- the first few dozen deliveries of a process take 7 ms stalls inside deliver_async now
+    # and then (measured: three of them between calls 31 and 45, none later) -- so it lasts at least SETTLE_STEPS and is not timed
+    run_block(max(args.steps, SETTLE_STEPS), deliver); rx.flush()
+    repeats = 1
+    if args.min_seconds > 0:                                        # size the region from one more block
+        t0 = time.perf_counter()
+        run_block(args.steps, deliver); rx.flush()
+        probe = time.perf_counter() - t0
+        repeats = max(1, int(np.ceil(args.min_seconds / max(probe, 1e-6))))
+        if world > 1:                              # every rank runs the same number of blocks
+            r_t = torch.tensor([repeats], device=dev, dtype=torch.int64); dist.all_reduce(r_t, op=dist.ReduceOp.MAX); repeats = int(r_t.item())
     chk.drain(); chk.compared = chk.bad = 0; chk.mpdu_compared = 0
     barrier()
     for k_ in ("t_submit", "t_wait", "t_check"):
@@ -305,12 +345,20 @@ def main():
     barrier()
     t1 = time.perf_counter()
     host_ms = {k_[2:]: round(1e3 * stats[k_] / (args.steps * repeats), 4) for k_ in ("t_submit", "t_wait", "t_check")}
+    if args.dump_outputs:
+        if deliver:
+            b = bufs[last["bi"]]                                    # the last timed step's delivered table (already compared: chk.drain above)
+        else:                                                       # nothing was delivered in the timed region: fetch the last call's table now
+            b = bufs[0]; rx.deliver_async(last["tk"], b); rx.wait(last["tk"])
+        dump_outputs(args.dump_outputs, sora_amd, b.rows[:int(b.nrows[0])], b.mpdu, "rank%d_" % rank if world > 1 else "")
     if args.headline_only:
         if rank == 0:
             print(json.dumps({"ms_per_step": round(1e3 * (t1 - t0) / (args.steps * repeats), 4), "steps": args.steps * repeats, "calls_in_flight": depth, "captures_per_call": nfr,
                               "calls_with_wrong_rows": chk.bad, "host_ms_per_step": host_ms}))
         return
     timed_steps = args.steps * repeats
+    sections = bool(args.sections_out)
+    side_reps = max(1, int(np.ceil(1.0 / max((t1 - t0) / repeats, 1e-6))))  # the side sections' blocks: K-step blocks for about a second, as the headline once was
     stats["delivered"], stats["bad"] = chk.compared, chk.bad
     stats["mpdu_compared_timed"] = getattr(chk, "mpdu_compared", 0)
     mpdu_ok = bool(deliver) and all((b.mpdu == exp_mpdu).all() for b in bufs)     # the last calls' MPDU arrays once more, byte for byte
@@ -349,11 +397,11 @@ def main():
     # handle's streams in use -- fewer than the runtime's default four hardware queues, so GPU_MAX_HW_QUEUES plays no part -- same timed-region
     # protocol (delivery + comparison inside), each trellis kernel pinned in turn.
     plain = {}
-    if world == 1 and not args.no_plain and not shard:
+    if sections and world == 1 and not args.no_plain and not shard:
         if order["any"] and deliver:                                 # the headline's calls in flight with the round-3 loop: always wait for the OLDEST ticket
             rx.set_trellis(lanes); rx.set_depth(depth); rx.flush(); order["any"] = False
             run_block(args.warmup, deliver); rx.flush(); chk.drain(); bad0 = chk.bad
-            nblk = max(1, repeats // 4)
+            nblk = max(1, side_reps // 4)
             tp0 = time.perf_counter()
             run_block(args.steps * nblk, deliver)
             rx.flush(); chk.drain()
@@ -365,7 +413,7 @@ def main():
             for l in (64, 16, 1):
                 rx.set_trellis(l); rx.set_depth(dval); rx.flush()
                 run_block(args.warmup, deliver, dval); rx.flush(); chk.drain(); bad0 = chk.bad
-                nblk = max(1, repeats // 6)
+                nblk = max(1, side_reps // 6)
                 tp0 = time.perf_counter()
                 run_block(args.steps * nblk, deliver, dval)
                 rx.flush(); chk.drain()
@@ -376,7 +424,7 @@ def main():
         for dval in (1, 2):
             rx.set_trellis(1); rx.set_depth(dval); rx.flush()
             run_block(args.warmup, deliver, dval, bound=True); rx.flush(); chk.drain(); bad0 = chk.bad
-            nblk = max(1, repeats // 6)
+            nblk = max(1, side_reps // 6)
             tp0 = time.perf_counter()
             run_block(args.steps * nblk, deliver, dval, bound=True)
             rx.flush(); chk.drain()
@@ -388,7 +436,7 @@ def main():
         best2 = min((k for k in plain if k.startswith("calls_in_flight_2")), key=lambda k: plain[k]["ms_per_step"])
         plain["best_with_at_most_two_calls_in_flight"] = dict(plain[best2], config=best2)
         try:
-            plain["two_calls_in_flight_of_%d_captures" % (8 * nfr)] = bench_large_call(torch, sora_amd, local_rank, d_iqs, nfr, MAXF, exp_rows, exp_mpdu, args.min_seconds,
+            plain["two_calls_in_flight_of_%d_captures" % (8 * nfr)] = bench_large_call(torch, sora_amd, local_rank, d_iqs, nfr, MAXF, exp_rows, exp_mpdu, 1.0,
                                                                                            share[1:] if len(share) > 1 else None)
         except Exception as e:                                      # (a second 320 MB input and its workspace: report, do not lose the line)
             plain["two_calls_in_flight_of_%d_captures" % (8 * nfr)] = {"error": repr(e)}
@@ -396,7 +444,7 @@ def main():
                          "issue rate) or 4096 of k_viterbi (1.7x the instructions): DESIGN.md section 3.6, profiles/r04_a_depth_table.txt" % (depth, " on %s hardware queues" % os.environ["GPU_MAX_HW_QUEUES"] if os.environ.get("GPU_MAX_HW_QUEUES") else ""))
     rx.set_trellis(trellis_setting); rx.set_depth(depth); rx.flush()
     latency = e2e = None
-    if world == 1 and not args.no_extras and not shard:
+    if sections and world == 1 and not args.no_extras and not shard:
         latency = bench_latency(torch, sora_amd, dev, rx, d_iq, descs, nfr)
         e2e = bench_e2e(torch, sora_amd, dev, rx, iq, nfr, exp_rows, exp_mpdu)
 
@@ -472,7 +520,7 @@ def main():
             out["latency"] = latency
         if e2e is not None:
             out["e2e"] = e2e
-        if world == 1 and not args.no_extras and not shard:
+        if sections and world == 1 and not args.no_extras and not shard:
             out["stages"] = bench_stages(torch, sora_amd, dev)
             out["ingest"] = bench_ingest(torch, sora_amd, dev)
             out["tx"] = bench_tx(torch, sora_amd)
@@ -484,6 +532,11 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(iq, nfr * fpc)
             out["realtime"]["cpu_reference_factor_one_core"] = round(20.0 / out["cpu_baseline"]["single_core_value"], 4) if out["cpu_baseline"].get("single_core_value") else None
+        if sections:                                                # the whole object to the file, the line without the side sections
+            with open(args.sections_out, "w") as fh:
+                json.dump(out, fh)
+            out = {k_: v for k_, v in out.items() if k_ not in SIDE_SECTIONS}
+            out["sections_out"] = args.sections_out
         print(json.dumps(out))
     if world > 1:
         dist.barrier()
