@@ -31,7 +31,7 @@ extern "C" {
 
 /* 3 (round 5).  Against 2: (i) behaviour that round 4 changed under the old number: a call that has been delivered (sora_rx_deliver_async) AND waited for
  * (sora_rx_wait / _wait_any; the same for the rx11b / rx11n / ht40 handles) is RELEASED -- its pipeline is the first to be reused, so its ticket is valid for `depth`
- * further calls only if the host has not both delivered and waited for it; sora_rx_set_fused(1) answers SORA_E_NOT_SUPPORTED in the default build;
+ * further calls only if the host has not both delivered and waited for it; sora_rx_set_fused(1) answers SORA_E_NOT_SUPPORTED (k_decode has since been removed);
  * sora_rx11b_set_single_pass defaults to 2 (automatic); sora_ht40_deliver_async needs max_rows >= 2 x captures x max_frames.  (ii) new this round, all additive:
  * SORA_TRELLIS_WINDOWED and sora_rx_window_stats, sora_rx_set_front / sora_rx_front, sora_hip_table_*, sora_hip_freq_comp11a / _equalize11a / _phase_comp11a,
  * and the automatic choices of sora_rx_set_trellis / sora_rx_set_front (results are identical whichever kernels run).  INTEGRATION.md section 1 lists them. */
@@ -267,10 +267,10 @@ int  sora_rx_set_graph(sora_rx_t* rx, int enable);
 /* The data field (T11aDataSymbol .. T11aViterbi) is decoded by k_frame (symbol chain, soft values to HBM packed three bits each)
  * followed by k_viterbi16 / k_viterbi (sora_rx_set_trellis).  Rounds 2-3 also shipped k_decode -- both in one kernel, symbol waves
  * feeding trellis waves through a ring in LDS the way the reference's RxThread feeds its ViterbiThread through TThreadSeparator
- * (stdbrick.hpp:89-248) -- which lost to the split form at every depth (0.80 against 0.46 ms per step, BENCH_r03) and is a BUILD
- * VARIANT since round 4 (sora_amd.build.build_variant("fused", ["SORA_WITH_K_DECODE"])): in the default library
- * sora_rx_set_fused(rx, 1) returns SORA_E_NOT_SUPPORTED and changes nothing; enable = 0 and the query (enable < 0) still work and
- * return the previous value.  sora_rx_kernel_name_fused(i) names the kernels of the fused chain ("" = slot not used). */
+ * (stdbrick.hpp:89-248) -- which lost to the split form at every depth (0.80 against 0.46 ms per step, BENCH_r03), left the library
+ * in round 4 and has since been REMOVED.  The two entry points stay in the ABI: sora_rx_set_fused(rx, 1) returns SORA_E_NOT_SUPPORTED
+ * and changes nothing; enable = 0 and the query (enable < 0) return 0.  sora_rx_kernel_name_fused(i) still names the kernels of the
+ * removed chain ("" = slot not used). */
 int  sora_rx_set_fused(sora_rx_t* rx, int enable);
 const char* sora_rx_kernel_name_fused(size_t index);
 
@@ -565,8 +565,7 @@ int  sora_shard_gather_results_mpdu(sora_shard_t* sh, sora_rx_t* rx, int ticket,
  * FCS bytes and one stale buffer byte, PHY_11b.hpp:725-731); start_sample, nsym and cfo_est are 0.  Long preamble; 1 Mbps
  * DBPSK, 2 Mbps DQPSK, 5.5 and 11 Mbps CCK payloads (all four rates of the reference graph).
  * Two kernels per call: the first has no CCK decoders in it (more resident waves) and hands a capture over when a header announces
- * 5.5 / 11 Mbps; the second redoes the handed-over captures.  (A build variant, SORA_VARIANT_11B_ONE_KERNEL, sends every capture through the
- * second one only: 1 / 2 Mbps traffic 3-6 % slower, CCK traffic 28 % faster, same rows either way.)
+ * 5.5 / 11 Mbps; the second redoes the handed-over captures.
  * ------------------------------------------------------------------------------------------------ */
 #define SORA_E_NOT_SUPPORTED     ((int)0x80000003)
 #define SORA_E_SFD_FAIL          ((int)0x80000004)

@@ -14,9 +14,6 @@ OBJ = os.path.join(HERE, "lib", "obj")
 LIB = os.path.join(HERE, "lib", "libsora_hip.so")
 SOURCES = ["k_scan.hip", "k_rx.hip", "k_vit16.hip", "k_vitwin.hip", "k_stage.hip", "k_tx.hip", "k_rx11b.hip", "k_11n.hip", "k_rx11n.hip", "k_ht40.hip", "k_deliver.hip",
     "sora_hip.cpp", "sora_shard.cpp"]
-# k_decode.hip (the data field in one kernel, sora_rx_set_fused) left the default library in round 4: build_variant("fused", ["SORA_WITH_K_DECODE"])
-# compiles it in (the entry point answers SORA_E_NOT_SUPPORTED otherwise).
-VARIANT_SOURCES = {"SORA_WITH_K_DECODE": ["k_decode.hip"]}
 HEADERS = ["dev_arith.h", "dev_viterbi.h", "dev_vit16.h", "dev_winplan.h", "dev_vitwin.h", "dev_11n.h", "rx_types.h", "kernels.h", os.path.join("..", "..", "include", "sora_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-x", "hip"]   # hidden: the library exports what include/sora_hip.h declares, nothing else
 
@@ -100,10 +97,9 @@ def build_variant(name, defines):
     run any entry point with SORA_HIP_LIB=<that file>)."""
     out_dir = os.path.join(HERE, "lib", "variants"); os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, name + ".so")
-    if any(d.startswith(("SORA_EXP_", "SORA_DBG_", "SORA_SCAN_PROBE")) for d in defines) and "SORA_TOOLS" not in defines:
-        defines = list(defines) + ["SORA_TOOLS"]                                  # every experiment / probe switch lives in the tools variant only (kernels.h refuses otherwise)
-    extra = [f for d in defines for f in VARIANT_SOURCES.get(d.split("=")[0], [])]
-    cmd = [hipcc()] + FLAGS + ["-shared", "-w"] + ["-D" + d for d in defines] + [os.path.join(CSRC, f) for f in SOURCES + extra] + ["-ldl", "-o", out]
+    if any(d.startswith(("SORA_DBG_", "SORA_SCAN_PROBE")) for d in defines) and "SORA_TOOLS" not in defines:
+        defines = list(defines) + ["SORA_TOOLS"]                                  # every probe switch lives in the tools variant only (kernels.h refuses otherwise)
+    cmd = [hipcc()] + FLAGS + ["-shared", "-w"] + ["-D" + d for d in defines] + [os.path.join(CSRC, f) for f in SOURCES] + ["-ldl", "-o", out]
     subprocess.check_call(cmd)
     return out
 

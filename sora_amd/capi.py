@@ -310,7 +310,6 @@ class Rx:
         self.wait_for_producer = True      # process_dev first waits for torch's current stream (bench.py turns it off: its inputs are resident)
         # harness-side overrides (the library itself reads no environment variable): A/B runs of the tools and tests
         if os.environ.get("SORA_HIP_DEPTH"): self.set_depth(int(os.environ["SORA_HIP_DEPTH"]))
-        if os.environ.get("SORA_HIP_FUSED"): self.set_fused(int(os.environ["SORA_HIP_FUSED"]))
         if os.environ.get("SORA_HIP_GRAPH"): self.set_graph(int(os.environ["SORA_HIP_GRAPH"]))
         if os.environ.get("SORA_HIP_TRELLIS"): self.set_trellis(int(os.environ["SORA_HIP_TRELLIS"]))
         if os.environ.get("SORA_HIP_FRONT"): self.set_front(int(os.environ["SORA_HIP_FRONT"]))
@@ -499,8 +498,7 @@ class Rx:
         return int(self._L.sora_rx_set_graph(self._h, int(enable)))
 
     def set_fused(self, enable=-1):
-        """1: decode the data field with the fused kernel (k_decode -- a build variant since round 4: SoraError SORA_E_NOT_SUPPORTED in the
-        default library), 0: k_frame + k_viterbi; returns the previous setting"""
+        """The fused data-field kernel (k_decode) has been removed: 1 raises SoraError SORA_E_NOT_SUPPORTED, 0 and the query (-1) return 0"""
         r = int(self._L.sora_rx_set_fused(self._h, int(enable)))
         if r not in (0, 1):
             raise SoraError(r, (self._L.sora_hip_last_error() or b"").decode())
@@ -510,7 +508,7 @@ class Rx:
         """{kernel name: ms} of the profiled process calls (HIP events on the handle's streams)."""
         ms = (ctypes.c_float * 8)(); n = ctypes.c_size_t(0)
         _check(self._L.sora_rx_kernel_times(self._h, ms, 8, ctypes.byref(n)))
-        name = self._L.sora_rx_kernel_name_fused if self.set_fused(-1) else self._L.sora_rx_kernel_name
+        name = self._L.sora_rx_kernel_name
         return {name(i).decode(): ms[i] for i in range(n.value) if name(i)}
 
     def flush(self):

@@ -71,13 +71,6 @@ __device__ __forceinline__ UnitRef unit_ref(const VitJob& J, uint32_t n, uint32_
     return UnitRef{ idx, uu, m, nun };
 }
 template <int CR, int WIN, int LOOK, typename JOBS>
-__device__ __forceinline__ UnitRef unit_ref_at(JOBS job_at, uint32_t n, uint32_t p, uint32_t q)
-{
-    const bool inside = p < win_slots(n, q);
-    const uint32_t upos = inside ? p / n : 0u, idx = inside ? p - upos * n : 0u;
-    return unit_ref<CR, WIN, LOOK>(job_at(idx), n, p, q, inside, upos, idx);
-}
-template <int CR, int WIN, int LOOK, typename JOBS>
 __device__ __forceinline__ UnitGeom unit_geom(JOBS job_at, uint32_t n, uint32_t p, uint32_t q, uint32_t vbase, uint8_t* __restrict__ out)
 {
     const bool inside = p < win_slots(n, q);
@@ -276,13 +269,10 @@ __device__ __forceinline__ void forward16w(Lds16<WIN, LOOK>& S, const uint8_t* _
 
 // (S: the wave's own LDS block.  wave_index: which eighth-of-units of the call.  jobs_of(list): that list's job_at.  ready(A, B, list): called once the wave's units are
 // known, before the first soft value is read -- k_pipe waits there for the symbol chain; false = give up.)
-// done(cr, list, nl, w, q, job_at): what the wave does once its eight units (positions 8 w .. 8 w + 7 of the list) have written their bytes and vectors -- nothing, or
-// k_viterbi16w_fin's tail (k_rx.hip): the LAST unit of a frame to arrive proves and finishes the frame
-struct NothingDone { template <typename CRT, typename JOBS> __device__ __forceinline__ void operator()(CRT, uint32_t, uint32_t, uint32_t, uint32_t, JOBS) const {} };
-template <int WIN, int LOOK, int BITS, typename JOBSOF, typename READY, typename DONE = NothingDone>
+template <int WIN, int LOOK, int BITS, typename JOBSOF, typename READY>
 __device__ __forceinline__ void viterbi16w_wave(Lds16<WIN, LOOK>& S, uint32_t wave_index, JOBSOF jobs_of, READY ready, const uint32_t* __restrict__ hdr,
         uint32_t target, uint32_t vstride,
-                                                const uint8_t* __restrict__ soft, uint8_t* __restrict__ out, uint16_t* __restrict__ vecs, DONE done = DONE())
+                                                const uint8_t* __restrict__ soft, uint8_t* __restrict__ out, uint16_t* __restrict__ vecs)
 {
     auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     const uint32_t n[3] = { hdr[0], hdr[1], hdr[2] };
@@ -303,7 +293,6 @@ __device__ __forceinline__ void viterbi16w_wave(Lds16<WIN, LOOK>& S, uint32_t wa
         if (!B.valid) { const bool v = false; B = A; B.valid = v; B.vstep = B.estep = kNever; B.nsteps = 0; }
         if (!A.valid) { const bool v = false; const UnitGeom T = B; A = T; A.valid = v; A.vstep = A.estep = kNever; A.nsteps = 0; }
         forward16w<CR, WIN, LOOK, BITS>(S, soft, A, B, vecs, [&]() { return ready(A, B, list); });
-        done(cr, list, nl, w, q, job_at);
     };
     if (code_rate == 0) run(std::integral_constant<int, 0>{});
     else if (code_rate == 1) run(std::integral_constant<int, 1>{});

@@ -238,11 +238,7 @@ __global__ void __launch_bounds__(256) k_frame(RxArgs A)
     __syncthreads();                                                             // the only block barrier: the waves are independent from here on
     if (!locate_job(blockIdx.x * 4, A.njobs).ok) return;                         // (the whole workgroup)
     const JobRef jr = locate_job(blockIdx.x * 4 + (threadIdx.x >> 6), A.njobs);
-#ifdef SORA_DBG_KFRAME_PRIVATE                                                   // (tools variant: every wave tracks its own frame, as before round 6)
-    if (jr.ok) frame_symbols<false>(A, jr.list * A.nrows + jr.idx, lds);
-#else
     frame_symbols<true>(A, jr.ok ? jr.list * A.nrows + jr.idx : 0u, lds, jr.ok);   // slot of the job in jobs[] / joblist[]; a wave without one still meets the others at the barriers
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -255,7 +251,7 @@ __global__ void __launch_bounds__(256) k_frame(RxArgs A)
 // instructions per symbol) on a whole wave for the four lanes that hold a symbol's pilots: 36 % of its vector
 // instructions, and a frame's symbols one pass after the other (fsample-6's 465 symbols: 117 passes, 0.30 ms for one wave).
 //   k_sym_front  per SYMBOL SLOT (rx_types.h): samples -> equalised bins eq[slot][64] in HBM      (16 lanes per symbol)
-//   k_track      per FRAME, four lanes (= the four pilots) each, sixteen frames per wave: the chain over the frame's
+//   k_track_lds  per FRAME, four lanes (= the four pilots) each, sixteen frames per wave: the chain over the frame's
 //                symbols in order, reading 16 bytes per symbol, writing the rotation parameters track[slot] (TrackRec)
 //   k_sym_back   per SYMBOL SLOT: eq[slot] x CompCoeffs x rotation -> demap -> de-interleave -> packed soft stream
 // The symbol kernels find a slot's frame through slot_row[] (written by k_scan for the data symbols of every frame it
@@ -326,7 +322,7 @@ __device__ __forceinline__ void sym_front_block(const RxArgs& A, uint32_t bid, u
     auto store = [&](uint32_t slot, const uint32_t o[4]) {
         if (THROUGH) store16_through(eq4 + ((size_t)slot * 16u + (uint32_t)e), uint4{ o[0], o[1], o[2], o[3] });
         else eq4[(size_t)slot * 16u + (uint32_t)e] = uint4{ o[0], o[1], o[2], o[3] };
-        // the four pilot bins once more, densely (16 bytes per slot: k_track reads nothing else): bins 43, 57, 7, 21 = (e, q) (10,3), (14,1), (1,3), (5,1)
+        // the four pilot bins once more, densely (16 bytes per slot: k_track_lds reads nothing else): bins 43, 57, 7, 21 = (e, q) (10,3), (14,1), (1,3), (5,1)
         auto pilot = [&](uint32_t k, uint32_t v) { if (THROUGH) store4_through(A.pil + ((size_t)slot * 4u + k), v); else A.pil[(size_t)slot * 4u + k] = v; };
         if (e == 10) pilot(0u, o[3]);
         if (e == 14) pilot(1u, o[1]);
@@ -389,73 +385,6 @@ __global__ void __launch_bounds__(256) k_sym_front(RxArgs A)
     sym_front_block<false>(A, blockIdx.x, s_eq);
 }
 
-// The loop-carried part (freqoffset.hpp:28-30, pilot.hpp:166-233): pilot k of a frame in lane 4 f + k, sixteen frames per wave, every
-// frame stepping through its own symbols; the four angles of a frame meet through quad broadcasts.
-__global__ void __launch_bounds__(256) k_track(RxArgs A)
-{
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, pk = lane & 3;
-    const Tables& T = A.T;
-    const JobRef jr = locate_job((blockIdx.x * 4u + (uint32_t)w) * 16u + (uint32_t)(lane >> 2), A.njobs);
-    const uint32_t j = jr.ok ? jr.list * A.nrows + jr.idx : 0u;
-    const uint32_t f = jr.ok ? A.joblist[j] : 0u;
-    FrameRow r = A.frames[f];
-    const int nsym = jr.ok ? (int)r.nsym : 0;
-    if (jr.ok && pk == 0) {
-        VitJob J;
-        J.valid = 1; J.soft_off = r.slot0 * (uint32_t)kSoftBytesPerSlot; J.nsoft = (uint32_t)r.nsym * 48u * r.nbpsc; J.length = r.length;
-        J.dec_off = 0; J.out_off = r.slot0 * (uint32_t)kOutPerSlot; J.code_rate = r.code_rate; J.soft_bits = 3;
-        A.jobs[j] = J;
-    }
-    // pilot k in lane k: bins 43, 57, 7, 21 = carriers -21, -7, +7, +21 (pilot.hpp:138-164)
-    const int pc = pk == 0 ? -21 : pk == 1 ? -7 : pk == 2 ? 7 : 21;
-    int cfo_comp = r.cfo_comp, sfo_comp = r.sfo_comp, cfo_tr = r.cfo_tracker, sfo_tr = r.sfo_tracker;
-    unsigned symbol_count = 0;                                                   // 127 -> 0 after the SIGNAL symbol
-    int nmax = nsym;
-#pragma unroll
-    for (int o = 32; o >= 4; o >>= 1) nmax = max(nmax, __shfl_xor(nmax, o));
-    nmax = __builtin_amdgcn_readfirstlane(nmax);
-    // pilot k of data symbol s at pp[4 (s - 1)]: 16 bytes per symbol and frame (k_sym_front)
-    const uint32_t* pp = A.pil + (size_t)(r.slot0 + 1u) * 4u + (uint32_t)pk;
-    TrackRec* trk = A.track + r.slot0 + 1u;
-    // symbols requested ahead of the one in the chain (each step is two dependent table reads long)
-    constexpr int kAhead = 4;
-    uint32_t q[kAhead];
-#pragma unroll
-    for (int i = 0; i < kAhead; i++) q[i] = i < nsym ? pp[4 * i] : 0u;
-    for (int s = 1; s <= nmax; s++) {
-        const uint32_t cur = q[0];
-#pragma unroll
-        for (int i = 0; i + 1 < kAhead; i++) q[i] = q[i + 1];
-        q[kAhead - 1] = s + kAhead <= nsym ? pp[4 * (s + kAhead - 1)] : 0u;
-        if (s <= nsym) {                                                         // (uniform inside a quad: the cross-lane reads below see their whole quad)
-            const cpx p = mul_q15(unpack(cur), rot_coeff(T, w16(cfo_comp + pc * sfo_comp)));
-            int th = pk == 3 ? uatan2(T, -p.im, -p.re) : uatan2(T, p.im, p.re);
-            if (pilot_sgn(symbol_count)) th = w16(th + 0x8000);
-            symbol_count++; if (symbol_count >= 127) symbol_count = 0;
-            // The four angles of the quad, in every lane.  Written as assembler on purpose: with __builtin_amdgcn_update_dpp the compiler folds two of
-            // the broadcasts into the arithmetic that follows (v_add_u32_dpp / v_subrev_u32_dpp writing the register it reads through the DPP
-            // selector) and `del` comes out a few LSB off -- reproduced in round 4 (tools/dbg_arrays.py), the same fault round 3 noted in k_frame.
-            // (s_nop 1: a VALU write of th followed by a DPP read needs two wait states, and the hazard pass does not look into assembler.)
-            int th1, th2, th3, th4;
-            asm volatile("s_nop 1\n\t"
-                         "v_mov_b32_dpp %0, %4 quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                         "v_mov_b32_dpp %1, %4 quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                         "v_mov_b32_dpp %2, %4 quad_perm:[2,2,2,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                         "v_mov_b32_dpp %3, %4 quad_perm:[3,3,3,3] row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                         : "=&v"(th1), "=&v"(th2), "=&v"(th3), "=&v"(th4) : "v"(th));
-            const int avg = w16((th1 + th2 + th3 + th4) / 4);
-            const int del = w16(((th3 - th1) / 28 + (th4 - th2) / 28) >> 1);
-#ifdef SORA_DBG_TRACK_TH
-            if (pk == 0) { TrackRec t; t.cfo_comp = (int16_t)th1; t.sfo_comp = (int16_t)th2; t.avg = (int16_t)th3; t.del = (int16_t)th4; trk[s - 1] = t; }
-#else
-            if (pk == 0) { TrackRec t; t.cfo_comp = (int16_t)cfo_comp; t.sfo_comp = (int16_t)sfo_comp; t.avg = (int16_t)avg; t.del = (int16_t)del; trk[s - 1] = t; }
-#endif
-            cfo_tr = w16(cfo_tr + (avg >> 2)); sfo_tr = w16(sfo_tr + (del >> 2));
-            cfo_comp = w16(cfo_comp + avg + cfo_tr); sfo_comp = w16(sfo_comp + del + sfo_tr);
-        }
-    }
-}
-
 // One symbol of the chain out of the folded tables in LDS (freqoffset.hpp:28-30, pilot.hpp:166-233): pilot k of the frame in lane k of a quad, `cur` its equalised bin, `flip`
 // 0x8000 for a symbol of pilot polarity -1.  Advances the state and returns the symbol's TrackRec { cfo_comp, sfo_comp, avg, del } as two words.
 __device__ __forceinline__ uint2 track_step(const TrkTables& s_t, uint32_t cur, int flip, int pc, int m3, int& cfo, int& sfo, int& ctr, int& str)
@@ -477,7 +406,11 @@ __device__ __forceinline__ uint2 track_step(const TrkTables& s_t, uint32_t cur, 
     const int sh = max(25 - __builtin_clz((unsigned)(max(x, -x) | max(y, -y)) | 1u), 0);
     int th = trk_uatan2_entry(s_t, y >> sh, x >> sh);
     th = __builtin_amdgcn_sbfe(th ^ flip, 0, 16);                                // + 0x8000 mod 2^16 for a pilot of polarity -1
-    int th1, th2, th3, th4;                                                      // the four angles of the quad, in every lane (assembler: see k_track)
+    // The four angles of the quad, in every lane.  Written as assembler on purpose: with __builtin_amdgcn_update_dpp the compiler folds two of
+    // the broadcasts into the arithmetic that follows (v_add_u32_dpp / v_subrev_u32_dpp writing the register it reads through the DPP
+    // selector) and `del` comes out a few LSB off -- reproduced in round 4 (tools/dbg_arrays.py), the same fault round 3 noted in k_frame.
+    // (s_nop 1: a VALU write of th followed by a DPP read needs two wait states, and the hazard pass does not look into assembler.)
+    int th1, th2, th3, th4;
     asm volatile("s_nop 1\n\t"
                  "v_mov_b32_dpp %0, %4 quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
                  "v_mov_b32_dpp %1, %4 quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
@@ -517,8 +450,8 @@ __device__ __forceinline__ void track_tables_to_lds(const uint32_t* __restrict__
     }
 }
 
-// Round 5: the same chain with its three tables in LDS -- the tracker for FEW frames in flight (a single capture: fsample-6's 465 symbols).
-// k_track's step is two dependent L2 gathers long (rot[] is 256 KB, uatan2[] 128 KB: 0.7 us per symbol); here a workgroup first copies the folded tables
+// Round 5: the tracker's chain with its three tables in LDS -- the tracker for FEW frames in flight (a single capture: fsample-6's 465 symbols).
+// Out of L2 its step is two dependent gathers long (rot[] is 256 KB, uatan2[] 128 KB: 0.7 us per symbol); here a workgroup first copies the folded tables
 // (dev_arith.h TrkTables, 129 KB: quarter-wave sine + two-bit corrections, uatan2 for y >= 0) into its LDS, and the step is three LDS reads deep.  One wave is
 // alone on its SIMD, so the step costs what its instructions cost to ISSUE (~5 cycles each): the loop is written for few instructions, not for few dependent ones --
 // no exec-mask juggling (frames shorter than the wave's longest keep stepping on clamped reads and write nothing), the pilot polarity a scalar, the state wrapped
@@ -1013,12 +946,8 @@ __device__ __forceinline__ void viterbi_forward(const VitJob& JA, const VitJob& 
 
     // Normalize (viterbicore.h:444-465), both frames; marks and guard are clear here and no half borrows (its minimum is subtracted): one 32-bit VOP2
     auto normalize = [&]() { V.U = V.U - dpp_pkmin_wave(V.U); };
-#ifdef SORA_DBG_NO_TRACE                                                        // experiment (tools/ab_decode.sh): the forward pass alone -- results are wrong, only the duration means something
-    auto trace = [&](unsigned, unsigned, uint32_t, uint32_t, uint32_t) {};
-#else
     auto trace = [&](unsigned mA, unsigned mB, uint32_t cntA, uint32_t cntB, uint32_t top) { viterbi_trace<RG::kMaxWalk>(V.U, ring, tr, ob, mA, mB, cntA, cntB,
             A.out, B.out, top); };
-#endif
     auto next_event = [&]() -> uint32_t {
         uint32_t t = ob + (uint32_t)(WIN + LOOK + 6);
         if (!A.done) t = min(t, A.tr_end);
@@ -1174,12 +1103,8 @@ __device__ __forceinline__ void viterbi_forward_unit(const UnitGeom& GA, const U
 
     // Normalize (viterbicore.h:444-465), both frames; marks and guard are clear here and no half borrows (its minimum is subtracted): one 32-bit VOP2
     auto normalize = [&]() { V.U = V.U - dpp_pkmin_wave(V.U); };
-#ifdef SORA_DBG_NO_TRACE                                                        // experiment (tools/ab_decode.sh): the forward pass alone -- results are wrong, only the duration means something
-    auto trace = [&](unsigned, unsigned, uint32_t, uint32_t, uint32_t) {};
-#else
     auto trace = [&](unsigned mA, unsigned mB, uint32_t cntA, uint32_t cntB, uint32_t top) { viterbi_trace<RG::kMaxWalk>(V.U, ring, tr, ob, mA, mB, cntA, cntB,
             A.out, B.out, top); };
-#endif
     auto next_event = [&]() -> uint32_t {
         uint32_t t = ob + (uint32_t)(WIN + LOOK + 6);
         if (!A.done) t = min(t, A.tr_end);
@@ -1602,89 +1527,6 @@ __global__ void __launch_bounds__(256) k_win_redo_finish(const VitJob* jobs, con
 __global__ void __launch_bounds__(256) k_win_redo_finish_pipe(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride,
                                                               const uint16_t* vecs, const uint8_t* soft, uint8_t* out, unsigned long long* stats, RxArgs A, uint32_t* host_note)
 { win_redo_finish_body<true>(jobs, hdr, jstride, target, vstride, vecs, soft, out, stats, A, host_note); }
-
-#ifdef SORA_EXP_FIN
-// Round 6, MEASURED AND NOT ADOPTED (tools variant only: -DSORA_EXP_FIN=3; profiles/r06_c_unit_finish_experiment.json): the window-parallel trellis whose LAST UNIT OF A
-// FRAME TO ARRIVE finishes the frame (a frame is complete when its own bytes are, not when the call's last kernel has run).
-// k_viterbi16w's wave, then a tail: the wave publishes its units' bytes and vectors (release), counts each of its up to eight
-// units in at its frame (wdone[list][idx]); the wave whose count completes a frame -- every other unit of the frame has published before it counted -- checks the
-// frame's boundaries exactly as k_win_redo's gate does and, if they all hold, descrambles the frame, checks its CRC, stores the MPDU (into the host's page-locked
-// array too when one is bound: sora_rx_bind_mpdu -- the bytes cross PCIe WHILE the other frames are still being decoded, which is what a lone call's 0.13 ms of
-// finishing kernel was) and writes the row's verdict.  Nobody waits for anybody: a frame whose proof fails is simply left to k_win_redo_finish behind this kernel,
-// which decodes it again and finishes it as before; for a frame finished here its finish_frame returns at once (error_code is set).  The counter is reset by the
-// wave that completes it: every call finds zeros.  The finishing tables live in the trellis's own LDS block, which is free by then.
-// Result, a lone 4096-capture call: identical rows, and SLOWER -- k_viterbi16w 0.262 -> 0.297 ms with the release and the counting alone (SORA_EXP_FIN=1), 0.317 with the
-// proofs' reads behind the acquire (=2), 0.372 with the frames finished (0.442 when the MPDUs also cross PCIe from here), against 0.027 (0.134) ms of k_win_redo_finish
-// saved: all units of a call run side by side (2048 waves on 1792 slots), so every frame's last unit arrives at the END of the launch, and the 512 waves that hold the
-// frames' last pieces then finish eight frames each, one after the other, where the finishing kernel has 2048 waves doing it at once.
-struct FinTail {
-    const RxArgs* A; uint32_t* wdone; uint32_t jstride, vstride; const uint16_t* vecs; Lds16<256, 24>* S; const VitJob* jobs;
-    // (out of line: the tail gets registers of its own instead of living beside the forward pass's 143)
-    template <typename CRT, typename JOBS>
-    __device__ __forceinline__ void operator()(CRT, uint32_t list, uint32_t nl, uint32_t w, uint32_t q, JOBS) const { tail<CRT::value>(list, nl, w, q); }
-    template <int CR>
-    __device__ __attribute__((noinline)) void tail(uint32_t list, uint32_t nl, uint32_t w, uint32_t q) const
-    {
-        const VitJob* __restrict__ jl = jobs + (size_t)list * jstride;
-        auto job_at = [jl](uint32_t idx) { return jl[idx]; };
-        static_assert(sizeof(FinishLds) <= sizeof(Lds16<256, 24>), "the finishing tables take the place of the trellis's LDS block");
-        const unsigned lane = threadIdx.x & 63;
-        FinishLds& L = *reinterpret_cast<FinishLds*>(S);
-        bool tables = false;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                       // this wave's bytes and vectors, before its units are counted
-        for (uint32_t sidx = 0; sidx < 8u; sidx++) {
-            const UnitRef R = unit_ref_at<CR, 256, 24>(job_at, nl, 8u * w + sidx, q);      // (uniform: every lane works out the same position)
-            if (R.uu == kWinNone) continue;
-            uint32_t* cnt = wdone + (size_t)list * jstride + R.idx;
-            uint32_t old = 0;
-            if (lane == 0) old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            old = (uint32_t)__builtin_amdgcn_readfirstlane((int)old);
-            if (old + 1u != R.nun) continue;
-            if (lane == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if defined(SORA_EXP_FIN) && SORA_EXP_FIN == 1
-            continue;                                                            // experiment: what do the fence and the counting cost by themselves?
-#endif
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                   // ... what the frame's other units published before they counted
-            const size_t vec0 = (size_t)list * vstride + (size_t)R.idx * q;
-            uint32_t bad = 0;
-            for (uint32_t u = 1u + lane; u < R.nun; u += 64u) {
-                const uint4* a = reinterpret_cast<const uint4*>(vecs + ((vec0 + u) * 2u) * 64u);
-                const uint4* b = reinterpret_cast<const uint4*>(vecs + ((vec0 + u - 1u) * 2u + 1u) * 64u);
-                uint32_t d = 0;
-#pragma unroll
-                for (int i = 0; i < 8; i++) { const uint4 x = a[i], y = b[i]; d |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w); }
-                bad |= d;
-            }
-            if (__ballot(bad != 0u) != 0ull) continue;                           // (k_win_redo_finish decodes the pair again and finishes it)
-#if defined(SORA_EXP_FIN) && SORA_EXP_FIN == 2
-            continue;                                                            // experiment: ... and the proof's reads behind the acquire?
-#endif
-            if (!tables) {
-                tables = true;
-                for (uint32_t i = lane; i < 256u; i += 64u) L.crc[i] = A->T.crc[i];
-                for (uint32_t i = lane; i < 6u * 8u * 16u; i += 64u) L.z[i] = A->T.crcz[i];
-                for (uint32_t pp = lane; pp < 127u; pp += 64u) {
-                    const uint8_t* qq = A->T.scr_seq;
-                    L.seq4[pp] = (uint32_t)qq[pp] | ((uint32_t)qq[(pp + 8u) % 127u] << 8) | ((uint32_t)qq[(pp + 16u) % 127u] << 16) | ((uint32_t)qq[(pp + 24u) % 127u] << 24);
-                }
-                for (uint32_t i = lane; i < 128u; i += 64u) L.phase[i] = A->T.scr_phase[i];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
-            finish_frame(*A, A->joblist[list * A->nrows + R.idx], L);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-    }
-};
-__global__ void __launch_bounds__(64) k_viterbi16w_fin(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ hdr, uint32_t jstride, uint32_t target, uint32_t vstride,
-                                                       const uint8_t* __restrict__ soft, uint8_t* out, uint16_t* vecs, uint32_t* wdone, RxArgs A)
-{
-    __shared__ Lds16<256, 24> S;
-    auto jobs_of = [&](uint32_t list) { const VitJob* __restrict__ jl = jobs + (size_t)list * jstride; return [jl](uint32_t idx) { return jl[idx]; }; };
-    auto ready = [](const UnitGeom&, const UnitGeom&, uint32_t) { return true; };
-    viterbi16w_wave<256, 24, 3>(S, blockIdx.x, jobs_of, ready, hdr, target, vstride, soft, out, vecs, FinTail{ &A, wdone, jstride, vstride, vecs, &S, jobs });
-}
-
-#endif  // SORA_EXP_FIN
 
 // ------------------------------------------------------------------------------------------------
 // k_pack: compacts the per-capture frame table into dense sora_frame_result rows in (capture, time) order, on the

@@ -1081,11 +1081,6 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
     Rx11bArgs A;
     A.iq = reinterpret_cast<const uint32_t*>(d_iq); A.caps = S.d_caps; A.ncaps = (uint32_t)ncaps; A.thr = rx->cfg.cca_pwr_threshold;
     A.max_frames = rx->cfg.max_frames_per_capture; A.rows = S.d_rows; A.nframes = S.d_nframes; A.mpdu = S.d_mpdu; A.crc = rx->d_crc; A.needs_cck = S.d_needs_cck;
-#ifdef SORA_VARIANT_11B_ONE_KERNEL                                             // build variant (sora_amd.build.build_variant): every capture through the CCK instantiation
-    constexpr bool one_kernel = true;
-#else
-    constexpr bool one_kernel = false;
-#endif
     // The pass plan.  Automatic (default): a two-pass call also counts, on the device, how many captures its first pass handed over; once such a
     // count has come back (no waiting: the event is only queried) and says "more than half", the following calls go straight through the CCK
     // instantiation -- which decodes all four rates with identical rows -- except every 16th, which is a two-pass call again and measures.
@@ -1096,7 +1091,7 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
         // (hipErrorNotReady is sticky for hipGetLastError: the check at the end of this call must not see it -- ADVICE r4)
         else (void)hipGetLastError();
     }
-    bool single = one_kernel || rx->pass_plan == 1;
+    bool single = rx->pass_plan == 1;
     if (rx->pass_plan == 2 && rx->auto_single && (++rx->auto_calls & 15u) != 0u) single = true;
     HIPCHK11(hipMemsetAsync(S.d_needs_cck, single ? 1 : 0, 4 * ncaps, S.stream));
     if (!single) hipLaunchKernelGGL(k_rx11b, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, S.stream, A);

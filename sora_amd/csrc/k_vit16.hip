@@ -94,9 +94,7 @@ __device__ __forceinline__ void forward16(Lds16<WIN, LOOK>& S, const uint8_t* __
     auto pos_of = [&](uint32_t p, int jb) -> uint32_t { const uint32_t q = p + (uint32_t)jb; return q >= (uint32_t)P ? q - (uint32_t)P : q; };
 
     auto trace = [&](uint32_t my_cnt, int t24_last) {
-#ifndef SORA_EXP_NORING
         trace16<WIN, LOOK>((unsigned)(uintptr_t)&S, V.U[0], V.U[1], V.U[2], V.U[3], tr, ob, pos_of(pos, t24_last / 8), (uint32_t)(t24_last % 8), my_cnt, my_out);
-#endif
     };
     auto next_event = [&]() -> uint32_t {
         const uint32_t mine = my_done ? 0xFFFFFFFFu : my_tr_end;
@@ -153,11 +151,7 @@ __device__ __forceinline__ void forward16(Lds16<WIN, LOOK>& S, const uint8_t* __
     unsigned pos512[3];
     auto set_row_pos = [&]() {
 #pragma unroll
-#ifdef SORA_EXP_NORING
-        for (int jb = 0; jb < 3; jb++) pos512[jb] = 0u;
-#else
         for (int jb = 0; jb < 3; jb++) pos512[jb] = pos_of(pos, jb) * 512u;
-#endif
     };
     auto end_row = [&]() { pos = pos_of(pos, 3); set_row_pos(); };
     set_row_pos();
@@ -285,27 +279,9 @@ __device__ __forceinline__ void viterbi16_body(const VitJob* __restrict__ jobs, 
 
 }  // namespace
 
-#ifdef SORA_EXP_LB
-#define SORA_VIT16_BOUNDS __launch_bounds__(64, SORA_EXP_LB)
-#else
-#define SORA_VIT16_BOUNDS __launch_bounds__(64)
-#endif
-__global__ void SORA_VIT16_BOUNDS k_viterbi16(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ njobs3, uint32_t njobs_single, uint32_t stride,
+__global__ void __launch_bounds__(64) k_viterbi16(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ njobs3, uint32_t njobs_single, uint32_t stride,
         const uint8_t* __restrict__ soft, uint8_t* __restrict__ out)
-{
-#ifdef SORA_EXP_STAGGER                                         // experiment (round 4): waves of one launch start up to SORA_EXP_STAGGER x 16 x 1.75 us apart (a hash of the workgroup), so that the
-    // two waves of a SIMD are not in the add-compare-select stretch and in the trace-back at the same time
-    {
-        const uint32_t d = ((blockIdx.x * 2654435761u) >> 28) * SORA_EXP_STAGGER;
-        for (uint32_t i = 0; i < d; i++) __builtin_amdgcn_s_sleep(63);
-    }
-#endif
-#ifdef SORA_EXP_VIT_PRIO
-    // experiment (round 4): the issue-bound trellis waves ahead of the latency-bound front-end waves on their SIMD
-    __builtin_amdgcn_s_setprio(SORA_EXP_VIT_PRIO);
-#endif
-    viterbi16_body<256, 24, 3>(jobs, njobs3, njobs_single, stride, soft, out);
-}
+{ viterbi16_body<256, 24, 3>(jobs, njobs3, njobs_single, stride, soft, out); }
 __global__ void __launch_bounds__(64) k_viterbi16_11n(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ njobs3, uint32_t njobs_single,
         uint32_t stride, const uint8_t* __restrict__ soft, uint8_t* __restrict__ out)
 { viterbi16_body<192, 36, 8>(jobs, njobs3, njobs_single, stride, soft, out); }

@@ -6,12 +6,10 @@
 #include "rx_types.h"
 #include "../../include/sora_hip.h"
 
-// Experiment and probe switches (SORA_EXP_*, SORA_DBG_*) belong to the TOOLS variant of the library (sora_amd.build.build_variant adds -DSORA_TOOLS for them): the product
+// Probe switches (SORA_SCAN_PROBE, SORA_DBG_*) belong to the TOOLS variant of the library (sora_amd.build.build_variant adds -DSORA_TOOLS for them): the product
 // build refuses them, so no measurement scaffolding can reach it by accident.
-#if !defined(SORA_TOOLS) && (defined(SORA_EXP_NORING) || defined(SORA_EXP_LB) || defined(SORA_EXP_STAGGER) || defined(SORA_EXP_VIT_PRIO) || defined(SORA_DBG_TRACK_TH) || \
-                             defined(SORA_DBG_NO_TRACE) || defined(SORA_DBG_KFRAME_PRIVATE) || defined(SORA_DBG_NO_SYMBOLS) || defined(SORA_DBG_NO_TRELLIS) || defined(SORA_SCAN_PROBE) || \
-                             defined(SORA_EXP_FIN))
-#error "SORA_EXP_* / SORA_DBG_* switches need -DSORA_TOOLS (sora_amd.build.build_variant)"
+#if !defined(SORA_TOOLS) && (defined(SORA_SCAN_PROBE) || defined(SORA_DBG_PIPE_TIMELINE) || defined(SORA_DBG_PIPE_LOSE_FLAGS))
+#error "SORA_SCAN_PROBE / SORA_DBG_* switches need -DSORA_TOOLS (sora_amd.build.build_variant)"
 #endif
 
 namespace sora {
@@ -54,16 +52,16 @@ struct RxArgs {
     Tables          T;
     FrameRow*       frames;
     const FrameCtx* fctx;
-    uint8_t*        soft;           // [slots*108] the frames' packed soft streams (three bits per value, rx_types.h); unused by the fused decode kernel
+    uint8_t*        soft;           // [slots*108] the frames' packed soft streams (three bits per value, rx_types.h)
     uint8_t*        vout;           // [slots*32]
     uint8_t*        mpdu;           // [slots*32]
-    VitJob*         jobs;           // [3][nrows] (indexed by job); unused by the fused decode kernel
+    VitJob*         jobs;           // [3][nrows] (indexed by job)
     const uint32_t* njobs;
     const uint32_t* joblist;
     const uint32_t* slot_row;       // [total_slots] owner row of a symbol slot, 0xFFFFFFFF = none (k_scan)
-    uint32_t*       eq;             // [total_slots][64] equalised bins, packed COMPLEX16 (k_sym_front -> k_track, k_sym_back)
-    TrackRec*       track;          // [total_slots] rotation parameters of a data symbol (k_track -> k_sym_back)
-    uint32_t*       pil;            // [total_slots][4] the four pilot bins (43, 57, 7, 21) of eq[] once more, densely: all k_track reads
+    uint32_t*       eq;             // [total_slots][64] equalised bins, packed COMPLEX16 (k_sym_front -> k_track_lds, k_sym_back)
+    TrackRec*       track;          // [total_slots] rotation parameters of a data symbol (k_track_lds -> k_sym_back)
+    uint32_t*       pil;            // [total_slots][4] the four pilot bins (43, 57, 7, 21) of eq[] once more, densely: all k_track_lds reads
     const uint32_t* pipe_flags;     // k_finish behind k_pipe: word 0 != 0 = a hand-off inside that launch gave up (else null)
     // sora_rx_bind_mpdu: the caller's page-locked MPDU array (the geometry of mpdu[]): the frame sink writes every MPDU there as well, over PCIe, as it finishes the frame (else null)
     uint8_t*        mpdu_host;
@@ -85,11 +83,9 @@ struct PipeArgs {
 __global__ void k_scan(ScanArgs A);
 __global__ void k_frame(RxArgs A);
 __global__ void k_sym_front(RxArgs A);
-__global__ void k_track(RxArgs A);
 __global__ void k_track_lds(RxArgs A);
 __global__ void k_sym_back(RxArgs A);
 __global__ void k_pipe(RxArgs A, PipeArgs P);
-__global__ void k_decode(RxArgs A);
 __global__ void k_viterbi(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
 __global__ void k_viterbi11n(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
 // k_vit16.hip
@@ -98,10 +94,6 @@ __global__ void k_viterbi16_11n(const VitJob* jobs, const uint32_t* njobs3, uint
 // k_vitwin.hip: the window-parallel trellis.  hdr = the call's counter block (njobs per code rate in its first three words); jstride = capacity of a list of jobs;
 // target = units the call is cut into at least, frames permitting; vstride = vectors per code-rate list
 __global__ void k_viterbi16w(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint8_t* soft, uint8_t* out, uint16_t* vecs);
-#ifdef SORA_EXP_FIN
-__global__ void k_viterbi16w_fin(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint8_t* soft, uint8_t* out, uint16_t* vecs,
-                                 uint32_t* wdone, RxArgs A);
-#endif
 __global__ void k_viterbi16w_11n(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint8_t* soft, uint8_t* out, uint16_t* vecs);
 __global__ void k_win_redo_11n(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint16_t* vecs,
         const uint8_t* soft, uint8_t* out, unsigned long long* stats);

@@ -24,14 +24,10 @@ using namespace sora;
 static thread_local std::string g_last_error;
 hipError_t sora_internal_stream_create(hipStream_t* out, int index)
 {
-#ifndef SORA_ONE_STREAM_PRIORITY
     int least = 0, greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
     const int level = index % 3, prio = level == 0 ? 0 : level == 1 ? greatest : least;
     if (least != greatest) return hipStreamCreateWithPriority(out, hipStreamNonBlocking, prio);
-#else
-    (void)index;
-#endif
     return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
 }
 
@@ -432,7 +428,6 @@ struct RxPipe {
     // (the pipeline's calls alternate between two sets of counters, words 0-3 and 8-11 of the 64-byte block in front of the frame table) -- no fill kernel in front of a call
     // unless counters_ready says that nothing has: the first call, a call recorded into a hipGraph (its arguments are frozen: it always uses set 0 behind its own fill)
     uint32_t parity = 0; bool counters_ready = false;
-    bool fused = false;                                         // data field decoded by k_decode (soft values stay in LDS) instead of k_frame + k_viterbi
     // trellis kernel of the split path: 0 = k_viterbi (64 lanes per frame pair), 1 = k_viterbi16 (16 lanes per pair, k_vit16.hip),
     // 2 = k_viterbi16w + k_win_redo (the proof, and the serial decode of what fails it) (window-parallel, k_vitwin.hip)
     int  lanes16 = 0;
@@ -441,8 +436,6 @@ struct RxPipe {
     // sora_rx_set_ordered: this call's trellis kernel starts behind the previous call's (wait_for = that call's ev_trellis), so that calls in flight COMPLETE in the order they were
     // submitted -- the front kernels (latency chains) of a call still run beside the trellis of the one before it, and its delivery beside the trellis of the one after it
     hipEvent_t ev_trellis = nullptr, wait_for = nullptr; bool ordered = false;
-    bool unit_finish = true;       // (SORA_EXP_FIN builds; sora_internal_rx_unit_finish(0) = the plain k_viterbi16w in front of k_win_redo_finish, for A/B timing)
-    uint32_t* d_wdone = nullptr;   // k_viterbi16w_fin (SORA_EXP_FIN): units of a frame that have arrived, per code-rate list and place (zero between calls)
     uint8_t* d_vout = nullptr; uint8_t* d_mpdu = nullptr; uint32_t* d_njobs = nullptr; uint32_t* d_joblist = nullptr;
     sora_complex16* d_iq_own = nullptr; size_t iq_own_samples = 0;
     uint8_t* d_dump = nullptr; size_t dump_cap = 0;             // sora_rx_process_dump: the raw dump bytes of this pipeline's call
@@ -479,6 +472,10 @@ struct RxPipe {
 constexpr uint32_t kWinLoneWaves = 3 * sora::kWinLonePad / 8;
 // units a call of the window-parallel trellis is cut into at least, frames permitting: one round of the chip's 2048 eight-unit trellis slots
 constexpr uint32_t kWinUnitsTarget = 16384;
+// the window-parallel trellis of a call of `rows` frame rows: the units it is cut into at most (a frame has at most 80 windows) ...
+static uint64_t win_units(uint64_t rows) { return std::min<uint64_t>(std::max<uint64_t>(kWinUnitsTarget, rows), 80ull * rows); }
+// ... and its waves: eight units each, + a partly filled one per code-rate list + the lone layout's gaps
+static uint64_t win_waves(uint64_t rows) { return (win_units(rows) + 7) / 8 + 3 + kWinLoneWaves; }
 // Probe hooks (which kernels of the chain a call launches, empty launches appended to a call, the calls' kernel boundaries on one time base, the device arrays between the
 // kernels) exist in the TOOLS variant of the library only -- sora_amd.build.build_variant("tools", ["SORA_TOOLS"]), loaded by the scripts under tools/ through SORA_HIP_LIB.
 // The product build has neither the entry points nor the branches they steer.
@@ -490,7 +487,8 @@ constexpr uint32_t kWinUnitsTarget = 16384;
 #endif
 static constexpr size_t kNumTimed = 5;
 static const char* const kKernelNames[kNumTimed] = { "memset+caps", "k_scan", "k_frame", "k_viterbi", "k_finish" };
-static const char* const kKernelNamesFused[kNumTimed] = { "memset+caps", "k_scan", "k_decode", "", "k_finish" };   // "" = not launched
+// (sora_rx_kernel_name_fused: the removed k_decode chain, kept in the ABI; "" = not launched)
+static const char* const kKernelNamesFused[kNumTimed] = { "memset+caps", "k_scan", "k_decode", "", "k_finish" };
 
 namespace sora {
 // n16 16-byte words <- 0, then m16 of `ones` <- all ones,
@@ -526,7 +524,7 @@ static void rx_free(RxPipe* rx)
     if (!rx) return;
     void* ptrs[] = { rx->d_caps, rx->d_fctx, rx->d_nframes,
                      rx->d_soft, rx->d_jobs, rx->d_vout, rx->d_mpdu, rx->d_iq_own, rx->d_rows, rx->d_nrows, rx->d_njobs, rx->d_joblist, rx->d_dump, rx->d_slot_row, rx->d_eq, rx->d_track, rx->d_pil,
-                     rx->d_wvecs, rx->d_wstats, rx->d_wdone, rx->d_pflags };
+                     rx->d_wvecs, rx->d_wstats, rx->d_pflags };
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& e : rx->ev) if (e) (void)hipEventDestroy(e);
     if (rx->ev_trellis) (void)hipEventDestroy(rx->ev_trellis);
@@ -715,26 +713,18 @@ static int pipe_process_dev(RxPipe* rx, const sora_complex16* d_iq, const sora_c
     rx->h_caps.swap(hc);
     rx->ncaps = (uint32_t)ncaps; rx->total_slots = slots; rx->have_results = false; rx->delivered = rx->released = false;
     if (ncaps == 0) { rx->have_results = true; return SORA_OK; }
-    if (!rx->fused && !rx->d_soft) {                                             // the packed soft streams and the job table exist only for the split path
+    if (!rx->d_soft) {                                                           // the packed soft streams and the job table, on the first call
         HIPCHK(hipMalloc((void**)&rx->d_soft, (size_t)kSoftBytesPerSlot * rx->cap_slots + kSoftSlack));   // three bits per soft value (rx_types.h)
         HIPCHK(hipMalloc((void**)&rx->d_jobs, 3 * sizeof(VitJob) * rx->cap_rows));
     }
     if (rx->lanes16 == 2 && !rx->d_wvecs) {                                      // the window-parallel trellis's arrays, on its first use
         // (a call is cut into at most max(target, rows) units and a frame into at most 80: a single-capture handle needs 80 vectors per row, not the target's 16384)
-        rx->wstride = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(kWinUnitsTarget, rx->cap_rows), 80ull * rx->cap_rows) + rx->cap_rows;
+        rx->wstride = (uint32_t)win_units(rx->cap_rows) + rx->cap_rows;
         HIPCHK(hipMalloc((void**)&rx->d_wvecs, 3 * (size_t)kWinVecBytes * rx->wstride));
         HIPCHK(hipMalloc((void**)&rx->d_wstats, (4 * kWinStatBanks + 1) * sizeof(unsigned long long)));   // (+ 1: calls whose data field k_win_redo_finish_pipe made again)
         HIPCHK(hipMemset(rx->d_wstats, 0, (4 * kWinStatBanks + 1) * sizeof(unsigned long long)));
-#ifdef SORA_EXP_FIN
-        HIPCHK(hipMalloc((void**)&rx->d_wdone, 3 * sizeof(uint32_t) * (size_t)rx->cap_rows));
-        HIPCHK(hipMemset(rx->d_wdone, 0, 3 * sizeof(uint32_t) * (size_t)rx->cap_rows));
-#endif
     }
-#ifdef SORA_FRAME_SPLIT3
-    const bool split = true;
-#else
-    const bool split = rx->front >= 3 && !rx->fused;
-#endif
+    const bool split = rx->front >= 3;
     // (the handle only asks for k_pipe where its workgroups are all resident at once: pipe_fits)
     const bool pipe = split && rx->front == 4 && rx->lanes16 == 2;
     if (pipe && !rx->d_pflags) {
@@ -764,13 +754,15 @@ static int pipe_process_dev(RxPipe* rx, const sora_complex16* d_iq, const sora_c
         caps_changed = true;
     }
     const uint32_t nrows = rx->ncaps * rx->cfg.max_frames_per_capture;
+    // workgroups of the kernels that take PAIRS of frames (four per workgroup: at most ceil(n / 2) + 2 pairs over the three code-rate lists), of the window-parallel trellis
+    const uint32_t pair_groups = (nrows / 2 + 3 + 3) / 4, win_groups = (uint32_t)win_waves(nrows);
 
     auto enqueue = [&](bool recording) -> int {                                  // the kernel chain of one call, in stream order (recording: into a hipGraph)
 #ifdef SORA_TOOLS
         // (the tools variant's partial chains and array dumps want the plain protocol: a fill in front of every call)
         const bool self_clean = false;
 #else
-        const bool self_clean = !recording && !rx->fused;
+        const bool self_clean = !recording;
 #endif
         const bool fill = !self_clean || !rx->counters_ready;
         const uint32_t par = fill ? 0u : rx->parity;
@@ -784,12 +776,11 @@ static int pipe_process_dev(RxPipe* rx, const sora_complex16* d_iq, const sora_c
             const uint32_t n16 = (uint32_t)((64 + sizeof(FrameRow) * (size_t)nrows) / 16), m16 = split ? (slots + 3) / 4 : 0u;
             const uint32_t k16 = (pipe_words + 3u) / 4u;
             hipLaunchKernelGGL(k_clear16, dim3((n16 + m16 + k16 + 255) / 256), dim3(256), 0, st, reinterpret_cast<uint4*>(rx->d_njobs), n16,
-                    reinterpret_cast<uint4*>(rx->d_slot_row), m16,
-                               reinterpret_cast<uint4*>(rx->d_pflags), k16);
+                               reinterpret_cast<uint4*>(rx->d_slot_row), m16, reinterpret_cast<uint4*>(rx->d_pflags), k16);
         }
         ScanArgs S{};
         S.iq = reinterpret_cast<const uint32_t*>(d_iq); S.caps = rx->d_caps; S.ncaps = rx->ncaps; S.str = rx->str;
-            S.keep_queue = rx->cfg.sample_rate_mhz == 44 ? 1u : 0u; S.thr = rx->cfg.cca_pwr_threshold;
+        S.keep_queue = rx->cfg.sample_rate_mhz == 44 ? 1u : 0u; S.thr = rx->cfg.cca_pwr_threshold;
         S.max_frames = rx->cfg.max_frames_per_capture; S.T = rx->tabs.T; S.frames = rx->d_frames; S.fctx = rx->d_fctx; S.nframes = rx->d_nframes;
         S.njobs = counters; S.joblist = rx->d_joblist; S.nrows = nrows; S.slot_row = split ? rx->d_slot_row : nullptr; S.cont = rx->cont; S.consumed = rx->consumed;
         // this call's k_scan prepares the next one's (and its own slot owners and hand-off words)
@@ -800,100 +791,74 @@ static int pipe_process_dev(RxPipe* rx, const sora_complex16* d_iq, const sora_c
         mark();
         if (RX_ONLY(rx, 1u)) hipLaunchKernelGGL(k_scan, dim3(rx->ncaps), dim3(64), 0, st, S);
         mark();
+
         RxArgs R{};
-        bool redo_finish = false;
         R.iq = S.iq; R.caps = rx->d_caps; R.str = rx->str; R.total_slots = slots; R.nrows = nrows; R.T = rx->tabs.T;
         R.frames = rx->d_frames; R.fctx = rx->d_fctx;
         R.vout = rx->d_vout; R.mpdu = rx->d_mpdu; R.njobs = counters; R.joblist = rx->d_joblist; R.mpdu_host = rx->bound_mpdu;
-#ifdef SORA_WITH_K_DECODE
-        if (rx->fused) {
-            // the data field of every frame, samples -> decoded bytes, in one kernel: two frames per trellis wave, two pairs per
-            // workgroup (at most ceil(n / 2) + 2 pairs over the three code-rate lists; surplus workgroups return at once)
-            hipLaunchKernelGGL(k_decode, dim3(((nrows + 1) / 2 + 2 + 1) / 2), dim3(256), 0, st, R);
-            mark(); mark();
-        } else
-#endif
-        {
-            R.soft = rx->d_soft; R.jobs = rx->d_jobs; R.slot_row = rx->d_slot_row; R.eq = rx->d_eq; R.track = rx->d_track; R.pil = rx->d_pil;
-            redo_finish = rx->lanes16 == 2 && RX_ONLY(rx, 4u) && RX_ONLY(rx, 8u);
-            // the window-parallel trellis: a frame has at most 80 windows
-            const uint32_t units_max = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(kWinUnitsTarget, nrows), 80ull * nrows);
-            if (pipe) {
-                R.pipe_flags = rx->d_pflags;
-                // a handful of frames: the symbol chain AND the window-parallel trellis as one launch (k_rx.hip: k_pipe), the proof behind it
-                if (RX_ONLY(rx, 2u)) {
-                    PipeArgs P{};
-                    P.nfront = (slots + 63) / 64; P.ntrack = nrows; P.flags = rx->d_pflags; P.target = kWinUnitsTarget; P.vstride = rx->wstride;
-                        P.vecs = rx->d_wvecs; P.stamp_base = rx->pflag_words;
-                    P.lanes64 = rx->pipe64 ? 1u : 0u; P.wait_ticks = rx->pipe_wait_ticks;
-                    // trellis waves: eight units each (+ a partly filled one per code-rate list + the lone layout's gaps), or -- 64-lane form -- unit u of two frames each
-                    const uint32_t waves = rx->pipe64 ? kWinMaxUnits * ((nrows + 3) / 2) : (units_max + 7) / 8 + 3 + kWinLoneWaves;
-                    hipLaunchKernelGGL(k_pipe, dim3(P.nfront + P.ntrack + (waves + 3) / 4), dim3(256), 0, st, R, P);
-                }
-                mark();
-                if (RX_ONLY(rx, 4u) && !redo_finish)
-                    hipLaunchKernelGGL(k_win_redo, dim3((nrows / 2 + 3 + 3) / 4), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters,
-                            nrows, kWinUnitsTarget, rx->wstride,
-                                       (const uint16_t*)rx->d_wvecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wstats);
-                mark();
-            } else {
-            if (split) {
-                // The symbol chain as three kernels (k_rx.hip): per symbol slot in front of and behind the tracker, per frame (four lanes each) for the tracker.  Round 4 built it
-                // (k_track, tables in L2) and did not adopt it: no faster than k_frame for a full batch (profiles/r04_h_*).  Round 5: the tracker with its tables in LDS
-                // (k_track_lds) makes it the chain for FEW frames in flight, where k_frame's one wave per frame is a 465-symbol serial loop (fsample-6).
-                if (RX_ONLY(rx, 2u)) {
-                    hipLaunchKernelGGL(k_sym_front, dim3((slots + 63) / 64), dim3(256), 0, st, R);
-#ifdef SORA_FRAME_SPLIT3
-                    hipLaunchKernelGGL(k_track, dim3((nrows + 63) / 64), dim3(256), 0, st, R);
-#else
-                    hipLaunchKernelGGL(k_track_lds, dim3((nrows + 63) / 64), dim3(256), 0, st, R);
-#endif
-                    hipLaunchKernelGGL(k_sym_back, dim3((slots + 63) / 64), dim3(256), 0, st, R);
-                }
-            } else if (RX_ONLY(rx, 2u)) hipLaunchKernelGGL(k_frame, dim3((nrows + 3) / 4), dim3(256), 0, st, R);
+        R.soft = rx->d_soft; R.jobs = rx->d_jobs; R.slot_row = rx->d_slot_row; R.eq = rx->d_eq; R.track = rx->d_track; R.pil = rx->d_pil;
+        R.pipe_flags = pipe ? rx->d_pflags : nullptr;
+        // behind the window-parallel trellis the proof, the decode of what fails it and T11aDesc / the frame sink are ONE launch: the wave that holds a pair of frames
+        // finishes them
+        const bool redo_finish = rx->lanes16 == 2 && RX_ONLY(rx, 4u) && RX_ONLY(rx, 8u);
+        // the proof of the window-parallel trellis and the serial decode of the pairs of frames that fail it (none, normally: its waves check and return)
+        auto win_redo = [&]() {
+            hipLaunchKernelGGL(k_win_redo, dim3(pair_groups), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, nrows, kWinUnitsTarget, rx->wstride,
+                               (const uint16_t*)rx->d_wvecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wstats);
+        };
+
+        // the symbol chain
+        if (pipe) {
+            // a handful of frames: the symbol chain AND the window-parallel trellis as one launch (k_rx.hip: k_pipe), the proof behind it
+            if (RX_ONLY(rx, 2u)) {
+                PipeArgs P{};
+                P.nfront = (slots + 63) / 64; P.ntrack = nrows; P.flags = rx->d_pflags; P.target = kWinUnitsTarget; P.vstride = rx->wstride;
+                P.vecs = rx->d_wvecs; P.stamp_base = rx->pflag_words;
+                P.lanes64 = rx->pipe64 ? 1u : 0u; P.wait_ticks = rx->pipe_wait_ticks;
+                // trellis waves: those of k_viterbi16w, or -- 64-lane form -- unit u of two frames each
+                const uint32_t waves = rx->pipe64 ? kWinMaxUnits * ((nrows + 3) / 2) : win_groups;
+                hipLaunchKernelGGL(k_pipe, dim3(P.nfront + P.ntrack + (waves + 3) / 4), dim3(256), 0, st, R, P);
+            }
             mark();
+            if (RX_ONLY(rx, 4u) && !redo_finish) win_redo();
+        } else if (split) {
+            // The symbol chain as three kernels (k_rx.hip): per symbol slot in front of and behind the tracker, per frame (four lanes each) for the tracker, whose tables
+            // are in LDS: the chain for FEW frames in flight, where k_frame's one wave per frame is a 465-symbol serial loop (fsample-6).
+            if (RX_ONLY(rx, 2u)) {
+                hipLaunchKernelGGL(k_sym_front, dim3((slots + 63) / 64), dim3(256), 0, st, R);
+                hipLaunchKernelGGL(k_track_lds, dim3((nrows + 63) / 64), dim3(256), 0, st, R);
+                hipLaunchKernelGGL(k_sym_back, dim3((slots + 63) / 64), dim3(256), 0, st, R);
+            }
+        } else if (RX_ONLY(rx, 2u)) hipLaunchKernelGGL(k_frame, dim3((nrows + 3) / 4), dim3(256), 0, st, R);
+        mark();
+
+        // the trellis (k_pipe holds it itself)
+        if (!pipe) {
             if (rx->wait_for && !recording) (void)hipStreamWaitEvent(st, rx->wait_for, 0);   // (sora_rx_set_ordered: behind the previous call's trellis)
             if (!RX_ONLY(rx, 4u)) {}
             else if (rx->lanes16 == 2) {
-                // window-parallel: the call's units (at most target + one per row, eight per wave, + a partly filled wave per code-rate list), then the proof
-                // and the serial decode of the pairs of frames that fail it (none, normally: k_win_redo's waves check and return)
-#ifdef SORA_EXP_FIN
-                // (experiment, not adopted: the last unit of a frame to arrive finishes the frame -- k_rx.hip, k_viterbi16w_fin)
-                if (redo_finish && rx->unit_finish)
-                    hipLaunchKernelGGL(k_viterbi16w_fin, dim3((units_max + 7) / 8 + 3 + kWinLoneWaves), dim3(64), 0, st, (const VitJob*)rx->d_jobs,
-                            (const uint32_t*)counters, nrows, kWinUnitsTarget, rx->wstride,
-                                       (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wvecs, rx->d_wdone, R);
-                else
-#endif
-                hipLaunchKernelGGL(k_viterbi16w, dim3((units_max + 7) / 8 + 3 + kWinLoneWaves), dim3(64), 0, st, (const VitJob*)rx->d_jobs,
-                        (const uint32_t*)counters, nrows, kWinUnitsTarget, rx->wstride,
-                                   (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wvecs);
-                if (!redo_finish)
-                    hipLaunchKernelGGL(k_win_redo, dim3((nrows / 2 + 3 + 3) / 4), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters,
-                            nrows, kWinUnitsTarget, rx->wstride,
-                                       (const uint16_t*)rx->d_wvecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wstats);
+                // window-parallel: the call's units (at most target + one per row), then the proof
+                hipLaunchKernelGGL(k_viterbi16w, dim3(win_groups), dim3(64), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, nrows, kWinUnitsTarget,
+                                   rx->wstride, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wvecs);
+                if (!redo_finish) win_redo();
             }
             else if (rx->lanes16)   // eight frames per one-wave workgroup: at most ceil(n / 8) + 2 waves over the three lists
                 hipLaunchKernelGGL(k_viterbi16, dim3((nrows + 7) / 8 + 2), dim3(64), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, 0u, nrows,
-                        (const uint8_t*)rx->d_soft, rx->d_vout);
+                                   (const uint8_t*)rx->d_soft, rx->d_vout);
             else
-                // at most ceil(n/2) + 2 pairs over the three lists
-                hipLaunchKernelGGL(k_viterbi, dim3((nrows / 2 + 3 + 3) / 4), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, 0u, nrows,
-                        (const uint8_t*)rx->d_soft, rx->d_vout);
+                hipLaunchKernelGGL(k_viterbi, dim3(pair_groups), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, 0u, nrows,
+                                   (const uint8_t*)rx->d_soft, rx->d_vout);
             if (rx->ordered && !recording && rx->ev_trellis) (void)hipEventRecord(rx->ev_trellis, st);
             mark();
-            }
         }
-        // (behind the window-parallel trellis the proof, the decode of what fails it and T11aDesc
-        // / the frame sink are ONE launch: the wave that holds a pair of frames finishes them)
-        if (redo_finish && pipe)                                                 // (behind k_pipe: ... and the plain chain's code for the whole call if a wait inside k_pipe gave up)
-            hipLaunchKernelGGL(k_win_redo_finish_pipe, dim3((nrows / 2 + 3 + 3) / 4), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, nrows,
-                    kWinUnitsTarget, rx->wstride,
-                               (const uint16_t*)rx->d_wvecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wstats, R, rx->d_note);
+
+        // the finish (behind k_pipe: ... and the plain chain's code for the whole call if a wait inside k_pipe gave up)
+        if (redo_finish && pipe)
+            hipLaunchKernelGGL(k_win_redo_finish_pipe, dim3(pair_groups), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, nrows, kWinUnitsTarget,
+                               rx->wstride, (const uint16_t*)rx->d_wvecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wstats, R, rx->d_note);
         else if (redo_finish)
-            hipLaunchKernelGGL(k_win_redo_finish, dim3((nrows / 2 + 3 + 3) / 4), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, nrows,
-                    kWinUnitsTarget, rx->wstride,
-                               (const uint16_t*)rx->d_wvecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wstats, R);
+            hipLaunchKernelGGL(k_win_redo_finish, dim3(pair_groups), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, nrows, kWinUnitsTarget,
+                               rx->wstride, (const uint16_t*)rx->d_wvecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wstats, R);
         else if (RX_ONLY(rx, 8u)) hipLaunchKernelGGL(k_finish, dim3((nrows + 3) / 4), dim3(256), 0, st, R);
 #ifdef SORA_TOOLS
         for (unsigned x = 0; x < rx->extra; x++) hipLaunchKernelGGL(k_clear16, dim3(1), dim3(256), 0, st, reinterpret_cast<uint4*>(rx->d_njobs), 0u);
@@ -1090,7 +1055,6 @@ struct sora_rx {
     int cur = 0;                 // pipeline of the most recent process call
     bool started = false;
     bool profiling = false;
-    bool fused = false;
     int seq = 0;                 // ticket of the most recent process call
     RxPipe* pipes[kMaxDepth] = {};
     // stream mode (sora_rx_set_stream_mode): capture k of a call continues capture k of the call before it
@@ -1158,7 +1122,7 @@ static RxPipe* pipe_at(sora_rx* rx, int i)
 {
     if (!rx->pipes[i]) {
         if (pipe_create(&rx->cfg, &rx->pipes[i], i) != SORA_OK) return nullptr;
-        rx->pipes[i]->fused = rx->fused; rx->pipes[i]->use_graph = rx->use_graph;
+        rx->pipes[i]->use_graph = rx->use_graph;
         if (rx->profiling) (void)pipe_set_profiling(rx->pipes[i], 1);
         rx->pipes[i]->tl = &rx->tl; rx->pipes[i]->tl_base = &rx->tl_base; rx->pipes[i]->index = i;
         rx->pipes[i]->d_note = rx->d_note;
@@ -1175,7 +1139,7 @@ int sora_rx_create(const sora_rx_cfg* cfg, sora_rx_t** out)
     const int rc = pipe_create(cfg, &p0);
     if (rc != SORA_OK) return rc;
     sora_rx* rx = new sora_rx();
-    rx->cfg = *cfg; rx->pipes[0] = p0; rx->fused = p0->fused;
+    rx->cfg = *cfg; rx->pipes[0] = p0;
     // (host-mapped, written by k_win_redo_finish_pipe; without it the safety net still works, the handle just does not learn from it)
     if (hipHostMalloc((void**)&rx->h_note, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer((void**)&rx->d_note, rx->h_note, 0) == hipSuccess) *rx->h_note = 0;
     else { (void)hipGetLastError(); if (rx->h_note) (void)hipHostFree(rx->h_note); rx->h_note = rx->d_note = nullptr; }
@@ -1197,19 +1161,12 @@ void sora_rx_destroy(sora_rx_t* rx)
     delete rx;
 }
 
+// k_decode (the data field in one kernel) has been removed: the switch stays in the ABI, always off
 int sora_rx_set_fused(sora_rx_t* rx, int enable)
 {
     if (!rx) return SORA_ERR_INVALID_PARAM;
-    const int old = rx->fused ? 1 : 0;
-#ifndef SORA_WITH_K_DECODE
-    if (enable > 0) return fail(SORA_E_NOT_SUPPORTED, "sora_rx_set_fused: k_decode is not part of this build of the library "
-                                                      "(a build variant since round 4: sora_amd.build.build_variant(\"fused\", [\"SORA_WITH_K_DECODE\"]))");
-#endif
-    if (enable >= 0) {
-        rx->fused = enable != 0;
-        for (RxPipe* p : rx->pipes) if (p) { p->fused = rx->fused; p->last_valid = false; }      // (a recorded hipGraph holds the other kernel chain)
-    }
-    return old;
+    if (enable > 0) return fail(SORA_E_NOT_SUPPORTED, "sora_rx_set_fused: k_decode has been removed from the library");
+    return 0;
 }
 
 // Which trellis kernel a call uses: k_viterbi16 pays off once enough frames are in flight to give every SIMD a wave of it (it packs
@@ -1241,8 +1198,7 @@ static uint64_t pipe_groups(const sora_rx* rx, bool lanes64)                   /
 {
     const uint64_t str = rx->cfg.sample_rate_mhz == 20 ? 1 : 2, rows = (uint64_t)rx->cfg.max_captures * rx->cfg.max_frames_per_capture;
     const uint64_t slots = rx->cfg.max_total_samples / str / 80 + rx->cfg.max_captures + 16;
-    const uint64_t units = std::min<uint64_t>(std::max<uint64_t>(kWinUnitsTarget, rows), 80ull * rows);
-    const uint64_t waves = lanes64 ? (uint64_t)kWinMaxUnits * ((rows + 3) / 2) : (units + 7) / 8 + 3 + kWinLoneWaves;
+    const uint64_t waves = lanes64 ? (uint64_t)kWinMaxUnits * ((rows + 3) / 2) : win_waves(rows);
     return (slots + 63) / 64 + rows + (waves + 3) / 4;
 }
 // frame rows in flight up to which the automatic choice is k_pipe
@@ -1531,14 +1487,6 @@ SORA_TOOL_HOOK int sora_internal_rx_only(sora_rx_t* rx, unsigned mask)
 {
     if (!rx) return SORA_ERR_INVALID_PARAM;
     for (int i = 0; i < sora_rx::kMaxDepth; i++) { RxPipe* p = pipe_at(rx, i); if (p) { p->only = mask & 0xFu; p->last_valid = false; } if (i + 1 >= rx->depth) break; }
-    return SORA_OK;
-}
-
-// Test / tool hook: 0 = the plain k_viterbi16w in front of k_win_redo_finish (round 5's chain) instead of k_viterbi16w_fin -- for A/B timing (tools/r06_lone_call_timeline.py)
-SORA_TOOL_HOOK int sora_internal_rx_unit_finish(sora_rx_t* rx, int on)
-{
-    if (!rx) return SORA_ERR_INVALID_PARAM;
-    for (int i = 0; i < rx->depth; i++) { RxPipe* p = pipe_at(rx, i); if (p) { p->unit_finish = on != 0; p->last_valid = false; } }
     return SORA_OK;
 }
 
