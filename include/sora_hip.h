@@ -365,6 +365,22 @@ size_t sora_hip_tx11a_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps);
 int sora_hip_tx11a(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps,
                    const uint8_t* d_seed, size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream);
 
+/* 802.11n 2x2 transmitter: the reference's modulation graphs CreatePreambleGraph11n + CreateSigGraph11n + CreateModGraph11n
+ * (kernel/bb/demod11/fb11nmod_config.hpp) as Test11N_FB_Mod runs them (fb11n_mod.cpp:28-70): L-STF, L-LTF, L-SIG, HT-SIG, HT-STF,
+ * HT-LTF1, HT-LTF2, data; 20 MHz, long GI, MCS 8..14 (two spatial streams, one per TX chain), a batch of frames per call.
+ * Frame f: MPDU WITHOUT FCS (the FCS is appended) of d_len[f] bytes at d_mpdu + d_off[f], MCS d_mcs[f], scrambler seed d_seed[f]
+ * (d_seed NULL: 0xAB for every frame, what the reference harness uses, fb11nmod_config.hpp:51).  Writes sora_hip_tx11n_samples(len,
+ * mcs) COMPLEX16 samples at 40 MHz per chain -- what the graph's sinks receive, GetSinkSampleCount(), without the 32 extra samples
+ * fb11n_mod.cpp writes to its files -- at sample d_out_off[f] of d_out0 (TX chain 0) and of d_out1 (TX chain 1).
+ * Accepted: MCS 8..14 and 1..4092 bytes without FCS; sora_hip_tx11n_samples is 0 for anything else (MCS 15 is routed to TDropAny by
+ * the reference: no frame).  The MCS and length arrays are device memory: a frame whose MCS or length is not accepted gets nothing
+ * written to its output range, and the other frames of the call are not affected.
+ * The sample count follows the reference, not the standard: the data field has one symbol more than the standard's N_SYM whenever
+ * N_SYM x N_DBPS is not a multiple of 8 (MCS 8, 10 and 14; ht_padding_bytes rounds the padded field up to whole bytes). */
+size_t sora_hip_tx11n_samples(uint32_t mpdu_len_nofcs, uint32_t mcs);
+int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
+                   size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 802.11n 2x2, stage level (the whole-path graph is sora_rx11n_* below).  Batched bricks, n symbols per call:
  * T11nDemap{BPSK,QPSK,QAM16,QAM64} (kernel/bb/Brick11/src/demapper11n.hpp:89-309): IPORT COMPLEX16 x 64 (one pilot-tracked

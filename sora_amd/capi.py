@@ -61,7 +61,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_rx_kernel_name_fused", "sora_hip_fft64", "sora_hip_fft128", "sora_hip_lts11a", "sora_hip_symfront11a", "sora_hip_pilot_track11a", "sora_hip_pilot11a",
                       "sora_hip_freq_comp11a", "sora_hip_equalize11a", "sora_hip_phase_comp11a", "sora_hip_demap11a", "sora_hip_deinterleave11a", "sora_hip_viterbi11a",
                       "sora_hip_viterbi11a_ws", "sora_hip_viterbi11a_workspace_bytes",
-           "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples",
+           "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11n", "sora_hip_tx11n_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n", "sora_rx11b_create",
                       "sora_rx11b_destroy", "sora_rx11b_stream", "sora_rx11b_synchronize", "sora_rx11b_process_dev", "sora_rx11b_process", "sora_rx11b_results", "sora_rx11b_ticket",
@@ -222,6 +222,8 @@ def load(build_if_missing=True):
     L.sora_hip_stream_synchronize.argtypes = [ctypes.c_void_p]
     L.sora_hip_tx11a_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11a_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.sora_hip_tx11n_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11n_samples.restype = ctypes.c_size_t
+    L.sora_hip_tx11n.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
     L.sora_hip_ingest_count.argtypes = [ctypes.c_size_t, ctypes.c_uint]; L.sora_hip_ingest_count.restype = ctypes.c_size_t
     L.sora_hip_ingest.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t,
                                   ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
@@ -1151,3 +1153,41 @@ def tx11a(mpdus, rates_kbps, seeds=None, device=0, stream=None, sync=True, gaps=
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     return out, [int(v) for v in ooff]
+
+
+def tx11n_samples(mpdu_len_nofcs, mcs):
+    """Samples per TX chain of one 802.11n 2x2 frame (sora_hip_tx11n_samples); 0 for an unsupported MCS or length."""
+    return int(load().sora_hip_tx11n_samples(int(mpdu_len_nofcs), int(mcs)))
+
+
+def tx11n(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None):
+    """Modulate a batch of MPDUs (bytes WITHOUT FCS) as 802.11n 2x2 frames on the GPU (MCS 8..14).
+    -> (out0, out1, offsets): int16 CUDA tensors [total,2] COMPLEX16 @40 MHz for TX chains 0 and 1, and the offsets list.
+    Frame f occupies samples offsets[f] .. offsets[f+1] of both (gaps[f] zero samples in front of frame f, if given, included at its start).
+    seeds: scrambler seeds (None: 0xAB, the reference harness's).  A frame with an unsupported MCS or length is refused before any launch."""
+    import torch
+    n = len(mpdus)
+    mcs = [int(m) for m in mcs] if np.ndim(mcs) else [int(mcs)] * n
+    lens = [len(m) for m in mpdus]
+    ns = [tx11n_samples(l, m) for l, m in zip(lens, mcs)]
+    if len(mcs) != n or any(v == 0 for v in ns):
+        raise SoraError(-1, "tx11n: unsupported MCS or length (MCS 8..14, 1..4092 bytes)")
+    off = np.zeros(n + 1, np.int64); np.cumsum([(l + 3) // 4 * 4 for l in lens], out=off[1:])
+    blob = np.zeros(max(int(off[-1]), 4), np.uint8)
+    for f, m in enumerate(mpdus):
+        blob[off[f]:off[f] + lens[f]] = np.frombuffer(bytes(m), np.uint8)
+    gaps = [0] * n if gaps is None else [int(v) for v in gaps]
+    ooff = np.zeros(n + 1, np.uint64); np.cumsum([a + b for a, b in zip(ns, gaps)], out=ooff[1:])
+    first = ooff[:-1] + np.asarray(gaps, np.uint64)
+    dev = torch.device("cuda", device)
+    d_blob = torch.from_numpy(blob).to(dev); d_off = torch.from_numpy(off[:-1].astype(np.int32)).to(dev)
+    d_len = torch.from_numpy(np.asarray(lens, np.int32)).to(dev); d_mcs = torch.from_numpy(np.asarray(mcs, np.int32)).to(dev)
+    d_seed = torch.from_numpy(np.asarray(seeds, np.uint8)).to(dev) if seeds is not None else None
+    d_ooff = torch.from_numpy(first.astype(np.int64)).to(dev)
+    out0 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
+    out1 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
+    _check(load().sora_hip_tx11n(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
+                                 _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
+    if sync:
+        _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
+    return out0, out1, [int(v) for v in ooff]

@@ -11,21 +11,13 @@
 // One 256-thread block per frame; eight OFDM symbols per pass, 32 lanes each (IFFT<128>: 4 points per lane).
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "dev_tx.h"
 
 namespace sora {
 
 __device__ __constant__ uint8_t kLtsPos[64] = {              // LTS_Positive_table (ieee80211const.h:23-28)
     0,1,0,0,1,1,0,1,0,1,0,0,0,0,0,1, 1,0,0,1,0,1,0,1,1,1,1,0,0,0,0,0,
     0,0,0,0,0,0,1,1,0,0,1,1,0,1,0,1, 1,1,1,1,1,0,0,1,1,0,1,0,1,1,1,1 };
-constexpr uint8_t kPilotSgnTx[128] = {         // pilot.hpp:10-28: 1 <=> polarity -1
-    0,0,0,1,1,1,0,1, 1,1,1,0,0,1,0,1, 1,0,0,1,0,0,1,0, 0,0,0,0,0,1,0,0,
-    0,1,0,0,1,1,0,0, 0,1,0,1,1,1,0,1, 0,1,1,0,1,1,0,0, 0,0,0,1,1,0,0,1,
-    1,0,1,0,1,0,0,1, 1,1,0,0,1,1,1,1, 0,1,1,0,1,0,0,0, 0,1,0,1,0,1,0,1,
-    1,1,1,1,0,1,0,0, 1,0,1,0,0,0,1,1, 0,1,1,1,0,0,0,1, 1,1,1,1,1,1,0,0 };
-
-constexpr uint32_t pilot_word(int w) { uint32_t v = 0; for (int j = 0; j < 32; j++) v |= (uint32_t)kPilotSgnTx[32 * w + j] << j; return v; }   // bit n of word n >> 5 = kPilotSgnTx[n]
-constexpr uint32_t kPilotW0 = pilot_word(0), kPilotW1 = pilot_word(1), kPilotW2 = pilot_word(2), kPilotW3 = pilot_word(3);
-static_assert(kPilotW0 == 0x2049a7b8u && kPilotW3 == 0x3f8ec52fu, "pilot polarity words");
 constexpr int kBpskMod = 10720;                              // mapper11a.hpp:8-11
 __device__ __forceinline__ int kmod_of(int nb) { return nb == 1 ? kBpskMod : nb == 2 ? (int)(kBpskMod / 1.414) : nb == 4 ? (int)(kBpskMod / 3.162) : (int)(kBpskMod / 6.481); }
 __device__ __forceinline__ int sat8(int v) { return min(max(v, -128), 127); }          // _mm_packs_epi16 (stdbrick.hpp:430)

@@ -129,6 +129,46 @@ struct TxArgs {                // sora_hip_tx11a (k_tx.hip)
 };
 __global__ void k_tx_preamble(int8_t* out8, Tables T);
 __global__ void k_tx11a(TxArgs A);
+
+// ---- 802.11n 2x2 transmitter (k_tx11n.hip)
+struct Tx11nArgs {             // sora_hip_tx11n
+    const uint8_t*  mpdu;      // MPDUs without FCS, frame f at mpdu + off[f]
+    const uint32_t* off;
+    const uint32_t* len;       // bytes without FCS (HT LENGTH = len + 4)
+    const uint32_t* mcs;       // 8..14
+    const uint8_t*  seed;      // scrambler register before the first byte; nullptr: 0xAB for every frame (fb11nmod_config.hpp:51)
+    uint32_t*       out0;      // packed COMPLEX16, TX chain 0
+    uint32_t*       out1;      // TX chain 1
+    const uint64_t* out_off;   // first sample of frame f in both streams
+    const uint32_t* preamble;  // [2][1120]: per chain L-STF, L-LTF (640) then HT-STF, HT-LTF1, HT-LTF2 (480)
+    Tables          T;
+};
+// The frame geometry the reference's data graph produces (PHY_11n.hpp:15-150, ieee80211n_cmn.h:34-55, pinqueue.h:133-147).
+// TBB11nSrc emits nbytes = ceil(nstd * NDBPS / 8) bytes (nstd: the standard's symbol count); on Flush every pipe pads its
+// last burst with zeros -- the encoder's input to a whole group (1, 2 or 3 bytes for rate 1/2, 2/3, 3/4), the stream parser's
+// input to a whole symbol -- so the field carries nvalid input bits and nsym = ceil(coded bytes / 13 N_BPSC) symbols, one more
+// than nstd whenever nstd * NDBPS is not a multiple of 8 (MCS 8, 10 and 14 with odd nstd).
+struct Tx11nPlan { int nb, cr, ndbps; uint32_t nstd, nbytes, nvalid, nsym; };
+__host__ __device__ inline bool tx11n_plan(uint32_t len, uint32_t mcs, Tx11nPlan& P)
+{
+    if (len < 1 || len > 4092) return false;
+    switch (mcs) {                                       // DOT11N_RATE_PARAMS, BB11nGetCodingRateFromMcsIndex; cr: 0 = 1/2, 1 = 2/3, 2 = 3/4
+    case 8:  P.nb = 1; P.cr = 0; P.ndbps = 52;  break;  case 9:  P.nb = 2; P.cr = 0; P.ndbps = 104; break;
+    case 10: P.nb = 2; P.cr = 2; P.ndbps = 156; break;  case 11: P.nb = 4; P.cr = 0; P.ndbps = 208; break;
+    case 12: P.nb = 4; P.cr = 2; P.ndbps = 312; break;  case 13: P.nb = 6; P.cr = 1; P.ndbps = 416; break;
+    case 14: P.nb = 6; P.cr = 2; P.ndbps = 468; break;
+    default: return false;                               // MCS 15 goes to TDropAny: no frame
+    }
+    const uint32_t nd = (uint32_t)P.ndbps, gin = (uint32_t)P.cr + 1, gout = (uint32_t)P.cr + 2;
+    P.nstd = ((len + 4) * 8 + 16 + 6 + nd - 1) / nd;     // SERVICE 16 bits, tail 6 bits
+    P.nbytes = (P.nstd * nd + 7) / 8;
+    const uint32_t ngroups = (P.nbytes + gin - 1) / gin;
+    P.nvalid = 8 * gin * ngroups;
+    P.nsym = (gout * ngroups + 13 * (uint32_t)P.nb - 1) / (13 * (uint32_t)P.nb);
+    return true;
+}
+constexpr uint32_t kTx11nPreamble = 1120;                // samples per chain of the table: L-STF + L-LTF + HT-STF + 2 HT-LTF
+__global__ void k_tx11n(Tx11nArgs A);
 __global__ void k_ingest(const uint8_t* raw, uint32_t* out, uint64_t m0, uint64_t n_out, unsigned flags);
 __global__ void k_ingest_tile(const uint8_t* raw, uint32_t* out, unsigned flags, uint32_t tiles);
 __global__ void k_soft_pack3(const uint8_t* soft8, const uint32_t* off8, const uint32_t* nsoft, const uint16_t* flen, const uint32_t* out_off,

@@ -324,6 +324,7 @@ struct DevTables {
     std::vector<void*> allocs;
     int device = -1;
     int8_t* tx_preamble = nullptr;      // 640 COMPLEX8 samples (k_tx_preamble), built on first use of the transmitter
+    uint32_t* tx11n_preamble = nullptr; // [2][1120] COMPLEX16 (tx11n_preamble_host), built on first use of the 802.11n transmitter
 };
 
 template <typename V>
@@ -1815,6 +1816,84 @@ int sora_hip_tx11a(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t*
     A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.rate = d_rate_kbps; A.seed = d_seed; A.out8 = d_out; A.out_off = d_out_off;
     A.preamble = D->tx_preamble; A.T = D->T;
     hipLaunchKernelGGL(k_tx11a, dim3((unsigned)nframes), dim3(256), 0, st, A);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+// ---- 802.11n 2x2 transmitter
+// The fixed fields of LSrc / HTSrc (preamble11n.hpp:8-83), per chain: L-STF (320), L-LTF (320), HT-STF, HT-LTF1, HT-LTF2 (160 each).
+// Each is round(s * sum_k X_k exp(+2 pi i k n / 128)) in double precision -- the standard's frequency-domain sequence X in bins -26..26
+// (-28..28 for the HT-LTF) of a 128-point grid, no 1/128 -- repeated or cyclically extended, chain 1 delayed circularly by 8 samples
+// (L fields) or 16 (HT fields), HT-LTF2 negated on chain 0 (the 2x2 P matrix).  The scales are fitted to the reference modulator's
+// output (tests/golden/refgraph_11n.npz, the first 640 and the 480 from sample 1120 on, both chains, all four frames) and reproduce
+// it exactly inside these intervals:
+//   L-STF, HT-STF: s = 256 sqrt(2) = 362.039 (exact for s in [361.982, 362.095])
+//   L-LTF: s = K / sqrt(52), HT-LTF: s = K / sqrt(56), K = 1773.7209 (exact for K in [1773.7204, 1773.7213], both LTFs together)
+static void tx11n_preamble_host(std::vector<uint32_t>& tab)
+{
+    static const int kLtf[53] = { 1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 0,
+                                  1, -1, -1, 1, 1, -1, 1, -1, 1, -1, -1, -1, -1, -1, 1, 1, -1, -1, 1, -1, 1, -1, 1, 1, 1, 1 };
+    static const int kStf[13] = { 1, -1, 1, -1, -1, 1, 0, -1, -1, 1, 1, 1, 1 };        // x (1 + j) on carriers -24, -20, .., 24
+    const double K = 1773.7209, pi = 3.14159265358979323846;
+    std::vector<double> Xr(128 * 3, 0.0), Xi(128 * 3, 0.0);                                // 0: STF, 1: L-LTF, 2: HT-LTF
+    for (int i = 0; i < 13; i++) { const int b = (4 * i - 24) & 127; Xr[b] = kStf[i]; Xi[b] = kStf[i]; }
+    for (int i = 0; i < 53; i++) Xr[128 + ((i - 26) & 127)] = kLtf[i];
+    for (int i = 0; i < 57; i++) Xr[256 + ((i - 28) & 127)] = i < 2 ? 1 : i > 54 ? -1 : kLtf[i - 2];
+    const double scale[3] = { 256.0 * std::sqrt(2.0), K / std::sqrt(52.0), K / std::sqrt(56.0) };
+    int16_t t[3][128][2];
+    for (int f = 0; f < 3; f++)
+        for (int n = 0; n < 128; n++) {
+            double re = 0, im = 0;
+            for (int k = 0; k < 128; k++) {
+                if (Xr[128 * f + k] == 0 && Xi[128 * f + k] == 0) continue;
+                const double c = std::cos(2 * pi * k * n / 128), sn = std::sin(2 * pi * k * n / 128);
+                re += Xr[128 * f + k] * c - Xi[128 * f + k] * sn; im += Xr[128 * f + k] * sn + Xi[128 * f + k] * c;
+            }
+            t[f][n][0] = (int16_t)std::llround(scale[f] * re); t[f][n][1] = (int16_t)std::llround(scale[f] * im);
+        }
+    auto word = [&](int f, int n, int sign) { return (uint32_t)(uint16_t)(sign * t[f][n & 127][0]) | ((uint32_t)(uint16_t)(sign * t[f][n & 127][1]) << 16); };
+    tab.assign(2 * kTx11nPreamble, 0);
+    for (int ch = 0; ch < 2; ch++) {
+        uint32_t* o = tab.data() + ch * kTx11nPreamble;
+        const int dl = 8 * ch, dh = 16 * ch;                                              // TCSD: 200 ns / 400 ns at 40 MHz
+        for (int n = 0; n < 320; n++) o[n] = word(0, n - dl, 1);                          // L-STF
+        for (int n = 0; n < 320; n++) o[320 + n] = word(1, n - 64 - dl, 1);               // L-LTF: GI2 of 64, two symbols
+        for (int n = 0; n < 160; n++) o[640 + n] = word(0, n - 32 - dh, 1);               // HT-STF
+        for (int n = 0; n < 160; n++) o[800 + n] = word(2, n - 32 - dh, 1);               // HT-LTF1
+        for (int n = 0; n < 160; n++) o[960 + n] = word(2, n - 32 - dh, ch ? 1 : -1);     // HT-LTF2
+    }
+}
+
+size_t sora_hip_tx11n_samples(uint32_t mpdu_len_nofcs, uint32_t mcs)
+{
+    Tx11nPlan P;
+    if (!tx11n_plan(mpdu_len_nofcs, mcs, P)) return 0;
+    return 1600 + 160 * (size_t)P.nsym;
+}
+
+int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
+                   size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
+{
+    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
+    if (!d_mpdu || !d_off || !d_len || !d_mcs || !d_out0 || !d_out1 || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_tx11n: null pointer");
+    if (nframes == 0) return SORA_OK;
+    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    {
+        std::lock_guard<std::mutex> lock(g_stage_mutex);                          // built once per device, complete before it is published
+        if (!D->tx11n_preamble) {
+            std::vector<uint32_t> tab; tx11n_preamble_host(tab);
+            uint32_t* p = nullptr;
+            HIPCHK(hipMalloc((void**)&p, tab.size() * sizeof(uint32_t)));
+            const hipError_t e = hipMemcpy(p, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+            if (e != hipSuccess) { (void)hipFree(p); return fail(SORA_ERR_HARDWARE_FAILED, "tx11n preamble upload", e); }
+            D->tx11n_preamble = p; D->allocs.push_back(p);
+        }
+    }
+    Tx11nArgs A{};
+    A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.mcs = d_mcs; A.seed = d_seed;
+    A.out0 = reinterpret_cast<uint32_t*>(d_out0); A.out1 = reinterpret_cast<uint32_t*>(d_out1); A.out_off = d_out_off;
+    A.preamble = D->tx11n_preamble; A.T = D->T;
+    hipLaunchKernelGGL(k_tx11n, dim3((unsigned)nframes), dim3(256), 0, (hipStream_t)stream, A);
     HIPCHK(hipGetLastError());
     return SORA_OK;
 }

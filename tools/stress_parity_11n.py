@@ -1,6 +1,8 @@
 """GPU (sora_rx11n_*) against the CPU oracle on many random two-chain 802.11n captures built from the recorded waveforms of the
 reference modulator (tests/golden/refgraph_11n.npz): decoded frames, FCS failures, header failures (MCS 12), frames cut by the end
-of the capture, several frames per capture.  usage: python tools/stress_parity_11n.py [captures] [seed] [trellis: 64 | 16 | 1 | 0]"""
+of the capture, several frames per capture.  usage: python tools/stress_parity_11n.py [captures] [seed] [trellis: 64 | 16 | 1 | 0] [--gpu-tx]
+--gpu-tx: the captures are built from fresh frames of the GPU transmitter (sora_amd.tx11n: random MCS 8..14, lengths and scrambler
+seeds) instead of the recorded waveforms and the compiled reference modulator's frames."""
 import os
 import sys
 import time
@@ -16,14 +18,23 @@ from oracle.pyoracle import Oracle  # noqa: E402
 def main():
     import torch
     import sora_amd
-    ncap = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    z = np.load(os.path.join(ROOT, "tests", "golden", "refgraph_11n.npz"))
-    frames = [(z["tx%d_0" % i], z["tx%d_1" % i]) for i in range(4)]
+    gpu_tx = "--gpu-tx" in sys.argv
+    argv = [sys.argv[0]] + [a for a in sys.argv[1:] if a != "--gpu-tx"]
+    ncap = int(argv[1]) if len(argv) > 1 else 2000
+    seed = int(argv[2]) if len(argv) > 2 else 1
     rng = np.random.default_rng(seed); o = Oracle()
+    if gpu_tx:                                                              # one call of the GPU transmitter: 64 fresh frames
+        mcs = [int(v) for v in rng.integers(8, 15, 64)]
+        lens = [int(rng.integers(1, 1497)) if rng.integers(0, 3) else int(rng.integers(1, 60)) for _ in range(64)]
+        o0, o1, fo = sora_amd.tx11n([rng.integers(0, 256, n).astype(np.uint8).tobytes() for n in lens], mcs, [int(v) for v in rng.integers(1, 128, 64)])
+        a0, a1 = o0.cpu().numpy(), o1.cpu().numpy()
+        frames = [(a0[fo[i]:fo[i + 1]], a1[fo[i]:fo[i + 1]]) for i in range(64)]
+    else:
+        z = np.load(os.path.join(ROOT, "tests", "golden", "refgraph_11n.npz"))
+        frames = [(z["tx%d_0" % i], z["tx%d_1" % i]) for i in range(4)]
     from oracle.pyoracle import ReferenceGraph
     g = ReferenceGraph()
-    if g.available():                                                       # the compiled reference modulator: fresh frames of any length
+    if g.available() and not gpu_tx:                                        # the compiled reference modulator: fresh frames of any length
         for _ in range(36):
             mcs = int(rng.choice([8, 9, 10, 10, 12])); ln = int(rng.integers(1, 1497)) if rng.integers(0, 3) else int(rng.integers(1, 60))
             frames.append(g.tx11n(rng.integers(0, 256, ln).astype(np.uint8).tobytes(), mcs))
@@ -36,8 +47,8 @@ def main():
     for i, (a, _) in enumerate(caps):
         descs.append((off, len(a), i)); off += len(a)
     rx = sora_amd.Rx11n(ncap, len(iq0), max_frames_per_capture=8)
-    if len(sys.argv) > 3:                                                  # trellis kernel: 64, 16, 1 (the window-parallel form, round 6), 0 = automatic
-        rx.set_trellis(int(sys.argv[3]))
+    if len(argv) > 3:                                                      # trellis kernel: 64, 16, 1 (the window-parallel form, round 6), 0 = automatic
+        rx.set_trellis(int(argv[3]))
     t0 = time.perf_counter()
     rx.process_dev(torch.from_numpy(iq0).cuda(), torch.from_numpy(iq1).cuda(), descs)
     per = [[] for _ in caps]
