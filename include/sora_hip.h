@@ -381,6 +381,26 @@ size_t sora_hip_tx11n_samples(uint32_t mpdu_len_nofcs, uint32_t mcs);
 int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
                    size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
 
+/* 802.11b transmitter: the reference's modulation graph CreateModGraph (kernel/bb/demod11/fb11bmod_config.hpp:28-50) as
+ * Test11B_FB_Mod runs it (fb11b_mod.cpp:40-70): long preamble (SYNC, SFD), PLCP header, MPDU + FCS at 1, 2, 5.5 or 11 Mbps, Barker
+ * DBPSK / DQPSK or CCK, TQuickPulseShaper; a batch of frames per call.
+ * Frame f: MPDU WITHOUT FCS (the FCS is appended) of d_len[f] bytes at d_mpdu + d_off[f], rate d_rate_kbps[f] (1000, 2000, 5500 or
+ * 11000).  Writes sora_hip_tx11b_samples(len, rate) COMPLEX8 samples at 44 MHz -- what TModSink receives, tx_sample_cnt() -- at sample
+ * d_out_off[f] of d_out (64-bit offsets: a batch may exceed 2^31 samples).
+ * Accepted: those four rates and 1..4092 bytes without FCS; sora_hip_tx11b_samples is 0 for anything else (the short preamble is not
+ * offered: the reference refuses it).  The rate and length arrays are device memory: a frame whose rate or length is not accepted gets
+ * nothing written (its output range and d_phase_out[f] stay as they are), and the other frames of the call are not affected.
+ * Differential phase: the reference's four spreaders share CF_DifferentialMap::last_phase (0: 0, 1: -pi/2, 2: pi/2, 3: pi), and no
+ * reset touches it, so one reference process carries it from frame to frame; the preamble reads only its low bit, so a frame comes out
+ * as W or -W.  d_phase_in[f] is last_phase when frame f starts (d_phase_in NULL: 0, a fresh reference process); d_phase_out, if not
+ * NULL, receives last_phase after frame f.  Frames of one call are independent: a host chains calls by passing d_phase_out back as
+ * d_phase_in.  Sample count: 192 x 44 + (len + 4) x S + 24, S = 352, 176, 64, 32 samples a byte at 1, 2, 5.5, 11 Mbps; the 24
+ * are the shaper's five flush steps and TPackSample16to8's padding of its last burst. */
+size_t sora_hip_tx11b_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps);
+int sora_hip_tx11b(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps,
+                   const uint8_t* d_phase_in, uint8_t* d_phase_out, size_t nframes,
+                   int8_t* d_out, const uint64_t* d_out_off, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 802.11n 2x2, stage level (the whole-path graph is sora_rx11n_* below).  Batched bricks, n symbols per call:
  * T11nDemap{BPSK,QPSK,QAM16,QAM64} (kernel/bb/Brick11/src/demapper11n.hpp:89-309): IPORT COMPLEX16 x 64 (one pilot-tracked

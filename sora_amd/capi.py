@@ -61,7 +61,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_rx_kernel_name_fused", "sora_hip_fft64", "sora_hip_fft128", "sora_hip_lts11a", "sora_hip_symfront11a", "sora_hip_pilot_track11a", "sora_hip_pilot11a",
                       "sora_hip_freq_comp11a", "sora_hip_equalize11a", "sora_hip_phase_comp11a", "sora_hip_demap11a", "sora_hip_deinterleave11a", "sora_hip_viterbi11a",
                       "sora_hip_viterbi11a_ws", "sora_hip_viterbi11a_workspace_bytes",
-           "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11n", "sora_hip_tx11n_samples",
+           "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx11b",
+           "sora_hip_tx11b_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n", "sora_rx11b_create",
                       "sora_rx11b_destroy", "sora_rx11b_stream", "sora_rx11b_synchronize", "sora_rx11b_process_dev", "sora_rx11b_process", "sora_rx11b_results", "sora_rx11b_ticket",
@@ -224,6 +225,8 @@ def load(build_if_missing=True):
     L.sora_hip_tx11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.sora_hip_tx11n_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11n_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11n.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
+    L.sora_hip_tx11b_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11b_samples.restype = ctypes.c_size_t
+    L.sora_hip_tx11b.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
     L.sora_hip_ingest_count.argtypes = [ctypes.c_size_t, ctypes.c_uint]; L.sora_hip_ingest_count.restype = ctypes.c_size_t
     L.sora_hip_ingest.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t,
                                   ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
@@ -1191,3 +1194,53 @@ def tx11n(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None):
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     return out0, out1, [int(v) for v in ooff]
+
+
+TX11B_RATES = (1000, 2000, 5500, 11000)
+
+
+def tx11b_samples(mpdu_len_nofcs, rate_kbps):
+    """Samples of one 802.11b frame (sora_hip_tx11b_samples); 0 for an unsupported rate or length."""
+    return int(load().sora_hip_tx11b_samples(int(mpdu_len_nofcs), int(rate_kbps)))
+
+
+def tx11b(mpdus, rates_kbps, phase_in=None, device=0, stream=None, sync=True, gaps=None, return_phase=False):
+    """Modulate a batch of MPDUs (bytes WITHOUT FCS) as 802.11b frames on the GPU (1000, 2000, 5500, 11000 kbps, long preamble).
+    -> (out, offsets): an int8 CUDA tensor [total,2] COMPLEX8 @44 MHz and the offsets list; frame f occupies samples offsets[f] ..
+    offsets[f+1] (gaps[f] zero samples in front of frame f, if given, included at its start).
+    phase_in: the reference's last_phase (0..3) at the start of each frame, one value or one per frame (None: 0, a fresh reference
+    process).  return_phase: also return last_phase after each frame, a list -- pass it back as phase_in to continue one reference
+    process's sequence.  A frame with an unsupported rate or length is refused before any launch."""
+    import torch
+    n = len(mpdus)
+    rates = [int(r) for r in rates_kbps] if np.ndim(rates_kbps) else [int(rates_kbps)] * n
+    lens = [len(m) for m in mpdus]
+    ns = [tx11b_samples(l, r) for l, r in zip(lens, rates)]
+    if len(rates) != n or any(v == 0 for v in ns):
+        raise SoraError(-1, "tx11b: unsupported rate or length (1000/2000/5500/11000 kbps, 1..4092 bytes)")
+    if phase_in is not None:
+        phase_in = [int(p) for p in phase_in] if np.ndim(phase_in) else [int(phase_in)] * n
+        if len(phase_in) != n or any(not 0 <= p <= 3 for p in phase_in):
+            raise SoraError(-1, "tx11b: phase_in must hold one value 0..3 per frame")
+    off = np.zeros(n + 1, np.int64); np.cumsum([(l + 3) // 4 * 4 for l in lens], out=off[1:])
+    blob = np.zeros(max(int(off[-1]), 4), np.uint8)
+    for f, m in enumerate(mpdus):
+        blob[off[f]:off[f] + lens[f]] = np.frombuffer(bytes(m), np.uint8)
+    gaps = [0] * n if gaps is None else [int(v) for v in gaps]
+    ooff = np.zeros(n + 1, np.uint64); np.cumsum([a + b for a, b in zip(ns, gaps)], out=ooff[1:])
+    first = ooff[:-1] + np.asarray(gaps, np.uint64)
+    dev = torch.device("cuda", device)
+    d_blob = torch.from_numpy(blob).to(dev); d_off = torch.from_numpy(off[:-1].astype(np.int32)).to(dev)
+    d_len = torch.from_numpy(np.asarray(lens, np.int32)).to(dev); d_rate = torch.from_numpy(np.asarray(rates, np.int32)).to(dev)
+    d_pin = torch.from_numpy(np.asarray(phase_in, np.uint8)).to(dev) if phase_in is not None else None
+    d_pout = torch.zeros(n, dtype=torch.uint8, device=dev) if return_phase else None
+    d_ooff = torch.from_numpy(first.astype(np.int64)).to(dev)
+    out = torch.zeros((int(ooff[-1]), 2), dtype=torch.int8, device=dev)
+    _check(load().sora_hip_tx11b(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_rate),
+                                 _dev_ptr(d_pin) if d_pin is not None else None, _dev_ptr(d_pout) if d_pout is not None else None, n,
+                                 _dev_ptr(out), _dev_ptr(d_ooff), _stream_ptr(stream)))
+    if sync:
+        _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
+    if return_phase:
+        return out, [int(v) for v in ooff], [int(v) for v in d_pout.cpu().numpy()]
+    return out, [int(v) for v in ooff]

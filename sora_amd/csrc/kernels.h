@@ -169,6 +169,37 @@ __host__ __device__ inline bool tx11n_plan(uint32_t len, uint32_t mcs, Tx11nPlan
 }
 constexpr uint32_t kTx11nPreamble = 1120;                // samples per chain of the table: L-STF + L-LTF + HT-STF + 2 HT-LTF
 __global__ void k_tx11n(Tx11nArgs A);
+
+// ---- 802.11b transmitter (k_tx11b.hip)
+struct Tx11bArgs {             // sora_hip_tx11b
+    const uint8_t*  mpdu;      // MPDUs without FCS, frame f at mpdu + off[f]
+    const uint32_t* off;
+    const uint32_t* len;       // bytes without FCS
+    const uint32_t* rate;      // kbps: 1000, 2000, 5500, 11000
+    const uint8_t*  phase_in;  // CF_DifferentialMap::last_phase before the frame (0..3); nullptr: 0
+    uint8_t*        phase_out; // last_phase after the frame; nullptr: not written
+    int8_t*         out;       // COMPLEX8 at 44 MHz
+    const uint64_t* out_off;   // first sample of frame f
+    Tables          T;
+};
+// The PPDU is 24 header bytes (SYNC, SFD, PLCP header) spread by DBPSK at 88 chips a byte, then MPDU + FCS at the frame's
+// rate: cpb chips a byte in symbols of ls chips, spb symbols a byte.  TQuickPulseShaper emits four samples per chip and five
+// more chip steps at Flush; the last burst of eight samples is padded: sora_hip_tx11b_samples = 4 nchips + 24.
+struct Tx11bPlan { uint32_t code, cpb, ls, spb, nchips; };
+__host__ __device__ inline bool tx11b_plan(uint32_t len, uint32_t rate_kbps, Tx11bPlan& P)
+{
+    if (len < 1 || len > 4092) return false;
+    switch (rate_kbps) {                                   // SIGNAL: the rate in units of 100 kbit/s
+    case 1000:  P.code = 0x0A; P.cpb = 88; P.ls = 11; P.spb = 8; break;   // DBPSK, Barker
+    case 2000:  P.code = 0x14; P.cpb = 44; P.ls = 11; P.spb = 4; break;   // DQPSK, Barker
+    case 5500:  P.code = 0x37; P.cpb = 16; P.ls = 8;  P.spb = 2; break;   // CCK, 4 bits a symbol
+    case 11000: P.code = 0x6E; P.cpb = 8;  P.ls = 8;  P.spb = 1; break;   // CCK, 8 bits a symbol
+    default: return false;
+    }
+    P.nchips = 24 * 88 + (len + 4) * P.cpb;
+    return true;
+}
+__global__ void k_tx11b(Tx11bArgs A);
 __global__ void k_ingest(const uint8_t* raw, uint32_t* out, uint64_t m0, uint64_t n_out, unsigned flags);
 __global__ void k_ingest_tile(const uint8_t* raw, uint32_t* out, unsigned flags, uint32_t tiles);
 __global__ void k_soft_pack3(const uint8_t* soft8, const uint32_t* off8, const uint32_t* nsoft, const uint16_t* flen, const uint32_t* out_off,
