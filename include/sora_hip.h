@@ -335,8 +335,20 @@ size_t sora_hip_viterbi11a_workspace_bytes(size_t soft_span_bytes, size_t n);
 int sora_hip_viterbi11a_ws(const uint8_t* d_soft, size_t soft_span_bytes, const uint32_t* d_soft_off, const uint32_t* d_nsoft,
                            const uint16_t* d_frame_len, int code_rate, uint8_t* d_out, const uint32_t* d_out_off,
                            size_t n, void* d_workspace, size_t workspace_bytes, int lanes_per_pair, void* stream);
-/* lanes_per_pair: which of the two trellis kernels decodes (identical results): 64 (or 0) = k_viterbi, 16 = k_viterbi16 (see
- * sora_rx_set_trellis). */
+/* lanes_per_pair: which trellis kernel decodes (identical results): 64 (or 0) = k_viterbi, 16 = k_viterbi16, SORA_TRELLIS_WINDOWED =
+ * k_viterbi16w + k_win_redo (see sora_rx_set_trellis).  The window-parallel form cuts the n jobs into units by the receive path's own plan, so the
+ * batch size decides the units' geometry: one job gives units of one window, a few thousand units of several windows, 16384 or more one unit per job. */
+/* T11aViterbi<5000*8,312,192,36>, the 802.11n graph's decoder (fb11ndemod_config.hpp:199), as the same stage: one BYTE per soft value, of which
+ * only the low three bits are read (VitJob::soft_bits = 8).  lanes_per_pair: 64 (or 0) = k_viterbi11n, 16 = k_viterbi16_11n, SORA_TRELLIS_WINDOWED =
+ * k_viterbi16w_11n + k_win_redo_11n.  The workspace holds a copy of the caller's soft_span_bytes. */
+size_t sora_hip_viterbi11n_workspace_bytes(size_t soft_span_bytes, size_t n);
+int sora_hip_viterbi11n_ws(const uint8_t* d_soft, size_t soft_span_bytes, const uint32_t* d_soft_off, const uint32_t* d_nsoft,
+                           const uint16_t* d_frame_len, int code_rate, uint8_t* d_out, const uint32_t* d_out_off,
+                           size_t n, void* d_workspace, size_t workspace_bytes, int lanes_per_pair, void* stream);
+/* The proof record of the last SORA_TRELLIS_WINDOWED call of sora_hip_viterbi11a_ws / sora_hip_viterbi11n_ws on this workspace, in
+ * sora_rx_window_stats's order: out[0] unit boundaries compared, out[1] boundaries whose vectors differed, out[2] jobs decoded again serially
+ * because of that, out[3] units.  Waits for `stream` (the stream of that call).  Calls with another lanes_per_pair leave the record as it was. */
+int sora_hip_viterbi_window_stats(const void* d_workspace, unsigned long long out[4], void* stream);
 
 /* Capture ingest in front of the receive graph, one streaming pass on the device:
  *   SORA_INGEST_RXBLOCK    the input is a Sora dump: 128-byte RX_BLOCKs = 16-byte descriptor + 28 COMPLEX16

@@ -327,6 +327,15 @@ class Reference:
         n = self.L.ref_vit_decode_frame(h, _P(a), len(a), code_rate, frame_length, _P(o))
         self.L.ref_vit_free(h); return o[:n]
 
+    def viterbi_frame_ex(self, soft, code_rate, frame_length, depth, lookahead):
+        """the same schedule with another trace-back depth / look-ahead: 192 / 36 is the 802.11n graph's T11aViterbi<5000*8,312,192,36>"""
+        a = np.ascontiguousarray(soft, np.uint8); o = np.zeros(frame_length + 64, np.uint8)
+        h = ctypes.c_void_p(self.L.ref_vit_new())
+        n = self.L.ref_vit_decode_frame_ex(h, _P(a), len(a), code_rate, frame_length, _P(o), depth, lookahead)
+        self.L.ref_vit_free(h)
+        if n < 0: raise ValueError("ref_vit_decode_frame_ex: depth %d / lookahead %d not supported" % (depth, lookahead))
+        return o[:n]
+
     def crc32(self, b):
         a = np.frombuffer(bytes(b), np.uint8); return self.L.ref_crc32(_P(a), len(a))
 

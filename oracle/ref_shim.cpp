@@ -120,14 +120,19 @@ EXPORT void ref_vit_acs1b(void* h, uint32_t b) { ((RefCore*)h)->BranchACS((const
 EXPORT void ref_vit_normalize(void* h) { ((RefCore*)h)->Normalize(); }
 EXPORT void ref_vit_traceback(void* h, uint8_t* out, uint32_t bits, uint32_t lookahead) { ((RefCore*)h)->Traceback((char*)out, bits, lookahead); }
 
-// The frame-level schedule of T11aViterbi<5000*8,48,256,24>::Filter::Process (viterbi.hpp:148-235) driven
-// over the REFERENCE core: used as the "reference SSE Viterbi" leg of the CPU baseline and as a pin.
+// The frame-level schedule of T11aViterbi<5000*8, N_INPUT, depth, lookahead>::Filter::Process (viterbi.hpp:148-235) driven over the
+// REFERENCE core: depth / lookahead 256 / 24 is the 802.11a graph's decoder (fb11ademod_config.hpp), 192 / 36 the 802.11n graph's
+// (fb11ndemod_config.hpp:199); N_INPUT only sets the burst size.  Used as the "reference SSE Viterbi" leg of the CPU baseline and as a pin.
 // code_rate: 0 = 1/2, 1 = 2/3, 2 = 3/4 (ieee80211const.h:14-20).  Returns number of bytes written.
-EXPORT int ref_vit_decode_frame(void* h, const uint8_t* soft, uint32_t nsoft, int code_rate, uint32_t frame_length, uint8_t* out)
+// (The frame's final trace-back covers up to depth + lookahead + 2 bits, more than the brick's m_outbuf[depth / 8 + 1] holds: the buffer
+// here is sized for it.)
+EXPORT int ref_vit_decode_frame_ex(void* h, const uint8_t* soft, uint32_t nsoft, int code_rate, uint32_t frame_length, uint8_t* out,
+                                   uint32_t depth, uint32_t lookahead)
 {
     RefCore& v = *(RefCore*)h;
-    const uint32_t DEPTH = 256, LOOK = 24, PREFIX = 6;
-    uint8_t buf[DEPTH / 8 + 1];
+    const uint32_t DEPTH = depth, LOOK = lookahead, PREFIX = 6;
+    if (DEPTH == 0 || DEPTH > 256 || DEPTH % 8 || LOOK > 64) return -1;
+    uint8_t buf[(256 + 64 + 16) / 8 + 1];
     uint32_t ob = 0; int nout = 0;
     v.Reset();
     const uint8_t* p = soft; const uint8_t* end = soft + nsoft;
@@ -142,6 +147,7 @@ EXPORT int ref_vit_decode_frame(void* h, const uint8_t* soft, uint32_t nsoft, in
         if (tr >= tr_end) { cnt = tr_end - ob - PREFIX; look = tr - tr_end; }
         else if (tr >= ob + DEPTH + LOOK + PREFIX) { uint32_t remain = (tr - (ob + DEPTH + LOOK + PREFIX)) % 8; cnt = DEPTH; look = LOOK + remain; }
         if (cnt) {
+            if (cnt >= 8 * sizeof buf) return -1;
             v.Traceback((char*)buf, cnt, look);
             ob += cnt;
             memcpy(out + nout, buf, cnt >> 3); nout += cnt >> 3;
@@ -150,6 +156,8 @@ EXPORT int ref_vit_decode_frame(void* h, const uint8_t* soft, uint32_t nsoft, in
     }
     return nout;
 }
+EXPORT int ref_vit_decode_frame(void* h, const uint8_t* soft, uint32_t nsoft, int code_rate, uint32_t frame_length, uint8_t* out)
+{ return ref_vit_decode_frame_ex(h, soft, nsoft, code_rate, frame_length, out, 256, 24); }
 
 // TDownSample44_40 (sampling.hpp:35-66) over the REFERENCE resampler (44MTo40M.hpp:62-123): feed whole 28-sample
 // RX blocks, collect the 28-sample output blocks exactly as the brick forwards them.  Returns samples written.

@@ -60,7 +60,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_hip_table_count", "sora_hip_table_name", "sora_hip_table_pin", "sora_hip_table_digest", "sora_hip_table_read", "sora_rx_set_graph",
                       "sora_rx_kernel_name_fused", "sora_hip_fft64", "sora_hip_fft128", "sora_hip_lts11a", "sora_hip_symfront11a", "sora_hip_pilot_track11a", "sora_hip_pilot11a",
                       "sora_hip_freq_comp11a", "sora_hip_equalize11a", "sora_hip_phase_comp11a", "sora_hip_demap11a", "sora_hip_deinterleave11a", "sora_hip_viterbi11a",
-                      "sora_hip_viterbi11a_ws", "sora_hip_viterbi11a_workspace_bytes",
+                      "sora_hip_viterbi11a_ws", "sora_hip_viterbi11a_workspace_bytes", "sora_hip_viterbi11n_ws", "sora_hip_viterbi11n_workspace_bytes",
+                      "sora_hip_viterbi_window_stats",
            "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx11b",
            "sora_hip_tx11b_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
@@ -220,6 +221,9 @@ def load(build_if_missing=True):
     L.sora_hip_viterbi11a_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t]; L.sora_hip_viterbi11a_workspace_bytes.restype = ctypes.c_size_t
     L.sora_hip_viterbi11a_ws.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    L.sora_hip_viterbi11n_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t]; L.sora_hip_viterbi11n_workspace_bytes.restype = ctypes.c_size_t
+    L.sora_hip_viterbi11n_ws.argtypes = L.sora_hip_viterbi11a_ws.argtypes
+    L.sora_hip_viterbi_window_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_void_p]
     L.sora_hip_stream_synchronize.argtypes = [ctypes.c_void_p]
     L.sora_hip_tx11a_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11a_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -1092,7 +1096,8 @@ def viterbi11a_workspace_bytes(soft_span_bytes, n):
 
 def viterbi11a_ws(soft, soft_off, nsoft, frame_len, code_rate, workspace, out=None, out_off=None, out_stride=2560, lanes_per_pair=0, stream=None):
     """The Viterbi brick out of a caller-owned workspace (uint8 CUDA tensor of >= viterbi11a_workspace_bytes(soft.numel(), n)):
-    no allocation and no host wait inside the call; the caller synchronises the stream before reading `out`."""
+    no allocation and no host wait inside the call; the caller synchronises the stream before reading `out`.
+    lanes_per_pair: 64 (or 0) = k_viterbi, 16 = k_viterbi16, TRELLIS_WINDOWED = k_viterbi16w + k_win_redo."""
     import torch
     n = soft_off.shape[0]
     if out is None:
@@ -1101,6 +1106,31 @@ def viterbi11a_ws(soft, soft_off, nsoft, frame_len, code_rate, workspace, out=No
     _check(load().sora_hip_viterbi11a_ws(_dev_ptr(soft), soft.numel(), _dev_ptr(soft_off), _dev_ptr(nsoft), _dev_ptr(frame_len), code_rate,
                                          _dev_ptr(out), _dev_ptr(out_off), n, _dev_ptr(workspace), workspace.numel(), int(lanes_per_pair), _stream_ptr(stream)))
     return out
+
+
+def viterbi11n_workspace_bytes(soft_span_bytes, n):
+    return int(load().sora_hip_viterbi11n_workspace_bytes(int(soft_span_bytes), int(n)))
+
+
+def viterbi11n_ws(soft, soft_off, nsoft, frame_len, code_rate, workspace, out=None, out_off=None, out_stride=2560, lanes_per_pair=0, stream=None):
+    """viterbi11a_ws for the 802.11n graph's decoder T11aViterbi<..,192,36>: one byte per soft value (its low three bits), a workspace of
+    >= viterbi11n_workspace_bytes(soft.numel(), n).  lanes_per_pair: 64 (or 0), 16 or TRELLIS_WINDOWED."""
+    import torch
+    n = soft_off.shape[0]
+    if out is None:
+        out = torch.zeros((n, out_stride), dtype=torch.uint8, device=soft.device)
+        out_off = (torch.arange(n, device=soft.device, dtype=torch.int32) * out_stride).contiguous()
+    _check(load().sora_hip_viterbi11n_ws(_dev_ptr(soft), soft.numel(), _dev_ptr(soft_off), _dev_ptr(nsoft), _dev_ptr(frame_len), code_rate,
+                                         _dev_ptr(out), _dev_ptr(out_off), n, _dev_ptr(workspace), workspace.numel(), int(lanes_per_pair), _stream_ptr(stream)))
+    return out
+
+
+def viterbi_window_stats(workspace, stream=None):
+    """The proof record of the last TRELLIS_WINDOWED call of viterbi11a_ws / viterbi11n_ws on `workspace` (waits for `stream`):
+    (boundaries, boundaries failed, jobs decoded again, units)."""
+    v = (ctypes.c_ulonglong * 4)()
+    _check(load().sora_hip_viterbi_window_stats(_dev_ptr(workspace), v, _stream_ptr(stream)))
+    return tuple(int(x) for x in v)
 
 
 INGEST_RXBLOCK, INGEST_RAW14, INGEST_44TO40, INGEST_DECIMATE2 = 1, 2, 4, 8

@@ -1602,4 +1602,16 @@ __global__ void __launch_bounds__(256) k_soft_pack3(const uint8_t* soft8, const 
     }
 }
 
+// sora_hip_viterbi11n takes one byte per soft value and hands the bytes to the trellis kernels as they are (VitJob::soft_bits = 8: they read the low three bits); its
+// streams sit in the workspace at the caller's own offsets, so the job table is all this stage has to make.  One thread per job.
+__global__ void __launch_bounds__(256) k_soft_jobs8(const uint32_t* off8, const uint32_t* nsoft, const uint16_t* flen, const uint32_t* out_off, int code_rate,
+                                                    uint32_t n, VitJob* jobs)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    VitJob J; J.soft_off = off8[j]; J.nsoft = nsoft[j]; J.length = flen[j]; J.dec_off = 0; J.out_off = out_off[j];
+    J.valid = 1; J.code_rate = (uint32_t)code_rate; J.soft_bits = 8;
+    jobs[j] = J;
+}
+
 }  // namespace sora

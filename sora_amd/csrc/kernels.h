@@ -204,6 +204,7 @@ __global__ void k_ingest(const uint8_t* raw, uint32_t* out, uint64_t m0, uint64_
 __global__ void k_ingest_tile(const uint8_t* raw, uint32_t* out, unsigned flags, uint32_t tiles);
 __global__ void k_soft_pack3(const uint8_t* soft8, const uint32_t* off8, const uint32_t* nsoft, const uint16_t* flen, const uint32_t* out_off,
                              int code_rate, uint8_t* packed, VitJob* jobs);
+__global__ void k_soft_jobs8(const uint32_t* off8, const uint32_t* nsoft, const uint16_t* flen, const uint32_t* out_off, int code_rate, uint32_t n, VitJob* jobs);
 
 // ---- 802.11b receive graph (k_rx11b.hip)
 struct Rx11bRow { uint32_t end_sample, error_code, rate_kbps, length, crc32; };

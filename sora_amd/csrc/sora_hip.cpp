@@ -1969,39 +1969,114 @@ int sora_hip_ingest(const void* d_raw, size_t raw_bytes, unsigned flags, sora_co
     return SORA_OK;
 }
 
-// The stage works out of a caller-owned workspace (no allocation, no host wait): every job's soft values packed to three bits each
-// (k_soft_pack3: at byte ceil(off / 2), disjoint for any offsets and lengths because the caller's ranges are), followed by the job table.  sora_hip_viterbi11a keeps
-// the original signature on top of a grow-only workspace cached per device.
-static size_t vit_ws_packed_bytes(size_t soft_span_bytes) { return (soft_span_bytes / 2 + 4 + kSoftSlack + 255) & ~(size_t)255; }
+// The stage works out of a caller-owned workspace (no allocation, no host wait).  Its layout, front to back:
+//   head      the window-parallel trellis's code-rate list header (hdr[3]: this call's one list) and its proof record (4 kWinStatBanks counters)
+//   soft      802.11a: every job's soft values packed to three bits each (k_soft_pack3: at byte ceil(off / 2), disjoint for any offsets and lengths because the
+//             caller's ranges are); 802.11n: the caller's bytes as they are, at their own offsets (the trellis kernels read one byte past a stream's last value)
+//   jobs      the job table
+//   vecs      the window-parallel trellis's metric vectors (kWinVecBytes per unit, at most win_units(n) units)
+// sora_hip_viterbi11a keeps the original signature on top of a grow-only workspace cached per device.
+constexpr size_t kVitWsHdr = 0, kVitWsStats = 256, kVitWsHead = kVitWsStats + 4 * kWinStatBanks * sizeof(unsigned long long);
+static size_t vit_ws_round(size_t b) { return (b + 255) & ~(size_t)255; }
+static size_t vit_ws_packed_bytes(size_t soft_span_bytes) { return vit_ws_round(soft_span_bytes / 2 + 4 + kSoftSlack); }
+static size_t vit_ws_bytes8(size_t soft_span_bytes) { return vit_ws_round(soft_span_bytes + kSoftSlack); }
+static uint32_t vit_ws_vecs(size_t n) { return (uint32_t)(win_units(n) + n); }
+static size_t vit_ws_tail(size_t n) { return vit_ws_round(sizeof(VitJob) * n) + (size_t)kWinVecBytes * vit_ws_vecs(n); }
 size_t sora_hip_viterbi11a_workspace_bytes(size_t soft_span_bytes, size_t n)
 {
-    return vit_ws_packed_bytes(soft_span_bytes) + sizeof(VitJob) * n;
+    return kVitWsHead + vit_ws_packed_bytes(soft_span_bytes) + vit_ws_tail(n);
 }
+size_t sora_hip_viterbi11n_workspace_bytes(size_t soft_span_bytes, size_t n)
+{
+    return kVitWsHead + vit_ws_bytes8(soft_span_bytes) + vit_ws_tail(n);
+}
+
+// Both stage doors: check the arguments, make the soft streams and the job table in the workspace, then run the chosen trellis kernel over them.  WIN = 256: the
+// 802.11a graph's T11aViterbi<5000*8,48,256,24>; WIN = 192: the 802.11n graph's T11aViterbi<5000*8,312,192,36>.
+extern "C++" {
+template <int WIN>
+static int viterbi_ws(const char* name, const uint8_t* d_soft, size_t soft_span_bytes, const uint32_t* d_soft_off, const uint32_t* d_nsoft,
+                      const uint16_t* d_frame_len, int code_rate, uint8_t* d_out, const uint32_t* d_out_off, size_t n, void* d_workspace, size_t workspace_bytes,
+                      int lanes_per_pair, void* stream)
+{
+    const std::string nm(name);
+    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
+    if (!d_soft || !d_soft_off || !d_nsoft || !d_frame_len || !d_out || !d_out_off || code_rate < 0 || code_rate > 2) return fail(SORA_ERR_INVALID_PARAM,
+            (nm + ": bad argument").c_str());
+    if (n == 0) return SORA_OK;
+    if (lanes_per_pair != 0 && lanes_per_pair != 16 && lanes_per_pair != 64 && lanes_per_pair != SORA_TRELLIS_WINDOWED) return fail(SORA_ERR_INVALID_PARAM,
+            (nm + ": lanes_per_pair is 0 (default: 64), 16, 64 or SORA_TRELLIS_WINDOWED").c_str());
+    if (!d_workspace || ((uintptr_t)d_workspace & 15)) return fail(SORA_ERR_INVALID_PARAM, (nm + ": the workspace must be a 16-byte aligned device buffer").c_str());
+    const size_t need = WIN == 256 ? sora_hip_viterbi11a_workspace_bytes(soft_span_bytes, n) : sora_hip_viterbi11n_workspace_bytes(soft_span_bytes, n);
+    if (workspace_bytes < need) return fail(SORA_ERR_CAPACITY, (nm + ": workspace smaller than its _workspace_bytes()").c_str());
+    if (soft_span_bytes >= (1ull << 32) || n >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, (nm + ": batch too large").c_str());
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = (uint8_t*)d_workspace;
+    uint32_t* hdr = (uint32_t*)(ws + kVitWsHdr);
+    unsigned long long* stats = (unsigned long long*)(ws + kVitWsStats);
+    uint8_t* soft = ws + kVitWsHead;
+    VitJob* jobs = (VitJob*)(soft + (WIN == 256 ? vit_ws_packed_bytes(soft_span_bytes) : vit_ws_bytes8(soft_span_bytes)));
+    uint16_t* vecs = (uint16_t*)((uint8_t*)jobs + vit_ws_round(sizeof(VitJob) * n));
+    if (WIN == 256)
+        hipLaunchKernelGGL(k_soft_pack3, dim3((unsigned)n), dim3(256), 0, st, d_soft, d_soft_off, d_nsoft, d_frame_len, d_out_off, code_rate, soft, jobs);
+    else {
+        HIPCHK(hipMemcpyAsync(soft, d_soft, soft_span_bytes, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_soft_jobs8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_soft_off, d_nsoft, d_frame_len, d_out_off, code_rate, (uint32_t)n, jobs);
+    }
+    const VitJob* cjobs = jobs;
+    const uint8_t* csoft = soft;
+    if (lanes_per_pair == SORA_TRELLIS_WINDOWED) {
+        // the receive path's own unit plan over one code-rate list of n frames: the batch size decides the units' geometry (dev_winplan.h)
+        const uint32_t q = sora::win_units_per_frame((uint32_t)n, kWinUnitsTarget), waves = (sora::win_slots((uint32_t)n, q) + 7) / 8;
+        const uint32_t vstride = vit_ws_vecs(n), pair_groups = (uint32_t)(((n + 1) / 2 + 3) / 4);
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)hdr, 0, 4, st));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)hdr, (int)n, 1, st));
+        HIPCHK(hipMemsetAsync(stats, 0, 4 * kWinStatBanks * sizeof(unsigned long long), st));
+        if (WIN == 256) {
+            hipLaunchKernelGGL(k_viterbi16w, dim3(waves), dim3(64), 0, st, cjobs, (const uint32_t*)hdr, (uint32_t)n, kWinUnitsTarget, vstride, csoft, d_out, vecs);
+            hipLaunchKernelGGL(k_win_redo, dim3(pair_groups), dim3(256), 0, st, cjobs, (const uint32_t*)hdr, (uint32_t)n, kWinUnitsTarget, vstride,
+                               (const uint16_t*)vecs, csoft, d_out, stats);
+        } else {
+            hipLaunchKernelGGL(k_viterbi16w_11n, dim3(waves), dim3(64), 0, st, cjobs, (const uint32_t*)hdr, (uint32_t)n, kWinUnitsTarget, vstride, csoft, d_out, vecs);
+            hipLaunchKernelGGL(k_win_redo_11n, dim3(pair_groups), dim3(256), 0, st, cjobs, (const uint32_t*)hdr, (uint32_t)n, kWinUnitsTarget, vstride,
+                               (const uint16_t*)vecs, csoft, d_out, stats);
+        }
+    }
+    else if (lanes_per_pair == 16) {
+        if (WIN == 256) hipLaunchKernelGGL(k_viterbi16, dim3((unsigned)((n + 7) / 8)), dim3(64), 0, st, cjobs, (const uint32_t*)nullptr, (uint32_t)n, 0u, csoft, d_out);
+        else hipLaunchKernelGGL(k_viterbi16_11n, dim3((unsigned)((n + 7) / 8)), dim3(64), 0, st, cjobs, (const uint32_t*)nullptr, (uint32_t)n, 0u, csoft, d_out);
+    }
+    else {
+        if (WIN == 256) hipLaunchKernelGGL(k_viterbi, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, st, cjobs, (const uint32_t*)nullptr, (uint32_t)n, 0u, csoft, d_out);
+        else hipLaunchKernelGGL(k_viterbi11n, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, st, cjobs, (const uint32_t*)nullptr, (uint32_t)n, 0u, csoft, d_out);
+    }
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+}  // extern "C++"
 
 int sora_hip_viterbi11a_ws(const uint8_t* d_soft, size_t soft_span_bytes, const uint32_t* d_soft_off, const uint32_t* d_nsoft, const uint16_t* d_frame_len,
                            int code_rate, uint8_t* d_out, const uint32_t* d_out_off, size_t n, void* d_workspace, size_t workspace_bytes, int lanes_per_pair, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_soft || !d_soft_off || !d_nsoft || !d_frame_len || !d_out || !d_out_off || code_rate < 0 || code_rate > 2) return fail(SORA_ERR_INVALID_PARAM,
-            "sora_hip_viterbi11a: bad argument");
-    if (n == 0) return SORA_OK;
-    if (lanes_per_pair != 0 && lanes_per_pair != 16 && lanes_per_pair != 64) return fail(SORA_ERR_INVALID_PARAM,
-            "sora_hip_viterbi11a_ws: lanes_per_pair is 0 (default: 64), 16 or 64");
-    if (!d_workspace || ((uintptr_t)d_workspace & 15)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_viterbi11a_ws: the workspace must be a 16-byte aligned device buffer");
-    if (workspace_bytes < sora_hip_viterbi11a_workspace_bytes(soft_span_bytes, n)) return fail(SORA_ERR_CAPACITY,
-            "sora_hip_viterbi11a_ws: workspace smaller than sora_hip_viterbi11a_workspace_bytes()");
-    if (soft_span_bytes >= (1ull << 32) || n >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_viterbi11a: batch too large");
+    return viterbi_ws<256>("sora_hip_viterbi11a_ws", d_soft, soft_span_bytes, d_soft_off, d_nsoft, d_frame_len, code_rate, d_out, d_out_off, n, d_workspace,
+                           workspace_bytes, lanes_per_pair, stream);
+}
+int sora_hip_viterbi11n_ws(const uint8_t* d_soft, size_t soft_span_bytes, const uint32_t* d_soft_off, const uint32_t* d_nsoft, const uint16_t* d_frame_len,
+                           int code_rate, uint8_t* d_out, const uint32_t* d_out_off, size_t n, void* d_workspace, size_t workspace_bytes, int lanes_per_pair, void* stream)
+{
+    return viterbi_ws<192>("sora_hip_viterbi11n_ws", d_soft, soft_span_bytes, d_soft_off, d_nsoft, d_frame_len, code_rate, d_out, d_out_off, n, d_workspace,
+                           workspace_bytes, lanes_per_pair, stream);
+}
+
+int sora_hip_viterbi_window_stats(const void* d_workspace, unsigned long long out[4], void* stream)
+{
+    if (!d_workspace || !out) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_viterbi_window_stats: null argument");
     hipStream_t st = (hipStream_t)stream;
-    uint8_t* packed = (uint8_t*)d_workspace;
-    VitJob* jobs = (VitJob*)((uint8_t*)d_workspace + vit_ws_packed_bytes(soft_span_bytes));
-    hipLaunchKernelGGL(k_soft_pack3, dim3((unsigned)n), dim3(256), 0, st, d_soft, d_soft_off, d_nsoft, d_frame_len, d_out_off, code_rate, packed, jobs);
-    if (lanes_per_pair == 16)
-        hipLaunchKernelGGL(k_viterbi16, dim3((unsigned)((n + 7) / 8)), dim3(64), 0, st, (const VitJob*)jobs, (const uint32_t*)nullptr, (uint32_t)n, 0u,
-                (const uint8_t*)packed, d_out);
-    else
-        hipLaunchKernelGGL(k_viterbi, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, st, (const VitJob*)jobs, (const uint32_t*)nullptr, (uint32_t)n, 0u,
-                (const uint8_t*)packed, d_out);
-    HIPCHK(hipGetLastError());
+    unsigned long long v[4 * kWinStatBanks];
+    HIPCHK(hipMemcpyAsync(v, (const uint8_t*)d_workspace + kVitWsStats, sizeof v, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    for (unsigned i = 0; i < 4 * kWinStatBanks; i++) out[i & 3u] += v[i];
     return SORA_OK;
 }
 

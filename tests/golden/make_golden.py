@@ -16,6 +16,9 @@
                          its receive graph reports for captures made of them (tests/test_oracle_11b.channel_11b).
   refgraph_11b_cck.npz   the same for six 5.5 / 11 Mbps CCK frames (`python make_golden.py 11b_cck` writes only this file).
   ref_vectors_11n.npz    802.11n stage bricks: inputs and what the reference's own T11nDemap* / T11nDeinterleave*_S{0,1} bricks make of them.
+  trellis_adversarial.npz  a subset of the adversarial soft streams of tests/trellis_streams.py at every code rate and what the reference's
+                         TViterbiCore makes of them under both trace-back schedules, 256 / 24 and 192 / 36 (`python make_golden.py trellis`
+                         writes only this file).
 All files travel to the GPU box; /root/reference does not.
 """
 import hashlib
@@ -59,7 +62,35 @@ def record_11b(G, name, cases, seed):
 CCK_CASES = [(5500, 1), (5500, 30), (5500, 200), (11000, 2), (11000, 77), (11000, 400)]
 
 
+def trellis_subset(cr):
+    """the recorded subset of tests/trellis_streams.py: ties, wrap, bursts, the shortest lengths and a schedule corner"""
+    import trellis_streams as ts
+    t = ts.ties(cr)
+    jobs = t[0:16:2] + t[16:19] + ts.wrap(cr)[:1] + ts.bursts(cr, "11a", 64, 4, length=300)[0] + ts.bursts(cr, "11n", 64, 2, length=300)[0]
+    ln = ts.lengths(cr, "11a")
+    jobs += ln[:40] + ln[100:104]
+    return jobs
+
+
+def record_trellis(R):
+    v = {}
+    for cr in (CR_12, CR_23, CR_34):
+        jobs = trellis_subset(cr)
+        v["soft_%d" % cr] = np.concatenate([s for s, _ in jobs])
+        v["nsoft_%d" % cr] = np.array([len(s) for s, _ in jobs], np.int32)
+        v["len_%d" % cr] = np.array([L for _, L in jobs], np.int32)
+        for name, (win, look) in (("11a", (256, 24)), ("11n", (192, 36))):
+            outs = [R.viterbi_frame_ex(s, cr, L, win, look) for s, L in jobs]
+            assert all(len(o) == L + 2 for o, (_, L) in zip(outs, jobs))
+            v["out%s_%d" % (name, cr)] = np.concatenate(outs)
+    np.savez_compressed(os.path.join(OUT, "trellis_adversarial.npz"), **v)
+
+
 def main():
+    if sys.argv[1:] == ["trellis"]:
+        R = Reference(); assert R.available(), "build oracle/_ref first (oracle/build_ref.sh)"
+        record_trellis(R)
+        return
     if sys.argv[1:] == ["11b_cck"]:
         G = ReferenceGraph(); assert G.available()
         record_11b(G, "refgraph_11b_cck.npz", CCK_CASES, 1103)
