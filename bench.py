@@ -17,15 +17,19 @@ of sixteen back-to-back frames per GPU (256 concurrent captures over 8 GPUs) ins
 
 The timed region is exactly --steps steps (with --min-seconds S > 0 the K-step block is repeated until S seconds have passed); every
 step is a process call whose dense result rows AND MPDU array are delivered to page-locked host memory behind the kernels, and the
-oldest call in flight is waited for and its rows compared with the verified ones.  Before anything is timed, the first
-call's rows are compared, capture by capture, with what the compiled reference graph reports (--check 0 = all captures).
+oldest call in flight is waited for and its rows compared with the verified ones.
 --dump-outputs DIR writes what the last timed step delivered (rows and MPDU bytes, see dump_outputs) as DIR/<name>.npy.
 
-Prints ONE JSON line on rank 0, with `ms_per_step` (one timed step), `roofline` for the dominant kernel (HIP events on the
-library's own streams, one call in flight) and `cpu_baseline` (the reference's SSE graph compiled from its sources, on all
-usable host cores; the scalar restatement where that library is absent).  The side sections (plain host, latency, stages,
-ingest, tx, 11b, 11n, HT40, shard shape) are measured only with --sections-out FILE, which receives the whole object: the line
-itself stays a few KB.
+A plain run does only what the headline needs: it sets up, warms up, times the steps, dumps if asked and prints the line.
+Everything else is measured or checked only with --full: the first call's rows against what the compiled reference graph
+reports, capture by capture (--check 0 = all captures); the same steps again with HIP events (`ms_per_step_profiled`,
+`kernel_ms`) and each trellis kernel alone on the chip (`roofline`, `kernel_ms_one_call_in_flight`); `cpu_baseline` (the
+reference's SSE graph compiled from its sources, on all usable host cores; the scalar restatement where that library is
+absent); and with --gpus N > 1 the RCCL exchange of rows and MPDUs (`gathered`).
+
+Prints ONE JSON line on rank 0, with `ms_per_step` (one timed step).  The side sections (plain host, latency, stages, ingest,
+tx, 11b, 11n, HT40, shard shape) are measured only with --sections-out FILE (which implies --full) and the file receives the
+whole object: the line itself stays a few KB.
 """
 import argparse
 import json
@@ -164,12 +168,14 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the stage / ingest / tx / 11b / 11n sections")
     ap.add_argument("--depth", type=int, default=0, help="process calls in flight on the handle's internal pipelines (0 = library default)")
     ap.add_argument("--trellis", type=int, default=-1, help="trellis kernel: 64 = k_viterbi, 16 = k_viterbi16, 0 = the library's choice from the depth (default: leave the handle as created)")
-    ap.add_argument("--check", type=int, default=0, help="captures compared with the reference after the timed region (0 = all)")
+    ap.add_argument("--check", type=int, default=0, help="with --full: captures of the first call compared with the reference before the timed region (0 = all)")
     ap.add_argument("--min-seconds", type=float, default=0.0, help="0 (default): the timed region is exactly --steps steps; > 0: the K-step block is repeated "
                     "until it has lasted this long")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one delivered (result rows, MPDU bytes) as DIR/<name>.npy")
-    ap.add_argument("--sections-out", metavar="FILE", help="also measure the side sections (plain host, latency, stages, ingest, tx, 11b, 11n, HT40, shard shape) "
-                    "and write the whole result object, them included, to FILE as JSON")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: the first call against the reference, "
+                    "the profiled steps and each trellis kernel alone (roofline), the CPU baseline, the multi-GPU result exchange")
+    ap.add_argument("--sections-out", metavar="FILE", help="implies --full; also measure the side sections (plain host, latency, stages, ingest, tx, 11b, 11n, HT40, "
+                    "shard shape) and write the whole result object, them included, to FILE as JSON")
     ap.add_argument("--no-deliver", action="store_true", help="do not deliver rows + MPDUs to the host inside the timed region (round-1 behaviour)")
     ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES for this process (read before HIP starts); 0 = leave the runtime default")
     ap.add_argument("--shape", default="batch", choices=["batch", "shard"], help="batch: --frames captures of one frame per GPU (BASELINE configs[2], the headline); "
@@ -177,6 +183,7 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true", help="only start the ranks, let them find each other (gloo) and print one line: the CPU test of --gpus N's own launcher")
     ap.add_argument("--only", default="", help="run just one of the extra sections (stages, ingest, tx, rx11b, rx11b_cck, rx11n, rx11n_40, shard_32x16, latency) and print its object: for profiling that section alone")
     args = ap.parse_args()
+    full = args.full or bool(args.sections_out)
 
     if args.gpus > 1 and "RANK" not in os.environ:                               # not under torch.distributed.run: this process becomes the launcher of the N ranks
         if not args.launcher_selftest:
@@ -247,14 +254,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- the first call is checked before anything is timed: every capture against the reference (or --check of them)
+    # ---- the first call's table is what every timed call is compared with; with --full it is checked before anything is timed: every
+    # capture against the reference (or --check of them)
     t = rx.process_dev(d_iq, descs)
     res = rx.results(ticket=t)
-    kind, want = reference_rows(iq, nfr, oracle, fpc)
-    idx = list(range(nfr)) if args.check <= 0 or args.check >= nfr else list(range(0, nfr, max(1, nfr // args.check)))[:args.check]
-    parity_ok, why = check_against_reference(res, kind, want, idx)
-    if not parity_ok:
-        print("PARITY MISMATCH vs %s: %s" % (kind, why), file=sys.stderr)
+    if full:
+        kind, want = reference_rows(iq, nfr, oracle, fpc)
+        idx = list(range(nfr)) if args.check <= 0 or args.check >= nfr else list(range(0, nfr, max(1, nfr // args.check)))[:args.check]
+        parity_ok, why = check_against_reference(res, kind, want, idx)
+        if not parity_ok:
+            print("PARITY MISMATCH vs %s: %s" % (kind, why), file=sys.stderr)
     n_ok = sum(1 for r in res if r["error_code"] == sora_amd.E_FRAME_OK)
     seen = {}                                                       # (rows come in capture, time order: the k-th row of a capture is its k-th frame)
     n_payload_ok = 0
@@ -270,7 +279,7 @@ def main():
     rx.deliver_async(t, bufs[0]); rx.wait(t)
     exp_n = int(bufs[0].nrows[0]); exp_rows = bufs[0].rows[:exp_n].copy(); exp_mpdu = bufs[0].mpdu.copy()
     exp_bytes = exp_rows.tobytes()
-    host_rows_ok = exp_n == len(res) and all(int(exp_rows[k]["crc32"]) == res[k]["crc32"] and int(exp_rows[k]["error_code"]) == res[k]["error_code"] for k in range(exp_n)) \
+    host_rows_ok = full and exp_n == len(res) and all(int(exp_rows[k]["crc32"]) == res[k]["crc32"] and int(exp_rows[k]["error_code"]) == res[k]["error_code"] for k in range(exp_n)) \
         and all(bytes(exp_mpdu[int(r["mpdu_offset"]):int(r["mpdu_offset"]) + int(r["length"])]) == res[k]["mpdu"] for k, r in enumerate(exp_rows) if int(r["error_code"]) == 1)
     stats = {"t_submit": 0.0, "t_wait": 0.0, "t_check": 0.0}
     share = pin_rank_threads(local_rank, world)                     # this rank's cores: the submit thread on the first, the checker's threads on the others
@@ -361,37 +370,38 @@ def main():
     side_reps = max(1, int(np.ceil(1.0 / max((t1 - t0) / repeats, 1e-6))))  # the side sections' blocks: K-step blocks for about a second, as the headline once was
     stats["delivered"], stats["bad"] = chk.compared, chk.bad
     stats["mpdu_compared_timed"] = getattr(chk, "mpdu_compared", 0)
-    mpdu_ok = bool(deliver) and all((b.mpdu == exp_mpdu).all() for b in bufs)     # the last calls' MPDU arrays once more, byte for byte
-    # the same K steps once more with HIP events around every kernel launch (on the streams the kernels run on): the
-    # roofline's launch durations are means over this region; `value` comes from the un-instrumented region above
-    # (recording 6 events per call costs a few percent, reported as ms_per_step_profiled)
-    rx.set_profiling(True)
-    barrier()
-    t2 = time.perf_counter()
-    run_block(args.steps, deliver)
-    rx.flush()
-    barrier()
-    t3 = time.perf_counter()
-    ktimes = rx.kernel_times()
-    rx.set_profiling(False)
-    # and with ONE call in flight: each kernel alone on the chip (the per-kernel roofline without the CU sharing of overlapped calls).
-    # The trellis kernel is pinned to the one the timed region used (left to itself the library picks k_viterbi for a single call in
-    # flight and k_viterbi16 from depth 4); the other one is measured alone as well, for the record.
-    lanes = rx.trellis(); trellis_setting = rx.set_trellis(-1)
+    lanes = rx.trellis(); trellis_setting = rx.set_trellis(-1)               # the trellis kernel the timed region used, and the handle's setting
     tname = TRELLIS_NAMES
-
-    def alone(l):
-        rx.set_trellis(l); rx.set_depth(1); rx.flush()
+    if full:
+        mpdu_ok = bool(deliver) and all((b.mpdu == exp_mpdu).all() for b in bufs)     # the last calls' MPDU arrays once more, byte for byte
+        # the same K steps once more with HIP events around every kernel launch (on the streams the kernels run on): the
+        # roofline's launch durations are means over this region; `value` comes from the un-instrumented region above
+        # (recording 6 events per call costs a few percent, reported as ms_per_step_profiled)
         rx.set_profiling(True)
-        for _ in range(max(10, args.steps // 2)):
-            rx.process_dev(d_iq, descs)
+        barrier()
+        t2 = time.perf_counter()
+        run_block(args.steps, deliver)
         rx.flush()
-        kt = rx.kernel_times()
+        barrier()
+        t3 = time.perf_counter()
+        ktimes = rx.kernel_times()
         rx.set_profiling(False)
-        return {(tname[l] if k == "k_viterbi" else k): v for k, v in kt.items()}
-    ktimes1 = alone(lanes)
-    ktimes1_others = {l: alone(l) for l in TRELLIS_NAMES if l != lanes}
-    ktimes = {(tname[lanes] if k == "k_viterbi" else k): v for k, v in ktimes.items()}
+        # and with ONE call in flight: each kernel alone on the chip (the per-kernel roofline without the CU sharing of overlapped calls).
+        # The trellis kernel is pinned to the one the timed region used (left to itself the library picks k_viterbi for a single call in
+        # flight and k_viterbi16 from depth 4); the other one is measured alone as well, for the record.
+
+        def alone(l):
+            rx.set_trellis(l); rx.set_depth(1); rx.flush()
+            rx.set_profiling(True)
+            for _ in range(max(10, args.steps // 2)):
+                rx.process_dev(d_iq, descs)
+            rx.flush()
+            kt = rx.kernel_times()
+            rx.set_profiling(False)
+            return {(tname[l] if k == "k_viterbi" else k): v for k, v in kt.items()}
+        ktimes1 = alone(lanes)
+        ktimes1_others = {l: alone(l) for l in TRELLIS_NAMES if l != lanes}
+        ktimes = {(tname[lanes] if k == "k_viterbi" else k): v for k, v in ktimes.items()}
 
     # ---- what a plain host gets: process -> deliver -> wait with ONE or TWO calls in flight, i.e. at most two of the
     # handle's streams in use -- fewer than the runtime's default four hardware queues, so GPU_MAX_HW_QUEUES plays no part -- same timed-region
@@ -457,11 +467,12 @@ def main():
     counters = torch.tensor([len(res), n_ok, n_payload_ok, stats["delivered"], stats["bad"]], device=dev, dtype=torch.int64)
     gathered_rows = None; gathered = None
     if world > 1:
-        # the path's one exchange step: RCCL all-gathers of the device-packed result rows AND the MPDUs (every MPDU
-        # reaches the one host buffer, fb11a_demod.cpp:64-70) + all-reduce of counters.  Per rank and exchange: 8 bytes of counts,
-        # 36 bytes x 2 x captures of rows, MPDU_LEN x captures of MPDU bytes.
-        gathered = exchange_results(torch, rx, d_iq, descs, dev, nfr, MAXF, fpc)
-        gathered_rows = gathered["rows"]
+        if full:
+            # the path's one exchange step: RCCL all-gathers of the device-packed result rows AND the MPDUs (every MPDU
+            # reaches the one host buffer, fb11a_demod.cpp:64-70) + all-reduce of counters.  Per rank and exchange: 8 bytes of counts,
+            # 36 bytes x 2 x captures of rows, MPDU_LEN x captures of MPDU bytes.
+            gathered = exchange_results(torch, rx, d_iq, descs, dev, nfr, MAXF, fpc)
+            gathered_rows = gathered["rows"]
         dist.all_reduce(counters)
     tot_frames, tot_ok, tot_payload_ok, tot_delivered, tot_bad = [int(v) for v in counters.tolist()]
 
@@ -469,17 +480,13 @@ def main():
     msps = total_samples / elapsed / 1e6
     ms_per_step = elapsed / timed_steps * 1e3
     if rank == 0:
-        dom = max((k for k in ktimes if k.startswith("k_")), key=lambda k: ktimes[k])
-        launch_bytes = nfr * fpc * FRAME_SAMPLES * ALG_BYTES_PER_SAMPLE
-        ach = launch_bytes / (ktimes[dom] * 1e-3)
-        ach1 = launch_bytes / (ktimes1[dom] * 1e-3)
         air_s = nfr * fpc * CAPTURE_SAMPLES / 20e6                                   # what one step's captures last on the air
         out = {
             "metric": "IQ Msamples/s through 802.11a 54 Mbps RX PHY",
             "value": round(msps, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "timed_steps": timed_steps, "timed_seconds": round(elapsed, 4),
-            "ms_per_step": round(ms_per_step, 4), "ms_per_step_profiled": round((t3 - t2) / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "int16 IQ / u8 path metrics", "data": "synthetic",
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "int16 IQ / u8 path metrics", "data": "synthetic", "full": full,
             "config": {"workload": ("802.11a 54 Mbps (64-QAM r=3/4) RX, %d concurrent captures/GPU x %d back-to-back 1500-byte frames (4880 samples @20 MHz, +160 silence each), AWGN 30/27 dB on 3 of 4: BASELINE configs[4]" % (nfr, fpc)) if shard else
                                    "802.11a 54 Mbps (64-QAM r=3/4) RX, %d captures/GPU x one 1500-byte frame (4880 samples @20 MHz, +160 silence), AWGN 30/27 dB on 3 of 4" % nfr,
                        "shape": args.shape, "captures_per_gpu": nfr, "frames_per_capture": fpc,
@@ -488,27 +495,35 @@ def main():
                        "timed_region": "%d x %d steps in one continuous run; every step = process call + pack + async delivery of rows and MPDUs to pinned host memory + wait for %s, whose rows and MPDU bytes are compared with the verified ones by %d host threads%s" % (repeats, args.steps, "whichever call in flight finishes first (sora_rx_wait_any)" if order["any"] else "the oldest call in flight", TableChecker.EXTRA, "" if world == 1 else " (every rank pins its submit thread and its checker threads to its own slice of the host's cores)")
                                        if deliver else "%d x %d process calls, nothing delivered" % (repeats, args.steps)},
             "decoded_mbit_per_s": round(msps * (MPDU_LEN * 8.0 / FRAME_SAMPLES), 2),
-            "frames": tot_frames, "gathered_rows": gathered_rows, "gathered": gathered, "frames_crc_ok": tot_ok, "frames_payload_ok": tot_payload_ok,
-            "parity": {"against": kind, "captures_checked": len(idx), "ok": parity_ok, "host_rows_ok": host_rows_ok},
+            "frames": tot_frames, "frames_crc_ok": tot_ok, "frames_payload_ok": tot_payload_ok,
             "host_ms_per_step": host_ms,
             "delivery": {"enabled": deliver, "calls_delivered_and_compared": tot_delivered, "calls_with_wrong_rows": tot_bad, "rows_per_call": exp_n,
-                         "row_bytes_per_call": 36 * nfr * MAXF, "mpdu_bytes_per_call": int(exp_mpdu.size), "last_calls_mpdu_ok": mpdu_ok, "calls_with_mpdu_bytes_compared": stats.get("mpdu_compared_timed", 0)},
+                         "row_bytes_per_call": 36 * nfr * MAXF, "mpdu_bytes_per_call": int(exp_mpdu.size), "calls_with_mpdu_bytes_compared": stats.get("mpdu_compared_timed", 0)},
             # the reference's own figure of merit (MACStopwatch.h:84-128): cost / required time, < 1 = faster than real time
-            "realtime": {"factor": round(ms_per_step * 1e-3 / air_s, 7), "channels_20mhz_in_real_time": round(air_s / (ms_per_step * 1e-3), 1),
-                         "call_latency_ms_one_in_flight": round(sum(v for k, v in ktimes1.items()), 4)},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(ach1 / 1e9, 2), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": round(ach1 / HBM_PEAK, 5), "traffic": measured_traffic(dom) if nfr == FRAMES_PER_GPU and not shard else None,
-                         "traffic_source": _traffic_profile()[1],
-                         "algorithmic_bytes_per_launch": launch_bytes, "kernel_ms": round(ktimes1[dom], 4),
-                         "kernel_ms_note": "mean launch duration with ONE call in flight (the kernel alone on the chip); with %d calls overlapped the same launch lasts %.4f ms (frac %.5f) because it shares the CUs" % (depth, ktimes[dom], ach / HBM_PEAK),
-                         "whole_path_frac": round(msps * 1e6 / world * ALG_BYTES_PER_SAMPLE / HBM_PEAK, 5),
-                         "other_trellis_kernels": {tname[l]: {"kernel_ms": round(kt[tname[l]], 4), "frac": round(launch_bytes / (kt[tname[l]] * 1e-3) / HBM_PEAK, 5)} for l, kt in ktimes1_others.items()},
-                         "other_trellis_kernels_note": "sora_rx_set_trellis, each alone on the chip: k_viterbi = two frames per wave, k_viterbi16 = eight per wave (the one for 32768 and more captures in flight), k_viterbi16w = the frames' "
-                                                       "trace-back windows decoded side by side and proven afterwards (the one below that; the automatic choice follows depth x max_captures; the proof runs in the waves of the finishing kernel, k_win_redo_finish)",
-                         "valu": valu_roofline(nfr, ms_per_step) if not shard else None},
-            "kernel_ms": {k: round(v, 4) for k, v in ktimes.items()},
-            "kernel_ms_one_call_in_flight": {k: round(v, 4) for k, v in ktimes1.items()},
+            "realtime": {"factor": round(ms_per_step * 1e-3 / air_s, 7), "channels_20mhz_in_real_time": round(air_s / (ms_per_step * 1e-3), 1)},
         }
+        if full:
+            dom = max((k for k in ktimes if k.startswith("k_")), key=lambda k: ktimes[k])
+            launch_bytes = nfr * fpc * FRAME_SAMPLES * ALG_BYTES_PER_SAMPLE
+            ach = launch_bytes / (ktimes[dom] * 1e-3)
+            ach1 = launch_bytes / (ktimes1[dom] * 1e-3)
+            out["ms_per_step_profiled"] = round((t3 - t2) / args.steps * 1e3, 4)
+            out["gathered_rows"] = gathered_rows; out["gathered"] = gathered
+            out["parity"] = {"against": kind, "captures_checked": len(idx), "ok": parity_ok, "host_rows_ok": host_rows_ok}
+            out["delivery"]["last_calls_mpdu_ok"] = mpdu_ok
+            out["realtime"]["call_latency_ms_one_in_flight"] = round(sum(v for k, v in ktimes1.items()), 4)
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(ach1 / 1e9, 2), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                               "frac": round(ach1 / HBM_PEAK, 5), "traffic": measured_traffic(dom) if nfr == FRAMES_PER_GPU and not shard else None,
+                               "traffic_source": _traffic_profile()[1],
+                               "algorithmic_bytes_per_launch": launch_bytes, "kernel_ms": round(ktimes1[dom], 4),
+                               "kernel_ms_note": "mean launch duration with ONE call in flight (the kernel alone on the chip); with %d calls overlapped the same launch lasts %.4f ms (frac %.5f) because it shares the CUs" % (depth, ktimes[dom], ach / HBM_PEAK),
+                               "whole_path_frac": round(msps * 1e6 / world * ALG_BYTES_PER_SAMPLE / HBM_PEAK, 5),
+                               "other_trellis_kernels": {tname[l]: {"kernel_ms": round(kt[tname[l]], 4), "frac": round(launch_bytes / (kt[tname[l]] * 1e-3) / HBM_PEAK, 5)} for l, kt in ktimes1_others.items()},
+                               "other_trellis_kernels_note": "sora_rx_set_trellis, each alone on the chip: k_viterbi = two frames per wave, k_viterbi16 = eight per wave (the one for 32768 and more captures in flight), k_viterbi16w = the frames' "
+                                                             "trace-back windows decoded side by side and proven afterwards (the one below that; the automatic choice follows depth x max_captures; the proof runs in the waves of the finishing kernel, k_win_redo_finish)",
+                               "valu": valu_roofline(nfr, ms_per_step) if not shard else None}
+            out["kernel_ms"] = {k: round(v, 4) for k, v in ktimes.items()}
+            out["kernel_ms_one_call_in_flight"] = {k: round(v, 4) for k, v in ktimes1.items()}
         try:                                                        # where the library this run loaded came from
             from sora_amd import build as _b
             out["build"] = dict(_b.build_info(), loaded=os.environ.get("SORA_HIP_LIB") or "sora_amd/lib/libsora_hip.so")
@@ -529,7 +544,7 @@ def main():
             out["rx11n"] = bench_11n(torch, sora_amd, dev)
             out["rx11n_40"] = bench_ht40(torch, sora_amd, dev)
             out["shard_32x16"] = bench_shard_shape(torch, sora_amd, dev, oracle)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(iq, nfr * fpc)
             out["realtime"]["cpu_reference_factor_one_core"] = round(20.0 / out["cpu_baseline"]["single_core_value"], 4) if out["cpu_baseline"].get("single_core_value") else None
         if sections:                                                # the whole object to the file, the line without the side sections

@@ -1,6 +1,6 @@
 """bench.py's result line and --dump-outputs: the line is one compact JSON object whose `steps` are the timed steps and whose `ms_per_step` is one of
 them; the dump is what the last timed step delivered (result rows, MPDU bytes) as float32 / float64 .npy files, at most 64 MB, the same from
-run to run for the same arguments."""
+run to run for the same arguments.  A plain run carries the headline only; --full adds the reference check, the roofline and the CPU baseline."""
 import json
 import os
 import subprocess
@@ -64,7 +64,7 @@ def test_bench_line_and_dump_on_the_gpu(tmp_path):
     lines = []
     for d, k in (("a", 3), ("b", 7)):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(k), "--warmup", "2", "--frames", "256", "--check", "16",
-                            "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600)
+                            "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-3000:]
         out = [ln for ln in p.stdout.splitlines() if ln.strip()]
         assert len(out) == 1, p.stdout[-3000:]
@@ -75,3 +75,30 @@ def test_bench_line_and_dump_on_the_gpu(tmp_path):
     a, b = _load(str(tmp_path / "a")), _load(str(tmp_path / "b"))
     assert set(a) == set(b) and all(np.array_equal(a[f], b[f]) for f in a)
     assert len(a["row_index.npy"]) == lines[0]["delivery"]["rows_per_call"] and a["mpdu.npy"].size > 0
+
+
+FULL_ONLY = ("parity", "roofline", "kernel_ms", "kernel_ms_one_call_in_flight", "ms_per_step_profiled", "cpu_baseline", "gathered")
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_the_headline_alone(tmp_path):
+    """A run without --full prints the headline fields and none of what --full measures, and its timed steps deliver exactly what a --full
+    run's do: the two dumps are equal."""
+    lines = {}
+    for d, extra in (("plain", []), ("full", ["--full", "--check", "16", "--no-cpu-baseline"])):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--frames", "256",
+                            "--dump-outputs", str(tmp_path / d)] + extra, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(out) == 1, p.stdout[-3000:]
+        lines[d] = json.loads(out[0])
+    r = lines["plain"]
+    assert r["full"] is False and lines["full"]["full"] is True
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(r), r
+    assert r["metric"] == lines["full"]["metric"] and r["unit"] == "Msamples/s" and r["higher_is_better"] is True and r["dtype"] == lines["full"]["dtype"]
+    assert r["steps"] == 3 and r["timed_steps"] == 3 and r["value"] > 0 and r["ms_per_step"] > 0
+    assert r["delivery"]["calls_with_wrong_rows"] == 0 and r["delivery"]["calls_delivered_and_compared"] > 0, r["delivery"]
+    assert not set(FULL_ONLY) & set(r), set(FULL_ONLY) & set(r)
+    assert {"parity", "roofline", "kernel_ms_one_call_in_flight"} <= set(lines["full"]) and lines["full"]["parity"]["ok"]
+    a, b = _load(str(tmp_path / "plain")), _load(str(tmp_path / "full"))
+    assert set(a) == set(b) and all(np.array_equal(a[f], b[f]) for f in a)

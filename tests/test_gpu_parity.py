@@ -594,7 +594,7 @@ def test_host_descriptor_past_the_buffer_is_refused(sora, torch_cuda, oracle):
 def test_config3_full_batch_equals_the_reference_graph(sora, torch_cuda, oracle):
     """BASELINE configs[2] at its stated size: the bench workload (4096 captures x one 1500-byte 54 Mbps frame, same seeds)
     through one process call, every capture against the reference's own graph compiled from its sources -- event for event
-    (error code, source position, rate, length, FCS, MPDU bytes).  bench.py gates its headline on the same comparison."""
+    (error code, source position, rate, length, FCS, MPDU bytes).  bench.py --full checks its first call with the same comparison."""
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     import bench

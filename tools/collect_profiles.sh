@@ -14,7 +14,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks -o p -- p
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks1 -o p -- python $R/bench.py $QUICK --headline-only --min-seconds 2 --depth 1 --trellis 16 > $OUT/${TAG}_ks1_bench.json 2> $OUT/${TAG}_ks1.err
 # the PMC passes, once per trellis kernel (sora_rx_set_trellis: 16 = k_viterbi16, what the default bench uses; 64 = k_viterbi; 1 = the window-parallel k_viterbi16w)
 for T in ${TRELLISES:-16 64 1}; do
-  PMC="$QUICK --steps 3 --warmup 1 --depth 1 --trellis $T --min-seconds 0 --no-deliver"
+  PMC="$QUICK --full --steps 3 --warmup 1 --depth 1 --trellis $T --min-seconds 0 --no-deliver"
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_fetch -o p -- python $R/bench.py $PMC > /dev/null 2> $OUT/${TAG}_fetch.err
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_write -o p -- python $R/bench.py $PMC > /dev/null 2> $OUT/${TAG}_write.err
   rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $OUT/${TAG}_insts -o p -- python $R/bench.py $PMC > /dev/null 2> $OUT/${TAG}_insts.err

@@ -5,7 +5,7 @@ TAG=${1:-insts}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-PMC="--no-cpu-baseline --no-extras --check 64 --steps 3 --warmup 1 --depth 1 --trellis 16 --min-seconds 0 --no-deliver"
+PMC="--full --no-cpu-baseline --no-extras --check 64 --steps 3 --warmup 1 --depth 1 --trellis 16 --min-seconds 0 --no-deliver"
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $OUT/${TAG}_insts -o p -- python $R/bench.py $PMC > /dev/null 2> $OUT/${TAG}_insts.err
 I=$(find $OUT/${TAG}_insts -name "*counter_collection.csv" | head -1)
 python3 - "$I" <<'PY'

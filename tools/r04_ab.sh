@@ -7,7 +7,7 @@ for v in "$@"; do
   if [ "$v" = main ]; then unset SORA_HIP_LIB; else export SORA_HIP_LIB=$R/sora_amd/lib/variants/$v.so; fi
   for cfg in ${AB_CFGS:-"16:8:16" "0:2:64" "0:1:64"}; do
     IFS=: read q d t <<< "$cfg"
-    timeout 300 python bench.py --no-cpu-baseline --no-extras --hw-queues $q --depth $d --trellis $t --check 256 --min-seconds 1 ${AB_ARGS:-} 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --no-cpu-baseline --no-extras --hw-queues $q --depth $d --trellis $t --check 256 --min-seconds 1 ${AB_ARGS:-} 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('$v hwq $q depth $d trellis $t ms_per_step', d['ms_per_step'], 'in_flight', {k: round(v, 4) for k, v in d['kernel_ms'].items()}, 'alone', {k: round(v, 4) for k, v in d['kernel_ms_one_call_in_flight'].items()}, 'parity', d['parity']['ok'], d['frames_crc_ok'])"

@@ -4,7 +4,7 @@
 TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$R/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--no-cpu-baseline --no-extras --check 64 --steps 3 --warmup 1 --depth 1 --min-seconds 0 --no-deliver $*"
+ARGS="--full --no-cpu-baseline --no-extras --check 64 --steps 3 --warmup 1 --depth 1 --min-seconds 0 --no-deliver $*"
 timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAVES --output-format csv -d $OUT/${TAG}_i -o p -- python $R/bench.py $ARGS > /dev/null 2> $OUT/${TAG}_i.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_k -o p -- python $R/bench.py $ARGS > /dev/null 2> $OUT/${TAG}_k.err
 python - <<PY

@@ -4,7 +4,7 @@
 set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$R/gpurun_out; mkdir -p $OUT
 cd $R
-Q="--no-cpu-baseline --no-extras --check 64"
+Q="--full --no-cpu-baseline --no-extras --check 64"
 : > $OUT/r04_a_depth_table.txt
 for cfg in "0 1 16" "0 1 64" "0 2 16" "0 2 64" "0 3 64" "0 3 16" "0 4 16" "0 8 16" "16 8 16"; do
   set -- $cfg

@@ -11,5 +11,5 @@ rm -rf $OUT/r05_single
 cd $R
 timeout 200 python tools/pipe_timeline.py > $OUT/r05_pipe_timeline.txt 2>&1
 timeout 300 python tools/r05_window_latency.py --reps 40 > $OUT/r05_window_latency.json 2> $OUT/r05_window_latency.err
-timeout 900 python bench.py > $OUT/r05_final_bench.json 2> $OUT/r05_final_bench.err
+timeout 900 python bench.py --full > $OUT/r05_final_bench.json 2> $OUT/r05_final_bench.err
 tail -c 400 $OUT/r05_final_bench.json; tail -3 $OUT/r05_final_bench.err; cat $OUT/r05_pipe_timeline.txt | tail -14; head -30 $OUT/r05_single_capture_kernels.json

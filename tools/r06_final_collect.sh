@@ -13,6 +13,6 @@ python $R/tools/rocprof_kernels.py "$DB" --last 3 > $OUT/r06_single_capture_kern
 rm -rf $OUT/r06_single
 cd $R
 for a in "--shard" "--fsample6" ""; do echo "== probe_scan $a"; timeout 200 python tools/probe_scan.py $a 2>&1 | tail -9; done > $OUT/r06_probe_scan.txt
-timeout 600 python bench.py --shape shard --no-cpu-baseline > $OUT/r06_final_bench_shape_shard.json 2> $OUT/r06_final_bench_shape_shard.err
-timeout 1200 python bench.py > $OUT/r06_final_bench.json 2> $OUT/r06_final_bench.err
+timeout 600 python bench.py --full --shape shard --no-cpu-baseline > $OUT/r06_final_bench_shape_shard.json 2> $OUT/r06_final_bench_shape_shard.err
+timeout 1200 python bench.py --full > $OUT/r06_final_bench.json 2> $OUT/r06_final_bench.err
 tail -c 300 $OUT/r06_final_bench.json; tail -3 $OUT/r06_final_bench.err; cat $OUT/r06_probe_scan.txt | tail -30; head -12 $OUT/r06_final_kernel_stats_shard_32x16_one_call_in_flight.csv
