@@ -655,6 +655,27 @@ int   sora_rx11b_results_of(sora_rx11b_t* rx, int ticket, sora_frame_result* out
  * captures x frames rows and all mpdu_cap bytes, every call: give mpdu_cap the size the traffic needs (frames x MTU), not a worst case
  * (rows x 4096 costs tens of MB over the host link per call and delivers stale bytes behind h_counts[1]). */
 int   sora_rx11b_deliver_async(sora_rx11b_t* rx, int ticket, sora_frame_result* h_rows, size_t max_rows, uint32_t* h_counts, uint8_t* h_mpdu, size_t mpdu_cap);
+/* Stream continuation, as sora_rx_set_stream_mode (the live-source case: a host binds CreateDemodGraph11b to TRxStream, and the graph's state --
+ * the DC estimate, the energy detector, the facades a reset leaves alone, the harness's output buffer -- carries over from one read to the
+ * next).  With sora_rx11b_set_stream_mode(rx, 1) capture k of a process call CONTINUES capture k of the call before it:
+ *   - after a call, sora_rx11b_stream_consumed(rx, ticket, h, n) gives, per capture, the RESUME POINT: the number of 44 MHz samples of that
+ *     capture that are final.  It is a source-call boundary in plain carrier sense (no frame under way, no event pending) with only whole
+ *     28-sample calls in front of it; since the Seek behind a frame (352, 176, 64 or 32 samples) shifts the calls, it is a multiple of 4,
+ *     not of 28 (0 if the capture holds none).  Every row the call reports ends at or in front of it (end_sample <= resume point); a frame
+ *     still running at the end of the capture, or whose Seek the capture's end cut short, lies behind it and is NOT reported: the next call
+ *     finds it again, so every frame is reported exactly once.  When a capture holds more row events than max_frames_per_capture, its resume
+ *     point stops in front of the first event that found no row: no event is lost.  A zero-length capture leaves its stream as it was;
+ *   - the host builds the next call's capture k from the stream FROM THAT POINT on: the unconsumed tail of what it submitted plus whatever
+ *     has arrived since (capture lengths are still whole 28-sample source calls, offsets multiples of 4).  The library starts it with the
+ *     state the graph had at the resume point, so the rows of all the calls together (positions relative to their own capture: add the
+ *     stream position of its first sample) are exactly the events MAC11b_Receive reports on the uncut stream -- tests/test_gpu_stream11b.py
+ *     holds streams cut at random source calls to the compiled reference graph's events on the whole;
+ *   - calls of a handle in stream mode run one after the other (a process call first waits for both calls in flight: it needs their
+ *     records); throughput comes from many streams (captures) per call.  Both process forms and every pass plan work in stream mode.
+ *     sora_rx11b_stream_consumed exists for the most recent ticket only.  Switching the mode, either way, starts every stream afresh.
+ * Returns the previous mode; a negative argument only queries. */
+int   sora_rx11b_set_stream_mode(sora_rx11b_t* rx, int enable);
+int   sora_rx11b_stream_consumed(sora_rx11b_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps);
 
 /* ------------------------------------------------------------------------------------------------
  * Small device-memory helpers so a pure-C host needs no HIP headers.

@@ -35,6 +35,7 @@ constexpr uint32_t E_NOT_SUPPORTED = 0x80000003u, E_SFD_FAIL = 0x80000004u, E_SF
 enum { RATE_SYNC = 0, RATE_1M, RATE_2M, RATE_5P5M, RATE_11M };
 enum { NO_PEAK_FOUND = 0, PEAK_FOUND, PEAK_VALID, PEAK_VALIDED, BARKER_SYNCED };
 constexpr uint32_t kOutBuf = 4096;                                    // OUTPUTBUF_SIZE (fb11b_demod.cpp:21)
+constexpr uint32_t kRec11bMagic = 0x534F3142u;                        // a continuation record holds a resume point (a fresh stream is not all zeros)
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ int lane_of(int v, int l) { return __builtin_amdgcn_readlane(v, uni(l)); }
@@ -52,7 +53,10 @@ __device__ __forceinline__ uint32_t dot_sign(int rre, int rim, int xre, int xim)
 // fits 64 VGPRs and runs 8 waves per SIMD.  When a header announces 5.5 / 11 Mbps it abandons the capture and flags it; the CCK = true instantiation
 // (125 VGPRs, 4 waves per SIMD) then redoes the flagged captures from their first sample.  Both write the same rows: the result is what one kernel
 // with everything inlined gives (that single kernel cost every capture 7-13 % of its speed).
-template <bool CCK>
+// STREAM = true (sora_rx11b_set_stream_mode): the capture continues the stream its continuation record left off, and the
+// record and the resume point are rewritten by the pass that finishes the capture.  Every addition sits under "if constexpr (STREAM)": the
+// default kernels are the instruction stream they were.
+template <bool CCK, bool STREAM>
 __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
 {
     __shared__ uint8_t s_out_all[4][kOutBuf];
@@ -105,8 +109,39 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
     uint32_t byte_count = 0, crc32 = 0xFFFFFFFFu;                                         // TBB11bFrameSink
     uint32_t nfr = 0;
 
+    // ---- stream continuation.  A RESUME POINT is a source-call boundary in plain carrier sense (power == 0, nothing pending) with only whole
+    // 28-sample calls in front of it (a partial last call, or a Seek that the capture's end clipped, reads what the uncut stream does not) and
+    // no event behind it that found no row slot.  Everything the graph knows there: the facades graph_reset() leaves alone, the carrier-sense
+    // state that moves between resets (TEnergyDetect's average, counter and window, TDCEstimator's counter and sums) and the stale output
+    // buffer.  The record (kRec11bWords): [0] kRec11bMagic, [1] which of the two s_out copies holds the resume point's, [2..14] the registers,
+    // [16..23] the energy window, [24] the position, [25] the rows in front of it, then two 4 KiB copies of s_out.  The register part is
+    // written once, at the end of the capture: if the capture ends at a resume point, from the state there; else from rp_hdr (one word per
+    // lane), saved when a carrier-sense call that starts at a resume point does not end at one -- power comes up or the call is partial --,
+    // which happens once per frame, not once per call.  s_out changes only inside a frame, so it is written at the first resume point after
+    // one, to the copy the record does NOT name: a first pass that hands the capture to the CCK pass leaves the record as the CCK pass finds it.
+    uint32_t rp_hdr = 0, rp_bad = 0, s_hw = 0, half = 0, snapped = 0;
+    uint32_t* const rec = STREAM ? A.cont + (size_t)cap_i * kRec11bWords : nullptr;
+    if constexpr (STREAM) {
+        const uint32_t h = rec[lane];
+        const uint32_t wv = (uint32_t)__shfl((int)h, 16 + (lane & 7));
+        if ((uint32_t)lane_of((int)h, 0) == kRec11bMagic) {
+            auto w = [&](int k) __attribute__((always_inline)) { return (uint32_t)lane_of((int)h, k); };
+            half = w(1) & 1u; dc_re = (int)w(2); dc_im = (int)w(3); last_re = (int)w(4); last_im = (int)w(5); byte_reg = w(6); frame_length = w(7);
+            rate_kbps = w(8); frame_crc32 = w(9); avg_energy = w(10); ecount = w(11); update_cnt = w(12); sdc_re = (int)w(13); sdc_im = (int)w(14);
+            if (lane < 8) win[lane] = wv;
+            const uint4* src = reinterpret_cast<const uint4*>(rec + 64 + 1024 * half);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const uint4 v = src[lane + 64 * q]; uint32_t* d = reinterpret_cast<uint32_t*>(s_out) + 4 * (lane + 64 * q);
+                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+            }
+            lds_order();
+        }
+    }
+
     // (every lambda below is force-inlined: a called closure would keep the state it captures in scratch memory)
     auto graph_reset = [&]() __attribute__((always_inline)) {                                          // BB11bDemodCtx.reset() + pRxSource->Reset()
+        if constexpr (STREAM) s_hw = max(s_hw, min(byte_count, kOutBuf));                              // s_out bytes [0, byte_count) were written
         error_code = 0; power = 0; rxrate = RATE_SYNC; plcp_data = 0;
         avg_energy = 0; ecount = 0;
         update_cnt = 8; sdc_re = sdc_im = 0;
@@ -118,6 +153,12 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
         sym_n = 0; sym_byte = 0; hdr_n = 0; hdr_lo = hdr_hi = 0;
         byte_count = 0; crc32 = 0xFFFFFFFFu;
     };
+
+    // the record's register part as the state stands, one word per lane (a resume point at sample `at`).  (A macro: a closure defined outside
+    // the STREAM branches, even unused, moves the default kernels' spill slots.)
+#define RP_PACK(v, at) do { v = lane >= 16 && lane < 24 ? win[lane & 7] : 0u; const uint32_t w_[16] = { kRec11bMagic, 0u, (uint32_t)dc_re, (uint32_t)dc_im, \
+        (uint32_t)last_re, (uint32_t)last_im, byte_reg, frame_length, rate_kbps, frame_crc32, avg_energy, ecount, update_cnt, (uint32_t)sdc_re, (uint32_t)sdc_im, 0u }; \
+        for (int k_ = 0; k_ < 15; k_++) v = lane == k_ ? w_[k_] : v; v = lane == 24 ? (at) : lane == 25 ? nfr : v; } while (0)
 
     // ---- TBB11bFrameSink (PHY_11b.hpp:700-740)
     auto frame_sink = [&](uint32_t b) __attribute__((always_inline)) {
@@ -817,12 +858,28 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
 #define U(v) v = (decltype(v))uni((int)v)
         U(last_re); U(last_im); U(byte_reg); U(frame_length); U(rate_kbps); U(frame_crc32); U(ref_re); U(ref_im); U(qoff); U(cck_n); U(cck_even);
 #undef U
+        if constexpr (STREAM) {
+            if (!power && !rp_bad) {                                    // a resume point, unless an event found no row slot
+                if (nfr > A.max_frames) break;                          // (nothing behind that event is reported: stop here)
+                if (s_hw != 0) {                                        // s_out as it stands here: the whole copy first, then what frames rewrote
+                    const uint32_t nq = snapped ? (s_hw + 15u) >> 4 : kOutBuf / 16u;
+                    uint4* dst = reinterpret_cast<uint4*>(rec + 64 + 1024 * (half ^ 1u));
+                    lds_order();
+                    for (uint32_t g = (uint32_t)lane; g < nq; g += 64) {
+                        const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s_out) + 4 * g;
+                        dst[g] = make_uint4(s4[0], s4[1], s4[2], s4[3]);
+                    }
+                    snapped = 1; s_hw = 0;
+                }
+            }
+        }
         // ---- TMemSamples::Process (memsource.hpp:87-114)
         const bool ret = remain != 0;
         if (ret) {
             p_start = c_start; p_take = c_take; p_stale = c_stale;
             c_stale = c_start; c_start = pos; c_take = remain > 28 ? 28u : remain;
             pos += c_take; remain -= c_take;
+            if constexpr (STREAM) rp_bad |= c_take < 28u ? 1u : 0u;
             if (!power) {
                 // TDCRemove -> TBB11bRxSwitch -> TEnergyDetect -> TDCEstimator on the call's seven bursts (of four samples) at once: lane = sample.
                 // The only thing that moves inside a call is the DC estimate, once at most (every 8th burst, after burst j0 = update_cnt): the
@@ -855,6 +912,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
                 const unsigned long long evb = __ballot(lane < 28 && (lane & 3) == 0 && ecn >= 32u && (ecn >= 100u || avg >= thr));
                 const int js = evb != 0 ? __builtin_ctzll(evb) >> 2 : 7; // the burst that ends carrier sensing, if any
                 const int np = min(js + 1, 7), nd = min(js, 7);         // bursts through TEnergyDetect / through TDCEstimator
+                if constexpr (STREAM) if (js < 7 || c_take < 28u) RP_PACK(rp_hdr, c_start);     // this call started at a resume point
                 avg_energy = (uint32_t)lane_of((int)avg, 4 * (np - 1));
                 {                                                       // the window moves on by np entries
                     const uint32_t av8 = (uint32_t)__shfl((int)ave, 4 * (lane - 8));     // (a statement of its own: inside the select's arm it would run with
@@ -915,6 +973,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             }
             if (err == E_FRAME_OK || err == E_CRC32_FAIL) {             // "jump advance of the last CRC byte": Seek (memsource.hpp:116-150)
                 uint32_t off = rate_kbps == 1000 ? 8 * 11 * 4 : rate_kbps == 2000 ? 4 * 11 * 4 : rate_kbps == 5500 ? 8 * 2 * 4 : rate_kbps == 11000 ? 8 * 1 * 4 : 0;
+                if constexpr (STREAM) rp_bad |= off > remain ? 1u : 0u;   // the uncut stream seeks further than this capture reaches
                 off = min(off, remain); pos += off; remain -= off;
             }
             // pRxSource->Flush(): what is queued is padded with zero samples and pushed through (brick.h FlushPort);
@@ -939,11 +998,23 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
         }
         if (!ret) break;
     }
+    if constexpr (STREAM) {                                             // the latest resume point: record, rows in front of it, position
+        uint32_t v = rp_hdr;
+        if (!power && !rp_bad && nfr <= A.max_frames) RP_PACK(v, pos);
+        v = lane == 1 ? (snapped ? half ^ 1u : half) : v;
+        rec[lane] = v;
+        const uint32_t at = (uint32_t)lane_of((int)v, 24), nrows = (uint32_t)lane_of((int)v, 25);
+        if (lane == 0) { A.consumed[cap_i] = at; A.nframes[cap_i] = nrows; }
+        return;
+    }
     if (lane == 0) A.nframes[cap_i] = nfr;
+#undef RP_PACK
 }
 
-__global__ void __launch_bounds__(256, 4) k_rx11b(Rx11bArgs A) { rx11b_capture<false>(A); }
-__global__ void __launch_bounds__(256, 4) k_rx11b_cck(Rx11bArgs A) { rx11b_capture<true>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b(Rx11bArgs A) { rx11b_capture<false, false>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b_cck(Rx11bArgs A) { rx11b_capture<true, false>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b_stream(Rx11bArgs A) { rx11b_capture<false, true>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b_cck_stream(Rx11bArgs A) { rx11b_capture<true, true>(A); }
 
 // how many captures the first pass handed over (the automatic pass plan's measurement): one block
 __global__ void __launch_bounds__(1024) k_rx11b_count_flagged(const uint32_t* __restrict__ needs_cck, uint32_t ncaps, uint32_t* __restrict__ out)
@@ -995,6 +1066,9 @@ struct sora_rx11b {
     int  pass_plan = 2;
     bool auto_single = false;       // automatic plan: what the most recent measurement said (more than half of a call's captures carried CCK frames)
     uint32_t auto_calls = 0;        // ... and every 16th call of a single-pass run is a two-pass call again, to measure
+    // sora_rx11b_set_stream_mode: capture k of a call continues capture k of the call before it (allocated when the mode is first enabled)
+    bool stream_mode = false;
+    uint32_t* d_cont = nullptr; uint32_t* d_consumed = nullptr;
 };
 
 #define HIPCHK11(call) do { hipError_t _e = (call); if (_e != hipSuccess) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, #call, (int)_e); } while (0)
@@ -1009,7 +1083,7 @@ static void rx11b_free(sora_rx11b_t* rx)
             if (S.ev_done) (void)hipEventDestroy(S.ev_done);
         sora_internal_dense_free(&S.dense);
     }
-    (void)hipFree(rx->d_iq_own);
+    (void)hipFree(rx->d_iq_own); (void)hipFree(rx->d_cont); (void)hipFree(rx->d_consumed);
     delete rx;
 }
 
@@ -1060,6 +1134,8 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
     if (!rx || (ncaps && (!d_iq || !caps))) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_process_dev: null argument", 0);
     if (ncaps > rx->cfg.max_captures) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_rx11b_process_dev: more captures than max_captures", 0);
     HIPCHK11(hipSetDevice(rx->cfg.device));
+    // stream mode: this call continues the records the one before it leaves, so calls run one after the other
+    if (rx->stream_mode) for (Slot11b& Q : rx->slot) HIPCHK11(hipStreamSynchronize(Q.stream));
     rx->next = slots_next(rx->slot, kSlots11b);                                       // an unused slot, else a released call's, else the oldest call's
     Slot11b& S = rx->slot[rx->next];
     std::vector<CapDesc>& h = S.h_desc;
@@ -1081,6 +1157,7 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
     Rx11bArgs A;
     A.iq = reinterpret_cast<const uint32_t*>(d_iq); A.caps = S.d_caps; A.ncaps = (uint32_t)ncaps; A.thr = rx->cfg.cca_pwr_threshold;
     A.max_frames = rx->cfg.max_frames_per_capture; A.rows = S.d_rows; A.nframes = S.d_nframes; A.mpdu = S.d_mpdu; A.crc = rx->d_crc; A.needs_cck = S.d_needs_cck;
+    A.cont = rx->stream_mode ? rx->d_cont : nullptr; A.consumed = rx->stream_mode ? rx->d_consumed : nullptr;
     // The pass plan.  Automatic (default): a two-pass call also counts, on the device, how many captures its first pass handed over; once such a
     // count has come back (no waiting: the event is only queried) and says "more than half", the following calls go straight through the CCK
     // instantiation -- which decodes all four rates with identical rows -- except every 16th, which is a two-pass call again and measures.
@@ -1094,7 +1171,8 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
     bool single = rx->pass_plan == 1;
     if (rx->pass_plan == 2 && rx->auto_single && (++rx->auto_calls & 15u) != 0u) single = true;
     HIPCHK11(hipMemsetAsync(S.d_needs_cck, single ? 1 : 0, 4 * ncaps, S.stream));
-    if (!single) hipLaunchKernelGGL(k_rx11b, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, S.stream, A);
+    const dim3 grid((unsigned)((ncaps + 3) / 4));
+    if (!single) hipLaunchKernelGGL(rx->stream_mode ? k_rx11b_stream : k_rx11b, grid, dim3(256), 0, S.stream, A);
     if (!single && rx->pass_plan == 2 && !S.flagged_pending) {
         hipLaunchKernelGGL(k_rx11b_count_flagged, dim3(1), dim3(1024), 0, S.stream, (const uint32_t*)S.d_needs_cck, (uint32_t)ncaps, S.d_flagged);
         S.h_flagged[1] = (uint32_t)ncaps;
@@ -1103,7 +1181,7 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
         S.flagged_pending = true;
     }
     // redoes the captures the first pass flagged (a wave of any other capture returns at once)
-    hipLaunchKernelGGL(k_rx11b_cck, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, S.stream, A);
+    hipLaunchKernelGGL(rx->stream_mode ? k_rx11b_cck_stream : k_rx11b_cck, grid, dim3(256), 0, S.stream, A);
     HIPCHK11(hipGetLastError());
     return SORA_OK;
 }
@@ -1191,6 +1269,36 @@ int sora_rx11b_set_single_pass(sora_rx11b_t* rx, int enable)
     const int old = rx->pass_plan;
     if (enable >= 0) { rx->pass_plan = enable > 2 ? 2 : enable; rx->auto_single = false; rx->auto_calls = 0; }
     return old;
+}
+int sora_rx11b_set_stream_mode(sora_rx11b_t* rx, int enable)
+{
+    if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_set_stream_mode: null handle", 0);
+    const int old = rx->stream_mode ? 1 : 0;
+    if (enable < 0) return old;
+    HIPCHK11(hipSetDevice(rx->cfg.device));
+    for (Slot11b& S : rx->slot) HIPCHK11(hipStreamSynchronize(S.stream));
+    if (enable && !rx->d_cont) {
+        HIPCHK11(hipMalloc((void**)&rx->d_cont, 4 * (size_t)kRec11bWords * rx->cfg.max_captures));
+        HIPCHK11(hipMalloc((void**)&rx->d_consumed, 4 * (size_t)rx->cfg.max_captures));
+    }
+    if (rx->d_cont) {                                                                 // switching either way starts every stream afresh
+        HIPCHK11(hipMemset(rx->d_cont, 0, 4 * (size_t)kRec11bWords * rx->cfg.max_captures));
+        HIPCHK11(hipMemset(rx->d_consumed, 0, 4 * (size_t)rx->cfg.max_captures));
+    }
+    rx->stream_mode = enable != 0;
+    return old;
+}
+int sora_rx11b_stream_consumed(sora_rx11b_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps)
+{
+    if (!rx || !h_consumed) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_stream_consumed: null argument", 0);
+    if (!rx->stream_mode) return sora_internal_fail(SORA_ERR_FAILED, "sora_rx11b_stream_consumed: the handle is not in stream mode", 0);
+    Slot11b* S = slot11b_of(rx, ticket);
+    if (!S || ticket != rx->seq) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_stream_consumed: only the most recent call's resume points exist", 0);
+    if (ncaps > S->ncaps) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_stream_consumed: more captures than the call had", 0);
+    HIPCHK11(hipSetDevice(rx->cfg.device));
+    HIPCHK11(hipStreamSynchronize(S->stream));
+    if (ncaps) HIPCHK11(hipMemcpy(h_consumed, rx->d_consumed, 4 * ncaps, hipMemcpyDeviceToHost));
+    return SORA_OK;
 }
 int sora_rx11b_wait(sora_rx11b_t* rx, int ticket)
 {

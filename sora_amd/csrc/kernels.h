@@ -220,9 +220,15 @@ struct Rx11bArgs {
     const uint32_t* crc;        // CRC-32 table
     // [ncaps]: set by the first pass for a capture in which a header announces 5.5 / 11 Mbps; such captures are redone by k_rx11b_cck
     uint32_t*       needs_cck;
+    // stream continuation (sora_rx11b_set_stream_mode): capture k of this call continues capture k of the call before it; null = off
+    uint32_t*       cont;       // [ncaps][kRec11bWords] the continuation records: read at entry, rewritten by the pass that finishes the capture
+    uint32_t*       consumed;   // [ncaps] the capture's last resume point, in 44 MHz samples: the host submits the stream from there on next time
 };
+constexpr uint32_t kRec11bWords = 64 + 2 * 1024;    // registers and energy window, then two copies of the 4 KiB output buffer (k_rx11b.hip)
 __global__ void k_rx11b(Rx11bArgs A);
 __global__ void k_rx11b_cck(Rx11bArgs A);
+__global__ void k_rx11b_stream(Rx11bArgs A);        // the same two passes, in stream form
+__global__ void k_rx11b_cck_stream(Rx11bArgs A);
 
 // one event of the 40 MHz HT front end (k_scan_ht40 in k_rx11n.hip), row cap * max_frames + i
 struct Ht40Found {
