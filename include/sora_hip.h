@@ -503,6 +503,33 @@ int   sora_rx11n_wait_any(sora_rx11n_t* rx, int* ticket);
 int   sora_rx11n_results_of(sora_rx11n_t* rx, int ticket, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap);
 /* as sora_rx11b_deliver_async */
 int   sora_rx11n_deliver_async(sora_rx11n_t* rx, int ticket, sora_frame_result* h_rows, size_t max_rows, uint32_t* h_counts, uint8_t* h_mpdu, size_t mpdu_cap);
+/* Stream continuation, as sora_rx11b_set_stream_mode (the live-source case: a host binds CreateDemodGraph11n to TRxStream, and the graph's
+ * carrier-sense state -- the two chains' MimoAutoCorr rings and running sums, the delayed-energy ring, the TCCA11n counters -- carries over from
+ * one read to the next).  With sora_rx11n_set_stream_mode(rx, 1) capture k of a process call CONTINUES capture k of the call before it; one
+ * descriptor addresses the same range of both chain buffers, as in every call:
+ *   - after a call, sora_rx11n_stream_consumed(rx, ticket, h, n) gives, per capture, the RESUME POINT: the number of 40 MHz samples of that
+ *     capture that are final.  It is a position where a 4-sample burst boundary of the 20 MHz graph falls on a source-call boundary (14
+ *     samples at 20 MHz, 28 at 40 MHz) while the graph is in carrier sense; bursts restart at each post-event origin, which is a call
+ *     boundary, so it is a multiple of 28 (0 if the capture holds none).  Every row the call reports ends at or in front of it
+ *     (end_sample <= resume point);
+ *   - NO FLUSH: stream mode never issues the end-of-stream flush that ends a capture with the mode off (TMemSamples2 running dry: missing
+ *     symbols read as zeros).  A capture's end is not the stream's end, so a frame still running when the capture ends -- its L-LTF, SIG,
+ *     HT-LTF or data symbols reach past the capture -- lies behind the resume point and is NOT reported, nor decoded from zero padding: the
+ *     next call finds it again, so every frame is reported exactly once.  When a capture holds more row events than max_frames_per_capture,
+ *     its resume point stops in front of the first event that found no row: no event is lost.  A zero-length capture leaves its stream as
+ *     it was;
+ *   - the host builds the next call's capture k from the stream FROM THAT POINT on: the unconsumed tail of what it submitted plus whatever
+ *     has arrived since, in both chains (capture lengths are still whole 28-sample source calls).  The library starts it with the state the
+ *     graph had at the resume point, so the rows of all the calls together (positions relative to their own capture: add the stream position
+ *     of its first sample) are exactly the events RxThread reports on the uncut stream -- tests/test_gpu_stream11n.py holds streams cut at
+ *     random source calls to the compiled reference graph's events on the whole;
+ *   - calls of a handle in stream mode run one after the other (a process call first waits for every call in flight: it needs their
+ *     records); throughput comes from many streams (captures) per call.  Both process forms, every trellis choice and any depth work in stream
+ *     mode: the records belong to the handle, not to a pipeline.  sora_rx11n_stream_consumed exists for the most recent ticket only.
+ *     Switching the mode, either way, starts every stream afresh.
+ * Returns the previous mode; a negative argument only queries. */
+int   sora_rx11n_set_stream_mode(sora_rx11n_t* rx, int enable);
+int   sora_rx11n_stream_consumed(sora_rx11n_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps);
 
 /* ------------------------------------------------------------------------------------------------
  * The data field of an HT-mixed 40 MHz, two-stream frame (BASELINE.json configs[3]: 128-point FFT, MMSE MIMO detection, one decoder per

@@ -68,7 +68,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n", "sora_rx11b_create",
                       "sora_rx11b_destroy", "sora_rx11b_stream", "sora_rx11b_synchronize", "sora_rx11b_process_dev", "sora_rx11b_process", "sora_rx11b_results", "sora_rx11b_ticket",
                       "sora_rx11b_calls_in_flight", "sora_rx11b_set_single_pass", "sora_rx11b_wait", "sora_rx11b_wait_any", "sora_rx11b_stream_of", "sora_rx11b_results_of",
-                      "sora_rx11b_deliver_async", "sora_rx11b_set_stream_mode", "sora_rx11b_stream_consumed", "sora_rx11n_deliver_async", "sora_ht40_deliver_async",
+                      "sora_rx11b_deliver_async", "sora_rx11b_set_stream_mode", "sora_rx11b_stream_consumed", "sora_rx11n_deliver_async",
+                      "sora_rx11n_set_stream_mode", "sora_rx11n_stream_consumed", "sora_ht40_deliver_async",
            "sora_rx11n_create", "sora_rx11n_destroy", "sora_rx11n_stream", "sora_rx11n_process_dev", "sora_rx11n_process", "sora_rx11n_results",
            "sora_rx11n_set_depth", "sora_rx11n_set_trellis", "sora_rx11n_trellis", "sora_rx11n_window_stats", "sora_rx11n_synchronize", "sora_rx11n_ticket", "sora_rx11n_wait",
                       "sora_rx11n_wait_any", "sora_rx11n_results_of",
@@ -251,6 +252,8 @@ def load(build_if_missing=True):
     L.sora_rx11n_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11n_process.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11n_set_depth.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.sora_rx11n_set_stream_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.sora_rx11n_stream_consumed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
     L.sora_rx11n_ticket.argtypes = [ctypes.c_void_p]
     L.sora_rx11n_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.sora_rx11n_wait_any.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
@@ -730,6 +733,23 @@ class Rx11n:
     def trellis(self):
         """the trellis kernel the next call uses: 64, 16 or 1 (TRELLIS_WINDOWED)"""
         return int(self._L.sora_rx11n_trellis(self._h))
+
+    def ticket(self):
+        """ticket of the most recent process call (0: none)"""
+        return self._L.sora_rx11n_ticket(self._h)
+
+    def set_stream_mode(self, enable=-1):
+        """1: capture k of a call continues capture k of the call before it (sora_hip.h: sora_rx11n_set_stream_mode); returns the previous mode"""
+        r = int(self._L.sora_rx11n_set_stream_mode(self._h, int(enable)))
+        if r not in (0, 1):
+            raise SoraError(r, (self._L.sora_hip_last_error() or b"").decode())
+        return r
+
+    def stream_consumed(self, ticket, ncaps):
+        """per capture of the most recent call: 40 MHz samples that are final = where the next call's capture must start in the stream"""
+        out = np.zeros(ncaps, np.uint32)
+        _check(self._L.sora_rx11n_stream_consumed(self._h, int(ticket), out.ctypes.data, int(ncaps)))
+        return out
 
     def window_stats(self):
         v = (ctypes.c_ulonglong * 4)()

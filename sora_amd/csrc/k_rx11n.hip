@@ -126,7 +126,14 @@ struct FrameLds {
     alignas(4) uint8_t joined[256];
     uint8_t  dtab[208];
 };
+// stream continuation (sora_rx11n_set_stream_mode): the carrier-sense rings at the latest resume point in front of a detection (k_scan11n_stream)
+struct RingLds {                   // the same layout as the head of ScanLds
+    uint32_t his[2][32]; int hcr[2][32], hci[2][32], he[2][32];
+    long long his_e[64];
+};
+constexpr uint32_t kRec11nMagic = 0x534F314Eu;     // a continuation record holds a resume point (a fresh stream is all zeros)
 }  // namespace
+constexpr uint32_t kRec11nWords = 64 + 4 * 64 + 128;   // header, the four MimoAutoCorr rings of both chains, the 64 delayed energies
 
 // HT40 = false: the reference's 20 MHz graph (k_scan11n).  HT40 = true: the same front end on the legacy part of an HT-mixed 40 MHz frame
 // (k_scan_ht40): the legacy preamble and HT-SIG are the 20 MHz waveforms sent on both halves of the channel, the upper one rotated by
@@ -136,8 +143,22 @@ struct FrameLds {
 // accepted (PHY_11n.hpp:497 accepts 8..10 at 1500), and instead of queueing a 20 MHz data field the frame is recorded for the 40 MHz
 // data-field kernels (k_ht40.hip) with what they need from here: position, CFO (per 40 MHz sample) and the noise variance, estimated
 // from the difference of the two L-LTF symbols.  That part is this library's own definition: parity unpinned.
-template <bool HT40>
-__device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* found)
+//
+// STREAM = true (k_scan11n_stream, sora_rx11n_set_stream_mode): the capture continues the stream its continuation record
+// left off.  A RESUME POINT is a burst boundary of carrier sense that falls on a source-call boundary: 28 samples (20 MHz) apart from each
+// origin, and every post-event origin.  The record: [0] kRec11nMagic, [1] ring_pos, [2] his_index, [3..8] the running sums, [9..12] the
+// TCCA11n counters pf, pc, sense, timeout, then the rings in their LDS layout.  Three things differ from the default kernel:
+//   * carrier-sense blocks are 56 samples, so every block starts at a resume point, and carrier sense stops at the last resume point of the
+//     capture (a detection behind it cannot complete its L-LTF and SIG inside the capture);
+//   * a frame is taken only when all of its symbols lie inside the capture (no flush: a capture's end is not the stream's end), and only when
+//     it finds a row slot; else the capture ends at the latest resume point in front of its detection.  That point is the detecting block's
+//     start or its middle (sample 28): at the detection, before the block's ring writes, the rings as they stand there -- the block's own
+//     samples in front of it, the block-start values behind -- go to an LDS copy with the sums and counters of that point.  That costs one
+//     copy per detection and nothing per block, and it is exact: nothing but the block's writes moved the rings since the block started;
+//   * the record is written once, at the end of the capture, from the rings or their copy (a zero-length capture leaves it as it was).
+// Every addition sits under "if constexpr (STREAM)": the default kernels are the instruction stream they were.
+template <bool HT40, bool STREAM = false>
+__device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* found, uint32_t* cont = nullptr, uint32_t* consumed = nullptr)
 {
     __shared__ ScanLds s_w[4];
     __shared__ uint8_t s_lut[6][256];
@@ -159,11 +180,35 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
     const Fft64Tw tw = fft64_twiddles(A.T, lane & 15);
     auto nosync = []() __attribute__((always_inline)) { wsync(); };
 
+    int sr[2] = { 0, 0 }, si[2] = { 0, 0 }, se[2] = { 0, 0 };
+    int ring_pos = 0, his_index = 0;
+    // stream mode: the counters the next carrier sense starts from, the state at the latest resume point in front of a detection (sv_*, RingLds),
+    // and where the capture ends
+    RingLds* SV = nullptr;
+    uint32_t* const rec = STREAM ? cont + (size_t)cap * kRec11nWords : nullptr;
+    int ld_pf = 0, ld_pc = 0, ld_sense = 0, ld_to = 0;
+    int sv_ring = 0, sv_hisi = 0, sv_sr[2] = { 0, 0 }, sv_si[2] = { 0, 0 }, sv_se[2] = { 0, 0 }, sv_pf = 0, sv_pc = 0, sv_sense = 0, sv_to = 0;
+    uint32_t sv_pos = 0, fin_pos = 0; bool saved = false, fin = false;
+    bool fresh = true;
+    if constexpr (STREAM) {
+        __shared__ RingLds s_sv[4];
+        SV = &s_sv[wv];
+        const uint32_t h = rec[lane];
+        if ((uint32_t)__builtin_amdgcn_readlane((int)h, 0) == kRec11nMagic) {
+            fresh = false;
+            auto w = [&](int k) __attribute__((always_inline)) { return __builtin_amdgcn_readlane((int)h, k); };
+            ring_pos = w(1); his_index = w(2); sr[0] = w(3); sr[1] = w(4); si[0] = w(5); si[1] = w(6); se[0] = w(7); se[1] = w(8);
+            ld_pf = w(9); ld_pc = w(10); ld_sense = w(11); ld_to = w(12);
+            const uint32_t* rw = rec + 64;
+            W.his[lane >> 5][lane & 31] = rw[lane]; W.hcr[lane >> 5][lane & 31] = (int)rw[64 + lane];
+            W.hci[lane >> 5][lane & 31] = (int)rw[128 + lane]; W.he[lane >> 5][lane & 31] = (int)rw[192 + lane];
+            W.his_e[lane] = reinterpret_cast<const long long*>(rec + 64 + 256)[lane];
+        }
+    }
+    if (fresh)
     for (int k = lane; k < 64; k += 64) { W.his[0][k & 31] = 0; W.his[1][k & 31] = 0; W.hcr[k >> 5][k & 31] = 0; W.hci[k >> 5][k & 31] = 0;
         W.he[k >> 5][k & 31] = 0; W.his_e[k] = 0x7FFFFFFFFFFFFFFFll; }
     wsync();
-    int sr[2] = { 0, 0 }, si[2] = { 0, 0 }, se[2] = { 0, 0 };
-    int ring_pos = 0, his_index = 0;
     uint32_t origin = 0, nfr = 0;
     Rx11bRow* rows = A.rows + (size_t)cap * A.max_frames;
 
@@ -171,9 +216,15 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
         // ================================================================ carrier sense from `origin` (cca_11n.hpp:46-127)
         const uint32_t nb_total = (n20 - origin + 3) / 4;
         bool pf = false, timeout = false; int pc = 0, sense = 0;
+        // stream mode: 56-sample blocks, up to the capture's last resume point
+        constexpr uint32_t kBlk = STREAM ? 56u : 64u;
+        const uint32_t cs_end = STREAM ? (n20 - origin) / 28 * 28 : nb_total * 4;
+        bool b_pf = false, b_to = false; int b_pc = 0, b_sense = 0, c_pf = 0, c_pc = 0, c_sense = 0, c_to = 0;
+        if constexpr (STREAM) { pf = ld_pf != 0; pc = ld_pc; sense = ld_sense; timeout = ld_to != 0; ld_pf = ld_pc = ld_sense = ld_to = 0; }
         int64_t det_at = -1;
-        for (uint32_t base = 0; base < nb_total * 4 && det_at < 0; base += 64) {
-            const int lim = (int)min(64u, nb_total * 4 - base);
+        for (uint32_t base = 0; base < cs_end && det_at < 0; base += kBlk) {
+            const int lim = (int)min(kBlk, cs_end - base);
+            if constexpr (STREAM) { b_pf = pf; b_pc = pc; b_sense = sense; b_to = timeout; }
             int pr[2], pi[2], pe[2], cre[2], cim[2], een[2]; uint32_t xr[2];
             const int slot = (ring_pos + lane) & 31;
 #pragma unroll
@@ -238,9 +289,32 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
                     const uint32_t s4 = base + (uint32_t)i - 3;
                     if (timeout && (s4 + 3) / 14 != (s4 + 7) / 14) { timeout = false; pf = false; pc = 0; sense = 0; }
                 }
+                if constexpr (STREAM) if (i == 27) { c_pf = pf; c_pc = pc; c_sense = sense; c_to = timeout; }   // the block's middle resume point
             }
             const int ne = det >= 0 ? det : lim;
             const int na = det >= 0 ? (det | 3) + 1 : lim;
+            if constexpr (STREAM) {
+                if (det >= 0) {
+                    // the latest resume point in front of the detecting burst: the block's start (m = 0) or its middle (m = 28).  The rings there:
+                    // slot ring_pos + j (j < 32) holds lane j's sample if j < m, else what it held when the block started
+                    const int m = (det & ~3) >= 28 ? 28 : 0;
+                    if (lane < 32) {
+#pragma unroll
+                        for (int r = 0; r < 2; r++) {
+                            SV->his[r][slot] = lane < m ? xr[r] : W.his[r][slot]; SV->hcr[r][slot] = lane < m ? cre[r] : W.hcr[r][slot];
+                            SV->hci[r][slot] = lane < m ? cim[r] : W.hci[r][slot]; SV->he[r][slot] = lane < m ? een[r] : W.he[r][slot];
+                        }
+                    }
+                    SV->his_e[(his_index + lane) & 63] = lane < m ? energy : olde;
+                    sv_ring = (ring_pos + m) & 31; sv_hisi = (his_index + m) & 63;
+#pragma unroll
+                    for (int r = 0; r < 2; r++) {
+                        sv_sr[r] = m ? __shfl(pr[r], 27) : sr[r]; sv_si[r] = m ? __shfl(pi[r], 27) : si[r]; sv_se[r] = m ? __shfl(pe[r], 27) : se[r];
+                    }
+                    sv_pf = m ? c_pf : b_pf; sv_pc = m ? c_pc : b_pc; sv_sense = m ? c_sense : b_sense; sv_to = m ? c_to : b_to;
+                    sv_pos = origin + base + (uint32_t)m;
+                }
+            }
             if (lane < ne) W.his_e[(his_index + lane) & 63] = energy;
             if (lane < na && lane >= na - 32) {
 #pragma unroll
@@ -252,10 +326,14 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
             wsync();
             if (det >= 0) det_at = (int64_t)base + na;
         }
+        if constexpr (STREAM) if (det_at < 0) { ld_pf = pf; ld_pc = pc; ld_sense = sense; ld_to = timeout; fin_pos = origin + cs_end; fin = true; }
         if (det_at < 0) break;
         const uint32_t n_real = n20 - origin;
         const uint32_t n_pad = (n_real + 3) & ~3u;                           // the last burst is delivered zero-padded
         const uint32_t l0 = (uint32_t)det_at;
+        // stream mode: the L-LTF and the three SIG symbols inside the capture, and a row slot for the event every such frame raises; else the
+        // capture ends in front of the detection
+        if constexpr (STREAM) if (l0 + 128 + 240 > n_real || nfr >= A.max_frames) { saved = true; break; }
         if (l0 + 128 > n_pad) break;
         // ================================================================ L-LTF: CFO, compensation, four FFTs, SISO channel
         int cfo;
@@ -418,6 +496,10 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
             const uint32_t S = mcs == 8 ? 104u : 208u, sps = code_rate == 0 ? S / 2 : S / 4 * 3;     // soft values / trellis steps per symbol
             const uint32_t nsym = (tr_end + sps - 1) / sps;                  // the symbol in which the decoder passes tr_end
             const uint32_t a_data = a + 240;
+            if constexpr (STREAM) {                                          // all of the data field inside the capture, or no event (and no flush)
+                if (a_data + 80 * nsym <= n_real) { nproc = nsym; event = true; queue = true; nsoft = nsym * S; last_burst_end = a_data + 80 * nsym; }
+            }
+            else {
             if (a_data < n_pad) nproc = min(nsym, (n_pad - a_data + 79) / 80);
             if (nproc == nsym) { event = true; queue = true; nsoft = nsym * S; last_burst_end = min(a_data + 80 * nsym, n_pad); }
             else if (a + 160 < n_pad && nproc > 0 && (nproc * S) % 312 != 0) {
@@ -427,7 +509,9 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
                 const uint32_t steps = code_rate == 0 ? nsoft / 2 : nsoft / 4 * 3;
                 if (steps >= tr_end) { event = true; queue = true; last_burst_end = n_pad; }
             }
+            }
         }
+        if constexpr (STREAM) if (!event) { saved = true; break; }          // the frame runs past the capture: the next call finds it
         if (!event) break;                                                   // the capture ended inside a frame without an event
         const uint32_t abs_end = origin + last_burst_end;
         const uint32_t call = (abs_end - 1) / 14;
@@ -458,10 +542,35 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
         nfr++;
         origin = 14 * (call + 1);
     }
+    if constexpr (STREAM) {
+        // the capture's latest resume point: the copy in front of a detection, the end of carrier sense, or the origin behind the last event
+        if (!fin && !saved) fin_pos = origin;
+        if (saved) fin_pos = sv_pos;
+        if (n20 != 0) {                                                      // (a zero-length capture leaves its stream as it was)
+            const RingLds* src = saved ? SV : reinterpret_cast<const RingLds*>(&W);
+            wsync();
+            uint32_t* rw = rec + 64;
+            rw[lane] = src->his[lane >> 5][lane & 31]; rw[64 + lane] = (uint32_t)src->hcr[lane >> 5][lane & 31];
+            rw[128 + lane] = (uint32_t)src->hci[lane >> 5][lane & 31]; rw[192 + lane] = (uint32_t)src->he[lane >> 5][lane & 31];
+            reinterpret_cast<long long*>(rec + 64 + 256)[lane] = src->his_e[lane];
+            const int hw[13] = { (int)kRec11nMagic, saved ? sv_ring : ring_pos, saved ? sv_hisi : his_index, saved ? sv_sr[0] : sr[0], saved ? sv_sr[1] : sr[1],
+                                 saved ? sv_si[0] : si[0], saved ? sv_si[1] : si[1], saved ? sv_se[0] : se[0], saved ? sv_se[1] : se[1],
+                                 saved ? sv_pf : ld_pf, saved ? sv_pc : ld_pc, saved ? sv_sense : ld_sense, saved ? sv_to : ld_to };
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = 0; k < 13; k++) v = lane == k ? (uint32_t)hw[k] : v;
+            rec[lane] = v;
+        }
+        if (lane == 0) { consumed[cap] = 2 * fin_pos; A.nframes[cap] = nfr; }
+        return;
+    }
     if (lane == 0) A.nframes[cap] = nfr;
 }
 
 __global__ void __launch_bounds__(256) k_scan11n(Scan11nArgs A) { scan11n_body<false>(A, nullptr); }
+// the stream form (sora_rx11n_set_stream_mode): cont = the continuation records [ncaps][kRec11nWords], consumed = each capture's latest
+// resume point in 40 MHz samples
+__global__ void __launch_bounds__(256) k_scan11n_stream(Scan11nArgs A, uint32_t* cont, uint32_t* consumed) { scan11n_body<false, true>(A, nullptr, cont, consumed); }
 // The front end of the 40 MHz HT receiver (sora_ht40_process_captures_dev, k_ht40.hip): carrier sense, L-LTF, L-SIG / HT-SIG on the
 // duplicated legacy preamble -> one Ht40Found record per event.
 __global__ void __launch_bounds__(256) k_scan_ht40(Scan11nArgs A, Ht40Found* found) { scan11n_body<true>(A, found); }
@@ -672,6 +781,10 @@ struct sora_rx11n {
     static constexpr int kMaxDepth = 8;
     Pipe11n* pipes[kMaxDepth] = {};
     int depth = 1, cur = 0, next_ticket = 0; bool started = false;
+    // sora_rx11n_set_stream_mode: capture k of a call continues capture k of the call before it; the records belong to the handle, not to a
+    // pipeline (allocated when the mode is first enabled)
+    bool stream_mode = false;
+    uint32_t* d_cont = nullptr; uint32_t* d_consumed = nullptr;
 };
 
 #define HIPCHK11N(call) do { hipError_t _e = (call); if (_e != hipSuccess) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, #call, (int)_e); } while (0)
@@ -691,7 +804,7 @@ static void rx11n_free(sora_rx11n_t* rx)
 {
     if (!rx) return;
     for (Pipe11n* p : rx->pipes) pipe11n_free(p);
-    (void)hipFree(rx->d_iq_own[0]); (void)hipFree(rx->d_iq_own[1]);
+    (void)hipFree(rx->d_iq_own[0]); (void)hipFree(rx->d_iq_own[1]); (void)hipFree(rx->d_cont); (void)hipFree(rx->d_consumed);
     delete rx;
 }
 static hipError_t pipe11n_create(sora_rx11n_t* rx, Pipe11n** out, int index = 0)
@@ -828,6 +941,36 @@ static Pipe11n* pipe11n_of(sora_rx11n_t* rx, int ticket)
     for (int i = 0; i < rx->depth; i++) if (rx->pipes[i] && rx->pipes[i]->ticket == ticket) return rx->pipes[i];
     return nullptr;
 }
+int sora_rx11n_set_stream_mode(sora_rx11n_t* rx, int enable)
+{
+    if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_set_stream_mode: null handle", 0);
+    const int old = rx->stream_mode ? 1 : 0;
+    if (enable < 0) return old;
+    HIPCHK11N(hipSetDevice(rx->cfg.device));
+    for (Pipe11n* p : rx->pipes) if (p) HIPCHK11N(hipStreamSynchronize(p->stream));
+    if (enable && !rx->d_cont) {
+        HIPCHK11N(hipMalloc((void**)&rx->d_cont, 4 * (size_t)kRec11nWords * rx->cfg.max_captures));
+        HIPCHK11N(hipMalloc((void**)&rx->d_consumed, 4 * (size_t)rx->cfg.max_captures));
+    }
+    if (rx->d_cont) {                                                                 // switching either way starts every stream afresh
+        HIPCHK11N(hipMemset(rx->d_cont, 0, 4 * (size_t)kRec11nWords * rx->cfg.max_captures));
+        HIPCHK11N(hipMemset(rx->d_consumed, 0, 4 * (size_t)rx->cfg.max_captures));
+    }
+    rx->stream_mode = enable != 0;
+    return old;
+}
+int sora_rx11n_stream_consumed(sora_rx11n_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps)
+{
+    if (!rx || !h_consumed) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_stream_consumed: null argument", 0);
+    if (!rx->stream_mode) return sora_internal_fail(SORA_ERR_FAILED, "sora_rx11n_stream_consumed: the handle is not in stream mode", 0);
+    Pipe11n* P = pipe11n_of(rx, ticket);
+    if (!P || ticket != rx->next_ticket) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_stream_consumed: only the most recent call's resume points exist", 0);
+    if (ncaps > P->ncaps) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_stream_consumed: more captures than the call had", 0);
+    HIPCHK11N(hipSetDevice(rx->cfg.device));
+    HIPCHK11N(hipStreamSynchronize(P->stream));
+    if (ncaps) HIPCHK11N(hipMemcpy(h_consumed, rx->d_consumed, 4 * ncaps, hipMemcpyDeviceToHost));
+    return SORA_OK;
+}
 int sora_rx11n_ticket(sora_rx11n_t* rx) { return rx && rx->started ? rx->pipes[rx->cur]->ticket : 0; }
 int sora_rx11n_wait(sora_rx11n_t* rx, int ticket)
 {
@@ -882,6 +1025,8 @@ int sora_rx11n_process_dev(sora_rx11n_t* rx, const sora_complex16* d_iq0, const 
     if (!rx || (ncaps && (!d_iq0 || !d_iq1 || !caps))) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_process_dev: null argument", 0);
     if (ncaps > rx->cfg.max_captures) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_rx11n_process_dev: more captures than max_captures", 0);
     HIPCHK11N(hipSetDevice(rx->cfg.device));
+    // stream mode: this call continues the records the one before it leaves, so calls run one after the other
+    if (rx->stream_mode) for (Pipe11n* p : rx->pipes) if (p) HIPCHK11N(hipStreamSynchronize(p->stream));
     const int idx = next_pipe11n(rx);                                            // consecutive calls rotate over the pipelines; a released one first
     Pipe11n* P = rx->pipes[idx];
     std::vector<CapDesc> h(ncaps);                                               // validated first: a refused call leaves the handle's calls intact
@@ -908,7 +1053,8 @@ int sora_rx11n_process_dev(sora_rx11n_t* rx, const sora_complex16* d_iq0, const 
     Scan11nArgs S;
     S.iq0 = A.iq0; S.iq1 = A.iq1; S.caps = P->d_caps; S.ncaps = (uint32_t)ncaps; S.max_frames = A.max_frames; S.rows = P->d_rows; S.nframes = P->d_nframes;
     S.T = rx->T; S.sincos = rx->sincos; S.atan = rx->atan; S.frames = P->d_frames; S.jobs = P->d_jobs; S.njobs = P->d_njobs; S.nrows = nrows;
-    hipLaunchKernelGGL(k_scan11n, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S);
+    if (rx->stream_mode) hipLaunchKernelGGL(k_scan11n_stream, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S, rx->d_cont, rx->d_consumed);
+    else hipLaunchKernelGGL(k_scan11n, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S);
     Frame11nArgs F;
     F.iq0 = A.iq0; F.iq1 = A.iq1; F.caps = P->d_caps; F.frames = P->d_frames; F.njobs = P->d_njobs; F.nrows = nrows; F.T = rx->T; F.sincos = rx->sincos; F.atan = rx->atan;
     F.soft = P->d_soft; F.jobs = P->d_jobs; F.vout = P->d_vout; F.rows = P->d_rows; F.mpdu = P->d_mpdu;
