@@ -138,8 +138,18 @@ int  sora_rx_process_dump(sora_rx_t* rx, const void* h_dump, size_t dump_bytes, 
  *     stream position of its first sample) are exactly the events the graph reports on the uncut stream -- tests/test_gpu_stream.py holds a
  *     40 MHz stream cut at arbitrary 28-sample boundaries to the compiled reference graph's events on the whole;
  *   - calls of a handle in stream mode run one after the other (a process call first waits for the one before it: it needs its records);
- *     throughput comes from many streams (captures) per call.  sora_rx_reset, and switching the mode, start every stream afresh.  Not
- *     available for sample_rate_mhz = 44 (SORA_E_NOT_SUPPORTED).  Returns the previous mode; a negative argument only queries. */
+ *     throughput comes from many streams (captures) per call.  sora_rx_reset, and switching the mode, start every stream afresh;
+ *   - sample_rate_mhz = 44 (CreateDemodGraph11a_44M): TDownSample44_40 is empty only on its period, 308 source samples in, 280 out.  So a
+ *     resume point is also a multiple of 280 resampled samples (140 at 20 MHz), and `used` is one.  The host keeps the 44 MHz source,
+ *     resumes it at used * 11 / 10 (a multiple of 308 = 11 RX_BLOCKs) and ingests each piece on its own (sora_hip_ingest with
+ *     SORA_INGEST_44TO40, or sora_rx_process_dump); a piece may end at any RX_BLOCK.  Several pieces in one dump: each starts a multiple of
+ *     11 RX_BLOCKs in (zero blocks as padding), capture offset (first block / 11) * 280, length sora_hip_ingest_count(piece bytes, flags).
+ *     A frame is reported by the first call whose capture holds a resume point behind it.  That point may lie up to 280 resampled samples
+ *     behind the frame's end (more if another frame follows at once), so a capture can end before it; the frame is then withheld: no row,
+ *     and no MPDU byte written, also not into an array bound with sora_rx_bind_mpdu (its data field is decoded all the same, and again by
+ *     the call that reports it).  So every row still ends in front of `used`, and the rows of all calls are the uncut stream's events
+ *     (tests/test_gpu_stream44.py).
+ *   Returns the previous mode; a negative argument only queries. */
 int  sora_rx_set_stream_mode(sora_rx_t* rx, int enable);
 int  sora_rx_stream_consumed(sora_rx_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps);
 

@@ -317,10 +317,11 @@ __device__ __noinline__ SigOut header_section(ScanTabs tabs, uint32_t lts_start_
 
 // Stream continuation: the record of a resume point (see k_scan).  Out of line, everything by value: its selects and shuffles stay out of the
 // carrier-sense loop's register allocation (inlined at its two call sites it cost the loop 56 more SGPR spills and 48 bytes of scratch).
+// Word 42 is not state: it holds the number of frames in front of the resume point, for cont_rows.
 constexpr uint32_t kContMagic = 0x534F5241u;
 __device__ __noinline__ void cont_store(uint32_t* crec, uint32_t* consumed, uint32_t Hv, uint32_t Zr, uint32_t Zi, uint32_t Ze, int rr, int ri, int re,
                                         uint32_t sense_count, uint32_t high_count, int peak_corr, int peak_index, uint32_t dc_cnt, int sum_dc_re, int sum_dc_im,
-                                        int dc_re, int dc_im, uint32_t at)
+                                        int dc_re, int dc_im, uint32_t at, uint32_t nfr)
 {
     const int l = threadIdx.x;
     // window element (l & 3) sits in lanes 4 (l & 3) ..
@@ -328,11 +329,23 @@ __device__ __noinline__ void cont_store(uint32_t* crec, uint32_t* consumed, uint
     const uint32_t hv = (uint32_t)__shfl((int)Hv, l & 15);
     uint32_t v = l < 16 ? hv : l < 20 ? zr : l < 24 ? zi : l < 28 ? ze : 0u;
     const uint32_t sc[16] = { (uint32_t)rr, (uint32_t)ri, (uint32_t)re, sense_count, high_count, (uint32_t)peak_corr, (uint32_t)peak_index, dc_cnt,
-                              (uint32_t)sum_dc_re, (uint32_t)sum_dc_im, (uint32_t)dc_re, (uint32_t)dc_im, at, kContMagic, 0u, 0u };
+                              (uint32_t)sum_dc_re, (uint32_t)sum_dc_im, (uint32_t)dc_re, (uint32_t)dc_im, at, kContMagic, nfr, 0u };
 #pragma unroll
     for (int k = 0; k < 16; k++) if (l == 28 + k) v = sc[k];
     crec[l] = v;
     if (l == 0) *consumed = at;
+}
+// In stream mode a capture's rows are the frames in front of its last resume point (0 if it holds none; k_scan clears word 42 at entry).  Each
+// lane reads back the word it wrote.  The rows k_scan wrote for frames behind it (rows[n .. written)) are withheld: marked invalid, so that
+// k_finish writes no MPDU of theirs, neither to the device array nor to one bound with sora_rx_bind_mpdu (their decode jobs still run).  Lane 0
+// wrote those rows and clears them.  Out of line for the same reason as cont_store: inlined, it moved k_scan's register figures.
+__device__ __noinline__ void cont_rows(const uint32_t* crec, uint32_t* nframes, FrameRow* rows, uint32_t written)
+{
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)crec[threadIdx.x], 42);
+    if (threadIdx.x == 0) {
+        *nframes = n;
+        for (uint32_t k = n; k < written; k++) rows[k].valid = 0;
+    }
 }
 
 // x / 14 and ceil(x / 14) for x < 2^31 (a source call = 14 samples at the 20 MHz rate) as a multiply: 0x92492493 = ceil(2^35 / 14)
@@ -409,15 +422,24 @@ __global__ void __launch_bounds__(64, 4) k_scan(ScanArgs A)
     // pending): everything the graph knows there is the record below.  The capture's last resume point is published (A.consumed) and its
     // record kept; the next call's capture k starts AT that point of the stream and the record is its initial state -- so what the graph
     // reports from there on is what it reports on the uncut stream, and a frame cut by the end of a capture is simply found again.
+    //
+    // The 44 MHz graph (A.keep_queue) has TDownSample44_40 in front, and that brick is empty only on its period: 308 source samples in, 280
+    // out, i.e. 140 samples here.  Only there can the host cut the 44 MHz source and ingest the next capture on its own, so at 44 MHz a resume
+    // point is also a multiple of 140.  The queue in front of TDownSample2 that survives a frame (s_next below) needs no record: in this graph
+    // s stays a multiple of 4 (a frame's end is a burst end, and the walk goes on at consumed_to), and 140 is a multiple of the burst and of
+    // the 14-sample source call, so that queue is empty at every such point.  A frame is only followed by a resume point once carrier sense
+    // reaches the next 140-multiple, so a capture's rows are the frames in front of its last resume point (cont_rows); a frame behind it is
+    // found again by the next call.  (At 40 MHz every frame is followed by one: the walk goes on at a source-call boundary in reset carrier sense.)
     const bool streaming = A.cont != nullptr;
     auto cont_save = [&](uint32_t at) {
         cont_store(A.cont + (size_t)cap_i * kContWords, A.consumed + cap_i, Hv, ac_re.Z, ac_im.Z, energy.Z, ac_re.reg, ac_im.reg, energy.reg, sense_count,
                 high_count, peak_corr, peak_index,
-                   dc_cnt, sum_dc_re, sum_dc_im, dc_re, dc_im, at << sh);
+                   dc_cnt, sum_dc_re, sum_dc_im, dc_re, dc_im, at << sh, nfr);
     };
     if (streaming) {
         if (lane == 0) A.consumed[cap_i] = 0;
         const uint32_t v = A.cont[(size_t)cap_i * kContWords + lane];
+        if (lane == 42) A.cont[(size_t)cap_i * kContWords + lane] = 0;        // no frame in front of a resume point yet
         if ((uint32_t)__builtin_amdgcn_readlane((int)v, 41) == kContMagic) {       // a record exists: this capture continues a stream
             auto sc = [&](int k) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 28 + k); };
             Hv = (uint32_t)__shfl((int)v, lane & 15);
@@ -479,11 +501,17 @@ __global__ void __launch_bounds__(64, 4) k_scan(ScanArgs A)
                 if (jraise < K) { const uint32_t be = s + 4u * jraise + 4u; ce_raise = call_end(be); K = min(K, jraise + 1u + ((ce_raise - be) >> 2)); }
             }
             if (streaming) {
-                const uint32_t m = s - div14(s) * 14u;                          // position in the source call
-                if (m == 0u && plain) cont_save(s);
-                // a pass ends at the next resume point (burst boundary = source-call boundary), so that it is seen: j bursts on, m + 4 j = 0 (mod 14): j = 3 (m / 2) (mod 7), 0 -> 7
-                const uint32_t j = (3u * (m >> 1)) % 7u;
-                K = min(K, j ? j : 7u);
+                if (A.keep_queue) {
+                    const uint32_t m = s % 140u;                                // position in TDownSample44_40's period
+                    if (m == 0u && plain) cont_save(s);
+                    if (m) K = min(K, (143u - m) >> 2);                         // a pass ends at the next one (35 bursts apart; rounded up, a pass always moves)
+                } else {
+                    const uint32_t m = s - div14(s) * 14u;                      // position in the source call
+                    if (m == 0u && plain) cont_save(s);
+                    // a pass ends at the next resume point (burst boundary = source-call boundary), so that it is seen: j bursts on, m + 4 j = 0 (mod 14): j = 3 (m / 2) (mod 7), 0 -> 7
+                    const uint32_t j = (3u * (m >> 1)) % 7u;
+                    K = min(K, j ? j : 7u);
+                }
             }
             PROBE_A(_tg, 1);
             PROBE_T0();
@@ -708,10 +736,11 @@ __global__ void __launch_bounds__(64, 4) k_scan(ScanArgs A)
         to_pending = false; cca_detected = 0; cs_reset();                            // BB11aDemodCtx.Reset(), every brick's Reset (fb11a_demod.cpp:64-70)
         PROBE_A(_tc, 7);
     }
-    // the capture ends in plain carrier sense: all of it is final
-    if (streaming && s == NS && !cca_detected && !sync_high && auto_count == 0 && !to_pending) cont_save(s);
+    // the capture ends in plain carrier sense (at 44 MHz: on the resampler's period): all of it is final
+    if (streaming && s == NS && !cca_detected && !sync_high && auto_count == 0 && !to_pending && (!A.keep_queue || s % 140u == 0u)) cont_save(s);
     flush_jobs();
-    if (lane == 0) A.nframes[cap_i] = nfr;
+    if (streaming) cont_rows(A.cont + (size_t)cap_i * kContWords, A.nframes + cap_i, A.frames + (size_t)cap_i * A.max_frames, min(nfr, A.max_frames));
+    else if (lane == 0) A.nframes[cap_i] = nfr;
     PROBE_ADDK(5);
 }
 

@@ -1382,8 +1382,6 @@ int sora_rx_set_stream_mode(sora_rx_t* rx, int enable)
     if (!rx) return SORA_ERR_INVALID_PARAM;
     const int old = rx->stream_mode ? 1 : 0;
     if (enable < 0) return old;
-    if (enable && rx->cfg.sample_rate_mhz == 44) return fail(SORA_E_NOT_SUPPORTED,
-            "sora_rx_set_stream_mode: not for the 44 MHz graph (its resampler's queue is not part of the continuation record)");
     HIPCHK(hipSetDevice(rx->cfg.device));
     for (RxPipe* q : rx->pipes) if (q) { const int rc = pipe_flush(q); if (rc) return rc; }
     if (enable && !rx->d_cont) {
