@@ -138,32 +138,21 @@ def load(build_if_missing=True):
     L.sora_hip_memcpy_h2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     L.sora_hip_memcpy_d2h.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     L.sora_rx_create.argtypes = [ctypes.POINTER(RxCfg), ctypes.POINTER(ctypes.c_void_p)]
-    L.sora_rx_destroy.argtypes = [ctypes.c_void_p]; L.sora_rx_destroy.restype = None
     L.sora_rx_reset.argtypes = [ctypes.c_void_p]
     L.sora_rx_flush.argtypes = [ctypes.c_void_p]
-    L.sora_rx_stream.argtypes = [ctypes.c_void_p]; L.sora_rx_stream.restype = ctypes.c_void_p
     L.sora_rx_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx_process.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx_results.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
                                   ctypes.c_void_p, ctypes.c_size_t]
     L.sora_rx_results_dev.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
-    L.sora_rx_ticket.argtypes = [ctypes.c_void_p]
-    L.sora_rx_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.sora_rx_wait_any.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-    L.sora_rx_results_of.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
-                                     ctypes.c_void_p, ctypes.c_size_t]
     L.sora_rx_results_dev_of.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
-    L.sora_rx_stream_of.argtypes = [ctypes.c_void_p, ctypes.c_int]; L.sora_rx_stream_of.restype = ctypes.c_void_p
     L.sora_rx_mpdu_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]; L.sora_rx_mpdu_bytes.restype = ctypes.c_size_t
-    L.sora_rx_deliver_async.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     L.sora_hip_host_alloc.argtypes = [ctypes.c_size_t]; L.sora_hip_host_alloc.restype = ctypes.c_void_p
     L.sora_hip_host_free.argtypes = [ctypes.c_void_p]; L.sora_hip_host_free.restype = None
     L.sora_rx_set_profiling.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.sora_rx_kernel_times.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.sora_rx_kernel_name.argtypes = [ctypes.c_size_t]; L.sora_rx_kernel_name.restype = ctypes.c_char_p
     L.sora_rx_set_depth.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.sora_rx_set_stream_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.sora_rx_stream_consumed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
     L.sora_rx_process_dump.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx_set_fused.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.sora_rx_set_trellis.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -190,9 +179,6 @@ def load(build_if_missing=True):
     L.sora_rx_kernel_name_fused.argtypes = [ctypes.c_size_t]; L.sora_rx_kernel_name_fused.restype = ctypes.c_char_p
     L.sora_ht40_symbols.argtypes = [ctypes.c_uint32] * 4; L.sora_ht40_symbols.restype = ctypes.c_uint32
     L.sora_ht40_create.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
-    L.sora_ht40_destroy.argtypes = [ctypes.c_void_p]; L.sora_ht40_destroy.restype = None
-    L.sora_ht40_stream.argtypes = [ctypes.c_void_p]; L.sora_ht40_stream.restype = ctypes.c_void_p
-    L.sora_ht40_synchronize.argtypes = [ctypes.c_void_p]
     L.sora_ht40_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Ht40Frame), ctypes.c_size_t, ctypes.c_void_p]
     L.sora_ht40_results.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t]
     L.sora_shard_unique_id.argtypes = [ctypes.c_void_p]
@@ -247,41 +233,28 @@ def load(build_if_missing=True):
     L.sora_hip_sig_demap11n.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_sig_decode11n.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
     L.sora_rx11n_create.argtypes = [ctypes.POINTER(RxCfg), ctypes.POINTER(ctypes.c_void_p)]
-    L.sora_rx11n_destroy.argtypes = [ctypes.c_void_p]; L.sora_rx11n_destroy.restype = None
-    L.sora_rx11n_stream.argtypes = [ctypes.c_void_p]; L.sora_rx11n_stream.restype = ctypes.c_void_p
     L.sora_rx11n_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11n_process.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11n_set_depth.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.sora_rx11n_set_stream_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.sora_rx11n_stream_consumed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
-    L.sora_rx11n_ticket.argtypes = [ctypes.c_void_p]
-    L.sora_rx11n_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.sora_rx11n_wait_any.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-    L.sora_rx11n_results_of.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t]
     L.sora_rx11n_results.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
                                      ctypes.c_void_p, ctypes.c_size_t]
     L.sora_rx11b_create.argtypes = [ctypes.POINTER(RxCfg), ctypes.POINTER(ctypes.c_void_p)]
     L.sora_rx11b_set_single_pass.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.sora_rx11b_set_stream_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.sora_rx11b_stream_consumed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
-    L.sora_rx11b_destroy.argtypes = [ctypes.c_void_p]; L.sora_rx11b_destroy.restype = None
-    L.sora_rx11b_stream.argtypes = [ctypes.c_void_p]; L.sora_rx11b_stream.restype = ctypes.c_void_p
-    L.sora_rx11b_synchronize.argtypes = [ctypes.c_void_p]
     L.sora_rx11b_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11b_process.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     _res_of = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t]
     _deliver = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     L.sora_ht40_process_captures_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
-    for pre in ("sora_rx11b", "sora_ht40"):
-        getattr(L, pre + "_ticket").argtypes = [ctypes.c_void_p]
-        getattr(L, pre + "_calls_in_flight").argtypes = [ctypes.c_void_p]
-        getattr(L, pre + "_wait").argtypes = [ctypes.c_void_p, ctypes.c_int]
-        getattr(L, pre + "_wait_any").argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        getattr(L, pre + "_stream_of").argtypes = [ctypes.c_void_p, ctypes.c_int]; getattr(L, pre + "_stream_of").restype = ctypes.c_void_p
-        getattr(L, pre + "_results_of").argtypes = _res_of
-        getattr(L, pre + "_deliver_async").argtypes = _deliver
-    L.sora_rx11n_deliver_async.argtypes = _deliver
-    L.sora_rx11n_synchronize.argtypes = [ctypes.c_void_p]
+    # what the four receive handles share (include/sora_hip.h: tickets, calls in flight, stream continuation where the handle has it)
+    vp = ctypes.c_void_p
+    shared = [("_destroy", [vp], None), ("_stream", [vp], vp), ("_ticket", [vp], ctypes.c_int), ("_wait", [vp, ctypes.c_int], ctypes.c_int),
+              ("_wait_any", [vp, ctypes.POINTER(ctypes.c_int)], ctypes.c_int), ("_stream_of", [vp, ctypes.c_int], vp), ("_results_of", _res_of, ctypes.c_int),
+              ("_deliver_async", _deliver, ctypes.c_int), ("_synchronize", [vp], ctypes.c_int), ("_calls_in_flight", [vp], ctypes.c_int),
+              ("_set_stream_mode", [vp, ctypes.c_int], ctypes.c_int), ("_stream_consumed", [vp, ctypes.c_int, vp, ctypes.c_size_t], ctypes.c_int)]
+    for pre in ("sora_rx", "sora_rx11b", "sora_rx11n", "sora_ht40"):
+        for suffix, args, res in shared:
+            if pre + suffix in EXPORTS:
+                f = getattr(L, pre + suffix); f.argtypes = args; f.restype = res
     L.sora_rx11b_results.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
                                      ctypes.c_void_p, ctypes.c_size_t]
     _lib = L
@@ -310,8 +283,74 @@ def _dev_ptr(x):
     raise TypeError("expected a torch CUDA tensor or an integer device address")
 
 
-class Rx:
+class _Handle:
+    """What the four receive handles share (include/sora_hip.h): their calls in flight -- tickets, wait, wait_any, deliver_async --, stream
+    continuation where the handle has it, and the step from a FrameResult table to dicts.  _pre: the prefix of the handle's C entry points."""
+    _pre = ""
+    _h = None
+
+    def _c(self, suffix):
+        return getattr(self._L, self._pre + suffix)
+
+    def close(self):
+        if self._h:
+            self._c("_destroy")(self._h); self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def ticket(self):
+        """ticket of the most recent process call (0: none)"""
+        return self._c("_ticket")(self._h)
+
+    def wait(self, ticket):
+        _check(self._c("_wait")(self._h, int(ticket)))
+
+    def wait_any(self):
+        """Block until some call with an enqueued delivery (deliver_async) has finished -> its ticket (the oldest finished one).  The call is then
+        released: the next process call may reuse its slot ahead of older calls still in flight."""
+        t = ctypes.c_int(0)
+        _check(self._c("_wait_any")(self._h, ctypes.byref(t)))
+        return t.value
+
+    def deliver_async(self, ticket, buf):
+        """Enqueue the delivery of the call's rows (+ MPDU array when buf.mpdu is not None) into the page-locked HostResults `buf`, behind the
+        call's kernels; valid after wait(ticket).  (buf.counts and buf.nrows start at the same address.)"""
+        _check(self._c("_deliver_async")(self._h, int(ticket), buf.rows.ctypes.data, len(buf.rows), buf.counts.ctypes.data,
+                                         buf.mpdu.ctypes.data if buf.mpdu is not None else None, buf.mpdu.size if buf.mpdu is not None else 0))
+
+    def set_stream_mode(self, enable=-1):
+        """1: capture k of a call continues capture k of the call before it (sora_hip.h: stream continuation); returns the previous mode"""
+        r = int(self._c("_set_stream_mode")(self._h, int(enable)))
+        if r not in (0, 1):
+            raise SoraError(r, (self._L.sora_hip_last_error() or b"").decode())
+        return r
+
+    def stream_consumed(self, ticket, ncaps):
+        """per capture of the most recent call: input-rate samples that are final = where the next call's capture must start in the stream"""
+        out = np.zeros(ncaps, np.uint32)
+        _check(self._c("_stream_consumed")(self._h, int(ticket), out.ctypes.data, int(ncaps)))
+        return out
+
+    @staticmethod
+    def _table(res, n, mp, every_row=False):
+        """the first n FrameResult rows -> dicts; "mpdu": the row's bytes of mp (rows with E_FRAME_OK / E_CRC32_FAIL, or every row), no key if mp is None"""
+        out = []
+        for r in res[:n]:
+            d = {f: getattr(r, f) for f, _ in FrameResult._fields_}
+            if mp is not None:
+                has = every_row or r.error_code in (E_FRAME_OK, E_CRC32_FAIL)
+                d["mpdu"] = mp[r.mpdu_offset:r.mpdu_offset + min(r.length, 4096)].tobytes() if has else b""
+            out.append(d)
+        return out
+
+
+class Rx(_Handle):
     """sora_rx_t: the 802.11a demod graph over a batch of captures."""
+    _pre = "sora_rx"
 
     def __init__(self, max_captures, max_total_samples, sample_rate_mhz=20, device=0, max_frames_per_capture=2,
                  cca_pwr_threshold=0):
@@ -327,16 +366,6 @@ class Rx:
         if os.environ.get("SORA_HIP_GRAPH"): self.set_graph(int(os.environ["SORA_HIP_GRAPH"]))
         if os.environ.get("SORA_HIP_TRELLIS"): self.set_trellis(int(os.environ["SORA_HIP_TRELLIS"]))
         if os.environ.get("SORA_HIP_FRONT"): self.set_front(int(os.environ["SORA_HIP_FRONT"]))
-
-    def close(self):
-        if self._h:
-            self._L.sora_rx_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def stream(self):
@@ -369,26 +398,13 @@ class Rx:
         arr, ptr = self._caps(captures)
         _hold(self, d_iq)
         _check(self._L.sora_rx_process_dev(self._h, _dev_ptr(d_iq), ptr, len(arr)))
-        return self._L.sora_rx_ticket(self._h)
+        return self.ticket()
 
     def process(self, h_iq, captures):
         a = np.ascontiguousarray(h_iq, np.int16).reshape(-1, 2)
         arr, ptr = self._caps(captures)
         _check(self._L.sora_rx_process(self._h, a.ctypes.data, len(a), ptr, len(arr)))
-        return self._L.sora_rx_ticket(self._h)
-
-    def set_stream_mode(self, enable=-1):
-        """1: capture k of a call continues capture k of the call before it (sora_hip.h: stream continuation); returns the previous mode"""
-        r = int(self._L.sora_rx_set_stream_mode(self._h, int(enable)))
-        if r not in (0, 1):
-            raise SoraError(r, (self._L.sora_hip_last_error() or b"").decode())
-        return r
-
-    def stream_consumed(self, ticket, ncaps):
-        """per capture of the most recent call: input-rate samples that are final = where the next call's capture must start in the stream"""
-        out = np.zeros(ncaps, np.uint32)
-        _check(self._L.sora_rx_stream_consumed(self._h, int(ticket), out.ctypes.data, int(ncaps)))
-        return out
+        return self.ticket()
 
     def process_dump(self, h_dump, flags, captures):
         """h_dump: the raw dump bytes in host memory -- a numpy uint8 array or a (pinned) torch CPU uint8 tensor, untouched until the call has
@@ -402,29 +418,10 @@ class Rx:
             self._keep = collections.deque(maxlen=17)
         self._keep.append(h_dump)
         _check(self._L.sora_rx_process_dump(self._h, ctypes.c_void_p(addr), nbytes, int(flags), ptr, len(arr)))
-        return self._L.sora_rx_ticket(self._h)
-
-    def ticket(self):
-        """ticket of the most recent process call (0: none)"""
-        return self._L.sora_rx_ticket(self._h)
-
-    def wait(self, ticket):
-        _check(self._L.sora_rx_wait(self._h, int(ticket)))
-
-    def wait_any(self):
-        """Block until some call with an enqueued delivery (deliver_async) has finished -> its ticket (the oldest finished one).  The call is then
-        released: the next process call may reuse its pipeline ahead of older calls still in flight."""
-        t = ctypes.c_int(0)
-        _check(self._L.sora_rx_wait_any(self._h, ctypes.byref(t)))
-        return t.value
+        return self.ticket()
 
     def mpdu_bytes(self, ticket):
         return int(self._L.sora_rx_mpdu_bytes(self._h, int(ticket)))
-
-    def deliver_async(self, ticket, buf):
-        """Enqueue the delivery of the call's rows (+ MPDU array when buf.mpdu is not None) into the page-locked HostResults `buf`."""
-        _check(self._L.sora_rx_deliver_async(self._h, int(ticket), buf.rows.ctypes.data, len(buf.rows), buf.nrows.ctypes.data,
-                                             buf.mpdu.ctypes.data if buf.mpdu is not None else None, buf.mpdu.size if buf.mpdu is not None else 0))
 
     def results_dev(self, ticket=None):
         """Device-resident results of the last call (or of the call `ticket` names): (rows int32 tensor [cap_rows, 9] (36-byte
@@ -542,14 +539,7 @@ class Rx:
             _check(self._L.sora_rx_results(self._h, res, max_frames, ctypes.byref(n), mp.ctypes.data if with_mpdu else None, mp.size))
         else:
             _check(self._L.sora_rx_results_of(self._h, int(ticket), res, max_frames, ctypes.byref(n), mp.ctypes.data if with_mpdu else None, mp.size))
-        out = []
-        for i in range(n.value):
-            r = res[i]
-            d = {f: getattr(r, f) for f, _ in FrameResult._fields_}
-            if with_mpdu:
-                d["mpdu"] = mp[r.mpdu_offset:r.mpdu_offset + r.length].tobytes() if r.error_code in (E_FRAME_OK, E_CRC32_FAIL) else b""
-            out.append(d)
-        return out
+        return self._table(res, n.value, mp if with_mpdu else None)
 
 
 ROW_DTYPE = np.dtype([("capture_id", "<u4"), ("start_sample", "<u4"), ("end_sample", "<u4"), ("error_code", "<u4"), ("rate_kbps", "<u4"),
@@ -605,8 +595,9 @@ class HostResults:
             pass
 
 
-class Rx11b:
+class Rx11b(_Handle):
     """sora_rx11b_t: the 802.11b demod graph (44 MHz samples) over a batch of captures."""
+    _pre = "sora_rx11b"
 
     def __init__(self, max_captures, max_total_samples, device=0, max_frames_per_capture=8, cca_pwr_threshold=0):
         L = load()
@@ -615,16 +606,6 @@ class Rx11b:
         _check(L.sora_rx11b_create(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h; self._L = L; self.cfg = cfg; self._keep = None
 
-    def close(self):
-        if self._h:
-            self._L.sora_rx11b_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def synchronize(self):
         _check(self._L.sora_rx11b_synchronize(self._h))
 
@@ -632,10 +613,7 @@ class Rx11b:
         arr, ptr = Rx._caps(captures)
         _hold(self, d_iq)
         _check(self._L.sora_rx11b_process_dev(self._h, _dev_ptr(d_iq), ptr, len(arr)))
-        return self._L.sora_rx11b_ticket(self._h)
-
-    def ticket(self):
-        return self._L.sora_rx11b_ticket(self._h)
+        return self.ticket()
 
     def calls_in_flight(self):
         return int(self._L.sora_rx11b_calls_in_flight(self._h))
@@ -643,33 +621,6 @@ class Rx11b:
     def set_single_pass(self, enable=-1):
         """the pass plan: 2 automatic (default), 1 every capture straight through the CCK-capable kernel, 0 always two passes; returns the previous plan"""
         return int(self._L.sora_rx11b_set_single_pass(self._h, int(enable)))
-
-    def set_stream_mode(self, enable=-1):
-        """1: capture k of a call continues capture k of the call before it (sora_hip.h: sora_rx11b_set_stream_mode); returns the previous mode"""
-        r = int(self._L.sora_rx11b_set_stream_mode(self._h, int(enable)))
-        if r not in (0, 1):
-            raise SoraError(r, (self._L.sora_hip_last_error() or b"").decode())
-        return r
-
-    def stream_consumed(self, ticket, ncaps):
-        """per capture of the most recent call: 44 MHz samples that are final = where the next call's capture must start in the stream"""
-        out = np.zeros(ncaps, np.uint32)
-        _check(self._L.sora_rx11b_stream_consumed(self._h, int(ticket), out.ctypes.data, int(ncaps)))
-        return out
-
-    def wait(self, ticket):
-        _check(self._L.sora_rx11b_wait(self._h, int(ticket)))
-
-    def wait_any(self):
-        """-> the ticket of the oldest finished call with an enqueued delivery (blocks until there is one); that call is released"""
-        t = ctypes.c_int(0)
-        _check(self._L.sora_rx11b_wait_any(self._h, ctypes.byref(t)))
-        return t.value
-
-    def deliver_async(self, ticket, buf):
-        """rows + dense MPDUs of the call into the page-locked HostResults `buf`, behind the call's kernels; valid after wait(ticket)"""
-        _check(self._L.sora_rx11b_deliver_async(self._h, int(ticket), buf.rows.ctypes.data, len(buf.rows), buf.counts.ctypes.data,
-                          buf.mpdu.ctypes.data if buf.mpdu is not None else None, buf.mpdu.size if buf.mpdu is not None else 0))
 
     def process(self, h_iq, captures):
         a = np.ascontiguousarray(h_iq, np.int16).reshape(-1, 2)
@@ -685,16 +636,12 @@ class Rx11b:
             _check(self._L.sora_rx11b_results(self._h, res, max_frames, ctypes.byref(n), mp.ctypes.data if with_mpdu else None, mp.size))
         else:
             _check(self._L.sora_rx11b_results_of(self._h, int(ticket), res, max_frames, ctypes.byref(n), mp.ctypes.data if with_mpdu else None, mp.size))
-        out = []
-        for r in res[:n.value]:
-            d = {f: getattr(r, f) for f, _ in FrameResult._fields_}
-            d["mpdu"] = mp[r.mpdu_offset:r.mpdu_offset + min(r.length, 4096)].tobytes() if with_mpdu and r.error_code in (E_FRAME_OK, E_CRC32_FAIL) else b""
-            out.append(d)
-        return out
+        return self._table(res, n.value, mp if with_mpdu else mp[:0])        # (without MPDUs every row's "mpdu" is b"")
 
 
-class Rx11n:
+class Rx11n(_Handle):
     """sora_rx11n_t: the 802.11n 2x2 demod graph (two RX chains at 40 MHz) over a batch of captures; rate_kbps = MCS index."""
+    _pre = "sora_rx11n"
 
     def __init__(self, max_captures, max_total_samples, device=0, max_frames_per_capture=8):
         L = load()
@@ -703,22 +650,9 @@ class Rx11n:
         _check(L.sora_rx11n_create(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h; self._L = L; self.cfg = cfg; self._keep = None
 
-    def close(self):
-        if self._h:
-            self._L.sora_rx11n_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def synchronize(self):
         """waits for every call in flight"""
-        t = self._L.sora_rx11n_ticket(self._h)
-        for k in range(max(1, t - 3), t + 1):
-            if self._L.sora_rx11n_wait(self._h, k) != SORA_OK:
-                pass                                                     # a ticket whose pipeline has been reused: that call finished long ago
+        _check(self._L.sora_rx11n_synchronize(self._h))
 
     def set_depth(self, depth=0):
         r = self._L.sora_rx11n_set_depth(self._h, depth)
@@ -734,47 +668,16 @@ class Rx11n:
         """the trellis kernel the next call uses: 64, 16 or 1 (TRELLIS_WINDOWED)"""
         return int(self._L.sora_rx11n_trellis(self._h))
 
-    def ticket(self):
-        """ticket of the most recent process call (0: none)"""
-        return self._L.sora_rx11n_ticket(self._h)
-
-    def set_stream_mode(self, enable=-1):
-        """1: capture k of a call continues capture k of the call before it (sora_hip.h: sora_rx11n_set_stream_mode); returns the previous mode"""
-        r = int(self._L.sora_rx11n_set_stream_mode(self._h, int(enable)))
-        if r not in (0, 1):
-            raise SoraError(r, (self._L.sora_hip_last_error() or b"").decode())
-        return r
-
-    def stream_consumed(self, ticket, ncaps):
-        """per capture of the most recent call: 40 MHz samples that are final = where the next call's capture must start in the stream"""
-        out = np.zeros(ncaps, np.uint32)
-        _check(self._L.sora_rx11n_stream_consumed(self._h, int(ticket), out.ctypes.data, int(ncaps)))
-        return out
-
     def window_stats(self):
         v = (ctypes.c_ulonglong * 4)()
         _check(self._L.sora_rx11n_window_stats(self._h, v))
         return {"boundaries": int(v[0]), "boundaries_failed": int(v[1]), "frames_decoded_again": int(v[2]), "units": int(v[3])}
 
-    def wait(self, ticket):
-        _check(self._L.sora_rx11n_wait(self._h, int(ticket)))
-
-    def wait_any(self):
-        """-> the ticket of the oldest finished call with an enqueued delivery (blocks until there is one); that call is released"""
-        t = ctypes.c_int(0)
-        _check(self._L.sora_rx11n_wait_any(self._h, ctypes.byref(t)))
-        return t.value
-
-    def deliver_async(self, ticket, buf):
-        """rows + dense MPDUs of the call into the page-locked HostResults `buf`, behind the call's kernels; valid after wait(ticket)"""
-        _check(self._L.sora_rx11n_deliver_async(self._h, int(ticket), buf.rows.ctypes.data, len(buf.rows), buf.counts.ctypes.data,
-                          buf.mpdu.ctypes.data if buf.mpdu is not None else None, buf.mpdu.size if buf.mpdu is not None else 0))
-
     def process_dev(self, d_iq0, d_iq1, captures):
         arr, ptr = Rx._caps(captures)
         _hold(self, (d_iq0, d_iq1))
         _check(self._L.sora_rx11n_process_dev(self._h, _dev_ptr(d_iq0), _dev_ptr(d_iq1), ptr, len(arr)))
-        return self._L.sora_rx11n_ticket(self._h)
+        return self.ticket()
 
     def process(self, h_iq0, h_iq1, captures):
         a = np.ascontiguousarray(h_iq0, np.int16).reshape(-1, 2); b = np.ascontiguousarray(h_iq1, np.int16).reshape(-1, 2)
@@ -791,32 +694,18 @@ class Rx11n:
             _check(self._L.sora_rx11n_results(self._h, res, max_frames, ctypes.byref(n), mp.ctypes.data, mp.size))
         else:
             _check(self._L.sora_rx11n_results_of(self._h, int(ticket), res, max_frames, ctypes.byref(n), mp.ctypes.data, mp.size))
-        out = []
-        for r in res[:n.value]:
-            d = {f: getattr(r, f) for f, _ in FrameResult._fields_}
-            d["mpdu"] = mp[r.mpdu_offset:r.mpdu_offset + min(r.length, 4096)].tobytes() if r.error_code in (E_FRAME_OK, E_CRC32_FAIL) else b""
-            out.append(d)
-        return out
+        return self._table(res, n.value, mp)
 
 
-class RxHt40:
+class RxHt40(_Handle):
     """sora_ht40_t: the data field of HT-mixed 40 MHz two-stream frames (BASELINE configs[3]; parity unpinned, see include/sora_hip.h)."""
+    _pre = "sora_ht40"
 
     def __init__(self, max_frames, max_soft_values, device=0):
         L = load()
         h = ctypes.c_void_p()
         _check(L.sora_ht40_create(device, max_frames, max_soft_values, ctypes.byref(h)))
         self._h = h; self._L = L; self.max_frames = max_frames; self._keep = None
-
-    def close(self):
-        if self._h:
-            self._L.sora_ht40_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def synchronize(self):
         _check(self._L.sora_ht40_synchronize(self._h))
@@ -842,7 +731,7 @@ class RxHt40:
         arr = self.frames(descs); n = getattr(arr, "_n", len(arr))
         _hold(self, (d_iq0, d_iq1, d_weights)); self._n = n
         _check(self._L.sora_ht40_process_dev(self._h, _dev_ptr(d_iq0), _dev_ptr(d_iq1), arr, n, _dev_ptr(d_weights) if d_weights is not None else None))
-        t = self._L.sora_ht40_ticket(self._h)
+        t = self.ticket()
         self._nof = getattr(self, "_nof", {}); self._nof[t] = n
         self._prune_nof()
         return t
@@ -858,31 +747,14 @@ class RxHt40:
         arr, ptr = Rx._caps(captures)
         _hold(self, (d_iq0, d_iq1))
         _check(self._L.sora_ht40_process_captures_dev(self._h, _dev_ptr(d_iq0), _dev_ptr(d_iq1), ptr, len(arr), int(max_frames_per_capture)))
-        t = self._L.sora_ht40_ticket(self._h)
+        t = self.ticket()
         self._n = len(arr) * int(max_frames_per_capture)
         self._nof = getattr(self, "_nof", {}); self._nof[t] = self._n
         self._prune_nof()
         return t
 
-    def ticket(self):
-        return self._L.sora_ht40_ticket(self._h)
-
     def calls_in_flight(self):
         return int(self._L.sora_ht40_calls_in_flight(self._h))
-
-    def wait(self, ticket):
-        _check(self._L.sora_ht40_wait(self._h, int(ticket)))
-
-    def wait_any(self):
-        """-> the ticket of the oldest finished call with an enqueued delivery (blocks until there is one); that call is released"""
-        t = ctypes.c_int(0)
-        _check(self._L.sora_ht40_wait_any(self._h, ctypes.byref(t)))
-        return t.value
-
-    def deliver_async(self, ticket, buf):
-        """rows + dense MPDUs of the call into the page-locked HostResults `buf`, behind the call's kernels; valid after wait(ticket)"""
-        _check(self._L.sora_ht40_deliver_async(self._h, int(ticket), buf.rows.ctypes.data, len(buf.rows), buf.counts.ctypes.data,
-                          buf.mpdu.ctypes.data if buf.mpdu is not None else None, buf.mpdu.size if buf.mpdu is not None else 0))
 
     def results(self, with_mpdu=True, ticket=None):
         n2 = 2 * (self._n if ticket is None else self._nof.get(int(ticket), self.max_frames))
@@ -892,13 +764,9 @@ class RxHt40:
             _check(self._L.sora_ht40_results(self._h, res, n2, ctypes.byref(n), mp.ctypes.data if with_mpdu else None, mp.size))
         else:
             _check(self._L.sora_ht40_results_of(self._h, int(ticket), res, n2, ctypes.byref(n), mp.ctypes.data if with_mpdu else None, mp.size))
-        out = []
-        for r in res[:n.value]:
-            d = {f: getattr(r, f) for f, _ in FrameResult._fields_}
+        out = self._table(res, n.value, mp if with_mpdu else None, every_row=True)
+        for d in out:
             d["stream"] = d["start_sample"]
-            if with_mpdu:
-                d["mpdu"] = mp[r.mpdu_offset:r.mpdu_offset + r.length].tobytes()
-            out.append(d)
         return out
 
 

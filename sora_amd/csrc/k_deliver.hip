@@ -8,9 +8,12 @@
 //                  order, with each row's MPDU placed at the running sum of the MPDU lengths before it (two block scans)
 //   k_dense_mpdu   one wave per dense row: the MPDU bytes from the row's 4096-byte slot -> the dense MPDU block
 // then three copies into the caller's page-locked buffers: {rows, MPDU bytes}, the row table, the MPDU block.
+// sora_internal_rows_results: the same table walk on the host, for *_results / *_results_of of the 802.11b and 802.11n handles (a host wait).
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <string.h>
 #include "kernels.h"
+#include "host_calls.h"
 #include "../../include/sora_hip.h"
 
 namespace sora {
@@ -136,5 +139,46 @@ int sora_internal_dense_deliver(DenseStage* D, const Rx11bRow* d_rows, const uin
     if (e == hipSuccess && h_mpdu) e = hipMemcpyAsync(h_mpdu, D->d_mpdu, mpdu_cap, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "deliver_async", (int)e);
+    return SORA_OK;
+}
+
+int sora_internal_rows_results(const Rx11bRow* d_rows, const uint32_t* d_nframes, const uint8_t* d_mpdu, const sora_capture_desc* caps, uint32_t ncaps, uint32_t mf,
+                               int device, hipStream_t st, const char* who, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap)
+{
+    if (ncaps == 0) return SORA_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<Rx11bRow> rows((size_t)ncaps * mf); std::vector<uint32_t> nfr(ncaps);
+    HIPCHK(hipMemcpy(rows.data(), d_rows, sizeof(Rx11bRow) * rows.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(nfr.data(), d_nframes, 4 * (size_t)ncaps, hipMemcpyDeviceToHost));
+    // MPDU bytes: one bulk copy of the per-frame slots that are in use when that is cheap, else frame by frame
+    size_t used_rows = 0;
+    for (uint32_t c = 0; c < ncaps; c++) used_rows += nfr[c] < mf ? nfr[c] : mf;
+    std::vector<uint8_t> bulk;
+    const size_t slots = (size_t)ncaps * mf;
+    if (h_mpdu && used_rows > 16 && slots * 4096 <= ((size_t)1 << 30)) {
+        bulk.resize(slots * 4096);
+        HIPCHK(hipMemcpy(bulk.data(), d_mpdu, bulk.size(), hipMemcpyDeviceToHost));
+    }
+    size_t n = 0, moff = 0; int rc = SORA_OK;
+    for (uint32_t c = 0; c < ncaps; c++)
+        for (uint32_t i = 0; i < nfr[c] && i < mf; i++) {
+            const Rx11bRow& r = rows[(size_t)c * mf + i];
+            if (n >= max_out) { rc = SORA_ERR_CAPACITY; continue; }
+            sora_frame_result& o = out[n++];
+            memset(&o, 0, sizeof(o));
+            o.capture_id = caps[c].capture_id; o.end_sample = r.end_sample; o.error_code = r.error_code; o.rate_kbps = r.rate_kbps;
+            o.length = (uint16_t)r.length; o.crc32 = r.crc32; o.mpdu_offset = (uint32_t)moff;
+            if (i + 1 == mf && nfr[c] > mf) o.flags = SORA_ROW_TRUNCATED;             // more frames were found than the capture has rows
+            if (h_mpdu && (r.error_code == E_FRAME_OK || r.error_code == E_CRC32_FAIL)) {
+                const size_t len = r.length < 4096 ? r.length : 4096;
+                if (moff + len > mpdu_cap) { rc = SORA_ERR_CAPACITY; continue; }
+                if (!bulk.empty()) memcpy(h_mpdu + moff, bulk.data() + ((size_t)c * mf + i) * 4096, len);
+                else HIPCHK(hipMemcpy(h_mpdu + moff, d_mpdu + ((size_t)c * mf + i) * 4096, len, hipMemcpyDeviceToHost));
+                moff += len;
+            }
+        }
+    *nout = n;
+    if (rc != SORA_OK) return fail_at(rc, who, "output buffer too small");
     return SORA_OK;
 }

@@ -16,7 +16,6 @@
 // W = diag((W' H)_ss)^-1 W', W' = (H^H H + s2 I)^-1 H^H (unbiased MMSE) in single precision (documented tolerance: +-1 LSB of the int16 weight against a float64 evaluation,
 // tests/test_gpu_ht40.py).  The model the tests generate captures with is oracle/py_ht40.py.
 #include <vector>
-#include <thread>
 #include <algorithm>
 #include <string.h>
 #include "kernels.h"
@@ -378,6 +377,7 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
 }  // namespace sora
 
 // ------------------------------------------------------------------------------------------------ host side (C ABI, include/sora_hip.h)
+#include "host_calls.h"
 using namespace sora;
 
 // A handle owns kHt40Slots independent slots (stream + every intermediate), used round-robin: a call waits only for the call that used its
@@ -386,13 +386,10 @@ using namespace sora;
 static constexpr int kHt40Slots = 8;
 // frame: index into the call's described frames, -1 = header failed
 struct Ht40Event { uint32_t capture_id, end_sample, error_code, mcs, length, nsym; int frame; bool truncated; };
-struct Ht40Slot {
-    hipStream_t stream = nullptr;
+struct Ht40Slot : Call {       // the stream, ticket and completion state of the call this slot holds (host_calls.h)
     Ht40Frame* d_frames = nullptr; VitJob* d_jobs = nullptr; uint32_t* d_njobs = nullptr; Ht40Job* d_fjobs = nullptr;
     uint8_t* d_soft = nullptr; uint8_t* d_vout = nullptr; uint8_t* d_mpdu = nullptr; Rx11bRow* d_rows = nullptr;
     std::vector<sora_ht40_frame> h_frames; uint32_t nframes = 0;
-    int ticket = 0;             // of the call this slot holds (0: none)
-    hipEvent_t ev_done = nullptr; bool delivered = false, released = false;     // sora_ht40_wait_any (kernels.h: slots_next / slots_poll)
     // sora_ht40_process_captures_dev: the front end's arrays (grow-only) and what it found in this slot's call
     CapDesc* d_caps = nullptr; size_t caps_bytes = 0; Rx11bRow* d_scanrows = nullptr; size_t scanrows_bytes = 0;
     uint32_t* d_nfr = nullptr; size_t nfr_bytes = 0; Ht40Found* d_found = nullptr; size_t found_bytes = 0;
@@ -419,7 +416,6 @@ struct sora_ht40 {
     int lanes16 = 1;
 };
 
-#define HIPCHK40(call) do { hipError_t _e = (call); if (_e != hipSuccess) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, #call, (int)_e); } while (0)
 static constexpr uint32_t kVoutStride = 4352;
 
 static void ht40_free(sora_ht40_t* rx)
@@ -455,7 +451,7 @@ int sora_ht40_create(int device, uint32_t max_frames, uint64_t max_soft_values, 
     if (device < 0 || device >= ndev) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "device ordinal out of range", 0);
     if (max_soft_values * 2 + 4096 + 1024 >= (1ull << 32)) return sora_internal_fail(SORA_ERR_CAPACITY,
             "sora_ht40_create: max_soft_values exceeds the 32-bit offsets of one handle", 0);
-    HIPCHK40(hipSetDevice(device));
+    HIPCHK(hipSetDevice(device));
     sora_ht40_t* rx = new sora_ht40();
     rx->device = device; rx->max_frames = max_frames; rx->max_soft = max_soft_values;
     const size_t nj = 2 * (size_t)max_frames;
@@ -494,9 +490,7 @@ int sora_ht40_set_trellis(sora_ht40_t* rx, int lanes_per_pair)
 int sora_ht40_synchronize(sora_ht40_t* rx)
 {
     if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_synchronize: null handle", 0);
-    HIPCHK40(hipSetDevice(rx->device));
-    for (Ht40Slot& S : rx->slot) HIPCHK40(hipStreamSynchronize(S.stream));
-    return SORA_OK;
+    return calls_synchronize(rx->slot, kHt40Slots, rx->device);
 }
 
 // the data field of `nframes` described frames on slot S (its stream is idle): descriptors -> device, k_ht40_frame, the trellis kernel, k_ht40_finish
@@ -538,11 +532,11 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
     S.ticket = ++rx->seq; S.delivered = S.released = false;
     if (nframes == 0) return SORA_OK;
     for (int r = 0; r < 4; r++) nj_stage[r] = nj[r];
-    HIPCHK40(hipMemcpyAsync(S.d_frames, hf, sizeof(Ht40Frame) * nframes, hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemcpyAsync(S.d_frames, hf, sizeof(Ht40Frame) * nframes, hipMemcpyHostToDevice, S.stream));
     for (int r = 0; r < 3; r++)                                                   // (only the filled part of each code-rate list)
-        if (nj[r]) HIPCHK40(hipMemcpyAsync(S.d_jobs + r * stride, hj + r * stride, sizeof(VitJob) * nj[r], hipMemcpyHostToDevice, S.stream));
-    HIPCHK40(hipMemcpyAsync(S.d_njobs, nj_stage, 16, hipMemcpyHostToDevice, S.stream));
-    HIPCHK40(hipMemcpyAsync(S.d_fjobs, fj, sizeof(Ht40Job) * 2 * nframes, hipMemcpyHostToDevice, S.stream));
+        if (nj[r]) HIPCHK(hipMemcpyAsync(S.d_jobs + r * stride, hj + r * stride, sizeof(VitJob) * nj[r], hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemcpyAsync(S.d_njobs, nj_stage, 16, hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemcpyAsync(S.d_fjobs, fj, sizeof(Ht40Job) * 2 * nframes, hipMemcpyHostToDevice, S.stream));
     Ht40Args A;
     A.iq0 = reinterpret_cast<const uint32_t*>(d_iq0); A.iq1 = reinterpret_cast<const uint32_t*>(d_iq1); A.frames = S.d_frames; A.nframes = (uint32_t)nframes;
     A.T = rx->T; A.sincos = rx->sincos; A.atan = rx->atan; A.soft = S.d_soft; A.w_out = reinterpret_cast<uint32_t*>(d_weights); A.plan = nullptr;
@@ -556,17 +550,17 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
                 (uint32_t)stride, (const uint8_t*)S.d_soft, S.d_vout);
     Ht40FinishArgs Fi; Fi.jobs = S.d_fjobs; Fi.njobs = njobs; Fi.vout = S.d_vout; Fi.mpdu = S.d_mpdu; Fi.rows = S.d_rows; Fi.T = rx->T; Fi.plan = nullptr;
     hipLaunchKernelGGL(k_ht40_finish, dim3((njobs + 3) / 4), dim3(256), 0, S.stream, Fi);
-    HIPCHK40(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SORA_OK;
 }
 
 int sora_ht40_process_dev(sora_ht40_t* rx, const sora_complex16* d_iq0, const sora_complex16* d_iq1, const sora_ht40_frame* frames, size_t nframes, sora_complex16* d_weights)
 {
     if (!rx || (nframes && (!d_iq0 || !d_iq1 || !frames))) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_process_dev: null argument", 0);
-    HIPCHK40(hipSetDevice(rx->device));
-    rx->next = slots_next(rx->slot, kHt40Slots);                                  // an unused slot, else a released call's, else the oldest call's
+    HIPCHK(hipSetDevice(rx->device));
+    rx->next = call_next(rx->slot, kHt40Slots);                                   // an unused slot, else a released call's, else the oldest call's
     Ht40Slot& S = rx->slot[rx->next];
-    HIPCHK40(hipStreamSynchronize(S.stream));                                     // the call that used this slot kHt40Slots calls ago
+    HIPCHK(hipStreamSynchronize(S.stream));                                     // the call that used this slot kHt40Slots calls ago
     S.events.clear(); S.capture_mode = false; S.events_pending = false; S.plan_error = false;
     return ht40_submit(rx, S, d_iq0, d_iq1, frames, nframes, d_weights);
 }
@@ -584,10 +578,10 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     if (!rx || (ncaps && (!d_iq0 || !d_iq1 || !caps)) || max_frames_per_capture == 0) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
             "sora_ht40_process_captures_dev: bad argument", 0);
     if ((uint64_t)ncaps * max_frames_per_capture >= (1ull << 31)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_process_captures_dev: too many rows", 0);
-    HIPCHK40(hipSetDevice(rx->device));
-    rx->next = slots_next(rx->slot, kHt40Slots);                                  // an unused slot, else a released call's, else the oldest call's
+    HIPCHK(hipSetDevice(rx->device));
+    rx->next = call_next(rx->slot, kHt40Slots);                                   // an unused slot, else a released call's, else the oldest call's
     Ht40Slot& S = rx->slot[rx->next];
-    HIPCHK40(hipStreamSynchronize(S.stream));                                     // the call that used this slot kHt40Slots calls ago
+    HIPCHK(hipStreamSynchronize(S.stream));                                     // the call that used this slot kHt40Slots calls ago
     const uint32_t mf = max_frames_per_capture;
     const size_t nrows = ncaps * (size_t)mf;
     for (size_t i = 0; i < ncaps; i++) {
@@ -619,17 +613,17 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     S.ticket = ++rx->seq; S.delivered = S.released = false;
     S.h_plan[0] = S.h_plan[1] = S.h_plan[2] = S.h_plan[3] = 0;
     if (ncaps == 0) { S.events_pending = false; return SORA_OK; }
-    HIPCHK40(hipMemcpyAsync(S.d_caps, S.h_capsup, sizeof(CapDesc) * ncaps, hipMemcpyHostToDevice, S.stream));
-    HIPCHK40(hipMemsetAsync(S.d_nfr, 0, 4 * ncaps, S.stream));
+    HIPCHK(hipMemcpyAsync(S.d_caps, S.h_capsup, sizeof(CapDesc) * ncaps, hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemsetAsync(S.d_nfr, 0, 4 * ncaps, S.stream));
     { const int rc = sora_internal_scan_ht40(reinterpret_cast<const uint32_t*>(d_iq0), reinterpret_cast<const uint32_t*>(d_iq1), S.d_caps, (uint32_t)ncaps, mf,
             S.d_scanrows, S.d_nfr, S.d_found,
                                              rx->T, rx->sincos, rx->atan, S.stream); if (rc) return rc; }
     const size_t stride = 2 * (size_t)rx->max_frames;
     hipLaunchKernelGGL(k_ht40_plan, dim3(1), dim3(1024), 0, S.stream, (const CapDesc*)S.d_caps, (uint32_t)ncaps, mf, (const uint32_t*)S.d_nfr, (const Ht40Found*)S.d_found,
                        rx->max_frames, (uint64_t)rx->max_soft, kVoutStride, S.d_frames, S.d_jobs, (uint32_t)stride, S.d_njobs, S.d_fjobs, S.d_evtmpl, S.d_plan, S.d_evbase, S.d_evn);
-    HIPCHK40(hipMemcpyAsync(S.h_nfr, S.d_nfr, 4 * ncaps, hipMemcpyDeviceToHost, S.stream));
-    HIPCHK40(hipMemcpyAsync(S.h_found, S.d_found, sizeof(Ht40Found) * nrows, hipMemcpyDeviceToHost, S.stream));
-    HIPCHK40(hipMemcpyAsync(S.h_plan, S.d_plan, 16, hipMemcpyDeviceToHost, S.stream));
+    HIPCHK(hipMemcpyAsync(S.h_nfr, S.d_nfr, 4 * ncaps, hipMemcpyDeviceToHost, S.stream));
+    HIPCHK(hipMemcpyAsync(S.h_found, S.d_found, sizeof(Ht40Found) * nrows, hipMemcpyDeviceToHost, S.stream));
+    HIPCHK(hipMemcpyAsync(S.h_plan, S.d_plan, 16, hipMemcpyDeviceToHost, S.stream));
     // the kernels are launched for the most frames there can be and stop at the planned count
     const uint32_t bf = S.bound_frames, bj = 2 * bf;
     Ht40Args A;
@@ -644,7 +638,7 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
                 (uint32_t)stride, (const uint8_t*)S.d_soft, S.d_vout);
     Ht40FinishArgs Fi; Fi.jobs = S.d_fjobs; Fi.njobs = bj; Fi.vout = S.d_vout; Fi.mpdu = S.d_mpdu; Fi.rows = S.d_rows; Fi.T = rx->T; Fi.plan = S.d_plan;
     hipLaunchKernelGGL(k_ht40_finish, dim3((bj + 3) / 4), dim3(256), 0, S.stream, Fi);
-    HIPCHK40(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SORA_OK;
 }
 
@@ -679,14 +673,14 @@ static int ht40_collect_events(Ht40Slot& S)
 static int ht40_slot_results(sora_ht40_t* rx, Ht40Slot& S, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap)
 {
     if (S.capture_mode) {                                                        // rows per event of the front end, in (capture, time) order
-        HIPCHK40(hipSetDevice(rx->device));
-        HIPCHK40(hipStreamSynchronize(S.stream));
+        HIPCHK(hipSetDevice(rx->device));
+        HIPCHK(hipStreamSynchronize(S.stream));
         { const int rc = ht40_collect_events(S); if (rc) return rc; }
         const size_t nj = 2 * (size_t)S.nframes;
         std::vector<Rx11bRow> rows(nj);
-        if (nj) HIPCHK40(hipMemcpy(rows.data(), S.d_rows, sizeof(Rx11bRow) * nj, hipMemcpyDeviceToHost));
+        if (nj) HIPCHK(hipMemcpy(rows.data(), S.d_rows, sizeof(Rx11bRow) * nj, hipMemcpyDeviceToHost));
         std::vector<uint8_t> bulk;
-        if (h_mpdu && nj) { bulk.resize(nj * 4096); HIPCHK40(hipMemcpy(bulk.data(), S.d_mpdu, bulk.size(), hipMemcpyDeviceToHost)); }
+        if (h_mpdu && nj) { bulk.resize(nj * 4096); HIPCHK(hipMemcpy(bulk.data(), S.d_mpdu, bulk.size(), hipMemcpyDeviceToHost)); }
         size_t n = 0, moff = 0;
         for (const Ht40Event& E : S.events) {
             for (int k = 0; k < (E.frame >= 0 ? 2 : 1); k++) {
@@ -709,14 +703,14 @@ static int ht40_slot_results(sora_ht40_t* rx, Ht40Slot& S, sora_frame_result* ou
         return SORA_OK;
     }
     if (S.nframes == 0) return SORA_OK;
-    HIPCHK40(hipSetDevice(rx->device));
-    HIPCHK40(hipStreamSynchronize(S.stream));
+    HIPCHK(hipSetDevice(rx->device));
+    HIPCHK(hipStreamSynchronize(S.stream));
     const size_t nj = 2 * (size_t)S.nframes;
     if (nj > max_out) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_results: two rows per frame are reported", 0);
     std::vector<Rx11bRow> rows(nj);
-    HIPCHK40(hipMemcpy(rows.data(), S.d_rows, sizeof(Rx11bRow) * nj, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rows.data(), S.d_rows, sizeof(Rx11bRow) * nj, hipMemcpyDeviceToHost));
     std::vector<uint8_t> bulk;
-    if (h_mpdu) { bulk.resize(nj * 4096); HIPCHK40(hipMemcpy(bulk.data(), S.d_mpdu, bulk.size(), hipMemcpyDeviceToHost)); }
+    if (h_mpdu) { bulk.resize(nj * 4096); HIPCHK(hipMemcpy(bulk.data(), S.d_mpdu, bulk.size(), hipMemcpyDeviceToHost)); }
     size_t moff = 0;
     for (size_t j = 0; j < nj; j++) {
         sora_frame_result& o = out[j];
@@ -743,45 +737,31 @@ int sora_ht40_results(sora_ht40_t* rx, sora_frame_result* out, size_t max_out, s
 }
 
 // Tickets (as sora_rx_ticket / _wait / _results_of): every process call is addressable until kHt40Slots further calls have reused its slot.
-static Ht40Slot* ht40_slot_of(sora_ht40_t* rx, int ticket)
-{
-    if (!rx || ticket <= 0) return nullptr;
-    for (Ht40Slot& S : rx->slot) if (S.ticket == ticket) return &S;
-    return nullptr;
-}
-static const char* const kStaleHt40 = "stale ticket: its slot has been reused by a later process call (or the ticket was never issued)";
 int sora_ht40_ticket(sora_ht40_t* rx) { return rx && rx->have_results ? rx->slot[rx->last].ticket : 0; }
 int sora_ht40_calls_in_flight(sora_ht40_t* rx) { (void)rx; return kHt40Slots; }
 int sora_ht40_wait(sora_ht40_t* rx, int ticket)
 {
-    Ht40Slot* S = ht40_slot_of(rx, ticket);
-    if (!S) return sora_internal_fail(SORA_ERR_INVALID_PARAM, kStaleHt40, 0);
-    HIPCHK40(hipSetDevice(rx->device));
-    HIPCHK40(hipStreamSynchronize(S->stream));
-    if (S->delivered) S->released = true;
-    return S->capture_mode ? ht40_collect_events(*S) : SORA_OK;                  // (a raw-capture call that outgrew the handle's capacity says so here)
+    Ht40Slot* S = rx ? call_find(rx->slot, kHt40Slots, ticket) : nullptr;
+    if (!S) return call_stale("sora_ht40_wait");
+    const int rc = call_wait(rx->device, *S);
+    return rc == SORA_OK && S->capture_mode ? ht40_collect_events(*S) : rc;      // (a raw-capture call that outgrew the handle's capacity says so here)
 }
+// (the ticket is reported even when its call outgrew the handle's capacity)
 int sora_ht40_wait_any(sora_ht40_t* rx, int* ticket)
 {
     if (!rx || !ticket) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_wait_any: null argument", 0);
-    *ticket = 0;
-    HIPCHK40(hipSetDevice(rx->device));
-    for (unsigned spin = 0;; spin++) {
-        bool pending; hipError_t err;
-        Ht40Slot* S = slots_poll(rx->slot, kHt40Slots, &pending, &err);
-        if (err != hipSuccess) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "sora_ht40_wait_any: hipEventQuery", (int)err);
-        // (the ticket is reported even when its call outgrew the handle's capacity)
-        if (S) { const int t = S->ticket; const int rc = sora_ht40_wait(rx, t); *ticket = t; return rc; }
-        if (!pending) return sora_internal_fail(SORA_ERR_FAILED, "sora_ht40_wait_any: no call with an enqueued delivery (sora_ht40_deliver_async) is in flight", 0);
-        if (spin > 64) std::this_thread::yield();
-    }
+    return calls_wait_any(rx->slot, kHt40Slots, rx->device, ticket, "sora_ht40", [rx](int t) { return sora_ht40_wait(rx, t); });
 }
-void* sora_ht40_stream_of(sora_ht40_t* rx, int ticket) { Ht40Slot* S = ht40_slot_of(rx, ticket); return S ? (void*)S->stream : nullptr; }
+void* sora_ht40_stream_of(sora_ht40_t* rx, int ticket)
+{
+    Ht40Slot* S = rx ? call_find(rx->slot, kHt40Slots, ticket) : nullptr;
+    return S ? (void*)S->stream : nullptr;
+}
 int sora_ht40_deliver_async(sora_ht40_t* rx, int ticket, sora_frame_result* h_rows, size_t max_rows, uint32_t* h_counts, uint8_t* h_mpdu, size_t mpdu_cap)
 {
-    Ht40Slot* S = ht40_slot_of(rx, ticket);
-    if (!S) return sora_internal_fail(SORA_ERR_INVALID_PARAM, kStaleHt40, 0);
-    HIPCHK40(hipSetDevice(rx->device));
+    Ht40Slot* S = rx ? call_find(rx->slot, kHt40Slots, ticket) : nullptr;
+    if (!S) return call_stale("sora_ht40_deliver_async");
+    HIPCHK(hipSetDevice(rx->device));
     // raw captures: the event table (rows per event, template rows, source rows) and the event count were written by
     if (S->capture_mode) {
         // k_ht40_plan; the host knows only the bound ncaps x max_frames_per_capture.  The table is the one sora_ht40_results_of reports: a header that failed is a row, the
@@ -789,7 +769,7 @@ int sora_ht40_deliver_async(sora_ht40_t* rx, int ticket, sora_frame_result* h_ro
         const int rc = sora_internal_dense_deliver(&S->dense, S->d_rows, S->d_evn, nullptr, nullptr, S->bound_events, 2, S->d_mpdu, S->stream,
                                                    h_rows, max_rows, h_counts, h_mpdu, mpdu_cap, S->d_evtmpl, S->d_plan + 4, S->d_evbase);
         if (rc != SORA_OK) return rc;
-        HIPCHK40(slots_mark_delivered(*S));
+        HIPCHK(call_mark_delivered(*S));
         return SORA_OK;
     }
     S->h_tmpl.resize(2 * (size_t)S->nframes);
@@ -804,7 +784,7 @@ int sora_ht40_deliver_async(sora_ht40_t* rx, int ticket, sora_frame_result* h_ro
     const int rc = sora_internal_dense_deliver(&S->dense, S->d_rows, nullptr, nullptr, S->h_tmpl.data(), S->nframes, 2, S->d_mpdu, S->stream,
                                                h_rows, max_rows, h_counts, h_mpdu, mpdu_cap);
     if (rc != SORA_OK) return rc;
-    HIPCHK40(slots_mark_delivered(*S));
+    HIPCHK(call_mark_delivered(*S));
     return SORA_OK;
 }
 
@@ -812,7 +792,7 @@ int sora_ht40_results_of(sora_ht40_t* rx, int ticket, sora_frame_result* out, si
 {
     if (!nout || !out) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_results_of: null argument", 0);
     *nout = 0;
-    Ht40Slot* S = ht40_slot_of(rx, ticket);
-    if (!S) return sora_internal_fail(SORA_ERR_INVALID_PARAM, kStaleHt40, 0);
+    Ht40Slot* S = rx ? call_find(rx->slot, kHt40Slots, ticket) : nullptr;
+    if (!S) return call_stale("sora_ht40_results_of");
     return ht40_slot_results(rx, *S, out, max_out, nout, h_mpdu, mpdu_cap);
 }

@@ -1033,9 +1033,9 @@ __global__ void __launch_bounds__(1024) k_rx11b_count_flagged(const uint32_t* __
 
 // ------------------------------------------------------------------------------------------------ host side (C ABI, include/sora_hip.h)
 #include <vector>
-#include <thread>
 #include <string.h>
 #include "../../include/sora_hip.h"
+#include "host_calls.h"
 
 using namespace sora;
 
@@ -1043,12 +1043,9 @@ using namespace sora;
 // waves of call n and the first of call n + 1 share the chip (one wave per capture: a batch rarely fills the resident waves evenly).
 // sora_rx11b_results reports the most recent call.
 static constexpr int kSlots11b = 2;
-struct Slot11b {
-    hipStream_t stream = nullptr;
+struct Slot11b : Call {          // the stream, ticket and completion state of the call this slot holds (host_calls.h)
     CapDesc* d_caps = nullptr; Rx11bRow* d_rows = nullptr; uint32_t* d_nframes = nullptr; uint8_t* d_mpdu = nullptr; uint32_t* d_needs_cck = nullptr;
     std::vector<sora_capture_desc> h_caps;
-    int ticket = 0;              // of the call this slot holds (0: none)
-    hipEvent_t ev_done = nullptr; bool delivered = false, released = false;      // sora_rx11b_wait_any (kernels.h: slots_next / slots_poll)
     DenseStage dense;            // sora_rx11b_deliver_async
     std::vector<CapDesc> h_desc;                 // staging for the descriptor upload (kept until the slot's next call)
     uint32_t ncaps = 0;
@@ -1066,12 +1063,8 @@ struct sora_rx11b {
     int  pass_plan = 2;
     bool auto_single = false;       // automatic plan: what the most recent measurement said (more than half of a call's captures carried CCK frames)
     uint32_t auto_calls = 0;        // ... and every 16th call of a single-pass run is a two-pass call again, to measure
-    // sora_rx11b_set_stream_mode: capture k of a call continues capture k of the call before it (allocated when the mode is first enabled)
-    bool stream_mode = false;
-    uint32_t* d_cont = nullptr; uint32_t* d_consumed = nullptr;
+    StreamRecords records{kRec11bWords};     // sora_rx11b_set_stream_mode
 };
-
-#define HIPCHK11(call) do { hipError_t _e = (call); if (_e != hipSuccess) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, #call, (int)_e); } while (0)
 
 static void rx11b_free(sora_rx11b_t* rx)
 {
@@ -1083,19 +1076,13 @@ static void rx11b_free(sora_rx11b_t* rx)
             if (S.ev_done) (void)hipEventDestroy(S.ev_done);
         sora_internal_dense_free(&S.dense);
     }
-    (void)hipFree(rx->d_iq_own); (void)hipFree(rx->d_cont); (void)hipFree(rx->d_consumed);
+    (void)hipFree(rx->d_iq_own); rx->records.free();
     delete rx;
 }
 
 int sora_rx11b_create(const sora_rx_cfg* cfg, sora_rx11b_t** out)
 {
-    if (!cfg || !out || cfg->struct_size != sizeof(sora_rx_cfg)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_create: bad cfg", 0);
-    if (cfg->sample_rate_mhz != 44) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_create: the 802.11b graph takes 44 MHz samples (sample_rate_mhz = 44)", 0);
-    if (cfg->max_captures == 0 || cfg->max_total_samples == 0 || cfg->max_frames_per_capture == 0) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "zero capacity", 0);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (cfg->device < 0 || cfg->device >= ndev) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "device ordinal out of range", 0);
-    HIPCHK11(hipSetDevice(cfg->device));
+    { const int rc = check_rx_cfg(cfg, out, 44, "sora_rx11b_create"); if (rc) return rc; }
     sora_rx11b_t* rx = new sora_rx11b();
     rx->cfg = *cfg;
     if (rx->cfg.cca_pwr_threshold == 0) rx->cfg.cca_pwr_threshold = 1000 * 1000;      // BB11bDemodCtx.init (fb11bdemod_config.hpp:95)
@@ -1122,9 +1109,7 @@ void* sora_rx11b_stream(sora_rx11b_t* rx) { return rx ? (void*)rx->slot[rx->last
 int sora_rx11b_synchronize(sora_rx11b_t* rx)
 {
     if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_synchronize: null handle", 0);
-    HIPCHK11(hipSetDevice(rx->cfg.device));
-    for (Slot11b& S : rx->slot) HIPCHK11(hipStreamSynchronize(S.stream));
-    return SORA_OK;
+    return calls_synchronize(rx->slot, kSlots11b, rx->cfg.device);
 }
 
 void sora_rx11b_destroy(sora_rx11b_t* rx) { if (rx) { (void)hipSetDevice(rx->cfg.device); rx11b_free(rx); } }
@@ -1133,13 +1118,13 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
 {
     if (!rx || (ncaps && (!d_iq || !caps))) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_process_dev: null argument", 0);
     if (ncaps > rx->cfg.max_captures) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_rx11b_process_dev: more captures than max_captures", 0);
-    HIPCHK11(hipSetDevice(rx->cfg.device));
+    HIPCHK(hipSetDevice(rx->cfg.device));
     // stream mode: this call continues the records the one before it leaves, so calls run one after the other
-    if (rx->stream_mode) for (Slot11b& Q : rx->slot) HIPCHK11(hipStreamSynchronize(Q.stream));
-    rx->next = slots_next(rx->slot, kSlots11b);                                       // an unused slot, else a released call's, else the oldest call's
+    if (rx->records.on) for (Slot11b& Q : rx->slot) HIPCHK(hipStreamSynchronize(Q.stream));
+    rx->next = call_next(rx->slot, kSlots11b);                                        // an unused slot, else a released call's, else the oldest call's
     Slot11b& S = rx->slot[rx->next];
     std::vector<CapDesc>& h = S.h_desc;
-    HIPCHK11(hipStreamSynchronize(S.stream));                                         // the slot's previous call may still be reading d_caps / writing results
+    HIPCHK(hipStreamSynchronize(S.stream));                                         // the slot's previous call may still be reading d_caps / writing results
     h.resize(ncaps);
     uint64_t total = 0;
     for (size_t i = 0; i < ncaps; i++) {
@@ -1153,11 +1138,11 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
     rx->last = rx->next;
     S.ticket = ++rx->seq; S.delivered = S.released = false;
     if (ncaps == 0) return SORA_OK;
-    HIPCHK11(hipMemcpyAsync(S.d_caps, h.data(), sizeof(CapDesc) * ncaps, hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemcpyAsync(S.d_caps, h.data(), sizeof(CapDesc) * ncaps, hipMemcpyHostToDevice, S.stream));
     Rx11bArgs A;
     A.iq = reinterpret_cast<const uint32_t*>(d_iq); A.caps = S.d_caps; A.ncaps = (uint32_t)ncaps; A.thr = rx->cfg.cca_pwr_threshold;
     A.max_frames = rx->cfg.max_frames_per_capture; A.rows = S.d_rows; A.nframes = S.d_nframes; A.mpdu = S.d_mpdu; A.crc = rx->d_crc; A.needs_cck = S.d_needs_cck;
-    A.cont = rx->stream_mode ? rx->d_cont : nullptr; A.consumed = rx->stream_mode ? rx->d_consumed : nullptr;
+    A.cont = rx->records.on ? rx->records.d_cont : nullptr; A.consumed = rx->records.on ? rx->records.d_consumed : nullptr;
     // The pass plan.  Automatic (default): a two-pass call also counts, on the device, how many captures its first pass handed over; once such a
     // count has come back (no waiting: the event is only queried) and says "more than half", the following calls go straight through the CCK
     // instantiation -- which decodes all four rates with identical rows -- except every 16th, which is a two-pass call again and measures.
@@ -1170,19 +1155,19 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
     }
     bool single = rx->pass_plan == 1;
     if (rx->pass_plan == 2 && rx->auto_single && (++rx->auto_calls & 15u) != 0u) single = true;
-    HIPCHK11(hipMemsetAsync(S.d_needs_cck, single ? 1 : 0, 4 * ncaps, S.stream));
+    HIPCHK(hipMemsetAsync(S.d_needs_cck, single ? 1 : 0, 4 * ncaps, S.stream));
     const dim3 grid((unsigned)((ncaps + 3) / 4));
-    if (!single) hipLaunchKernelGGL(rx->stream_mode ? k_rx11b_stream : k_rx11b, grid, dim3(256), 0, S.stream, A);
+    if (!single) hipLaunchKernelGGL(rx->records.on ? k_rx11b_stream : k_rx11b, grid, dim3(256), 0, S.stream, A);
     if (!single && rx->pass_plan == 2 && !S.flagged_pending) {
         hipLaunchKernelGGL(k_rx11b_count_flagged, dim3(1), dim3(1024), 0, S.stream, (const uint32_t*)S.d_needs_cck, (uint32_t)ncaps, S.d_flagged);
         S.h_flagged[1] = (uint32_t)ncaps;
-        HIPCHK11(hipMemcpyAsync(S.h_flagged, S.d_flagged, 4, hipMemcpyDeviceToHost, S.stream));
-        HIPCHK11(hipEventRecord(S.ev_flagged, S.stream));
+        HIPCHK(hipMemcpyAsync(S.h_flagged, S.d_flagged, 4, hipMemcpyDeviceToHost, S.stream));
+        HIPCHK(hipEventRecord(S.ev_flagged, S.stream));
         S.flagged_pending = true;
     }
     // redoes the captures the first pass flagged (a wave of any other capture returns at once)
-    hipLaunchKernelGGL(rx->stream_mode ? k_rx11b_cck_stream : k_rx11b_cck, grid, dim3(256), 0, S.stream, A);
-    HIPCHK11(hipGetLastError());
+    hipLaunchKernelGGL(rx->records.on ? k_rx11b_cck_stream : k_rx11b_cck, grid, dim3(256), 0, S.stream, A);
+    HIPCHK(hipGetLastError());
     return SORA_OK;
 }
 
@@ -1190,56 +1175,13 @@ int sora_rx11b_process(sora_rx11b_t* rx, const sora_complex16* h_iq, size_t nsam
 {
     if (!rx || (nsamples && !h_iq)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_process: null argument", 0);
     if (nsamples > rx->cfg.max_total_samples) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_rx11b_process: more samples than max_total_samples", 0);
-    for (size_t i = 0; i < ncaps; i++)                                               // the buffer's size is known here: no descriptor may reach past it
-        if (caps && (caps[i].offset > nsamples || caps[i].nsamples > nsamples - caps[i].offset)) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
-                "a capture descriptor reaches past the end of the sample buffer", 0);
-    HIPCHK11(hipSetDevice(rx->cfg.device));
-    if (!rx->d_iq_own) HIPCHK11(hipMalloc((void**)&rx->d_iq_own, sizeof(sora_complex16) * (rx->cfg.max_total_samples + 64)));
-    for (Slot11b& S : rx->slot) HIPCHK11(hipStreamSynchronize(S.stream));             // one upload buffer: no call may still be reading it
-    rx->next = slots_next(rx->slot, kSlots11b);                                       // (the slot process_dev is about to pick: nothing changes in between)
-    HIPCHK11(hipMemcpyAsync(rx->d_iq_own, h_iq, sizeof(sora_complex16) * nsamples, hipMemcpyHostToDevice, rx->slot[rx->next].stream));
+    { const int rc = check_caps_in_buffer(caps, ncaps, nsamples); if (rc) return rc; }
+    HIPCHK(hipSetDevice(rx->cfg.device));
+    if (!rx->d_iq_own) HIPCHK(hipMalloc((void**)&rx->d_iq_own, sizeof(sora_complex16) * (rx->cfg.max_total_samples + 64)));
+    for (Slot11b& S : rx->slot) HIPCHK(hipStreamSynchronize(S.stream));              // one upload buffer: no call may still be reading it
+    rx->next = call_next(rx->slot, kSlots11b);                                        // (the slot process_dev is about to pick: nothing changes in between)
+    HIPCHK(hipMemcpyAsync(rx->d_iq_own, h_iq, sizeof(sora_complex16) * nsamples, hipMemcpyHostToDevice, rx->slot[rx->next].stream));
     return sora_rx11b_process_dev(rx, rx->d_iq_own, caps, ncaps);
-}
-
-static int slot11b_results(sora_rx11b_t* rx, Slot11b& S, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap)
-{
-    if (S.ncaps == 0) return SORA_OK;
-    HIPCHK11(hipSetDevice(rx->cfg.device));
-    HIPCHK11(hipStreamSynchronize(S.stream));
-    const uint32_t mf = rx->cfg.max_frames_per_capture;
-    std::vector<Rx11bRow> rows((size_t)S.ncaps * mf); std::vector<uint32_t> nfr(S.ncaps);
-    HIPCHK11(hipMemcpy(rows.data(), S.d_rows, sizeof(Rx11bRow) * rows.size(), hipMemcpyDeviceToHost));
-    HIPCHK11(hipMemcpy(nfr.data(), S.d_nframes, 4 * (size_t)S.ncaps, hipMemcpyDeviceToHost));
-    // MPDU bytes: one bulk copy of the per-frame slots that are in use when that is cheap, else frame by frame
-    size_t used_rows = 0;
-    for (uint32_t c = 0; c < S.ncaps; c++) used_rows += nfr[c] < mf ? nfr[c] : mf;
-    std::vector<uint8_t> bulk;
-    const size_t slots = (size_t)S.ncaps * mf;
-    if (h_mpdu && used_rows > 16 && slots * 4096 <= ((size_t)1 << 30)) {
-        bulk.resize(slots * 4096);
-        HIPCHK11(hipMemcpy(bulk.data(), S.d_mpdu, bulk.size(), hipMemcpyDeviceToHost));
-    }
-    size_t n = 0, moff = 0; int rc = SORA_OK;
-    for (uint32_t c = 0; c < S.ncaps; c++)
-        for (uint32_t i = 0; i < nfr[c] && i < mf; i++) {
-            const Rx11bRow& r = rows[(size_t)c * mf + i];
-            if (n >= max_out) { rc = SORA_ERR_CAPACITY; continue; }
-            sora_frame_result& o = out[n++];
-            memset(&o, 0, sizeof(o));
-            o.capture_id = S.h_caps[c].capture_id; o.end_sample = r.end_sample; o.error_code = r.error_code; o.rate_kbps = r.rate_kbps;
-            o.length = (uint16_t)r.length; o.crc32 = r.crc32; o.mpdu_offset = (uint32_t)moff;
-            if (i + 1 == mf && nfr[c] > mf) o.flags = SORA_ROW_TRUNCATED;             // more frames were found than the capture has rows
-            if (h_mpdu && (r.error_code == 1u || r.error_code == 0x80000006u)) {
-                const size_t len = r.length < 4096 ? r.length : 4096;
-                if (moff + len > mpdu_cap) { rc = SORA_ERR_CAPACITY; continue; }
-                if (!bulk.empty()) memcpy(h_mpdu + moff, bulk.data() + ((size_t)c * mf + i) * 4096, len);
-                else HIPCHK11(hipMemcpy(h_mpdu + moff, S.d_mpdu + ((size_t)c * mf + i) * 4096, len, hipMemcpyDeviceToHost));
-                moff += len;
-            }
-        }
-    *nout = n;
-    if (rc != SORA_OK) return sora_internal_fail(rc, "sora_rx11b_results: output buffer too small", 0);
-    return SORA_OK;
 }
 
 int sora_rx11b_results(sora_rx11b_t* rx, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap)
@@ -1247,17 +1189,12 @@ int sora_rx11b_results(sora_rx11b_t* rx, sora_frame_result* out, size_t max_out,
     if (!rx || !nout) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_results: null argument", 0);
     *nout = 0;
     if (!rx->have_results) return sora_internal_fail(SORA_ERR_FAILED, "no process call to report", 0);
-    return slot11b_results(rx, rx->slot[rx->last], out, max_out, nout, h_mpdu, mpdu_cap);
+    const Slot11b& S = rx->slot[rx->last];
+    return sora_internal_rows_results(S.d_rows, S.d_nframes, S.d_mpdu, S.h_caps.data(), S.ncaps, rx->cfg.max_frames_per_capture, rx->cfg.device, S.stream,
+                                      "sora_rx11b_results", out, max_out, nout, h_mpdu, mpdu_cap);
 }
 
 // Tickets (as sora_rx_ticket / _wait / _results_of): every process call is addressable until kSlots11b further calls have reused its slot.
-static Slot11b* slot11b_of(sora_rx11b_t* rx, int ticket)
-{
-    if (!rx || ticket <= 0) return nullptr;
-    for (Slot11b& S : rx->slot) if (S.ticket == ticket) return &S;
-    return nullptr;
-}
-static const char* const kStale11b = "stale ticket: its slot has been reused by a later process call (or the ticket was never issued)";
 int sora_rx11b_ticket(sora_rx11b_t* rx) { return rx && rx->have_results ? rx->slot[rx->last].ticket : 0; }
 int sora_rx11b_calls_in_flight(sora_rx11b_t* rx) { (void)rx; return kSlots11b; }
 // Two passes (default): k_rx11b (90 VGPRs, the Barker rates) decodes every capture and hands the ones whose PLCP header announces 5.5 / 11 Mbps
@@ -1273,66 +1210,38 @@ int sora_rx11b_set_single_pass(sora_rx11b_t* rx, int enable)
 int sora_rx11b_set_stream_mode(sora_rx11b_t* rx, int enable)
 {
     if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_set_stream_mode: null handle", 0);
-    const int old = rx->stream_mode ? 1 : 0;
-    if (enable < 0) return old;
-    HIPCHK11(hipSetDevice(rx->cfg.device));
-    for (Slot11b& S : rx->slot) HIPCHK11(hipStreamSynchronize(S.stream));
-    if (enable && !rx->d_cont) {
-        HIPCHK11(hipMalloc((void**)&rx->d_cont, 4 * (size_t)kRec11bWords * rx->cfg.max_captures));
-        HIPCHK11(hipMalloc((void**)&rx->d_consumed, 4 * (size_t)rx->cfg.max_captures));
-    }
-    if (rx->d_cont) {                                                                 // switching either way starts every stream afresh
-        HIPCHK11(hipMemset(rx->d_cont, 0, 4 * (size_t)kRec11bWords * rx->cfg.max_captures));
-        HIPCHK11(hipMemset(rx->d_consumed, 0, 4 * (size_t)rx->cfg.max_captures));
-    }
-    rx->stream_mode = enable != 0;
-    return old;
+    if (enable >= 0) { const int rc = sora_rx11b_synchronize(rx); if (rc) return rc; }
+    return rx->records.set(enable, rx->cfg.device, rx->cfg.max_captures);
 }
 int sora_rx11b_stream_consumed(sora_rx11b_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps)
 {
     if (!rx || !h_consumed) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_stream_consumed: null argument", 0);
-    if (!rx->stream_mode) return sora_internal_fail(SORA_ERR_FAILED, "sora_rx11b_stream_consumed: the handle is not in stream mode", 0);
-    Slot11b* S = slot11b_of(rx, ticket);
-    if (!S || ticket != rx->seq) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_stream_consumed: only the most recent call's resume points exist", 0);
-    if (ncaps > S->ncaps) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_stream_consumed: more captures than the call had", 0);
-    HIPCHK11(hipSetDevice(rx->cfg.device));
-    HIPCHK11(hipStreamSynchronize(S->stream));
-    if (ncaps) HIPCHK11(hipMemcpy(h_consumed, rx->d_consumed, 4 * ncaps, hipMemcpyDeviceToHost));
-    return SORA_OK;
+    return rx->records.consumed("sora_rx11b_stream_consumed", rx->cfg.device, call_find(rx->slot, kSlots11b, ticket), ticket == rx->seq, h_consumed, ncaps);
 }
 int sora_rx11b_wait(sora_rx11b_t* rx, int ticket)
 {
-    Slot11b* S = slot11b_of(rx, ticket);
-    if (!S) return sora_internal_fail(SORA_ERR_INVALID_PARAM, kStale11b, 0);
-    HIPCHK11(hipSetDevice(rx->cfg.device));
-    HIPCHK11(hipStreamSynchronize(S->stream));
-    if (S->delivered) S->released = true;
-    return SORA_OK;
+    Slot11b* S = rx ? call_find(rx->slot, kSlots11b, ticket) : nullptr;
+    return S ? call_wait(rx->cfg.device, *S) : call_stale("sora_rx11b_wait");
 }
 int sora_rx11b_wait_any(sora_rx11b_t* rx, int* ticket)
 {
     if (!rx || !ticket) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_wait_any: null argument", 0);
-    *ticket = 0;
-    HIPCHK11(hipSetDevice(rx->cfg.device));
-    for (unsigned spin = 0;; spin++) {
-        bool pending; hipError_t err;
-        Slot11b* S = slots_poll(rx->slot, kSlots11b, &pending, &err);
-        if (err != hipSuccess) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "sora_rx11b_wait_any: hipEventQuery", (int)err);
-        if (S) { const int t = S->ticket; const int rc = sora_rx11b_wait(rx, t); if (rc == SORA_OK) *ticket = t; return rc; }
-        if (!pending) return sora_internal_fail(SORA_ERR_FAILED, "sora_rx11b_wait_any: no call with an enqueued delivery (sora_rx11b_deliver_async) is in flight", 0);
-        if (spin > 64) std::this_thread::yield();
-    }
+    return calls_wait_any(rx->slot, kSlots11b, rx->cfg.device, ticket, "sora_rx11b", [rx](int t) { return sora_rx11b_wait(rx, t); });
 }
-void* sora_rx11b_stream_of(sora_rx11b_t* rx, int ticket) { Slot11b* S = slot11b_of(rx, ticket); return S ? (void*)S->stream : nullptr; }
+void* sora_rx11b_stream_of(sora_rx11b_t* rx, int ticket)
+{
+    Slot11b* S = rx ? call_find(rx->slot, kSlots11b, ticket) : nullptr;
+    return S ? (void*)S->stream : nullptr;
+}
 int sora_rx11b_deliver_async(sora_rx11b_t* rx, int ticket, sora_frame_result* h_rows, size_t max_rows, uint32_t* h_counts, uint8_t* h_mpdu, size_t mpdu_cap)
 {
-    Slot11b* S = slot11b_of(rx, ticket);
-    if (!S) return sora_internal_fail(SORA_ERR_INVALID_PARAM, kStale11b, 0);
-    HIPCHK11(hipSetDevice(rx->cfg.device));
+    Slot11b* S = rx ? call_find(rx->slot, kSlots11b, ticket) : nullptr;
+    if (!S) return call_stale("sora_rx11b_deliver_async");
+    HIPCHK(hipSetDevice(rx->cfg.device));
     const int rc = sora_internal_dense_deliver(&S->dense, S->d_rows, S->d_nframes, S->d_caps, nullptr, S->ncaps, rx->cfg.max_frames_per_capture, S->d_mpdu, S->stream,
                                                h_rows, max_rows, h_counts, h_mpdu, mpdu_cap);
     if (rc != SORA_OK) return rc;
-    HIPCHK11(slots_mark_delivered(*S));
+    HIPCHK(call_mark_delivered(*S));
     return SORA_OK;
 }
 
@@ -1340,7 +1249,8 @@ int sora_rx11b_results_of(sora_rx11b_t* rx, int ticket, sora_frame_result* out, 
 {
     if (!nout) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_results_of: null argument", 0);
     *nout = 0;
-    Slot11b* S = slot11b_of(rx, ticket);
-    if (!S) return sora_internal_fail(SORA_ERR_INVALID_PARAM, kStale11b, 0);
-    return slot11b_results(rx, *S, out, max_out, nout, h_mpdu, mpdu_cap);
+    const Slot11b* S = rx ? call_find(rx->slot, kSlots11b, ticket) : nullptr;
+    if (!S) return call_stale("sora_rx11b_results_of");
+    return sora_internal_rows_results(S->d_rows, S->d_nframes, S->d_mpdu, S->h_caps.data(), S->ncaps, rx->cfg.max_frames_per_capture, rx->cfg.device, S->stream,
+                                      "sora_rx11b_results_of", out, max_out, nout, h_mpdu, mpdu_cap);
 }

@@ -753,21 +753,19 @@ __global__ void __launch_bounds__(256) k_finish11n(Frame11nArgs A)
 
 // ------------------------------------------------------------------------------------------------ host side (C ABI, include/sora_hip.h)
 #include <vector>
-#include <thread>
 #include <string.h>
 #include <stdlib.h>
+#include "host_calls.h"
 using namespace sora;
 
 
-struct Pipe11n {                         // one call in flight: a stream and every device array a call writes
-    hipStream_t stream = nullptr;
+struct Pipe11n : Call {                  // one call in flight: its stream, ticket and completion state (host_calls.h) and every device array a call writes
     CapDesc* d_caps = nullptr; Rx11bRow* d_rows = nullptr; uint32_t* d_nframes = nullptr; uint8_t* d_mpdu = nullptr;
     N11Frame* d_frames = nullptr; VitJob* d_jobs = nullptr; uint32_t* d_njobs = nullptr; uint8_t* d_soft = nullptr; uint8_t* d_vout = nullptr;
     uint16_t* d_wvecs = nullptr; unsigned long long* d_wstats = nullptr; uint32_t wstride = 0;   // the window-parallel trellis's vectors and proof record (on its first use)
     std::vector<sora_capture_desc> h_caps; std::vector<CapDesc> h_desc;
-    uint32_t ncaps = 0; bool have_results = false; int ticket = 0;
+    uint32_t ncaps = 0; bool have_results = false;
     DenseStage dense;                       // sora_rx11n_deliver_async
-    hipEvent_t ev_done = nullptr; bool delivered = false, released = false;     // sora_rx11n_wait_any (the rules of sora_rx_wait_any, include/sora_hip.h)
 };
 struct sora_rx11n {
     sora_rx_cfg cfg{};
@@ -781,13 +779,9 @@ struct sora_rx11n {
     static constexpr int kMaxDepth = 8;
     Pipe11n* pipes[kMaxDepth] = {};
     int depth = 1, cur = 0, next_ticket = 0; bool started = false;
-    // sora_rx11n_set_stream_mode: capture k of a call continues capture k of the call before it; the records belong to the handle, not to a
-    // pipeline (allocated when the mode is first enabled)
-    bool stream_mode = false;
-    uint32_t* d_cont = nullptr; uint32_t* d_consumed = nullptr;
+    // sora_rx11n_set_stream_mode: the records belong to the handle, not to a pipeline
+    StreamRecords records{kRec11nWords};
 };
-
-#define HIPCHK11N(call) do { hipError_t _e = (call); if (_e != hipSuccess) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, #call, (int)_e); } while (0)
 
 static void pipe11n_free(Pipe11n* p)
 {
@@ -804,7 +798,7 @@ static void rx11n_free(sora_rx11n_t* rx)
 {
     if (!rx) return;
     for (Pipe11n* p : rx->pipes) pipe11n_free(p);
-    (void)hipFree(rx->d_iq_own[0]); (void)hipFree(rx->d_iq_own[1]); (void)hipFree(rx->d_cont); (void)hipFree(rx->d_consumed);
+    (void)hipFree(rx->d_iq_own[0]); (void)hipFree(rx->d_iq_own[1]); rx->records.free();
     delete rx;
 }
 static hipError_t pipe11n_create(sora_rx11n_t* rx, Pipe11n** out, int index = 0)
@@ -837,13 +831,7 @@ static hipError_t pipe11n_create(sora_rx11n_t* rx, Pipe11n** out, int index = 0)
 
 int sora_rx11n_create(const sora_rx_cfg* cfg, sora_rx11n_t** out)
 {
-    if (!cfg || !out || cfg->struct_size != sizeof(sora_rx_cfg)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_create: bad cfg", 0);
-    if (cfg->sample_rate_mhz != 40) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_create: the 802.11n graph takes 40 MHz samples (sample_rate_mhz = 40)", 0);
-    if (cfg->max_captures == 0 || cfg->max_total_samples == 0 || cfg->max_frames_per_capture == 0) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "zero capacity", 0);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (cfg->device < 0 || cfg->device >= ndev) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "device ordinal out of range", 0);
-    HIPCHK11N(hipSetDevice(cfg->device));
+    { const int rc = check_rx_cfg(cfg, out, 40, "sora_rx11n_create"); if (rc) return rc; }
     sora_rx11n_t* rx = new sora_rx11n();
     rx->cfg = *cfg;
     if (!(sora_internal_tables(cfg->device, &rx->T) == SORA_OK && sora_internal_dsp_tables(&rx->sincos, &rx->atan) == SORA_OK)) { rx11n_free(rx);
@@ -867,8 +855,7 @@ int sora_rx11n_set_depth(sora_rx11n_t* rx, int depth)
     const int prev = rx->depth;
     if (depth <= 0) return prev;
     if (depth > sora_rx11n::kMaxDepth) depth = sora_rx11n::kMaxDepth;
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
-    for (Pipe11n* p : rx->pipes) if (p) HIPCHK11N(hipStreamSynchronize(p->stream));
+    { const int rc = sora_rx11n_synchronize(rx); if (rc) return rc; }
     for (int i = 0; i < depth; i++)
         if (!rx->pipes[i]) { const hipError_t e = pipe11n_create(rx, &rx->pipes[i], i);
             if (e != hipSuccess) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "sora_rx11n_set_depth: device allocation", (int)e); }
@@ -900,134 +887,68 @@ int sora_rx11n_trellis(sora_rx11n_t* rx) { return rx ? trellis11n_for(rx) : SORA
 int sora_rx11n_window_stats(sora_rx11n_t* rx, unsigned long long out[4])
 {
     if (!rx || !out) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_window_stats: null argument", 0);
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
+    HIPCHK(hipSetDevice(rx->cfg.device));
     for (int i = 0; i < 4; i++) out[i] = 0;
     for (Pipe11n* p : rx->pipes) if (p && p->d_wstats) {
         unsigned long long v[4 * kWinStatBanks];
-        HIPCHK11N(hipStreamSynchronize(p->stream));
-        HIPCHK11N(hipMemcpy(v, p->d_wstats, sizeof v, hipMemcpyDeviceToHost));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        HIPCHK(hipMemcpy(v, p->d_wstats, sizeof v, hipMemcpyDeviceToHost));
         for (unsigned i = 0; i < 4 * kWinStatBanks; i++) out[i & 3u] += v[i];
     }
     return SORA_OK;
 }
 
-static Pipe11n* pipe11n_of(sora_rx11n_t* rx, int ticket);
 int sora_rx11n_deliver_async(sora_rx11n_t* rx, int ticket, sora_frame_result* h_rows, size_t max_rows, uint32_t* h_counts, uint8_t* h_mpdu, size_t mpdu_cap)
 {
-    Pipe11n* P = pipe11n_of(rx, ticket);
-    if (!P || !P->have_results) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
-            "sora_rx11n_deliver_async: stale ticket (its pipeline has been reused by a later process call, or the ticket was never issued)", 0);
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
+    Pipe11n* P = rx ? call_find(rx->pipes, rx->depth, ticket) : nullptr;
+    if (!P) return call_stale("sora_rx11n_deliver_async");
+    HIPCHK(hipSetDevice(rx->cfg.device));
     const int rc = sora_internal_dense_deliver(&P->dense, P->d_rows, P->d_nframes, P->d_caps, nullptr, P->ncaps, rx->cfg.max_frames_per_capture, P->d_mpdu, P->stream,
                                                h_rows, max_rows, h_counts, h_mpdu, mpdu_cap);
     if (rc != SORA_OK) return rc;
-    if (!P->ev_done) HIPCHK11N(hipEventCreateWithFlags(&P->ev_done, hipEventDisableTiming));
-    HIPCHK11N(hipEventRecord(P->ev_done, P->stream));
-    P->delivered = true;
+    HIPCHK(call_mark_delivered(*P));
     return SORA_OK;
 }
 
 int sora_rx11n_synchronize(sora_rx11n_t* rx)
 {
     if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_synchronize: null handle", 0);
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
-    for (Pipe11n* p : rx->pipes) if (p) HIPCHK11N(hipStreamSynchronize(p->stream));
-    return SORA_OK;
+    return calls_synchronize(rx->pipes, sora_rx11n::kMaxDepth, rx->cfg.device);
 }
 
-static Pipe11n* pipe11n_of(sora_rx11n_t* rx, int ticket)
-{
-    if (!rx || ticket <= 0) return nullptr;
-    for (int i = 0; i < rx->depth; i++) if (rx->pipes[i] && rx->pipes[i]->ticket == ticket) return rx->pipes[i];
-    return nullptr;
-}
 int sora_rx11n_set_stream_mode(sora_rx11n_t* rx, int enable)
 {
     if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_set_stream_mode: null handle", 0);
-    const int old = rx->stream_mode ? 1 : 0;
-    if (enable < 0) return old;
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
-    for (Pipe11n* p : rx->pipes) if (p) HIPCHK11N(hipStreamSynchronize(p->stream));
-    if (enable && !rx->d_cont) {
-        HIPCHK11N(hipMalloc((void**)&rx->d_cont, 4 * (size_t)kRec11nWords * rx->cfg.max_captures));
-        HIPCHK11N(hipMalloc((void**)&rx->d_consumed, 4 * (size_t)rx->cfg.max_captures));
-    }
-    if (rx->d_cont) {                                                                 // switching either way starts every stream afresh
-        HIPCHK11N(hipMemset(rx->d_cont, 0, 4 * (size_t)kRec11nWords * rx->cfg.max_captures));
-        HIPCHK11N(hipMemset(rx->d_consumed, 0, 4 * (size_t)rx->cfg.max_captures));
-    }
-    rx->stream_mode = enable != 0;
-    return old;
+    if (enable >= 0) { const int rc = sora_rx11n_synchronize(rx); if (rc) return rc; }
+    return rx->records.set(enable, rx->cfg.device, rx->cfg.max_captures);
 }
 int sora_rx11n_stream_consumed(sora_rx11n_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps)
 {
     if (!rx || !h_consumed) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_stream_consumed: null argument", 0);
-    if (!rx->stream_mode) return sora_internal_fail(SORA_ERR_FAILED, "sora_rx11n_stream_consumed: the handle is not in stream mode", 0);
-    Pipe11n* P = pipe11n_of(rx, ticket);
-    if (!P || ticket != rx->next_ticket) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_stream_consumed: only the most recent call's resume points exist", 0);
-    if (ncaps > P->ncaps) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_stream_consumed: more captures than the call had", 0);
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
-    HIPCHK11N(hipStreamSynchronize(P->stream));
-    if (ncaps) HIPCHK11N(hipMemcpy(h_consumed, rx->d_consumed, 4 * ncaps, hipMemcpyDeviceToHost));
-    return SORA_OK;
+    return rx->records.consumed("sora_rx11n_stream_consumed", rx->cfg.device, call_find(rx->pipes, rx->depth, ticket), ticket == rx->next_ticket, h_consumed, ncaps);
 }
+// Tickets are looked up, and calls placed, among the first `depth` pipelines: a depth shrink makes the dropped pipelines' tickets stale
 int sora_rx11n_ticket(sora_rx11n_t* rx) { return rx && rx->started ? rx->pipes[rx->cur]->ticket : 0; }
 int sora_rx11n_wait(sora_rx11n_t* rx, int ticket)
 {
-    Pipe11n* p = pipe11n_of(rx, ticket);
-    if (!p) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
-            "sora_rx11n_wait: stale ticket (its pipeline has been reused by a later process call, or the ticket was never issued)", 0);
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
-    HIPCHK11N(hipStreamSynchronize(p->stream));
-    if (p->delivered) p->released = true;
-    return SORA_OK;
+    Pipe11n* p = rx ? call_find(rx->pipes, rx->depth, ticket) : nullptr;
+    return p ? call_wait(rx->cfg.device, *p) : call_stale("sora_rx11n_wait");
 }
 
 int sora_rx11n_wait_any(sora_rx11n_t* rx, int* ticket)
 {
     if (!rx || !ticket) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_wait_any: null argument", 0);
-    *ticket = 0;
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
-    for (unsigned spin = 0;; spin++) {
-        Pipe11n* done = nullptr; bool pending = false;
-        for (int i = 0; i < rx->depth; i++) {
-            Pipe11n* p = rx->pipes[i];
-            if (!p || p->ticket == 0 || !p->delivered || p->released) continue;
-            pending = true;
-            const hipError_t q = hipEventQuery(p->ev_done);
-            if (q == hipSuccess) { if (!done || p->ticket < done->ticket) done = p; }
-            else if (q != hipErrorNotReady) { (void)hipGetLastError(); return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "sora_rx11n_wait_any: hipEventQuery", (int)q); }
-        }
-        if (done) { HIPCHK11N(hipStreamSynchronize(done->stream)); done->released = true; *ticket = done->ticket; return SORA_OK; }
-        if (!pending) return sora_internal_fail(SORA_ERR_FAILED, "sora_rx11n_wait_any: no call with an enqueued delivery (sora_rx11n_deliver_async) is in flight", 0);
-        (void)hipGetLastError();
-        if (spin > 64) std::this_thread::yield();
-    }
-}
-
-// The pipeline of the next call: an unused one, else the released call with the oldest ticket, else the oldest call (plain rotation) -- sora_hip.cpp next_pipe()
-static int next_pipe11n(const sora_rx11n_t* rx)
-{
-    if (!rx->started) return 0;
-    int best = -1, best_rel = -1;
-    for (int i = 0; i < rx->depth; i++) {
-        const Pipe11n* p = rx->pipes[i];
-        if (!p) continue;
-        if (p->ticket == 0) return i;
-        if (p->released && (best_rel < 0 || p->ticket < rx->pipes[best_rel]->ticket)) best_rel = i;
-        if (best < 0 || p->ticket < rx->pipes[best]->ticket) best = i;
-    }
-    return best_rel >= 0 ? best_rel : best;
+    return calls_wait_any(rx->pipes, rx->depth, rx->cfg.device, ticket, "sora_rx11n", [rx](int t) { return sora_rx11n_wait(rx, t); });
 }
 
 int sora_rx11n_process_dev(sora_rx11n_t* rx, const sora_complex16* d_iq0, const sora_complex16* d_iq1, const sora_capture_desc* caps, size_t ncaps)
 {
     if (!rx || (ncaps && (!d_iq0 || !d_iq1 || !caps))) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_process_dev: null argument", 0);
     if (ncaps > rx->cfg.max_captures) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_rx11n_process_dev: more captures than max_captures", 0);
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
+    HIPCHK(hipSetDevice(rx->cfg.device));
     // stream mode: this call continues the records the one before it leaves, so calls run one after the other
-    if (rx->stream_mode) for (Pipe11n* p : rx->pipes) if (p) HIPCHK11N(hipStreamSynchronize(p->stream));
-    const int idx = next_pipe11n(rx);                                            // consecutive calls rotate over the pipelines; a released one first
+    if (rx->records.on) for (Pipe11n* p : rx->pipes) if (p) HIPCHK(hipStreamSynchronize(p->stream));
+    const int idx = call_next(rx->pipes, rx->depth);                             // consecutive calls rotate over the pipelines; a released one first
     Pipe11n* P = rx->pipes[idx];
     std::vector<CapDesc> h(ncaps);                                               // validated first: a refused call leaves the handle's calls intact
     uint64_t total = 0, slots = 0;
@@ -1039,21 +960,21 @@ int sora_rx11n_process_dev(sora_rx11n_t* rx, const sora_complex16* d_iq0, const 
     }
     if (total > rx->cfg.max_total_samples || slots > rx->cap_slots) return sora_internal_fail(SORA_ERR_CAPACITY,
             "sora_rx11n_process_dev: more samples than max_total_samples", 0);
-    HIPCHK11N(hipStreamSynchronize(P->stream));                                  // the call that used this pipeline `depth` calls ago has finished
+    HIPCHK(hipStreamSynchronize(P->stream));                                  // the call that used this pipeline `depth` calls ago has finished
     P->h_desc.swap(h);
     P->h_caps.assign(caps, caps + ncaps); P->ncaps = (uint32_t)ncaps; P->have_results = true; P->ticket = ++rx->next_ticket; P->delivered = P->released = false;
     rx->cur = idx; rx->started = true;
     if (ncaps == 0) return SORA_OK;
-    HIPCHK11N(hipMemcpyAsync(P->d_caps, P->h_desc.data(), sizeof(CapDesc) * ncaps, hipMemcpyHostToDevice, P->stream));
+    HIPCHK(hipMemcpyAsync(P->d_caps, P->h_desc.data(), sizeof(CapDesc) * ncaps, hipMemcpyHostToDevice, P->stream));
     Rx11nArgs A;
     A.iq0 = reinterpret_cast<const uint32_t*>(d_iq0); A.iq1 = reinterpret_cast<const uint32_t*>(d_iq1); A.caps = P->d_caps; A.ncaps = (uint32_t)ncaps;
     A.max_frames = rx->cfg.max_frames_per_capture; A.rows = P->d_rows; A.nframes = P->d_nframes; A.mpdu = P->d_mpdu; A.T = rx->T; A.sincos = rx->sincos; A.atan = rx->atan;
     const uint32_t nrows = (uint32_t)ncaps * rx->cfg.max_frames_per_capture;
-    HIPCHK11N(hipMemsetAsync(P->d_njobs, 0, 16, P->stream));
+    HIPCHK(hipMemsetAsync(P->d_njobs, 0, 16, P->stream));
     Scan11nArgs S;
     S.iq0 = A.iq0; S.iq1 = A.iq1; S.caps = P->d_caps; S.ncaps = (uint32_t)ncaps; S.max_frames = A.max_frames; S.rows = P->d_rows; S.nframes = P->d_nframes;
     S.T = rx->T; S.sincos = rx->sincos; S.atan = rx->atan; S.frames = P->d_frames; S.jobs = P->d_jobs; S.njobs = P->d_njobs; S.nrows = nrows;
-    if (rx->stream_mode) hipLaunchKernelGGL(k_scan11n_stream, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S, rx->d_cont, rx->d_consumed);
+    if (rx->records.on) hipLaunchKernelGGL(k_scan11n_stream, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S, rx->records.d_cont, rx->records.d_consumed);
     else hipLaunchKernelGGL(k_scan11n, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S);
     Frame11nArgs F;
     F.iq0 = A.iq0; F.iq1 = A.iq1; F.caps = P->d_caps; F.frames = P->d_frames; F.njobs = P->d_njobs; F.nrows = nrows; F.T = rx->T; F.sincos = rx->sincos; F.atan = rx->atan;
@@ -1065,9 +986,9 @@ int sora_rx11n_process_dev(sora_rx11n_t* rx, const sora_complex16* d_iq0, const 
         if (!P->d_wvecs) {
             const uint64_t cap_rows = (uint64_t)rx->cfg.max_captures * rx->cfg.max_frames_per_capture;
             P->wstride = (uint32_t)(std::min<uint64_t>(std::max<uint64_t>(kTarget, cap_rows), (uint64_t)kWinMaxUnits * cap_rows) + cap_rows);
-            HIPCHK11N(hipMalloc((void**)&P->d_wvecs, 3 * (size_t)kWinVecBytes * P->wstride));
-            HIPCHK11N(hipMalloc((void**)&P->d_wstats, 4 * kWinStatBanks * sizeof(unsigned long long)));
-            HIPCHK11N(hipMemsetAsync(P->d_wstats, 0, 4 * kWinStatBanks * sizeof(unsigned long long), P->stream));
+            HIPCHK(hipMalloc((void**)&P->d_wvecs, 3 * (size_t)kWinVecBytes * P->wstride));
+            HIPCHK(hipMalloc((void**)&P->d_wstats, 4 * kWinStatBanks * sizeof(unsigned long long)));
+            HIPCHK(hipMemsetAsync(P->d_wstats, 0, 4 * kWinStatBanks * sizeof(unsigned long long), P->stream));
         }
         const uint32_t units_max = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(kTarget, nrows), (uint64_t)kWinMaxUnits * nrows);
         hipLaunchKernelGGL(k_viterbi16w_11n, dim3((units_max + 7) / 8 + 3 + kLoneWaves), dim3(64), 0, P->stream, (const VitJob*)P->d_jobs, (const uint32_t*)P->d_njobs,
@@ -1083,7 +1004,7 @@ int sora_rx11n_process_dev(sora_rx11n_t* rx, const sora_complex16* d_iq0, const 
         hipLaunchKernelGGL(k_viterbi11n, dim3((nrows / 2 + 3 + 3) / 4), dim3(256), 0, P->stream, (const VitJob*)P->d_jobs, (const uint32_t*)P->d_njobs, 0u,
                 nrows, (const uint8_t*)P->d_soft, P->d_vout);
     hipLaunchKernelGGL(k_finish11n, dim3((nrows + 3) / 4), dim3(256), 0, P->stream, F);
-    HIPCHK11N(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SORA_OK;
 }
 
@@ -1091,73 +1012,34 @@ int sora_rx11n_process(sora_rx11n_t* rx, const sora_complex16* h_iq0, const sora
 {
     if (!rx || (nsamples && (!h_iq0 || !h_iq1))) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_process: null argument", 0);
     if (nsamples > rx->cfg.max_total_samples) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_rx11n_process: more samples than max_total_samples", 0);
-    for (size_t i = 0; i < ncaps; i++)                                               // the buffer's size is known here: no descriptor may reach past it
-        if (caps && (caps[i].offset > nsamples || caps[i].nsamples > nsamples - caps[i].offset)) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
-                "a capture descriptor reaches past the end of the sample buffer", 0);
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
+    { const int rc = check_caps_in_buffer(caps, ncaps, nsamples); if (rc) return rc; }
+    HIPCHK(hipSetDevice(rx->cfg.device));
     // the handle's own sample buffers are shared by its pipelines: calls in flight read them
-    for (Pipe11n* p : rx->pipes) if (p) HIPCHK11N(hipStreamSynchronize(p->stream));
+    for (Pipe11n* p : rx->pipes) if (p) HIPCHK(hipStreamSynchronize(p->stream));
     const sora_complex16* src[2] = { h_iq0, h_iq1 };
     for (int k = 0; k < 2; k++) {
-        if (!rx->d_iq_own[k]) HIPCHK11N(hipMalloc((void**)&rx->d_iq_own[k], sizeof(sora_complex16) * (rx->cfg.max_total_samples + 64)));
-        HIPCHK11N(hipMemcpy(rx->d_iq_own[k], src[k], sizeof(sora_complex16) * nsamples, hipMemcpyHostToDevice));
+        if (!rx->d_iq_own[k]) HIPCHK(hipMalloc((void**)&rx->d_iq_own[k], sizeof(sora_complex16) * (rx->cfg.max_total_samples + 64)));
+        HIPCHK(hipMemcpy(rx->d_iq_own[k], src[k], sizeof(sora_complex16) * nsamples, hipMemcpyHostToDevice));
     }
     return sora_rx11n_process_dev(rx, rx->d_iq_own[0], rx->d_iq_own[1], caps, ncaps);
-}
-
-static int pipe11n_results(sora_rx11n_t* rx, Pipe11n* P, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap)
-{
-    *nout = 0;
-    if (!P->have_results) return sora_internal_fail(SORA_ERR_FAILED, "no process call to report", 0);
-    if (P->ncaps == 0) return SORA_OK;
-    HIPCHK11N(hipSetDevice(rx->cfg.device));
-    HIPCHK11N(hipStreamSynchronize(P->stream));
-    const uint32_t mf = rx->cfg.max_frames_per_capture;
-    std::vector<Rx11bRow> rows((size_t)P->ncaps * mf); std::vector<uint32_t> nfr(P->ncaps);
-    HIPCHK11N(hipMemcpy(rows.data(), P->d_rows, sizeof(Rx11bRow) * rows.size(), hipMemcpyDeviceToHost));
-    HIPCHK11N(hipMemcpy(nfr.data(), P->d_nframes, 4 * (size_t)P->ncaps, hipMemcpyDeviceToHost));
-    size_t used_rows = 0;
-    for (uint32_t c = 0; c < P->ncaps; c++) used_rows += nfr[c] < mf ? nfr[c] : mf;
-    std::vector<uint8_t> bulk;
-    const size_t slots = (size_t)P->ncaps * mf;
-    if (h_mpdu && used_rows > 16 && slots * 4096 <= ((size_t)1 << 30)) {
-        bulk.resize(slots * 4096);
-        HIPCHK11N(hipMemcpy(bulk.data(), P->d_mpdu, bulk.size(), hipMemcpyDeviceToHost));
-    }
-    size_t n = 0, moff = 0; int rc = SORA_OK;
-    for (uint32_t c = 0; c < P->ncaps; c++)
-        for (uint32_t i = 0; i < nfr[c] && i < mf; i++) {
-            const Rx11bRow& r = rows[(size_t)c * mf + i];
-            if (n >= max_out) { rc = SORA_ERR_CAPACITY; continue; }
-            sora_frame_result& o = out[n++];
-            memset(&o, 0, sizeof(o));
-            o.capture_id = P->h_caps[c].capture_id; o.end_sample = r.end_sample; o.error_code = r.error_code; o.rate_kbps = r.rate_kbps;
-            o.length = (uint16_t)r.length; o.crc32 = r.crc32; o.mpdu_offset = (uint32_t)moff;
-            if (i + 1 == mf && nfr[c] > mf) o.flags = SORA_ROW_TRUNCATED;             // more frames were found than the capture has rows
-            if (h_mpdu && (r.error_code == 1u || r.error_code == 0x80000006u)) {
-                const size_t len = r.length < 4096 ? r.length : 4096;
-                if (moff + len > mpdu_cap) { rc = SORA_ERR_CAPACITY; continue; }
-                if (!bulk.empty()) memcpy(h_mpdu + moff, bulk.data() + ((size_t)c * mf + i) * 4096, len);
-                else HIPCHK11N(hipMemcpy(h_mpdu + moff, P->d_mpdu + ((size_t)c * mf + i) * 4096, len, hipMemcpyDeviceToHost));
-                moff += len;
-            }
-        }
-    *nout = n;
-    if (rc != SORA_OK) return sora_internal_fail(rc, "sora_rx11n_results: output buffer too small", 0);
-    return SORA_OK;
 }
 
 int sora_rx11n_results(sora_rx11n_t* rx, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap)
 {
     if (!rx || !nout) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_results: null argument", 0);
-    return pipe11n_results(rx, rx->pipes[rx->cur], out, max_out, nout, h_mpdu, mpdu_cap);
+    *nout = 0;
+    const Pipe11n* P = rx->pipes[rx->cur];
+    if (!P->have_results) return sora_internal_fail(SORA_ERR_FAILED, "no process call to report", 0);
+    return sora_internal_rows_results(P->d_rows, P->d_nframes, P->d_mpdu, P->h_caps.data(), P->ncaps, rx->cfg.max_frames_per_capture, rx->cfg.device, P->stream,
+                                      "sora_rx11n_results", out, max_out, nout, h_mpdu, mpdu_cap);
 }
 
 int sora_rx11n_results_of(sora_rx11n_t* rx, int ticket, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap)
 {
     if (!rx || !nout) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_results_of: null argument", 0);
-    Pipe11n* P = pipe11n_of(rx, ticket);
-    if (!P) { *nout = 0; return sora_internal_fail(SORA_ERR_INVALID_PARAM,
-            "sora_rx11n_results_of: stale ticket (its pipeline has been reused by a later process call, or the ticket was never issued)", 0); }
-    return pipe11n_results(rx, P, out, max_out, nout, h_mpdu, mpdu_cap);
+    *nout = 0;
+    const Pipe11n* P = call_find(rx->pipes, rx->depth, ticket);
+    if (!P) return call_stale("sora_rx11n_results_of");
+    return sora_internal_rows_results(P->d_rows, P->d_nframes, P->d_mpdu, P->h_caps.data(), P->ncaps, rx->cfg.max_frames_per_capture, rx->cfg.device, P->stream,
+                                      "sora_rx11n_results_of", out, max_out, nout, h_mpdu, mpdu_cap);
 }

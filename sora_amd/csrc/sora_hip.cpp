@@ -14,9 +14,9 @@
 #include <mutex>
 #include <string>
 #include <vector>
-#include <thread>
 #include "../../include/sora_hip.h"
 #include "kernels.h"
+#include "host_calls.h"
 #include "dev_winplan.h"
 
 using namespace sora;
@@ -39,7 +39,6 @@ static int fail(int code, const char* what, hipError_t e = hipSuccess)
     g_last_error = buf;
     return code;
 }
-#define HIPCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) return fail(SORA_ERR_HARDWARE_FAILED, #call, _e); } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // Look-up tables, regenerated from closed forms (each was checked entry-for-entry against the reference header it
@@ -404,10 +403,9 @@ const uint32_t* sora_internal_crc_table(int device)
 }
 
 // ------------------------------------------------------------------------------------------------
-// One receive pipeline: a stream, the device arrays of one call in flight, and that call's bookkeeping.
-struct RxPipe {
+// One receive pipeline: a stream, the device arrays of one call in flight, and that call's bookkeeping (its ticket and completion state: host_calls.h).
+struct RxPipe : Call {
     sora_rx_cfg cfg{};
-    hipStream_t stream = nullptr;
     DevTables tabs;
     uint32_t str = 1;
     // capacities
@@ -448,10 +446,6 @@ struct RxPipe {
     CapDesc* h_caps_pinned = nullptr; size_t caps_resident = 0; hipEvent_t ev_caps = nullptr;
     uint32_t ncaps = 0, total_slots = 0;
     bool have_results = false;
-    int ticket = 0;              // the process call this pipeline holds (sora_rx_ticket); 0 = none
-    // completion order (sora_rx_wait_any): a call whose delivery has been enqueued (ev_done follows its last copy) and waited for is RELEASED --
-    // everything it produced is in the caller's memory -- and its pipeline may be reused ahead of older calls still in flight
-    hipEvent_t ev_done = nullptr; bool delivered = false, released = false;
     // Opt-in (SORA_HIP_GRAPH=1): a call that repeats the previous one's geometry (same IQ buffer, same capture set) replays
     // the kernel chain as one hipGraph launch.  Off by default: on this path the GPU time per call dwarfs the six enqueues,
     // and instantiating the graph on the second identical call costs more than it saves for short runs.
@@ -1029,9 +1023,7 @@ static int pipe_deliver_async(RxPipe* rx, sora_frame_result* h_rows, size_t max_
     if (nr) HIPCHK(hipMemcpyAsync(h_rows, rx->d_rows, sizeof(sora_frame_result) * nr, hipMemcpyDeviceToHost, rx->stream));
     // (a call bound to this very array has written its MPDUs there already: sora_rx_bind_mpdu)
     if (h_mpdu && need && h_mpdu != rx->bound_mpdu) HIPCHK(hipMemcpyAsync(h_mpdu, rx->d_mpdu, need, hipMemcpyDeviceToHost, rx->stream));
-    if (!rx->ev_done) HIPCHK(hipEventCreateWithFlags(&rx->ev_done, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(rx->ev_done, rx->stream));
-    rx->delivered = true;
+    HIPCHK(call_mark_delivered(*rx));
     return SORA_OK;
 }
 
@@ -1058,9 +1050,7 @@ struct sora_rx {
     bool profiling = false;
     int seq = 0;                 // ticket of the most recent process call
     RxPipe* pipes[kMaxDepth] = {};
-    // stream mode (sora_rx_set_stream_mode): capture k of a call continues capture k of the call before it
-    bool stream_mode = false;
-    uint32_t* d_cont = nullptr; uint32_t* d_consumed = nullptr;
+    StreamRecords records{kContWords};                                            // sora_rx_set_stream_mode
     // tool hook (sora_internal_rx_timeline)
     std::vector<float> tl; hipEvent_t tl_base = nullptr;
     // k_pipe's safety net: the bound of the waits inside its launch; the host-mapped word its finishing kernel sets when one of them gave up (the call's rows are
@@ -1093,30 +1083,6 @@ static bool chip_is_shared(const sora_rx* me)
         if (rows >= kBatchRows && t != 0 && now - t < g_shared_window_ns.load(std::memory_order_relaxed)) return true;
     }
     return false;
-}
-
-static RxPipe* pipe_of(sora_rx* rx, int ticket)
-{
-    if (!rx || ticket <= 0) return nullptr;
-    for (RxPipe* p : rx->pipes) if (p && p->ticket == ticket) return p;
-    return nullptr;
-}
-
-// The pipeline the next process call uses: an unused one; else the RELEASED call with the oldest ticket (delivered and waited for: nothing of it is
-// left to read on the device); else the oldest call -- plain rotation, the call then waits for that pipeline's stream as it always did.  A host that only
-// ever waits for its oldest ticket sees exactly the round-robin of before; one that takes completions as they come (sora_rx_wait_any) keeps every
-// pipeline busy although calls overtake one another (their streams sit on different dispatch priorities).
-static int next_pipe(const sora_rx* rx)
-{
-    if (!rx->started) return 0;
-    int best = -1, best_rel = -1;
-    for (int i = 0; i < rx->depth; i++) {
-        const RxPipe* p = rx->pipes[i];
-        if (!p || p->ticket == 0) return i;
-        if (p->released && (best_rel < 0 || p->ticket < rx->pipes[best_rel]->ticket)) best_rel = i;
-        if (best < 0 || p->ticket < rx->pipes[best]->ticket) best = i;
-    }
-    return best_rel >= 0 ? best_rel : best;
 }
 
 static RxPipe* pipe_at(sora_rx* rx, int i)
@@ -1155,8 +1121,7 @@ void sora_rx_destroy(sora_rx_t* rx)
     if (!rx) return;
     { std::lock_guard<std::mutex> lk(g_rx_mu); g_rx_all.erase(std::remove(g_rx_all.begin(), g_rx_all.end(), rx), g_rx_all.end()); }
     for (RxPipe* p : rx->pipes) if (p) pipe_destroy(p);
-    if (rx->d_cont) (void)hipFree(rx->d_cont);
-    if (rx->d_consumed) (void)hipFree(rx->d_consumed);
+    rx->records.free();
     if (rx->tl_base) (void)hipEventDestroy(rx->tl_base);
     if (rx->h_note) (void)hipHostFree(rx->h_note);
     delete rx;
@@ -1258,7 +1223,7 @@ int sora_rx_call_front(sora_rx_t* rx, int ticket)                              /
 {
     if (!rx) return SORA_ERR_INVALID_PARAM;
     if (ticket == 0) ticket = rx->seq;
-    RxPipe* p = pipe_of(rx, ticket);
+    RxPipe* p = call_find(rx->pipes, sora_rx::kMaxDepth, ticket);
     return p ? p->front : fail(SORA_ERR_INVALID_PARAM, "sora_rx_call_front: no call with this ticket is held by the handle");
 }
 uint32_t sora_hip_set_share_window_us(uint32_t us)
@@ -1350,11 +1315,7 @@ int sora_rx_reset(sora_rx_t* rx)
 {
     if (!rx) return SORA_ERR_INVALID_PARAM;
     for (RxPipe* p : rx->pipes) if (p) { const int rc = pipe_reset(p); if (rc) return rc; }
-    if (rx->d_cont) {                                                            // ISource::Reset: every stream starts afresh
-        HIPCHK(hipMemset(rx->d_cont, 0, 4 * (size_t)kContWords * rx->cfg.max_captures));
-        HIPCHK(hipMemset(rx->d_consumed, 0, 4 * (size_t)rx->cfg.max_captures));
-    }
-    return SORA_OK;
+    return rx->records.zero(rx->cfg.max_captures);                               // ISource::Reset: every stream starts afresh
 }
 
 int sora_rx_flush(sora_rx_t* rx)
@@ -1371,42 +1332,23 @@ void* sora_rx_stream(sora_rx_t* rx) { return rx ? pipe_stream(rx->pipes[rx->cur]
 static int stream_prologue(sora_rx* rx, RxPipe* p)
 {
     p->cont = nullptr; p->consumed = nullptr;
-    if (!rx->stream_mode) return SORA_OK;
-    for (RxPipe* q : rx->pipes) if (q) { const int rc = pipe_flush(q); if (rc) return rc; }
-    p->cont = rx->d_cont; p->consumed = rx->d_consumed; p->last_valid = false;
+    if (!rx->records.on) return SORA_OK;
+    { const int rc = sora_rx_flush(rx); if (rc) return rc; }
+    p->cont = rx->records.d_cont; p->consumed = rx->records.d_consumed; p->last_valid = false;
     return SORA_OK;
 }
 
 int sora_rx_set_stream_mode(sora_rx_t* rx, int enable)
 {
     if (!rx) return SORA_ERR_INVALID_PARAM;
-    const int old = rx->stream_mode ? 1 : 0;
-    if (enable < 0) return old;
-    HIPCHK(hipSetDevice(rx->cfg.device));
-    for (RxPipe* q : rx->pipes) if (q) { const int rc = pipe_flush(q); if (rc) return rc; }
-    if (enable && !rx->d_cont) {
-        HIPCHK(hipMalloc((void**)&rx->d_cont, 4 * (size_t)kContWords * rx->cfg.max_captures));
-        HIPCHK(hipMalloc((void**)&rx->d_consumed, 4 * (size_t)rx->cfg.max_captures));
-    }
-    if (rx->d_cont) {                                                            // switching either way starts every stream afresh
-        HIPCHK(hipMemset(rx->d_cont, 0, 4 * (size_t)kContWords * rx->cfg.max_captures));
-        HIPCHK(hipMemset(rx->d_consumed, 0, 4 * (size_t)rx->cfg.max_captures));
-    }
-    rx->stream_mode = enable != 0;
-    return old;
+    if (enable >= 0) { const int rc = sora_rx_flush(rx); if (rc) return rc; }
+    return rx->records.set(enable, rx->cfg.device, rx->cfg.max_captures);
 }
 
 int sora_rx_stream_consumed(sora_rx_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps)
 {
     if (!rx || !h_consumed) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_stream_consumed: null argument");
-    if (!rx->stream_mode) return fail(SORA_ERR_FAILED, "sora_rx_stream_consumed: the handle is not in stream mode");
-    RxPipe* p = pipe_of(rx, ticket);
-    if (!p || ticket != rx->seq) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_stream_consumed: only the most recent call's resume points exist");
-    if (ncaps > p->ncaps) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_stream_consumed: more captures than the call had");
-    HIPCHK(hipSetDevice(rx->cfg.device));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    if (ncaps) HIPCHK(hipMemcpy(h_consumed, rx->d_consumed, 4 * ncaps, hipMemcpyDeviceToHost));
-    return SORA_OK;
+    return rx->records.consumed("sora_rx_stream_consumed", rx->cfg.device, call_find(rx->pipes, sora_rx::kMaxDepth, ticket), ticket == rx->seq, h_consumed, ncaps);
 }
 
 // The kernels of the next call on pipeline p (the handle's settings, its capacity in flight, what else the chip is doing).  k_pipe's finishing kernel leaves a note when a
@@ -1429,7 +1371,7 @@ static void choose_kernels(sora_rx* rx, RxPipe* p)
 int sora_rx_process_dev(sora_rx_t* rx, const sora_complex16* d_iq, const sora_capture_desc* caps, size_t ncaps)
 {
     if (!rx) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_process_dev: null argument");
-    const int next = next_pipe(rx);
+    const int next = call_next(rx->pipes, rx->depth);
     RxPipe* p = pipe_at(rx, next);
     if (!p) return SORA_ERR_HARDWARE_FAILED;
     { const int rc = stream_prologue(rx, p); if (rc) return rc; }
@@ -1442,7 +1384,7 @@ int sora_rx_process_dev(sora_rx_t* rx, const sora_complex16* d_iq, const sora_ca
 int sora_rx_process(sora_rx_t* rx, const sora_complex16* h_iq, size_t total_samples, const sora_capture_desc* caps, size_t ncaps)
 {
     if (!rx) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_process: null argument");
-    const int next = next_pipe(rx);
+    const int next = call_next(rx->pipes, rx->depth);
     RxPipe* p = pipe_at(rx, next);
     if (!p) return SORA_ERR_HARDWARE_FAILED;
     { const int rc = stream_prologue(rx, p); if (rc) return rc; }
@@ -1455,7 +1397,7 @@ int sora_rx_process(sora_rx_t* rx, const sora_complex16* h_iq, size_t total_samp
 int sora_rx_process_dump(sora_rx_t* rx, const void* h_dump, size_t dump_bytes, unsigned ingest_flags, const sora_capture_desc* caps, size_t ncaps)
 {
     if (!rx) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_process_dump: null argument");
-    const int next = next_pipe(rx);
+    const int next = call_next(rx->pipes, rx->depth);
     RxPipe* p = pipe_at(rx, next);
     if (!p) return SORA_ERR_HARDWARE_FAILED;
     { const int rc = stream_prologue(rx, p); if (rc) return rc; }
@@ -1536,66 +1478,49 @@ int sora_rx_results_dev(sora_rx_t* rx, const sora_frame_result** d_rows, const u
 
 int sora_rx_ticket(sora_rx_t* rx) { return rx && rx->started ? rx->pipes[rx->cur]->ticket : 0; }
 
-static const char* const kStale = "stale ticket: its pipeline has been reused by a later process call (or the ticket was never issued)";
-
+// Tickets are looked up, and delivered calls polled, among all kMaxDepth pipelines; the next call is placed among the first `depth`
 int sora_rx_wait(sora_rx_t* rx, int ticket)
 {
-    RxPipe* p = pipe_of(rx, ticket);
-    if (!p) return fail(SORA_ERR_INVALID_PARAM, kStale);
-    const int rc = pipe_flush(p);
-    if (rc == SORA_OK && p->delivered) p->released = true;
-    return rc;
+    RxPipe* p = rx ? call_find(rx->pipes, sora_rx::kMaxDepth, ticket) : nullptr;
+    return p ? call_wait(p->cfg.device, *p) : call_stale("sora_rx_wait");
 }
 
 int sora_rx_wait_any(sora_rx_t* rx, int* ticket)
 {
     if (!rx || !ticket) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_wait_any: null argument");
-    *ticket = 0;
-    HIPCHK(hipSetDevice(rx->cfg.device));
-    for (unsigned spin = 0;; spin++) {
-        RxPipe* done = nullptr; bool pending = false;
-        for (int i = 0; i < sora_rx::kMaxDepth; i++) {
-            RxPipe* p = rx->pipes[i];
-            if (!p || p->ticket == 0 || !p->delivered || p->released) continue;
-            pending = true;
-            const hipError_t q = hipEventQuery(p->ev_done);
-            if (q == hipSuccess) { if (!done || p->ticket < done->ticket) done = p; }
-            else if (q != hipErrorNotReady) { (void)hipGetLastError(); return fail(SORA_ERR_HARDWARE_FAILED, "sora_rx_wait_any: hipEventQuery failed"); }
-        }
-        if (done) {
-            const int rc = pipe_flush(done);                                    // (its stream is idle: returns at once)
-            if (rc) return rc;
-            done->released = true; *ticket = done->ticket;
-            return SORA_OK;
-        }
-        if (!pending) return fail(SORA_ERR_FAILED, "sora_rx_wait_any: no call with an enqueued delivery (sora_rx_deliver_async) is in flight");
-        (void)hipGetLastError();                                                // (hipErrorNotReady is sticky for hipGetLastError)
-        if (spin > 64) std::this_thread::yield();
-    }
+    return calls_wait_any(rx->pipes, sora_rx::kMaxDepth, rx->cfg.device, ticket, "sora_rx", [rx](int t) { return sora_rx_wait(rx, t); });
 }
 
-void* sora_rx_stream_of(sora_rx_t* rx, int ticket) { RxPipe* p = pipe_of(rx, ticket); return p ? pipe_stream(p) : nullptr; }
+void* sora_rx_stream_of(sora_rx_t* rx, int ticket)
+{
+    RxPipe* p = rx ? call_find(rx->pipes, sora_rx::kMaxDepth, ticket) : nullptr;
+    return p ? pipe_stream(p) : nullptr;
+}
 
 int sora_rx_results_of(sora_rx_t* rx, int ticket, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap)
 {
-    RxPipe* p = pipe_of(rx, ticket);
-    if (!p) return fail(SORA_ERR_INVALID_PARAM, kStale);
+    RxPipe* p = rx ? call_find(rx->pipes, sora_rx::kMaxDepth, ticket) : nullptr;
+    if (!p) return call_stale("sora_rx_results_of");
     return pipe_results(p, out, max_out, nout, h_mpdu, mpdu_cap);
 }
 
 int sora_rx_results_dev_of(sora_rx_t* rx, int ticket, const sora_frame_result** d_rows, const uint32_t** d_nrows, const uint8_t** d_mpdu)
 {
-    RxPipe* p = pipe_of(rx, ticket);
-    if (!p) return fail(SORA_ERR_INVALID_PARAM, kStale);
+    RxPipe* p = rx ? call_find(rx->pipes, sora_rx::kMaxDepth, ticket) : nullptr;
+    if (!p) return call_stale("sora_rx_results_dev_of");
     return pipe_results_dev(p, d_rows, d_nrows, d_mpdu);
 }
 
-size_t sora_rx_mpdu_bytes(sora_rx_t* rx, int ticket) { RxPipe* p = pipe_of(rx, ticket); return p ? (size_t)kOutPerSlot * p->total_slots : 0; }
+size_t sora_rx_mpdu_bytes(sora_rx_t* rx, int ticket)
+{
+    RxPipe* p = rx ? call_find(rx->pipes, sora_rx::kMaxDepth, ticket) : nullptr;
+    return p ? (size_t)kOutPerSlot * p->total_slots : 0;
+}
 
 int sora_rx_deliver_async(sora_rx_t* rx, int ticket, sora_frame_result* h_rows, size_t max_rows, uint32_t* h_nrows, uint8_t* h_mpdu, size_t mpdu_bytes)
 {
-    RxPipe* p = pipe_of(rx, ticket);
-    if (!p) return fail(SORA_ERR_INVALID_PARAM, kStale);
+    RxPipe* p = rx ? call_find(rx->pipes, sora_rx::kMaxDepth, ticket) : nullptr;
+    if (!p) return call_stale("sora_rx_deliver_async");
     return pipe_deliver_async(p, h_rows, max_rows, h_nrows, h_mpdu, mpdu_bytes);
 }
 

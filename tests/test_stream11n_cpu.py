@@ -29,12 +29,30 @@ def test_exports_are_declared_bound_and_typed(lib):
         assert getattr(lib, n).argtypes is not None, n
 
 
-def test_null_handle_is_an_invalid_parameter(lib):
-    out = (ctypes.c_uint32 * 4)()
-    assert lib.sora_rx11n_set_stream_mode(None, 1) == SORA_ERR_INVALID_PARAM
-    assert lib.sora_rx11n_set_stream_mode(None, -1) == SORA_ERR_INVALID_PARAM
-    assert lib.sora_rx11n_stream_consumed(None, 1, ctypes.cast(out, ctypes.c_void_p), 4) == SORA_ERR_INVALID_PARAM
-    assert b"sora_rx11n_stream_consumed" in lib.sora_hip_last_error()
+# every receive handle's calls-in-flight and stream-mode entry points, and those whose message names them for a null handle
+PREFIXES = ("sora_rx", "sora_rx11b", "sora_rx11n", "sora_ht40")
+NAMED = {"sora_rx": {"wait_any", "stream_consumed"}, "sora_rx11b": {"wait_any", "set_stream_mode", "stream_consumed"},
+         "sora_rx11n": {"wait", "wait_any", "results_of", "deliver_async", "set_stream_mode", "stream_consumed"}, "sora_ht40": {"wait_any"}}
+
+
+@pytest.mark.parametrize("pre", PREFIXES)
+def test_null_handle_is_an_invalid_parameter(lib, pre):
+    from sora_amd import capi
+    out = (ctypes.c_uint32 * 4)(); rows = (capi.FrameResult * 4)(); n = ctypes.c_size_t(0); t = ctypes.c_int(0)
+    calls = [("wait", (None, 1)), ("wait_any", (None, ctypes.byref(t))), ("results_of", (None, 1, rows, 4, ctypes.byref(n), None, 0)),
+             ("deliver_async", (None, 1, None, 0, None, None, 0)), ("set_stream_mode", (None, 1)), ("set_stream_mode", (None, -1)),
+             ("stream_consumed", (None, 1, ctypes.cast(out, ctypes.c_void_p), 4))]
+    for fn, args in calls:
+        name = pre + "_" + fn
+        if name not in capi.EXPORTS:
+            continue
+        lib.sora_hip_table_digest(None, None)                           # leaves a message that names no receive handle
+        assert getattr(lib, name)(*args) == SORA_ERR_INVALID_PARAM, name
+        if fn in NAMED[pre]:
+            assert name.encode() in lib.sora_hip_last_error(), (name, lib.sora_hip_last_error())
+    assert getattr(lib, pre + "_ticket")(None) == 0
+    if pre + "_stream_of" in capi.EXPORTS:
+        assert getattr(lib, pre + "_stream_of")(None, 1) is None
 
 
 def kernel_metadata(tmp_path):
