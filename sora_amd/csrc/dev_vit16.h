@@ -1,6 +1,7 @@
 // dev_vit16.h -- the pieces of the 16-lanes-per-frame-pair trellis layout shared by k_viterbi16 (k_vit16.hip: one serial chain per frame) and
-// k_viterbi16w (k_vitwin.hip: the window-parallel form, round 5): the LDS layout, the coset <-> lane maps, the add-compare-select step and the
-// lane-parallel trace-back of one window.  The layout itself is described at the top of k_vit16.hip.
+// k_viterbi16w (k_vitwin.hip: the window-parallel form, round 5): the LDS layout, the coset <-> lane maps, the add-compare-select step, the
+// lane's state and chunk machinery of the forward pass (Forward16: forward16 of k_vit16.hip and forward16w of dev_vitwin.h put their loops and
+// schedules on top of it) and the lane-parallel trace-back of one window.  The layout itself is described at the top of k_vit16.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels.h"
@@ -22,7 +23,7 @@ template <int WIN, int LOOK> struct Lds16 {
         uint32_t udump[4][64];                                                  // the metrics registers at a trace-back (the start state's unfinished block)
         // [row][operand of the chunk][frame]: the soft values as metric fields -- live only inside
         uint16_t ops[4][24][2];
-        //   forward16's unpack() / the fast loop's two alternating tables, never across a trace-back:
+        //   Forward16::unpack() / forward16's two alternating tables of its fast loop, never across a trace-back:
         uint16_t ops2[2][4][24][2];
     };                                                                          //   they share their bytes with the trace-back's register dump
     uint8_t  path[8][Geom16<WIN, LOOK>::kPathBytes];                             // [row * 2 + frame][walk position]: the bytes along the traced path
@@ -111,8 +112,145 @@ __device__ __forceinline__ unsigned row_pkmin(unsigned v)
 }
 __device__ __forceinline__ unsigned wave_min_u32(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)dpp_min_u32_wave(v)); }
 __device__ __forceinline__ unsigned wave_max_u32(unsigned v) { return ~wave_min_u32(~v); }
-__device__ __forceinline__ void lds_fence() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
+
+// The forward pass of a wave in this layout, less its loop and its schedule: the lane's metrics and masks, its part in fetching a chunk of soft values and handing
+// them round the row, the steps of a chunk, the ring position.  The form on top owns what ends a run of steps (next_thr, all_done, its check()).
+template <int CR, int WIN, int LOOK, int BITS>
+struct Forward16 {
+    static constexpr int P = Geom16<WIN, LOOK>::P, GB = Puncture<CR>::GB, GS = Puncture<CR>::GS, CW = Puncture<CR>::CW;
+    static constexpr int NV = Puncture<CR>::NV;                                 // soft values a lane fetches per chunk: operands j, j + 8 (, j + 16) of its frame
+    struct Chunk { uint32_t v[CW]; };
+    struct Raw { SoftRaw r[NV]; };
+
+    Vit16 V;
+    unsigned row, half;                                                         // this lane's frame: (row, half)
+    uint32_t my_j;
+    SoftCursor<BITS, CW> cur[NV];
+    const uint8_t* soft;
+    uint16_t* my_ops;
+    const uint4* row_ops;
+    uint32_t pos;                                                               // ring position (block index % P) of the current row's first block
+    unsigned pos512[3];
+    uint32_t tr, nsteps;                                                        // steps taken / of the wave's longest side (wave-uniform)
+    uint32_t next_thr;
+    bool all_done;
+
+    // start: the metric of every state but state 0 (both halves); my_soft_off, my_first, my_last: this lane's frame's stream, the value of its first step, its last
+    // value (fetches past it repeat it: well-formed operands nobody uses)
+    __device__ __forceinline__ void init(Lds16<WIN, LOOK>& S, const uint8_t* __restrict__ soft_, uint32_t my_soft_off, uint32_t my_first, uint32_t my_last, unsigned start,
+                                         uint32_t nsteps_)
+    {
+        const unsigned lane = threadIdx.x & 63, l16 = lane & 15;
+        row = lane >> 4; half = lane & 1u;
+        const unsigned v0 = v_of_lane(l16);
+        nsteps = nsteps_;
+#pragma unroll
+        for (int i = 0; i < 4; i++) V.U[i] = (v0 ^ kW[i]) == 0 ? 0u : start;
+        const unsigned ring_base = (unsigned)(uintptr_t)&S.ring[0][0][0];       // (the low half of a flat LDS address is the LDS offset)
+#pragma unroll
+        for (int jb = 0; jb < 3; jb++)
+#pragma unroll
+            // (8 jb + 8) mod 6
+            for (int i = 0; i < 4; i++) V.sadr[jb][i] = ring_base + ((row * 64u + rev6u(rol6(v0 ^ kW[i], jb == 0 ? 2 : jb == 1 ? 4 : 0))) << 1);
+#pragma unroll
+        for (int t = 0; t < 24; t++) {
+            const int ph = t % 6, k = t % 8;
+            const unsigned n = rol6(v0, ph + 1);                                // register 0's state after the step (all four registers agree on the masks)
+            const bool vb = (v0 >> (5 - ph)) & 1u;                              // the lane's half of the role bit
+            const unsigned ma = (__popc(n & 0155) & 1) ? 7u * kFld : 0u, mb = (__popc(n & 0117) & 1) ? 7u * kFld : 0u;
+            const unsigned mx = Puncture<CR>::which_of(ph) == 2 ? mb : ma;
+            V.MX[t] = vb ? ((mx ^ (7u * kFld)) | (kOne << k)) : mx;
+            if (t < 6) V.MY[t] = vb ? (mb ^ (7u * kFld)) : mb;
+        }
+        tr = 0; pos = 0;
+        my_j = l16 >> 1;
+#pragma unroll
+        for (int v = 0; v < NV; v++) cur[v].init(my_soft_off, my_first + my_j + 8u * v, my_last);
+        soft = soft_;
+        my_ops = &S.ops[row][my_j][half];
+        row_ops = reinterpret_cast<const uint4*>(&S.ops[row][0][0]);
+        set_row_pos();
+    }
+    __device__ __forceinline__ bool going() const { return tr < nsteps && !all_done; }
+
+    __device__ __forceinline__ void normalize()                                 // Normalize (viterbicore.h:444-465): the row's minimum, both frames
+    {
+        const unsigned m = row_pkmin(pk_min16(pk_min16(V.U[0], V.U[1]), pk_min16(V.U[2], V.U[3])));
+#pragma unroll
+        for (int i = 0; i < 4; i++) V.U[i] -= m;
+    }
+    static __device__ __forceinline__ uint32_t pos_of(uint32_t p, int jb) { const uint32_t q = p + (uint32_t)jb; return q >= (uint32_t)P ? q - (uint32_t)P : q; }
+    __device__ __forceinline__ void set_row_pos()
+    {
+#pragma unroll
+        for (int jb = 0; jb < 3; jb++) pos512[jb] = pos_of(pos, jb) * 512u;
+    }
+    __device__ __forceinline__ void end_row() { pos = pos_of(pos, 3); set_row_pos(); }
+    __device__ __forceinline__ Raw fetch(uint32_t c) const                      // chunk c: the loads only
+    {
+        Raw R;
+#pragma unroll
+        for (int v = 0; v < NV; v++) R.r[v] = cur[v].fetch(soft, c);
+        return R;
+    }
+    // a chunk's fields into the lane's slots of an operand table (operand j + 8 v; slots up to 23 exist, those past CW are never read) ...
+    __device__ __forceinline__ void put(const Raw& R, uint16_t* mine) const
+    {
+#pragma unroll
+        for (int v = 0; v < NV; v++) mine[16 * v] = (uint16_t)cur[v].field(R.r[v]);
+    }
+    // ... and the row's table into every lane's registers
+    static __device__ __forceinline__ Chunk get(const uint4* table)
+    {
+        Chunk K;
+#pragma unroll
+        for (int i = 0; i < (CW + 3) / 4; i++) {
+            const uint4 x = table[i];
+            K.v[4 * i] = x.x; K.v[4 * i + 1] = x.y;
+            if (4 * i + 2 < CW) { K.v[4 * i + 2] = x.z; K.v[4 * i + 3] = x.w; }
+        }
+        return K;
+    }
+    __device__ __forceinline__ Chunk unpack(const Raw& R) const                 // ... their values -> the row's operand table -> every lane's registers
+    {
+        put(R, my_ops);
+        lds_fence();
+        const Chunk K = get(row_ops);
+        lds_fence();
+        return K;
+    }
+    // one puncture group = GS steps; i0 = step inside the chunk, h = half of the 24-step row
+    __device__ __forceinline__ void group(const Chunk& K, int h, int i0)
+    {
+        const int k0 = i0 / GS * GB, t24 = 12 * h + i0;
+        acs16<0, P>(V, t24, K.v[k0], K.v[k0 + 1], pos512);                      // ACS(A,B)
+        if (CR != 0) acs16<1, P>(V, t24 + 1, K.v[k0 + 2], 0, pos512);           // ACS(A)     2/3, 3/4 (viterbi.hpp:173-187)
+        if (CR == 2) acs16<2, P>(V, t24 + 2, 0, K.v[k0 + 3], pos512);           // ACS(B)     3/4
+        if ((t24 + GS) % 8 == 0) normalize();                                   // (trellis index & 7) == 0 after a group
+    }
+    __device__ __forceinline__ void fast_chunk(const Chunk& K, int h)           // 12 steps, no trace-back due inside: straight-line code
+    {
+#pragma unroll
+        for (int g = 0; g < 12 / GS; g++) group(K, h, g * GS);
+        tr += 12;
+    }
+    // up to 12 steps with the schedule examined after every group (check(t24 of the group's last step): the form's)
+    template <typename CHECK> __device__ __forceinline__ void slow_chunk(const Chunk& K, int h, CHECK& check)
+    {
+#pragma unroll
+        for (int g = 0; g < 12 / GS; g++) {
+            if (going()) {
+                group(K, h, g * GS);
+                tr += GS;
+                check(12 * h + g * GS + GS - 1);
+            }
+        }
+    }
+    template <typename CHECK> __device__ __forceinline__ void chunk(const Chunk& K, int h, CHECK& check)   // tr % 24 == 12 h on entry
+    {
+        if (tr + 12 <= nsteps && next_thr > tr + 12) fast_chunk(K, h); else slow_chunk(K, h, check);
+    }
+};
 
 // Trace-back of one window for every frame of the wave whose count is non-zero (my_cnt: this lane's frame = (row, lane & 1)); kept out of
 // line (it is reached from every puncture group of the slow path), so everything arrives by value and the LDS block by its offset.

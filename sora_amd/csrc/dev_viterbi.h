@@ -1,5 +1,6 @@
 // dev_viterbi.h -- the 64-state trellis machinery shared by k_viterbi (k_rx.hip: soft values from the frames' packed streams in HBM, handed
-// round through an operand table in LDS) and k_viterbi16 (k_vit16.hip: the same in the 16-lanes-per-pair layout).
+// round through an operand table in LDS) and k_viterbi16 (k_vit16.hip: the same in the 16-lanes-per-pair layout), and the forward pass of the
+// 64-lanes-per-pair layout (VitForward: what viterbi_forward and viterbi_forward_unit of k_rx.hip run under their two schedules).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rx_types.h"
@@ -43,6 +44,21 @@ namespace sora {
 // v_pk_min_u16; the cross-lane moves carry both).  Measured issue cost on gfx950 at 2 waves/SIMD (tools/gen_probe_issue.py):
 // VOP2 add/sub/xor/and/mov 5.0, VOP3/VOP3P/DPP 9.4, compare->SGPR / v_addc 9.9, permlane swap 16.9 (units of 0.67 ns).
 // Per packed step: 1 move + 2 adds + 1 min + 2..3 for the branch metrics; no compare, no carry chain, no LDS.
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }   // a per-wave uniform value: keep it in an SGPR
+// LDS written by some lanes of the wave, read by others
+__device__ __forceinline__ void lds_fence() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
+constexpr uint32_t kNever = 0xFFFFFFFFu;
+
+// The puncture pattern of code rate CR (0 = 1/2, 1 = 2/3, 2 = 3/4)
+template <int CR> struct Puncture {
+    static constexpr int GB = CR == 0 ? 2 : CR == 2 ? 4 : 3;                    // soft values per puncture group
+    static constexpr int GS = CR == 0 ? 1 : CR == 2 ? 3 : 2;                    // trellis steps per group
+    static constexpr int CW = 12 / GS * GB;                                     // operands (dwords) per 12-step chunk: 24 / 18 / 16
+    static constexpr int NV = (CW + 7) / 8;                                     // sixteen-lane layout: soft values a lane fetches per chunk
+    static constexpr int which_of(int ph) { return CR == 0 ? 0 : CR == 1 ? (ph & 1) : ph % 3; }   // step kinds of a puncture group (viterbi.hpp:167-187)
+};
+
 __device__ __forceinline__ unsigned rol6(unsigned v, unsigned r) { r %= 6; return ((v << r) | (v >> (6 - r))) & 63u; }
 // Physical lane <-> label lane.  The butterfly partner of label lane v at phase ph is v ^ (32 >> ph); every XOR distance
 // except 4 is one cross-lane move (permlane swaps for 32/16, row_ror:8, quad_perm for 2/1).  Placing label lane v in
@@ -266,5 +282,195 @@ __device__ __noinline__ void viterbi_trace(unsigned U, const uint16_t* ring, uin
     if (lane < (cntA >> 3)) outA[m_lo + (int)lane] = (uint8_t)((loA >> 6) | ((upA & 0x3Fu) << 2));
     if (lane < (cntB >> 3)) outB[m_lo + (int)lane] = (uint8_t)((loB >> 6) | ((upB & 0x3Fu) << 2));
 }
+
+// ------------------------------------------------------------------------------------------------
+// The forward pass of a wave in the 64-lanes-per-pair layout: two frames (or two units of the window-parallel trellis, k_rx.hip) side by side.
+//
+// Soft input: the two frames a wave decodes (consecutive jobs of one code-rate list) each have their own packed stream (rx_types.h: three
+// bits per value, or a byte).  Per 12-step chunk, lane k < 32 fetches value k of frame A, lane 32 + k value k of frame B (one 16-bit load
+// each, two chunks ahead), shifts it into a 16-bit metric field and writes it to the wave's operand table in LDS; five or six broadcast
+// ds_read_b128 then give every lane the chunk's operands, dword i = field A | field B << 16 -- exactly what acs_step xors with the lane's
+// mask.  (Round 3 first kept such operand dwords in HBM -- 264 MB per call written and read, fetched through the scalar cache; round 2 a
+// 16-bit stream per frame that cost one s_pack per value.)  Past a frame's end its last value is repeated: its trellis half keeps stepping
+// on well-formed operands (a half fed garbage could carry twice into the guard bit within one block).
+//
+// Trace-back (TViterbiCore::Traceback, viterbicore.h:468-555) runs in the same wave, out of LDS, whenever the window
+// schedule of T11aViterbi<..,256,24>::Process (viterbi.hpp:196-214) fires: the ring holds, per 8-column block j
+// (columns 8j+1..8j+8) and per state at column 8j+8, the 8 decisions of the survivor path into that state (bit i =
+// column 8j+1+i).  One lookup walks 8 columns: the decisions are the decoded bits, and the state at column 8j is the 6
+// oldest decisions, newest in bit 0 (s' = d << 5 | s >> 1 applied 8 times).  Decoded bit i of the frame is the
+// decision at column i + 7 on the traced path (6-bit decoder delay), so output byte m is (block m >> 6) | (block m+1
+// & 0x3F) << 2.
+// WIN / LOOK: the window schedule of T11aViterbi<.., N_INPUT, TRELLIS_DEPTH = WIN, TRELLIS_LOOKAHEAD = LOOK> -- 256 / 24 in the 802.11a graph
+// (fb11ademod_config.hpp:199), 192 / 36 in the 802.11n graph (fb11ndemod_config.hpp:199); a walk touches at most (WIN + LOOK + 7) / 8 + 2 <= 38 blocks.
+struct VitSide {             // one of the wave's two frames (wave-uniform)
+    uint8_t* out; uint32_t nsteps, tr_end; bool done;                           // where its bytes go, its steps, its last trace-back, nothing left to decode
+    uint32_t soft_off, last, i0;                                                // its stream, the stream's last value, the value of its first step
+};
+
+// A wave that decodes whole frames has no event but its windows and its frames' ends.  (A schedule says what else ends a run of rows that need no look at it --
+// next_event(t): t, or its own next event if that comes first -- and what happens there: at_event(E) in front of the trace-back decision, window_done(E) behind a window.)
+struct WholeFrames {
+    __device__ __forceinline__ uint32_t next_event(uint32_t t) const { return t; }
+    template <typename E> __device__ __forceinline__ void at_event(E&) {}
+    template <typename E> __device__ __forceinline__ void window_done(E&) {}
+};
+
+template <int CR, int WIN, int LOOK, int BITS>
+struct VitForward {
+    using RG = RingGeom<WIN, LOOK>;
+    static constexpr int P = RG::P, GB = Puncture<CR>::GB, GS = Puncture<CR>::GS, CW = Puncture<CR>::CW;
+    struct Chunk { uint32_t v[(CW + 3) / 4 * 4]; };
+
+    VitLane V;
+    VitSide A, B;
+    uint32_t nsteps;                                                            // of the longer side
+    uint32_t tr, ob;                                                            // steps taken / where the next window's bits begin (same schedule for both sides)
+    uint32_t next_thr;
+    SoftCursor<BITS, CW> cur;
+    const uint8_t* soft_base;
+    uint16_t *ops, *my_op;
+
+    // start: the metric of every state but state 0 (both halves); ob0: the first window's first bit, in steps
+    __device__ __forceinline__ void init(const VitSide& A_, const VitSide& B_, unsigned start, uint32_t ob0, const uint8_t* __restrict__ soft_base_, uint16_t* ring, uint16_t* ops_)
+    {
+        const unsigned lane = threadIdx.x & 63;
+        A = A_; B = B_;
+        nsteps = max(A.nsteps, B.nsteps);
+        // this lane's part in fetching a chunk: value (lane & 31) of frame lane >> 5 (a side that is done before it starts does not exist: both halves fetch A's)
+        const VitSide& M = lane >= 32u && !B.done ? B : A;
+        const uint32_t my_k = lane & 31u;
+
+        const unsigned vl = lane_map(lane);                                     // label lane: holds state rol6^t(vl) after t steps
+        V.U = vl == 0 ? 0u : start;
+        V.ring = ring; V.rowpos = 0;
+        V.sidx[0] = __brev(rol6(vl, 2)) >> 26; V.sidx[1] = __brev(rol6(vl, 4)) >> 26; V.sidx[2] = __brev(vl) >> 26;   // rev6 of the state: (8j + 8) mod 6 = 2, 4, 0
+#pragma unroll
+        for (int t = 0; t < 24; t++) {
+            const int ph = t % 6, k = t % 8;
+            const unsigned n = rol6(vl, ph + 1);                                // state held after a phase-ph step
+            const bool own1 = ph >= 2 && ((vl >> (5 - ph)) & 1);                // DPP phases: the lane's own metric is the decision-1 candidate
+            const unsigned ma = (__popc(n & 0155) & 1) ? 7u * kFld : 0u, mb = (__popc(n & 0117) & 1) ? 7u * kFld : 0u;
+            const unsigned mx = Puncture<CR>::which_of(ph) == 2 ? mb : ma;
+            V.MX[t] = own1 ? ((mx ^ (7u * kFld)) | (kOne << k)) : mx;
+            if (t < 6) V.MY[t] = own1 ? (mb ^ (7u * kFld)) : mb;
+        }
+        tr = 0; ob = ob0;
+        cur.init(M.soft_off, my_k + M.i0, M.last);
+        soft_base = soft_base_; ops = ops_;
+        my_op = ops + 2u * my_k + (lane >> 5);                                  // operand k, frame's half (k up to 31: the table has 32 operands, those past CW are never read)
+    }
+    __device__ __forceinline__ bool going() const { return tr < nsteps && !(A.done && B.done); }
+
+    // Normalize (viterbicore.h:444-465), both frames; marks and guard are clear here and no half borrows (its minimum is subtracted): one 32-bit VOP2
+    __device__ __forceinline__ void normalize() { V.U = V.U - dpp_pkmin_wave(V.U); }
+    __device__ __forceinline__ SoftRaw fetch(uint32_t c) const { return cur.fetch(soft_base, c); }
+    __device__ __forceinline__ Chunk unpack(const SoftRaw& R)
+    {
+        *my_op = (uint16_t)cur.field(R);
+        lds_fence();
+        Chunk K;
+#pragma unroll
+        for (int i = 0; i < (CW + 3) / 4; i++) {
+            const uint4 x = reinterpret_cast<const uint4*>(ops)[i];
+            K.v[4 * i] = x.x; K.v[4 * i + 1] = x.y; K.v[4 * i + 2] = x.z; K.v[4 * i + 3] = x.w;
+        }
+        lds_fence();
+        return K;
+    }
+    // one puncture group = GS steps; i0 = step index inside the 12-step chunk, h = which half of the 24-step row
+    __device__ __forceinline__ void group(const Chunk& K, int h, int i0)
+    {
+        const int k0 = i0 / GS * GB, t24 = 12 * h + i0;
+        acs_step<0, P>(V, t24, K.v[k0], K.v[k0 + 1]);                           // ACS(A,B)
+        if (CR != 0) acs_step<1, P>(V, t24 + 1, K.v[k0 + 2], 0);                // ACS(A)     2/3, 3/4 (viterbi.hpp:173-187)
+        if (CR == 2) acs_step<2, P>(V, t24 + 2, 0, K.v[k0 + 3]);                // ACS(B)     3/4
+        if ((t24 + GS) % 8 == 0) normalize();                                   // (trellis index & 7) == 0 after a group
+    }
+    __device__ __forceinline__ void end_row() { V.rowpos = V.rowpos + 3 * 64 == (unsigned)P * 64 ? 0u : V.rowpos + 3 * 64; }   // P is a multiple of 3: the wrap falls between rows
+    __device__ __forceinline__ void fast_chunk(const Chunk& K, int h)           // 12 steps, no trace-back due inside: straight-line code
+    {
+#pragma unroll
+        for (int g = 0; g < 12 / GS; g++) group(K, h, g * GS);
+        tr += 12;
+    }
+
+    template <typename SCHED> __device__ __forceinline__ uint32_t next_event(const SCHED& sched) const
+    {
+        uint32_t t = ob + (uint32_t)(WIN + LOOK + 6);
+        if (!A.done) t = min(t, A.tr_end);
+        if (!B.done) t = min(t, B.tr_end);
+        return sched.next_event(t);
+    }
+    template <typename SCHED> __device__ __forceinline__ void check(SCHED& sched, int t24_last)   // trace-back schedule (viterbi.hpp:196-214), per frame
+    {
+        if (tr >= next_thr) {
+            sched.at_event(*this);
+            const int k = t24_last % 8;                                         // the last decision: mark k of the field, or bit 7 of the block just banked
+            const uint32_t pos = V.rowpos + (uint32_t)(t24_last / 8) * 64u;     // ring position (x 64) of block (tr - 1) >> 3
+            unsigned lastA, lastB;
+            if (k == 7) { const unsigned w = V.ring[pos + V.sidx[t24_last / 8]]; lastA = (w >> 7) & 1u; lastB = (w >> 15) & 1u; }
+            else { lastA = (V.U >> k) & 1u; lastB = (V.U >> (17 + k)) & 1u; }
+            const unsigned mA = ((V.U & 0xFFFFu) >> 9 << 1) | lastA, mB = (V.U >> 25 << 1) | lastB;
+            const bool partial = tr >= ob + (uint32_t)(WIN + LOOK + 6);
+            uint32_t cntA = 0, cntB = 0;
+            if (!A.done) {
+                if (tr >= A.tr_end) { cntA = A.tr_end - ob - 6; A.done = true; }
+                else if (partial) cntA = WIN;
+            }
+            if (!B.done) {
+                if (tr >= B.tr_end) { cntB = B.tr_end - ob - 6; B.done = true; }
+                else if (partial) cntB = WIN;
+            }
+            if (cntA | cntB) viterbi_trace<RG::kMaxWalk>(V.U, V.ring, tr, ob, mA, mB, cntA, cntB, A.out, B.out, (pos >> 6) + (uint32_t)P);
+            if (partial) { ob += WIN; sched.window_done(*this); }
+            next_thr = next_event(sched);
+        }
+    }
+    template <typename SCHED> __device__ __forceinline__ void slow_chunk(SCHED& sched, const Chunk& K, int h)   // up to 12 steps with the schedule examined after every group
+    {
+#pragma unroll
+        for (int g = 0; g < 12 / GS; g++) {
+            if (going()) {
+                group(K, h, g * GS);
+                tr += GS;
+                check(sched, 12 * h + g * GS + GS - 1);
+            }
+        }
+    }
+    template <typename SCHED> __device__ __forceinline__ void chunk(SCHED& sched, const Chunk& K, int h)   // tr % 24 == 12 h on entry
+    {
+        if (tr + 12 <= nsteps && next_thr > tr + 12) fast_chunk(K, h); else slow_chunk(sched, K, h);
+    }
+
+    // From the first soft value to the end of both sides.
+    template <typename SCHED> __device__ __forceinline__ void run(SCHED& sched)
+    {
+        next_thr = next_event(sched);
+        // Vector loads return in order: chunk c + 2 is requested before chunk c is stepped through (the compiler's vmcnt waits follow from that).
+        uint32_t c = 0;
+        SoftRaw r0 = fetch(0), r1 = fetch(1);
+        while (going()) {
+            // rows (2 chunks) that certainly need no look at the schedule: run them back to back, 9 rows out of 10
+            const uint32_t lim = min(nsteps, next_thr - 1);
+            for (uint32_t rows = lim > tr ? (lim - tr) / 24 : 0; rows > 0; rows--) {
+                const Chunk K0 = unpack(r0); r0 = fetch(c + 2);
+                fast_chunk(K0, 0);
+                const Chunk K1 = unpack(r1); r1 = fetch(c + 3);
+                fast_chunk(K1, 1);
+                c += 2;
+                end_row();
+            }
+            if (!(tr < nsteps)) break;
+            const Chunk K0 = unpack(r0); r0 = fetch(c + 2);
+            chunk(sched, K0, 0);
+            if (!going()) break;
+            const Chunk K1 = unpack(r1); r1 = fetch(c + 3);
+            chunk(sched, K1, 1);
+            c += 2;
+            end_row();
+        }
+    }
+};
 
 }  // namespace sora

@@ -1,6 +1,7 @@
 // dev_vitwin.h -- the window-parallel trellis's device code (the description is at the top of k_vitwin.hip): a unit's geometry, the forward pass of a wave's eight
-// units, and the wave's body.  Shared by k_viterbi16w (k_vitwin.hip: one wave per workgroup, launched behind the symbol kernels) and k_pipe (k_rx.hip: the same wave
-// inside the single-launch chain for a handful of frames, where it first waits until the soft values it needs have been published).
+// units (Forward16 of dev_vit16.h under a unit's schedule), and the wave's body.  Shared by k_viterbi16w (k_vitwin.hip: one wave per workgroup, launched behind the
+// symbol kernels) and k_pipe (k_rx.hip: the same wave inside the single-launch chain for a handful of frames, where it first waits until the soft values it needs
+// have been published).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -10,8 +11,6 @@
 namespace sora {
 
 namespace {
-
-constexpr uint32_t kNever = 0xFFFFFFFFu;
 
 // what a lane knows about one of the two units of its row
 struct UnitGeom {
@@ -35,7 +34,7 @@ struct UnitGeom {
 template <int CR, int WIN, int LOOK>
 __device__ __forceinline__ UnitGeom unit_of(const VitJob& J, uint32_t idx, uint32_t uu, uint32_t m, uint32_t nun, uint32_t q, uint32_t vbase, uint8_t* __restrict__ out)
 {
-    constexpr uint32_t GB = CR == 0 ? 2 : CR == 2 ? 4 : 3, GS = CR == 0 ? 1 : CR == 2 ? 3 : 2;
+    constexpr uint32_t GB = Puncture<CR>::GB, GS = Puncture<CR>::GS;
     UnitGeom g;
     const bool has = uu != kWinNone;
     const uint32_t u = has ? uu : 0u;
@@ -88,180 +87,88 @@ __device__ __forceinline__ UnitGeom unit_geom_direct(JOBS job_at, uint32_t idx, 
     return unit_of<CR, WIN, LOOK>(J, idx, exists && u < nun ? u : kWinNone, m, nun, q, vbase, out);
 }
 
-// (ready(): called once, behind the wave's set-up and in front of its first soft value: false = give up)
+// The unit form of the forward pass: each half of a row is a unit of its own, with its own place in its frame (my_ob), its two verification vectors and an end after
+// its windows.  (ready(): called once, behind the wave's set-up and in front of its first soft value: false = give up)
 template <int CR, int WIN, int LOOK, int BITS, typename READY>
 __device__ __forceinline__ void forward16w(Lds16<WIN, LOOK>& S, const uint8_t* __restrict__ soft, const UnitGeom& GA, const UnitGeom& GB_, uint16_t* __restrict__ vecs, READY ready)
 {
-    using G = Geom16<WIN, LOOK>;
-    constexpr int P = G::P;
-    constexpr int GB = CR == 0 ? 2 : CR == 2 ? 4 : 3;                           // soft values per puncture group
-    constexpr int GS = CR == 0 ? 1 : CR == 2 ? 3 : 2;                           // trellis steps per group
-    constexpr int CW = 12 / GS * GB;                                            // operands per 12-step chunk: 24 / 18 / 16
+    using F16 = Forward16<CR, WIN, LOOK, BITS>;
+    using Raw = typename F16::Raw;
     constexpr uint32_t THR = WIN + LOOK + 6;
-    const unsigned lane = threadIdx.x & 63, row = lane >> 4, l16 = lane & 15, half = lane & 1u;
-    const unsigned v0 = v_of_lane(l16);
-    const UnitGeom& Mine = half ? GB_ : GA;
-    const uint32_t nsteps = wave_max_u32(max(GA.nsteps, GB_.nsteps));
-    const uint32_t my_last = Mine.last;
-
-    auto which_of = [](int ph) { return CR == 0 ? 0 : CR == 1 ? (ph & 1) : ph % 3; };
-    Vit16 V;
+    const unsigned l16 = threadIdx.x & 15;
+    const UnitGeom& Mine = (threadIdx.x & 1u) ? GB_ : GA;
+    F16 F;
     // the frame's first unit starts from ALL_INIT0 / ALL_INIT (viterbilut.h:22-30), every other one from all-equal metrics; each half of the registers is a unit of its own
-    {
-        const unsigned ia = GA.first ? 0x18u << 9 : 0u, ib = GB_.first ? 0x18u << 25 : 0u;
-#pragma unroll
-        for (int i = 0; i < 4; i++) V.U[i] = (v0 ^ kW[i]) == 0 ? 0u : (ia | ib);
-    }
-    const unsigned ring_base = (unsigned)(uintptr_t)&S.ring[0][0][0];
-#pragma unroll
-    for (int jb = 0; jb < 3; jb++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) V.sadr[jb][i] = ring_base + ((row * 64u + rev6u(rol6(v0 ^ kW[i], jb == 0 ? 2 : jb == 1 ? 4 : 0))) << 1);
-#pragma unroll
-    for (int t = 0; t < 24; t++) {
-        const int ph = t % 6, k = t % 8;
-        const unsigned n = rol6(v0, ph + 1);
-        const bool vb = (v0 >> (5 - ph)) & 1u;
-        const unsigned ma = (__popc(n & 0155) & 1) ? 7u * kFld : 0u, mb = (__popc(n & 0117) & 1) ? 7u * kFld : 0u;
-        const unsigned mx = which_of(ph) == 2 ? mb : ma;
-        V.MX[t] = vb ? ((mx ^ (7u * kFld)) | (kOne << k)) : mx;
-        if (t < 6) V.MY[t] = vb ? (mb ^ (7u * kFld)) : mb;
-    }
+    F.init(S, soft, Mine.soft_off, Mine.i0, Mine.last, (GA.first ? 0x18u << 9 : 0u) | (GB_.first ? 0x18u << 25 : 0u), wave_max_u32(max(GA.nsteps, GB_.nsteps)));
 
-    uint32_t tr = 0;                                                            // steps taken, in every unit's own count (wave-uniform)
-    uint32_t pos = 0;
+    // (F.tr: steps taken, in every unit's own count)
     uint32_t my_ob = Mine.ob, my_wleft = Mine.wleft;
     const uint32_t my_tr_end = Mine.tr_end;
     bool my_done = !Mine.valid;
     uint32_t vstepA = GA.vstep, vstepB = GB_.vstep, estepA = GA.estep, estepB = GB_.estep;   // (row-uniform: every lane holds a coset of BOTH units' metrics)
 
-    auto normalize = [&]() {
-        const unsigned m = row_pkmin(pk_min16(pk_min16(V.U[0], V.U[1]), pk_min16(V.U[2], V.U[3])));
-#pragma unroll
-        for (int i = 0; i < 4; i++) V.U[i] -= m;
-    };
-    auto pos_of = [&](uint32_t p, int jb) -> uint32_t { const uint32_t q = p + (uint32_t)jb; return q >= (uint32_t)P ? q - (uint32_t)P : q; };
     auto trace = [&](uint32_t my_cnt, int t24_last) {
-        trace16<WIN, LOOK, true>((unsigned)(uintptr_t)&S, V.U[0], V.U[1], V.U[2], V.U[3], tr, my_ob, pos_of(pos, t24_last / 8), (uint32_t)(t24_last % 8), my_cnt, Mine.out);
+        trace16<WIN, LOOK, true>((unsigned)(uintptr_t)&S, F.V.U[0], F.V.U[1], F.V.U[2], F.V.U[3], F.tr, my_ob, F16::pos_of(F.pos, t24_last / 8), (uint32_t)(t24_last % 8), my_cnt,
+                                 Mine.out);
     };
     auto next_event = [&]() -> uint32_t {
         uint32_t mine = my_done ? kNever : min(my_ob + THR, my_tr_end);
         mine = min(min(mine, min(vstepA, vstepB)), min(estepA, estepB));
         return wave_min_u32(mine);
     };
-    uint32_t next_thr = next_event();
-    bool all_done = wave_min_u32(my_done ? 1u : 0u) != 0u;
+    F.next_thr = next_event();
+    F.all_done = wave_min_u32(my_done ? 1u : 0u) != 0u;
     // a vector: register i of row-lane l16 at [16 i + l16], the unit's half of the register -- the same order at both ends of a comparison (both are taken at a
     // multiple of 24 of the unit's own steps, where the state <-> lane map is the identity)
     auto save = [&](uint32_t vec, int which, bool hi) {
         uint16_t* d = vecs + ((size_t)vec * 2u + (uint32_t)which) * 64u + l16;
 #pragma unroll
-        for (int i = 0; i < 4; i++) d[16 * i] = (uint16_t)(hi ? V.U[i] >> 16 : V.U[i]);
+        for (int i = 0; i < 4; i++) d[16 * i] = (uint16_t)(hi ? F.V.U[i] >> 16 : F.V.U[i]);
     };
     auto check = [&](int t24_last) {
-        if (tr >= next_thr) {
+        if (F.tr >= F.next_thr) {
             // verification vectors: due only at multiples of 24 steps, i.e. straight after a normalisation, marks and carry guard cleared
-            if (tr == vstepA) { save(GA.vec, 0, false); vstepA = kNever; }
-            if (tr == vstepB) { save(GB_.vec, 0, true); vstepB = kNever; }
-            if (tr == estepA) { save(GA.vec, 1, false); estepA = kNever; }
-            if (tr == estepB) { save(GB_.vec, 1, true); estepB = kNever; }
+            if (F.tr == vstepA) { save(GA.vec, 0, false); vstepA = kNever; }
+            if (F.tr == vstepB) { save(GB_.vec, 0, true); vstepB = kNever; }
+            if (F.tr == estepA) { save(GA.vec, 1, false); estepA = kNever; }
+            if (F.tr == estepB) { save(GB_.vec, 1, true); estepB = kNever; }
             // trace-back schedule (viterbi.hpp:196-214), per unit
             uint32_t cnt = 0; bool partial = false;
             if (!my_done) {
-                if (tr >= my_tr_end) { cnt = my_tr_end - my_ob - 6; my_done = true; }
-                else if (tr >= my_ob + THR) { cnt = WIN; partial = true; }
+                if (F.tr >= my_tr_end) { cnt = my_tr_end - my_ob - 6; my_done = true; }
+                else if (F.tr >= my_ob + THR) { cnt = WIN; partial = true; }
             }
             if (wave_max_u32(cnt) != 0u) trace(cnt, t24_last);
             if (partial) { my_ob += WIN; if (--my_wleft == 0) my_done = true; }
-            next_thr = next_event();
-            all_done = wave_min_u32(my_done ? 1u : 0u) != 0u;
+            F.next_thr = next_event();
+            F.all_done = wave_min_u32(my_done ? 1u : 0u) != 0u;
         }
     };
-
-    struct Chunk { uint32_t v[CW]; };
-    constexpr int NV = (CW + 7) / 8;
-    struct Raw { SoftRaw r[NV]; };
-    const uint32_t my_j = l16 >> 1;
-    SoftCursor<BITS, CW> cur[NV];
-#pragma unroll
-    for (int v = 0; v < NV; v++) cur[v].init(Mine.soft_off, Mine.i0 + my_j + 8u * v, my_last);
-    auto fetch = [&](uint32_t c) -> Raw {
-        Raw R;
-#pragma unroll
-        for (int v = 0; v < NV; v++) R.r[v] = cur[v].fetch(soft, c);
-        return R;
-    };
-    uint16_t* my_ops = &S.ops[row][my_j][half];
-    const uint4* row_ops = reinterpret_cast<const uint4*>(&S.ops[row][0][0]);
-    auto unpack = [&](const Raw& R) -> Chunk {
-#pragma unroll
-        for (int v = 0; v < NV; v++) my_ops[16 * v] = (uint16_t)cur[v].field(R.r[v]);
-        lds_fence();
-        Chunk K;
-#pragma unroll
-        for (int i = 0; i < (CW + 3) / 4; i++) {
-            const uint4 x = row_ops[i];
-            K.v[4 * i] = x.x; K.v[4 * i + 1] = x.y;
-            if (4 * i + 2 < CW) { K.v[4 * i + 2] = x.z; K.v[4 * i + 3] = x.w; }
-        }
-        lds_fence();
-        return K;
-    };
-    unsigned pos512[3];
-    auto set_row_pos = [&]() {
-#pragma unroll
-        for (int jb = 0; jb < 3; jb++) pos512[jb] = pos_of(pos, jb) * 512u;
-    };
-    auto end_row = [&]() { pos = pos_of(pos, 3); set_row_pos(); };
-    set_row_pos();
-    auto group = [&](const Chunk& K, int h, int i0) {
-        const int k0 = i0 / GS * GB, t24 = 12 * h + i0;
-        acs16<0, P>(V, t24, K.v[k0], K.v[k0 + 1], pos512);
-        if (CR != 0) acs16<1, P>(V, t24 + 1, K.v[k0 + 2], 0, pos512);
-        if (CR == 2) acs16<2, P>(V, t24 + 2, 0, K.v[k0 + 3], pos512);
-        if ((t24 + GS) % 8 == 0) normalize();
-    };
-    auto fast_chunk = [&](const Chunk& K, int h) {
-#pragma unroll
-        for (int g = 0; g < 12 / GS; g++) group(K, h, g * GS);
-        tr += 12;
-    };
-    auto slow_chunk = [&](const Chunk& K, int h) {
-#pragma unroll
-        for (int g = 0; g < 12 / GS; g++) {
-            if (tr < nsteps && !all_done) {
-                group(K, h, g * GS);
-                tr += GS;
-                check(12 * h + g * GS + GS - 1);
-            }
-        }
-    };
-    auto chunk = [&](const Chunk& K, int h) { if (tr + 12 <= nsteps && next_thr > tr + 12) fast_chunk(K, h); else slow_chunk(K, h); };
 
     // A unit is a few hundred to a few thousand steps: the plain loop of k_viterbi16 (operands unpacked at the head of every chunk), without its
     // two-table hand-over -- half the code, and what that hand-over buys (2 % for a wave alone on its SIMD) a unit gives back many times over.
     uint32_t c = 0;
     if (!ready()) return;
-    Raw b0 = fetch(0), b1 = fetch(1), b2, b3;
-    while (tr < nsteps && !all_done) {
-        const uint32_t lim = min(nsteps, next_thr - 1);
-        uint32_t rows = lim > tr ? (lim - tr) / 24 : 0;                         // rows that certainly need no look at the schedule
+    Raw b0 = F.fetch(0), b1 = F.fetch(1), b2, b3;
+    while (F.going()) {
+        const uint32_t lim = min(F.nsteps, F.next_thr - 1);
+        uint32_t rows = lim > F.tr ? (lim - F.tr) / 24 : 0;                     // rows that certainly need no look at the schedule
         for (; rows > 0; rows--) {
-            b2 = fetch(c + 2);
-            fast_chunk(unpack(b0), 0);
-            b3 = fetch(c + 3);
-            fast_chunk(unpack(b1), 1);
-            end_row();
+            b2 = F.fetch(c + 2);
+            F.fast_chunk(F.unpack(b0), 0);
+            b3 = F.fetch(c + 3);
+            F.fast_chunk(F.unpack(b1), 1);
+            F.end_row();
             b0 = b2; b1 = b3;
             c += 2;
         }
-        if (!(tr < nsteps)) break;
-        b2 = fetch(c + 2);
-        chunk(unpack(b0), 0);
-        if (!(tr < nsteps && !all_done)) break;
-        b3 = fetch(c + 3);
-        chunk(unpack(b1), 1);
-        end_row();
+        if (!(F.tr < F.nsteps)) break;
+        b2 = F.fetch(c + 2);
+        F.chunk(F.unpack(b0), 0, check);
+        if (!F.going()) break;
+        b3 = F.fetch(c + 3);
+        F.chunk(F.unpack(b1), 1, check);
+        F.end_row();
         b0 = b2; b1 = b3;
         c += 2;
     }
@@ -274,7 +181,6 @@ __device__ __forceinline__ void viterbi16w_wave(Lds16<WIN, LOOK>& S, uint32_t wa
         uint32_t target, uint32_t vstride,
                                                 const uint8_t* __restrict__ soft, uint8_t* __restrict__ out, uint16_t* __restrict__ vecs)
 {
-    auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     const uint32_t n[3] = { hdr[0], hdr[1], hdr[2] };
     const uint32_t q = uni(win_units_per_frame(n[0] + n[1] + n[2], target));
     uint32_t w = uni(wave_index), list = 0;

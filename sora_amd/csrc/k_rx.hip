@@ -862,18 +862,21 @@ __device__ __forceinline__ bool pipe_units_ready(const RxArgs& A, const PipeArgs
 }
 
 // ---- role 3: a wave of the window-parallel trellis
+// job_at(idx) of a code-rate list inside k_pipe: the VitJob of the frame at place idx, worked out from the frame table
+__device__ __forceinline__ auto pipe_jobs_of(const RxArgs& A, uint32_t list)
+{
+    const uint32_t* jl = A.joblist + (size_t)list * A.nrows; const FrameRow* fr = A.frames;
+    return [jl, fr](uint32_t idx) {
+        const FrameRow& r = fr[jl[idx]];
+        VitJob J;
+        J.valid = 1; J.soft_off = r.slot0 * (uint32_t)kSoftBytesPerSlot; J.nsoft = (uint32_t)r.nsym * 48u * r.nbpsc; J.length = r.length;
+        J.dec_off = 0; J.out_off = r.slot0 * (uint32_t)kOutPerSlot; J.code_rate = r.code_rate; J.soft_bits = 3;
+        return J;
+    };
+}
 __device__ __forceinline__ void pipe_trellis_wave(const RxArgs& A, const PipeArgs& P, uint32_t wave_index, Lds16<256, 24>& S)
 {
-    auto jobs_of = [&](uint32_t list) {
-        const uint32_t* jl = A.joblist + (size_t)list * A.nrows; const FrameRow* fr = A.frames;
-        return [jl, fr](uint32_t idx) {
-            const FrameRow& r = fr[jl[idx]];
-            VitJob J;
-            J.valid = 1; J.soft_off = r.slot0 * (uint32_t)kSoftBytesPerSlot; J.nsoft = (uint32_t)r.nsym * 48u * r.nbpsc; J.length = r.length;
-            J.dec_off = 0; J.out_off = r.slot0 * (uint32_t)kOutPerSlot; J.code_rate = r.code_rate; J.soft_bits = 3;
-            return J;
-        };
-    };
+    auto jobs_of = [&](uint32_t list) { return pipe_jobs_of(A, list); };
     auto ready = [&](const UnitGeom& GA, const UnitGeom& GB_, uint32_t list) -> bool {
         const unsigned lane = threadIdx.x & 63;
         return pipe_units_ready(A, P, list, (lane & 1u) ? GB_ : GA, (lane & 15u) < 2u, wave_index);      // one lane per unit polls
@@ -884,337 +887,71 @@ __device__ __forceinline__ void pipe_trellis_wave(const RxArgs& A, const PipeArg
 
 // (k_pipe's 64-lane trellis role and the kernel itself follow viterbi_forward_unit below)
 
-// (the trellis machinery -- metric representation, ACS step, trace-back -- lives in dev_viterbi.h)
-struct VitSide {            // wave-uniform per-frame bookkeeping
-    uint8_t* out; uint32_t nsteps, tr_end; bool done;
-};
-
-// Soft input: the two frames a wave decodes (consecutive jobs of one code-rate list) each have their own packed stream (rx_types.h: three
-// bits per value, or a byte).  Per 12-step chunk, lane k < 32 fetches value k of frame A, lane 32 + k value k of frame B (one 16-bit load
-// each, two chunks ahead), shifts it into a 16-bit metric field and writes it to the wave's operand table in LDS; five or six broadcast
-// ds_read_b128 then give every lane the chunk's operands, dword i = field A | field B << 16 -- exactly what acs_step xors with the lane's
-// mask.  (Round 3 first kept such operand dwords in HBM -- 264 MB per call written and read, fetched through the scalar cache; round 2 a
-// 16-bit stream per frame that cost one s_pack per value.)  Past a frame's end its last value is repeated: its trellis half keeps stepping
-// on well-formed operands (a half fed garbage could carry twice into the guard bit within one block).
-//
-// Trace-back (TViterbiCore::Traceback, viterbicore.h:468-555) runs in the same wave, out of LDS, whenever the window
-// schedule of T11aViterbi<..,256,24>::Process (viterbi.hpp:196-214) fires: the ring holds, per 8-column block j
-// (columns 8j+1..8j+8) and per state at column 8j+8, the 8 decisions of the survivor path into that state (bit i =
-// column 8j+1+i).  One lookup walks 8 columns: the decisions are the decoded bits, and the state at column 8j is the 6
-// oldest decisions, newest in bit 0 (s' = d << 5 | s >> 1 applied 8 times).  Decoded bit i of the frame is the
-// decision at column i + 7 on the traced path (6-bit decoder delay), so output byte m is (block m >> 6) | (block m+1
-// & 0x3F) << 2.
-// WIN / LOOK: the window schedule of T11aViterbi<.., N_INPUT, TRELLIS_DEPTH = WIN, TRELLIS_LOOKAHEAD = LOOK> -- 256 / 24 in the 802.11a graph
-// (fb11ademod_config.hpp:199), 192 / 36 in the 802.11n graph (fb11ndemod_config.hpp:199); a walk touches at most (WIN + LOOK + 7) / 8 + 2 <= 38 blocks.
+// (the trellis machinery -- metric representation, ACS step, trace-back, and the forward pass VitForward with its soft input and LDS -- lives in dev_viterbi.h)
+// A wave decoding two whole frames (JB: any job when !hasB): start at ALL_INIT0 / ALL_INIT, first window at the frame's first bit, no event but the windows' own.
 template <int CR, int WIN, int LOOK, int BITS>
 __device__ __forceinline__ void viterbi_forward(const VitJob& JA, const VitJob& JB, bool hasB, const uint8_t* __restrict__ soft_base,
         uint8_t* __restrict__ out_base, uint16_t* ring, uint16_t* ops)
 {
-    using RG = RingGeom<WIN, LOOK>;
-    constexpr int P = RG::P;
-    constexpr int GB = CR == 0 ? 2 : CR == 2 ? 4 : 3;                           // soft values per puncture group (CR: 0=1/2, 1=2/3, 2=3/4)
-    constexpr int GS = CR == 0 ? 1 : CR == 2 ? 3 : 2;                           // trellis steps per group
-    constexpr int CW = 12 / GS * GB;                                            // operands (dwords) per 12-step chunk: 24 / 18 / 16
-    const unsigned lane = threadIdx.x & 63;
-    VitSide A, B;
-    A.out = out_base + JA.out_off; A.nsteps = JA.nsoft / GB * GS; A.tr_end = JA.length * 8u + 16u + 6u; A.done = false;
-    B.out = out_base + JB.out_off; B.nsteps = hasB ? JB.nsoft / GB * GS : 0u; B.tr_end = hasB ? JB.length * 8u + 16u + 6u : 0u; B.done = !hasB;
-    const uint32_t nsteps = max(A.nsteps, B.nsteps);
-    // this lane's part in fetching a chunk: value (lane & 31) of frame lane >> 5
-    const bool mineB = lane >= 32u && hasB;
-    const uint32_t my_soft_off = mineB ? JB.soft_off : JA.soft_off;
-    const uint32_t my_last = max(mineB ? JB.nsoft : JA.nsoft, 1u) - 1u, my_k = lane & 31u;
-
-    auto which_of = [](int ph) { return CR == 0 ? 0 : CR == 1 ? (ph & 1) : ph % 3; };   // step kinds of a puncture group (viterbi.hpp:167-187)
-    VitLane V;
-    const unsigned vl = lane_map(lane);                                         // label lane: holds state rol6^t(vl) after t steps
-    V.U = vl == 0 ? 0u : 0x18u * kFld;                                         // ALL_INIT0 / ALL_INIT = 0x00 / 0x30 (viterbilut.h:22-30)
-    V.ring = ring; V.rowpos = 0;
-    V.sidx[0] = __brev(rol6(vl, 2)) >> 26; V.sidx[1] = __brev(rol6(vl, 4)) >> 26; V.sidx[2] = __brev(vl) >> 26;   // rev6 of the state: (8j + 8) mod 6 = 2, 4, 0
-#pragma unroll
-    for (int t = 0; t < 24; t++) {
-        const int ph = t % 6, k = t % 8;
-        const unsigned n = rol6(vl, ph + 1);                                    // state held after a phase-ph step
-        const bool own1 = ph >= 2 && ((vl >> (5 - ph)) & 1);                    // DPP phases: the lane's own metric is the decision-1 candidate
-        const unsigned ma = (__popc(n & 0155) & 1) ? 7u * kFld : 0u, mb = (__popc(n & 0117) & 1) ? 7u * kFld : 0u;
-        const unsigned mx = which_of(ph) == 2 ? mb : ma;
-        V.MX[t] = own1 ? ((mx ^ (7u * kFld)) | (kOne << k)) : mx;
-        if (t < 6) V.MY[t] = own1 ? (mb ^ (7u * kFld)) : mb;
-    }
-
-    uint32_t tr = 0, ob = 0;                                                    // ob: bits handed out by the partial windows (same schedule for both frames)
-
-    // Normalize (viterbicore.h:444-465), both frames; marks and guard are clear here and no half borrows (its minimum is subtracted): one 32-bit VOP2
-    auto normalize = [&]() { V.U = V.U - dpp_pkmin_wave(V.U); };
-    auto trace = [&](unsigned mA, unsigned mB, uint32_t cntA, uint32_t cntB, uint32_t top) { viterbi_trace<RG::kMaxWalk>(V.U, ring, tr, ob, mA, mB, cntA, cntB,
-            A.out, B.out, top); };
-    auto next_event = [&]() -> uint32_t {
-        uint32_t t = ob + (uint32_t)(WIN + LOOK + 6);
-        if (!A.done) t = min(t, A.tr_end);
-        if (!B.done) t = min(t, B.tr_end);
-        return t;
+    auto side = [&](const VitJob& J, bool has) {
+        VitSide s;
+        s.out = out_base + J.out_off; s.nsteps = has ? J.nsoft / Puncture<CR>::GB * Puncture<CR>::GS : 0u; s.tr_end = has ? J.length * 8u + 16u + 6u : 0u; s.done = !has;
+        s.soft_off = J.soft_off; s.last = max(J.nsoft, 1u) - 1u; s.i0 = 0;
+        return s;
     };
-    uint32_t next_thr = next_event();
-    auto check = [&](int t24_last) {                                            // trace-back schedule (viterbi.hpp:196-214), per frame
-        if (tr >= next_thr) {
-            const int k = t24_last % 8;                                         // the last decision: mark k of the field, or bit 7 of the block just banked
-            const uint32_t pos = V.rowpos + (uint32_t)(t24_last / 8) * 64u;     // ring position (x 64) of block (tr - 1) >> 3
-            unsigned lastA, lastB;
-            if (k == 7) { const unsigned w = ring[pos + V.sidx[t24_last / 8]]; lastA = (w >> 7) & 1u; lastB = (w >> 15) & 1u; }
-            else { lastA = (V.U >> k) & 1u; lastB = (V.U >> (17 + k)) & 1u; }
-            const unsigned mA = ((V.U & 0xFFFFu) >> 9 << 1) | lastA, mB = (V.U >> 25 << 1) | lastB;
-            const bool partial = tr >= ob + (uint32_t)(WIN + LOOK + 6);
-            uint32_t cntA = 0, cntB = 0;
-            if (!A.done) {
-                if (tr >= A.tr_end) { cntA = A.tr_end - ob - 6; A.done = true; }
-                else if (partial) cntA = WIN;
-            }
-            if (!B.done) {
-                if (tr >= B.tr_end) { cntB = B.tr_end - ob - 6; B.done = true; }
-                else if (partial) cntB = WIN;
-            }
-            if (cntA | cntB) trace(mA, mB, cntA, cntB, (pos >> 6) + (uint32_t)P);
-            if (partial) ob += WIN;
-            next_thr = next_event();
-        }
-    };
-    struct Chunk { uint32_t v[(CW + 3) / 4 * 4]; };
-    SoftCursor<BITS, CW> cur;
-    cur.init(my_soft_off, my_k, my_last);
-    auto fetch = [&](uint32_t c) -> SoftRaw { return cur.fetch(soft_base, c); };
-    // operand k, frame's half (k up to 31: the table has 32 operands, those past CW are never read)
-    uint16_t* my_op = ops + 2u * my_k + (lane >> 5);
-    auto lds_order = []() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
-    auto unpack = [&](const SoftRaw& R) -> Chunk {
-        *my_op = (uint16_t)cur.field(R);
-        lds_order();
-        Chunk K;
-#pragma unroll
-        for (int i = 0; i < (CW + 3) / 4; i++) {
-            const uint4 x = reinterpret_cast<const uint4*>(ops)[i];
-            K.v[4 * i] = x.x; K.v[4 * i + 1] = x.y; K.v[4 * i + 2] = x.z; K.v[4 * i + 3] = x.w;
-        }
-        lds_order();
-        return K;
-    };
-    auto op = [](const Chunk& K, int i) -> uint32_t { return K.v[i]; };
-    // one puncture group = GS steps; i0 = step index inside the 12-step chunk, h = which half of the 24-step row
-    auto group = [&](const Chunk& K, int h, int i0) {
-        const int k0 = i0 / GS * GB, t24 = 12 * h + i0;
-        acs_step<0, P>(V, t24, op(K, k0), op(K, k0 + 1));                       // ACS(A,B)
-        if (CR != 0) acs_step<1, P>(V, t24 + 1, op(K, k0 + 2), 0);              // ACS(A)     2/3, 3/4 (viterbi.hpp:173-187)
-        if (CR == 2) acs_step<2, P>(V, t24 + 2, 0, op(K, k0 + 3));              // ACS(B)     3/4
-        if ((t24 + GS) % 8 == 0) normalize();                                   // (trellis index & 7) == 0 after a group
-    };
-    auto end_row = [&]() { V.rowpos = V.rowpos + 3 * 64 == (unsigned)P * 64 ? 0u : V.rowpos + 3 * 64; };   // P is a multiple of 3: the wrap falls between rows
-    auto fast_chunk = [&](const Chunk& K, int h) {                              // 12 steps, no trace-back due inside: straight-line code
-#pragma unroll
-        for (int g = 0; g < 12 / GS; g++) group(K, h, g * GS);
-        tr += 12;
-    };
-    auto slow_chunk = [&](const Chunk& K, int h) {                              // up to 12 steps with the schedule examined after every group
-#pragma unroll
-        for (int g = 0; g < 12 / GS; g++) {
-            if (tr < nsteps && !(A.done && B.done)) {
-                group(K, h, g * GS);
-                tr += GS;
-                check(12 * h + g * GS + GS - 1);
-            }
-        }
-    };
-    auto chunk = [&](const Chunk& K, int h) {                                   // tr % 24 == 12 h on entry
-        if (tr + 12 <= nsteps && next_thr > tr + 12) fast_chunk(K, h); else slow_chunk(K, h);
-    };
-
-    // Vector loads return in order: chunk c + 2 is requested before chunk c is stepped through (the compiler's vmcnt waits follow from that).
-    uint32_t c = 0;
-    SoftRaw r0 = fetch(0), r1 = fetch(1);
-    while (tr < nsteps && !(A.done && B.done)) {
-        // rows (2 chunks) that certainly need no look at the schedule: run them back to back, 9 rows out of 10
-        const uint32_t lim = min(nsteps, next_thr - 1);
-        for (uint32_t rows = lim > tr ? (lim - tr) / 24 : 0; rows > 0; rows--) {
-            const Chunk K0 = unpack(r0); r0 = fetch(c + 2);
-            fast_chunk(K0, 0);
-            const Chunk K1 = unpack(r1); r1 = fetch(c + 3);
-            fast_chunk(K1, 1);
-            c += 2;
-            end_row();
-        }
-        if (!(tr < nsteps)) break;
-        const Chunk K0 = unpack(r0); r0 = fetch(c + 2);
-        chunk(K0, 0);
-        if (!(tr < nsteps && !(A.done && B.done))) break;
-        const Chunk K1 = unpack(r1); r1 = fetch(c + 3);
-        chunk(K1, 1);
-        c += 2;
-        end_row();
-    }
+    VitForward<CR, WIN, LOOK, BITS> F;
+    F.init(side(JA, true), side(JB, hasB), 0x18u * kFld, 0, soft_base, ring, ops);   // ALL_INIT0 / ALL_INIT = 0x00 / 0x30 (viterbilut.h:22-30)
+    WholeFrames sched;
+    F.run(sched);
 }
 
 // The same wave decoding one UNIT of the window-parallel trellis per half instead of a whole frame (dev_vitwin.h; k_pipe's 64-lane form for a lone capture: a unit is
 // 33 ns per step here against 50 in the sixteen-lane layout, and the launch's last unit is what the capture waits for).  GA / GB_ are unit `u` of two frames of one
 // code-rate list (or GB_ invalid): the same unit index, hence the same distance ob between the unit's first step and its first window and ONE trace-back schedule for
 // the wave, as in the whole-frame form.  What a unit adds: all-equal metrics at its start (the frame's first unit starts like the frame), its stream read from its
-// first step on, its metric vector stored at its verify point and at the next unit's, and an end after its windows.  ready(): see forward16w.
+// first step on, its metric vector stored at its verify point and at the next unit's, and an end after its windows.
+struct UnitSchedule64 {
+    uint16_t* __restrict__ vecs;
+    uint32_t vecA, vecB;
+    uint32_t wA, wB, vstepA, vstepB, estepA, estepB;
+    __device__ __forceinline__ uint32_t next_event(uint32_t t) const { return min(min(t, min(vstepA, vstepB)), min(estepA, estepB)); }
+    // a vector: the lane's 16-bit field of the unit's half -- taken at a multiple of 24 of the unit's own steps: straight after a normalisation, marks and guard clear,
+    // the state <-> lane map the identity (the same at both ends of a comparison)
+    __device__ __forceinline__ void save(unsigned U, uint32_t vec, int which, bool hi) const
+    {
+        vecs[((size_t)vec * 2u + (uint32_t)which) * 64u + (threadIdx.x & 63)] = (uint16_t)(hi ? U >> 16 : U);
+    }
+    template <typename E> __device__ __forceinline__ void at_event(E& F)
+    {
+        if (F.tr == vstepA) { save(F.V.U, vecA, 0, false); vstepA = kNever; }
+        if (F.tr == vstepB) { save(F.V.U, vecB, 0, true); vstepB = kNever; }
+        if (F.tr == estepA) { save(F.V.U, vecA, 1, false); estepA = kNever; }
+        if (F.tr == estepB) { save(F.V.U, vecB, 1, true); estepB = kNever; }
+    }
+    template <typename E> __device__ __forceinline__ void window_done(E& F)    // a unit ends behind its last window (the frame's last unit: at the frame's end)
+    {
+        if (!F.A.done && --wA == 0) F.A.done = true;
+        if (!F.B.done && --wB == 0) F.B.done = true;
+    }
+};
+// (ready(): called once, behind the wave's set-up and in front of its first soft value: false = give up)
 template <int CR, int WIN, int LOOK, int BITS, typename READY>
 __device__ __forceinline__ void viterbi_forward_unit(const UnitGeom& GA, const UnitGeom& GB_, const uint8_t* __restrict__ soft_base, uint16_t* ring, uint16_t* ops,
         uint16_t* __restrict__ vecs, READY ready)
 {
     const bool hasB = GB_.valid;
-    using RG = RingGeom<WIN, LOOK>;
-    constexpr int P = RG::P;
-    constexpr int GB = CR == 0 ? 2 : CR == 2 ? 4 : 3;                           // soft values per puncture group (CR: 0=1/2, 1=2/3, 2=3/4)
-    constexpr int GS = CR == 0 ? 1 : CR == 2 ? 3 : 2;                           // trellis steps per group
-    constexpr int CW = 12 / GS * GB;                                            // operands (dwords) per 12-step chunk: 24 / 18 / 16
-    const unsigned lane = threadIdx.x & 63;
-    VitSide A, B;
-    A.out = GA.out; A.nsteps = GA.nsteps; A.tr_end = GA.tr_end; A.done = false;
-    B.out = GB_.out; B.nsteps = hasB ? GB_.nsteps : 0u; B.tr_end = hasB ? GB_.tr_end : 0u; B.done = !hasB;
-    const uint32_t nsteps = max(A.nsteps, B.nsteps);
-    // this lane's part in fetching a chunk: value (lane & 31) of frame lane >> 5
-    const bool mineB = lane >= 32u && hasB;
-    const uint32_t my_soft_off = mineB ? GB_.soft_off : GA.soft_off;
-    const uint32_t my_last = mineB ? GB_.last : GA.last, my_k = lane & 31u;
-    const uint32_t my_first = my_k + (mineB ? GB_.i0 : GA.i0);                 // (the unit's first value: a whole number of puncture groups into the stream)
-
-    auto which_of = [](int ph) { return CR == 0 ? 0 : CR == 1 ? (ph & 1) : ph % 3; };   // step kinds of a puncture group (viterbi.hpp:167-187)
-    VitLane V;
-    const unsigned vl = lane_map(lane);                                         // label lane: holds state rol6^t(vl) after t steps
-    V.U = vl == 0 ? 0u : ((GA.first ? 0x18u << 9 : 0u) | ((hasB && GB_.first) ? 0x18u << 25 : 0u));   // a frame's first unit: ALL_INIT0 / ALL_INIT (viterbilut.h:22-30); any other: all equal
-    V.ring = ring; V.rowpos = 0;
-    V.sidx[0] = __brev(rol6(vl, 2)) >> 26; V.sidx[1] = __brev(rol6(vl, 4)) >> 26; V.sidx[2] = __brev(vl) >> 26;   // rev6 of the state: (8j + 8) mod 6 = 2, 4, 0
-#pragma unroll
-    for (int t = 0; t < 24; t++) {
-        const int ph = t % 6, k = t % 8;
-        const unsigned n = rol6(vl, ph + 1);                                    // state held after a phase-ph step
-        const bool own1 = ph >= 2 && ((vl >> (5 - ph)) & 1);                    // DPP phases: the lane's own metric is the decision-1 candidate
-        const unsigned ma = (__popc(n & 0155) & 1) ? 7u * kFld : 0u, mb = (__popc(n & 0117) & 1) ? 7u * kFld : 0u;
-        const unsigned mx = which_of(ph) == 2 ? mb : ma;
-        V.MX[t] = own1 ? ((mx ^ (7u * kFld)) | (kOne << k)) : mx;
-        if (t < 6) V.MY[t] = own1 ? (mb ^ (7u * kFld)) : mb;
-    }
-
-    uint32_t tr = 0, ob = GA.ob;                                                // steps taken / where the next window's bits begin, both in the units' own step count (the same for both)
-    uint32_t wA = GA.wleft, wB = GB_.wleft;
-    uint32_t vstepA = GA.vstep, vstepB = hasB ? GB_.vstep : kNever, estepA = GA.estep, estepB = hasB ? GB_.estep : kNever;
-    // a vector: the lane's 16-bit field of the unit's half -- taken at a multiple of 24 of the unit's own steps: straight after a normalisation, marks and guard clear,
-    // the state <-> lane map the identity (the same at both ends of a comparison)
-    auto save = [&](uint32_t vec, int which, bool hi) { vecs[((size_t)vec * 2u + (uint32_t)which) * 64u + lane] = (uint16_t)(hi ? V.U >> 16 : V.U); };
-
-    // Normalize (viterbicore.h:444-465), both frames; marks and guard are clear here and no half borrows (its minimum is subtracted): one 32-bit VOP2
-    auto normalize = [&]() { V.U = V.U - dpp_pkmin_wave(V.U); };
-    auto trace = [&](unsigned mA, unsigned mB, uint32_t cntA, uint32_t cntB, uint32_t top) { viterbi_trace<RG::kMaxWalk>(V.U, ring, tr, ob, mA, mB, cntA, cntB,
-            A.out, B.out, top); };
-    auto next_event = [&]() -> uint32_t {
-        uint32_t t = ob + (uint32_t)(WIN + LOOK + 6);
-        if (!A.done) t = min(t, A.tr_end);
-        if (!B.done) t = min(t, B.tr_end);
-        return min(min(t, min(vstepA, vstepB)), min(estepA, estepB));
+    auto side = [](const UnitGeom& G, bool has) {
+        VitSide s;
+        s.out = G.out; s.nsteps = has ? G.nsteps : 0u; s.tr_end = has ? G.tr_end : 0u; s.done = !has;
+        s.soft_off = G.soft_off; s.last = G.last; s.i0 = G.i0;                  // (the unit's first value: a whole number of puncture groups into the stream)
+        return s;
     };
-    uint32_t next_thr = next_event();
-    auto check = [&](int t24_last) {                                            // trace-back schedule (viterbi.hpp:196-214), per frame
-        if (tr >= next_thr) {
-            if (tr == vstepA) { save(GA.vec, 0, false); vstepA = kNever; }
-            if (tr == vstepB) { save(GB_.vec, 0, true); vstepB = kNever; }
-            if (tr == estepA) { save(GA.vec, 1, false); estepA = kNever; }
-            if (tr == estepB) { save(GB_.vec, 1, true); estepB = kNever; }
-            const int k = t24_last % 8;                                         // the last decision: mark k of the field, or bit 7 of the block just banked
-            const uint32_t pos = V.rowpos + (uint32_t)(t24_last / 8) * 64u;     // ring position (x 64) of block (tr - 1) >> 3
-            unsigned lastA, lastB;
-            if (k == 7) { const unsigned w = ring[pos + V.sidx[t24_last / 8]]; lastA = (w >> 7) & 1u; lastB = (w >> 15) & 1u; }
-            else { lastA = (V.U >> k) & 1u; lastB = (V.U >> (17 + k)) & 1u; }
-            const unsigned mA = ((V.U & 0xFFFFu) >> 9 << 1) | lastA, mB = (V.U >> 25 << 1) | lastB;
-            const bool partial = tr >= ob + (uint32_t)(WIN + LOOK + 6);
-            uint32_t cntA = 0, cntB = 0;
-            if (!A.done) {
-                if (tr >= A.tr_end) { cntA = A.tr_end - ob - 6; A.done = true; }
-                else if (partial) cntA = WIN;
-            }
-            if (!B.done) {
-                if (tr >= B.tr_end) { cntB = B.tr_end - ob - 6; B.done = true; }
-                else if (partial) cntB = WIN;
-            }
-            if (cntA | cntB) trace(mA, mB, cntA, cntB, (pos >> 6) + (uint32_t)P);
-            if (partial) {                                                      // a unit ends behind its last window (the frame's last unit: at the frame's end)
-                ob += WIN;
-                if (!A.done && --wA == 0) A.done = true;
-                if (!B.done && --wB == 0) B.done = true;
-            }
-            next_thr = next_event();
-        }
-    };
-    struct Chunk { uint32_t v[(CW + 3) / 4 * 4]; };
-    SoftCursor<BITS, CW> cur;
-    cur.init(my_soft_off, my_first, my_last);
-    auto fetch = [&](uint32_t c) -> SoftRaw { return cur.fetch(soft_base, c); };
-    // operand k, frame's half (k up to 31: the table has 32 operands, those past CW are never read)
-    uint16_t* my_op = ops + 2u * my_k + (lane >> 5);
-    auto lds_order = []() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
-    auto unpack = [&](const SoftRaw& R) -> Chunk {
-        *my_op = (uint16_t)cur.field(R);
-        lds_order();
-        Chunk K;
-#pragma unroll
-        for (int i = 0; i < (CW + 3) / 4; i++) {
-            const uint4 x = reinterpret_cast<const uint4*>(ops)[i];
-            K.v[4 * i] = x.x; K.v[4 * i + 1] = x.y; K.v[4 * i + 2] = x.z; K.v[4 * i + 3] = x.w;
-        }
-        lds_order();
-        return K;
-    };
-    auto op = [](const Chunk& K, int i) -> uint32_t { return K.v[i]; };
-    // one puncture group = GS steps; i0 = step index inside the 12-step chunk, h = which half of the 24-step row
-    auto group = [&](const Chunk& K, int h, int i0) {
-        const int k0 = i0 / GS * GB, t24 = 12 * h + i0;
-        acs_step<0, P>(V, t24, op(K, k0), op(K, k0 + 1));                       // ACS(A,B)
-        if (CR != 0) acs_step<1, P>(V, t24 + 1, op(K, k0 + 2), 0);              // ACS(A)     2/3, 3/4 (viterbi.hpp:173-187)
-        if (CR == 2) acs_step<2, P>(V, t24 + 2, 0, op(K, k0 + 3));              // ACS(B)     3/4
-        if ((t24 + GS) % 8 == 0) normalize();                                   // (trellis index & 7) == 0 after a group
-    };
-    auto end_row = [&]() { V.rowpos = V.rowpos + 3 * 64 == (unsigned)P * 64 ? 0u : V.rowpos + 3 * 64; };   // P is a multiple of 3: the wrap falls between rows
-    auto fast_chunk = [&](const Chunk& K, int h) {                              // 12 steps, no trace-back due inside: straight-line code
-#pragma unroll
-        for (int g = 0; g < 12 / GS; g++) group(K, h, g * GS);
-        tr += 12;
-    };
-    auto slow_chunk = [&](const Chunk& K, int h) {                              // up to 12 steps with the schedule examined after every group
-#pragma unroll
-        for (int g = 0; g < 12 / GS; g++) {
-            if (tr < nsteps && !(A.done && B.done)) {
-                group(K, h, g * GS);
-                tr += GS;
-                check(12 * h + g * GS + GS - 1);
-            }
-        }
-    };
-    auto chunk = [&](const Chunk& K, int h) {                                   // tr % 24 == 12 h on entry
-        if (tr + 12 <= nsteps && next_thr > tr + 12) fast_chunk(K, h); else slow_chunk(K, h);
-    };
-
-    // Vector loads return in order: chunk c + 2 is requested before chunk c is stepped through (the compiler's vmcnt waits follow from that).
-    uint32_t c = 0;
+    VitForward<CR, WIN, LOOK, BITS> F;
+    // a frame's first unit: ALL_INIT0 / ALL_INIT (viterbilut.h:22-30); any other: all equal.  ob: in the units' own step count (the same for both)
+    F.init(side(GA, true), side(GB_, hasB), (GA.first ? 0x18u << 9 : 0u) | ((hasB && GB_.first) ? 0x18u << 25 : 0u), GA.ob, soft_base, ring, ops);
+    UnitSchedule64 sched{ vecs, GA.vec, GB_.vec, GA.wleft, GB_.wleft, GA.vstep, hasB ? GB_.vstep : kNever, GA.estep, hasB ? GB_.estep : kNever };
     if (!ready()) return;
-    SoftRaw r0 = fetch(0), r1 = fetch(1);
-    while (tr < nsteps && !(A.done && B.done)) {
-        // rows (2 chunks) that certainly need no look at the schedule: run them back to back, 9 rows out of 10
-        const uint32_t lim = min(nsteps, next_thr - 1);
-        for (uint32_t rows = lim > tr ? (lim - tr) / 24 : 0; rows > 0; rows--) {
-            const Chunk K0 = unpack(r0); r0 = fetch(c + 2);
-            fast_chunk(K0, 0);
-            const Chunk K1 = unpack(r1); r1 = fetch(c + 3);
-            fast_chunk(K1, 1);
-            c += 2;
-            end_row();
-        }
-        if (!(tr < nsteps)) break;
-        const Chunk K0 = unpack(r0); r0 = fetch(c + 2);
-        chunk(K0, 0);
-        if (!(tr < nsteps && !(A.done && B.done))) break;
-        const Chunk K1 = unpack(r1); r1 = fetch(c + 3);
-        chunk(K1, 1);
-        c += 2;
-        end_row();
-    }
+    F.run(sched);
 }
 
 // ---- role 3, 64-lane form (P.lanes64: the handle's calls in flight are so few that two units per wave still fit the chip): wave w of a code-rate list of n frames holds
@@ -1223,21 +960,13 @@ struct PipeUnitLds { uint16_t ring[RingGeom<256, 24>::kEntries]; uint16_t ops[64
 static_assert(4 * sizeof(PipeUnitLds) <= kPipeLdsBytes, "k_pipe: four 64-lane trellis waves' LDS");
 __device__ __forceinline__ void pipe_trellis_wave64(const RxArgs& A, const PipeArgs& P, uint32_t wave_index, PipeUnitLds& L)
 {
-    auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     const uint32_t n[3] = { A.njobs[0], A.njobs[1], A.njobs[2] };
     const uint32_t q = uni(win_units_per_frame(n[0] + n[1] + n[2], P.target));
     uint32_t w = uni(wave_index), list = 0;
     while (list < 3 && w >= q * ((n[list] + 1u) / 2u)) { w -= q * ((n[list] + 1u) / 2u); list++; }
     if (list >= 3) return;
     const uint32_t nl = uni(n[list]), pairs = (nl + 1u) / 2u, u = w / pairs, ia = 2u * (w - u * pairs), ib = ia + 1u;
-    const uint32_t* jl = A.joblist + (size_t)list * A.nrows; const FrameRow* fr = A.frames;
-    auto job_at = [jl, fr](uint32_t idx) {
-        const FrameRow& r = fr[jl[idx]];
-        VitJob J;
-        J.valid = 1; J.soft_off = r.slot0 * (uint32_t)kSoftBytesPerSlot; J.nsoft = (uint32_t)r.nsym * 48u * r.nbpsc; J.length = r.length;
-        J.dec_off = 0; J.out_off = r.slot0 * (uint32_t)kOutPerSlot; J.code_rate = r.code_rate; J.soft_bits = 3;
-        return J;
-    };
+    const auto job_at = pipe_jobs_of(A, list);
     const uint32_t code_rate = uni(job_at(0).code_rate), vbase = list * P.vstride;
     auto run = [&](auto cr) {
         constexpr int CR = decltype(cr)::value;
@@ -1295,9 +1024,9 @@ __device__ __forceinline__ void viterbi_kernel_body(const VitJob* __restrict__ j
 {
     // 39 KB / 33 KB: survivor history, two copies of every block (RingGeom), per wave
     __shared__ uint16_t s_ring[4][RingGeom<WIN, LOOK>::kEntries];
-    // [wave][operand of the chunk][frame]: the soft values as metric fields (viterbi_forward); with it under 40 KB: four workgroups per CU
+    // [wave][operand of the chunk][frame]: the soft values as metric fields (VitForward::unpack); with it under 40 KB: four workgroups per CU
     __shared__ uint16_t s_ops[4][64];
-    auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };   // everything below is per-wave uniform: keep it in SGPRs
+    // everything below is per-wave uniform: keep it in SGPRs (uni)
     // wave -> (code-rate list, pair): list r has ceil(n_r / 2) pairs (njobs3 == nullptr: one list of njobs_single jobs)
     uint32_t n[3] = { njobs_single, 0, 0 };
     if (njobs3) { n[0] = njobs3[0]; n[1] = njobs3[1]; n[2] = njobs3[2]; }
