@@ -269,14 +269,14 @@ __global__ void __launch_bounds__(256) k_ht40_finish(Ht40FinishArgs A)
 // tables on the host: one host wait per call).  One block: per capture the number of recorded frames, their soft bytes and their number per
 // code rate; five exclusive prefix sums over the captures; then every capture writes its frames' descriptors, the two decoder jobs of each
 // (neighbours in their code-rate list: one wave decodes both streams), the finish jobs and the rows' templates, in (capture, time) order.
-__device__ __forceinline__ uint32_t ht40_ndbps_dev(uint32_t nb, uint32_t cr) { return 108u * nb * (cr == 0 ? 1u : cr == 1 ? 2u : 3u) / (cr == 0 ? 2u : cr == 1 ? 3u : 4u); }
+__host__ __device__ __forceinline__ uint32_t ht40_ndbps(uint32_t nb, uint32_t cr) { return 108u * nb * (cr == 0 ? 1u : cr == 1 ? 2u : 3u) / (cr == 0 ? 2u : cr == 1 ? 3u : 4u); }
 struct Ht40Geom { uint32_t nb, cr, nsym, per, per_pad; };
 __device__ __forceinline__ Ht40Geom ht40_geom(const Ht40Found& F)
 {
     Ht40Geom G;
     G.nb = F.mcs == 8 ? 1u : F.mcs <= 10 ? 2u : F.mcs <= 12 ? 4u : 6u;
     G.cr = (F.mcs == 10 || F.mcs == 12 || F.mcs == 14) ? 2u : F.mcs == 13 ? 1u : 0u;
-    const uint32_t nd = ht40_ndbps_dev(G.nb, G.cr);
+    const uint32_t nd = ht40_ndbps(G.nb, G.cr);
     G.nsym = (16u + 8u * F.ht_len + 6u + nd - 1u) / nd;                          // sora_ht40_symbols(len, len, nb, cr)
     G.per = G.nsym * 108u * G.nb; G.per_pad = (G.per + 31u) / 32u * 32u;
     return G;
@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
 }  // namespace sora
 
 // ------------------------------------------------------------------------------------------------ host side (C ABI, include/sora_hip.h)
-#include "host_calls.h"
+#include "host_trellis.h"
 using namespace sora;
 
 // A handle owns kHt40Slots independent slots (stream + every intermediate), used round-robin: a call waits only for the call that used its
@@ -411,9 +411,9 @@ struct sora_ht40 {
     int device = 0; uint32_t max_frames = 0; uint64_t max_soft = 0;
     Tables T{}; const uint32_t* sincos = nullptr; const short* atan = nullptr;
     Ht40Slot slot[kHt40Slots]; int next = 0, last = 0, seq = 0; bool have_results = false;
-    // trellis kernel: 1 = k_viterbi16_11n (default: the handle keeps eight calls in flight), 0 =
+    // trellis kernel (host_trellis.h): Lanes16 = k_viterbi16_11n (default: the handle keeps eight calls in flight), Lanes64 =
     // k_viterbi11n (64 lanes per stream pair; the faster one for a call alone) -- sora_ht40_set_trellis
-    int lanes16 = 1;
+    Trellis trellis = Trellis::Lanes16;
 };
 
 static constexpr uint32_t kVoutStride = 4352;
@@ -433,8 +433,6 @@ static void ht40_free(sora_ht40_t* rx)
     }
     delete rx;
 }
-
-static uint32_t ht40_ndbps(uint32_t nb, uint32_t cr) { return 108u * nb * (cr == 0 ? 1u : cr == 1 ? 2u : 3u) / (cr == 0 ? 2u : cr == 1 ? 3u : 4u); }
 
 uint32_t sora_ht40_symbols(uint32_t length0, uint32_t length1, uint32_t n_bpsc, uint32_t code_rate)
 {
@@ -481,8 +479,9 @@ void* sora_ht40_stream(sora_ht40_t* rx) { return rx ? (void*)rx->slot[rx->last].
 int sora_ht40_set_trellis(sora_ht40_t* rx, int lanes_per_pair)
 {
     if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_set_trellis: null handle", 0);
-    const int old = rx->lanes16 ? 16 : 64;
-    if (lanes_per_pair == 16 || lanes_per_pair == 64) rx->lanes16 = lanes_per_pair == 16;
+    const int old = trellis_abi(rx->trellis);
+    TrellisChoice c;
+    if (trellis_parse(lanes_per_pair, &c) && (c == Trellis::Lanes16 || c == Trellis::Lanes64)) rx->trellis = *c;
     else if (lanes_per_pair >= 0) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_set_trellis: 16 or 64 lanes per stream pair", 0);
     return old;
 }
@@ -493,7 +492,23 @@ int sora_ht40_synchronize(sora_ht40_t* rx)
     return calls_synchronize(rx->slot, kHt40Slots, rx->device);
 }
 
-// the data field of `nframes` described frames on slot S (its stream is idle): descriptors -> device, k_ht40_frame, the trellis kernel, k_ht40_finish
+// the data field's kernels on slot S: k_ht40_frame over at most nframes frames, the trellis kernel, k_ht40_finish.  plan: the device's own count of them (k_ht40_plan), else
+// nullptr: there are exactly nframes
+static int ht40_data_field(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0, const sora_complex16* d_iq1, uint32_t nframes, sora_complex16* d_weights, const uint32_t* plan)
+{
+    const uint32_t njobs = 2 * nframes;
+    Ht40Args A;
+    A.iq0 = reinterpret_cast<const uint32_t*>(d_iq0); A.iq1 = reinterpret_cast<const uint32_t*>(d_iq1); A.frames = S.d_frames; A.nframes = nframes;
+    A.T = rx->T; A.sincos = rx->sincos; A.atan = rx->atan; A.soft = S.d_soft; A.w_out = reinterpret_cast<uint32_t*>(d_weights); A.plan = plan;
+    hipLaunchKernelGGL(k_ht40_frame, dim3((nframes + 3) / 4), dim3(256), 0, S.stream, A);
+    trellis_launch<192>(rx->trellis, trellis_lists(S.d_jobs, S.d_njobs, njobs, 2 * rx->max_frames), S.d_soft, S.d_vout, S.stream);
+    Ht40FinishArgs Fi; Fi.jobs = S.d_fjobs; Fi.njobs = njobs; Fi.vout = S.d_vout; Fi.mpdu = S.d_mpdu; Fi.rows = S.d_rows; Fi.T = rx->T; Fi.plan = plan;
+    hipLaunchKernelGGL(k_ht40_finish, dim3((njobs + 3) / 4), dim3(256), 0, S.stream, Fi);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+// the data field of `nframes` described frames on slot S (its stream is idle): descriptors -> device, then the data field's kernels
 static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0, const sora_complex16* d_iq1, const sora_ht40_frame* frames, size_t nframes,
         sora_complex16* d_weights)
 {
@@ -537,21 +552,7 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
         if (nj[r]) HIPCHK(hipMemcpyAsync(S.d_jobs + r * stride, hj + r * stride, sizeof(VitJob) * nj[r], hipMemcpyHostToDevice, S.stream));
     HIPCHK(hipMemcpyAsync(S.d_njobs, nj_stage, 16, hipMemcpyHostToDevice, S.stream));
     HIPCHK(hipMemcpyAsync(S.d_fjobs, fj, sizeof(Ht40Job) * 2 * nframes, hipMemcpyHostToDevice, S.stream));
-    Ht40Args A;
-    A.iq0 = reinterpret_cast<const uint32_t*>(d_iq0); A.iq1 = reinterpret_cast<const uint32_t*>(d_iq1); A.frames = S.d_frames; A.nframes = (uint32_t)nframes;
-    A.T = rx->T; A.sincos = rx->sincos; A.atan = rx->atan; A.soft = S.d_soft; A.w_out = reinterpret_cast<uint32_t*>(d_weights); A.plan = nullptr;
-    hipLaunchKernelGGL(k_ht40_frame, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, S.stream, A);
-    const uint32_t njobs = 2 * (uint32_t)nframes;
-    if (rx->lanes16)
-        hipLaunchKernelGGL(k_viterbi16_11n, dim3((njobs + 7) / 8 + 2), dim3(64), 0, S.stream, (const VitJob*)S.d_jobs, (const uint32_t*)S.d_njobs, 0u,
-                (uint32_t)stride, (const uint8_t*)S.d_soft, S.d_vout);
-    else
-        hipLaunchKernelGGL(k_viterbi11n, dim3((njobs / 2 + 3 + 3) / 4), dim3(256), 0, S.stream, (const VitJob*)S.d_jobs, (const uint32_t*)S.d_njobs, 0u,
-                (uint32_t)stride, (const uint8_t*)S.d_soft, S.d_vout);
-    Ht40FinishArgs Fi; Fi.jobs = S.d_fjobs; Fi.njobs = njobs; Fi.vout = S.d_vout; Fi.mpdu = S.d_mpdu; Fi.rows = S.d_rows; Fi.T = rx->T; Fi.plan = nullptr;
-    hipLaunchKernelGGL(k_ht40_finish, dim3((njobs + 3) / 4), dim3(256), 0, S.stream, Fi);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
+    return ht40_data_field(rx, S, d_iq0, d_iq1, (uint32_t)nframes, d_weights, nullptr);
 }
 
 int sora_ht40_process_dev(sora_ht40_t* rx, const sora_complex16* d_iq0, const sora_complex16* d_iq1, const sora_ht40_frame* frames, size_t nframes, sora_complex16* d_weights)
@@ -625,21 +626,7 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     HIPCHK(hipMemcpyAsync(S.h_found, S.d_found, sizeof(Ht40Found) * nrows, hipMemcpyDeviceToHost, S.stream));
     HIPCHK(hipMemcpyAsync(S.h_plan, S.d_plan, 16, hipMemcpyDeviceToHost, S.stream));
     // the kernels are launched for the most frames there can be and stop at the planned count
-    const uint32_t bf = S.bound_frames, bj = 2 * bf;
-    Ht40Args A;
-    A.iq0 = reinterpret_cast<const uint32_t*>(d_iq0); A.iq1 = reinterpret_cast<const uint32_t*>(d_iq1); A.frames = S.d_frames; A.nframes = bf;
-    A.T = rx->T; A.sincos = rx->sincos; A.atan = rx->atan; A.soft = S.d_soft; A.w_out = nullptr; A.plan = S.d_plan;
-    hipLaunchKernelGGL(k_ht40_frame, dim3((bf + 3) / 4), dim3(256), 0, S.stream, A);
-    if (rx->lanes16)
-        hipLaunchKernelGGL(k_viterbi16_11n, dim3((bj + 7) / 8 + 2), dim3(64), 0, S.stream, (const VitJob*)S.d_jobs, (const uint32_t*)S.d_njobs, 0u,
-                (uint32_t)stride, (const uint8_t*)S.d_soft, S.d_vout);
-    else
-        hipLaunchKernelGGL(k_viterbi11n, dim3((bj / 2 + 3 + 3) / 4), dim3(256), 0, S.stream, (const VitJob*)S.d_jobs, (const uint32_t*)S.d_njobs, 0u,
-                (uint32_t)stride, (const uint8_t*)S.d_soft, S.d_vout);
-    Ht40FinishArgs Fi; Fi.jobs = S.d_fjobs; Fi.njobs = bj; Fi.vout = S.d_vout; Fi.mpdu = S.d_mpdu; Fi.rows = S.d_rows; Fi.T = rx->T; Fi.plan = S.d_plan;
-    hipLaunchKernelGGL(k_ht40_finish, dim3((bj + 3) / 4), dim3(256), 0, S.stream, Fi);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
+    return ht40_data_field(rx, S, d_iq0, d_iq1, S.bound_frames, nullptr, S.d_plan);
 }
 
 // a raw-capture call whose stream has been waited for: the front end's records (in page-locked memory by now) -> the call's events

@@ -16,8 +16,7 @@
 #include <vector>
 #include "../../include/sora_hip.h"
 #include "kernels.h"
-#include "host_calls.h"
-#include "dev_winplan.h"
+#include "host_trellis.h"
 
 using namespace sora;
 
@@ -416,7 +415,7 @@ struct RxPipe : Call {
     // ... the three symbol kernels' tables: slot owners, equalised bins (256 B per slot), rotation parameters
     uint32_t* d_slot_row = nullptr; uint32_t* d_eq = nullptr; TrackRec* d_track = nullptr; uint32_t* d_pil = nullptr;
     // symbol chain: 1 = k_frame (one wave per frame), 3 = k_sym_front -> k_track_lds -> k_sym_back (few frames in flight),
-    // 4 = k_pipe: those three AND the window-parallel trellis as one launch (a handful of frames; needs lanes16 == 2)
+    // 4 = k_pipe: those three AND the window-parallel trellis as one launch (a handful of frames; needs the windowed trellis)
     int  front = 1;
     uint32_t* d_pflags = nullptr; uint32_t pflag_words = 0;     // ... k_pipe's hand-off words (kernels.h PipeArgs), zeroed for every call
     // sora_rx_bind_mpdu: this call's MPDUs go straight to the host's array (last_bound: what the last enqueue / recorded graph carries)
@@ -427,11 +426,9 @@ struct RxPipe : Call {
     // (the pipeline's calls alternate between two sets of counters, words 0-3 and 8-11 of the 64-byte block in front of the frame table) -- no fill kernel in front of a call
     // unless counters_ready says that nothing has: the first call, a call recorded into a hipGraph (its arguments are frozen: it always uses set 0 behind its own fill)
     uint32_t parity = 0; bool counters_ready = false;
-    // trellis kernel of the split path: 0 = k_viterbi (64 lanes per frame pair), 1 = k_viterbi16 (16 lanes per pair, k_vit16.hip),
-    // 2 = k_viterbi16w + k_win_redo (the proof, and the serial decode of what fails it) (window-parallel, k_vitwin.hip)
-    int  lanes16 = 0;
-    // ... its verification vectors (per code-rate list: wstride units), the frames to decode again, its record
-    uint16_t* d_wvecs = nullptr; unsigned long long* d_wstats = nullptr; uint32_t wstride = 0;
+    // trellis kernel of the split path (host_trellis.h), and the window-parallel one's scratch (on its first use)
+    Trellis trellis = Trellis::Lanes64;
+    WinScratch win;
     // sora_rx_set_ordered: this call's trellis kernel starts behind the previous call's (wait_for = that call's ev_trellis), so that calls in flight COMPLETE in the order they were
     // submitted -- the front kernels (latency chains) of a call still run beside the trellis of the one before it, and its delivery beside the trellis of the one after it
     hipEvent_t ev_trellis = nullptr, wait_for = nullptr; bool ordered = false;
@@ -463,14 +460,6 @@ struct RxPipe : Call {
     unsigned only = 0xF;         // tool hook (sora_internal_rx_only): which kernels of the chain a call launches (1 scan, 2 frame, 4 trellis, 8 finish)
 };
 
-// waves a call may need on top of its units' eight per wave: a code-rate list of ONE frame is laid out with gaps (dev_winplan.h)
-constexpr uint32_t kWinLoneWaves = 3 * sora::kWinLonePad / 8;
-// units a call of the window-parallel trellis is cut into at least, frames permitting: one round of the chip's 2048 eight-unit trellis slots
-constexpr uint32_t kWinUnitsTarget = 16384;
-// the window-parallel trellis of a call of `rows` frame rows: the units it is cut into at most (a frame has at most 80 windows) ...
-static uint64_t win_units(uint64_t rows) { return std::min<uint64_t>(std::max<uint64_t>(kWinUnitsTarget, rows), 80ull * rows); }
-// ... and its waves: eight units each, + a partly filled one per code-rate list + the lone layout's gaps
-static uint64_t win_waves(uint64_t rows) { return (win_units(rows) + 7) / 8 + 3 + kWinLoneWaves; }
 // Probe hooks (which kernels of the chain a call launches, empty launches appended to a call, the calls' kernel boundaries on one time base, the device arrays between the
 // kernels) exist in the TOOLS variant of the library only -- sora_amd.build.build_variant("tools", ["SORA_TOOLS"]), loaded by the scripts under tools/ through SORA_HIP_LIB.
 // The product build has neither the entry points nor the branches they steer.
@@ -519,8 +508,9 @@ static void rx_free(RxPipe* rx)
     if (!rx) return;
     void* ptrs[] = { rx->d_caps, rx->d_fctx, rx->d_nframes,
                      rx->d_soft, rx->d_jobs, rx->d_vout, rx->d_mpdu, rx->d_iq_own, rx->d_rows, rx->d_nrows, rx->d_njobs, rx->d_joblist, rx->d_dump, rx->d_slot_row, rx->d_eq, rx->d_track, rx->d_pil,
-                     rx->d_wvecs, rx->d_wstats, rx->d_pflags };
+                     rx->d_pflags };
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    rx->win.free();
     for (auto& e : rx->ev) if (e) (void)hipEventDestroy(e);
     if (rx->ev_trellis) (void)hipEventDestroy(rx->ev_trellis);
     if (rx->graph_exec) (void)hipGraphExecDestroy(rx->graph_exec);
@@ -712,16 +702,12 @@ static int pipe_process_dev(RxPipe* rx, const sora_complex16* d_iq, const sora_c
         HIPCHK(hipMalloc((void**)&rx->d_soft, (size_t)kSoftBytesPerSlot * rx->cap_slots + kSoftSlack));   // three bits per soft value (rx_types.h)
         HIPCHK(hipMalloc((void**)&rx->d_jobs, 3 * sizeof(VitJob) * rx->cap_rows));
     }
-    if (rx->lanes16 == 2 && !rx->d_wvecs) {                                      // the window-parallel trellis's arrays, on its first use
-        // (a call is cut into at most max(target, rows) units and a frame into at most 80: a single-capture handle needs 80 vectors per row, not the target's 16384)
-        rx->wstride = (uint32_t)win_units(rx->cap_rows) + rx->cap_rows;
-        HIPCHK(hipMalloc((void**)&rx->d_wvecs, 3 * (size_t)kWinVecBytes * rx->wstride));
-        HIPCHK(hipMalloc((void**)&rx->d_wstats, (4 * kWinStatBanks + 1) * sizeof(unsigned long long)));   // (+ 1: calls whose data field k_win_redo_finish_pipe made again)
-        HIPCHK(hipMemset(rx->d_wstats, 0, (4 * kWinStatBanks + 1) * sizeof(unsigned long long)));
-    }
+    const bool windowed = rx->trellis == Trellis::Windowed;
+    // the window-parallel trellis's arrays, on its first use (... and the count of calls whose data field k_win_redo_finish_pipe made again)
+    if (windowed) { const int rc = rx->win.ensure(rx->cap_rows, nullptr, true); if (rc) return rc; }
     const bool split = rx->front >= 3;
     // (the handle only asks for k_pipe where its workgroups are all resident at once: pipe_fits)
-    const bool pipe = split && rx->front == 4 && rx->lanes16 == 2;
+    const bool pipe = split && rx->front == 4 && windowed;
     if (pipe && !rx->d_pflags) {
         rx->pflag_words = (4u + 4u * rx->cap_rows + (rx->cap_slots + 63u) / 64u + 4u + 3u) / 4u * 4u;
         HIPCHK(hipMalloc((void**)&rx->d_pflags, 4 * ((size_t)rx->pflag_words + 1024)));   // (+ the tools variant's time stamps)
@@ -749,8 +735,6 @@ static int pipe_process_dev(RxPipe* rx, const sora_complex16* d_iq, const sora_c
         caps_changed = true;
     }
     const uint32_t nrows = rx->ncaps * rx->cfg.max_frames_per_capture;
-    // workgroups of the kernels that take PAIRS of frames (four per workgroup: at most ceil(n / 2) + 2 pairs over the three code-rate lists), of the window-parallel trellis
-    const uint32_t pair_groups = (nrows / 2 + 3 + 3) / 4, win_groups = (uint32_t)win_waves(nrows);
 
     auto enqueue = [&](bool recording) -> int {                                  // the kernel chain of one call, in stream order (recording: into a hipGraph)
 #ifdef SORA_TOOLS
@@ -795,27 +779,25 @@ static int pipe_process_dev(RxPipe* rx, const sora_complex16* d_iq, const sora_c
         R.pipe_flags = pipe ? rx->d_pflags : nullptr;
         // behind the window-parallel trellis the proof, the decode of what fails it and T11aDesc / the frame sink are ONE launch: the wave that holds a pair of frames
         // finishes them
-        const bool redo_finish = rx->lanes16 == 2 && RX_ONLY(rx, 4u) && RX_ONLY(rx, 8u);
-        // the proof of the window-parallel trellis and the serial decode of the pairs of frames that fail it (none, normally: its waves check and return)
-        auto win_redo = [&]() {
-            hipLaunchKernelGGL(k_win_redo, dim3(pair_groups), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, nrows, kWinUnitsTarget, rx->wstride,
-                               (const uint16_t*)rx->d_wvecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wstats);
-        };
+        const bool redo_finish = windowed && RX_ONLY(rx, 4u) && RX_ONLY(rx, 8u);
+        // the call's job table: three code-rate lists of nrows jobs behind this call's counters
+        const TrellisJobs J = trellis_lists(rx->d_jobs, counters, nrows, nrows);
+        const uint32_t pair_groups = trellis_pair_groups(J);
 
         // the symbol chain
         if (pipe) {
             // a handful of frames: the symbol chain AND the window-parallel trellis as one launch (k_rx.hip: k_pipe), the proof behind it
             if (RX_ONLY(rx, 2u)) {
                 PipeArgs P{};
-                P.nfront = (slots + 63) / 64; P.ntrack = nrows; P.flags = rx->d_pflags; P.target = kWinUnitsTarget; P.vstride = rx->wstride;
-                P.vecs = rx->d_wvecs; P.stamp_base = rx->pflag_words;
+                P.nfront = (slots + 63) / 64; P.ntrack = nrows; P.flags = rx->d_pflags; P.target = kWinUnitsTarget; P.vstride = rx->win.stride;
+                P.vecs = rx->win.d_vecs; P.stamp_base = rx->pflag_words;
                 P.lanes64 = rx->pipe64 ? 1u : 0u; P.wait_ticks = rx->pipe_wait_ticks;
                 // trellis waves: those of k_viterbi16w, or -- 64-lane form -- unit u of two frames each
-                const uint32_t waves = rx->pipe64 ? kWinMaxUnits * ((nrows + 3) / 2) : win_groups;
+                const uint32_t waves = rx->pipe64 ? kWinMaxUnits * ((nrows + 3) / 2) : trellis_win_waves(J);
                 hipLaunchKernelGGL(k_pipe, dim3(P.nfront + P.ntrack + (waves + 3) / 4), dim3(256), 0, st, R, P);
             }
             mark();
-            if (RX_ONLY(rx, 4u) && !redo_finish) win_redo();
+            if (RX_ONLY(rx, 4u) && !redo_finish) trellis_proof<256>(J, rx->d_soft, rx->d_vout, rx->win, st);
         } else if (split) {
             // The symbol chain as three kernels (k_rx.hip): per symbol slot in front of and behind the tracker, per frame (four lanes each) for the tracker, whose tables
             // are in LDS: the chain for FEW frames in flight, where k_frame's one wave per frame is a 465-symbol serial loop (fsample-6).
@@ -830,30 +812,19 @@ static int pipe_process_dev(RxPipe* rx, const sora_complex16* d_iq, const sora_c
         // the trellis (k_pipe holds it itself)
         if (!pipe) {
             if (rx->wait_for && !recording) (void)hipStreamWaitEvent(st, rx->wait_for, 0);   // (sora_rx_set_ordered: behind the previous call's trellis)
-            if (!RX_ONLY(rx, 4u)) {}
-            else if (rx->lanes16 == 2) {
-                // window-parallel: the call's units (at most target + one per row), then the proof
-                hipLaunchKernelGGL(k_viterbi16w, dim3(win_groups), dim3(64), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, nrows, kWinUnitsTarget,
-                                   rx->wstride, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wvecs);
-                if (!redo_finish) win_redo();
-            }
-            else if (rx->lanes16)   // eight frames per one-wave workgroup: at most ceil(n / 8) + 2 waves over the three lists
-                hipLaunchKernelGGL(k_viterbi16, dim3((nrows + 7) / 8 + 2), dim3(64), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, 0u, nrows,
-                                   (const uint8_t*)rx->d_soft, rx->d_vout);
-            else
-                hipLaunchKernelGGL(k_viterbi, dim3(pair_groups), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, 0u, nrows,
-                                   (const uint8_t*)rx->d_soft, rx->d_vout);
+            // (window-parallel: the proof is the finisher's, below, unless the finisher is not launched)
+            if (RX_ONLY(rx, 4u)) trellis_launch<256>(rx->trellis, J, rx->d_soft, rx->d_vout, st, rx->win, !redo_finish);
             if (rx->ordered && !recording && rx->ev_trellis) (void)hipEventRecord(rx->ev_trellis, st);
             mark();
         }
 
         // the finish (behind k_pipe: ... and the plain chain's code for the whole call if a wait inside k_pipe gave up)
         if (redo_finish && pipe)
-            hipLaunchKernelGGL(k_win_redo_finish_pipe, dim3(pair_groups), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, nrows, kWinUnitsTarget,
-                               rx->wstride, (const uint16_t*)rx->d_wvecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wstats, R, rx->d_note);
+            hipLaunchKernelGGL(k_win_redo_finish_pipe, dim3(pair_groups), dim3(256), 0, st, J.jobs, J.hdr, nrows, kWinUnitsTarget,
+                               rx->win.stride, (const uint16_t*)rx->win.d_vecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->win.d_stats, R, rx->d_note);
         else if (redo_finish)
-            hipLaunchKernelGGL(k_win_redo_finish, dim3(pair_groups), dim3(256), 0, st, (const VitJob*)rx->d_jobs, (const uint32_t*)counters, nrows, kWinUnitsTarget,
-                               rx->wstride, (const uint16_t*)rx->d_wvecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->d_wstats, R);
+            hipLaunchKernelGGL(k_win_redo_finish, dim3(pair_groups), dim3(256), 0, st, J.jobs, J.hdr, nrows, kWinUnitsTarget,
+                               rx->win.stride, (const uint16_t*)rx->win.d_vecs, (const uint8_t*)rx->d_soft, rx->d_vout, rx->win.d_stats, R);
         else if (RX_ONLY(rx, 8u)) hipLaunchKernelGGL(k_finish, dim3((nrows + 3) / 4), dim3(256), 0, st, R);
 #ifdef SORA_TOOLS
         for (unsigned x = 0; x < rx->extra; x++) hipLaunchKernelGGL(k_clear16, dim3(1), dim3(256), 0, st, reinterpret_cast<uint4*>(rx->d_njobs), 0u);
@@ -1042,7 +1013,7 @@ struct sora_rx {
     static constexpr int kMaxDepth = 16;
     sora_rx_cfg cfg{};
     std::atomic<int> depth{8};   // (read by other handles' automatic kernel choice under g_rx_mu)
-    int trellis = 0;             // sora_rx_set_trellis: 0 = chosen from the depth, 64 / 16 = lanes per frame pair
+    TrellisChoice trellis;       // sora_rx_set_trellis: no value = chosen from the depth
     int front = 0;               // sora_rx_set_front: 0 = chosen from the capacity in flight, 1 = k_frame, 3 = the three-kernel symbol chain
     bool use_graph = false;
     int cur = 0;                 // pipeline of the most recent process call
@@ -1138,10 +1109,10 @@ int sora_rx_set_fused(sora_rx_t* rx, int enable)
 // Which trellis kernel a call uses: k_viterbi16 pays off once enough frames are in flight to give every SIMD a wave of it (it packs
 // eight frames into a wave, k_viterbi two); see DESIGN.md section 3.1.  What counts is the handle's capacity in flight, not the number
 // of tickets: two calls of 16384 captures fill the chip like eight of 4096, and eight calls of 64 captures do not.
-static int lanes16_for(const sora_rx* rx)                                       // -> RxPipe::lanes16: 0 k_viterbi, 1 k_viterbi16, 2 window-parallel
+static Trellis trellis_for(const sora_rx* rx)                                   // -> RxPipe::trellis
 {
-    if (rx->trellis) return rx->trellis == 16 ? 1 : rx->trellis == SORA_TRELLIS_WINDOWED ? 2 : 0;
-    return (long long)rx->depth * (long long)rx->cfg.max_captures >= kAutoLanes16Captures ? 1 : 2;
+    if (rx->trellis) return *rx->trellis;
+    return (long long)rx->depth * (long long)rx->cfg.max_captures >= kAutoLanes16Captures ? Trellis::Lanes16 : Trellis::Windowed;
 }
 
 // The symbol chain: one wave per frame (k_frame) is the cheaper one when the chip is full of frames; the three-kernel chain spreads a frame's symbols over the
@@ -1172,7 +1143,7 @@ static uint64_t pipe_groups(const sora_rx* rx, bool lanes64)                   /
 static bool pipe_candidate(const sora_rx* h, long long now)
 {
     if (h->front != 4 && h->front != 0) return false;
-    if (h->trellis != 0 && h->trellis != SORA_TRELLIS_WINDOWED) return false;
+    if (h->trellis && *h->trellis != Trellis::Windowed) return false;
     const long long rows = (long long)h->depth * (long long)h->cfg.max_captures * (long long)h->cfg.max_frames_per_capture;
     if (h->front == 0 && rows > kAutoPipeRows) return false;
     const long long t = h->last_call_ns.load(std::memory_order_relaxed);
@@ -1189,14 +1160,14 @@ static bool pipe_fits(const sora_rx* rx, bool lanes64 = false)
         for (const sora_rx* h : g_rx_all)
             if (h != rx && h->cfg.device == rx->cfg.device && pipe_candidate(h, now)) groups += pipe_groups(h, false) * (uint64_t)h->depth;
     }
-    // (64-lane form: every frame must come out cut into single windows, i.e. get its full 80 units: 16384 / 80 frames at most)
+    // (64-lane form: every frame must come out cut into single windows, i.e. get its full 80 units: kWinUnitsTarget / 80 frames at most)
     return groups <= device_cus(rx->cfg.device) * 3 / 4 && (!lanes64 || rows * (uint64_t)rx->depth <= 204);   // (three quarters of the CUs: 192 of an MI355X's 256)
 }
 static int front_for(const sora_rx* rx)                                        // -> RxPipe::front
 {
     if (rx->front == 1 || rx->front == 3) return rx->front;
     // (a wait inside one of this handle's k_pipe launches gave up a few calls ago: somebody else -- another process, other GPU work -- holds CUs; the chain for a while)
-    const bool can_pipe = rx->pipe_backoff == 0 && lanes16_for(rx) == 2 && pipe_fits(rx);
+    const bool can_pipe = rx->pipe_backoff == 0 && trellis_for(rx) == Trellis::Windowed && pipe_fits(rx);
     if (rx->front == 4) return can_pipe ? 4 : 3;
     const long long rows = (long long)rx->depth * (long long)rx->cfg.max_captures * (long long)rx->cfg.max_frames_per_capture;
     return rows <= kAutoPipeRows && can_pipe && !chip_is_shared(rx) ? 4 : rows <= kAutoSplitRows ? 3 : 1;
@@ -1234,9 +1205,8 @@ uint32_t sora_hip_set_share_window_us(uint32_t us)
 int sora_rx_set_trellis(sora_rx_t* rx, int lanes_per_pair)
 {
     if (!rx) return SORA_ERR_INVALID_PARAM;
-    const int old = rx->trellis;
-    if (lanes_per_pair == 0 || lanes_per_pair == 16 || lanes_per_pair == 64 || lanes_per_pair == SORA_TRELLIS_WINDOWED) {
-        rx->trellis = lanes_per_pair;
+    const int old = trellis_abi(rx->trellis);
+    if (trellis_parse(lanes_per_pair, &rx->trellis)) {
         for (RxPipe* p : rx->pipes) if (p) p->last_valid = false;               // (a recorded hipGraph holds the other kernel)
     } else if (lanes_per_pair > 0) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_set_trellis: 0 (automatic), 16 or 64 lanes per frame pair, or SORA_TRELLIS_WINDOWED");
     return old;
@@ -1246,15 +1216,7 @@ int sora_rx_set_trellis(sora_rx_t* rx, int lanes_per_pair)
 int sora_rx_window_stats(sora_rx_t* rx, unsigned long long out[4])
 {
     if (!rx || !out) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_window_stats: null argument");
-    HIPCHK(hipSetDevice(rx->cfg.device));
-    for (int i = 0; i < 4; i++) out[i] = 0;
-    for (RxPipe* p : rx->pipes) if (p && p->d_wstats) {
-        unsigned long long v[4 * kWinStatBanks];
-        HIPCHK(hipStreamSynchronize(p->stream));
-        HIPCHK(hipMemcpy(v, p->d_wstats, sizeof v, hipMemcpyDeviceToHost));
-        for (unsigned i = 0; i < 4 * kWinStatBanks; i++) out[i & 3u] += v[i];
-    }
-    return SORA_OK;
+    return win_stats_sum(rx->pipes, sora_rx::kMaxDepth, rx->cfg.device, out);
 }
 
 // The NEXT process call's frame sink writes every MPDU straight into the caller's page-locked array as well (same geometry as the device's: sora_frame_result::mpdu_offset of
@@ -1280,10 +1242,10 @@ int sora_rx_pipe_stats(sora_rx_t* rx, unsigned long long out[2])
     if (!rx || !out) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_pipe_stats: null argument");
     HIPCHK(hipSetDevice(rx->cfg.device));
     out[0] = 0;
-    for (RxPipe* p : rx->pipes) if (p && p->d_wstats) {
+    for (RxPipe* p : rx->pipes) if (p && p->win.d_stats) {
         unsigned long long v = 0;
         HIPCHK(hipStreamSynchronize(p->stream));
-        HIPCHK(hipMemcpy(&v, p->d_wstats + 4 * kWinStatBanks, sizeof v, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&v, p->win.redone(), sizeof v, hipMemcpyDeviceToHost));
         out[0] += v;
     }
     if (rx->h_note && *(volatile uint32_t*)rx->h_note != 0u) { *(volatile uint32_t*)rx->h_note = 0u; rx->pipe_backoff = kPipeBackoffCalls; rx->pipe_backoffs++; }
@@ -1293,7 +1255,7 @@ int sora_rx_pipe_stats(sora_rx_t* rx, unsigned long long out[2])
 
 int sora_internal_rx_device(sora_rx_t* rx) { return rx ? rx->cfg.device : -1; }
 
-int sora_rx_trellis(sora_rx_t* rx) { return rx ? (lanes16_for(rx) == 2 ? SORA_TRELLIS_WINDOWED : lanes16_for(rx) ? 16 : 64) : SORA_ERR_INVALID_PARAM; }
+int sora_rx_trellis(sora_rx_t* rx) { return rx ? trellis_abi(trellis_for(rx)) : SORA_ERR_INVALID_PARAM; }
 
 int sora_rx_set_graph(sora_rx_t* rx, int enable)
 {
@@ -1362,7 +1324,7 @@ static void choose_kernels(sora_rx* rx, RxPipe* p)
     if (p->ordered && !p->ev_trellis && hipEventCreateWithFlags(&p->ev_trellis, hipEventDisableTiming) != hipSuccess) { p->ev_trellis = nullptr; p->ordered = false; (void)hipGetLastError(); }
     p->wait_for = p->ordered && rx->last_trellis != p->ev_trellis ? rx->last_trellis : nullptr;     // (its own previous call is ahead of it in its stream anyway)
     if (p->ordered) rx->last_trellis = p->ev_trellis; else rx->last_trellis = nullptr;
-    if (p->lanes16 != lanes16_for(rx)) { p->lanes16 = lanes16_for(rx); p->last_valid = false; }
+    if (p->trellis != trellis_for(rx)) { p->trellis = trellis_for(rx); p->last_valid = false; }
     { const int fr = front_for(rx); if (p->front != fr) { p->front = fr; p->last_valid = false; } }
     { const bool p64 = p->front == 4 && pipe_fits(rx, true); if (p->pipe64 != p64) { p->pipe64 = p64; p->last_valid = false; } }
     { const uint32_t wt = rx->pipe_wait_us > 40000000u ? 0xFFFFFFFFu : rx->pipe_wait_us * 100u; if (p->pipe_wait_ticks != wt) { p->pipe_wait_ticks = wt; p->last_valid = false; } }
@@ -1899,12 +1861,11 @@ int sora_hip_ingest(const void* d_raw, size_t raw_bytes, unsigned flags, sora_co
 //   jobs      the job table
 //   vecs      the window-parallel trellis's metric vectors (kWinVecBytes per unit, at most win_units(n) units)
 // sora_hip_viterbi11a keeps the original signature on top of a grow-only workspace cached per device.
-constexpr size_t kVitWsHdr = 0, kVitWsStats = 256, kVitWsHead = kVitWsStats + 4 * kWinStatBanks * sizeof(unsigned long long);
+constexpr size_t kVitWsHdr = 0, kVitWsStats = 256, kVitWsHead = kVitWsStats + kWinStatsBytes;
 static size_t vit_ws_round(size_t b) { return (b + 255) & ~(size_t)255; }
 static size_t vit_ws_packed_bytes(size_t soft_span_bytes) { return vit_ws_round(soft_span_bytes / 2 + 4 + kSoftSlack); }
 static size_t vit_ws_bytes8(size_t soft_span_bytes) { return vit_ws_round(soft_span_bytes + kSoftSlack); }
-static uint32_t vit_ws_vecs(size_t n) { return (uint32_t)(win_units(n) + n); }
-static size_t vit_ws_tail(size_t n) { return vit_ws_round(sizeof(VitJob) * n) + (size_t)kWinVecBytes * vit_ws_vecs(n); }
+static size_t vit_ws_tail(size_t n) { return vit_ws_round(sizeof(VitJob) * n) + (size_t)kWinVecBytes * win_vstride(n); }
 size_t sora_hip_viterbi11a_workspace_bytes(size_t soft_span_bytes, size_t n)
 {
     return kVitWsHead + vit_ws_packed_bytes(soft_span_bytes) + vit_ws_tail(n);
@@ -1927,8 +1888,8 @@ static int viterbi_ws(const char* name, const uint8_t* d_soft, size_t soft_span_
     if (!d_soft || !d_soft_off || !d_nsoft || !d_frame_len || !d_out || !d_out_off || code_rate < 0 || code_rate > 2) return fail(SORA_ERR_INVALID_PARAM,
             (nm + ": bad argument").c_str());
     if (n == 0) return SORA_OK;
-    if (lanes_per_pair != 0 && lanes_per_pair != 16 && lanes_per_pair != 64 && lanes_per_pair != SORA_TRELLIS_WINDOWED) return fail(SORA_ERR_INVALID_PARAM,
-            (nm + ": lanes_per_pair is 0 (default: 64), 16, 64 or SORA_TRELLIS_WINDOWED").c_str());
+    TrellisChoice choice;
+    if (!trellis_parse(lanes_per_pair, &choice)) return fail(SORA_ERR_INVALID_PARAM, (nm + ": lanes_per_pair is 0 (default: 64), 16, 64 or SORA_TRELLIS_WINDOWED").c_str());
     if (!d_workspace || ((uintptr_t)d_workspace & 15)) return fail(SORA_ERR_INVALID_PARAM, (nm + ": the workspace must be a 16-byte aligned device buffer").c_str());
     const size_t need = WIN == 256 ? sora_hip_viterbi11a_workspace_bytes(soft_span_bytes, n) : sora_hip_viterbi11n_workspace_bytes(soft_span_bytes, n);
     if (workspace_bytes < need) return fail(SORA_ERR_CAPACITY, (nm + ": workspace smaller than its _workspace_bytes()").c_str());
@@ -1946,33 +1907,15 @@ static int viterbi_ws(const char* name, const uint8_t* d_soft, size_t soft_span_
         HIPCHK(hipMemcpyAsync(soft, d_soft, soft_span_bytes, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(k_soft_jobs8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_soft_off, d_nsoft, d_frame_len, d_out_off, code_rate, (uint32_t)n, jobs);
     }
-    const VitJob* cjobs = jobs;
-    const uint8_t* csoft = soft;
-    if (lanes_per_pair == SORA_TRELLIS_WINDOWED) {
+    const Trellis kind = choice.value_or(Trellis::Lanes64);
+    const WinScratch W{ vecs, stats, win_vstride(n) };                           // (a view of the workspace: nothing is owned)
+    if (kind == Trellis::Windowed) {
         // the receive path's own unit plan over one code-rate list of n frames: the batch size decides the units' geometry (dev_winplan.h)
-        const uint32_t q = sora::win_units_per_frame((uint32_t)n, kWinUnitsTarget), waves = (sora::win_slots((uint32_t)n, q) + 7) / 8;
-        const uint32_t vstride = vit_ws_vecs(n), pair_groups = (uint32_t)(((n + 1) / 2 + 3) / 4);
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)hdr, 0, 4, st));
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)hdr, (int)n, 1, st));
-        HIPCHK(hipMemsetAsync(stats, 0, 4 * kWinStatBanks * sizeof(unsigned long long), st));
-        if (WIN == 256) {
-            hipLaunchKernelGGL(k_viterbi16w, dim3(waves), dim3(64), 0, st, cjobs, (const uint32_t*)hdr, (uint32_t)n, kWinUnitsTarget, vstride, csoft, d_out, vecs);
-            hipLaunchKernelGGL(k_win_redo, dim3(pair_groups), dim3(256), 0, st, cjobs, (const uint32_t*)hdr, (uint32_t)n, kWinUnitsTarget, vstride,
-                               (const uint16_t*)vecs, csoft, d_out, stats);
-        } else {
-            hipLaunchKernelGGL(k_viterbi16w_11n, dim3(waves), dim3(64), 0, st, cjobs, (const uint32_t*)hdr, (uint32_t)n, kWinUnitsTarget, vstride, csoft, d_out, vecs);
-            hipLaunchKernelGGL(k_win_redo_11n, dim3(pair_groups), dim3(256), 0, st, cjobs, (const uint32_t*)hdr, (uint32_t)n, kWinUnitsTarget, vstride,
-                               (const uint16_t*)vecs, csoft, d_out, stats);
-        }
+        HIPCHK(hipMemsetAsync(stats, 0, kWinStatsBytes, st));
     }
-    else if (lanes_per_pair == 16) {
-        if (WIN == 256) hipLaunchKernelGGL(k_viterbi16, dim3((unsigned)((n + 7) / 8)), dim3(64), 0, st, cjobs, (const uint32_t*)nullptr, (uint32_t)n, 0u, csoft, d_out);
-        else hipLaunchKernelGGL(k_viterbi16_11n, dim3((unsigned)((n + 7) / 8)), dim3(64), 0, st, cjobs, (const uint32_t*)nullptr, (uint32_t)n, 0u, csoft, d_out);
-    }
-    else {
-        if (WIN == 256) hipLaunchKernelGGL(k_viterbi, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, st, cjobs, (const uint32_t*)nullptr, (uint32_t)n, 0u, csoft, d_out);
-        else hipLaunchKernelGGL(k_viterbi11n, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, st, cjobs, (const uint32_t*)nullptr, (uint32_t)n, 0u, csoft, d_out);
-    }
+    trellis_launch<WIN>(kind, trellis_single(jobs, hdr, (uint32_t)n), soft, d_out, st, W);
     HIPCHK(hipGetLastError());
     return SORA_OK;
 }
@@ -1995,12 +1938,8 @@ int sora_hip_viterbi_window_stats(const void* d_workspace, unsigned long long ou
 {
     if (!d_workspace || !out) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_viterbi_window_stats: null argument");
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long v[4 * kWinStatBanks];
-    HIPCHK(hipMemcpyAsync(v, (const uint8_t*)d_workspace + kVitWsStats, sizeof v, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
     for (int i = 0; i < 4; i++) out[i] = 0;
-    for (unsigned i = 0; i < 4 * kWinStatBanks; i++) out[i & 3u] += v[i];
-    return SORA_OK;
+    return win_stats_add((const unsigned long long*)((const uint8_t*)d_workspace + kVitWsStats), st, out);
 }
 
 namespace {
