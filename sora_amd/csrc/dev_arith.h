@@ -299,6 +299,7 @@ __device__ __forceinline__ pcx pk_neg16_hi(pcx b) { return (b & 0xFFFFu) | ((0u 
 struct PkTw { pcx a, b; };                                     // second operands of the two dot products of a complex product
 __device__ __forceinline__ PkTw pk_tw_fft(pcx w) { return PkTw{ w ^ 0xFFFF0000u, pk_swap(w) }; }         // mul_shift15: (re, ~im), (im, re)
 __device__ __forceinline__ PkTw pk_tw_mul(pcx w) { return PkTw{ pk_neg16_hi(w), pk_swap(w) }; }           // mul / mul_q15: (re, neg16(im)), (im, re)
+__device__ __forceinline__ PkTw pk_tw_mul(PkTw t) { return t; }                                                 // (already a pair: dev_sym11a.h takes coefficients in either form)
 template <int SHIFT>
 __device__ __forceinline__ pcx pk_cmul(pcx x, PkTw t)         // ((x.re t.a.lo + x.im t.a.hi) >> SHIFT, (x.re t.b.lo + x.im t.b.hi) >> SHIFT), wrapping packs
 {

@@ -1,24 +1,27 @@
-// k_rx.hip -- batched per-symbol / per-frame kernels of the 802.11a receive path (gfx950).
+// k_rx.hip -- the kernels of the 802.11a receive path behind k_scan (gfx950).
 //
-//   k_frame       T11aDataSymbol -> TFreqCompensation -> TFFT64 -> TChannelEqualization -> TPhaseCompensate ->
-//                 TPilotTrack -> T11aDemap<N> -> T11aDeinterleave                           (one wave per frame, 4 symbols per pass)
-//   k_viterbi<CR> T11aViterbi<5000*8,48,256,24>: 64-state ACS + windowed trace-back out of LDS (one wave per two frames)
-//   k_finish      T11aDesc + TBB11aFrameSink (descramble, CRC-32, FRAME_OK / CRC32_FAIL)   (one wave per frame)
-// plus the stand-alone stage kernels behind the per-stage C entry points.
+// The data field's symbol chain, T11aDataSymbol -> TFreqCompensation -> TFFT64 -> TChannelEqualization -> TPhaseCompensate -> TPilotTrack -> T11aDemap<N> ->
+// T11aDeinterleave -> the packed soft stream, in four forms.  Its arithmetic is in dev_sym11a.h; a form is a schedule, a layout and its hand-offs:
+//   k_frame                                one wave per frame, 4 symbols per pass; the workgroup's four pilot trackers in wave 0 (frame_symbols<true>): the batch path
+//   k_sym_front, k_track_lds, k_sym_back   per symbol slot / per frame (tracker tables in LDS) / per symbol slot: few, long frames
+//   k_pipe                                 those three and the window-parallel trellis as ONE launch of roles: a lone capture
+//   k_win_redo_finish_pipe                 behind k_pipe; when a wait inside k_pipe gave up, the data field again a frame at a time (frame_symbols<false>)
+// The trellis, T11aViterbi<5000*8,48,256,24> (64-state ACS + windowed trace-back out of LDS, dev_viterbi.h):
+//   k_viterbi, k_viterbi11n                one wave per two whole frames
+//   k_win_redo, k_win_redo_11n             the proof of the window-parallel trellis's units (k_vitwin.hip) and the serial decode of what fails it
+// Behind it, T11aDesc + TBB11aFrameSink (descramble, CRC-32, FRAME_OK / CRC32_FAIL):
+//   k_finish                               one wave per frame;  k_win_redo_finish(_pipe): k_win_redo and k_finish as one launch
+//   k_pack                                 the frame table as dense result rows
+// plus k_soft_pack3 / k_soft_jobs8 behind the stand-alone trellis entry points (the other stage kernels: k_stage.hip).
 #include <hip/hip_runtime.h>
 #include <utility>
 #include "kernels.h"
+#include "dev_sym11a.h"
 #include "dev_viterbi.h"
 #include "dev_winplan.h"
 #include "dev_vitwin.h"
 
 namespace sora {
-
-__device__ __constant__ uint8_t kPilotSgn[128] = {        // pilot.hpp:10-28: 1 <=> polarity -1
-    0,0,0,1,1,1,0,1, 1,1,1,0,0,1,0,1, 1,0,0,1,0,0,1,0, 0,0,0,0,0,1,0,0,
-    0,1,0,0,1,1,0,0, 0,1,0,1,1,1,0,1, 0,1,1,0,1,1,0,0, 0,0,0,1,1,0,0,1,
-    1,0,1,0,1,0,0,1, 1,1,0,0,1,1,1,1, 0,1,1,0,1,0,0,0, 0,1,0,1,0,1,0,1,
-    1,1,1,1,0,1,0,0, 1,0,1,0,0,0,1,1, 0,1,1,1,0,0,0,1, 1,1,1,1,1,1,0,0 };
 
 // ------------------------------------------------------------------------------------------------
 // k_frame: everything between the frame table and the soft stream, one wave per frame:
@@ -55,16 +58,9 @@ __device__ __forceinline__ void frame_symbols(const RxArgs& A, uint32_t j, Frame
     const uint32_t f = valid ? A.joblist[j] : 0u;
     FrameRow r = A.frames[f];
     if (!valid) { r.nsym = 0; r.nbpsc = 1; }
-    const uint32_t my_nsoft = (uint32_t)r.nsym * 48u * r.nbpsc;
-    if (lane == 0 && valid) {
-        VitJob J;
-        J.valid = 1; J.soft_off = r.slot0 * (uint32_t)kSoftBytesPerSlot; J.nsoft = my_nsoft; J.length = r.length;
-        J.dec_off = 0; J.out_off = r.slot0 * (uint32_t)kOutPerSlot; J.code_rate = r.code_rate; J.soft_bits = 3;
-        A.jobs[j] = J;
-    }
+    if (lane == 0 && valid) A.jobs[j] = frame_vitjob(r);
     const FrameCtx* fx = A.fctx + f;
     const uint32_t* iq = A.iq + A.caps[r.capture].offset;
-    auto wsync = []() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
     const Fft64TwPk W = fft64_twiddles_pk(T, e);
     // FreqCoeffs / ChannelCoeffs as the operand pairs of the packed complex product
     PkTw fq[4], ch[4];
@@ -72,14 +68,9 @@ __device__ __forceinline__ void frame_symbols(const RxArgs& A, uint32_t j, Frame
     for (int m = 0; m < 4; m++) { fq[m] = pk_tw_mul(fx->freq[e + 16 * m]); ch[m] = pk_tw_mul(fx->chan[e + 16 * m]); }
     // (wave-uniform: scalar branches on the modulation)
     const int nb = __builtin_amdgcn_readfirstlane((int)r.nbpsc), ncbps = 48 * nb, nsym = __builtin_amdgcn_readfirstlane((int)r.nsym);
-    // de-interleaver source indices of output positions 8 lane .. 8 lane + 7 (lane < N_CBPS / 8: one three-byte group of the packed stream), two per register
     uint32_t mp[4];
-    const bool packs = 8 * lane < ncbps;
-    {
-        const uint16_t* map = T.deint + (nb == 1 ? 0 : nb == 2 ? 1 : nb == 4 ? 2 : 3) * 288;
-#pragma unroll
-        for (int t = 0; t < 4; t++) mp[t] = packs ? (uint32_t)map[8 * lane + 2 * t] | ((uint32_t)map[8 * lane + 2 * t + 1] << 16) : 0u;
-    }
+    const bool packs = deint_packs(nb, lane);
+    deint_map_words(T, nb, lane, mp);
     // the frame's packed soft stream: symbol s (1-based) at 3 N_CBPS / 8 * (s - 1) bytes
     uint8_t* dst = A.soft + (size_t)r.slot0 * kSoftBytesPerSlot;
     // pilot k in lane k: bins 43, 57, 7, 21 = carriers -21, -7, +7, +21 (pilot.hpp:138-164)
@@ -109,23 +100,22 @@ __device__ __forceinline__ void frame_symbols(const RxArgs& A, uint32_t j, Frame
         const int sym = s0 + g;
         const bool active = sym <= nsym;
         const bool mine = s0 <= nsym;                                            // (SHARED: a wave whose frame is shorter only keeps the barriers company)
-        int my_cfo = 0, my_sfo = 0, my_avg = 0, my_del = 0;
+        int4 rec = { 0, 0, 0, 0 };                                               // group g's symbol: { CFO_comp, SFO_comp, mean phase, slope } (track_advance)
+        // ---- TFreqCompensation + TFFT64 + TChannelEqualization, symbol `sym` in group g.  Not sym_front_quad: that one hands a lane bins 4e .. 4e+3 for a 16-byte
+        // store to memory; here the symbol stays in LDS, where the tracker and the back end pick single bins, and in bins e + 16 q the guard band's test is a compare
+        // on e for q = 1, 2 and nothing for q = 0, 3 (this kernel is priced by its instructions; the quad's layout cost 26 more of them per kernel, in this loop)
         if (mine) {
-        // ---- TFreqCompensation + TFFT64 + TChannelEqualization on packed COMPLEX16 (dev_arith.h), symbol `sym` in group g
-        pcx x[4], Y[4];
+            pcx x[4], Y[4];
 #pragma unroll
-        for (int m = 0; m < 4; m++) x[m] = pk_cmul<15>(pk_sra(raw[m], 1), fq[m]);   // >>1, x FreqCoeffs (channel_11a.hpp:643-644)
-        if (s0 + 4 <= nsym) load_samples(s0 + 4, raw);                           // next pass: in flight during the tracking loop
-        fft64_core_pk(x, s_eq[w][g], e, W, wsync);
+            for (int m = 0; m < 4; m++) x[m] = sym_freq_comp(raw[m], fq[m]);
+            if (s0 + 4 <= nsym) load_samples(s0 + 4, raw);                       // next pass: in flight during the tracking loop
+            fft64_core_pk(x, s_eq[w][g], e, W, wave_lds_sync);
 #pragma unroll
-        for (int q = 0; q < 4; q++) Y[q] = s_eq[w][g][__brev((unsigned)(e + 16 * q)) >> 26];
-        wsync();
+            for (int q = 0; q < 4; q++) Y[q] = s_eq[w][g][__brev((unsigned)(e + 16 * q)) >> 26];
+            wave_lds_sync();
 #pragma unroll
-        for (int q = 0; q < 4; q++) {                                            // channel_11a.hpp:548-574
-            const int bin = e + 16 * q;
-            s_eq[w][g][bin] = (bin >= 28 && bin < 36) ? 0u : pk_cmul<8>(Y[q], ch[q]);
-        }
-        wsync();
+            for (int q = 0; q < 4; q++) s_eq[w][g][e + 16 * q] = sym_equalise(Y[q], ch[q], e + 16 * q);
+            wave_lds_sync();
         }
         // ---- the loop-carried part, symbols s0 .. s0+3 in order
         if (SHARED) {
@@ -134,12 +124,9 @@ __device__ __forceinline__ void frame_symbols(const RxArgs& A, uint32_t j, Frame
                 const int fr = (lane >> 2) & 3;                                  // lanes 16 .. 63 repeat lanes 0 .. 15 (one instruction stream either way)
 #pragma unroll
                 for (int gg = 0; gg < 4; gg++) {
-                    const bool act = s0 + gg <= nsym_f;
-                    const int c0 = cfo_comp, s0c = sfo_comp;
                     const cpx p = mul_q15(unpack(s_eq[fr][gg][pbin]), rot_coeff(T, w16(cfo_comp + pc * sfo_comp)));
-                    int th = pk == 3 ? uatan2(T, -p.im, -p.re) : uatan2(T, p.im, p.re);
                     // (the symbol index is the same for every frame -- all of them start behind their SIGNAL symbol -- and wave-uniform: a scalar)
-                    if (kPilotSgn[(symbol_count + (unsigned)gg) % 127u]) th = w16(th + 0x8000);
+                    const int th = pilot_angle(pk == 3 ? uatan2(T, -p.im, -p.re) : uatan2(T, p.im, p.re), (symbol_count + (unsigned)gg) % 127u);
                     // the frame's four angles in each of its four lanes: quad_perm broadcasts
                     int th1 = __builtin_amdgcn_update_dpp(0, th, 0x00, 0xF, 0xF, true), th2 = __builtin_amdgcn_update_dpp(0, th, 0x55, 0xF, 0xF, true);
                     int th3 = __builtin_amdgcn_update_dpp(0, th, 0xAA, 0xF, 0xF, true), th4 = __builtin_amdgcn_update_dpp(0, th, 0xFF, 0xF, 0xF, true);
@@ -147,88 +134,48 @@ __device__ __forceinline__ void frame_symbols(const RxArgs& A, uint32_t j, Frame
                     // form gave th2 - th4 where the source says th4 - th2 (measured round 6: one frame in sixteen lost its CRC through the slope's sign; the same
                     // arithmetic through four separate v_mov_b32_dpp, or through ds_bpermute, is bit-exact: DESIGN.md section 3.11).
                     asm volatile("" : "+v"(th1), "+v"(th2), "+v"(th3), "+v"(th4));
-                    const int avg = w16((th1 + th2 + th3 + th4) / 4);
-                    const int del = w16(((th3 - th1) / 28 + (th4 - th2) / 28) >> 1);
-                    if (act) {
-                        cfo_tr = w16(cfo_tr + (avg >> 2)); sfo_tr = w16(sfo_tr + (del >> 2));
-                        cfo_comp = w16(cfo_comp + avg + cfo_tr); sfo_comp = w16(sfo_comp + del + sfo_tr);
-                    }
-                    if (lane < 16 && pk == 0) lds.trk[fr][gg] = int4{ c0, s0c, act ? avg : 0, act ? del : 0 };
+                    const int4 t = track_advance(th1, th2, th3, th4, s0 + gg <= nsym_f, cfo_comp, sfo_comp, cfo_tr, sfo_tr);
+                    if (lane < 16 && pk == 0) lds.trk[fr][gg] = t;
                 }
             }
             symbol_count = (symbol_count + 4u) % 127u;
             __syncthreads();
-            const int4 t = lds.trk[w][g];
-            my_cfo = t.x; my_sfo = t.y; my_avg = t.z; my_del = t.w;
+            rec = lds.trk[w][g];
         } else {
-        int t_cfo[4], t_sfo[4], t_avg[4], t_del[4];
+            // (not the SHARED form with one frame: that form's block barriers need all four waves of the workgroup in step, and the waves of the redo path are not)
+            int4 t[4];
 #pragma unroll
-        for (int gg = 0; gg < 4; gg++) {
-            t_cfo[gg] = cfo_comp; t_sfo[gg] = sfo_comp; t_avg[gg] = 0; t_del[gg] = 0;
-            if (s0 + gg <= nsym) {
-                cpx p = mul_q15(unpack(s_eq[w][gg][pbin]), rot_coeff(T, w16(cfo_comp + pc * sfo_comp)));
-                int th = pk == 3 ? uatan2(T, -p.im, -p.re) : uatan2(T, p.im, p.re);
-                if (kPilotSgn[symbol_count]) th = w16(th + 0x8000);
-                symbol_count++; if (symbol_count >= 127) symbol_count = 0;
-                const int th1 = __builtin_amdgcn_readlane(th, 0), th2 = __builtin_amdgcn_readlane(th, 1);
-                const int th3 = __builtin_amdgcn_readlane(th, 2), th4 = __builtin_amdgcn_readlane(th, 3);
-                const int avg = w16((th1 + th2 + th3 + th4) / 4);
-                const int del = w16(((th3 - th1) / 28 + (th4 - th2) / 28) >> 1);
-                t_avg[gg] = avg; t_del[gg] = del;
-                cfo_tr = w16(cfo_tr + (avg >> 2)); sfo_tr = w16(sfo_tr + (del >> 2));
-                cfo_comp = w16(cfo_comp + avg + cfo_tr); sfo_comp = w16(sfo_comp + del + sfo_tr);
+            for (int gg = 0; gg < 4; gg++) {
+                t[gg] = int4{ cfo_comp, sfo_comp, 0, 0 };
+                if (s0 + gg <= nsym) {
+                    const cpx p = mul_q15(unpack(s_eq[w][gg][pbin]), rot_coeff(T, w16(cfo_comp + pc * sfo_comp)));
+                    const int th = pilot_angle(pk == 3 ? uatan2(T, -p.im, -p.re) : uatan2(T, p.im, p.re), symbol_count);
+                    symbol_count++; if (symbol_count >= 127) symbol_count = 0;
+                    t[gg] = track_advance(__builtin_amdgcn_readlane(th, 0), __builtin_amdgcn_readlane(th, 1), __builtin_amdgcn_readlane(th, 2), __builtin_amdgcn_readlane(th, 3),
+                                          true, cfo_comp, sfo_comp, cfo_tr, sfo_tr);
+                }
             }
-        }
-        my_cfo = g == 0 ? t_cfo[0] : g == 1 ? t_cfo[1] : g == 2 ? t_cfo[2] : t_cfo[3];
-        my_sfo = g == 0 ? t_sfo[0] : g == 1 ? t_sfo[1] : g == 2 ? t_sfo[2] : t_sfo[3];
-        my_avg = g == 0 ? t_avg[0] : g == 1 ? t_avg[1] : g == 2 ? t_avg[2] : t_avg[3];
-        my_del = g == 0 ? t_del[0] : g == 1 ? t_del[1] : g == 2 ? t_del[2] : t_del[3];
+            rec = t[0];
+            if (g == 1) rec = t[1]; else if (g == 2) rec = t[2]; else if (g == 3) rec = t[3];
         }
         if (!mine) continue;
         // ---- TPhaseCompensate + TPilotTrack::_rotate + T11aDemap, 3 data carriers per lane
         if (active) {
-            cpx c1[3], c2[3];
+            uint32_t v3[3];
 #pragma unroll
-            for (int m = 0; m < 3; m++) {                                        // all six coefficient reads in flight together
-                const int bin = carrier_bin48(e + 16 * m);
-                const int c = bin < 32 ? bin : bin - 64;
-                c1[m] = rot_coeff(T, w16(my_cfo + c * my_sfo));
-                c2[m] = rot_coeff(T, w16(my_avg + c * my_del));
-            }
-#pragma unroll
-            for (int m = 0; m < 3; m++) {
-                const int k = e + 16 * m;
-                cpx v = unpack(s_eq[w][g][carrier_bin48(k)]);
-                v = mul_q15(v, c1[m]);
-                v = mul_q15(v, c2[m]);
-                int re = v.re >> 4, im = v.im >> 4;                               // demap_limit<64> (demapper.h:141-151)
-                re = min(max(re, -128), 127); im = min(max(im, -128), 127);
-                const unsigned ur = (unsigned)re & 0xFF, ui = (unsigned)im & 0xFF;
-                uint8_t* o = s_soft[w][g] + k * nb;                               // DemapperCore::Demap<N_BPSC> (demapper.h:16-45)
-                if (nb == 1) { o[0] = s_demap[ur]; }
-                else if (nb == 2) { o[0] = s_demap[ur]; o[1] = s_demap[ui]; }
-                else if (nb == 4) { o[0] = s_demap[ur]; o[1] = s_demap[256 + ur]; o[2] = s_demap[ui]; o[3] = s_demap[256 + ui]; }
-                else { o[0] = s_demap[ur]; o[1] = s_demap[512 + ur]; o[2] = s_demap[768 + ur];
-                       o[3] = s_demap[ui]; o[4] = s_demap[512 + ui]; o[5] = s_demap[768 + ui]; }
-            }
+            for (int m = 0; m < 3; m++) v3[m] = s_eq[w][g][carrier_bin48(e + 16 * m)];
+            sym_back_demap(T, s_demap, v3, rec, nb, e, s_soft[w][g]);
         }
-        wsync();
+        wave_lds_sync();
         // ---- T11aDeinterleave*: out[k] = in[j(k)], eight values -> three bytes of the frame's stream (soft3_store8), symbol by symbol
         {
             const int nact = min(4, nsym - s0 + 1);
             const uint32_t sym_bytes = 3u * (uint32_t)ncbps / 8u;
             uint8_t* d = dst + (size_t)(s0 - 1) * sym_bytes;
-            for (int gs = 0; gs < nact; gs++, d += sym_bytes) {
-                if (packs) {
-                    const uint8_t* src = s_soft[w][gs];
-                    uint32_t v[8];
-#pragma unroll
-                    for (int t = 0; t < 4; t++) { v[2 * t] = src[mp[t] & 0xFFFFu]; v[2 * t + 1] = src[mp[t] >> 16]; }
-                    soft3_store8(d, (uint32_t)lane, soft3_pack8(v));
-                }
-            }
+            for (int gs = 0; gs < nact; gs++, d += sym_bytes)
+                if (packs) soft3_store8(d, (uint32_t)lane, deint_gather24(s_soft[w][gs], mp));
         }
-        wsync();
+        wave_lds_sync();
     }
 }
 __global__ void __launch_bounds__(256) k_frame(RxArgs A)
@@ -257,35 +204,6 @@ __global__ void __launch_bounds__(256) k_frame(RxArgs A)
 // The symbol kernels find a slot's frame through slot_row[] (written by k_scan for the data symbols of every frame it
 // queues).  HBM is the idle resource of this path (4.6 % of the roofline in round 3): the equalised symbols cost
 // 256 B written + ~210 B read per symbol (59 + 48 MB per 4096-frame call) and buy the tracker's instructions back.
-struct SlotOwner { uint32_t row; bool ok; };
-
-// pilot.hpp:10-28 as a bit string (bit i of word i >> 5 = polarity -1 of symbol count i)
-__device__ __forceinline__ unsigned pilot_sgn(unsigned count)
-{
-    const unsigned w = count < 32 ? 0x2049a7b8u : count < 64 ? 0x9836ba32u : count < 96 ? 0xaa16f395u : 0x3f8ec52fu;
-    return (w >> (count & 31u)) & 1u;
-}
-
-constexpr int kSlotIters = 4;                                                    // quads of slots per wave: 16 consecutive slots
-
-// One quad of slots through TFreqCompensation, TFFT64 and TChannelEqualization: group g's symbol from raw[] (its 64 samples behind the cyclic
-// prefix, sample e + 16 m) with the frame's FreqCoeffs / ChannelCoeffs already in their packed-product form; bins 4e .. 4e+3 out.
-template <typename SYNC>
-__device__ __forceinline__ void sym_front_quad(const uint32_t raw[4], const PkTw fq[4], const PkTw ch[4], uint32_t* sl, int e, const Fft64TwPk& W, SYNC wsync, uint32_t o[4])
-{
-    pcx x[4];
-#pragma unroll
-    for (int m = 0; m < 4; m++) x[m] = pk_cmul<15>(pk_sra(raw[m], 1), fq[m]);   // >>1, x FreqCoeffs (channel_11a.hpp:643-644)
-    fft64_core_pk(x, sl, e, W, wsync);
-    const unsigned rv = __brev((unsigned)e) >> 28;                               // bin 4e+q sits at slot bitrev6(4e+q) = bitrev4(e) + 16 bitrev2(q)
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int bin = 4 * e + q;
-        o[q] = (bin >= 28 && bin < 36) ? 0u : pk_cmul<8>(sl[rv + 16u * ((q & 1) * 2 + (q >> 1))], ch[q]);   // channel_11a.hpp:548-574
-    }
-    wsync();
-}
-
 // Stores another workgroup of the SAME launch reads (k_pipe): written through to memory (sc1), so that the publishing flag needs no write-back of the XCD's L2 behind it
 // (cdna_hip_programming.md, guideline 16, form R1: sc1 payload, every storing wave drains, one relaxed agent-scope flag).
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
@@ -302,20 +220,11 @@ __device__ __forceinline__ void sym_front_block(const RxArgs& A, uint32_t bid, u
 {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, e = lane & 15;
     const Tables& T = A.T;
-    const uint32_t slot_first = (bid * 4u + (uint32_t)w) * (4u * kSlotIters);
-    if (slot_first >= A.total_slots) return;
-    auto wsync = []() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
-    // the owners of the wave's 16 slots: lane l < 16 asks for slot slot_first + l, the groups pick theirs up by cross-lane reads
-    const uint32_t my_slot = slot_first + (uint32_t)(lane & 15);
-    const uint32_t my_own = (lane < 16 && my_slot < A.total_slots) ? A.slot_row[my_slot] : 0xFFFFFFFFu;
-    const unsigned long long owned = __ballot(my_own != 0xFFFFFFFFu);
-    if (owned == 0) return;                                                      // preamble / silence only
-    const uint32_t row0 = (uint32_t)__builtin_amdgcn_readlane((int)my_own, __builtin_ctzll(owned));
-    // the usual case: every owned slot of the wave belongs to ONE frame
-    const bool one_frame = __ballot(lane < 16 && my_own != 0xFFFFFFFFu && my_own != row0) == 0;
+    const WaveSlots S = wave_slots(A, bid);
+    if (S.owned == 0) return;                                                    // preamble / silence only
     uint32_t own[kSlotIters];
 #pragma unroll
-    for (int it = 0; it < kSlotIters; it++) own[it] = (uint32_t)__shfl((int)my_own, 4 * it + g);
+    for (int it = 0; it < kSlotIters; it++) own[it] = S.owner(it, g);
     const Fft64TwPk W = fft64_twiddles_pk(T, e);
     uint32_t* sl = s_eq[w][g];
     uint4* eq4 = reinterpret_cast<uint4*>(A.eq);
@@ -329,38 +238,38 @@ __device__ __forceinline__ void sym_front_block(const RxArgs& A, uint32_t bid, u
         if (e == 1)  pilot(2u, o[3]);
         if (e == 5)  pilot(3u, o[1]);
     };
-    if (one_frame) {
+    if (S.one_frame) {
         // ---- one frame: its row and its coefficients once per wave, every sample load in flight before the first butterfly
-        const FrameRow& r = A.frames[row0];
+        const FrameRow& r = A.frames[S.row0];
         const uint32_t* iq = A.iq + A.caps[r.capture].offset;
         const uint32_t ds = r.data_start, s0 = r.slot0, str = A.str;
-        const FrameCtx* fx = A.fctx + row0;
+        const FrameCtx* fx = A.fctx + S.row0;
         uint32_t raw[kSlotIters][4];
 #pragma unroll
         for (int it = 0; it < kSlotIters; it++) {
-            const uint32_t p0 = ds + 80u * (slot_first + 4u * it + (uint32_t)g - s0) + 8u;   // skip_cp = 8 (PHY_11a.hpp:365,394)
+            const uint32_t p0 = ds + 80u * (S.slot(it, g) - s0) + 8u;   // skip_cp = 8 (PHY_11a.hpp:365,394)
 #pragma unroll
-            for (int m = 0; m < 4; m++) raw[it][m] = own[it] != 0xFFFFFFFFu ? iq[(size_t)(p0 + (uint32_t)(e + 16 * m)) * str] : 0u;
+            for (int m = 0; m < 4; m++) raw[it][m] = own[it] != kNoOwner ? iq[(size_t)(p0 + (uint32_t)(e + 16 * m)) * str] : 0u;
         }
         PkTw fq[4], ch[4];
 #pragma unroll
         for (int m = 0; m < 4; m++) { fq[m] = pk_tw_mul(fx->freq[e + 16 * m]); ch[m] = pk_tw_mul(fx->chan[4 * e + m]); }
 #pragma unroll
         for (int it = 0; it < kSlotIters; it++) {
-            if (((owned >> (4 * it)) & 0xFull) == 0) continue;                   // (wave-uniform)
+            if (S.quad(it) == 0) continue;                   // (wave-uniform)
             uint32_t o[4];
-            sym_front_quad(raw[it], fq, ch, sl, e, W, wsync, o);
-            if (own[it] != 0xFFFFFFFFu) store(slot_first + 4u * it + (uint32_t)g, o);
+            sym_front_quad(raw[it], fq, ch, sl, e, W, o);
+            if (own[it] != kNoOwner) store(S.slot(it, g), o);
         }
         return;
     }
     // ---- several frames meet in these 16 slots (the end of one and the start of the next, captures of a few symbols): per group and quad
 #pragma unroll 1
     for (int it = 0; it < kSlotIters; it++) {
-        if (((owned >> (4 * it)) & 0xFull) == 0) continue;
-        const uint32_t ow = (uint32_t)__shfl((int)my_own, 4 * it + g);
-        const bool mine = ow != 0xFFFFFFFFu;
-        const uint32_t slot = slot_first + 4u * it + (uint32_t)g;
+        if (S.quad(it) == 0) continue;
+        const uint32_t ow = S.owner(it, g);
+        const bool mine = ow != kNoOwner;
+        const uint32_t slot = S.slot(it, g);
         uint32_t raw[4] = { 0u, 0u, 0u, 0u };
         PkTw fq[4], ch[4];
         const FrameCtx* fx = A.fctx + (mine ? ow : 0u);
@@ -374,7 +283,7 @@ __device__ __forceinline__ void sym_front_block(const RxArgs& A, uint32_t bid, u
 #pragma unroll
         for (int m = 0; m < 4; m++) { fq[m] = pk_tw_mul(mine ? fx->freq[e + 16 * m] : 0u); ch[m] = pk_tw_mul(mine ? fx->chan[4 * e + m] : 0u); }
         uint32_t o[4];
-        sym_front_quad(raw, fq, ch, sl, e, W, wsync, o);
+        sym_front_quad(raw, fq, ch, sl, e, W, o);
         if (mine) store(slot, o);
     }
 }
@@ -470,12 +379,7 @@ __global__ void __launch_bounds__(256) k_track_lds(RxArgs A)
     const uint32_t f = jr.ok ? A.joblist[j] : 0u;
     const FrameRow r = A.frames[f];
     const int nsym = jr.ok ? (int)r.nsym : 0;
-    if (jr.ok && pk == 0) {
-        VitJob J;
-        J.valid = 1; J.soft_off = r.slot0 * (uint32_t)kSoftBytesPerSlot; J.nsoft = (uint32_t)r.nsym * 48u * r.nbpsc; J.length = r.length;
-        J.dec_off = 0; J.out_off = r.slot0 * (uint32_t)kOutPerSlot; J.code_rate = r.code_rate; J.soft_bits = 3;
-        A.jobs[j] = J;
-    }
+    if (jr.ok && pk == 0) A.jobs[j] = frame_vitjob(r);
     const int pc = pk == 0 ? -21 : pk == 1 ? -7 : pk == 2 ? 7 : 21;             // pilot k in lane k: carriers -21, -7, +7, +21 (pilot.hpp:138-164)
     const int m3 = pk == 3 ? -1 : 0;                                             // the fourth pilot's angle is taken of -p (pilot.hpp:166-233)
     // cfo / sfo wrapped to 16 bits after every step; the trackers run free (they are only ever added)
@@ -515,36 +419,8 @@ __global__ void __launch_bounds__(256) k_track_lds(RxArgs A)
     }
 }
 
-// TPhaseCompensate + TPilotTrack::_rotate + T11aDemap for one group's symbol (3 data carriers per lane, 16 lanes per symbol): the three bins v3
-// (carriers e, e + 16, e + 32 in demap order) x CompCoeffs(cfo, sfo) x rotation(avg, del) -> soft values in carrier order at `dst`.
-__device__ __forceinline__ void sym_back_demap(const Tables& T, const uint8_t* s_demap, const uint32_t v3[3], TrackRec tr, int nb, int e, uint8_t* dst)
-{
-    cpx c1[3], c2[3];
-#pragma unroll
-    for (int m = 0; m < 3; m++) {                                                // all six coefficient reads in flight together
-        const int bin = carrier_bin48(e + 16 * m);
-        const int c = bin < 32 ? bin : bin - 64;
-        c1[m] = rot_coeff(T, w16((int)tr.cfo_comp + c * (int)tr.sfo_comp));
-        c2[m] = rot_coeff(T, w16((int)tr.avg + c * (int)tr.del));
-    }
-#pragma unroll
-    for (int m = 0; m < 3; m++) {
-        const int k = e + 16 * m;
-        cpx v = mul_q15(unpack(v3[m]), c1[m]);
-        v = mul_q15(v, c2[m]);
-        int re = v.re >> 4, im = v.im >> 4;                                       // demap_limit<64> (demapper.h:141-151)
-        re = min(max(re, -128), 127); im = min(max(im, -128), 127);
-        const unsigned ur = (unsigned)re & 0xFF, ui = (unsigned)im & 0xFF;
-        uint8_t* o = dst + k * nb;                                                // DemapperCore::Demap<N_BPSC> (demapper.h:16-45)
-        if (nb == 1) { o[0] = s_demap[ur]; }
-        else if (nb == 2) { o[0] = s_demap[ur]; o[1] = s_demap[ui]; }
-        else if (nb == 4) { o[0] = s_demap[ur]; o[1] = s_demap[256 + ur]; o[2] = s_demap[ui]; o[3] = s_demap[256 + ui]; }
-        else { o[0] = s_demap[ur]; o[1] = s_demap[512 + ur]; o[2] = s_demap[768 + ur];
-               o[3] = s_demap[ui]; o[4] = s_demap[512 + ui]; o[5] = s_demap[768 + ui]; }
-    }
-}
-
-// ... then T11aDeinterleave + the packed three-bit stream, a symbol at a time across the wave (eight values -> three bytes per lane).
+// Behind the tracker: TPhaseCompensate + TPilotTrack::_rotate + T11aDemap per group (sym_back_demap), then T11aDeinterleave + the packed three-bit stream, a
+// symbol at a time across the wave (eight values -> three bytes per lane).
 __global__ void __launch_bounds__(256) k_sym_back(RxArgs A)
 {
     __shared__ uint8_t s_soft[4][4][288];                                        // [wave][group]: soft values in carrier order
@@ -553,57 +429,42 @@ __global__ void __launch_bounds__(256) k_sym_back(RxArgs A)
     const Tables& T = A.T;
     reinterpret_cast<uint32_t*>(s_demap)[threadIdx.x] = reinterpret_cast<const uint32_t*>(T.demap)[threadIdx.x];
     __syncthreads();                                                             // the only block barrier: the waves are independent from here on
-    const uint32_t slot_first = (blockIdx.x * 4u + (uint32_t)w) * (4u * kSlotIters);
-    if (slot_first >= A.total_slots) return;
-    auto wsync = []() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
-    const uint32_t my_slot = slot_first + (uint32_t)(lane & 15);
-    const uint32_t my_own = (lane < 16 && my_slot < A.total_slots) ? A.slot_row[my_slot] : 0xFFFFFFFFu;
-    const unsigned long long owned = __ballot(my_own != 0xFFFFFFFFu);
-    if (owned == 0) return;
-    const uint32_t row0 = (uint32_t)__builtin_amdgcn_readlane((int)my_own, __builtin_ctzll(owned));
-    const bool one_frame = __ballot(lane < 16 && my_own != 0xFFFFFFFFu && my_own != row0) == 0;
+    const WaveSlots S = wave_slots(A, blockIdx.x);
+    if (S.owned == 0) return;
     int bins[3];
 #pragma unroll
     for (int m = 0; m < 3; m++) bins[m] = carrier_bin48(e + 16 * m);
-    if (one_frame) {
+    if (S.one_frame) {
         // ---- one frame: modulation, stream position and de-interleaver entries once per wave; the loads of all four quads up front
-        const FrameRow& r = A.frames[row0];
+        const FrameRow& r = A.frames[S.row0];
         const int nb = __builtin_amdgcn_readfirstlane((int)r.nbpsc), ncbps = 48 * nb;
         const uint32_t slot0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.slot0), sym_bytes = 3u * (uint32_t)ncbps / 8u;
         uint8_t* stream = A.soft + (size_t)slot0 * kSoftBytesPerSlot;
-        const bool packs = 8 * lane < ncbps;
+        const bool packs = deint_packs(nb, lane);
         uint32_t mp[4];
-        {
-            const uint16_t* map = T.deint + (nb == 1 ? 0 : nb == 2 ? 1 : nb == 4 ? 2 : 3) * 288;
-#pragma unroll
-            for (int t = 0; t < 4; t++) mp[t] = packs ? (uint32_t)map[8 * lane + 2 * t] | ((uint32_t)map[8 * lane + 2 * t + 1] << 16) : 0u;
-        }
+        deint_map_words(T, nb, lane, mp);
         TrackRec tr[kSlotIters]; uint32_t v3[kSlotIters][3];
 #pragma unroll
         for (int it = 0; it < kSlotIters; it++) {
-            const uint32_t slot = slot_first + 4u * it + (uint32_t)g;
-            const bool mine = (owned >> (4 * it + g)) & 1ull;
+            const uint32_t slot = S.slot(it, g);
+            const bool mine = (S.quad(it) >> g) & 1u;
             tr[it] = mine ? A.track[slot] : TrackRec{ 0, 0, 0, 0 };
 #pragma unroll
             for (int m = 0; m < 3; m++) v3[it][m] = mine ? A.eq[(size_t)slot * 64u + (uint32_t)bins[m]] : 0u;
         }
 #pragma unroll
         for (int it = 0; it < kSlotIters; it++) {
-            const unsigned quad = (unsigned)(owned >> (4 * it)) & 0xFu;
+            const unsigned quad = S.quad(it);
             if (quad == 0) continue;                                             // (wave-uniform)
-            if ((quad >> g) & 1u) sym_back_demap(T, s_demap, v3[it], tr[it], nb, e, s_soft[w][g]);
-            wsync();
+            if ((quad >> g) & 1u) sym_back_demap(T, s_demap, v3[it], track_rec4(tr[it]), nb, e, s_soft[w][g]);
+            wave_lds_sync();
 #pragma unroll
             for (int gs = 0; gs < 4; gs++) {
                 if (!((quad >> gs) & 1u) || !packs) continue;
-                const uint32_t sg = slot_first + 4u * it + (uint32_t)gs;         // data symbol sg - slot0 of the frame
-                const uint8_t* src = s_soft[w][gs];
-                uint32_t v[8];
-#pragma unroll
-                for (int t = 0; t < 4; t++) { v[2 * t] = src[mp[t] & 0xFFFFu]; v[2 * t + 1] = src[mp[t] >> 16]; }
-                soft3_store8(stream + (size_t)(sg - slot0 - 1u) * sym_bytes, (uint32_t)lane, soft3_pack8(v));
+                const uint32_t sg = S.slot(it, gs);                              // data symbol sg - slot0 of the frame
+                soft3_store8(stream + (size_t)(sg - slot0 - 1u) * sym_bytes, (uint32_t)lane, deint_gather24(s_soft[w][gs], mp));
             }
-            wsync();
+            wave_lds_sync();
         }
         return;
     }
@@ -612,11 +473,11 @@ __global__ void __launch_bounds__(256) k_sym_back(RxArgs A)
     int cur_nb = 0; uint32_t mp[4] = { 0, 0, 0, 0 };
 #pragma unroll 1
     for (int it = 0; it < kSlotIters; it++) {
-        const unsigned quad = (unsigned)(owned >> (4 * it)) & 0xFu;
+        const unsigned quad = S.quad(it);
         if (quad == 0) continue;
-        const uint32_t ow = (uint32_t)__shfl((int)my_own, 4 * it + g);
-        const bool mine = ow != 0xFFFFFFFFu;
-        const uint32_t slot = slot_first + 4u * it + (uint32_t)g;
+        const uint32_t ow = S.owner(it, g);
+        const bool mine = ow != kNoOwner;
+        const uint32_t slot = S.slot(it, g);
         int nb = 0; uint32_t slot0 = 0;
         if (mine) {
             const FrameRow& r = A.frames[ow];
@@ -624,33 +485,22 @@ __global__ void __launch_bounds__(256) k_sym_back(RxArgs A)
             uint32_t v3[3];
 #pragma unroll
             for (int m = 0; m < 3; m++) v3[m] = A.eq[(size_t)slot * 64u + (uint32_t)bins[m]];
-            sym_back_demap(T, s_demap, v3, A.track[slot], nb, e, s_soft[w][g]);
+            sym_back_demap(T, s_demap, v3, track_rec4(A.track[slot]), nb, e, s_soft[w][g]);
         }
-        wsync();
+        wave_lds_sync();
 #pragma unroll 1
         for (int gs = 0; gs < 4; gs++) {
             if (!((quad >> gs) & 1u)) continue;
             const int nbg = __shfl(nb, 16 * gs);
             const uint32_t slot0g = (uint32_t)__shfl((int)slot0, 16 * gs);
-            const int ncbps = 48 * nbg;
-            if (nbg != cur_nb) {
-                cur_nb = nbg;
-                const uint16_t* map = T.deint + (nbg == 1 ? 0 : nbg == 2 ? 1 : nbg == 4 ? 2 : 3) * 288;
-                const bool packs = 8 * lane < ncbps;
-#pragma unroll
-                for (int t = 0; t < 4; t++) mp[t] = packs ? (uint32_t)map[8 * lane + 2 * t] | ((uint32_t)map[8 * lane + 2 * t + 1] << 16) : 0u;
-            }
-            if (8 * lane < ncbps) {
-                const uint32_t sg = slot_first + 4u * it + (uint32_t)gs;
-                uint8_t* d = A.soft + (size_t)slot0g * kSoftBytesPerSlot + (size_t)(sg - slot0g - 1u) * (3u * (uint32_t)ncbps / 8u);
-                const uint8_t* src = s_soft[w][gs];
-                uint32_t v[8];
-#pragma unroll
-                for (int t = 0; t < 4; t++) { v[2 * t] = src[mp[t] & 0xFFFFu]; v[2 * t + 1] = src[mp[t] >> 16]; }
-                soft3_store8(d, (uint32_t)lane, soft3_pack8(v));
+            if (nbg != cur_nb) { cur_nb = nbg; deint_map_words(T, nbg, lane, mp); }
+            if (deint_packs(nbg, lane)) {
+                const uint32_t sg = S.slot(it, gs);
+                uint8_t* d = A.soft + (size_t)slot0g * kSoftBytesPerSlot + (size_t)(sg - slot0g - 1u) * (3u * 48u * (uint32_t)nbg / 8u);
+                soft3_store8(d, (uint32_t)lane, deint_gather24(s_soft[w][gs], mp));
             }
         }
-        wsync();
+        wave_lds_sync();
     }
 }
 
@@ -712,11 +562,7 @@ __device__ __forceinline__ void pipe_track_block(const RxArgs& A, const PipeArgs
     const FrameRow r = A.frames[f];
     const uint32_t nsym = min((uint32_t)r.nsym, kPipeMaxSym - 8u), slot0 = r.slot0;
     if (threadIdx.x == 0) {
-        VitJob J;
-        J.valid = 1; J.soft_off = slot0 * (uint32_t)kSoftBytesPerSlot; J.nsoft = (uint32_t)r.nsym * 48u * r.nbpsc; J.length = r.length;
-        J.dec_off = 0; J.out_off = slot0 * (uint32_t)kOutPerSlot; J.code_rate = r.code_rate; J.soft_bits = 3;
-        // (for the kernels behind this launch; the trellis waves of this one work it out themselves)
-        A.jobs[j] = J;
+        A.jobs[j] = frame_vitjob(r);                                             // (for the kernels behind this launch; the trellis waves of this one work it out themselves)
         L.done = 0; L.give_up = 0; L.next_quad[0] = 0; L.next_quad[1] = 1; L.next_quad[2] = 2;
     }
     if (w == 0) {
@@ -777,17 +623,12 @@ __device__ __forceinline__ void pipe_track_block(const RxArgs& A, const PipeArgs
     // ---- the helpers: TPhaseCompensate + the pilots' rotation + T11aDemap + T11aDeinterleave + the packed stream, quad by quad behind the chain
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                           // (eq[] was written by the front workgroups of this launch)
     const int h = w - 1, g = lane >> 4, e = lane & 15;
-    auto wsync = []() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
     const int nb = __builtin_amdgcn_readfirstlane((int)r.nbpsc), ncbps = 48 * nb;
     const uint32_t sym_bytes = 3u * (uint32_t)ncbps / 8u;
     uint8_t* stream = A.soft + (size_t)slot0 * kSoftBytesPerSlot;
-    const bool packs = 8 * lane < ncbps;
+    const bool packs = deint_packs(nb, lane);
     uint32_t mp[4];
-    {
-        const uint16_t* map = A.T.deint + (nb == 1 ? 0 : nb == 2 ? 1 : nb == 4 ? 2 : 3) * 288;
-#pragma unroll
-        for (int tt = 0; tt < 4; tt++) mp[tt] = packs ? (uint32_t)map[8 * lane + 2 * tt] | ((uint32_t)map[8 * lane + 2 * tt + 1] << 16) : 0u;
-    }
+    deint_map_words(A.T, nb, lane, mp);
     int bins[3];
 #pragma unroll
     for (int m = 0; m < 3; m++) bins[m] = carrier_bin48(e + 16 * m);
@@ -805,31 +646,23 @@ __device__ __forceinline__ void pipe_track_block(const RxArgs& A, const PipeArgs
         while (*done < 4u * k + nact) __builtin_amdgcn_s_sleep(1);
         asm volatile("" ::: "memory");
         const uint2 rw = L.rec[(s - 1u) & (kPipeRing - 1u)];
-        TrackRec tr;
-        tr.cfo_comp = (int16_t)rw.x; tr.sfo_comp = (int16_t)(rw.x >> 16); tr.avg = (int16_t)rw.y; tr.del = (int16_t)(rw.y >> 16);
-        if (mine) sym_back_demap(A.T, L.demap, v3, tr, nb, e, L.soft[h][g]);
-        wsync();
+        if (mine) sym_back_demap(A.T, L.demap, v3, int4{ (int16_t)rw.x, (int16_t)(rw.x >> 16), (int16_t)rw.y, (int16_t)(rw.y >> 16) }, nb, e, L.soft[h][g]);
+        wave_lds_sync();
         uint32_t b24[4];
 #pragma unroll
-        for (int gs = 0; gs < 4; gs++) {
-            const uint8_t* src = L.soft[h][gs];
-            uint32_t v[8];
-#pragma unroll
-            for (int tt = 0; tt < 4; tt++) { v[2 * tt] = src[mp[tt] & 0xFFFFu]; v[2 * tt + 1] = src[mp[tt] >> 16]; }
-            b24[gs] = soft3_pack8(v);
-        }
-        wsync();
+        for (int gs = 0; gs < 4; gs++) b24[gs] = deint_gather24(L.soft[h][gs], mp);
+        wave_lds_sync();
         if (packs) {
 #pragma unroll
             for (int gs = 0; gs < 4; gs++) soft3_store8(bytes + (uint32_t)gs * sym_bytes, (uint32_t)lane, b24[gs]);
         }
-        wsync();
+        wave_lds_sync();
         // the quad's bytes (a multiple of eight from a multiple-of-four address: 72 N_BPSC per quad; a last, shorter quad is rounded up into the frame's own spare slot)
         const uint32_t ndw = (nact * sym_bytes + 3u) / 4u;
         uint32_t* out32 = reinterpret_cast<uint32_t*>(stream + (size_t)(4u * k) * sym_bytes);
         for (uint32_t i = (uint32_t)lane; i < ndw; i += 64u) store4_through(out32 + i, reinterpret_cast<const uint32_t*>(bytes)[i]);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wsync();
+        wave_lds_sync();
         quads++;
         if (lane == 0) { store4_through(my_count, quads); nq[h] = k + 3u; }
     }
@@ -866,13 +699,7 @@ __device__ __forceinline__ bool pipe_units_ready(const RxArgs& A, const PipeArgs
 __device__ __forceinline__ auto pipe_jobs_of(const RxArgs& A, uint32_t list)
 {
     const uint32_t* jl = A.joblist + (size_t)list * A.nrows; const FrameRow* fr = A.frames;
-    return [jl, fr](uint32_t idx) {
-        const FrameRow& r = fr[jl[idx]];
-        VitJob J;
-        J.valid = 1; J.soft_off = r.slot0 * (uint32_t)kSoftBytesPerSlot; J.nsoft = (uint32_t)r.nsym * 48u * r.nbpsc; J.length = r.length;
-        J.dec_off = 0; J.out_off = r.slot0 * (uint32_t)kOutPerSlot; J.code_rate = r.code_rate; J.soft_bits = 3;
-        return J;
-    };
+    return [jl, fr](uint32_t idx) { return frame_vitjob(fr[jl[idx]]); };
 }
 __device__ __forceinline__ void pipe_trellis_wave(const RxArgs& A, const PipeArgs& P, uint32_t wave_index, Lds16<256, 24>& S)
 {

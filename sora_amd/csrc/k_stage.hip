@@ -14,17 +14,13 @@
 // >= 64 KB of reads in flight (6.3 TB/s x ~2 us of latency = ~50 KB per CU is what the chip needs to stay busy).
 // Pointers given to these entry points must be 16-byte aligned (any hipMalloc'd buffer is).
 #include "kernels.h"
+#include "dev_sym11a.h"
 
 namespace sora {
 
 __device__ __constant__ uint8_t kLtsSeqS[64] = {        // LTS_Sequence_11a (channel_11a.hpp:13-18)
     0,1,0,0,1,1,0,1,0,1,0,0,0,0,0,1, 1,0,0,1,0,1,0,1,1,1,1,0,0,0,0,0,
     0,0,0,0,0,0,1,1,0,0,1,1,0,1,0,1, 1,1,1,1,1,0,0,1,1,0,1,0,1,1,1,1 };
-__device__ __constant__ uint8_t kPilotSgnS[128] = {     // pilot.hpp:10-28: 1 <=> polarity -1
-    0,0,0,1,1,1,0,1, 1,1,1,0,0,1,0,1, 1,0,0,1,0,0,1,0, 0,0,0,0,0,1,0,0,
-    0,1,0,0,1,1,0,0, 0,1,0,1,1,1,0,1, 0,1,1,0,1,1,0,0, 0,0,0,1,1,0,0,1,
-    1,0,1,0,1,0,0,1, 1,1,0,0,1,1,1,1, 0,1,1,0,1,0,0,0, 0,1,0,1,0,1,0,1,
-    1,1,1,1,0,1,0,0, 1,0,1,0,0,0,1,1, 0,1,1,1,0,0,0,1, 1,1,1,1,1,1,0,0 };
 
 __device__ __forceinline__ int wave_sum_i(int v)
 {
@@ -107,17 +103,10 @@ __global__ void __launch_bounds__(256) k_symfront_batch(const uint32_t* __restri
         wave_lds_sync();
         reinterpret_cast<uint4*>(s)[e] = v[t];
         wave_lds_sync();
-        pcx x[4];
+        uint32_t raw[4], o[4];
 #pragma unroll
-        for (int m = 0; m < 4; m++) x[m] = pk_cmul<15>(pk_sra(s[e + 16 * m], 1), pk_tw_mul(fq[m]));   // >>1, x FreqCoeffs (channel_11a.hpp:643-644)
-        fft64_core_pk(x, s, e, W, wave_lds_sync);
-        uint32_t o[4];
-        const unsigned r = __brev((unsigned)e) >> 28;                                // bin 4e+q sits at slot bitrev6(4e+q) = bitrev4(e) + 16 bitrev2(q)
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int bin = 4 * e + q;
-            o[q] = (bin >= 28 && bin < 36) ? 0u : pk_cmul<8>(s[r + 16u * ((q & 1) * 2 + (q >> 1))], pk_tw_mul(ch[q]));   // channel_11a.hpp:548-574
-        }
+        for (int m = 0; m < 4; m++) raw[m] = s[e + 16 * m];
+        sym_front_quad(raw, fq, ch, s, e, W, o);
         if (i < n) reinterpret_cast<uint4*>(eq)[(size_t)i * 16 + e] = uint4{o[0], o[1], o[2], o[3]};
     }
 }
@@ -301,17 +290,13 @@ __global__ void __launch_bounds__(64) k_ptrack_batch(const uint32_t* eq, const u
         const uint32_t pk = pack(pc);
         const cpx p43 = unpack((uint32_t)__shfl((int)pk, 43)), p57 = unpack((uint32_t)__shfl((int)pk, 57));
         const cpx p7 = unpack((uint32_t)__shfl((int)pk, 7)),   p21 = unpack((uint32_t)__shfl((int)pk, 21));
-        int th1 = uatan2(T, p43.im, p43.re), th2 = uatan2(T, p57.im, p57.re);
-        int th3 = uatan2(T, p7.im, p7.re),   th4 = uatan2(T, -p21.im, -p21.re);
-        if (kPilotSgnS[symbol_count & 127]) { th1 = w16(th1 + 0x8000); th2 = w16(th2 + 0x8000); th3 = w16(th3 + 0x8000); th4 = w16(th4 + 0x8000); }
+        const unsigned cnt = symbol_count & 127;
         symbol_count++; if (symbol_count >= 127) symbol_count = 0;
-        const int avg = w16((th1 + th2 + th3 + th4) / 4);
-        const int del = w16(((th3 - th1) / 28 + (th4 - th2) / 28) >> 1);
+        const int4 rec = track_advance(pilot_angle(uatan2(T, p43.im, p43.re), cnt), pilot_angle(uatan2(T, p57.im, p57.re), cnt), pilot_angle(uatan2(T, p7.im, p7.re), cnt),
+                                       pilot_angle(uatan2(T, -p21.im, -p21.re), cnt), true, cfo_comp, sfo_comp, cfo_tr, sfo_tr);
         cpx o = mk(0, 0);                                                        // bins 0, 27..37: not produced by _rotate / undefined in the reference
-        if (data_bin) o = mul_q15(pc, rot_coeff(T, w16(avg + c * del)));
+        if (data_bin) o = mul_q15(pc, rot_coeff(T, w16(rec.z + c * rec.w)));
         out[(size_t)(s0 + s) * 64 + lane] = pack(o);
-        cfo_tr = w16(cfo_tr + (avg >> 2)); sfo_tr = w16(sfo_tr + (del >> 2));
-        cfo_comp = w16(cfo_comp + avg + cfo_tr); sfo_comp = w16(sfo_comp + del + sfo_tr);
         if (data_bin) comp = rot_coeff(T, w16(cfo_comp + c * sfo_comp));         // _build_coeff(CompCoeffs, CFO_comp, SFO_comp)
     }
     st[3 + lane] = pack(comp);

@@ -11,7 +11,7 @@
 // One 256-thread block per frame; eight OFDM symbols per pass, 32 lanes each (IFFT<128>: 4 points per lane).
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include "dev_tx.h"
+#include "dev_pilot11a.h"
 
 namespace sora {
 

@@ -18,7 +18,7 @@
 // so a group keeps its stream (and its per-lane bit addresses) for the whole frame and a wave's two groups share their symbol.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include "dev_tx.h"
+#include "dev_pilot11a.h"
 #include "dev_11n.h"
 
 namespace sora {
