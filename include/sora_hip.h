@@ -505,6 +505,18 @@ int   sora_rx11n_set_depth(sora_rx11n_t* rx, int depth);
 int   sora_rx11n_set_trellis(sora_rx11n_t* rx, int lanes_per_pair);
 int   sora_rx11n_trellis(sora_rx11n_t* rx);
 int   sora_rx11n_window_stats(sora_rx11n_t* rx, unsigned long long out[4]);
+/* Highest MCS the handle's SIG parser accepts: 10 (default: exactly PHY_11n.hpp:497) .. 14.  Returns the previous value; <= 0 only queries; any other value:
+ * SORA_ERR_INVALID_PARAM.  Waits for the calls in flight and re-sizes the pipelines (SORA_ERR_CAPACITY, and no change, where max_total_samples does not fit the wider
+ * symbol slots of one handle); in stream mode it starts every stream afresh.
+ *   - The reference's behaviour: everything at the default.  With the gate at 10 every row, byte and position is what the reference's graph gives; MCS 11..14 frames
+ *     are PLCP header failures, as T11nSigParser::_parse_htsig reports them (ht_frame_mcs >= 11).
+ *   - The library's own definition, with the gate raised: "the reference's graph with the one comparison moved".  CreateDemodGraph11n is wired for these rates --
+ *     rate_selector routes MCS 11/12 to T11nDemapQAM16 -> T11nDeinterleaveQAM16_S0/_S1 -> TStreamJoin<2,208> -> TStreamConcat<2,2> and MCS 13/14 to the QAM64 bricks
+ *     -> TStreamJoin<2,312> -> TStreamConcat<2,3>, all into the one T11aViterbi<5000*8,312,192,36> (rate 1/2 for MCS 11, 3/4 for 12 and 14, 2/3 for 13) -- and
+ *     this handle runs those bricks; the symbol count follows N_DBPS = 208, 312, 416, 468.  No compiled reference decodes such a frame: tests/rx11n_ext_model.py
+ *     restates that graph from the reference-pinned stage functions and is what the GPU rows are compared with.  rate_kbps carries the MCS index 11..14.
+ *   - Unchanged at every gate: MCS < 8 and MCS 15 are refused, as are HT lengths above 1500 and every L-SIG check. */
+int   sora_rx11n_set_mcs_max(sora_rx11n_t* rx, int mcs_max);
 int   sora_rx11n_ticket(sora_rx11n_t* rx);
 int   sora_rx11n_synchronize(sora_rx11n_t* rx);                                                       /* every call issued so far has finished */
 int   sora_rx11n_wait(sora_rx11n_t* rx, int ticket);

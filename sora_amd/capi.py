@@ -72,7 +72,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_rx11n_set_stream_mode", "sora_rx11n_stream_consumed", "sora_ht40_deliver_async",
            "sora_rx11n_create", "sora_rx11n_destroy", "sora_rx11n_stream", "sora_rx11n_process_dev", "sora_rx11n_process", "sora_rx11n_results",
            "sora_rx11n_set_depth", "sora_rx11n_set_trellis", "sora_rx11n_trellis", "sora_rx11n_window_stats", "sora_rx11n_synchronize", "sora_rx11n_ticket", "sora_rx11n_wait",
-                      "sora_rx11n_wait_any", "sora_rx11n_results_of",
+                      "sora_rx11n_wait_any", "sora_rx11n_results_of", "sora_rx11n_set_mcs_max",
            "sora_ht40_symbols", "sora_ht40_create", "sora_ht40_destroy", "sora_ht40_stream", "sora_ht40_synchronize", "sora_ht40_set_trellis", "sora_ht40_process_dev",
                       "sora_ht40_process_captures_dev", "sora_ht40_results", "sora_ht40_ticket", "sora_ht40_calls_in_flight", "sora_ht40_wait", "sora_ht40_wait_any",
                       "sora_ht40_stream_of", "sora_ht40_results_of",
@@ -236,6 +236,7 @@ def load(build_if_missing=True):
     L.sora_rx11n_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11n_process.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11n_set_depth.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.sora_rx11n_set_mcs_max.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.sora_rx11n_results.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
                                      ctypes.c_void_p, ctypes.c_size_t]
     L.sora_rx11b_create.argtypes = [ctypes.POINTER(RxCfg), ctypes.POINTER(ctypes.c_void_p)]
@@ -667,6 +668,12 @@ class Rx11n(_Handle):
     def trellis(self):
         """the trellis kernel the next call uses: 64, 16 or 1 (TRELLIS_WINDOWED)"""
         return int(self._L.sora_rx11n_trellis(self._h))
+
+    def set_mcs_max(self, mcs_max=-1):
+        """the highest MCS the SIG parser accepts: 10 (default: the reference's gate) .. 14; returns the previous value (sora_hip.h: sora_rx11n_set_mcs_max)"""
+        r = int(self._L.sora_rx11n_set_mcs_max(self._h, int(mcs_max)))
+        if r < 0: _check(r)
+        return r
 
     def window_stats(self):
         v = (ctypes.c_ulonglong * 4)()

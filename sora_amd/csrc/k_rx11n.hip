@@ -92,7 +92,13 @@ struct Scan11nArgs {
     VitJob*   jobs;                // [3][nrows], same order
     uint32_t* njobs;               // [3]
     uint32_t  nrows;
+    // sora_rx11n_set_mcs_max: the highest MCS the SIG parser accepts (10 = PHY_11n.hpp:497), and the handle's bytes per symbol slot (soft values / decoded bytes)
+    uint32_t  mcs_max, soft_per_slot, out_per_slot;
 };
+// A symbol slot of the 802.11n handle: kSoftPerSlot / kOutPerSlot (rx_types.h) while the gate stands at MCS 10 (208 soft values, 19.5 decoded bytes per symbol at
+// most); with the gate raised a symbol brings up to 624 soft values and 58.5 decoded bytes (MCS 14)
+constexpr uint32_t kSoftPerSlot11nWide = 640, kOutPerSlot11nWide = 64;
+__host__ __device__ inline uint32_t nbpsc11n(uint32_t mcs) { return mcs == 8 ? 1u : mcs <= 10 ? 2u : mcs <= 12 ? 4u : 6u; }   // rate_selector (fb11ndemod_config.hpp:136-147)
 struct Frame11nArgs {
     const uint32_t* iq0; const uint32_t* iq1; const CapDesc* caps;
     const N11Frame* frames; const uint32_t* njobs; uint32_t nrows;
@@ -101,6 +107,7 @@ struct Frame11nArgs {
     VitJob*   jobs;                // [3][nrows]: k_frame11n fills in the pair stream's offset (the mate is known only after the scan)
     const uint8_t* vout;           // [slots * 32]
     Rx11bRow* rows; uint8_t* mpdu;
+    uint32_t soft_per_slot, out_per_slot;
 };
 
 namespace {
@@ -122,9 +129,7 @@ struct FrameLds {
     uint32_t y[2][128];
     uint32_t hinv[4][64];
     uint32_t xs[2][64];
-    uint8_t  soft[2][160];
-    alignas(4) uint8_t joined[256];
-    uint8_t  dtab[208];
+    uint8_t  soft[2][320];         // the two streams' demapped symbol: up to 52 x 6 values each
 };
 // stream continuation (sora_rx11n_set_stream_mode): the carrier-sense rings at the latest resume point in front of a detection (k_scan11n_stream)
 struct RingLds {                   // the same layout as the head of ScanLds
@@ -467,9 +472,9 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
                     if (mc < 8 || mc > 14 || !((ht >> 7) & 1) || hl > 4000 || hl < 4) break;     // two streams, 40 MHz, a rate this library has a decoder for
                     mcs = mc; ht_len = hl; code_rate = (mc == 10 || mc == 12 || mc == 14) ? 2u : mc == 13 ? 1u : 0u;
                 } else {
-                    if (mc < 8 || mc >= 11) break;
+                    if (mc < 8 || mc > A.mcs_max) break;                                           // (mcs_max = 10: the reference's ht_frame_mcs >= 11)
                     if (hl > 1500) break;
-                    mcs = mc; ht_len = hl; code_rate = mc == 10 ? 2u : 0u;
+                    mcs = mc; ht_len = hl; code_rate = (mc == 10 || mc == 12 || mc == 14) ? 2u : mc == 13 ? 1u : 0u;
                 }
                 sig_ok = true;
             } while (0);
@@ -493,7 +498,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
             // HT-STF at a, HT-LTF at a + 80 / a + 160, data symbol d at a + 240 + 80 d; a symbol is processed when it starts inside the
             // padded capture (its missing samples read as zero: the flush of the partly filled queues)
             const uint32_t tr_end = ht_len * 8 + 16 + 6;
-            const uint32_t S = mcs == 8 ? 104u : 208u, sps = code_rate == 0 ? S / 2 : S / 4 * 3;     // soft values / trellis steps per symbol
+            const uint32_t S = 104u * nbpsc11n(mcs), sps = code_rate == 0 ? S / 2 : code_rate == 1 ? S / 3 * 2 : S / 4 * 3;   // soft values / trellis steps per symbol
             const uint32_t nsym = (tr_end + sps - 1) / sps;                  // the symbol in which the decoder passes tr_end
             const uint32_t a_data = a + 240;
             if constexpr (STREAM) {                                          // all of the data field inside the capture, or no event (and no flush)
@@ -504,9 +509,10 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
             if (nproc == nsym) { event = true; queue = true; nsoft = nsym * S; last_burst_end = min(a_data + 80 * nsym, n_pad); }
             else if (a + 160 < n_pad && nproc > 0 && (nproc * S) % 312 != 0) {
                 // the capture ends inside the data field: T11aViterbi's 312-value input burst is padded with zero soft values; an
-                // event only if that takes the decoder past tr_end
+                // event only if that takes the decoder past tr_end.  (64-QAM: a symbol is two whole bursts, the decoder holds nothing back and
+                // a cut frame raises no event; 16-QAM: a symbol is a burst and a third, as QPSK's is two thirds.)
                 nsoft = (nproc * S + 311) / 312 * 312;
-                const uint32_t steps = code_rate == 0 ? nsoft / 2 : nsoft / 4 * 3;
+                const uint32_t steps = code_rate == 0 ? nsoft / 2 : code_rate == 1 ? nsoft / 3 * 2 : nsoft / 4 * 3;
                 if (steps >= tr_end) { event = true; queue = true; last_burst_end = n_pad; }
             }
             }
@@ -532,8 +538,8 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
                     F.nproc = nproc; F.nsoft = nsoft; F.slot0 = cd.slot_base + (origin + a + 240) / 80;
                     for (int k = 0; k < 6; k++) F.pad[k] = 0;
                     A.frames[(size_t)list * A.nrows + idx] = F;
-                    VitJob J; J.soft_off = F.slot0 * (uint32_t)kSoftPerSlot; J.soft_bits = 8; J.nsoft = nsoft; J.length = ht_len; J.dec_off = 0;
-                        J.out_off = F.slot0 * (uint32_t)kOutPerSlot;
+                    VitJob J; J.soft_off = F.slot0 * A.soft_per_slot; J.soft_bits = 8; J.nsoft = nsoft; J.length = ht_len; J.dec_off = 0;
+                        J.out_off = F.slot0 * A.out_per_slot;
                     J.valid = 1; J.code_rate = code_rate;
                     A.jobs[(size_t)list * A.nrows + idx] = J;
                 }
@@ -583,6 +589,7 @@ int sora_internal_scan_ht40(const uint32_t* iq0, const uint32_t* iq1, const sora
     Scan11nArgs S{};
     S.iq0 = iq0; S.iq1 = iq1; S.caps = d_caps; S.ncaps = ncaps; S.max_frames = max_frames; S.rows = d_rows; S.nframes = d_nframes; S.T = T; S.sincos = sincos; S.atan = atan;
     S.frames = nullptr; S.jobs = nullptr; S.njobs = nullptr; S.nrows = ncaps * max_frames;
+    S.mcs_max = 14; S.soft_per_slot = 0; S.out_per_slot = 0;                     // (the HT40 form has its own gate and queues no 20 MHz data field)
     hipLaunchKernelGGL(k_scan_ht40, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SORA_OK : sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "k_scan_ht40", (int)e);
@@ -609,11 +616,16 @@ __global__ void __launch_bounds__(256) k_frame11n(Frame11nArgs A)
     auto nosync = []() __attribute__((always_inline)) { wsync(); };
     const int cfo = uni(F.cfo);
     const uint32_t l0 = (uint32_t)uni((int)F.l0), mcs = (uint32_t)uni((int)F.mcs), nproc = (uint32_t)uni((int)F.nproc);
-    const int nb = mcs == 8 ? 1 : 2;
-    // joined position g = lane + 64 t (stream g & 1 = lane & 1) <- soft[lane & 1][dt[t]]: the lane's four de-interleaver entries stay in registers
-    uint32_t dt[4];
+    const int nb = (int)nbpsc11n(mcs);
+    // TStreamJoin<2, 52 nb> -> TStreamConcat<2, s>, s = max(nb / 2, 1): joined position g = lane + 64 t takes element (g / 2s) s + g % s of stream (g / s) & 1,
+    // that is soft[stream][deint11n_index]: the lane's de-interleaver entries (offset into W.soft, ten at most: 624 positions) stay in registers
+    const int scat = nb >= 4 ? nb / 2 : 1;
+    uint32_t dt[10];
 #pragma unroll
-    for (int t = 0; t < 4; t++) { const int g = lane + 64 * t; dt[t] = g < 104 * nb ? (uint32_t)deint11n_index(nb, g & 1, g >> 1) : 0xFFFFFFFFu; }
+    for (int t = 0; t < 10; t++) {
+        const int g = lane + 64 * t, iss = (g / scat) & 1, k = g / (2 * scat) * scat + g % scat;
+        dt[t] = g < 104 * nb ? (uint32_t)(320 * iss + deint11n_index(nb, iss, k)) : 0xFFFFFFFFu;
+    }
     int theta = 0;
     // one symbol at 20 MHz index `pos` (its CP included): TFreqComp_11n (running phase n * CFO - theta, n counted from the L-LTF), two FFTs -> W.y[.][64 * half ..]
     auto symbol_fft = [&](uint32_t pos, uint32_t x0, uint32_t x1, int half) __attribute__((always_inline)) {
@@ -666,7 +678,7 @@ __global__ void __launch_bounds__(256) k_frame11n(Frame11nArgs A)
     const uint32_t a_data = a_ltf + 160;
     const uint32_t S = 104u * (uint32_t)nb;
     // the frame's soft stream, one byte per value (VitJob::soft_bits = 8), in its own symbol slots
-    uint8_t* dst = A.soft + (size_t)F.slot0 * kSoftPerSlot;
+    uint8_t* dst = A.soft + (size_t)F.slot0 * A.soft_per_slot;
     uint32_t nx0 = fetch(0, a_data + 16 + lane), nx1 = fetch(1, a_data + 16 + lane);     // the next symbol's samples are requested one symbol ahead
     for (uint32_t d = 0; d < nproc; d++) {
         const uint32_t pos = a_data + 80 * d;
@@ -695,16 +707,23 @@ __global__ void __launch_bounds__(256) k_frame11n(Frame11nArgs A)
             for (int s = 0; s < 2; s++) {
                 const cpx x = unpack(W.xs[s][data_bin(lane)]);
                 const int re = min(max(x.re, -128), 127) + 128, im = min(max(x.im, -128), 127) + 128;
-                if (nb == 1) W.soft[s][lane] = s_lut[0][re];
-                else { W.soft[s][2 * lane] = s_lut[0][re]; W.soft[s][2 * lane + 1] = s_lut[0][im]; }
+                uint8_t* o = W.soft[s] + nb * lane;                           // T11nDemap{BPSK,QPSK,QAM16,QAM64} (demapper11n.hpp:89-309), as k_demap11n_batch
+                if (nb == 1) o[0] = s_lut[0][re];
+                else if (nb == 2) { o[0] = s_lut[0][re]; o[1] = s_lut[0][im]; }
+                else if (nb == 4) { o[0] = s_lut[1][re]; o[1] = s_lut[2][re]; o[2] = s_lut[1][im]; o[3] = s_lut[2][im]; }
+                else { o[0] = s_lut[3][re]; o[1] = s_lut[4][re]; o[2] = s_lut[5][re]; o[3] = s_lut[3][im]; o[4] = s_lut[4][im]; o[5] = s_lut[5][im]; }
             }
         }
         wsync();
         {
-            const uint8_t* mine = W.soft[lane & 1];
+            const uint8_t* both = W.soft[0];
             uint8_t* o = dst + (size_t)d * S + lane;
 #pragma unroll
-            for (int t = 0; t < 4; t++) if (dt[t] != 0xFFFFFFFFu) o[64 * t] = mine[dt[t]];
+            for (int t = 0; t < 4; t++) if (dt[t] != 0xFFFFFFFFu) o[64 * t] = both[dt[t]];
+            if (nb >= 4) {                                                   // 16-QAM: 416 positions, 64-QAM: 624
+#pragma unroll
+                for (int t = 4; t < 10; t++) if (dt[t] != 0xFFFFFFFFu) o[64 * t] = both[dt[t]];
+            }
         }
         wsync();
     }
@@ -724,7 +743,7 @@ __global__ void __launch_bounds__(256) k_finish11n(Frame11nArgs A)
     const JobRef jr = locate_job(blockIdx.x * 4 + wv, A.njobs);
     if (!jr.ok) return;
     const N11Frame F = A.frames[(size_t)jr.list * A.nrows + jr.idx];
-    const uint8_t* dec = A.vout + (size_t)F.slot0 * kOutPerSlot;
+    const uint8_t* dec = A.vout + (size_t)F.slot0 * A.out_per_slot;
     uint8_t* mp = A.mpdu + (size_t)F.row * 4096;
     uint8_t* bytes = reinterpret_cast<uint8_t*>(s_bufs[wv]);
     const uint32_t L = F.ht_len;
@@ -776,6 +795,8 @@ struct sora_rx11n {
     // frames in flight (one wave-slot per frame leaves the chip idle: a lone capture's 8000-step frame was 0.23 ms of a 0.37 ms call), k_viterbi11n above that
     TrellisChoice trellis;
     uint64_t cap_slots = 0;
+    // sora_rx11n_set_mcs_max: the SIG parser's gate and the symbol-slot geometry that goes with it (a handle left at the default allocates what it always did)
+    int mcs_max = 10; uint32_t soft_per_slot = kSoftPerSlot, out_per_slot = kOutPerSlot;
     static constexpr int kMaxDepth = 8;
     Pipe11n* pipes[kMaxDepth] = {};
     int depth = 1, cur = 0, next_ticket = 0; bool started = false;
@@ -801,6 +822,17 @@ static void rx11n_free(sora_rx11n_t* rx)
     (void)hipFree(rx->d_iq_own[0]); (void)hipFree(rx->d_iq_own[1]); rx->records.free();
     delete rx;
 }
+// the soft streams and decoded bytes of one pipeline, in the handle's slot geometry; every byte starts out defined: the decoder reads its soft stream in 12-step
+// chunks (the tail of a frame's last chunk is read, never used)
+static hipError_t pipe11n_slots(const sora_rx11n_t* rx, hipStream_t st, uint8_t** d_soft, uint8_t** d_vout)
+{
+    const size_t nsoft = (size_t)rx->cap_slots * rx->soft_per_slot + kSoftSlack, nout = (size_t)rx->cap_slots * rx->out_per_slot + 256;
+    hipError_t e = hipMalloc((void**)d_soft, nsoft);
+    if (e == hipSuccess) e = hipMalloc((void**)d_vout, nout);
+    if (e == hipSuccess) e = hipMemsetAsync(*d_soft, 0, nsoft, st);
+    if (e == hipSuccess) e = hipMemsetAsync(*d_vout, 0, nout, st);
+    return e;
+}
 static hipError_t pipe11n_create(sora_rx11n_t* rx, Pipe11n** out, int index = 0)
 {
     const sora_rx_cfg* cfg = &rx->cfg;
@@ -814,13 +846,9 @@ static hipError_t pipe11n_create(sora_rx11n_t* rx, Pipe11n** out, int index = 0)
     if (e == hipSuccess) e = hipMalloc((void**)&p->d_frames, 3 * sizeof(N11Frame) * rows);
     if (e == hipSuccess) e = hipMalloc((void**)&p->d_jobs, 3 * sizeof(VitJob) * rows);
     if (e == hipSuccess) e = hipMalloc((void**)&p->d_njobs, 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&p->d_soft, (size_t)rx->cap_slots * kSoftPerSlot + kSoftSlack);
-    if (e == hipSuccess) e = hipMalloc((void**)&p->d_vout, (size_t)rx->cap_slots * kOutPerSlot + 256);
-    // every array starts out defined: the decoder reads its soft stream in 12-step chunks (the tail of a frame's last chunk is read, never used)
+    if (e == hipSuccess) e = pipe11n_slots(rx, p->stream, &p->d_soft, &p->d_vout);
     if (e == hipSuccess) {
         (void)hipMemsetAsync(p->d_frames, 0, 3 * sizeof(N11Frame) * rows, p->stream); (void)hipMemsetAsync(p->d_jobs, 0, 3 * sizeof(VitJob) * rows, p->stream);
-        (void)hipMemsetAsync(p->d_soft, 0, (size_t)rx->cap_slots * kSoftPerSlot + kSoftSlack, p->stream); (void)hipMemsetAsync(p->d_vout, 0,
-                (size_t)rx->cap_slots * kOutPerSlot + 256, p->stream);
     }
     if (e == hipSuccess) { (void)hipMemsetAsync(p->d_rows, 0, sizeof(Rx11bRow) * rows, p->stream); (void)hipMemsetAsync(p->d_nframes, 0,
             4 * (size_t)cfg->max_captures, p->stream); }
@@ -838,7 +866,7 @@ int sora_rx11n_create(const sora_rx_cfg* cfg, sora_rx11n_t** out)
         return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "sora_rx11n_create: tables", 0); }
     // symbol slots: 80 samples at 20 MHz each, + 4 per capture (the decoder's padded last burst and its chunked reads may reach past the last symbol)
     rx->cap_slots = cfg->max_total_samples / 2 / 80 + 4 * (uint64_t)cfg->max_captures + 4;
-    if (rx->cap_slots * (uint64_t)kSoftPerSlot * 2 >= (1ull << 32)) { rx11n_free(rx); return sora_internal_fail(SORA_ERR_CAPACITY,
+    if (rx->cap_slots * (uint64_t)rx->soft_per_slot * 2 >= (1ull << 32)) { rx11n_free(rx); return sora_internal_fail(SORA_ERR_CAPACITY,
             "sora_rx11n_create: max_total_samples exceeds the 32-bit slot geometry of one handle (split the batch over several handles)", 0); }
     const hipError_t e = pipe11n_create(rx, &rx->pipes[0]);
     if (e != hipSuccess) { rx11n_free(rx); return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "sora_rx11n_create: device allocation", (int)e); }
@@ -863,6 +891,39 @@ int sora_rx11n_set_depth(sora_rx11n_t* rx, int depth)
     // fall outside it become stale, as the header says)
     if (rx->cur >= depth) { std::swap(rx->pipes[0], rx->pipes[rx->cur]); rx->cur = 0; }
     rx->depth = depth;
+    return prev;
+}
+
+int sora_rx11n_set_mcs_max(sora_rx11n_t* rx, int mcs_max)
+{
+    if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_set_mcs_max: null handle", 0);
+    const int prev = rx->mcs_max;
+    if (mcs_max <= 0) return prev;
+    if (mcs_max < 10 || mcs_max > 14) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11n_set_mcs_max: the gate is 10 (the reference's) .. 14", 0);
+    { const int rc = sora_rx11n_synchronize(rx); if (rc) return rc; }
+    const bool wide = mcs_max > 10;
+    const uint32_t soft_per_slot = wide ? kSoftPerSlot11nWide : (uint32_t)kSoftPerSlot, out_per_slot = wide ? kOutPerSlot11nWide : (uint32_t)kOutPerSlot;
+    if (soft_per_slot != rx->soft_per_slot) {
+        if (rx->cap_slots * (uint64_t)soft_per_slot * 2 >= (1ull << 32)) return sora_internal_fail(SORA_ERR_CAPACITY,
+                "sora_rx11n_set_mcs_max: max_total_samples exceeds the 32-bit slot geometry of one handle at this gate (split the batch over several handles)", 0);
+        // the pipelines' slot arrays in the new geometry: all of them made before any is replaced, so that a failure leaves the handle as it was
+        const uint32_t old_soft = rx->soft_per_slot, old_out = rx->out_per_slot;
+        uint8_t* ns[sora_rx11n::kMaxDepth] = {}; uint8_t* nv[sora_rx11n::kMaxDepth] = {};
+        rx->soft_per_slot = soft_per_slot; rx->out_per_slot = out_per_slot;
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < sora_rx11n::kMaxDepth && e == hipSuccess; i++) if (rx->pipes[i]) e = pipe11n_slots(rx, rx->pipes[i]->stream, &ns[i], &nv[i]);
+        if (e != hipSuccess) {
+            for (int i = 0; i < sora_rx11n::kMaxDepth; i++) { (void)hipFree(ns[i]); (void)hipFree(nv[i]); }
+            rx->soft_per_slot = old_soft; rx->out_per_slot = old_out;
+            return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "sora_rx11n_set_mcs_max: device allocation", (int)e);
+        }
+        for (int i = 0; i < sora_rx11n::kMaxDepth; i++) if (rx->pipes[i]) {
+            (void)hipFree(rx->pipes[i]->d_soft); (void)hipFree(rx->pipes[i]->d_vout);
+            rx->pipes[i]->d_soft = ns[i]; rx->pipes[i]->d_vout = nv[i];
+        }
+    }
+    if (rx->records.on) { const int rc = rx->records.zero(rx->cfg.max_captures); if (rc) return rc; }     // every stream starts afresh
+    rx->mcs_max = mcs_max;
     return prev;
 }
 
@@ -966,11 +1027,13 @@ int sora_rx11n_process_dev(sora_rx11n_t* rx, const sora_complex16* d_iq0, const 
     Scan11nArgs S;
     S.iq0 = A.iq0; S.iq1 = A.iq1; S.caps = P->d_caps; S.ncaps = (uint32_t)ncaps; S.max_frames = A.max_frames; S.rows = P->d_rows; S.nframes = P->d_nframes;
     S.T = rx->T; S.sincos = rx->sincos; S.atan = rx->atan; S.frames = P->d_frames; S.jobs = P->d_jobs; S.njobs = P->d_njobs; S.nrows = nrows;
+    S.mcs_max = (uint32_t)rx->mcs_max; S.soft_per_slot = rx->soft_per_slot; S.out_per_slot = rx->out_per_slot;
     if (rx->records.on) hipLaunchKernelGGL(k_scan11n_stream, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S, rx->records.d_cont, rx->records.d_consumed);
     else hipLaunchKernelGGL(k_scan11n, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S);
     Frame11nArgs F;
     F.iq0 = A.iq0; F.iq1 = A.iq1; F.caps = P->d_caps; F.frames = P->d_frames; F.njobs = P->d_njobs; F.nrows = nrows; F.T = rx->T; F.sincos = rx->sincos; F.atan = rx->atan;
     F.soft = P->d_soft; F.jobs = P->d_jobs; F.vout = P->d_vout; F.rows = P->d_rows; F.mpdu = P->d_mpdu;
+    F.soft_per_slot = rx->soft_per_slot; F.out_per_slot = rx->out_per_slot;
     hipLaunchKernelGGL(k_frame11n, dim3((nrows + 3) / 4), dim3(256), 0, P->stream, F);
     const Trellis trellis = trellis11n_for(rx);
     // (the window-parallel trellis's arrays on its first use: its counters are zeroed in this call's stream, in front of its proof)
