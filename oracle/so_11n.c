@@ -183,16 +183,21 @@ int16_t so_dsp_atan16(int16_t x, int16_t y)                               /* dsp
     srad ^= sign; srad = (int16_t)(srad - sign);
     return srad;
 }
-int16_t so_dsp_atan32(int32_t x, int32_t y)                               /* dsp_math::atan(int, int) */
+/* dsp_math::atan(int, int).  Its imax() forms x + y + |x - y| = 2 max(x, y) in int, which overflows once either magnitude reaches 2^30 -- undefined
+ * in C++.  The compiled reference does not wrap there: tmax and tmin only feed the __int64 division, so the sum is formed 64 bits wide and tmax, tmin
+ * are the exact larger and smaller magnitude (TFreqEstimator_11n reaches this on an L-LTF near the int16 rails: 128 products >> 7 add up to 2 |x|^2).
+ * Where abs() itself overflows (x = INT_MIN) the compiled reference was measured over 12000 arguments: it returns 0 at (INT_MIN, 0) and at
+ * (INT_MIN, INT_MIN) -- the latter is what an L-LTF of nothing but -32768 sums to -- and what the arithmetic below gives everywhere else. */
+int16_t so_dsp_atan32(int32_t x, int32_t y)
 {
     dsp_init();
+    if (x == INT32_MIN && (y == 0 || y == INT32_MIN)) return 0;
     const int16_t sign = (int16_t)(((x ^ y) >> 31) & 0xFFFF);
     const int32_t absx = iabs32(x), absy = iabs32(y);
     const int16_t tsign = (int16_t)((so_w32((int64_t)absx - absy) >> 31) & 0xFFFF);
-    int32_t tmax = absx, tmin = absy; const int32_t tsum = so_w32((int64_t)tmax + tmin);
-    tmax = imax32(tmax, tmin); tmin = so_w32((int64_t)tsum - tmax);
-    int64_t i64x = (int64_t)tmin << 16, i64y = tmax;
-    if (i64y == 0) i64y = 1;
+    const int64_t tsum = (int64_t)absx + absy, d = (int64_t)absx - absy;
+    const int64_t tmax = (tsum + (d < 0 ? -d : d)) >> 1, tmin = tsum - tmax;
+    const int64_t i64x = tmin * 65536, i64y = tmax == 0 ? 1 : tmax;
     int idx = (int)((i64x + (i64y >> 1)) / i64y);
     idx >>= 4;
     if (idx < 0 || idx >= 4097) return 0;

@@ -130,15 +130,19 @@ __device__ __forceinline__ int dsp_atan16(const short* tab, int x, int y)      /
     } else idx = (int)(((unsigned)tmin << 16) + (unsigned)(tmax >> 1)) / tmax;
     return atan_tail(tab, idx >> 4, tsign, sign);
 }
-__device__ __forceinline__ int dsp_atan32(const short* tab, int x, int y)      // dsp_math::atan(int, int), for |x| + |y| < 2^31
+// dsp_math::atan(int, int).  The reference's imax() forms 2 max(|x|, |y|) in int, which overflows from 2^30 on; its compiled code forms that sum 64 bits
+// wide (it only feeds the __int64 division), so tmax / tmin are the exact larger / smaller magnitude.  An L-LTF near the int16 rails gets there: the 128
+// products >> 7 of TFreqEstimator_11n add up to 2 |x|^2.  x = INT_MIN: 0 at y = 0 and y = INT_MIN as measured on the compiled reference (oracle/so_11n.c).
+__device__ __forceinline__ int dsp_atan32(const short* tab, int x, int y)
 {
+    if (x == (int)0x80000000 && (y == 0 || y == (int)0x80000000)) return 0;
     const int sign = (int)(short)(((x ^ y) >> 31) & 0xFFFF);
-    const int absx = (x ^ (x >> 31)) - (x >> 31), absy = (y ^ (y >> 31)) - (y >> 31);
-    const int tsign = (int)(short)(((absx - absy) >> 31) & 0xFFFF);
-    const int tsum = absx + absy, d = absx - absy;
-    const int tmax = (tsum + ((d ^ (d >> 31)) - (d >> 31))) >> 1, tmin = tsum - tmax;
+    const int absx = (int)(((unsigned)x ^ (unsigned)(x >> 31)) - (unsigned)(x >> 31)), absy = (int)(((unsigned)y ^ (unsigned)(y >> 31)) - (unsigned)(y >> 31));
+    const int tsign = (int)(short)(((int)((unsigned)absx - (unsigned)absy) >> 31) & 0xFFFF);
+    const long long tsum = (long long)absx + absy, d = (long long)absx - absy;
+    const long long tmax = (tsum + (d < 0 ? -d : d)) >> 1, tmin = tsum - tmax;
     const long long i64y = tmax == 0 ? 1 : tmax;
-    const int idx = (int)((((long long)tmin << 16) + (i64y >> 1)) / i64y);
+    const int idx = (int)((tmin * 65536 + (i64y >> 1)) / i64y);
     return atan_tail(tab, idx >> 4, tsign, sign);
 }
 

@@ -19,6 +19,10 @@
   trellis_adversarial.npz  a subset of the adversarial soft streams of tests/trellis_streams.py at every code rate and what the reference's
                          TViterbiCore makes of them under both trace-back schedules, 256 / 24 and 192 / 36 (`python make_golden.py trellis`
                          writes only this file).
+  refgraph_levels.npz    the capture families of tests/level_captures.py (overdriven, DC-shifted, near-silent, rails; 802.11a at 40 and 44 MHz, 802.11b,
+                         802.11n 2x2): per capture a sha256 of the regenerated int16 samples and the events of the compiled reference graph -- code, source
+                         position, rate or MCS, length, FCS word, first 8 bytes of the MPDU's sha256 (`python make_golden.py levels` writes only this file
+                         and prints the per-family counts quoted in the helper's docstring).
 All files travel to the GPU box; /root/reference does not.
 """
 import hashlib
@@ -86,7 +90,25 @@ def record_trellis(R):
     np.savez_compressed(os.path.join(OUT, "trellis_adversarial.npz"), **v)
 
 
+def record_levels():
+    import level_captures as lc
+    O = Oracle(); G = ReferenceGraph()
+    assert G.available(), "build oracle/_ref first (oracle/build_ref.sh)"
+    v = {}
+    for ch in lc.CHAINS:
+        caps = lc.chain(ch, O)
+        ev = [lc.run_reference(G, ch, c) for c in caps]
+        v.update(lc.pack(ch, caps, ev))
+        for fam, n in lc.census(caps, ev).items():
+            print("  %-6s %-10s %3d captures, %3d with a frame, %3d without an event; events %s" % (
+                ch, fam, n["captures"], n["framed"], n["mute"], ", ".join("%#x: %d" % kv for kv in sorted(n["codes"].items()))))
+    np.savez_compressed(lc.FIXTURE, **v)
+
+
 def main():
+    if sys.argv[1:] == ["levels"]:
+        record_levels()
+        return
     if sys.argv[1:] == ["trellis"]:
         R = Reference(); assert R.available(), "build oracle/_ref first (oracle/build_ref.sh)"
         record_trellis(R)

@@ -83,6 +83,69 @@ def test_oracle_phase_bricks(o):
     assert len(set(z["cfo_state"][:, 1].tolist())) > 4                     # the recorded offsets really differ
 
 
+def _atan32_exact(table, x, y):
+    """dsp_math::atan(int, int) in unbounded integers: the quotient min(|x|, |y|) / max(|x|, |y|) looked up in the 4097-entry table, folded into the octant"""
+    sign = -1 if (x < 0) != (y < 0) else 0
+    ax, ay = abs(x), abs(y)
+    tsign = -1 if ax < ay else 0
+    big, small = max(ax, ay), min(ax, ay)
+    idx = ((small << 16) + (max(big, 1) >> 1)) // max(big, 1) >> 4
+    if idx >= 4097:
+        return 0
+    s = (int(table[idx]) ^ tsign) - tsign + (16384 & tsign)
+    s = (s + 32768) % 65536 - 32768
+    return ((s ^ sign) - sign + 32768) % 65536 - 32768
+
+
+def test_oracle_cfo_estimate_of_a_full_scale_lltf(o):
+    """TFreqEstimator_11n sums 128 products >> 7: on an L-LTF near the int16 rails the sum passes 2^30, where dsp_math::atan(int, int)'s imax() overflows
+    int.  The compiled reference forms that sum 64 bits wide, so its arctangent stays the exact one; a restatement that wraps at 32 bits returns 0 there
+    (the table index falls out of range) and loses the carrier offset of exactly the frames that clip.  Three checks: the oracle's atan against unbounded
+    integer arithmetic over the whole int32 range (the reference's own function live, where oracle/_ref is built); constant L-LTFs whose second half is the
+    first turned by exactly 90 degrees, which must estimate +-16384 >> 6 = +-256 per 64 samples whatever the table holds -- |a|^2 = 2^30 x 1.01, 1.19 and 2.00
+    in the first four rows, so each of them reproduces the fault (the sum of the 128 products >> 7 is |a|^2), and 0.84 in the last, which stays below it --;
+    and the reference's brick on coherent full-scale L-LTFs."""
+    import ctypes
+    o.L.so_dsp_atan32.restype = ctypes.c_int16
+    o.L.so_dsp_atan_table.restype = ctypes.POINTER(ctypes.c_int16)
+    table = np.ctypeslib.as_array(o.L.so_dsp_atan_table(), shape=(4097,)).copy()
+    g = ReferenceGraph()
+    rng = np.random.default_rng(30)
+    edge = [0, 1, -1, 65536, -65536, 2 ** 30 - 1, 2 ** 30, 2 ** 30 + 1, -2 ** 30, -2 ** 30 - 1, 3 * 2 ** 29, -3 * 2 ** 29, 2 ** 31 - 1, -2 ** 31 + 1]
+    pairs = [(x, y) for x in edge for y in edge] + [tuple(int(v) for v in rng.integers(-2 ** 31 + 1, 2 ** 31, 2)) for _ in range(20000)]
+    pairs += [(int(x), int(y) >> int(sh)) for (x, y), sh in zip(rng.integers(-2 ** 31 + 1, 2 ** 31, size=(5000, 2)), rng.integers(0, 31, 5000))]
+    beyond = 0
+    for x, y in pairs:
+        want = _atan32_exact(table, x, y)
+        assert o.L.so_dsp_atan32(x, y) == want, (x, y)
+        if g.available():
+            assert ctypes.c_int16(g.L.ref_dsp_atan(x, y, 1)).value == want, (x, y)
+        beyond += max(abs(x), abs(y)) >= 2 ** 30
+    assert beyond > 5000
+    if g.available():                                                      # x = INT_MIN, where abs() itself overflows: only the compiled reference can say
+        for y in [0, 1, -1, 65536, 2 ** 30, -2 ** 30, 2 ** 31 - 1, -2 ** 31] + [int(v) for v in rng.integers(-2 ** 31, 2 ** 31, 500)]:
+            for a, b in ((-2 ** 31, y), (y, -2 ** 31)):
+                assert o.L.so_dsp_atan32(a, b) == ctypes.c_int16(g.L.ref_dsp_atan(a, b, 1)).value, (a, b)
+    for a, turns, want in (((32000, 8000), 1, -256), ((32000, 8000), 3, 256), ((-21000, 29000), 1, -256), ((32767, 32767), 3, 256), ((30000, 1000), 0, 0)):
+        assert (a[0] ** 2 + a[1] ** 2 >= 2 ** 30) == (turns != 0)
+        first = np.tile(np.array(a, np.int32), (64, 1)); second = first
+        for _ in range(turns):
+            second = np.stack([-second[:, 1], second[:, 0]], 1)                # times j
+        l = np.concatenate([first, second]).astype(np.int16)
+        st = o.cfo_est11n(l, l)
+        assert st[1] == want and st[8] == want * 8 and (st[:8] == want * np.arange(8)).all(), (a, turns, st[:9].tolist())
+    if g.available():
+        for t in range(300):
+            amp = (32767, 30000, 26000, 23000)[t % 4]
+            a = rng.integers(-amp, amp + 1, size=(2, 64, 2)); ph = np.exp(1j * rng.uniform(-np.pi, np.pi)); l = []
+            for c in a:                                                        # the second half: the first turned by one angle, so the 128 products add up coherently
+                z = (c[:, 0] + 1j * c[:, 1]) * ph
+                l.append(np.concatenate([c, np.stack([np.clip(np.rint(z.real), -32768, 32767), np.clip(np.rint(z.imag), -32768, 32767)], 1)]).astype(np.int16))
+            if t % 5 == 0:
+                l = [np.where(x < 0, -32768, 32767).astype(np.int16) for x in l]   # rail-only
+            assert np.array_equal(o.cfo_est11n(l[0], l[1]), g.cfo_est11n(l[0], l[1])), t
+
+
 def test_oracle_legacy_preamble_bricks(o):
     """TSisoChannelEst, TSisoChannelComp -> TMrcCombine, T11nSigDemap against recorded reference-brick output, and live where oracle/_ref exists."""
     z = np.load(GOLD)
@@ -226,6 +289,77 @@ def test_gpu_phase_stage_kernels(o):
         t = o.pilot_track11n(t, x0[s], x1[s])
         assert np.array_equal(th[s], t), s
     assert np.array_equal(dstate.cpu().numpy()[1, 16:], t) and np.array_equal(dstate.cpu().numpy()[0, 16:], z["pt_theta"][-1])
+
+
+def _level_inputs(rng, n, shape):
+    """n arrays of int16 `shape`: uniform over +-32767, rail-only (-32768 / 32767), and all-one-rail ones"""
+    x = rng.integers(-32767, 32768, size=(n,) + shape).astype(np.int16)
+    rails = np.array([-32768, 32767], np.int16)
+    x[n // 3:2 * n // 3] = rails[rng.integers(0, 2, size=(2 * n // 3 - n // 3,) + shape)]
+    x[2 * n // 3] = -32768; x[2 * n // 3 + 1] = 32767; x[2 * n // 3 + 2, ..., 0] = -32768; x[2 * n // 3 + 2, ..., 1] = 32767
+    return x
+
+
+@pytest.mark.gpu
+def test_gpu_stage_kernels_at_full_scale_and_on_the_rails(o):
+    """freq_comp11n, mimo_comp11n, siso_comp11n (+ MRC), pilot_track11n and cfo_est11n driven at +-32767 and with rail-only inputs, against the oracle (whose
+    bricks equal the reference's at these amplitudes).  cfo_est11n also on coherent L-LTFs, where the sum of products passes 2^30."""
+    import torch
+    import sora_amd
+    if sora_amd.device_count() <= 0:
+        pytest.skip("no HIP device")
+    rng = np.random.default_rng(32767)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    # TFreqEstimator_11n: full-scale noise, rails, and full-scale L-LTFs whose halves differ by one rotation
+    n = 240
+    l0 = _level_inputs(rng, n, (128, 2)); l1 = _level_inputs(rng, n, (128, 2))
+    for f in range(0, n // 3, 2):
+        for l in (l0, l1):
+            z = (l[f, :64, 0].astype(np.float64) + 1j * l[f, :64, 1]) * np.exp(1j * rng.uniform(-np.pi, np.pi))
+            l[f, 64:, 0] = np.clip(np.rint(z.real), -32768, 32767); l[f, 64:, 1] = np.clip(np.rint(z.imag), -32768, 32767)
+    for f in range(n // 3, n // 2):                                           # rail-only, coherent
+        l0[f, 64:] = l0[f, :64]; l1[f, 64:] = l1[f, :64][:, ::-1]
+    st = sora_amd.cfo_est11n(dev(l0), dev(l1)).cpu().numpy()
+    want = np.stack([o.cfo_est11n(a, b) for a, b in zip(l0, l1)])
+    assert np.array_equal(st, want), np.argwhere((st != want).any(1)).ravel()[:8].tolist()
+    assert len(set(want[:, 1].tolist())) > 40                                # many different offsets, the large ones among them
+    # TFreqComp_11n: 20 bursts per frame, phase steps of every size
+    nf = 60
+    in0 = _level_inputs(rng, nf, (160, 2)); in1 = _level_inputs(rng, nf, (160, 2))
+    state = np.zeros((nf, 24), np.int16)
+    d = rng.integers(-512, 512, size=nf); state[:, :8] = (d[:, None] * np.arange(8)).astype(np.int16); state[:, 8:16] = (d[:, None] * 8).astype(np.int16)
+    state[:, 16:] = rng.integers(-32768, 32768, size=(nf, 1))
+    dstate = dev(state.copy())
+    first = np.arange(nf, dtype=np.int32) * 160; nb = np.full(nf, 20, np.int32)
+    o0, o1 = sora_amd.freq_comp11n(dev(in0.reshape(-1, 2)), dev(in1.reshape(-1, 2)), dev(first), dev(nb), dstate)
+    o0 = o0.cpu().numpy().reshape(nf, 160, 2); o1 = o1.cpu().numpy().reshape(nf, 160, 2); dstate = dstate.cpu().numpy()
+    for f in range(nf):
+        wst, w0, w1 = o.freq_comp11n(state[f], in0[f], in1[f])
+        assert np.array_equal(dstate[f], wst) and np.array_equal(o0[f], w0) and np.array_equal(o1[f], w1), f
+    assert (np.abs(o0.astype(int)) >= 32767).sum() > 1000                      # the saturating pack is at work
+    # TMimoChannelComp and TSisoChannelComp -> TMrcCombine: coefficients and symbols both at full scale
+    nf, ns = 30, 300
+    hinv = _level_inputs(rng, nf, (2, 128, 2)); ch = _level_inputs(rng, nf, (2, 64, 2))
+    y0 = _level_inputs(rng, ns, (64, 2)); y1 = _level_inputs(rng, ns, (64, 2)); fi = rng.integers(0, nf, size=ns).astype(np.int32)
+    x0, x1 = (t.cpu().numpy() for t in sora_amd.mimo_comp11n(dev(hinv), dev(y0), dev(y1), frame_index=dev(fi)))
+    s0, s1, m = (t.cpu().numpy() for t in sora_amd.siso_comp11n(dev(ch), dev(y0), dev(y1), frame_index=dev(fi)))
+    for s_ in range(ns):
+        w0, w1 = o.mimo_comp11n(hinv[fi[s_]], y0[s_], y1[s_])
+        assert np.array_equal(x0[s_], w0) and np.array_equal(x1[s_], w1), s_
+        w = o.siso_comp11n(ch[fi[s_]], y0[s_], y1[s_])
+        assert np.array_equal(s0[s_], w[0]) and np.array_equal(s1[s_], w[1]) and np.array_equal(m[s_], w[2]), s_
+    # TPilotTrack_11n: two frames of 150 symbols, pilots at full scale and on the rails (atan(short, short) with |x| = 32768)
+    ns = 150
+    p0 = _level_inputs(rng, 2 * ns, (64, 2)); p1 = _level_inputs(rng, 2 * ns, (64, 2))
+    state = np.zeros((2, 24), np.int16); state[0, 16:] = 32000; state[1, 16:] = -32768
+    dstate = dev(state.copy())
+    th = sora_amd.pilot_track11n(dev(p0), dev(p1), torch.tensor([0, ns], dtype=torch.int32).cuda(), torch.tensor([ns, ns], dtype=torch.int32).cuda(), dstate).cpu().numpy()
+    for f in range(2):
+        t = state[f, 16:].copy()
+        for s_ in range(f * ns, (f + 1) * ns):
+            t = o.pilot_track11n(t, p0[s_], p1[s_])
+            assert np.array_equal(th[s_], t), s_
+        assert np.array_equal(dstate.cpu().numpy()[f, 16:], t)
 
 
 @pytest.mark.gpu
