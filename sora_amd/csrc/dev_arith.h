@@ -130,6 +130,7 @@ __device__ __forceinline__ void wave_lds_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }            // a value every lane holds alike -> SGPR
 
 // ---------------------------------------------------------------------------------------------
 // 64-point radix-4 DIF FFT (core/inc/fft_r4dif.h) for a group of 16 lanes, 4 points per lane, staged

@@ -1,8 +1,10 @@
-// k_11n.hip -- 802.11n 2x2, stage level: the bricks of the reference's 11n receive graph that exist here
-// so far, as batched per-stage entry points with the brick port shapes (the whole-path graph is not built yet):
+// k_11n.hip -- 802.11n 2x2, stage level: the bricks of the reference's 11n receive graph as batched per-stage entry points with
+// the brick port shapes (sora_hip_*11n).  The whole-path graph is k_rx11n.hip, the 40 MHz data field k_ht40.hip; the bricks' arithmetic is stated once, in
+// dev_11n.h, and a kernel here is a brick's piece behind its loads and in front of its stores.
 //   sora_hip_demap11n         T11nDemap{BPSK,QPSK,QAM16,QAM64}        kernel/bb/Brick11/src/demapper11n.hpp:89-309 (dsp_demap.h)
 //   sora_hip_deinterleave11n  T11nDeinterleave{...}_S0 / _S1           kernel/bb/Brick11/src/deinterleaver_11n.hpp:4-1618
-// Both are pure gathers: one coalesced read of a symbol, table look-ups out of LDS, one coalesced write -- HBM-bound.
+//   sora_hip_mimo_est11n / _mimo_comp11n, _siso_est11n / _siso_comp11n, _sig_demap11n / _sig_decode11n, _cfo_est11n / _freq_comp11n, _pilot_track11n
+// Demap and de-interleave are pure gathers: one coalesced read of a symbol, table look-ups out of LDS, one coalesced write -- HBM-bound.
 // The soft-value tables of dsp_demap.h are step functions of the limited coordinate v in [-128,127]; they are regenerated
 // from their run lengths (value, count from v = -128 upward).  The de-interleavers are the standard HT interleaver
 // (N_COL 13, N_ROW 4 N_BPSC, N_ROT 11) inverted, computed per element instead of the reference's unrolled tables.
@@ -22,15 +24,7 @@ __global__ void __launch_bounds__(256) k_demap11n_batch(const uint32_t* in, uint
     const int lane = threadIdx.x & 63;
     const uint32_t sym = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (sym >= n || lane >= 52) return;
-    const cpx x = unpack(in[(size_t)sym * 64 + data_bin(lane)]);
-    const int re = min(max(x.re, -128), 127) + 128, im = min(max(x.im, -128), 127) + 128;      // demap_limit
-    uint8_t* o = soft + ((size_t)sym * 52 + lane) * nb;
-    switch (nb) {
-    case 1: o[0] = s_lut[0][re]; break;
-    case 2: o[0] = s_lut[0][re]; o[1] = s_lut[0][im]; break;
-    case 4: o[0] = s_lut[1][re]; o[1] = s_lut[2][re]; o[2] = s_lut[1][im]; o[3] = s_lut[2][im]; break;
-    default: o[0] = s_lut[3][re]; o[1] = s_lut[4][re]; o[2] = s_lut[5][re]; o[3] = s_lut[3][im]; o[4] = s_lut[4][im]; o[5] = s_lut[5][im];
-    }
+    demap11n_store(soft + ((size_t)sym * 52 + lane) * nb, s_lut, unpack(in[(size_t)sym * 64 + data_bin(lane)]), nb);
 }
 
 // one thread per output soft value
@@ -48,34 +42,18 @@ __global__ void __launch_bounds__(256) k_deint11n_batch(const uint8_t* in, uint8
 
 __global__ void __launch_bounds__(256) k_mimo_est11n_batch(const uint32_t* ltf0, const uint32_t* ltf1, uint32_t* h, uint32_t* hinv, uint32_t nframes)
 {
-#pragma clang fp contract(off)
     const uint32_t f = blockIdx.x * 4 + (threadIdx.x >> 6); const int i = threadIdx.x & 63;
     if (f >= nframes) return;
     const int k = i < 32 ? i : i - 64;
     const bool negate = !(k >= -28 && k <= 28 && kHtLtf[k + 28] == 1);             // _80211n_HTLTFMask: every bin whose HT-LTF value is not +1
-    cpx hh[2][2];
+    const uint32_t* l0 = ltf0 + (size_t)f * 128; const uint32_t* l1 = ltf1 + (size_t)f * 128;
+    cpx hh[2][2]; cf w[4];
+    mimo_h_carrier(unpack(l0[i]), unpack(l0[i + 64]), unpack(l1[i]), unpack(l1[i + 64]), negate, hh);
 #pragma unroll
-    for (int r = 0; r < 2; r++) {
-        const uint32_t* l = (r ? ltf1 : ltf0) + (size_t)f * 128;
-        const cpx a = unpack(l[i]), b = unpack(l[i + 64]);
-        cpx d = sra(csubs(a, b), 1), s = sra(cadds(a, b), 1);                      // P-matrix combination of the two HT-LTFs
-        if (negate) { d = mk(neg16(d.re), neg16(d.im)); s = mk(neg16(s.re), neg16(s.im)); }
-        hh[r][0] = d; hh[r][1] = s;
-        h[((size_t)f * 2 + r) * 128 + i] = pack(d); h[((size_t)f * 2 + r) * 128 + 64 + i] = pack(s);
-    }
-    // 2x2 inverse x 2^16 in single precision, operation for operation as brick/inc/sora_matrix.h:134-148,305-313
-    const cf a00 = { (float)hh[0][0].re, (float)hh[0][0].im }, a01 = { (float)hh[0][1].re, (float)hh[0][1].im };
-    const cf a10 = { (float)hh[1][0].re, (float)hh[1][0].im }, a11 = { (float)hh[1][1].re, (float)hh[1][1].im };
-    const cf ad = cf_mul(a00, a11), bc = cf_mul(a01, a10);
-    const cf det = { ad.re - bc.re, ad.im - bc.im };
-    const float n = ((det.re * det.re) + (det.im * det.im)) / 65536.0f;
-    const cf ds = { det.re, -det.im }, m01 = { -a01.re, -a01.im }, m10 = { -a10.re, -a10.im };
-    const cf r00 = cf_mul(a11, ds), r01 = cf_mul(m01, ds), r10 = cf_mul(m10, ds), r11 = cf_mul(a00, ds);
-    uint32_t* o = hinv + (size_t)f * 256;
-    o[i]       = pack(mk(cvtps_sat16(r00.re / n), cvtps_sat16(r00.im / n)));
-    o[64 + i]  = pack(mk(cvtps_sat16(r01.re / n), cvtps_sat16(r01.im / n)));
-    o[128 + i] = pack(mk(cvtps_sat16(r10.re / n), cvtps_sat16(r10.im / n)));
-    o[192 + i] = pack(mk(cvtps_sat16(r11.re / n), cvtps_sat16(r11.im / n)));
+    for (int r = 0; r < 2; r++) { h[((size_t)f * 2 + r) * 128 + i] = pack(hh[r][0]); h[((size_t)f * 2 + r) * 128 + 64 + i] = pack(hh[r][1]); }
+    mimo_inverse(hh, w);
+#pragma unroll
+    for (int m = 0; m < 4; m++) hinv[(size_t)f * 256 + 64 * m + i] = mimo_weight_pack(w[m]);
 }
 
 // ---- TMimoChannelComp (channel_11n.hpp:445-521): x = (Hinv y) >> 9, saturating pack; one thread per carrier
@@ -86,26 +64,16 @@ __global__ void __launch_bounds__(256) k_mimo_comp11n_batch(const uint32_t* hinv
     if (sidx >= nsym) return;
     const uint32_t* hi = hinv + (size_t)(frame_index ? frame_index[sidx] : 0u) * 256;
     const cpx a = unpack(y0[(size_t)sidx * 64 + i]), b = unpack(y1[(size_t)sidx * 64 + i]);
-    int ar, ai, br, bi;
-    mul32(unpack(hi[i]), a, ar, ai); mul32(unpack(hi[64 + i]), b, br, bi);
-    x0[(size_t)sidx * 64 + i] = pack(mk(sat16((int)((unsigned)ar + (unsigned)br) >> 9), sat16((int)((unsigned)ai + (unsigned)bi) >> 9)));
-    mul32(unpack(hi[128 + i]), a, ar, ai); mul32(unpack(hi[192 + i]), b, br, bi);
-    x1[(size_t)sidx * 64 + i] = pack(mk(sat16((int)((unsigned)ar + (unsigned)br) >> 9), sat16((int)((unsigned)ai + (unsigned)bi) >> 9)));
+    x0[(size_t)sidx * 64 + i] = pack(mimo_comp_row(unpack(hi[i]), unpack(hi[64 + i]), a, b));
+    x1[(size_t)sidx * 64 + i] = pack(mimo_comp_row(unpack(hi[128 + i]), unpack(hi[192 + i]), a, b));
 }
 
-// ---- TSisoChannelEst (channel_11n.hpp:33-231): one thread per (frame, RX chain, carrier).  The rounding term is added lane for lane as
-// the reference's vectors line up: component c of carrier j of a group of four gets |x[(2j + c) mod 4]|^2 >> 1.
+// ---- TSisoChannelEst (channel_11n.hpp:33-231): one thread per (frame, RX chain, carrier)
 __global__ void __launch_bounds__(256) k_siso_est11n_batch(const uint32_t* l0, const uint32_t* l1, uint32_t* ch, uint32_t nframes)
 {
     const uint32_t f = blockIdx.x * 2 + (threadIdx.x >> 7); const int r = (threadIdx.x >> 6) & 1, i = threadIdx.x & 63;
     if (f >= nframes) return;
-    uint32_t out = 0;
-    if (i < 28 || i >= 36) {
-        const uint32_t* l = (r ? l1 : l0) + (size_t)f * 128 + (i & ~3);
-        const cpx a = siso_one(l, i & 3, i), b = siso_one(l + 64, i & 3, i);
-        out = pack(mk((short)((short)(a.re + b.re) >> 1), (short)((short)(a.im + b.im) >> 1)));
-    }
-    ch[(size_t)f * 128 + r * 64 + i] = out;
+    ch[(size_t)f * 128 + r * 64 + i] = siso_est_carrier((r ? l1 : l0) + (size_t)f * 128, i);
 }
 
 // ---- TSisoChannelComp (channel_11n.hpp:233-297) + TMrcCombine (PHY_11n.hpp:362-398): x_r = sat((y_r * c_r) >> 9), mrc = (x_0 + x_1) >> 1
@@ -115,12 +83,11 @@ __global__ void __launch_bounds__(256) k_siso_comp11n_batch(const uint32_t* ch, 
     const uint32_t sidx = blockIdx.x * 4 + (threadIdx.x >> 6); const int i = threadIdx.x & 63;
     if (sidx >= nsym) return;
     const uint32_t* c = ch + (size_t)(frame_index ? frame_index[sidx] : 0u) * 128;
-    int re, im;
-    mul32(unpack(y0[(size_t)sidx * 64 + i]), unpack(c[i]), re, im);      const cpx a = mk(sat16(re >> 9), sat16(im >> 9));
-    mul32(unpack(y1[(size_t)sidx * 64 + i]), unpack(c[64 + i]), re, im); const cpx b = mk(sat16(re >> 9), sat16(im >> 9));
+    cpx a, b;
+    const cpx m = siso_comp_mrc(unpack(y0[(size_t)sidx * 64 + i]), unpack(c[i]), unpack(y1[(size_t)sidx * 64 + i]), unpack(c[64 + i]), a, b);
     if (x0) x0[(size_t)sidx * 64 + i] = pack(a);
     if (x1) x1[(size_t)sidx * 64 + i] = pack(b);
-    if (mrc) mrc[(size_t)sidx * 64 + i] = pack(mk((short)((short)(a.re + b.re) >> 1), (short)((short)(a.im + b.im) >> 1)));
+    if (mrc) mrc[(size_t)sidx * 64 + i] = pack(m);
 }
 
 // ---- T11nSigDemap (demapper11n.hpp:6-87): three symbols per frame, L-SIG on I, HT-SIG 1/2 on Q; one wave per symbol, lane < 48 = carrier
@@ -132,12 +99,7 @@ __global__ void __launch_bounds__(256) k_sig_demap11n_batch(const uint32_t* sym,
     const int lane = threadIdx.x & 63;
     const uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6);                  // symbol number = 3 * frame + s
     if (g >= nframes * 3u || lane >= 48) return;
-    const int s = (int)(g % 3u);
-    int bin;                                                                 // carriers -26..-1 then 1..26 without the pilots
-    if (lane < 24) bin = 38 + lane + (lane >= 5) + (lane >= 18); else { const int m = lane - 24; bin = 1 + m + (m >= 6) + (m >= 19); }
-    const cpx v = unpack(sym[(size_t)g * 64 + bin]);
-    const int q = s == 0 ? v.re : v.im;
-    soft[(size_t)g * 48 + lane] = s_lut[0][min(max(q, -128), 127) + 128];
+    soft[(size_t)g * 48 + lane] = sig_demap_soft(unpack(sym[(size_t)g * 64 + carrier_bin48(lane)]), (int)(g % 3u), s_lut);
 }
 
 // ---- T11aDeinterleaveBPSK x3 -> T11nViterbiSig (viterbi.hpp:51-99) -> T11nSigParser (PHY_11n.hpp:432-513): one wave per frame,
@@ -149,57 +111,42 @@ __global__ void __launch_bounds__(256) k_sig_decode11n_batch(const uint8_t* soft
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint32_t f = blockIdx.x * 4 + w;
     if (f >= nframes) return;                                                // whole waves leave; no block-wide barrier below
-    for (int k = lane; k < 144; k += 64) { const int s3 = k / 48, kk = k - 48 * s3; s_soft[w][k] = soft[(size_t)f * 144 + 48 * s3 + 3 * (kk & 15) + (kk >> 4)]; }
+    for (int k = lane; k < 144; k += 64) { const int s3 = k / 48, kk = k - 48 * s3; s_soft[w][k] = soft[(size_t)f * 144 + 48 * s3 + sig_deint_index(kk)]; }
     __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_wave_barrier();
     const uint32_t lsig = (uint32_t)(viterbi_sig_wave<24>(s_soft[w], s_dec[w], lane) >> 6);
     __builtin_amdgcn_wave_barrier();
     const uint64_t ht = viterbi_sig_wave<48>(s_soft[w] + 48, s_dec[w], lane) >> 6;
     if (lane != 0) return;
-    uint32_t fl[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    // the record: what the parser had extracted when it stopped (the reference's gate: 8 <= MCS < 11, at most 1500 bytes)
+    const SigFront P = sig_parse_front(lsig, ht);
+    uint32_t fl[9] = { 0, P.rate_kbps, P.lsig_len, 0, 0, 0, 0, 0, 0 };
     bool ok = false;
     do {
-        const uint32_t sig = lsig & 0xFFFFFF;
-        if (sig & 0xFC0010) break;
-        if (__popc(sig) & 1) break;
-        const uint32_t code = sig & 0xF;                                     // ieee80211a_cmn.h:97-107
-        fl[1] = code == 0x8 ? 48000u : code == 0x9 ? 24000u : code == 0xA ? 12000u : code == 0xB ? 6000u : code == 0xC ? 54000u
-              : code == 0xD ? 36000u : code == 0xE ? 18000u : code == 0xF ? 9000u : 0u;
-        if (fl[1] == 0) break;
-        fl[2] = ((sig >> 5) & 0xFFF) * 2;
-        if (fl[2] > 1500) break;
-        uint32_t crc = 0xFF;                                                 // CalcCRC8(ip, 4, 2): reflected, polynomial 0xE0, over HT-SIG bits 0..33
-        for (int b = 0; b < 34; b++) { crc ^= (uint32_t)(ht >> b) & 1; crc = (crc & 1) ? (crc >> 1) ^ 0xE0 : crc >> 1; }
-        if (((~crc) & 0xFF) != (uint32_t)((ht >> 34) & 0x3FFF)) break;      // compared in int: bits 42.. (always 0 after the >> 6) included
-        fl[3] = (uint32_t)ht & 0x7F;
+        if (!P.ok) break;
+        fl[3] = P.mcs;
         if (fl[3] < 8 || fl[3] >= 11) break;
-        fl[4] = (uint32_t)(ht >> 8) & 0xFFFF;
+        fl[4] = P.ht_len;
         if (fl[4] > 1500) break;
-        fl[5] = fl[3] == 10 ? 2u : 0u;                                       // CR_34 : CR_12
-        const uint32_t nd = 52u * (fl[3] - 7);                               // DOT11N_RATE_PARAMS[8..10].ndbps
+        fl[5] = code_rate11n(fl[3]);                                         // CR_34 : CR_12
+        const uint32_t nd = data_bits11n(104u * nbpsc11n(fl[3]), fl[5]);     // DOT11N_RATE_PARAMS[8..10].ndbps
         fl[6] = fl[7] = (fl[4] * 8 + 22 + nd - 1) / nd + 4;
         fl[2] = fl[4]; fl[8] = 3;                                            // frame_length = ht_frame_length; SYMBOL_HT_STF
         ok = true;
     } while (0);
-    if (!ok) fl[0] = 0x80000005u;                                            // E_ERROR_PLCP_HEADER_FAIL
+    if (!ok) fl[0] = E_PLCP_HEADER_FAIL;
     uint32_t* o = rec + (size_t)f * 12;
     for (int i = 0; i < 9; i++) o[i] = fl[i];
     o[9] = lsig & 0xFFFFFF; o[10] = (uint32_t)ht; o[11] = (uint32_t)(ht >> 32);
 }
-
-// ---- dsp_math (Brick11/src/dsp_math.h:96-213): arctangent through a 4097-entry table, exactly as the reference indexes it
 
 // TFreqEstimator_11n (freqoffset_11n.hpp:42-160): one wave per frame, lane = sample of the first L-LTF half, both RX chains
 __global__ void __launch_bounds__(256) k_cfo_est11n_batch(const uint32_t* l0, const uint32_t* l1, short* state, uint32_t nframes, const short* atan_tab)
 {
     const uint32_t f = blockIdx.x * 4 + (threadIdx.x >> 6); const int i = threadIdx.x & 63;
     if (f >= nframes) return;
-    int re, im, sre, sim;
-    conj_mul32(unpack(l0[(size_t)f * 128 + i]), unpack(l0[(size_t)f * 128 + 64 + i]), re, im); sre = re >> 7; sim = im >> 7;
-    conj_mul32(unpack(l1[(size_t)f * 128 + i]), unpack(l1[(size_t)f * 128 + 64 + i]), re, im); sre += re >> 7; sim += im >> 7;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { sre += __shfl_xor(sre, d); sim += __shfl_xor(sim, d); }       // wrapping 32-bit sums: order does not matter
+    const int delta = cfo_est11n(atan_tab, unpack(l0[(size_t)f * 128 + i]), unpack(l0[(size_t)f * 128 + 64 + i]), unpack(l1[(size_t)f * 128 + i]),
+                                 unpack(l1[(size_t)f * 128 + 64 + i]));
     if (i < 8) {
-        const int delta = dsp_atan32(atan_tab, sre, sim) >> 6;
         short* st = state + (size_t)f * 24;
         st[i] = (short)(i * delta); st[8 + i] = (short)(delta << 3); st[16 + i] = 0;
     }
@@ -217,9 +164,7 @@ __global__ void __launch_bounds__(256) k_freq_comp11n_batch(const uint32_t* in0,
         const int ph = (int)(short)(st[k] + (short)(b * st[8 + k]) - st[16 + k]);
         const cpx cof = unpack(sincos[(unsigned)ph & 0xFFFFu]);
         const size_t at = (size_t)first[f] + m;
-        int re, im;
-        mul32(unpack(in0[at]), cof, re, im); out0[at] = pack(mk(sat16(re >> 15), sat16(im >> 15)));
-        mul32(unpack(in1[at]), cof, re, im); out1[at] = pack(mk(sat16(re >> 15), sat16(im >> 15)));
+        out0[at] = pack(freq_comp11n(unpack(in0[at]), cof)); out1[at] = pack(freq_comp11n(unpack(in1[at]), cof));
     }
 }
 __global__ void k_freq_comp11n_advance(const uint32_t* nbursts, short* state, uint32_t nframes)       // vfo_delta_i += nbursts * vfo_step_i

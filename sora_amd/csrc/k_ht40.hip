@@ -1,7 +1,7 @@
 // k_ht40.hip -- the data field of an 802.11n HT-mixed 40 MHz, two-stream frame (BASELINE.json configs[3]: "2x2 MIMO 40 MHz HT, 128-pt FFT,
 // MMSE MIMO detect, dual Viterbi"), SURVEY.md section 8(f)1 extension.  PARITY UNPINNED: the reference has no 40 MHz receive graph -- its
 // 802.11n graph is 20 MHz, zero-forcing, one decoder, MCS 8-10 (kernel/bb/Brick11/src/PHY_11n.hpp:497, channel_11n.hpp:423-433).  What IS
-// pinned is every piece the reference does have, used here unchanged:
+// pinned is every piece the reference does have, used here unchanged (the 802.11n bricks through their one statement in dev_11n.h):
 //   FFT<128>                      core/inc/fft_r4dif.h (fft128_group, pinned by tests/golden/ref_vectors.npz)
 //   TFreqComp_11n                 freqoffset_11n.hpp:162-280: sat((x * sincos(n cfo - theta)) >> 15), dsp_math tables
 //   TMimoChannelEst               channel_11n.hpp:329-443: P-matrix combination of the two HT-LTFs; with noise_var = 0 the weights are its
@@ -49,8 +49,6 @@ static __constant__ int8_t kHtLtf40[117] = {    // carriers -58..58 (IEEE 802.11
     1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 1, 1, -1, -1, 1, 1, -1, 1, -1, 1, -1, -1, -1, -1, -1, 1, 1, -1, -1, 1, -1, 1, -1, 1, 1, 1, 1,
     -1, -1, -1, 1, 0, 0, 0, -1, 1, 1, -1,
     1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 1, 1, -1, -1, 1, 1, -1, 1, -1, 1, -1, -1, -1, -1, -1, 1, 1, -1, -1, 1, -1, 1, -1, 1, 1, 1, 1 };
-__device__ __forceinline__ void wsync40() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
 __device__ __forceinline__ int data_bin40(int c)          // data carrier c (0..107) -> FFT bin: -58..-2 then 2..58 without +-11, +-25, +-53
 {
     int k;
@@ -93,7 +91,6 @@ __global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A)
     const int ncb = 108 * nb;
     for (int k = lane; k < ncb; k += 64) { W.dtab[0][k] = (uint16_t)deint40_index(nb, 0, k); W.dtab[1][k] = (uint16_t)deint40_index(nb, 1, k); }
     int theta = 0;
-    auto nosync = []() __attribute__((always_inline)) { wsync40(); };
     const Fft128TwPk twpk = fft128_twiddles_pk(A.T, lane & 31);
     // one 160-sample symbol starting at sample `pos` of the frame: TFreqComp_11n, cyclic prefix dropped, FFT<128> per chain (32 lanes each) -> W.y[slot]
     auto symbol_fft = [&](uint32_t pos, int slot) __attribute__((always_inline)) {
@@ -102,20 +99,17 @@ __global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A)
             const uint32_t n = pos + 32 + 64 * h + (uint32_t)lane;
             const cpx cof = unpack(A.sincos[(unsigned)((int)n * cfo - theta) & 0xFFFFu]);
 #pragma unroll
-            for (int r = 0; r < 2; r++) {
-                int re, im; mul32(unpack(iq[r][n]), cof, re, im);
-                W.buf[r][64 * h + lane] = pack(mk(sat16(re >> 15), sat16(im >> 15)));
-            }
+            for (int r = 0; r < 2; r++) W.buf[r][64 * h + lane] = pack(freq_comp11n(unpack(iq[r][n]), cof));
         }
-        wsync40();
+        wave_lds_sync();
         const int r = lane >> 5, e = lane & 31; pcx x[4];
 #pragma unroll
         for (int m = 0; m < 4; m++) x[m] = W.buf[r][e + 32 * m];
         // the packed-arithmetic FFT<128> of k_fft128_batch (dev_arith.h): point j at slot bitrev7(j)
-        fft128_core_pk(x, W.fft[r], e, twpk, nosync);
+        fft128_core_pk(x, W.fft[r], e, twpk, wave_lds_sync);
 #pragma unroll
         for (int q = 0; q < 4; q++) W.y[slot][r][e + 32 * q] = W.fft[r][__brev((unsigned)(e + 32 * q)) >> 25];
-        wsync40();
+        wave_lds_sync();
     };
     symbol_fft(0, 0);
     symbol_fft(160, 1);
@@ -126,26 +120,13 @@ __global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A)
         const int i = lane + 64 * hb, k = i < 64 ? i : i - 128;
         const int ltf = (k >= -58 && k <= 58) ? (int)kHtLtf40[k + 58] : 0;
         const bool negate = ltf != 1;
-        cpx hh[2][2];
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-            const cpx p = unpack(W.y[0][r][i]), q = unpack(W.y[1][r][i]);
-            cpx d = sra(csubs(p, q), 1), s = sra(cadds(p, q), 1);
-            if (negate) { d = mk(neg16(d.re), neg16(d.im)); s = mk(neg16(s.re), neg16(s.im)); }
-            hh[r][0] = d; hh[r][1] = s;
-        }
-        const cf a00 = { (float)hh[0][0].re, (float)hh[0][0].im }, a01 = { (float)hh[0][1].re, (float)hh[0][1].im };
-        const cf a10 = { (float)hh[1][0].re, (float)hh[1][0].im }, a11 = { (float)hh[1][1].re, (float)hh[1][1].im };
-        cf w00, w01, w10, w11;
-        if (F.noise_var == 0.0f) {
-            // zero forcing, exactly as TMimoChannelEst computes the inverse (brick/inc/sora_matrix.h:134-148,305-313)
-            const cf ad = cf_mul(a00, a11), bc = cf_mul(a01, a10);
-            const cf det = { ad.re - bc.re, ad.im - bc.im };
-            const float nn = ((det.re * det.re) + (det.im * det.im)) / 65536.0f;
-            const cf ds = { det.re, -det.im }, m01 = { -a01.re, -a01.im }, m10 = { -a10.re, -a10.im };
-            const cf r00 = cf_mul(a11, ds), r01 = cf_mul(m01, ds), r10 = cf_mul(m10, ds), r11 = cf_mul(a00, ds);
-            w00 = { r00.re / nn, r00.im / nn }; w01 = { r01.re / nn, r01.im / nn }; w10 = { r10.re / nn, r10.im / nn }; w11 = { r11.re / nn, r11.im / nn };
-        } else {
+        cpx hh[2][2]; cf w[4];
+        mimo_h_carrier(unpack(W.y[0][0][i]), unpack(W.y[1][0][i]), unpack(W.y[0][1][i]), unpack(W.y[1][1][i]), negate, hh);
+        if (F.noise_var == 0.0f) mimo_inverse(hh, w);                        // zero forcing: TMimoChannelEst's own inverse
+        else {
+            const cf a00 = { (float)hh[0][0].re, (float)hh[0][0].im }, a01 = { (float)hh[0][1].re, (float)hh[0][1].im };
+            const cf a10 = { (float)hh[1][0].re, (float)hh[1][0].im }, a11 = { (float)hh[1][1].re, (float)hh[1][1].im };
+            cf w00, w01, w10, w11;
             // MMSE: W = (H^H H + s2 I)^-1 H^H = adj(G) H^H / det(G), G Hermitian
             auto cj = [](cf a) { return cf{ a.re, -a.im }; };
             auto n2 = [](cf a) { return (a.re * a.re) + (a.im * a.im); };
@@ -165,15 +146,16 @@ __global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A)
             const float beta0 = (e0.re + e1.re) / 65536.0f, beta1 = (e2.re + e3.re) / 65536.0f;
             w00 = { w00.re / beta0, w00.im / beta0 }; w01 = { w01.re / beta0, w01.im / beta0 };
             w10 = { w10.re / beta1, w10.im / beta1 }; w11 = { w11.re / beta1, w11.im / beta1 };
+            w[0] = w00; w[1] = w01; w[2] = w10; w[3] = w11;
         }
-        W.w[0][i] = pack(mk(cvtps_sat16(w00.re), cvtps_sat16(w00.im))); W.w[1][i] = pack(mk(cvtps_sat16(w01.re), cvtps_sat16(w01.im)));
-        W.w[2][i] = pack(mk(cvtps_sat16(w10.re), cvtps_sat16(w10.im))); W.w[3][i] = pack(mk(cvtps_sat16(w11.re), cvtps_sat16(w11.im)));
+#pragma unroll
+        for (int m = 0; m < 4; m++) W.w[m][i] = mimo_weight_pack(w[m]);
         if (A.w_out) {
 #pragma unroll
             for (int m = 0; m < 4; m++) A.w_out[((size_t)f * 4 + m) * 128 + i] = W.w[m][i];
         }
     }
-    wsync40();
+    wave_lds_sync();
     // ---- data symbols, in order (the pilot phase of symbol d rotates symbol d + 1)
     uint8_t* dst = A.soft + F.soft_off;
     const uint32_t per_pad = (F.nsym * 108u * F.nb + 31u) / 32u * 32u;         // stream 1 starts here (ht40_submit lays the job records out the same way)
@@ -183,13 +165,10 @@ __global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A)
         for (int hb = 0; hb < 2; hb++) {                                     // TMimoChannelComp
             const int i = lane + 64 * hb;
             const cpx p = unpack(W.y[0][0][i]), q = unpack(W.y[0][1][i]);
-            int ar, ai, br, bi;
-            mul32(unpack(W.w[0][i]), p, ar, ai); mul32(unpack(W.w[1][i]), q, br, bi);
-            W.xs[0][i] = pack(mk(sat16((int)((unsigned)ar + (unsigned)br) >> 9), sat16((int)((unsigned)ai + (unsigned)bi) >> 9)));
-            mul32(unpack(W.w[2][i]), p, ar, ai); mul32(unpack(W.w[3][i]), q, br, bi);
-            W.xs[1][i] = pack(mk(sat16((int)((unsigned)ar + (unsigned)br) >> 9), sat16((int)((unsigned)ai + (unsigned)bi) >> 9)));
+            W.xs[0][i] = pack(mimo_comp_row(unpack(W.w[0][i]), unpack(W.w[1][i]), p, q));
+            W.xs[1][i] = pack(mimo_comp_row(unpack(W.w[2][i]), unpack(W.w[3][i]), p, q));
         }
-        wsync40();
+        wave_lds_sync();
         {   // pilot phases: lane 8 s + k (k < 6) takes pilot k of stream s
             const int k = lane & 7, sidx = (lane >> 3) & 1;
             const int pk = k == 0 ? -53 : k == 1 ? -25 : k == 2 ? -11 : k == 3 ? 11 : k == 4 ? 25 : 53;
@@ -205,26 +184,16 @@ __global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A)
             if (c < 108) {
                 const int bin = data_bin40(c);
 #pragma unroll
-                for (int s = 0; s < 2; s++) {
-                    const cpx x = unpack(W.xs[s][bin]);
-                    const int re = min(max(x.re, -128), 127) + 128, im = min(max(x.im, -128), 127) + 128;
-                    uint8_t* o = W.soft[s] + c * nb;
-                    switch (nb) {
-                    case 1: o[0] = s_lut[0][re]; break;
-                    case 2: o[0] = s_lut[0][re]; o[1] = s_lut[0][im]; break;
-                    case 4: o[0] = s_lut[1][re]; o[1] = s_lut[2][re]; o[2] = s_lut[1][im]; o[3] = s_lut[2][im]; break;
-                    default: o[0] = s_lut[3][re]; o[1] = s_lut[4][re]; o[2] = s_lut[5][re]; o[3] = s_lut[3][im]; o[4] = s_lut[4][im]; o[5] = s_lut[5][im];
-                    }
-                }
+                for (int s = 0; s < 2; s++) demap11n_store(W.soft[s] + c * nb, s_lut, unpack(W.xs[s][bin]), nb);
             }
         }
-        wsync40();
+        wave_lds_sync();
         // de-interleave both streams, each into its own byte stream (one decoder wave takes stream 0 in its low halves and stream 1 in its high halves)
         for (int g = lane; g < ncb; g += 64) {
             dst[(size_t)d * ncb + g] = W.soft[0][W.dtab[0][g]];
             dst[per_pad + (size_t)d * ncb + g] = W.soft[1][W.dtab[1][g]];
         }
-        wsync40();
+        wave_lds_sync();
     }
 }
 
@@ -240,28 +209,9 @@ __global__ void __launch_bounds__(256) k_ht40_finish(Ht40FinishArgs A)
     const uint32_t j = blockIdx.x * 4 + wv;
     if (j >= (A.plan ? min(A.njobs, 2u * A.plan[0]) : A.njobs)) return;
     const Ht40Job J = A.jobs[j];
-    const uint8_t* dec = A.vout + J.out_off;
-    uint8_t* mp = A.mpdu + (size_t)J.row * 4096;
-    uint8_t* bytes = reinterpret_cast<uint8_t*>(s_bufs[wv]);
-    const uint32_t L = J.length;
-    const unsigned seed = dec[1] >> 1;
-    const unsigned phase = A.T.scr_phase[seed & 0x7F];
-    for (uint32_t i = lane; i < L; i += 64) {
-        const unsigned sb = phase == 255 ? 0u : A.T.scr_seq[(phase + 8u * i) % 127u];
-        const unsigned o = dec[2 + i] ^ sb;
-        bytes[i] = (uint8_t)o; mp[i] = (uint8_t)o;
-    }
-    wsync40();
-    const int n = L >= 4 ? (int)L - 4 : 0;
-    uint32_t crc;
-    if (n >= 4) crc = crc32_wave(bytes, n, s_crc, s_z, lane);
-    else { crc = 0xFFFFFFFFu; for (int i = 0; i < n; i++) crc = (crc >> 8) ^ s_crc[(bytes[i] ^ crc) & 0xFF]; }
-    if (lane == 0) {
-        uint32_t fcs = 0;
-        if (L >= 4) fcs = (uint32_t)bytes[L - 4] | ((uint32_t)bytes[L - 3] << 8) | ((uint32_t)bytes[L - 2] << 16) | ((uint32_t)bytes[L - 1] << 24);
-        Rx11bRow r; r.end_sample = 0; r.rate_kbps = 0; r.length = L; r.crc32 = fcs; r.error_code = ((~crc) == fcs) ? 1u : 0x80000006u;
-        A.rows[J.row] = r;
-    }
+    uint32_t fcs;
+    const uint32_t verdict = finish_frame(A.T, A.vout + J.out_off, J.length, reinterpret_cast<uint8_t*>(s_bufs[wv]), A.mpdu + (size_t)J.row * 4096, s_crc, s_z, lane, fcs);
+    if (lane == 0) { Rx11bRow r; r.end_sample = 0; r.rate_kbps = 0; r.length = J.length; r.crc32 = fcs; r.error_code = verdict; A.rows[J.row] = r; }
 }
 
 // ---- raw-capture calls: what the front end found (k_scan_ht40: per capture a count and up to `mf` Ht40Found records in time order) -> the data
@@ -269,13 +219,11 @@ __global__ void __launch_bounds__(256) k_ht40_finish(Ht40FinishArgs A)
 // tables on the host: one host wait per call).  One block: per capture the number of recorded frames, their soft bytes and their number per
 // code rate; five exclusive prefix sums over the captures; then every capture writes its frames' descriptors, the two decoder jobs of each
 // (neighbours in their code-rate list: one wave decodes both streams), the finish jobs and the rows' templates, in (capture, time) order.
-__host__ __device__ __forceinline__ uint32_t ht40_ndbps(uint32_t nb, uint32_t cr) { return 108u * nb * (cr == 0 ? 1u : cr == 1 ? 2u : 3u) / (cr == 0 ? 2u : cr == 1 ? 3u : 4u); }
 struct Ht40Geom { uint32_t nb, cr, nsym, per, per_pad; };
 __device__ __forceinline__ Ht40Geom ht40_geom(const Ht40Found& F)
 {
     Ht40Geom G;
-    G.nb = F.mcs == 8 ? 1u : F.mcs <= 10 ? 2u : F.mcs <= 12 ? 4u : 6u;
-    G.cr = (F.mcs == 10 || F.mcs == 12 || F.mcs == 14) ? 2u : F.mcs == 13 ? 1u : 0u;
+    G.nb = nbpsc11n(F.mcs); G.cr = code_rate11n(F.mcs);
     const uint32_t nd = ht40_ndbps(G.nb, G.cr);
     G.nsym = (16u + 8u * F.ht_len + 6u + nd - 1u) / nd;                          // sora_ht40_symbols(len, len, nb, cr)
     G.per = G.nsym * 108u * G.nb; G.per_pad = (G.per + 31u) / 32u * 32u;

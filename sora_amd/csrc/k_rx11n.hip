@@ -38,12 +38,6 @@ struct Rx11nArgs {
 };
 
 namespace {
-constexpr uint32_t E_OK = 1u, E_PLCP = 0x80000005u, E_CRC = 0x80000006u;
-
-__device__ __forceinline__ void wsync() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }            // a value every lane holds alike -> SGPR
 __device__ __forceinline__ unsigned long long uni64(unsigned long long v)
 {
     return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
@@ -98,7 +92,6 @@ struct Scan11nArgs {
 // A symbol slot of the 802.11n handle: kSoftPerSlot / kOutPerSlot (rx_types.h) while the gate stands at MCS 10 (208 soft values, 19.5 decoded bytes per symbol at
 // most); with the gate raised a symbol brings up to 624 soft values and 58.5 decoded bytes (MCS 14)
 constexpr uint32_t kSoftPerSlot11nWide = 640, kOutPerSlot11nWide = 64;
-__host__ __device__ inline uint32_t nbpsc11n(uint32_t mcs) { return mcs == 8 ? 1u : mcs <= 10 ? 2u : mcs <= 12 ? 4u : 6u; }   // rate_selector (fb11ndemod_config.hpp:136-147)
 struct Frame11nArgs {
     const uint32_t* iq0; const uint32_t* iq1; const CapDesc* caps;
     const N11Frame* frames; const uint32_t* njobs; uint32_t nrows;
@@ -183,7 +176,6 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
         return v;
     };
     const Fft64Tw tw = fft64_twiddles(A.T, lane & 15);
-    auto nosync = []() __attribute__((always_inline)) { wsync(); };
 
     int sr[2] = { 0, 0 }, si[2] = { 0, 0 }, se[2] = { 0, 0 };
     int ring_pos = 0, his_index = 0;
@@ -213,7 +205,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
     if (fresh)
     for (int k = lane; k < 64; k += 64) { W.his[0][k & 31] = 0; W.his[1][k & 31] = 0; W.hcr[k >> 5][k & 31] = 0; W.hci[k >> 5][k & 31] = 0;
         W.he[k >> 5][k & 31] = 0; W.his_e[k] = 0x7FFFFFFFFFFFFFFFll; }
-    wsync();
+    wave_lds_sync();
     uint32_t origin = 0, nfr = 0;
     Rx11bRow* rows = A.rows + (size_t)cap * A.max_frames;
 
@@ -328,7 +320,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
 #pragma unroll
             for (int r = 0; r < 2; r++) { sr[r] = __shfl(pr[r], na - 1); si[r] = __shfl(pi[r], na - 1); se[r] = __shfl(pe[r], na - 1); }
             his_index = (his_index + ne) & 63; ring_pos = (ring_pos + na) & 31;
-            wsync();
+            wave_lds_sync();
             if (det >= 0) det_at = (int64_t)base + na;
         }
         if constexpr (STREAM) if (det_at < 0) { ld_pf = pf; ld_pc = pc; ld_sense = sense; ld_to = timeout; fin_pos = origin + cs_end; fin = true; }
@@ -341,37 +333,26 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
         if constexpr (STREAM) if (l0 + 128 + 240 > n_real || nfr >= A.max_frames) { saved = true; break; }
         if (l0 + 128 > n_pad) break;
         // ================================================================ L-LTF: CFO, compensation, four FFTs, SISO channel
-        int cfo;
-        {
-            int sre = 0, sim = 0;
-#pragma unroll
-            for (int r = 0; r < 2; r++) {
-                int re, im; conj_mul32(unpack(fetch(r, origin + l0 + lane)), unpack(fetch(r, origin + l0 + 64 + lane)), re, im);
-                sre += re >> 7; sim += im >> 7;
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) { sre += __shfl_xor(sre, d); sim += __shfl_xor(sim, d); }
-            cfo = uni(dsp_atan32(A.atan, sre, sim) >> 6);
-        }
+        const int cfo = uni(cfo_est11n(A.atan, unpack(fetch(0, origin + l0 + lane)), unpack(fetch(0, origin + l0 + 64 + lane)),
+                                       unpack(fetch(1, origin + l0 + lane)), unpack(fetch(1, origin + l0 + 64 + lane))));
 #pragma unroll
         for (int r = 0; r < 2; r++)
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const int n = 64 * h + lane;
                 const cpx cof = unpack(A.sincos[(unsigned)(n * cfo) & 0xFFFFu]);
-                int re, im; mul32(unpack(fetch(r, origin + l0 + n)), cof, re, im);
-                W.buf[r][n] = pack(mk(sat16(re >> 15), sat16(im >> 15)));
+                W.buf[r][n] = pack(freq_comp11n(unpack(fetch(r, origin + l0 + n)), cof));
             }
-        wsync();
+        wave_lds_sync();
         {
             const int g = lane >> 4, e = lane & 15; cpx x[4], yy[4];
 #pragma unroll
             for (int m = 0; m < 4; m++) x[m] = unpack(W.buf[g >> 1][64 * (g & 1) + e + 16 * m]);
-            fft64_group(x, yy, W.fft[g], e, tw, nosync);
+            fft64_group(x, yy, W.fft[g], e, tw, wave_lds_sync);
 #pragma unroll
             for (int q = 0; q < 4; q++) W.y[g >> 1][64 * (g & 1) + e + 16 * q] = pack(yy[q]);
         }
-        wsync();
+        wave_lds_sync();
         float noise_var = 0.0f;
         // the two L-LTF symbols differ by noise only: E|Y1 - Y2|^2 = 2 var(FFT<64> bin); an FFT<128> bin of the
         if (HT40) {
@@ -390,16 +371,8 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
             noise_var = acc * (1.0f / 416.0f);
         }
 #pragma unroll
-        for (int r = 0; r < 2; r++) {
-            uint32_t o = 0;
-            if (lane < 28 || lane >= 36) {
-                const uint32_t* l = W.y[r] + (lane & ~3);
-                const cpx a = siso_one(l, lane & 3, lane), b = siso_one(l + 64, lane & 3, lane);
-                o = pack(mk((short)((short)(a.re + b.re) >> 1), (short)((short)(a.im + b.im) >> 1)));
-            }
-            W.ch[r][lane] = o;
-        }
-        wsync();
+        for (int r = 0; r < 2; r++) W.ch[r][lane] = siso_est_carrier(W.y[r], lane);
+        wave_lds_sync();
         // ================================================================ the SIG field: three symbols, theta = 0 (no pilot tracking before the data field)
         uint32_t err = 0, mcs = 0, ht_len = 0, code_rate = 0;
         bool sig_ok = false, decoded = false;
@@ -412,73 +385,50 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
             for (int r = 0; r < 2; r++) {
                 const uint32_t n = a - l0 + 16 + lane;
                 const cpx cof = unpack(A.sincos[(unsigned)((int)n * cfo) & 0xFFFFu]);
-                int re, im; mul32(unpack(fetch(r, origin + a + 16 + lane)), cof, re, im);
-                W.buf[r][lane] = pack(mk(sat16(re >> 15), sat16(im >> 15)));
+                W.buf[r][lane] = pack(freq_comp11n(unpack(fetch(r, origin + a + 16 + lane)), cof));
             }
-            wsync();
+            wave_lds_sync();
             {
                 const int g = lane >> 4, e = lane & 15; cpx x[4], yy[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) x[q] = unpack(W.buf[g & 1][e + 16 * q]);
-                fft64_group(x, yy, W.fft[g], e, tw, nosync);
+                fft64_group(x, yy, W.fft[g], e, tw, wave_lds_sync);
                 if (g < 2) {
 #pragma unroll
                     for (int q = 0; q < 4; q++) W.y[g][e + 16 * q] = pack(yy[q]);
                 }
             }
-            wsync();
+            wave_lds_sync();
             {
-                int re, im;
-                mul32(unpack(W.y[0][lane]), unpack(W.ch[0][lane]), re, im); const cpx x0 = mk(sat16(re >> 9), sat16(im >> 9));
-                mul32(unpack(W.y[1][lane]), unpack(W.ch[1][lane]), re, im); const cpx x1 = mk(sat16(re >> 9), sat16(im >> 9));
-                W.sig[64 * nsig + lane] = pack(mk((short)((short)(x0.re + x1.re) >> 1), (short)((short)(x0.im + x1.im) >> 1)));
+                cpx x0, x1;
+                W.sig[64 * nsig + lane] = pack(siso_comp_mrc(unpack(W.y[0][lane]), unpack(W.ch[0][lane]), unpack(W.y[1][lane]), unpack(W.ch[1][lane]), x0, x1));
             }
             nsig++; a += 80;
-            wsync();
+            wave_lds_sync();
         }
         // T11nSymSel::Flush: the missing symbols are zeros
         if (at_end && nsig > 0) { for (int k = lane; k < 64 * (3 - nsig); k += 64) W.sig[64 * nsig + k] = 0; }
         if (!at_end || nsig > 0) {
             // T11nSigDemap -> T11aDeinterleaveBPSK -> T11nViterbiSig -> T11nSigParser on W.sig
             decoded = true;
-            wsync();
+            wave_lds_sync();
             for (int g = lane; g < 144; g += 64) {
                 const int s3 = g / 48, k = g - 48 * s3;
-                int bin; if (k < 24) bin = 38 + k + (k >= 5) + (k >= 18); else { const int q = k - 24; bin = 1 + q + (q >= 6) + (q >= 19); }
-                const cpx v = unpack(W.sig[64 * s3 + bin]);
-                const int qv = s3 == 0 ? v.re : v.im;
-                W.soft0[g] = s_lut[0][min(max(qv, -128), 127) + 128];
+                W.soft0[g] = sig_demap_soft(unpack(W.sig[64 * s3 + carrier_bin48(k)]), s3, s_lut);
             }
-            wsync();
-            for (int g = lane; g < 144; g += 64) { const int s3 = g / 48, kk = g - 48 * s3; W.sigsoft[g] = W.soft0[48 * s3 + 3 * (kk & 15) + (kk >> 4)]; }
-            wsync();
+            wave_lds_sync();
+            for (int g = lane; g < 144; g += 64) { const int s3 = g / 48, kk = g - 48 * s3; W.sigsoft[g] = W.soft0[48 * s3 + sig_deint_index(kk)]; }
+            wave_lds_sync();
             const uint32_t lsig = (uint32_t)uni((int)(uint32_t)(viterbi_sig_wave<24>(W.sigsoft, reinterpret_cast<uint64_t*>(W.dec), lane) >> 6));
-            wsync();
+            wave_lds_sync();
             const unsigned long long ht = uni64(viterbi_sig_wave<48>(W.sigsoft + 48, reinterpret_cast<uint64_t*>(W.dec), lane) >> 6);
-            wsync();
-            do {
-                const uint32_t sg = lsig & 0xFFFFFF;
-                if (sg & 0xFC0010) break;
-                if (__popc(sg) & 1) break;
-                const uint32_t code = sg & 0xF;
-                if (code < 8) break;
-                if (((sg >> 5) & 0xFFF) * 2 > 1500) break;
-                uint32_t crc = 0xFF;
-                for (int b = 0; b < 34; b++) { crc ^= (uint32_t)(ht >> b) & 1; crc = (crc & 1) ? (crc >> 1) ^ 0xE0 : crc >> 1; }
-                if (((~crc) & 0xFF) != (uint32_t)((ht >> 34) & 0x3FFF)) break;
-                const uint32_t mc = (uint32_t)ht & 0x7F;
-                const uint32_t hl = (uint32_t)(ht >> 8) & 0xFFFF;
-                if (HT40) {
-                    if (mc < 8 || mc > 14 || !((ht >> 7) & 1) || hl > 4000 || hl < 4) break;     // two streams, 40 MHz, a rate this library has a decoder for
-                    mcs = mc; ht_len = hl; code_rate = (mc == 10 || mc == 12 || mc == 14) ? 2u : mc == 13 ? 1u : 0u;
-                } else {
-                    if (mc < 8 || mc > A.mcs_max) break;                                           // (mcs_max = 10: the reference's ht_frame_mcs >= 11)
-                    if (hl > 1500) break;
-                    mcs = mc; ht_len = hl; code_rate = (mc == 10 || mc == 12 || mc == 14) ? 2u : mc == 13 ? 1u : 0u;
-                }
-                sig_ok = true;
-            } while (0);
-            if (!sig_ok) err = E_PLCP;
+            wave_lds_sync();
+            const SigFront P = sig_parse_front(lsig, ht);
+            // the gate.  HT40: two streams, 40 MHz, a rate this library has a decoder for; else mcs_max (10: the reference's ht_frame_mcs >= 11) and 1500 bytes
+            if (HT40) sig_ok = P.ok && P.mcs >= 8 && P.mcs <= 14 && P.cbw40 && P.ht_len <= 4000 && P.ht_len >= 4;
+            else sig_ok = P.ok && P.mcs >= 8 && P.mcs <= A.mcs_max && P.ht_len <= 1500;
+            if (sig_ok) { mcs = P.mcs; ht_len = P.ht_len; code_rate = code_rate11n(P.mcs); }
+            else err = E_PLCP_HEADER_FAIL;
         }
         // ================================================================ what happens to the frame, without looking at its data field
         uint32_t last_burst_end = n_pad;                                     // (relative to origin) behind the burst that raises the event
@@ -488,8 +438,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
         else if (HT40 && decoded && !at_end) {
             // HT-STF at a, HT-LTF 1 / 2 at a + 80 / a + 160, data symbol d at a + 240 + 80 d (20 MHz indices; 4 us symbols).  The frame is
             // recorded when all of it lies inside the capture; a frame the capture cuts off raises no event (as the 20 MHz graph behaves).
-            const uint32_t nb = mcs == 8 ? 1u : mcs <= 10 ? 2u : mcs <= 12 ? 4u : 6u;
-            const uint32_t ndbps = 108u * nb * (code_rate == 0 ? 1u : code_rate == 1 ? 2u : 3u) / (code_rate == 0 ? 2u : code_rate == 1 ? 3u : 4u);
+            const uint32_t ndbps = ht40_ndbps(nbpsc11n(mcs), code_rate);
             const uint32_t nsym = (16u + 8u * ht_len + 6u + ndbps - 1u) / ndbps;
             nproc = nsym;
             if (a + 240 + 80 * nsym <= n_real) { event = true; queue = true; last_burst_end = a + 240 + 80 * nsym; }
@@ -498,7 +447,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
             // HT-STF at a, HT-LTF at a + 80 / a + 160, data symbol d at a + 240 + 80 d; a symbol is processed when it starts inside the
             // padded capture (its missing samples read as zero: the flush of the partly filled queues)
             const uint32_t tr_end = ht_len * 8 + 16 + 6;
-            const uint32_t S = 104u * nbpsc11n(mcs), sps = code_rate == 0 ? S / 2 : code_rate == 1 ? S / 3 * 2 : S / 4 * 3;   // soft values / trellis steps per symbol
+            const uint32_t S = 104u * nbpsc11n(mcs), sps = data_bits11n(S, code_rate);     // soft values / trellis steps per symbol
             const uint32_t nsym = (tr_end + sps - 1) / sps;                  // the symbol in which the decoder passes tr_end
             const uint32_t a_data = a + 240;
             if constexpr (STREAM) {                                          // all of the data field inside the capture, or no event (and no flush)
@@ -512,7 +461,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
                 // event only if that takes the decoder past tr_end.  (64-QAM: a symbol is two whole bursts, the decoder holds nothing back and
                 // a cut frame raises no event; 16-QAM: a symbol is a burst and a third, as QPSK's is two thirds.)
                 nsoft = (nproc * S + 311) / 312 * 312;
-                const uint32_t steps = code_rate == 0 ? nsoft / 2 : code_rate == 1 ? nsoft / 3 * 2 : nsoft / 4 * 3;
+                const uint32_t steps = data_bits11n(nsoft, code_rate);
                 if (steps >= tr_end) { event = true; queue = true; last_burst_end = n_pad; }
             }
             }
@@ -554,7 +503,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
         if (saved) fin_pos = sv_pos;
         if (n20 != 0) {                                                      // (a zero-length capture leaves its stream as it was)
             const RingLds* src = saved ? SV : reinterpret_cast<const RingLds*>(&W);
-            wsync();
+            wave_lds_sync();
             uint32_t* rw = rec + 64;
             rw[lane] = src->his[lane >> 5][lane & 31]; rw[64 + lane] = (uint32_t)src->hcr[lane >> 5][lane & 31];
             rw[128 + lane] = (uint32_t)src->hci[lane >> 5][lane & 31]; rw[192 + lane] = (uint32_t)src->he[lane >> 5][lane & 31];
@@ -613,7 +562,6 @@ __global__ void __launch_bounds__(256) k_frame11n(Frame11nArgs A)
     auto fetch = [&](int r, uint32_t i) __attribute__((always_inline)) -> uint32_t { return i < n20 ? iq[r][2 * (size_t)i] : 0u; };
     // the packed-arithmetic FFT<64> of k_frame (dev_arith.h): half the instructions of the unpacked one
     const Fft64TwPk tw = fft64_twiddles_pk(A.T, lane & 15);
-    auto nosync = []() __attribute__((always_inline)) { wsync(); };
     const int cfo = uni(F.cfo);
     const uint32_t l0 = (uint32_t)uni((int)F.l0), mcs = (uint32_t)uni((int)F.mcs), nproc = (uint32_t)uni((int)F.nproc);
     const int nb = (int)nbpsc11n(mcs);
@@ -631,49 +579,31 @@ __global__ void __launch_bounds__(256) k_frame11n(Frame11nArgs A)
     auto symbol_fft = [&](uint32_t pos, uint32_t x0, uint32_t x1, int half) __attribute__((always_inline)) {
         const uint32_t n = pos - l0 + 16 + (uint32_t)lane;
         const cpx cof = unpack(A.sincos[(unsigned)((int)n * cfo - theta) & 0xFFFFu]);
-        int re, im;
-        mul32(unpack(x0), cof, re, im); W.buf[0][lane] = pack(mk(sat16(re >> 15), sat16(im >> 15)));
-        mul32(unpack(x1), cof, re, im); W.buf[1][lane] = pack(mk(sat16(re >> 15), sat16(im >> 15)));
-        wsync();
+        W.buf[0][lane] = pack(freq_comp11n(unpack(x0), cof)); W.buf[1][lane] = pack(freq_comp11n(unpack(x1), cof));
+        wave_lds_sync();
         const int g = lane >> 4, e = lane & 15; pcx x[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) x[q] = W.buf[g & 1][e + 16 * q];
-        fft64_core_pk(x, W.fft[g], e, tw, nosync);                               // bin j at slot bitrev6(j) of W.fft[g]
+        fft64_core_pk(x, W.fft[g], e, tw, wave_lds_sync);                               // bin j at slot bitrev6(j) of W.fft[g]
         if (g < 2) {
 #pragma unroll
             for (int q = 0; q < 4; q++) W.y[g][64 * half + e + 16 * q] = W.fft[g][__brev((unsigned)(e + 16 * q)) >> 26];
         }
-        wsync();
+        wave_lds_sync();
     };
     const uint32_t a_ltf = l0 + 128 + 320;                                   // L-LTF (128), three SIG symbols, HT-STF
     // ---- the two HT-LTF symbols -> TMimoChannelEst (channel_11n.hpp:329-443), as k_mimo_est11n_batch
     symbol_fft(a_ltf, fetch(0, a_ltf + 16 + lane), fetch(1, a_ltf + 16 + lane), 0);
     symbol_fft(a_ltf + 80, fetch(0, a_ltf + 96 + lane), fetch(1, a_ltf + 96 + lane), 1);
     {
-#pragma clang fp contract(off)
-        const int i = lane, k = i < 32 ? i : i - 64;
+        const int k = lane < 32 ? lane : lane - 64;
         const bool negate = !(k >= -28 && k <= 28 && kHtLtf[k + 28] == 1);
-        cpx hh[2][2];
+        cpx hh[2][2]; uint32_t w[4];
+        mimo_est_carrier(unpack(W.y[0][lane]), unpack(W.y[0][lane + 64]), unpack(W.y[1][lane]), unpack(W.y[1][lane + 64]), negate, hh, w);
 #pragma unroll
-        for (int r = 0; r < 2; r++) {
-            const cpx p = unpack(W.y[r][i]), q = unpack(W.y[r][i + 64]);
-            cpx d = sra(csubs(p, q), 1), s = sra(cadds(p, q), 1);
-            if (negate) { d = mk(neg16(d.re), neg16(d.im)); s = mk(neg16(s.re), neg16(s.im)); }
-            hh[r][0] = d; hh[r][1] = s;
-        }
-        const cf a00 = { (float)hh[0][0].re, (float)hh[0][0].im }, a01 = { (float)hh[0][1].re, (float)hh[0][1].im };
-        const cf a10 = { (float)hh[1][0].re, (float)hh[1][0].im }, a11 = { (float)hh[1][1].re, (float)hh[1][1].im };
-        const cf ad = cf_mul(a00, a11), bc = cf_mul(a01, a10);
-        const cf det = { ad.re - bc.re, ad.im - bc.im };
-        const float nn = ((det.re * det.re) + (det.im * det.im)) / 65536.0f;
-        const cf ds = { det.re, -det.im }, m01 = { -a01.re, -a01.im }, m10 = { -a10.re, -a10.im };
-        const cf r00 = cf_mul(a11, ds), r01 = cf_mul(m01, ds), r10 = cf_mul(m10, ds), r11 = cf_mul(a00, ds);
-        W.hinv[0][i] = pack(mk(cvtps_sat16(r00.re / nn), cvtps_sat16(r00.im / nn)));
-        W.hinv[1][i] = pack(mk(cvtps_sat16(r01.re / nn), cvtps_sat16(r01.im / nn)));
-        W.hinv[2][i] = pack(mk(cvtps_sat16(r10.re / nn), cvtps_sat16(r10.im / nn)));
-        W.hinv[3][i] = pack(mk(cvtps_sat16(r11.re / nn), cvtps_sat16(r11.im / nn)));
+        for (int m = 0; m < 4; m++) W.hinv[m][lane] = w[m];
     }
-    wsync();
+    wave_lds_sync();
     // ---- the data symbols, in order
     const uint32_t a_data = a_ltf + 160;
     const uint32_t S = 104u * (uint32_t)nb;
@@ -687,12 +617,9 @@ __global__ void __launch_bounds__(256) k_frame11n(Frame11nArgs A)
         symbol_fft(pos, x0, x1, 0);
         // TMimoChannelComp -> TPilotTrack_11n -> demap -> de-interleave -> stream parser
         const cpx p = unpack(W.y[0][lane]), q = unpack(W.y[1][lane]);
-        int ar, ai, br, bi;
-        mul32(unpack(W.hinv[0][lane]), p, ar, ai); mul32(unpack(W.hinv[1][lane]), q, br, bi);
-        W.xs[0][lane] = pack(mk(sat16((int)((unsigned)ar + (unsigned)br) >> 9), sat16((int)((unsigned)ai + (unsigned)bi) >> 9)));
-        mul32(unpack(W.hinv[2][lane]), p, ar, ai); mul32(unpack(W.hinv[3][lane]), q, br, bi);
-        W.xs[1][lane] = pack(mk(sat16((int)((unsigned)ar + (unsigned)br) >> 9), sat16((int)((unsigned)ai + (unsigned)bi) >> 9)));
-        wsync();
+        W.xs[0][lane] = pack(mimo_comp_row(unpack(W.hinv[0][lane]), unpack(W.hinv[1][lane]), p, q));
+        W.xs[1][lane] = pack(mimo_comp_row(unpack(W.hinv[2][lane]), unpack(W.hinv[3][lane]), p, q));
+        wave_lds_sync();
         {
             const int k = lane & 3, sidx = (lane >> 2) & 1;
             const int pbin = k == 0 ? 64 - 21 : k == 1 ? 64 - 7 : k == 2 ? 7 : 21;
@@ -704,17 +631,9 @@ __global__ void __launch_bounds__(256) k_frame11n(Frame11nArgs A)
         }
         if (lane < 52) {
 #pragma unroll
-            for (int s = 0; s < 2; s++) {
-                const cpx x = unpack(W.xs[s][data_bin(lane)]);
-                const int re = min(max(x.re, -128), 127) + 128, im = min(max(x.im, -128), 127) + 128;
-                uint8_t* o = W.soft[s] + nb * lane;                           // T11nDemap{BPSK,QPSK,QAM16,QAM64} (demapper11n.hpp:89-309), as k_demap11n_batch
-                if (nb == 1) o[0] = s_lut[0][re];
-                else if (nb == 2) { o[0] = s_lut[0][re]; o[1] = s_lut[0][im]; }
-                else if (nb == 4) { o[0] = s_lut[1][re]; o[1] = s_lut[2][re]; o[2] = s_lut[1][im]; o[3] = s_lut[2][im]; }
-                else { o[0] = s_lut[3][re]; o[1] = s_lut[4][re]; o[2] = s_lut[5][re]; o[3] = s_lut[3][im]; o[4] = s_lut[4][im]; o[5] = s_lut[5][im]; }
-            }
+            for (int s = 0; s < 2; s++) demap11n_store(W.soft[s] + nb * lane, s_lut, unpack(W.xs[s][data_bin(lane)]), nb);
         }
-        wsync();
+        wave_lds_sync();
         {
             const uint8_t* both = W.soft[0];
             uint8_t* o = dst + (size_t)d * S + lane;
@@ -725,7 +644,7 @@ __global__ void __launch_bounds__(256) k_frame11n(Frame11nArgs A)
                 for (int t = 4; t < 10; t++) if (dt[t] != 0xFFFFFFFFu) o[64 * t] = both[dt[t]];
             }
         }
-        wsync();
+        wave_lds_sync();
     }
     for (uint32_t g = nproc * S + lane; g < F.nsoft; g += 64) dst[g] = 0;                     // the zero soft values of a flush at the end of the capture
 }
@@ -743,29 +662,10 @@ __global__ void __launch_bounds__(256) k_finish11n(Frame11nArgs A)
     const JobRef jr = locate_job(blockIdx.x * 4 + wv, A.njobs);
     if (!jr.ok) return;
     const N11Frame F = A.frames[(size_t)jr.list * A.nrows + jr.idx];
-    const uint8_t* dec = A.vout + (size_t)F.slot0 * A.out_per_slot;
-    uint8_t* mp = A.mpdu + (size_t)F.row * 4096;
-    uint8_t* bytes = reinterpret_cast<uint8_t*>(s_bufs[wv]);
-    const uint32_t L = F.ht_len;
-    const unsigned seed = dec[1] >> 1;
-    const unsigned phase = A.T.scr_phase[seed & 0x7F];
-    for (uint32_t i = lane; i < L; i += 64) {
-        const unsigned sb = phase == 255 ? 0u : A.T.scr_seq[(phase + 8u * i) % 127u];
-        const unsigned o = dec[2 + i] ^ sb;
-        bytes[i] = (uint8_t)o; mp[i] = (uint8_t)o;
-    }
-    wsync();
-    const int n = L >= 4 ? (int)L - 4 : 0;
-    uint32_t crc;
-    if (n >= 4) crc = crc32_wave(bytes, n, s_crc, s_z, lane);
-    else { crc = 0xFFFFFFFFu; for (int i = 0; i < n; i++) crc = (crc >> 8) ^ s_crc[(bytes[i] ^ crc) & 0xFF]; }
-    if (lane == 0) {
-        uint32_t fcs = 0;
-        if (L >= 4) fcs = (uint32_t)bytes[L - 4] | ((uint32_t)bytes[L - 3] << 8) | ((uint32_t)bytes[L - 2] << 16) | ((uint32_t)bytes[L - 1] << 24);
-        Rx11bRow& r = A.rows[F.row];
-        r.crc32 = fcs;
-        r.error_code = ((~crc) == fcs) ? E_OK : E_CRC;
-    }
+    uint32_t fcs;
+    const uint32_t verdict = finish_frame(A.T, A.vout + (size_t)F.slot0 * A.out_per_slot, F.ht_len, reinterpret_cast<uint8_t*>(s_bufs[wv]),
+                                          A.mpdu + (size_t)F.row * 4096, s_crc, s_z, lane, fcs);
+    if (lane == 0) { Rx11bRow& r = A.rows[F.row]; r.crc32 = fcs; r.error_code = verdict; }
 }
 
 }  // namespace sora

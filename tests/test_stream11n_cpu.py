@@ -1,6 +1,6 @@
 """Stream continuation of the 802.11n receive handle (sora_rx11n_set_stream_mode), checked without a GPU: the two exports are in the library,
 declared in the header and bound with argument types; a null handle is refused before any device work; and the stream form of the scan
-kernel ships as a kernel of its own that, like the default front ends, keeps every register in registers (code-object metadata)."""
+kernel ships as a kernel of its own that, like the default front ends and the data field's kernels behind them, keeps every register in registers (code-object metadata)."""
 import ctypes
 import os
 import re
@@ -79,8 +79,8 @@ def kernel_metadata(tmp_path):
 
 def test_stream_scan_kernel_exists_and_nothing_spills(tmp_path):
     md = kernel_metadata(tmp_path)
-    names = {re.sub(r"^_ZN4sora\d+(\w+?)ENS_\d+Scan11nArgsE.*$", r"\1", k): v for k, v in md.items()}
-    for k in ("k_scan11n", "k_scan_ht40", "k_scan11n_stream"):
+    names = {re.sub(r"^_ZN4sora\d+(\w+?)ENS_\d+(?:Scan|Frame)11nArgsE.*$", r"\1", k): v for k, v in md.items()}
+    for k in ("k_scan11n", "k_scan_ht40", "k_scan11n_stream", "k_frame11n", "k_finish11n"):
         assert k in names, "kernel %s missing from libsora_hip.so (found %s)" % (k, sorted(names))
         assert names[k]["private_segment_fixed_size"] == 0 and names[k].get("vgpr_spill_count", 0) == 0, (k, names[k])
     waves = lambda v: 512 // ((v + 7) // 8 * 8)                          # waves per SIMD the VGPR budget allows (gfx950: 512 per lane)
