@@ -387,6 +387,26 @@ size_t sora_hip_tx11a_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps);
 int sora_hip_tx11a(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps,
                    const uint8_t* d_seed, size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream);
 
+/* The same transmitter at a Sora radio's own 44 MHz: CreateModGraph11a_44M + CreatePreamble11a_44M (fb11amod_config.hpp), the graphs
+ * the reference's live applications send with (kernel/bb/umxsdrbrick/dot11main.cpp:222-223, umxsdra/dot11main.cpp:201-202,
+ * umxsniffer/dot11main.cpp:212-213, kernel/bb/demod11/fb11a_mod.cpp:39-40).  They are the 40 MHz graphs with TUpsample40MTo44M
+ * (Brick11/src/sampling.hpp:8-32, 40MTo44M.hpp) between TIFFTx (or TTS11aSrc) and TPackSample16to8.  The brick turns each 160-sample
+ * block x of 16-bit samples into 176 samples y and carries nothing from block to block; for I and Q apart, m = 0..15:
+ *     mh(a, c)  = (a * c + 16384) >> 15                                           (_mm_mulhrs_epi16)
+ *     S(k)      = floor(k * 32767 / 11)                                           (k = 1..10)
+ *     y[11m]    = mh(x[10m], 32767)
+ *     y[11m+r]  = int16(mh(x[10m+r-1], S(r)) + mh(x[10m+r], S(11-r)))             (r = 1..10)
+ * and only then are the samples saturated to 8 bits: upsampling the 40 MHz COMPLEX8 stream instead differs wherever that stream
+ * touches a rail.  y[175] needs x[160], which the reference loads from behind its input block (40MTo44M.hpp:112).  The preamble source
+ * hands its 640 samples on as one burst, so its blocks 0..2 see the next block's first sample there, and so do they here.  Its block 3,
+ * the SIGNAL symbol and every data symbol read whatever memory follows the pin queue's buffer -- an accident of the build's layout, not
+ * arithmetic -- and here x[160] = 0 for them: sample 176 j + 175 of a frame, j >= 3, is the closed form with x[160] = 0.
+ * A frame is sora_hip_tx11a44_samples(len, rate) = 11/10 of sora_hip_tx11a_samples(len, rate) samples (0 where that is 0), d_out_off
+ * counts 44 MHz samples; every other rule, error code and null check is sora_hip_tx11a's. */
+size_t sora_hip_tx11a44_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps);
+int sora_hip_tx11a44(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps,
+                     const uint8_t* d_seed, size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream);
+
 /* 802.11n 2x2 transmitter: the reference's modulation graphs CreatePreambleGraph11n + CreateSigGraph11n + CreateModGraph11n
  * (kernel/bb/demod11/fb11nmod_config.hpp) as Test11N_FB_Mod runs them (fb11n_mod.cpp:28-70): L-STF, L-LTF, L-SIG, HT-SIG, HT-STF,
  * HT-LTF1, HT-LTF2, data; 20 MHz, long GI, MCS 8..14 (two spatial streams, one per TX chain), a batch of frames per call.

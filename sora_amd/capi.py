@@ -62,8 +62,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_hip_freq_comp11a", "sora_hip_equalize11a", "sora_hip_phase_comp11a", "sora_hip_demap11a", "sora_hip_deinterleave11a", "sora_hip_viterbi11a",
                       "sora_hip_viterbi11a_ws", "sora_hip_viterbi11a_workspace_bytes", "sora_hip_viterbi11n_ws", "sora_hip_viterbi11n_workspace_bytes",
                       "sora_hip_viterbi_window_stats",
-           "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx11b",
-           "sora_hip_tx11b_samples",
+           "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11a44", "sora_hip_tx11a44_samples",
+           "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx11b", "sora_hip_tx11b_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n", "sora_rx11b_create",
                       "sora_rx11b_destroy", "sora_rx11b_stream", "sora_rx11b_synchronize", "sora_rx11b_process_dev", "sora_rx11b_process", "sora_rx11b_results", "sora_rx11b_ticket",
@@ -214,6 +214,8 @@ def load(build_if_missing=True):
     L.sora_hip_stream_synchronize.argtypes = [ctypes.c_void_p]
     L.sora_hip_tx11a_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11a_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.sora_hip_tx11a44_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11a44_samples.restype = ctypes.c_size_t
+    L.sora_hip_tx11a44.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.sora_hip_tx11n_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11n_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11n.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
     L.sora_hip_tx11b_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11b_samples.restype = ctypes.c_size_t
@@ -1064,14 +1066,26 @@ def ingest(raw, flags, stream=None, sync=True):
     return out[:got.value]
 
 
-def tx11a_samples(mpdu_len_nofcs, rate_kbps):
-    return int(load().sora_hip_tx11a_samples(int(mpdu_len_nofcs), int(rate_kbps)))
+def _tx11a_entry(sample_rate_mhz):
+    """(samples, call) of the 802.11a transmitter at 40 MHz (`demod11 -m`'s file format) or 44 MHz (a Sora radio's own rate)."""
+    if sample_rate_mhz == 40:
+        return load().sora_hip_tx11a_samples, load().sora_hip_tx11a
+    if sample_rate_mhz == 44:
+        return load().sora_hip_tx11a44_samples, load().sora_hip_tx11a44
+    raise ValueError("tx11a: sample_rate_mhz must be 40 or 44, not %r" % (sample_rate_mhz,))
 
 
-def tx11a(mpdus, rates_kbps, seeds=None, device=0, stream=None, sync=True, gaps=None):
+def tx11a_samples(mpdu_len_nofcs, rate_kbps, sample_rate_mhz=40):
+    """Samples of one 802.11a frame at 40 or 44 MHz (sora_hip_tx11a_samples / sora_hip_tx11a44_samples); 0 for an unsupported rate or length."""
+    return int(_tx11a_entry(sample_rate_mhz)[0](int(mpdu_len_nofcs), int(rate_kbps)))
+
+
+def tx11a(mpdus, rates_kbps, seeds=None, device=0, stream=None, sync=True, gaps=None, sample_rate_mhz=40):
     """Modulate a batch of MPDUs (bytes WITHOUT FCS) on the GPU.  -> (int8 CUDA tensor [total,2] COMPLEX8 @40 MHz, offsets list).
-    Frame f occupies samples offsets[f] .. offsets[f+1] (gaps[f] zero samples in front of frame f, if given, included at its start)."""
+    Frame f occupies samples offsets[f] .. offsets[f+1] (gaps[f] zero samples in front of frame f, if given, included at its start).
+    sample_rate_mhz=44: the reference's 44 MHz graphs (TUpsample40MTo44M in front of the pack), samples, offsets and gaps at 44 MHz."""
     import torch
+    count, call = _tx11a_entry(sample_rate_mhz)
     n = len(mpdus)
     seeds = [0xFF] * n if seeds is None else list(seeds)
     lens = [len(m) for m in mpdus]
@@ -1079,7 +1093,7 @@ def tx11a(mpdus, rates_kbps, seeds=None, device=0, stream=None, sync=True, gaps=
     blob = np.zeros(max(int(off[-1]), 4), np.uint8)
     for f, m in enumerate(mpdus):
         blob[off[f]:off[f] + lens[f]] = np.frombuffer(bytes(m), np.uint8)
-    ns = [tx11a_samples(l, r) for l, r in zip(lens, rates_kbps)]
+    ns = [int(count(int(l), int(r))) for l, r in zip(lens, rates_kbps)]
     if any(v == 0 for v in ns):
         raise SoraError(-1, "tx11a: unsupported rate or length")
     gaps = [0] * n if gaps is None else [int(v) for v in gaps]
@@ -1091,8 +1105,8 @@ def tx11a(mpdus, rates_kbps, seeds=None, device=0, stream=None, sync=True, gaps=
     d_len = torch.from_numpy(np.asarray(lens, np.int32)).to(dev); d_rate = torch.from_numpy(np.asarray(rates_kbps, np.int32)).to(dev)
     d_seed = t(np.asarray(seeds, np.uint8), np.uint8); d_ooff = torch.from_numpy(first.astype(np.int64)).to(dev)
     out = torch.zeros((int(ooff[-1]), 2), dtype=torch.int8, device=dev)
-    _check(load().sora_hip_tx11a(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_rate), _dev_ptr(d_seed), n,
-                                 _dev_ptr(out), _dev_ptr(d_ooff), _stream_ptr(stream)))
+    _check(call(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_rate), _dev_ptr(d_seed), n,
+                _dev_ptr(out), _dev_ptr(d_ooff), _stream_ptr(stream)))
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     return out, [int(v) for v in ooff]

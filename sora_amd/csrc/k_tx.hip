@@ -2,7 +2,8 @@
 //   TBB11aSrc -> T11aSc -> TBB11aMRSelect -> TConvEncode_{12,23,34} -> T11aInterleave* -> TMap11a* -> T11aAddPilot
 //   -> TIFFTx -> TPackSample16to8 -> TModSink          (kernel/bb/demod11/fb11amod_config.hpp:74-110)
 // plus the preamble source (kernel/bb/Brick11/src/preamble11a.hpp:19-140).  Output: COMPLEX8 at 40 MHz, what
-// `demod11 -m` writes.  Every stage is data-parallel once restated:
+// `demod11 -m` writes -- or, k_tx11a<true>, at 44 MHz: CreateModGraph11a_44M / CreatePreamble11a_44M, the same graphs with TUpsample40MTo44M
+// (Brick11/src/sampling.hpp:8-32, 40MTo44M.hpp) in front of TPackSample16to8, what the reference's radio applications send.  Every stage is data-parallel once restated:
 //   * scrambler (scramble.hpp:237-251): the register sequence is a phase of one period-127 cycle -> two table reads
 //   * convolutional encoder (conv_enc.hpp:6-14): coded bit = xor of five of the last seven input bits; the puncturing
 //     patterns map a coded-bit index to (input bit, generator) in closed form
@@ -46,7 +47,41 @@ __device__ __forceinline__ uint32_t pk_sra_clamp8(uint32_t v, uint32_t sh)
     const s16x2_t x = __builtin_bit_cast(s16x2_t, v) >> __builtin_bit_cast(s16x2_t, sh);
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_elementwise_max(x, lo), hi));
 }
-template <typename SYNC>
+// TUpsample40MTo44M (40MTo44M.hpp:66-125) on one 160-sample block x -> 176 samples y, in 16 bits, no state between blocks.  In closed form, with
+//   mh(a, c) = (a c + 16384) >> 15 (_mm_mulhrs_epi16, I and Q apart) and S(k) = floor(32767 k / 11) (S1(), 40MTo44M.hpp:12):  for j = 11 m + r, r = 0..10,
+//   y[j] = int16(mh(x[j - m - 1], S(r)) + mh(x[j - m], S(11 - r)))          (S(0) = 0, S(11) = 32767: y[11 m] = mh(x[10 m], 32767))
+// y[175] asks for x[160]: the reference loads it from behind its input (40MTo44M.hpp:112); here a block ends in x[160] = 0 unless the same
+// pin-queue burst holds the next block (the preamble's blocks 0..2).
+__device__ __forceinline__ int mulhrs(int a, int c) { return (a * c + 16384) >> 15; }
+__device__ __forceinline__ uint32_t up44_mix(uint32_t lo, uint32_t hi, int r)    // -> COMPLEX8 in the low 16 bits (the clamp of TPackSample16to8 comes last)
+{
+    const int cl = r * 32767 / 11, ch = (11 - r) * 32767 / 11;
+    const int re = (short)(mulhrs((short)lo, cl) + mulhrs((short)hi, ch)), im = (short)(mulhrs((int)lo >> 16, cl) + mulhrs((int)hi >> 16, ch));
+    return (uint32_t)(sat8(re) & 255) | ((uint32_t)(sat8(im) & 255) << 8);
+}
+// sample i of the 40 MHz symbol as TIFFTx hands it on (16 bits, shifted), read where the IFFT's last stage left it; 0 behind the symbol
+__device__ __forceinline__ uint32_t x40_at(const uint32_t* s_bins, int i)
+{
+    const uint32_t sh = (i < 2 || i >= 158) ? 0x00050005u : 0x00040004u;
+    const s16x2_t v = __builtin_bit_cast(s16x2_t, s_bins[__brev((unsigned)((i + 96) & 127)) >> 25]) >> __builtin_bit_cast(s16x2_t, sh);
+    return i >= 160 ? 0u : __builtin_bit_cast(uint32_t, v);
+}
+// 44 MHz samples 4 w .. 4 w + 3 of the symbol (w = 0..43) as one 8-byte word: they lie between five 40 MHz samples in a row
+__device__ __forceinline__ uint2 up44_word(const uint32_t* s_bins, int w)
+{
+    const int j0 = 4 * w, base = j0 - j0 / 11;
+    uint32_t v[5], b[4];
+#pragma unroll
+    for (int t = 0; t < 5; t++) v[t] = x40_at(s_bins, base - 1 + t);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int j = j0 + k, m = j / 11, r = j - 11 * m;
+        const bool step = j - m - base == k;                                     // (false once a multiple of 11 lies in j0 + 1 .. j: there the input index stands still)
+        b[k] = up44_mix(step || k == 0 ? v[k] : v[k - 1], step || k == 0 ? v[k + 1] : v[k], r);
+    }
+    return make_uint2(b[0] | (b[1] << 16), b[2] | (b[3] << 16));
+}
+template <bool UP44, typename SYNC>
 __device__ __forceinline__ void ifft_emit(uint32_t* s_bins, int e, const Fft128Tw& tw, const EmitPlan& P, int8_t* out8, SYNC sync)
 {
     pcx x[4];
@@ -55,6 +90,18 @@ __device__ __forceinline__ void ifft_emit(uint32_t* s_bins, int e, const Fft128T
     for (int m = 0; m < 4; m++) x[m] = s_bins[e + 32 * m];
     ifft128_core_pk(x, s_bins, e, tw, sync);                                     // IFFT<128> on packed COMPLEX16 (bit-exact with fft128_core<true>)
     if (out8 == nullptr) return;                                                 // (a group past the last symbol only keeps the barriers company)
+    if constexpr (UP44) {                                                        // 176 samples = 44 words of 8 bytes: one per lane, then 12 more
+        if ((reinterpret_cast<uintptr_t>(out8) & 7u) == 0) {
+            reinterpret_cast<uint2*>(out8)[e] = up44_word(s_bins, e);
+            if (e < 12) reinterpret_cast<uint2*>(out8)[32 + e] = up44_word(s_bins, 32 + e);
+        } else {
+            for (int j = e; j < 176; j += 32) {
+                const int m = j / 11;
+                reinterpret_cast<uint16_t*>(out8)[j] = (uint16_t)up44_mix(x40_at(s_bins, j - m - 1), x40_at(s_bins, j - m), j - 11 * m);
+            }
+        }
+        return;
+    }
     if ((reinterpret_cast<uintptr_t>(out8) & 7u) == 0) {
         const uint32_t w0 = pk_sra_clamp8(s_bins[P.a4], P.sh01), w1 = pk_sra_clamp8(s_bins[P.a4 + 64], P.sh01);
         const uint32_t w2 = pk_sra_clamp8(s_bins[P.a4 + 32], 0x00040004u), w3 = pk_sra_clamp8(s_bins[P.a4 + 96], 0x00040004u), w4 = pk_sra_clamp8(s_bins[P.a1], P.shs);
@@ -70,8 +117,8 @@ __device__ __forceinline__ void ifft_emit(uint32_t* s_bins, int e, const Fft128T
     }
 }
 
-// The 640-sample preamble (preamble11a.hpp:19-100), computed once per device into a table.
-__global__ void __launch_bounds__(64) k_tx_preamble(int8_t* out8, Tables T)
+// The 640-sample preamble (preamble11a.hpp:19-100), computed once per device into a table, and the 704 samples of its 44 MHz form.
+__global__ void __launch_bounds__(64) k_tx_preamble(int8_t* out8, int8_t* out44, Tables T)
 {
     __shared__ uint32_t s_f[2][128];
     __shared__ uint32_t s_t[2][128];
@@ -107,11 +154,24 @@ __global__ void __launch_bounds__(64) k_tx_preamble(int8_t* out8, Tables T)
         cpx v = unpack(s_lut[i]);
         if (i == 0 || i == 1 || i == 318 || i == 319 || i == 320 || i == 321 || i == 638 || i == 639) v = sra(v, 1);
         out8[2 * i] = (int8_t)sat8(v.re); out8[2 * i + 1] = (int8_t)sat8(v.im);
+        s_lut[i] = pack(v);
+    }
+    sync();
+    // CreatePreamble11a_44M: TUpsample40MTo44M over the four 160-sample blocks of the 16-bit preamble, before the clamp.  The source hands all 640 samples on as one
+    // burst, so blocks 0..2 find the next block's first sample behind their last one; block 3 ends in x[160] = 0.
+    for (int j = threadIdx.x; j < 704; j += 64) {
+        const int blk = j / 176, jj = j - 176 * blk, m = jj / 11, hi = 160 * blk + jj - m;
+        reinterpret_cast<uint16_t*>(out44)[j] = (uint16_t)up44_mix(s_lut[max(hi - 1, 0)], hi < 640 ? s_lut[hi] : 0u, jj - 11 * m);
     }
 }
 
-__global__ void __launch_bounds__(256, 8) k_tx11a(TxArgs A)
+// UP44: COMPLEX8 at 44 MHz -- A.preamble is the 704-sample table, A.out_off counts 44 MHz samples, a symbol is 176 samples.  Everything up to the IFFT is one code.
+// The 44 MHz form keeps its two words' addresses, weights and selects in registers across the symbol loop (98 of them): four workgroups per CU without scratch,
+// where eight would spill 50 dwords; the 40 MHz form stays at eight.
+template <bool UP44>
+__global__ void __launch_bounds__(256, UP44 ? 4 : 8) k_tx11a(TxArgs A)
 {
+    constexpr int kPre = UP44 ? 704 : 640, kSym = UP44 ? 176 : 160;
     __shared__ alignas(4) uint8_t s_data[2608];
     // generator outputs A (133) / B (171) of the whole data field, bit i of the stream = bit i & 31 of word i >> 5
     __shared__ uint32_t s_gab[2][656];
@@ -167,7 +227,7 @@ __global__ void __launch_bounds__(256, 8) k_tx11a(TxArgs A)
             s_data[i] = (uint8_t)c;
         }
     }
-    for (int i = tid; i < 640; i += 256) reinterpret_cast<uint16_t*>(out)[i] = reinterpret_cast<const uint16_t*>(A.preamble)[i];
+    for (int i = tid; i < kPre; i += 256) reinterpret_cast<uint16_t*>(out)[i] = reinterpret_cast<const uint16_t*>(A.preamble)[i];
     __syncthreads();
     // TConvEncode_* (conv_enc.hpp:6-14) 32 input bits at a time: A = x ^ x>>2 ^ x>>3 ^ x>>5 ^ x>>6, B = x ^ x>>1 ^ x>>2 ^ x>>3 ^ x>>6 over the bit
     // stream (x>>k = the bit k positions EARLIER: shifted in from the previous word; the encoder starts from state 0)
@@ -278,9 +338,11 @@ __global__ void __launch_bounds__(256, 8) k_tx11a(TxArgs A)
                 s_bins[g][bin < 32 ? bin : bin + 64] = pack(mk(e == 1 ? -p : p, 0));
             }
         }
-        ifft_emit(s_bins[g], e, tw, plan, active ? out + 2 * (640 + 160 * (size_t)s) : (int8_t*)nullptr, sync);
+        ifft_emit<UP44>(s_bins[g], e, tw, plan, active ? out + 2 * (kPre + kSym * (size_t)s) : (int8_t*)nullptr, sync);
         sync();
     }
 }
+template __global__ void k_tx11a<false>(TxArgs A);
+template __global__ void k_tx11a<true>(TxArgs A);
 
 }  // namespace sora

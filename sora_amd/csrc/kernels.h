@@ -124,11 +124,11 @@ struct TxArgs {                // sora_hip_tx11a (k_tx.hip)
     const uint8_t*  seed;      // scrambler register before the first byte (the harness uses 0xFF)
     int8_t*         out8;      // COMPLEX8 stream
     const uint64_t* out_off;   // first sample of frame f
-    const int8_t*   preamble;  // 640 samples
+    const int8_t*   preamble;  // 640 samples (UP44: 704)
     Tables          T;
 };
-__global__ void k_tx_preamble(int8_t* out8, Tables T);
-__global__ void k_tx11a(TxArgs A);
+__global__ void k_tx_preamble(int8_t* out8, int8_t* out44, Tables T);   // 640 samples at 40 MHz, 704 at 44 MHz
+template <bool UP44> __global__ void k_tx11a(TxArgs A);                 // UP44: TUpsample40MTo44M in front of the 16 -> 8 bit pack (sora_hip_tx11a44)
 
 // ---- 802.11n 2x2 transmitter (k_tx11n.hip)
 struct Tx11nArgs {             // sora_hip_tx11n

@@ -321,7 +321,7 @@ struct DevTables {
     Tables T{};
     std::vector<void*> allocs;
     int device = -1;
-    int8_t* tx_preamble = nullptr;      // 640 COMPLEX8 samples (k_tx_preamble), built on first use of the transmitter
+    int8_t* tx_preamble = nullptr;      // 640 COMPLEX8 samples at 40 MHz, then 704 at 44 MHz (k_tx_preamble), built on first use of the transmitter
     uint32_t* tx11n_preamble = nullptr; // [2][1120] COMPLEX16 (tx11n_preamble_host), built on first use of the 802.11n transmitter
 };
 
@@ -1675,22 +1675,23 @@ size_t sora_hip_tx11a_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps)
     return 640 + 160 * (size_t)(1 + nbytes * 8 / (uint32_t)nd);
 }
 
-int sora_hip_tx11a(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_seed,
-                   size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream)
+// both rates: the 44 MHz form differs in the kernel's last step and in the preamble table alone
+static int tx11a_launch(bool up44, const char* who, const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_seed,
+                        size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream)
 {
     if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_mpdu || !d_off || !d_len || !d_rate_kbps || !d_seed || !d_out || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_tx11a: null pointer");
+    if (!d_mpdu || !d_off || !d_len || !d_rate_kbps || !d_seed || !d_out || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, who);
     if (nframes == 0) return SORA_OK;
     DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     hipStream_t st = (hipStream_t)stream;
     {
         // built once per device, under the lock, and complete before it is published: a call on another stream or thread
-        // must never see a half-written preamble
+        // must never see a half-written preamble (640 samples at 40 MHz, then 704 at 44 MHz)
         std::lock_guard<std::mutex> lock(g_stage_mutex);
         if (!D->tx_preamble) {
             int8_t* p = nullptr;
-            HIPCHK(hipMalloc((void**)&p, 1280));
-            hipLaunchKernelGGL(k_tx_preamble, dim3(1), dim3(64), 0, st, p, D->T);
+            HIPCHK(hipMalloc((void**)&p, 1280 + 1408));
+            hipLaunchKernelGGL(k_tx_preamble, dim3(1), dim3(64), 0, st, p, p + 1280, D->T);
             hipError_t e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) { (void)hipFree(p); return fail(SORA_ERR_HARDWARE_FAILED, "k_tx_preamble", e); }
@@ -1699,10 +1700,28 @@ int sora_hip_tx11a(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t*
     }
     TxArgs A{};
     A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.rate = d_rate_kbps; A.seed = d_seed; A.out8 = d_out; A.out_off = d_out_off;
-    A.preamble = D->tx_preamble; A.T = D->T;
-    hipLaunchKernelGGL(k_tx11a, dim3((unsigned)nframes), dim3(256), 0, st, A);
+    A.preamble = D->tx_preamble + (up44 ? 1280 : 0); A.T = D->T;
+    if (up44) hipLaunchKernelGGL(k_tx11a<true>, dim3((unsigned)nframes), dim3(256), 0, st, A);
+    else      hipLaunchKernelGGL(k_tx11a<false>, dim3((unsigned)nframes), dim3(256), 0, st, A);
     HIPCHK(hipGetLastError());
     return SORA_OK;
+}
+
+int sora_hip_tx11a(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_seed,
+                   size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream)
+{
+    return tx11a_launch(false, "sora_hip_tx11a: null pointer", d_mpdu, d_off, d_len, d_rate_kbps, d_seed, nframes, d_out, d_out_off, stream);
+}
+
+size_t sora_hip_tx11a44_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps)
+{
+    return sora_hip_tx11a_samples(mpdu_len_nofcs, rate_kbps) / 10 * 11;          // whole 160-sample blocks, 176 samples each
+}
+
+int sora_hip_tx11a44(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_seed,
+                     size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream)
+{
+    return tx11a_launch(true, "sora_hip_tx11a44: null pointer", d_mpdu, d_off, d_len, d_rate_kbps, d_seed, nframes, d_out, d_out_off, stream);
 }
 
 // ---- 802.11n 2x2 transmitter
