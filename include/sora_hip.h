@@ -423,6 +423,26 @@ size_t sora_hip_tx11n_samples(uint32_t mpdu_len_nofcs, uint32_t mcs);
 int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
                    size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
 
+/* 40 MHz HT 2x2 transmitter: the frame the 40 MHz receiver below (sora_ht40_*) takes -- HT-mixed format, 40 MHz, two spatial streams,
+ * long GI, MCS 8..14, a batch of frames per call.  PARITY UNPINNED, as for that receiver: the reference has no 40 MHz graph.  The format is
+ * the one oracle/py_ht40.py (tx_frame) defines: L-STF 320, L-LTF 320, L-SIG 160, HT-SIG 2 x 160, HT-STF 160 samples (the 20 MHz legacy
+ * waveforms on both halves of the channel, the upper half rotated by +90 degrees, identical on both chains, no cyclic shifts), then two
+ * HT-LTF symbols (P = [[1, -1], [1, 1]]) and N_SYM = ceil((16 + 8 (len + 4) + 6) / N_DBPS) data symbols of 160 on 114 carriers; each spatial
+ * stream carries its own PSDU through its own scrambler, encoder and interleaver and leaves on its own TX chain.  The waveform is that
+ * model restated in integers (tests/tx_ht40_model.py) and held to it: every frequency-domain value times A = 16384 (an HT-LTF carrier),
+ * rounded, every symbol through the reference's fixed-point IFFT<128>; this call equals the integer model sample for sample, and the
+ * integer model equals tx_frame x A / 128 to within the transform's rounding (about 10 LSB at an rms of about 1200).
+ * Frame f: two MPDUs WITHOUT FCS (the FCS is appended to each) of d_len[f] bytes each -- HT-SIG carries one LENGTH -- at d_mpdu +
+ * d_off[2 f] (stream 0) and d_mpdu + d_off[2 f + 1] (stream 1), MCS d_mcs[f], scrambler seeds d_seed[2 f], d_seed[2 f + 1] (seven bits
+ * used; d_seed NULL: 0x5D and 0x2B, the model's defaults).  Writes sora_hip_tx_ht40_samples(len, mcs) = 1280 + 160 (2 + N_SYM) COMPLEX16
+ * samples at 40 MHz per chain at sample d_out_off[f] of d_out0 (TX chain 0) and of d_out1 (TX chain 1); HT-LTF 1 starts 1280 samples in
+ * (sora_ht40_frame.offset).  Accepted: MCS 8..14 and 1..3996 bytes without FCS (LENGTH = len + 4 <= 4000, the receiver's limit; N_SYM =
+ * sora_ht40_symbols(len + 4, len + 4, n_bpsc, code_rate)); sora_hip_tx_ht40_samples is 0 for anything else.  Null checks, error codes,
+ * the behaviour without a device and "a frame that is not accepted gets nothing written, the others are not affected" are sora_hip_tx11n's. */
+size_t sora_hip_tx_ht40_samples(uint32_t mpdu_len_nofcs, uint32_t mcs);
+int sora_hip_tx_ht40(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
+                     size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
+
 /* 802.11b transmitter: the reference's modulation graph CreateModGraph (kernel/bb/demod11/fb11bmod_config.hpp:28-50) as
  * Test11B_FB_Mod runs it (fb11b_mod.cpp:40-70): long preamble (SYNC, SFD), PLCP header, MPDU + FCS at 1, 2, 5.5 or 11 Mbps, Barker
  * DBPSK / DQPSK or CCK, TQuickPulseShaper; a batch of frames per call.

@@ -63,7 +63,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_hip_viterbi11a_ws", "sora_hip_viterbi11a_workspace_bytes", "sora_hip_viterbi11n_ws", "sora_hip_viterbi11n_workspace_bytes",
                       "sora_hip_viterbi_window_stats",
            "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11a44", "sora_hip_tx11a44_samples",
-           "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx11b", "sora_hip_tx11b_samples",
+           "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx_ht40", "sora_hip_tx_ht40_samples", "sora_hip_tx11b", "sora_hip_tx11b_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n", "sora_rx11b_create",
                       "sora_rx11b_destroy", "sora_rx11b_stream", "sora_rx11b_synchronize", "sora_rx11b_process_dev", "sora_rx11b_process", "sora_rx11b_results", "sora_rx11b_ticket",
@@ -218,6 +218,8 @@ def load(build_if_missing=True):
     L.sora_hip_tx11a44.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.sora_hip_tx11n_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11n_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11n.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
+    L.sora_hip_tx_ht40_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx_ht40_samples.restype = ctypes.c_size_t
+    L.sora_hip_tx_ht40.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
     L.sora_hip_tx11b_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11b_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11b.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
     L.sora_hip_ingest_count.argtypes = [ctypes.c_size_t, ctypes.c_uint]; L.sora_hip_ingest_count.restype = ctypes.c_size_t
@@ -1145,6 +1147,51 @@ def tx11n(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None):
     out1 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
     _check(load().sora_hip_tx11n(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
                                  _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
+    if sync:
+        _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
+    return out0, out1, [int(v) for v in ooff]
+
+
+def tx_ht40_samples(mpdu_len_nofcs, mcs):
+    """Samples per TX chain of one 40 MHz HT 2x2 frame (sora_hip_tx_ht40_samples): 1280 + 160 (2 + N_SYM); 0 for an MCS or length that is not accepted."""
+    return int(load().sora_hip_tx_ht40_samples(int(mpdu_len_nofcs), int(mcs)))
+
+
+def tx_ht40(mpdus0, mpdus1, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None):
+    """Modulate a batch of MPDU pairs (bytes WITHOUT FCS; mpdus0[f] on spatial stream 0, mpdus1[f] on stream 1, of equal length) as HT-mixed
+    40 MHz two-stream frames on the GPU (MCS 8..14): what RxHt40 receives.
+    -> (out0, out1, offsets): int16 CUDA tensors [total,2] COMPLEX16 @40 MHz for TX chains 0 and 1, and the offsets list.
+    Frame f occupies samples offsets[f] .. offsets[f+1] of both (gaps[f] zero samples in front of frame f, if given, included at its start);
+    its HT-LTF 1 starts 1280 samples after its first sample.
+    seeds: one (seed0, seed1) pair of scrambler seeds per frame (None: 0x5D, 0x2B).  A frame that is not accepted is refused before any launch."""
+    import torch
+    n = len(mpdus0)
+    mcs = [int(m) for m in mcs] if np.ndim(mcs) else [int(mcs)] * n
+    lens = [len(m) for m in mpdus0]
+    if len(mpdus1) != n or len(mcs) != n or any(len(b) != l for b, l in zip(mpdus1, lens)):
+        raise SoraError(-1, "tx_ht40: one MPDU per stream and frame, both of a frame of the same length")
+    ns = [tx_ht40_samples(l, m) for l, m in zip(lens, mcs)]
+    if any(v == 0 for v in ns):
+        raise SoraError(-1, "tx_ht40: unsupported MCS or length (MCS 8..14, 1..3996 bytes)")
+    if seeds is not None and (len(seeds) != n or any(len(p) != 2 for p in seeds)):
+        raise SoraError(-1, "tx_ht40: seeds must hold one pair per frame")
+    off = np.zeros(2 * n + 1, np.int64); np.cumsum([(l + 3) // 4 * 4 for l in lens for _ in range(2)], out=off[1:])
+    blob = np.zeros(max(int(off[-1]), 4), np.uint8)
+    for f in range(n):
+        blob[off[2 * f]:off[2 * f] + lens[f]] = np.frombuffer(bytes(mpdus0[f]), np.uint8)
+        blob[off[2 * f + 1]:off[2 * f + 1] + lens[f]] = np.frombuffer(bytes(mpdus1[f]), np.uint8)
+    gaps = [0] * n if gaps is None else [int(v) for v in gaps]
+    ooff = np.zeros(n + 1, np.uint64); np.cumsum([a + b for a, b in zip(ns, gaps)], out=ooff[1:])
+    first = ooff[:-1] + np.asarray(gaps, np.uint64)
+    dev = torch.device("cuda", device)
+    d_blob = torch.from_numpy(blob).to(dev); d_off = torch.from_numpy(off[:-1].astype(np.int32)).to(dev)
+    d_len = torch.from_numpy(np.asarray(lens, np.int32)).to(dev); d_mcs = torch.from_numpy(np.asarray(mcs, np.int32)).to(dev)
+    d_seed = torch.from_numpy(np.asarray(seeds, np.int64).astype(np.uint8).reshape(-1)).to(dev) if seeds is not None else None
+    d_ooff = torch.from_numpy(first.astype(np.int64)).to(dev)
+    out0 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
+    out1 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
+    _check(load().sora_hip_tx_ht40(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
+                                   _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     return out0, out1, [int(v) for v in ooff]

@@ -424,23 +424,29 @@ __device__ __forceinline__ void pk_r4_inv(pcx x0, pcx x1, pcx x2, pcx x3, const 
     y2 = pk_conj_cmul15(pk_adds(a_c, jb), w[0]);
     y3 = pk_conj_cmul15(pk_subs(a_c, jb), w[2]);
 }
-// fft128_core<true> on packed values; the 8-point terminal stage shared by a lane pair as in fft128_core_pk
-template <typename SYNC>
+// Where point i of a 128-word transform buffer lies when the buffer is swizzled: the four 8-word blocks of quarter k = i >> 5 are permuted by
+// XOR with brev2(k).  Dense, the 32-point stage's lanes (quarter k, j = e & 7) meet four to a bank (word 32 k + j + 8 q: banks are word mod 32);
+// swizzled, the four quarters take four different blocks, and the 128-point stage (32 consecutive words), the terminal stage's 16-byte
+// accesses (a block stays whole and aligned) and the emission's reads at brev7(n) stay free of conflicts as well.
+__device__ __forceinline__ int fft128_swz(int i) { return i ^ ((i >> 1) & 16) ^ ((i >> 3) & 8); }
+// fft128_core<true> on packed values; the 8-point terminal stage shared by a lane pair as in fft128_core_pk.  SWZ: s[] is swizzled
+// (fft128_swz), on entry for x[] -- the caller's to read -- and for the result: time sample n at word fft128_swz(brev7(n)).  Same arithmetic.
+template <bool SWZ = false, typename SYNC>
 __device__ __forceinline__ void ifft128_core_pk(const pcx x[4], uint32_t* s, int e, const Fft128Tw& W, SYNC sync)
 {
     sync();
-    pk_r4_inv(x[0], x[1], x[2], x[3], W.w128, s[e], s[e + 32], s[e + 64], s[e + 96]);
+    pk_r4_inv(x[0], x[1], x[2], x[3], W.w128, s[e], s[(SWZ ? e ^ 16 : e) + 32], s[(SWZ ? e ^ 8 : e) + 64], s[(SWZ ? e ^ 24 : e) + 96]);
     sync();
     {
-        const int base = 32 * (e >> 3) + (e & 7);
+        const int base = 32 * (e >> 3) + (e & 7), z = SWZ ? fft128_swz(32 * (e >> 3)) & 24 : 0;
         pcx y0, y1, y2, y3;
-        pk_r4_inv(s[base], s[base + 8], s[base + 16], s[base + 24], W.w32, y0, y1, y2, y3);
-        s[base] = y0; s[base + 8] = y1; s[base + 16] = y2; s[base + 24] = y3;
+        pk_r4_inv(s[base + z], s[base + (8 ^ z)], s[base + (16 ^ z)], s[base + (24 ^ z)], W.w32, y0, y1, y2, y3);
+        s[base + z] = y0; s[base + (8 ^ z)] = y1; s[base + (16 ^ z)] = y2; s[base + (24 ^ z)] = y3;
     }
     sync();
     {
         const bool hi = e & 1;                                                    // difference half
-        uint32_t* p = s + 8 * (e >> 1);
+        uint32_t* p = s + (SWZ ? fft128_swz(8 * (e >> 1)) : 8 * (e >> 1));
         const uint4 A = reinterpret_cast<const uint4*>(p)[0], B = reinterpret_cast<const uint4*>(p)[1];
         pcx v[4];
         const pcx a[4] = { pk_sra(A.x, 3), pk_sra(A.y, 3), pk_sra(A.z, 3), pk_sra(A.w, 3) }, b[4] = { pk_sra(B.x, 3), pk_sra(B.y, 3), pk_sra(B.z, 3), pk_sra(B.w, 3) };

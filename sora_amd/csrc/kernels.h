@@ -170,6 +170,39 @@ __host__ __device__ inline bool tx11n_plan(uint32_t len, uint32_t mcs, Tx11nPlan
 constexpr uint32_t kTx11nPreamble = 1120;                // samples per chain of the table: L-STF + L-LTF + HT-STF + 2 HT-LTF
 __global__ void k_tx11n(Tx11nArgs A);
 
+// ---- 40 MHz HT 2x2 transmitter (k_tx_ht40.hip)
+struct TxHt40Args {            // sora_hip_tx_ht40
+    const uint8_t*  mpdu;      // MPDUs without FCS: stream s of frame f at mpdu + off[2 f + s]
+    const uint32_t* off;       // [2 nframes]
+    const uint32_t* len;       // [nframes] bytes without FCS, the same for both streams (HT LENGTH = len + 4)
+    const uint32_t* mcs;       // 8..14
+    const uint8_t*  seed;      // [2 nframes] scrambler seeds (py_ht40.scramble_seq's, 7 bits used); nullptr: 0x5D, 0x2B
+    uint32_t*       out0;      // packed COMPLEX16, TX chain 0 (spatial stream 0)
+    uint32_t*       out1;      // TX chain 1
+    const uint64_t* out_off;   // first sample of frame f in both streams
+    const uint32_t* preamble;  // [2][1120]: per chain L-STF, L-LTF (640) then HT-STF, HT-LTF1, HT-LTF2 (480), k_tx_ht40_preamble
+    Tables          T;
+};
+// N_SYM = ceil((16 + 8 (len + 4) + 6) / N_DBPS) with N_DBPS = 108 N_BPSC R: sora_ht40_symbols(len + 4, len + 4, nb, cr), py_ht40.nsym_for
+struct TxHt40Plan { int nb, cr, ndbps; uint32_t nsym; };
+__host__ __device__ inline bool tx_ht40_plan(uint32_t len, uint32_t mcs, TxHt40Plan& P)
+{
+    if (len < 1 || len > 3996) return false;             // HT LENGTH <= 4000, the receiver's limit
+    switch (mcs) {                                       // cr: 0 = 1/2, 1 = 2/3, 2 = 3/4
+    case 8:  P.nb = 1; P.cr = 0; P.ndbps = 54;  break;  case 9:  P.nb = 2; P.cr = 0; P.ndbps = 108; break;
+    case 10: P.nb = 2; P.cr = 2; P.ndbps = 162; break;  case 11: P.nb = 4; P.cr = 0; P.ndbps = 216; break;
+    case 12: P.nb = 4; P.cr = 2; P.ndbps = 324; break;  case 13: P.nb = 6; P.cr = 1; P.ndbps = 432; break;
+    case 14: P.nb = 6; P.cr = 2; P.ndbps = 486; break;
+    default: return false;
+    }
+    P.nsym = (16u + 8u * (len + 4u) + 6u + (uint32_t)P.ndbps - 1u) / (uint32_t)P.ndbps;
+    return true;
+}
+constexpr uint32_t kTxHt40Preamble = 1120;               // samples per chain of the table: L-STF + L-LTF + HT-STF + 2 HT-LTF
+constexpr int kTxHt40Amp = 16384;                        // A: the bin value of an LTF / SIG carrier (tests/tx_ht40_model.py)
+__global__ void k_tx_ht40_preamble(uint32_t* tab, Tables T);
+__global__ void k_tx_ht40(TxHt40Args A);
+
 // ---- 802.11b transmitter (k_tx11b.hip)
 struct Tx11bArgs {             // sora_hip_tx11b
     const uint8_t*  mpdu;      // MPDUs without FCS, frame f at mpdu + off[f]

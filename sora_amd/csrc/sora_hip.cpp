@@ -323,6 +323,7 @@ struct DevTables {
     int device = -1;
     int8_t* tx_preamble = nullptr;      // 640 COMPLEX8 samples at 40 MHz, then 704 at 44 MHz (k_tx_preamble), built on first use of the transmitter
     uint32_t* tx11n_preamble = nullptr; // [2][1120] COMPLEX16 (tx11n_preamble_host), built on first use of the 802.11n transmitter
+    uint32_t* tx_ht40_preamble = nullptr; // [2][1120] COMPLEX16 (k_tx_ht40_preamble), built on first use of the 40 MHz HT transmitter
 };
 
 template <typename V>
@@ -1798,6 +1799,45 @@ int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t*
     A.out0 = reinterpret_cast<uint32_t*>(d_out0); A.out1 = reinterpret_cast<uint32_t*>(d_out1); A.out_off = d_out_off;
     A.preamble = D->tx11n_preamble; A.T = D->T;
     hipLaunchKernelGGL(k_tx11n, dim3((unsigned)nframes), dim3(256), 0, (hipStream_t)stream, A);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+// ---- 40 MHz HT 2x2 transmitter
+size_t sora_hip_tx_ht40_samples(uint32_t mpdu_len_nofcs, uint32_t mcs)
+{
+    TxHt40Plan P;
+    if (!tx_ht40_plan(mpdu_len_nofcs, mcs, P)) return 0;
+    return 1280 + 160 * (2 + (size_t)P.nsym);
+}
+
+int sora_hip_tx_ht40(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
+                     size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
+{
+    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
+    if (!d_mpdu || !d_off || !d_len || !d_mcs || !d_out0 || !d_out1 || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_tx_ht40: null pointer");
+    if (nframes == 0) return SORA_OK;
+    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    hipStream_t st = (hipStream_t)stream;
+    {
+        // the fixed fields through the same fixed-point IFFT as every other symbol: built once per device, under the lock, and complete
+        // before it is published
+        std::lock_guard<std::mutex> lock(g_stage_mutex);
+        if (!D->tx_ht40_preamble) {
+            uint32_t* p = nullptr;
+            HIPCHK(hipMalloc((void**)&p, 2 * kTxHt40Preamble * sizeof(uint32_t)));
+            hipLaunchKernelGGL(k_tx_ht40_preamble, dim3(1), dim3(128), 0, st, p, D->T);
+            hipError_t e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) { (void)hipFree(p); return fail(SORA_ERR_HARDWARE_FAILED, "k_tx_ht40_preamble", e); }
+            D->tx_ht40_preamble = p; D->allocs.push_back(p);
+        }
+    }
+    TxHt40Args A{};
+    A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.mcs = d_mcs; A.seed = d_seed;
+    A.out0 = reinterpret_cast<uint32_t*>(d_out0); A.out1 = reinterpret_cast<uint32_t*>(d_out1); A.out_off = d_out_off;
+    A.preamble = D->tx_ht40_preamble; A.T = D->T;
+    hipLaunchKernelGGL(k_tx_ht40, dim3((unsigned)nframes), dim3(256), 0, st, A);
     HIPCHK(hipGetLastError());
     return SORA_OK;
 }
