@@ -658,6 +658,42 @@ int   sora_ht40_results_of(sora_ht40_t* rx, int ticket, sora_frame_result* h_out
  * fails, an unsupported MCS: E_ERROR_PLCP_HEADER_FAIL, no PSDU); the rows of the last event a full capture could hold carry SORA_ROW_TRUNCATED.
  * max_rows: at least 2 x the call's frames (descriptor calls) / 2 x ncaps x max_frames_per_capture (raw-capture calls: the host knows only that bound). */
 int   sora_ht40_deliver_async(sora_ht40_t* rx, int ticket, sora_frame_result* h_rows, size_t max_rows, uint32_t* h_counts, uint8_t* h_mpdu, size_t mpdu_cap);
+/* Stream continuation of the raw-capture form, as sora_rx11n_set_stream_mode (the live-source case: a host with a two-chain 40 MHz source hands
+ * the stream over in pieces, and the front end's carrier-sense state -- the two chains' MimoAutoCorr rings and running sums, the delayed-energy
+ * ring, the TCCA11n counters -- carries over from one read to the next).  With sora_ht40_set_stream_mode(rx, 1) capture k of a
+ * sora_ht40_process_captures_dev call CONTINUES capture k of the previous such call; one descriptor addresses the same range of both chain
+ * buffers, as in every call:
+ *   - after a call, sora_ht40_stream_consumed(rx, ticket, h, n) gives, per capture, the RESUME POINT: the number of 40 MHz samples of that
+ *     capture that are final.  It is a position where a 4-sample burst boundary of the 20 MHz front end falls on a source-call boundary (14
+ *     samples at 20 MHz, 28 at 40 MHz) while the front end is in carrier sense; bursts restart at each post-event origin, which is a call
+ *     boundary, so it is a multiple of 28 (0 if the capture holds none).  Every row the call reports ends at or in front of it
+ *     (end_sample <= resume point).  (A multiple of 28 is an even number of 20 MHz samples: the front end's derotation x[2m] (-1)^m runs on
+ *     unbroken, so the 40 MHz handle needs no alignment rule beyond "continue from the resume point".);
+ *   - NO PADDING: with the mode off a capture's last burst is delivered zero-padded and missing SIG symbols read as zeros; stream mode never
+ *     reads zeros past the capture's end.  A frame is taken only when its L-LTF, its three SIG symbols and -- for a valid header -- its
+ *     HT-STF, both HT-LTFs and all data symbols lie inside the capture's samples; otherwise the capture ends at the latest resume point in
+ *     front of the frame's detection and the next call finds the frame again, so every frame is reported exactly once.  A header that fails
+ *     with its three SIG symbols inside the capture is an event as usual.  An event that finds no row slot (max_frames_per_capture) stops
+ *     the capture's resume point in front of it: no event is lost.  A zero-length capture leaves its stream as it was;
+ *   - the host builds the next call's capture k from the stream FROM THAT POINT on: the unconsumed tail of what it submitted plus whatever
+ *     has arrived since, in both chains (capture lengths are still whole 28-sample source bursts).  The library starts it with the state
+ *     the front end had at the resume point, so the rows of all the calls together (positions relative to their own capture: add the stream
+ *     position of its first sample) are exactly the rows the mode-off handle reports on the uncut stream -- tests/test_gpu_stream_ht40.py
+ *     holds streams cut at random source calls to that;
+ *   - calls of a handle in stream mode run one after the other (a sora_ht40_process_captures_dev call first waits for every call of the
+ *     handle in flight: it needs their records); throughput comes from many streams (captures) per call.  Both trellis choices work in
+ *     stream mode: the records belong to the handle, not to a slot.  sora_ht40_stream_consumed exists for the most recent ticket only.
+ *     Switching the mode, either way, first waits for every call in flight and starts every stream afresh.  sora_ht40_process_dev (the
+ *     descriptor form) does not touch the records;
+ *   - sora_ht40_create takes no capture count: the records are sized once, when the mode is first enabled, for max_frames streams, and a
+ *     raw-capture call in stream mode with ncaps > max_frames answers SORA_ERR_INVALID_PARAM before anything is launched;
+ *   - a stream-mode call that ends in SORA_ERR_CAPACITY (more frames / soft values than the handle was created for) has already advanced
+ *     its streams: its frames are lost, nothing is rolled back, and the host restarts the streams by switching the mode.
+ * sora_ht40_set_stream_mode returns the previous mode; a negative argument only queries.  sora_ht40_stream_consumed fails when the handle
+ * is not in stream mode (SORA_ERR_FAILED), for any ticket but the most recent call's and for more captures than that call had
+ * (SORA_ERR_INVALID_PARAM). */
+int   sora_ht40_set_stream_mode(sora_ht40_t* rx, int enable);
+int   sora_ht40_stream_consumed(sora_ht40_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU sharding for a C host.  Captures are independent -- the reference resets its context per

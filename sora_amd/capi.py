@@ -75,7 +75,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_rx11n_wait_any", "sora_rx11n_results_of", "sora_rx11n_set_mcs_max",
            "sora_ht40_symbols", "sora_ht40_create", "sora_ht40_destroy", "sora_ht40_stream", "sora_ht40_synchronize", "sora_ht40_set_trellis", "sora_ht40_process_dev",
                       "sora_ht40_process_captures_dev", "sora_ht40_results", "sora_ht40_ticket", "sora_ht40_calls_in_flight", "sora_ht40_wait", "sora_ht40_wait_any",
-                      "sora_ht40_stream_of", "sora_ht40_results_of",
+                      "sora_ht40_stream_of", "sora_ht40_results_of", "sora_ht40_set_stream_mode", "sora_ht40_stream_consumed",
            "sora_shard_unique_id", "sora_shard_create", "sora_shard_destroy", "sora_shard_world", "sora_shard_partition", "sora_shard_gather_rows",
            "sora_shard_reduce_counters", "sora_shard_gather_results", "sora_shard_gather_results_mpdu"]
 
@@ -250,7 +250,7 @@ def load(build_if_missing=True):
     _res_of = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t]
     _deliver = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     L.sora_ht40_process_captures_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
-    # what the four receive handles share (include/sora_hip.h: tickets, calls in flight, stream continuation where the handle has it)
+    # what the four receive handles share (include/sora_hip.h: tickets, calls in flight, stream continuation)
     vp = ctypes.c_void_p
     shared = [("_destroy", [vp], None), ("_stream", [vp], vp), ("_ticket", [vp], ctypes.c_int), ("_wait", [vp, ctypes.c_int], ctypes.c_int),
               ("_wait_any", [vp, ctypes.POINTER(ctypes.c_int)], ctypes.c_int), ("_stream_of", [vp, ctypes.c_int], vp), ("_results_of", _res_of, ctypes.c_int),
@@ -290,7 +290,7 @@ def _dev_ptr(x):
 
 class _Handle:
     """What the four receive handles share (include/sora_hip.h): their calls in flight -- tickets, wait, wait_any, deliver_async --, stream
-    continuation where the handle has it, and the step from a FrameResult table to dicts.  _pre: the prefix of the handle's C entry points."""
+    continuation, and the step from a FrameResult table to dicts.  _pre: the prefix of the handle's C entry points."""
     _pre = ""
     _h = None
 
@@ -709,7 +709,8 @@ class Rx11n(_Handle):
 
 
 class RxHt40(_Handle):
-    """sora_ht40_t: the data field of HT-mixed 40 MHz two-stream frames (BASELINE configs[3]; parity unpinned, see include/sora_hip.h)."""
+    """sora_ht40_t: the data field of HT-mixed 40 MHz two-stream frames (BASELINE configs[3]; parity unpinned, see include/sora_hip.h).  set_stream_mode /
+    stream_consumed (the shared ones above) apply to process_captures_dev: a stream-mode call takes at most max_frames captures."""
     _pre = "sora_ht40"
 
     def __init__(self, max_frames, max_soft_values, device=0):

@@ -1,7 +1,7 @@
 // host_calls.h -- host side of the contract every receive handle (sora_rx, sora_rx11b, sora_rx11n, sora_ht40) keeps for its calls in flight (include/sora_hip.h):
 // a call gets a ticket; a call whose delivery was enqueued (*_deliver_async) and that was waited for is RELEASED; the next call takes an unused slot, else the
 // released call with the oldest ticket, else the oldest call; *_wait_any returns the oldest finished delivered call.  Also the stream-continuation records of
-// the handles that have them (11a, 11b, 11n) and the checks the handles' entry points share.  Host code only.
+// the four handles and the checks the handles' entry points share.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -103,7 +103,7 @@ template <typename S> inline int calls_synchronize(S* s, int n, int device)
     return SORA_OK;
 }
 
-// Stream continuation (sora_rx_set_stream_mode and its 11b / 11n twins): capture k of a call continues capture k of the call before it.  The handle owns, per
+// Stream continuation (sora_rx_set_stream_mode and its 11b / 11n / HT40 twins): capture k of a call continues capture k of the call before it.  The handle owns, per
 // capture, a continuation record of `words` words and a resume point.  Each handle serialises its calls in stream mode its own way.
 struct StreamRecords {
     uint32_t words;                           // per capture: kContWords, kRec11bWords, kRec11nWords

@@ -324,6 +324,7 @@ struct Ht40Slot : Call {       // the stream, ticket and completion state of the
     CapDesc* d_caps = nullptr; size_t caps_bytes = 0; Rx11bRow* d_scanrows = nullptr; size_t scanrows_bytes = 0;
     uint32_t* d_nfr = nullptr; size_t nfr_bytes = 0; Ht40Found* d_found = nullptr; size_t found_bytes = 0;
     bool capture_mode = false; uint32_t capture_mf = 0; std::vector<Ht40Event> events;
+    uint32_t ncaps = 0;         // captures of a raw-capture call (sora_ht40_stream_consumed); 0 for a descriptor call
     // ... planned on the device (k_ht40_plan): the records come back asynchronously into page-locked memory and are turned into `events` when the call is collected
     uint32_t* d_plan = nullptr;
     // the call's event table (k_ht40_plan -> sora_ht40_deliver_async)
@@ -344,6 +345,8 @@ struct sora_ht40 {
     // trellis kernel (host_trellis.h): Lanes16 = k_viterbi16_11n (default: the handle keeps eight calls in flight), Lanes64 =
     // k_viterbi11n (64 lanes per stream pair; the faster one for a call alone) -- sora_ht40_set_trellis
     Trellis trellis = Trellis::Lanes16;
+    // sora_ht40_set_stream_mode: the records belong to the handle, not to a slot; sized for max_frames streams when the mode is first enabled
+    StreamRecords records{kRec11nWords};
 };
 
 static constexpr uint32_t kVoutStride = 4352;
@@ -361,6 +364,7 @@ static void ht40_free(sora_ht40_t* rx)
         (void)hipFree(S.d_plan); (void)hipFree(S.d_evbase); (void)hipFree(S.d_evn); (void)hipFree(S.d_evtmpl); if (S.h_pin) (void)hipHostFree(S.h_pin);
             if (S.h_stage) (void)hipHostFree(S.h_stage);
     }
+    rx->records.free();
     delete rx;
 }
 
@@ -420,6 +424,18 @@ int sora_ht40_synchronize(sora_ht40_t* rx)
 {
     if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_synchronize: null handle", 0);
     return calls_synchronize(rx->slot, kHt40Slots, rx->device);
+}
+
+int sora_ht40_set_stream_mode(sora_ht40_t* rx, int enable)
+{
+    if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_set_stream_mode: null handle", 0);
+    if (enable >= 0) { const int rc = sora_ht40_synchronize(rx); if (rc) return rc; }
+    return rx->records.set(enable, rx->device, rx->max_frames);
+}
+int sora_ht40_stream_consumed(sora_ht40_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps)
+{
+    if (!rx || !h_consumed) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_stream_consumed: null argument", 0);
+    return rx->records.consumed("sora_ht40_stream_consumed", rx->device, call_find(rx->slot, kHt40Slots, ticket), ticket == rx->seq, h_consumed, ncaps);
 }
 
 // the data field's kernels on slot S: k_ht40_frame over at most nframes frames, the trellis kernel, k_ht40_finish.  plan: the device's own count of them (k_ht40_plan), else
@@ -492,7 +508,7 @@ int sora_ht40_process_dev(sora_ht40_t* rx, const sora_complex16* d_iq0, const so
     rx->next = call_next(rx->slot, kHt40Slots);                                   // an unused slot, else a released call's, else the oldest call's
     Ht40Slot& S = rx->slot[rx->next];
     HIPCHK(hipStreamSynchronize(S.stream));                                     // the call that used this slot kHt40Slots calls ago
-    S.events.clear(); S.capture_mode = false; S.events_pending = false; S.plan_error = false;
+    S.events.clear(); S.capture_mode = false; S.events_pending = false; S.plan_error = false; S.ncaps = 0;
     return ht40_submit(rx, S, d_iq0, d_iq1, frames, nframes, d_weights);
 }
 
@@ -509,7 +525,12 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     if (!rx || (ncaps && (!d_iq0 || !d_iq1 || !caps)) || max_frames_per_capture == 0) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
             "sora_ht40_process_captures_dev: bad argument", 0);
     if ((uint64_t)ncaps * max_frames_per_capture >= (1ull << 31)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_process_captures_dev: too many rows", 0);
+    // stream mode: the records hold max_frames streams (the handle has no capture count of its own)
+    if (rx->records.on && ncaps > rx->max_frames) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
+            "sora_ht40_process_captures_dev: in stream mode a call takes at most max_frames captures (streams)", 0);
     HIPCHK(hipSetDevice(rx->device));
+    // stream mode: this call continues the records the one before it leaves, so calls run one after the other
+    if (rx->records.on) for (Ht40Slot& Q : rx->slot) HIPCHK(hipStreamSynchronize(Q.stream));
     rx->next = call_next(rx->slot, kHt40Slots);                                   // an unused slot, else a released call's, else the oldest call's
     Ht40Slot& S = rx->slot[rx->next];
     HIPCHK(hipStreamSynchronize(S.stream));                                     // the call that used this slot kHt40Slots calls ago
@@ -538,7 +559,7 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     for (size_t i = 0; i < ncaps; i++) { CapDesc& h = S.h_capsup[i]; h.offset = caps[i].offset; h.nsamples = caps[i].nsamples;
         h.capture_id = caps[i].capture_id; h.slot_base = 0; h.nslots = 0; }
     S.h_caps.assign(caps, caps + ncaps);
-    S.events.clear(); S.capture_mode = true; S.capture_mf = mf; S.events_pending = true; S.plan_error = false; S.nframes = 0;
+    S.events.clear(); S.capture_mode = true; S.capture_mf = mf; S.ncaps = (uint32_t)ncaps; S.events_pending = true; S.plan_error = false; S.nframes = 0;
     S.bound_frames = (uint32_t)std::min<uint64_t>(nrows, rx->max_frames); S.bound_events = (uint32_t)nrows;
     rx->have_results = true; rx->last = rx->next;
     S.ticket = ++rx->seq; S.delivered = S.released = false;
@@ -548,7 +569,8 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     HIPCHK(hipMemsetAsync(S.d_nfr, 0, 4 * ncaps, S.stream));
     { const int rc = sora_internal_scan_ht40(reinterpret_cast<const uint32_t*>(d_iq0), reinterpret_cast<const uint32_t*>(d_iq1), S.d_caps, (uint32_t)ncaps, mf,
             S.d_scanrows, S.d_nfr, S.d_found,
-                                             rx->T, rx->sincos, rx->atan, S.stream); if (rc) return rc; }
+                                             rx->T, rx->sincos, rx->atan, S.stream, rx->records.on ? rx->records.d_cont : nullptr,
+                                             rx->records.on ? rx->records.d_consumed : nullptr); if (rc) return rc; }
     const size_t stride = 2 * (size_t)rx->max_frames;
     hipLaunchKernelGGL(k_ht40_plan, dim3(1), dim3(1024), 0, S.stream, (const CapDesc*)S.d_caps, (uint32_t)ncaps, mf, (const uint32_t*)S.d_nfr, (const Ht40Found*)S.d_found,
                        rx->max_frames, (uint64_t)rx->max_soft, kVoutStride, S.d_frames, S.d_jobs, (uint32_t)stride, S.d_njobs, S.d_fjobs, S.d_evtmpl, S.d_plan, S.d_evbase, S.d_evn);

@@ -131,7 +131,6 @@ struct RingLds {                   // the same layout as the head of ScanLds
 };
 constexpr uint32_t kRec11nMagic = 0x534F314Eu;     // a continuation record holds a resume point (a fresh stream is all zeros)
 }  // namespace
-constexpr uint32_t kRec11nWords = 64 + 4 * 64 + 128;   // header, the four MimoAutoCorr rings of both chains, the 64 delayed energies
 
 // HT40 = false: the reference's 20 MHz graph (k_scan11n).  HT40 = true: the same front end on the legacy part of an HT-mixed 40 MHz frame
 // (k_scan_ht40): the legacy preamble and HT-SIG are the 20 MHz waveforms sent on both halves of the channel, the upper one rotated by
@@ -142,7 +141,7 @@ constexpr uint32_t kRec11nWords = 64 + 4 * 64 + 128;   // header, the four MimoA
 // data-field kernels (k_ht40.hip) with what they need from here: position, CFO (per 40 MHz sample) and the noise variance, estimated
 // from the difference of the two L-LTF symbols.  That part is this library's own definition: parity unpinned.
 //
-// STREAM = true (k_scan11n_stream, sora_rx11n_set_stream_mode): the capture continues the stream its continuation record
+// STREAM = true (k_scan11n_stream / k_scan_ht40_stream, sora_rx11n_set_stream_mode / sora_ht40_set_stream_mode): the capture continues the stream its continuation record
 // left off.  A RESUME POINT is a burst boundary of carrier sense that falls on a source-call boundary: 28 samples (20 MHz) apart from each
 // origin, and every post-event origin.  The record: [0] kRec11nMagic, [1] ring_pos, [2] his_index, [3..8] the running sums, [9..12] the
 // TCCA11n counters pf, pc, sense, timeout, then the rings in their LDS layout.  Three things differ from the default kernel:
@@ -169,6 +168,10 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
     const CapDesc cd = A.caps[cap];
     const uint32_t* iq[2] = { A.iq0 + cd.offset, A.iq1 + cd.offset };
     const uint32_t n20 = cd.nsamples / 2;
+    // HT40: the derotation sign goes by i & 1, the 20 MHz index counted from the capture's first sample.  A continued capture (STREAM) starts at a resume
+    // point: a multiple of 28 samples at 40 MHz, that is 14 k at 20 MHz from the previous capture's start -- an even number.  So the sign pattern runs on
+    // unbroken from call to call, the rings in the continuation record hold derotated samples of the same phase, and the host's "continue from the resume
+    // point" rule needs no alignment rule of its own for the 40 MHz front end.
     auto fetch = [&](int r, uint32_t i) __attribute__((always_inline)) -> uint32_t {
         if (i >= n20) return 0u;
         const uint32_t v = iq[r][2 * (size_t)i];
@@ -529,19 +532,23 @@ __global__ void __launch_bounds__(256) k_scan11n_stream(Scan11nArgs A, uint32_t*
 // The front end of the 40 MHz HT receiver (sora_ht40_process_captures_dev, k_ht40.hip): carrier sense, L-LTF, L-SIG / HT-SIG on the
 // duplicated legacy preamble -> one Ht40Found record per event.
 __global__ void __launch_bounds__(256) k_scan_ht40(Scan11nArgs A, Ht40Found* found) { scan11n_body<true>(A, found); }
+// its stream form (sora_ht40_set_stream_mode): the records and resume points of k_scan11n_stream (kRec11nWords, 40 MHz samples); a20 and end_sample of the
+// Ht40Found records stay relative to the capture, so what follows the scan (k_ht40_plan, the data field's kernels) is the same in both modes
+__global__ void __launch_bounds__(256) k_scan_ht40_stream(Scan11nArgs A, Ht40Found* found, uint32_t* cont, uint32_t* consumed) { scan11n_body<true, true>(A, found, cont, consumed); }
 
 }  // namespace sora
 int sora_internal_scan_ht40(const uint32_t* iq0, const uint32_t* iq1, const sora::CapDesc* d_caps, uint32_t ncaps, uint32_t max_frames, sora::Rx11bRow* d_rows, uint32_t* d_nframes,
-                            sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st)
+                            sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st, uint32_t* d_cont, uint32_t* d_consumed)
 {
     using namespace sora;
     Scan11nArgs S{};
     S.iq0 = iq0; S.iq1 = iq1; S.caps = d_caps; S.ncaps = ncaps; S.max_frames = max_frames; S.rows = d_rows; S.nframes = d_nframes; S.T = T; S.sincos = sincos; S.atan = atan;
     S.frames = nullptr; S.jobs = nullptr; S.njobs = nullptr; S.nrows = ncaps * max_frames;
     S.mcs_max = 14; S.soft_per_slot = 0; S.out_per_slot = 0;                     // (the HT40 form has its own gate and queues no 20 MHz data field)
-    hipLaunchKernelGGL(k_scan_ht40, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found);
+    if (d_cont) hipLaunchKernelGGL(k_scan_ht40_stream, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found, d_cont, d_consumed);
+    else hipLaunchKernelGGL(k_scan_ht40, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SORA_OK : sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "k_scan_ht40", (int)e);
+    return e == hipSuccess ? SORA_OK : sora_internal_fail(SORA_ERR_HARDWARE_FAILED, d_cont ? "k_scan_ht40_stream" : "k_scan_ht40", (int)e);
 }
 namespace sora {
 

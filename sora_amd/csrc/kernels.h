@@ -263,6 +263,8 @@ __global__ void k_rx11b_cck(Rx11bArgs A);
 __global__ void k_rx11b_stream(Rx11bArgs A);        // the same two passes, in stream form
 __global__ void k_rx11b_cck_stream(Rx11bArgs A);
 
+// a continuation record of the 802.11n / HT40 front ends' stream forms (k_rx11n.hip): header, the four MimoAutoCorr rings of both chains, the 64 delayed energies
+constexpr uint32_t kRec11nWords = 64 + 4 * 64 + 128;
 // one event of the 40 MHz HT front end (k_scan_ht40 in k_rx11n.hip), row cap * max_frames + i
 struct Ht40Found {
     uint32_t a20;                  // 20 MHz index (in the capture) of the first HT-STF sample: HT-LTF 1 starts 2 * a20 + 160 samples @40 MHz into the capture
@@ -275,8 +277,10 @@ struct Ht40Found {
 
 }  // namespace sora
 
+// d_cont / d_consumed: the streams' continuation records [ncaps][kRec11nWords] and resume points [ncaps] (k_scan_ht40_stream); null = k_scan_ht40
 int sora_internal_scan_ht40(const uint32_t* iq0, const uint32_t* iq1, const sora::CapDesc* d_caps, uint32_t ncaps, uint32_t max_frames, sora::Rx11bRow* d_rows, uint32_t* d_nframes,
-                            sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st);
+                            sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st,
+                            uint32_t* d_cont = nullptr, uint32_t* d_consumed = nullptr);
 
 // k_deliver.hip: dense rows + MPDUs of a call of the Rx11bRow-table handles into page-locked host memory, behind the call's kernels
 struct DenseStage {                  // per slot / pipeline (grow-only device staging)
