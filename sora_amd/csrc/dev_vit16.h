@@ -26,7 +26,7 @@ template <int WIN, int LOOK> struct Lds16 {
         //   Forward16::unpack() / forward16's two alternating tables of its fast loop, never across a trace-back:
         uint16_t ops2[2][4][24][2];
     };                                                                          //   they share their bytes with the trace-back's register dump
-    uint8_t  path[8][Geom16<WIN, LOOK>::kPathBytes];                             // [row * 2 + frame][walk position]: the bytes along the traced path
+    uint32_t path[8][Geom16<WIN, LOOK>::kPathBytes / 4];                         // [row * 2 + frame]: the bytes along the traced path in stream order (trace16's byte path only)
 };                                                                              // 20288 / 17216 bytes: eight one-wave workgroups per CU (20480 each)
 
 constexpr unsigned kW[4] = { 0u, 21u, 42u, 63u };
@@ -129,7 +129,7 @@ struct Forward16 {
     const uint8_t* soft;
     uint16_t* my_ops;
     const uint4* row_ops;
-    uint32_t pos;                                                               // ring position (block index % P) of the current row's first block
+    uint32_t pos;                                                               // ring position of the current row's first block, in BYTES: 512 (block index % P)
     unsigned pos512[3];
     uint32_t tr, nsteps;                                                        // steps taken / of the wave's longest side (wave-uniform)
     uint32_t next_thr;
@@ -179,13 +179,14 @@ struct Forward16 {
 #pragma unroll
         for (int i = 0; i < 4; i++) V.U[i] -= m;
     }
-    static __device__ __forceinline__ uint32_t pos_of(uint32_t p, int jb) { const uint32_t q = p + (uint32_t)jb; return q >= (uint32_t)P ? q - (uint32_t)P : q; }
+    // The position jb blocks on.  It is kept in bytes and wrapped by one unsigned minimum (p < 512 P: p - 512 P is huge unless p has passed the ring's end), so a
+    // banked block costs the scalar unit an add, a subtract and a minimum -- as a block index it was add, shift, add, compare, select.
+    static __device__ __forceinline__ uint32_t pos_of(uint32_t p, int jb) { const uint32_t q = p + 512u * (uint32_t)jb; return min(q, q - 512u * (uint32_t)P); }
     __device__ __forceinline__ void set_row_pos()
     {
-#pragma unroll
-        for (int jb = 0; jb < 3; jb++) pos512[jb] = pos_of(pos, jb) * 512u;
+        pos512[0] = pos; pos512[1] = pos_of(pos, 1); pos512[2] = pos_of(pos512[1], 1);
     }
-    __device__ __forceinline__ void end_row() { pos = pos_of(pos, 3); set_row_pos(); }
+    __device__ __forceinline__ void end_row() { pos = pos_of(pos512[2], 1); set_row_pos(); }
     __device__ __forceinline__ Raw fetch(uint32_t c) const                      // chunk c: the loads only
     {
         Raw R;
@@ -254,15 +255,28 @@ struct Forward16 {
 
 // Trace-back of one window for every frame of the wave whose count is non-zero (my_cnt: this lane's frame = (row, lane & 1)); kept out of
 // line (it is reached from every puncture group of the slow path), so everything arrives by value and the LDS block by its offset.
-// pj = ring position of block j = (tr - 1) >> 3; k = index in its 8-step block of the last step taken.
+// pj = ring position, in bytes (Forward16::pos), of block j = (tr - 1) >> 3; k = index in its 8-step block of the last step taken.
 // LANE_OB (k_vitwin.hip): ob_ is a per-lane value -- the units a wave decodes hand out their bits at different positions of their frames.
+//
+// The bytes along the traced path stay in registers.  The walk is unrolled in full, so walk position i is a compile-time place: the bytes are packed four to a
+// register in the order the decoded stream wants them (stream byte s = walk position kMaxWalk - 1 - s; two raw ring words -> one register -> v_perm_b32 picks
+// this frame's byte of each pair), and decoded byte z of the window is bits 8 (s0 + z) + 6 .. + 13 of that stream, s0 = kMaxWalk - 1 - (j - ob / 8).
+//   * a whole window (count WIN) of the whole-frame form always has s0 = 1: a decoded dword is one v_alignbit_b32 by 14 of two neighbouring registers, and the
+//     lane that owns the frame (lane & 15 < 2) stores the window's WIN / 8 bytes as dwords;
+//   * any other case in the wave -- a frame's last, partial window, an output that is not dword-aligned, and every trace-back of the LANE_OB form, whose units put
+//     s0 anywhere and their bytes at any alignment -- takes the byte path: the registers go to Lds16::path as dwords, and the row's lanes assemble and store the
+//     bytes one by one as before.
 template <int WIN, int LOOK, bool LANE_OB = false>
 __device__ __noinline__ void trace16(unsigned lds_off, unsigned U0, unsigned U1, unsigned U2, unsigned U3, uint32_t tr_, uint32_t ob_, uint32_t pj_, uint32_t k_,
                                      uint32_t my_cnt, uint8_t* my_out)
 {
     using G = Geom16<WIN, LOOK>;
-    constexpr int P = G::P;
+    constexpr int P = G::P, K = G::kMaxWalk;
+    constexpr int NR = K - 1, NF = NR / 4, NW = K / 4 + 1;                      // ring words read by the walk; registers they fill; registers of the stream (position 0 included)
+    static_assert(NR % 4 == 0 || NR % 4 == 2, "the walk's words are packed in pairs");
+    static_assert(NW * 4 <= G::kPathBytes && NW >= WIN / 32 + 1, "the stream's registers hold a window and fit Lds16::path");
     typedef __attribute__((address_space(3))) Lds16<WIN, LOOK> lds_t;
+    typedef __attribute__((address_space(3))) const uint16_t lds_u16;
     lds_t& S = *(lds_t*)(uintptr_t)lds_off;
     auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     const uint32_t tr = uni(tr_), ob = LANE_OB ? ob_ : uni(ob_), pj = uni(pj_), k = uni(k_);
@@ -270,6 +284,8 @@ __device__ __noinline__ void trace16(unsigned lds_off, unsigned U0, unsigned U1,
     const unsigned v0 = v_of_lane(l16);
     const unsigned U[4] = { U0, U1, U2, U3 };
     const uint32_t j = (tr - 1) >> 3, nn = tr - 8u * j, m_lo = ob >> 3;
+    const unsigned rowbase = (unsigned)(uintptr_t)&S.ring[0][row][0], sh = 8u * half;
+    auto ring_j = [&](unsigned idx) -> unsigned { return *(lds_u16*)(uintptr_t)(rowbase + pj + (idx << 1)); };   // block j's entry of this row
     // the metrics registers -> LDS (the start state's unfinished block is read from there); the ring writes of this block are visible after the fence
 #pragma unroll
     for (int i = 0; i < 4; i++) S.udump[i][lane] = U[i];
@@ -280,7 +296,7 @@ __device__ __noinline__ void trace16(unsigned lds_off, unsigned U0, unsigned U1,
     for (int i = 0; i < 4; i++) {
         const unsigned st = rol6(v0 ^ kW[i], tr);
         unsigned lastA, lastB;
-        if (k == 7) { const unsigned w = S.ring[pj][row][rev6u(st)]; lastA = (w >> 7) & 1u; lastB = (w >> 15) & 1u; }
+        if (k == 7) { const unsigned w = ring_j(rev6u(st)); lastA = (w >> 7) & 1u; lastB = (w >> 15) & 1u; }
         else { lastA = (U[i] >> k) & 1u; lastB = (U[i] >> (17 + k)) & 1u; }
         const unsigned mA = ((U[i] & 0xFFFFu) >> 9 << 1) | lastA, mB = (U[i] >> 25 << 1) | lastB;
         key[0] = min(key[0], (mA << 8) | (st << 2)); key[1] = min(key[1], (mB << 8) | (st << 2));
@@ -294,34 +310,59 @@ __device__ __noinline__ void trace16(unsigned lds_off, unsigned U0, unsigned U1,
     const unsigned sl = lane_of_v((s0 ^ (b4 ? 21u : 0u) ^ (b5 ? 42u : 0u)) & 15u);
     const unsigned Ust = S.udump[ri][row * 16u + sl];
     unsigned H;
-    if (nn == 8) H = ((unsigned)S.ring[pj][row][rev6u(st)] >> (8u * half)) & 0xFFu;
+    if (nn == 8) H = (ring_j(rev6u(st)) >> sh) & 0xFFu;
     else H = ((Ust >> (17u * half)) & 0xFFu) & ((1u << nn) - 1u);
     unsigned q = rev6u(((st >> nn) | rev6u(H & 0x3Fu)) & 0x3Fu);                 // ring index at column 8j
-    __attribute__((address_space(3))) uint8_t* pth = S.path[row * 2u + half];
-    pth[0] = (uint8_t)H;
-    // The walk, unrolled in full: the ring position of step i is pj - i (mod P), a scalar -- its row's byte offset is one v_lshl_add off the dependence chain --
-    // so that a block costs four vector instructions (shift, field, two address adds) and the chain ds_read -> bfe -> lshl_add -> ds_read (round 4: it was seven,
-    // with the position counted down in a vector register).
-    typedef __attribute__((address_space(3))) const uint16_t lds_u16;
-    const unsigned rowbase = (unsigned)(uintptr_t)&S.ring[0][row][0], sh = 8u * half;
+    // The walk, unrolled in full: the ring position steps down by 512 (mod 512 P), a scalar -- its row's byte offset is one v_lshl_add off the dependence
+    // chain -- so that a block costs the chain ds_read -> bfe -> lshl_add -> ds_read and half an instruction to pair its word with its neighbour's.
+    unsigned pr[NR / 2];                                                        // pair n: the raw words of stream bytes 2n (low half) and 2n + 1
+    uint32_t p = pj;
 #pragma unroll
-    for (int i = 1; i < G::kMaxWalk; i++) {                                     // always the full length: blocks below the window are read and never used
-        const int d = (int)pj - i;
-        const uint32_t p = (uint32_t)(d < 0 ? d + P : d);
-        unsigned base = rowbase + p * 512u;
+    for (int i = 1; i < K; i++) {                                               // always the full length: blocks below the window are read and never used
+        uint32_t d;
+        p = __builtin_sub_overflow(p, 512u, &d) ? 512u * (uint32_t)(P - 1) : d;     // (s_sub_u32, s_cselect_b32 on its borrow)
+        unsigned base = rowbase + p;
         // (one register: the chain's add is then v_lshl_add, not a three-input add behind a shift)
         asm volatile("" : "+v"(base));
         const unsigned raw = *(lds_u16*)(uintptr_t)(base + (q << 1));
-        pth[i] = (uint8_t)(raw >> sh);                                          // (this frame's byte of the pair)
         q = __builtin_amdgcn_ubfe(raw, sh, 6u);
+        const int s = K - 1 - i;
+        if (s & 1) pr[s >> 1] = raw << 16; else pr[s >> 1] |= raw;
     }
-    lds_fence();
-    // decoded byte m = (block m >> 6) | (block m + 1 & 0x3F) << 2; block m sits at walk position j - m.  Lane (l16 >> 1) of the row's
-    // eight lanes with this `half` takes bytes m_lo + (l16 >> 1) + 8 z.
-    const uint32_t nbytes = my_cnt >> 3;
-    for (uint32_t z = l16 >> 1; z < nbytes; z += 8) {
-        const uint32_t m = m_lo + z, i1 = j - m;                                // >= 1: the window ends at least one block below the start column
-        my_out[m] = (uint8_t)(((unsigned)pth[i1] >> 6) | (((unsigned)pth[i1 - 1] & 0x3Fu) << 2));
+    // this frame's byte of each word of two pairs -> four stream bytes; walk position 0 (H) ends the stream
+    unsigned R[NW];
+    const unsigned sel = 0x06040200u + 0x01010101u * half;
+#pragma unroll
+    for (int w = 0; w < NF; w++) R[w] = __builtin_amdgcn_perm(pr[2 * w + 1], pr[2 * w], sel);
+    if (NR % 4 == 0) R[NF] = H;
+    else R[NF] = __builtin_amdgcn_perm(H, pr[2 * NF], 0x0C040200u + 0x00000101u * half);
+    // decoded byte m = (block m >> 6) | (block m + 1 & 0x3F) << 2; block m sits at walk position j - m
+    const uint32_t sfirst = (uint32_t)(K - 1) - (j - m_lo);                     // stream byte of the window's first block
+    bool fast = !LANE_OB;
+    if (!LANE_OB) {
+        const bool whole = my_cnt == (uint32_t)WIN && sfirst == 1u && (((uintptr_t)my_out + m_lo) & 3u) == 0;
+        fast = __ballot(!(whole || my_cnt == 0)) == 0;
+    }
+    if (fast) {
+        if (my_cnt != 0 && l16 < 2) {                                           // lane (row, half): its own frame's window, WIN / 8 bytes
+            uint32_t* o = reinterpret_cast<uint32_t*>(my_out + m_lo);
+#pragma unroll
+            for (int dw = 0; dw < WIN / 32; dw++) o[dw] = __builtin_amdgcn_alignbit(R[dw + 1], R[dw], 14);
+        }
+    } else {
+        __attribute__((address_space(3))) uint32_t* pw = S.path[row * 2u + half];
+        if (l16 < 2) {
+#pragma unroll
+            for (int w = 0; w < NW; w++) pw[w] = R[w];
+        }
+        lds_fence();
+        // Lane (l16 >> 1) of the row's eight lanes with this `half` takes bytes m_lo + (l16 >> 1) + 8 z.
+        __attribute__((address_space(3))) const uint8_t* pth = (__attribute__((address_space(3))) const uint8_t*)pw;
+        const uint32_t nbytes = my_cnt >> 3;
+        for (uint32_t z = l16 >> 1; z < nbytes; z += 8) {
+            const uint32_t sb = sfirst + z;                                     // <= kMaxWalk - 2: the window ends at least one block below the start column
+            my_out[m_lo + z] = (uint8_t)(((unsigned)pth[sb] >> 6) | (((unsigned)pth[sb + 1] & 0x3Fu) << 2));
+        }
     }
     lds_fence();
 }

@@ -79,10 +79,15 @@ __device__ __forceinline__ void frame_symbols(const RxArgs& A, uint32_t j, Frame
     int cfo_comp = r.cfo_comp, sfo_comp = r.sfo_comp, cfo_tr = r.cfo_tracker, sfo_tr = r.sfo_tracker;
     unsigned symbol_count = 0;                                                   // 127 -> 0 after the SIGNAL symbol
 
-    auto load_samples = [&](int s0, uint32_t raw[4]) {                           // the 64 samples after the cyclic prefix, symbol s0 + g
-        const uint32_t p0 = r.data_start + 80u * (uint32_t)(s0 + g) + 8u;        // skip_cp = 8 (PHY_11a.hpp:365,394)
+    // The 64 samples after the cyclic prefix, symbol s0 + g; s0 <= nsym (the pass has a symbol).  A group whose symbol the frame does not have loads the frame's
+    // last one again: what it makes of it is never used (the tracker does not advance on it, the back end and the packer skip it), and four unguarded loads
+    // are four exec-mask branches less per pass.  Sample p (at 20 MHz) is word p * str of the capture, str = 1 or 2 (kernels.h): a shift, exact in 32 bits (a
+    // handle's samples number below 2^32, sora_rx_create) -- as the product of a widened index it was a v_mad_u64_u32 in front of every load's v_lshl_add_u64.
+    const uint32_t str_shift = A.str >> 1;
+    auto load_samples = [&](int s0, uint32_t raw[4]) {
+        const uint32_t p0 = r.data_start + __umul24(80u, (uint32_t)min(s0 + g, nsym)) + 8u + (uint32_t)e;   // skip_cp = 8 (PHY_11a.hpp:365,394)
 #pragma unroll
-        for (int m = 0; m < 4; m++) raw[m] = (s0 + g <= nsym) ? iq[(size_t)(p0 + (uint32_t)(e + 16 * m)) * A.str] : 0u;
+        for (int m = 0; m < 4; m++) raw[m] = iq[(p0 + 16u * (uint32_t)m) << str_shift];
     };
     // ---- SHARED: the frames' lengths and tracker states to wave 0, lanes 4 f + k (pilot k of the frame of wave f)
     int nsym_loop = nsym, nsym_f = nsym;
@@ -94,8 +99,8 @@ __device__ __forceinline__ void frame_symbols(const RxArgs& A, uint32_t j, Frame
         nsym_f = lds.nsym_of[fr];
         cfo_comp = lds.st0[fr][0]; sfo_comp = lds.st0[fr][1]; cfo_tr = lds.st0[fr][2]; sfo_tr = lds.st0[fr][3];   // (only wave 0 uses them from here on)
     }
-    uint32_t raw[4];
-    load_samples(1, raw);
+    uint32_t raw[4] = { 0u, 0u, 0u, 0u };
+    if (1 <= nsym) load_samples(1, raw);
     for (int s0 = 1; s0 <= nsym_loop; s0 += 4) {
         const int sym = s0 + g;
         const bool active = sym <= nsym;

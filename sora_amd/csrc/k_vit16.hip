@@ -32,8 +32,9 @@
 //
 // Trace-back.  The survivor ring is indexed by rev6(state) as in k_viterbi (the next index is the low six bits of the byte
 // read), one 128-byte table per row and block.  The walk is lane-parallel instead of readlane-serial: every lane walks the
-// path of frame (row, lane & 1) with one LDS read per block, the eight paths of the wave side by side, and the rows' lanes
-// then assemble and store the decoded bytes.  Per window ~450 instructions for eight frames (k_viterbi: ~400 for two).
+// path of frame (row, lane & 1) with one LDS read per block, the eight paths of the wave side by side, and keeps the path's
+// bytes in registers: a whole window leaves as dwords from the lane that owns the frame, anything else through the rows'
+// lanes byte by byte (trace16, dev_vit16.h).  Per window ~450 instructions for eight frames (k_viterbi: ~400 for two).
 //
 // Cost.  Eight frames per wave means 512 waves for the 4096-frame batch of BASELINE configs[2]: alone on the chip this kernel
 // is slower than k_viterbi (half the SIMDs idle), with several calls in flight it is faster; sora_rx_set_trellis selects.
