@@ -274,7 +274,7 @@ int  sora_rx_pipe_stats(sora_rx_t* rx, unsigned long long out[2]);
  * kernel launches: 1 = on, 0 = off (default).  Returns the previous setting; a negative argument only queries. */
 int  sora_rx_set_graph(sora_rx_t* rx, int enable);
 
-/* The data field (T11aDataSymbol .. T11aViterbi) is decoded by k_frame (symbol chain, soft values to HBM packed three bits each)
+/* The data field (T11aDataSymbol .. T11aViterbi) is decoded by k_frame (symbol chain, soft values to HBM one pre-scaled byte each)
  * followed by k_viterbi16 / k_viterbi (sora_rx_set_trellis).  Rounds 2-3 also shipped k_decode -- both in one kernel, symbol waves
  * feeding trellis waves through a ring in LDS the way the reference's RxThread feeds its ViterbiThread through TThreadSeparator
  * (stdbrick.hpp:89-248) -- which lost to the split form at every depth (0.80 against 0.46 ms per step, BENCH_r03), left the library

@@ -1,5 +1,5 @@
 // dev_sym11a.h -- the pieces of the 802.11a data field's symbol chain (fb11ademod_config.hpp:200-222):
-//   TFreqCompensation -> TFFT64 -> TChannelEqualization -> TPhaseCompensate -> TPilotTrack -> T11aDemap -> T11aDeinterleave -> packed soft stream
+//   TFreqCompensation -> TFFT64 -> TChannelEqualization -> TPhaseCompensate -> TPilotTrack -> T11aDemap -> T11aDeinterleave -> soft stream
 // Every form of the chain -- k_frame, k_sym_front / k_track_lds / k_sym_back, k_pipe, the fallback behind k_pipe (k_rx.hip) and the per-stage kernels
 // (k_stage.hip) -- takes the reference's arithmetic from here and keeps only its own schedule, layout and hand-offs.
 #pragma once
@@ -9,12 +9,12 @@
 
 namespace sora {
 
-// ---- the frame's VitJob: its packed soft stream and its decoded bytes sit at the frame's first symbol slot (rx_types.h)
+// ---- the frame's VitJob: its soft stream (one pre-scaled byte per value) and its decoded bytes sit at the frame's first symbol slot (rx_types.h)
 __device__ __forceinline__ VitJob frame_vitjob(const FrameRow& r)
 {
     VitJob J;
     J.valid = 1; J.soft_off = r.slot0 * (uint32_t)kSoftBytesPerSlot; J.nsoft = (uint32_t)r.nsym * 48u * r.nbpsc; J.length = r.length;
-    J.dec_off = 0; J.out_off = r.slot0 * (uint32_t)kOutPerSlot; J.code_rate = r.code_rate; J.soft_bits = 3;
+    J.dec_off = 0; J.out_off = r.slot0 * (uint32_t)kOutPerSlot; J.code_rate = r.code_rate; J.soft_bits = (uint32_t)kSoftScaled;
     return J;
 }
 
@@ -134,8 +134,15 @@ __device__ __forceinline__ void sym_back_demap(const Tables& T, const uint8_t* s
     }
 }
 
-// ---- T11aDeinterleave*: out[k] = in[j(k)] within a symbol, eight values -> three bytes of the packed stream per lane (lane < N_CBPS / 8).
-// The lane's source indices of output positions 8 lane .. 8 lane + 7 for modulation nb, two per register (0 for a lane that packs nothing)
+// ---- the demap step tables as a producer of the soft stream stages them in LDS: every entry (a soft value 0..7) doubled, so that what T11aDemap looks up and
+// T11aDeinterleave gathers IS the stream's byte v << 1 (rx_types.h).  The table in HBM stays the reference's own (tests/test_table_pins.py).  256 threads.
+__device__ __forceinline__ void demap_table_to_lds(const Tables& T, uint8_t* s_demap)
+{
+    reinterpret_cast<uint32_t*>(s_demap)[threadIdx.x] = (reinterpret_cast<const uint32_t*>(T.demap)[threadIdx.x] << 1) & 0xFEFEFEFEu;
+}
+
+// ---- T11aDeinterleave*: out[k] = in[j(k)] within a symbol, eight values -> eight bytes of the stream per lane (lane < N_CBPS / 8).
+// The lane's source indices of output positions 8 lane .. 8 lane + 7 for modulation nb, two per register (0 for a lane that stores nothing)
 __device__ __forceinline__ bool deint_packs(int nb, int lane) { return 8 * lane < 48 * nb; }
 __device__ __forceinline__ void deint_map_words(const Tables& T, int nb, int lane, uint32_t mp[4])
 {
@@ -144,13 +151,15 @@ __device__ __forceinline__ void deint_map_words(const Tables& T, int nb, int lan
 #pragma unroll
     for (int t = 0; t < 4; t++) mp[t] = packs ? (uint32_t)map[8 * lane + 2 * t] | ((uint32_t)map[8 * lane + 2 * t + 1] << 16) : 0u;
 }
-// ... and the lane's 24 bits of one symbol, gathered out of its soft values in carrier order (LDS)
-__device__ __forceinline__ uint32_t deint_gather24(const uint8_t* src, const uint32_t mp[4])
+// ... and the lane's eight bytes of one symbol, gathered out of its (doubled) soft values in carrier order (LDS): values 8 lane .. 8 lane + 3, then + 4 .. + 7
+__device__ __forceinline__ uint2 deint_gather8(const uint8_t* src, const uint32_t mp[4])
 {
     uint32_t v[8];
 #pragma unroll
     for (int t = 0; t < 4; t++) { v[2 * t] = src[mp[t] & 0xFFFFu]; v[2 * t + 1] = src[mp[t] >> 16]; }
-    return soft3_pack8(v);
+    return uint2{ v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24), v[4] | (v[5] << 8) | (v[6] << 16) | (v[7] << 24) };
 }
+// ... as one 8-byte store: bytes 8 lane .. 8 lane + 7 of the symbol at `sym` (8-byte aligned: a slot is 288 bytes, a symbol 48 N_BPSC)
+__device__ __forceinline__ void soft8_store(uint8_t* sym, uint32_t lane, uint2 b) { reinterpret_cast<uint2*>(sym)[lane] = b; }
 
 }  // namespace sora

@@ -126,6 +126,7 @@ struct Forward16 {
     unsigned row, half;                                                         // this lane's frame: (row, half)
     uint32_t my_j;
     SoftCursor<BITS, CW> cur[NV];
+    uint32_t my_base;                                                           // byte offset (from the soft base) of operand j of chunk 0, unclamped (fetch_at)
     const uint8_t* soft;
     uint16_t* my_ops;
     const uint4* row_ops;
@@ -166,10 +167,12 @@ struct Forward16 {
         my_j = l16 >> 1;
 #pragma unroll
         for (int v = 0; v < NV; v++) cur[v].init(my_soft_off, my_first + my_j + 8u * v, my_last);
+        my_base = my_soft_off + my_first + my_j;
         soft = soft_;
         my_ops = &S.ops[row][my_j][half];
         row_ops = reinterpret_cast<const uint4*>(&S.ops[row][0][0]);
         set_row_pos();
+        clear_ops(S);
     }
     __device__ __forceinline__ bool going() const { return tr < nsteps && !all_done; }
 
@@ -198,7 +201,29 @@ struct Forward16 {
     __device__ __forceinline__ void put(const Raw& R, uint16_t* mine) const
     {
 #pragma unroll
-        for (int v = 0; v < NV; v++) mine[16 * v] = (uint16_t)cur[v].field(R.r[v]);
+        for (int v = 0; v < NV; v++) soft_put(mine + 16 * v, cur[v], R.r[v]);
+    }
+    // The receive handle's bytes (kSoftScaled) fill only the high byte of a slot: the low bytes of both tables are zeroed when the wave starts and again behind every
+    // trace-back, whose register dump (Lds16::udump) lies over them -- three stores per lane and 256 steps.
+    __device__ __forceinline__ void clear_ops(Lds16<WIN, LOOK>& S) const
+    {
+        if constexpr (BITS == kSoftScaled) {
+            static_assert(sizeof(S.ops2) == 3 * 64 * 4, "three dwords per lane");
+            uint32_t* z = reinterpret_cast<uint32_t*>(&S.ops2[0][0][0][0]) + (threadIdx.x & 63);
+            z[0] = 0u; z[64] = 0u; z[128] = 0u;
+            lds_fence();
+        }
+    }
+    // The same chunk's loads without the clamp, for a loop that knows the buffer behind the streams to be padded (rx_types.h: kSoftPad): the address is p + a
+    // compile-time offset, p = fast_base(c0) the lane's byte offset of operand j of chunk c0 -- one register, advanced once per turn of the loop by whoever calls.
+    __device__ __forceinline__ uint32_t fast_base(uint32_t c0) const { return my_base + c0 * (uint32_t)CW; }
+    template <int DC> __device__ __forceinline__ Raw fetch_at(uint32_t p) const
+    {
+        static_assert(BITS == kSoftScaled, "one byte per value");
+        Raw R;
+#pragma unroll
+        for (int v = 0; v < NV; v++) { R.r[v].sh = 0; R.r[v].w = soft[(size_t)p + (size_t)(DC * CW + 8 * v)]; }
+        return R;
     }
     // ... and the row's table into every lane's registers
     static __device__ __forceinline__ Chunk get(const uint4* table)

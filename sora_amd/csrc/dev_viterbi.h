@@ -99,7 +99,7 @@ __device__ __forceinline__ unsigned dpp_pkmin_wave(unsigned v)         // per-ha
 }
 
 // ------------------------------------------------------------------------------------------------
-// The soft stream (rx_types.h).  Producers pack eight values (three bits each, value j in bits 3 j ..) into three bytes; a trellis lane
+// The packed soft stream (rx_types.h: what sora_hip_viterbi11a* makes of its caller's bytes).  Eight values (three bits each, value j in bits 3 j ..) are three bytes; a trellis lane
 // fetches the 16 bits that contain value i of its frame -- at any byte address: gfx950 serves unaligned 16-bit loads
 // (tools/calib/unaligned_probe.hip) -- and shifts.
 __device__ __forceinline__ uint32_t soft3_pack8(const uint32_t v[8])
@@ -112,8 +112,9 @@ __device__ __forceinline__ void soft3_store8(uint8_t* stream, uint32_t group, ui
     p[0] = (uint8_t)bits24; p[1] = (uint8_t)(bits24 >> 8); p[2] = (uint8_t)(bits24 >> 16);
 }
 struct SoftRaw { uint32_t w, sh; };                        // a fetched value before the shift
-// One lane's view of one frame's stream: value k of every CW-value chunk.  BITS is a property of the kernel (3 for the 802.11a graph's
-// producers, 8 for the 802.11n / 40 MHz ones).  When a chunk is a whole number of bytes (every case but three-bit values at rate 2/3) the
+// One lane's view of one frame's stream: value k of every CW-value chunk.  BITS is a property of the kernel (3 for the streams sora_hip_viterbi11a*
+// packs, 8 for the 802.11n / 40 MHz producers' raw bytes; kSoftScaled, the 802.11a handle's pre-scaled bytes, has a cursor of its own below).
+// When a chunk is a whole number of bytes (every case but three-bit values at rate 2/3) the
 // value's bit offset inside its byte never changes: a fetch is an add, a clamp and a load, the field a shift and a mask.  Past the frame's
 // end the fetch address stays on the frame's last value (some well-formed value: nobody uses it).
 template <int BITS, int CW> struct SoftCursor {
@@ -141,6 +142,25 @@ template <int BITS, int CW> struct SoftCursor {
         return kConst ? (r.w << lsh) & 0x0E00u : ((r.w >> r.sh) & 7u) << 9;
     }
 };
+
+// The receive handle's format (rx_types.h: kSoftScaled): one byte per value, already v << 1 -- the high byte of the 16-bit metric field.  A fetch is an add, a
+// clamp and a byte load; there is no field(): the byte goes into byte 1 of the lane's operand slot as it is (soft_put), and the slot's low byte stays zero.
+template <int CW> struct SoftCursor<kSoftScaled, CW> {
+    uint32_t off, lim;       // byte offset (from the soft base) of the value in chunk 0 / of the frame's last value
+    __device__ __forceinline__ void init(uint32_t stream_off, uint32_t k, uint32_t last) { off = stream_off + min(k, last); lim = stream_off + last; }
+    __device__ __forceinline__ SoftRaw fetch(const uint8_t* __restrict__ base, uint32_t c) const
+    {
+        SoftRaw r; r.sh = 0; r.w = base[min(off + c * (uint32_t)CW, lim)];
+        return r;
+    }
+};
+// a fetched value into its 16-bit slot of an operand table in LDS
+template <int BITS, int CW>
+__device__ __forceinline__ void soft_put(uint16_t* slot, const SoftCursor<BITS, CW>& cur, const SoftRaw& r)
+{
+    if constexpr (BITS == kSoftScaled) reinterpret_cast<uint8_t*>(slot)[1] = (uint8_t)r.w;
+    else *slot = (uint16_t)cur.field(r);
+}
 
 constexpr unsigned kFld = (1u << 9) | (1u << 25);        // one unit of u in both halves
 // mark bit 0 of both frames: bit 0 (frame A), bit 17 (frame B; bit 16 is the carry guard, see acs_step)
@@ -358,6 +378,7 @@ struct VitForward {
         tr = 0; ob = ob0;
         cur.init(M.soft_off, my_k + M.i0, M.last);
         soft_base = soft_base_; ops = ops_;
+        if (BITS == kSoftScaled) { ops[lane] = 0; lds_fence(); }                // the slots' low bytes: soft_put writes the high ones only, and nothing else writes this table
         my_op = ops + 2u * my_k + (lane >> 5);                                  // operand k, frame's half (k up to 31: the table has 32 operands, those past CW are never read)
     }
     __device__ __forceinline__ bool going() const { return tr < nsteps && !(A.done && B.done); }
@@ -367,7 +388,7 @@ struct VitForward {
     __device__ __forceinline__ SoftRaw fetch(uint32_t c) const { return cur.fetch(soft_base, c); }
     __device__ __forceinline__ Chunk unpack(const SoftRaw& R)
     {
-        *my_op = (uint16_t)cur.field(R);
+        soft_put(my_op, cur, R);
         lds_fence();
         Chunk K;
 #pragma unroll

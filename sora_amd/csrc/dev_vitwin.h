@@ -138,7 +138,7 @@ __device__ __forceinline__ void forward16w(Lds16<WIN, LOOK>& S, const uint8_t* _
                 if (F.tr >= my_tr_end) { cnt = my_tr_end - my_ob - 6; my_done = true; }
                 else if (F.tr >= my_ob + THR) { cnt = WIN; partial = true; }
             }
-            if (wave_max_u32(cnt) != 0u) trace(cnt, t24_last);
+            if (wave_max_u32(cnt) != 0u) { trace(cnt, t24_last); F.clear_ops(S); }
             if (partial) { my_ob += WIN; if (--my_wleft == 0) my_done = true; }
             F.next_thr = next_event();
             F.all_done = wave_min_u32(my_done ? 1u : 0u) != 0u;

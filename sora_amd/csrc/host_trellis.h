@@ -44,9 +44,11 @@ inline uint32_t win_vstride(uint64_t rows) { return (uint32_t)(win_units(rows) +
 
 // The job table a launch works over: three code-rate lists of `stride` jobs each behind a header of their three counts, holding at most n jobs together (a handle's
 // call), or ONE list of exactly n jobs (the stage entry points: the serial kernels take n itself and no header; the windowed form reads hdr = {n, 0, 0}).
-struct TrellisJobs { const VitJob* jobs; const uint32_t* hdr; uint32_t n, stride; bool single; };
-inline TrellisJobs trellis_lists(const VitJob* jobs, const uint32_t* hdr, uint32_t n, uint32_t stride) { return TrellisJobs{ jobs, hdr, n, stride, false }; }
-inline TrellisJobs trellis_single(const VitJob* jobs, const uint32_t* hdr, uint32_t n) { return TrellisJobs{ jobs, hdr, n, n, true }; }
+// packed3 (WIN = 256 only): the streams are the three-bit ones sora_hip_viterbi11a* packs into its caller's workspace, not a receive handle's pre-scaled bytes in its
+// padded array (rx_types.h) -- the *_p3 instantiations of the same kernels, which clamp every fetch.
+struct TrellisJobs { const VitJob* jobs; const uint32_t* hdr; uint32_t n, stride; bool single, packed3; };
+inline TrellisJobs trellis_lists(const VitJob* jobs, const uint32_t* hdr, uint32_t n, uint32_t stride) { return TrellisJobs{ jobs, hdr, n, stride, false, false }; }
+inline TrellisJobs trellis_single(const VitJob* jobs, const uint32_t* hdr, uint32_t n, bool packed3) { return TrellisJobs{ jobs, hdr, n, n, true, packed3 }; }
 // workgroups of the kernels that take PAIRS of frames, four pairs each (k_viterbi*, k_win_redo*): at most ceil(n / 2) + 2 pairs over three lists, ceil(n / 2) of one
 inline uint32_t trellis_pair_groups(const TrellisJobs& J) { return J.single ? (J.n + 7) / 8 : (J.n / 2 + 3 + 3) / 4; }
 // one-wave workgroups of k_viterbi16*, eight frames each: at most ceil(n / 8) + 2 waves over three lists
@@ -104,7 +106,8 @@ template <int WIN> inline void trellis_proof(const TrellisJobs& J, const uint8_t
 {
     static_assert(WIN == 256 || WIN == 192, "the 802.11a (256) or the 802.11n (192) window schedule");
     if constexpr (WIN == 256)
-        hipLaunchKernelGGL(k_win_redo, dim3(trellis_pair_groups(J)), dim3(256), 0, st, J.jobs, J.hdr, J.stride, kWinUnitsTarget, W.stride, (const uint16_t*)W.d_vecs, soft, out, W.d_stats);
+        hipLaunchKernelGGL(J.packed3 ? k_win_redo_p3 : k_win_redo, dim3(trellis_pair_groups(J)), dim3(256), 0, st, J.jobs, J.hdr, J.stride, kWinUnitsTarget, W.stride,
+                           (const uint16_t*)W.d_vecs, soft, out, W.d_stats);
     else
         hipLaunchKernelGGL(k_win_redo_11n, dim3(trellis_pair_groups(J)), dim3(256), 0, st, J.jobs, J.hdr, J.stride, kWinUnitsTarget, W.stride, (const uint16_t*)W.d_vecs, soft, out, W.d_stats);
 }
@@ -117,14 +120,16 @@ template <int WIN> inline void trellis_launch(Trellis kind, const TrellisJobs& J
     const uint32_t* hdr = J.single ? nullptr : J.hdr;
     const uint32_t n1 = J.single ? J.n : 0u, stride = J.single ? 0u : J.stride;    // (the serial kernels: a header and a stride, or a count)
     if (kind == Trellis::Windowed) {
-        if constexpr (WIN == 256) hipLaunchKernelGGL(k_viterbi16w, dim3(trellis_win_waves(J)), dim3(64), 0, st, J.jobs, J.hdr, J.stride, kWinUnitsTarget, W.stride, soft, out, W.d_vecs);
+        if constexpr (WIN == 256)
+            hipLaunchKernelGGL(J.packed3 ? k_viterbi16w_p3 : k_viterbi16w, dim3(trellis_win_waves(J)), dim3(64), 0, st, J.jobs, J.hdr, J.stride, kWinUnitsTarget, W.stride, soft, out,
+                               W.d_vecs);
         else hipLaunchKernelGGL(k_viterbi16w_11n, dim3(trellis_win_waves(J)), dim3(64), 0, st, J.jobs, J.hdr, J.stride, kWinUnitsTarget, W.stride, soft, out, W.d_vecs);
         if (proof) trellis_proof<WIN>(J, soft, out, W, st);
     } else if (kind == Trellis::Lanes16) {
-        if constexpr (WIN == 256) hipLaunchKernelGGL(k_viterbi16, dim3(trellis_waves16(J)), dim3(64), 0, st, J.jobs, hdr, n1, stride, soft, out);
+        if constexpr (WIN == 256) hipLaunchKernelGGL(J.packed3 ? k_viterbi16_p3 : k_viterbi16, dim3(trellis_waves16(J)), dim3(64), 0, st, J.jobs, hdr, n1, stride, soft, out);
         else hipLaunchKernelGGL(k_viterbi16_11n, dim3(trellis_waves16(J)), dim3(64), 0, st, J.jobs, hdr, n1, stride, soft, out);
     } else {
-        if constexpr (WIN == 256) hipLaunchKernelGGL(k_viterbi, dim3(trellis_pair_groups(J)), dim3(256), 0, st, J.jobs, hdr, n1, stride, soft, out);
+        if constexpr (WIN == 256) hipLaunchKernelGGL(J.packed3 ? k_viterbi_p3 : k_viterbi, dim3(trellis_pair_groups(J)), dim3(256), 0, st, J.jobs, hdr, n1, stride, soft, out);
         else hipLaunchKernelGGL(k_viterbi11n, dim3(trellis_pair_groups(J)), dim3(256), 0, st, J.jobs, hdr, n1, stride, soft, out);
     }
 }

@@ -32,7 +32,7 @@ namespace sora {
 // the pass's four symbols in order, pilot k in lane k, the loop state in scalar registers.  The equalised symbol never
 // leaves LDS; the small tables (demap steps, de-interleaver map) live in LDS, the FFT twiddles in registers; the next
 // pass's samples are requested before the tracking loop so that their latency hides behind it.
-//   algorithmic bytes per data symbol: 256 read (64 of the 80 samples) + 3 N_CBPS / 8 written (the packed soft stream, rx_types.h)
+//   algorithmic bytes per data symbol: 256 read (64 of the 80 samples) + 3 N_CBPS / 8 (three bits per soft value; the stream itself is a byte per value, rx_types.h)
 struct FrameLds {
     uint32_t eq[4][4][64];                                                       // [wave][symbol of the pass]: FFT staging, then the equalised bins
     uint8_t  soft[4][4][288];                                                    // [wave][symbol of the pass]: soft values in carrier order
@@ -71,7 +71,7 @@ __device__ __forceinline__ void frame_symbols(const RxArgs& A, uint32_t j, Frame
     uint32_t mp[4];
     const bool packs = deint_packs(nb, lane);
     deint_map_words(T, nb, lane, mp);
-    // the frame's packed soft stream: symbol s (1-based) at 3 N_CBPS / 8 * (s - 1) bytes
+    // the frame's soft stream: symbol s (1-based) at N_CBPS * (s - 1) bytes
     uint8_t* dst = A.soft + (size_t)r.slot0 * kSoftBytesPerSlot;
     // pilot k in lane k: bins 43, 57, 7, 21 = carriers -21, -7, +7, +21 (pilot.hpp:138-164)
     const int pk = lane & 3;
@@ -172,13 +172,13 @@ __device__ __forceinline__ void frame_symbols(const RxArgs& A, uint32_t j, Frame
             sym_back_demap(T, s_demap, v3, rec, nb, e, s_soft[w][g]);
         }
         wave_lds_sync();
-        // ---- T11aDeinterleave*: out[k] = in[j(k)], eight values -> three bytes of the frame's stream (soft3_store8), symbol by symbol
+        // ---- T11aDeinterleave*: out[k] = in[j(k)], eight values -> eight bytes of the frame's stream (one store), symbol by symbol
         {
             const int nact = min(4, nsym - s0 + 1);
-            const uint32_t sym_bytes = 3u * (uint32_t)ncbps / 8u;
+            const uint32_t sym_bytes = (uint32_t)ncbps;
             uint8_t* d = dst + (size_t)(s0 - 1) * sym_bytes;
             for (int gs = 0; gs < nact; gs++, d += sym_bytes)
-                if (packs) soft3_store8(d, (uint32_t)lane, deint_gather24(s_soft[w][gs], mp));
+                if (packs) soft8_store(d, (uint32_t)lane, deint_gather8(s_soft[w][gs], mp));
         }
         wave_lds_sync();
     }
@@ -186,7 +186,7 @@ __device__ __forceinline__ void frame_symbols(const RxArgs& A, uint32_t j, Frame
 __global__ void __launch_bounds__(256) k_frame(RxArgs A)
 {
     __shared__ FrameLds lds;
-    reinterpret_cast<uint32_t*>(lds.demap)[threadIdx.x] = reinterpret_cast<const uint32_t*>(A.T.demap)[threadIdx.x];
+    demap_table_to_lds(A.T, lds.demap);
     __syncthreads();                                                             // the only block barrier: the waves are independent from here on
     if (!locate_job(blockIdx.x * 4, A.njobs).ok) return;                         // (the whole workgroup)
     const JobRef jr = locate_job(blockIdx.x * 4 + (threadIdx.x >> 6), A.njobs);
@@ -424,15 +424,15 @@ __global__ void __launch_bounds__(256) k_track_lds(RxArgs A)
     }
 }
 
-// Behind the tracker: TPhaseCompensate + TPilotTrack::_rotate + T11aDemap per group (sym_back_demap), then T11aDeinterleave + the packed three-bit stream, a
-// symbol at a time across the wave (eight values -> three bytes per lane).
+// Behind the tracker: TPhaseCompensate + TPilotTrack::_rotate + T11aDemap per group (sym_back_demap), then T11aDeinterleave + the soft stream, a
+// symbol at a time across the wave (eight values -> eight bytes per lane).
 __global__ void __launch_bounds__(256) k_sym_back(RxArgs A)
 {
     __shared__ uint8_t s_soft[4][4][288];                                        // [wave][group]: soft values in carrier order
     __shared__ uint8_t s_demap[1024];                                            // DemapperCore step tables
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, e = lane & 15;
     const Tables& T = A.T;
-    reinterpret_cast<uint32_t*>(s_demap)[threadIdx.x] = reinterpret_cast<const uint32_t*>(T.demap)[threadIdx.x];
+    demap_table_to_lds(T, s_demap);
     __syncthreads();                                                             // the only block barrier: the waves are independent from here on
     const WaveSlots S = wave_slots(A, blockIdx.x);
     if (S.owned == 0) return;
@@ -443,7 +443,7 @@ __global__ void __launch_bounds__(256) k_sym_back(RxArgs A)
         // ---- one frame: modulation, stream position and de-interleaver entries once per wave; the loads of all four quads up front
         const FrameRow& r = A.frames[S.row0];
         const int nb = __builtin_amdgcn_readfirstlane((int)r.nbpsc), ncbps = 48 * nb;
-        const uint32_t slot0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.slot0), sym_bytes = 3u * (uint32_t)ncbps / 8u;
+        const uint32_t slot0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.slot0), sym_bytes = (uint32_t)ncbps;
         uint8_t* stream = A.soft + (size_t)slot0 * kSoftBytesPerSlot;
         const bool packs = deint_packs(nb, lane);
         uint32_t mp[4];
@@ -467,7 +467,7 @@ __global__ void __launch_bounds__(256) k_sym_back(RxArgs A)
             for (int gs = 0; gs < 4; gs++) {
                 if (!((quad >> gs) & 1u) || !packs) continue;
                 const uint32_t sg = S.slot(it, gs);                              // data symbol sg - slot0 of the frame
-                soft3_store8(stream + (size_t)(sg - slot0 - 1u) * sym_bytes, (uint32_t)lane, deint_gather24(s_soft[w][gs], mp));
+                soft8_store(stream + (size_t)(sg - slot0 - 1u) * sym_bytes, (uint32_t)lane, deint_gather8(s_soft[w][gs], mp));
             }
             wave_lds_sync();
         }
@@ -501,8 +501,8 @@ __global__ void __launch_bounds__(256) k_sym_back(RxArgs A)
             if (nbg != cur_nb) { cur_nb = nbg; deint_map_words(T, nbg, lane, mp); }
             if (deint_packs(nbg, lane)) {
                 const uint32_t sg = S.slot(it, gs);
-                uint8_t* d = A.soft + (size_t)slot0g * kSoftBytesPerSlot + (size_t)(sg - slot0g - 1u) * (3u * 48u * (uint32_t)nbg / 8u);
-                soft3_store8(d, (uint32_t)lane, deint_gather24(s_soft[w][gs], mp));
+                uint8_t* d = A.soft + (size_t)slot0g * kSoftBytesPerSlot + (size_t)(sg - slot0g - 1u) * (48u * (uint32_t)nbg);
+                soft8_store(d, (uint32_t)lane, deint_gather8(s_soft[w][gs], mp));
             }
         }
         wave_lds_sync();
@@ -562,7 +562,7 @@ __device__ __forceinline__ void pipe_track_block(const RxArgs& A, const PipeArgs
     const JobRef jr = locate_job(t, A.njobs);
     if (!jr.ok) return;                                                          // (the whole workgroup)
     track_tables_to_lds(A.T.trk, L.t, L.pol);                                    // (its loads are in flight while wave 0 waits for the front workgroups)
-    reinterpret_cast<uint32_t*>(L.demap)[threadIdx.x] = reinterpret_cast<const uint32_t*>(A.T.demap)[threadIdx.x];
+    demap_table_to_lds(A.T, L.demap);
     const uint32_t j = jr.list * A.nrows + jr.idx, f = A.joblist[j];
     const FrameRow r = A.frames[f];
     const uint32_t nsym = min((uint32_t)r.nsym, kPipeMaxSym - 8u), slot0 = r.slot0;
@@ -629,7 +629,7 @@ __device__ __forceinline__ void pipe_track_block(const RxArgs& A, const PipeArgs
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                           // (eq[] was written by the front workgroups of this launch)
     const int h = w - 1, g = lane >> 4, e = lane & 15;
     const int nb = __builtin_amdgcn_readfirstlane((int)r.nbpsc), ncbps = 48 * nb;
-    const uint32_t sym_bytes = 3u * (uint32_t)ncbps / 8u;
+    const uint32_t sym_bytes = (uint32_t)ncbps;
     uint8_t* stream = A.soft + (size_t)slot0 * kSoftBytesPerSlot;
     const bool packs = deint_packs(nb, lane);
     uint32_t mp[4];
@@ -653,17 +653,17 @@ __device__ __forceinline__ void pipe_track_block(const RxArgs& A, const PipeArgs
         const uint2 rw = L.rec[(s - 1u) & (kPipeRing - 1u)];
         if (mine) sym_back_demap(A.T, L.demap, v3, int4{ (int16_t)rw.x, (int16_t)(rw.x >> 16), (int16_t)rw.y, (int16_t)(rw.y >> 16) }, nb, e, L.soft[h][g]);
         wave_lds_sync();
-        uint32_t b24[4];
+        uint2 b8[4];
 #pragma unroll
-        for (int gs = 0; gs < 4; gs++) b24[gs] = deint_gather24(L.soft[h][gs], mp);
+        for (int gs = 0; gs < 4; gs++) b8[gs] = deint_gather8(L.soft[h][gs], mp);
         wave_lds_sync();
         if (packs) {
 #pragma unroll
-            for (int gs = 0; gs < 4; gs++) soft3_store8(bytes + (uint32_t)gs * sym_bytes, (uint32_t)lane, b24[gs]);
+            for (int gs = 0; gs < 4; gs++) soft8_store(bytes + (uint32_t)gs * sym_bytes, (uint32_t)lane, b8[gs]);
         }
         wave_lds_sync();
-        // the quad's bytes (a multiple of eight from a multiple-of-four address: 72 N_BPSC per quad; a last, shorter quad is rounded up into the frame's own spare slot)
-        const uint32_t ndw = (nact * sym_bytes + 3u) / 4u;
+        // the quad's bytes (whole dwords: 48 N_BPSC per symbol)
+        const uint32_t ndw = nact * sym_bytes / 4u;
         uint32_t* out32 = reinterpret_cast<uint32_t*>(stream + (size_t)(4u * k) * sym_bytes);
         for (uint32_t i = (uint32_t)lane; i < ndw; i += 64u) store4_through(out32 + i, reinterpret_cast<const uint32_t*>(bytes)[i]);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -713,7 +713,7 @@ __device__ __forceinline__ void pipe_trellis_wave(const RxArgs& A, const PipeArg
         const unsigned lane = threadIdx.x & 63;
         return pipe_units_ready(A, P, list, (lane & 1u) ? GB_ : GA, (lane & 15u) < 2u, wave_index);      // one lane per unit polls
     };
-    viterbi16w_wave<256, 24, 3>(S, wave_index, jobs_of, ready, A.njobs, P.target, P.vstride, (const uint8_t*)A.soft, A.vout, P.vecs);
+    viterbi16w_wave<256, 24, kSoftScaled>(S, wave_index, jobs_of, ready, A.njobs, P.target, P.vstride, (const uint8_t*)A.soft, A.vout, P.vecs);
     PIPE_STAMP(P, 17 + 2 * wave_index);
 }
 
@@ -810,7 +810,7 @@ __device__ __forceinline__ void pipe_trellis_wave64(const RxArgs& A, const PipeA
         if (GB_.valid && (!GA.valid || GB_.ob != GA.ob)) { if (!GA.valid) { GA = GB_; } const bool no = false; GB_.valid = no; }
         if (!GA.valid) return;
         const unsigned lane = threadIdx.x & 63;
-        viterbi_forward_unit<CR, 256, 24, 3>(GA, GB_, (const uint8_t*)A.soft, L.ring, L.ops, P.vecs,
+        viterbi_forward_unit<CR, 256, 24, kSoftScaled>(GA, GB_, (const uint8_t*)A.soft, L.ring, L.ops, P.vecs,
                                              [&]() { return pipe_units_ready(A, P, list, lane >= 32u ? GB_ : GA, (lane & 31u) == 0u, wave_index); });
     };
     if (code_rate == 0) run(std::integral_constant<int, 0>{});
@@ -890,6 +890,10 @@ __device__ __forceinline__ void viterbi_kernel_body(const VitJob* __restrict__ j
 
 __global__ void __launch_bounds__(256) k_viterbi(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ njobs3, uint32_t njobs_single, uint32_t stride,
         const uint8_t* __restrict__ soft, uint8_t* __restrict__ out)
+{ viterbi_kernel_body<256, 24, kSoftScaled>(jobs, njobs3, njobs_single, stride, soft, out); }
+// the same decoder over three-bit streams in a caller's workspace (sora_hip_viterbi11a*)
+__global__ void __launch_bounds__(256) k_viterbi_p3(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ njobs3, uint32_t njobs_single, uint32_t stride,
+        const uint8_t* __restrict__ soft, uint8_t* __restrict__ out)
 { viterbi_kernel_body<256, 24, 3>(jobs, njobs3, njobs_single, stride, soft, out); }
 // the 802.11n graph's decoder: T11aViterbi<5000*8, 312, 192, 36> (fb11ndemod_config.hpp:199)
 __global__ void __launch_bounds__(256) k_viterbi11n(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ njobs3, uint32_t njobs_single,
@@ -937,6 +941,11 @@ using WinProofGate = WinProofGateT<256u, 24u>;
 __global__ void __launch_bounds__(256) k_win_redo(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ hdr, uint32_t jstride, uint32_t target,
         uint32_t vstride, const uint16_t* __restrict__ vecs,
                                                   const uint8_t* __restrict__ soft, uint8_t* __restrict__ out, unsigned long long* __restrict__ stats)
+{ viterbi_kernel_body<256, 24, kSoftScaled>(jobs, hdr, 0u, jstride, soft, out, WinProofGate{ jobs, hdr, jstride, target, vstride, vecs, stats }); }
+// ... over three-bit streams in a caller's workspace (sora_hip_viterbi11a*)
+__global__ void __launch_bounds__(256) k_win_redo_p3(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ hdr, uint32_t jstride, uint32_t target,
+        uint32_t vstride, const uint16_t* __restrict__ vecs,
+                                                     const uint8_t* __restrict__ soft, uint8_t* __restrict__ out, unsigned long long* __restrict__ stats)
 { viterbi_kernel_body<256, 24, 3>(jobs, hdr, 0u, jstride, soft, out, WinProofGate{ jobs, hdr, jstride, target, vstride, vecs, stats }); }
 // ... for the 802.11n graph's decoder (windows of 192 bits, 36 of look-ahead, one byte per soft value)
 __global__ void __launch_bounds__(256) k_win_redo_11n(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ hdr, uint32_t jstride, uint32_t target,
@@ -1069,17 +1078,17 @@ __device__ __forceinline__ void win_redo_finish_body(const VitJob* jobs, const u
     const WinProofGate proof{ jobs, hdr, jstride, target, vstride, vecs, stats };
     if constexpr (PIPE) {
         __shared__ FrameLds F;
-        reinterpret_cast<uint32_t*>(F.demap)[threadIdx.x] = reinterpret_cast<const uint32_t*>(A.T.demap)[threadIdx.x];
+        demap_table_to_lds(A.T, F.demap);
         __syncthreads();
         const bool gave_up = __builtin_amdgcn_readfirstlane((int)A.pipe_flags[0]) != 0;
         if (gave_up && blockIdx.x == 0 && threadIdx.x == 0) {
             if (stats) atomicAdd(&stats[4u * kWinStatBanks], 1ull);
             if (host_note) __hip_atomic_store(host_note, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
-        viterbi_kernel_body<256, 24, 3>(jobs, hdr, 0u, jstride, soft, out, PipeFallbackGate{ proof, &A, &F, gave_up }, after);
+        viterbi_kernel_body<256, 24, kSoftScaled>(jobs, hdr, 0u, jstride, soft, out, PipeFallbackGate{ proof, &A, &F, gave_up }, after);
     } else {
         __syncthreads();
-        viterbi_kernel_body<256, 24, 3>(jobs, hdr, 0u, jstride, soft, out, proof, after);
+        viterbi_kernel_body<256, 24, kSoftScaled>(jobs, hdr, 0u, jstride, soft, out, proof, after);
     }
 }
 __global__ void __launch_bounds__(256) k_win_redo_finish(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride,

@@ -24,9 +24,9 @@
 // frames (k_viterbi: 5 to 8 for two).
 //
 // Operands.  The four rows decode different pairs, so the operands are per-lane values.  Lane (row, 2 j + f) fetches soft
-// values j, j + 8 (, j + 16) of the chunk from frame f's packed stream (rx_types.h: three bits per value; 16-bit loads, two
-// chunks ahead -- vector loads return in order, so the look-ahead is just a deeper vmcnt), shifts them into 16-bit metric
-// fields and writes them to the row's operand table in LDS; four to six broadcast ds_read_b128 then hand every lane the
+// values j, j + 8 (, j + 16) of the chunk from frame f's stream (rx_types.h: a byte that is the high byte of the 16-bit metric
+// field; byte loads, two chunks ahead -- vector loads return in order, so the look-ahead is just a deeper vmcnt) and writes
+// them into the high bytes of its slots of the row's operand table in LDS (the other formats: a 16-bit load, a shift, a mask); four to six broadcast ds_read_b128 then hand every lane the
 // chunk's operands (field A | field B << 16).  Round 3 first read ready-made operand dwords from HBM (264 MB per call
 // written and read; now 50).
 //
@@ -78,7 +78,7 @@ __device__ __forceinline__ void forward16(Lds16<WIN, LOOK>& S, const uint8_t* __
                 if (F.tr >= my_tr_end) { cnt = my_tr_end - ob - 6; my_done = true; }
                 else if (partial) cnt = WIN;
             }
-            if (wave_max_u32(cnt) != 0u) trace(cnt, t24_last);
+            if (wave_max_u32(cnt) != 0u) { trace(cnt, t24_last); F.clear_ops(S); }
             if (partial) ob += WIN;
             F.next_thr = next_event();
             F.all_done = wave_min_u32(my_done ? 1u : 0u) != 0u;
@@ -114,14 +114,28 @@ __device__ __forceinline__ void forward16(Lds16<WIN, LOOK>& S, const uint8_t* __
             Chunk Ka, Kb;
             b2 = F.fetch(c + 2);
             stage(b0, 0); Ka = collect(0); lds_fence();
-            for (; rows >= 2; rows -= 2) {
-                b3 = F.fetch(c + 3); stage(b1, 1); fast_chunk_mid(Ka, 0, Kb, 1);
-                b0 = F.fetch(c + 4); stage(b2, 0); fast_chunk_mid(Kb, 1, Ka, 0);
-                F.end_row();
-                b1 = F.fetch(c + 5); stage(b3, 1); fast_chunk_mid(Ka, 0, Kb, 1);
-                b2 = F.fetch(c + 6); stage(b0, 0); fast_chunk_mid(Kb, 1, Ka, 0);
-                F.end_row();
-                c += 4;
+            if constexpr (BITS == kSoftScaled) {
+                // the handle's padded buffer: no clamp, one address register per turn and the turn's four chunks at compile-time offsets from it
+                uint32_t p = F.fast_base(c);
+                for (; rows >= 2; rows -= 2) {
+                    b3 = F.template fetch_at<3>(p); stage(b1, 1); fast_chunk_mid(Ka, 0, Kb, 1);
+                    b0 = F.template fetch_at<4>(p); stage(b2, 0); fast_chunk_mid(Kb, 1, Ka, 0);
+                    F.end_row();
+                    b1 = F.template fetch_at<5>(p); stage(b3, 1); fast_chunk_mid(Ka, 0, Kb, 1);
+                    b2 = F.template fetch_at<6>(p); stage(b0, 0); fast_chunk_mid(Kb, 1, Ka, 0);
+                    F.end_row();
+                    c += 4; p += 4u * (uint32_t)F16::CW;
+                }
+            } else {
+                for (; rows >= 2; rows -= 2) {
+                    b3 = F.fetch(c + 3); stage(b1, 1); fast_chunk_mid(Ka, 0, Kb, 1);
+                    b0 = F.fetch(c + 4); stage(b2, 0); fast_chunk_mid(Kb, 1, Ka, 0);
+                    F.end_row();
+                    b1 = F.fetch(c + 5); stage(b3, 1); fast_chunk_mid(Ka, 0, Kb, 1);
+                    b2 = F.fetch(c + 6); stage(b0, 0); fast_chunk_mid(Kb, 1, Ka, 0);
+                    F.end_row();
+                    c += 4;
+                }
             }
             // (the tables share their bytes with unpack()'s and the trace-back's: nothing of them is pending past here)
             lds_fence();
@@ -172,6 +186,10 @@ __device__ __forceinline__ void viterbi16_body(const VitJob* __restrict__ jobs, 
 }  // namespace
 
 __global__ void __launch_bounds__(64) k_viterbi16(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ njobs3, uint32_t njobs_single, uint32_t stride,
+        const uint8_t* __restrict__ soft, uint8_t* __restrict__ out)
+{ viterbi16_body<256, 24, kSoftScaled>(jobs, njobs3, njobs_single, stride, soft, out); }
+// the same decoder over three-bit streams in a caller's workspace (sora_hip_viterbi11a*: every fetch clamped, nothing assumed behind the streams)
+__global__ void __launch_bounds__(64) k_viterbi16_p3(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ njobs3, uint32_t njobs_single, uint32_t stride,
         const uint8_t* __restrict__ soft, uint8_t* __restrict__ out)
 { viterbi16_body<256, 24, 3>(jobs, njobs3, njobs_single, stride, soft, out); }
 __global__ void __launch_bounds__(64) k_viterbi16_11n(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ njobs3, uint32_t njobs_single,

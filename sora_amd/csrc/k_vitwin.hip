@@ -32,6 +32,10 @@ namespace sora {
 
 __global__ void __launch_bounds__(64) k_viterbi16w(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ hdr, uint32_t jstride, uint32_t target, uint32_t vstride,
                                                    const uint8_t* __restrict__ soft, uint8_t* __restrict__ out, uint16_t* __restrict__ vecs)
+{ viterbi16w_body<256, 24, kSoftScaled>(jobs, hdr, jstride, target, vstride, soft, out, vecs); }
+// ... over three-bit streams in a caller's workspace (sora_hip_viterbi11a*)
+__global__ void __launch_bounds__(64) k_viterbi16w_p3(const VitJob* __restrict__ jobs, const uint32_t* __restrict__ hdr, uint32_t jstride, uint32_t target, uint32_t vstride,
+                                                      const uint8_t* __restrict__ soft, uint8_t* __restrict__ out, uint16_t* __restrict__ vecs)
 { viterbi16w_body<256, 24, 3>(jobs, hdr, jstride, target, vstride, soft, out, vecs); }
 // the 802.11n graph's decoder, T11aViterbi<5000*8, 312, 192, 36> (fb11ndemod_config.hpp:199), one byte per soft value: the same body -- a unit's verify point
 // floor24(192 k0) is 192 k0 itself

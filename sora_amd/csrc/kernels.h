@@ -52,7 +52,7 @@ struct RxArgs {
     Tables          T;
     FrameRow*       frames;
     const FrameCtx* fctx;
-    uint8_t*        soft;           // [slots*108] the frames' packed soft streams (three bits per value, rx_types.h)
+    uint8_t*        soft;           // [slots*288 + pad] the frames' soft streams (one byte per value, v << 1: rx_types.h)
     uint8_t*        vout;           // [slots*32]
     uint8_t*        mpdu;           // [slots*32]
     VitJob*         jobs;           // [3][nrows] (indexed by job)
@@ -87,17 +87,22 @@ __global__ void k_track_lds(RxArgs A);
 __global__ void k_sym_back(RxArgs A);
 __global__ void k_pipe(RxArgs A, PipeArgs P);
 __global__ void k_viterbi(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
+__global__ void k_viterbi_p3(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
 __global__ void k_viterbi11n(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
 // k_vit16.hip
 __global__ void k_viterbi16(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
+__global__ void k_viterbi16_p3(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
 __global__ void k_viterbi16_11n(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
 // k_vitwin.hip: the window-parallel trellis.  hdr = the call's counter block (njobs per code rate in its first three words); jstride = capacity of a list of jobs;
 // target = units the call is cut into at least, frames permitting; vstride = vectors per code-rate list
 __global__ void k_viterbi16w(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint8_t* soft, uint8_t* out, uint16_t* vecs);
+__global__ void k_viterbi16w_p3(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint8_t* soft, uint8_t* out, uint16_t* vecs);
 __global__ void k_viterbi16w_11n(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint8_t* soft, uint8_t* out, uint16_t* vecs);
 __global__ void k_win_redo_11n(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint16_t* vecs,
         const uint8_t* soft, uint8_t* out, unsigned long long* stats);
 __global__ void k_win_redo(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint16_t* vecs,
+        const uint8_t* soft, uint8_t* out, unsigned long long* stats);
+__global__ void k_win_redo_p3(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint16_t* vecs,
         const uint8_t* soft, uint8_t* out, unsigned long long* stats);
 __global__ void k_win_redo_finish(const VitJob* jobs, const uint32_t* hdr, uint32_t jstride, uint32_t target, uint32_t vstride, const uint16_t* vecs,
         const uint8_t* soft, uint8_t* out, unsigned long long* stats,

@@ -5,11 +5,16 @@
 //   caps[]        per capture {offset, nsamples, id, slot_base}
 //   frames[]      frame table, max_frames_per_capture rows per capture, filled by k_scan in time order
 //   fctx[]        per frame: FreqCoeffs[64] + ChannelCoeffs[64] (CF_FreqCompensate / CF_Channel_11a)
-//   soft[]        per frame: its de-interleaved soft values (0..7) as a packed bit stream, THREE BITS per value, value i in bits
-//                 3 i .. 3 i + 2 (little-endian), base = slot0 * 108 bytes (a 64-QAM symbol's 288 values are exactly 108 bytes, so a
-//                 frame's stream never leaves its own symbol slots).  VitJob::soft_bits = 3: what k_viterbi / k_viterbi16 read.  (The 802.11n and
-//                 40 MHz producers write one BYTE per value, soft_bits = 8, read by k_viterbi11n / k_viterbi16_11n: the format is a
-//                 property of the kernel.)  Readers fetch 16 bits at byte (bits * i) >> 3 and take three of them.
+//   soft[]        per frame: its de-interleaved soft values (0..7), ONE BYTE per value holding v << 1, base = slot0 * 288 bytes (a 64-QAM
+//                 symbol's 288 values, so a frame's stream never leaves its own symbol slots).  The byte IS the high byte of the trellis's
+//                 16-bit metric field v << 9: a trellis lane loads it and stores it into byte 1 of its operand slot, no shift, no mask
+//                 (VitJob::soft_bits = kSoftScaled: what k_viterbi / k_viterbi16 / k_viterbi16w read).  The array is zeroed once and only
+//                 ever holds such bytes, and kSoftPad bytes follow the last slot: a lane whose frame has ended may fetch anywhere up to one
+//                 maximal stream past its own and still steps on well-formed operands nobody uses.
+//                 Two more formats exist, each a property of the kernel that reads it: one raw BYTE per value, its low three bits
+//                 (soft_bits = 8: the 802.11n and 40 MHz producers, k_viterbi11n / k_viterbi16_11n), and THREE BITS per value, value i in
+//                 bits 3 i .. 3 i + 2 of a little-endian bit stream (soft_bits = 3: what sora_hip_viterbi11a* packs the caller's bytes to in
+//                 its workspace, k_viterbi_p3 / k_viterbi16_p3 / k_viterbi16w_p3); their readers fetch 16 bits at byte (bits * i) >> 3.
 //   vout[]        per frame: Viterbi output bytes (length+2), base = slot0*32
 //   mpdu[]        per frame: descrambled MPDU, base = slot0*32 (same geometry as vout)
 //   rows[]        compacted sora_frame_result rows + counter
@@ -56,7 +61,8 @@ struct VitJob {             // one Viterbi decode: a frame of the RX path or one
     uint32_t out_off;       // bytes from the output base
     uint32_t valid;
     uint32_t code_rate;
-    // 3: packed three bits per soft value; 8: one byte per soft value (its low three bits) -- informative: the trellis kernel's template parameter decides
+    // 3: packed three bits per soft value; 8: one byte per soft value (its low three bits); kSoftScaled: one byte per soft value, v << 1 -- informative: the trellis
+    // kernel's template parameter decides
     uint32_t soft_bits;
 };
 
@@ -90,8 +96,14 @@ __host__ __device__ inline JobRef locate_job(uint32_t g, const uint32_t* njobs)
 }
 
 constexpr int kSoftPerSlot = 288;      // N_CBPS max
-constexpr int kSoftBytesPerSlot = 108; // ... at three bits each
+constexpr int kSoftBytesPerSlot = 288; // ... one byte each (v << 1)
 constexpr int kSoftSlack = 64;         // bytes behind the last stream that a reader's 16-bit fetch / a producer's padded last group may touch
+constexpr int kSoftScaled = 9;         // VitJob::soft_bits / the trellis kernels' BITS of the receive handle's format: a byte that is bits 8..15 of the field v << 9
+// Bytes behind a handle's last symbol slot.  The fast loop of k_viterbi16 fetches without a clamp: the lane of a frame that has ended goes on reading at its own
+// stream's offset + the wave's step count, at most one maximal stream (4095 bytes at 6 or 12 Mbps: 1366 x 48 or 683 x 96 = 65568 values) and the look-ahead of
+// seven 24-value chunks past its stream's start.
+constexpr int kSoftPad = 66 * 1024;
+static_assert(kSoftPad >= 65568 + 7 * 24 + 16 + kSoftSlack, "the pad holds a maximal stream and the look-ahead");
 constexpr int kOutPerSlot  = 32;       // decoded bytes per symbol max 27 -> 32
 
 constexpr uint32_t E_FRAME_OK = 0x00000001u, E_PLCP_HEADER_FAIL = 0x80000005u, E_CRC32_FAIL = 0x80000006u,

@@ -628,7 +628,7 @@ static int pipe_create(const sora_rx_cfg* cfg, RxPipe** out, int index = 0)
     // Symbol slots, frame rows and the byte offsets derived from them are 32-bit on the device: a configuration that would
     // wrap them is refused here instead of decoding garbage later.
     const uint64_t want_slots = n20 / 80 + cfg->max_captures + 16, want_rows = (uint64_t)cfg->max_captures * cfg->max_frames_per_capture;
-    if (want_slots * (1ull * kSoftPerSlot) >= (1ull << 32) || want_rows >= (1ull << 31) / 3 || cfg->max_total_samples >= (1ull << 32)) {
+    if (want_slots * (1ull * kSoftBytesPerSlot) + kSoftPad >= (1ull << 32) || want_rows >= (1ull << 31) / 3 || cfg->max_total_samples >= (1ull << 32)) {
         rx_free(rx);
         return fail(SORA_ERR_CAPACITY, "sora_rx_create: max_total_samples / max_captures x max_frames_per_capture exceed the 32-bit slot geometry of one handle "
                                        "(split the batch over several handles)");
@@ -699,8 +699,12 @@ static int pipe_process_dev(RxPipe* rx, const sora_complex16* d_iq, const sora_c
     rx->h_caps.swap(hc);
     rx->ncaps = (uint32_t)ncaps; rx->total_slots = slots; rx->have_results = false; rx->delivered = rx->released = false;
     if (ncaps == 0) { rx->have_results = true; return SORA_OK; }
-    if (!rx->d_soft) {                                                           // the packed soft streams and the job table, on the first call
-        HIPCHK(hipMalloc((void**)&rx->d_soft, (size_t)kSoftBytesPerSlot * rx->cap_slots + kSoftSlack));   // three bits per soft value (rx_types.h)
+    if (!rx->d_soft) {                                                           // the soft streams and the job table, on the first call
+        // one pre-scaled byte per soft value and the pad behind the last slot (rx_types.h).  Zeroed once: every byte a trellis lane can fetch, written yet or not, is
+        // a well-formed value
+        const size_t soft_bytes = (size_t)kSoftBytesPerSlot * rx->cap_slots + kSoftPad;
+        HIPCHK(hipMalloc((void**)&rx->d_soft, soft_bytes));
+        HIPCHK(hipMemsetAsync(rx->d_soft, 0, soft_bytes, rx->stream));
         HIPCHK(hipMalloc((void**)&rx->d_jobs, 3 * sizeof(VitJob) * rx->cap_rows));
     }
     const bool windowed = rx->trellis == Trellis::Windowed;
@@ -1974,7 +1978,7 @@ static int viterbi_ws(const char* name, const uint8_t* d_soft, size_t soft_span_
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)hdr, (int)n, 1, st));
         HIPCHK(hipMemsetAsync(stats, 0, kWinStatsBytes, st));
     }
-    trellis_launch<WIN>(kind, trellis_single(jobs, hdr, (uint32_t)n), soft, d_out, st, W);
+    trellis_launch<WIN>(kind, trellis_single(jobs, hdr, (uint32_t)n, WIN == 256), soft, d_out, st, W);
     HIPCHK(hipGetLastError());
     return SORA_OK;
 }

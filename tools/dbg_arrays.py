@@ -40,7 +40,7 @@ def grab(ptr, nbytes):
     return h
 out = {"frames": grab(ptrs[0], 64 * nrows.value).view(np.uint32).reshape(-1, 16), "slot_row": grab(ptrs[1], 4 * S).view(np.uint32),
        "eq": grab(ptrs[2], 256 * S).view(np.int16).reshape(S, 64, 2), "track": grab(ptrs[3], 8 * S).view(np.int16).reshape(S, 4),
-       "soft": grab(ptrs[4], 108 * S), "slots": np.array([S])}
+       "soft": grab(ptrs[4], 288 * S), "slots": np.array([S])}
 np.savez(sys.argv[1] if len(sys.argv) > 1 else "/tmp/dbg.npz", **out)
 fr = out["frames"][0]
 print("row0: capture", fr[0], "start", fr[1], "end", fr[2], "err", hex(fr[3]), "rate", fr[4], "len/nsym", fr[5] & 0xFFFF, fr[5] >> 16, "cr/nb", fr[6] & 0xFFFF, fr[6] >> 16, "slot0", fr[7])
@@ -48,4 +48,4 @@ sr = out["slot_row"]; own = np.nonzero(sr != 0xFFFFFFFF)[0]
 print("slots", S, "owned", len(own), own[:5], own[-5:] if len(own) else "")
 print("eq[slot0+1][:8]", out["eq"][fr[7] + 1][:8].tolist() if len(out["eq"]) else None)
 print("track[slot0+1..+4]", out["track"][fr[7] + 1:fr[7] + 5].tolist() if len(out["track"]) else None)
-print("soft first 24 bytes of the frame", out["soft"][fr[7] * 108:fr[7] * 108 + 24].tolist())
+print("soft first 24 bytes of the frame", out["soft"][fr[7] * 288:fr[7] * 288 + 24].tolist())
