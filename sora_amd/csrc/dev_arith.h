@@ -489,5 +489,13 @@ __device__ __forceinline__ uint32_t crc32_wave(const uint8_t* bytes, int n, cons
     }
     return c;
 }
+// Z_m of a register c for m = 40 * 2^k zero bytes (crc32_wave's tree tables): what joins the registers of two waves of crc32_wave
+__device__ __forceinline__ uint32_t crc_zeros(const uint32_t* s_z, int k, uint32_t c)
+{
+    uint32_t z = 0;
+#pragma unroll
+    for (int q = 0; q < 8; q++) z ^= s_z[(k * 8 + q) * 16 + ((c >> (4 * q)) & 15u)];
+    return z;
+}
 
 }  // namespace sora

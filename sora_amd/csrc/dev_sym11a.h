@@ -18,13 +18,7 @@ __device__ __forceinline__ VitJob frame_vitjob(const FrameRow& r)
     return J;
 }
 
-// ---- pilot polarity (dev_pilot11a.h): one bit of the sequence's four words ...
-__device__ __forceinline__ unsigned pilot_sgn(unsigned count)
-{
-    const unsigned w = count < 32 ? kPilotW0 : count < 64 ? kPilotW1 : count < 96 ? kPilotW2 : kPilotW3;
-    return (w >> (count & 31u)) & 1u;
-}
-// ... and as the table a kernel indexes with a symbol count it holds in a register
+// ---- pilot polarity: one bit of the sequence's four words is pilot_sgn (dev_pilot11a.h); here as the table a kernel indexes with a symbol count it holds in a register
 static __device__ __constant__ PilotPolarity kPilotSgn = kPilotPolarity;
 __device__ __forceinline__ int pilot_angle(int th, unsigned count) { return kPilotSgn.neg[count] ? w16(th + 0x8000) : th; }   // a pilot of polarity -1: + pi
 

@@ -9,13 +9,15 @@
 //     patterns map a coded-bit index to (input bit, generator) in closed form
 //   * interleaver (interleave.hpp:43-58): coded bit k -> position j(k), the table the receiver's de-interleaver reads
 //   * FCS: the parallel CRC-32 of k_finish
+// The bricks' arithmetic is dev_tx.h's; here are the frame geometry, the LDS plan, the 16 -> 8 bit emission and the 44 MHz resampler.
 // One 256-thread block per frame; eight OFDM symbols per pass, 32 lanes each (IFFT<128>: 4 points per lane).
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include "dev_pilot11a.h"
+#include "dev_tx.h"
 
 namespace sora {
 
+constexpr int kTx11aMpdu = kCrcWaveBytes;                   // the MPDU bytes k_tx11a's one-wave FCS and its LDS plan hold
 __device__ __constant__ uint8_t kLtsPos[64] = {              // LTS_Positive_table (ieee80211const.h:23-28)
     0,1,0,0,1,1,0,1,0,1,0,0,0,0,0,1, 1,0,0,1,0,1,0,1,1,1,1,0,0,0,0,0,
     0,0,0,0,0,0,1,1,0,0,1,1,0,1,0,1, 1,1,1,1,1,0,0,1,1,0,1,0,1,1,1,1 };
@@ -26,11 +28,9 @@ __device__ __forceinline__ int sat8(int v) { return min(max(v, -128), 127); }   
 // 160 time samples of one OFDM symbol from its 64 frequency bins (TIFFTx, fft.hpp:21-59): bins 0..31 -> 0..31, 32..63 ->
 // 96..127 of a 128-point IFFT, >> 4, GI = last 32, first/last two samples halved, saturating 16 -> 8 bit pack.
 // s_bins: 128 words (zero outside the 64 bins); 32 lanes, e = lane of the group.
-// Round 6: the samples leave straight from where the IFFT's last stage put them -- time sample n at word brev7(n) (FFT128LUTMap), output sample i of the symbol is
-// n = (i + 96) & 127 -- four per lane as one 8-byte store, the shift, the clamp (_mm_packs_epi16, stdbrick.hpp:430) and the byte pick on packed halves.  (Round 5
-// un-reversed into a 160-word symbol buffer, copied the GI behind a barrier and stored two bytes per lane and pass.)
-// Output sample i of a symbol is time sample n = (i + 96) & 127, which the IFFT's last stage left at word brev7(n).  A lane's four samples in a row, i = 4 e + k, sit at
-// brev5((e + 24) & 31) + 32 brev2(k); its one sample of the last 32, i = 128 + e, at 4 brev5(e) + 3.
+// The samples leave straight from where the IFFT's last stage put them: output sample i of a symbol is time sample n = (i + 96) & 127, at word brev7(n)
+// (FFT128LUTMap) -- four per lane as one 8-byte store, the shift, the clamp (_mm_packs_epi16, stdbrick.hpp:430) and the byte pick on packed halves.  A lane's four
+// samples in a row, i = 4 e + k, sit at brev5((e + 24) & 31) + 32 brev2(k); its one sample of the last 32, i = 128 + e, at 4 brev5(e) + 3.
 struct EmitPlan { uint32_t a4, a1; uint32_t sh01, shs; };
 __device__ __forceinline__ EmitPlan emit_plan(int e)
 {
@@ -63,7 +63,7 @@ __device__ __forceinline__ uint32_t up44_mix(uint32_t lo, uint32_t hi, int r)   
 __device__ __forceinline__ uint32_t x40_at(const uint32_t* s_bins, int i)
 {
     const uint32_t sh = (i < 2 || i >= 158) ? 0x00050005u : 0x00040004u;
-    const s16x2_t v = __builtin_bit_cast(s16x2_t, s_bins[__brev((unsigned)((i + 96) & 127)) >> 25]) >> __builtin_bit_cast(s16x2_t, sh);
+    const s16x2_t v = __builtin_bit_cast(s16x2_t, s_bins[brev7((uint32_t)(i + 96) & 127u)]) >> __builtin_bit_cast(s16x2_t, sh);
     return i >= 160 ? 0u : __builtin_bit_cast(uint32_t, v);
 }
 // 44 MHz samples 4 w .. 4 w + 3 of the symbol (w = 0..43) as one 8-byte word: they lie between five 40 MHz samples in a row
@@ -81,14 +81,10 @@ __device__ __forceinline__ uint2 up44_word(const uint32_t* s_bins, int w)
     }
     return make_uint2(b[0] | (b[1] << 16), b[2] | (b[3] << 16));
 }
-template <bool UP44, typename SYNC>
-__device__ __forceinline__ void ifft_emit(uint32_t* s_bins, int e, const Fft128Tw& tw, const EmitPlan& P, int8_t* out8, SYNC sync)
+template <bool UP44>
+__device__ __forceinline__ void ifft_emit(uint32_t* s_bins, int e, const Fft128Tw& tw, const EmitPlan& P, int8_t* out8)
 {
-    pcx x[4];
-    sync();
-#pragma unroll
-    for (int m = 0; m < 4; m++) x[m] = s_bins[e + 32 * m];
-    ifft128_core_pk(x, s_bins, e, tw, sync);                                     // IFFT<128> on packed COMPLEX16 (bit-exact with fft128_core<true>)
+    tx_ifft128<false>(s_bins, e, tw);
     if (out8 == nullptr) return;                                                 // (a group past the last symbol only keeps the barriers company)
     if constexpr (UP44) {                                                        // 176 samples = 44 words of 8 bytes: one per lane, then 12 more
         if ((reinterpret_cast<uintptr_t>(out8) & 7u) == 0) {
@@ -111,7 +107,7 @@ __device__ __forceinline__ void ifft_emit(uint32_t* s_bins, int e, const Fft128T
         reinterpret_cast<uint16_t*>(out8)[128 + e] = (uint16_t)__builtin_amdgcn_perm(0u, w4, 0x0c0c0200u);
     } else {                                                                     // (a frame the caller placed at a sample offset that is not a multiple of four)
         for (int i = e; i < 160; i += 32) {
-            const uint32_t w = pk_sra_clamp8(s_bins[__brev((unsigned)((i + 96) & 127)) >> 25], (i < 2 || i >= 158) ? 0x00050005u : 0x00040004u);
+            const uint32_t w = pk_sra_clamp8(s_bins[brev7((uint32_t)(i + 96) & 127u)], (i < 2 || i >= 158) ? 0x00050005u : 0x00040004u);
             reinterpret_cast<uint16_t*>(out8)[i] = (uint16_t)__builtin_amdgcn_perm(0u, w, 0x0c0c0200u);
         }
     }
@@ -172,6 +168,9 @@ template <bool UP44>
 __global__ void __launch_bounds__(256, UP44 ? 4 : 8) k_tx11a(TxArgs A)
 {
     constexpr int kPre = UP44 ? 704 : 640, kSym = UP44 ? 176 : 160;
+    // The LDS plan holds the MPDU one wave's FCS covers (kTx11aMpdu): SERVICE(2) + MPDU + FCS(4) + tail(1), at most 27 pad bytes (one symbol at
+    // 54 Mbps), the 8 bytes the loader clears behind them; a generator word per four field bytes.
+    static_assert(2 + kTx11aMpdu + 4 + 1 + 27 + 8 <= 2608 && (2 + kTx11aMpdu + 4 + 1 + 27 + 3) / 4 <= 656, "LDS plan");
     __shared__ alignas(4) uint8_t s_data[2608];
     // generator outputs A (133) / B (171) of the whole data field, bit i of the stream = bit i & 31 of word i >> 5
     __shared__ uint32_t s_gab[2][656];
@@ -209,45 +208,20 @@ __global__ void __launch_bounds__(256, UP44 ? 4 : 8) k_tx11a(TxArgs A)
     // (+ 8: the word-wise encoder reads up to 3 bytes past nbytes)
     for (uint32_t i = tid; i < nbytes + 8; i += 256) s_data[i] = (i >= 2 && i < 2 + L) ? mp[i - 2] : (uint8_t)0;
     __syncthreads();
-    if (tid < 64) {                                                              // FCS of the MPDU (PHY_11a.hpp:87,160-170)
-        uint32_t crc;
-        if (L >= 4) crc = crc32_wave(s_data + 2, (int)L, s_crc, s_z, tid);
-        else { crc = 0xFFFFFFFFu; for (uint32_t i = 0; i < L; i++) crc = (crc >> 8) ^ s_crc[(s_data[2 + i] ^ crc) & 0xFF]; }
-        if (tid == 0) s_fcs = ~crc;
-    }
+    if (tid < 64) tx_fcs_waves<1>(s_data + 2, L, s_crc, s_z, tid, &s_fcs);      // FCS of the MPDU: one wave
     __syncthreads();
-    if (tid < 4) s_data[2 + L + tid] = (uint8_t)(s_fcs >> (8 * tid));
+    if (tid < 4) s_data[2 + L + tid] = (uint8_t)(tx_fcs_join<1>(s_z, &s_fcs) >> (8 * tid));
     __syncthreads();
-    {   // T11aSc (scramble.hpp:237-251): register = previous 8 output bits; the tail byte keeps only its two pad bits
-        const unsigned s7 = A.seed[f] >> 1;
-        const unsigned phase = T.scr_phase[s7];                                  // 255: the all-zero state stays zero
-        for (uint32_t i = tid; i < nbytes; i += 256) {
-            unsigned c = s_data[i] ^ (phase == 255 ? 0u : T.scr_seq[(phase + 8u * i) % 127u]);
-            if (i == dbytes - 1) c &= 0xC0u;
-            s_data[i] = (uint8_t)c;
-        }
-    }
+    tx_scramble(s_data, nbytes, dbytes - 1, T.scr_phase[A.seed[f] >> 1], T, tid);   // T11aSc: the register holds the previous 8 output bits
     for (int i = tid; i < kPre; i += 256) reinterpret_cast<uint16_t*>(out)[i] = reinterpret_cast<const uint16_t*>(A.preamble)[i];
     __syncthreads();
-    // TConvEncode_* (conv_enc.hpp:6-14) 32 input bits at a time: A = x ^ x>>2 ^ x>>3 ^ x>>5 ^ x>>6, B = x ^ x>>1 ^ x>>2 ^ x>>3 ^ x>>6 over the bit
-    // stream (x>>k = the bit k positions EARLIER: shifted in from the previous word; the encoder starts from state 0)
-    {
-        const uint32_t* dw = reinterpret_cast<const uint32_t*>(s_data);
-        for (uint32_t w = tid; w < (nbytes + 3) / 4; w += 256) {
-            const uint32_t X = dw[w], P = w ? dw[w - 1] : 0u;
-            auto sh = [&](int k) { return (X << k) | (P >> (32 - k)); };
-            const uint32_t x2 = sh(2), x3 = sh(3), x6 = sh(6);
-            s_ga[w] = X ^ x2 ^ x3 ^ sh(5) ^ x6;
-            s_gb[w] = X ^ sh(1) ^ x2 ^ x3 ^ x6;
-        }
-    }
+    // TConvEncode_* over the whole field
+    for (uint32_t w = tid; w < (nbytes + 3) / 4; w += 256) tx_encode_word(reinterpret_cast<const uint32_t*>(s_data), w, 0xFFFFFFFFu, s_ga[w], s_gb[w]);
     __syncthreads();
 
-    // PLCP SIGNAL (ieee80211a_cmn.h:8-26): RATE, LENGTH, even parity
-    uint32_t sig = (uint32_t)rc | ((L + 4) << 5);
-    sig |= (uint32_t)(__popc(sig) & 1) << 17;
+    const uint32_t sig = tx_lsig((uint32_t)rc, L + 4);                           // PLCP SIGNAL
     // From here on every LDS slice is private to a 32-lane group (half a wave): a wave-level barrier orders what the groups of a wave
-    // write and read, the waves of the block run free of each other (a block barrier per stage of every pass used to hold them together).
+    // write and read, the waves of the block run free of each other.
     for (int i = tid; i < 48 * nb; i += 256) s_map[i] = T.deint[(nb == 1 ? 0 : nb == 2 ? 1 : nb == 4 ? 2 : 3) * 288 + i];
     if (tid < 48) s_map[288 + tid] = T.deint[tid];
     const Fft128Tw tw = fft128_twiddles(T, e);
@@ -255,45 +229,34 @@ __global__ void __launch_bounds__(256, UP44 ? 4 : 8) k_tx11a(TxArgs A)
     for (int k = tid; k < 48 * nb; k += 256) s_inv[s_map[k]] = (uint16_t)k;
     if (tid < 48) s_inv[288 + s_map[288 + tid]] = (uint16_t)tid;
     __syncthreads();
-    // Round 6: the mapper reads its bits where the encoder left them.  A symbol is 96 components (carrier c, I or Q; 48 for BPSK), three per lane of the symbol's 32:
+    // The mapper reads its bits where the encoder left them.  A symbol is 96 components (carrier c, I or Q; 48 for BPSK), three per lane of the symbol's 32:
     // component q = e + 32 t.  Its M bits sit at interleaved positions c N_BPSC + h M + m, i.e. are coded bits k = inverse(position) of the symbol, and coded bit k of
     // a symbol is generator `which` at input bit (s - 1) N_DBPS + il -- (il, which) follow from k and the puncturing pattern and do NOT depend on the symbol (N_CBPS is a
-    // whole number of puncture periods): nine bits per entry, three entries per component, held in one register per component.  (Round 5 wrote every coded bit into a byte
-    // array at its interleaved position and read the bytes back: 9 + 9 LDS byte accesses and their address arithmetic per lane and symbol.)
+    // whole number of puncture periods, tx_punct_offset).
     const int M = nb == 1 ? 1 : nb / 2;
-    auto entry_of = [&](int k) -> uint32_t {                                    // coded bit k of a data symbol -> il | which << 8
-        int il, which;
-        if (cr == 0) { il = k >> 1; which = k & 1; }
-        else if (cr == 1) { const int q3 = k / 3, r = k - 3 * q3; il = 2 * q3 + (r == 2); which = r == 1; }
-        else { const int q4 = k >> 2, r = k & 3; il = 3 * q4 + (r == 2 ? 1 : r == 3 ? 2 : 0); which = r & 1; }
-        return (uint32_t)il | ((uint32_t)which << 8);
-    };
     // (registers, not a packed word: the loop below neither unpacks nor recomputes anything that depends on the lane alone)
     // bit offset within s_gab of each of the component's bits at symbol 0: input bit within the symbol + 656 * 32 for generator B (a whole number of words)
     uint32_t il[3][3], ES[2] = { 0, 0 };
     uint32_t cw[3];                                                              // byte address of the component's 16-bit half in the symbol's bins
-    // TMap11a* + T11aAddPilot (mapper11a.hpp, pilot.hpp:76-118): carriers in the order -26..-1, +1..+26 without pilots; TIFFTx: bins 32..63 go to 96..127
-    auto bin_of = [](int c) { int bin; if (c < 24) { bin = 38 + c; if (bin >= 43) bin++; if (bin >= 57) bin++; } else { bin = 1 + (c - 24); if (bin >= 7) bin++; if (bin >= 21) bin++; }
-                              return bin < 32 ? bin : bin + 64; };
+    // TMap11a* + T11aAddPilot (mapper11a.hpp, pilot.hpp:76-118): carriers in the order -26..-1, +1..+26 without pilots (carrier_bin48)
 #pragma unroll
     for (int t = 0; t < 3; t++) {
         const int q = e + 32 * t;
 #pragma unroll
         for (int m = 0; m < 3; m++) il[t][m] = 0;
         if (nb == 1) {
-            if (t < 2 && q < 48) { const uint32_t en = entry_of(s_inv[q]); il[t][0] = (en & 255u) + (en >> 8) * (656u * 32u); }
-            cw[t] = (uint32_t)bin_of(t < 2 && q < 48 ? q : 0) * 4u;
+            if (t < 2 && q < 48) il[t][0] = tx_punct_offset(cr, s_inv[q], 656u * 32u);
+            cw[t] = (uint32_t)bin128(carrier_bin48(t < 2 && q < 48 ? q : 0)) * 4u;
         } else {
             const int c = q >> 1, h = q & 1;
 #pragma unroll
-            for (int m = 0; m < 3; m++) if (m < M) { const uint32_t en = entry_of(s_inv[c * nb + h * M + m]); il[t][m] = (en & 255u) + (en >> 8) * (656u * 32u); }
-            cw[t] = (uint32_t)bin_of(c) * 4u + 2u * (uint32_t)h;
+            for (int m = 0; m < 3; m++) if (m < M) il[t][m] = tx_punct_offset(cr, s_inv[c * nb + h * M + m], 656u * 32u);
+            cw[t] = (uint32_t)bin128(carrier_bin48(c)) * 4u + 2u * (uint32_t)h;
         }
         if (t < 2 && q < 48) { const int k = s_inv[288 + q]; ES[t] = (uint32_t)(k >> 1) | ((uint32_t)(k & 1) << 8); }
     }
     const EmitPlan plan = emit_plan(e);
     const int kmod = kmod_of(nb), lvl0 = -((1 << M) - 1) * kmod, kmod2 = 2 * kmod;
-    auto sync = []() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
     const uint32_t total = 1 + nsym;                                             // SIGNAL + data symbols
     const uint32_t* const gab = &s_gab[0][0];
     char* const bins = reinterpret_cast<char*>(s_bins[g]);
@@ -303,43 +266,32 @@ __global__ void __launch_bounds__(256, UP44 ? 4 : 8) k_tx11a(TxArgs A)
         const bool is_sig = s == 0;
         for (int i = e; i < 128; i += 32) s_bins[g][i] = 0;
         if (active) {
-            auto gen_bit = [&](uint32_t idx) -> uint32_t { return (gab[idx >> 5] >> (idx & 31u)) & 1u; };      // (idx >= 656 * 32: generator B's stream)
             if (is_sig) {
                 // the SIGNAL symbol: rate 1/2 over the 24 header bits (encoder state 0), BPSK
                 const uint32_t A_ = sig ^ (sig << 2) ^ (sig << 3) ^ (sig << 5) ^ (sig << 6), B_ = sig ^ (sig << 1) ^ (sig << 2) ^ (sig << 3) ^ (sig << 6);
 #pragma unroll
                 for (int t = 0; t < 2; t++) {
                     const int c = e + 32 * t;
-                    if (c < 48) { const unsigned bit = (((ES[t] >> 8) ? B_ : A_) >> (ES[t] & 255u)) & 1u; s_bins[g][bin_of(c)] = pack(mk(bit ? kBpskMod : -kBpskMod, 0)); }
+                    if (c < 48) { const unsigned bit = (((ES[t] >> 8) ? B_ : A_) >> (ES[t] & 255u)) & 1u; s_bins[g][bin128(carrier_bin48(c))] = pack(mk(bit ? kBpskMod : -kBpskMod, 0)); }
                 }
             } else {
                 const uint32_t ibase = (s - 1u) * (uint32_t)nd;
                 if (nb == 1) {
 #pragma unroll
                     for (int t = 0; t < 2; t++)
-                        if (e + 32 * t < 48) *reinterpret_cast<uint32_t*>(bins + cw[t]) = pack(mk(gen_bit(ibase + il[t][0]) ? kBpskMod : -kBpskMod, 0));
+                        if (e + 32 * t < 48) *reinterpret_cast<uint32_t*>(bins + cw[t]) = pack(mk(tx_gen_bit(gab, ibase + il[t][0]) ? kBpskMod : -kBpskMod, 0));
                 } else {
 #pragma unroll
-                    for (int t = 0; t < 3; t++) {
-                        unsigned v = 0;                                         // the component's bits, first-transmitted = MSB (InitQamMapLut's reversal, mapper11a.hpp:16-43)
-#pragma unroll
-                        for (int m = 0; m < 3; m++) if (m < M) v |= gen_bit(ibase + il[t][m]) << (M - 1 - m);
-                        unsigned bb = v ^ (v >> 1); bb ^= bb >> 2;                // Gray -> binary (M <= 3)
-                        *reinterpret_cast<uint16_t*>(bins + cw[t]) = (uint16_t)((int)bb * kmod2 + lvl0);
-                    }
+                    for (int t = 0; t < 3; t++) *reinterpret_cast<uint16_t*>(bins + cw[t]) = (uint16_t)tx_axis_level(gab, ibase, il[t], M, kmod2, lvl0);
                 }
             }
             if (e < 4) {
-                // pilot.hpp:10-28 as four words, bit n = 1 <=> polarity -1 at index n; m_PilotIndex 127 -> 0 after SIGNAL (pilot.hpp:66-69)
-                const unsigned pidx = is_sig ? 127u : (unsigned)((s - 1) % 127u);
-                const uint32_t pw = pidx < 64 ? (pidx < 32 ? kPilotW0 : kPilotW1) : (pidx < 96 ? kPilotW2 : kPilotW3);
-                const int p = (pw >> (pidx & 31u)) & 1u ? -kBpskMod : kBpskMod;
-                const int bin = e == 0 ? 7 : e == 1 ? 21 : e == 2 ? 64 - 7 : 64 - 21;
-                s_bins[g][bin < 32 ? bin : bin + 64] = pack(mk(e == 1 ? -p : p, 0));
+                const unsigned pidx = is_sig ? 127u : (unsigned)((s - 1) % 127u);   // m_PilotIndex 127 -> 0 after SIGNAL (pilot.hpp:66-69)
+                tx_put_pilots11a(s_bins[g], e, pilot_sgn(pidx) ? -kBpskMod : kBpskMod);
             }
         }
-        ifft_emit<UP44>(s_bins[g], e, tw, plan, active ? out + 2 * (kPre + kSym * (size_t)s) : (int8_t*)nullptr, sync);
-        sync();
+        ifft_emit<UP44>(s_bins[g], e, tw, plan, active ? out + 2 * (kPre + kSym * (size_t)s) : (int8_t*)nullptr);
+        wave_lds_sync();
     }
 }
 template __global__ void k_tx11a<false>(TxArgs A);

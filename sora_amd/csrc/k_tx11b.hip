@@ -16,6 +16,7 @@
 // tile: the symbol words of a tile into LDS, then one 16-byte store (two chip steps, eight samples) per lane and pass.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "dev_tx.h"
 
 namespace sora {
 
@@ -84,14 +85,6 @@ __device__ __forceinline__ uint2 shape4(uint32_t w, uint32_t valid)
         h[k] = ((uint32_t)min(max(re[k], -128), 127) & 0xFFu) | (((uint32_t)min(max(im[k], -128), 127) & 0xFFu) << 8);
     return make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
 }
-// register after m = 40 * 2^k zero bytes (crc32_wave's tree tables)
-__device__ __forceinline__ uint32_t crc_zeros(const uint32_t* s_z, int k, uint32_t c)
-{
-    uint32_t z = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) z ^= s_z[(k * 8 + q) * 16 + ((c >> (4 * q)) & 15u)];
-    return z;
-}
 }  // namespace
 
 __global__ void __launch_bounds__(kThreads) k_tx11b(Tx11bArgs A)
@@ -147,20 +140,10 @@ __global__ void __launch_bounds__(kThreads) k_tx11b(Tx11bArgs A)
     }
     __syncthreads();
     if (need_fcs) {                                                              // FCS = CalcCRC32 of the MPDU, little-endian
-        if (tid < 128) {
-            if (L >= 4) {
-                // two waves of crc32_wave: lanes 64..127 take the 2560 bytes before the last 2560; CRC(0, M1 | M2) = Z_2560(CRC(0, M1)) ^ CRC(0, M2)
-                const uint32_t c = crc32_wave(s_byte + 24, (int)L, s_crc, s_z, tid);
-                if ((tid & 63) == 0) s_crcw[tid >> 6] = c;
-            } else if (tid == 0) {
-                uint32_t c = 0xFFFFFFFFu;
-                for (uint32_t i = 0; i < L; i++) c = (c >> 8) ^ s_crc[(s_byte[24 + i] ^ c) & 0xFF];
-                s_crcw[0] = c; s_crcw[1] = 0;
-            }
-        }
+        if (tid < 128) tx_fcs_waves<2>(s_byte + 24, L, s_crc, s_z, tid, s_crcw);   // two waves (dev_tx.h)
         __syncthreads();
         if (tid == 0) {
-            const uint32_t fcs = ~(crc_zeros(s_z, 5, crc_zeros(s_z, 5, s_crcw[1])) ^ s_crcw[0]);
+            const uint32_t fcs = tx_fcs_join<2>(s_z, s_crcw);                    // a run that ends inside the FCS stores only its bytes
             for (uint32_t k = 0; k < 4 && 24 + L + k < B1; k++) s_byte[24 + L + k] = (uint8_t)(fcs >> (8 * k));
         }
         __syncthreads();

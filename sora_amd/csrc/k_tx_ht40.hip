@@ -10,13 +10,14 @@
 //     times j, k + 32), identical on both chains, no cyclic shifts; HT-LTFs with P = [[1, -1], [1, 1]]; each spatial stream has its
 //     own scrambler seed, K = 7 encoder, puncturing and HT interleaver (N_COL 18, N_ROW 6 N_BPSC, N_ROT 29) and goes out on its own chain.
 // Frame: L-STF 320, L-LTF 320, L-SIG 160, HT-SIG 2 x 160, HT-STF 160, HT-LTF 2 x 160, data nsym x 160 samples per chain.
-// One 256-thread block per frame, shaped like k_tx11n: both streams' scrambled fields and generator words in LDS; eight 32-lane groups,
-// group g carries stream g & 1 of data symbol 4 p + g / 2 in pass p.  Scrambler, encoder, puncturing and FCS are k_tx.hip's closed forms.
+// One 256-thread block per frame: both streams' scrambled fields and generator words in LDS; eight 32-lane groups, group g carries
+// stream g & 1 of data symbol 4 p + g / 2 in pass p.  FCS, scrambler, encoder, puncturing, mapper, SIG stream, IFFT and emission are dev_tx.h's pieces.
 // LDS layout: the symbol buffers are swizzled (fft128_swz, dev_arith.h) so that no stage of the IFFT, the 16-byte terminal stage and the
 // emission included, meets a bank conflict; a stream's B generator words lie 16 banks from its A words (kGen = 16 mod 32), so the at most
 // 17 + 17 consecutive words a symbol's bit gather reads overlap in at most one bank.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "dev_tx.h"
 #include "dev_ht40.h"
 
 namespace sora {
@@ -29,61 +30,18 @@ constexpr int kStf = 17053;                 // rint(A sqrt(13 / 12))
 constexpr int kPilot = 12288;               // 2 d(1)
 static_assert(kGen % 32 == 16 && kGen * 32 >= 32507 && kBytes >= 4 * 1016 + 4, "LDS plan");
 __device__ __forceinline__ int level40(int nb) { return nb <= 2 ? 6144 : nb == 4 ? 4000 : 2214; }   // rint(A LEVEL / 128), LEVEL = 48, 48, 31.25, 17.3
-__device__ __forceinline__ uint32_t brev7(uint32_t n) { return __brev(n) >> 25; }
 __device__ __forceinline__ uint32_t pk16(int re, int im) { return (uint32_t)(uint16_t)re | ((uint32_t)(uint16_t)im << 16); }
 static __constant__ int8_t kLLtf[53] = {    // L-LTF, carriers -26..26
     1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 0,
     1, -1, -1, 1, 1, -1, 1, -1, 1, -1, -1, -1, -1, -1, 1, 1, -1, -1, 1, -1, 1, -1, 1, 1, 1, 1 };
 static __constant__ int8_t kLStf[13] = { 1, -1, 1, -1, -1, 1, 0, -1, -1, 1, 1, 1, 1 };   // x (1 + j), carriers -24, -20, .., 24
 // data carrier c (0..47) of a legacy symbol: -26..26 without 0, +-7, +-21
-__device__ __forceinline__ int leg_carrier(int c)
-{
-    int k;
-    if (c < 24) { k = -26 + c; if (k >= -21) k++; if (k >= -7) k++; } else { k = 1 + (c - 24); if (k >= 7) k++; if (k >= 21) k++; }
-    return k;
-}
+__device__ __forceinline__ int leg_carrier(int c) { const int b = carrier_bin48(c); return b < 32 ? b : b - 64; }
 // legacy carrier k with value (re, im) on both halves of the channel: bin k - 32 as it is, bin k + 32 times j
 __device__ __forceinline__ void put_dup40(uint32_t* bins, int k, int re, int im)
 {
     bins[fft128_swz((k - 32) & 127)] = pk16(re, im);
     bins[fft128_swz((k + 32) & 127)] = pk16(-im, re);
-}
-// time sample n of a transformed symbol buffer
-__device__ __forceinline__ uint32_t tsample(const uint32_t* s, uint32_t n) { return s[fft128_swz((int)brev7(n & 127u))]; }
-// 160 samples of one chain from the IFFT's output: output sample i is time sample (i + 96) & 127.  Lane e stores samples 4e..4e+3 and, for
-// e < 8, 128+4e..+3 as 16-byte words where the stream allows; word by word otherwise.
-__device__ __forceinline__ void emit160(const uint32_t* s, int e, uint32_t* o)
-{
-    if ((reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
-        const uint32_t n0 = (uint32_t)(4 * e + 96);
-        uint4 v;
-        v.x = tsample(s, n0); v.y = tsample(s, n0 + 1); v.z = tsample(s, n0 + 2); v.w = tsample(s, n0 + 3);
-        reinterpret_cast<uint4*>(o)[e] = v;
-        if (e < 8) reinterpret_cast<uint4*>(o)[32 + e] = v;                      // samples 128 + 4e ..: time samples 4e + 96 .. once more
-    } else {                                                                     // (a frame placed at a sample offset that is not a multiple of four)
-        for (int i = e; i < 160; i += 32) o[i] = tsample(s, (uint32_t)(i + 96));
-    }
-}
-template <typename SYNC>
-__device__ __forceinline__ void ifft_swz(uint32_t* s, int e, const Fft128Tw& tw, SYNC sync)
-{
-    pcx x[4];
-    sync();
-#pragma unroll
-    for (int m = 0; m < 4; m++) x[m] = s[fft128_swz(e + 32 * m)];
-    ifft128_core_pk<true>(x, s, e, tw, sync);                                    // IFFT<128> on packed COMPLEX16, swizzled buffer
-}
-// the register after m = 40 * 2^k zero bytes (crc32_wave's tree tables)
-__device__ __forceinline__ uint32_t crc_zeros(const uint32_t* s_z, int k, uint32_t c)
-{
-    uint32_t z = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) z ^= s_z[(k * 8 + q) * 16 + ((c >> (4 * q)) & 15u)];
-    return z;
-}
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 }  // namespace
 
@@ -103,17 +61,17 @@ __global__ void __launch_bounds__(128) k_tx_ht40_preamble(uint32_t* tab, Tables 
     } else {
         for (int i = e; i < 117; i += 32) bins[fft128_swz((i - 58) & 127)] = pk16((g == 2 ? kAmp : -kAmp) * kHtLtf40[i], 0);
     }
-    ifft_swz(bins, e, fft128_twiddles(T, e), wave_sync);
+    tx_ifft128<true>(bins, e, fft128_twiddles(T, e));
     uint32_t* const t0 = tab, * const t1 = tab + kTxHt40Preamble;
     if (g == 0) {
-        for (int i = e; i < 320; i += 32) t0[i] = t1[i] = tsample(bins, (uint32_t)i);                        // the symbol tiled
-        for (int i = e; i < 160; i += 32) t0[640 + i] = t1[640 + i] = tsample(bins, (uint32_t)i);
+        for (int i = e; i < 320; i += 32) t0[i] = t1[i] = tx_tsample<true>(bins, (uint32_t)i);                        // the symbol tiled
+        for (int i = e; i < 160; i += 32) t0[640 + i] = t1[640 + i] = tx_tsample<true>(bins, (uint32_t)i);
     } else if (g == 1) {
-        for (int i = e; i < 320; i += 32) t0[320 + i] = t1[320 + i] = tsample(bins, (uint32_t)(i + 64));     // GI2 of 64, two symbols
+        for (int i = e; i < 320; i += 32) t0[320 + i] = t1[320 + i] = tx_tsample<true>(bins, (uint32_t)(i + 64));     // GI2 of 64, two symbols
     } else if (g == 2) {
-        for (int i = e; i < 160; i += 32) t0[800 + i] = t1[800 + i] = t1[960 + i] = tsample(bins, (uint32_t)(i + 96));
+        for (int i = e; i < 160; i += 32) t0[800 + i] = t1[800 + i] = t1[960 + i] = tx_tsample<true>(bins, (uint32_t)(i + 96));
     } else {
-        for (int i = e; i < 160; i += 32) t0[960 + i] = tsample(bins, (uint32_t)(i + 96));                  // P = [[1, -1], [1, 1]]
+        for (int i = e; i < 160; i += 32) t0[960 + i] = tx_tsample<true>(bins, (uint32_t)(i + 96));                  // P = [[1, -1], [1, 1]]
     }
 }
 
@@ -148,60 +106,28 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
         for (uint32_t i = tid; i < 4 * nw + 4; i += 256) s_data[st][i] = (i >= 2 && i < 2 + L) ? mp[i - 2] : (uint8_t)0;
     }
     __syncthreads();
-    {   // FCS of both MPDUs: stream tid >> 7, two waves of crc32_wave each (lanes 64..127 take the 2560 bytes before the last 2560)
-        const int st = tid >> 7, l = tid & 127;
-        if (L >= 4) {
-            const uint32_t c = crc32_wave(s_data[st] + 2, (int)L, s_crc, s_z, l);
-            if ((l & 63) == 0) s_crcw[2 * st + (l >> 6)] = c;
-        } else if (l == 0) {
-            uint32_t c = 0xFFFFFFFFu;
-            for (uint32_t i = 0; i < L; i++) c = (c >> 8) ^ s_crc[(s_data[st][2 + i] ^ c) & 0xFF];
-            s_crcw[2 * st] = c; s_crcw[2 * st + 1] = 0;
-        }
-    }
+    // FCS of both MPDUs: stream tid >> 7, two waves each
+    tx_fcs_waves<2>(s_data[tid >> 7] + 2, L, s_crc, s_z, tid & 127, s_crcw + 2 * (tid >> 7));
     __syncthreads();
-    if (tid < 2) {                                                               // CRC(0, M1 | M2) = Z_2560(CRC(0, M1)) ^ CRC(0, M2)
-        const uint32_t fcs = ~(crc_zeros(s_z, 5, crc_zeros(s_z, 5, s_crcw[2 * tid + 1])) ^ s_crcw[2 * tid]);
+    if (tid < 2) {
+        const uint32_t fcs = tx_fcs_join<2>(s_z, s_crcw + 2 * tid);
         for (int k = 0; k < 4; k++) s_data[tid][2 + L + k] = (uint8_t)(fcs >> (8 * k));
     }
     __syncthreads();
-    {   // scrambler: x[n] = x[n-4] ^ x[n-7], seed bit i = x[-1-i] (py_ht40.scramble_seq); the phase tables keep the register the other way
-        // round.  Everything up to the last symbol's last bit is scrambled, pad included; the six tail bits are forced to zero afterwards.
-        const uint32_t nbytes = (nsym * (uint32_t)nd + 7) / 8, tail = 2 + L + 4;
+    // scrambler: x[n] = x[n-4] ^ x[n-7], seed bit i = x[-1-i] (py_ht40.scramble_seq); the phase tables keep the register the other way
+    // round.  Everything up to the last symbol's last bit is scrambled, pad included; the six tail bits are forced to zero afterwards.
 #pragma unroll
-        for (int st = 0; st < 2; st++) {
-            const unsigned seed = A.seed ? A.seed[2 * f + st] : (st ? 0x2Bu : 0x5Du);
-            const unsigned phase = T.scr_phase[brev7(seed & 0x7Fu)];             // 255: the all-zero state stays zero
-            for (uint32_t i = tid; i < nbytes; i += 256) {
-                unsigned c = s_data[st][i] ^ (phase == 255 ? 0u : T.scr_seq[(phase + 8u * i) % 127u]);
-                if (i == tail) c &= 0xC0u;
-                s_data[st][i] = (uint8_t)c;
-            }
-        }
+    for (int st = 0; st < 2; st++) {
+        const unsigned seed = A.seed ? A.seed[2 * f + st] : (st ? 0x2Bu : 0x5Du);
+        tx_scramble(s_data[st], (nsym * (uint32_t)nd + 7) / 8, 2 + L + 4, T.scr_phase[brev7(seed & 0x7Fu)], T, tid);
     }
-    // the fixed fields from the per-device table: samples 0..639 and 1120..1599 of both chains
-#pragma unroll
-    for (int ch = 0; ch < 2; ch++) {
-        const uint32_t* src = A.preamble + ch * kTxHt40Preamble;
-        uint32_t* o = ch ? out1 : out0;
-        if ((reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
-            for (int i = tid; i < (int)kTxHt40Preamble / 4; i += 256)
-                reinterpret_cast<uint4*>(o + (i < 160 ? 0 : 480))[i] = reinterpret_cast<const uint4*>(src)[i];
-        } else {
-            for (int i = tid; i < (int)kTxHt40Preamble; i += 256) o[i < 640 ? i : i + 480] = src[i];
-        }
-    }
+    tx_copy_fixed_fields(A.preamble, out0, out1, tid);
     __syncthreads();
-    // the encoder 32 input bits at a time (k_tx.hip): A = x ^ x>>2 ^ x>>3 ^ x>>5 ^ x>>6, B = x ^ x>>1 ^ x>>2 ^ x>>3 ^ x>>6 (x>>k: k bits earlier)
+    // the K = 7 encoder, each stream's field on its own
     for (uint32_t i = tid; i < 2 * nw; i += 256) {
         const int st = i >= nw;
         const uint32_t w = st ? i - nw : i;
-        const uint32_t* dw = reinterpret_cast<const uint32_t*>(s_data[st]);
-        const uint32_t X = dw[w], Pw = w ? dw[w - 1] : 0u;
-        auto sh = [&](int k) { return (X << k) | (Pw >> (32 - k)); };
-        const uint32_t x2 = sh(2), x3 = sh(3), x6 = sh(6);
-        s_gab[st][0][w] = X ^ x2 ^ x3 ^ sh(5) ^ x6;
-        s_gab[st][1][w] = X ^ sh(1) ^ x2 ^ x3 ^ x6;
+        tx_encode_word(reinterpret_cast<const uint32_t*>(s_data[st]), w, 0xFFFFFFFFu, s_gab[st][0][w], s_gab[st][1][w]);
     }
     for (int k = tid; k < 108 * nb; k += 256) {
         s_inv[0][deint40_index(nb, 0, k)] = (uint16_t)k;
@@ -214,16 +140,8 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
     // L-SIG + HT-SIG: 24 + 48 bits at rate 1/2 from state 0 (L-SIG's six tail bits return the encoder to it), three BPSK symbols of 48 coded
     // bits through the legacy interleaver (coded bit k at position 3 (k mod 16) + k div 16), L-SIG on I, HT-SIG on Q, pilots 1, 1, 1, -1
     if (g < 4) {                                                                 // waves 0 and 1: groups 0..2 carry the three symbols
-        uint32_t lsig = 0xBu | ((12u + 3u * nsym) << 5);                         // 6 Mbps; LENGTH: the legacy duration that spans the HT frame
-        lsig |= (uint32_t)(__popc(lsig) & 1) << 17;
-        const uint32_t h4 = (mcs & 0x7Fu) | (1u << 7) | (((L + 4) & 0xFFFFu) << 8) | (7u << 24);   // MCS, CBW 40, LENGTH, smoothing, not sounding, reserved
-        uint32_t crc = 0xFF;                                                     // CRC-8 over bits 0..33: reflected, poly 0xE0, complemented
-        for (int b = 0; b < 34; b++) { crc ^= b < 32 ? (h4 >> b) & 1u : 0u; crc = (crc & 1u) ? (crc >> 1) ^ 0xE0u : crc >> 1; }
-        crc = ~crc & 0xFFu;
-        const uint64_t ht = (uint64_t)h4 | ((uint64_t)crc << 34);                   // CRC bits 34..41, tail 0
-        const uint64_t lo = (uint64_t)lsig | (ht << 24);                         // bits 0..63 of the 72-bit stream
-        const uint32_t hi = (uint32_t)(ht >> 40);                                // bits 64..71
-        auto bit = [&](int i) -> uint32_t { return i < 0 ? 0u : i < 64 ? (uint32_t)(lo >> i) & 1u : (hi >> (i - 64)) & 1u; };
+        // L-SIG LENGTH: the legacy duration that spans the HT frame; HT-SIG: MCS, CBW 40, LENGTH, smoothing, not sounding, reserved
+        const TxSig72 sig = tx_sig72(12u + 3u * nsym, (mcs & 0x7Fu) | (1u << 7) | (((L + 4) & 0xFFFFu) << 8) | (7u << 24));
         const int s = g;
         for (int i = e; i < 128; i += 32) bins[i] = 0;
         if (s < 3) {
@@ -231,17 +149,15 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
             for (int t = 0; t < 2; t++) {
                 const int c = e + 32 * t;
                 if (c < 48) {
-                    const int kg = 48 * s + 16 * (c % 3) + c / 3, i = kg >> 1;
-                    const uint32_t v = (kg & 1) ? bit(i) ^ bit(i - 1) ^ bit(i - 2) ^ bit(i - 3) ^ bit(i - 6) : bit(i) ^ bit(i - 2) ^ bit(i - 3) ^ bit(i - 5) ^ bit(i - 6);
-                    const int a = v ? kAmp : -kAmp;
+                    const int a = tx_sig_coded_bit(sig, 48 * s + 16 * (c % 3) + c / 3) ? kAmp : -kAmp;
                     put_dup40(bins, leg_carrier(c), s == 0 ? a : 0, s == 0 ? 0 : a);
                 }
             }
-            if (e < 4) put_dup40(bins, e == 0 ? -21 : e == 1 ? -7 : e == 2 ? 7 : 21, e == 3 ? -kAmp : kAmp, 0);
+            if (e < 4) put_dup40(bins, pilot_carrier(e), e == 3 ? -kAmp : kAmp, 0);
         }
-        ifft_swz(bins, e, tw, wave_sync);
-        if (s < 3) { emit160(bins, e, out0 + 640 + 160 * s); emit160(bins, e, out1 + 640 + 160 * s); }
-        wave_sync();
+        tx_ifft128<true>(bins, e, tw);
+        if (s < 3) { tx_emit160<true>(bins, e, out0 + 640 + 160 * s, 0); tx_emit160<true>(bins, e, out1 + 640 + 160 * s, 0); }   // no cyclic shifts
+        wave_lds_sync();
     }
 
     // data symbols.  Per lane, for its stream: up to four carriers c = e + 32 t, each of M bits per axis at interleaved positions
@@ -259,14 +175,8 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
 #pragma unroll
             for (int m = 0; m < 3; m++) {
                 boff[t][3 * h + m] = 0;
-                if (c < 108 && h < nax && m < M) {
-                    const int kc = s_inv[iss][c * nb + h * M + m];
-                    int il, which;
-                    if (P.cr == 0) { il = kc >> 1; which = kc & 1; }
-                    else if (P.cr == 1) { const int q3 = kc / 3, r = kc - 3 * q3; il = 2 * q3 + (r == 2); which = r == 1; }
-                    else { const int q4 = kc >> 2, r = kc & 3; il = 3 * q4 + (r == 2 ? 1 : r == 3 ? 2 : 0); which = r & 1; }
-                    boff[t][3 * h + m] = (uint32_t)il + (uint32_t)which * (kGen * 32u);
-                }
+                if (c < 108 && h < nax && m < M)
+                    boff[t][3 * h + m] = tx_punct_offset(P.cr, s_inv[iss][c * nb + h * M + m], kGen * 32u);
             }
     }
     const int d = level40(nb), lvl0 = -((1 << M) - 1) * d, d2 = 2 * d;
@@ -274,7 +184,6 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
     uint32_t* const out = iss ? out1 : out0;
     for (uint32_t s = (uint32_t)(g >> 1); s < nsym; s += 4) {                    // (a wave's two groups share their symbol: the trip count is the wave's)
         const uint32_t ibase = s * (uint32_t)nd;
-        auto gen_bit = [&](uint32_t idx) -> uint32_t { return (gab[idx >> 5] >> (idx & 31u)) & 1u; };
         // the 14 bins that carry nothing: 127, 0, 1 and 59..69 (the buffer holds the symbol before's samples)
         if (e < 14) bins[fft128_swz(e < 3 ? (e + 127) & 127 : 56 + e)] = 0;
         if (e < 6) bins[fft128_swz((e == 0 ? -53 : e == 1 ? -25 : e == 2 ? -11 : e == 3 ? 11 : e == 4 ? 25 : 53) & 127)] = pk16(kPilot, 0);
@@ -282,23 +191,17 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
         for (int t = 0; t < 4; t++) {
             if (e + 32 * t < 108) {
                 int ax[2] = { 0, 0 };
-                if (nb == 1) ax[0] = gen_bit(ibase + boff[t][0]) ? d : -d;
+                if (nb == 1) ax[0] = tx_gen_bit(gab, ibase + boff[t][0]) ? d : -d;
                 else {
 #pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        unsigned v = 0;                                         // first-transmitted bit = MSB of the axis's Gray code
-#pragma unroll
-                        for (int m = 0; m < 3; m++) if (m < M) v |= gen_bit(ibase + boff[t][3 * h + m]) << (M - 1 - m);
-                        unsigned bb = v ^ (v >> 1); bb ^= bb >> 2;                // Gray -> binary (M <= 3)
-                        ax[h] = (int)bb * d2 + lvl0;
-                    }
+                    for (int h = 0; h < 2; h++) ax[h] = tx_axis_level(gab, ibase, boff[t] + 3 * h, M, d2, lvl0);
                 }
                 bins[cw[t]] = pk16(ax[0], ax[1]);
             }
         }
-        ifft_swz(bins, e, tw, wave_sync);
-        emit160(bins, e, out + 1600 + 160 * (size_t)s);
-        wave_sync();
+        tx_ifft128<true>(bins, e, tw);
+        tx_emit160<true>(bins, e, out + 1600 + 160 * (size_t)s, 0);
+        wave_lds_sync();
     }
 }
 

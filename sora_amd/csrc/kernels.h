@@ -148,6 +148,20 @@ struct Tx11nArgs {             // sora_hip_tx11n
     const uint32_t* preamble;  // [2][1120]: per chain L-STF, L-LTF (640) then HT-STF, HT-LTF1, HT-LTF2 (480)
     Tables          T;
 };
+// MCS 8..14 of both HT transmitters (DOT11N_RATE_PARAMS, BB11nGetCodingRateFromMcsIndex): N_BPSC, the code rate R (cr: 0 = 1/2, 1 = 2/3, 2 = 3/4) and
+// dbpc2 = 2 N_BPSC R -- twice the data bits one carrier of one stream holds (1/2, 1, 3/2, 2, 3, 4, 9/2 for MCS 8..14), so that a plan's N_DBPS is one
+// multiplication: (data carriers per symbol, all streams) / 2 x dbpc2.  The plans run on the device too: no division by a run-time rate.
+__host__ __device__ inline bool tx_ht_mcs(uint32_t mcs, int& nb, int& cr, int& dbpc2)
+{
+    switch (mcs) {
+    case 8:  nb = 1; cr = 0; dbpc2 = 1; break;  case 9:  nb = 2; cr = 0; dbpc2 = 2; break;
+    case 10: nb = 2; cr = 2; dbpc2 = 3; break;  case 11: nb = 4; cr = 0; dbpc2 = 4; break;
+    case 12: nb = 4; cr = 2; dbpc2 = 6; break;  case 13: nb = 6; cr = 1; dbpc2 = 8; break;
+    case 14: nb = 6; cr = 2; dbpc2 = 9; break;
+    default: return false;
+    }
+    return true;
+}
 // The frame geometry the reference's data graph produces (PHY_11n.hpp:15-150, ieee80211n_cmn.h:34-55, pinqueue.h:133-147).
 // TBB11nSrc emits nbytes = ceil(nstd * NDBPS / 8) bytes (nstd: the standard's symbol count); on Flush every pipe pads its
 // last burst with zeros -- the encoder's input to a whole group (1, 2 or 3 bytes for rate 1/2, 2/3, 3/4), the stream parser's
@@ -157,13 +171,9 @@ struct Tx11nPlan { int nb, cr, ndbps; uint32_t nstd, nbytes, nvalid, nsym; };
 __host__ __device__ inline bool tx11n_plan(uint32_t len, uint32_t mcs, Tx11nPlan& P)
 {
     if (len < 1 || len > 4092) return false;
-    switch (mcs) {                                       // DOT11N_RATE_PARAMS, BB11nGetCodingRateFromMcsIndex; cr: 0 = 1/2, 1 = 2/3, 2 = 3/4
-    case 8:  P.nb = 1; P.cr = 0; P.ndbps = 52;  break;  case 9:  P.nb = 2; P.cr = 0; P.ndbps = 104; break;
-    case 10: P.nb = 2; P.cr = 2; P.ndbps = 156; break;  case 11: P.nb = 4; P.cr = 0; P.ndbps = 208; break;
-    case 12: P.nb = 4; P.cr = 2; P.ndbps = 312; break;  case 13: P.nb = 6; P.cr = 1; P.ndbps = 416; break;
-    case 14: P.nb = 6; P.cr = 2; P.ndbps = 468; break;
-    default: return false;                               // MCS 15 goes to TDropAny: no frame
-    }
+    int dbpc2;
+    if (!tx_ht_mcs(mcs, P.nb, P.cr, dbpc2)) return false;   // MCS 15 goes to TDropAny: no frame
+    P.ndbps = 52 * dbpc2;                                // two streams of 52 data carriers
     const uint32_t nd = (uint32_t)P.ndbps, gin = (uint32_t)P.cr + 1, gout = (uint32_t)P.cr + 2;
     P.nstd = ((len + 4) * 8 + 16 + 6 + nd - 1) / nd;     // SERVICE 16 bits, tail 6 bits
     P.nbytes = (P.nstd * nd + 7) / 8;
@@ -193,13 +203,9 @@ struct TxHt40Plan { int nb, cr, ndbps; uint32_t nsym; };
 __host__ __device__ inline bool tx_ht40_plan(uint32_t len, uint32_t mcs, TxHt40Plan& P)
 {
     if (len < 1 || len > 3996) return false;             // HT LENGTH <= 4000, the receiver's limit
-    switch (mcs) {                                       // cr: 0 = 1/2, 1 = 2/3, 2 = 3/4
-    case 8:  P.nb = 1; P.cr = 0; P.ndbps = 54;  break;  case 9:  P.nb = 2; P.cr = 0; P.ndbps = 108; break;
-    case 10: P.nb = 2; P.cr = 2; P.ndbps = 162; break;  case 11: P.nb = 4; P.cr = 0; P.ndbps = 216; break;
-    case 12: P.nb = 4; P.cr = 2; P.ndbps = 324; break;  case 13: P.nb = 6; P.cr = 1; P.ndbps = 432; break;
-    case 14: P.nb = 6; P.cr = 2; P.ndbps = 486; break;
-    default: return false;
-    }
+    int dbpc2;
+    if (!tx_ht_mcs(mcs, P.nb, P.cr, dbpc2)) return false;
+    P.ndbps = 54 * dbpc2;                                // 108 data carriers per stream
     P.nsym = (16u + 8u * (len + 4u) + 6u + (uint32_t)P.ndbps - 1u) / (uint32_t)P.ndbps;
     return true;
 }

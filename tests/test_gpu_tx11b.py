@@ -9,7 +9,8 @@ from test_tx11b_cpu import recorded_frames, ref_tx11b, start_parity
 
 pytestmark = pytest.mark.gpu
 RATES = (1000, 2000, 5500, 11000)
-LENS = [1, 2, 3, 4, 5, 6, 10, 14, 37, 100, 255, 1000, 1500]
+# 2560: the FCS's second wave is empty; 2561, 2563: the first four bytes, which the CRC complements, straddle its two waves
+LENS = [1, 2, 3, 4, 5, 6, 10, 14, 37, 100, 255, 1000, 1500, 2560, 2561, 2563]
 
 
 @pytest.fixture(scope="module")

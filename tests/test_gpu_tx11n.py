@@ -10,7 +10,8 @@ from gpu_util import same_events_11n
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refgraph_11n.npz")
-LENS = [1, 2, 3, 4, 5, 37, 100, 151, 1000, 1500, 4092]
+# 2560: the FCS's second wave is empty; 2561, 2563: the first four bytes, which the CRC complements, straddle its two waves
+LENS = [1, 2, 3, 4, 5, 37, 100, 151, 1000, 1500, 2560, 2561, 2563, 4092]
 EXTRA = {8: 7, 10: 150, 14: 1}          # a length per MCS whose data field has the reference's extra symbol (MCS 9, 11, 12, 13 have none)
 
 

@@ -48,6 +48,8 @@ def batch(env, oracle):
     frames.append((14, 3996, (0x11, 0x7F)))
     frames.append((8, 3996, (0x5D, 0x2B)))                             # 593 data symbols, the longest frame there is
     frames.append((11, 700, (0, 0x40)))                                # an all-zero seed: the scrambler stays silent
+    for mcs, ln in ((9, 2561), (12, 2563)):                            # the first four bytes, which the CRC complements, straddle the FCS's two waves
+        frames.append((mcs, ln, (int(rng.integers(1, 128)), int(rng.integers(1, 128)))))
     mp = [_mpdus(rng, ln) for _, ln, _ in frames]
     want = [T.frame_int_nofcs(a, b, mcs, seeds, oracle=oracle) for (mcs, _, seeds), (a, b) in zip(frames, mp)]
     return frames, mp, want

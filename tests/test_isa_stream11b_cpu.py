@@ -9,8 +9,8 @@ import pytest
 from test_isa_dpp_guard import LLVM, ROOT, code_objects
 
 
-def kernel_metadata(tmp_path):
-    """{kernel symbol: {field: value}} of every gfx950 code object that holds a k_rx11b kernel"""
+def kernel_metadata(tmp_path, holds=b"k_rx11b"):
+    """{kernel symbol: {field: value}} of every gfx950 code object that holds a kernel whose symbol contains `holds`"""
     lib = os.path.join(ROOT, "sora_amd", "lib", "libsora_hip.so")
     assert os.path.exists(lib), "libsora_hip.so is not built (__graft_entry__.build() / python -m sora_amd.build)"
     if not os.path.exists(os.path.join(LLVM, "llvm-readobj")):
@@ -19,7 +19,7 @@ def kernel_metadata(tmp_path):
     subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, str(fat)])
     out = {}
     for k, co in enumerate(code_objects(fat.read_bytes())):
-        if b"k_rx11b" not in co:
+        if holds not in co:
             continue
         p = tmp_path / ("co%d.o" % k)
         p.write_bytes(co)
@@ -27,7 +27,7 @@ def kernel_metadata(tmp_path):
         for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
             name = re.search(r"\.name:\s+(\S+)", blk)
             if name:
-                out[name.group(1)] = {f: int(v) for f, v in re.findall(r"\.(vgpr_count|sgpr_count|private_segment_fixed_size|vgpr_spill_count):\s+(\d+)", blk)}
+                out[name.group(1)] = {f: int(v) for f, v in re.findall(r"\.(vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|vgpr_spill_count):\s+(\d+)", blk)}
     return out
 
 
