@@ -627,6 +627,11 @@ int   sora_ht40_synchronize(sora_ht40_t* rx);                                   
                                                                                                         * process_dev waits only for the call eight calls back; results reports the most recent one) */
 int   sora_ht40_process_dev(sora_ht40_t* rx, const sora_complex16* d_iq0, const sora_complex16* d_iq1, const sora_ht40_frame* h_frames, size_t nframes, sora_complex16* d_weights);
 int   sora_ht40_results(sora_ht40_t* rx, sora_frame_result* h_out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap);
+/* Diagnostic, for tests (like d_weights): the nsym x 108 x n_bpsc de-interleaved soft bytes (0..7 each, one per coded bit, as the trellis reads them) of spatial
+ * stream `stream` (0 / 1) of described frame `frame` of the sora_ht40_process_dev call `ticket`.  Waits for that call as sora_ht40_results_of does.  *nsoft receives
+ * the count, also when cap is too small (SORA_ERR_CAPACITY; nothing is copied then).  SORA_ERR_INVALID_PARAM: a stale ticket, a raw-capture call (its frames are
+ * planned on the device), no such frame or stream.  tests/test_gpu_ht40_soft.py holds these bytes, bit for bit, to oracle/ht40_data_model.py. */
+int   sora_ht40_soft_of(sora_ht40_t* rx, int ticket, uint32_t frame, uint32_t stream, uint8_t* h_soft, size_t cap, size_t* nsoft);
 /* The same receiver on RAW CAPTURES, as every other handle takes its input: two-chain 40 MHz captures (whole 28-sample source bursts,
  * offsets a multiple of 4) in, the front end finds the frames.  The legacy preamble and HT-SIG of an HT-mixed 40 MHz frame are the 20 MHz
  * waveforms sent on both halves of the channel (the upper one rotated by 90 degrees), so the even samples of x[n] j^n are (1 + j) times

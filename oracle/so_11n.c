@@ -37,23 +37,30 @@ const uint8_t* so_demap11n_lut(int which) { init11n(); return g_lut[which]; }   
 
 static inline int lim(int v) { return v < -128 ? -128 : (v > 127 ? 127 : v); }   /* demap_limit (dsp_demap.h) */
 
+/* one carrier: I bits then Q bits; returns the number of soft values written (0: no such modulation) */
+static int demap_point(int nbpsc, so_c16 v, uint8_t* out)
+{
+    const int re = lim(v.re) + 128, im = lim(v.im) + 128;
+    switch (nbpsc) {
+    case 1: out[0] = g_lut[0][re]; return 1;                                    /* demap_bpsk_i */
+    case 2: out[0] = g_lut[0][re]; out[1] = g_lut[0][im]; return 2;
+    case 4: out[0] = g_lut[1][re]; out[1] = g_lut[2][re]; out[2] = g_lut[1][im]; out[3] = g_lut[2][im]; return 4;
+    case 6: out[0] = g_lut[3][re]; out[1] = g_lut[4][re]; out[2] = g_lut[5][re];
+            out[3] = g_lut[3][im]; out[4] = g_lut[4][im]; out[5] = g_lut[5][im]; return 6;
+    }
+    return 0;
+}
+
 int so_demap11n(int nbpsc, const so_c16 in[64], uint8_t* out)
 {
     init11n();
+    if (nbpsc != 1 && nbpsc != 2 && nbpsc != 4 && nbpsc != 6) return -1;
     int j = 0;
     for (int pass = 0; pass < 2; pass++) {
         const int lo = pass ? 1 : 64 - 28, hi = pass ? 28 : 63;
         for (int i = lo; i <= hi; i++) {
             if (i == 64 - 21 || i == 64 - 7 || i == 7 || i == 21) continue;         /* pilots */
-            const int re = lim(in[i].re) + 128, im = lim(in[i].im) + 128;
-            switch (nbpsc) {
-            case 1: out[j++] = g_lut[0][re]; break;                                 /* demap_bpsk_i */
-            case 2: out[j++] = g_lut[0][re]; out[j++] = g_lut[0][im]; break;
-            case 4: out[j++] = g_lut[1][re]; out[j++] = g_lut[2][re]; out[j++] = g_lut[1][im]; out[j++] = g_lut[2][im]; break;
-            case 6: out[j++] = g_lut[3][re]; out[j++] = g_lut[4][re]; out[j++] = g_lut[5][re];
-                    out[j++] = g_lut[3][im]; out[j++] = g_lut[4][im]; out[j++] = g_lut[5][im]; break;
-            default: return -1;
-            }
+            j += demap_point(nbpsc, in[i], out + j);
         }
     }
     return j;
@@ -103,43 +110,54 @@ static inline cf_t cf_mul(cf_t a, cf_t b)    /* vcf mul: moveldup/movehdup, two 
 }
 static inline int32_t cvtps(float x) { return (x >= -2147483648.0f && x < 2147483648.0f) ? (int32_t)lrintf(x) : INT32_MIN; }
 
+/* one carrier of TMimoChannelEst: p[r], q[r] = HT-LTF symbol 1 / 2 of RX chain r at this carrier; negate = the HT-LTF there is not +1.
+ * h[2 r + s] = chain r, stream s; hinv[2 s + r] = row s of the inverse x 2^16 */
+static void mimo_est_point(const so_c16 p[2], const so_c16 q[2], int negate, so_c16 h[4], so_c16 hinv[4])
+{
+    for (int r = 0; r < 2; r++) {
+        so_c16 d = so_sra(so_csubs(p[r], q[r]), 1), s = so_sra(so_cadds(p[r], q[r]), 1);
+        if (negate) { d = so_c(so_neg16(d.re), so_neg16(d.im)); s = so_c(so_neg16(s.re), so_neg16(s.im)); }
+        h[2 * r] = d; h[2 * r + 1] = s;
+    }
+    const cf_t a00 = { (float)h[0].re, (float)h[0].im }, a01 = { (float)h[1].re, (float)h[1].im };
+    const cf_t a10 = { (float)h[2].re, (float)h[2].im }, a11 = { (float)h[3].re, (float)h[3].im };
+    const cf_t ad = cf_mul(a00, a11), bc = cf_mul(a01, a10);
+    const cf_t det = { ad.re - bc.re, ad.im - bc.im };
+    const float t0 = det.re * det.re, t1 = det.im * det.im;
+    const float n = (t0 + t1) / 65536.0f;                                     /* SquaredNorm, then div(n, scale) */
+    const cf_t ds = { det.re, -det.im };
+    const cf_t m01 = { -a01.re, -a01.im }, m10 = { -a10.re, -a10.im };
+    const cf_t r00 = cf_mul(a11, ds), r01 = cf_mul(m01, ds), r10 = cf_mul(m10, ds), r11 = cf_mul(a00, ds);
+    const cf_t* rr[4] = { &r00, &r01, &r10, &r11 };
+    for (int k = 0; k < 4; k++) {
+        const float qre = rr[k]->re / n, qim = rr[k]->im / n;
+        hinv[k].re = so_sat16(cvtps(qre)); hinv[k].im = so_sat16(cvtps(qim));
+    }
+}
+/* one carrier of TMimoChannelComp: row (wa, wb) of the inverse applied to the two chains */
+static so_c16 mimo_comp_point(so_c16 wa, so_c16 wb, so_c16 y0, so_c16 y1)
+{
+    int32_t ar, ai, br, bi;
+    so_mul32(wa, y0, &ar, &ai); so_mul32(wb, y1, &br, &bi);
+    return so_c(so_sat16(so_w32((int64_t)ar + br) >> 9), so_sat16(so_w32((int64_t)ai + bi) >> 9));
+}
+
 void so_mimo_est11n(const so_c16 ltf0[128], const so_c16 ltf1[128], so_c16 h[2][128], so_c16 hinv[2][128])
 {
-    const so_c16* ltf[2] = { ltf0, ltf1 };
-    for (int r = 0; r < 2; r++)
-        for (int i = 0; i < 64; i++) {
-            so_c16 d = so_sra(so_csubs(ltf[r][i], ltf[r][i + 64]), 1), s = so_sra(so_cadds(ltf[r][i], ltf[r][i + 64]), 1);
-            if (htltf_negate(i)) { d = so_c(so_neg16(d.re), so_neg16(d.im)); s = so_c(so_neg16(s.re), so_neg16(s.im)); }
-            h[r][i] = d; h[r][i + 64] = s;
-        }
     for (int i = 0; i < 64; i++) {
-        const cf_t a00 = { (float)h[0][i].re, (float)h[0][i].im }, a01 = { (float)h[0][i + 64].re, (float)h[0][i + 64].im };
-        const cf_t a10 = { (float)h[1][i].re, (float)h[1][i].im }, a11 = { (float)h[1][i + 64].re, (float)h[1][i + 64].im };
-        const cf_t ad = cf_mul(a00, a11), bc = cf_mul(a01, a10);
-        const cf_t det = { ad.re - bc.re, ad.im - bc.im };
-        const float t0 = det.re * det.re, t1 = det.im * det.im;
-        const float n = (t0 + t1) / 65536.0f;                                     /* SquaredNorm, then div(n, scale) */
-        const cf_t ds = { det.re, -det.im };
-        const cf_t m01 = { -a01.re, -a01.im }, m10 = { -a10.re, -a10.im };
-        const cf_t r00 = cf_mul(a11, ds), r01 = cf_mul(m01, ds), r10 = cf_mul(m10, ds), r11 = cf_mul(a00, ds);
-        const cf_t* rr[4] = { &r00, &r01, &r10, &r11 };
-        so_c16* dst[4] = { &hinv[0][i], &hinv[0][i + 64], &hinv[1][i], &hinv[1][i + 64] };
-        for (int k = 0; k < 4; k++) {
-            const float qre = rr[k]->re / n, qim = rr[k]->im / n;
-            int32_t ire = cvtps(qre), iim = cvtps(qim);
-            dst[k]->re = so_sat16(ire); dst[k]->im = so_sat16(iim);
-        }
+        const so_c16 p[2] = { ltf0[i], ltf1[i] }, q[2] = { ltf0[i + 64], ltf1[i + 64] };
+        so_c16 hh[4], hi[4];
+        mimo_est_point(p, q, htltf_negate(i), hh, hi);
+        h[0][i] = hh[0]; h[0][i + 64] = hh[1]; h[1][i] = hh[2]; h[1][i + 64] = hh[3];
+        hinv[0][i] = hi[0]; hinv[0][i + 64] = hi[1]; hinv[1][i] = hi[2]; hinv[1][i + 64] = hi[3];
     }
 }
 
 void so_mimo_comp11n(const so_c16 hinv[2][128], const so_c16 y0[64], const so_c16 y1[64], so_c16 x0[64], so_c16 x1[64])
 {
     for (int i = 0; i < 64; i++) {
-        int32_t ar, ai, br, bi;
-        so_mul32(hinv[0][i], y0[i], &ar, &ai); so_mul32(hinv[0][i + 64], y1[i], &br, &bi);
-        x0[i] = so_c(so_sat16(so_w32((int64_t)ar + br) >> 9), so_sat16(so_w32((int64_t)ai + bi) >> 9));
-        so_mul32(hinv[1][i], y0[i], &ar, &ai); so_mul32(hinv[1][i + 64], y1[i], &br, &bi);
-        x1[i] = so_c(so_sat16(so_w32((int64_t)ar + br) >> 9), so_sat16(so_w32((int64_t)ai + bi) >> 9));
+        x0[i] = mimo_comp_point(hinv[0][i], hinv[0][i + 64], y0[i], y1[i]);
+        x1[i] = mimo_comp_point(hinv[1][i], hinv[1][i + 64], y0[i], y1[i]);
     }
 }
 
@@ -364,4 +382,70 @@ int so_sig_decode11n(const uint8_t soft[144], uint8_t out9[9], uint32_t f[9])
     } while (0);
     if (!ok) f[0] = SO_E_PLCP_HEADER_FAIL;
     return ok;
+}
+
+/* ------------------------------------------------------------------ the data field of a 40 MHz HT two-stream frame, composed from the bricks above
+ * PARITY UNPINNED as a whole (the reference has no 40 MHz graph); every operation below is one of the pinned bricks.  The carrier plan, the HT-LTF
+ * signs and the interleaver are the caller's (oracle/py_ht40.py states them from IEEE 802.11n-2009; oracle/ht40_data_model.py passes them in).
+ *   ht40_symbol          one 160-sample symbol at frame position pos: TFreqComp_11n at phase n cfo - theta (n from the frame's first sample, the
+ *                        cyclic prefix counted but dropped), FFT<128> per chain
+ *   so_ht40_zf_weights   TMimoChannelEst's arithmetic on the two HT-LTF symbols, carrier by carrier: w[0..3][bin] = rows of the inverse x 2^16
+ *   so_ht40_data_field   per data symbol: x_s = TMimoChannelComp with the GIVEN weights, theta += ((sum of stream 0's pilot arctangents / npilot)
+ *                        + (stream 1's)) >> 1 (TPilotTrack_11n's casts, effective from the next symbol), T11nDemap* over the data carriers in the
+ *                        given order, out[k] = demapped[deint[stream][k]] */
+static void ht40_symbol(const so_c16* iq0, const so_c16* iq1, uint32_t pos, int32_t cfo, int16_t theta, so_c16 y0[128], so_c16 y1[128])
+{
+    int16_t st[24]; so_c16 c0[128], c1[128];
+    for (int k = 0; k < 8; k++) {
+        st[k] = so_w16((int32_t)((pos + 32u + (uint32_t)k) * (uint32_t)cfo)); st[8 + k] = so_w16((int32_t)(8u * (uint32_t)cfo)); st[16 + k] = theta;
+    }
+    so_freq_comp11n(st, iq0 + pos + 32, iq1 + pos + 32, c0, c1, 16);
+    so_fft128(c0, y0); so_fft128(c1, y1);
+}
+
+void so_ht40_zf_weights(const so_c16* iq0, const so_c16* iq1, int32_t cfo, const int8_t ltf_sign[128], so_c16 w[4][128])
+{
+    so_c16 y[2][2][128];                                                         /* [HT-LTF symbol][chain][bin] */
+    for (int s = 0; s < 2; s++) ht40_symbol(iq0, iq1, 160u * (uint32_t)s, cfo, 0, y[s][0], y[s][1]);
+    for (int i = 0; i < 128; i++) {
+        const so_c16 p[2] = { y[0][0][i], y[0][1][i] }, q[2] = { y[1][0][i], y[1][1][i] };
+        so_c16 h[4], hi[4];
+        mimo_est_point(p, q, ltf_sign[i] != 1, h, hi);
+        for (int k = 0; k < 4; k++) w[k][i] = hi[k];
+    }
+}
+
+int so_ht40_data_field(const so_c16* iq0, const so_c16* iq1, uint32_t nsym, int nbpsc, int32_t cfo, const so_c16 w[4][128],
+                       const int16_t* data_bins, int ndata, const int16_t* pilot_bins, int npilot, const uint16_t* deint0, const uint16_t* deint1,
+                       uint8_t* soft0, uint8_t* soft1, int16_t* theta_at, so_c16* xs_out)
+{
+    init11n();
+    if ((nbpsc != 1 && nbpsc != 2 && nbpsc != 4 && nbpsc != 6) || ndata <= 0 || ndata > 128 || npilot <= 0) return -1;
+    const int ncb = ndata * nbpsc;
+    const uint16_t* deint[2] = { deint0, deint1 }; uint8_t* out[2] = { soft0, soft1 };
+    int16_t theta = 0;
+    for (uint32_t d = 0; d < nsym; d++) {
+        so_c16 y0[128], y1[128], x[2][128]; uint8_t raw[2][128 * 6];
+        if (theta_at) theta_at[d] = theta;                                       /* the phase symbol d is compensated with */
+        ht40_symbol(iq0, iq1, 320u + 160u * d, cfo, theta, y0, y1);
+        for (int i = 0; i < 128; i++) {
+            x[0][i] = mimo_comp_point(w[0][i], w[1][i], y0[i], y1[i]);
+            x[1][i] = mimo_comp_point(w[2][i], w[3][i], y0[i], y1[i]);
+        }
+        if (xs_out) memcpy(xs_out + (size_t)d * 256, x, sizeof(x));
+        int t[2];
+        for (int s = 0; s < 2; s++) {
+            int th = 0;
+            for (int k = 0; k < npilot; k++) th += so_dsp_atan16(x[s][pilot_bins[k]].re, x[s][pilot_bins[k]].im);
+            t[s] = (int16_t)(th / npilot);
+        }
+        theta = so_w16(theta + (int16_t)((t[0] + t[1]) >> 1));
+        for (int s = 0; s < 2; s++) {
+            int j = 0;
+            for (int c = 0; c < ndata; c++) j += demap_point(nbpsc, x[s][data_bins[c]], raw[s] + j);
+            for (int k = 0; k < ncb; k++) out[s][(size_t)d * ncb + k] = raw[s][deint[s][k]];
+        }
+    }
+    if (theta_at) theta_at[nsym] = theta;
+    return (int)nsym * ncb;
 }

@@ -145,6 +145,15 @@ void so_viterbi_sig_bits(const uint8_t* soft, int nbits, uint8_t* out);
 /* fields[9] = error_code, data_rate_kbps, frame_length, ht_frame_mcs, ht_frame_length, code_rate, total_symbols, remain_symbols, symbol_type */
 int so_sig_decode11n(const uint8_t soft[144], uint8_t out9[9], uint32_t fields[9]);
 void so_mimo_comp11n(const so_c16 hinv[2][128], const so_c16 y0[64], const so_c16 y1[64], so_c16 x0[64], so_c16 x1[64]);
+/* The data field of a 40 MHz HT two-stream frame composed from the bricks above (so_11n.c; the carrier plan, HT-LTF signs and interleaver are the
+ * caller's: oracle/ht40_data_model.py).  iq0 / iq1 point at the first sample (cyclic prefix) of HT-LTF 1 and hold (2 + nsym) x 160 samples;
+ * w[0..3][bin] = w00, w01, w10, w11 x 2^16.  soft0 / soft1: nsym x ndata x nbpsc de-interleaved soft bytes each; theta_at[nsym + 1] (optional): the
+ * tracked phase each symbol is compensated with, then the final one; xs_out [nsym][2][128] (optional): the detected symbols.  Returns the number of
+ * soft values per stream, < 0 for bad arguments. */
+void so_ht40_zf_weights(const so_c16* iq0, const so_c16* iq1, int32_t cfo, const int8_t ltf_sign[128], so_c16 w[4][128]);
+int so_ht40_data_field(const so_c16* iq0, const so_c16* iq1, uint32_t nsym, int nbpsc, int32_t cfo, const so_c16 w[4][128],
+                       const int16_t* data_bins, int ndata, const int16_t* pilot_bins, int npilot, const uint16_t* deint0, const uint16_t* deint1,
+                       uint8_t* soft0, uint8_t* soft1, int16_t* theta_at, so_c16* xs_out);
 
 /* RX_BLOCK dump de-framing (brick/inc/brickutil.h:20-58); raw14: apply the (int16)(x<<2) sign fix. */
 int so_load_dump(const uint8_t* file, uint32_t file_bytes, so_c16* out, uint32_t max_samples, int raw14);

@@ -75,7 +75,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_rx11n_wait_any", "sora_rx11n_results_of", "sora_rx11n_set_mcs_max",
            "sora_ht40_symbols", "sora_ht40_create", "sora_ht40_destroy", "sora_ht40_stream", "sora_ht40_synchronize", "sora_ht40_set_trellis", "sora_ht40_process_dev",
                       "sora_ht40_process_captures_dev", "sora_ht40_results", "sora_ht40_ticket", "sora_ht40_calls_in_flight", "sora_ht40_wait", "sora_ht40_wait_any",
-                      "sora_ht40_stream_of", "sora_ht40_results_of", "sora_ht40_set_stream_mode", "sora_ht40_stream_consumed",
+                      "sora_ht40_stream_of", "sora_ht40_results_of", "sora_ht40_soft_of", "sora_ht40_set_stream_mode", "sora_ht40_stream_consumed",
            "sora_shard_unique_id", "sora_shard_create", "sora_shard_destroy", "sora_shard_world", "sora_shard_partition", "sora_shard_gather_rows",
            "sora_shard_reduce_counters", "sora_shard_gather_results", "sora_shard_gather_results_mpdu"]
 
@@ -250,6 +250,7 @@ def load(build_if_missing=True):
     _res_of = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t]
     _deliver = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     L.sora_ht40_process_captures_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
+    L.sora_ht40_soft_of.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     # what the four receive handles share (include/sora_hip.h: tickets, calls in flight, stream continuation)
     vp = ctypes.c_void_p
     shared = [("_destroy", [vp], None), ("_stream", [vp], vp), ("_ticket", [vp], ctypes.c_int), ("_wait", [vp, ctypes.c_int], ctypes.c_int),
@@ -780,6 +781,18 @@ class RxHt40(_Handle):
         for d in out:
             d["stream"] = d["start_sample"]
         return out
+
+    def soft(self, frame, stream, ticket=None):
+        """sora_ht40_soft_of: the de-interleaved soft bytes (uint8 [nsym * 108 * n_bpsc]) of spatial stream `stream` of described frame `frame` of a process_dev call
+        (ticket None: the most recent call) -- a diagnostic for tests"""
+        t = self.ticket() if ticket is None else int(ticket)
+        n = ctypes.c_size_t(0)
+        rc = self._L.sora_ht40_soft_of(self._h, t, int(frame), int(stream), None, 0, ctypes.byref(n))
+        if rc != SORA_OK and n.value == 0:
+            _check(rc)
+        out = np.zeros(n.value, np.uint8)
+        _check(self._L.sora_ht40_soft_of(self._h, t, int(frame), int(stream), out.ctypes.data, out.size, ctypes.byref(n)))
+        return out[:n.value]
 
 
 def ht40_symbols(length0, length1, n_bpsc, code_rate):

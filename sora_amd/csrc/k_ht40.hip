@@ -727,6 +727,31 @@ int sora_ht40_deliver_async(sora_ht40_t* rx, int ticket, sora_frame_result* h_ro
     return SORA_OK;
 }
 
+// Diagnostic (tests): the de-interleaved soft bytes k_ht40_frame wrote for one stream of one described frame, as the trellis reads them.  The offsets are the ones
+// ht40_submit laid out: frame after frame, stream 1 of a frame behind stream 0 at the next multiple of 32.
+int sora_ht40_soft_of(sora_ht40_t* rx, int ticket, uint32_t frame, uint32_t stream, uint8_t* h_soft, size_t cap, size_t* nsoft)
+{
+    if (!rx || !nsoft || (!h_soft && cap)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_soft_of: null argument", 0);
+    *nsoft = 0;
+    Ht40Slot* S = call_find(rx->slot, kHt40Slots, ticket);
+    if (!S) return call_stale("sora_ht40_soft_of");
+    if (S->capture_mode) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_soft_of: descriptor calls (sora_ht40_process_dev) only", 0);
+    if (frame >= S->nframes || stream > 1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_soft_of: no such frame / stream in this call", 0);
+    uint64_t off = 0, per = 0;
+    for (uint32_t i = 0; i <= frame; i++) {
+        const sora_ht40_frame& f = S->h_frames[i];
+        per = (uint64_t)sora_ht40_symbols(f.length[0], f.length[1], f.n_bpsc, f.code_rate) * 108 * f.n_bpsc;
+        if (i < frame) off += 2 * ((per + 31) / 32 * 32);
+    }
+    off += stream * ((per + 31) / 32 * 32);
+    *nsoft = (size_t)per;
+    if (per > cap) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_soft_of: output buffer too small", 0);
+    HIPCHK(hipSetDevice(rx->device));
+    HIPCHK(hipStreamSynchronize(S->stream));
+    HIPCHK(hipMemcpy(h_soft, S->d_soft + off, (size_t)per, hipMemcpyDeviceToHost));
+    return SORA_OK;
+}
+
 int sora_ht40_results_of(sora_ht40_t* rx, int ticket, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap)
 {
     if (!nout || !out) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_results_of: null argument", 0);

@@ -155,3 +155,19 @@ def test_the_library_on_disk_is_built_from_the_sources_in_the_tree():
     info = build.build_info()
     assert info["exists"] and info["stamp"] and info["built_from_this_tree"], info
     assert info["stamp"]["sources_sha256"] == build.sources_sha256()
+
+
+def test_ht40_soft_read_out_is_declared_typed_and_refuses_a_null_handle(lib):
+    """sora_ht40_soft_of (the diagnostic tests/test_gpu_ht40_soft.py reads the data field's soft bytes with): in the header, exported, typed by the binding,
+    refused for a null handle or a null count before any device work, and RxHt40 carries the method."""
+    import sora_amd
+    from sora_amd import capi
+    n = "sora_ht40_soft_of"
+    assert n in declared_functions() and n in capi.EXPORTS and hasattr(lib, n)
+    assert len(lib.sora_ht40_soft_of.argtypes) == 7
+    lib.sora_hip_table_digest(None, None)                               # leaves a message that names no receive handle
+    ns = ctypes.c_size_t(5)
+    assert lib.sora_ht40_soft_of(None, 1, 0, 0, None, 0, ctypes.byref(ns)) == -1          # SORA_ERR_INVALID_PARAM
+    assert b"sora_ht40_soft_of" in lib.sora_hip_last_error()
+    assert lib.sora_ht40_soft_of(None, 1, 0, 0, None, 0, None) == -1
+    assert callable(getattr(sora_amd.RxHt40, "soft", None))
