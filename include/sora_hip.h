@@ -442,6 +442,22 @@ int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t*
 size_t sora_hip_tx_ht40_samples(uint32_t mpdu_len_nofcs, uint32_t mcs);
 int sora_hip_tx_ht40(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
                      size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
+/* The JOINT coding of the same frame (opt-in; DESIGN.md section 7 "g3"; the receiver takes it with sora_ht40_set_coding(rx, SORA_HT40_CODING_JOINT)).  As
+ * oracle/py_ht40.py::tx_frame, except that a frame carries ONE PSDU of LENGTH = len + 4 <= 4000 bytes, the way IEEE 802.11n-2009 (N_ES = 1) and the reference's own
+ * 20 MHz modulator (fb11nmod_config.hpp: one encoder, TStreamParser*) do it:
+ *   - bit field: SERVICE(16) + PSDU + tail(6) + pad up to N_SYM x N_DBPS bits, N_DBPS = 2 x 108 x N_BPSC x R, N_SYM = ceil((16 + 8 LENGTH + 6) / N_DBPS)
+ *     = sora_ht40_symbols_joint(LENGTH, n_bpsc, code_rate);
+ *   - coding: one scrambler (one seed, seven bits used, default 0x5D; the tail forced to zero after scrambling), one K = 7 encoder, the same three puncturing patterns;
+ *   - stream parser (the reference's rule, sora_hip_tx11n's): with s = max(1, N_BPSC / 2), coded bit kc (0 .. 2 N_CBPSS - 1) of a symbol goes to spatial stream
+ *     (kc / s) & 1 and becomes that stream's bit (kc / 2s) s + kc % s;
+ *   - unchanged: each stream's HT interleaver, mapper and carrier plan, the pilots, HT-LTFs, preamble, HT-SIG bits and the amplitudes A.  HT-SIG does not signal the
+ *     coding: it is a property of the call here and of the handle at the receiver.  L-SIG's length follows from the new N_SYM by the same formula.
+ * Frame f: one MPDU WITHOUT FCS of d_len[f] bytes at d_mpdu + d_off[f], MCS d_mcs[f], seed d_seed[f] (d_seed NULL: 0x5D).  Writes sora_hip_tx_ht40_joint_samples(len,
+ * mcs) = 1280 + 160 (2 + N_SYM) samples per chain (0 outside MCS 8..14 and 1..3996 bytes).  Sample-exact against tests/ht40_joint_model.py::frame_int_joint.  Null
+ * checks, error codes, the behaviour without a device and "a frame that is not accepted gets nothing written, the others are not affected" are sora_hip_tx_ht40's. */
+size_t sora_hip_tx_ht40_joint_samples(uint32_t mpdu_len_nofcs, uint32_t mcs);
+int sora_hip_tx_ht40_joint(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
+                           size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
 
 /* 802.11b transmitter: the reference's modulation graph CreateModGraph (kernel/bb/demod11/fb11bmod_config.hpp:28-50) as
  * Test11B_FB_Mod runs it (fb11b_mod.cpp:40-70): long preamble (SYNC, SFD), PLCP header, MPDU + FCS at 1, 2, 5.5 or 11 Mbps, Barker
@@ -699,6 +715,22 @@ int   sora_ht40_deliver_async(sora_ht40_t* rx, int ticket, sora_frame_result* h_
  * (SORA_ERR_INVALID_PARAM). */
 int   sora_ht40_set_stream_mode(sora_ht40_t* rx, int enable);
 int   sora_ht40_stream_consumed(sora_ht40_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps);
+/* The handle's CODING.  SORA_HT40_CODING_PER_STREAM (the default) is everything above: two PSDUs of equal length per frame, one decoder per spatial stream.
+ * SORA_HT40_CODING_JOINT takes the frames of sora_hip_tx_ht40_joint (its comment states the format): ONE PSDU per frame, one encoder's output stream-parsed over the
+ * two streams, one decoder.  HT-SIG does not signal the coding; the handle's setting decides.  A handle in joint coding:
+ *   - descriptor calls: length[0] is the PSDU length and length[1] must be 0 (else SORA_ERR_INVALID_PARAM before anything is launched); nsym =
+ *     sora_ht40_symbols_joint(length[0], n_bpsc, code_rate); ONE row per frame: start_sample 0, error_code, length, crc32, nsym and rate_kbps as above, capture_id =
+ *     frame_id.  max_soft_values: the same rule (a frame holds the same number of soft bytes);
+ *   - raw-capture calls and stream mode work as above with ONE row per recorded frame; a frame's extent follows the joint N_SYM;
+ *   - sora_ht40_soft_of: `stream` must be 0; the 2 x nsym x 108 x n_bpsc MERGED soft bytes are returned, as the trellis reads them (symbol after symbol, the
+ *     symbol's 2 N_CBPSS coded bits in the encoder's order);
+ *   - sora_ht40_deliver_async: max_rows as above (the bound is not halved).
+ * Returns the previous value; a negative argument only queries.  Like sora_ht40_set_stream_mode it first waits for every call in flight and starts every stream
+ * afresh.  Calls issued before the switch keep their coding when their results are read. */
+#define SORA_HT40_CODING_PER_STREAM 0
+#define SORA_HT40_CODING_JOINT      1
+int      sora_ht40_set_coding(sora_ht40_t* rx, int coding);
+uint32_t sora_ht40_symbols_joint(uint32_t length, uint32_t n_bpsc, uint32_t code_rate);   /* data symbols of a joint-coded frame (0: bad arguments) */
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU sharding for a C host.  Captures are independent -- the reference resets its context per

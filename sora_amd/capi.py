@@ -64,6 +64,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_hip_viterbi_window_stats",
            "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11a44", "sora_hip_tx11a44_samples",
            "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx_ht40", "sora_hip_tx_ht40_samples", "sora_hip_tx11b", "sora_hip_tx11b_samples",
+           "sora_hip_tx_ht40_joint", "sora_hip_tx_ht40_joint_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n", "sora_rx11b_create",
                       "sora_rx11b_destroy", "sora_rx11b_stream", "sora_rx11b_synchronize", "sora_rx11b_process_dev", "sora_rx11b_process", "sora_rx11b_results", "sora_rx11b_ticket",
@@ -76,6 +77,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_ht40_symbols", "sora_ht40_create", "sora_ht40_destroy", "sora_ht40_stream", "sora_ht40_synchronize", "sora_ht40_set_trellis", "sora_ht40_process_dev",
                       "sora_ht40_process_captures_dev", "sora_ht40_results", "sora_ht40_ticket", "sora_ht40_calls_in_flight", "sora_ht40_wait", "sora_ht40_wait_any",
                       "sora_ht40_stream_of", "sora_ht40_results_of", "sora_ht40_soft_of", "sora_ht40_set_stream_mode", "sora_ht40_stream_consumed",
+                      "sora_ht40_set_coding", "sora_ht40_symbols_joint",
            "sora_shard_unique_id", "sora_shard_create", "sora_shard_destroy", "sora_shard_world", "sora_shard_partition", "sora_shard_gather_rows",
            "sora_shard_reduce_counters", "sora_shard_gather_results", "sora_shard_gather_results_mpdu"]
 
@@ -178,6 +180,8 @@ def load(build_if_missing=True):
     L.sora_ht40_set_trellis.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.sora_rx_kernel_name_fused.argtypes = [ctypes.c_size_t]; L.sora_rx_kernel_name_fused.restype = ctypes.c_char_p
     L.sora_ht40_symbols.argtypes = [ctypes.c_uint32] * 4; L.sora_ht40_symbols.restype = ctypes.c_uint32
+    L.sora_ht40_symbols_joint.argtypes = [ctypes.c_uint32] * 3; L.sora_ht40_symbols_joint.restype = ctypes.c_uint32
+    L.sora_ht40_set_coding.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.sora_ht40_create.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
     L.sora_ht40_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Ht40Frame), ctypes.c_size_t, ctypes.c_void_p]
     L.sora_ht40_results.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t]
@@ -220,6 +224,8 @@ def load(build_if_missing=True):
     L.sora_hip_tx11n.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
     L.sora_hip_tx_ht40_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx_ht40_samples.restype = ctypes.c_size_t
     L.sora_hip_tx_ht40.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
+    L.sora_hip_tx_ht40_joint_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx_ht40_joint_samples.restype = ctypes.c_size_t
+    L.sora_hip_tx_ht40_joint.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
     L.sora_hip_tx11b_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11b_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11b.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
     L.sora_hip_ingest_count.argtypes = [ctypes.c_size_t, ctypes.c_uint]; L.sora_hip_ingest_count.restype = ctypes.c_size_t
@@ -740,6 +746,13 @@ class RxHt40(_Handle):
         if r < 0: _check(r)
         return r
 
+    def set_coding(self, coding=-1):
+        """sora_ht40_set_coding: CODING_PER_STREAM (0, the default) or CODING_JOINT (1: one PSDU per frame, stream-parsed; descriptors carry l1 = 0, one row per
+        frame, soft(frame, 0) is the merged stream).  -> the previous value; a negative argument only queries"""
+        r = int(self._L.sora_ht40_set_coding(self._h, int(coding)))
+        if r < 0: _check(r)
+        return r
+
     def process_dev(self, d_iq0, d_iq1, descs, d_weights=None):
         arr = self.frames(descs); n = getattr(arr, "_n", len(arr))
         _hold(self, (d_iq0, d_iq1, d_weights)); self._n = n
@@ -797,6 +810,14 @@ class RxHt40(_Handle):
 
 def ht40_symbols(length0, length1, n_bpsc, code_rate):
     return load().sora_ht40_symbols(length0, length1, n_bpsc, code_rate)
+
+
+HT40_CODING_PER_STREAM, HT40_CODING_JOINT = 0, 1
+
+
+def ht40_symbols_joint(length, n_bpsc, code_rate):
+    """data symbols of a joint-coded 40 MHz HT frame whose one PSDU has `length` bytes (sora_ht40_symbols_joint; 0: bad arguments)"""
+    return int(load().sora_ht40_symbols_joint(int(length), int(n_bpsc), int(code_rate)))
 
 
 # ---- per-stage entry points on torch CUDA tensors ---------------------------------------------------
@@ -1206,6 +1227,47 @@ def tx_ht40(mpdus0, mpdus1, mcs, seeds=None, device=0, stream=None, sync=True, g
     out1 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
     _check(load().sora_hip_tx_ht40(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
                                    _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
+    if sync:
+        _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
+    return out0, out1, [int(v) for v in ooff]
+
+
+def tx_ht40_joint_samples(mpdu_len_nofcs, mcs):
+    """Samples per TX chain of one joint-coded 40 MHz HT 2x2 frame (sora_hip_tx_ht40_joint_samples): 1280 + 160 (2 + N_SYM); 0 for an MCS or length that is not accepted."""
+    return int(load().sora_hip_tx_ht40_joint_samples(int(mpdu_len_nofcs), int(mcs)))
+
+
+def tx_ht40_joint(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None):
+    """Modulate a batch of MPDUs (bytes WITHOUT FCS), ONE per frame, as joint-coded HT-mixed 40 MHz two-stream frames on the GPU (MCS 8..14): what an RxHt40 in
+    CODING_JOINT receives.  -> (out0, out1, offsets) as tx_ht40.  seeds: one scrambler seed per frame (None: 0x5D).  A frame that is not accepted is refused before
+    any launch."""
+    import torch
+    n = len(mpdus)
+    mcs = [int(m) for m in mcs] if np.ndim(mcs) else [int(mcs)] * n
+    lens = [len(m) for m in mpdus]
+    if len(mcs) != n:
+        raise SoraError(-1, "tx_ht40_joint: one MCS per frame")
+    ns = [tx_ht40_joint_samples(l, m) for l, m in zip(lens, mcs)]
+    if any(v == 0 for v in ns):
+        raise SoraError(-1, "tx_ht40_joint: unsupported MCS or length (MCS 8..14, 1..3996 bytes)")
+    if seeds is not None and (len(seeds) != n or any(np.ndim(p) != 0 for p in seeds)):
+        raise SoraError(-1, "tx_ht40_joint: seeds must hold one seed per frame")
+    off = np.zeros(n + 1, np.int64); np.cumsum([(l + 3) // 4 * 4 for l in lens], out=off[1:])
+    blob = np.zeros(max(int(off[-1]), 4), np.uint8)
+    for f in range(n):
+        blob[off[f]:off[f] + lens[f]] = np.frombuffer(bytes(mpdus[f]), np.uint8)
+    gaps = [0] * n if gaps is None else [int(v) for v in gaps]
+    ooff = np.zeros(n + 1, np.uint64); np.cumsum([a + b for a, b in zip(ns, gaps)], out=ooff[1:])
+    first = ooff[:-1] + np.asarray(gaps, np.uint64)
+    dev = torch.device("cuda", device)
+    d_blob = torch.from_numpy(blob).to(dev); d_off = torch.from_numpy(off[:-1].astype(np.int32)).to(dev)
+    d_len = torch.from_numpy(np.asarray(lens, np.int32)).to(dev); d_mcs = torch.from_numpy(np.asarray(mcs, np.int32)).to(dev)
+    d_seed = torch.from_numpy(np.asarray(seeds, np.int64).astype(np.uint8).reshape(-1)).to(dev) if seeds is not None else None
+    d_ooff = torch.from_numpy(first.astype(np.int64)).to(dev)
+    out0 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
+    out1 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
+    _check(load().sora_hip_tx_ht40_joint(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
+                                         _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     return out0, out1, [int(v) for v in ooff]

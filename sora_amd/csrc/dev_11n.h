@@ -283,7 +283,10 @@ __device__ __forceinline__ int cfo_est11n(const short* atan_tab, cpx a0, cpx b0,
 
 // T11aDesc + TBB11aFrameSink (scramble.hpp:319-349, PHY_11a.hpp:660-692) on a decoded frame, one wave: dec = the decoder's bytes (SERVICE field first), L = the
 // PSDU length.  Descrambles by the phase table into `bytes` (the wave's LDS buffer, >= L bytes) and the MPDU slot `mp`, runs the parallel CRC-32 and
-// returns the verdict; fcs = the frame's last four bytes.  Both are lane 0's to store (crc32_wave leaves the register there)
+// returns the verdict; fcs = the frame's last four bytes.  Both are lane 0's to store (crc32_wave leaves the register there).  One pass of crc32_wave covers the
+// last 64 x 40 = 2560 bytes: enough for the 802.11n handle (LENGTH <= 1500).  LONG (the 40 MHz handle, LENGTH <= 4000): a longer PSDU takes a second pass over the
+// 2560 bytes in front of those, joined through Z_2560 as dev_tx.h joins the transmitter's two FCS waves.
+template <bool LONG = false>
 __device__ __forceinline__ uint32_t finish_frame(const Tables& T, const uint8_t* dec, uint32_t L, uint8_t* bytes, uint8_t* mp, const uint32_t* s_crc,
                                                  const uint32_t* s_z, int lane, uint32_t& fcs)
 {
@@ -297,7 +300,12 @@ __device__ __forceinline__ uint32_t finish_frame(const Tables& T, const uint8_t*
     wave_lds_sync();
     const int n = L >= 4 ? (int)L - 4 : 0;
     uint32_t crc;
-    if (n >= 4) crc = crc32_wave(bytes, n, s_crc, s_z, lane);
+    if (n >= 4) {
+        crc = crc32_wave(bytes, n, s_crc, s_z, lane);
+        if constexpr (LONG) {
+            if (n > 64 * 40) crc ^= crc_zeros(s_z, 5, crc_zeros(s_z, 5, crc32_wave(bytes, n, s_crc, s_z, lane + 64)));
+        }
+    }
     else { crc = 0xFFFFFFFFu; for (int i = 0; i < n; i++) crc = (crc >> 8) ^ s_crc[(bytes[i] ^ crc) & 0xFF]; }
     fcs = 0;
     if (L >= 4) fcs = (uint32_t)bytes[L - 4] | ((uint32_t)bytes[L - 3] << 8) | ((uint32_t)bytes[L - 2] << 16) | ((uint32_t)bytes[L - 1] << 24);

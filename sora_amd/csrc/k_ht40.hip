@@ -15,6 +15,8 @@
 // interleaver parameters for 40 MHz (N_COL 18, N_ROW 6 N_BPSC, N_ROT 29), per-stream encoding, and the MMSE weights
 // W = diag((W' H)_ss)^-1 W', W' = (H^H H + s2 I)^-1 H^H (unbiased MMSE) in single precision (documented tolerance: +-1 LSB of the int16 weight against a float64 evaluation,
 // tests/test_gpu_ht40.py).  The model the tests generate captures with is oracle/py_ht40.py.
+// Two codings (sora_ht40_set_coding): per stream, as above and the default -- two PSDUs of equal length per frame, one decoder each --, and
+// JOINT: one PSDU through one encoder, stream-parsed over the two streams by the reference's 802.11n rule; one decoder job, one finish job and one row per frame.
 #include <vector>
 #include <algorithm>
 #include <string.h>
@@ -57,7 +59,12 @@ struct Ht40Lds {
 };
 }  // namespace
 
-__global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A)
+// JOINT = false: the per-stream coding (each stream its own decoder: two byte streams per frame).  JOINT = true (sora_ht40_set_coding): ONE
+// encoder's output went through the reference's stream parser (k_tx11n.hip: with s = max(1, N_BPSC / 2), coded bit kc of a symbol goes to stream (kc / s) & 1 as that
+// stream's bit (kc / 2s) s + kc % s), so the symbol's 2 N_CBPSS soft bytes leave as one merged stream: position q reads W.soft through one table that composes the
+// de-parser with the stream's de-interleaver.  Every addition sits under "if constexpr (JOINT)": the per-stream kernel is the instruction stream it was.
+template <bool JOINT>
+__device__ __forceinline__ void ht40_frame_body(const Ht40Args& A)
 {
     __shared__ Ht40Lds s_w[4];
     __shared__ uint8_t s_lut[6][256];
@@ -71,6 +78,17 @@ __global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A)
     const uint32_t* iq[2] = { A.iq0 + F.offset, A.iq1 + F.offset };
     const int nb = (int)F.nb, cfo = F.cfo;
     const int ncb = 108 * nb;
+    static_assert(sizeof(W.dtab) == 2 * 1296 && sizeof(W.soft[0]) == 656, "the merged table: 2 N_CBPSS <= 1296 entries, each an index into W.soft taken as one array");
+    [[maybe_unused]] uint16_t* const jtab = &W.dtab[0][0];                                    // JOINT: merged position q -> iss * 656 + (where the stream's coded bit sits in its symbol)
+    [[maybe_unused]] const uint8_t* const jsoft = &W.soft[0][0];
+    if constexpr (JOINT) {
+        const int sp = nb / 2 > 1 ? nb / 2 : 1;
+        for (int q = lane; q < 2 * ncb; q += 64) {
+            const int iss = (q / sp) & 1;
+            jtab[q] = (uint16_t)(iss * 656 + deint40_index(nb, iss, (q / (2 * sp)) * sp + q % sp));
+        }
+    }
+    else
     for (int k = lane; k < ncb; k += 64) { W.dtab[0][k] = (uint16_t)deint40_index(nb, 0, k); W.dtab[1][k] = (uint16_t)deint40_index(nb, 1, k); }
     int theta = 0;
     const Fft128TwPk twpk = fft128_twiddles_pk(A.T, lane & 31);
@@ -171,6 +189,11 @@ __global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A)
         }
         wave_lds_sync();
         // de-interleave both streams, each into its own byte stream (one decoder wave takes stream 0 in its low halves and stream 1 in its high halves)
+        if constexpr (JOINT) {
+            // ... or, one coding over both streams: the symbol's 2 N_CBPSS merged positions into the frame's one byte stream
+            for (int q = lane; q < 2 * ncb; q += 64) dst[(size_t)d * (2 * ncb) + q] = jsoft[jtab[q]];
+        }
+        else
         for (int g = lane; g < ncb; g += 64) {
             dst[(size_t)d * ncb + g] = W.soft[0][W.dtab[0][g]];
             dst[per_pad + (size_t)d * ncb + g] = W.soft[1][W.dtab[1][g]];
@@ -178,8 +201,12 @@ __global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A)
         wave_lds_sync();
     }
 }
+__global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A) { ht40_frame_body<false>(A); }
+__global__ void __launch_bounds__(256) k_ht40_frame_joint(Ht40Args A) { ht40_frame_body<true>(A); }
 
-__global__ void __launch_bounds__(256) k_ht40_finish(Ht40FinishArgs A)
+// PER: finish jobs (= rows) per frame: 2 in the per-stream coding, 1 in the joint one
+template <uint32_t PER>
+__device__ __forceinline__ void ht40_finish_body(const Ht40FinishArgs& A)
 {
     __shared__ uint32_t s_crc[256];
     __shared__ uint32_t s_z[6 * 8 * 16];
@@ -189,12 +216,14 @@ __global__ void __launch_bounds__(256) k_ht40_finish(Ht40FinishArgs A)
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = (int)(threadIdx.x >> 6);
     const uint32_t j = blockIdx.x * 4 + wv;
-    if (j >= (A.plan ? min(A.njobs, 2u * A.plan[0]) : A.njobs)) return;
+    if (j >= (A.plan ? min(A.njobs, PER * A.plan[0]) : A.njobs)) return;
     const Ht40Job J = A.jobs[j];
     uint32_t fcs;
-    const uint32_t verdict = finish_frame(A.T, A.vout + J.out_off, J.length, reinterpret_cast<uint8_t*>(s_bufs[wv]), A.mpdu + (size_t)J.row * 4096, s_crc, s_z, lane, fcs);
+    const uint32_t verdict = finish_frame<true>(A.T, A.vout + J.out_off, J.length, reinterpret_cast<uint8_t*>(s_bufs[wv]), A.mpdu + (size_t)J.row * 4096, s_crc, s_z, lane, fcs);
     if (lane == 0) { Rx11bRow r; r.end_sample = 0; r.rate_kbps = 0; r.length = J.length; r.crc32 = fcs; r.error_code = verdict; A.rows[J.row] = r; }
 }
+__global__ void __launch_bounds__(256) k_ht40_finish(Ht40FinishArgs A) { ht40_finish_body<2>(A); }
+__global__ void __launch_bounds__(256) k_ht40_finish_joint(Ht40FinishArgs A) { ht40_finish_body<1>(A); }
 
 // ---- raw-capture calls: what the front end found (k_scan_ht40: per capture a count and up to `mf` Ht40Found records in time order) -> the data
 // field's tables, on the device, so that the call is one uninterrupted chain of kernels (the first version read the records back and built the
@@ -202,12 +231,12 @@ __global__ void __launch_bounds__(256) k_ht40_finish(Ht40FinishArgs A)
 // code rate; five exclusive prefix sums over the captures; then every capture writes its frames' descriptors, the two decoder jobs of each
 // (neighbours in their code-rate list: one wave decodes both streams), the finish jobs and the rows' templates, in (capture, time) order.
 struct Ht40Geom { uint32_t nb, cr, nsym, per, per_pad; };
-__device__ __forceinline__ Ht40Geom ht40_geom(const Ht40Found& F)
+__device__ __forceinline__ Ht40Geom ht40_geom(const Ht40Found& F, uint32_t joint)
 {
     Ht40Geom G;
     G.nb = nbpsc11n(F.mcs); G.cr = code_rate11n(F.mcs);
-    const uint32_t nd = ht40_ndbps(G.nb, G.cr);
-    G.nsym = (16u + 8u * F.ht_len + 6u + nd - 1u) / nd;                          // sora_ht40_symbols(len, len, nb, cr)
+    const uint32_t nd = ht40_ndbps(G.nb, G.cr) << joint;                         // joint coding: one field over both streams
+    G.nsym = (16u + 8u * F.ht_len + 6u + nd - 1u) / nd;                          // sora_ht40_symbols(len, len, nb, cr) / sora_ht40_symbols_joint(len, nb, cr)
     G.per = G.nsym * 108u * G.nb; G.per_pad = (G.per + 31u) / 32u * 32u;
     return G;
 }
@@ -215,8 +244,12 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
         const Ht40Found* __restrict__ found,
                                                     uint32_t max_frames, uint64_t max_soft, uint32_t vout_stride,
                                                     Ht40Frame* __restrict__ frames, VitJob* __restrict__ jobs, uint32_t stride, uint32_t* __restrict__ njobs, Ht40Job* __restrict__ fjobs,
-                                                    sora_frame_result* __restrict__ tmpl, uint32_t* __restrict__ plan, uint32_t* __restrict__ evbase, uint32_t* __restrict__ evn)
+                                                    sora_frame_result* __restrict__ tmpl, uint32_t* __restrict__ plan, uint32_t* __restrict__ evbase, uint32_t* __restrict__ evn,
+                                                    uint32_t joint)
 {
+    // joint (0 / 1): the handle's coding.  Joint: one decoder job over the frame's 2 x per merged soft bytes, one finish job and one row per frame (evn = 1, rows and
+    // MPDU slots numbered by frame); a frame keeps the 2 x per_pad soft bytes of the per-stream layout, so the capacity rule is one.
+    const uint32_t jpf = joint ? 1u : 2u;
     // Besides the data field's tables: the call's EVENT table for sora_ht40_deliver_async, in (capture, time) order like sora_ht40_results_of -- event e has evn[e] rows (two for a
     // recorded frame, one for a header that failed), template rows tmpl[2 e + k], and evbase[e] = the row of the decoder's row table its rows start at (0xFFFFFFFF: no frame).
     __shared__ uint32_t s_v[6][1024];
@@ -233,7 +266,7 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
         for (uint32_t i = 0; i < n; i++) {
             const Ht40Found& F = found[(size_t)c * mf + i];
             if (F.error_code != 0) continue;
-            const Ht40Geom G = ht40_geom(F);
+            const Ht40Geom G = ht40_geom(F, joint);
             mine[0]++; mine[1] += 2u * G.per_pad; mine[2 + G.cr]++;
         }
 #pragma unroll
@@ -263,26 +296,25 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
                 tmpl[2u * e] = o; evbase[e] = 0xFFFFFFFFu; evn[e] = 1u;
                 continue;
             }
-            const Ht40Geom G = ht40_geom(F);
-            const uint32_t fi = at[0], soft_off = at[1], pos = 2u * at[2 + G.cr];
+            const Ht40Geom G = ht40_geom(F, joint);
+            const uint32_t fi = at[0], soft_off = at[1], pos = jpf * at[2 + G.cr];
             at[0]++; at[1] += 2u * G.per_pad; at[2 + G.cr]++;
-            evbase[e] = 2u * fi; evn[e] = 2u;
+            evbase[e] = jpf * fi; evn[e] = jpf;
             // (reported by wait / results: SORA_ERR_CAPACITY)
             if (fi >= max_frames || (uint64_t)soft_off + 2u * G.per_pad > max_soft || !(F.noise_var >= 0.0f)) { s_err = 1u; evn[e] = 0u; continue; }
             Ht40Frame H;
             H.offset = caps[c].offset + 2ull * F.a20 + 160ull;                   // HT-STF is 4 us = 160 samples @40 MHz; HT-LTF 1 follows
             // one HT-SIG LENGTH: each stream carries its own PSDU of that length
-            H.nsym = G.nsym; H.nb = G.nb; H.code_rate = G.cr; H.length[0] = H.length[1] = F.ht_len;
+            H.nsym = G.nsym; H.nb = G.nb; H.code_rate = G.cr; H.length[0] = F.ht_len; H.length[1] = joint ? 0u : F.ht_len;
             H.cfo = F.cfo / 2;                                                   // per 20 MHz sample -> per 40 MHz sample
             H.noise_var = F.noise_var; H.soft_off = soft_off; H.pad[0] = H.pad[1] = H.pad[2] = H.pad[3] = 0;
             frames[fi] = H;
-#pragma unroll
-            for (uint32_t k = 0; k < 2; k++) {
+            for (uint32_t k = 0; k < jpf; k++) {
                 VitJob J;
-                J.soft_off = soft_off + k * G.per_pad; J.soft_bits = 8; J.nsoft = G.per; J.length = F.ht_len; J.dec_off = 0;
-                    J.out_off = (2u * fi + k) * vout_stride; J.valid = 1; J.code_rate = G.cr;
+                J.soft_off = soft_off + k * G.per_pad; J.soft_bits = 8; J.nsoft = joint ? 2u * G.per : G.per; J.length = F.ht_len; J.dec_off = 0;
+                    J.out_off = (jpf * fi + k) * vout_stride; J.valid = 1; J.code_rate = G.cr;
                 jobs[(size_t)G.cr * stride + pos + k] = J;
-                fjobs[2u * fi + k] = Ht40Job{ J.out_off, F.ht_len, 2u * fi + k, 0u };
+                fjobs[jpf * fi + k] = Ht40Job{ J.out_off, F.ht_len, jpf * fi + k, 0u };
                 sora_frame_result o;
                 o.capture_id = caps[c].capture_id; o.start_sample = k; o.end_sample = F.end_sample; o.error_code = 0; o.rate_kbps = F.mcs;
                 o.length = 0; o.nsym = (uint16_t)G.nsym; o.crc32 = 0; o.cfo_est = 0; o.flags = tflag; o.mpdu_offset = 0;
@@ -300,7 +332,7 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
     if (t == 0) {
         const bool bad = s_err != 0;
         plan[0] = bad ? 0u : s_base[0]; plan[1] = s_base[0]; plan[2] = s_base[1]; plan[3] = s_err; plan[4] = bad ? 0u : s_base[5];
-        njobs[0] = bad ? 0u : 2u * s_base[2]; njobs[1] = bad ? 0u : 2u * s_base[3]; njobs[2] = bad ? 0u : 2u * s_base[4]; njobs[3] = 0;
+        njobs[0] = bad ? 0u : jpf * s_base[2]; njobs[1] = bad ? 0u : jpf * s_base[3]; njobs[2] = bad ? 0u : jpf * s_base[4]; njobs[3] = 0;
     }
 }
 
@@ -324,6 +356,7 @@ struct Ht40Slot : Call {       // the stream, ticket and completion state of the
     CapDesc* d_caps = nullptr; size_t caps_bytes = 0; Rx11bRow* d_scanrows = nullptr; size_t scanrows_bytes = 0;
     uint32_t* d_nfr = nullptr; size_t nfr_bytes = 0; Ht40Found* d_found = nullptr; size_t found_bytes = 0;
     bool capture_mode = false; uint32_t capture_mf = 0; std::vector<Ht40Event> events;
+    bool joint = false;         // the coding the call was issued in (sora_ht40_set_coding): one job and one row per frame
     uint32_t ncaps = 0;         // captures of a raw-capture call (sora_ht40_stream_consumed); 0 for a descriptor call
     // ... planned on the device (k_ht40_plan): the records come back asynchronously into page-locked memory and are turned into `events` when the call is collected
     uint32_t* d_plan = nullptr;
@@ -345,6 +378,7 @@ struct sora_ht40 {
     // trellis kernel (host_trellis.h): Lanes16 = k_viterbi16_11n (default: the handle keeps eight calls in flight), Lanes64 =
     // k_viterbi11n (64 lanes per stream pair; the faster one for a call alone) -- sora_ht40_set_trellis
     Trellis trellis = Trellis::Lanes16;
+    int coding = SORA_HT40_CODING_PER_STREAM;                                    // sora_ht40_set_coding
     // sora_ht40_set_stream_mode: the records belong to the handle, not to a slot; sized for max_frames streams when the mode is first enabled
     StreamRecords records{kRec11nWords};
 };
@@ -373,6 +407,17 @@ uint32_t sora_ht40_symbols(uint32_t length0, uint32_t length1, uint32_t n_bpsc, 
     if (!(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6) || code_rate > 2) return 0;
     const uint32_t L = length0 > length1 ? length0 : length1, nd = ht40_ndbps(n_bpsc, code_rate);
     return (16u + 8u * L + 6u + nd - 1) / nd;
+}
+
+uint32_t sora_ht40_symbols_joint(uint32_t length, uint32_t n_bpsc, uint32_t code_rate)
+{
+    if (!(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6) || code_rate > 2) return 0;
+    return ht40_symbols_joint(length, 2u * ht40_ndbps(n_bpsc, code_rate));       // one field over both streams: N_DBPS = 2 x 108 N_BPSC R
+}
+// data symbols of a described frame in the coding of its call
+static uint32_t ht40_frame_symbols(const sora_ht40_frame& f, bool joint)
+{
+    return joint ? sora_ht40_symbols_joint(f.length[0], f.n_bpsc, f.code_rate) : sora_ht40_symbols(f.length[0], f.length[1], f.n_bpsc, f.code_rate);
 }
 
 int sora_ht40_create(int device, uint32_t max_frames, uint64_t max_soft_values, sora_ht40_t** out)
@@ -432,6 +477,19 @@ int sora_ht40_set_stream_mode(sora_ht40_t* rx, int enable)
     if (enable >= 0) { const int rc = sora_ht40_synchronize(rx); if (rc) return rc; }
     return rx->records.set(enable, rx->device, rx->max_frames);
 }
+int sora_ht40_set_coding(sora_ht40_t* rx, int coding)
+{
+    if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_set_coding: null handle", 0);
+    const int old = rx->coding;
+    if (coding < 0) return old;
+    if (coding != SORA_HT40_CODING_PER_STREAM && coding != SORA_HT40_CODING_JOINT) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
+            "sora_ht40_set_coding: SORA_HT40_CODING_PER_STREAM (0) or SORA_HT40_CODING_JOINT (1)", 0);
+    { const int rc = sora_ht40_synchronize(rx); if (rc) return rc; }
+    HIPCHK(hipSetDevice(rx->device));
+    { const int rc = rx->records.zero(rx->max_frames); if (rc) return rc; }       // a frame's extent depends on the coding: every stream starts afresh
+    rx->coding = coding;
+    return old;
+}
 int sora_ht40_stream_consumed(sora_ht40_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps)
 {
     if (!rx || !h_consumed) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_stream_consumed: null argument", 0);
@@ -442,14 +500,14 @@ int sora_ht40_stream_consumed(sora_ht40_t* rx, int ticket, uint32_t* h_consumed,
 // nullptr: there are exactly nframes
 static int ht40_data_field(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0, const sora_complex16* d_iq1, uint32_t nframes, sora_complex16* d_weights, const uint32_t* plan)
 {
-    const uint32_t njobs = 2 * nframes;
+    const uint32_t njobs = S.joint ? nframes : 2 * nframes;
     Ht40Args A;
     A.iq0 = reinterpret_cast<const uint32_t*>(d_iq0); A.iq1 = reinterpret_cast<const uint32_t*>(d_iq1); A.frames = S.d_frames; A.nframes = nframes;
     A.T = rx->T; A.sincos = rx->sincos; A.atan = rx->atan; A.soft = S.d_soft; A.w_out = reinterpret_cast<uint32_t*>(d_weights); A.plan = plan;
-    hipLaunchKernelGGL(k_ht40_frame, dim3((nframes + 3) / 4), dim3(256), 0, S.stream, A);
+    hipLaunchKernelGGL(S.joint ? k_ht40_frame_joint : k_ht40_frame, dim3((nframes + 3) / 4), dim3(256), 0, S.stream, A);
     trellis_launch<192>(rx->trellis, trellis_lists(S.d_jobs, S.d_njobs, njobs, 2 * rx->max_frames), S.d_soft, S.d_vout, S.stream);
     Ht40FinishArgs Fi; Fi.jobs = S.d_fjobs; Fi.njobs = njobs; Fi.vout = S.d_vout; Fi.mpdu = S.d_mpdu; Fi.rows = S.d_rows; Fi.T = rx->T; Fi.plan = plan;
-    hipLaunchKernelGGL(k_ht40_finish, dim3((njobs + 3) / 4), dim3(256), 0, S.stream, Fi);
+    hipLaunchKernelGGL(S.joint ? k_ht40_finish_joint : k_ht40_finish, dim3((njobs + 3) / 4), dim3(256), 0, S.stream, Fi);
     HIPCHK(hipGetLastError());
     return SORA_OK;
 }
@@ -467,9 +525,13 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
     uint32_t nj[4] = { 0, 0, 0, 0 };
     uint64_t soft = 0;
     const size_t stride = 2 * (size_t)rx->max_frames;
+    const bool joint = S.joint;
+    const size_t jpf = joint ? 1 : 2;                                             // decoder jobs, finish jobs and rows per frame
     for (size_t i = 0; i < nframes; i++) {
         const sora_ht40_frame& s = frames[i];
-        const uint32_t nsym = sora_ht40_symbols(s.length[0], s.length[1], s.n_bpsc, s.code_rate);
+        if (joint && s.length[1] != 0) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
+                "sora_ht40_process_dev: in joint coding a frame carries one PSDU: length[1] must be 0", 0);
+        const uint32_t nsym = ht40_frame_symbols(s, joint);
         if (nsym == 0 || s.length[0] > 4000 || s.length[1] > 4000 || !(s.noise_var >= 0.0f)) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
                 "sora_ht40_process_dev: bad frame descriptor (n_bpsc 1/2/4/6, code_rate 0..2, PSDU <= 4000 bytes, noise_var >= 0)", 0);
         Ht40Frame& F = hf[i];
@@ -477,12 +539,12 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
             F.noise_var = s.noise_var;
         const uint64_t per = (uint64_t)nsym * 108 * s.n_bpsc;                       // soft values per stream
         F.soft_off = (uint32_t)soft;
-        for (int k = 0; k < 2; k++) {
-            // the two streams of a frame are neighbours in their list: one wave decodes both
+        for (size_t k = 0; k < jpf; k++) {
+            // the two streams of a frame are neighbours in their list: one wave decodes both (joint coding: one job over the frame's merged bytes; two frames share a wave)
             VitJob& J = hj[s.code_rate * stride + nj[s.code_rate]++];
-            J.soft_off = F.soft_off + (uint32_t)k * (uint32_t)((per + 31) / 32 * 32); J.soft_bits = 8; J.nsoft = (uint32_t)per; J.length = s.length[k];
-                J.dec_off = 0; J.out_off = (uint32_t)((2 * i + k) * kVoutStride); J.valid = 1; J.code_rate = s.code_rate;
-            fj[2 * i + k] = Ht40Job{ J.out_off, s.length[k], (uint32_t)(2 * i + k), 0 };
+            J.soft_off = F.soft_off + (uint32_t)k * (uint32_t)((per + 31) / 32 * 32); J.soft_bits = 8; J.nsoft = (uint32_t)(joint ? 2 * per : per); J.length = s.length[k];
+                J.dec_off = 0; J.out_off = (uint32_t)((jpf * i + k) * kVoutStride); J.valid = 1; J.code_rate = s.code_rate;
+            fj[jpf * i + k] = Ht40Job{ J.out_off, s.length[k], (uint32_t)(jpf * i + k), 0 };
         }
         soft += 2 * ((per + 31) / 32 * 32);                                         // bytes: one per soft value, both streams
         F.pad[0] = F.pad[1] = F.pad[2] = F.pad[3] = 0;
@@ -497,7 +559,7 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
     for (int r = 0; r < 3; r++)                                                   // (only the filled part of each code-rate list)
         if (nj[r]) HIPCHK(hipMemcpyAsync(S.d_jobs + r * stride, hj + r * stride, sizeof(VitJob) * nj[r], hipMemcpyHostToDevice, S.stream));
     HIPCHK(hipMemcpyAsync(S.d_njobs, nj_stage, 16, hipMemcpyHostToDevice, S.stream));
-    HIPCHK(hipMemcpyAsync(S.d_fjobs, fj, sizeof(Ht40Job) * 2 * nframes, hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemcpyAsync(S.d_fjobs, fj, sizeof(Ht40Job) * jpf * nframes, hipMemcpyHostToDevice, S.stream));
     return ht40_data_field(rx, S, d_iq0, d_iq1, (uint32_t)nframes, d_weights, nullptr);
 }
 
@@ -508,7 +570,7 @@ int sora_ht40_process_dev(sora_ht40_t* rx, const sora_complex16* d_iq0, const so
     rx->next = call_next(rx->slot, kHt40Slots);                                   // an unused slot, else a released call's, else the oldest call's
     Ht40Slot& S = rx->slot[rx->next];
     HIPCHK(hipStreamSynchronize(S.stream));                                     // the call that used this slot kHt40Slots calls ago
-    S.events.clear(); S.capture_mode = false; S.events_pending = false; S.plan_error = false; S.ncaps = 0;
+    S.events.clear(); S.capture_mode = false; S.events_pending = false; S.plan_error = false; S.ncaps = 0; S.joint = rx->coding == SORA_HT40_CODING_JOINT;
     return ht40_submit(rx, S, d_iq0, d_iq1, frames, nframes, d_weights);
 }
 
@@ -559,6 +621,7 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     for (size_t i = 0; i < ncaps; i++) { CapDesc& h = S.h_capsup[i]; h.offset = caps[i].offset; h.nsamples = caps[i].nsamples;
         h.capture_id = caps[i].capture_id; h.slot_base = 0; h.nslots = 0; }
     S.h_caps.assign(caps, caps + ncaps);
+    S.joint = rx->coding == SORA_HT40_CODING_JOINT;
     S.events.clear(); S.capture_mode = true; S.capture_mf = mf; S.ncaps = (uint32_t)ncaps; S.events_pending = true; S.plan_error = false; S.nframes = 0;
     S.bound_frames = (uint32_t)std::min<uint64_t>(nrows, rx->max_frames); S.bound_events = (uint32_t)nrows;
     rx->have_results = true; rx->last = rx->next;
@@ -570,10 +633,11 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     { const int rc = sora_internal_scan_ht40(reinterpret_cast<const uint32_t*>(d_iq0), reinterpret_cast<const uint32_t*>(d_iq1), S.d_caps, (uint32_t)ncaps, mf,
             S.d_scanrows, S.d_nfr, S.d_found,
                                              rx->T, rx->sincos, rx->atan, S.stream, rx->records.on ? rx->records.d_cont : nullptr,
-                                             rx->records.on ? rx->records.d_consumed : nullptr); if (rc) return rc; }
+                                             rx->records.on ? rx->records.d_consumed : nullptr, S.joint ? 1u : 0u); if (rc) return rc; }
     const size_t stride = 2 * (size_t)rx->max_frames;
     hipLaunchKernelGGL(k_ht40_plan, dim3(1), dim3(1024), 0, S.stream, (const CapDesc*)S.d_caps, (uint32_t)ncaps, mf, (const uint32_t*)S.d_nfr, (const Ht40Found*)S.d_found,
-                       rx->max_frames, (uint64_t)rx->max_soft, kVoutStride, S.d_frames, S.d_jobs, (uint32_t)stride, S.d_njobs, S.d_fjobs, S.d_evtmpl, S.d_plan, S.d_evbase, S.d_evn);
+                       rx->max_frames, (uint64_t)rx->max_soft, kVoutStride, S.d_frames, S.d_jobs, (uint32_t)stride, S.d_njobs, S.d_fjobs, S.d_evtmpl, S.d_plan, S.d_evbase, S.d_evn,
+                       S.joint ? 1u : 0u);
     HIPCHK(hipMemcpyAsync(S.h_nfr, S.d_nfr, 4 * ncaps, hipMemcpyDeviceToHost, S.stream));
     HIPCHK(hipMemcpyAsync(S.h_found, S.d_found, sizeof(Ht40Found) * nrows, hipMemcpyDeviceToHost, S.stream));
     HIPCHK(hipMemcpyAsync(S.h_plan, S.d_plan, 16, hipMemcpyDeviceToHost, S.stream));
@@ -615,25 +679,26 @@ static int ht40_slot_results(sora_ht40_t* rx, Ht40Slot& S, sora_frame_result* ou
         HIPCHK(hipSetDevice(rx->device));
         HIPCHK(hipStreamSynchronize(S.stream));
         { const int rc = ht40_collect_events(S); if (rc) return rc; }
-        const size_t nj = 2 * (size_t)S.nframes;
+        const size_t jpf = S.joint ? 1 : 2;                                       // rows per recorded frame
+        const size_t nj = jpf * (size_t)S.nframes;
         std::vector<Rx11bRow> rows(nj);
         if (nj) HIPCHK(hipMemcpy(rows.data(), S.d_rows, sizeof(Rx11bRow) * nj, hipMemcpyDeviceToHost));
         std::vector<uint8_t> bulk;
         if (h_mpdu && nj) { bulk.resize(nj * 4096); HIPCHK(hipMemcpy(bulk.data(), S.d_mpdu, bulk.size(), hipMemcpyDeviceToHost)); }
         size_t n = 0, moff = 0;
         for (const Ht40Event& E : S.events) {
-            for (int k = 0; k < (E.frame >= 0 ? 2 : 1); k++) {
+            for (int k = 0; k < (E.frame >= 0 ? (int)jpf : 1); k++) {
                 if (n >= max_out) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_results: output buffer too small", 0);
                 sora_frame_result& o = out[n++];
                 memset(&o, 0, sizeof(o));
                 o.capture_id = E.capture_id; o.end_sample = E.end_sample; o.error_code = E.error_code; o.flags = E.truncated ? SORA_ROW_TRUNCATED : 0;
                     o.mpdu_offset = (uint32_t)moff;
                 if (E.frame >= 0) {
-                    const Rx11bRow& r = rows[2 * (size_t)E.frame + k];
+                    const Rx11bRow& r = rows[jpf * (size_t)E.frame + k];
                     o.start_sample = (uint32_t)k; o.rate_kbps = E.mcs; o.nsym = (uint16_t)E.nsym; o.error_code = r.error_code; o.length = (uint16_t)r.length; o.crc32 = r.crc32;
                     if (h_mpdu) {
                         if (moff + r.length > mpdu_cap) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_results: MPDU buffer too small", 0);
-                        memcpy(h_mpdu + moff, bulk.data() + (2 * (size_t)E.frame + k) * 4096, r.length); moff += r.length;
+                        memcpy(h_mpdu + moff, bulk.data() + (jpf * (size_t)E.frame + k) * 4096, r.length); moff += r.length;
                     }
                 }
             }
@@ -644,8 +709,9 @@ static int ht40_slot_results(sora_ht40_t* rx, Ht40Slot& S, sora_frame_result* ou
     if (S.nframes == 0) return SORA_OK;
     HIPCHK(hipSetDevice(rx->device));
     HIPCHK(hipStreamSynchronize(S.stream));
-    const size_t nj = 2 * (size_t)S.nframes;
-    if (nj > max_out) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_results: two rows per frame are reported", 0);
+    const size_t jpf = S.joint ? 1 : 2;
+    const size_t nj = jpf * (size_t)S.nframes;
+    if (nj > max_out) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_results: two rows per frame are reported (one in joint coding)", 0);
     std::vector<Rx11bRow> rows(nj);
     HIPCHK(hipMemcpy(rows.data(), S.d_rows, sizeof(Rx11bRow) * nj, hipMemcpyDeviceToHost));
     std::vector<uint8_t> bulk;
@@ -654,9 +720,10 @@ static int ht40_slot_results(sora_ht40_t* rx, Ht40Slot& S, sora_frame_result* ou
     for (size_t j = 0; j < nj; j++) {
         sora_frame_result& o = out[j];
         memset(&o, 0, sizeof(o));
-        o.capture_id = S.h_frames[j / 2].frame_id; o.start_sample = (uint32_t)(j & 1);                  // start_sample carries the spatial stream
-        o.error_code = rows[j].error_code; o.length = (uint16_t)rows[j].length; o.crc32 = rows[j].crc32; o.rate_kbps = S.h_frames[j / 2].n_bpsc * 10 + S.h_frames[j / 2].code_rate;
-        o.nsym = (uint16_t)sora_ht40_symbols(S.h_frames[j / 2].length[0], S.h_frames[j / 2].length[1], S.h_frames[j / 2].n_bpsc, S.h_frames[j / 2].code_rate);
+        const sora_ht40_frame& f = S.h_frames[j / jpf];
+        o.capture_id = f.frame_id; o.start_sample = (uint32_t)(j % jpf);                               // start_sample carries the spatial stream (joint coding: 0)
+        o.error_code = rows[j].error_code; o.length = (uint16_t)rows[j].length; o.crc32 = rows[j].crc32; o.rate_kbps = f.n_bpsc * 10 + f.code_rate;
+        o.nsym = (uint16_t)ht40_frame_symbols(f, S.joint);
         o.mpdu_offset = (uint32_t)moff;
         if (h_mpdu) {
             if (moff + rows[j].length > mpdu_cap) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_results: MPDU buffer too small", 0);
@@ -705,22 +772,24 @@ int sora_ht40_deliver_async(sora_ht40_t* rx, int ticket, sora_frame_result* h_ro
     if (S->capture_mode) {
         // k_ht40_plan; the host knows only the bound ncaps x max_frames_per_capture.  The table is the one sora_ht40_results_of reports: a header that failed is a row, the
         // last row a full capture could hold carries SORA_ROW_TRUNCATED (round 4; before, only decoded frames were delivered).
+        // (joint coding: an event has one row; the table keeps its two-row pitch, so max_rows is the same bound)
         const int rc = sora_internal_dense_deliver(&S->dense, S->d_rows, S->d_evn, nullptr, nullptr, S->bound_events, 2, S->d_mpdu, S->stream,
                                                    h_rows, max_rows, h_counts, h_mpdu, mpdu_cap, S->d_evtmpl, S->d_plan + 4, S->d_evbase);
         if (rc != SORA_OK) return rc;
         HIPCHK(call_mark_delivered(*S));
         return SORA_OK;
     }
-    S->h_tmpl.resize(2 * (size_t)S->nframes);
+    const size_t jpf = S->joint ? 1 : 2;
+    S->h_tmpl.resize(jpf * (size_t)S->nframes);
     for (size_t j = 0; j < S->h_tmpl.size(); j++) {                             // (the same fields sora_ht40_results fills in on the host)
-        sora_frame_result& o = S->h_tmpl[j]; const sora_ht40_frame& f = S->h_frames[j / 2];
+        sora_frame_result& o = S->h_tmpl[j]; const sora_ht40_frame& f = S->h_frames[j / jpf];
         memset(&o, 0, sizeof(o));
-        o.capture_id = f.frame_id; o.start_sample = (uint32_t)(j & 1); o.rate_kbps = f.n_bpsc * 10 + f.code_rate;
-        o.nsym = (uint16_t)sora_ht40_symbols(f.length[0], f.length[1], f.n_bpsc, f.code_rate);
+        o.capture_id = f.frame_id; o.start_sample = (uint32_t)(j % jpf); o.rate_kbps = f.n_bpsc * 10 + f.code_rate;
+        o.nsym = (uint16_t)ht40_frame_symbols(f, S->joint);
     }
-    // two rows per frame, always: "captures" = frames, max_frames_per_capture = 2, no per-capture counts.  (The template is read by an
+    // two rows per frame, always (one in joint coding): "captures" = frames, max_frames_per_capture = 2 (1), no per-capture counts.  (The template is read by an
     // asynchronous copy: it lives in the slot until the slot's next call.)
-    const int rc = sora_internal_dense_deliver(&S->dense, S->d_rows, nullptr, nullptr, S->h_tmpl.data(), S->nframes, 2, S->d_mpdu, S->stream,
+    const int rc = sora_internal_dense_deliver(&S->dense, S->d_rows, nullptr, nullptr, S->h_tmpl.data(), S->nframes, (uint32_t)jpf, S->d_mpdu, S->stream,
                                                h_rows, max_rows, h_counts, h_mpdu, mpdu_cap);
     if (rc != SORA_OK) return rc;
     HIPCHK(call_mark_delivered(*S));
@@ -736,14 +805,15 @@ int sora_ht40_soft_of(sora_ht40_t* rx, int ticket, uint32_t frame, uint32_t stre
     Ht40Slot* S = call_find(rx->slot, kHt40Slots, ticket);
     if (!S) return call_stale("sora_ht40_soft_of");
     if (S->capture_mode) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_soft_of: descriptor calls (sora_ht40_process_dev) only", 0);
-    if (frame >= S->nframes || stream > 1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_soft_of: no such frame / stream in this call", 0);
+    if (frame >= S->nframes || stream > (S->joint ? 0u : 1u)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_soft_of: no such frame / stream in this call", 0);
     uint64_t off = 0, per = 0;
     for (uint32_t i = 0; i <= frame; i++) {
         const sora_ht40_frame& f = S->h_frames[i];
-        per = (uint64_t)sora_ht40_symbols(f.length[0], f.length[1], f.n_bpsc, f.code_rate) * 108 * f.n_bpsc;
+        per = (uint64_t)ht40_frame_symbols(f, S->joint) * 108 * f.n_bpsc;
         if (i < frame) off += 2 * ((per + 31) / 32 * 32);
     }
     off += stream * ((per + 31) / 32 * 32);
+    if (S->joint) per *= 2;                                                      // the frame's merged bytes: both streams' values as one stream
     *nsoft = (size_t)per;
     if (per > cap) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_soft_of: output buffer too small", 0);
     HIPCHK(hipSetDevice(rx->device));

@@ -88,6 +88,7 @@ struct Scan11nArgs {
     uint32_t  nrows;
     // sora_rx11n_set_mcs_max: the highest MCS the SIG parser accepts (10 = PHY_11n.hpp:497), and the handle's bytes per symbol slot (soft values / decoded bytes)
     uint32_t  mcs_max, soft_per_slot, out_per_slot;
+    uint32_t  joint;               // HT40 only: 1 = the handle's coding is the joint one (sora_ht40_set_coding): a frame's N_DBPS spans both streams
 };
 // A symbol slot of the 802.11n handle: kSoftPerSlot / kOutPerSlot (rx_types.h) while the gate stands at MCS 10 (208 soft values, 19.5 decoded bytes per symbol at
 // most); with the gate raised a symbol brings up to 624 soft values and 58.5 decoded bytes (MCS 14)
@@ -441,7 +442,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
         else if (HT40 && decoded && !at_end) {
             // HT-STF at a, HT-LTF 1 / 2 at a + 80 / a + 160, data symbol d at a + 240 + 80 d (20 MHz indices; 4 us symbols).  The frame is
             // recorded when all of it lies inside the capture; a frame the capture cuts off raises no event (as the 20 MHz graph behaves).
-            const uint32_t ndbps = ht40_ndbps(nbpsc11n(mcs), code_rate);
+            const uint32_t ndbps = ht40_ndbps(nbpsc11n(mcs), code_rate) << A.joint;
             const uint32_t nsym = (16u + 8u * ht_len + 6u + ndbps - 1u) / ndbps;
             nproc = nsym;
             if (a + 240 + 80 * nsym <= n_real) { event = true; queue = true; last_burst_end = a + 240 + 80 * nsym; }
@@ -538,13 +539,14 @@ __global__ void __launch_bounds__(256) k_scan_ht40_stream(Scan11nArgs A, Ht40Fou
 
 }  // namespace sora
 int sora_internal_scan_ht40(const uint32_t* iq0, const uint32_t* iq1, const sora::CapDesc* d_caps, uint32_t ncaps, uint32_t max_frames, sora::Rx11bRow* d_rows, uint32_t* d_nframes,
-                            sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st, uint32_t* d_cont, uint32_t* d_consumed)
+                            sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st, uint32_t* d_cont, uint32_t* d_consumed,
+                            uint32_t joint)
 {
     using namespace sora;
     Scan11nArgs S{};
     S.iq0 = iq0; S.iq1 = iq1; S.caps = d_caps; S.ncaps = ncaps; S.max_frames = max_frames; S.rows = d_rows; S.nframes = d_nframes; S.T = T; S.sincos = sincos; S.atan = atan;
     S.frames = nullptr; S.jobs = nullptr; S.njobs = nullptr; S.nrows = ncaps * max_frames;
-    S.mcs_max = 14; S.soft_per_slot = 0; S.out_per_slot = 0;                     // (the HT40 form has its own gate and queues no 20 MHz data field)
+    S.mcs_max = 14; S.soft_per_slot = 0; S.out_per_slot = 0; S.joint = joint;                     // (the HT40 form has its own gate and queues no 20 MHz data field)
     if (d_cont) hipLaunchKernelGGL(k_scan_ht40_stream, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found, d_cont, d_consumed);
     else hipLaunchKernelGGL(k_scan_ht40, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found);
     const hipError_t e = hipGetLastError();
@@ -934,7 +936,7 @@ int sora_rx11n_process_dev(sora_rx11n_t* rx, const sora_complex16* d_iq0, const 
     Scan11nArgs S;
     S.iq0 = A.iq0; S.iq1 = A.iq1; S.caps = P->d_caps; S.ncaps = (uint32_t)ncaps; S.max_frames = A.max_frames; S.rows = P->d_rows; S.nframes = P->d_nframes;
     S.T = rx->T; S.sincos = rx->sincos; S.atan = rx->atan; S.frames = P->d_frames; S.jobs = P->d_jobs; S.njobs = P->d_njobs; S.nrows = nrows;
-    S.mcs_max = (uint32_t)rx->mcs_max; S.soft_per_slot = rx->soft_per_slot; S.out_per_slot = rx->out_per_slot;
+    S.mcs_max = (uint32_t)rx->mcs_max; S.soft_per_slot = rx->soft_per_slot; S.out_per_slot = rx->out_per_slot; S.joint = 0;
     if (rx->records.on) hipLaunchKernelGGL(k_scan11n_stream, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S, rx->records.d_cont, rx->records.d_consumed);
     else hipLaunchKernelGGL(k_scan11n, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S);
     Frame11nArgs F;

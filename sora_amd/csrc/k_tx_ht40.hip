@@ -15,6 +15,13 @@
 // LDS layout: the symbol buffers are swizzled (fft128_swz, dev_arith.h) so that no stage of the IFFT, the 16-byte terminal stage and the
 // emission included, meets a bank conflict; a stream's B generator words lie 16 banks from its A words (kGen = 16 mod 32), so the at most
 // 17 + 17 consecutive words a symbol's bit gather reads overlap in at most one bank.
+//
+// The JOINT coding (k_tx_ht40_joint, sora_hip_tx_ht40_joint) is the same frame with ONE PSDU: one field (SERVICE + PSDU + tail + pad up to
+// N_SYM x N_DBPS bits, N_DBPS = 2 x 108 N_BPSC R), one FCS, one scrambler pass (one seed, default 0x5D), one K = 7 encoder and puncturing, then the reference's stream
+// parser (k_tx11n.hip: with s = max(1, N_BPSC / 2), coded bit kc of a symbol goes to stream (kc / s) & 1 as that stream's bit (kc / 2s) s + kc % s); from there each
+// stream's interleaver, mapper and carrier plan are the ones above.  In the kernel the parser is composed with the stream's inverse interleaver in s_inv, so the
+// symbol loop is the per-stream one reading one pair of generator-word arrays.  LDS: the field reaches 32832 bits (MCS 13, LENGTH 4000) = 1026 generator words per
+// output -- inside one stream's kGen = 1040 -- and 4108 field bytes, more than one stream's kBytes: the two streams' byte arrays are used as one.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "dev_tx.h"
@@ -29,6 +36,7 @@ constexpr int kAmp = kTxHt40Amp;            // A: an LTF / SIG carrier
 constexpr int kStf = 17053;                 // rint(A sqrt(13 / 12))
 constexpr int kPilot = 12288;               // 2 d(1)
 static_assert(kGen % 32 == 16 && kGen * 32 >= 32507 && kBytes >= 4 * 1016 + 4, "LDS plan");
+static_assert(kGen >= 1026 && 2 * kBytes >= 4 * 1026 + 4, "LDS plan, joint coding: 32832 field bits = 1026 generator words, 4108 field bytes in the two streams' arrays");
 __device__ __forceinline__ int level40(int nb) { return nb <= 2 ? 6144 : nb == 4 ? 4000 : 2214; }   // rint(A LEVEL / 128), LEVEL = 48, 48, 31.25, 17.3
 __device__ __forceinline__ uint32_t pk16(int re, int im) { return (uint32_t)(uint16_t)re | ((uint32_t)(uint16_t)im << 16); }
 static __constant__ int8_t kLLtf[53] = {    // L-LTF, carriers -26..26
@@ -75,7 +83,8 @@ __global__ void __launch_bounds__(128) k_tx_ht40_preamble(uint32_t* tab, Tables 
     }
 }
 
-__global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
+template <bool JOINT>
+__device__ __forceinline__ void tx_ht40_body(const TxHt40Args& A)
 {
     __shared__ alignas(16) uint8_t s_data[2][kBytes];
     // generator outputs A (133) / B (171) of each stream's data field, bit i of the stream = bit i & 31 of word i >> 5
@@ -90,16 +99,22 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
     const Tables& T = A.T;
     const uint32_t L = A.len[f], mcs = A.mcs[f];
     TxHt40Plan P;
-    if (!tx_ht40_plan(L, mcs, P)) return;                                        // a frame that is not accepted: nothing is written
+    if (!(JOINT ? tx_ht40_plan_joint(L, mcs, P) : tx_ht40_plan(L, mcs, P))) return;   // a frame that is not accepted: nothing is written
     const int nb = P.nb, nd = P.ndbps;
     const uint32_t nsym = P.nsym;
-    const uint32_t nw = (nsym * (uint32_t)nd + 31) / 32;                         // generator words the data symbols read, per stream
+    const uint32_t nw = (nsym * (uint32_t)nd + 31) / 32;                         // generator words the data symbols read, per stream (joint: of the one field)
+    [[maybe_unused]] uint8_t* const jdata = &s_data[0][0];                       // joint: the one field, over both streams' byte arrays
     uint32_t* const out0 = A.out0 + A.out_off[f];
     uint32_t* const out1 = A.out1 + A.out_off[f];
 
     s_crc[tid] = T.crc[tid];
     for (int i = tid; i < 6 * 8 * 16; i += 256) s_z[i] = T.crcz[i];
     // per stream: SERVICE(2) + MPDU + FCS(4) + tail + pad, zero beyond
+    if constexpr (JOINT) {
+        const uint8_t* mp = A.mpdu + A.off[f];
+        for (uint32_t i = tid; i < 4 * nw + 4; i += 256) jdata[i] = (i >= 2 && i < 2 + L) ? mp[i - 2] : (uint8_t)0;
+    }
+    else
 #pragma unroll
     for (int st = 0; st < 2; st++) {
         const uint8_t* mp = A.mpdu + A.off[2 * f + st];
@@ -107,8 +122,17 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
     }
     __syncthreads();
     // FCS of both MPDUs: stream tid >> 7, two waves each
+    if constexpr (JOINT) { if (tid < 128) tx_fcs_waves<2>(jdata + 2, L, s_crc, s_z, tid, s_crcw); }
+    else
     tx_fcs_waves<2>(s_data[tid >> 7] + 2, L, s_crc, s_z, tid & 127, s_crcw + 2 * (tid >> 7));
     __syncthreads();
+    if constexpr (JOINT) {
+        if (tid == 0) {
+            const uint32_t fcs = tx_fcs_join<2>(s_z, s_crcw);
+            for (int k = 0; k < 4; k++) jdata[2 + L + k] = (uint8_t)(fcs >> (8 * k));
+        }
+    }
+    else
     if (tid < 2) {
         const uint32_t fcs = tx_fcs_join<2>(s_z, s_crcw + 2 * tid);
         for (int k = 0; k < 4; k++) s_data[tid][2 + L + k] = (uint8_t)(fcs >> (8 * k));
@@ -116,6 +140,11 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
     __syncthreads();
     // scrambler: x[n] = x[n-4] ^ x[n-7], seed bit i = x[-1-i] (py_ht40.scramble_seq); the phase tables keep the register the other way
     // round.  Everything up to the last symbol's last bit is scrambled, pad included; the six tail bits are forced to zero afterwards.
+    if constexpr (JOINT) {
+        const unsigned seed = A.seed ? A.seed[f] : 0x5Du;
+        tx_scramble(jdata, (nsym * (uint32_t)nd + 7) / 8, 2 + L + 4, T.scr_phase[brev7(seed & 0x7Fu)], T, tid);
+    }
+    else
 #pragma unroll
     for (int st = 0; st < 2; st++) {
         const unsigned seed = A.seed ? A.seed[2 * f + st] : (st ? 0x2Bu : 0x5Du);
@@ -123,12 +152,26 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
     }
     tx_copy_fixed_fields(A.preamble, out0, out1, tid);
     __syncthreads();
-    // the K = 7 encoder, each stream's field on its own
+    // the K = 7 encoder, each stream's field on its own (joint: the one field into stream 0's generator words)
+    if constexpr (JOINT) {
+        for (uint32_t w = tid; w < nw; w += 256) tx_encode_word(reinterpret_cast<const uint32_t*>(jdata), w, 0xFFFFFFFFu, s_gab[0][0][w], s_gab[0][1][w]);
+    }
+    else
     for (uint32_t i = tid; i < 2 * nw; i += 256) {
         const int st = i >= nw;
         const uint32_t w = st ? i - nw : i;
         tx_encode_word(reinterpret_cast<const uint32_t*>(s_data[st]), w, 0xFFFFFFFFu, s_gab[st][0][w], s_gab[st][1][w]);
     }
+    if constexpr (JOINT) {
+        // the stream parser composed with the inverse interleaver: bit k of stream iss is coded bit (k / s) 2s + iss s + k % s of the symbol
+        const int sp = nb / 2 > 1 ? nb / 2 : 1;
+        for (int k = tid; k < 108 * nb; k += 256) {
+            const int kc = (k / sp) * 2 * sp + k % sp;
+            s_inv[0][deint40_index(nb, 0, k)] = (uint16_t)kc;
+            s_inv[1][deint40_index(nb, 1, k)] = (uint16_t)(kc + sp);
+        }
+    }
+    else
     for (int k = tid; k < 108 * nb; k += 256) {
         s_inv[0][deint40_index(nb, 0, k)] = (uint16_t)k;
         s_inv[1][deint40_index(nb, 1, k)] = (uint16_t)k;
@@ -180,7 +223,7 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
             }
     }
     const int d = level40(nb), lvl0 = -((1 << M) - 1) * d, d2 = 2 * d;
-    const uint32_t* const gab = &s_gab[iss][0][0];
+    const uint32_t* const gab = &s_gab[JOINT ? 0 : iss][0][0];
     uint32_t* const out = iss ? out1 : out0;
     for (uint32_t s = (uint32_t)(g >> 1); s < nsym; s += 4) {                    // (a wave's two groups share their symbol: the trip count is the wave's)
         const uint32_t ibase = s * (uint32_t)nd;
@@ -204,5 +247,7 @@ __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A)
         wave_lds_sync();
     }
 }
+__global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A) { tx_ht40_body<false>(A); }
+__global__ void __launch_bounds__(256) k_tx_ht40_joint(TxHt40Args A) { tx_ht40_body<true>(A); }
 
 }  // namespace sora

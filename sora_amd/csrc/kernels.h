@@ -186,7 +186,7 @@ constexpr uint32_t kTx11nPreamble = 1120;                // samples per chain of
 __global__ void k_tx11n(Tx11nArgs A);
 
 // ---- 40 MHz HT 2x2 transmitter (k_tx_ht40.hip)
-struct TxHt40Args {            // sora_hip_tx_ht40
+struct TxHt40Args {            // sora_hip_tx_ht40; sora_hip_tx_ht40_joint: ONE MPDU and one seed per frame -- off[nframes], seed[nframes] (nullptr: 0x5D)
     const uint8_t*  mpdu;      // MPDUs without FCS: stream s of frame f at mpdu + off[2 f + s]
     const uint32_t* off;       // [2 nframes]
     const uint32_t* len;       // [nframes] bytes without FCS, the same for both streams (HT LENGTH = len + 4)
@@ -209,10 +209,23 @@ __host__ __device__ inline bool tx_ht40_plan(uint32_t len, uint32_t mcs, TxHt40P
     P.nsym = (16u + 8u * (len + 4u) + 6u + (uint32_t)P.ndbps - 1u) / (uint32_t)P.ndbps;
     return true;
 }
+// The joint coding (sora_hip_tx_ht40_joint): ONE PSDU through one scrambler and one encoder, stream-parsed over the two streams, so a
+// symbol carries N_DBPS = 2 x 108 N_BPSC R data bits: N_SYM = sora_ht40_symbols_joint(len + 4, nb, cr)
+__host__ __device__ inline uint32_t ht40_symbols_joint(uint32_t length, uint32_t ndbps_joint) { return (16u + 8u * length + 6u + ndbps_joint - 1u) / ndbps_joint; }
+__host__ __device__ inline bool tx_ht40_plan_joint(uint32_t len, uint32_t mcs, TxHt40Plan& P)
+{
+    if (len < 1 || len > 3996) return false;             // HT LENGTH <= 4000, the receiver's limit
+    int dbpc2;
+    if (!tx_ht_mcs(mcs, P.nb, P.cr, dbpc2)) return false;
+    P.ndbps = 108 * dbpc2;                               // 108 data carriers on each of the two streams
+    P.nsym = ht40_symbols_joint(len + 4u, (uint32_t)P.ndbps);
+    return true;
+}
 constexpr uint32_t kTxHt40Preamble = 1120;               // samples per chain of the table: L-STF + L-LTF + HT-STF + 2 HT-LTF
 constexpr int kTxHt40Amp = 16384;                        // A: the bin value of an LTF / SIG carrier (tests/tx_ht40_model.py)
 __global__ void k_tx_ht40_preamble(uint32_t* tab, Tables T);
 __global__ void k_tx_ht40(TxHt40Args A);
+__global__ void k_tx_ht40_joint(TxHt40Args A);
 
 // ---- 802.11b transmitter (k_tx11b.hip)
 struct Tx11bArgs {             // sora_hip_tx11b
@@ -289,9 +302,10 @@ struct Ht40Found {
 }  // namespace sora
 
 // d_cont / d_consumed: the streams' continuation records [ncaps][kRec11nWords] and resume points [ncaps] (k_scan_ht40_stream); null = k_scan_ht40
+// joint: 1 = a frame's extent follows the joint coding's N_SYM (sora_ht40_set_coding)
 int sora_internal_scan_ht40(const uint32_t* iq0, const uint32_t* iq1, const sora::CapDesc* d_caps, uint32_t ncaps, uint32_t max_frames, sora::Rx11bRow* d_rows, uint32_t* d_nframes,
                             sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st,
-                            uint32_t* d_cont = nullptr, uint32_t* d_consumed = nullptr);
+                            uint32_t* d_cont = nullptr, uint32_t* d_consumed = nullptr, uint32_t joint = 0);
 
 // k_deliver.hip: dense rows + MPDUs of a call of the Rx11bRow-table handles into page-locked host memory, behind the call's kernels
 struct DenseStage {                  // per slot / pipeline (grow-only device staging)

@@ -1815,11 +1815,20 @@ size_t sora_hip_tx_ht40_samples(uint32_t mpdu_len_nofcs, uint32_t mcs)
     return 1280 + 160 * (2 + (size_t)P.nsym);
 }
 
-int sora_hip_tx_ht40(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
-                     size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
+size_t sora_hip_tx_ht40_joint_samples(uint32_t mpdu_len_nofcs, uint32_t mcs)
+{
+    TxHt40Plan P;
+    if (!tx_ht40_plan_joint(mpdu_len_nofcs, mcs, P)) return 0;
+    return 1280 + 160 * (2 + (size_t)P.nsym);
+}
+
+// both codings: the per-stream one (two MPDUs and two seeds per frame) and the joint one (one of each)
+static int tx_ht40_launch(bool joint, const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
+                          size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
 {
     if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_mpdu || !d_off || !d_len || !d_mcs || !d_out0 || !d_out1 || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_tx_ht40: null pointer");
+    if (!d_mpdu || !d_off || !d_len || !d_mcs || !d_out0 || !d_out1 || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, joint ? "sora_hip_tx_ht40_joint: null pointer" :
+            "sora_hip_tx_ht40: null pointer");
     if (nframes == 0) return SORA_OK;
     DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     hipStream_t st = (hipStream_t)stream;
@@ -1841,9 +1850,19 @@ int sora_hip_tx_ht40(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_
     A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.mcs = d_mcs; A.seed = d_seed;
     A.out0 = reinterpret_cast<uint32_t*>(d_out0); A.out1 = reinterpret_cast<uint32_t*>(d_out1); A.out_off = d_out_off;
     A.preamble = D->tx_ht40_preamble; A.T = D->T;
-    hipLaunchKernelGGL(k_tx_ht40, dim3((unsigned)nframes), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(joint ? k_tx_ht40_joint : k_tx_ht40, dim3((unsigned)nframes), dim3(256), 0, st, A);
     HIPCHK(hipGetLastError());
     return SORA_OK;
+}
+int sora_hip_tx_ht40(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
+                     size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
+{
+    return tx_ht40_launch(false, d_mpdu, d_off, d_len, d_mcs, d_seed, nframes, d_out0, d_out1, d_out_off, stream);
+}
+int sora_hip_tx_ht40_joint(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
+                           size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
+{
+    return tx_ht40_launch(true, d_mpdu, d_off, d_len, d_mcs, d_seed, nframes, d_out0, d_out1, d_out_off, stream);
 }
 
 // ---- 802.11b transmitter
