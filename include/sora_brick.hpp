@@ -322,6 +322,160 @@ struct THip11nMimoComp : THipStage<sora_complex16, 128 * N, sora_complex16, 128 
         : THipStage<sora_complex16, 128 * N, sora_complex16, 128 * N, CallMimoComp11n, T_CTX, T_NEXT>(ctx, next, d_out, CallMimoComp11n{ d_hinv, N }, stream) {}
 };
 
+// ------------------------------------------------------------------------------------------------
+// The bricks of the 802.11a modulation graph (kernel/bb/demod11/fb11amod_config.hpp:74-109), each where its SSE brick sits.  Port TYPEs as in the reference, one burst =
+// N symbols (the byte-wide bricks: the bytes of N symbols, a whole number of the brick's own bursts).  The stateless ones are THipStage; the scrambler, the encoder and
+// the pilot brick keep their frame state from Process to Process and clear it in Reset, as the bricks do.  Their frame tables are device words the caller provides.
+
+// T11aSc (scramble.hpp:170-261): IPORT uchar x NBYTES -> OPORT uchar x NBYTES.  CF_ScramblerSeed = SetSeed, CF_ScramblerControl = SetTail: the byte of the frame (counted
+// from the last Reset) that goes through TAIL_SCRAMBLE, every other byte DO_SCRAMBLE.  The register is kept on the host: a byte's mask is a function of the register and
+// the byte's index alone, so it is advanced without looking at the data.  d_tab: 16 bytes of device memory.
+template <size_t NBYTES, class T_CTX, class T_NEXT>
+class THip11aSc : public HipFilter<T_CTX, T_NEXT> {
+public:
+    using iport_traits = port_traits<uint8_t, NBYTES>;
+    using oport_traits = port_traits<uint8_t, NBYTES>;
+    static constexpr uint32_t kNoTail = 0xFFFFFFFFu;
+    THip11aSc(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* d_tab, uint8_t seed = 0xFF, void* stream = nullptr)
+        : HipFilter<T_CTX, T_NEXT>(ctx, next, stream), opin_(d_out), d_tab_(static_cast<uint32_t*>(d_tab)), seed_(seed), reg_(seed) {}
+    void SetSeed(uint8_t seed) { seed_ = seed; }
+    void SetTail(uint32_t byte_of_frame) { tail_ = byte_of_frame; }
+    void Reset() { reg_ = seed_; done_ = 0; HipFilter<T_CTX, T_NEXT>::Reset(); }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            uint8_t* out = opin_.append();
+            const uint32_t tail = (tail_ != kNoTail && tail_ >= done_ && tail_ - done_ < NBYTES) ? tail_ - done_ : kNoTail;
+            const uint32_t tab[4] = { 0u, (uint32_t)NBYTES, tail, (uint32_t)reg_ };          // off, len, tail, seed (its low byte)
+            if (sora_hip_memcpy_h2d(d_tab_, tab, sizeof(tab)) != SORA_OK) return this->raise(SORA_ERR_HARDWARE_FAILED);
+            if (!this->raise(sora_hip_scramble11a(ipin.peek(), out, d_tab_, d_tab_ + 1, d_tab_ + 2, reinterpret_cast<const uint8_t*>(d_tab_ + 3), 1, NBYTES, this->stream_)))
+                return false;
+            for (size_t i = 0; i < NBYTES % 127 + 127; i++) reg_ = step(reg_);                 // (the 7-bit state has period 127 in byte steps)
+            done_ += (uint32_t)NBYTES;
+            ipin.pop();
+            if (this->next_ && !this->next_->Process(opin_)) return false;
+        }
+        return true;
+    }
+    DevicePin<uint8_t, NBYTES>& opin() { return opin_; }
+private:
+    static uint8_t step(uint8_t reg)                                                           // m_Reg = m_lut[m_Reg >> 1] (scramble.hpp:192-201)
+    {
+        uint8_t x = (uint8_t)((reg >> 1) << 1);
+        for (int k = 0; k < 8; k++) { const uint8_t o1 = ((x >> 1) ^ (x >> 4)) & 1; x = (uint8_t)((x >> 1) | (o1 << 7)); }
+        return x;
+    }
+    DevicePin<uint8_t, NBYTES> opin_; uint32_t* d_tab_; uint8_t seed_, reg_; uint32_t tail_ = kNoTail, done_ = 0;
+};
+
+// TConvEncode_12 / _23 / _34 (conv_enc.hpp:18-330), CR = SORA_CR_12 / _23 / _34: IPORT uchar x NIN (whole bursts of 1 / 2 / 3 bytes) -> OPORT uchar x NIN (CR + 2) / (CR + 1).
+// The stage starts every call from register 0; the adapter carries m_reg by encoding each burst behind the previous burst's last 1 / 2 / 3 bytes (zeros after Reset) and
+// handing on what follows their output.  d_work: kWorkBytes of device memory, 16-byte aligned, the adapter's own (it holds the output pin's buffer).
+template <int CR, size_t NIN, class T_CTX, class T_NEXT>
+class THipConvEncode : public HipFilter<T_CTX, T_NEXT> {
+    static constexpr size_t BIN = CR + 1, BOUT = CR + 2;
+    static_assert(CR >= 0 && CR <= 2 && NIN % BIN == 0 && NIN >= BIN, "whole bursts of the brick");
+public:
+    static constexpr size_t NOUT = NIN / BIN * BOUT;
+    static constexpr size_t kInAt = 16, kOutAt = 16 + (BIN + NIN + 15) / 16 * 16 + 16 - BOUT, kWorkBytes = kOutAt + BOUT + NOUT;
+    using iport_traits = port_traits<uint8_t, NIN>;
+    using oport_traits = port_traits<uint8_t, NOUT>;
+    THipConvEncode(T_CTX& ctx, T_NEXT* next, uint8_t* d_work, void* stream = nullptr)
+        : HipFilter<T_CTX, T_NEXT>(ctx, next, stream), w_(d_work), opin_(d_work + kOutAt + BOUT) {}
+    void Reset() { fresh_ = true; HipFilter<T_CTX, T_NEXT>::Reset(); }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            if (fresh_) {                                                                          // m_reg = 0, and the tables of the call: in_off, len, out_off
+                const uint32_t tab[4] = { (uint32_t)kInAt, (uint32_t)(BIN + NIN), (uint32_t)kOutAt, 0u };   // (word 3: BIN <= 3 zero bytes of history)
+                if (sora_hip_stream_synchronize(this->stream_) != SORA_OK || sora_hip_memcpy_h2d(w_, tab, sizeof(tab)) != SORA_OK ||
+                    sora_hip_memcpy_h2d(w_ + kInAt, tab + 3, BIN) != SORA_OK) return this->raise(SORA_ERR_HARDWARE_FAILED);
+                fresh_ = false;
+            }
+            const uint32_t* t = reinterpret_cast<const uint32_t*>(w_);
+            opin_.append();
+            if (sora_hip_memcpy_d2d(w_ + kInAt + BIN, ipin.peek(), NIN, this->stream_) != SORA_OK) return this->raise(SORA_ERR_HARDWARE_FAILED);
+            if (!this->raise(sora_hip_conv_encode11a(w_, t, t + 1, CR, w_, t + 2, 1, BIN + NIN, this->stream_))) return false;
+            if (sora_hip_memcpy_d2d(w_ + kInAt, w_ + kInAt + NIN, BIN, this->stream_) != SORA_OK) return this->raise(SORA_ERR_HARDWARE_FAILED);
+            ipin.pop();
+            if (this->next_ && !this->next_->Process(opin_)) return false;
+        }
+        return true;
+    }
+    DevicePin<uint8_t, NOUT>& opin() { return opin_; }
+private:
+    uint8_t* w_; DevicePin<uint8_t, NOUT> opin_; bool fresh_ = true;
+};
+
+// T11aInterleave{BPSK,QPSK,QAM16,QAM64} (interleave.hpp:16-114): IPORT uchar x 6 N_BPSC -> OPORT uchar x 6 N_BPSC, N symbols per burst
+struct CallInterleave11a { int nb; size_t n; int operator()(const uint8_t* in, uint8_t* out, void* st) const { return sora_hip_interleave11a(in, out, nb, n, st); } };
+template <int N_BPSC, size_t N, class T_CTX, class T_NEXT>
+struct THip11aInterleave : THipStage<uint8_t, 6 * N_BPSC * N, uint8_t, 6 * N_BPSC * N, CallInterleave11a, T_CTX, T_NEXT> {
+    THip11aInterleave(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* stream = nullptr)
+        : THipStage<uint8_t, 6 * N_BPSC * N, uint8_t, 6 * N_BPSC * N, CallInterleave11a, T_CTX, T_NEXT>(ctx, next, d_out, CallInterleave11a{ N_BPSC, N }, stream) {}
+};
+// TMap11a{BPSK,QPSK,QAM16,QAM64}<MOD> (mapper11a.hpp:8-300): IPORT uchar x 6 N_BPSC -> OPORT COMPLEX16 x 48; mod = the brick's MOD (0: the 802.11a amplitude)
+struct CallMap11a { int nb, mod; size_t n; int operator()(const uint8_t* in, sora_complex16* out, void* st) const { return sora_hip_map11a(in, out, nb, mod, n, st); } };
+template <int N_BPSC, size_t N, class T_CTX, class T_NEXT>
+struct THipMap11a : THipStage<uint8_t, 6 * N_BPSC * N, sora_complex16, 48 * N, CallMap11a, T_CTX, T_NEXT> {
+    THipMap11a(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, int mod = 0, void* stream = nullptr)
+        : THipStage<uint8_t, 6 * N_BPSC * N, sora_complex16, 48 * N, CallMap11a, T_CTX, T_NEXT>(ctx, next, d_out, CallMap11a{ N_BPSC, mod, N }, stream) {}
+};
+
+// T11aAddPilot<BPSK_MOD> (pilot.hpp:30-118): IPORT COMPLEX16 x 48 -> OPORT COMPLEX16 x 64, N symbols of ONE frame per burst.  m_PilotIndex is the count of symbols
+// since Reset (the first takes PilotSgn[127], the SIGNAL symbol's); d_tab: 16 bytes of device memory for the call's frame table.
+template <size_t N, class T_CTX, class T_NEXT>
+class THip11aAddPilot : public HipFilter<T_CTX, T_NEXT> {
+public:
+    using iport_traits = port_traits<sora_complex16, 48 * N>;
+    using oport_traits = port_traits<sora_complex16, 64 * N>;
+    THip11aAddPilot(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* d_tab, int bpsk_mod = 0, void* stream = nullptr)
+        : HipFilter<T_CTX, T_NEXT>(ctx, next, stream), opin_(d_out), d_tab_(static_cast<uint32_t*>(d_tab)), mod_(bpsk_mod) {}
+    void Reset() { pos_ = 0; HipFilter<T_CTX, T_NEXT>::Reset(); }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            sora_complex16* out = opin_.append();
+            const uint32_t tab[4] = { 0u, (uint32_t)N, pos_, 0u };                                 // first, nsym, position of the burst's first symbol in its frame
+            if (sora_hip_memcpy_h2d(d_tab_, tab, sizeof(tab)) != SORA_OK) return this->raise(SORA_ERR_HARDWARE_FAILED);
+            if (!this->raise(sora_hip_add_pilot11a_from(ipin.peek(), out, d_tab_, d_tab_ + 1, d_tab_ + 2, 1, mod_, this->stream_))) return false;
+            pos_ += (uint32_t)N;
+            ipin.pop();
+            if (this->next_ && !this->next_->Process(opin_)) return false;
+        }
+        return true;
+    }
+    DevicePin<sora_complex16, 64 * N>& opin() { return opin_; }
+private:
+    DevicePin<sora_complex16, 64 * N> opin_; uint32_t* d_tab_; int mod_; uint32_t pos_ = 0;
+};
+
+// TIFFTx (fft.hpp:7-61): IPORT COMPLEX16 x 64 -> OPORT COMPLEX16 x 160, N symbols per burst
+struct CallIFFTx { size_t n; int operator()(const sora_complex16* in, sora_complex16* out, void* st) const { return sora_hip_ifftx11a(in, out, n, st); } };
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipIFFTx : THipStage<sora_complex16, 64 * N, sora_complex16, 160 * N, CallIFFTx, T_CTX, T_NEXT> {
+    THipIFFTx(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* stream = nullptr)
+        : THipStage<sora_complex16, 64 * N, sora_complex16, 160 * N, CallIFFTx, T_CTX, T_NEXT>(ctx, next, d_out, CallIFFTx{ N }, stream) {}
+};
+// TUpsample40MTo44M (sampling.hpp:8-32): IPORT COMPLEX16 x 160 -> OPORT COMPLEX16 x 176, N blocks per burst.  d_sees_next: N device bytes, block b of a burst finds block
+// b + 1's first sample behind its last one (the preamble source's one burst of four blocks: 1, 1, 1, 0); null: every block ends in x[160] = 0.
+struct CallUpsample40to44 { const uint8_t* d_sees_next; size_t n; int operator()(const sora_complex16* in, sora_complex16* out, void* st) const
+    { return sora_hip_upsample40to44(in, out, d_sees_next, n, st); } };
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipUpsample40MTo44M : THipStage<sora_complex16, 160 * N, sora_complex16, 176 * N, CallUpsample40to44, T_CTX, T_NEXT> {
+    THipUpsample40MTo44M(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, const uint8_t* d_sees_next = nullptr, void* stream = nullptr)
+        : THipStage<sora_complex16, 160 * N, sora_complex16, 176 * N, CallUpsample40to44, T_CTX, T_NEXT>(ctx, next, d_out, CallUpsample40to44{ d_sees_next, N }, stream) {}
+};
+// TPackSample16to8 (stdbrick.hpp:415-445): IPORT COMPLEX16 x NSAMPLES -> OPORT COMPLEX8 x NSAMPLES (int8 re, int8 im), NSAMPLES a multiple of the brick's 8
+struct sora_complex8 { int8_t re, im; };
+struct CallPack16to8 { size_t n; int operator()(const sora_complex16* in, sora_complex8* out, void* st) const { return sora_hip_pack16to8(in, &out->re, n, st); } };
+template <size_t NSAMPLES, class T_CTX, class T_NEXT>
+struct THipPackSample16to8 : THipStage<sora_complex16, NSAMPLES, sora_complex8, NSAMPLES, CallPack16to8, T_CTX, T_NEXT> {
+    static_assert(NSAMPLES % 8 == 0, "whole bursts of TPackSample16to8");
+    THipPackSample16to8(T_CTX& ctx, T_NEXT* next, sora_complex8* d_out, void* stream = nullptr)
+        : THipStage<sora_complex16, NSAMPLES, sora_complex8, NSAMPLES, CallPack16to8, T_CTX, T_NEXT>(ctx, next, d_out, CallPack16to8{ NSAMPLES }, stream) {}
+};
+
 // ISource over a batch of captures = the whole demod graph behind one handle (brick.h:343-353: Process/Seek/Reset/Flush).
 class THipRx11aSource {
 public:

@@ -37,7 +37,9 @@ extern "C" {
  * and the automatic choices of sora_rx_set_trellis / sora_rx_set_front (results are identical whichever kernels run).  INTEGRATION.md section 1 lists them. */
 /* 4 (round 6).  Against 3: no row is ever delivered with SORA_E_INTERNAL_TIMEOUT (see sora_rx_set_front, form 4); new, additive: sora_rx_set_pipe_wait_us, sora_rx_pipe_stats,
  * sora_hip_pilot11a, sora_rx_bind_mpdu, sora_rx11n_trellis, sora_rx11n_window_stats, sora_rx_call_front, sora_rx_set_ordered, sora_hip_set_share_window_us, SORA_TRELLIS_WINDOWED and
- * the automatic choice for sora_rx11n_set_trellis. */
+ * the automatic choice for sora_rx11n_set_trellis.
+ * Additive since: the 802.11a modulation graph's bricks as stages -- sora_hip_scramble11a, _conv_encode11a, _interleave11a, _map11a, _add_pilot11a (_from), _ifftx11a,
+ * _upsample40to44, _pack16to8, _preamble11a. */
 #define SORA_HIP_ABI_VERSION 4
 
 /* COMPLEX16: kernel/core/inc/complex.h */
@@ -406,6 +408,56 @@ int sora_hip_tx11a(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t*
 size_t sora_hip_tx11a44_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps);
 int sora_hip_tx11a44(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps,
                      const uint8_t* d_seed, size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The bricks of the 802.11a modulation graph as stage entry points: what CreateModGraph11a_40M / _44M and CreatePreamble11a_40M / _44M
+ * (kernel/bb/demod11/fb11amod_config.hpp:74-110) are built from, each with the port format of the brick it replaces -- bits packed in bytes,
+ * LSB first, exactly as the brick's pins carry them -- so that a host can replace ONE brick, or compose the graphs from stages:
+ *     preamble -> [upsample40to44] -> pack16to8
+ *     scramble -> conv_encode -> interleave -> map -> add_pilot -> ifftx -> [upsample40to44] -> pack16to8
+ * The conventions are those of the stage entry points above: device pointers, stream order, no allocation, no host wait; a null pointer or a symbol
+ * buffer that is not 16-byte aligned gives SORA_ERR_INVALID_PARAM, no device SORA_ERR_NO_DEVICE, a count of 0 is SORA_OK and launches nothing.
+ * (The byte streams of the scrambler and the encoder lie at the caller's offsets and need no alignment.)  DESIGN.md section 7, f2b.
+ * ------------------------------------------------------------------------------------------------ */
+/* T11aSc (Brick11/src/scramble.hpp:170-261): IPORT uchar x 1 -> OPORT uchar x 1.  Frame f owns d_len[f] bytes at d_off[f] of both buffers (in place is
+ * fine).  The register starts at d_seed[f] -- the brick after Reset: all 8 bits are stored, each byte takes lut[reg >> 1].  Every byte is DO_SCRAMBLE except
+ * byte d_tail[f] where d_tail != NULL and d_tail[f] < d_len[f]: TAIL_SCRAMBLE, (b ^ reg) & 0xC0, the register advancing all the same.  NO_SCRAMBLE is not
+ * calling the stage.  max_len: a bound on every d_len[f] that the host knows (it sizes the grid; bytes of a frame at or behind it are not written). */
+int sora_hip_scramble11a(const uint8_t* d_in, uint8_t* d_out, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_tail, const uint8_t* d_seed,
+                         size_t nframes, size_t max_len, void* stream);
+/* TConvEncode_12 / _23 / _34 (conv_enc.hpp:18-330): IPORT uchar x 1 / 2 / 3 -> OPORT uchar x 2 / 3 / 4, code_rate = SORA_CR_12 / _23 / _34.  Frame f reads
+ * d_len[f] bytes at d_in + d_in_off[f], the register 0 at its first byte, and writes its whole bursts' output at d_out + d_out_off[f] in the bricks' bit order
+ * and puncturing (A B; A B A; A B A B').  Input bytes behind the last whole burst produce nothing (the brick leaves them queued); nothing behind the frame's
+ * output is written.  max_len as above, below 128 MiB. */
+int sora_hip_conv_encode11a(const uint8_t* d_in, const uint32_t* d_in_off, const uint32_t* d_len, int code_rate, uint8_t* d_out, const uint32_t* d_out_off,
+                            size_t nframes, size_t max_len, void* stream);
+/* T11aInterleave{BPSK,QPSK,QAM16,QAM64} (interleave.hpp:16-114; N_COL = 16, I_SS = 1): IPORT uchar x 6 n_bpsc -> OPORT uchar x 6 n_bpsc per symbol */
+int sora_hip_interleave11a(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, size_t nsym, void* stream);
+/* TMap11a{BPSK,QPSK,QAM16,QAM64}<MOD> (mapper11a.hpp:8-300): IPORT uchar x 6 n_bpsc -> OPORT COMPLEX16 x 48 per symbol.  mod = the brick's MOD template argument
+ * (1 .. 32767); 0 = the 802.11a default for n_bpsc: 10720, (short)(10720 / 1.414), / 3.162, / 6.481.  (The 802.11n graph instantiates the same bricks with
+ * 30339, 21453, 9594 and 4681.) */
+int sora_hip_map11a(const uint8_t* d_in, sora_complex16* d_out, int n_bpsc, int mod, size_t nsym, void* stream);
+/* T11aAddPilot<BPSK_MOD> (pilot.hpp:30-118): IPORT COMPLEX16 x 48 -> OPORT COMPLEX16 x 64 per symbol: the data carriers placed, the four pilots, every other bin 0.
+ * Frame f owns symbols d_first[f] .. d_first[f] + d_nsym[f] - 1 (sora_hip_pilot_track11a's frame tables).  The symbol at position j of its frame takes
+ * PilotSgn[127] for j = 0 and PilotSgn[(j - 1) mod 127] otherwise: the brick's m_PilotIndex starts at 127 and wraps at 127 (j = 0 is the SIGNAL symbol of a real
+ * frame).  bpsk_mod = 0 means 10720.  _from: table entry f is the part of a frame that begins at position d_pos0[f] (what a brick adapter that streams bursts
+ * of one frame needs); d_pos0 NULL = 0 everywhere = sora_hip_add_pilot11a. */
+int sora_hip_add_pilot11a(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, size_t nframes, int bpsk_mod,
+                          void* stream);
+int sora_hip_add_pilot11a_from(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_pos0,
+                               size_t nframes, int bpsk_mod, void* stream);
+/* TIFFTx (fft.hpp:7-61): IPORT COMPLEX16 x 64 -> OPORT COMPLEX16 x 160 per symbol.  Bins 0..31 and 32..63 go to bins 0..31 and 96..127 of the reference's fixed-point
+ * IFFT<128>; then >> 4, the last 32 samples copied to the front as the guard interval, and samples 0, 1, 158, 159 halved. */
+int sora_hip_ifftx11a(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream);
+/* TUpsample40MTo44M (sampling.hpp:8-32, 40MTo44M.hpp): IPORT COMPLEX16 x 160 -> OPORT COMPLEX16 x 176 per block, nothing carried from block to block; the closed form is
+ * given at sora_hip_tx11a44.  d_sees_next[b] != 0: block b's x[160] is block b + 1's first sample (the preamble's blocks 0..2, handed on as one burst); for the
+ * last block of the call, or d_sees_next NULL, x[160] = 0. */
+int sora_hip_upsample40to44(const sora_complex16* d_in, sora_complex16* d_out, const uint8_t* d_sees_next, size_t nblocks, void* stream);
+/* TPackSample16to8 (brick/inc/stdbrick.hpp:415-445): COMPLEX16 -> COMPLEX8 with signed saturation (_mm_packs_epi16).  nsamples must be a multiple of 8, the brick's
+ * burst (SORA_ERR_INVALID_PARAM otherwise). */
+int sora_hip_pack16to8(const sora_complex16* d_in, int8_t* d_out, size_t nsamples, void* stream);
+/* TTS11aSrc (preamble11a.hpp:19-140): the 640 COMPLEX16 preamble samples at 40 MHz, ncopies times back to back */
+int sora_hip_preamble11a(sora_complex16* d_out, size_t ncopies, void* stream);
 
 /* 802.11n 2x2 transmitter: the reference's modulation graphs CreatePreambleGraph11n + CreateSigGraph11n + CreateModGraph11n
  * (kernel/bb/demod11/fb11nmod_config.hpp) as Test11N_FB_Mod runs them (fb11n_mod.cpp:28-70): L-STF, L-LTF, L-SIG, HT-SIG, HT-STF,

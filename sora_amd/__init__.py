@@ -7,6 +7,8 @@ from .capi import (Rx, Rx11b, Rx11n, RxHt40, ht40_symbols, HostResults, ROW_DTYP
     pilot_track11a, pilot11a, set_share_window_us, freq_comp11a, equalize11a, phase_comp11a, demap11a, deinterleave11a, demap11n, deinterleave11n, mimo_est11n, mimo_comp11n,
     cfo_est11n, freq_comp11n, pilot_track11n, siso_est11n, siso_comp11n, sig_demap11n, sig_decode11n, viterbi11a, viterbi11a_ws, viterbi11a_workspace_bytes,  # noqa: F401
                    viterbi11n_ws, viterbi11n_workspace_bytes, viterbi_window_stats,
-                   ingest, ingest_count, tx11a, tx11a_samples, tx11n, tx11n_samples, tx_ht40, tx_ht40_samples, tx11b, tx11b_samples, INGEST_RXBLOCK, INGEST_RAW14, INGEST_44TO40, INGEST_DECIMATE2,
+                   ingest, ingest_count, scramble11a, conv_encode11a, interleave11a, map11a, add_pilot11a, ifftx11a, upsample40to44, pack16to8, preamble11a,
+                   mod11a_by_stages, Mod11aStages, mod11a_fields, CR_12, CR_23, CR_34,
+                   tx11a, tx11a_samples, tx11n, tx11n_samples, tx_ht40, tx_ht40_samples, tx11b, tx11b_samples, INGEST_RXBLOCK, INGEST_RAW14, INGEST_44TO40, INGEST_DECIMATE2,
                    ht40_symbols_joint, HT40_CODING_PER_STREAM, HT40_CODING_JOINT, tx_ht40_joint, tx_ht40_joint_samples,
                    E_FRAME_OK, E_CRC32_FAIL, E_PLCP_HEADER_FAIL, TRELLIS_WINDOWED, table_names, table_pin, table_digest, table_read)

@@ -63,6 +63,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_hip_viterbi11a_ws", "sora_hip_viterbi11a_workspace_bytes", "sora_hip_viterbi11n_ws", "sora_hip_viterbi11n_workspace_bytes",
                       "sora_hip_viterbi_window_stats",
            "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11a44", "sora_hip_tx11a44_samples",
+           "sora_hip_scramble11a", "sora_hip_conv_encode11a", "sora_hip_interleave11a", "sora_hip_map11a", "sora_hip_add_pilot11a", "sora_hip_add_pilot11a_from",
+           "sora_hip_ifftx11a", "sora_hip_upsample40to44", "sora_hip_pack16to8", "sora_hip_preamble11a",
            "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx_ht40", "sora_hip_tx_ht40_samples", "sora_hip_tx11b", "sora_hip_tx11b_samples",
            "sora_hip_tx_ht40_joint", "sora_hip_tx_ht40_joint_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
@@ -220,6 +222,17 @@ def load(build_if_missing=True):
     L.sora_hip_tx11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.sora_hip_tx11a44_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11a44_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11a44.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    # the 802.11a modulation graph's bricks as stages
+    L.sora_hip_scramble11a.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_conv_encode11a.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_interleave11a.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_map11a.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_add_pilot11a.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    L.sora_hip_add_pilot11a_from.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    L.sora_hip_ifftx11a.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_upsample40to44.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_pack16to8.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_preamble11a.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_tx11n_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11n_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11n.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
     L.sora_hip_tx_ht40_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx_ht40_samples.restype = ctypes.c_size_t
@@ -1147,6 +1160,224 @@ def tx11a(mpdus, rates_kbps, seeds=None, device=0, stream=None, sync=True, gaps=
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     return out, [int(v) for v in ooff]
+
+
+# ---- the 802.11a modulation graph's bricks as stages (include/sora_hip.h; the byte formats are the bricks': bits packed in bytes, LSB first)
+CR_12, CR_23, CR_34 = 0, 1, 2
+
+
+def _opt_ptr(x):
+    return None if x is None else _dev_ptr(x)
+
+
+def scramble11a(x, off, length, seed, tail=None, max_len=None, stream=None):
+    """T11aSc: x uint8 CUDA [nbytes]; off / length (/ tail) int32 CUDA [n]; seed uint8 CUDA [n] -> uint8 CUDA like x (bytes outside every frame are copied).
+    tail[f] < length[f]: that byte is TAIL_SCRAMBLE.  max_len: a bound on the lengths (default: read back from `length`)."""
+    out = x.clone()
+    n = off.shape[0]
+    if max_len is None:
+        max_len = int(length.max().item()) if n else 0
+    _check(load().sora_hip_scramble11a(_dev_ptr(x), _dev_ptr(out), _dev_ptr(off), _dev_ptr(length), _opt_ptr(tail), _dev_ptr(seed), n, int(max_len), _stream_ptr(stream)))
+    return out
+
+
+def conv_encode11a(x, in_off, length, code_rate, out, out_off, max_len=None, stream=None):
+    """TConvEncode_12 / _23 / _34 (code_rate = CR_12 / CR_23 / CR_34): frame f reads length[f] bytes at x[in_off[f]:] and writes its whole bursts' 2 / 3 / 4 bytes per
+    1 / 2 / 3 into out[out_off[f]:] (uint8 CUDA, written in place and returned); nothing else of `out` is touched."""
+    n = in_off.shape[0]
+    if max_len is None:
+        max_len = int(length.max().item()) if n else 0
+    _check(load().sora_hip_conv_encode11a(_dev_ptr(x), _dev_ptr(in_off), _dev_ptr(length), int(code_rate), _dev_ptr(out), _dev_ptr(out_off), n, int(max_len),
+                                          _stream_ptr(stream)))
+    return out
+
+
+def interleave11a(s, n_bpsc, stream=None):
+    """T11aInterleave*: s uint8 CUDA [n, 6 n_bpsc] -> same shape."""
+    import torch
+    out = torch.empty_like(s)
+    _check(load().sora_hip_interleave11a(_dev_ptr(s), _dev_ptr(out), int(n_bpsc), s.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def map11a(s, n_bpsc, mod=0, stream=None):
+    """TMap11a*<MOD>: s uint8 CUDA [n, 6 n_bpsc] -> int16 CUDA [n, 48, 2]; mod = 0: the 802.11a amplitude of n_bpsc."""
+    import torch
+    out = torch.empty((s.shape[0], 48, 2), dtype=torch.int16, device=s.device)
+    _check(load().sora_hip_map11a(_dev_ptr(s), _dev_ptr(out), int(n_bpsc), int(mod), s.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def add_pilot11a(x, first, nsym, bpsk_mod=0, pos0=None, stream=None):
+    """T11aAddPilot: x int16 CUDA [n, 48, 2]; first / nsym int32 CUDA [nframes] (pos0: the position in its frame of each entry's first symbol, default 0)
+    -> int16 CUDA [n, 64, 2]; symbols no frame owns stay 0."""
+    import torch
+    out = torch.zeros((x.shape[0], 64, 2), dtype=torch.int16, device=x.device)
+    if pos0 is None:
+        _check(load().sora_hip_add_pilot11a(_dev_ptr(x), _dev_ptr(out), _dev_ptr(first), _dev_ptr(nsym), first.shape[0], int(bpsk_mod), _stream_ptr(stream)))
+    else:
+        _check(load().sora_hip_add_pilot11a_from(_dev_ptr(x), _dev_ptr(out), _dev_ptr(first), _dev_ptr(nsym), _dev_ptr(pos0), first.shape[0], int(bpsk_mod),
+                                                 _stream_ptr(stream)))
+    return out
+
+
+def ifftx11a(x, stream=None):
+    """TIFFTx: x int16 CUDA [n, 64, 2] -> int16 CUDA [n, 160, 2]."""
+    import torch
+    out = torch.empty((x.shape[0], 160, 2), dtype=torch.int16, device=x.device)
+    _check(load().sora_hip_ifftx11a(_dev_ptr(x), _dev_ptr(out), x.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def upsample40to44(x, sees_next=None, stream=None):
+    """TUpsample40MTo44M: x int16 CUDA [n, 160, 2] -> int16 CUDA [n, 176, 2]; sees_next uint8 CUDA [n]: block b finds block b + 1's first sample behind its last."""
+    import torch
+    out = torch.empty((x.shape[0], 176, 2), dtype=torch.int16, device=x.device)
+    _check(load().sora_hip_upsample40to44(_dev_ptr(x), _dev_ptr(out), _opt_ptr(sees_next), x.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def pack16to8(x, stream=None):
+    """TPackSample16to8: x int16 CUDA [..., 2] of a multiple of 8 samples -> int8 CUDA of the same shape."""
+    import torch
+    out = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+    _check(load().sora_hip_pack16to8(_dev_ptr(x), _dev_ptr(out), x.numel() // 2, _stream_ptr(stream)))
+    return out
+
+
+def preamble11a(ncopies=1, device=0, stream=None):
+    """TTS11aSrc: -> int16 CUDA [ncopies, 640, 2], the 802.11a preamble at 40 MHz."""
+    import torch
+    out = torch.empty((int(ncopies), 640, 2), dtype=torch.int16, device=torch.device("cuda", device))
+    _check(load().sora_hip_preamble11a(_dev_ptr(out), int(ncopies), _stream_ptr(stream)))
+    return out
+
+
+_RATES_11A = {6000: (1, CR_12, 24, 0xB), 9000: (1, CR_34, 36, 0xF), 12000: (2, CR_12, 48, 0xA), 18000: (2, CR_34, 72, 0xE),
+              24000: (4, CR_12, 96, 0x9), 36000: (4, CR_34, 144, 0xD), 48000: (6, CR_23, 192, 0x8), 54000: (6, CR_34, 216, 0xC)}
+
+
+def mod11a_fields(mpdu, rate_kbps):
+    """What TBB11aSrc::Process (PHY_11a.hpp:111-202) sends down the graph for one MPDU without FCS: (the 3 SIGNAL bytes, which go unscrambled through the 6 Mbps
+    path; SERVICE + MPDU + FCS + tail + pad, whole symbols -- two at 9 Mbps; the index of the tail byte)."""
+    import zlib
+    nb, cr, nd, rc = _RATES_11A[int(rate_kbps)]
+    mpdu = bytes(mpdu)
+    sig = rc | ((len(mpdu) + 4) << 5)
+    sig |= (bin(sig).count("1") & 1) << 17
+    ndp = nd * 2 if int(rate_kbps) == 9000 else nd
+    dbytes = 2 + len(mpdu) + 4 + 1
+    rem = (dbytes * 8) % ndp
+    nbytes = dbytes + ((ndp - rem if rem else 0) + 7) // 8
+    data = np.zeros(nbytes, np.uint8)
+    data[2:2 + len(mpdu)] = np.frombuffer(mpdu, np.uint8)
+    data[2 + len(mpdu):2 + len(mpdu) + 4] = np.frombuffer(int(zlib.crc32(mpdu) & 0xFFFFFFFF).to_bytes(4, "little"), np.uint8)
+    return np.array([sig & 255, (sig >> 8) & 255, (sig >> 16) & 255], np.uint8), data, dbytes - 1
+
+
+class Mod11aStages:
+    """sora_amd.tx11a's frames composed from the nine stage entry points instead of the fused kernel: CreatePreamble11a_* and CreateModGraph11a_* (fb11amod_config.hpp:74-110)
+    brick by brick.  The constructor plays TBB11aSrc on the host (mod11a_fields) and uploads the fields and the frame tables; run() is the stage chain, every
+    intermediate through HBM.  The symbols are laid out by modulation (all SIGNAL symbols, then the data symbols of the BPSK, QPSK, 16-QAM and 64-QAM frames), so that
+    each stage is ONE call per modulation or code rate whatever the batch; a last index_select puts the 160 / 176-sample blocks into frame order."""
+
+    def __init__(self, mpdus, rates, seeds=None, sample_rate_mhz=40, device=0):
+        import torch
+        if sample_rate_mhz not in (40, 44):
+            raise ValueError("mod11a_by_stages: sample_rate_mhz must be 40 or 44, not %r" % (sample_rate_mhz,))
+        n = self.n = len(mpdus)
+        self.mhz = sample_rate_mhz
+        seeds = [0xFF] * n if seeds is None else list(seeds)
+        if any(int(r) not in _RATES_11A or len(m) + 4 > 4095 for m, r in zip(mpdus, rates)):
+            raise SoraError(-1, "mod11a_by_stages: unsupported rate or length")
+        dev = self.dev = torch.device("cuda", device)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
+        i32 = lambda a: up(np.asarray(a, np.int64).astype(np.int32), np.int32)
+        fields = [mod11a_fields(m, r) for m, r in zip(mpdus, rates)]
+        par = [_RATES_11A[int(r)] for r in rates]
+        nsym = [len(fl[1]) * 8 // p[2] for fl, p in zip(fields, par)]
+        # symbol slots: SIGNAL symbols 0 .. n - 1, then the data symbols, frames grouped by modulation (the BPSK group follows the SIGNAL symbols: one BPSK run)
+        order = sorted(range(n), key=lambda f: (par[f][0], f))
+        slot0 = [0] * n
+        at = n
+        for f in order:
+            slot0[f] = at; at += nsym[f]
+        self.nslots = at
+        self.run_of = {}                                                         # n_bpsc -> (first slot, slots)
+        for nb in (1, 2, 4, 6):
+            fs = [f for f in order if par[f][0] == nb]
+            cnt = sum(nsym[f] for f in fs)
+            self.run_of[nb] = (0, n + cnt) if nb == 1 else (slot0[fs[0]] if fs else at, cnt)
+        # the coded bytes of a run lie together, 6 n_bpsc per slot, every run from a 16-byte boundary
+        self.cbase, cat = {}, 0
+        for nb in (1, 2, 4, 6):
+            self.cbase[nb] = cat; cat += (self.run_of[nb][1] * 6 * nb + 15) // 16 * 16
+        self.coded_bytes = max(cat, 16)
+        coded_off = lambda nb, slot: self.cbase[nb] + (slot - self.run_of[nb][0]) * 6 * nb
+        # the uncoded bytes: SIGNAL fields (3 bytes each), then the data fields
+        dlen = [len(fl[1]) for fl in fields]
+        doff = np.zeros(n + 1, np.int64); np.cumsum(dlen, out=doff[1:]); doff += 3 * n
+        raw = np.zeros(max(int(doff[-1]), 1), np.uint8)
+        for f, fl in enumerate(fields):
+            raw[3 * f:3 * f + 3] = fl[0]; raw[doff[f]:doff[f + 1]] = fl[1]
+        self.d_raw = up(raw, np.uint8)
+        self.scr = (i32(doff[:-1]), i32(dlen), i32([fl[2] for fl in fields]), up(np.asarray(seeds, np.uint8), np.uint8), max(dlen))
+        # TConvEncode_*: the SIGNAL fields at rate 1/2, the data fields by code rate (a fresh register per field)
+        self.enc = [(CR_12, i32([3 * f for f in range(n)]), i32([3] * n), i32([coded_off(1, f) for f in range(n)]), n, 3)]
+        for cr in (CR_12, CR_23, CR_34):
+            fs = [f for f in range(n) if par[f][1] == cr]
+            if fs:
+                self.enc.append((cr, i32([doff[f] for f in fs]), i32([dlen[f] for f in fs]), i32([coded_off(par[f][0], slot0[f]) for f in fs]), len(fs),
+                                 max(dlen[f] for f in fs)))
+        # T11aAddPilot: the SIGNAL symbol is position 0 of its frame, the data symbols follow from position 1
+        self.pil = (i32(list(range(n)) + slot0), i32([1] * n + nsym), i32([0] * n + [1] * n))
+        sees = np.zeros(4 * n + self.nslots, np.uint8); sees[:4 * n] = np.tile([1, 1, 1, 0], n)     # the preamble is one burst: its blocks 0..2 see the next block
+        self.d_sees = up(sees, np.uint8)
+        blocks = []                                                              # frame order: preamble, SIGNAL, data
+        for f in range(n):
+            blocks += [4 * f, 4 * f + 1, 4 * f + 2, 4 * f + 3, 4 * n + f] + list(range(4 * n + slot0[f], 4 * n + slot0[f] + nsym[f]))
+        self.d_blocks = up(np.asarray(blocks, np.int64), np.int64)
+        per = 160 if sample_rate_mhz == 40 else 176
+        offs = np.zeros(n + 1, np.int64); np.cumsum([(5 + k) * per for k in nsym], out=offs[1:])
+        self.offsets = [int(v) for v in offs]
+
+    def run(self):
+        """-> int8 CUDA [total, 2]; everything in order on torch's current stream (the gather at the end is torch's), nothing waited for"""
+        import torch
+        L = load()
+        stream = None
+        st = _stream_ptr(stream)
+        n, dev, nslots = self.n, self.dev, self.nslots
+        off, ln, tail, seed, mx = self.scr
+        d_scr = scramble11a(self.d_raw, off, ln, seed, tail=tail, max_len=mx, stream=stream)        # (the SIGNAL bytes pass with NO_SCRAMBLE: in no frame of the call)
+        d_coded = torch.empty(self.coded_bytes, dtype=torch.uint8, device=dev)
+        for cr, in_off, ilen, out_off, cnt, mx in self.enc:
+            _check(L.sora_hip_conv_encode11a(_dev_ptr(d_scr), _dev_ptr(in_off), _dev_ptr(ilen), cr, _dev_ptr(d_coded), _dev_ptr(out_off), cnt, mx, st))
+        d_inter = torch.empty_like(d_coded)
+        d_car = torch.empty((nslots, 48, 2), dtype=torch.int16, device=dev)
+        for nb in (1, 2, 4, 6):                                                  # T11aInterleave* -> TMap11a*, one call per modulation
+            s0, ns = self.run_of[nb]
+            if ns:
+                _check(L.sora_hip_interleave11a(d_coded.data_ptr() + self.cbase[nb], d_inter.data_ptr() + self.cbase[nb], nb, ns, st))
+                _check(L.sora_hip_map11a(d_inter.data_ptr() + self.cbase[nb], d_car.data_ptr() + s0 * 192, nb, 0, ns, st))
+        d_bins = torch.empty((nslots, 64, 2), dtype=torch.int16, device=dev)     # (every slot belongs to a frame)
+        _check(L.sora_hip_add_pilot11a_from(_dev_ptr(d_car), _dev_ptr(d_bins), _dev_ptr(self.pil[0]), _dev_ptr(self.pil[1]), _dev_ptr(self.pil[2]), 2 * n, 0, st))
+        # TTS11aSrc and TIFFTx into one 16-bit stream of 160-sample blocks: n preambles (4 blocks each), then the symbol slots
+        d_x = torch.empty((4 * n + nslots, 160, 2), dtype=torch.int16, device=dev)
+        _check(L.sora_hip_preamble11a(d_x.data_ptr(), n, st))
+        _check(L.sora_hip_ifftx11a(d_bins.data_ptr(), d_x.data_ptr() + 4 * n * 640, nslots, st))
+        if self.mhz == 44:
+            d_x = upsample40to44(d_x, self.d_sees, stream=stream)
+        return pack16to8(d_x, stream=stream).index_select(0, self.d_blocks).reshape(-1, 2)
+
+
+def mod11a_by_stages(mpdus, rates, seeds=None, sample_rate_mhz=40, device=0, sync=True):
+    """Modulate a batch of MPDUs (bytes WITHOUT FCS) through the stage chain (Mod11aStages) -> (int8 CUDA [total, 2], offsets): the same as sora_amd.tx11a returns."""
+    plan = Mod11aStages(mpdus, rates, seeds, sample_rate_mhz, device)
+    out = plan.run()
+    if sync:
+        _check(load().sora_hip_stream_synchronize(_stream_ptr(None)))
+    return out, plan.offsets
 
 
 def tx11n_samples(mpdu_len_nofcs, mcs):

@@ -1,0 +1,337 @@
+// k_mod.hip -- the bricks of the 802.11a modulation graph (kernel/bb/demod11/fb11amod_config.hpp:74-110) as stand-alone, batched stages, one C entry point each
+// (include/sora_hip.h), with the reference bricks' port formats: bits packed in bytes, LSB first, as the pins carry them.
+//   k_mod_scramble    T11aSc                         (Brick11/src/scramble.hpp:170-261)       uchar x 1 -> uchar x 1
+//   k_mod_encode      TConvEncode_12 / _23 / _34     (conv_enc.hpp:18-330)                    uchar x 1 / 2 / 3 -> uchar x 2 / 3 / 4
+//   k_mod_interleave  T11aInterleave*                (interleave.hpp:16-114)                  uchar x 6 N_BPSC -> the same
+//   k_mod_map         TMap11a*<MOD>                  (mapper11a.hpp:8-300)                    uchar x 6 N_BPSC -> COMPLEX16 x 48
+//   k_mod_add_pilot   T11aAddPilot<BPSK_MOD>         (pilot.hpp:30-118)                       COMPLEX16 x 48 -> COMPLEX16 x 64
+//   k_mod_ifftx       TIFFTx                         (fft.hpp:7-61)                           COMPLEX16 x 64 -> COMPLEX16 x 160
+//   k_mod_upsample    TUpsample40MTo44M              (sampling.hpp:8-32, 40MTo44M.hpp)        COMPLEX16 x 160 -> COMPLEX16 x 176
+//   k_mod_pack16to8   TPackSample16to8               (brick/inc/stdbrick.hpp:415-445)         COMPLEX16 x 8 -> COMPLEX8 x 8
+//   k_mod_preamble    TTS11aSrc                      (preamble11a.hpp:19-140)                 -> COMPLEX16 x 640
+// The arithmetic is dev_tx.h's (what the fused transmitters run); here are the port formats and the streaming shape of k_stage.hip: a workgroup owns a tile of
+// consecutive symbols, every access to a symbol buffer is a 16-byte-per-lane load or store of a contiguous tile, the reshuffling inside a symbol happens in LDS.
+// The byte-wide stages (scrambler, encoder) are one thread per output byte: every output bit is a closed form of its position.
+#include <hip/hip_runtime.h>
+#include "kernels.h"
+#include "dev_tx.h"
+
+namespace sora {
+
+// a tile of nbytes contiguous bytes between 16-byte aligned global memory and LDS: 16 bytes per lane, the ragged end of a last tile byte by byte
+__device__ __forceinline__ void mod_tile_load(uint32_t* s, const uint8_t* g, int nbytes, int tid)
+{
+    for (int q = tid; q < (nbytes + 15) / 16; q += 256) {
+        if (16 * q + 16 <= nbytes) reinterpret_cast<uint4*>(s)[q] = reinterpret_cast<const uint4*>(g)[q];
+        else for (int b = 16 * q; b < 16 * q + 16; b++) reinterpret_cast<uint8_t*>(s)[b] = b < nbytes ? g[b] : (uint8_t)0;
+    }
+}
+__device__ __forceinline__ void mod_tile_store(uint8_t* g, const uint32_t* s, int nbytes, int tid)
+{
+    for (int q = tid; q < (nbytes + 15) / 16; q += 256) {
+        if (16 * q + 16 <= nbytes) reinterpret_cast<uint4*>(g)[q] = reinterpret_cast<const uint4*>(s)[q];
+        else for (int b = 16 * q; b < nbytes; b++) g[b] = reinterpret_cast<const uint8_t*>(s)[b];
+    }
+}
+
+// ---- T11aSc: byte i of frame f = in ^ (the register after i + 1 steps), the register a phase of the period-127 cycle (tx_scramble); the tail byte keeps its two pad bits.
+// chunks = workgroups per frame (the host's bound on the lengths / 256).
+__global__ void __launch_bounds__(256) k_mod_scramble(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const uint32_t* __restrict__ off, const uint32_t* __restrict__ len,
+        const uint32_t* __restrict__ tail, const uint8_t* __restrict__ seed, uint32_t nframes, uint32_t chunks, Tables T)
+{
+    const uint32_t f = blockIdx.x / chunks, i = (blockIdx.x - f * chunks) * 256u + threadIdx.x;
+    if (f >= nframes || i >= len[f]) return;
+    const unsigned phase = T.scr_phase[seed[f] >> 1];                            // m_Reg = lut[m_Reg >> 1]: bit 0 of the stored register is never read
+    const size_t at = (size_t)off[f] + i;
+    unsigned c = in[at] ^ (phase == 255 ? 0u : T.scr_seq[(phase + 8u * (i % 127u)) % 127u]);
+    if (tail && i == tail[f]) c &= 0xC0u;                                        // TAIL_SCRAMBLE
+    out[at] = (uint8_t)c;
+}
+
+// ---- TConvEncode_*: the punctured coded stream packed LSB first IS the bricks' output (their tables shift the newest coded bit in at the top); output byte j holds coded
+// bits 8 j .. 8 j + 7 of the frame, coded bit k = generator `which` at input bit il (tx_punct_offset), a xor of five of the seven input bits il - 6 .. il.  The eight bits
+// of a byte span at most 6 input bits, so with the 6 before them and a byte's misalignment they lie in three input bytes.  Bursts of 1 / 2 / 3 bytes -> 2 / 3 / 4.
+__global__ void __launch_bounds__(256) k_mod_encode(const uint8_t* __restrict__ in, const uint32_t* __restrict__ in_off, const uint32_t* __restrict__ len, int cr,
+        uint8_t* __restrict__ out, const uint32_t* __restrict__ out_off, uint32_t nframes, uint32_t chunks)
+{
+    const uint32_t f = blockIdx.x / chunks, j = (blockIdx.x - f * chunks) * 256u + threadIdx.x;
+    if (f >= nframes) return;
+    const uint32_t bin = (uint32_t)cr + 1u, L = len[f], nin = L / bin * bin;     // bytes behind the last whole burst stay queued in the brick: no output
+    if (j >= nin / bin * (bin + 1u)) return;
+    const uint8_t* src = in + in_off[f];
+    const uint32_t k0 = 8u * j;
+    const int i0 = (int)(tx_punct_offset(cr, (int)k0, 0x80000000u) & 0x7FFFFFFFu) - 6, b0 = i0 >> 3;
+    uint32_t w = 0;
+#pragma unroll
+    for (int t = 0; t < 3; t++) { const int b = b0 + t; if (b >= 0 && (uint32_t)b < nin) w |= (uint32_t)src[b] << (8 * t); }
+    w >>= i0 - 8 * b0;                                                           // bit t = input bit i0 + t (0 before the frame: the register starts at 0)
+    const uint32_t ga = (w >> 6) ^ (w >> 4) ^ (w >> 3) ^ (w >> 1) ^ w;           // bit d = generator A (133) at input bit i0 + 6 + d
+    const uint32_t gb = (w >> 6) ^ (w >> 5) ^ (w >> 4) ^ (w >> 3) ^ w;           // generator B (171)
+    unsigned o = 0;
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        const uint32_t p = tx_punct_offset(cr, (int)(k0 + b), 0x80000000u);
+        const int d = (int)(p & 0x7FFFFFFFu) - 6 - i0;
+        o |= ((((p >> 31) ? gb : ga) >> d) & 1u) << b;
+    }
+    out[(size_t)out_off[f] + j] = (uint8_t)o;
+}
+
+// ---- T11aInterleave*: bit k of a symbol goes to bit j(k) (T.deint holds j(k): the receiver's de-interleaver reads it the other way round).  A tile of 32 symbols is
+// staged in LDS; a thread makes whole output bytes through the inverted map.
+constexpr int kModSyms = 32;
+template <int NB>
+__global__ void __launch_bounds__(256) k_mod_interleave(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n, Tables T)
+{
+    constexpr int NCB = 48 * NB, SB = 6 * NB;                                    // coded bits, bytes per symbol
+    __shared__ alignas(16) uint32_t s_in[kModSyms * SB / 4];
+    __shared__ alignas(16) uint32_t s_out[kModSyms * SB / 4];
+    __shared__ uint16_t s_inv[NCB];
+    const int tid = threadIdx.x;
+    const uint32_t s0 = blockIdx.x * kModSyms;
+    const int ns = (int)min((uint32_t)kModSyms, n - s0), nbytes = ns * SB;
+    constexpr int di = NB == 1 ? 0 : NB == 2 ? 1 : NB == 4 ? 2 : 3;
+    for (int k = tid; k < NCB; k += 256) s_inv[T.deint[di * 288 + k]] = (uint16_t)k;
+    mod_tile_load(s_in, in + (size_t)s0 * SB, nbytes, tid);
+    __syncthreads();
+    const uint8_t* b = reinterpret_cast<const uint8_t*>(s_in);
+    for (int q = tid; q < nbytes; q += 256) {
+        const int sym = q / SB, p0 = 8 * (q - sym * SB);
+        unsigned o = 0;
+#pragma unroll
+        for (int t = 0; t < 8; t++) { const int k = s_inv[p0 + t]; o |= ((b[sym * SB + (k >> 3)] >> (k & 7)) & 1u) << t; }
+        reinterpret_cast<uint8_t*>(s_out)[q] = (uint8_t)o;
+    }
+    __syncthreads();
+    mod_tile_store(out + (size_t)s0 * SB, s_out, nbytes, tid);
+}
+template __global__ void k_mod_interleave<1>(const uint8_t*, uint8_t*, uint32_t, Tables);
+template __global__ void k_mod_interleave<2>(const uint8_t*, uint8_t*, uint32_t, Tables);
+template __global__ void k_mod_interleave<4>(const uint8_t*, uint8_t*, uint32_t, Tables);
+template __global__ void k_mod_interleave<6>(const uint8_t*, uint8_t*, uint32_t, Tables);
+
+// ---- TMap11a*<MOD>: carrier c of a symbol takes bits c N_BPSC .. of its 6 N_BPSC bytes, the first half for I and the second for Q (tx_axis_level; BPSK: +-MOD on I).
+// A thread makes four carriers in a row and stores them as one 16-byte word: 12 per symbol.
+template <int NB>
+__global__ void __launch_bounds__(256) k_mod_map(const uint8_t* __restrict__ in, uint32_t* __restrict__ out, int mod, uint32_t n)
+{
+    constexpr int SB = 6 * NB, M = NB == 1 ? 1 : NB / 2;
+    __shared__ alignas(16) uint32_t s_in[kModSyms * SB / 4];
+    const int tid = threadIdx.x;
+    const uint32_t s0 = blockIdx.x * kModSyms;
+    const int ns = (int)min((uint32_t)kModSyms, n - s0);
+    mod_tile_load(s_in, in + (size_t)s0 * SB, ns * SB, tid);
+    __syncthreads();
+    const int d2 = 2 * mod, lvl0 = -((1 << M) - 1) * mod;
+    const uint32_t off[3] = { 0u, 1u, 2u };
+    uint4* o4 = reinterpret_cast<uint4*>(out + (size_t)s0 * 48);
+    for (int q = tid; q < ns * 12; q += 256) {                                   // carriers 4 q .. 4 q + 3 of the tile; the tile's bits are one string (48 NB per symbol)
+        uint32_t v[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const uint32_t bit0 = (uint32_t)(4 * q + t) * NB;
+            if (NB == 1) v[t] = pack(mk(tx_gen_bit(s_in, bit0) ? mod : -mod, 0));
+            else v[t] = pack(mk(tx_axis_level(s_in, bit0, off, M, d2, lvl0), tx_axis_level(s_in, bit0 + M, off, M, d2, lvl0)));   // (short)(l * kmod): pack wraps
+        }
+        o4[q] = uint4{v[0], v[1], v[2], v[3]};
+    }
+}
+template __global__ void k_mod_map<1>(const uint8_t*, uint32_t*, int, uint32_t);
+template __global__ void k_mod_map<2>(const uint8_t*, uint32_t*, int, uint32_t);
+template __global__ void k_mod_map<4>(const uint8_t*, uint32_t*, int, uint32_t);
+template __global__ void k_mod_map<6>(const uint8_t*, uint32_t*, int, uint32_t);
+
+// ---- T11aAddPilot: 16 lanes per symbol, 16 symbols per pass of a workgroup; the 48 carriers arrive as twelve 16-byte loads, bins 4 e .. 4 e + 3 leave as one store.
+// Workgroup (f, y) takes passes y, y + gridDim.y, .. of frame f.  The symbol at position j of its frame (pos0[f] + its index in the table's range; pos0 null: 0) has
+// polarity PilotSgn[127] for j = 0 and PilotSgn[(j - 1) mod 127] behind it: m_PilotIndex starts at 127 and wraps at 127.
+__global__ void __launch_bounds__(256) k_mod_add_pilot(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const uint32_t* __restrict__ first,
+        const uint32_t* __restrict__ nsym, const uint32_t* __restrict__ pos0, uint32_t nframes, int mod)
+{
+    __shared__ alignas(16) uint32_t s_all[16][48];
+    const uint32_t f = blockIdx.x;
+    if (f >= nframes) return;
+    const int g = threadIdx.x >> 4, e = threadIdx.x & 15;
+    uint32_t* s = s_all[g];
+    const uint32_t sf = first[f], ns = nsym[f], p0 = pos0 ? pos0[f] : 0u;
+    int src[4];                                                                  // bin 4 e + q: carrier index in the input, -1 = a pilot, -2 = zero
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int b = 4 * e + q;
+        if (b == 7 || b == 21 || b == 43 || b == 57) src[q] = -1;
+        else if (b >= 1 && b <= 26) src[q] = 24 + (b - 1) - (b > 7) - (b > 21);
+        else if (b >= 38) src[q] = b - 38 - (b > 43) - (b > 57);
+        else src[q] = -2;
+    }
+    for (uint32_t t0 = blockIdx.y * 16u; t0 < ns; t0 += gridDim.y * 16u) {      // (uniform per workgroup: every lane keeps the barriers company)
+        const uint32_t t = t0 + (uint32_t)g;
+        const bool active = t < ns;
+        const size_t sym = (size_t)sf + t;
+        uint4 v = uint4{0, 0, 0, 0};
+        if (active && e < 12) v = reinterpret_cast<const uint4*>(in + sym * 48)[e];
+        wave_lds_sync();
+        if (e < 12) reinterpret_cast<uint4*>(s)[e] = v;
+        wave_lds_sync();
+        const uint32_t j = p0 + t;
+        const int p = pilot_sgn(j == 0 ? 127u : (j - 1u) % 127u) ? -mod : mod;
+        uint32_t o[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int b = 4 * e + q;
+            o[q] = src[q] >= 0 ? s[src[q]] : src[q] == -1 ? pack(mk(b == 21 ? -p : p, 0)) : 0u;
+        }
+        if (active) reinterpret_cast<uint4*>(out + sym * 64)[e] = uint4{o[0], o[1], o[2], o[3]};
+    }
+}
+
+// ---- TIFFTx: 32 lanes per symbol, 8 symbols per tile, 4 tiles per workgroup, every tile's load in flight before the first butterfly (k_fft128_batch's shape).  Lanes
+// 0 .. 15 bring bins 4 e .. 4 e + 3 as one 16-byte load and put them at bins 0 .. 31 / 96 .. 127 of the group's swizzled 128-word buffer, lanes 16 .. 31 clear the 64 bins
+// between; tx_ifft128<true> transforms in place; output sample i is time sample (i + 96) & 127, >> 4, so lane e stores samples 4 e .. 4 e + 3 and, for e < 8, the same
+// four time samples as 128 + 4 e .. (the guard interval is the symbol's last 32 samples in front): each output sample is written once, 16 bytes per lane.  Samples 0, 1, 158
+// and 159 are halved (the window).
+constexpr int kIfftTiles = 4;
+__device__ __forceinline__ uint4 mod_ifftx_quad(const uint32_t* s, int e, int sh01, int sh23)
+{
+    const uint32_t n0 = (uint32_t)(4 * e + 96);
+    return uint4{ pk_sra(tx_tsample<true>(s, n0), sh01), pk_sra(tx_tsample<true>(s, n0 + 1), sh01), pk_sra(tx_tsample<true>(s, n0 + 2), sh23), pk_sra(tx_tsample<true>(s, n0 + 3), sh23) };
+}
+__global__ void __launch_bounds__(256) k_mod_ifftx(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n, Tables T)
+{
+    __shared__ alignas(16) uint32_t s_all[8][128];
+    const int g = threadIdx.x >> 5, e = threadIdx.x & 31;
+    const Fft128Tw tw = fft128_twiddles(T, e);
+    uint32_t* s = s_all[g];
+    uint4 v[kIfftTiles];
+#pragma unroll
+    for (int t = 0; t < kIfftTiles; t++) {
+        const uint32_t i = (blockIdx.x * kIfftTiles + t) * 8 + g;
+        v[t] = (i < n && e < 16) ? reinterpret_cast<const uint4*>(in)[(size_t)i * 16 + e] : uint4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int t = 0; t < kIfftTiles; t++) {
+        const uint32_t i = (blockIdx.x * kIfftTiles + t) * 8 + g;
+        wave_lds_sync();
+        {
+            const int b0 = e < 16 ? bin128(4 * e) : 32 + 4 * (e - 16);               // four bins in a row on the 128-point grid; the swizzle moves them one by one
+            const uint32_t w[4] = { v[t].x, v[t].y, v[t].z, v[t].w };
+#pragma unroll
+            for (int q = 0; q < 4; q++) s[fft128_swz(b0 + q)] = w[q];
+        }
+        tx_ifft128<true>(s, e, tw);
+        wave_lds_sync();
+        if (i < n) {
+            uint4* o = reinterpret_cast<uint4*>(out + (size_t)i * 160);
+            o[e] = mod_ifftx_quad(s, e, e == 0 ? 5 : 4, 4);
+            if (e < 8) o[32 + e] = mod_ifftx_quad(s, e, 4, e == 7 ? 5 : 4);
+        }
+    }
+}
+
+// ---- TUpsample40MTo44M: y[11 m + r] = int16(mh(x[10 m + r - 1], S(r)) + mh(x[10 m + r], S(11 - r))) per 160-sample block, nothing carried between blocks (the closed form:
+// sora_hip.h at sora_hip_tx11a44).  A tile of 8 blocks in LDS, 161 words each: x[160] is the next block's first sample where sees_next says so, else 0.
+constexpr int kUpBlocks = 8;
+__device__ __forceinline__ int mod_mulhrs(int a, int c) { return (__mul24(a, c) + 16384) >> 15; }   // _mm_mulhrs_epi16 (16-bit sample x 15-bit weight: a 24-bit multiply)
+__global__ void __launch_bounds__(256) k_mod_upsample(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const uint8_t* __restrict__ sees_next, uint32_t nblocks)
+{
+    __shared__ alignas(16) uint32_t s_x[kUpBlocks][164];
+    const int tid = threadIdx.x;
+    const uint32_t b0 = blockIdx.x * kUpBlocks;
+    const int nb = (int)min((uint32_t)kUpBlocks, nblocks - b0);
+    const uint4* in4 = reinterpret_cast<const uint4*>(in + (size_t)b0 * 160);
+    for (int q = tid; q < nb * 40; q += 256) { const int blk = q / 40; reinterpret_cast<uint4*>(s_x[blk])[q - 40 * blk] = in4[q]; }
+    if (tid < nb) {
+        const uint32_t b = b0 + (uint32_t)tid;
+        s_x[tid][160] = (sees_next && b + 1 < nblocks && sees_next[b]) ? in[(size_t)(b + 1) * 160] : 0u;
+    }
+    __syncthreads();
+    // Lane t < 220 makes word w = t % 44 (outputs 4 w .. 4 w + 3) of blocks t / 44 and t / 44 + 5: which two inputs an output lies between and their weights depend on
+    // w alone, so they are worked out once.
+    if (tid >= 220) return;
+    const int w = tid % 44;
+    int ia[4], ib[4], cl[4], ch[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int j = 4 * w + k, m = j / 11, r = j - 11 * m;
+        ib[k] = j - m; ia[k] = max(j - m - 1, 0);
+        cl[k] = r * 32767 / 11; ch[k] = (11 - r) * 32767 / 11;
+    }
+    uint4* o4 = reinterpret_cast<uint4*>(out + (size_t)b0 * 176);
+    for (int blk = tid / 44; blk < nb; blk += 5) {
+        const uint32_t* x = s_x[blk];
+        uint32_t y[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const cpx a = unpack(x[ia[k]]), c = unpack(x[ib[k]]);
+            y[k] = pack(mk(mod_mulhrs(a.re, cl[k]) + mod_mulhrs(c.re, ch[k]), mod_mulhrs(a.im, cl[k]) + mod_mulhrs(c.im, ch[k])));         // (wraps like the brick's 16-bit add)
+        }
+        o4[blk * 44 + w] = uint4{y[0], y[1], y[2], y[3]};
+    }
+}
+
+// ---- TPackSample16to8: _mm_packs_epi16 over bursts of 8 samples: a thread takes one burst, two 16-byte loads and one store
+__device__ __forceinline__ uint32_t mod_sat8x2(uint32_t v)                       // COMPLEX16 -> COMPLEX8 in the low 16 bits
+{
+    const s16x2_t lo = { (short)-128, (short)-128 }, hi = { (short)127, (short)127 };
+    const uint32_t c = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_elementwise_max(__builtin_bit_cast(s16x2_t, v), lo), hi));
+    return (c & 0xFFu) | ((c >> 8) & 0xFF00u);
+}
+__global__ void __launch_bounds__(256) k_mod_pack16to8(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t nbursts)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nbursts) return;
+    const uint4 a = reinterpret_cast<const uint4*>(in)[2 * i], b = reinterpret_cast<const uint4*>(in)[2 * i + 1];
+    reinterpret_cast<uint4*>(out)[i] = uint4{ mod_sat8x2(a.x) | (mod_sat8x2(a.y) << 16), mod_sat8x2(a.z) | (mod_sat8x2(a.w) << 16),
+                                              mod_sat8x2(b.x) | (mod_sat8x2(b.y) << 16), mod_sat8x2(b.z) | (mod_sat8x2(b.w) << 16) };
+}
+
+// ---- TTS11aSrc: the 640 samples k_tx_preamble builds, in the 16 bits the source hands on (that kernel keeps them in LDS and writes their 8-bit form).  Every workgroup
+// builds them (two IFFTs) and writes copies blockIdx.x, blockIdx.x + gridDim.x, ..
+constexpr uint64_t mod_lts_bits()                                                // LTS_Positive_table (ieee80211const.h:23-28), entry i = bit i
+{
+    const int t[64] = { 0,1,0,0,1,1,0,1,0,1,0,0,0,0,0,1, 1,0,0,1,0,1,0,1,1,1,1,0,0,0,0,0, 0,0,0,0,0,0,1,1,0,0,1,1,0,1,0,1, 1,1,1,1,1,0,0,1,1,0,1,0,1,1,1,1 };
+    uint64_t v = 0;
+    for (int i = 0; i < 64; i++) v |= (uint64_t)t[i] << i;
+    return v;
+}
+constexpr uint64_t kModLtsPos = mod_lts_bits();
+__global__ void __launch_bounds__(64) k_mod_preamble(uint32_t* __restrict__ out, uint32_t ncopies, Tables T)
+{
+    constexpr int kMod = 10720;                                                  // bpsk_mod_11a
+    __shared__ uint32_t s_f[2][128];
+    __shared__ uint32_t s_t[2][128];
+    __shared__ alignas(16) uint32_t s_lut[640];
+    const int g = threadIdx.x >> 5, e = threadIdx.x & 31;
+    auto sync = []() { __syncthreads(); };
+    for (int i = e; i < 128; i += 32) s_f[g][i] = 0;
+    sync();
+    if (g == 0 && e < 12) {                                                      // short training symbol: 12 carriers
+        const int m = (int)(uint16_t)(1.0 * kMod * 1.472);
+        const int idx[12] = { 4, 8, 12, 16, 20, 24, 104, 108, 112, 116, 120, 124 };
+        const int sg[12]  = { -1, -1, 1, 1, 1, 1, 1, -1, 1, -1, -1, 1 };
+        const int v = w16(sg[e] * m); s_f[0][idx[e]] = pack(mk(v, v));
+    }
+    if (g == 1) {                                                                // long training symbol
+        for (int i = 1 + e; i <= 26; i += 32) s_f[1][i] = pack(mk(((kModLtsPos >> i) & 1) ? kMod : -kMod, 0));
+        for (int i = 64 - 26 + e; i < 64; i += 32) s_f[1][i + 64] = pack(mk(((kModLtsPos >> i) & 1) ? kMod : -kMod, 0));
+    }
+    sync();
+    cpx x[4], y[4];
+#pragma unroll
+    for (int m = 0; m < 4; m++) x[m] = unpack(s_f[g][e + 32 * m]);
+    fft128_group<true>(x, y, s_f[g], e, T, sync);
+#pragma unroll
+    for (int q = 0; q < 4; q++) s_t[g][e + 32 * q] = pack(sra(y[q], 4));
+    sync();
+    // STS: 128 samples repeated periodically over 320; LTS: GI2 (last 64 of the symbol) + two copies of 128; the first and last two samples of each half halved
+    for (int i = threadIdx.x; i < 640; i += 64) {
+        cpx v = unpack(i < 320 ? s_t[0][i & 127] : i < 384 ? s_t[1][64 + (i - 320)] : s_t[1][(i - 384) & 127]);
+        if (i == 0 || i == 1 || i == 318 || i == 319 || i == 320 || i == 321 || i == 638 || i == 639) v = sra(v, 1);
+        s_lut[i] = pack(v);
+    }
+    sync();
+    for (uint32_t c = blockIdx.x; c < ncopies; c += gridDim.x) {
+        uint4* o = reinterpret_cast<uint4*>(out + (size_t)c * 640);
+        for (int q = threadIdx.x; q < 160; q += 64) o[q] = reinterpret_cast<const uint4*>(s_lut)[q];
+    }
+}
+
+}  // namespace sora

@@ -135,6 +135,17 @@ struct TxArgs {                // sora_hip_tx11a (k_tx.hip)
 __global__ void k_tx_preamble(int8_t* out8, int8_t* out44, Tables T);   // 640 samples at 40 MHz, 704 at 44 MHz
 template <bool UP44> __global__ void k_tx11a(TxArgs A);                 // UP44: TUpsample40MTo44M in front of the 16 -> 8 bit pack (sora_hip_tx11a44)
 
+// ---- the 802.11a modulation graph's bricks as stages (k_mod.hip)
+__global__ void k_mod_scramble(const uint8_t* in, uint8_t* out, const uint32_t* off, const uint32_t* len, const uint32_t* tail, const uint8_t* seed, uint32_t nframes, uint32_t chunks, Tables T);
+__global__ void k_mod_encode(const uint8_t* in, const uint32_t* in_off, const uint32_t* len, int cr, uint8_t* out, const uint32_t* out_off, uint32_t nframes, uint32_t chunks);
+template <int NB> __global__ void k_mod_interleave(const uint8_t* in, uint8_t* out, uint32_t n, Tables T);
+template <int NB> __global__ void k_mod_map(const uint8_t* in, uint32_t* out, int mod, uint32_t n);
+__global__ void k_mod_add_pilot(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* nsym, const uint32_t* pos0, uint32_t nframes, int mod);
+__global__ void k_mod_ifftx(const uint32_t* in, uint32_t* out, uint32_t n, Tables T);
+__global__ void k_mod_upsample(const uint32_t* in, uint32_t* out, const uint8_t* sees_next, uint32_t nblocks);
+__global__ void k_mod_pack16to8(const uint32_t* in, uint32_t* out, uint64_t nbursts);
+__global__ void k_mod_preamble(uint32_t* out, uint32_t ncopies, Tables T);
+
 // ---- 802.11n 2x2 transmitter (k_tx11n.hip)
 struct Tx11nArgs {             // sora_hip_tx11n
     const uint8_t*  mpdu;      // MPDUs without FCS, frame f at mpdu + off[f]

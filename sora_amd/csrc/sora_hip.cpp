@@ -1729,6 +1729,153 @@ int sora_hip_tx11a44(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_
     return tx11a_launch(true, "sora_hip_tx11a44: null pointer", d_mpdu, d_off, d_len, d_rate_kbps, d_seed, nframes, d_out, d_out_off, stream);
 }
 
+// ---- the 802.11a modulation graph's bricks as stages (k_mod.hip)
+#define MOD_STAGE_ENTRY(who, nullcond, count) \
+    if (nullcond) return fail(SORA_ERR_INVALID_PARAM, who ": null pointer"); \
+    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path"); \
+    if ((count) == 0) return SORA_OK;
+static bool mod_nbpsc_ok(int nb) { return nb == 1 || nb == 2 || nb == 4 || nb == 6; }
+// workgroups of 256 positions per frame, frames x chunks in one grid dimension
+static bool mod_grid(size_t nframes, size_t max_items, uint32_t* chunks, unsigned* grid)
+{
+    const size_t c = (max_items + 255) / 256, g = nframes * c;
+    if (c == 0 || g >= (1ull << 31)) return false;
+    *chunks = (uint32_t)c; *grid = (unsigned)g;
+    return true;
+}
+
+int sora_hip_scramble11a(const uint8_t* d_in, uint8_t* d_out, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_tail, const uint8_t* d_seed,
+                         size_t nframes, size_t max_len, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_scramble11a", !d_in || !d_out || !d_off || !d_len || !d_seed, nframes)
+    if (max_len == 0) return SORA_OK;
+    uint32_t chunks; unsigned grid;
+    if (!mod_grid(nframes, max_len, &chunks, &grid)) return fail(SORA_ERR_CAPACITY, "sora_hip_scramble11a: nframes x max_len is too large for one call");
+    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    hipLaunchKernelGGL(k_mod_scramble, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_in, d_out, d_off, d_len, d_tail, d_seed, (uint32_t)nframes, chunks, D->T);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_conv_encode11a(const uint8_t* d_in, const uint32_t* d_in_off, const uint32_t* d_len, int code_rate, uint8_t* d_out, const uint32_t* d_out_off,
+                            size_t nframes, size_t max_len, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_conv_encode11a", !d_in || !d_in_off || !d_len || !d_out || !d_out_off, nframes)
+    if (code_rate != SORA_CR_12 && code_rate != SORA_CR_23 && code_rate != SORA_CR_34) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_conv_encode11a: bad code rate");
+    if (max_len >= (1u << 27)) return fail(SORA_ERR_CAPACITY, "sora_hip_conv_encode11a: a frame of 128 MiB or more");
+    const size_t bin = (size_t)code_rate + 1, max_out = max_len / bin * (bin + 1);
+    if (max_out == 0) return SORA_OK;
+    uint32_t chunks; unsigned grid;
+    if (!mod_grid(nframes, max_out, &chunks, &grid)) return fail(SORA_ERR_CAPACITY, "sora_hip_conv_encode11a: nframes x max_len is too large for one call");
+    hipLaunchKernelGGL(k_mod_encode, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_in, d_in_off, d_len, code_rate, d_out, d_out_off, (uint32_t)nframes, chunks);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_interleave11a(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, size_t nsym, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_interleave11a", !d_in || !d_out, nsym)
+    if (!mod_nbpsc_ok(n_bpsc)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_interleave11a: n_bpsc must be 1, 2, 4 or 6");
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_interleave11a: buffers must be 16-byte aligned");
+    if (nsym >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_interleave11a: too many symbols for one call");
+    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    const dim3 grid((unsigned)((nsym + 31) / 32)); hipStream_t st = (hipStream_t)stream;
+    switch (n_bpsc) {
+    case 1: hipLaunchKernelGGL(k_mod_interleave<1>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)nsym, D->T); break;
+    case 2: hipLaunchKernelGGL(k_mod_interleave<2>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)nsym, D->T); break;
+    case 4: hipLaunchKernelGGL(k_mod_interleave<4>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)nsym, D->T); break;
+    default: hipLaunchKernelGGL(k_mod_interleave<6>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)nsym, D->T); break;
+    }
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_map11a(const uint8_t* d_in, sora_complex16* d_out, int n_bpsc, int mod, size_t nsym, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_map11a", !d_in || !d_out, nsym)
+    if (!mod_nbpsc_ok(n_bpsc) || mod < 0 || mod > 32767) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11a: n_bpsc must be 1, 2, 4 or 6 and mod 0 .. 32767");
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11a: buffers must be 16-byte aligned");
+    if (nsym >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_map11a: too many symbols for one call");
+    if (mod == 0) mod = n_bpsc == 1 ? 10720 : n_bpsc == 2 ? (short)(10720 / 1.414) : n_bpsc == 4 ? (short)(10720 / 3.162) : (short)(10720 / 6.481);   // mapper11a.hpp:8-11
+    const dim3 grid((unsigned)((nsym + 31) / 32)); hipStream_t st = (hipStream_t)stream; uint32_t* out = reinterpret_cast<uint32_t*>(d_out);
+    switch (n_bpsc) {
+    case 1: hipLaunchKernelGGL(k_mod_map<1>, grid, dim3(256), 0, st, d_in, out, mod, (uint32_t)nsym); break;
+    case 2: hipLaunchKernelGGL(k_mod_map<2>, grid, dim3(256), 0, st, d_in, out, mod, (uint32_t)nsym); break;
+    case 4: hipLaunchKernelGGL(k_mod_map<4>, grid, dim3(256), 0, st, d_in, out, mod, (uint32_t)nsym); break;
+    default: hipLaunchKernelGGL(k_mod_map<6>, grid, dim3(256), 0, st, d_in, out, mod, (uint32_t)nsym); break;
+    }
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_add_pilot11a_from(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_pos0,
+                               size_t nframes, int bpsk_mod, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_add_pilot11a", !d_in || !d_out || !d_first || !d_nsym, nframes)
+    if (bpsk_mod < 0 || bpsk_mod > 32767) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11a: bpsk_mod must be 0 .. 32767");
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11a: buffers must be 16-byte aligned");
+    if (nframes >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_add_pilot11a: too many frames for one call");
+    // the frames' lengths are device memory: a batch of few frames gets several workgroups per frame, each striding over the frame's passes of 16 symbols
+    const unsigned gy = nframes >= 2048 ? 1u : (unsigned)std::min<size_t>(64, 2048 / nframes);
+    hipLaunchKernelGGL(k_mod_add_pilot, dim3((unsigned)nframes, gy), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
+                       reinterpret_cast<uint32_t*>(d_out), d_first, d_nsym, d_pos0, (uint32_t)nframes, bpsk_mod ? bpsk_mod : 10720);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+int sora_hip_add_pilot11a(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, size_t nframes, int bpsk_mod, void* stream)
+{
+    return sora_hip_add_pilot11a_from(d_in, d_out, d_first, d_nsym, nullptr, nframes, bpsk_mod, stream);
+}
+
+int sora_hip_ifftx11a(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_ifftx11a", !d_in || !d_out, nsym)
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_ifftx11a: buffers must be 16-byte aligned");
+    if (nsym >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_ifftx11a: too many symbols for one call");
+    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    hipLaunchKernelGGL(k_mod_ifftx, dim3((unsigned)((nsym + 31) / 32)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
+                       reinterpret_cast<uint32_t*>(d_out), (uint32_t)nsym, D->T);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_upsample40to44(const sora_complex16* d_in, sora_complex16* d_out, const uint8_t* d_sees_next, size_t nblocks, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_upsample40to44", !d_in || !d_out, nblocks)
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_upsample40to44: buffers must be 16-byte aligned");
+    if (nblocks >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_upsample40to44: too many blocks for one call");
+    hipLaunchKernelGGL(k_mod_upsample, dim3((unsigned)((nblocks + 7) / 8)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
+                       reinterpret_cast<uint32_t*>(d_out), d_sees_next, (uint32_t)nblocks);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_pack16to8(const sora_complex16* d_in, int8_t* d_out, size_t nsamples, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_pack16to8", !d_in || !d_out, nsamples)
+    if (nsamples % 8) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_pack16to8: nsamples must be a multiple of 8 (the brick's burst)");
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_pack16to8: buffers must be 16-byte aligned");
+    const uint64_t nb = nsamples / 8;
+    if ((nb + 255) / 256 >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_pack16to8: too many samples for one call");
+    hipLaunchKernelGGL(k_mod_pack16to8, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
+                       reinterpret_cast<uint32_t*>(d_out), nb);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_preamble11a(sora_complex16* d_out, size_t ncopies, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_preamble11a", !d_out, ncopies)
+    if ((uintptr_t)d_out & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble11a: the buffer must be 16-byte aligned");
+    if (ncopies >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_preamble11a: too many copies for one call");
+    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    hipLaunchKernelGGL(k_mod_preamble, dim3((unsigned)std::min<size_t>(ncopies, 2048)), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<uint32_t*>(d_out),
+                       (uint32_t)ncopies, D->T);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+#undef MOD_STAGE_ENTRY
+
 // ---- 802.11n 2x2 transmitter
 // The fixed fields of LSrc / HTSrc (preamble11n.hpp:8-83), per chain: L-STF (320), L-LTF (320), HT-STF, HT-LTF1, HT-LTF2 (160 each).
 // Each is round(s * sum_k X_k exp(+2 pi i k n / 128)) in double precision -- the standard's frequency-domain sequence X in bins -26..26
