@@ -105,6 +105,7 @@ typedef struct {                    /* one row per frame the reference's RxThrea
 } sora_frame_result;
 
 #define SORA_ROW_TRUNCATED 1u
+#define SORA_ROW_SHORT_PREAMBLE 2u       /* 802.11b rows: the frame came behind the short preamble (sora_rx11b_set_preamble) */
 
 /* create/destroy the graph: CreateDemodGraph11a_40M + BB11aDemodCtx.Init  /  IReferenceCounting::Release */
 int  sora_rx_create(const sora_rx_cfg* cfg, sora_rx_t** out);
@@ -517,8 +518,8 @@ int sora_hip_tx_ht40_joint(const uint8_t* d_mpdu, const uint32_t* d_off, const u
  * Frame f: MPDU WITHOUT FCS (the FCS is appended) of d_len[f] bytes at d_mpdu + d_off[f], rate d_rate_kbps[f] (1000, 2000, 5500 or
  * 11000).  Writes sora_hip_tx11b_samples(len, rate) COMPLEX8 samples at 44 MHz -- what TModSink receives, tx_sample_cnt() -- at sample
  * d_out_off[f] of d_out (64-bit offsets: a batch may exceed 2^31 samples).
- * Accepted: those four rates and 1..4092 bytes without FCS; sora_hip_tx11b_samples is 0 for anything else (the short preamble is not
- * offered: the reference refuses it).  The rate and length arrays are device memory: a frame whose rate or length is not accepted gets
+ * Accepted: those four rates and 1..4092 bytes without FCS; sora_hip_tx11b_samples is 0 for anything else.  The rate and length
+ * arrays are device memory: a frame whose rate or length is not accepted gets
  * nothing written (its output range and d_phase_out[f] stay as they are), and the other frames of the call are not affected.
  * Differential phase: the reference's four spreaders share CF_DifferentialMap::last_phase (0: 0, 1: -pi/2, 2: pi/2, 3: pi), and no
  * reset touches it, so one reference process carries it from frame to frame; the preamble reads only its low bit, so a frame comes out
@@ -530,6 +531,18 @@ size_t sora_hip_tx11b_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps);
 int sora_hip_tx11b(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps,
                    const uint8_t* d_phase_in, uint8_t* d_phase_out, size_t nframes,
                    int8_t* d_out, const uint64_t* d_out_off, void* stream);
+/* The same with a preamble kind per frame: d_preamble[f] = 0, the long preamble (sora_hip_tx11b's frame, byte for byte), or 1, the SHORT
+ * preamble, which the reference's source brick refuses (TBB11bSrc::PreparePLCPHeader, PHY_11b.hpp:115-119: "not supported yet") although
+ * TBB11bMRSelect already counts its header bytes (:224-229) and kernel/inc/dot11_plcp.h holds its constants.  Short PPDU: SYNC = 7 bytes of
+ * 0x00, SFD 0x05CF (bytes 0xCF, 0x05), both at 1 Mbps DBPSK; the six PLCP header bytes (built as for the long preamble) at 2 Mbps DQPSK;
+ * MPDU + FCS at 2000, 5500 or 11000 kbps (1000 is not accepted behind a short preamble); the scrambler starts from 0x1B; the differential
+ * phase runs on from SFD to header to payload, d_phase_in / d_phase_out as above.  Sample count: 96 x 44 + (len + 4) x S + 24.
+ * d_preamble NULL: every frame long, sora_hip_tx11b itself.  A kind other than 0 or 1 is treated like a rate that is not accepted:
+ * sora_hip_tx11b_pre_samples is 0 and nothing is written. */
+size_t sora_hip_tx11b_pre_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps, uint32_t preamble);
+int sora_hip_tx11b_pre(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_preamble,
+                       const uint8_t* d_phase_in, uint8_t* d_phase_out, size_t nframes,
+                       int8_t* d_out, const uint64_t* d_out_off, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 802.11n 2x2, stage level (the whole-path graph is sora_rx11n_* below).  Batched bricks, n symbols per call:
@@ -824,8 +837,8 @@ int  sora_shard_gather_results_mpdu(sora_shard_t* sh, sora_rx_t* rx, int ticket,
  * TCCK5P5Decoder / TCCK11Decoder (kernel/bb/Brick11/src/cck.hpp), TDesc741, TBB11bPlcpParser, TBB11bFrameSink.  cfg->sample_rate_mhz must be 44; capture lengths are whole 28-sample bursts.
  * Result rows: end_sample = CF_MemSamples::mem_sample_index() when the harness sees the event (44 MHz samples);
  * error_code also takes SORA_E_SFD_FAIL / SORA_E_SFD_TIMEOUT / SORA_E_SYNC_TIMEOUT; crc32 = the reference's FCS word (three
- * FCS bytes and one stale buffer byte, PHY_11b.hpp:725-731); start_sample, nsym and cfo_est are 0.  Long preamble; 1 Mbps
- * DBPSK, 2 Mbps DQPSK, 5.5 and 11 Mbps CCK payloads (all four rates of the reference graph).
+ * FCS bytes and one stale buffer byte, PHY_11b.hpp:725-731); start_sample, nsym and cfo_est are 0.  Long preamble (the short one too with
+ * sora_rx11b_set_preamble); 1 Mbps DBPSK, 2 Mbps DQPSK, 5.5 and 11 Mbps CCK payloads (all four rates of the reference graph).
  * Two kernels per call: the first has no CCK decoders in it (more resident waves) and hands a capture over when a header announces
  * 5.5 / 11 Mbps; the second redoes the handed-over captures.
  * ------------------------------------------------------------------------------------------------ */
@@ -856,6 +869,23 @@ int   sora_rx11b_calls_in_flight(sora_rx11b_t* rx);            /* how many calls
  * it) and says "more than half", the following calls take the single pass, except every 16th, which measures again; negative: query.  Returns the
  * previous setting (0, 1 or 2). */
 int   sora_rx11b_set_single_pass(sora_rx11b_t* rx, int enable);
+/* Which preambles the graph accepts.  mode 0 (DEFAULT): long only -- the reference's graph, whose TSFDSync knows one SFD; nothing changes, not a
+ * row, not a byte.  mode 1: long and short -- the reference's graph with TSFDSync EXTENDED (the one place it moves; the front end locks well
+ * inside the short SYNC and TDesc741 is self-synchronising, so nothing else in front changes).  THE RULE, per despread symbol, with a new state
+ * bit_zero_found beside bit_one_found (both cleared by the graph's reset):
+ *   - while neither is set: a window (the 16 most recent descrambled bits) of 0xFFFF sets bit_one_found, as in the reference; a window of
+ *     0x0000 sets bit_zero_found once 16 symbols have gone in (the window starts out as zeros: until it is full, "all zeros" says nothing).
+ *     The first to appear decides: the two are exclusive;
+ *   - bit_one_found set: 0xF3A0 -> RATE_1M, any window other than 0xFFFF and 0xF3A0 counts towards bit_err_cnt (> 32: SFD_FAIL), as in the reference;
+ *   - bit_zero_found set: 0x05CF -> the rate selector goes to RATE_2M with plcp_data still 0, so the six header bytes arrive through TDQPSKDemap
+ *     (first reference symbol = the SFD's last, CF_DifferentialDemap::last_symbol) -> TDesc741 -> TBB11bPlcpSwitch -> TBB11bPlcpParser, which is
+ *     untouched and sets the payload rate and length as ever; any window other than 0x0000 and 0x05CF counts towards bit_err_cnt, same > 32 rule;
+ *   - the sync_cnt > 128 + 16 timeout (SFD_TIMEOUT) is unchanged.
+ * Every row reported between a short SFD and the graph's next reset carries SORA_ROW_SHORT_PREAMBLE in flags; every other field means what it
+ * means in mode 0.  Both pass plans and all settings of sora_rx11b_set_single_pass carry the mode.  Stream mode works with it unchanged: resume
+ * points lie in plain carrier sense, where both flags are clear, so neither crosses a call.  Switching waits for the calls in flight (a call
+ * runs wholly in one mode).  Negative: query.  Returns the previous mode. */
+int   sora_rx11b_set_preamble(sora_rx11b_t* rx, int mode);
 int   sora_rx11b_wait(sora_rx11b_t* rx, int ticket);
 /* as sora_rx_wait_any: the oldest FINISHED call with an enqueued delivery; it is released and its slot reused first */
 int   sora_rx11b_wait_any(sora_rx11b_t* rx, int* ticket);

@@ -65,12 +65,12 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11a44", "sora_hip_tx11a44_samples",
            "sora_hip_scramble11a", "sora_hip_conv_encode11a", "sora_hip_interleave11a", "sora_hip_map11a", "sora_hip_add_pilot11a", "sora_hip_add_pilot11a_from",
            "sora_hip_ifftx11a", "sora_hip_upsample40to44", "sora_hip_pack16to8", "sora_hip_preamble11a",
-           "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx_ht40", "sora_hip_tx_ht40_samples", "sora_hip_tx11b", "sora_hip_tx11b_samples",
+           "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx_ht40", "sora_hip_tx_ht40_samples", "sora_hip_tx11b", "sora_hip_tx11b_samples", "sora_hip_tx11b_pre", "sora_hip_tx11b_pre_samples",
            "sora_hip_tx_ht40_joint", "sora_hip_tx_ht40_joint_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n", "sora_rx11b_create",
                       "sora_rx11b_destroy", "sora_rx11b_stream", "sora_rx11b_synchronize", "sora_rx11b_process_dev", "sora_rx11b_process", "sora_rx11b_results", "sora_rx11b_ticket",
-                      "sora_rx11b_calls_in_flight", "sora_rx11b_set_single_pass", "sora_rx11b_wait", "sora_rx11b_wait_any", "sora_rx11b_stream_of", "sora_rx11b_results_of",
+                      "sora_rx11b_calls_in_flight", "sora_rx11b_set_single_pass", "sora_rx11b_set_preamble", "sora_rx11b_wait", "sora_rx11b_wait_any", "sora_rx11b_stream_of", "sora_rx11b_results_of",
                       "sora_rx11b_deliver_async", "sora_rx11b_set_stream_mode", "sora_rx11b_stream_consumed", "sora_rx11n_deliver_async",
                       "sora_rx11n_set_stream_mode", "sora_rx11n_stream_consumed", "sora_ht40_deliver_async",
            "sora_rx11n_create", "sora_rx11n_destroy", "sora_rx11n_stream", "sora_rx11n_process_dev", "sora_rx11n_process", "sora_rx11n_results",
@@ -241,6 +241,8 @@ def load(build_if_missing=True):
     L.sora_hip_tx_ht40_joint.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
     L.sora_hip_tx11b_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11b_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11b.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
+    L.sora_hip_tx11b_pre_samples.argtypes = [ctypes.c_uint32] * 3; L.sora_hip_tx11b_pre_samples.restype = ctypes.c_size_t
+    L.sora_hip_tx11b_pre.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
     L.sora_hip_ingest_count.argtypes = [ctypes.c_size_t, ctypes.c_uint]; L.sora_hip_ingest_count.restype = ctypes.c_size_t
     L.sora_hip_ingest.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t,
                                   ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
@@ -264,6 +266,7 @@ def load(build_if_missing=True):
                                      ctypes.c_void_p, ctypes.c_size_t]
     L.sora_rx11b_create.argtypes = [ctypes.POINTER(RxCfg), ctypes.POINTER(ctypes.c_void_p)]
     L.sora_rx11b_set_single_pass.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.sora_rx11b_set_preamble.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.sora_rx11b_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11b_process.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     _res_of = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t]
@@ -570,6 +573,7 @@ class Rx(_Handle):
 ROW_DTYPE = np.dtype([("capture_id", "<u4"), ("start_sample", "<u4"), ("end_sample", "<u4"), ("error_code", "<u4"), ("rate_kbps", "<u4"),
                       ("length", "<u2"), ("nsym", "<u2"), ("crc32", "<u4"), ("cfo_est", "<i2"), ("flags", "<u2"), ("mpdu_offset", "<u4")])   # = sora_frame_result
 ROW_TRUNCATED = 1
+ROW_SHORT_PREAMBLE = 2        # an 802.11b row whose frame came behind the short preamble (Rx11b.set_preamble(1))
 
 
 class HostResults:
@@ -646,6 +650,13 @@ class Rx11b(_Handle):
     def set_single_pass(self, enable=-1):
         """the pass plan: 2 automatic (default), 1 every capture straight through the CCK-capable kernel, 0 always two passes; returns the previous plan"""
         return int(self._L.sora_rx11b_set_single_pass(self._h, int(enable)))
+
+    def set_preamble(self, mode=-1):
+        """which preambles TSFDSync accepts: 0 long only (default, the reference's graph), 1 long and short (rows of short-preamble frames carry
+        ROW_SHORT_PREAMBLE in "flags"); negative: query.  Waits for the calls in flight.  Returns the previous mode."""
+        r = int(self._L.sora_rx11b_set_preamble(self._h, int(mode)))
+        if r < 0: _check(r)
+        return r
 
     def process(self, h_iq, captures):
         a = np.ascontiguousarray(h_iq, np.int16).reshape(-1, 2)
@@ -1507,13 +1518,15 @@ def tx_ht40_joint(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps
 TX11B_RATES = (1000, 2000, 5500, 11000)
 
 
-def tx11b_samples(mpdu_len_nofcs, rate_kbps):
-    """Samples of one 802.11b frame (sora_hip_tx11b_samples); 0 for an unsupported rate or length."""
-    return int(load().sora_hip_tx11b_samples(int(mpdu_len_nofcs), int(rate_kbps)))
+def tx11b_samples(mpdu_len_nofcs, rate_kbps, preamble=0):
+    """Samples of one 802.11b frame (sora_hip_tx11b_pre_samples; preamble 0 = long, 1 = short); 0 for an unsupported rate, length or kind
+    (1000 kbps behind the short preamble is one)."""
+    return int(load().sora_hip_tx11b_pre_samples(int(mpdu_len_nofcs), int(rate_kbps), int(preamble) & 0xFFFFFFFF))
 
 
-def tx11b(mpdus, rates_kbps, phase_in=None, device=0, stream=None, sync=True, gaps=None, return_phase=False):
-    """Modulate a batch of MPDUs (bytes WITHOUT FCS) as 802.11b frames on the GPU (1000, 2000, 5500, 11000 kbps, long preamble).
+def tx11b(mpdus, rates_kbps, phase_in=None, device=0, stream=None, sync=True, gaps=None, return_phase=False, preamble=None):
+    """Modulate a batch of MPDUs (bytes WITHOUT FCS) as 802.11b frames on the GPU (1000, 2000, 5500, 11000 kbps).  preamble: None = every frame behind the
+    long preamble (sora_hip_tx11b); else 0 (long) or 1 (short: 2000, 5500, 11000 kbps only), one value or one per frame (sora_hip_tx11b_pre).
     -> (out, offsets): an int8 CUDA tensor [total,2] COMPLEX8 @44 MHz and the offsets list; frame f occupies samples offsets[f] ..
     offsets[f+1] (gaps[f] zero samples in front of frame f, if given, included at its start).
     phase_in: the reference's last_phase (0..3) at the start of each frame, one value or one per frame (None: 0, a fresh reference
@@ -1523,9 +1536,14 @@ def tx11b(mpdus, rates_kbps, phase_in=None, device=0, stream=None, sync=True, ga
     n = len(mpdus)
     rates = [int(r) for r in rates_kbps] if np.ndim(rates_kbps) else [int(rates_kbps)] * n
     lens = [len(m) for m in mpdus]
-    ns = [tx11b_samples(l, r) for l, r in zip(lens, rates)]
+    kinds = None
+    if preamble is not None:
+        kinds = [int(k) for k in preamble] if np.ndim(preamble) else [int(preamble)] * n
+        if len(kinds) != n or any(k not in (0, 1) for k in kinds):
+            raise SoraError(-1, "tx11b: preamble must hold one kind, 0 (long) or 1 (short), per frame")
+    ns = [tx11b_samples(l, r, k) for l, r, k in zip(lens, rates, kinds or [0] * n)]
     if len(rates) != n or any(v == 0 for v in ns):
-        raise SoraError(-1, "tx11b: unsupported rate or length (1000/2000/5500/11000 kbps, 1..4092 bytes)")
+        raise SoraError(-1, "tx11b: unsupported rate, length or preamble (1000/2000/5500/11000 kbps, 1..4092 bytes; no 1000 kbps behind the short preamble)")
     if phase_in is not None:
         phase_in = [int(p) for p in phase_in] if np.ndim(phase_in) else [int(phase_in)] * n
         if len(phase_in) != n or any(not 0 <= p <= 3 for p in phase_in):
@@ -1544,9 +1562,12 @@ def tx11b(mpdus, rates_kbps, phase_in=None, device=0, stream=None, sync=True, ga
     d_pout = torch.zeros(n, dtype=torch.uint8, device=dev) if return_phase else None
     d_ooff = torch.from_numpy(first.astype(np.int64)).to(dev)
     out = torch.zeros((int(ooff[-1]), 2), dtype=torch.int8, device=dev)
-    _check(load().sora_hip_tx11b(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_rate),
-                                 _dev_ptr(d_pin) if d_pin is not None else None, _dev_ptr(d_pout) if d_pout is not None else None, n,
-                                 _dev_ptr(out), _dev_ptr(d_ooff), _stream_ptr(stream)))
+    tail = (_dev_ptr(d_pin) if d_pin is not None else None, _dev_ptr(d_pout) if d_pout is not None else None, n, _dev_ptr(out), _dev_ptr(d_ooff), _stream_ptr(stream))
+    if kinds is None:
+        _check(load().sora_hip_tx11b(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_rate), *tail))
+    else:
+        d_kind = torch.from_numpy(np.asarray(kinds, np.uint8)).to(dev)
+        _check(load().sora_hip_tx11b_pre(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_rate), _dev_ptr(d_kind), *tail))
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     if return_phase:

@@ -62,7 +62,8 @@ __global__ void __launch_bounds__(1024) k_dense_rows(const Rx11bRow* __restrict_
             uint16_t tflags = 0;
             // (40 MHz HT: capture_id = frame id, start_sample = spatial stream, rate, symbols; a raw-capture call's truncation flag)
             if (tmpl) { o = tmpl[(size_t)c * mf + i]; tflags = o.flags; }
-            else { o.capture_id = caps[c].capture_id; o.start_sample = 0; o.nsym = 0; o.cfo_est = 0; o.rate_kbps = r.rate_kbps; o.end_sample = r.end_sample; }
+            else { o.capture_id = caps[c].capture_id; o.start_sample = 0; o.nsym = 0; o.cfo_est = 0; o.rate_kbps = r.rate_kbps & ~kRowShortBit; o.end_sample = r.end_sample;
+                   if (r.rate_kbps & kRowShortBit) tflags = SORA_ROW_SHORT_PREAMBLE; }
             o.error_code = r.error_code; o.length = (uint16_t)r.length; o.crc32 = r.crc32;
             o.flags = (uint16_t)(tflags | ((i + 1 == mf && found > mf) ? SORA_ROW_TRUNCATED : 0));
             const bool has = r.error_code == E_FRAME_OK || r.error_code == E_CRC32_FAIL;
@@ -167,9 +168,10 @@ int sora_internal_rows_results(const Rx11bRow* d_rows, const uint32_t* d_nframes
             if (n >= max_out) { rc = SORA_ERR_CAPACITY; continue; }
             sora_frame_result& o = out[n++];
             memset(&o, 0, sizeof(o));
-            o.capture_id = caps[c].capture_id; o.end_sample = r.end_sample; o.error_code = r.error_code; o.rate_kbps = r.rate_kbps;
+            o.capture_id = caps[c].capture_id; o.end_sample = r.end_sample; o.error_code = r.error_code; o.rate_kbps = r.rate_kbps & ~kRowShortBit;
             o.length = (uint16_t)r.length; o.crc32 = r.crc32; o.mpdu_offset = (uint32_t)moff;
             if (i + 1 == mf && nfr[c] > mf) o.flags = SORA_ROW_TRUNCATED;             // more frames were found than the capture has rows
+            if (r.rate_kbps & kRowShortBit) o.flags |= SORA_ROW_SHORT_PREAMBLE;
             if (h_mpdu && (r.error_code == E_FRAME_OK || r.error_code == E_CRC32_FAIL)) {
                 const size_t len = r.length < 4096 ? r.length : 4096;
                 if (moff + len > mpdu_cap) { rc = SORA_ERR_CAPACITY; continue; }

@@ -1,4 +1,4 @@
-// k_rx11b.hip -- the 802.11b receive graph for gfx950: 44 MHz samples in, long preamble, 1 Mbps DBPSK,
+// k_rx11b.hip -- the 802.11b receive graph for gfx950: 44 MHz samples in, long preamble (and, as an option, short), 1 Mbps DBPSK,
 // 2 Mbps DQPSK, 5.5 and 11 Mbps CCK payloads.  Reference: CreateDemodGraph (kernel/bb/demod11/fb11bdemod_config.hpp:122-172) driven by
 // MAC11b_Receive (kernel/bb/demod11/fb11b_demod.cpp:27-76):
 //   src -> TDCRemove -> TBB11bRxSwitch -+-> TEnergyDetect -> TDCEstimator                                  (carrier sense)
@@ -55,7 +55,10 @@ __device__ __forceinline__ uint32_t dot_sign(int rre, int rim, int xre, int xim)
 // STREAM = true (sora_rx11b_set_stream_mode): the capture continues the stream its continuation record left off, and the
 // record and the resume point are rewritten by the pass that finishes the capture.  Every addition sits under "if constexpr (STREAM)": the
 // default kernels are the instruction stream they were.
-template <bool CCK, bool STREAM>
+// PRE = true (sora_rx11b_set_preamble(rx, 1)): TSFDSync also knows the short preamble -- the rule is stated once, in include/sora_hip.h -- and a
+// short SFD sends the six header bytes through TDQPSKDemap.  Every addition sits under "if constexpr (PRE)"; rows of short-preamble frames carry
+// kRowShortBit in rate_kbps, which the delivery code turns into SORA_ROW_SHORT_PREAMBLE.
+template <bool CCK, bool STREAM, bool PRE>
 __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
 {
     __shared__ uint8_t s_out_all[4][kOutBuf];
@@ -103,6 +106,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
     // TCCK5P5Decoder / TCCK11Decoder: queued chips (lane j = j-th chip, packed), is_even
     int cck_n = 0; uint32_t cck_even = 0; uint32_t cbuf = 0;
     int bit_one_found = 0; uint32_t word = 0; int bit_err_cnt = 0; uint32_t sync_cnt = 0; // TSFDSync
+    int bit_zero_found = 0;                                                               // ... extended (PRE): the short preamble's SYNC was seen first
     int sym_n = 0; uint32_t sym_byte = 0; int ref_re = 0, ref_im = 0;                     // TDBPSKDemap / TDQPSKDemap burst in progress
     int hdr_n = 0; uint32_t hdr_lo = 0, hdr_hi = 0;                                       // TBB11bPlcpParser's 6-byte burst
     uint32_t byte_count = 0, crc32 = 0xFFFFFFFFu;                                         // TBB11bFrameSink
@@ -149,6 +153,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
         lds_order(); if (lane < 32) p_re[lane] = 0; lds_order();
         chip_n = 0; acc_re = acc_im = 0; cck_n = 0; cck_even = 0;
         bit_one_found = 0; word = 0; bit_err_cnt = 0; sync_cnt = 0;
+        if constexpr (PRE) bit_zero_found = 0;
         sym_n = 0; sym_byte = 0; hdr_n = 0; hdr_lo = hdr_hi = 0;
         byte_count = 0; crc32 = 0xFFFFFFFFu;
     };
@@ -319,6 +324,15 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             byte_reg = (byte_reg >> 1) | (bit << 6);
             word = ((word >> 1) | (sbit << 15)) & 0xFFFF;
             sync_cnt++;
+            if constexpr (PRE) {                                        // the extended rule (include/sora_hip.h): the first full window of ones or of zeros decides
+                const bool ones = word == 0xFFFF, zeros = word == 0 && sync_cnt >= 16, sfd = word == 0xF3A0, sfds = word == 0x05CF;   // DOT11B_PLCP_SHORT_PREAMBLE_SFD
+                const bool f1 = bit_one_found != 0, f0 = bit_zero_found != 0, none = !f1 && !f0;
+                bit_one_found |= none && ones ? 1 : 0; bit_zero_found |= none && zeros ? 1 : 0;          // (selects again)
+                rxrate = f1 && sfd ? RATE_1M : (f0 && sfds ? RATE_2M : rxrate);                            // short: the header is DQPSK, plcp_data still 0
+                if ((f1 && !sfd && !ones) || (f0 && !sfds && !zeros)) { if (bit_err_cnt++ > 32) { error_code = E_SFD_FAIL; return; } }
+                if (sync_cnt > 128 + 16) error_code = E_SFD_TIMEOUT;
+                return;
+            }
             const bool ones = word == 0xFFFF, sfd = word == 0xF3A0, found = bit_one_found != 0;     // DOT11B_PLCP_LONG_PREAMBLE_SFD
             bit_one_found |= ones ? 1 : 0;                              // (selects, not "store 1 to one of two variables": that becomes a pointer
             rxrate = found && sfd ? RATE_1M : rxrate;                   //  select and pins both to memory)
@@ -468,7 +482,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
         const int port = uni(rxrate);
         // 0: TSFDSync, 1: the PLCP header's bytes, 2: a Barker payload's, 3: a CCK payload's
         const int mode = port == RATE_SYNC ? 0 : (!uni(plcp_data) ? 1 : port <= RATE_2M ? 2 : 3);
-        if (mode == 1 && port != RATE_1M) return false;
+        if (mode == 1 && port != RATE_1M && !PRE) return false;        // (PRE: a short preamble's header, six bytes of DQPSK)
         if (mode == 3 && !CCK) return false;
         const int spb = port == RATE_2M ? 4 : 8;                        // symbols per byte
         const int need = port == RATE_5P5M ? 16 : 8;                    // CCK: chips per byte
@@ -748,12 +762,28 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             const uint32_t wn = (uint32_t)(Bw >> (lane + 1)) & 0xFFFFu;
             const bool ones = wn == 0xFFFFu, sfd = wn == 0xF3A0u;
             const unsigned long long onesm = __ballot(in && ones);
+            unsigned long long zerosm = 0, errm, evs;
+            if constexpr (PRE) {
+                // the zero window as the ones window; which of the two was seen first among the symbols in front of this lane's is the lowest
+                // set bit of both masks together
+                const bool zeros = wn == 0u && sync_cnt + (uint32_t)lane + 1u >= 16u, sfds = wn == 0x05CFu;
+                zerosm = __ballot(in && zeros);
+                const unsigned long long po = onesm & below, pz = zerosm & below, first = (po | pz) & (0ull - (po | pz));
+                const bool f1 = bit_one_found != 0 || (bit_zero_found == 0 && (first & po) != 0);
+                const bool f0 = bit_zero_found != 0 || (bit_one_found == 0 && (first & pz) != 0);
+                const bool err = (f1 && !sfd && !ones) || (f0 && !sfds && !zeros);
+                errm = __ballot(in && err);
+                const bool fail = err && bit_err_cnt + (int)__popcll(errm & below) > 32;
+                const bool late = sync_cnt + (uint32_t)lane + 1u > 128u + 16u;
+                evs = __ballot(in && ((f1 && sfd) || (f0 && sfds) || fail || late));
+            } else {
             const bool found = bit_one_found != 0 || (onesm & below) != 0;
             const bool err = found && !sfd && !ones;
-            const unsigned long long errm = __ballot(in && err);
+            errm = __ballot(in && err);
             const bool fail = err && bit_err_cnt + (int)__popcll(errm & below) > 32;
             const bool late = sync_cnt + (uint32_t)lane + 1u > 128u + 16u;
-            const unsigned long long evs = __ballot(in && ((found && sfd) || fail || late));
+            evs = __ballot(in && ((found && sfd) || fail || late));
+            }
             if (evs != 0) {                                             // cut back to the calls in front of the one that completes the event's symbol
                 const int gt = 11 * (__builtin_ctzll(evs) + 1) - 1;
                 Kc = __builtin_ctzll(__ballot(act && g0 <= gt && gt < g0 + cnt));
@@ -767,6 +797,11 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             if (nsym > 0) { last_re = lane_of(sre, nsym - 1); last_im = lane_of(sim, nsym - 1); }
             byte_reg = (uint32_t)(S >> nsym) & 0x7Fu; word = (uint32_t)(Bw >> nsym) & 0xFFFFu;
             sync_cnt += (uint32_t)nsym;
+            if constexpr (PRE) {
+                const unsigned long long d1 = onesm & done, d0 = zerosm & done, first = (d1 | d0) & (0ull - (d1 | d0));
+                const bool none = bit_one_found == 0 && bit_zero_found == 0;
+                bit_one_found |= none && (first & d1) != 0 ? 1 : 0; bit_zero_found |= none && (first & d0) != 0 ? 1 : 0;
+            } else
             bit_one_found |= (onesm & done) != 0 ? 1 : 0;
             bit_err_cnt += (int)__popcll(errm & done);
         } else {
@@ -960,6 +995,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             if (err != E_CS_TIMEOUT) {
                 if (lane == 0 && nfr < A.max_frames) {
                     Rx11bRow row; row.end_sample = pos; row.error_code = err; row.rate_kbps = rate_kbps; row.length = frame_length; row.crc32 = frame_crc32;
+                    if constexpr (PRE) row.rate_kbps |= bit_zero_found && uni(rxrate) != RATE_SYNC ? kRowShortBit : 0u;     // between a short SFD and the reset
                     A.rows[(size_t)cap_i * A.max_frames + nfr] = row;
                 }
                 if ((err == E_FRAME_OK || err == E_CRC32_FAIL) && nfr < A.max_frames) {
@@ -1010,10 +1046,15 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
 #undef RP_PACK
 }
 
-__global__ void __launch_bounds__(256, 4) k_rx11b(Rx11bArgs A) { rx11b_capture<false, false>(A); }
-__global__ void __launch_bounds__(256, 4) k_rx11b_cck(Rx11bArgs A) { rx11b_capture<true, false>(A); }
-__global__ void __launch_bounds__(256, 4) k_rx11b_stream(Rx11bArgs A) { rx11b_capture<false, true>(A); }
-__global__ void __launch_bounds__(256, 4) k_rx11b_cck_stream(Rx11bArgs A) { rx11b_capture<true, true>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b(Rx11bArgs A) { rx11b_capture<false, false, false>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b_cck(Rx11bArgs A) { rx11b_capture<true, false, false>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b_stream(Rx11bArgs A) { rx11b_capture<false, true, false>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b_cck_stream(Rx11bArgs A) { rx11b_capture<true, true, false>(A); }
+// the same four with the extended TSFDSync (sora_rx11b_set_preamble(rx, 1))
+__global__ void __launch_bounds__(256, 4) k_rx11b_pre(Rx11bArgs A) { rx11b_capture<false, false, true>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b_cck_pre(Rx11bArgs A) { rx11b_capture<true, false, true>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b_stream_pre(Rx11bArgs A) { rx11b_capture<false, true, true>(A); }
+__global__ void __launch_bounds__(256, 4) k_rx11b_cck_stream_pre(Rx11bArgs A) { rx11b_capture<true, true, true>(A); }
 
 // how many captures the first pass handed over (the automatic pass plan's measurement): one block
 __global__ void __launch_bounds__(1024) k_rx11b_count_flagged(const uint32_t* __restrict__ needs_cck, uint32_t ncaps, uint32_t* __restrict__ out)
@@ -1063,6 +1104,7 @@ struct sora_rx11b {
     bool auto_single = false;       // automatic plan: what the most recent measurement said (more than half of a call's captures carried CCK frames)
     uint32_t auto_calls = 0;        // ... and every 16th call of a single-pass run is a two-pass call again, to measure
     StreamRecords records{kRec11bWords};     // sora_rx11b_set_stream_mode
+    int preamble = 0;               // sora_rx11b_set_preamble: 0 = long only (the reference's graph), 1 = long and short
 };
 
 static void rx11b_free(sora_rx11b_t* rx)
@@ -1156,7 +1198,9 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
     if (rx->pass_plan == 2 && rx->auto_single && (++rx->auto_calls & 15u) != 0u) single = true;
     HIPCHK(hipMemsetAsync(S.d_needs_cck, single ? 1 : 0, 4 * ncaps, S.stream));
     const dim3 grid((unsigned)((ncaps + 3) / 4));
-    if (!single) hipLaunchKernelGGL(rx->records.on ? k_rx11b_stream : k_rx11b, grid, dim3(256), 0, S.stream, A);
+    // both passes carry the preamble mode (the CCK pass redoes a capture from its first sample)
+    const bool pre = rx->preamble != 0, st = rx->records.on;
+    if (!single) hipLaunchKernelGGL(pre ? (st ? k_rx11b_stream_pre : k_rx11b_pre) : (st ? k_rx11b_stream : k_rx11b), grid, dim3(256), 0, S.stream, A);
     if (!single && rx->pass_plan == 2 && !S.flagged_pending) {
         hipLaunchKernelGGL(k_rx11b_count_flagged, dim3(1), dim3(1024), 0, S.stream, (const uint32_t*)S.d_needs_cck, (uint32_t)ncaps, S.d_flagged);
         S.h_flagged[1] = (uint32_t)ncaps;
@@ -1165,7 +1209,7 @@ int sora_rx11b_process_dev(sora_rx11b_t* rx, const sora_complex16* d_iq, const s
         S.flagged_pending = true;
     }
     // redoes the captures the first pass flagged (a wave of any other capture returns at once)
-    hipLaunchKernelGGL(rx->records.on ? k_rx11b_cck_stream : k_rx11b_cck, grid, dim3(256), 0, S.stream, A);
+    hipLaunchKernelGGL(pre ? (st ? k_rx11b_cck_stream_pre : k_rx11b_cck_pre) : (st ? k_rx11b_cck_stream : k_rx11b_cck), grid, dim3(256), 0, S.stream, A);
     HIPCHK(hipGetLastError());
     return SORA_OK;
 }
@@ -1204,6 +1248,18 @@ int sora_rx11b_set_single_pass(sora_rx11b_t* rx, int enable)
     if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_set_single_pass: null handle", 0);
     const int old = rx->pass_plan;
     if (enable >= 0) { rx->pass_plan = enable > 2 ? 2 : enable; rx->auto_single = false; rx->auto_calls = 0; }
+    return old;
+}
+// Which preambles TSFDSync accepts (include/sora_hip.h).  Like the other handle settings it waits for the calls in flight: a call runs wholly in one mode.
+int sora_rx11b_set_preamble(sora_rx11b_t* rx, int mode)
+{
+    if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_set_preamble: null handle", 0);
+    const int old = rx->preamble;
+    if (mode >= 0) {
+        if (mode > 1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_rx11b_set_preamble: mode must be 0 (long) or 1 (long and short)", 0);
+        const int rc = sora_rx11b_synchronize(rx); if (rc) return rc;
+        rx->preamble = mode;
+    }
     return old;
 }
 int sora_rx11b_set_stream_mode(sora_rx11b_t* rx, int enable)

@@ -1,8 +1,11 @@
-// k_tx11b.hip -- 802.11b transmitter on the GPU (1, 2, 5.5 and 11 Mbps, long preamble): the reference's modulation graph
+// k_tx11b.hip -- 802.11b transmitter on the GPU (1, 2, 5.5 and 11 Mbps; long or short preamble): the reference's modulation graph
 //   TBB11bSrc -> TSc741 -> TBB11bMRSelect -> TBB11bDBPSKSpread / TBB11bDQPSKSpread / TCCK5Encode / TCCK11Encode
 //   -> TQuickPulseShaper -> TPackSample16to8 -> TModSink                (kernel/bb/demod11/fb11bmod_config.hpp:28-50)
 // Output: COMPLEX8 at 44 MHz (11 Mchip/s, four samples a chip).  Every stage restated so that it is data-parallel:
-//   * PPDU (PHY_11b.hpp:80-200): 16 x 0xFF, SFD 0xF3A0, SIGNAL, SERVICE, LENGTH (us), CRC-16, MPDU, FCS
+//   * PPDU (PHY_11b.hpp:80-200): 16 x 0xFF, SFD 0xF3A0, SIGNAL, SERVICE, LENGTH (us), CRC-16, MPDU, FCS.  The short preamble, which
+//     TBB11bSrc::PreparePLCPHeader refuses (PHY_11b.hpp:115-119) and TBB11bMRSelect already counts (:224-229): 7 x 0x00, SFD 0x05CF, the
+//     six PLCP bytes at 2 Mbps DQPSK, scrambler register 0x1B; the differential phase runs on from SFD to header to payload.  The
+//     header's geometry comes from tx11b_plan (kernels.h), for both kinds
 //   * scrambler (scramble.hpp:7-88): s[n] = b[n] ^ s[n-4] ^ s[n-7] from the register 0x6C.  Linear over GF(2) with a 7-bit state:
 //     each lane scrambles a run of bytes, and a scan composes the runs (the state after e zero-input steps is M^e s, e mod 127)
 //   * every chip is 1, j, -1 or -j: an angle a in quarter turns.  The differential phase is a sum mod 4 of per-byte increments
@@ -25,7 +28,6 @@ constexpr int kThreads = 256;
 constexpr uint32_t kMaxBytes = 24 + 4092 + 4;               // header + MPDU + FCS
 constexpr uint32_t kTileChunks = 4096;                      // chip-step pairs per tile: 8196 chips with the window, <= 1026 symbols of 8 chips
 constexpr uint32_t kTileSyms = 1032;
-constexpr uint32_t kHdrChips = 24 * 88;                     // 192 DBPSK symbols of 11 chips
 // TQuickPulseShaper's taps (pulse.hpp:254-293): tap(i) = (short)(x * 80 + .5), x = 4 cos(PI i / 2) / PI / (1 - i^2) (1 at i = +-1),
 // PI = 3.141593, for i = 8, 7, .., -11.  Output sample s of chip step m takes x[m - j] times kTx11bTaps[4 j + s], j = 0..4.
 constexpr int kTx11bTaps[20] = { -1, 0, 3, 0, -6, 0, 34, 80, 102, 80, 34, 0, -6, 0, 3, 0, -1, 0, 1, 0 };
@@ -101,10 +103,15 @@ __global__ void __launch_bounds__(kThreads) k_tx11b(Tx11bArgs A)
     const int tid = threadIdx.x;
     const uint32_t L = A.len[f];
     Tx11bPlan P;
-    if (!tx11b_plan(L, A.rate[f], P)) return;                                    // an unsupported frame: nothing is written
-    const uint32_t M = L + 28, N = P.nchips, Q = (N + 6) / 2;                    // bytes, chips, 16-byte chunks (two chip steps each)
-    auto chip_of_byte = [&](uint32_t b) { return b < 24 ? 88 * b : kHdrChips + (b - 24) * P.cpb; };
-    auto byte_ceil = [&](uint32_t c) { return c <= kHdrChips ? (c + 87) / 88 : 24 + (c - kHdrChips + P.cpb - 1) / P.cpb; };
+    // (a byte load goes through the vector unit: said to be wave-uniform, the kind and the whole plan derived from it stay in scalar registers)
+    const uint32_t kind = A.preamble ? (uint32_t)__builtin_amdgcn_readfirstlane((int)A.preamble[f]) : 0u;
+    if (!tx11b_plan(L, A.rate[f], P, kind)) return;                              // an unsupported frame: nothing is written
+    const uint32_t H1 = P.hb1, HB = P.hb, HS = P.hsyms, HC = P.hchips;          // header: DBPSK bytes, bytes, symbols, chips
+    // PPDU byte b lives at s_byte[24 - HB + b]: MPDU and FCS start at s_byte + 24 for either kind (a fixed, aligned place for the FCS waves' reads)
+    uint8_t* const ppdu = s_byte + (24 - HB);
+    const uint32_t M = L + HB + 4, N = P.nchips, Q = (N + 6) / 2;                    // bytes, chips, 16-byte chunks (two chip steps each)
+    auto chip_of_byte = [&](uint32_t b) { return b < H1 ? 88 * b : b < HB ? 88 * H1 + 44 * (b - H1) : HC + (b - HB) * P.cpb; };
+    auto byte_ceil = [&](uint32_t c) { return c <= 88 * H1 ? (c + 87) / 88 : c <= HC ? H1 + (c - 88 * H1 + 43) / 44 : HB + (c - HC + P.cpb - 1) / P.cpb; };
     const uint32_t B0 = byte_ceil((uint32_t)((uint64_t)N * g / G)), B1 = byte_ceil((uint32_t)((uint64_t)N * (g + 1) / G));
     if (B0 >= B1) return;                                                        // (more runs than bytes)
     const uint32_t q0 = chip_of_byte(B0) / 2, q1 = B1 == M ? Q : chip_of_byte(B1) / 2;
@@ -119,7 +126,7 @@ __global__ void __launch_bounds__(kThreads) k_tx11b(Tx11bArgs A)
         else if (P.cpb == 44) us = size * 4;
         else if (P.cpb == 16) us = (size * 16 + 10) / 11;
         else { us = (size * 8 + 10) / 11; ext = us * 11 - size * 8 >= 8 ? 1u : 0u; }
-        uint8_t h[8] = { 0xA0, 0xF3, (uint8_t)P.code, (uint8_t)(ext << 7), (uint8_t)us, (uint8_t)(us >> 8), 0, 0 };
+        uint8_t h[8] = { (uint8_t)P.sfd, (uint8_t)(P.sfd >> 8), (uint8_t)P.code, (uint8_t)(ext << 7), (uint8_t)us, (uint8_t)(us >> 8), 0, 0 };
         uint32_t c = 0xFFFFu;                                                    // CRC-16 of SIGNAL..LENGTH: reflected 0x8408, init 0xFFFF, inverted
         for (int i = 2; i < 6; i++) {
             c ^= h[i];
@@ -127,13 +134,13 @@ __global__ void __launch_bounds__(kThreads) k_tx11b(Tx11bArgs A)
         }
         c = ~c & 0xFFFFu;
         h[6] = (uint8_t)c; h[7] = (uint8_t)(c >> 8);
-        for (int i = 0; i < 16; i++) s_byte[i] = 0xFF;
-        for (int i = 0; i < 8; i++) s_byte[16 + i] = h[i];
+        for (uint32_t i = 0; i + 8 < HB; i++) ppdu[i] = (uint8_t)P.sync;
+        for (uint32_t i = 0; i < 8; i++) s_byte[16 + i] = h[i];
     }
     const uint8_t* mp = A.mpdu + A.off[f];
-    const uint32_t nm = min(B1, 24 + L) > 24 ? min(B1, 24 + L) - 24 : 0u;
+    const uint32_t nm = min(B1, HB + L) > HB ? min(B1, HB + L) - HB : 0u;
     for (uint32_t i = tid; i < nm; i += kThreads) s_byte[24 + i] = mp[i];
-    const bool need_fcs = B1 > 24 + L;
+    const bool need_fcs = B1 > HB + L;
     if (need_fcs) {
         s_crc[tid] = A.T.crc[tid];
         for (int i = tid; i < 6 * 8 * 16; i += kThreads) s_z[i] = A.T.crcz[i];
@@ -144,7 +151,7 @@ __global__ void __launch_bounds__(kThreads) k_tx11b(Tx11bArgs A)
         __syncthreads();
         if (tid == 0) {
             const uint32_t fcs = tx_fcs_join<2>(s_z, s_crcw);                    // a run that ends inside the FCS stores only its bytes
-            for (uint32_t k = 0; k < 4 && 24 + L + k < B1; k++) s_byte[24 + L + k] = (uint8_t)(fcs >> (8 * k));
+            for (uint32_t k = 0; k < 4 && HB + L + k < B1; k++) s_byte[24 + L + k] = (uint8_t)(fcs >> (8 * k));
         }
         __syncthreads();
     }
@@ -153,8 +160,8 @@ __global__ void __launch_bounds__(kThreads) k_tx11b(Tx11bArgs A)
     // y_t = M^(8 K) y_(t-1) ^ e_t, then pass 2 from the true entry state.
     const uint32_t K = (B1 + kThreads - 1) / kThreads;
     const uint32_t blo = min((uint32_t)tid * K, B1), bhi = min(blo + K, B1);
-    uint32_t r = tid == 0 ? 0x6Cu : 0u;                                         // DOT11B_PLCP_LONG_TX_SCRAMBLER_REGISTER
-    for (uint32_t b = blo; b < bhi; b++) (void)scramble8(s_byte[b], r);
+    uint32_t r = tid == 0 ? P.seed : 0u;                                        // DOT11B_PLCP_{LONG,SHORT}_TX_SCRAMBLER_REGISTER
+    for (uint32_t b = blo; b < bhi; b++) (void)scramble8(ppdu[b], r);
     uint32_t y = r;
     const uint32_t e8k = (8 * K) % 127;
     for (uint32_t d = 1; d < (uint32_t)kThreads; d <<= 1) {
@@ -165,17 +172,17 @@ __global__ void __launch_bounds__(kThreads) k_tx11b(Tx11bArgs A)
     }
     s_scan[tid] = y;
     __syncthreads();
-    r = tid == 0 ? 0x6Cu : s_scan[tid - 1];
+    r = tid == 0 ? P.seed : s_scan[tid - 1];
     // pass 2 scrambles in place and sums the run's phase increments (quarter turns a byte adds to the differential phase)
     uint32_t sum = 0;
     for (uint32_t b = blo; b < bhi; b++) {
-        const uint32_t v = scramble8(s_byte[b], r);
-        s_byte[b] = (uint8_t)v;
+        const uint32_t v = scramble8(ppdu[b], r);
+        ppdu[b] = (uint8_t)v;
         uint32_t inc;
-        if (b < 24 || P.cpb == 88) inc = 2 * (__popc(v) & 1);                    // DBPSK: pi per one bit
-        else if (P.cpb == 44) inc = dq(v & 3) + dq((v >> 2) & 3) + dq((v >> 4) & 3) + dq(v >> 6);
+        if (b < H1 || (b >= HB && P.cpb == 88)) inc = 2 * (__popc(v) & 1);       // DBPSK: pi per one bit
+        else if (b < HB || P.cpb == 44) inc = dq(v & 3) + dq((v >> 2) & 3) + dq((v >> 4) & 3) + dq(v >> 6);
         else if (P.cpb == 16) inc = dq(v & 3) + dq((v >> 4) & 3) + 2;            // two symbols, the second one odd
-        else inc = dq(v & 3) + 2 * ((b - 24) & 1);                              // odd PSDU symbols: pi more
+        else inc = dq(v & 3) + 2 * ((b - HB) & 1);                              // odd PSDU symbols: pi more
         s_ph[b] = (uint8_t)inc;
         sum += inc;
     }
@@ -197,20 +204,22 @@ __global__ void __launch_bounds__(kThreads) k_tx11b(Tx11bArgs A)
     }
     if (A.phase_out && bhi == M && blo < M) A.phase_out[f] = (uint8_t)code_of_angle(ph & 3u);
 
-    // symbols: 0..191 the header's DBPSK bits, then the data symbols
-    const uint32_t nsyms = 192 + (L + 4) * P.spb;
+    // symbols: 0..HS-1 the header's (8 H1 DBPSK bits, then the short header's DQPSK dibits), then the data symbols
+    const uint32_t nsyms = HS + (L + 4) * P.spb;
     const uint32_t spb_sh = P.spb == 8 ? 3u : P.spb == 4 ? 2u : P.spb == 2 ? 1u : 0u;
-    auto sym_of_chip = [&](uint32_t c) { return c < kHdrChips ? c / 11 : 192 + (P.ls == 8 ? (c - kHdrChips) >> 3 : (c - kHdrChips) / 11); };
-    auto sym_start = [&](uint32_t s) { return s < 192 ? 11 * s : kHdrChips + (s - 192) * P.ls; };
-    auto sym_len = [&](uint32_t s) { return s < 192 ? 11u : P.ls; };
+    auto sym_of_chip = [&](uint32_t c) { return c < HC ? c / 11 : HS + (P.ls == 8 ? (c - HC) >> 3 : (c - HC) / 11); };
+    auto sym_start = [&](uint32_t s) { return s < HS ? 11 * s : HC + (s - HS) * P.ls; };
+    auto sym_len = [&](uint32_t s) { return s < HS ? 11u : P.ls; };
     auto sym_word = [&](uint32_t s) -> uint32_t {                               // the absolute chip angles of symbol s, chip 0 lowest
-        const uint32_t b = s < 192 ? s >> 3 : 24 + ((s - 192) >> spb_sh), i = s < 192 ? s & 7u : (s - 192) & (P.spb - 1);
-        const uint32_t v = s_byte[b], p = s_ph[b];
-        if (s < 192 || P.cpb == 88) {                                            // DBPSK: the bits up to this one flip the phase
+        const uint32_t S1 = 8 * H1;                                              // the header's DBPSK symbols
+        const uint32_t b = s < S1 ? s >> 3 : s < HS ? H1 + ((s - S1) >> 2) : HB + ((s - HS) >> spb_sh);
+        const uint32_t i = s < S1 ? s & 7u : s < HS ? (s - S1) & 3u : (s - HS) & (P.spb - 1);
+        const uint32_t v = ppdu[b], p = s_ph[b];
+        if (s < S1 || (s >= HS && P.cpb == 88)) {                                          // DBPSK: the bits up to this one flip the phase
             const uint32_t a = (p + 2 * (__popc(v & ((2u << i) - 1u)) & 1)) & 3u;
             return kBarker22 ^ (a * kRep11);
         }
-        if (P.cpb == 44) {                                                       // DQPSK: dibits 0..i
+        if (s < HS || P.cpb == 44) {                                             // DQPSK: dibits 0..i
             uint32_t a = p;
             for (uint32_t k = 0; k <= i; k++) a += dq((v >> (2 * k)) & 3u);
             return kBarker22 ^ ((a & 3u) * kRep11);
@@ -221,7 +230,7 @@ __global__ void __launch_bounds__(kThreads) k_tx11b(Tx11bArgs A)
             a = p + dq(v & 3u) + (i ? dq((v >> 4) & 3u) + 2 : 0u);
             p2 = 1 + 2 * ((nib >> 2) & 1u); p3 = 0; p4 = 2 * (nib >> 3);
         } else {                                                                 // CCK 11: d0 d1 -> phi1, d2..d7 -> phi2..phi4
-            a = p + dq(v & 3u) + 2 * ((b - 24) & 1u);
+            a = p + dq(v & 3u) + 2 * ((b - HB) & 1u);
             p2 = cq((v >> 2) & 3u); p3 = cq((v >> 4) & 3u); p4 = cq(v >> 6);
         }
         const uint32_t o[8] = { p2 + p3 + p4, p3 + p4, p2 + p4, p4 + 2, p2 + p3, p3, p2 + 2, 0 };

@@ -249,14 +249,19 @@ struct Tx11bArgs {             // sora_hip_tx11b
     int8_t*         out;       // COMPLEX8 at 44 MHz
     const uint64_t* out_off;   // first sample of frame f
     Tables          T;
+    const uint8_t*  preamble;  // per frame: 0 = long, 1 = short; nullptr: all long (sora_hip_tx11b_pre)
 };
-// The PPDU is 24 header bytes (SYNC, SFD, PLCP header) spread by DBPSK at 88 chips a byte, then MPDU + FCS at the frame's
-// rate: cpb chips a byte in symbols of ls chips, spb symbols a byte.  TQuickPulseShaper emits four samples per chip and five
-// more chip steps at Flush; the last burst of eight samples is padded: sora_hip_tx11b_samples = 4 nchips + 24.
-struct Tx11bPlan { uint32_t code, cpb, ls, spb, nchips; };
-__host__ __device__ inline bool tx11b_plan(uint32_t len, uint32_t rate_kbps, Tx11bPlan& P)
+// The PPDU is a header (SYNC, SFD, PLCP header) spread over Barker, then MPDU + FCS at the frame's rate: cpb chips a byte in symbols of
+// ls chips, spb symbols a byte.  The header's geometry is stated here once, for the host's sample count and for the kernel:
+//   preamble 0 (long):  16 x 0xFF, SFD 0xF3A0, six PLCP bytes, all 24 at 1 Mbps DBPSK (88 chips a byte); scrambler register 0x6C
+//   preamble 1 (short):  7 x 0x00, SFD 0x05CF at 1 Mbps DBPSK (9 bytes), the six PLCP bytes at 2 Mbps DQPSK (44 chips a byte);
+//                        scrambler register 0x1B; payload at 2, 5.5 or 11 Mbps only (kernel/inc/dot11_plcp.h's short-preamble constants)
+// hb1 bytes of the header go out as DBPSK, hb - hb1 as DQPSK: hsyms symbols of 11 chips, hchips chips.  TQuickPulseShaper emits four
+// samples per chip and five more chip steps at Flush; the last burst of eight samples is padded: the sample count is 4 nchips + 24.
+struct Tx11bPlan { uint32_t code, cpb, ls, spb, nchips, hb1, hb, hsyms, hchips, sync, sfd, seed; };
+__host__ __device__ inline bool tx11b_plan(uint32_t len, uint32_t rate_kbps, Tx11bPlan& P, uint32_t preamble = 0)
 {
-    if (len < 1 || len > 4092) return false;
+    if (len < 1 || len > 4092 || preamble > 1) return false;
     switch (rate_kbps) {                                   // SIGNAL: the rate in units of 100 kbit/s
     case 1000:  P.code = 0x0A; P.cpb = 88; P.ls = 11; P.spb = 8; break;   // DBPSK, Barker
     case 2000:  P.code = 0x14; P.cpb = 44; P.ls = 11; P.spb = 4; break;   // DQPSK, Barker
@@ -264,7 +269,14 @@ __host__ __device__ inline bool tx11b_plan(uint32_t len, uint32_t rate_kbps, Tx1
     case 11000: P.code = 0x6E; P.cpb = 8;  P.ls = 8;  P.spb = 1; break;   // CCK, 8 bits a symbol
     default: return false;
     }
-    P.nchips = 24 * 88 + (len + 4) * P.cpb;
+    if (preamble == 0) { P.hb1 = 24; P.hb = 24; P.sync = 0xFF; P.sfd = 0xF3A0; P.seed = 0x6C; }   // DOT11B_PLCP_LONG_*
+    else {
+        if (rate_kbps == 1000) return false;               // (no 1 Mbps frame behind a short preamble)
+        P.hb1 = 9; P.hb = 15; P.sync = 0x00; P.sfd = 0x05CF; P.seed = 0x1B;                          // DOT11B_PLCP_SHORT_*
+    }
+    P.hsyms = 8 * P.hb1 + 4 * (P.hb - P.hb1);
+    P.hchips = 11 * P.hsyms;
+    P.nchips = P.hchips + (len + 4) * P.cpb;
     return true;
 }
 __global__ void k_tx11b(Tx11bArgs A);
@@ -276,6 +288,8 @@ __global__ void k_soft_jobs8(const uint32_t* off8, const uint32_t* nsoft, const 
 
 // ---- 802.11b receive graph (k_rx11b.hip)
 struct Rx11bRow { uint32_t end_sample, error_code, rate_kbps, length, crc32; };
+// 802.11b rows only: rate_kbps bit 31 = the frame came behind the short preamble; delivery (k_deliver.hip) moves it to SORA_ROW_SHORT_PREAMBLE
+constexpr uint32_t kRowShortBit = 0x80000000u;
 struct Rx11bArgs {
     const uint32_t* iq;         // packed COMPLEX16 @44 MHz
     const CapDesc*  caps;
@@ -297,6 +311,10 @@ __global__ void k_rx11b(Rx11bArgs A);
 __global__ void k_rx11b_cck(Rx11bArgs A);
 __global__ void k_rx11b_stream(Rx11bArgs A);        // the same two passes, in stream form
 __global__ void k_rx11b_cck_stream(Rx11bArgs A);
+__global__ void k_rx11b_pre(Rx11bArgs A);           // the same four with TSFDSync extended to the short preamble (sora_rx11b_set_preamble)
+__global__ void k_rx11b_cck_pre(Rx11bArgs A);
+__global__ void k_rx11b_stream_pre(Rx11bArgs A);
+__global__ void k_rx11b_cck_stream_pre(Rx11bArgs A);
 
 // a continuation record of the 802.11n / HT40 front ends' stream forms (k_rx11n.hip): header, the four MimoAutoCorr rings of both chains, the 64 delayed energies
 constexpr uint32_t kRec11nWords = 64 + 4 * 64 + 128;

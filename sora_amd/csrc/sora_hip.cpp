@@ -2013,29 +2013,40 @@ int sora_hip_tx_ht40_joint(const uint8_t* d_mpdu, const uint32_t* d_off, const u
 }
 
 // ---- 802.11b transmitter
-size_t sora_hip_tx11b_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps)
+size_t sora_hip_tx11b_pre_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps, uint32_t preamble)
 {
     Tx11bPlan P;
-    if (!tx11b_plan(mpdu_len_nofcs, rate_kbps, P)) return 0;
+    if (!tx11b_plan(mpdu_len_nofcs, rate_kbps, P, preamble)) return 0;
     return 4 * (size_t)P.nchips + 24;
 }
+size_t sora_hip_tx11b_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps) { return sora_hip_tx11b_pre_samples(mpdu_len_nofcs, rate_kbps, 0); }
 
-int sora_hip_tx11b(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps,
-                   const uint8_t* d_phase_in, uint8_t* d_phase_out, size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream)
+static int tx11b_launch(const char* who, const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_preamble,
+                        const uint8_t* d_phase_in, uint8_t* d_phase_out, size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream)
 {
     if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_mpdu || !d_off || !d_len || !d_rate_kbps || !d_out || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_tx11b: null pointer");
+    if (!d_mpdu || !d_off || !d_len || !d_rate_kbps || !d_out || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, (std::string(who) + ": null pointer").c_str());
     if (nframes == 0) return SORA_OK;
-    if (nframes > 0x7FFFFFFFu) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_tx11b: too many frames for one call");
+    if (nframes > 0x7FFFFFFFu) return fail(SORA_ERR_INVALID_PARAM, (std::string(who) + ": too many frames for one call").c_str());
     DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     Tx11bArgs A{};
     A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.rate = d_rate_kbps; A.phase_in = d_phase_in; A.phase_out = d_phase_out;
-    A.out = d_out; A.out_off = d_out_off; A.T = D->T;
+    A.out = d_out; A.out_off = d_out_off; A.T = D->T; A.preamble = d_preamble;
     // each frame's chips in G runs, one workgroup each, so that a small batch of long frames still fills the device
     const unsigned G = (unsigned)std::min<size_t>(64, std::max<size_t>(1, (2048 + nframes - 1) / nframes));
     hipLaunchKernelGGL(k_tx11b, dim3((unsigned)nframes, G), dim3(256), 0, (hipStream_t)stream, A);
     HIPCHK(hipGetLastError());
     return SORA_OK;
+}
+int sora_hip_tx11b(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps,
+                   const uint8_t* d_phase_in, uint8_t* d_phase_out, size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream)
+{
+    return tx11b_launch("sora_hip_tx11b", d_mpdu, d_off, d_len, d_rate_kbps, nullptr, d_phase_in, d_phase_out, nframes, d_out, d_out_off, stream);
+}
+int sora_hip_tx11b_pre(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_preamble,
+                       const uint8_t* d_phase_in, uint8_t* d_phase_out, size_t nframes, int8_t* d_out, const uint64_t* d_out_off, void* stream)
+{
+    return tx11b_launch("sora_hip_tx11b_pre", d_mpdu, d_off, d_len, d_rate_kbps, d_preamble, d_phase_in, d_phase_out, nframes, d_out, d_out_off, stream);
 }
 
 // ---- capture ingest
