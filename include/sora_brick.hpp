@@ -476,6 +476,105 @@ struct THipPackSample16to8 : THipStage<sora_complex16, NSAMPLES, sora_complex8, 
         : THipStage<sora_complex16, NSAMPLES, sora_complex8, NSAMPLES, CallPack16to8, T_CTX, T_NEXT>(ctx, next, d_out, CallPack16to8{ NSAMPLES }, stream) {}
 };
 
+// ------------------------------------------------------------------------------------------------
+// The fixed-ratio bricks of the 802.11b receive graph (kernel/bb/demod11/fb11bdemod_config.hpp:122-172), each where its SSE brick sits: one burst = N of the brick's own
+// bursts, one stream per adapter.  What the bricks keep in context facades -- CF_DifferentialDemap::last_symbol, CF_Descramber::byte_reg -- lies in ONE device record
+// (sora_stream11b_state) that the adapters of a graph share, as the bricks share their context: the demappers and the CCK decoders hand last_symbol on to each other, the
+// descrambler keeps byte_reg there, and no Reset clears either; TCCK11Decoder's is_even is brick state in the same record and its Reset clears it.  The record carries
+// the state from Process to Process by itself (the entry points read it and write it back).  d_tab: 16 bytes of device memory, the adapter's own (its stream table).
+// The bricks that consume a variable number of items (TEnergyDetect, TSymTiming, TBarkerSync, TSFDSync) and the two sinks have entry points but no adapter.
+template <class IT, size_t IB, class OT, size_t OB, class T_CTX, class T_NEXT>
+class THip11bStage : public HipFilter<T_CTX, T_NEXT> {
+public:
+    using iport_traits = port_traits<IT, IB>;
+    using oport_traits = port_traits<OT, OB>;
+    THip11bStage(T_CTX& ctx, T_NEXT* next, OT* d_out, void* d_tab, uint32_t units, void* stream)
+        : HipFilter<T_CTX, T_NEXT>(ctx, next, stream), opin_(d_out), d_tab_(static_cast<uint32_t*>(d_tab)), units_(units) {}
+    DevicePin<OT, OB>& opin() { return opin_; }
+protected:
+    // CALL: int(const IT* in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const uint32_t* d_word3, OT* out, void* stream)
+    template <class T_IPIN, class CALL> bool run(T_IPIN& ipin, CALL call)
+    {
+        while (ipin.check_read()) {
+            if (dirty_) {                                                                          // first, n, out_first, one word of the brick's own
+                const uint32_t tab[4] = { 0u, units_, 0u, word3_ };
+                if (sora_hip_stream_synchronize(this->stream_) != SORA_OK || sora_hip_memcpy_h2d(d_tab_, tab, sizeof(tab)) != SORA_OK) return this->raise(SORA_ERR_HARDWARE_FAILED);
+                dirty_ = false;
+            }
+            OT* out = opin_.append();
+            if (!this->raise(call(ipin.peek(), d_tab_, d_tab_ + 1, d_tab_ + 2, d_tab_ + 3, out, this->stream_))) return false;
+            ipin.pop();
+            if (this->next_ && !this->next_->Process(opin_)) return false;
+        }
+        return true;
+    }
+    DevicePin<OT, OB> opin_; uint32_t* d_tab_; uint32_t units_, word3_ = 0; bool dirty_ = true;
+};
+
+// TDCRemove (dc.hpp:6-38): IPORT COMPLEX16 x 4 N -> OPORT COMPLEX16 x 4 N.  CF_VecDC = SetDC (what TDCEstimator, the host's or sora_hip_energy_detect11b's, last said).
+template <size_t N, class T_CTX, class T_NEXT>
+class THip11bDCRemove : public THip11bStage<sora_complex16, 4 * N, sora_complex16, 4 * N, T_CTX, T_NEXT> {
+    using Base = THip11bStage<sora_complex16, 4 * N, sora_complex16, 4 * N, T_CTX, T_NEXT>;
+public:
+    THip11bDCRemove(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* d_tab, void* stream = nullptr) : Base(ctx, next, d_out, d_tab, (uint32_t)N, stream) {}
+    void SetDC(sora_complex16 dc) { this->word3_ = (uint32_t)(uint16_t)dc.re | ((uint32_t)(uint16_t)dc.im << 16); this->dirty_ = true; }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        return this->run(ipin, [](const sora_complex16* in, const uint32_t* f, const uint32_t* n, const uint32_t* of, const uint32_t* dc, sora_complex16* out, void* st) {
+            return sora_hip_dc_remove11b(in, f, n, of, reinterpret_cast<const sora_complex16*>(dc), out, 1, N, st); });
+    }
+};
+
+// TBB11bDespread (barkerspread.hpp:277-303): IPORT COMPLEX16 x 11 N -> OPORT COMPLEX16 x N
+template <size_t N, class T_CTX, class T_NEXT>
+class THip11bDespread : public THip11bStage<sora_complex16, 11 * N, sora_complex16, N, T_CTX, T_NEXT> {
+    using Base = THip11bStage<sora_complex16, 11 * N, sora_complex16, N, T_CTX, T_NEXT>;
+public:
+    THip11bDespread(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* d_tab, void* stream = nullptr) : Base(ctx, next, d_out, d_tab, (uint32_t)N, stream) {}
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        return this->run(ipin, [](const sora_complex16* in, const uint32_t* f, const uint32_t* n, const uint32_t* of, const uint32_t*, sora_complex16* out, void* st) {
+            return sora_hip_despread11b(in, f, n, of, out, 1, N, st); });
+    }
+};
+
+// The five bricks over the shared record: IPORT IT x UNIT N -> OPORT uchar x N through ENTRY (a sora_hip_*11b stream stage)
+template <class IT, size_t UNIT, size_t N, int (*ENTRY)(const IT*, const uint32_t*, const uint32_t*, const uint32_t*, sora_stream11b_state*, uint8_t*, size_t, size_t, void*),
+          class T_CTX, class T_NEXT>
+class THip11bStreamStage : public THip11bStage<IT, UNIT * N, uint8_t, N, T_CTX, T_NEXT> {
+    using Base = THip11bStage<IT, UNIT * N, uint8_t, N, T_CTX, T_NEXT>;
+public:
+    THip11bStreamStage(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* d_tab, sora_stream11b_state* d_state, void* stream = nullptr)
+        : Base(ctx, next, d_out, d_tab, (uint32_t)N, stream), d_state_(d_state) {}
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        sora_stream11b_state* state = d_state_;
+        return this->run(ipin, [state](const IT* in, const uint32_t* f, const uint32_t* n, const uint32_t* of, const uint32_t*, uint8_t* out, void* st) {
+            return ENTRY(in, f, n, of, state, out, 1, N, st); });
+    }
+protected:
+    sora_stream11b_state* d_state_;
+};
+// TDBPSKDemap (barkerspread.hpp:312-390), 8 -> 1; TDQPSKDemap (:396-454), 4 -> 1; TCCK5P5Decoder (cck.hpp:70-206), 16 -> 1; TDesc741 (scramble.hpp:93-170), 1 -> 1
+template <size_t N, class T_CTX, class T_NEXT> using THip11bDBPSKDemap = THip11bStreamStage<sora_complex16, 8, N, sora_hip_dbpsk_demap11b, T_CTX, T_NEXT>;
+template <size_t N, class T_CTX, class T_NEXT> using THip11bDQPSKDemap = THip11bStreamStage<sora_complex16, 4, N, sora_hip_dqpsk_demap11b, T_CTX, T_NEXT>;
+template <size_t N, class T_CTX, class T_NEXT> using THip11bCCK5P5Decoder = THip11bStreamStage<sora_complex16, 16, N, sora_hip_cck5p5_decode11b, T_CTX, T_NEXT>;
+template <size_t N, class T_CTX, class T_NEXT> using THip11bDesc741 = THip11bStreamStage<uint8_t, 1, N, sora_hip_desc741_11b, T_CTX, T_NEXT>;
+// TCCK11Decoder (cck.hpp:255-763), 8 -> 1: Reset clears is_even (waiting for the stream: the record is the device's)
+template <size_t N, class T_CTX, class T_NEXT>
+class THip11bCCK11Decoder : public THip11bStreamStage<sora_complex16, 8, N, sora_hip_cck11_decode11b, T_CTX, T_NEXT> {
+    using Base = THip11bStreamStage<sora_complex16, 8, N, sora_hip_cck11_decode11b, T_CTX, T_NEXT>;
+public:
+    using Base::Base;
+    void Reset()
+    {
+        const uint32_t zero = 0;
+        if (sora_hip_stream_synchronize(this->stream_) != SORA_OK || sora_hip_memcpy_h2d(&this->d_state_->is_even, &zero, sizeof(zero)) != SORA_OK)
+            this->raise(SORA_ERR_HARDWARE_FAILED);
+        HipFilter<T_CTX, T_NEXT>::Reset();
+    }
+};
+
 // ISource over a batch of captures = the whole demod graph behind one handle (brick.h:343-353: Process/Seek/Reset/Flush).
 class THipRx11aSource {
 public:

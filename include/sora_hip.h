@@ -922,6 +922,94 @@ int   sora_rx11b_set_stream_mode(sora_rx11b_t* rx, int enable);
 int   sora_rx11b_stream_consumed(sora_rx11b_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps);
 
 /* ------------------------------------------------------------------------------------------------
+ * The bricks of the 802.11b receive graph as stage entry points: what CreateDemodGraph (fb11bdemod_config.hpp:122-172) is built from, each with the ports of the
+ * brick it replaces, so that a host can replace ONE brick, or compose the graph from stages (sora_amd.rx11b_by_stages does):
+ *     dc_remove -> energy_detect | symtiming -> barker_sync -> despread -> sfd_sync | dbpsk_demap / dqpsk_demap -> desc741 -> plcp_parse | frame_sink
+ *                                                             cck5p5_decode / cck11_decode -> desc741 -> frame_sink
+ * TBB11bRxSwitch, TBB11bRxRateSel and TBB11bPlcpSwitch only route and stay the host's.  The conventions are those of the stage entry points above: device
+ * pointers, stream order, no allocation, no host wait; a null pointer gives SORA_ERR_INVALID_PARAM (sora_hip_last_error() names the function), no device
+ * SORA_ERR_NO_DEVICE, nstreams = 0 is SORA_OK and launches nothing.  The bricks are stateful streams, so a call works on a BATCH of independent streams described by
+ * device tables, as sora_hip_pilot_track11a does: stream f owns d_n[f] input units (a unit is the brick's burst: 4 samples, 11 chips, 8 symbols, ..) starting at
+ * ELEMENT d_first[f] of d_in -- sample, chip, symbol or byte: a stream begins wherever the brick in front of it stopped swallowing -- and writes its output from element
+ * d_out_first[f] of d_out.  What the brick keeps, and the context-facade fields it touches, lie in a per-stream
+ * record, all 32-bit words, that the call reads and writes back: the state after the call is the state the brick would hold, and the same stream cut into two calls
+ * gives what one call gives.  max_n bounds every d_n[f] (it sizes the grid; units of a stream at or behind it are not touched).  Offsets and buffers need no
+ * alignment beyond their element's; the two record tables are 16- and 8-byte aligned.  Every stage equals tests/cxx/rx11b_stage_model.c bit for bit
+ * (tests/test_gpu_11b_stages.py).  DESIGN.md section 7, f4b.
+ * ------------------------------------------------------------------------------------------------ */
+#define SORA_E_CS_TIMEOUT        ((int)0x80000007)  /* TEnergyDetect: 100 bursts without power (the harness resets the graph and does not report it) */
+/* CF_11bRxMRSel::rxrate_state */
+#define SORA_11B_RATE_SYNC 0
+#define SORA_11B_RATE_1M   1
+#define SORA_11B_RATE_2M   2
+#define SORA_11B_RATE_5P5M 3
+#define SORA_11B_RATE_11M  4
+/* TBarkerSync::sync_flag */
+#define SORA_11B_BARKER_SYNCED 4
+/* what the demappers, the CCK decoders and TDesc741 carry: CF_DifferentialDemap::last_symbol, CF_Descramber::byte_reg (context: no Reset clears them) and
+ * TCCK11Decoder's is_even (brick state, 0 after Reset).  Each stage reads and writes its own fields and leaves the others alone. */
+typedef struct { sora_complex16 last_symbol; uint32_t byte_reg; uint32_t is_even; uint32_t reserved; } sora_stream11b_state;
+/* TEnergyDetect + TDCEstimator; after Reset: all 0 but update_cnt = 8; cca_pwr_threshold and dc are context (the reference harness: 1000 * 1000; dc is never reset) */
+typedef struct { uint32_t average_energy, window[8], idx, count, power_detected, error_code, cca_pwr_threshold, update_cnt; sora_complex16 sum_dc, dc; } sora_energy11b_state;
+/* TSymTiming; after Reset: 2, 0 */
+typedef struct { int32_t m_index, m_frag; } sora_symtiming11b_state;
+/* TBarkerSync; after Reset: all 0 but last_peak_cnt = -1 */
+typedef struct { int32_t sync_flag, last_peak_cnt, m_max, search_count; sora_complex16 partial[10]; uint32_t error_code; } sora_barker11b_state;
+/* TSFDSync; after Reset: all 0 but last_symbol and byte_reg, which are context */
+typedef struct { sora_complex16 last_symbol; uint32_t byte_reg, bit_one_found, bit_zero_found, word, bit_err_cnt, sync_cnt, rxrate_state, error_code; } sora_sfd11b_state;
+typedef struct { uint32_t error_code, data_rate_kbps, frame_length, rxrate_state; } sora_plcp11b_rec;
+typedef struct { uint32_t error_code, frame_crc32; } sora_sink11b_rec;
+
+/* TDCRemove (Brick11/src/dc.hpp:6-38), 4 -> 4: out = wrap16(in - d_dc[f]); a unit is a burst of 4 samples */
+int sora_hip_dc_remove11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const sora_complex16* d_dc,
+                          sora_complex16* d_out, size_t nstreams, size_t max_n, void* stream);
+/* TEnergyDetect (cca.hpp:11-98) with the TDCEstimator (dc.hpp:92-166) it feeds, as one entry: stream f consumes bursts of 4 DC-removed samples until power_detected is set
+ * or an error (SORA_E_CS_TIMEOUT) stands, d_n[f] at most; d_used[f] = the bursts consumed, the one that set power_detected included (it does not reach the estimator).
+ * dc is reported as it stands afterwards; subtracting it is the host's TDCRemove.  A stream that enters with power_detected or error_code set consumes nothing. */
+int sora_hip_energy_detect11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_energy11b_state* d_state, uint32_t* d_used,
+                              size_t nstreams, size_t max_n, void* stream);
+/* TSymTiming (symtiming.hpp:10-170), 28 -> 1: d_n[f] blocks of 28 samples -> the decimated chips, 6, 7 or 8 per block, from chip d_out_first[f] of d_out (room for
+ * 8 d_n[f]); d_nchips[f] = the chips written.  The state is a brick's: m_index in -1 .. 4. */
+int sora_hip_symtiming11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_symtiming11b_state* d_state,
+                          sora_complex16* d_out, uint32_t* d_nchips, size_t nstreams, size_t max_n, void* stream);
+/* TBarkerSync (symtiming.hpp:176-315), 1 -> 1: swallows chips until the brick is BARKER_SYNCED; d_used[f] = the chips consumed before pass-through begins, or up to and
+ * including the chip that raised SORA_E_SYNC_TIMEOUT (search_count >= 44).  The chips behind them are the brick's output and are not copied.  A stream that enters
+ * synced or with error_code set consumes nothing. */
+int sora_hip_barker_sync11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_barker11b_state* d_state, uint32_t* d_used,
+                            size_t nstreams, size_t max_n, void* stream);
+/* TBB11bDespread (barkerspread.hpp:277-303), 11 -> 1: QuickBarkerDespread with its order of negate, >> 4 and wrapping sums.  Stateless. */
+int sora_hip_despread11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_complex16* d_out,
+                         size_t nstreams, size_t max_n, void* stream);
+/* TSFDSync (sfd_sync.hpp:10-134), a sink of symbols: mode 0 is the reference's brick, mode 1 adds the short preamble by the rule stated at sora_rx11b_set_preamble.
+ * Stream f consumes symbols up to and including the one that sets rxrate_state (RATE_1M, or RATE_2M behind a short SFD) or an error (SORA_E_SFD_FAIL,
+ * SORA_E_SFD_TIMEOUT) -- one symbol can do both, and both are reported --; d_used[f] = the symbols consumed.  A stream that enters with either set consumes nothing. */
+int sora_hip_sfd_sync11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_sfd11b_state* d_state, uint32_t* d_used,
+                         size_t nstreams, size_t max_n, int mode, void* stream);
+/* TDBPSKDemap (barkerspread.hpp:312-390), 8 -> 1 byte, and TDQPSKDemap (:396-454), 4 -> 1 byte; state: last_symbol */
+int sora_hip_dbpsk_demap11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state,
+                            uint8_t* d_out, size_t nstreams, size_t max_n, void* stream);
+int sora_hip_dqpsk_demap11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state,
+                            uint8_t* d_out, size_t nstreams, size_t max_n, void* stream);
+/* TCCK5P5Decoder (cck.hpp:70-206), 16 chips -> 1 byte; state: last_symbol.  TCCK11Decoder (cck.hpp:255-763), 8 chips -> 1 byte, the reference's pruned search (phi2 = 0
+ * and pi/2, then the one of 3 pi/2 / pi that m1 > m2 picks) with its strict comparisons; state: last_symbol and is_even. */
+int sora_hip_cck5p5_decode11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state,
+                              uint8_t* d_out, size_t nstreams, size_t max_n, void* stream);
+int sora_hip_cck11_decode11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state,
+                             uint8_t* d_out, size_t nstreams, size_t max_n, void* stream);
+/* TDesc741 (scramble.hpp:93-170), 1 -> 1 byte: z^-7 + z^-4 + 1, self-synchronising; state: byte_reg */
+int sora_hip_desc741_11b(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state,
+                         uint8_t* d_out, size_t nstreams, size_t max_n, void* stream);
+/* TBB11bPlcpParser (PHY_11b.hpp:524-640): d_hdr[f][6] -> d_rec[f] (16-byte aligned): error_code 0 or SORA_E_PLCP_HEADER_FAIL (the CRC-16; the other fields are then 0),
+ * data_rate_kbps (0 for an unknown SIGNAL, with frame_length 0 and rxrate_state 0 = "unchanged"), frame_length by the four length formulas with the SERVICE bits,
+ * rxrate_state (SORA_11B_RATE_*) */
+int sora_hip_plcp_parse11b(const uint8_t* d_hdr, sora_plcp11b_rec* d_rec, size_t nstreams, void* stream);
+/* TBB11bFrameSink (PHY_11b.hpp:643-749) over one frame per stream: the descrambled bytes of frame f from byte d_first[f] of d_bytes, d_len[f] = frame_length (<= 65535).
+ * d_rec[f] (8-byte aligned) = error_code SORA_E_FRAME_OK / SORA_E_CRC32_FAIL (0 where the brick raises nothing: lengths below 4) and frame_crc32 = the three FCS bytes the
+ * sink holds when it decides, the fourth byte 0 (the brick: a stale buffer byte).  The sink decides one byte early: byte frame_length - 1 is never read.  Bytes from index
+ * 4096 on lie behind the brick's buffer: they count for the CRC and read back as 0. */
+int sora_hip_frame_sink11b(const uint8_t* d_bytes, const uint32_t* d_first, const uint32_t* d_len, sora_sink11b_rec* d_rec, size_t nstreams, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Small device-memory helpers so a pure-C host needs no HIP headers.
  * ------------------------------------------------------------------------------------------------ */
 int   sora_hip_device_count(void);

@@ -18,6 +18,10 @@ E_FRAME_OK = 0x1
 TRELLIS_WINDOWED = 1          # sora_rx_set_trellis: the window-parallel trellis (include/sora_hip.h SORA_TRELLIS_WINDOWED)
 E_PLCP_HEADER_FAIL = 0x80000005
 E_CRC32_FAIL = 0x80000006
+E_SFD_FAIL = 0x80000004
+E_CS_TIMEOUT = 0x80000007
+E_SFD_TIMEOUT = 0x80000008
+E_SYNC_TIMEOUT = 0x80000009
 ERR_NO_DEVICE = -5
 ERR_CAPACITY = -6
 
@@ -65,6 +69,9 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11a44", "sora_hip_tx11a44_samples",
            "sora_hip_scramble11a", "sora_hip_conv_encode11a", "sora_hip_interleave11a", "sora_hip_map11a", "sora_hip_add_pilot11a", "sora_hip_add_pilot11a_from",
            "sora_hip_ifftx11a", "sora_hip_upsample40to44", "sora_hip_pack16to8", "sora_hip_preamble11a",
+           "sora_hip_dc_remove11b", "sora_hip_energy_detect11b", "sora_hip_symtiming11b", "sora_hip_barker_sync11b", "sora_hip_despread11b", "sora_hip_sfd_sync11b",
+           "sora_hip_dbpsk_demap11b", "sora_hip_dqpsk_demap11b", "sora_hip_cck5p5_decode11b", "sora_hip_cck11_decode11b", "sora_hip_desc741_11b", "sora_hip_plcp_parse11b",
+           "sora_hip_frame_sink11b",
            "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx_ht40", "sora_hip_tx_ht40_samples", "sora_hip_tx11b", "sora_hip_tx11b_samples", "sora_hip_tx11b_pre", "sora_hip_tx11b_pre_samples",
            "sora_hip_tx_ht40_joint", "sora_hip_tx_ht40_joint_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
@@ -82,6 +89,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_ht40_set_coding", "sora_ht40_symbols_joint",
            "sora_shard_unique_id", "sora_shard_create", "sora_shard_destroy", "sora_shard_world", "sora_shard_partition", "sora_shard_gather_rows",
            "sora_shard_reduce_counters", "sora_shard_gather_results", "sora_shard_gather_results_mpdu"]
+
+STREAM11B_STAGES = ("sora_hip_dbpsk_demap11b", "sora_hip_dqpsk_demap11b", "sora_hip_cck5p5_decode11b", "sora_hip_cck11_decode11b", "sora_hip_desc741_11b")
 
 _lib = None
 
@@ -233,6 +242,16 @@ def load(build_if_missing=True):
     L.sora_hip_upsample40to44.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_pack16to8.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_preamble11a.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    # the 802.11b receive graph's bricks as stages
+    L.sora_hip_dc_remove11b.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    for fn in ("sora_hip_energy_detect11b", "sora_hip_barker_sync11b", "sora_hip_despread11b"):
+        getattr(L, fn).argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_sfd_sync11b.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    L.sora_hip_symtiming11b.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    for fn in STREAM11B_STAGES:
+        getattr(L, fn).argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_plcp_parse11b.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_frame_sink11b.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_tx11n_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11n_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11n.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
     L.sora_hip_tx_ht40_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx_ht40_samples.restype = ctypes.c_size_t
@@ -1389,6 +1408,333 @@ def mod11a_by_stages(mpdus, rates, seeds=None, sample_rate_mhz=40, device=0, syn
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(None)))
     return out, plan.offsets
+
+
+# ---- the 802.11b receive graph's bricks as stages (include/sora_hip.h: sora_hip_*11b) -----------------------------
+# Records, as int32 words per stream (a complex16 is one word: re | im << 16):
+#   stream state [n, 4]   last_symbol, byte_reg, is_even, reserved                         (sora_stream11b_state)
+#   energy       [n, 17]  average_energy, window[8], idx, count, power_detected, error_code, cca_pwr_threshold, update_cnt, sum_dc, dc
+#   symtiming    [n, 2]   m_index, m_frag
+#   barker       [n, 15]  sync_flag, last_peak_cnt, m_max, search_count, partial[10], error_code
+#   sfd          [n, 9]   last_symbol, byte_reg, bit_one_found, bit_zero_found, word, bit_err_cnt, sync_cnt, rxrate_state, error_code
+STATE11B_WORDS = {"stream": 4, "energy": 17, "symtiming": 2, "barker": 15, "sfd": 9, "plcp": 4, "sink": 2}
+RATE11B_SYNC, RATE11B_1M, RATE11B_2M, RATE11B_5P5M, RATE11B_11M = range(5)
+
+
+def state11b_reset(kind, n, cca_pwr_threshold=1000 * 1000):
+    """-> int32 numpy [n, words]: the record `kind` of STATE11B_WORDS as the brick holds it after Reset in a fresh context (every context field 0)"""
+    s = np.zeros((n, STATE11B_WORDS[kind]), np.int32)
+    if kind == "energy":
+        s[:, 13] = cca_pwr_threshold; s[:, 14] = 8
+    elif kind == "symtiming":
+        s[:, 0] = 2
+    elif kind == "barker":
+        s[:, 1] = -1
+    return s
+
+
+def _max_n(n, max_n):
+    return int(n.max().item()) if max_n is None and n.shape[0] else int(max_n or 0)
+
+
+def dc_remove11b(x, first, n, out_first, dc, out, max_n=None, stream=None):
+    """TDCRemove: x / out int16 CUDA [samples, 2]; first / n / out_first int32 CUDA [streams] (n in bursts of 4 samples, the offsets in samples); dc int16 CUDA
+    [streams, 2] -> out, stream f's 4 n[f] samples from out_first[f] written in place"""
+    _check(load().sora_hip_dc_remove11b(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(out_first), _dev_ptr(dc), _dev_ptr(out), first.shape[0], _max_n(n, max_n),
+                                        _stream_ptr(stream)))
+    return out
+
+
+def _search11b(fn, x, first, n, state, max_n, stream, *extra):
+    import torch
+    used = torch.zeros(first.shape[0], dtype=torch.int32, device=x.device)
+    _check(getattr(load(), fn)(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(state), _dev_ptr(used), first.shape[0], _max_n(n, max_n), *extra, _stream_ptr(stream)))
+    return used
+
+
+def energy_detect11b(x, first, n, state, max_n=None, stream=None):
+    """TEnergyDetect + TDCEstimator: x = DC-removed samples; n in bursts of 4; state int32 CUDA [streams, 17] (in / out) -> used int32 CUDA [streams]: the bursts consumed"""
+    return _search11b("sora_hip_energy_detect11b", x, first, n, state, max_n, stream)
+
+
+def barker_sync11b(x, first, n, state, max_n=None, stream=None):
+    """TBarkerSync: x = chips; n in chips; state int32 CUDA [streams, 15] (in / out) -> used: the chips swallowed"""
+    return _search11b("sora_hip_barker_sync11b", x, first, n, state, max_n, stream)
+
+
+def sfd_sync11b(x, first, n, state, mode=0, max_n=None, stream=None):
+    """TSFDSync (mode 1: with the short preamble): x = symbols; n in symbols; state int32 CUDA [streams, 9] (in / out) -> used: the symbols consumed"""
+    return _search11b("sora_hip_sfd_sync11b", x, first, n, state, max_n, stream, int(mode))
+
+
+def symtiming11b(x, first, n, out_first, state, out, max_n=None, stream=None):
+    """TSymTiming: n in blocks of 28 samples; state int32 CUDA [streams, 2] (in / out); out int16 CUDA [chips, 2] with room for 8 n[f] chips from out_first[f]
+    -> nchips int32 CUDA [streams]: the chips written"""
+    import torch
+    nchips = torch.zeros(first.shape[0], dtype=torch.int32, device=x.device)
+    _check(load().sora_hip_symtiming11b(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(out_first), _dev_ptr(state), _dev_ptr(out), _dev_ptr(nchips), first.shape[0],
+                                        _max_n(n, max_n), _stream_ptr(stream)))
+    return nchips
+
+
+def despread11b(x, first, n, out_first, out, max_n=None, stream=None):
+    """TBB11bDespread: n[f] symbols from the 11 n[f] chips at chip first[f] -> out (symbols, written from out_first[f])"""
+    _check(load().sora_hip_despread11b(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(out_first), _dev_ptr(out), first.shape[0], _max_n(n, max_n), _stream_ptr(stream)))
+    return out
+
+
+def _stream11b(fn, x, first, n, out_first, state, out, max_n, stream):
+    _check(getattr(load(), fn)(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(out_first), _dev_ptr(state), _dev_ptr(out), first.shape[0], _max_n(n, max_n),
+                               _stream_ptr(stream)))
+    return out
+
+
+def dbpsk_demap11b(x, first, n, out_first, state, out, max_n=None, stream=None):
+    """TDBPSKDemap: n[f] bytes from the 8 n[f] symbols at symbol first[f] -> out uint8 CUDA (from byte out_first[f]); state int32 CUDA [streams, 4] (last_symbol in / out)"""
+    return _stream11b("sora_hip_dbpsk_demap11b", x, first, n, out_first, state, out, max_n, stream)
+
+
+def dqpsk_demap11b(x, first, n, out_first, state, out, max_n=None, stream=None):
+    """TDQPSKDemap: n[f] bytes from 4 n[f] symbols (as dbpsk_demap11b)"""
+    return _stream11b("sora_hip_dqpsk_demap11b", x, first, n, out_first, state, out, max_n, stream)
+
+
+def cck5p5_decode11b(x, first, n, out_first, state, out, max_n=None, stream=None):
+    """TCCK5P5Decoder: n[f] bytes from 16 n[f] chips; state: last_symbol"""
+    return _stream11b("sora_hip_cck5p5_decode11b", x, first, n, out_first, state, out, max_n, stream)
+
+
+def cck11_decode11b(x, first, n, out_first, state, out, max_n=None, stream=None):
+    """TCCK11Decoder: n[f] bytes from 8 n[f] chips; state: last_symbol and is_even"""
+    return _stream11b("sora_hip_cck11_decode11b", x, first, n, out_first, state, out, max_n, stream)
+
+
+def desc741_11b(x, first, n, out_first, state, out, max_n=None, stream=None):
+    """TDesc741: n[f] bytes from byte first[f] of x (uint8 CUDA); state: byte_reg"""
+    return _stream11b("sora_hip_desc741_11b", x, first, n, out_first, state, out, max_n, stream)
+
+
+def plcp_parse11b(hdr, stream=None):
+    """TBB11bPlcpParser: hdr uint8 CUDA [n, 6] -> int32 CUDA [n, 4]: error_code, data_rate_kbps, frame_length, rxrate_state"""
+    import torch
+    rec = torch.zeros((hdr.shape[0], 4), dtype=torch.int32, device=hdr.device)
+    _check(load().sora_hip_plcp_parse11b(_dev_ptr(hdr), _dev_ptr(rec), hdr.shape[0], _stream_ptr(stream)))
+    return rec
+
+
+def frame_sink11b(x, first, length, stream=None):
+    """TBB11bFrameSink: frame f = the descrambled bytes from byte first[f] of x (uint8 CUDA), length[f] = frame_length -> int32 CUDA [n, 2]: error_code, frame_crc32"""
+    import torch
+    rec = torch.zeros((first.shape[0], 2), dtype=torch.int32, device=x.device)
+    _check(load().sora_hip_frame_sink11b(_dev_ptr(x), _dev_ptr(first), _dev_ptr(length), _dev_ptr(rec), first.shape[0], _stream_ptr(stream)))
+    return rec
+
+
+class _Gpu11bOps:
+    """rx11b_stages' bricks on the GPU: host tables and records (numpy) up, one stage call, the records and counts back.  Buffers are torch CUDA tensors."""
+
+    def __init__(self, device):
+        import torch
+        self.torch = torch; self.dev = device
+
+    def _up(self, a, dt=np.int32):
+        return self.torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(dt, copy=False))).to(self.dev)
+
+    def alloc_c16(self, n):
+        return self.torch.zeros((max(int(n), 1), 2), dtype=self.torch.int16, device=self.dev)
+
+    def alloc_u8(self, n):
+        return self.torch.zeros(max(int(n), 1), dtype=self.torch.uint8, device=self.dev)
+
+    def host_u8(self, buf, a, b):
+        return buf[a:b].cpu().numpy().tobytes()
+
+    def dc_remove(self, x, first, n, out_first, dc, out):
+        dc_remove11b(x, self._up(first), self._up(n), self._up(out_first), self._up(dc).view(self.torch.int16).reshape(-1, 2), out, max_n=int(max(n)))
+
+    def _search(self, fn, x, first, n, state, *extra):
+        st = self._up(state)
+        used = fn(x, self._up(first), self._up(n), st, *extra, max_n=int(max(n)))
+        return st.cpu().numpy(), used.cpu().numpy()
+
+    def energy_detect(self, x, first, n, state):
+        return self._search(energy_detect11b, x, first, n, state)
+
+    def barker_sync(self, x, first, n, state):
+        return self._search(barker_sync11b, x, first, n, state)
+
+    def sfd_sync(self, x, first, n, state, mode):
+        return self._search(sfd_sync11b, x, first, n, state, mode)
+
+    def symtiming(self, x, first, n, out_first, state, out):
+        st = self._up(state)
+        nchips = symtiming11b(x, self._up(first), self._up(n), self._up(out_first), st, out, max_n=int(max(n)))
+        return st.cpu().numpy(), nchips.cpu().numpy()
+
+    def despread(self, x, first, n, out_first, out):
+        despread11b(x, self._up(first), self._up(n), self._up(out_first), out, max_n=int(max(n)))
+
+    def stream_stage(self, kind, x, first, n, out_first, state, out):
+        fn = {"dbpsk": dbpsk_demap11b, "dqpsk": dqpsk_demap11b, "cck5p5": cck5p5_decode11b, "cck11": cck11_decode11b, "desc741": desc741_11b}[kind]
+        st = self._up(state)
+        fn(x, self._up(first), self._up(n), self._up(out_first), st, out, max_n=int(max(n)))
+        return st.cpu().numpy()
+
+    def plcp_parse(self, hdr, nhdr):
+        return plcp_parse11b(hdr[:6 * nhdr].reshape(nhdr, 6)).cpu().numpy()
+
+    def frame_sink(self, x, first, length):
+        return frame_sink11b(x, self._up(first), self._up(length)).cpu().numpy()
+
+
+def rx11b_stages(ops, iq, descs, mode=0, cca_pwr_threshold=1000 * 1000):
+    """The 802.11b receive graph (CreateDemodGraph under MAC11b_Receive, fb11b_demod.cpp:27-76) up to the FIRST event of every capture, composed from the thirteen brick
+    stages through `ops` (the GPU's: rx11b_by_stages; the C model's: tests/rx11b_stage_model.first_event).  The host plays the three routing bricks (TBB11bRxSwitch,
+    TBB11bRxRateSel, TBB11bPlcpSwitch) and the harness: it reads every stage's counts and records back and builds the next stage's tables from them.
+    iq: the captures' samples (ops' buffer), descs: [(first sample, samples)], whole 28-sample source calls each.
+    -> per capture None (carrier sense never fires, or the capture ends first) or a dict error_code, rate_kbps, length, crc32, flags, mpdu."""
+    nc = len(descs)
+    off = np.array([int(d[0]) for d in descs], np.int64); ns = np.array([int(d[1]) for d in descs], np.int64)
+    if nc == 0:
+        return []
+    if (ns % 28).any() or (off % 4).any():
+        raise ValueError("rx11b_stages: a capture is whole 28-sample source calls at an offset of whole bursts")
+    u32 = lambda a: np.asarray(a, np.int64).astype(np.uint32).view(np.int32)
+    events = [None] * nc
+    d_dcr = ops.alloc_c16(int((off + ns).max()))
+    # ---- the front: TDCRemove -> TBB11bRxSwitch -> TEnergyDetect -> TDCEstimator, in pieces that end where the estimator changes dc (every eighth burst, the burst that
+    # finds update_cnt 0): the bursts of a piece see one dc.  SORA_E_CS_TIMEOUT is the harness's: the rest of the 28-sample source call is dropped, the graph reset.
+    nb = ns // 4
+    est = state11b_reset("energy", nc, cca_pwr_threshold)
+    pos = np.zeros(nc, np.int64)
+    active = nb > 0
+    while active.any():
+        n = np.where(active, np.minimum(est[:, 14].astype(np.int64) + 1, nb - pos), 0)
+        first = off + 4 * pos
+        ops.dc_remove(iq, u32(first), u32(n), u32(first), est[:, 16], d_dcr)
+        est, used = ops.energy_detect(d_dcr, u32(first), u32(n), est)
+        est = est.copy(); pos += used.astype(np.int64)
+        for c in np.nonzero(active)[0]:
+            if est[c, 11]:
+                active[c] = False
+            elif est[c, 12]:
+                pos[c] = (pos[c] + 6) // 7 * 7
+                dc = est[c, 16]
+                est[c] = state11b_reset("energy", 1, cca_pwr_threshold)[0]; est[c, 16] = dc
+            if pos[c] >= nb[c]:
+                active[c] = False
+    live = [c for c in range(nc) if est[c, 11]]
+    if not live:
+        return events
+    # ---- behind the switch: TDCRemove (dc stands still: the estimator is gated) -> TSymTiming over the rest of the capture, in blocks counted from the first burst routed
+    blocks = np.array([(ns[c] - 4 * pos[c]) // 28 for c in live], np.int64)
+    first = np.array([off[c] + 4 * pos[c] for c in live], np.int64)
+    chip0 = np.concatenate([[0], np.cumsum(8 * blocks)])[:-1]
+    d_chips = ops.alloc_c16(int(8 * blocks.sum()) + 16)
+    nchips = np.zeros(len(live), np.int64)
+    if blocks.max() > 0:
+        ops.dc_remove(iq, u32(first), u32(7 * blocks), u32(first), est[live, 16], d_dcr)
+        _, nch = ops.symtiming(d_dcr, u32(first), u32(blocks), u32(chip0), state11b_reset("symtiming", len(live)), d_chips)
+        nchips = nch.astype(np.int64)
+    cc = np.zeros(len(live), np.int64)                                         # chips consumed, per live capture
+    short = np.zeros(len(live), bool)
+
+    def event(j, err, kbps=0, length=0, crc=0, mpdu=b""):
+        events[live[j]] = {"error_code": int(err) & 0xFFFFFFFF, "rate_kbps": int(kbps), "length": int(length), "crc32": int(crc) & 0xFFFFFFFF,
+                           "flags": ROW_SHORT_PREAMBLE if short[j] else 0, "mpdu": mpdu}
+
+    # ---- TBarkerSync
+    go = list(range(len(live)))
+    bst, used = ops.barker_sync(d_chips, u32(chip0), u32(nchips), state11b_reset("barker", len(live)))
+    cc += used.astype(np.int64)
+    nxt = []
+    for j in go:
+        if bst[j, 14]:
+            event(j, bst[j, 14])
+        elif bst[j, 0] == 4:
+            nxt.append(j)
+    go = nxt
+    if not go:
+        return events
+    # ---- TBB11bRxRateSel port 0: TBB11bDespread -> TSFDSync (145 symbols decide)
+    sym0 = np.concatenate([[0], np.cumsum(nchips // 11 + 16)])[:-1]
+    d_sym = ops.alloc_c16(int((nchips // 11 + 16).sum()))
+    nsym = np.array([min((nchips[j] - cc[j]) // 11, 160) for j in go], np.int64)
+    ops.despread(d_chips, u32(chip0[go] + cc[go]), u32(nsym), u32(sym0[go]), d_sym)
+    sst, used = ops.sfd_sync(d_sym, u32(sym0[go]), u32(nsym), state11b_reset("sfd", len(go)), mode)
+    sstate = state11b_reset("stream", len(live))                                # CF_DifferentialDemap, CF_Descramber: what TSFDSync leaves is what the demappers find
+    rate = np.zeros(len(live), np.int64)
+    nxt = []
+    for k, j in enumerate(go):
+        cc[j] += 11 * int(used[k])
+        rate[j] = sst[k, 7]; short[j] = bool(sst[k, 3]) and rate[j] != RATE11B_SYNC
+        sstate[j, 0] = sst[k, 0]; sstate[j, 1] = sst[k, 1]
+        if sst[k, 8]:
+            event(j, sst[k, 8])
+        elif rate[j] != RATE11B_SYNC:
+            nxt.append(j)
+    go = nxt
+    # ---- the PLCP header: 48 symbols through TDBPSKDemap (RATE_1M) or 24 through TDQPSKDemap (RATE_2M, behind a short SFD) -> TDesc741 -> TBB11bPlcpParser
+    d_raw = ops.alloc_u8(4096 * len(live)); d_bytes = ops.alloc_u8(4096 * len(live)); d_hdr = ops.alloc_u8(6 * len(live))
+    byte0 = 4096 * np.arange(len(live), dtype=np.int64)
+
+    def demod(js, r, nbytes, out, out_first):
+        """nbytes[k] descrambled bytes of capture js[k] at rate r, from its chip cursor, into out at out_first[k]"""
+        js = list(js); nbytes = np.asarray(nbytes, np.int64)
+        if r in (RATE11B_1M, RATE11B_2M):
+            per = 8 if r == RATE11B_1M else 4
+            ops.despread(d_chips, u32(chip0[js] + cc[js]), u32(per * nbytes), u32(sym0[js]), d_sym)
+            sstate[js] = ops.stream_stage("dbpsk" if r == RATE11B_1M else "dqpsk", d_sym, u32(sym0[js]), u32(nbytes), u32(byte0[js]), sstate[js], d_raw)
+            cc[js] += 11 * per * nbytes
+        else:
+            per = 16 if r == RATE11B_5P5M else 8
+            sstate[js] = ops.stream_stage("cck5p5" if r == RATE11B_5P5M else "cck11", d_chips, u32(chip0[js] + cc[js]), u32(nbytes), u32(byte0[js]), sstate[js], d_raw)
+            cc[js] += per * nbytes
+        sstate[js] = ops.stream_stage("desc741", d_raw, u32(byte0[js]), u32(nbytes), u32(out_first), sstate[js], out)
+
+    chips_per_byte = {RATE11B_1M: 88, RATE11B_2M: 44, RATE11B_5P5M: 16, RATE11B_11M: 8}
+    hdr_of = []                                                                 # captures with a whole header, in d_hdr's order
+    for r in (RATE11B_1M, RATE11B_2M):
+        js = [j for j in go if rate[j] == r and nchips[j] - cc[j] >= 6 * chips_per_byte[r]]
+        if js:
+            demod(js, r, [6] * len(js), d_hdr, 6 * (len(hdr_of) + np.arange(len(js), dtype=np.int64)))
+            hdr_of += js
+    if not hdr_of:
+        return events
+    rec = ops.plcp_parse(d_hdr, len(hdr_of))
+    length = np.zeros(len(live), np.int64); kbps = np.zeros(len(live), np.int64)
+    go = []
+    for k, j in enumerate(hdr_of):
+        if rec[k, 0]:
+            event(j, rec[k, 0])
+            continue
+        kbps[j] = rec[k, 1]; length[j] = rec[k, 2]
+        if rec[k, 3]:
+            rate[j] = rec[k, 3]
+        # an unknown SIGNAL (length 0) and lengths below 4 never let TBB11bFrameSink decide; a frame the capture cuts off raises nothing either (nor, here, one
+        # longer than the harness's 4096-byte buffer)
+        if kbps[j] and 4 <= length[j] <= 4096 and nchips[j] - cc[j] >= (length[j] - 1) * chips_per_byte[int(rate[j])]:
+            go.append(j)
+    # ---- the payload: frame_length - 1 bytes (the sink decides one byte early) through the rate's demodulator -> TDesc741 -> TBB11bFrameSink
+    for r in (RATE11B_1M, RATE11B_2M, RATE11B_5P5M, RATE11B_11M):
+        js = [j for j in go if rate[j] == r]
+        if js:
+            demod(js, r, length[js] - 1, d_bytes, byte0[js])
+    if go:
+        rec = ops.frame_sink(d_bytes, u32(byte0[go]), u32(length[go]))
+        for k, j in enumerate(go):
+            if rec[k, 0]:
+                event(j, rec[k, 0], kbps[j], length[j], rec[k, 1], ops.host_u8(d_bytes, int(byte0[j]), int(byte0[j] + length[j] - 1)) + b"\0")
+    return events
+
+
+def rx11b_by_stages(d_iq, descs, mode=0, cca_pwr_threshold=1000 * 1000):
+    """The first event of every capture of a batch, through the thirteen 802.11b stage entry points alone (rx11b_stages with the GPU's bricks): d_iq int16 CUDA
+    [samples, 2] at 44 MHz, descs [(first sample, samples)], mode as Rx11b.set_preamble -> per capture None or a dict error_code, rate_kbps, length, crc32, flags
+    (ROW_SHORT_PREAMBLE), mpdu.  The MPDU's last byte and crc32's top byte are 0: what the reference's sink holds for the first frame of a capture.
+    A DEMONSTRATION and a test vehicle, not a fast path: between stages it reads counts and records back to the host to build the next tables, some twenty round trips
+    per hundred bursts of silence in front of the frame.  The counterpart of mod11a_by_stages; the fast path is Rx11b."""
+    return rx11b_stages(_Gpu11bOps(d_iq.device), d_iq, descs, mode, cca_pwr_threshold)
 
 
 def tx11n_samples(mpdu_len_nofcs, mcs):

@@ -8,7 +8,7 @@
 
 // Probe switches (SORA_SCAN_PROBE, SORA_DBG_*) belong to the TOOLS variant of the library (sora_amd.build.build_variant adds -DSORA_TOOLS for them): the product
 // build refuses them, so no measurement scaffolding can reach it by accident.
-#if !defined(SORA_TOOLS) && (defined(SORA_SCAN_PROBE) || defined(SORA_DBG_PIPE_TIMELINE) || defined(SORA_DBG_PIPE_LOSE_FLAGS))
+#if !defined(SORA_TOOLS) && (defined(SORA_SCAN_PROBE) || defined(SORA_DBG_PIPE_TIMELINE) || defined(SORA_DBG_PIPE_LOSE_FLAGS) || defined(SORA_DBG_SYMT_NO_SCAN))
 #error "SORA_SCAN_PROBE / SORA_DBG_* switches need -DSORA_TOOLS (sora_amd.build.build_variant)"
 #endif
 
@@ -145,6 +145,23 @@ __global__ void k_mod_ifftx(const uint32_t* in, uint32_t* out, uint32_t n, Table
 __global__ void k_mod_upsample(const uint32_t* in, uint32_t* out, const uint8_t* sees_next, uint32_t nblocks);
 __global__ void k_mod_pack16to8(const uint32_t* in, uint32_t* out, uint64_t nbursts);
 __global__ void k_mod_preamble(uint32_t* out, uint32_t ncopies, Tables T);
+
+// ---- the 802.11b receive graph's bricks as stages (k_11b.hip): stream f = n[f] units from element first[f] of `in`, written from element out_first[f] of `out`; grid = nstreams x chunks
+// workgroups of 256 units (the position-parallel stages), one workgroup (symtiming) or one wave (the searches, the sink) per stream
+__global__ void k_11b_dc_remove(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, const uint32_t* dc, uint32_t nstreams, uint32_t chunks);
+__global__ void k_11b_despread(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, uint32_t nstreams, uint32_t chunks);
+template <int BITS> __global__ void k_11b_demap(const uint32_t* in, uint8_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, const uint32_t* state,
+                                                uint32_t nstreams, uint32_t chunks);
+template <int R> __global__ void k_11b_cck(const uint32_t* in, uint8_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, const uint32_t* state,
+                                           uint32_t nstreams, uint32_t chunks);
+__global__ void k_11b_desc741(const uint8_t* in, uint8_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, const uint32_t* state, uint32_t nstreams, uint32_t chunks);
+__global__ void k_11b_stream_state(const void* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t nstreams, int kind);
+__global__ void k_11b_symtiming(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, int* state, uint32_t* nchips, uint32_t nstreams);
+__global__ void k_11b_energy_detect(const uint32_t* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t* used, uint32_t nstreams);
+__global__ void k_11b_barker_sync(const uint32_t* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t* used, uint32_t nstreams);
+__global__ void k_11b_sfd_sync(const uint32_t* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t* used, uint32_t nstreams, int mode);
+__global__ void k_11b_plcp_parse(const uint8_t* hdr, uint32_t* rec, uint32_t nstreams);
+__global__ void k_11b_frame_sink(const uint8_t* bytes, const uint32_t* first, const uint32_t* len, uint32_t* rec, uint32_t nstreams, const uint32_t* crc_tab);
 
 // ---- 802.11n 2x2 transmitter (k_tx11n.hip)
 struct Tx11nArgs {             // sora_hip_tx11n

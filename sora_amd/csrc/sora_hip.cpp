@@ -1876,6 +1876,137 @@ int sora_hip_preamble11a(sora_complex16* d_out, size_t ncopies, void* stream)
 }
 #undef MOD_STAGE_ENTRY
 
+// ---- the 802.11b receive graph's bricks as stages (k_11b.hip)
+#define ST11B_ENTRY(who, nullcond, count) \
+    if (nullcond) return fail(SORA_ERR_INVALID_PARAM, who ": null pointer"); \
+    if ((count) == 0) return SORA_OK;                       /* (nothing to launch: true with or without a device) */ \
+    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path"); \
+    if ((count) >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, who ": too many streams for one call");
+static_assert(sizeof(sora_stream11b_state) == 16 && sizeof(sora_energy11b_state) == 68 && sizeof(sora_symtiming11b_state) == 8 && sizeof(sora_barker11b_state) == 60 &&
+              sizeof(sora_sfd11b_state) == 36 && sizeof(sora_plcp11b_rec) == 16 && sizeof(sora_sink11b_rec) == 8, "the 802.11b stage records are 32-bit words");
+static inline const uint32_t* w32(const void* p) { return static_cast<const uint32_t*>(p); }
+static inline uint32_t* w32(void* p) { return static_cast<uint32_t*>(p); }
+
+int sora_hip_dc_remove11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const sora_complex16* d_dc,
+                          sora_complex16* d_out, size_t nstreams, size_t max_n, void* stream)
+{
+    ST11B_ENTRY("sora_hip_dc_remove11b", !d_in || !d_first || !d_n || !d_out_first || !d_dc || !d_out, nstreams)
+    if (max_n == 0) return SORA_OK;
+    uint32_t chunks; unsigned grid;
+    if (max_n >= (1u << 29) || !mod_grid(nstreams, 4 * max_n, &chunks, &grid)) return fail(SORA_ERR_CAPACITY, "sora_hip_dc_remove11b: nstreams x max_n is too large for one call");
+    hipLaunchKernelGGL(k_11b_dc_remove, dim3(grid), dim3(256), 0, (hipStream_t)stream, w32(d_in), w32(d_out), d_first, d_n, d_out_first, w32(d_dc), (uint32_t)nstreams, chunks);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_energy_detect11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_energy11b_state* d_state, uint32_t* d_used,
+                              size_t nstreams, size_t max_n, void* stream)
+{
+    (void)max_n;                                                                 // (a wave per stream walks its own d_n[f])
+    ST11B_ENTRY("sora_hip_energy_detect11b", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
+    hipLaunchKernelGGL(k_11b_energy_detect, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, w32(d_in), d_first, d_n, w32(d_state), d_used, (uint32_t)nstreams);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_symtiming11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_symtiming11b_state* d_state,
+                          sora_complex16* d_out, uint32_t* d_nchips, size_t nstreams, size_t max_n, void* stream)
+{
+    (void)max_n;
+    ST11B_ENTRY("sora_hip_symtiming11b", !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out || !d_nchips, nstreams)
+    hipLaunchKernelGGL(k_11b_symtiming, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, w32(d_in), w32(d_out), d_first, d_n, d_out_first,
+                       reinterpret_cast<int*>(d_state), d_nchips, (uint32_t)nstreams);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_barker_sync11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_barker11b_state* d_state, uint32_t* d_used,
+                            size_t nstreams, size_t max_n, void* stream)
+{
+    (void)max_n;
+    ST11B_ENTRY("sora_hip_barker_sync11b", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
+    hipLaunchKernelGGL(k_11b_barker_sync, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, w32(d_in), d_first, d_n, w32(d_state), d_used, (uint32_t)nstreams);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_despread11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_complex16* d_out,
+                         size_t nstreams, size_t max_n, void* stream)
+{
+    ST11B_ENTRY("sora_hip_despread11b", !d_in || !d_first || !d_n || !d_out_first || !d_out, nstreams)
+    if (max_n == 0) return SORA_OK;
+    uint32_t chunks; unsigned grid;
+    if (!mod_grid(nstreams, max_n, &chunks, &grid)) return fail(SORA_ERR_CAPACITY, "sora_hip_despread11b: nstreams x max_n is too large for one call");
+    hipLaunchKernelGGL(k_11b_despread, dim3(grid), dim3(256), 0, (hipStream_t)stream, w32(d_in), w32(d_out), d_first, d_n, d_out_first, (uint32_t)nstreams, chunks);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_sfd_sync11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_sfd11b_state* d_state, uint32_t* d_used,
+                         size_t nstreams, size_t max_n, int mode, void* stream)
+{
+    (void)max_n;
+    ST11B_ENTRY("sora_hip_sfd_sync11b", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
+    if (mode != 0 && mode != 1) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_sfd_sync11b: mode must be 0 or 1");
+    hipLaunchKernelGGL(k_11b_sfd_sync, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, w32(d_in), d_first, d_n, w32(d_state), d_used, (uint32_t)nstreams, mode);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+// the five position-parallel stream stages with a sora_stream11b_state: the stage's kernel, then the state behind it (kind: k_11b_stream_state)
+static int stream11b_stage(int kind, const char* who, const void* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state,
+                           uint8_t* d_out, size_t nstreams, size_t max_n, void* stream)
+{
+    if (max_n == 0) return SORA_OK;
+    uint32_t chunks; unsigned grid;
+    if (!mod_grid(nstreams, max_n, &chunks, &grid)) return fail(SORA_ERR_CAPACITY, who);
+    hipStream_t st = (hipStream_t)stream; const uint32_t ns = (uint32_t)nstreams; uint32_t* state = w32(d_state);
+    switch (kind) {
+    case 0: hipLaunchKernelGGL(k_11b_demap<1>, dim3(grid), dim3(256), 0, st, w32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
+    case 1: hipLaunchKernelGGL(k_11b_demap<2>, dim3(grid), dim3(256), 0, st, w32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
+    case 2: hipLaunchKernelGGL(k_11b_cck<5>, dim3(grid), dim3(256), 0, st, w32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
+    case 3: hipLaunchKernelGGL(k_11b_cck<11>, dim3(grid), dim3(256), 0, st, w32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
+    default: hipLaunchKernelGGL(k_11b_desc741, dim3(grid), dim3(256), 0, st, static_cast<const uint8_t*>(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
+    }
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_11b_stream_state, dim3((ns + 255) / 256), dim3(256), 0, st, d_in, d_first, d_n, state, ns, kind);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+#define STREAM11B(name, kind, in_t) \
+    int name(const in_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state, uint8_t* d_out, size_t nstreams, \
+             size_t max_n, void* stream) \
+    { \
+        ST11B_ENTRY(#name, !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out, nstreams) \
+        return stream11b_stage(kind, #name ": nstreams x max_n is too large for one call", d_in, d_first, d_n, d_out_first, d_state, d_out, nstreams, max_n, stream); \
+    }
+STREAM11B(sora_hip_dbpsk_demap11b, 0, sora_complex16)
+STREAM11B(sora_hip_dqpsk_demap11b, 1, sora_complex16)
+STREAM11B(sora_hip_cck5p5_decode11b, 2, sora_complex16)
+STREAM11B(sora_hip_cck11_decode11b, 3, sora_complex16)
+STREAM11B(sora_hip_desc741_11b, 4, uint8_t)
+#undef STREAM11B
+
+int sora_hip_plcp_parse11b(const uint8_t* d_hdr, sora_plcp11b_rec* d_rec, size_t nstreams, void* stream)
+{
+    ST11B_ENTRY("sora_hip_plcp_parse11b", !d_hdr || !d_rec, nstreams)
+    if ((uintptr_t)d_rec & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_plcp_parse11b: the records must be 16-byte aligned");
+    hipLaunchKernelGGL(k_11b_plcp_parse, dim3((unsigned)((nstreams + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_hdr, w32(d_rec), (uint32_t)nstreams);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_frame_sink11b(const uint8_t* d_bytes, const uint32_t* d_first, const uint32_t* d_len, sora_sink11b_rec* d_rec, size_t nstreams, void* stream)
+{
+    ST11B_ENTRY("sora_hip_frame_sink11b", !d_bytes || !d_first || !d_len || !d_rec, nstreams)
+    if ((uintptr_t)d_rec & 7) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_frame_sink11b: the records must be 8-byte aligned");
+    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    hipLaunchKernelGGL(k_11b_frame_sink, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, d_bytes, d_first, d_len, w32(d_rec), (uint32_t)nstreams, D->T.crc);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+#undef ST11B_ENTRY
+
 // ---- 802.11n 2x2 transmitter
 // The fixed fields of LSrc / HTSrc (preamble11n.hpp:8-83), per chain: L-STF (320), L-LTF (320), HT-STF, HT-LTF1, HT-LTF2 (160 each).
 // Each is round(s * sum_k X_k exp(+2 pi i k n / 128)) in double precision -- the standard's frequency-domain sequence X in bins -26..26
