@@ -728,6 +728,32 @@ int   sora_ht40_soft_of(sora_ht40_t* rx, int ticket, uint32_t frame, uint32_t st
  * hold more frames / soft values than the handle was created for are reported by sora_ht40_wait / _results_of (SORA_ERR_CAPACITY). */
 int   sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0, const sora_complex16* d_iq1, const sora_capture_desc* h_caps, size_t ncaps,
                                      uint32_t max_frames_per_capture);
+/* The front end's own definitions, stated in full (tests/cxx/ht40_front_model.c restates them on the oracle's bricks and tests/test_gpu_ht40_front.py holds the
+ * records below to that model, field for field):
+ *   - kept sample m of a capture (m counts from the capture's first sample, and on from call to call in stream mode) is x[2m], negated with int16 saturation
+ *     when m is odd (-(-32768) = 32767);
+ *   - the gate behind T11nSigParser's own checks (L-SIG tail / reserved bit / parity / rate, HT-SIG CRC-8 and tail) is 8 <= MCS <= 14 && CBW 40 && 4 <= LENGTH <= 4000;
+ *     the parser's L-SIG bound (2 x the L-SIG LENGTH field <= 1500, PHY_11n.hpp _parse_plcp) stands as it is, so a frame that announces more than 750 there
+ *     -- about 1 ms behind L-SIG: MCS 8 beyond roughly 1650 bytes -- fails its header whatever HT-SIG says;
+ *   - a frame with a sound header is an event only if HT-STF, both HT-LTFs and all nsym data symbols lie inside the capture's real samples (nsym =
+ *     sora_ht40_symbols, in joint coding sora_ht40_symbols_joint); otherwise there is no event and the capture is over.  A capture that ends inside the SIG field
+ *     decodes its missing symbols as zeros, as the reference's flush does: a header that fails then is an event, one that passes is a frame cut off;
+ *   - end_sample and the origin of the next carrier sense follow RxThread's source calls of 28 samples;
+ *   - noise_var = S / 416 in single precision, S = the sum of |Y1 - Y2|^2 over the 52 occupied carriers of both chains' two L-LTF FFT<64> outputs.
+ * Diagnostic, for tests (like sora_ht40_soft_of: no kernel and no launch differ for it): the records of capture `capture` (index into the call's h_caps) of the
+ * raw-capture call `ticket`, in time order.  Waits for that call as sora_ht40_results_of does, and answers also for a call that ended in SORA_ERR_CAPACITY (the
+ * records exist either way).  *nfound receives min(events the capture raised, max_frames_per_capture), also when cap is too small (SORA_ERR_CAPACITY; nothing is
+ * copied then).  SORA_ERR_INVALID_PARAM: a stale ticket, a descriptor call, a capture index past the call's. */
+typedef struct {
+    uint32_t a20;           /* 20 MHz index in the capture (40 MHz sample 2 x a20) behind the last SIG symbol taken: the first HT-STF sample of a recorded frame */
+    uint32_t mcs, ht_len;   /* HT-SIG's MCS and LENGTH; 0 unless the frame was recorded */
+    uint32_t nsym;          /* data symbols in the call's coding; 0 unless the frame was recorded */
+    int32_t  cfo;           /* the L-LTF estimate, phase step per 20 MHz sample, 65536 = 2 pi; the data field takes cfo / 2 (C division: toward zero) */
+    float    noise_var;     /* as handed to the data field */
+    uint32_t end_sample;    /* 40 MHz source position at which the event is seen */
+    uint32_t error_code;    /* 0: recorded (the data field's rows say FRAME_OK / CRC32_FAIL), else SORA_E_PLCP_HEADER_FAIL */
+} sora_ht40_found;
+int   sora_ht40_found_of(sora_ht40_t* rx, int ticket, uint32_t capture, sora_ht40_found* h_found, size_t cap, size_t* nfound);
 /* Tickets, as for sora_rx_t: every process call has one; it stays valid until sora_ht40_calls_in_flight() (8) further calls have reused its
  * slot (or, once the call is released -- delivered and waited for -- until the next call, which takes a released slot first) -- so back-to-back calls are all collectable, each by its own
  * ticket, while later ones run.  The INPUT buffers of a call must stay

@@ -54,6 +54,11 @@ class Ht40Frame(ctypes.Structure):
                 ("cfo", ctypes.c_int32), ("noise_var", ctypes.c_float), ("frame_id", ctypes.c_uint32)]
 
 
+class Ht40Found(ctypes.Structure):                      # sora_ht40_found: one record of the 40 MHz HT front end (sora_ht40_found_of)
+    _fields_ = [("a20", ctypes.c_uint32), ("mcs", ctypes.c_uint32), ("ht_len", ctypes.c_uint32), ("nsym", ctypes.c_uint32), ("cfo", ctypes.c_int32),
+                ("noise_var", ctypes.c_float), ("end_sample", ctypes.c_uint32), ("error_code", ctypes.c_uint32)]
+
+
 EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count", "sora_hip_malloc", "sora_hip_free",
            "sora_hip_memcpy_h2d", "sora_hip_memcpy_d2h", "sora_hip_memcpy_d2d", "sora_hip_stream_synchronize", "sora_rx_create", "sora_rx_destroy", "sora_rx_reset",
            "sora_rx_flush", "sora_rx_stream", "sora_rx_process_dev", "sora_rx_process_dump", "sora_rx_set_stream_mode", "sora_rx_stream_consumed", "sora_rx_process", "sora_rx_results",
@@ -85,7 +90,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_rx11n_wait_any", "sora_rx11n_results_of", "sora_rx11n_set_mcs_max",
            "sora_ht40_symbols", "sora_ht40_create", "sora_ht40_destroy", "sora_ht40_stream", "sora_ht40_synchronize", "sora_ht40_set_trellis", "sora_ht40_process_dev",
                       "sora_ht40_process_captures_dev", "sora_ht40_results", "sora_ht40_ticket", "sora_ht40_calls_in_flight", "sora_ht40_wait", "sora_ht40_wait_any",
-                      "sora_ht40_stream_of", "sora_ht40_results_of", "sora_ht40_soft_of", "sora_ht40_set_stream_mode", "sora_ht40_stream_consumed",
+                      "sora_ht40_stream_of", "sora_ht40_results_of", "sora_ht40_soft_of", "sora_ht40_found_of", "sora_ht40_set_stream_mode", "sora_ht40_stream_consumed",
                       "sora_ht40_set_coding", "sora_ht40_symbols_joint",
            "sora_shard_unique_id", "sora_shard_create", "sora_shard_destroy", "sora_shard_world", "sora_shard_partition", "sora_shard_gather_rows",
            "sora_shard_reduce_counters", "sora_shard_gather_results", "sora_shard_gather_results_mpdu"]
@@ -292,6 +297,7 @@ def load(build_if_missing=True):
     _deliver = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     L.sora_ht40_process_captures_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
     L.sora_ht40_soft_of.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    L.sora_ht40_found_of.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     # what the four receive handles share (include/sora_hip.h: tickets, calls in flight, stream continuation)
     vp = ctypes.c_void_p
     shared = [("_destroy", [vp], None), ("_stream", [vp], vp), ("_ticket", [vp], ctypes.c_int), ("_wait", [vp, ctypes.c_int], ctypes.c_int),
@@ -849,6 +855,19 @@ class RxHt40(_Handle):
         out = np.zeros(n.value, np.uint8)
         _check(self._L.sora_ht40_soft_of(self._h, t, int(frame), int(stream), out.ctypes.data, out.size, ctypes.byref(n)))
         return out[:n.value]
+
+    def found(self, capture, ticket=None):
+        """sora_ht40_found_of: the front end's records of capture `capture` (index into the call's captures) of a process_captures_dev call (ticket None: the most
+        recent call), in time order: [{a20, mcs, ht_len, nsym, cfo, noise_var (numpy float32), end_sample, error_code}] -- a diagnostic for tests"""
+        t = self.ticket() if ticket is None else int(ticket)
+        n = ctypes.c_size_t(0)
+        rc = self._L.sora_ht40_found_of(self._h, t, int(capture), None, 0, ctypes.byref(n))
+        if rc != SORA_OK and n.value == 0:
+            _check(rc)
+        arr = (Ht40Found * max(1, n.value))()
+        _check(self._L.sora_ht40_found_of(self._h, t, int(capture), arr, n.value, ctypes.byref(n)))
+        return [{"a20": r.a20, "mcs": r.mcs, "ht_len": r.ht_len, "nsym": r.nsym, "cfo": r.cfo, "noise_var": np.float32(r.noise_var), "end_sample": r.end_sample,
+                 "error_code": r.error_code} for r in arr[:n.value]]
 
 
 def ht40_symbols(length0, length1, n_bpsc, code_rate):

@@ -822,6 +822,29 @@ int sora_ht40_soft_of(sora_ht40_t* rx, int ticket, uint32_t frame, uint32_t stre
     return SORA_OK;
 }
 
+// Diagnostic (tests): the front end's records of one capture of a raw-capture call, as they lie in the slot's page-locked memory behind the call's kernels
+// (S.h_nfr, S.h_found: the copies ht40_collect_events reads).  They exist whatever k_ht40_plan made of them, so a call that ended in SORA_ERR_CAPACITY answers too.
+int sora_ht40_found_of(sora_ht40_t* rx, int ticket, uint32_t capture, sora_ht40_found* h_found, size_t cap, size_t* nfound)
+{
+    if (!rx || !nfound || (!h_found && cap)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_found_of: null argument", 0);
+    *nfound = 0;
+    Ht40Slot* S = call_find(rx->slot, kHt40Slots, ticket);
+    if (!S) return call_stale("sora_ht40_found_of");
+    if (!S->capture_mode) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_found_of: raw-capture calls (sora_ht40_process_captures_dev) only", 0);
+    if (capture >= S->ncaps) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_found_of: no such capture in this call", 0);
+    HIPCHK(hipSetDevice(rx->device));
+    HIPCHK(hipStreamSynchronize(S->stream));
+    const uint32_t mf = S->capture_mf, n = std::min(S->h_nfr[capture], mf);
+    *nfound = n;
+    if (n > cap) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_found_of: output buffer too small", 0);
+    for (uint32_t i = 0; i < n; i++) {
+        const Ht40Found& F = S->h_found[(size_t)capture * mf + i];
+        sora_ht40_found& o = h_found[i];
+        o.a20 = F.a20; o.mcs = F.mcs; o.ht_len = F.ht_len; o.nsym = F.nsym; o.cfo = F.cfo; o.noise_var = F.noise_var; o.end_sample = F.end_sample; o.error_code = F.error_code;
+    }
+    return SORA_OK;
+}
+
 int sora_ht40_results_of(sora_ht40_t* rx, int ticket, sora_frame_result* out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap)
 {
     if (!nout || !out) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_results_of: null argument", 0);

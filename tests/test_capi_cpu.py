@@ -171,3 +171,23 @@ def test_ht40_soft_read_out_is_declared_typed_and_refuses_a_null_handle(lib):
     assert b"sora_ht40_soft_of" in lib.sora_hip_last_error()
     assert lib.sora_ht40_soft_of(None, 1, 0, 0, None, 0, None) == -1
     assert callable(getattr(sora_amd.RxHt40, "soft", None))
+
+
+def test_ht40_found_read_out_is_declared_typed_and_refuses_a_null_handle(lib):
+    """sora_ht40_found_of (the diagnostic tests/test_gpu_ht40_front.py reads the front end's records with): in the header, exported, typed by the binding, its
+    struct eight 32-bit words as the header lays them out, refused for a null handle, a null count or a null buffer with room before any device work, and RxHt40
+    carries the method."""
+    import sora_amd
+    from sora_amd import capi
+    n = "sora_ht40_found_of"
+    assert n in declared_functions() and n in capi.EXPORTS and hasattr(lib, n)
+    assert len(lib.sora_ht40_found_of.argtypes) == 6
+    assert ctypes.sizeof(capi.Ht40Found) == 32 and [f[0] for f in capi.Ht40Found._fields_] == re.findall(
+        r"(\w+);", re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct \{([^}]*)\} sora_ht40_found;", open(HEADER).read(), re.S).group(1), flags=re.S).replace(",", ";"))
+    lib.sora_hip_table_digest(None, None)                               # leaves a message that names no receive handle
+    nf = ctypes.c_size_t(5)
+    assert lib.sora_ht40_found_of(None, 1, 0, None, 0, ctypes.byref(nf)) == -1            # SORA_ERR_INVALID_PARAM
+    assert b"sora_ht40_found_of" in lib.sora_hip_last_error()
+    assert lib.sora_ht40_found_of(None, 1, 0, None, 0, None) == -1
+    assert lib.sora_ht40_found_of(ctypes.c_void_p(16), 1, 0, None, 4, ctypes.byref(nf)) == -1             # a null buffer with room for four records
+    assert callable(getattr(sora_amd.RxHt40, "found", None))

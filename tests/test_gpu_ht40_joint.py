@@ -9,6 +9,7 @@ import pytest
 from oracle import ht40_data_model as dm
 from oracle import py_ht40 as m
 import ht40_joint_model as J
+from ht40_soft_check import assert_is_the_joint_model as assert_is_the_model, joint_models as models, joint_soft_capacity as soft_capacity
 from test_gpu_ht40_soft import GRID_RATES, H0, adversarial_inputs, place
 from test_gpu_ht40_soft import lengths_for as per_stream_lengths_for, real_frame as per_stream_frame
 
@@ -45,11 +46,6 @@ def real_frame(rng, nb, cr, length, sigma, cfo_step=0.0):
     return m.channel(x, H0, sigma, rng, cfo_step=cfo_step), psdu
 
 
-def soft_capacity(descs):
-    """the handle's rule, unchanged by the coding: 2 x nsym x 108 n_bpsc (+ 64) per frame"""
-    return sum(2 * (J.nsym_for(d[3], d[1], d[2]) * 108 * d[1] + 64) for d in descs)
-
-
 # ------------------------------------------------------------------ one call, read back whole
 def gpu_call(env, iq, descs, want_w=True, trellis=None):
     """-> dict: rows (results), soft[frame] (the merged bytes), w int16 [nframes, 4, 128, 2] or None"""
@@ -64,26 +60,6 @@ def gpu_call(env, iq, descs, want_w=True, trellis=None):
     soft = [rx.soft(f, 0, ticket=t) for f in range(len(descs))]
     rx.close()
     return {"rows": rows, "soft": soft, "w": w.cpu().numpy() if want_w else None}
-
-
-def models(iq, descs, w):
-    return [J.rx_model(iq, d[0], d[1], d[2], d[3], d[5], w[f]) for f, d in enumerate(descs)]
-
-
-def assert_is_the_model(got, want, descs, what=""):
-    """every merged soft byte, every row field and every PSDU byte of every frame: ONE row per frame"""
-    assert len(got["rows"]) == len(descs), (what, len(got["rows"]))
-    for f, d in enumerate(descs):
-        tag = (what, f, d[1:6])
-        assert got["soft"][f].shape == want[f].soft.shape == (want[f].nsym * 216 * d[1],), tag
-        if not np.array_equal(got["soft"][f], want[f].soft):
-            bad = np.nonzero(got["soft"][f] != want[f].soft)[0]
-            raise AssertionError("%r: %d merged soft bytes differ, the first in symbol %d (position %d: GPU %d, model %d)"
-                                 % (tag, len(bad), bad[0] // (216 * d[1]), bad[0], got["soft"][f][bad[0]], want[f].soft[bad[0]]))
-        r = got["rows"][f]; wf = want[f]
-        assert (r["capture_id"], r["start_sample"], r["stream"]) == (d[7], 0, 0), tag
-        assert (r["error_code"], r["length"], r["crc32"]) == (wf.error_code, d[3], wf.crc32), (tag, hex(r["error_code"]), hex(wf.error_code))
-        assert r["nsym"] == wf.nsym and r["rate_kbps"] == 10 * d[1] + d[2] and r["mpdu"] == wf.psdu, tag
 
 
 # ------------------------------------------------------------------ the shape grid

@@ -11,6 +11,7 @@ import pytest
 
 from oracle import ht40_data_model as dm
 from oracle import py_ht40 as m
+from ht40_soft_check import assert_is_the_model, models, soft_capacity
 
 pytestmark = pytest.mark.gpu
 
@@ -58,10 +59,6 @@ def place(segments, mods=None):
     return np.concatenate(parts, axis=1), offs
 
 
-def soft_capacity(sora, descs):
-    return sum(2 * (sora.ht40_symbols(d[3], d[4], d[1], d[2]) * 108 * d[1] + 64) for d in descs)
-
-
 # ------------------------------------------------------------------ one call, read back whole
 def gpu_call(env, iq, descs, want_w=True, trellis=None):
     """-> dict: rows (results), soft[frame][stream], w int16 [nframes, 4, 128, 2] or None"""
@@ -75,27 +72,6 @@ def gpu_call(env, iq, descs, want_w=True, trellis=None):
     soft = [[rx.soft(f, s, ticket=t) for s in range(2)] for f in range(len(descs))]
     rx.close()
     return {"rows": rows, "soft": soft, "w": w.cpu().numpy() if want_w else None}
-
-
-def models(iq, descs, w):
-    return [dm.model(iq, d[0], d[1], d[2], (d[3], d[4]), d[5], w[f]) for f, d in enumerate(descs)]
-
-
-def assert_is_the_model(got, want, descs, what=""):
-    """every soft byte, every row field and every PSDU byte of every frame and stream"""
-    assert len(got["rows"]) == 2 * len(descs)
-    for f, d in enumerate(descs):
-        for s in range(2):
-            tag = (what, f, s, d[1:6])
-            assert got["soft"][f][s].shape == want[f].soft[s].shape == (want[f].nsym * 108 * d[1],), tag
-            if not np.array_equal(got["soft"][f][s], want[f].soft[s]):
-                bad = np.nonzero(got["soft"][f][s] != want[f].soft[s])[0]
-                raise AssertionError("%r: %d soft bytes differ, the first in symbol %d (position %d: GPU %d, model %d)"
-                                     % (tag, len(bad), bad[0] // (108 * d[1]), bad[0], got["soft"][f][s][bad[0]], want[f].soft[s][bad[0]]))
-            r = got["rows"][2 * f + s]; ws = want[f].streams[s]
-            assert (r["capture_id"], r["stream"]) == (d[7], s), tag
-            assert (r["error_code"], r["length"], r["crc32"]) == (ws.error_code, d[3 + s], ws.crc32), (tag, hex(r["error_code"]), hex(ws.error_code))
-            assert r["nsym"] == want[f].nsym and r["mpdu"] == ws.psdu, tag
 
 
 def saturated_symbols(want):
