@@ -142,12 +142,11 @@ __global__ void __launch_bounds__(256) k_11b_stream_state(const void* __restrict
 
 // ---- TSymTiming: one wave per stream, tiles of 64 blocks of 28 samples (under 8 KB of LDS: some twenty streams' walks share a CU and hide each other's latency).
 // Per tile: (1) the tile is staged in LDS (29 words per block: an odd stride); lane b sums the
-// four phase energies of block b and boils them down to what AdjustTiming would do for each of the four values m_index can have there: 3 bits each, one word per block; (2) the
+// four phase energies of block b and boils them down to what AdjustTiming would do for each of the four values m_index can have there: 4 bits each (b11_timing_code), one word per block; (2) the
 // wave walks the recurrence of m_index / m_frag over those words ALONE -- the words come 64 at a time into one register, block j's by v_readlane, so the walk is a chain of scalar
 // instructions with no memory access on it -- and leaves each block's first index and output position; (3) lane b gathers its block's 6, 7 or 8 chips from LDS to that position.
 // state = { m_index, m_frag }.  A block gives at most 8 chips: an m_index below -4, which no brick holds, is decimated as -4.
 constexpr int kSymtTile = 64;                                                   // = the workgroup: one wave
-enum { kSymtNone = 0, kSymtLate, kSymtFragUp, kSymtEarly, kSymtFragDown };        // AdjustTiming's outcomes: m_index++ (m_frag = 0), m_frag++, m_index-- (m_frag = 0), m_frag--
 __global__ void __launch_bounds__(kSymtTile) k_11b_symtiming(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const uint32_t* __restrict__ first, const uint32_t* __restrict__ n,
         const uint32_t* __restrict__ out_first, int* __restrict__ state, uint32_t* __restrict__ nchips, uint32_t nstreams)
 {
@@ -174,11 +173,8 @@ __global__ void __launch_bounds__(kSymtTile) k_11b_symtiming(const uint32_t* __r
             for (int i = 0; i < 28; i++) sum[i & 3] = wadd32(sum[i & 3], sqnorm(sra(unpack(s_x[tid * 29 + i]), 3)));
             uint32_t code = 0;
 #pragma unroll
-            for (int mi = 0; mi < 4; mi++) {                                     // AdjustTiming (:118-170): the early-late detector on the energies of the four sampling phases
-                const int se = sum[(mi + 3) & 3], sl = sum[(mi + 1) & 3], sm = sum[mi];
-                const uint32_t c = se < sl ? (sm < se ? kSymtLate : sm < sl ? kSymtFragUp : kSymtNone) : (sm < sl ? kSymtEarly : sm < se ? kSymtFragDown : kSymtNone);
-                code |= c << (3 * mi);
-            }
+            for (int mi = 0; mi < 4; mi++)                                       // AdjustTiming at each of the four sampling phases
+                code |= b11_timing_code(b11_adjust_timing(sum[mi], sum[(mi + 3) & 3], sum[(mi + 1) & 3])) << (4 * mi);
             s_code[tid] = code;
         }
         __syncthreads();
@@ -204,13 +200,7 @@ __global__ void __launch_bounds__(kSymtTile) k_11b_symtiming(const uint32_t* __r
                     const uint32_t rec = ((uint32_t)(idx0 + 4) << 16) | pos;
                     mine = tid == j ? rec : mine;
                     pos += (uint32_t)c;
-                    const uint32_t act = (code >> (3 * mi)) & 7u;
-                    const int late = act == kSymtLate, early = act == kSymtEarly;              // (selects, not branches: the chain stays a dozen scalar instructions)
-                    mi += late - early;
-                    fr = (late | early) ? 0 : fr + (act == kSymtFragUp) - (act == kSymtFragDown);
-                    const int over = fr >= 4, under = fr <= -4;
-                    mi += over - under;
-                    fr = over ? -3 : under ? 3 : fr;
+                    b11_timing_carry(b11_timing_of(code >> (4 * mi)), mi, fr);                  // (selects, not branches: the chain stays a dozen scalar instructions)
                 }
                 if (tid < m) s_rec[j0 + tid] = mine;
             }
@@ -267,7 +257,7 @@ __global__ void __launch_bounds__(64) k_11b_energy_detect(const uint32_t* __rest
                 if (++s_st[9] >= 8) s_st[9] = 0;
                 s_st[10]++;
                 if (s_st[10] >= 32) {
-                    if (s_st[10] >= 100) { s_st[12] = kE11bCsTimeout; continue; }
+                    if (s_st[10] >= 100) { s_st[12] = E_CS_TIMEOUT; continue; }
                     if (s_st[0] >= s_st[13]) s_st[11] = 1;
                 }
                 if (!s_st[11]) {                                                 // energy gating: only low-power bursts reach the DC estimator
@@ -314,18 +304,9 @@ __global__ void __launch_bounds__(64) k_11b_barker_sync(const uint32_t* __restri
                 const cpx ss = unpack(s_ss[used - c0]);
                 used++;
                 search++;
-                if (search >= 11 * 4) { err = kE11bSyncTimeout; break; }
-                const cpx o = csub16(p[0], ss);                                  // UpdateBarkerCorrelation (:296-313)
-                p[0] = csub16(p[1], ss); p[1] = csub16(p[2], ss); p[2] = cadd16(p[3], ss); p[3] = cadd16(p[4], ss); p[4] = cadd16(p[5], ss); p[5] = csub16(p[6], ss);
-                p[6] = cadd16(p[7], ss); p[7] = cadd16(p[8], ss); p[8] = csub16(p[9], ss); p[9] = ss;
-                const int corr = sqnorm(o);
-                if (flag == k11bNoPeak) {
-                    if (corr > mmax) { mmax = corr; peak = 1; } else if (++peak == 11) flag = k11bPeakFound;
-                } else if (flag == k11bPeakFound) {
-                    mmax = corr / 2; peak = 1; flag = k11bPeakValid;
-                } else if (flag == k11bPeakValid) {
-                    if (corr > mmax) { mmax = corr; peak = 0; flag = k11bNoPeak; } else if (++peak == 11) flag = k11bPeakValided;
-                } else flag = k11bBarkerSynced;                                  // "just skip one more symbol"
+                if (search >= 11 * 4) { err = E_SYNC_TIMEOUT; break; }
+                const cpx o = b11_barker_shift(ss, [&](int k) { return p[k]; }, [&](int k, cpx v) { p[k] = v; });
+                b11_barker_peak(sqnorm(o), flag, peak, mmax);
             }
             s_st[0] = (uint32_t)flag; s_st[1] = (uint32_t)peak; s_st[2] = (uint32_t)mmax; s_st[3] = (uint32_t)search; s_st[14] = err;
 #pragma unroll
@@ -376,12 +357,12 @@ __global__ void __launch_bounds__(64) k_11b_sfd_sync(const uint32_t* __restrict_
                     else if (mode >= 1 && word == 0 && cnt >= 16) zero = 1;
                 } else if (one) {
                     if (word == 0xF3A0u) rate = k11bRate1M;
-                    else if (word != 0xFFFFu) { if (errs++ > 32) { err = kE11bSfdFail; continue; } }
+                    else if (word != 0xFFFFu) { if (errs++ > 32) { err = E_SFD_FAIL; continue; } }
                 } else {
                     if (word == 0x05CFu) rate = k11bRate2M;
-                    else if (word != 0) { if (errs++ > 32) { err = kE11bSfdFail; continue; } }
+                    else if (word != 0) { if (errs++ > 32) { err = E_SFD_FAIL; continue; } }
                 }
-                if (cnt > 128 + 16) err = kE11bSfdTimeout;
+                if (cnt > 128 + 16) err = E_SFD_TIMEOUT;
             }
             if (used > 0) s_st[0] = src[used - 1];
             s_st[1] = reg; s_st[2] = one; s_st[3] = zero; s_st[4] = word; s_st[5] = errs; s_st[6] = cnt; s_st[7] = rate; s_st[8] = err;
@@ -402,19 +383,12 @@ __global__ void __launch_bounds__(256) k_11b_plcp_parse(const uint8_t* __restric
     uint32_t h[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) h[k] = hdr[(size_t)6 * f + k];
-    uint32_t err = 0, kbps = 0, len = 0, rate = 0;
-    if (b11_crc16(h) != (h[4] | (h[5] << 8))) err = kE11bPlcpFail;
-    else {
-        const uint32_t l = h[2] | (h[3] << 8), ext = (h[1] >> 7) + ((h[1] >> 3) & 1u);
-        switch (h[0]) {
-        case 0x0A: kbps = 1000;  len = l >> 3; rate = k11bRate1M; break;
-        case 0x14: kbps = 2000;  len = l >> 2; rate = k11bRate2M; break;
-        case 0x37: kbps = 5500;  len = (((l * 11u) >> 4) - ext) & 0xFFFFu; rate = k11bRate5p5M; break;
-        case 0x6E: kbps = 11000; len = (((l * 11u) >> 3) - ext) & 0xFFFFu; rate = k11bRate11M; break;
-        default: break;
-        }
+    uint4 r = uint4{ E_PLCP_HEADER_FAIL, 0u, 0u, 0u };
+    if (b11_crc16(h) == (h[4] | (h[5] << 8))) {
+        const B11Plcp p = b11_plcp_fields(h[0], h[1], h[2] | (h[3] << 8), k11bRateSync);
+        r = uint4{ 0u, p.kbps, p.len, (uint32_t)p.rate };
     }
-    reinterpret_cast<uint4*>(rec)[f] = uint4{ err, kbps, len, rate };
+    reinterpret_cast<uint4*>(rec)[f] = r;
 }
 
 // ---- TBB11bFrameSink: one wave per frame; the CRC-32 table in LDS, lane 0 runs the register over bytes 0 .. len - 5 and compares with bytes len - 4 .. len - 2 (the sink
@@ -436,7 +410,7 @@ __global__ void __launch_bounds__(64) k_11b_frame_sink(const uint8_t* __restrict
         uint32_t c = 0xFFFFFFFFu;
         for (uint32_t i = 0; i + 4 < len; i++) c = s_crc[(c ^ src[i]) & 0xFFu] ^ (c >> 8);
         for (uint32_t k = 0; k < 3; k++) { const uint32_t i = len - 4 + k; if (i < 4096u) p |= (uint32_t)src[i] << (8 * k); }
-        err = ((~c & 0x00FFFFFFu) == (p & 0x00FFFFFFu)) ? kE11bFrameOk : kE11bCrc32Fail;
+        err = b11_fcs_verdict(c, p);
     }
     reinterpret_cast<uint2*>(rec)[f] = uint2{ err, p };
 }

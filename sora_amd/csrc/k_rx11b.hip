@@ -26,14 +26,11 @@
 // -- the reference's three "modules" of four correlations each (cck.hpp:268-745) are the quads of that grid -- and the reference's
 // comparison tree (ties included) runs as two quad_perm exchanges plus four scalar compares.  phi4 and the DQPSK bits are scalar.
 #include "kernels.h"
+#include "dev_11b.h"
 
 namespace sora {
 
 namespace {
-// the others: rx_types.h
-constexpr uint32_t E_NOT_SUPPORTED = 0x80000003u, E_SFD_FAIL = 0x80000004u, E_SFD_TIMEOUT = 0x80000008u, E_SYNC_TIMEOUT = 0x80000009u;
-enum { RATE_SYNC = 0, RATE_1M, RATE_2M, RATE_5P5M, RATE_11M };
-enum { NO_PEAK_FOUND = 0, PEAK_FOUND, PEAK_VALID, PEAK_VALIDED, BARKER_SYNCED };
 constexpr uint32_t kOutBuf = 4096;                                    // OUTPUTBUF_SIZE (fb11b_demod.cpp:21)
 constexpr uint32_t kRec11bMagic = 0x534F3142u;                        // a continuation record holds a resume point (a fresh stream is not all zeros)
 
@@ -44,13 +41,11 @@ template <int CTRL> __device__ __forceinline__ int dpp(int v) { return __builtin
 __device__ __forceinline__ int quad_sum(int v) { v += dpp<0xB1>(v); return v + dpp<0x4E>(v); }
 __device__ __forceinline__ int sum8(int v) { v = quad_sum(v); return v + dpp<0x104>(v); }                        // + row_shl:4: lanes 0..3 hold lanes 0..7
 __device__ __forceinline__ void lds_order() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-__device__ __forceinline__ uint32_t dot_sign(int rre, int rim, int xre, int xim)          // (ulong)(ref.re*s.re + ref.im*s.im) >> 31
-{ return ((uint32_t)(rre * xre) + (uint32_t)(rim * xim)) >> 31; }
 }  // namespace
 
 // Two instantiations.  CCK = false is the kernel for what nearly every capture holds (Barker-spread 1 / 2 Mbps frames): without the CCK decoders it
-// fits 64 VGPRs and runs 8 waves per SIMD.  When a header announces 5.5 / 11 Mbps it abandons the capture and flags it; the CCK = true instantiation
-// (125 VGPRs, 4 waves per SIMD) then redoes the flagged captures from their first sample.  Both write the same rows: the result is what one kernel
+// takes 84-89 VGPRs over its four forms (5 waves per SIMD) and no scratch.  When a header announces 5.5 / 11 Mbps it abandons the capture and flags it; the CCK = true instantiation
+// (128 VGPRs, 4 waves per SIMD, 28-100 bytes of scratch) then redoes the flagged captures from their first sample.  Both write the same rows: the result is what one kernel
 // with everything inlined gives (that single kernel cost every capture 7-13 % of its speed).
 // STREAM = true (sora_rx11b_set_stream_mode): the capture continues the stream its continuation record left off, and the
 // record and the resume point are rewritten by the pass that finishes the capture.  Every addition sits under "if constexpr (STREAM)": the
@@ -93,7 +88,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
     // "if (c) a++; else b++;" and "if (c) a = 1; else b = 1;" are merged by the optimiser into a store through a SELECTED POINTER, which pins
     // both variables to private memory; loads from there count as divergent and drag every branch of the state machine into exec-masked
     // vector code (3x the instructions).  Hence the select-style updates below.  Check: opt -passes='print<uniformity>' on the device IR.
-    uint32_t error_code = 0; int power = 0, rxrate = RATE_SYNC, plcp_data = 0;
+    uint32_t error_code = 0; int power = 0, rxrate = k11bRateSync, plcp_data = 0;
     int dc_re = 0, dc_im = 0;                                          // CF_VecDC
     int last_re = 0, last_im = 0; uint32_t byte_reg = 0;              // CF_DifferentialDemap::last_symbol, CF_Descramber::byte_reg: never reset
     uint32_t frame_length = 0, rate_kbps = 0, frame_crc32 = 0;
@@ -101,7 +96,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
     uint32_t avg_energy = 0, ecount = 0;                                                  // TEnergyDetect (window in LDS)
     uint32_t update_cnt = 8; int sdc_re = 0, sdc_im = 0;                                  // TDCEstimator
     int m_index = 2, m_frag = 0;                                                          // TSymTiming
-    int sync_flag = NO_PEAK_FOUND, last_peak_cnt = -1, m_max = 0, search_count = 0;      // TBarkerSync
+    int sync_flag = k11bNoPeak, last_peak_cnt = -1, m_max = 0, search_count = 0;      // TBarkerSync
     int chip_n = 0, acc_re = 0, acc_im = 0;                                               // the current port's despreader
     // TCCK5P5Decoder / TCCK11Decoder: queued chips (lane j = j-th chip, packed), is_even
     int cck_n = 0; uint32_t cck_even = 0; uint32_t cbuf = 0;
@@ -145,11 +140,11 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
     // (every lambda below is force-inlined: a called closure would keep the state it captures in scratch memory)
     auto graph_reset = [&]() __attribute__((always_inline)) {                                          // BB11bDemodCtx.reset() + pRxSource->Reset()
         if constexpr (STREAM) s_hw = max(s_hw, min(byte_count, kOutBuf));                              // s_out bytes [0, byte_count) were written
-        error_code = 0; power = 0; rxrate = RATE_SYNC; plcp_data = 0;
+        error_code = 0; power = 0; rxrate = k11bRateSync; plcp_data = 0;
         avg_energy = 0; ecount = 0;
         update_cnt = 8; sdc_re = sdc_im = 0;
         m_index = 2; m_frag = 0;
-        sync_flag = NO_PEAK_FOUND; last_peak_cnt = -1; m_max = 0; search_count = 0;
+        sync_flag = k11bNoPeak; last_peak_cnt = -1; m_max = 0; search_count = 0;
         lds_order(); if (lane < 32) p_re[lane] = 0; lds_order();
         chip_n = 0; acc_re = acc_im = 0; cck_n = 0; cck_even = 0;
         bit_one_found = 0; word = 0; bit_err_cnt = 0; sync_cnt = 0;
@@ -180,41 +175,21 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
                 for (int k = 0; k < 4; k++) { const uint32_t at = byte_count - 3 + k; p |= (at < kOutBuf ? (uint32_t)s_out[at] : 0u) << (8 * k); }
                 p = (uint32_t)uni((int)p);
                 frame_crc32 = p;
-                error_code = ((~crc32 & 0x00FFFFFFu) == (p & 0x00FFFFFFu)) ? E_FRAME_OK : E_CRC32_FAIL;
+                error_code = b11_fcs_verdict(crc32, p);
             }
         }
     };
     // ---- TBB11bPlcpParser (PHY_11b.hpp:560-640)
     auto plcp_parser = [&]() __attribute__((always_inline)) {
-        uint32_t c = 0xFFFF;                                            // CalcCRC16 over the first four bytes (CRC16.h: reflected 0x8408, init 0xFFFF, ~)
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            c ^= (hdr_lo >> (8 * i)) & 0xFF;
-#pragma unroll
-            for (int k = 0; k < 8; k++) c = (c & 1) ? (c >> 1) ^ 0x8408u : c >> 1;
-        }
-        if (((~c) & 0xFFFFu) != (hdr_hi & 0xFFFFu)) { error_code = E_PLCP_HEADER_FAIL; return; }
-        const uint32_t signal = hdr_lo & 0xFF, service = (hdr_lo >> 8) & 0xFF; uint32_t len = hdr_lo >> 16;
-        switch (signal) {
-        case 0x0A: rate_kbps = 1000;  len = len >> 3; rxrate = RATE_1M; break;
-        case 0x14: rate_kbps = 2000;  len = len >> 2; rxrate = RATE_2M; break;
-        case 0x37: rate_kbps = 5500;  len = (((len * 11) >> 4) - (service >> 7) - ((service >> 3) & 1)) & 0xFFFF; rxrate = RATE_5P5M; break;
-        case 0x6E: rate_kbps = 11000; len = (((len * 11) >> 3) - (service >> 7) - ((service >> 3) & 1)) & 0xFFFF; rxrate = RATE_11M; break;
-        default:   rate_kbps = 0; len = 0;
-        }
-        frame_length = len; plcp_data = 1;
-        if (!CCK && uni(rxrate) > RATE_2M) { cck_abort = 1; error_code = E_NOT_SUPPORTED; }        // this capture goes to the CCK instantiation
+        const uint32_t h[4] = { hdr_lo & 0xFFu, (hdr_lo >> 8) & 0xFFu, (hdr_lo >> 16) & 0xFFu, hdr_lo >> 24 };
+        if (b11_crc16(h) != (hdr_hi & 0xFFFFu)) { error_code = E_PLCP_HEADER_FAIL; return; }
+        const B11Plcp p = b11_plcp_fields(h[0], h[1], hdr_lo >> 16, rxrate);
+        rate_kbps = p.kbps; frame_length = p.len; rxrate = p.rate; plcp_data = 1;
+        if (!CCK && uni(rxrate) > k11bRate2M) { cck_abort = 1; error_code = E_NOT_SUPPORTED; }        // this capture goes to the CCK instantiation
     };
     // ---- TDesc741 (scramble.hpp:93-170) -> TBB11bPlcpSwitch (PHY_11b.hpp:459-519)
     auto byte_out = [&](uint32_t b) __attribute__((always_inline)) {
-        uint32_t st = byte_reg & 0x7F, xx = b, o = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t o1 = (xx ^ st ^ (st >> 3)) & 1;
-            st = (st >> 1) | ((xx & 1) << 6);
-            o = (o >> 1) | (o1 << 7);
-            xx >>= 1;
-        }
+        const uint32_t o = b11_desc741(byte_reg, b);
         byte_reg = b >> 1;
         if (!uni(plcp_data)) {
             const uint32_t sh = o << (8 * (hdr_n & 3));                 // (no pointer select between the two words: that would pin them to memory)
@@ -223,45 +198,23 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
         } else frame_sink(o);
     };
     // ---- TCCK11Decoder / TCCK5P5Decoder (cck.hpp): one code word = the chips in lanes 0..7 of `w` (packed COMPLEX16), wave-uniform result.
-    // Lane 4m+s (m, s = 0..3): r = (-j)^m, q = j^s;  A1 = P1 + r P0, A2 = r P2 - P3, A3 = P5 + r P4, A4 = P7 - r P6;
-    // Bx = (A2 + q A1) >> 2, By = (A4 + q A3) >> 2;  L = conj(Bx) By  (cck.hpp:268-303 and its three repetitions).
-    struct CckLane { int lre, lim, l5; };
+    // Lane 4m+s (m, s = 0..3) takes b11_cck_corr's hypothesis r = (-j)^m, q = j^s.
     auto cck_correlate = [&](uint32_t w, int first) __attribute__((always_inline)) {
-        int pre[8], pim[8];
+        cpx P[8];
 #pragma unroll
-        for (int i = 0; i < 8; i++) { const int v = lane_of((int)w, first + i); pre[i] = (int)(short)v; pim[i] = v >> 16; }
-        const int k = (4 - (lane >> 2)) & 3, sq = lane & 3;
-        auto rot = [](int re, int im, int kk, int& ore, int& oim) __attribute__((always_inline)) {     // (re + j im) * j^kk, exact in 32 bits
-            const int xr = (kk & 1) ? im : re, xi = (kk & 1) ? re : im;
-            ore = ((kk + 1) & 2) ? -xr : xr; oim = (kk & 2) ? -xi : xi;
-        };
-        int t_re, t_im, a1r, a1i, a2r, a2i, a3r, a3i, a4r, a4i;
-        rot(pre[0], pim[0], k, t_re, t_im); a1r = pre[1] + t_re; a1i = pim[1] + t_im;
-        rot(pre[2], pim[2], k, t_re, t_im); a2r = t_re - pre[3]; a2i = t_im - pim[3];
-        rot(pre[4], pim[4], k, t_re, t_im); a3r = pre[5] + t_re; a3i = pim[5] + t_im;
-        rot(pre[6], pim[6], k, t_re, t_im); a4r = pre[7] - t_re; a4i = pim[7] - t_im;
-        rot(a1r, a1i, sq, t_re, t_im); const int bxr0 = a2r + t_re, bxi0 = a2i + t_im;
-        rot(a3r, a3i, sq, t_re, t_im); const int byr0 = a4r + t_re, byi0 = a4i + t_im;
-        const int bxr = bxr0 >> 2, bxi = bxi0 >> 2, byr = byr0 >> 2, byi = byi0 >> 2;
-        CckLane o;
-        o.lre = (int)((uint32_t)(bxr * byr) + (uint32_t)(bxi * byi));
-        o.lim = (int)((uint32_t)(bxr * byi) - (uint32_t)(bxi * byr));
-        o.l5  = (int)((uint32_t)(bxr * byr) - (uint32_t)(((-bxi0) >> 2) * byi));     // 5.5 Mbps: B[0].im is negated BEFORE the shift (cck.hpp:94-98)
-        return o;
+        for (int i = 0; i < 8; i++) P[i] = unpack((uint32_t)lane_of((int)w, first + i));
+        return b11_cck_corr(P, (4 - (lane >> 2)) & 3, lane & 3);
     };
-    // demap_dqpsk_bits (core/inc/soradsp.h:190-198): halves first
-    auto cck_dqpsk = [&](int pos, int xre, int xim) __attribute__((always_inline)) {
-        const int re = (int)((uint32_t)(last_re * xre) + (uint32_t)(last_im * xim)) >> 1, im = (int)((uint32_t)(last_re * xim) - (uint32_t)(last_im * xre)) >> 1;
-        return ((((uint32_t)re + (uint32_t)im) >> 31) << pos) | ((((uint32_t)re - (uint32_t)im) >> 31) << (pos + 1));
+    // the code word's last chip: its DQPSK pair against the chip before the word (demap_dqpsk_bits: halves first), then the next word's reference
+    auto cck_dqpsk = [&](uint32_t w, int at) __attribute__((always_inline)) {
+        const cpx x = unpack((uint32_t)lane_of((int)w, at));
+        const uint32_t bits = b11_dqpsk_bits<1>(mk(last_re, last_im), x);
+        last_re = x.re; last_im = x.im;
+        return bits;
     };
     auto cck11_decode = [&](uint32_t w) __attribute__((always_inline)) {                               // CCK11_DECODER (cck.hpp:255-763)
-        const CckLane c = cck_correlate(w, 0);
-        const int a1 = c.lre < 0 ? -c.lre : c.lre, a2 = c.lim < 0 ? -c.lim : c.lim;                   // (wrapping negation, as the reference's)
-        const int sq = lane & 3;
-        const uint32_t base = sq == 0 ? 0x00u : sq == 1 ? 0x30u : sq == 2 ? 0x10u : 0x20u;
         int M; uint32_t V;
-        if (a1 > a2) { M = c.lre > 0 ? c.lre : -c.lre; V = base | (c.lre > 0 ? 0x00u : 0x40u); }
-        else         { M = c.lim > 0 ? c.lim : -c.lim; V = base | (c.lim > 0 ? 0xC0u : 0x80u); }
+        b11_cck11_leaf(cck_correlate(w, 0), lane & 3, M, V);
         {   // "if (Max1 > Max2) 1 else 2", "if (Max3 > Max4) 3 else 4": the even lane keeps its own only when strictly larger
             const int oM = dpp<0xB1>(M); const uint32_t oV = (uint32_t)dpp<0xB1>((int)V);
             const bool other = (lane & 1) ? (oM > M) : !(M > oM);
@@ -277,10 +230,8 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
                 8) | 0x04u, v4 = (uint32_t)lane_of((int)V, 12) | 0x0Cu;
         // "lable4" tests 3pi/2 against module 1, else pi against module 2
         uint32_t out = m1 > m2 ? (m1 > m4 ? v1 : v4) : (m2 > m3 ? v2 : v3);
-        const int p7 = lane_of((int)w, 7); const int xre = (int)(short)p7, xim = p7 >> 16;
-        out |= cck_dqpsk(0, xre, xim);
+        out |= cck_dqpsk(w, 7);
         out ^= (cck_even << 1) | cck_even; cck_even ^= 1u;
-        last_re = xre; last_im = xim;
         return out & 0xFFu;
     };
     // TCCK5P5Decoder: even + odd half byte (cck.hpp:26-46, 70-206)
@@ -288,14 +239,8 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
         uint32_t out = 0;
 #pragma unroll
         for (int half = 0; half < 2; half++) {
-            const CckLane c = cck_correlate(w, 8 * half);
-            const int l1 = lane_of(c.l5, 4), l2 = lane_of(c.l5, 12);                                  // phi2 = pi/2 and 3pi/2, phi3 = 0
-            const int max1 = l1 > 0 ? l1 : -l1, max2 = l2 > 0 ? l2 : -l2;
-            const uint32_t nib = max1 > max2 ? (l1 > 0 ? 0x0u : 0x8u) : (l2 > 0 ? 0x4u : 0xCu);
-            out |= nib << (4 * half);
-            const int p7 = lane_of((int)w, 8 * half + 7); const int xre = (int)(short)p7, xim = p7 >> 16;
-            out |= cck_dqpsk(4 * half, xre, xim);
-            last_re = xre; last_im = xim;
+            const B11Corr c = cck_correlate(w, 8 * half);
+            out |= (b11_cck5_pick(lane_of(c.l5, 4), lane_of(c.l5, 12)) | cck_dqpsk(w, 8 * half + 7)) << (4 * half);       // phi2 = pi/2 and 3pi/2, phi3 = 0
         }
         return (out ^ 0x30u) & 0xFFu;
     };
@@ -305,7 +250,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
         const uint32_t moved = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * ((lane - cck_n + k0) & 63), (int)chips);
         if (lane >= cck_n && lane < cck_n + n) cbuf = moved;
         cck_n += n;
-        const int need = uni(rxrate) == RATE_5P5M ? 16 : 8;
+        const int need = uni(rxrate) == k11bRate5p5M ? 16 : 8;
         if (cck_n >= need) {
             const uint32_t b = need == 8 ? cck11_decode(cbuf) : cck5p5_decode(cbuf);
             cbuf = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * ((lane + need) & 63), (int)cbuf);
@@ -316,8 +261,8 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
     };
     // ---- one despread symbol into the brick the rate selector's port leads to
     auto symbol_out = [&](int port, int sre, int sim) __attribute__((always_inline)) {
-        if (port == RATE_SYNC) {                                        // TSFDSync (sfd_sync.hpp:76-126)
-            const uint32_t bit = dot_sign(last_re, last_im, sre, sim);
+        if (port == k11bRateSync) {                                        // TSFDSync (sfd_sync.hpp:76-126)
+            const uint32_t bit = b11_dot_sign(mk(last_re, last_im), mk(sre, sim));
             last_re = sre; last_im = sim;
             byte_reg &= 0x7F;
             const uint32_t sbit = (bit ^ byte_reg ^ (byte_reg >> 3)) & 1;
@@ -328,73 +273,49 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
                 const bool ones = word == 0xFFFF, zeros = word == 0 && sync_cnt >= 16, sfd = word == 0xF3A0, sfds = word == 0x05CF;   // DOT11B_PLCP_SHORT_PREAMBLE_SFD
                 const bool f1 = bit_one_found != 0, f0 = bit_zero_found != 0, none = !f1 && !f0;
                 bit_one_found |= none && ones ? 1 : 0; bit_zero_found |= none && zeros ? 1 : 0;          // (selects again)
-                rxrate = f1 && sfd ? RATE_1M : (f0 && sfds ? RATE_2M : rxrate);                            // short: the header is DQPSK, plcp_data still 0
+                rxrate = f1 && sfd ? k11bRate1M : (f0 && sfds ? k11bRate2M : rxrate);                            // short: the header is DQPSK, plcp_data still 0
                 if ((f1 && !sfd && !ones) || (f0 && !sfds && !zeros)) { if (bit_err_cnt++ > 32) { error_code = E_SFD_FAIL; return; } }
                 if (sync_cnt > 128 + 16) error_code = E_SFD_TIMEOUT;
                 return;
             }
             const bool ones = word == 0xFFFF, sfd = word == 0xF3A0, found = bit_one_found != 0;     // DOT11B_PLCP_LONG_PREAMBLE_SFD
             bit_one_found |= ones ? 1 : 0;                              // (selects, not "store 1 to one of two variables": that becomes a pointer
-            rxrate = found && sfd ? RATE_1M : rxrate;                   //  select and pins both to memory)
+            rxrate = found && sfd ? k11bRate1M : rxrate;                   //  select and pins both to memory)
             if (found && !sfd && !ones) { if (bit_err_cnt++ > 32) { error_code = E_SFD_FAIL; return; } }
             if (sync_cnt > 128 + 16) error_code = E_SFD_TIMEOUT;
-        } else if (port == RATE_1M) {                                   // TDBPSKDemap (barkerspread.hpp:312-390): 8 symbols -> 1 byte
+        } else if (port == k11bRate1M) {                                   // TDBPSKDemap (barkerspread.hpp:312-390): 8 symbols -> 1 byte
             if (sym_n == 0) { ref_re = last_re; ref_im = last_im; }
-            sym_byte |= dot_sign(ref_re, ref_im, sre, sim) << sym_n;
+            sym_byte |= b11_dot_sign(mk(ref_re, ref_im), mk(sre, sim)) << sym_n;
             ref_re = sre; ref_im = sim;
             if (++sym_n == 8) { last_re = sre; last_im = sim; const uint32_t b = sym_byte; sym_n = 0; sym_byte = 0; byte_out(b); }
         } else {                                                        // TDQPSKDemap (barkerspread.hpp:396-454): 4 symbols -> 1 byte
             if (sym_n == 0) { ref_re = last_re; ref_im = last_im; }
-            const int re = (int)((uint32_t)(ref_re * sre) + (uint32_t)(ref_im * sim));
-            const int im = (int)((uint32_t)(ref_re * sim) - (uint32_t)(ref_im * sre));
-            sym_byte |= (((uint32_t)re + (uint32_t)im) >> 31) << (2 * sym_n);
-            sym_byte |= (((uint32_t)re - (uint32_t)im) >> 31) << (2 * sym_n + 1);
+            sym_byte |= b11_dqpsk_bits<0>(mk(ref_re, ref_im), mk(sre, sim)) << (2 * sym_n);
             ref_re = sre; ref_im = sim;
             if (++sym_n == 4) { last_re = sre; last_im = sim; const uint32_t b = sym_byte; sym_n = 0; sym_byte = 0; byte_out(b); }
         }
     };
     // ---- TBarkerSync (symtiming.hpp:229-313) -> TBB11bRxRateSel -> TBB11bDespread::QuickBarkerDespread (barkerspread.hpp:277-303)
     auto chip_in = [&](int cre, int cim) __attribute__((always_inline)) {
-        if (sync_flag == BARKER_SYNCED) {
+        if (sync_flag == k11bBarkerSynced) {
             const int port = uni(rxrate);                               // (a CCK rate never gets here: its blocks take the lane-parallel path of sym_timing)
-            int tre, tim;
-            if (chip_n == 1 || chip_n == 4) { tre = neg16(cre) >> 4; tim = neg16(cim) >> 4; }          // negated before the shift
-            else { tre = cre >> 4; tim = cim >> 4; if (chip_n >= 8) { tre = -tre; tim = -tim; } }       // chips 8..10 subtracted after it
-            acc_re = w16(acc_re + tre); acc_im = w16(acc_im + tim);
+            const cpx t = b11_barker_term(mk(cre, cim), chip_n);
+            acc_re = w16(acc_re + t.re); acc_im = w16(acc_im + t.im);
             if (++chip_n == 11) { const int sre = acc_re, sim = acc_im; chip_n = 0; acc_re = acc_im = 0; symbol_out(port, sre, sim); }
             return;
         }
         search_count++;
         if (search_count >= 11 * 4) { error_code = E_SYNC_TIMEOUT; return; }
-        const int sr = cre >> 4, si = cim >> 4;
         // (values read back from LDS are wave-uniform; saying so keeps everything derived from them -- the whole state machine -- scalar)
-        const int o_re = w16(uni(p_re[0]) - sr), o_im = w16(uni(p_im[0]) - si);
-#define P_SUB(d, s) p_re[d] = w16(uni(p_re[s]) - sr); p_im[d] = w16(uni(p_im[s]) - si);
-#define P_ADD(d, s) p_re[d] = w16(uni(p_re[s]) + sr); p_im[d] = w16(uni(p_im[s]) + si);
-        P_SUB(0, 1) P_SUB(1, 2) P_ADD(2, 3) P_ADD(3, 4) P_ADD(4, 5) P_SUB(5, 6) P_ADD(6, 7) P_ADD(7, 8) P_SUB(8, 9)
-#undef P_SUB
-#undef P_ADD
-        p_re[9] = sr; p_im[9] = si;
-        const int corr = (int)((uint32_t)(o_re * o_re) + (uint32_t)(o_im * o_im));
-        switch (sync_flag) {
-        case NO_PEAK_FOUND:
-            if (corr > m_max) { m_max = corr; last_peak_cnt = 1; } else if (++last_peak_cnt == 11) sync_flag = PEAK_FOUND;
-            break;
-        case PEAK_FOUND:
-            m_max = corr / 2; last_peak_cnt = 1; sync_flag = PEAK_VALID;
-            break;
-        case PEAK_VALID:
-            if (corr > m_max) { m_max = corr; last_peak_cnt = 0; sync_flag = NO_PEAK_FOUND; } else if (++last_peak_cnt == 11) sync_flag = PEAK_VALIDED;
-            break;
-        default:
-            sync_flag = BARKER_SYNCED;
-        }
+        const cpx o = b11_barker_shift(mk(cre >> 4, cim >> 4), [&](int k) __attribute__((always_inline)) { return mk(uni(p_re[k]), uni(p_im[k])); },
+                                       [&](int k, cpx v) __attribute__((always_inline)) { p_re[k] = v.re; p_im[k] = v.im; });
+        b11_barker_peak(sqnorm(o), sync_flag, last_peak_cnt, m_max);
     };
     // ---- TSymTiming::Process on one 28-sample block held one sample per lane (symtiming.hpp:42-170)
     auto sym_timing = [&](uint32_t braw) __attribute__((always_inline)) {
         const cpx bu = unpack(braw);
         const int bre = w16(bu.re - dc_re), bim = w16(bu.im - dc_im);      // TDCRemove (dc.hpp:6-38): the estimate is frozen while demodulating
-        if (sync_flag == BARKER_SYNCED) {
+        if (sync_flag == k11bBarkerSynced) {
             // Decimation + rate selector + despreader for the whole block at once: chip k of the block in lane k.  A block
             // yields 6..8 chips and a symbol takes 11, so at most one symbol ends inside it; every operation of the
             // despreader is a wrapping add, so the two partial sums (before / after that boundary) are lane reductions.
@@ -404,21 +325,19 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             const cpx cu = unpack((uint32_t)__shfl((int)braw, at));
             const int cre = w16(cu.re - dc_re), cim = w16(cu.im - dc_im);
             if (mi < 0) m_index += 4;
-            if (uni(rxrate) > RATE_2M) cck_push(pack(mk(cre, cim)), 0, cnt);     // (uni: see the note at rxrate's declaration)
+            if (uni(rxrate) > k11bRate2M) cck_push(pack(mk(cre, cim)), 0, cnt);     // (uni: see the note at rxrate's declaration)
             else {
             int c = chip_n + lane; const bool first = c < 11; if (!first) c -= 11;
-            int tre, tim;
-            if (c == 1 || c == 4) { tre = neg16(cre) >> 4; tim = neg16(cim) >> 4; }
-            else { tre = cre >> 4; tim = cim >> 4; if (c >= 8) { tre = -tre; tim = -tim; } }
+            const cpx t = b11_barker_term(mk(cre, cim), c);
             const bool valid = lane < cnt;
-            int a_re = valid && first ? tre : 0, a_im = valid && first ? tim : 0, b_re = valid && !first ? tre : 0, b_im = valid && !first ? tim : 0;
+            int a_re = valid && first ? t.re : 0, a_im = valid && first ? t.im : 0, b_re = valid && !first ? t.re : 0, b_im = valid && !first ? t.im : 0;
             a_re = uni(sum8(a_re)); a_im = uni(sum8(a_im)); b_re = uni(sum8(b_re)); b_im = uni(sum8(b_im));
             if (chip_n + cnt >= 11) {
                 const int port = uni(rxrate), sre = w16(acc_re + a_re), sim = w16(acc_im + a_im);
                 acc_re = w16(b_re); acc_im = w16(b_im); chip_n = chip_n + cnt - 11;
                 symbol_out(port, sre, sim);
                 // the header has just announced a CCK rate: the chips after the symbol boundary are the first of the payload
-                if (uni(rxrate) > RATE_2M) {
+                if (uni(rxrate) > k11bRate2M) {
                     const int k0 = cnt - chip_n, n = chip_n;
                     chip_n = 0; acc_re = acc_im = 0;
                     cck_push(pack(mk(cre, cim)), k0, n);
@@ -447,13 +366,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
         const int sl = mi == 0 ? s1 : mi == 1 ? s2 : mi == 2 ? s3 : s0;
         // (branch-free, as selects: "m_index++ else m_frag++" would become a pointer select that pins both to memory, and the scalar
         //  unit is what this kernel runs out of -- every avoided branch counts)
-        const bool late_better = se < sl, a = sm < se, b = sm < sl;
-        const bool jump = late_better ? a : b;
-        const int di = late_better ? (a ? 1 : 0) : (b ? -1 : 0);
-        const int df = late_better ? (!a && b ? 1 : 0) : (!b && a ? -1 : 0);
-        int mf = jump ? 0 : m_frag + df;
-        const int carry = mf >= 4 ? 1 : (mf <= -4 ? -1 : 0);
-        m_index += di + carry; m_frag = carry > 0 ? -3 : (carry < 0 ? 3 : mf);
+        b11_timing_carry(b11_adjust_timing(sm, se, sl), m_index, m_frag);
     };
 
 
@@ -481,11 +394,11 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             int qoff_) __attribute__((always_inline)) -> bool {
         const int port = uni(rxrate);
         // 0: TSFDSync, 1: the PLCP header's bytes, 2: a Barker payload's, 3: a CCK payload's
-        const int mode = port == RATE_SYNC ? 0 : (!uni(plcp_data) ? 1 : port <= RATE_2M ? 2 : 3);
-        if (mode == 1 && port != RATE_1M && !PRE) return false;        // (PRE: a short preamble's header, six bytes of DQPSK)
+        const int mode = port == k11bRateSync ? 0 : (!uni(plcp_data) ? 1 : port <= k11bRate2M ? 2 : 3);
+        if (mode == 1 && port != k11bRate1M && !PRE) return false;        // (PRE: a short preamble's header, six bytes of DQPSK)
         if (mode == 3 && !CCK) return false;
-        const int spb = port == RATE_2M ? 4 : 8;                        // symbols per byte
-        const int need = port == RATE_5P5M ? 16 : 8;                    // CCK: chips per byte
+        const int spb = port == k11bRate2M ? 4 : 8;                        // symbols per byte
+        const int need = port == k11bRate5p5M ? 16 : 8;                    // CCK: chips per byte
         int K = min(mode == 3 ? 62 : 64, (int)(remain_ / 28u));         // (62 calls: at most 63 code words with the queued chips)
         if (mode == 3) {
             if (byte_count + 1 >= frame_length) return false;
@@ -495,7 +408,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             if (mode == 2 && byte_count + 1 >= frame_length) return false;
             const int R = mode == 2 ? (int)(frame_length - 1 - byte_count) : 6 - hdr_n;     // bytes up to and including the one that raises the event
             const int chips_to_event = 11 * (R * spb - sym_n) - chip_n;
-            K = min(port == RATE_2M ? 32 : K, min(K, (chips_to_event - 1) / 8 - 1));        // (2 Mbps: 32 calls fill the 64-bit bit string)
+            K = min(port == k11bRate2M ? 32 : K, min(K, (chips_to_event - 1) / 8 - 1));        // (2 Mbps: 32 calls fill the 64-bit bit string)
         }
         if (K < 6) return false;
         const int m_index0 = m_index, m_frag0 = m_frag;
@@ -527,10 +440,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             const int sm = mx == 0 ? e0 : mx == 1 ? e1 : mx == 2 ? e2 : e3;
             const int se = mx == 0 ? e3 : mx == 1 ? e0 : mx == 2 ? e1 : e2;
             const int sl = mx == 0 ? e1 : mx == 1 ? e2 : mx == 2 ? e3 : e0;
-            const bool late_better = se < sl, a = sm < se, b = sm < sl;
-            const int di = late_better ? (a ? 1 : 0) : (b ? -1 : 0);
-            const int df = late_better ? (!a && b ? 1 : 0) : (!b && a ? -1 : 0);
-            codes |= (uint32_t)((di + 1) | ((df + 1) << 2)) << (4 * mx);
+            codes |= b11_timing_code(b11_adjust_timing(sm, se, sl)) << (4 * mx);
         }
         // State: mx = m_index & 3 (what Decimation leaves: -1 -> 3 after its "idx < 0" step, 4 -> 0), M = m_frag + 3.  As long as the index
         // stays where it is every call just moves the fraction by its df, so a whole run of calls is settled by a prefix sum over the lanes:
@@ -627,77 +537,32 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             lds_order();
             const int T = cck_n + total, nw = T >> 3;                   // chips in the buffer, complete words
             const bool inw = lane < nw;
-            int pre[8], pim[8];
+            cpx P[8];
             {
                 const uint4 c0 = *reinterpret_cast<const uint4*>(chipbuf + 8 * (inw ? lane : 0)), c1 = *reinterpret_cast<const uint4*>(chipbuf + 8 * (inw ? lane : 0) + 4);
                 const uint32_t cw[8] = { c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w };
 #pragma unroll
-                for (int i = 0; i < 8; i++) { pre[i] = (int)(short)(cw[i] & 0xFFFFu); pim[i] = (int)cw[i] >> 16; }
+                for (int i = 0; i < 8; i++) P[i] = unpack(cw[i]);
             }
-            auto rotc = [](int re, int im, int kk, int& ore, int& oim) __attribute__((always_inline)) {  // (re + j im) * j^kk, kk a constant
-                const int xr = (kk & 1) ? im : re, xi = (kk & 1) ? re : im;
-                ore = ((kk + 1) & 2) ? -xr : xr; oim = (kk & 2) ? -xi : xi;
-            };
-            // A1..A4 of hypothesis phi2 = m pi/2 (r = (-j)^m = j^k, k = (4 - m) & 3), then Bx, By and L of hypothesis phi3 = s-th of 0, pi/2, pi, 3pi/2
-            auto corr = [&](int m, int sq, int& lre, int& lim, int& l5) __attribute__((always_inline)) {
-                const int k = (4 - m) & 3;
-                int t_re, t_im;
-                rotc(pre[0], pim[0], k, t_re, t_im); const int a1r = pre[1] + t_re, a1i = pim[1] + t_im;
-                rotc(pre[2], pim[2], k, t_re, t_im); const int a2r = t_re - pre[3], a2i = t_im - pim[3];
-                rotc(pre[4], pim[4], k, t_re, t_im); const int a3r = pre[5] + t_re, a3i = pim[5] + t_im;
-                rotc(pre[6], pim[6], k, t_re, t_im); const int a4r = pre[7] - t_re, a4i = pim[7] - t_im;
-                rotc(a1r, a1i, sq, t_re, t_im); const int bxr0 = a2r + t_re, bxi0 = a2i + t_im;
-                rotc(a3r, a3i, sq, t_re, t_im); const int byr0 = a4r + t_re, byi0 = a4i + t_im;
-                const int bxr = bxr0 >> 2, bxi = bxi0 >> 2, byr = byr0 >> 2, byi = byi0 >> 2;
-                lre = (int)((uint32_t)(bxr * byr) + (uint32_t)(bxi * byi));
-                lim = (int)((uint32_t)(bxr * byi) - (uint32_t)(bxi * byr));
-                l5  = (int)((uint32_t)(bxr * byr) - (uint32_t)(((-bxi0) >> 2) * byi));
-            };
-            const uint32_t p7 = (uint32_t)(pre[7] & 0xFFFF) | ((uint32_t)pim[7] << 16);
-            // wave_shr:1: the previous word's last chip
-            const uint32_t p7prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)p7, 0x138, 0xF, 0xF, false);
-            const int qre = lane == 0 ? last_re : (int)(short)(p7prev & 0xFFFFu), qim = lane == 0 ? last_im : (int)p7prev >> 16;
-            const int dre = (int)((uint32_t)(qre * pre[7]) + (uint32_t)(qim * pim[7])) >> 1, dim = (int)((uint32_t)(qre * pim[7]) - (uint32_t)(qim * pre[7])) >> 1;
-            // demap_dqpsk_bits (soradsp.h:190-198)
-            const uint32_t dq = (((uint32_t)dre + (uint32_t)dim) >> 31) | ((((uint32_t)dre - (uint32_t)dim) >> 31) << 1);
+            // the DQPSK pair of the word's last chip against the previous word's (wave_shr:1; the first word: the chip before the pass)
+            const uint32_t p7prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pack(P[7]), 0x138, 0xF, 0xF, false);
+            const uint32_t dq = b11_dqpsk_bits<1>(lane == 0 ? mk(last_re, last_im) : unpack(p7prev), P[7]);
             uint32_t raw; int nbytes;                                   // lane i: the i-th byte in front of the descrambler
-            if (port == RATE_11M) {
-                int Mm[4]; uint32_t Vm[4];
-#pragma unroll
-                for (int m = 0; m < 4; m++) {
-                    int Ms[4]; uint32_t Vs[4];
-#pragma unroll
-                    for (int sq = 0; sq < 4; sq++) {
-                        int lre, lim, l5; corr(m, sq, lre, lim, l5);
-                        const int a1 = lre < 0 ? -lre : lre, a2 = lim < 0 ? -lim : lim;
-                        const uint32_t base = sq == 0 ? 0x00u : sq == 1 ? 0x30u : sq == 2 ? 0x10u : 0x20u;
-                        const bool first = a1 > a2;
-                        Ms[sq] = first ? (lre > 0 ? lre : -lre) : (lim > 0 ? lim : -lim);
-                        Vs[sq] = base | (first ? (lre > 0 ? 0x00u : 0x40u) : (lim > 0 ? 0xC0u : 0x80u));
-                    }
-                    // "if (Max1 > Max2) 1 else 2", "if (Max3 > Max4) 3 else 4"
-                    const bool k01 = Ms[0] > Ms[1], k23 = Ms[2] > Ms[3];
-                    const int M01 = k01 ? Ms[0] : Ms[1], M23 = k23 ? Ms[2] : Ms[3];
-                    const uint32_t V01 = k01 ? Vs[0] : Vs[1], V23 = k23 ? Vs[2] : Vs[3];
-                    const bool up = M23 > M01;                                                          // "if (Max34 > Module) Module = Max34"
-                    Mm[m] = up ? M23 : M01; Vm[m] = (up ? V23 : V01) | (m == 0 ? 0x00u : m == 1 ? 0x08u : m == 2 ? 0x04u : 0x0Cu);
-                }
-                uint32_t out = Mm[0] > Mm[1] ? (Mm[0] > Mm[3] ? Vm[0] : Vm[3]) : (Mm[1] > Mm[2] ? Vm[1] : Vm[2]);   // "lable4"
+            if (port == k11bRate11M) {
+                int m1, m2, m3, m4; uint32_t v1, v2, v3, v4;           // all four modules, then "lable4": what the pruned search of b11_cck11_bits computes
+                b11_cck11_module(P, 0, m1, v1); b11_cck11_module(P, 3, m2, v2); b11_cck11_module(P, 2, m3, v3); b11_cck11_module(P, 1, m4, v4);
+                uint32_t out = m1 > m2 ? (m1 > m4 ? v1 : v4 | 0x0Cu) : (m2 > m3 ? v2 | 0x08u : v3 | 0x04u);
                 out |= dq;
                 out ^= ((cck_even ^ (uint32_t)lane) & 1u) ? 3u : 0u;   // the extra pi of every other symbol
                 raw = out & 0xFFu; nbytes = nw;
             } else {
-                int lre, lim, l1, l2;
-                corr(1, 0, lre, lim, l1); corr(3, 0, lre, lim, l2);     // phi2 = pi/2 and 3pi/2, phi3 = 0
-                const int max1 = l1 > 0 ? l1 : -l1, max2 = l2 > 0 ? l2 : -l2;
-                const uint32_t half = (max1 > max2 ? (l1 > 0 ? 0x0u : 0x8u) : (l2 > 0 ? 0x4u : 0xCu)) | dq;
+                const uint32_t half = b11_cck5_nibble(P) | dq;
                 const uint32_t h0 = (uint32_t)__shfl((int)half, 2 * lane), h1 = (uint32_t)__shfl((int)half, 2 * lane + 1);
                 raw = ((h0 | (h1 << 4)) ^ 0x30u) & 0xFFu; nbytes = nw >> 1;
             }
             // TDesc741 a byte per lane: the seven bits in front of it are the top of the byte to the left (byte_reg for the first)
             const uint32_t rprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)raw, 0x138, 0xF, 0xF, false);
-            const uint32_t S15 = (raw << 7) | (lane == 0 ? (byte_reg & 0x7Fu) : (rprev >> 1));
-            const uint32_t ob = ((S15 >> 7) ^ (S15 >> 3) ^ S15) & 0xFFu;
+            const uint32_t ob = b11_desc741(lane == 0 ? byte_reg : rprev >> 1, raw);
             if (nbytes > 0) {
                 byte_reg = (uint32_t)lane_of((int)raw, nbytes - 1) >> 1;
                 const uint32_t idx = byte_count + (uint32_t)lane;
@@ -717,8 +582,8 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
                 }
                 byte_count += (uint32_t)nbytes;
                 const int lw = nbytes * (need >> 3) - 1;                // the last word decoded
-                last_re = lane_of(pre[7], lw); last_im = lane_of(pim[7], lw);
-                if (port == RATE_11M) cck_even ^= (uint32_t)nbytes & 1u;
+                last_re = lane_of(P[7].re, lw); last_im = lane_of(P[7].im, lw);
+                if (port == k11bRate11M) cck_even ^= (uint32_t)nbytes & 1u;
             }
             const int used = nbytes * need;
             lds_order();
@@ -755,7 +620,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             // compared with all-ones and with the SFD; "ones seen before" and the error count are prefix counts over lane masks
             if (lane == 0) { qre = last_re; qim = last_im; }
             const bool in = lane < nsym;
-            const unsigned long long bits = __ballot(in && dot_sign(qre, qim, sre, sim));
+            const unsigned long long bits = __ballot(in && b11_dot_sign(mk(qre, qim), mk(sre, sim)));
             const unsigned long long S = (bits << 7) | (unsigned long long)(byte_reg & 0x7Fu);
             const unsigned long long O = (S >> 7) ^ (S >> 3) ^ S;
             const unsigned long long Bw = (unsigned long long)(word & 0xFFFFu) | (O << 16);      // word after symbol n = bits n + 1 .. n + 16
@@ -809,13 +674,12 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             const int cin_re = sym_n == 0 ? last_re : ref_re, cin_im = sym_n == 0 ? last_im : ref_im;
             if (lane == 0) { qre = cin_re; qim = cin_im; }
             unsigned long long W; int nbits;
-            if (port == RATE_1M) {
-                const unsigned long long b0 = __ballot(lane < nsym && dot_sign(qre, qim, sre, sim));
+            if (port == k11bRate1M) {
+                const unsigned long long b0 = __ballot(lane < nsym && b11_dot_sign(mk(qre, qim), mk(sre, sim)));
                 W = (unsigned long long)sym_byte | (b0 << sym_n); nbits = sym_n + nsym;
             } else {
-                const int re = (int)((uint32_t)(qre * sre) + (uint32_t)(qim * sim)), im = (int)((uint32_t)(qre * sim) - (uint32_t)(qim * sre));
-                unsigned long long b0 = __ballot(lane < nsym && ((((uint32_t)re + (uint32_t)im) >> 31) != 0));
-                unsigned long long b1 = __ballot(lane < nsym && ((((uint32_t)re - (uint32_t)im) >> 31) != 0));
+                const uint32_t dq = b11_dqpsk_bits<0>(mk(qre, qim), mk(sre, sim));
+                const unsigned long long b0 = __ballot(lane < nsym && (dq & 1u) != 0), b1 = __ballot(lane < nsym && (dq & 2u) != 0);
                 auto spread = [](unsigned long long v) { v &= 0xFFFFFFFFull; v = (v | (v << 16)) & 0x0000FFFF0000FFFFull; v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
                                                          v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full; v = (v | (v << 2)) & 0x3333333333333333ull;
                                                              v = (v | (v << 1)) & 0x5555555555555555ull; return v; };
@@ -823,8 +687,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             }
             const int nbytes = nbits >> 3;
             // TDesc741 is self-synchronising -- out[n] = in[n] ^ in[n-4] ^ in[n-7] -- so the whole bit string is descrambled with two shifts
-            const unsigned long long S = (W << 7) | (unsigned long long)(byte_reg & 0x7Fu);
-            const unsigned long long O = (S >> 7) ^ (S >> 3) ^ S;
+            const unsigned long long O = b11_desc741_bits(byte_reg, W);
             if (nbytes > 0) {
                 byte_reg = (uint32_t)(W >> (8 * nbytes - 7)) & 0x7Fu;
                 // TBB11bPlcpSwitch -> TBB11bPlcpParser's burst (at most five bytes: the sixth is the event)
@@ -978,8 +841,8 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
                 // Steady state (aligned to the Barker code, no event pending, whole calls that follow one another): further source
                 // calls are taken right here.  Same semantics as going round the outer loop -- MAC11b_Receive only looks at
                 // error_code after a call -- but in a loop of its own the compiler keeps just this phase's state in registers.
-                while (error_code == 0 && sync_flag == BARKER_SYNCED && remain >= 28 && c_take == 28 && c_start + 28 == pos) {
-                    if ((uni(rxrate) <= RATE_2M || (CCK && uni(plcp_data))) && bulk_pass(pos, remain, c_start, c_stale, p_start, p_stale, qoff)) { p_take = 28;
+                while (error_code == 0 && sync_flag == k11bBarkerSynced && remain >= 28 && c_take == 28 && c_start + 28 == pos) {
+                    if ((uni(rxrate) <= k11bRate2M || (CCK && uni(plcp_data))) && bulk_pass(pos, remain, c_start, c_stale, p_start, p_stale, qoff)) { p_take = 28;
                         pf_ok = false; continue; }
                     p_start = c_start; p_take = 28; p_stale = c_stale;
                     c_stale = c_start; c_start = pos; pos += 28; remain -= 28;
@@ -995,7 +858,7 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
             if (err != E_CS_TIMEOUT) {
                 if (lane == 0 && nfr < A.max_frames) {
                     Rx11bRow row; row.end_sample = pos; row.error_code = err; row.rate_kbps = rate_kbps; row.length = frame_length; row.crc32 = frame_crc32;
-                    if constexpr (PRE) row.rate_kbps |= bit_zero_found && uni(rxrate) != RATE_SYNC ? kRowShortBit : 0u;     // between a short SFD and the reset
+                    if constexpr (PRE) row.rate_kbps |= bit_zero_found && uni(rxrate) != k11bRateSync ? kRowShortBit : 0u;     // between a short SFD and the reset
                     A.rows[(size_t)cap_i * A.max_frames + nfr] = row;
                 }
                 if ((err == E_FRAME_OK || err == E_CRC32_FAIL) && nfr < A.max_frames) {
@@ -1020,11 +883,11 @@ __device__ __forceinline__ void rx11b_capture(const Rx11bArgs& A)
                     const uint32_t padded = lane < qoff ? pack(mk(q.re, q.im)) : pack(mk(dc_re, dc_im));
                     sym_timing(padded); qoff = 0;
                 }
-                if (uni(rxrate) <= RATE_2M && chip_n > 0) { const int sre = acc_re, sim = acc_im; chip_n = 0; acc_re = acc_im = 0; symbol_out(uni(rxrate), sre, sim); }
+                if (uni(rxrate) <= k11bRate2M && chip_n > 0) { const int sre = acc_re, sim = acc_im; chip_n = 0; acc_re = acc_im = 0; symbol_out(uni(rxrate), sre, sim); }
                 if constexpr (CCK) {
-                if (uni(rxrate) > RATE_2M && cck_n > 0) {               // opin3/4().pad(): zero chips complete the burst, one more byte comes out
+                if (uni(rxrate) > k11bRate2M && cck_n > 0) {               // opin3/4().pad(): zero chips complete the burst, one more byte comes out
                     const uint32_t w = lane < cck_n ? cbuf : 0u; cck_n = 0;
-                    byte_out(uni(rxrate) == RATE_5P5M ? cck5p5_decode(w) : cck11_decode(w));
+                    byte_out(uni(rxrate) == k11bRate5p5M ? cck5p5_decode(w) : cck11_decode(w));
                 }
                 }
             }
@@ -1240,7 +1103,7 @@ int sora_rx11b_results(sora_rx11b_t* rx, sora_frame_result* out, size_t max_out,
 // Tickets (as sora_rx_ticket / _wait / _results_of): every process call is addressable until kSlots11b further calls have reused its slot.
 int sora_rx11b_ticket(sora_rx11b_t* rx) { return rx && rx->have_results ? rx->slot[rx->last].ticket : 0; }
 int sora_rx11b_calls_in_flight(sora_rx11b_t* rx) { (void)rx; return kSlots11b; }
-// Two passes (default): k_rx11b (90 VGPRs, the Barker rates) decodes every capture and hands the ones whose PLCP header announces 5.5 / 11 Mbps
+// Two passes (default): k_rx11b (89 VGPRs, the Barker rates) decodes every capture and hands the ones whose PLCP header announces 5.5 / 11 Mbps
 // to k_rx11b_cck (128 VGPRs), which redoes them from their first sample.  A host that expects mostly CCK traffic skips the first pass:
 // every capture goes straight through the CCK-capable instantiation (it decodes all four rates; identical rows).  Returns the previous setting.
 int sora_rx11b_set_single_pass(sora_rx11b_t* rx, int enable)
