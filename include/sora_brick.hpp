@@ -477,6 +477,116 @@ struct THipPackSample16to8 : THipStage<sora_complex16, NSAMPLES, sora_complex8, 
 };
 
 // ------------------------------------------------------------------------------------------------
+// The bricks of the 802.11n 2x2 modulation graphs (kernel/bb/demod11/fb11nmod_config.hpp) beyond the 802.11a ones above (T11aSc, TConvEncode_*, the SIG graph's
+// T11aInterleaveBPSK and T11aAddPilot<30339> are THip11aSc, THipConvEncode, THip11aInterleave<1> and THip11aAddPilot with bpsk_mod 30339).  One burst = N symbols;
+// kRow11n = the bricks' N_b bytes per stream and symbol.
+constexpr size_t kRow11n(int n_bpsc) { return (size_t)(52 * n_bpsc + 7) / 8; }
+
+// TStreamParser{BPSK,QPSK,QAM16,QAM64}_12 (streamparser.hpp): IPORT uchar x 13 N_BPSC -> OPORTS 0 and 1 uchar x N_b, a demux: Next0 and Next1 take the two spatial streams
+template <int N_BPSC, size_t N, class T_CTX, class T_NEXT0, class T_NEXT1>
+class THipStreamParser {
+public:
+    using iport_traits = port_traits<uint8_t, 13 * N_BPSC * N>;
+    using oport_traits = port_traits<uint8_t, kRow11n(N_BPSC) * N>;
+    THipStreamParser(T_CTX& ctx, T_NEXT0* next0, T_NEXT1* next1, uint8_t* d_out0, uint8_t* d_out1, void* stream = nullptr)
+        : ctx_(ctx), next0_(next0), next1_(next1), opin0_(d_out0), opin1_(d_out1), stream_(stream) {}
+    void Reset() { if (next0_) next0_->Reset(); if (next1_) next1_->Reset(); }
+    void Flush() { if (next0_) next0_->Flush(); if (next1_) next1_->Flush(); }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            uint8_t* out0 = opin0_.append(); uint8_t* out1 = opin1_.append();
+            const int rc = sora_hip_stream_parse11n(ipin.peek(), out0, out1, N_BPSC, N, stream_);
+            if (rc != SORA_OK) { ctx_.error_code = (uint32_t)rc; return false; }
+            ipin.pop();
+            if (next0_ && !next0_->Process(opin0_)) return false;
+            if (next1_ && !next1_->Process(opin1_)) return false;
+        }
+        return true;
+    }
+    DevicePin<uint8_t, kRow11n(N_BPSC) * N>& opin0() { return opin0_; }
+    DevicePin<uint8_t, kRow11n(N_BPSC) * N>& opin1() { return opin1_; }
+private:
+    T_CTX& ctx_; T_NEXT0* next0_; T_NEXT1* next1_; DevicePin<uint8_t, kRow11n(N_BPSC) * N> opin0_, opin1_; void* stream_;
+};
+
+// T11nInterleave{BPSK,QPSK,QAM16,QAM64}_S1 / _S2 (interleave.hpp:116-123), SPATIAL_STREAM 0 / 1: IPORT uchar x N_b -> OPORT uchar x N_b
+struct CallInterleave11n { int nb, ss; size_t n; int operator()(const uint8_t* in, uint8_t* out, void* st) const
+    { return sora_hip_interleave11n(in, out, nb, ss, n, st); } };
+template <int N_BPSC, int SPATIAL_STREAM, size_t N, class T_CTX, class T_NEXT>
+struct THip11nInterleave : THipStage<uint8_t, kRow11n(N_BPSC) * N, uint8_t, kRow11n(N_BPSC) * N, CallInterleave11n, T_CTX, T_NEXT> {
+    THip11nInterleave(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* stream = nullptr)
+        : THipStage<uint8_t, kRow11n(N_BPSC) * N, uint8_t, kRow11n(N_BPSC) * N, CallInterleave11n, T_CTX, T_NEXT>(ctx, next, d_out,
+              CallInterleave11n{ N_BPSC, SPATIAL_STREAM, N }, stream) {}
+};
+// TMap11a*<MOD> behind them: IPORT uchar x N_b -> OPORT COMPLEX16 x 52; mod = the brick's MOD (0: 30339 / 21453 / 9594 / 4681).  The BPSK brick's pin carries 56 carriers
+// per symbol, of which T11nAddPilot drops the last four: this adapter hands on the 52.
+struct CallMap11n { int nb, mod; size_t n; int operator()(const uint8_t* in, sora_complex16* out, void* st) const { return sora_hip_map11n(in, out, nb, mod, n, st); } };
+template <int N_BPSC, size_t N, class T_CTX, class T_NEXT>
+struct THipMap11n : THipStage<uint8_t, kRow11n(N_BPSC) * N, sora_complex16, 52 * N, CallMap11n, T_CTX, T_NEXT> {
+    THipMap11n(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, int mod = 0, void* stream = nullptr)
+        : THipStage<uint8_t, kRow11n(N_BPSC) * N, sora_complex16, 52 * N, CallMap11n, T_CTX, T_NEXT>(ctx, next, d_out, CallMap11n{ N_BPSC, mod, N }, stream) {}
+};
+// TSigMap11n (mapper11n.hpp): IPORT uchar x 18 -> OPORT COMPLEX16 x 144, N frames per burst
+struct CallSigMap11n { size_t n; int operator()(const uint8_t* in, sora_complex16* out, void* st) const { return sora_hip_sig_map11n(in, out, n, st); } };
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipSigMap11n : THipStage<uint8_t, 18 * N, sora_complex16, 144 * N, CallSigMap11n, T_CTX, T_NEXT> {
+    THipSigMap11n(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* stream = nullptr)
+        : THipStage<uint8_t, 18 * N, sora_complex16, 144 * N, CallSigMap11n, T_CTX, T_NEXT>(ctx, next, d_out, CallSigMap11n{ N }, stream) {}
+};
+
+// T11nAddPilot<ISS> (pilot_11n.hpp:7-82): IPORT COMPLEX16 x 52 -> OPORT COMPLEX16 x 64, N symbols of ONE frame per burst.  pilot_index is the count of symbols since
+// Reset, handed to the stage through d_pos0; d_tab: 16 bytes of device memory for the call's frame table.
+template <int ISS, size_t N, class T_CTX, class T_NEXT>
+class THip11nAddPilot : public HipFilter<T_CTX, T_NEXT> {
+public:
+    using iport_traits = port_traits<sora_complex16, 52 * N>;
+    using oport_traits = port_traits<sora_complex16, 64 * N>;
+    THip11nAddPilot(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* d_tab, void* stream = nullptr)
+        : HipFilter<T_CTX, T_NEXT>(ctx, next, stream), opin_(d_out), d_tab_(static_cast<uint32_t*>(d_tab)) {}
+    void Reset() { pos_ = 0; HipFilter<T_CTX, T_NEXT>::Reset(); }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            sora_complex16* out = opin_.append();
+            const uint32_t tab[4] = { 0u, (uint32_t)N, pos_, 0u };                                 // first, nsym, position of the burst's first symbol in its frame
+            if (sora_hip_memcpy_h2d(d_tab_, tab, sizeof(tab)) != SORA_OK) return this->raise(SORA_ERR_HARDWARE_FAILED);
+            if (!this->raise(sora_hip_add_pilot11n(ipin.peek(), out, d_tab_, d_tab_ + 1, d_tab_ + 2, 1, ISS, this->stream_))) return false;
+            pos_ += (uint32_t)N;
+            ipin.pop();
+            if (this->next_ && !this->next_->Process(opin_)) return false;
+        }
+        return true;
+    }
+    DevicePin<sora_complex16, 64 * N>& opin() { return opin_; }
+private:
+    DevicePin<sora_complex16, 64 * N> opin_; uint32_t* d_tab_; uint32_t pos_ = 0;
+};
+
+// TIFFTxOnly (fft.hpp:63-103): IPORT COMPLEX16 x 64 -> OPORT COMPLEX16 x 128
+struct CallIFFTxOnly { size_t n; int operator()(const sora_complex16* in, sora_complex16* out, void* st) const { return sora_hip_ifft_only11n(in, out, n, st); } };
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipIFFTxOnly : THipStage<sora_complex16, 64 * N, sora_complex16, 128 * N, CallIFFTxOnly, T_CTX, T_NEXT> {
+    THipIFFTxOnly(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* stream = nullptr)
+        : THipStage<sora_complex16, 64 * N, sora_complex16, 128 * N, CallIFFTxOnly, T_CTX, T_NEXT>(ctx, next, d_out, CallIFFTxOnly{ N }, stream) {}
+};
+// TCSD<NCSD> (csd.hpp): IPORT COMPLEX16 x 128 -> OPORT COMPLEX16 x 128 (the output pin's buffer must not be the input pin's)
+struct CallCSD { int ncsd; size_t n; int operator()(const sora_complex16* in, sora_complex16* out, void* st) const { return sora_hip_csd11n(in, out, ncsd, n, st); } };
+template <int NCSD, size_t N, class T_CTX, class T_NEXT>
+struct THipCSD : THipStage<sora_complex16, 128 * N, sora_complex16, 128 * N, CallCSD, T_CTX, T_NEXT> {
+    static_assert(NCSD >= 1 && NCSD <= 31, "a delay of 4 .. 124 samples");
+    THipCSD(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* stream = nullptr)
+        : THipStage<sora_complex16, 128 * N, sora_complex16, 128 * N, CallCSD, T_CTX, T_NEXT>(ctx, next, d_out, CallCSD{ NCSD, N }, stream) {}
+};
+// TAddGI (gi.hpp): IPORT COMPLEX16 x 128 -> OPORT COMPLEX16 x 160
+struct CallAddGI { size_t n; int operator()(const sora_complex16* in, sora_complex16* out, void* st) const { return sora_hip_add_gi11n(in, out, n, st); } };
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipAddGI : THipStage<sora_complex16, 128 * N, sora_complex16, 160 * N, CallAddGI, T_CTX, T_NEXT> {
+    THipAddGI(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* stream = nullptr)
+        : THipStage<sora_complex16, 128 * N, sora_complex16, 160 * N, CallAddGI, T_CTX, T_NEXT>(ctx, next, d_out, CallAddGI{ N }, stream) {}
+};
+
+// ------------------------------------------------------------------------------------------------
 // The fixed-ratio bricks of the 802.11b receive graph (kernel/bb/demod11/fb11bdemod_config.hpp:122-172), each where its SSE brick sits: one burst = N of the brick's own
 // bursts, one stream per adapter.  What the bricks keep in context facades -- CF_DifferentialDemap::last_symbol, CF_Descramber::byte_reg -- lies in ONE device record
 // (sora_stream11b_state) that the adapters of a graph share, as the bricks share their context: the demappers and the CCK decoders hand last_symbol on to each other, the

@@ -39,7 +39,8 @@ extern "C" {
  * sora_hip_pilot11a, sora_rx_bind_mpdu, sora_rx11n_trellis, sora_rx11n_window_stats, sora_rx_call_front, sora_rx_set_ordered, sora_hip_set_share_window_us, SORA_TRELLIS_WINDOWED and
  * the automatic choice for sora_rx11n_set_trellis.
  * Additive since: the 802.11a modulation graph's bricks as stages -- sora_hip_scramble11a, _conv_encode11a, _interleave11a, _map11a, _add_pilot11a (_from), _ifftx11a,
- * _upsample40to44, _pack16to8, _preamble11a. */
+ * _upsample40to44, _pack16to8, _preamble11a; the 802.11n modulation graphs' -- sora_hip_stream_parse11n, _interleave11n, _map11n, _sig_map11n, _add_pilot11n,
+ * _ifft_only11n, _csd11n, _add_gi11n, _preamble11n. */
 #define SORA_HIP_ABI_VERSION 4
 
 /* COMPLEX16: kernel/core/inc/complex.h */
@@ -459,6 +460,50 @@ int sora_hip_upsample40to44(const sora_complex16* d_in, sora_complex16* d_out, c
 int sora_hip_pack16to8(const sora_complex16* d_in, int8_t* d_out, size_t nsamples, void* stream);
 /* TTS11aSrc (preamble11a.hpp:19-140): the 640 COMPLEX16 preamble samples at 40 MHz, ncopies times back to back */
 int sora_hip_preamble11a(sora_complex16* d_out, size_t ncopies, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The bricks of the 802.11n 2x2 modulation graphs as stage entry points: what CreatePreambleGraph11n, CreateSigGraph11n and CreateModGraph11n
+ * (kernel/bb/demod11/fb11nmod_config.hpp) are built from beyond the 802.11a stages above, each with the port format of the brick it replaces:
+ *     preamble11n(0)
+ *     SIG:  conv_encode11a -> interleave11a -> sig_map11n -> add_pilot11a (bpsk_mod 30339) -> ifft_only11n -> chain 0 add_gi11n, chain 1 csd11n(2) + add_gi11n
+ *     preamble11n(1)
+ *     data: scramble11a -> conv_encode11a -> stream_parse11n -> per stream interleave11n -> map11n -> add_pilot11n -> ifft_only11n -> chain 1 csd11n(4) -> add_gi11n
+ * T11aSc, TConvEncode_*, the SIG graph's T11aInterleaveBPSK and T11aAddPilot<30339> are the 802.11a stages; TBB11nSrc, TBB11nSigSrc and TBB11nMRSelect are the host's.
+ * The conventions are those of the 802.11a block: device pointers, stream order, no allocation, no host wait; a null pointer or a symbol buffer that is not 16-byte
+ * aligned gives SORA_ERR_INVALID_PARAM, no device SORA_ERR_NO_DEVICE, a count of 0 is SORA_OK and launches nothing.  Bits are packed in bytes, LSB first.
+ * N_b = ceil(52 n_bpsc / 8) = 7, 13, 26, 39 bytes per stream and symbol; rows lie back to back, unpadded.  DESIGN.md section 7, f5b.
+ * ------------------------------------------------------------------------------------------------ */
+/* TStreamParser{BPSK,QPSK,QAM16,QAM64}_12 (Brick11/src/streamparser.hpp, _b_stream_parser.h): IPORT uchar x 13 n_bpsc -> OPORTS 0 and 1 uchar x N_b per symbol.
+ * With s = max(1, n_bpsc / 2), coded bit k goes to stream (k / s) & 1 as its bit (k / 2s) s + k % s.  BPSK's seventh byte carries four bits: its upper half is 0
+ * on both outputs, as the brick's half-byte table writes it. */
+int sora_hip_stream_parse11n(const uint8_t* d_in, uint8_t* d_out0, uint8_t* d_out1, int n_bpsc, size_t nsym, void* stream);
+/* T11nInterleave{BPSK,QPSK,QAM16,QAM64}_S1 / _S2 = T11Interleave<52 n_bpsc, n_bpsc, 13, 11, I_SS> (interleave.hpp:17-123): IPORT uchar x N_b -> OPORT uchar x N_b
+ * per symbol.  spatial_stream as for sora_hip_deinterleave11n: 0 = _S1 (first stream), 1 = _S2.  The brick's table is indexed by whole input bytes; for BPSK its bits
+ * 52..55 are ORed onto output positions below 52 (where its loop over k = 52..55 sends them) and output bits 52..55 are 0.  The parser leaves those input bits 0. */
+int sora_hip_interleave11n(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, int spatial_stream, size_t nsym, void* stream);
+/* TMap11a{BPSK,QPSK,QAM16,QAM64}<MOD> behind the 11n interleavers: IPORT uchar x N_b -> COMPLEX16 x 52 per symbol.  mod = the brick's MOD (1 .. 32767); 0 = what the
+ * 802.11n graph instantiates: 30339, 21453, 9594, 4681.  For BPSK the brick emits 56 carriers per 7 bytes and T11nAddPilot discards the last four (ipin.clear(),
+ * pilot_11n.hpp:78-79): this stage produces the 52 -- the one place where a stage's format is not the brick's pin. */
+int sora_hip_map11n(const uint8_t* d_in, sora_complex16* d_out, int n_bpsc, int mod, size_t nsym, void* stream);
+/* TSigMap11n (mapper11n.hpp): IPORT uchar x 18 -> OPORT COMPLEX16 x 144 per frame: bytes 0..5 (L-SIG) MapBPSK, +-30339 on I; bytes 6..17 (HT-SIG) MapQBPSK, on Q */
+int sora_hip_sig_map11n(const uint8_t* d_in, sora_complex16* d_out, size_t nframes, void* stream);
+/* T11nAddPilot<spatial_stream> (pilot_11n.hpp:7-82, _b_dot11_pilot.h): IPORT COMPLEX16 x 52 -> OPORT COMPLEX16 x 64 per symbol: data on bins 36..63 then 1..28
+ * without +-7 and +-21, pilots 30339 x sign at 43, 57, 7, 21, every other bin 0.  The frame tables are sora_hip_add_pilot11a's; the symbol at position n of its frame
+ * takes _pilot_sign[(n + 3) % 127] x _pilot[n & 3][spatial_stream][k].  Table entry f begins at position d_pos0[f] of its frame (d_pos0 NULL: 0 everywhere), as for
+ * sora_hip_add_pilot11a_from.  Symbols that no frame owns are not written. */
+int sora_hip_add_pilot11n(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_pos0,
+                          size_t nframes, int spatial_stream, void* stream);
+/* TIFFTxOnly (fft.hpp:63-103): IPORT COMPLEX16 x 64 -> OPORT COMPLEX16 x 128 per symbol: bins 0..31 and 32..63 at bins 0..31 and 96..127 of the reference's fixed-point
+ * IFFT<128>; no shift, no guard interval, no window */
+int sora_hip_ifft_only11n(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream);
+/* TCSD<ncsd> (csd.hpp): COMPLEX16 x 128 -> 128 per symbol, output sample (i + 4 ncsd) mod 128 = input sample i.  ncsd 1 .. 31 (the graphs use 2 and 4).  Out of place
+ * only: d_in == d_out gives SORA_ERR_INVALID_PARAM. */
+int sora_hip_csd11n(const sora_complex16* d_in, sora_complex16* d_out, int ncsd, size_t nsym, void* stream);
+/* TAddGI (gi.hpp): COMPLEX16 x 128 -> 160 per symbol: the last 32 samples, then the 128 */
+int sora_hip_add_gi11n(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream);
+/* LSrc (field 0: L-STF, L-LTF, 640 COMPLEX16 per chain) / HTSrc (field 1: HT-STF, HT-LTF1, HT-LTF2, 480 per chain) (preamble11n.hpp), ncopies times back to back into
+ * d_out0 (TX chain 0) and d_out1 (chain 1): the fixed fields sora_hip_tx11n writes, from the same table */
+int sora_hip_preamble11n(sora_complex16* d_out0, sora_complex16* d_out1, int field, size_t ncopies, void* stream);
 
 /* 802.11n 2x2 transmitter: the reference's modulation graphs CreatePreambleGraph11n + CreateSigGraph11n + CreateModGraph11n
  * (kernel/bb/demod11/fb11nmod_config.hpp) as Test11N_FB_Mod runs them (fb11n_mod.cpp:28-70): L-STF, L-LTF, L-SIG, HT-SIG, HT-STF,

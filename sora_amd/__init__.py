@@ -9,6 +9,8 @@ from .capi import (Rx, Rx11b, Rx11n, RxHt40, ht40_symbols, HostResults, ROW_DTYP
                    viterbi11n_ws, viterbi11n_workspace_bytes, viterbi_window_stats,
                    ingest, ingest_count, scramble11a, conv_encode11a, interleave11a, map11a, add_pilot11a, ifftx11a, upsample40to44, pack16to8, preamble11a,
                    mod11a_by_stages, Mod11aStages, mod11a_fields, CR_12, CR_23, CR_34,
+                   stream_parse11n, interleave11n, map11n, sig_map11n, add_pilot11n, ifft_only11n, csd11n, add_gi11n, preamble11n,
+                   mod11n_by_stages, Mod11nStages, mod11n_fields,
                    dc_remove11b, energy_detect11b, symtiming11b, barker_sync11b, despread11b, sfd_sync11b, dbpsk_demap11b, dqpsk_demap11b, cck5p5_decode11b,
                    cck11_decode11b, desc741_11b, plcp_parse11b, frame_sink11b, rx11b_by_stages, rx11b_stages, state11b_reset, STATE11B_WORDS,
                    tx11a, tx11a_samples, tx11n, tx11n_samples, tx_ht40, tx_ht40_samples, tx11b, tx11b_samples, INGEST_RXBLOCK, INGEST_RAW14, INGEST_44TO40, INGEST_DECIMATE2,

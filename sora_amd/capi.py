@@ -74,6 +74,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11a44", "sora_hip_tx11a44_samples",
            "sora_hip_scramble11a", "sora_hip_conv_encode11a", "sora_hip_interleave11a", "sora_hip_map11a", "sora_hip_add_pilot11a", "sora_hip_add_pilot11a_from",
            "sora_hip_ifftx11a", "sora_hip_upsample40to44", "sora_hip_pack16to8", "sora_hip_preamble11a",
+           "sora_hip_stream_parse11n", "sora_hip_interleave11n", "sora_hip_map11n", "sora_hip_sig_map11n", "sora_hip_add_pilot11n", "sora_hip_ifft_only11n",
+           "sora_hip_csd11n", "sora_hip_add_gi11n", "sora_hip_preamble11n",
            "sora_hip_dc_remove11b", "sora_hip_energy_detect11b", "sora_hip_symtiming11b", "sora_hip_barker_sync11b", "sora_hip_despread11b", "sora_hip_sfd_sync11b",
            "sora_hip_dbpsk_demap11b", "sora_hip_dqpsk_demap11b", "sora_hip_cck5p5_decode11b", "sora_hip_cck11_decode11b", "sora_hip_desc741_11b", "sora_hip_plcp_parse11b",
            "sora_hip_frame_sink11b",
@@ -247,6 +249,16 @@ def load(build_if_missing=True):
     L.sora_hip_upsample40to44.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_pack16to8.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_preamble11a.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    # the 802.11n modulation graphs' bricks as stages
+    L.sora_hip_stream_parse11n.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_interleave11n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_map11n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_sig_map11n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_add_pilot11n.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    L.sora_hip_ifft_only11n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_csd11n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_add_gi11n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_preamble11n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
     # the 802.11b receive graph's bricks as stages
     L.sora_hip_dc_remove11b.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
     for fn in ("sora_hip_energy_detect11b", "sora_hip_barker_sync11b", "sora_hip_despread11b"):
@@ -1792,6 +1804,233 @@ def tx11n(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None):
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     return out0, out1, [int(v) for v in ooff]
+
+
+# ---- the 802.11n modulation graphs' bricks as stages (include/sora_hip.h; bits packed in bytes, LSB first; N_b = ceil(52 n_bpsc / 8) bytes per stream and symbol)
+def _row11n(n_bpsc):
+    return (52 * int(n_bpsc) + 7) // 8
+
+
+def stream_parse11n(s, n_bpsc, out=None, stream=None):
+    """TStreamParser*_12: s uint8 CUDA [n, 13 n_bpsc] -> (uint8 CUDA [n, N_b], the same) for spatial streams 0 and 1; out: a pair of buffers to write into"""
+    import torch
+    n = s.shape[0]
+    o0, o1 = out if out is not None else (torch.empty((n, _row11n(n_bpsc)), dtype=torch.uint8, device=s.device) for _ in range(2))
+    _check(load().sora_hip_stream_parse11n(_dev_ptr(s), _dev_ptr(o0), _dev_ptr(o1), int(n_bpsc), n, _stream_ptr(stream)))
+    return o0, o1
+
+
+def interleave11n(s, n_bpsc, spatial_stream, out=None, stream=None):
+    """T11nInterleave*_S1 / _S2 (spatial_stream 0 / 1): s uint8 CUDA [n, N_b] -> the same shape"""
+    import torch
+    out = torch.empty_like(s) if out is None else out
+    _check(load().sora_hip_interleave11n(_dev_ptr(s), _dev_ptr(out), int(n_bpsc), int(spatial_stream), s.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def map11n(s, n_bpsc, mod=0, out=None, stream=None):
+    """TMap11a*<MOD> of the 802.11n graph: s uint8 CUDA [n, N_b] -> int16 CUDA [n, 52, 2]; mod = 0: 30339 / 21453 / 9594 / 4681"""
+    import torch
+    out = torch.empty((s.shape[0], 52, 2), dtype=torch.int16, device=s.device) if out is None else out
+    _check(load().sora_hip_map11n(_dev_ptr(s), _dev_ptr(out), int(n_bpsc), int(mod), s.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def sig_map11n(s, stream=None):
+    """TSigMap11n: s uint8 CUDA [n, 18] -> int16 CUDA [n, 144, 2]"""
+    import torch
+    out = torch.empty((s.shape[0], 144, 2), dtype=torch.int16, device=s.device)
+    _check(load().sora_hip_sig_map11n(_dev_ptr(s), _dev_ptr(out), s.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def add_pilot11n(x, first, nsym, spatial_stream, pos0=None, out=None, stream=None):
+    """T11nAddPilot<spatial_stream>: x int16 CUDA [n, 52, 2]; first / nsym (/ pos0) int32 CUDA [nframes] -> int16 CUDA [n, 64, 2]; symbols no frame owns stay
+    as they were (0 in a buffer of the wrapper's)"""
+    import torch
+    out = torch.zeros((x.shape[0], 64, 2), dtype=torch.int16, device=x.device) if out is None else out
+    _check(load().sora_hip_add_pilot11n(_dev_ptr(x), _dev_ptr(out), _dev_ptr(first), _dev_ptr(nsym), _opt_ptr(pos0), first.shape[0], int(spatial_stream),
+                                        _stream_ptr(stream)))
+    return out
+
+
+def ifft_only11n(x, stream=None):
+    """TIFFTxOnly: x int16 CUDA [n, 64, 2] -> int16 CUDA [n, 128, 2]"""
+    import torch
+    out = torch.empty((x.shape[0], 128, 2), dtype=torch.int16, device=x.device)
+    _check(load().sora_hip_ifft_only11n(_dev_ptr(x), _dev_ptr(out), x.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def csd11n(x, ncsd, stream=None):
+    """TCSD<ncsd>: x int16 CUDA [n, 128, 2] -> the same shape, each symbol delayed circularly by 4 ncsd samples"""
+    import torch
+    out = torch.empty_like(x)
+    _check(load().sora_hip_csd11n(_dev_ptr(x), _dev_ptr(out), int(ncsd), x.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def add_gi11n(x, stream=None):
+    """TAddGI: x int16 CUDA [n, 128, 2] -> int16 CUDA [n, 160, 2]"""
+    import torch
+    out = torch.empty((x.shape[0], 160, 2), dtype=torch.int16, device=x.device)
+    _check(load().sora_hip_add_gi11n(_dev_ptr(x), _dev_ptr(out), x.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def preamble11n(field, ncopies=1, device=0, stream=None):
+    """LSrc (field 0) / HTSrc (field 1): -> (int16 CUDA [ncopies, 640 or 480, 2] for TX chain 0, the same for chain 1)"""
+    import torch
+    ns = {0: 640, 1: 480}.get(int(field), 640)
+    o0, o1 = (torch.empty((int(ncopies), ns, 2), dtype=torch.int16, device=torch.device("cuda", device)) for _ in range(2))
+    _check(load().sora_hip_preamble11n(_dev_ptr(o0), _dev_ptr(o1), int(field), int(ncopies), _stream_ptr(stream)))
+    return o0, o1
+
+
+_MCS_11N = {8: (1, CR_12, 52), 9: (2, CR_12, 104), 10: (2, CR_34, 156), 11: (4, CR_12, 208), 12: (4, CR_34, 312), 13: (6, CR_23, 416), 14: (6, CR_34, 468)}
+
+
+def mod11n_fields(mpdu, mcs, seed=0xAB):
+    """What TBB11nSigSrc and TBB11nSrc (PHY_11n.hpp:81-133, 251-278) send down the graphs for one MPDU without FCS: (the 9 SIG bytes: L-SIG at 6 Mbps with the LENGTH
+    that spans the HT frame, then HT-SIG; SERVICE + MPDU + FCS + tail + pad -- ht_padding_bytes rounds N_SYM x N_DBPS bits up to whole bytes; the index of the tail
+    byte; the symbols the graph emits once Flush has padded the encoder's last burst and the parser's last symbol with zeros; the scrambler register T11aSc starts from)"""
+    import zlib
+    nb, cr, nd = _MCS_11N[int(mcs)]
+    mpdu = bytes(mpdu)
+    ln = len(mpdu) + 4
+    nstd = -(-(ln * 8 + 16 + 6) // nd)                                           # ht_symbol_count
+    lsig = 0xB | ((((nstd + 5) * 24 - 16 - 6) // 8) << 5)
+    lsig |= (bin(lsig).count("1") & 1) << 17
+    ht = [int(mcs) & 0xFF, ln & 0xFF, (ln >> 8) & 0xFF, 3, 0, 0]
+    crc = 0xFF                                                                   # CalcCRC8(cdata, 4, 2): reflected, poly 0xE0, over 34 bits, complemented
+    for b in range(34):
+        crc ^= (ht[b >> 3] >> (b & 7)) & 1
+        crc = (crc >> 1) ^ 0xE0 if crc & 1 else crc >> 1
+    crc = ~crc & 0xFF
+    ht[4] |= (crc << 2) & 0xFF; ht[5] |= crc >> 6
+    nbytes = (nstd * nd + 7) // 8
+    data = np.zeros(nbytes, np.uint8)
+    data[2:2 + len(mpdu)] = np.frombuffer(mpdu, np.uint8)
+    data[2 + len(mpdu):2 + ln] = np.frombuffer(int(zlib.crc32(mpdu) & 0xFFFFFFFF).to_bytes(4, "little"), np.uint8)
+    ngroups = -(-nbytes // (cr + 1))
+    nsym = -(-(cr + 2) * ngroups // (13 * nb))
+    return np.array([lsig & 255, (lsig >> 8) & 255, (lsig >> 16) & 255] + ht, np.uint8), data, 2 + ln, nsym, int(seed) & 0xFF
+
+
+class Mod11nStages:
+    """sora_amd.tx11n's frames composed from stage entry points instead of the fused kernel: CreatePreambleGraph11n, CreateSigGraph11n and CreateModGraph11n
+    (fb11nmod_config.hpp) brick by brick.  The constructor plays TBB11nSigSrc and TBB11nSrc on the host (mod11n_fields) and uploads the fields and the frame tables;
+    run() is the stage chain, every intermediate through HBM.  The data symbols are laid out by modulation, so that each stage is one call per modulation, code rate
+    or spatial stream whatever the batch; the three SIG symbols of every frame and both streams' data symbols share the IFFT and guard-interval calls; a last
+    index_select puts the 160-sample blocks into frame order."""
+
+    def __init__(self, mpdus, mcs, seeds=None, device=0):
+        import torch
+        n = self.n = len(mpdus)
+        mcs = [int(m) for m in mcs] if np.ndim(mcs) else [int(mcs)] * n
+        if len(mcs) != n or any(m not in _MCS_11N or not 1 <= len(p) <= 4092 for p, m in zip(mpdus, mcs)):
+            raise SoraError(-1, "mod11n_by_stages: unsupported MCS or length (MCS 8..14, 1..4092 bytes)")
+        seeds = [0xAB] * n if seeds is None else list(seeds)
+        dev = self.dev = torch.device("cuda", device)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
+        i32 = lambda a: up(np.asarray(a, np.int64).astype(np.int32), np.int32)
+        fields = [mod11n_fields(p, m, s) for p, m, s in zip(mpdus, mcs, seeds)]
+        par = [_MCS_11N[m] for m in mcs]
+        nsym = [fl[3] for fl in fields]
+        order = sorted(range(n), key=lambda f: (par[f][0], f))                   # data symbol slots, frames grouped by modulation
+        slot0, at = [0] * n, 0
+        for f in order:
+            slot0[f] = at; at += nsym[f]
+        self.nslots = at
+        self.run_of, self.cbase, self.sbase, cat, sat = {}, {}, {}, 18 * n + (-18 * n) % 16, 0
+        for nb in (1, 2, 4, 6):                                                  # n_bpsc -> (first slot, slots); the coded bytes (13 n_bpsc per slot) and the
+            fs = [f for f in order if par[f][0] == nb]                           # stream bytes (N_b per slot) of a run lie together, from a 16-byte boundary
+            cnt = sum(nsym[f] for f in fs)
+            self.run_of[nb] = (slot0[fs[0]] if fs else at, cnt)
+            self.cbase[nb] = cat; cat += (cnt * 13 * nb + 15) // 16 * 16
+            self.sbase[nb] = sat; sat += (cnt * _row11n(nb) + 15) // 16 * 16
+        self.coded_bytes, self.stream_bytes = cat, max(sat, 16)
+        # the uncoded bytes: the SIG fields (9 bytes each), then the data fields, each with room for the zeros Flush pads the encoder's last burst with
+        glen = [-(-len(fl[1]) // (p[1] + 1)) * (p[1] + 1) for fl, p in zip(fields, par)]
+        doff = np.zeros(n + 1, np.int64); np.cumsum(glen, out=doff[1:]); doff += 9 * n
+        raw = np.zeros(int(doff[-1]), np.uint8)
+        for f, fl in enumerate(fields):
+            raw[9 * f:9 * f + 9] = fl[0]; raw[doff[f]:doff[f] + len(fl[1])] = fl[1]
+        self.d_raw = up(raw, np.uint8)
+        dlen = [len(fl[1]) for fl in fields]
+        self.scr = (i32(doff[:-1]), i32(dlen), i32([fl[2] for fl in fields]), up(np.asarray([fl[4] for fl in fields], np.uint8), np.uint8), max(dlen))
+        # TConvEncode_*: the SIG fields at rate 1/2 (18 bytes each from byte 0 of the coded buffer), the data fields by code rate; a fresh register per field
+        self.enc = [(CR_12, i32([9 * f for f in range(n)]), i32([9] * n), i32([18 * f for f in range(n)]), n, 9)]
+        for cr in (CR_12, CR_23, CR_34):
+            fs = [f for f in range(n) if par[f][1] == cr]
+            if fs:
+                self.enc.append((cr, i32([doff[f] for f in fs]), i32([glen[f] for f in fs]),
+                                 i32([self.cbase[par[f][0]] + (slot0[f] - self.run_of[par[f][0]][0]) * 13 * par[f][0] for f in fs]), len(fs), max(glen[f] for f in fs)))
+        self.sig_pil = (i32([3 * f for f in range(n)]), i32([3] * n))           # T11aAddPilot<30339>: L-SIG is position 0 of its three symbols
+        self.pil = (i32(slot0), i32(nsym))                                       # T11nAddPilot: the first data symbol is position 0
+        # 160-sample blocks of a chain's buffer: n x 4 of LSrc, 3 n SIG symbols, the data slots, n x 3 of HTSrc; frame order: L, SIG, HT, data
+        ht0 = 7 * n + self.nslots
+        blocks = []
+        for f in range(n):
+            blocks += list(range(4 * f, 4 * f + 4)) + list(range(4 * n + 3 * f, 4 * n + 3 * f + 3)) + list(range(ht0 + 3 * f, ht0 + 3 * f + 3))
+            blocks += list(range(7 * n + slot0[f], 7 * n + slot0[f] + nsym[f]))
+        self.d_blocks = up(np.asarray(blocks, np.int64), np.int64)
+        offs = np.zeros(n + 1, np.int64); np.cumsum([1600 + 160 * k for k in nsym], out=offs[1:])
+        self.offsets = [int(v) for v in offs]
+
+    def run(self):
+        """-> (out0, out1): int16 CUDA [total, 2] per TX chain; everything in order on torch's current stream (the gather at the end is torch's), nothing waited for"""
+        import torch
+        L = load()
+        st = _stream_ptr(None)
+        n, dev, ns = self.n, self.dev, self.nslots
+        u8 = lambda k: torch.zeros(k, dtype=torch.uint8, device=dev)
+        i16 = lambda *shape: torch.empty(shape + (2,), dtype=torch.int16, device=dev)
+        off, ln, tail, seed, mx = self.scr
+        d_scr = scramble11a(self.d_raw, off, ln, seed, tail=tail, max_len=mx)    # (the SIG bytes and the encoder's pad bytes are in no frame of the call)
+        d_coded = u8(self.coded_bytes)                                           # zeros: what Flush pads the parser's last symbol with
+        for cr, in_off, ilen, out_off, cnt, mxl in self.enc:
+            _check(L.sora_hip_conv_encode11a(_dev_ptr(d_scr), _dev_ptr(in_off), _dev_ptr(ilen), cr, _dev_ptr(d_coded), _dev_ptr(out_off), cnt, mxl, st))
+        # bins of every symbol that goes through TIFFTxOnly: 3 n SIG symbols, the data slots of stream 0, those of stream 1
+        d_bins = i16(3 * n + 2 * ns, 64)
+        d_sig = interleave11a(d_coded[:18 * n].view(3 * n, 6), 1)
+        d_sigcar = sig_map11n(d_sig.view(n, 18))
+        _check(L.sora_hip_add_pilot11a_from(_dev_ptr(d_sigcar), _dev_ptr(d_bins), _dev_ptr(self.sig_pil[0]), _dev_ptr(self.sig_pil[1]), None, n, 30339, st))
+        d_par = [u8(self.stream_bytes), u8(self.stream_bytes)]
+        d_int = [u8(self.stream_bytes), u8(self.stream_bytes)]
+        d_car = i16(2 * ns, 52)
+        for nb in (1, 2, 4, 6):                                                  # TStreamParser* -> T11nInterleave*_S1 / _S2 -> TMap11a*, per modulation
+            s0, cnt = self.run_of[nb]
+            if cnt:
+                sb = self.sbase[nb]
+                _check(L.sora_hip_stream_parse11n(d_coded.data_ptr() + self.cbase[nb], d_par[0].data_ptr() + sb, d_par[1].data_ptr() + sb, nb, cnt, st))
+                for iss in (0, 1):
+                    _check(L.sora_hip_interleave11n(d_par[iss].data_ptr() + sb, d_int[iss].data_ptr() + sb, nb, iss, cnt, st))
+                    _check(L.sora_hip_map11n(d_int[iss].data_ptr() + sb, d_car.data_ptr() + (iss * ns + s0) * 208, nb, 0, cnt, st))
+        for iss in (0, 1):                                                       # (every slot belongs to a frame)
+            _check(L.sora_hip_add_pilot11n(d_car.data_ptr() + iss * ns * 208, d_bins.data_ptr() + (3 * n + iss * ns) * 256, _dev_ptr(self.pil[0]),
+                                           _dev_ptr(self.pil[1]), None, n, iss, st))
+        d_t = ifft_only11n(d_bins)
+        d_c = i16(3 * n + ns, 128)                                               # chain 1 before its guard interval: TCSD<2> of the SIG symbols, TCSD<4> of stream 1
+        _check(L.sora_hip_csd11n(d_t.data_ptr(), d_c.data_ptr(), 2, 3 * n, st))
+        if ns:
+            _check(L.sora_hip_csd11n(d_t.data_ptr() + (3 * n + ns) * 512, d_c.data_ptr() + 3 * n * 512, 4, ns, st))
+        outs = []
+        for ch, src in enumerate((d_t, d_c)):                                    # a chain's blocks: LSrc, SIG + data behind TAddGI, HTSrc
+            outs.append(i16(10 * n + ns, 160))
+            _check(L.sora_hip_add_gi11n(src.data_ptr(), outs[ch].data_ptr() + 4 * n * 640, 3 * n + ns, st))
+        _check(L.sora_hip_preamble11n(outs[0].data_ptr(), outs[1].data_ptr(), 0, n, st))
+        _check(L.sora_hip_preamble11n(outs[0].data_ptr() + (7 * n + ns) * 640, outs[1].data_ptr() + (7 * n + ns) * 640, 1, n, st))
+        return tuple(o.index_select(0, self.d_blocks).reshape(-1, 2) for o in outs)
+
+
+def mod11n_by_stages(mpdus, mcs, seeds=None, device=0, sync=True):
+    """Modulate a batch of MPDUs (bytes WITHOUT FCS) through the stage chain (Mod11nStages) -> (out0, out1, offsets): the same as sora_amd.tx11n returns."""
+    plan = Mod11nStages(mpdus, mcs, seeds, device)
+    out0, out1 = plan.run()
+    if sync:
+        _check(load().sora_hip_stream_synchronize(_stream_ptr(None)))
+    return out0, out1, plan.offsets
 
 
 def tx_ht40_samples(mpdu_len_nofcs, mcs):

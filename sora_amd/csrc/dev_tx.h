@@ -112,6 +112,37 @@ __device__ __forceinline__ void tx_put_pilots11a(uint32_t* bins, int k, int p)
     bins[bin128(pilot_carrier(k) & 63)] = pack(mk(k == 3 ? -p : p, 0));
 }
 
+// ---- the 802.11n 2x2 data graph (fb11nmod_config.hpp), the pieces k_tx11n.hip and the stages of k_mod11n.hip share
+constexpr int kBpsk11n = 30339;             // fb11nmod_config.hpp: TMap11aBPSK<30339>, T11nAddPilot, T11aAddPilot<30339>, TSigMap11n
+__device__ __forceinline__ int kmod11n(int nb) { return nb == 1 ? kBpsk11n : nb == 2 ? 21453 : nb == 4 ? 9594 : 4681; }
+// TStreamParser*_12 (_b_stream_parser.h): bit k of spatial stream iss is coded bit ((k / S) 2 + iss) S + k % S of the symbol, S = max(1, N_BPSC / 2) bits per stream and turn
+__device__ __forceinline__ int tx_parse11n_index(int S, int iss, int k) { return ((k / S) * 2 + iss) * S + k % S; }
+// T11nAddPilot<iss> (pilot_11n.hpp:44-73, _b_dot11_pilot.h): pilot k of symbol n = polarity[(n + 3) % 127] x Psi_iss[(n + k) & 3] x 30339,
+// Psi_0 = {1, 1, -1, -1}, Psi_1 = {1, -1, -1, 1}; k = 0..3 at carriers -21, -7, 7, 21
+__device__ __forceinline__ int tx_pilot11n(int iss, uint32_t n, int k)
+{
+    const int j = (int)((n + (uint32_t)k) & 3u);
+    const int psi = iss == 0 ? (j < 2 ? 1 : -1) : ((j == 0 || j == 3) ? 1 : -1);
+    return (pilot_sgn((n + 3u) % 127u) ? -psi : psi) * kBpsk11n;
+}
+
+// ---- a tile of nbytes contiguous bytes between 16-byte aligned global memory and LDS (the stages of k_mod.hip and k_mod11n.hip, 256 threads): 16 bytes per lane, the
+// ragged end of a last tile byte by byte
+__device__ __forceinline__ void mod_tile_load(uint32_t* s, const uint8_t* g, int nbytes, int tid)
+{
+    for (int q = tid; q < (nbytes + 15) / 16; q += 256) {
+        if (16 * q + 16 <= nbytes) reinterpret_cast<uint4*>(s)[q] = reinterpret_cast<const uint4*>(g)[q];
+        else for (int b = 16 * q; b < 16 * q + 16; b++) reinterpret_cast<uint8_t*>(s)[b] = b < nbytes ? g[b] : (uint8_t)0;
+    }
+}
+__device__ __forceinline__ void mod_tile_store(uint8_t* g, const uint32_t* s, int nbytes, int tid)
+{
+    for (int q = tid; q < (nbytes + 15) / 16; q += 256) {
+        if (16 * q + 16 <= nbytes) reinterpret_cast<uint4*>(g)[q] = reinterpret_cast<const uint4*>(s)[q];
+        else for (int b = 16 * q; b < nbytes; b++) g[b] = reinterpret_cast<const uint8_t*>(s)[b];
+    }
+}
+
 // ---- IFFT<128> of a group's 128-word symbol buffer in place (ifft128_core_pk: packed COMPLEX16, bit-exact with fft128_core<true>): time sample n is left at
 // word brev7(n), swizzled (fft128_swz) where the buffer is.  The buffer is private to a 32-lane group: wave-level barriers.
 template <bool SWZ>

@@ -18,22 +18,7 @@
 
 namespace sora {
 
-// a tile of nbytes contiguous bytes between 16-byte aligned global memory and LDS: 16 bytes per lane, the ragged end of a last tile byte by byte
-__device__ __forceinline__ void mod_tile_load(uint32_t* s, const uint8_t* g, int nbytes, int tid)
-{
-    for (int q = tid; q < (nbytes + 15) / 16; q += 256) {
-        if (16 * q + 16 <= nbytes) reinterpret_cast<uint4*>(s)[q] = reinterpret_cast<const uint4*>(g)[q];
-        else for (int b = 16 * q; b < 16 * q + 16; b++) reinterpret_cast<uint8_t*>(s)[b] = b < nbytes ? g[b] : (uint8_t)0;
-    }
-}
-__device__ __forceinline__ void mod_tile_store(uint8_t* g, const uint32_t* s, int nbytes, int tid)
-{
-    for (int q = tid; q < (nbytes + 15) / 16; q += 256) {
-        if (16 * q + 16 <= nbytes) reinterpret_cast<uint4*>(g)[q] = reinterpret_cast<const uint4*>(s)[q];
-        else for (int b = 16 * q; b < nbytes; b++) g[b] = reinterpret_cast<const uint8_t*>(s)[b];
-    }
-}
-
+// (mod_tile_load / mod_tile_store, a tile between global memory and LDS: dev_tx.h)
 // ---- T11aSc: byte i of frame f = in ^ (the register after i + 1 steps), the register a phase of the period-127 cycle (tx_scramble); the tail byte keeps its two pad bits.
 // chunks = workgroups per frame (the host's bound on the lengths / 256).
 __global__ void __launch_bounds__(256) k_mod_scramble(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const uint32_t* __restrict__ off, const uint32_t* __restrict__ len,

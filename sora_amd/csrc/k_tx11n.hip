@@ -25,9 +25,7 @@ namespace sora {
 
 namespace {
 constexpr int kWords = 1056;                // generator words per stream: nsym * NDBPS input bits of a 4092-byte MPDU is at most 33696 (MCS 14)
-constexpr int kBpsk11n = 30339;             // fb11nmod_config.hpp: TMap11aBPSK<30339>, T11nAddPilot, T11aAddPilot<30339>, TSigMap11n
-__device__ __forceinline__ int kmod11n(int nb) { return nb == 1 ? kBpsk11n : nb == 2 ? 21453 : nb == 4 ? 9594 : 4681; }
-}  // namespace
+}  // namespace                             // (kBpsk11n, kmod11n, the parser's index rule and the 11n pilots: dev_tx.h)
 
 __global__ void __launch_bounds__(256) k_tx11n(Tx11nArgs A)
 {
@@ -122,7 +120,7 @@ __global__ void __launch_bounds__(256) k_tx11n(Tx11nArgs A)
             boff[t][m] = 0;
             if (q < ncomp && m < M) {
                 const int k = s_inv[iss][c * nb + h * M + m];
-                const int kc = ((k / S) * 2 + iss) * S + k % S;
+                const int kc = tx_parse11n_index(S, iss, k);
                 boff[t][m] = tx_punct_offset(P.cr, kc, kWords * 32u);
             }
         }
@@ -148,12 +146,7 @@ __global__ void __launch_bounds__(256) k_tx11n(Tx11nArgs A)
                 }
             }
             if (e < 4) {
-                // T11nAddPilot<iss> (pilot_11n.hpp:44-73, _b_dot11_pilot.h): pilot k of symbol n = polarity[(n + 3) % 127] x Psi_iss[(n + k) & 3],
-                // Psi_0 = {1, 1, -1, -1}, Psi_1 = {1, -1, -1, 1}; k = 0..3 at carriers -21, -7, 7, 21
-                const int j = (int)((s + (uint32_t)e) & 3u);
-                const int psi = iss == 0 ? (j < 2 ? 1 : -1) : ((j == 0 || j == 3) ? 1 : -1);
-                const int p = (pilot_sgn((s + 3u) % 127u) ? -psi : psi) * kBpsk11n;
-                bins[bin128(pilot_carrier(e) & 63)] = pack(mk(p, 0));
+                bins[bin128(pilot_carrier(e) & 63)] = pack(mk(tx_pilot11n(iss, s, e), 0));   // T11nAddPilot<iss>: pilot e of symbol s
             }
         }
         tx_ifft128<false>(bins, e, tw);                                          // (a group past the last symbol only keeps the barriers company)

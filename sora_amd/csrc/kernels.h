@@ -213,6 +213,17 @@ __host__ __device__ inline bool tx11n_plan(uint32_t len, uint32_t mcs, Tx11nPlan
 constexpr uint32_t kTx11nPreamble = 1120;                // samples per chain of the table: L-STF + L-LTF + HT-STF + 2 HT-LTF
 __global__ void k_tx11n(Tx11nArgs A);
 
+// ---- the 802.11n modulation graphs' bricks as stages (k_mod11n.hip); symbol counts n, 16-byte words nwords
+template <int NB> __global__ void k_mod11n_parse(const uint8_t* in, uint8_t* out0, uint8_t* out1, uint32_t n);
+template <int NB> __global__ void k_mod11n_interleave(const uint8_t* in, uint8_t* out, int iss, uint32_t n);
+template <int NB> __global__ void k_mod11n_map(const uint8_t* in, uint32_t* out, int mod, uint32_t n);
+__global__ void k_mod11n_sig_map(const uint8_t* in, uint32_t* out, uint32_t n);
+__global__ void k_mod11n_add_pilot(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* nsym, const uint32_t* pos0, uint32_t nframes, int iss);
+__global__ void k_mod11n_ifft(const uint32_t* in, uint32_t* out, uint32_t n, Tables T);
+__global__ void k_mod11n_csd(const uint4* in, uint4* out, int ncsd, uint64_t nwords);
+__global__ void k_mod11n_add_gi(const uint4* in, uint4* out, uint64_t nwords);
+__global__ void k_mod11n_preamble(const uint4* table, uint4* out0, uint4* out1, uint32_t w0, uint32_t nw, uint64_t nwords);
+
 // ---- 40 MHz HT 2x2 transmitter (k_tx_ht40.hip)
 struct TxHt40Args {            // sora_hip_tx_ht40; sora_hip_tx_ht40_joint: ONE MPDU and one seed per frame -- off[nframes], seed[nframes] (nullptr: 0x5D)
     const uint8_t*  mpdu;      // MPDUs without FCS: stream s of frame f at mpdu + off[2 f + s]

@@ -1874,7 +1874,7 @@ int sora_hip_preamble11a(sora_complex16* d_out, size_t ncopies, void* stream)
     HIPCHK(hipGetLastError());
     return SORA_OK;
 }
-#undef MOD_STAGE_ENTRY
+// (MOD_STAGE_ENTRY also opens the 802.11n modulation stages, behind sora_hip_tx11n whose preamble table they share)
 
 // ---- the 802.11b receive graph's bricks as stages (k_11b.hip)
 #define ST11B_ENTRY(who, nullcond, count) \
@@ -2051,6 +2051,21 @@ static void tx11n_preamble_host(std::vector<uint32_t>& tab)
     }
 }
 
+// the table on the device (sora_hip_tx11n and sora_hip_preamble11n): built once per device, complete before it is published
+static int tx11n_preamble_ready(DevTables* D)
+{
+    std::lock_guard<std::mutex> lock(g_stage_mutex);
+    if (!D->tx11n_preamble) {
+        std::vector<uint32_t> tab; tx11n_preamble_host(tab);
+        uint32_t* p = nullptr;
+        HIPCHK(hipMalloc((void**)&p, tab.size() * sizeof(uint32_t)));
+        const hipError_t e = hipMemcpy(p, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(p); return fail(SORA_ERR_HARDWARE_FAILED, "tx11n preamble upload", e); }
+        D->tx11n_preamble = p; D->allocs.push_back(p);
+    }
+    return SORA_OK;
+}
+
 size_t sora_hip_tx11n_samples(uint32_t mpdu_len_nofcs, uint32_t mcs)
 {
     Tx11nPlan P;
@@ -2065,17 +2080,7 @@ int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t*
     if (!d_mpdu || !d_off || !d_len || !d_mcs || !d_out0 || !d_out1 || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_tx11n: null pointer");
     if (nframes == 0) return SORA_OK;
     DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    {
-        std::lock_guard<std::mutex> lock(g_stage_mutex);                          // built once per device, complete before it is published
-        if (!D->tx11n_preamble) {
-            std::vector<uint32_t> tab; tx11n_preamble_host(tab);
-            uint32_t* p = nullptr;
-            HIPCHK(hipMalloc((void**)&p, tab.size() * sizeof(uint32_t)));
-            const hipError_t e = hipMemcpy(p, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-            if (e != hipSuccess) { (void)hipFree(p); return fail(SORA_ERR_HARDWARE_FAILED, "tx11n preamble upload", e); }
-            D->tx11n_preamble = p; D->allocs.push_back(p);
-        }
-    }
+    if (const int rc = tx11n_preamble_ready(D)) return rc;
     Tx11nArgs A{};
     A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.mcs = d_mcs; A.seed = d_seed;
     A.out0 = reinterpret_cast<uint32_t*>(d_out0); A.out1 = reinterpret_cast<uint32_t*>(d_out1); A.out_off = d_out_off;
@@ -2084,6 +2089,140 @@ int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t*
     HIPCHK(hipGetLastError());
     return SORA_OK;
 }
+
+// ---- the 802.11n modulation graphs' bricks as stages (k_mod11n.hip)
+#define MOD11N_ALIGNED(who, bits) \
+    if ((bits) & 15) return fail(SORA_ERR_INVALID_PARAM, who ": buffers must be 16-byte aligned");
+#define MOD11N_COUNT(who, count) \
+    if ((count) >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, who ": too many for one call");
+#define MOD11N_BY_NB(kernel, ...) \
+    switch (n_bpsc) { \
+    case 1: hipLaunchKernelGGL(kernel<1>, grid, dim3(256), 0, st, __VA_ARGS__); break; \
+    case 2: hipLaunchKernelGGL(kernel<2>, grid, dim3(256), 0, st, __VA_ARGS__); break; \
+    case 4: hipLaunchKernelGGL(kernel<4>, grid, dim3(256), 0, st, __VA_ARGS__); break; \
+    default: hipLaunchKernelGGL(kernel<6>, grid, dim3(256), 0, st, __VA_ARGS__); break; \
+    }
+
+int sora_hip_stream_parse11n(const uint8_t* d_in, uint8_t* d_out0, uint8_t* d_out1, int n_bpsc, size_t nsym, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_stream_parse11n", !d_in || !d_out0 || !d_out1, nsym)
+    if (!mod_nbpsc_ok(n_bpsc)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_stream_parse11n: n_bpsc must be 1, 2, 4 or 6");
+    MOD11N_ALIGNED("sora_hip_stream_parse11n", (uintptr_t)d_in | (uintptr_t)d_out0 | (uintptr_t)d_out1)
+    MOD11N_COUNT("sora_hip_stream_parse11n", nsym)
+    const dim3 grid((unsigned)((nsym + 31) / 32)); hipStream_t st = (hipStream_t)stream;
+    MOD11N_BY_NB(k_mod11n_parse, d_in, d_out0, d_out1, (uint32_t)nsym)
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_interleave11n(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, int spatial_stream, size_t nsym, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_interleave11n", !d_in || !d_out, nsym)
+    if (!mod_nbpsc_ok(n_bpsc) || spatial_stream < 0 || spatial_stream > 1)
+        return fail(SORA_ERR_INVALID_PARAM, "sora_hip_interleave11n: n_bpsc must be 1, 2, 4 or 6 and spatial_stream 0 or 1");
+    MOD11N_ALIGNED("sora_hip_interleave11n", (uintptr_t)d_in | (uintptr_t)d_out)
+    MOD11N_COUNT("sora_hip_interleave11n", nsym)
+    const dim3 grid((unsigned)((nsym + 31) / 32)); hipStream_t st = (hipStream_t)stream;
+    MOD11N_BY_NB(k_mod11n_interleave, d_in, d_out, spatial_stream, (uint32_t)nsym)
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_map11n(const uint8_t* d_in, sora_complex16* d_out, int n_bpsc, int mod, size_t nsym, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_map11n", !d_in || !d_out, nsym)
+    if (!mod_nbpsc_ok(n_bpsc) || mod < 0 || mod > 32767) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11n: n_bpsc must be 1, 2, 4 or 6 and mod 0 .. 32767");
+    MOD11N_ALIGNED("sora_hip_map11n", (uintptr_t)d_in | (uintptr_t)d_out)
+    MOD11N_COUNT("sora_hip_map11n", nsym)
+    if (mod == 0) mod = n_bpsc == 1 ? 30339 : n_bpsc == 2 ? 21453 : n_bpsc == 4 ? 9594 : 4681;   // fb11nmod_config.hpp:121-128
+    const dim3 grid((unsigned)((nsym + 31) / 32)); hipStream_t st = (hipStream_t)stream; uint32_t* out = reinterpret_cast<uint32_t*>(d_out);
+    MOD11N_BY_NB(k_mod11n_map, d_in, out, mod, (uint32_t)nsym)
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_sig_map11n(const uint8_t* d_in, sora_complex16* d_out, size_t nframes, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_sig_map11n", !d_in || !d_out, nframes)
+    MOD11N_ALIGNED("sora_hip_sig_map11n", (uintptr_t)d_in | (uintptr_t)d_out)
+    MOD11N_COUNT("sora_hip_sig_map11n", nframes)
+    hipLaunchKernelGGL(k_mod11n_sig_map, dim3((unsigned)((nframes + 31) / 32)), dim3(256), 0, (hipStream_t)stream, d_in, reinterpret_cast<uint32_t*>(d_out), (uint32_t)nframes);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_add_pilot11n(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_pos0,
+                          size_t nframes, int spatial_stream, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_add_pilot11n", !d_in || !d_out || !d_first || !d_nsym, nframes)
+    if (spatial_stream < 0 || spatial_stream > 1) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11n: spatial_stream must be 0 or 1");
+    MOD11N_ALIGNED("sora_hip_add_pilot11n", (uintptr_t)d_in | (uintptr_t)d_out)
+    MOD11N_COUNT("sora_hip_add_pilot11n", nframes)
+    // (sora_hip_add_pilot11a's grid: a batch of few frames gets several workgroups per frame, each striding over the frame's passes of 16 symbols)
+    const unsigned gy = nframes >= 2048 ? 1u : (unsigned)std::min<size_t>(64, 2048 / nframes);
+    hipLaunchKernelGGL(k_mod11n_add_pilot, dim3((unsigned)nframes, gy), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
+                       reinterpret_cast<uint32_t*>(d_out), d_first, d_nsym, d_pos0, (uint32_t)nframes, spatial_stream);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_ifft_only11n(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_ifft_only11n", !d_in || !d_out, nsym)
+    MOD11N_ALIGNED("sora_hip_ifft_only11n", (uintptr_t)d_in | (uintptr_t)d_out)
+    MOD11N_COUNT("sora_hip_ifft_only11n", nsym)
+    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    hipLaunchKernelGGL(k_mod11n_ifft, dim3((unsigned)((nsym + 31) / 32)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
+                       reinterpret_cast<uint32_t*>(d_out), (uint32_t)nsym, D->T);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_csd11n(const sora_complex16* d_in, sora_complex16* d_out, int ncsd, size_t nsym, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_csd11n", !d_in || !d_out, nsym)
+    if (ncsd < 1 || ncsd > 31) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_csd11n: ncsd must be 1 .. 31");
+    if (d_in == d_out) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_csd11n: out of place only");
+    MOD11N_ALIGNED("sora_hip_csd11n", (uintptr_t)d_in | (uintptr_t)d_out)
+    MOD11N_COUNT("sora_hip_csd11n", nsym)
+    const uint64_t nwords = (uint64_t)nsym * 32;
+    hipLaunchKernelGGL(k_mod11n_csd, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(d_in),
+                       reinterpret_cast<uint4*>(d_out), ncsd, nwords);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_add_gi11n(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_add_gi11n", !d_in || !d_out, nsym)
+    MOD11N_ALIGNED("sora_hip_add_gi11n", (uintptr_t)d_in | (uintptr_t)d_out)
+    MOD11N_COUNT("sora_hip_add_gi11n", nsym)
+    const uint64_t nwords = (uint64_t)nsym * 40;
+    hipLaunchKernelGGL(k_mod11n_add_gi, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(d_in),
+                       reinterpret_cast<uint4*>(d_out), nwords);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_preamble11n(sora_complex16* d_out0, sora_complex16* d_out1, int field, size_t ncopies, void* stream)
+{
+    MOD_STAGE_ENTRY("sora_hip_preamble11n", !d_out0 || !d_out1, ncopies)
+    if (field != 0 && field != 1) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble11n: field must be 0 (LSrc) or 1 (HTSrc)");
+    MOD11N_ALIGNED("sora_hip_preamble11n", (uintptr_t)d_out0 | (uintptr_t)d_out1)
+    if (ncopies >= (1ull << 24)) return fail(SORA_ERR_CAPACITY, "sora_hip_preamble11n: too many copies for one call");
+    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    if (const int rc = tx11n_preamble_ready(D)) return rc;
+    const uint32_t w0 = field ? 160u : 0u, nw = field ? 120u : 160u;             // 16-byte words: samples 0..639 / 640..1119 of a chain's 1120
+    const uint64_t nwords = (uint64_t)ncopies * nw;
+    hipLaunchKernelGGL(k_mod11n_preamble, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(D->tx11n_preamble),
+                       reinterpret_cast<uint4*>(d_out0), reinterpret_cast<uint4*>(d_out1), w0, nw, nwords);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+#undef MOD11N_BY_NB
+#undef MOD11N_COUNT
+#undef MOD11N_ALIGNED
+#undef MOD_STAGE_ENTRY
 
 // ---- 40 MHz HT 2x2 transmitter
 size_t sora_hip_tx_ht40_samples(uint32_t mpdu_len_nofcs, uint32_t mcs)
