@@ -685,6 +685,116 @@ public:
     }
 };
 
+// ------------------------------------------------------------------------------------------------
+// The bricks of the 802.11b modulation graph (kernel/bb/demod11/fb11bmod_config.hpp:28-50) behind TBB11bSrc (sora_hip_ppdu11b, or the host's) and TBB11bMRSelect (the
+// host's: it only routes): one burst = N of the brick's own bursts, one stream per adapter, d_tab as above.  What the bricks keep lies in device records that the entry
+// points read and write back, so the state crosses from Process to Process by itself: the four spreaders share ONE sora_mod11b_state as the bricks share
+// CF_DifferentialMap::last_phase (no Reset clears it); TCCK11Encode's bEven is is_even of the same record and its Reset clears it; the scrambler has its register, which
+// Reset sets to CF_ScramblerSeed::sc_seed; the shaper has its m_temps, which Reset clears.  Adapters of different burst sizes may share a record (the reference's pin
+// queues re-burst between the bricks; here each burst size is an adapter of its own over the same state).
+template <size_t N, class T_CTX, class T_NEXT>
+class THip11bSc741 : public THip11bStage<uint8_t, N, uint8_t, N, T_CTX, T_NEXT> {            // TSc741 (scramble.hpp:7-88), 1 -> 1
+    using Base = THip11bStage<uint8_t, N, uint8_t, N, T_CTX, T_NEXT>;
+public:
+    THip11bSc741(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* d_tab, uint32_t* d_reg, uint8_t sc_seed = 0x6C, void* stream = nullptr)
+        : Base(ctx, next, d_out, d_tab, (uint32_t)N, stream), d_reg_(d_reg), seed_(sc_seed) {}
+    void SetSeed(uint8_t sc_seed) { seed_ = sc_seed; }                                        // 0x6C behind the long preamble, 0x1B behind the short one
+    void Reset()
+    {
+        const uint32_t reg = seed_;
+        if (sora_hip_stream_synchronize(this->stream_) != SORA_OK || sora_hip_memcpy_h2d(d_reg_, &reg, sizeof(reg)) != SORA_OK) this->raise(SORA_ERR_HARDWARE_FAILED);
+        HipFilter<T_CTX, T_NEXT>::Reset();
+    }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        uint32_t* reg = d_reg_;
+        return this->run(ipin, [reg](const uint8_t* in, const uint32_t* f, const uint32_t* n, const uint32_t* of, const uint32_t*, uint8_t* out, void* st) {
+            return sora_hip_sc741_11b(in, f, n, of, reg, out, 1, N, st); });
+    }
+private:
+    uint32_t* d_reg_; uint8_t seed_;
+};
+
+// The four spreaders over the shared record: IPORT uchar x N -> OPORT COMPLEX8 x CHIPS N through ENTRY
+template <size_t CHIPS, size_t N, int (*ENTRY)(const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, sora_mod11b_state*, int8_t*, size_t, size_t, void*),
+          class T_CTX, class T_NEXT>
+class THip11bSpreadStage : public THip11bStage<uint8_t, N, sora_complex8, CHIPS * N, T_CTX, T_NEXT> {
+    using Base = THip11bStage<uint8_t, N, sora_complex8, CHIPS * N, T_CTX, T_NEXT>;
+public:
+    THip11bSpreadStage(T_CTX& ctx, T_NEXT* next, sora_complex8* d_out, void* d_tab, sora_mod11b_state* d_state, void* stream = nullptr)
+        : Base(ctx, next, d_out, d_tab, (uint32_t)N, stream), d_state_(d_state) {}
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        sora_mod11b_state* state = d_state_;
+        return this->run(ipin, [state](const uint8_t* in, const uint32_t* f, const uint32_t* n, const uint32_t* of, const uint32_t*, sora_complex8* out, void* st) {
+            return ENTRY(in, f, n, of, state, &out->re, 1, N, st); });
+    }
+protected:
+    sora_mod11b_state* d_state_;
+};
+// TBB11bDBPSKSpread (barkerspread.hpp:9-111), 1 -> 88; TBB11bDQPSKSpread (:113-225), 1 -> 44; TCCK5Encode (cck.hpp:880-953), 1 -> 16
+template <size_t N, class T_CTX, class T_NEXT> using THip11bDBPSKSpread = THip11bSpreadStage<88, N, sora_hip_dbpsk_spread11b, T_CTX, T_NEXT>;
+template <size_t N, class T_CTX, class T_NEXT> using THip11bDQPSKSpread = THip11bSpreadStage<44, N, sora_hip_dqpsk_spread11b, T_CTX, T_NEXT>;
+template <size_t N, class T_CTX, class T_NEXT> using THip11bCCK5Encode = THip11bSpreadStage<16, N, sora_hip_cck5_encode11b, T_CTX, T_NEXT>;
+// TCCK11Encode (cck.hpp:782-870), 1 -> 8: Reset clears bEven
+template <size_t N, class T_CTX, class T_NEXT>
+class THip11bCCK11Encode : public THip11bSpreadStage<8, N, sora_hip_cck11_encode11b, T_CTX, T_NEXT> {
+    using Base = THip11bSpreadStage<8, N, sora_hip_cck11_encode11b, T_CTX, T_NEXT>;
+public:
+    using Base::Base;
+    void Reset()
+    {
+        const uint32_t zero = 0;
+        if (sora_hip_stream_synchronize(this->stream_) != SORA_OK || sora_hip_memcpy_h2d(&this->d_state_->is_even, &zero, sizeof(zero)) != SORA_OK)
+            this->raise(SORA_ERR_HARDWARE_FAILED);
+        HipFilter<T_CTX, T_NEXT>::Reset();
+    }
+};
+
+// TQuickPulseShaper (pulse.hpp:254-384), 1 -> 4: IPORT COMPLEX8 x N -> OPORT COMPLEX16 x 4 N.  Flush runs the brick's five bursts from zero input (20 samples) and hands
+// them on in whole output bursts, the last one padded with zeros as the reference's pin queue pads it for the brick behind: d_out has room for kFlushBursts bursts.
+template <size_t N, class T_CTX, class T_NEXT>
+class THip11bQuickPulseShaper : public THip11bStage<sora_complex8, N, sora_complex16, 4 * N, T_CTX, T_NEXT> {
+    using Base = THip11bStage<sora_complex8, N, sora_complex16, 4 * N, T_CTX, T_NEXT>;
+public:
+    static constexpr size_t kFlushBursts = (20 + 4 * N - 1) / (4 * N);
+    THip11bQuickPulseShaper(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* d_tab, sora_shaper11b_state* d_state, void* stream = nullptr)
+        : Base(ctx, next, d_out, d_tab, (uint32_t)N, stream), d_state_(d_state) { this->word3_ = 1; }
+    void Reset()
+    {
+        const sora_shaper11b_state zero{};
+        if (sora_hip_stream_synchronize(this->stream_) != SORA_OK || sora_hip_memcpy_h2d(d_state_, &zero, sizeof(zero)) != SORA_OK) this->raise(SORA_ERR_HARDWARE_FAILED);
+        HipFilter<T_CTX, T_NEXT>::Reset();
+    }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        sora_shaper11b_state* state = d_state_;
+        return this->run(ipin, [state](const sora_complex8* in, const uint32_t* f, const uint32_t* n, const uint32_t* of, const uint32_t*, sora_complex16* out, void* st) {
+            return sora_hip_pulse_shape11b(&in->re, f, n, of, nullptr, state, out, 1, N, st); });
+    }
+    void Flush()
+    {
+        const sora_complex16 zeros[kFlushBursts * 4 * N] = {};
+        const uint32_t tab[4] = { 0u, (uint32_t)N, 0u, 1u };                                  // Process's table; its word 0 is the flush call's count, its word 3 the flag
+        sora_complex16* out = this->opin_.append();
+        this->opin_.clear();
+        bool ok = sora_hip_stream_synchronize(this->stream_) == SORA_OK && sora_hip_memcpy_h2d(out, zeros, sizeof(zeros)) == SORA_OK &&
+                  sora_hip_memcpy_h2d(this->d_tab_, tab, sizeof(tab)) == SORA_OK;
+        if (!ok) this->raise(SORA_ERR_HARDWARE_FAILED);
+        // no chips: d_in is not read, any device address serves
+        ok = ok && this->raise(sora_hip_pulse_shape11b(reinterpret_cast<const int8_t*>(out), this->d_tab_, this->d_tab_, this->d_tab_ + 2,
+                                                       reinterpret_cast<const uint8_t*>(this->d_tab_ + 3), d_state_, out, 1, 0, this->stream_));
+        for (size_t k = 0; ok && this->next_ && k < kFlushBursts; k++) {
+            DevicePin<sora_complex16, 4 * N> pin(out + k * 4 * N);
+            pin.append();
+            ok = this->next_->Process(pin);
+        }
+        HipFilter<T_CTX, T_NEXT>::Flush();
+    }
+private:
+    sora_shaper11b_state* d_state_;
+};
+
 // ISource over a batch of captures = the whole demod graph behind one handle (brick.h:343-353: Process/Seek/Reset/Flush).
 class THipRx11aSource {
 public:

@@ -40,7 +40,8 @@ extern "C" {
  * the automatic choice for sora_rx11n_set_trellis.
  * Additive since: the 802.11a modulation graph's bricks as stages -- sora_hip_scramble11a, _conv_encode11a, _interleave11a, _map11a, _add_pilot11a (_from), _ifftx11a,
  * _upsample40to44, _pack16to8, _preamble11a; the 802.11n modulation graphs' -- sora_hip_stream_parse11n, _interleave11n, _map11n, _sig_map11n, _add_pilot11n,
- * _ifft_only11n, _csd11n, _add_gi11n, _preamble11n. */
+ * _ifft_only11n, _csd11n, _add_gi11n, _preamble11n; the 802.11b modulation graph's -- sora_hip_ppdu11b, _sc741_11b, _dbpsk_spread11b, _dqpsk_spread11b, _cck5_encode11b,
+ * _cck11_encode11b, _pulse_shape11b (sora_mod11b_state, sora_shaper11b_state). */
 #define SORA_HIP_ABI_VERSION 4
 
 /* COMPLEX16: kernel/core/inc/complex.h */
@@ -588,6 +589,56 @@ size_t sora_hip_tx11b_pre_samples(uint32_t mpdu_len_nofcs, uint32_t rate_kbps, u
 int sora_hip_tx11b_pre(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_preamble,
                        const uint8_t* d_phase_in, uint8_t* d_phase_out, size_t nframes,
                        int8_t* d_out, const uint64_t* d_out_off, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The bricks of the 802.11b modulation graph as stage entry points: what CreateModGraph (kernel/bb/demod11/fb11bmod_config.hpp:28-50) is built from, each with the
+ * ports of the brick it replaces, so that a host can replace ONE brick, or compose the graph from stages (sora_amd.mod11b_by_stages does):
+ *     ppdu -> sc741 -> dbpsk_spread / dqpsk_spread / cck5_encode / cck11_encode -> pulse_shape -> pack16to8 (sora_hip_pack16to8, above)
+ * TBB11bMRSelect only routes and stays the host's; TModSink is the caller's buffer.  The conventions are those of the 802.11b receive stages below: device pointers,
+ * stream order, no allocation, no host wait; a null pointer gives SORA_ERR_INVALID_PARAM (sora_hip_last_error() names the function), no device SORA_ERR_NO_DEVICE,
+ * nstreams = 0 is SORA_OK and launches nothing.  The bricks are stateful streams, so a call works on a BATCH of independent streams described by device tables: stream f
+ * owns d_n[f] input units (bytes; chips for the shaper) starting at ELEMENT d_first[f] of d_in and writes its output from element d_out_first[f] of d_out (bytes,
+ * COMPLEX8 chips, COMPLEX16 samples).  What the brick keeps lies in a per-stream record of 32-bit words that the call reads and writes back: the state after the call
+ * is the state the brick would hold, the same stream cut into two calls gives what one call gives, output and state, and bytes of d_out that no stream owns are not
+ * written.  A stream with d_n[f] = 0 leaves its record as it is.  max_n bounds every d_n[f] (units of a stream at or behind it are not touched; at most 2^24).  Offsets
+ * need no alignment beyond their element's (d_in / d_out themselves: their element's).  A workgroup walks one stream, kMod11bT = 1024 units a pass, 16 bytes per lane
+ * and store.  Every stage equals tests/mod11b_model.py bit for bit, output and record (tests/test_gpu_mod11b_stages.py).  Measured on one MI355X on the commit that
+ * adds them (parent b2fead2), 4096 streams of a 1500-byte frame per call (tools/bench_mod11b_stages.py, profiles/mod11b_stages.json): the spreaders 0.224 / 0.122 /
+ * 0.045 / 0.033 ms at 1 / 2 / 5.5 / 11 Mbps (62 / 57 / 58 / 40 % of the HBM peak), the shaper 2.76 / 1.36 / 0.47 / 0.24 ms (45-47 %) beside sora_hip_pack16to8's 75 %
+ * in the same run, ppdu and sc741 0.024 ms each; composed they take 4.8 to 5.9 times sora_hip_tx11b's time.  DESIGN.md section 7, f6b.
+ * ------------------------------------------------------------------------------------------------ */
+/* CF_DifferentialMap::last_phase (0: 0, 1: -pi/2, 2: pi/2, 3: pi; context: no Reset clears it), which the four spreaders share, and TCCK11Encode's bEven (brick
+ * state, 0 after Reset).  Each stage reads and writes its own fields and leaves the others alone. */
+typedef struct { uint32_t last_phase, is_even, reserved[2]; } sora_mod11b_state;
+/* TQuickPulseShaper's m_temps[0..3]: the partial sums of the next four bursts (its fifth row is never written and stays 0).  All 0 after Reset. */
+typedef struct { sora_complex16 temps[4][4]; } sora_shaper11b_state;
+/* TBB11bSrc (PHY_11b.hpp:19-206) with the preamble kind per frame of sora_hip_tx11b_pre: frame f's MPDU WITHOUT FCS, d_len[f] bytes at d_mpdu + d_off[f] -> the PPDU
+ * bytes the source brick emits, from byte d_out_first[f] of d_out: SYNC, SFD, SIGNAL, SERVICE, LENGTH, CRC-16, MPDU, FCS -- 24 + len + 4 bytes behind the long preamble
+ * (d_preamble[f] = 0), 15 + len + 4 behind the short one (1).  A frame that sora_hip_tx11b_pre_samples answers with 0 gets nothing written. */
+int sora_hip_ppdu11b(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_preamble, uint8_t* d_out,
+                     const uint32_t* d_out_first, size_t nframes, void* stream);
+/* TSc741 (scramble.hpp:7-88), 1 -> 1 byte.  d_reg[f]: the 7-bit register; after Reset it is the context's sc_seed, 0x6C behind the long preamble and 0x1B behind the
+ * short one.  Only the low 7 bits are read: the reference indexes a [256][128] table, so a larger value is out of ITS bounds. */
+int sora_hip_sc741_11b(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, uint32_t* d_reg, uint8_t* d_out,
+                       size_t nstreams, size_t max_n, void* stream);
+/* TBB11bDBPSKSpread (barkerspread.hpp:9-111), 1 byte -> 88 COMPLEX8 (d_out: re, im pairs; d_out_first in COMPLEX8): reads only last_phase & 1 and leaves 0 or 3.
+ * TBB11bDQPSKSpread (:113-225), 1 -> 44: reads last_phase & 3. */
+int sora_hip_dbpsk_spread11b(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_mod11b_state* d_state, int8_t* d_out,
+                             size_t nstreams, size_t max_n, void* stream);
+int sora_hip_dqpsk_spread11b(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_mod11b_state* d_state, int8_t* d_out,
+                             size_t nstreams, size_t max_n, void* stream);
+/* TCCK5Encode (cck.hpp:880-953), 1 byte -> 16 COMPLEX8; TCCK11Encode (:782-870), 1 -> 8, whose bEven (is_even, low bit read) flips with every byte.  last_phase: the
+ * low two bits are read (the bricks index their tables with it unmasked). */
+int sora_hip_cck5_encode11b(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_mod11b_state* d_state, int8_t* d_out,
+                            size_t nstreams, size_t max_n, void* stream);
+int sora_hip_cck11_encode11b(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_mod11b_state* d_state, int8_t* d_out,
+                             size_t nstreams, size_t max_n, void* stream);
+/* TQuickPulseShaper (pulse.hpp:254-384), 1 COMPLEX8 -> 4 COMPLEX16: ANY COMPLEX8, -128 included, with QuickShape's arithmetic (mul_low, wrapping 16-bit adds).  The
+ * record holds the brick's PARTIAL SUMS, not past inputs, and one that no input history produces is honoured: sample s of step m of the call is
+ * wrap16(temps[m][s] (m < 4) + sum_{j = 0 .. min(m, 4)} x[m - j] tap[4 j + s]).  d_flush (may be NULL: no stream flushes): d_flush[f] != 0 runs the brick's Flush behind
+ * the stream's chips, five more bursts from zero input -- the stream then writes 4 (d_n[f] + 5) samples (and d_n[f] = 0 is five bursts from the record). */
+int sora_hip_pulse_shape11b(const int8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const uint8_t* d_flush,
+                            sora_shaper11b_state* d_state, sora_complex16* d_out, size_t nstreams, size_t max_n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 802.11n 2x2, stage level (the whole-path graph is sora_rx11n_* below).  Batched bricks, n symbols per call:

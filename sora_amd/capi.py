@@ -80,6 +80,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_hip_dbpsk_demap11b", "sora_hip_dqpsk_demap11b", "sora_hip_cck5p5_decode11b", "sora_hip_cck11_decode11b", "sora_hip_desc741_11b", "sora_hip_plcp_parse11b",
            "sora_hip_frame_sink11b",
            "sora_hip_tx11n", "sora_hip_tx11n_samples", "sora_hip_tx_ht40", "sora_hip_tx_ht40_samples", "sora_hip_tx11b", "sora_hip_tx11b_samples", "sora_hip_tx11b_pre", "sora_hip_tx11b_pre_samples",
+           "sora_hip_ppdu11b", "sora_hip_sc741_11b", "sora_hip_dbpsk_spread11b", "sora_hip_dqpsk_spread11b", "sora_hip_cck5_encode11b", "sora_hip_cck11_encode11b",
+           "sora_hip_pulse_shape11b",
            "sora_hip_tx_ht40_joint", "sora_hip_tx_ht40_joint_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n", "sora_rx11b_create",
@@ -98,6 +100,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_shard_reduce_counters", "sora_shard_gather_results", "sora_shard_gather_results_mpdu"]
 
 STREAM11B_STAGES = ("sora_hip_dbpsk_demap11b", "sora_hip_dqpsk_demap11b", "sora_hip_cck5p5_decode11b", "sora_hip_cck11_decode11b", "sora_hip_desc741_11b")
+
+SPREAD11B_STAGES = ("sora_hip_dbpsk_spread11b", "sora_hip_dqpsk_spread11b", "sora_hip_cck5_encode11b", "sora_hip_cck11_encode11b")
 
 _lib = None
 
@@ -279,6 +283,11 @@ def load(build_if_missing=True):
     L.sora_hip_tx11b.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
     L.sora_hip_tx11b_pre_samples.argtypes = [ctypes.c_uint32] * 3; L.sora_hip_tx11b_pre_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11b_pre.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
+    # the 802.11b modulation graph's bricks as stages
+    L.sora_hip_ppdu11b.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
+    for fn in ("sora_hip_sc741_11b",) + SPREAD11B_STAGES:
+        getattr(L, fn).argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_pulse_shape11b.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_ingest_count.argtypes = [ctypes.c_size_t, ctypes.c_uint]; L.sora_hip_ingest_count.restype = ctypes.c_size_t
     L.sora_hip_ingest.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t,
                                   ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
@@ -2128,15 +2137,8 @@ def tx11b_samples(mpdu_len_nofcs, rate_kbps, preamble=0):
     return int(load().sora_hip_tx11b_pre_samples(int(mpdu_len_nofcs), int(rate_kbps), int(preamble) & 0xFFFFFFFF))
 
 
-def tx11b(mpdus, rates_kbps, phase_in=None, device=0, stream=None, sync=True, gaps=None, return_phase=False, preamble=None):
-    """Modulate a batch of MPDUs (bytes WITHOUT FCS) as 802.11b frames on the GPU (1000, 2000, 5500, 11000 kbps).  preamble: None = every frame behind the
-    long preamble (sora_hip_tx11b); else 0 (long) or 1 (short: 2000, 5500, 11000 kbps only), one value or one per frame (sora_hip_tx11b_pre).
-    -> (out, offsets): an int8 CUDA tensor [total,2] COMPLEX8 @44 MHz and the offsets list; frame f occupies samples offsets[f] ..
-    offsets[f+1] (gaps[f] zero samples in front of frame f, if given, included at its start).
-    phase_in: the reference's last_phase (0..3) at the start of each frame, one value or one per frame (None: 0, a fresh reference
-    process).  return_phase: also return last_phase after each frame, a list -- pass it back as phase_in to continue one reference
-    process's sequence.  A frame with an unsupported rate or length is refused before any launch."""
-    import torch
+def _tx11b_frames(mpdus, rates_kbps, phase_in, preamble):
+    """what tx11b and mod11b_by_stages accept -> (n, rates, lengths, kinds or None, samples per frame, phase_in as a list or None); the rest is refused"""
     n = len(mpdus)
     rates = [int(r) for r in rates_kbps] if np.ndim(rates_kbps) else [int(rates_kbps)] * n
     lens = [len(m) for m in mpdus]
@@ -2152,6 +2154,19 @@ def tx11b(mpdus, rates_kbps, phase_in=None, device=0, stream=None, sync=True, ga
         phase_in = [int(p) for p in phase_in] if np.ndim(phase_in) else [int(phase_in)] * n
         if len(phase_in) != n or any(not 0 <= p <= 3 for p in phase_in):
             raise SoraError(-1, "tx11b: phase_in must hold one value 0..3 per frame")
+    return n, rates, lens, kinds, ns, phase_in
+
+
+def tx11b(mpdus, rates_kbps, phase_in=None, device=0, stream=None, sync=True, gaps=None, return_phase=False, preamble=None):
+    """Modulate a batch of MPDUs (bytes WITHOUT FCS) as 802.11b frames on the GPU (1000, 2000, 5500, 11000 kbps).  preamble: None = every frame behind the
+    long preamble (sora_hip_tx11b); else 0 (long) or 1 (short: 2000, 5500, 11000 kbps only), one value or one per frame (sora_hip_tx11b_pre).
+    -> (out, offsets): an int8 CUDA tensor [total,2] COMPLEX8 @44 MHz and the offsets list; frame f occupies samples offsets[f] ..
+    offsets[f+1] (gaps[f] zero samples in front of frame f, if given, included at its start).
+    phase_in: the reference's last_phase (0..3) at the start of each frame, one value or one per frame (None: 0, a fresh reference
+    process).  return_phase: also return last_phase after each frame, a list -- pass it back as phase_in to continue one reference
+    process's sequence.  A frame with an unsupported rate or length is refused before any launch."""
+    import torch
+    n, rates, lens, kinds, ns, phase_in = _tx11b_frames(mpdus, rates_kbps, phase_in, preamble)
     off = np.zeros(n + 1, np.int64); np.cumsum([(l + 3) // 4 * 4 for l in lens], out=off[1:])
     blob = np.zeros(max(int(off[-1]), 4), np.uint8)
     for f, m in enumerate(mpdus):
@@ -2177,3 +2192,137 @@ def tx11b(mpdus, rates_kbps, phase_in=None, device=0, stream=None, sync=True, ga
     if return_phase:
         return out, [int(v) for v in ooff], [int(v) for v in d_pout.cpu().numpy()]
     return out, [int(v) for v in ooff]
+
+
+# ---- the 802.11b modulation graph's bricks as stages (include/sora_hip.h: sora_hip_ppdu11b .. sora_hip_pulse_shape11b) -----------------------------
+# Records, as int32 words per stream: the spreaders' [n, 4] last_phase, is_even, reserved x 2 (sora_mod11b_state); the scrambler's [n] register; the shaper's
+# [n, 16] m_temps[0..3] as packed COMPLEX16 (sora_shaper11b_state).  Offsets and counts are int32 CUDA [streams].
+MOD11B_CHIPS_PER_BYTE = {1000: 88, 2000: 44, 5500: 16, 11000: 8}
+
+
+def ppdu11b(mpdu, off, length, rate_kbps, preamble, out, out_first, stream=None):
+    """TBB11bSrc: mpdu uint8 CUDA; off / length / rate_kbps / out_first int32 CUDA [frames]; preamble uint8 CUDA [frames] (0 long, 1 short) -> out uint8 CUDA, frame f's
+    PPDU bytes (24 or 15 + length + 4) from byte out_first[f] written in place; a frame that is not accepted gets nothing written"""
+    _check(load().sora_hip_ppdu11b(_dev_ptr(mpdu), _dev_ptr(off), _dev_ptr(length), _dev_ptr(rate_kbps), _dev_ptr(preamble), _dev_ptr(out), _dev_ptr(out_first), off.shape[0],
+                                   _stream_ptr(stream)))
+    return out
+
+
+def _mod11b(fn, x, first, n, out_first, state, out, max_n, stream):
+    _check(getattr(load(), fn)(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(out_first), _dev_ptr(state), _dev_ptr(out), first.shape[0], _max_n(n, max_n),
+                               _stream_ptr(stream)))
+    return out
+
+
+def sc741_11b(x, first, n, out_first, reg, out, max_n=None, stream=None):
+    """TSc741: n[f] bytes from byte first[f] of x (uint8 CUDA) -> out (from byte out_first[f]); reg int32 CUDA [streams] (the 7-bit register, in / out)"""
+    return _mod11b("sora_hip_sc741_11b", x, first, n, out_first, reg, out, max_n, stream)
+
+
+def dbpsk_spread11b(x, first, n, out_first, state, out, max_n=None, stream=None):
+    """TBB11bDBPSKSpread: n[f] bytes -> 88 n[f] chips, out int8 CUDA [chips, 2] from chip out_first[f]; state int32 CUDA [streams, 4] (last_phase in / out)"""
+    return _mod11b("sora_hip_dbpsk_spread11b", x, first, n, out_first, state, out, max_n, stream)
+
+
+def dqpsk_spread11b(x, first, n, out_first, state, out, max_n=None, stream=None):
+    """TBB11bDQPSKSpread: n[f] bytes -> 44 n[f] chips (as dbpsk_spread11b)"""
+    return _mod11b("sora_hip_dqpsk_spread11b", x, first, n, out_first, state, out, max_n, stream)
+
+
+def cck5_encode11b(x, first, n, out_first, state, out, max_n=None, stream=None):
+    """TCCK5Encode: n[f] bytes -> 16 n[f] chips; state: last_phase"""
+    return _mod11b("sora_hip_cck5_encode11b", x, first, n, out_first, state, out, max_n, stream)
+
+
+def cck11_encode11b(x, first, n, out_first, state, out, max_n=None, stream=None):
+    """TCCK11Encode: n[f] bytes -> 8 n[f] chips; state: last_phase and is_even"""
+    return _mod11b("sora_hip_cck11_encode11b", x, first, n, out_first, state, out, max_n, stream)
+
+
+def pulse_shape11b(x, first, n, out_first, state, out, flush=None, max_n=None, stream=None):
+    """TQuickPulseShaper: x int8 CUDA [chips, 2]; n[f] chips from chip first[f] -> out int16 CUDA [samples, 2], 4 n[f] samples from sample out_first[f] (4 (n[f] + 5) where
+    flush[f], uint8 CUDA [streams], is not 0: the brick's Flush); state int32 CUDA [streams, 16] (m_temps[0..3], in / out)"""
+    _check(load().sora_hip_pulse_shape11b(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(out_first), _opt_ptr(flush), _dev_ptr(state), _dev_ptr(out), first.shape[0],
+                                          _max_n(n, max_n), _stream_ptr(stream)))
+    return out
+
+
+class Mod11bStages:
+    """The 802.11b modulation graph composed from its stage entry points, for a batch of MPDUs (bytes WITHOUT FCS): ppdu11b -> sc741_11b -> the host's TBB11bMRSelect
+    (the header's bytes to the DBPSK stage -- behind the short preamble its six PLCP bytes to the DQPSK stage --, MPDU + FCS to the stage of the frame's rate, all on one
+    last_phase record per frame) -> pulse_shape11b with Flush -> the last burst of eight padded with zeros -> pack16to8.  The constructor refuses what tx11b refuses,
+    lays the batch out and uploads it; run() is the launches alone (up to ten) and may be repeated.  offsets: as tx11b's; state[:, 0]: last_phase after each frame."""
+
+    def __init__(self, mpdus, rates_kbps, phase_in=None, preamble=None, device=0):
+        import torch
+        n, rates, lens, kinds, ns, phase_in = _tx11b_frames(mpdus, rates_kbps, phase_in, preamble)
+        kinds = kinds or [0] * n
+        dev = torch.device("cuda", device)
+
+        def i32(v):                                                               # (offsets are unsigned 32-bit words on the device)
+            return torch.from_numpy(np.asarray(v, np.int64).astype(np.uint32).view(np.int32)).to(dev)
+
+        hb1 = np.asarray([24 if k == 0 else 9 for k in kinds], np.int64)          # header bytes through the DBPSK spreader, then through the DQPSK one
+        hb2 = np.asarray([0 if k == 0 else 6 for k in kinds], np.int64)
+        pay = np.asarray(lens, np.int64) + 4
+        cpb = np.asarray([MOD11B_CHIPS_PER_BYTE[r] for r in rates], np.int64)
+        moff = np.zeros(n + 1, np.int64); np.cumsum([(l + 3) // 4 * 4 for l in lens], out=moff[1:])
+        blob = np.zeros(max(int(moff[-1]), 4), np.uint8)
+        for f, m in enumerate(mpdus):
+            blob[moff[f]:moff[f] + lens[f]] = np.frombuffer(bytes(m), np.uint8)
+        poff = np.zeros(n + 1, np.int64); np.cumsum(hb1 + hb2 + pay, out=poff[1:])   # PPDU bytes
+        nchips = 88 * hb1 + 44 * hb2 + pay * cpb
+        coff = np.zeros(n + 1, np.int64); np.cumsum(nchips, out=coff[1:])
+        soff = np.zeros(n + 1, np.int64); np.cumsum(ns, out=soff[1:])               # samples: 4 (chips + 5) and four of padding
+        assert all(int(a) == 4 * int(b) + 24 for a, b in zip(ns, nchips))
+        if int(soff[-1]) >= 1 << 32:
+            raise SoraError(-6, "Mod11bStages: the batch's samples must stay below 2^32 (the stages' offsets are 32-bit)")
+        self.n, self.offsets = n, [int(v) for v in soff]
+        self._blob, self._moff, self._lens, self._rates = torch.from_numpy(blob).to(dev), i32(moff[:-1]), i32(lens), i32(rates)
+        self._kinds = torch.from_numpy(np.asarray(kinds, np.uint8)).to(dev)
+        self._poff, self._nppdu = i32(poff[:-1]), i32(hb1 + hb2 + pay)
+        self._reg0 = i32([0x6C if k == 0 else 0x1B for k in kinds])               # DOT11B_PLCP_{LONG,SHORT}_TX_SCRAMBLER_REGISTER
+        self._state0 = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+        if phase_in is not None:
+            self._state0[:, 0] = i32(phase_in)
+        # TBB11bMRSelect: a stream of 0 bytes leaves the record alone, so every call takes all frames and the frame's own segments carry its last_phase on
+        self._calls = [(dbpsk_spread11b, i32(poff[:-1]), i32(hb1), i32(coff[:-1]), int(hb1.max()))]
+        if hb2.any():
+            self._calls.append((dqpsk_spread11b, i32(poff[:-1] + hb1), i32(hb2), i32(coff[:-1] + 88 * hb1), 6))
+        for rate, fn in ((1000, dbpsk_spread11b), (2000, dqpsk_spread11b), (5500, cck5_encode11b), (11000, cck11_encode11b)):
+            sel = np.asarray([r == rate for r in rates])
+            if sel.any():
+                self._calls.append((fn, i32(poff[:-1] + hb1 + hb2), i32(np.where(sel, pay, 0)), i32(coff[:-1] + 88 * hb1 + 44 * hb2), int(pay[sel].max())))
+        self._coff, self._nchips, self._soff = i32(coff[:-1]), i32(nchips), i32(soff[:-1])
+        self._max_ppdu, self._max_chips = int((hb1 + hb2 + pay).max()), int(nchips.max())
+        self._flush = torch.ones(n, dtype=torch.uint8, device=dev)
+        self.ppdu = torch.zeros(int(poff[-1]), dtype=torch.uint8, device=dev)
+        self.scrambled = torch.zeros_like(self.ppdu)
+        self.reg = self._reg0.clone(); self.state = self._state0.clone()
+        self.shaper = torch.zeros((n, 16), dtype=torch.int32, device=dev)
+        self.chips = torch.zeros((int(coff[-1]), 2), dtype=torch.int8, device=dev)
+        self.wide = torch.zeros((int(soff[-1]), 2), dtype=torch.int16, device=dev)    # (the padding behind each frame's flush stays 0)
+        self.out = torch.empty((int(soff[-1]), 2), dtype=torch.int8, device=dev)
+
+    def run(self, stream=None):
+        """-> int8 CUDA [total, 2], the same as sora_amd.tx11b returns; the records start afresh with every run"""
+        self.reg.copy_(self._reg0); self.state.copy_(self._state0); self.shaper.zero_()
+        ppdu11b(self._blob, self._moff, self._lens, self._rates, self._kinds, self.ppdu, self._poff, stream)
+        sc741_11b(self.ppdu, self._poff, self._nppdu, self._poff, self.reg, self.scrambled, self._max_ppdu, stream)
+        for fn, first, cnt, out_first, max_n in self._calls:
+            fn(self.scrambled, first, cnt, out_first, self.state, self.chips, max_n, stream)
+        pulse_shape11b(self.chips, self._coff, self._nchips, self._soff, self.shaper, self.wide, self._flush, self._max_chips, stream)
+        _check(load().sora_hip_pack16to8(_dev_ptr(self.wide), _dev_ptr(self.out), self.wide.shape[0], _stream_ptr(stream)))
+        return self.out
+
+
+def mod11b_by_stages(mpdus, rates_kbps, phase_in=None, preamble=None, device=0, sync=True):
+    """The 802.11b modulation graph composed from its stage entry points (Mod11bStages) for a batch of MPDUs (bytes WITHOUT FCS): the host does TBB11bMRSelect's
+    routing for both preamble kinds and pads the last burst of TPackSample16to8.
+    -> (out, offsets, phase_out): what sora_amd.tx11b(mpdus, rates_kbps, phase_in, return_phase=True, preamble=preamble) returns, and it refuses what tx11b refuses,
+    before any launch.  A demonstration of the stages, up to ten launches and every intermediate through HBM: not a fast path (that is tx11b)."""
+    plan = Mod11bStages(mpdus, rates_kbps, phase_in, preamble, device)
+    out = plan.run()
+    if sync:
+        _check(load().sora_hip_stream_synchronize(_stream_ptr(None)))
+    return out, plan.offsets, [int(v) for v in plan.state[:, 0].cpu().numpy()]

@@ -308,6 +308,18 @@ __host__ __device__ inline bool tx11b_plan(uint32_t len, uint32_t rate_kbps, Tx1
     return true;
 }
 __global__ void k_tx11b(Tx11bArgs A);
+
+// ---- the 802.11b modulation graph's bricks as stages (k_mod11b.hip): a workgroup per stream, in passes of kMod11bT input units (bytes; chips for the shaper)
+constexpr int kMod11bT = 1024;
+__global__ void k_mod11b_ppdu(const uint8_t* mpdu, const uint32_t* off, const uint32_t* len, const uint32_t* rate, const uint8_t* kind, uint8_t* out, const uint32_t* out_first,
+                              const uint32_t* crc, const uint32_t* crcz);
+__global__ void k_mod11b_sc741(const uint8_t* in, uint8_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, uint32_t* reg, uint32_t max_n);
+__global__ void k_mod11b_dbpsk(const uint8_t* in, uint16_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, uint32_t* state, uint32_t max_n);
+__global__ void k_mod11b_dqpsk(const uint8_t* in, uint16_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, uint32_t* state, uint32_t max_n);
+__global__ void k_mod11b_cck5(const uint8_t* in, uint16_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, uint32_t* state, uint32_t max_n);
+__global__ void k_mod11b_cck11(const uint8_t* in, uint16_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, uint32_t* state, uint32_t max_n);
+__global__ void k_mod11b_shape(const uint16_t* in, uint32_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, const uint8_t* flush, uint32_t* state,
+                               uint32_t max_n);
 __global__ void k_ingest(const uint8_t* raw, uint32_t* out, uint64_t m0, uint64_t n_out, unsigned flags);
 __global__ void k_ingest_tile(const uint8_t* raw, uint32_t* out, unsigned flags, uint32_t tiles);
 __global__ void k_soft_pack3(const uint8_t* soft8, const uint32_t* off8, const uint32_t* nsoft, const uint16_t* flen, const uint32_t* out_off,

@@ -2319,6 +2319,70 @@ int sora_hip_tx11b_pre(const uint8_t* d_mpdu, const uint32_t* d_off, const uint3
     return tx11b_launch("sora_hip_tx11b_pre", d_mpdu, d_off, d_len, d_rate_kbps, d_preamble, d_phase_in, d_phase_out, nframes, d_out, d_out_off, stream);
 }
 
+// ---- the 802.11b modulation graph's bricks as stages (k_mod11b.hip): a workgroup per stream
+#define MOD11B_ENTRY(who, nullcond, count) \
+    if (nullcond) return fail(SORA_ERR_INVALID_PARAM, who ": null pointer"); \
+    if ((count) == 0) return SORA_OK;                       /* (nothing to launch: true with or without a device) */ \
+    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path"); \
+    if ((count) >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, who ": too many streams for one call");
+static_assert(sizeof(sora_mod11b_state) == 16 && sizeof(sora_shaper11b_state) == 64, "the 802.11b modulation stage records are 32-bit words");
+constexpr size_t kMod11bMaxN = (size_t)1 << 24;             // 88 chips a byte: a stream's output offsets stay 32-bit
+
+int sora_hip_ppdu11b(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_preamble, uint8_t* d_out,
+                     const uint32_t* d_out_first, size_t nframes, void* stream)
+{
+    MOD11B_ENTRY("sora_hip_ppdu11b", !d_mpdu || !d_off || !d_len || !d_rate_kbps || !d_preamble || !d_out || !d_out_first, nframes)
+    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    hipLaunchKernelGGL(k_mod11b_ppdu, dim3((unsigned)nframes), dim3(256), 0, (hipStream_t)stream, d_mpdu, d_off, d_len, d_rate_kbps, d_preamble, d_out, d_out_first,
+                       D->T.crc, D->T.crcz);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+int sora_hip_sc741_11b(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, uint32_t* d_reg, uint8_t* d_out,
+                       size_t nstreams, size_t max_n, void* stream)
+{
+    MOD11B_ENTRY("sora_hip_sc741_11b", !d_in || !d_first || !d_n || !d_out_first || !d_reg || !d_out, nstreams)
+    if (max_n == 0) return SORA_OK;
+    if (max_n > kMod11bMaxN) return fail(SORA_ERR_CAPACITY, "sora_hip_sc741_11b: max_n is too large for one call");
+    hipLaunchKernelGGL(k_mod11b_sc741, dim3((unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, d_in, d_out, d_first, d_n, d_out_first, d_reg, (uint32_t)max_n);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+
+#define MOD11B_SPREAD(name, kernel) \
+    int name(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_mod11b_state* d_state, int8_t* d_out, size_t nstreams, \
+             size_t max_n, void* stream) \
+    { \
+        MOD11B_ENTRY(#name, !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out, nstreams) \
+        if (max_n == 0) return SORA_OK; \
+        if (max_n > kMod11bMaxN) return fail(SORA_ERR_CAPACITY, #name ": max_n is too large for one call"); \
+        if ((uintptr_t)d_out & 1) return fail(SORA_ERR_INVALID_PARAM, #name ": d_out must be aligned to a COMPLEX8"); \
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, d_in, reinterpret_cast<uint16_t*>(d_out), d_first, d_n, d_out_first, \
+                           reinterpret_cast<uint32_t*>(d_state), (uint32_t)max_n); \
+        HIPCHK(hipGetLastError()); \
+        return SORA_OK; \
+    }
+MOD11B_SPREAD(sora_hip_dbpsk_spread11b, k_mod11b_dbpsk)
+MOD11B_SPREAD(sora_hip_dqpsk_spread11b, k_mod11b_dqpsk)
+MOD11B_SPREAD(sora_hip_cck5_encode11b, k_mod11b_cck5)
+MOD11B_SPREAD(sora_hip_cck11_encode11b, k_mod11b_cck11)
+#undef MOD11B_SPREAD
+
+int sora_hip_pulse_shape11b(const int8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const uint8_t* d_flush,
+                            sora_shaper11b_state* d_state, sora_complex16* d_out, size_t nstreams, size_t max_n, void* stream)
+{
+    MOD11B_ENTRY("sora_hip_pulse_shape11b", !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out, nstreams)
+    if (max_n == 0 && !d_flush) return SORA_OK;
+    if (max_n > kMod11bMaxN) return fail(SORA_ERR_CAPACITY, "sora_hip_pulse_shape11b: max_n is too large for one call");
+    if (((uintptr_t)d_in & 1) || ((uintptr_t)d_out & 3)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_pulse_shape11b: d_in and d_out must be aligned to their elements");
+    hipLaunchKernelGGL(k_mod11b_shape, dim3((unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint16_t*>(d_in), reinterpret_cast<uint32_t*>(d_out),
+                       d_first, d_n, d_out_first, d_flush, reinterpret_cast<uint32_t*>(d_state), (uint32_t)max_n);
+    HIPCHK(hipGetLastError());
+    return SORA_OK;
+}
+#undef MOD11B_ENTRY
+
 // ---- capture ingest
 size_t sora_hip_ingest_count(size_t raw_bytes, unsigned flags)
 {
