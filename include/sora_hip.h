@@ -157,6 +157,14 @@ int  sora_rx_process_dump(sora_rx_t* rx, const void* h_dump, size_t dump_bytes, 
  *   Returns the previous mode; a negative argument only queries. */
 int  sora_rx_set_stream_mode(sora_rx_t* rx, int enable);
 int  sora_rx_stream_consumed(sora_rx_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps);
+/* Diagnostic: a copy of the continuation record of capture `capture` (index into the call's captures) as the handle's most recent call left it,
+ * after that call has completed: *n_words = 64 words, the graph's carrier-sense state at the capture's last resume point (words 0-15 sample_his in
+ * time order, already >> 2; 16-19 / 20-23 / 24-27 the auto-correlation (re, im) and energy windows, oldest first; 28-30 their sums; 31 sense_count;
+ * 32 high_count; 33 peak_corr; 34 peak_index; 35 the DC estimator's countdown; 36-37 its sums; 38-39 the DC estimate; 40 the resume point; 41 a
+ * magic word once a record exists; 42 the frames reported in front of the point; the rest 0).  tests/test_gpu_scan_sense.py holds every word to the
+ * reference graph's restatement.  SORA_ERR_INVALID_PARAM when stream mode is off or the call has no such capture, SORA_ERR_CAPACITY (with *n_words
+ * set) when cap_words is too small.  Read-only. */
+int  sora_rx_stream_record_of(sora_rx_t* rx, int ticket, uint32_t capture, uint32_t* h_words, size_t cap_words, size_t* n_words);
 
 /* TBB11aFrameSink's frame buffer + CF_Error per frame: copies results of the last process call to the host.
  * h_mpdu may be NULL (descriptors only).  *nout = rows written. Frames appear in (capture, time) order. */

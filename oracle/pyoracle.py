@@ -21,6 +21,11 @@ E_PLCP_HEADER_FAIL = 0x80000005
 E_CRC32_FAIL = 0x80000006
 CR_12, CR_23, CR_34 = 0, 1, 2
 RATES = (6000, 9000, 12000, 18000, 24000, 36000, 48000, 54000)
+# so_oracle.h: SO_CS_* in order, SO_CS_RECORD_WORDS, SO_CS_RECORD_MAGIC
+CS_COUNTERS = ("true_test", "est_lock", "est_no_lock", "est_lock_late_peak", "lock_dropped", "lock_dropped_dc_update", "frame_detected",
+               "peak_raised", "dc_update", "timeout_raised", "true_test_timeout_pending")
+CS_RECORD_WORDS = 64
+CS_RECORD_MAGIC = 0x534F5241
 
 
 def rate_params(kbps):
@@ -162,6 +167,26 @@ class Oracle:
             ctx, eq, trk, soft, dec = keep
             return out, {"ctx": ctx, "eq": eq[:tr.n_syms], "tracked": trk[:tr.n_syms], "soft": soft[:tr.n_soft], "decoded": dec}
         return out
+
+    # ---- carrier sense: branch counters and the state at every resume point (so_oracle.h)
+    def cs_counters(self, enable):
+        """Zero the carrier-sense branch counters and switch them on or off (off is the default: nothing is counted)."""
+        self.L.so_cs_counters(1 if enable else 0)
+
+    def cs_counters_read(self):
+        """-> {name: count} over every rx_capture / cs_trace call since cs_counters(True)"""
+        v = np.zeros(len(CS_COUNTERS), np.uint64); self.L.so_cs_counters_read(_P(v))
+        return {n: int(x) for n, x in zip(CS_COUNTERS, v)}
+
+    def cs_trace(self, iq, rate_mhz=40):
+        """-> (pos20 uint32 [n], records uint32 [n, 64]): every resume point of the capture, its 20 MHz-rate position and the carrier-sense state
+        there in the layout of the receive kernel's continuation record."""
+        iq = np.ascontiguousarray(iq, np.int16).reshape(-1, 2)
+        cap = len(iq) // (14 if rate_mhz == 20 else 28) + 2
+        pos = np.zeros(cap, np.uint32); rec = np.zeros((cap, CS_RECORD_WORDS), np.uint32)
+        n = self.L.so_rx11a_cs_trace(_P(iq), len(iq), rate_mhz, _P(pos), _P(rec), cap)
+        assert 0 <= n <= cap
+        return pos[:n], rec[:n]
 
     def demap11n(self, nbpsc, sym64):
         a = np.ascontiguousarray(sym64, np.int16).reshape(64, 2); o = np.zeros(52 * nbpsc, np.uint8)

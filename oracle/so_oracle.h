@@ -112,6 +112,37 @@ typedef struct {             /* optional intermediates of the FIRST decoded fram
 int so_rx11a_capture(const so_c16* iq, uint32_t nsamples, int sample_rate_mhz,
                      so_frame_result* res, int max_res, uint8_t* mpdu_buf, uint32_t mpdu_cap, so_trace* trace);
 
+/* Optional counters of the carrier-sense restatement's branches (TDCRemoveEx -> TCCA11a -> TDCEstimator, cca.hpp:126-437, dc.hpp:92-166), over every
+ * so_rx11a_capture / so_rx11a_cs_trace call made while they are enabled.  so_cs_counters(1) zeroes and enables them, so_cs_counters(0) zeroes and
+ * disables them (the default: nothing is counted).  Process-wide, not thread-safe. */
+enum {
+    SO_CS_TRUE_TEST = 0,               /* carrier tests that were true (cca.hpp:400) */
+    SO_CS_EST_LOCK,                    /* establish_sync calls that lock */
+    SO_CS_EST_NO_LOCK,                 /* ... that do not (peak_corr <= sum_corr >> 3) */
+    SO_CS_EST_LOCK_LATE_PEAK,          /* locks with peak_index > 3 */
+    SO_CS_LOCK_DROPPED,                /* check_sync failures with high_count <= 8 */
+    SO_CS_LOCK_DROPPED_DC_UPDATE,      /* ... on a burst with dc_update_cnt == 0 */
+    SO_CS_FRAME_DETECTED,              /* check_sync failures with high_count > 8 */
+    SO_CS_PEAK_RAISED,                 /* check_sync raising peak_corr */
+    SO_CS_DC_UPDATE,                   /* TDCEstimator updates */
+    SO_CS_TIMEOUT_RAISED,              /* E_CS_TIMEOUT raised (once per time-out) */
+    SO_CS_TRUE_TEST_TIMEOUT_PENDING,   /* true carrier tests between a time-out being raised and the end of its source call */
+    SO_CS_NCOUNTERS
+};
+void so_cs_counters(int enable);
+void so_cs_counters_read(uint64_t out[SO_CS_NCOUNTERS]);
+
+/* The carrier-sense state at every RESUME POINT of a capture, in the layout of the receive kernel's continuation record.  A resume point: a burst is
+ * about to be pushed at a 20 MHz-rate position that is a multiple of 14 (140 at sample_rate_mhz == 44) while cca_detected == 0, sync_state is
+ * no_energy, auto_count == 0 and error_code == E_SUCCESS; and the capture's end, when the walk ends there in that condition with nothing queued.
+ * Record words: 0-15 sample_his in time order (packed re | im << 16, already >> 2); 16-19 / 20-23 / 24-27 the windows of the auto-correlation
+ * (re, im) and the energy, oldest first; 28-30 their accumulators; 31 sense_count; 32 high_count; 33 peak_corr; 34 peak_index; 35 dc_update_cnt;
+ * 36-37 sum_dc; 38-39 direct_current (sign-extended); 40 the position in input samples; 41 SO_CS_RECORD_MAGIC; 42 events reported in front of the
+ * point; 43-63 zero.  pos20[i] / records[i][64] are filled for the first max_points points; returns the number of points found. */
+#define SO_CS_RECORD_WORDS 64
+#define SO_CS_RECORD_MAGIC 0x534F5241u
+int so_rx11a_cs_trace(const so_c16* iq, uint32_t nsamples, int sample_rate_mhz, uint32_t* pos20, uint32_t* records, int max_points);
+
 /* 802.11b receive graph (so_rx11b.c): one 44 MHz capture; end_sample = source position (44 MHz samples) at which the
  * harness sees the event, rate_kbps/length/crc32 as the reference's CF_11bRxVector holds them (crc32: 3 FCS bytes + 1 stale). */
 int so_rx11b_capture(const so_c16* iq, uint32_t nsamples, so_frame_result* res, int max_res, uint8_t* mpdu_buf, uint32_t mpdu_cap);

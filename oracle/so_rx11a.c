@@ -429,7 +429,15 @@ typedef struct {
     so_trace* trace; int traced;
     uint32_t sym_idx;
     uint32_t frame_crc;
+    uint32_t nframes;                             /* events reported so far, the ones past max_res included */
 } rx_t;
+
+/* optional counters of carrier_sense()'s branches (so_cs_counters): NULL = not asked for, nothing is counted */
+static uint64_t g_cs_cnt[SO_CS_NCOUNTERS];
+static uint64_t* g_cnt = NULL;
+#define CS_COUNT(i) do { if (g_cnt) g_cnt[i]++; } while (0)
+void so_cs_counters(int enable) { memset(g_cs_cnt, 0, sizeof(g_cs_cnt)); g_cnt = enable ? g_cs_cnt : NULL; }
+void so_cs_counters_read(uint64_t out[SO_CS_NCOUNTERS]) { memcpy(out, g_cs_cnt, sizeof(g_cs_cnt)); }
 
 static void cs_brick_reset(cs_state* s)          /* TCCA11a::__init (cca.hpp:279-295) + TDCEstimator::__init */
 {
@@ -463,6 +471,7 @@ static void carrier_sense(rx_t* rx, const vcs_t* in)
     cs_state* s = &rx->cs;
     const so_c16* pat = so_sts_pattern();
     vcs_t pi;
+    int dropped = 0;
     for (int e = 0; e < 4; e++) pi.v[e] = so_c(so_w16((int32_t)in->v[e].re - rx->dc[e].re), so_w16((int32_t)in->v[e].im - rx->dc[e].im));  /* rep_sub (dc.hpp:68) */
 
     if (!s->sync_high) {
@@ -485,6 +494,8 @@ static void carrier_sense(rx_t* rx, const vcs_t* in)
         if (iEnergy > (int)rx->cca_pwr_threshold && iAuto >= iEnergy - (iEnergy >> 3)) {
             s->auto_count++;
             s->sense_count = 0;
+            CS_COUNT(SO_CS_TRUE_TEST);
+            if (rx->error_code == SO_E_CS_TIMEOUT) CS_COUNT(SO_CS_TRUE_TEST_TIMEOUT_PENDING);
             if (s->auto_count >= 4) {
                 /* establish_sync (cca.hpp:220-243) */
                 int sindex = s->his_idx, sum_corr = 0;
@@ -497,8 +508,9 @@ static void carrier_sense(rx_t* rx, const vcs_t* in)
                 if (s->peak_corr > (sum_corr >> 3)) {
                     s->sync_high = 1;
                     s->high_count = 0;
-                    if (s->peak_index > 3) { s->high_count = (uint32_t)s->peak_index / 4; s->peak_index &= 3; }
-                }
+                    CS_COUNT(SO_CS_EST_LOCK);
+                    if (s->peak_index > 3) { s->high_count = (uint32_t)s->peak_index / 4; s->peak_index &= 3; CS_COUNT(SO_CS_EST_LOCK_LATE_PEAK); }
+                } else CS_COUNT(SO_CS_EST_NO_LOCK);
             }
         } else {
             s->auto_count = 0;
@@ -511,10 +523,10 @@ static void carrier_sense(rx_t* rx, const vcs_t* in)
             /* check_sync (cca.hpp:245-265) */
             int corr = cross_corr(s, s->his_idx, pat + 16 * s->peak_index);
             int ok;
-            if (corr < (s->peak_corr >> 1)) ok = 0; else { if (corr > s->peak_corr) s->peak_corr = corr; ok = 1; }
+            if (corr < (s->peak_corr >> 1)) ok = 0; else { if (corr > s->peak_corr) { s->peak_corr = corr; CS_COUNT(SO_CS_PEAK_RAISED); } ok = 1; }
             if (!ok) {
-                if (s->high_count > 8) { rx->cca_detected = 1; rx->frame_start = rx->pos20 + 4; }
-                else { s->sync_high = 0; s->sense_count = 0; }
+                if (s->high_count > 8) { rx->cca_detected = 1; rx->frame_start = rx->pos20 + 4; CS_COUNT(SO_CS_FRAME_DETECTED); }
+                else { s->sync_high = 0; s->sense_count = 0; dropped = 1; CS_COUNT(SO_CS_LOCK_DROPPED); }
             }
         }
     }
@@ -524,6 +536,8 @@ static void carrier_sense(rx_t* rx, const vcs_t* in)
         for (int e = 0; e < 4; e++) { hr = so_w16((int32_t)hr + (pi.v[e].re >> 5)); hi = so_w16((int32_t)hi + (pi.v[e].im >> 5)); }
         for (int e = 0; e < 4; e++) { s->sum_dc[e].re = so_w16((int32_t)s->sum_dc[e].re + hr); s->sum_dc[e].im = so_w16((int32_t)s->sum_dc[e].im + hi); }
         if (s->dc_update_cnt == 0) {
+            CS_COUNT(SO_CS_DC_UPDATE);
+            if (dropped) CS_COUNT(SO_CS_LOCK_DROPPED_DC_UPDATE);
             for (int e = 0; e < 4; e++) {
                 rx->dc[e].re = so_w16((int32_t)rx->dc[e].re + (s->sum_dc[e].re >> 2));
                 rx->dc[e].im = so_w16((int32_t)rx->dc[e].im + (s->sum_dc[e].im >> 2));
@@ -533,7 +547,40 @@ static void carrier_sense(rx_t* rx, const vcs_t* in)
         s->dc_update_cnt--;
     }
     /* cca.hpp:433-437 */
-    if (s->sense_count >= 84 && !s->sync_high) rx->error_code = SO_E_CS_TIMEOUT;
+    if (s->sense_count >= 84 && !s->sync_high) {
+        if (rx->error_code != SO_E_CS_TIMEOUT) CS_COUNT(SO_CS_TIMEOUT_RAISED);
+        rx->error_code = SO_E_CS_TIMEOUT;
+    }
+}
+
+/* The carrier-sense state as the receive kernel's continuation record lays it out (so_oracle.h: so_rx11a_cs_trace) */
+typedef struct { uint32_t* pos20; uint32_t* rec; int cap, n; } cs_sink;
+static uint32_t pack16(so_c16 a) { return ((uint32_t)(uint16_t)a.re) | ((uint32_t)(uint16_t)a.im << 16); }
+static int cs_plain(const rx_t* rx)
+{
+    return !rx->cca_detected && !rx->cs.sync_high && rx->cs.auto_count == 0 && rx->error_code == SO_E_SUCCESS;
+}
+static void cs_record(const rx_t* rx, cs_sink* k, uint32_t pos20, uint32_t raw_pos)
+{
+    if (k->n < k->cap) {
+        const cs_state* s = &rx->cs;
+        uint32_t* w = k->rec + (size_t)SO_CS_RECORD_WORDS * k->n;
+        memset(w, 0, SO_CS_RECORD_WORDS * sizeof(uint32_t));
+        for (int g = 0; g < 4; g++) {
+            for (int e = 0; e < 4; e++) w[4 * g + e] = pack16(s->his[(s->his_idx + g) & 3].v[e]);
+            w[16 + g] = (uint32_t)s->ac_re.e[(s->ac_re.idx + g) & 3];
+            w[20 + g] = (uint32_t)s->ac_im.e[(s->ac_im.idx + g) & 3];
+            w[24 + g] = (uint32_t)s->energy.e[(s->energy.idx + g) & 3];
+        }
+        w[28] = (uint32_t)s->ac_re.reg; w[29] = (uint32_t)s->ac_im.reg; w[30] = (uint32_t)s->energy.reg;
+        w[31] = s->sense_count; w[32] = s->high_count; w[33] = (uint32_t)s->peak_corr; w[34] = (uint32_t)s->peak_index;
+        w[35] = s->dc_update_cnt;
+        w[36] = (uint32_t)(int32_t)s->sum_dc[0].re; w[37] = (uint32_t)(int32_t)s->sum_dc[0].im;
+        w[38] = (uint32_t)(int32_t)rx->dc[0].re;    w[39] = (uint32_t)(int32_t)rx->dc[0].im;
+        w[40] = raw_pos; w[41] = SO_CS_RECORD_MAGIC; w[42] = rx->nframes;
+        k->pos20[k->n] = pos20;
+    }
+    k->n++;
 }
 
 static void soft_push(rx_t* rx, const uint8_t* p, uint32_t n)
@@ -627,6 +674,7 @@ static void frame_reset(rx_t* rx)                /* ssrc->Flush(); BB11aDemodCtx
 
 static void emit_result(rx_t* rx, uint32_t err)
 {
+    rx->nframes++;
     if (rx->nres >= rx->max_res) return;
     so_frame_result* r = &rx->res[rx->nres++];
     memset(r, 0, sizeof(*r));
@@ -640,8 +688,8 @@ static void emit_result(rx_t* rx, uint32_t err)
     if (rx->trace) rx->traced = 1;
 }
 
-int so_rx11a_capture(const so_c16* iq, uint32_t nsamples, int sample_rate_mhz,
-                     so_frame_result* res, int max_res, uint8_t* mpdu_buf, uint32_t mpdu_cap, so_trace* trace)
+static int rx11a_run(const so_c16* iq, uint32_t nsamples, int sample_rate_mhz,
+                     so_frame_result* res, int max_res, uint8_t* mpdu_buf, uint32_t mpdu_cap, so_trace* trace, cs_sink* sink)
 {
     so_init();
     rx_t* rx = (rx_t*)calloc(1, sizeof(rx_t));
@@ -665,6 +713,7 @@ int so_rx11a_capture(const so_c16* iq, uint32_t nsamples, int sample_rate_mhz,
     const uint32_t APP  = 28 / (2 / STR);                                  /* 28 raw  | 14 */
     const uint32_t BUR  = 8 / (2 / STR);                                   /* 8 raw   | 4  */
     const uint32_t QSZ  = 56 / (2 / STR);
+    const uint32_t GRID = keep_queue ? 140 : 14;                           /* resume points: the source-call grid; TDownSample44_40's period at 44 */
     so_c16 q[56]; memset(q, 0, sizeof(q));
     uint32_t w_cnt = 0, r_cnt = 0;
     uint32_t q_base = 0;                                                   /* source index (queue units) of q[0] */
@@ -687,6 +736,7 @@ int so_rx11a_capture(const so_c16* iq, uint32_t nsamples, int sample_rate_mhz,
                 vcs_t v;
                 for (uint32_t e = 0; e < 4; e++) v.v[e] = q[r_cnt + e * STR];
                 rx->pos20 = (q_base + r_cnt) / STR;
+                if (sink && rx->pos20 % GRID == 0 && cs_plain(rx)) cs_record(rx, sink, rx->pos20, q_base + r_cnt);
                 r_cnt += BUR;
                 consumed = (q_base + r_cnt) / STR;                         /* before the drained queue forgets its extent */
                 if (r_cnt == w_cnt) r_cnt = w_cnt = 0;
@@ -709,9 +759,25 @@ int so_rx11a_capture(const so_c16* iq, uint32_t nsamples, int sample_rate_mhz,
             }
         }
     }
+    /* the capture's end is a resume point too when the walk ends there, nothing queued, in plain carrier sense */
+    if (sink && w_cnt == r_cnt && src == nsamples && nsamples % STR == 0 && (nsamples / STR) % GRID == 0 && cs_plain(rx))
+        cs_record(rx, sink, nsamples / STR, nsamples);
     int n = rx->nres;
     free(rx->soft); free(rx);
     return n;
+}
+
+int so_rx11a_capture(const so_c16* iq, uint32_t nsamples, int sample_rate_mhz,
+                     so_frame_result* res, int max_res, uint8_t* mpdu_buf, uint32_t mpdu_cap, so_trace* trace)
+{
+    return rx11a_run(iq, nsamples, sample_rate_mhz, res, max_res, mpdu_buf, mpdu_cap, trace, NULL);
+}
+
+int so_rx11a_cs_trace(const so_c16* iq, uint32_t nsamples, int sample_rate_mhz, uint32_t* pos20, uint32_t* records, int max_points)
+{
+    cs_sink k = { pos20, records, max_points, 0 };
+    rx11a_run(iq, nsamples, sample_rate_mhz, NULL, 0, NULL, 0, NULL, &k);
+    return k.n;
 }
 
 /* ------------------------------------------------------------------ dump de-framing (brickutil.h:20-58) */

@@ -61,7 +61,8 @@ class Ht40Found(ctypes.Structure):                      # sora_ht40_found: one r
 
 EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count", "sora_hip_malloc", "sora_hip_free",
            "sora_hip_memcpy_h2d", "sora_hip_memcpy_d2h", "sora_hip_memcpy_d2d", "sora_hip_stream_synchronize", "sora_rx_create", "sora_rx_destroy", "sora_rx_reset",
-           "sora_rx_flush", "sora_rx_stream", "sora_rx_process_dev", "sora_rx_process_dump", "sora_rx_set_stream_mode", "sora_rx_stream_consumed", "sora_rx_process", "sora_rx_results",
+           "sora_rx_flush", "sora_rx_stream", "sora_rx_process_dev", "sora_rx_process_dump", "sora_rx_set_stream_mode", "sora_rx_stream_consumed",
+           "sora_rx_stream_record_of", "sora_rx_process", "sora_rx_results",
            "sora_rx_results_dev", "sora_rx_ticket", "sora_rx_wait", "sora_rx_wait_any", "sora_rx_results_of", "sora_rx_results_dev_of", "sora_rx_stream_of",
            "sora_rx_mpdu_bytes", "sora_rx_deliver_async", "sora_hip_host_alloc", "sora_hip_host_free", "sora_rx_set_profiling", "sora_rx_kernel_times", "sora_rx_kernel_name",
                       "sora_rx_set_depth", "sora_rx_set_fused", "sora_rx_set_trellis", "sora_rx_trellis", "sora_rx_window_stats", "sora_rx_set_front", "sora_rx_front",
@@ -319,6 +320,7 @@ def load(build_if_missing=True):
     L.sora_ht40_process_captures_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
     L.sora_ht40_soft_of.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.sora_ht40_found_of.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    L.sora_rx_stream_record_of.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     # what the four receive handles share (include/sora_hip.h: tickets, calls in flight, stream continuation)
     vp = ctypes.c_void_p
     shared = [("_destroy", [vp], None), ("_stream", [vp], vp), ("_ticket", [vp], ctypes.c_int), ("_wait", [vp, ctypes.c_int], ctypes.c_int),
@@ -539,6 +541,12 @@ class Rx(_Handle):
 
     def front(self):
         return int(self._L.sora_rx_front(self._h))
+
+    def stream_record_of(self, ticket, capture):
+        """sora_rx_stream_record_of: the 64 words of capture `capture`'s continuation record after the most recent call (a diagnostic; stream mode only)"""
+        out = np.zeros(64, np.uint32); n = ctypes.c_size_t(0)
+        _check(self._L.sora_rx_stream_record_of(self._h, int(ticket), int(capture), out.ctypes.data, out.size, ctypes.byref(n)))
+        return out[:n.value]
 
     def set_ordered(self, on=-1):
         """1: calls in flight complete in submission order (a call's trellis kernel starts behind the previous call's); returns the previous setting"""

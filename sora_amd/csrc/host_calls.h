@@ -143,6 +143,20 @@ struct StreamRecords {
         if (ncaps) HIPCHK(hipMemcpy(h_consumed, d_consumed, 4 * ncaps, hipMemcpyDeviceToHost));
         return SORA_OK;
     }
+    // *_stream_record_of: a copy of capture `capture`'s continuation record as call c (its ticket's; latest: the handle's most recent call) left it
+    template <typename C> int record_of(const char* who, int device, const C* c, bool latest, uint32_t capture, uint32_t* out, size_t cap_words, size_t* n_words) const
+    {
+        *n_words = 0;
+        if (!on) return fail_at(SORA_ERR_INVALID_PARAM, who, "the handle is not in stream mode");
+        if (!c || !latest) return fail_at(SORA_ERR_INVALID_PARAM, who, "only the most recent call's records exist");
+        if (capture >= c->ncaps) return fail_at(SORA_ERR_INVALID_PARAM, who, "no such capture in this call");
+        *n_words = words;
+        if (cap_words < words) return fail_at(SORA_ERR_CAPACITY, who, "output buffer too small");
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(out, d_cont + (size_t)capture * words, 4 * (size_t)words, hipMemcpyDeviceToHost));
+        return SORA_OK;
+    }
 };
 
 // *_create of a handle configured by a sora_rx_cfg whose graph takes rate_mhz samples: the checks, then the device is current

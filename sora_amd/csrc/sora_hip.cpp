@@ -1318,6 +1318,14 @@ int sora_rx_stream_consumed(sora_rx_t* rx, int ticket, uint32_t* h_consumed, siz
     return rx->records.consumed("sora_rx_stream_consumed", rx->cfg.device, call_find(rx->pipes, sora_rx::kMaxDepth, ticket), ticket == rx->seq, h_consumed, ncaps);
 }
 
+// Diagnostic (tests): the continuation record k_scan left for one capture of the most recent call (kernels.h: kContWords words; k_scan.hip: cont_store has the layout)
+int sora_rx_stream_record_of(sora_rx_t* rx, int ticket, uint32_t capture, uint32_t* h_words, size_t cap_words, size_t* n_words)
+{
+    if (!rx || !n_words || (!h_words && cap_words)) return fail(SORA_ERR_INVALID_PARAM, "sora_rx_stream_record_of: null argument");
+    return rx->records.record_of("sora_rx_stream_record_of", rx->cfg.device, call_find(rx->pipes, sora_rx::kMaxDepth, ticket), ticket == rx->seq, capture, h_words,
+                                 cap_words, n_words);
+}
+
 // The kernels of the next call on pipeline p (the handle's settings, its capacity in flight, what else the chip is doing).  k_pipe's finishing kernel leaves a note when a
 // wait inside that launch gave up (the call's rows are right all the same); the handle then keeps to the three-kernel chain for the next kPipeBackoffCalls calls.
 static void choose_kernels(sora_rx* rx, RxPipe* p)

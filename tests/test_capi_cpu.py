@@ -191,3 +191,20 @@ def test_ht40_found_read_out_is_declared_typed_and_refuses_a_null_handle(lib):
     assert lib.sora_ht40_found_of(None, 1, 0, None, 0, None) == -1
     assert lib.sora_ht40_found_of(ctypes.c_void_p(16), 1, 0, None, 4, ctypes.byref(nf)) == -1             # a null buffer with room for four records
     assert callable(getattr(sora_amd.RxHt40, "found", None))
+
+
+def test_stream_record_read_out_is_declared_typed_and_refuses_a_null_handle(lib):
+    """sora_rx_stream_record_of (the diagnostic tests/test_gpu_scan_sense.py reads k_scan's continuation records with): in the header, exported, typed by the
+    binding, refused for a null handle, a null count or a null buffer with room before any device work, and Rx carries the method."""
+    import sora_amd
+    from sora_amd import capi
+    n = "sora_rx_stream_record_of"
+    assert n in declared_functions() and n in capi.EXPORTS and hasattr(lib, n)
+    assert len(lib.sora_rx_stream_record_of.argtypes) == 6
+    lib.sora_hip_table_digest(None, None)                               # leaves a message that names no receive handle
+    nw = ctypes.c_size_t(5)
+    assert lib.sora_rx_stream_record_of(None, 1, 0, None, 0, ctypes.byref(nw)) == -1      # SORA_ERR_INVALID_PARAM
+    assert b"sora_rx_stream_record_of" in lib.sora_hip_last_error()
+    assert lib.sora_rx_stream_record_of(None, 1, 0, None, 0, None) == -1
+    assert lib.sora_rx_stream_record_of(ctypes.c_void_p(16), 1, 0, None, 64, ctypes.byref(nw)) == -1      # a null buffer with room for a record
+    assert callable(getattr(sora_amd.Rx, "stream_record_of", None))
