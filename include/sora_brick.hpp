@@ -686,6 +686,132 @@ public:
 };
 
 // ------------------------------------------------------------------------------------------------
+// The bricks that complete the 802.11n receive graph (kernel/bb/demod11/fb11ndemod_config.hpp:166-264), each where its SSE brick sits.  The bricks with NSTREAM = 2 ports
+// carry the two chains / spatial streams as the two halves of one burst, as THip11nMimoComp does.  d_tab: 16 bytes of device memory, the adapter's own (its tables).
+// T11nDataSymbol (PHY_11n.hpp:288-356): IPORT COMPLEX16 x 2 x 80 N (chain 0's N symbols, then chain 1's) -> OPORT COMPLEX16 x 2 x 64 N.  remain_symbols and the Flush at
+// zero stay the host's.
+template <size_t N, class T_CTX, class T_NEXT>
+class THip11nDataSymbol : public THip11bStage<sora_complex16, 160 * N, sora_complex16, 128 * N, T_CTX, T_NEXT> {
+    using Base = THip11bStage<sora_complex16, 160 * N, sora_complex16, 128 * N, T_CTX, T_NEXT>;
+public:
+    THip11nDataSymbol(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* d_tab, void* stream = nullptr) : Base(ctx, next, d_out, d_tab, (uint32_t)N, stream) {}
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        return this->run(ipin, [](const sora_complex16* in, const uint32_t* f, const uint32_t* n, const uint32_t* of, const uint32_t*, sora_complex16* out, void* st) {
+            return sora_hip_data_symbol11n(in, in + 80 * N, f, n, of, out, out + 64 * N, 1, N, st); });
+    }
+};
+// TStreamJoin<2, 52 N_BPSC> -> TStreamConcat<2, max(N_BPSC / 2, 1)> (stdbrick.hpp:640-720): IPORT uchar x 2 x 52 N_BPSC N (stream 0's N symbols, then stream 1's) ->
+// OPORT uchar x 104 N_BPSC N, the decoder's soft stream
+struct CallStreamJoin11n { int nb; size_t n; int operator()(const uint8_t* in, uint8_t* out, void* st) const { return sora_hip_stream_join11n(in, in + 52 * nb * n, out, nb, n, st); } };
+template <int N_BPSC, size_t N, class T_CTX, class T_NEXT>
+struct THip11nStreamJoin : THipStage<uint8_t, 104 * N_BPSC * N, uint8_t, 104 * N_BPSC * N, CallStreamJoin11n, T_CTX, T_NEXT> {
+    THip11nStreamJoin(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* stream = nullptr)
+        : THipStage<uint8_t, 104 * N_BPSC * N, uint8_t, 104 * N_BPSC * N, CallStreamJoin11n, T_CTX, T_NEXT>(ctx, next, d_out, CallStreamJoin11n{ N_BPSC, N }, stream) {}
+};
+// T11aDesc (scramble.hpp:269-355), behind the trellis of the 802.11a graph as of the 802.11n one: IPORT uchar x frame_length + 2 (what the trellis stages write) -> OPORT
+// uchar x frame_length.  Like the trellis adapter it knows the frame from the context (SetFrame = CF_11aRxVector::frame_length).
+template <class T_CTX, class T_NEXT>
+class THip11aDesc : public HipFilter<T_CTX, T_NEXT> {
+public:
+    THip11aDesc(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* d_tab, void* stream = nullptr)
+        : HipFilter<T_CTX, T_NEXT>(ctx, next, stream), opin_(d_out), d_tab_(static_cast<uint32_t*>(d_tab)) {}
+    void SetFrame(uint16_t frame_length) { len_ = frame_length; dirty_ = true; }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            if (dirty_) {                                                                          // off, len, out_off
+                const uint32_t tab[4] = { 0u, len_, 0u, 0u };
+                if (sora_hip_stream_synchronize(this->stream_) != SORA_OK || sora_hip_memcpy_h2d(d_tab_, tab, sizeof(tab)) != SORA_OK) return this->raise(SORA_ERR_HARDWARE_FAILED);
+                dirty_ = false;
+            }
+            uint8_t* out = opin_.append();
+            if (!this->raise(sora_hip_desc11a(ipin.peek(), d_tab_, d_tab_ + 1, out, d_tab_ + 2, 1, this->stream_))) return false;
+            ipin.pop();
+            if (this->next_ && !this->next_->Process(opin_)) return false;
+        }
+        return true;
+    }
+    DevicePin<uint8_t, 4096>& opin() { return opin_; }
+private:
+    DevicePin<uint8_t, 4096> opin_; uint32_t* d_tab_; uint32_t len_ = 0; bool dirty_ = true;
+};
+// The two sinks on context.  TBB11aFrameSink (PHY_11a.hpp:609-700): IPORT uchar x frame_length; fills CF_11aSink (CF_Error::error_code, CF_11aRxVector::crc32) and, as the
+// brick does when it has decided, returns false.  d_rec: one sora_sink11a_rec of device memory.
+struct CF_11aSink { uint32_t error_code = 0, frame_crc32 = 0; };
+class THip11aFrameSink {
+public:
+    THip11aFrameSink(CF_11aSink& ctx, sora_sink11a_rec* d_rec, void* d_tab, void* stream = nullptr) : ctx_(ctx), d_rec_(d_rec), d_tab_(static_cast<uint32_t*>(d_tab)), stream_(stream) {}
+    void SetFrame(uint16_t frame_length) { len_ = frame_length; }
+    void Reset() {}
+    void Flush() {}
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            const uint32_t tab[4] = { 0u, len_, 0u, 0u };
+            sora_sink11a_rec rec;
+            int rc = sora_hip_stream_synchronize(stream_);
+            if (rc == SORA_OK) rc = sora_hip_memcpy_h2d(d_tab_, tab, sizeof(tab));
+            if (rc == SORA_OK) rc = sora_hip_frame_sink11a(ipin.peek(), d_tab_, d_tab_ + 1, d_rec_, 1, stream_);
+            if (rc == SORA_OK) rc = sora_hip_stream_synchronize(stream_);
+            if (rc == SORA_OK) rc = sora_hip_memcpy_d2h(&rec, d_rec_, sizeof(rec));
+            ipin.pop();
+            if (rc != SORA_OK) { ctx_.error_code = (uint32_t)rc; return false; }
+            ctx_.error_code = rec.error_code; ctx_.frame_crc32 = rec.frame_crc32;
+            if (rec.error_code) return false;                                                      // E_ERROR_FRAME_OK / E_ERROR_CRC32_FAIL: the frame is over
+        }
+        return true;
+    }
+private:
+    CF_11aSink& ctx_; sora_sink11a_rec* d_rec_; uint32_t* d_tab_; void* stream_; uint32_t len_ = 0;
+};
+// TCCA11n (cca_11n.hpp): IPORT COMPLEX16 x 2 x 4 N (chain 0's N bursts, then chain 1's), a sink: fills CF_11nCCA (CF_11CCA::cca_state, cca_pwr_reading, CF_Error::error_code)
+// and reports the bursts it swallowed (used(): the rest of the burst queue is the frame's).  d_state: one sora_cca11n_state of device memory that the adapter constructs;
+// Reset() is the brick's _reset() with the context cleared, as BB11nDemodCtx.Reset and RxThread's ResetCarrierSense do it.
+struct CF_11nCCA { uint32_t cca_state = 0, cca_pwr_reading = 0, error_code = 0; };
+template <size_t N>
+class THip11nCCA {
+public:
+    THip11nCCA(CF_11nCCA& ctx, sora_cca11n_state* d_state, void* d_tab, unsigned flags = 0, void* stream = nullptr)
+        : ctx_(ctx), d_state_(d_state), d_tab_(static_cast<uint32_t*>(d_tab)), flags_(flags), stream_(stream) {}
+    void Flush() {}
+    bool Reset()
+    {
+        const uint32_t zero[6] = { 0, 0, 0, 0, 0, 0 };                                             // cca_state, error_code | (cca_pwr_reading stands) | the three counters
+        ctx_.cca_state = 0; ctx_.error_code = 0;
+        return sora_hip_stream_synchronize(stream_) == SORA_OK && sora_hip_memcpy_h2d(d_state_, zero, 8) == SORA_OK &&
+               sora_hip_memcpy_h2d(reinterpret_cast<uint32_t*>(d_state_) + 3, zero, 12) == SORA_OK;
+    }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            int rc = SORA_OK;
+            if (!constructed_) {
+                sora_cca11n_state s{};
+                for (auto& e : s.his_moving_energy) { e[0] = 0xFFFFFFFFu; e[1] = 0x7FFFFFFFu; }    // LLONG_MAX
+                rc = sora_hip_memcpy_h2d(d_state_, &s, sizeof(s));
+                constructed_ = rc == SORA_OK;
+            }
+            const uint32_t tab[4] = { 0u, (uint32_t)N, 0u, 0u };                                   // first, n, used
+            uint32_t head[3] = { 0, 0, 0 };
+            if (rc == SORA_OK) rc = sora_hip_stream_synchronize(stream_);
+            if (rc == SORA_OK) rc = sora_hip_memcpy_h2d(d_tab_, tab, sizeof(tab));
+            if (rc == SORA_OK) rc = sora_hip_cca11n(ipin.peek(), ipin.peek() + 4 * N, d_tab_, d_tab_ + 1, d_state_, d_tab_ + 2, 1, N, flags_, stream_);
+            if (rc == SORA_OK) rc = sora_hip_stream_synchronize(stream_);
+            if (rc == SORA_OK) rc = sora_hip_memcpy_d2h(head, d_state_, sizeof(head));
+            if (rc == SORA_OK) rc = sora_hip_memcpy_d2h(&used_, d_tab_ + 2, sizeof(used_));
+            ipin.pop();
+            if (rc != SORA_OK) { ctx_.error_code = (uint32_t)rc; return false; }
+            ctx_.cca_state = head[0]; ctx_.error_code = head[1]; ctx_.cca_pwr_reading = head[2];
+        }
+        return true;
+    }
+    uint32_t used() const { return used_; }
+private:
+    CF_11nCCA& ctx_; sora_cca11n_state* d_state_; uint32_t* d_tab_; unsigned flags_; void* stream_; uint32_t used_ = 0; bool constructed_ = false;
+};
+
+// ------------------------------------------------------------------------------------------------
 // The bricks of the 802.11b modulation graph (kernel/bb/demod11/fb11bmod_config.hpp:28-50) behind TBB11bSrc (sora_hip_ppdu11b, or the host's) and TBB11bMRSelect (the
 // host's: it only routes): one burst = N of the brick's own bursts, one stream per adapter, d_tab as above.  What the bricks keep lies in device records that the entry
 // points read and write back, so the state crosses from Process to Process by itself: the four spreaders share ONE sora_mod11b_state as the bricks share

@@ -41,7 +41,8 @@ extern "C" {
  * Additive since: the 802.11a modulation graph's bricks as stages -- sora_hip_scramble11a, _conv_encode11a, _interleave11a, _map11a, _add_pilot11a (_from), _ifftx11a,
  * _upsample40to44, _pack16to8, _preamble11a; the 802.11n modulation graphs' -- sora_hip_stream_parse11n, _interleave11n, _map11n, _sig_map11n, _add_pilot11n,
  * _ifft_only11n, _csd11n, _add_gi11n, _preamble11n; the 802.11b modulation graph's -- sora_hip_ppdu11b, _sc741_11b, _dbpsk_spread11b, _dqpsk_spread11b, _cck5_encode11b,
- * _cck11_encode11b, _pulse_shape11b (sora_mod11b_state, sora_shaper11b_state). */
+ * _cck11_encode11b, _pulse_shape11b (sora_mod11b_state, sora_shaper11b_state); the bricks that complete the 802.11n receive graph -- sora_hip_cca11n
+ * (sora_cca11n_state), _data_symbol11n, _stream_join11n, and the tail it shares with the 802.11a graph, sora_hip_desc11a, _frame_sink11a (sora_sink11a_rec). */
 #define SORA_HIP_ABI_VERSION 4
 
 /* COMPLEX16: kernel/core/inc/complex.h */
@@ -347,6 +348,8 @@ int sora_hip_deinterleave11a(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, si
 int sora_hip_viterbi11a(const uint8_t* d_soft, const uint32_t* d_soft_off, const uint32_t* d_nsoft,
                         const uint16_t* d_frame_len, int code_rate, uint8_t* d_out, const uint32_t* d_out_off,
                         size_t n, void* stream);
+/* (What stands behind the decoder in the 802.11a graph as in the 802.11n one, T11aDesc -> TBB11aFrameSink, is the stage pair sora_hip_desc11a / sora_hip_frame_sink11a,
+ * declared with the 802.11n receive stages below: it reads exactly the frame_len[i] + 2 bytes per frame that this stage writes.) */
 /* The same brick for a caller that streams bursts through it (a BRICK adapter calls once per burst): no allocation, no host
  * wait, everything in stream order.  soft_span_bytes = the extent of the caller's soft buffer that the n jobs address
  * (max over i of soft_off[i] + nsoft[i]; the jobs' ranges must not overlap -- any offsets, any order, any nsoft >= 24: a
@@ -653,6 +656,12 @@ int sora_hip_pulse_shape11b(const int8_t* d_in, const uint32_t* d_first, const u
  * T11nDemap{BPSK,QPSK,QAM16,QAM64} (kernel/bb/Brick11/src/demapper11n.hpp:89-309): IPORT COMPLEX16 x 64 (one pilot-tracked
  * symbol of one spatial stream) -> OPORT uint8 x 52*N_BPSC soft values 0..7;
  * T11nDeinterleave{...}_S0/_S1 (deinterleaver_11n.hpp:4-1618): 52*N_BPSC soft values of spatial stream 0 or 1 -> de-interleaved.
+ * All of CreateDemodGraph11n (fb11ndemod_config.hpp:166-264) stands here as stages, so that a host can replace ONE brick, or compose the graph (sora_amd.rx11n_by_stages):
+ *     ingest (TDownSample2) -> cca | cfo_est -> freq_comp -> fft64 -> siso_est                                                   (carrier sense, L-LTF)
+ *                                  | freq_comp -> data_symbol -> fft64 -> siso_comp (MRC) -> sig_demap -> sig_decode              (L-SIG, HT-SIG)
+ *                                                                      -> mimo_est                                               (HT-LTF)
+ *                                                                      -> mimo_comp -> pilot_track -> demap -> deinterleave -> stream_join -> viterbi11n_ws -> desc11a -> frame_sink11a
+ * RxSwitch, T11nSymSel, T11nRxRateSel, Mimo64Join and TStreamFork only route and stay the host's.
  * ------------------------------------------------------------------------------------------------ */
 int sora_hip_demap11n(const sora_complex16* d_in, uint8_t* d_soft, int n_bpsc, size_t n, void* stream);
 int sora_hip_deinterleave11n(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, int spatial_stream, size_t n, void* stream);
@@ -699,6 +708,50 @@ int sora_hip_sig_decode11n(const uint8_t* d_soft, uint32_t* d_rec, size_t nframe
 int sora_hip_mimo_est11n(const sora_complex16* d_ltf0, const sora_complex16* d_ltf1, sora_complex16* d_h, sora_complex16* d_hinv, size_t nframes, void* stream);
 int sora_hip_mimo_comp11n(const sora_complex16* d_hinv, const uint32_t* d_frame_index, const sora_complex16* d_y0, const sora_complex16* d_y1,
                           sora_complex16* d_x0, sora_complex16* d_x1, size_t nsym, void* stream);
+
+/* ---- The bricks that complete the graph.  Conventions: those of the 802.11b receive stage block below (above sora_hip_dc_remove11b): device pointers, stream order, no
+ * allocation, no host wait; a null pointer gives SORA_ERR_INVALID_PARAM before any device work (sora_hip_last_error() names the function), no device SORA_ERR_NO_DEVICE, a count of
+ * 0 is SORA_OK and launches nothing; a stateful brick works on a batch of independent streams described by device tables, with a per-stream record of 32-bit words that is read
+ * and written back, and the same stream cut into two calls gives what one call gives.  Every stage equals tests/rx11n_stage_model.py bit for bit
+ * (tests/test_gpu_11n_rx_stages.py).  DESIGN.md section 7, f1b. */
+#define SORA_CCA11N_REARM 1u
+/* TCCA11n (Brick11/src/cca_11n.hpp) with its MimoAutoCorr (autocorr.hpp:5-147).  The record holds the context fields the brick touches (cca_state: 0 power_clear, 1
+ * power_detected; error_code; cca_pwr_reading), its three counters, his_index, the ring his_moving_energy as 64 pairs of words (low, high), a `timeouts` count
+ * (SORA_CCA11N_REARM), and, in place of MimoAutoCorr's sample, product and sum arrays, the last 64 samples of both chains that the brick has consumed, oldest first: from a
+ * constructed brick the wrapping moving sums are the sums of the last 32 products mod 2^32, so the samples determine them.  The record's domain is therefore the states
+ * reachable from a constructed brick.
+ *   as constructed:  every word 0, but the 64 ring entries, which are LLONG_MAX (0xFFFFFFFF, 0x7FFFFFFF) -- "prevent initial fake trigger" -- (sora_amd.cca11n_states makes them)
+ *   after Reset():   sense_count, peak_found, peak_count = 0; everything else stands (cca_state and error_code are the context's: BB11nDemodCtx.Reset clears them) */
+typedef struct {
+    uint32_t cca_state, error_code, cca_pwr_reading, sense_count, peak_found, peak_count, his_index, timeouts;
+    uint32_t his_moving_energy[64][2];
+    sora_complex16 history[2][64];
+} sora_cca11n_state;
+/* d_in0 / d_in1: the two RX chains at 20 MHz (behind TDownSample2).  A unit is the brick's burst: 4 samples of both chains.  Stream f consumes bursts from SAMPLE d_first[f]
+ * of both buffers, d_n[f] at most, until cca_state is power_detected or an error stands; d_used[f] = the bursts consumed, the deciding one included (the brick leaves the
+ * rest of that burst unlooked at and unrecorded in the ring; the auto-correlator has seen it).  A stream that enters with power detected or an error standing consumes nothing.
+ * flags 0: SORA_E_CS_TIMEOUT (defined with the 802.11b stages below; here: sense_count >= 84 at the end of a burst) stands and the stream ends there, as in
+ * sora_hip_energy_detect11b.  SORA_CCA11N_REARM: the time-out does not stand -- the brick's _reset() is
+ * applied, as RxThread does after the event (fb11n_demod.cpp:60-66), `timeouts` counts it, and the stream goes on.  max_n bounds every d_n[f] (< 2^30). */
+int sora_hip_cca11n(const sora_complex16* d_in0, const sora_complex16* d_in1, const uint32_t* d_first, const uint32_t* d_n, sora_cca11n_state* d_state, uint32_t* d_used,
+                    size_t nstreams, size_t max_n, unsigned flags, void* stream);
+/* T11nDataSymbol (PHY_11n.hpp:288-356), 2 x 80 -> 2 x 64: frame f owns d_nsym[f] symbols of 80 samples from SAMPLE d_first[f] of both chains (no alignment beyond a
+ * sample's); samples 16..79 of symbol k go to SYMBOL d_out_first[f] + k of d_out0 / d_out1, 64 samples each: the layout sora_hip_fft64 reads.  The brick's remain_symbols
+ * count-down and its Flush at zero are the host's.  max_nsym >= every d_nsym[f]; at most 65535 frames per call. */
+int sora_hip_data_symbol11n(const sora_complex16* d_in0, const sora_complex16* d_in1, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_out_first,
+                            sora_complex16* d_out0, sora_complex16* d_out1, size_t nframes, size_t max_nsym, void* stream);
+/* TStreamJoin<2, 52 N_BPSC> -> TStreamConcat<2, s> (brick/inc/stdbrick.hpp:640-720), s = max(N_BPSC / 2, 1) as the graph wires it (StreamConcat_1 for BPSK and QPSK, _2
+ * for 16-QAM, _3 for 64-QAM): d_s0 / d_s1 [n][52 N_BPSC] = the de-interleaved soft values of spatial stream 0 / 1 (sora_hip_deinterleave11n) -> d_out[n][104 N_BPSC] in groups of
+ * s bytes, alternating stream 0, stream 1: byte for byte one job's soft values for sora_hip_viterbi11n_ws.  n_bpsc 1, 2, 4 or 6, else SORA_ERR_INVALID_PARAM. */
+int sora_hip_stream_join11n(const uint8_t* d_s0, const uint8_t* d_s1, uint8_t* d_out, int n_bpsc, size_t n, void* stream);
+/* T11aDesc (scramble.hpp:269-355), the descrambler of the 802.11a and the 802.11n graph: frame i reads d_len[i] + 2 decoded bytes at d_dec + d_off[i] -- what the trellis stages
+ * write --, drops byte 0, seeds the register with byte 1 >> 1 and writes d_len[i] descrambled bytes at d_out + d_out_off[i]. */
+int sora_hip_desc11a(const uint8_t* d_dec, const uint32_t* d_off, const uint32_t* d_len, uint8_t* d_out, const uint32_t* d_out_off, size_t n, void* stream);
+/* TBB11aFrameSink (PHY_11a.hpp:609-700) over one frame each: d_len[i] = frame_length (a ushort: the low 16 bits) descrambled bytes at d_bytes + d_off[i] -> d_rec[i]:
+ * error_code SORA_E_FRAME_OK / SORA_E_CRC32_FAIL and frame_crc32 = the frame's last four bytes as the brick reads them (little-endian).  Lengths below 4: the brick compares
+ * byte_count with (ulong)(frame_length - 4), which has wrapped, so every byte goes into the CRC and it never decides: the record is 0, 0. */
+typedef struct { uint32_t error_code, frame_crc32; } sora_sink11a_rec;
+int sora_hip_frame_sink11a(const uint8_t* d_bytes, const uint32_t* d_off, const uint32_t* d_len, sora_sink11a_rec* d_rec, size_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 802.11n 2x2 receive graph = CreateDemodGraph11n (kernel/bb/demod11/fb11ndemod_config.hpp:166-257) driven by

@@ -13,6 +13,7 @@ from .capi import (Rx, Rx11b, Rx11n, RxHt40, ht40_symbols, HostResults, ROW_DTYP
                    mod11n_by_stages, Mod11nStages, mod11n_fields,
                    dc_remove11b, energy_detect11b, symtiming11b, barker_sync11b, despread11b, sfd_sync11b, dbpsk_demap11b, dqpsk_demap11b, cck5p5_decode11b,
                    cck11_decode11b, desc741_11b, plcp_parse11b, frame_sink11b, rx11b_by_stages, rx11b_stages, state11b_reset, STATE11B_WORDS,
+                   cca11n, cca11n_states, data_symbol11n, stream_join11n, desc11a, frame_sink11a, rx11n_by_stages, rx11n_stages, CCA11N_WORDS, CCA11N_REARM,
                    ppdu11b, sc741_11b, dbpsk_spread11b, dqpsk_spread11b, cck5_encode11b, cck11_encode11b, pulse_shape11b, mod11b_by_stages, Mod11bStages,
                    tx11a, tx11a_samples, tx11n, tx11n_samples, tx_ht40, tx_ht40_samples, tx11b, tx11b_samples, INGEST_RXBLOCK, INGEST_RAW14, INGEST_44TO40, INGEST_DECIMATE2,
                    ht40_symbols_joint, HT40_CODING_PER_STREAM, HT40_CODING_JOINT, tx_ht40_joint, tx_ht40_joint_samples,

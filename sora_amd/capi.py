@@ -85,7 +85,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_hip_pulse_shape11b",
            "sora_hip_tx_ht40_joint", "sora_hip_tx_ht40_joint_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
-                      "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n", "sora_rx11b_create",
+                      "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n",
+           "sora_hip_cca11n", "sora_hip_data_symbol11n", "sora_hip_stream_join11n", "sora_hip_desc11a", "sora_hip_frame_sink11a", "sora_rx11b_create",
                       "sora_rx11b_destroy", "sora_rx11b_stream", "sora_rx11b_synchronize", "sora_rx11b_process_dev", "sora_rx11b_process", "sora_rx11b_results", "sora_rx11b_ticket",
                       "sora_rx11b_calls_in_flight", "sora_rx11b_set_single_pass", "sora_rx11b_set_preamble", "sora_rx11b_wait", "sora_rx11b_wait_any", "sora_rx11b_stream_of", "sora_rx11b_results_of",
                       "sora_rx11b_deliver_async", "sora_rx11b_set_stream_mode", "sora_rx11b_stream_consumed", "sora_rx11n_deliver_async",
@@ -303,6 +304,12 @@ def load(build_if_missing=True):
     L.sora_hip_siso_comp11n.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_sig_demap11n.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_sig_decode11n.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
+    # the bricks that complete the 802.11n receive graph
+    L.sora_hip_cca11n.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p]
+    L.sora_hip_data_symbol11n.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_stream_join11n.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_desc11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_frame_sink11a.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]
     L.sora_rx11n_create.argtypes = [ctypes.POINTER(RxCfg), ctypes.POINTER(ctypes.c_void_p)]
     L.sora_rx11n_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11n_process.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
@@ -1783,6 +1790,292 @@ def rx11b_by_stages(d_iq, descs, mode=0, cca_pwr_threshold=1000 * 1000):
     A DEMONSTRATION and a test vehicle, not a fast path: between stages it reads counts and records back to the host to build the next tables, some twenty round trips
     per hundred bursts of silence in front of the frame.  The counterpart of mod11a_by_stages; the fast path is Rx11b."""
     return rx11b_stages(_Gpu11bOps(d_iq.device), d_iq, descs, mode, cca_pwr_threshold)
+
+
+# ---- the bricks that complete the 802.11n receive graph as stages (include/sora_hip.h, sora_hip_cca11n .. sora_hip_frame_sink11a)
+# sora_cca11n_state as int32 words [n, 264]: 0 cca_state, 1 error_code, 2 cca_pwr_reading, 3 sense_count, 4 peak_found, 5 peak_count, 6 his_index, 7 timeouts,
+# 8..135 his_moving_energy (low, high) x 64, 136..199 / 200..263 the last 64 samples of chain 0 / 1 (re | im << 16), oldest first
+CCA11N_WORDS = 264
+CCA11N_REARM = 1
+
+
+def cca11n_states(n):
+    """-> int32 numpy [n, 264]: sora_cca11n_state as a constructed TCCA11n holds it in a fresh context: all 0 but the ring, which is LLONG_MAX"""
+    s = np.zeros((n, CCA11N_WORDS), np.int32)
+    s[:, 8:136:2] = -1; s[:, 9:136:2] = 0x7FFFFFFF
+    return s
+
+
+def cca11n(in0, in1, first, n, state, flags=0, max_n=None, stream=None):
+    """TCCA11n: in0 / in1 int16 CUDA [samples, 2], the two chains at 20 MHz; first (samples) / n (bursts of 4) int32 CUDA [streams]; state int32 CUDA [streams, 264]
+    (in / out) -> used int32 CUDA [streams]: the bursts consumed"""
+    import torch
+    used = torch.zeros(first.shape[0], dtype=torch.int32, device=in0.device)
+    _check(load().sora_hip_cca11n(_dev_ptr(in0), _dev_ptr(in1), _dev_ptr(first), _dev_ptr(n), _dev_ptr(state), _dev_ptr(used), first.shape[0], _max_n(n, max_n), int(flags),
+                                  _stream_ptr(stream)))
+    return used
+
+
+def data_symbol11n(in0, in1, first, nsym, out_first, out0, out1, max_nsym=None, stream=None):
+    """T11nDataSymbol: frame f's nsym[f] symbols of 80 samples from sample first[f] of in0 / in1 -> their samples 16..79 at symbol out_first[f] of out0 / out1 (int16 CUDA
+    [symbols * 64, 2])"""
+    _check(load().sora_hip_data_symbol11n(_dev_ptr(in0), _dev_ptr(in1), _dev_ptr(first), _dev_ptr(nsym), _dev_ptr(out_first), _dev_ptr(out0), _dev_ptr(out1), first.shape[0],
+                                          _max_n(nsym, max_nsym), _stream_ptr(stream)))
+    return out0, out1
+
+
+def stream_join11n(s0, s1, n_bpsc, out=None, stream=None):
+    """TStreamJoin + TStreamConcat: s0 / s1 uint8 CUDA [n, 52 n_bpsc] -> uint8 CUDA [n, 104 n_bpsc], groups of max(n_bpsc / 2, 1) bytes alternating stream 0 / 1"""
+    import torch
+    n = s0.shape[0]
+    if out is None:
+        out = torch.empty((n, 104 * n_bpsc), dtype=torch.uint8, device=s0.device)
+    _check(load().sora_hip_stream_join11n(_dev_ptr(s0), _dev_ptr(s1), _dev_ptr(out), int(n_bpsc), n, _stream_ptr(stream)))
+    return out
+
+
+def desc11a(dec, off, length, out, out_off, stream=None):
+    """T11aDesc: frame i = length[i] + 2 decoded bytes at dec[off[i]] (uint8 CUDA) -> length[i] descrambled bytes at out[out_off[i]]"""
+    _check(load().sora_hip_desc11a(_dev_ptr(dec), _dev_ptr(off), _dev_ptr(length), _dev_ptr(out), _dev_ptr(out_off), off.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def frame_sink11a(x, off, length, stream=None):
+    """TBB11aFrameSink: frame i = length[i] descrambled bytes at x[off[i]] (uint8 CUDA) -> int32 CUDA [n, 2]: error_code, frame_crc32"""
+    import torch
+    rec = torch.zeros((off.shape[0], 2), dtype=torch.int32, device=x.device)
+    _check(load().sora_hip_frame_sink11a(_dev_ptr(x), _dev_ptr(off), _dev_ptr(length), _dev_ptr(rec), off.shape[0], _stream_ptr(stream)))
+    return rec
+
+
+class _Gpu11nOps:
+    """rx11n_stages' bricks on the GPU: host tables and records (numpy) up, one stage call, records back.  Buffers are torch CUDA tensors."""
+
+    def __init__(self, device):
+        import torch
+        self.torch = torch; self.dev = device; self.comp = None
+
+    def _up(self, a, dt=np.int32):
+        return self.torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(dt, copy=False))).to(self.dev)
+
+    def host(self, a):
+        return a.cpu().numpy()
+
+    def downsample2(self, iq):
+        return ingest(iq, INGEST_DECIMATE2)
+
+    def cca(self, x0, x1, first, n, state, flags):
+        st = self._up(state)
+        used = cca11n(x0, x1, self._up(first), self._up(n), st, flags, max_n=int(max(n)))
+        return st.cpu().numpy(), used.cpu().numpy()
+
+    def take(self, x, starts, length):
+        idx = (self._up(starts, np.int64)[:, None] + self.torch.arange(length, device=self.dev)[None, :]).reshape(-1)
+        return x[idx].contiguous()
+
+    def rows(self, a, idx):
+        return a[self._up(idx, np.int64)].contiguous()
+
+    def concat(self, parts):
+        return self.torch.cat([p.reshape(-1) for p in parts]).contiguous()
+
+    def cfo_est(self, l0, l1):
+        return cfo_est11n(l0.reshape(-1, 128, 2), l1.reshape(-1, 128, 2))
+
+    def freq_comp(self, x0, x1, first, nbursts, state):
+        if self.comp is None:
+            self.comp = (self.torch.zeros_like(x0), self.torch.zeros_like(x1))
+        d_first, d_n = self._up(first), self._up(nbursts)                           # (held until the call has been issued on the null stream, which orders their reuse)
+        _check(load().sora_hip_freq_comp11n(_dev_ptr(x0), _dev_ptr(x1), _dev_ptr(self.comp[0]), _dev_ptr(self.comp[1]), _dev_ptr(d_first), _dev_ptr(d_n),
+                                            _dev_ptr(state), state.shape[0], int(max(nbursts)), None))
+        return self.comp
+
+    def data_symbol(self, x0, x1, first, nsym, out_first, total):
+        o0 = self.torch.zeros((max(total, 1) * 64, 2), dtype=self.torch.int16, device=self.dev); o1 = self.torch.zeros_like(o0)
+        data_symbol11n(x0, x1, self._up(first), self._up(nsym), self._up(out_first), o0, o1, max_nsym=int(max(nsym)))
+        return o0[:total * 64], o1[:total * 64]
+
+    def fft64(self, x):
+        return fft64(x.reshape(-1, 64, 2)).reshape(-1, 2)
+
+    def siso_est(self, l0, l1):
+        return siso_est11n(l0.reshape(-1, 128, 2), l1.reshape(-1, 128, 2))
+
+    def siso_comp_mrc(self, ch, y0, y1, frame_index):
+        return siso_comp11n(ch, y0.reshape(-1, 64, 2), y1.reshape(-1, 64, 2), self._up(frame_index))[2].reshape(-1, 2)
+
+    def sig_demap(self, mrc):
+        return sig_demap11n(mrc.reshape(-1, 3, 64, 2))
+
+    def sig_decode(self, soft):
+        return sig_decode11n(soft).cpu().numpy().view(np.uint32)
+
+    def mimo_est(self, l0, l1):
+        return mimo_est11n(l0.reshape(-1, 128, 2), l1.reshape(-1, 128, 2))[1]
+
+    def mimo_comp(self, hinv, y0, y1, frame_index):
+        a, b = mimo_comp11n(hinv, y0.reshape(-1, 64, 2), y1.reshape(-1, 64, 2), self._up(frame_index))
+        return a, b
+
+    def pilot_track(self, x0, x1, first, nsym, state):
+        pilot_track11n(x0, x1, self._up(first), self._up(nsym), state, want_theta=False)
+
+    def demap_deint(self, x, nb, iss):
+        return deinterleave11n(demap11n(x, nb), nb, iss)
+
+    def stream_join(self, s0, s1, nb):
+        return stream_join11n(s0, s1, nb)
+
+    def viterbi(self, soft, soft_off, nsoft, lens, code_rate):
+        ws = self.torch.empty(viterbi11n_workspace_bytes(soft.numel(), len(lens)), dtype=self.torch.uint8, device=self.dev)
+        out = viterbi11n_ws(soft, self._up(soft_off), self._up(nsoft), self._up(lens, np.int16), int(code_rate), ws)
+        self.torch.cuda.synchronize(self.dev)
+        return out.reshape(-1)
+
+    def desc(self, dec, off, lens, out_off, total):
+        out = self.torch.zeros(max(total, 1), dtype=self.torch.uint8, device=self.dev)
+        return desc11a(dec, self._up(off), self._up(lens), out, self._up(out_off))
+
+    def frame_sink(self, x, off, lens):
+        return frame_sink11a(x, self._up(off), self._up(lens)).cpu().numpy().view(np.uint32)
+
+
+def sig_gate11n(rec, mcs_max=10):
+    """T11nSigParser's checks in its order (PHY_11n.hpp:432-513) on the decoded bits of one sora_hip_sig_decode11n record (words 9..11), with the gate `mcs >= 11`
+    at mcs_max + 1 -> None (SORA_E_PLCP_HEADER_FAIL) or (mcs, ht_length, code_rate, data symbols)"""
+    sig = int(rec[9]) & 0xFFFFFF; ht = int(rec[10]) | (int(rec[11]) << 32)
+    if (sig & 0xFC0010) or (bin(sig).count("1") & 1) or (sig & 0xF) < 8 or ((sig >> 5) & 0xFFF) * 2 > 1500:
+        return None
+    crc = 0xFF
+    for b in range(34):
+        crc ^= (ht >> b) & 1
+        crc = (crc >> 1) ^ 0xE0 if crc & 1 else crc >> 1
+    if ((~crc) & 0xFF) != ((ht >> 34) & 0x3FFF):
+        return None
+    mcs = ht & 0x7F; length = (ht >> 8) & 0xFFFF
+    if mcs < 8 or mcs > mcs_max or length > 1500:
+        return None
+    cr = 2 if mcs in (10, 12, 14) else 1 if mcs == 13 else 0
+    nd = (52, 104, 156, 208, 312, 416, 468)[mcs - 8]
+    return mcs, length, cr, (length * 8 + 22 + nd - 1) // nd
+
+
+def rx11n_stages(ops, iq0, iq1, descs, mcs_max=10, trace=None):
+    """The 802.11n 2x2 receive graph (CreateDemodGraph11n under RxThread, fb11n_demod.cpp:30-85) up to the FIRST event of every capture, composed from the brick stages
+    through `ops` (the GPU's: rx11n_by_stages; the model's: tests/rx11n_stage_model.first_events), along the walk of oracle/so_rx11n.c:157-239.  The host plays the routing
+    bricks (RxSwitch, T11nSymSel, T11nRxRateSel, Mimo64Join, TStreamFork), the parser's gate at mcs_max and the harness: it reads counts and records back and builds the next
+    stage's tables from them.  Each phase is one call over all captures still alive; the data field goes symbol by symbol, because TPilotTrack_11n's phase of symbol k
+    steers TFreqComp_11n on symbol k + 1.
+    iq0 / iq1: the two chains at 40 MHz (ops' buffers), descs: [(first sample, samples)], whole 28-sample source calls at even offsets.
+    -> per capture None (no detection, or the capture ends before the event: the end-of-capture flush of zero-padded symbols is not reproduced) or a dict error_code,
+    rate_kbps (= MCS), length, crc32, mpdu.  Carrier-sense time-outs re-arm at the burst that raises them (SORA_CCA11N_REARM); RxThread re-arms at the end of its
+    28-sample source call, up to three bursts later.  trace: a list that receives (name, host copy) of what each phase hands on."""
+    nc = len(descs)
+    if nc == 0:
+        return []
+    off = np.array([int(d[0]) for d in descs], np.int64); ns = np.array([int(d[1]) for d in descs], np.int64)
+    if (ns % 28).any() or (off % 2).any():
+        raise ValueError("rx11n_stages: a capture is whole 28-sample source calls at an even offset")
+    u32 = lambda a: np.asarray(a, np.int64).astype(np.uint32).view(np.int32)
+
+    def note(name, a, host=True):
+        if trace is not None:
+            trace.append((name, np.array(ops.host(a) if host else a)))
+
+    events = [None] * nc
+    x0 = ops.downsample2(iq0); x1 = ops.downsample2(iq1)                       # TDownSample2: the even samples
+    first = off // 2; nb = np.minimum(ns // 8, (int(x0.shape[0]) - off // 2) // 4)      # (sora_hip_ingest decimates whole groups of 8 raw samples of the BUFFER)
+    note("x0", x0); note("x1", x1)
+    # ---- TCCA11n behind RxSwitch
+    st, used = ops.cca(x0, x1, u32(first), u32(nb), cca11n_states(nc), CCA11N_REARM)
+    note("cca_state", st, False); note("cca_used", used, False)
+    s0 = first + 4 * used.astype(np.int64); left = 4 * (nb - used.astype(np.int64))
+    live = np.array([c for c in range(nc) if st[c, 0] == 1 and left[c] >= 368], np.int64)
+    if len(live) == 0:
+        return events
+    s0 = s0[live]; left = left[live]; nl = len(live)
+    # ---- L-LTF: TFreqEstimator_11n, TFreqComp_11n, 2 x 2 TFFT64, TSisoChannelEst
+    vfo = ops.cfo_est(ops.take(x0, s0, 128), ops.take(x1, s0, 128))
+    c0, c1 = ops.freq_comp(x0, x1, u32(s0), u32(np.full(nl, 16)), vfo)
+    ch = ops.siso_est(ops.fft64(ops.take(c0, s0, 128)), ops.fft64(ops.take(c1, s0, 128)))
+    note("vfo_lltf", vfo); note("ch", ch)
+    # ---- L-SIG, HT-SIG 1 / 2: TFreqComp_11n, T11nDataSymbol, TFFT64, TSisoChannelComp + TMrcCombine, T11nSigDemap, the SIG decoder; the parser's gate
+    c0, c1 = ops.freq_comp(x0, x1, u32(s0 + 128), u32(np.full(nl, 30)), vfo)
+    y0, y1 = ops.data_symbol(c0, c1, u32(s0 + 128), u32(np.full(nl, 3)), u32(3 * np.arange(nl)), 3 * nl)
+    note("sig_y0", y0); note("sig_y1", y1)
+    mrc = ops.siso_comp_mrc(ch, ops.fft64(y0), ops.fft64(y1), u32(np.repeat(np.arange(nl), 3)))
+    soft = ops.sig_demap(mrc)
+    rec = ops.sig_decode(soft)
+    note("sig_mrc", mrc); note("sig_soft", soft); note("sig_rec", rec, False)
+    mcs = np.zeros(nl, np.int64); length = np.zeros(nl, np.int64); cr = np.zeros(nl, np.int64); nsym = np.zeros(nl, np.int64)
+    go = []
+    for j in range(nl):
+        g = sig_gate11n(rec[j], mcs_max)
+        if g is None:
+            events[live[j]] = {"error_code": 0x80000005, "rate_kbps": 0, "length": 0, "crc32": 0, "mpdu": b""}
+            continue
+        mcs[j], length[j], cr[j], nsym[j] = g
+        if left[j] >= 608 + 80 * nsym[j]:
+            go.append(j)
+    if not go:
+        return events
+    go = np.array(go, np.int64)
+    # ---- HT-STF (dropped), HT-LTF 1 / 2: TMimoChannelEst
+    nbur = np.zeros(nl, np.int64); nbur[go] = 30
+    c0, c1 = ops.freq_comp(x0, x1, u32(s0 + 368), u32(nbur), vfo)
+    y0, y1 = ops.data_symbol(c0, c1, u32(s0[go] + 448), u32(np.full(len(go), 2)), u32(2 * np.arange(len(go))), 2 * len(go))
+    hinv = ops.mimo_est(ops.fft64(y0), ops.fft64(y1))
+    note("hinv", hinv)
+    # ---- the data field, symbol by symbol over the captures that still have one
+    nbpsc = {8: 1, 9: 2, 10: 2, 11: 4, 12: 4, 13: 6, 14: 6}
+    chunks = {int(j): [] for j in go}
+    for k in range(int(nsym[go].max())):
+        al = go[nsym[go] > k]                                                   # alive, as indices into the live captures; their rank in `go` finds their channel
+        rank = np.searchsorted(go, al)
+        nbur = np.zeros(nl, np.int64); nbur[al] = 10
+        c0, c1 = ops.freq_comp(x0, x1, u32(s0 + 608 + 80 * k), u32(nbur), vfo)
+        y0, y1 = ops.data_symbol(c0, c1, u32(s0[al] + 608 + 80 * k), u32(np.ones(len(al))), u32(np.arange(len(al))), len(al))
+        e0, e1 = ops.mimo_comp(hinv, ops.fft64(y0), ops.fft64(y1), u32(rank))
+        pf = np.zeros(nl, np.int64); pn = np.zeros(nl, np.int64); pf[al] = np.arange(len(al)); pn[al] = 1
+        ops.pilot_track(e0, e1, u32(pf), u32(pn), vfo)
+        for b in (1, 2, 4, 6):
+            sel = np.array([i for i, j in enumerate(al) if nbpsc[int(mcs[j])] == b], np.int64)
+            if len(sel) == 0:
+                continue
+            j0 = ops.demap_deint(ops.rows(e0, sel), b, 0); j1 = ops.demap_deint(ops.rows(e1, sel), b, 1)
+            joined = ops.stream_join(j0, j1, b)
+            if k == 0:
+                note("joined0_nb%d" % b, joined)
+            for i, r in enumerate(sel):
+                chunks[int(al[r])].append(joined[i])
+    note("vfo_end", vfo)
+    # ---- T11aViterbi<5000 * 8, 312, 192, 36> per code rate, T11aDesc, TBB11aFrameSink
+    for rate in (0, 1, 2):
+        js = [int(j) for j in go if cr[j] == rate]
+        if not js:
+            continue
+        nsoft = np.array([104 * nbpsc[int(mcs[j])] * nsym[j] for j in js], np.int64)
+        soff = np.concatenate([[0], np.cumsum(nsoft)])[:-1]
+        soft = ops.concat([p for j in js for p in chunks[j]])
+        dec = ops.viterbi(soft, u32(soff), u32(nsoft), length[js], rate)
+        boff = 1504 * np.arange(len(js))
+        by = ops.desc(dec, u32(2560 * np.arange(len(js))), u32(length[js]), u32(boff), 1504 * len(js))
+        srec = ops.frame_sink(by, u32(boff), u32(length[js]))
+        hb = ops.host(by)
+        note("mpdu_cr%d" % rate, by); note("sink_cr%d" % rate, srec, False)
+        for i, j in enumerate(js):
+            if srec[i, 0]:
+                events[live[j]] = {"error_code": int(srec[i, 0]), "rate_kbps": int(mcs[j]), "length": int(length[j]), "crc32": int(srec[i, 1]),
+                                   "mpdu": hb[boff[i]:boff[i] + length[j]].tobytes()}
+    return events
+
+
+def rx11n_by_stages(d_iq0, d_iq1, descs, mcs_max=10, trace=None):
+    """The first event of every capture of a batch of two-chain 40 MHz captures, through the 802.11n stage entry points alone (rx11n_stages with the GPU's bricks):
+    d_iq0 / d_iq1 int16 CUDA [samples, 2], descs [(first sample, samples)] -> per capture None or a dict error_code, rate_kbps (= MCS), length, crc32, mpdu.
+    A DEMONSTRATION and a test vehicle, not a fast path: between stages it reads counts and records back to the host to build the next tables, and the data field costs
+    some ten calls per OFDM symbol.  It does not reproduce the flush of zero-padded symbols at the end of a capture.  The fast path is Rx11n."""
+    return rx11n_stages(_Gpu11nOps(d_iq0.device), d_iq0, d_iq1, descs, mcs_max, trace)
 
 
 def tx11n_samples(mpdu_len_nofcs, mcs):

@@ -11,7 +11,7 @@
 //   T11nSigParser     sig_parse_front (what stands in front of each form's own gate)
 //   TMimoChannelEst   mimo_h_carrier, mimo_inverse, mimo_weight_pack, mimo_est_carrier          TMimoChannelComp   mimo_comp_row
 //   TPilotTrack_11n   dsp_atan16                              T11nDemap*          demap11n_store
-//   T11nDeinterleave  deint11n_index                          T11aDesc + TBB11aFrameSink   finish_frame
+//   T11nDeinterleave  deint11n_index                          T11aDesc + TBB11aFrameSink   finish_frame = desc11a_phase / desc11a_byte + fcs_verdict
 #pragma once
 #include "dev_arith.h"
 #include "rx_types.h"
@@ -286,18 +286,34 @@ __device__ __forceinline__ int cfo_est11n(const short* atan_tab, cpx a0, cpx b0,
 // returns the verdict; fcs = the frame's last four bytes.  Both are lane 0's to store (crc32_wave leaves the register there).  One pass of crc32_wave covers the
 // last 64 x 40 = 2560 bytes: enough for the 802.11n handle (LENGTH <= 1500).  LONG (the 40 MHz handle, LENGTH <= 4000): a longer PSDU takes a second pass over the
 // 2560 bytes in front of those, joined through Z_2560 as dev_tx.h joins the transmitter's two FCS waves.
+// The two halves, which are also the stages sora_hip_desc11a and sora_hip_frame_sink11a (k_11n.hip):
+//   desc11a_phase / desc11a_byte   T11aDesc: byte 0 of the decoder's output is dropped, byte 1 >> 1 seeds the register; descrambled byte i is decoded byte 2 + i
+//                                  xor the scrambler's byte 8 i cycle positions behind the seed's (seed 0: the register stays 0)
+//   fcs_verdict                    TBB11aFrameSink on L descrambled bytes (in LDS, L >= 4 for the brick to decide): the CRC-32 over the first L - 4 against the last four
+__device__ __forceinline__ unsigned desc11a_phase(const Tables& T, const uint8_t* dec) { return T.scr_phase[(dec[1] >> 1) & 0x7F]; }
+__device__ __forceinline__ unsigned desc11a_byte(const Tables& T, unsigned phase, const uint8_t* dec, uint32_t i)
+{
+    const unsigned sb = phase == 255 ? 0u : T.scr_seq[(phase + 8u * i) % 127u];
+    return dec[2 + i] ^ sb;
+}
+template <bool LONG>
+__device__ __forceinline__ uint32_t fcs_verdict(const uint8_t* bytes, uint32_t L, const uint32_t* s_crc, const uint32_t* s_z, int lane, uint32_t& fcs);
+
 template <bool LONG = false>
 __device__ __forceinline__ uint32_t finish_frame(const Tables& T, const uint8_t* dec, uint32_t L, uint8_t* bytes, uint8_t* mp, const uint32_t* s_crc,
                                                  const uint32_t* s_z, int lane, uint32_t& fcs)
 {
-    const unsigned seed = dec[1] >> 1;
-    const unsigned phase = T.scr_phase[seed & 0x7F];
+    const unsigned phase = desc11a_phase(T, dec);
     for (uint32_t i = lane; i < L; i += 64) {
-        const unsigned sb = phase == 255 ? 0u : T.scr_seq[(phase + 8u * i) % 127u];
-        const unsigned o = dec[2 + i] ^ sb;
+        const unsigned o = desc11a_byte(T, phase, dec, i);
         bytes[i] = (uint8_t)o; mp[i] = (uint8_t)o;
     }
     wave_lds_sync();
+    return fcs_verdict<LONG>(bytes, L, s_crc, s_z, lane, fcs);
+}
+template <bool LONG>
+__device__ __forceinline__ uint32_t fcs_verdict(const uint8_t* bytes, uint32_t L, const uint32_t* s_crc, const uint32_t* s_z, int lane, uint32_t& fcs)
+{
     const int n = L >= 4 ? (int)L - 4 : 0;
     uint32_t crc;
     if (n >= 4) {
