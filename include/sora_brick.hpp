@@ -812,6 +812,152 @@ private:
 };
 
 // ------------------------------------------------------------------------------------------------
+// The front-end bricks of the 802.11a receive graph (kernel/bb/demod11/fb11ademod_config.hpp:169-232), each where its SSE brick sits: one burst = N of the brick's own
+// bursts, one stream per adapter.  d_tab: 32 bytes of device memory, the adapter's own (its tables).
+// TDCRemoveEx<4>::Filter (brick/inc/dc.hpp:46-86): IPORT COMPLEX16 x 4 N -> OPORT COMPLEX16 x 4 N.  CF_VecDC = SetDC (what THip11aDCEstimator, or the host's brick, last said).
+template <size_t N, class T_CTX, class T_NEXT>
+class THip11aDCRemoveEx : public THip11bStage<sora_complex16, 4 * N, sora_complex16, 4 * N, T_CTX, T_NEXT> {
+    using Base = THip11bStage<sora_complex16, 4 * N, sora_complex16, 4 * N, T_CTX, T_NEXT>;
+public:
+    THip11aDCRemoveEx(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* d_tab, void* stream = nullptr) : Base(ctx, next, d_out, d_tab, (uint32_t)N, stream) {}
+    void SetDC(sora_complex16 dc) { this->word3_ = (uint32_t)(uint16_t)dc.re | ((uint32_t)(uint16_t)dc.im << 16); this->dirty_ = true; }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        return this->run(ipin, [](const sora_complex16* in, const uint32_t* f, const uint32_t* n, const uint32_t* of, const uint32_t* dc, sora_complex16* out, void* st) {
+            return sora_hip_dc_remove11a(in, f, n, of, reinterpret_cast<const sora_complex16*>(dc), out, 1, N, st); });
+    }
+};
+// T11aDataSymbol (PHY_11a.hpp:361-430): IPORT COMPLEX16 x 80 N -> OPORT COMPLEX16 x 64 N.  remain_symbols and the Flush at zero stay the host's.
+template <size_t N, class T_CTX, class T_NEXT>
+class THip11aDataSymbol : public THip11bStage<sora_complex16, 80 * N, sora_complex16, 64 * N, T_CTX, T_NEXT> {
+    using Base = THip11bStage<sora_complex16, 80 * N, sora_complex16, 64 * N, T_CTX, T_NEXT>;
+public:
+    THip11aDataSymbol(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* d_tab, void* stream = nullptr) : Base(ctx, next, d_out, d_tab, (uint32_t)N, stream) {}
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        return this->run(ipin, [](const sora_complex16* in, const uint32_t* f, const uint32_t* n, const uint32_t* of, const uint32_t*, sora_complex16* out, void* st) {
+            return sora_hip_data_symbol11a(in, f, n, of, out, 1, N, st); });
+    }
+};
+// T11aViterbiSig (viterbi.hpp:8-49): IPORT uchar x 48 N -> OPORT uint x N
+struct CallViterbiSig11a { size_t n; int operator()(const uint8_t* in, uint32_t* out, void* st) const { return sora_hip_viterbi_sig11a(in, out, n, st); } };
+template <size_t N, class T_CTX, class T_NEXT>
+struct THip11aViterbiSig : THipStage<uint8_t, 48 * N, uint32_t, N, CallViterbiSig11a, T_CTX, T_NEXT> {
+    THip11aViterbiSig(T_CTX& ctx, T_NEXT* next, uint32_t* d_out, void* stream = nullptr)
+        : THipStage<uint8_t, 48 * N, uint32_t, N, CallViterbiSig11a, T_CTX, T_NEXT>(ctx, next, d_out, CallViterbiSig11a{ N }, stream) {}
+};
+// T11aPLCPParser (PHY_11a.hpp:518-604), a sink of uint x 1: fills CF_11aPLCP -- CF_11aRxVector's fields as the parser leaves them from 0 (partial behind a reject: see
+// sora_hip_plcp_parse11a), remain_symbols = total_symbols, CF_11RxPLCPSwitch::plcp_state (1 = plcp_data) and CF_Error::error_code.  d_rec: one sora_plcp11a_rec.
+struct CF_11aPLCP { uint32_t error_code = 0, data_rate_kbps = 0, frame_length = 0, code_rate = 0, total_symbols = 0, remain_symbols = 0, plcp_state = 0; };
+class THip11aPLCPParser {
+public:
+    THip11aPLCPParser(CF_11aPLCP& ctx, sora_plcp11a_rec* d_rec, void* stream = nullptr) : ctx_(ctx), d_rec_(d_rec), stream_(stream) {}
+    void Reset() {}
+    void Flush() {}
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            sora_plcp11a_rec rec;
+            int rc = sora_hip_plcp_parse11a(ipin.peek(), d_rec_, 1, stream_);
+            if (rc == SORA_OK) rc = sora_hip_stream_synchronize(stream_);
+            if (rc == SORA_OK) rc = sora_hip_memcpy_d2h(&rec, d_rec_, sizeof(rec));
+            ipin.pop();
+            if (rc != SORA_OK) { ctx_.error_code = (uint32_t)rc; return false; }
+            ctx_.data_rate_kbps = rec.data_rate_kbps; ctx_.frame_length = rec.frame_length; ctx_.code_rate = rec.code_rate; ctx_.total_symbols = rec.total_symbols;
+            if (rec.error_code) ctx_.error_code = rec.error_code;                                  // E_ERROR_PLCP_HEADER_FAIL; the brick's Process still returns true
+            else { ctx_.remain_symbols = rec.total_symbols; ctx_.plcp_state = 1; }
+        }
+        return true;
+    }
+private:
+    CF_11aPLCP& ctx_; sora_plcp11a_rec* d_rec_; void* stream_;
+};
+// TDCEstimator (dc.hpp:99-165): IPORT COMPLEX16 x 4 N, passed through untouched (not copied: hand the same pin on).  d_state: one sora_dcest11a_state that the
+// adapter constructs (update_cnt 8); Reset() is the brick's __init (DC stands).  DC() = CF_VecDC::direct_current after the last burst (one element: the four are equal).
+template <size_t N>
+class THip11aDCEstimator {
+public:
+    THip11aDCEstimator(sora_dcest11a_state* d_state, void* d_tab, void* stream = nullptr) : d_state_(d_state), d_tab_(static_cast<uint32_t*>(d_tab)), stream_(stream) {}
+    void Flush() {}
+    bool Reset()
+    {
+        const uint32_t init[2] = { 8u, 0u };                                                       // update_cnt, sum_dc
+        return sora_hip_stream_synchronize(stream_) == SORA_OK && sora_hip_memcpy_h2d(d_state_, init, sizeof(init)) == SORA_OK;
+    }
+    // n: the bursts of the pin's burst that count (THip11aCCA::npass() where the pin is its gated output)
+    template <class T_IPIN> bool Process(T_IPIN& ipin, uint32_t n = (uint32_t)N)
+    {
+        while (ipin.check_read()) {
+            int rc = SORA_OK;
+            if (!constructed_) { const sora_dcest11a_state s = { 8u, { 0, 0 }, { 0, 0 }, 0u }; rc = sora_hip_memcpy_h2d(d_state_, &s, sizeof(s)); constructed_ = rc == SORA_OK; }
+            const uint32_t tab[2] = { 0u, n };
+            if (rc == SORA_OK) rc = sora_hip_stream_synchronize(stream_);
+            if (rc == SORA_OK) rc = sora_hip_memcpy_h2d(d_tab_, tab, sizeof(tab));
+            if (rc == SORA_OK) rc = sora_hip_dc_estimate11a(ipin.peek(), d_tab_, d_tab_ + 1, d_state_, 1, N, stream_);
+            if (rc == SORA_OK) rc = sora_hip_stream_synchronize(stream_);
+            if (rc == SORA_OK) rc = sora_hip_memcpy_d2h(&dc_, &d_state_->dc, sizeof(dc_));
+            ipin.pop();
+            if (rc != SORA_OK) return false;
+        }
+        return true;
+    }
+    sora_complex16 DC() const { return dc_; }
+private:
+    sora_dcest11a_state* d_state_; uint32_t* d_tab_; void* stream_; sora_complex16 dc_ = { 0, 0 }; bool constructed_ = false;
+};
+// TCCA11a (Brick11/src/cca.hpp:104-441): IPORT COMPLEX16 x 4 N (DC-removed), a sink with a gated output: fills CF_11aCCA (CF_11CCA's cca_state, cca_pwr_reading,
+// cca_peak_index; cca_pwr_threshold is read when the record is constructed; CF_Error::error_code), reports the bursts it swallowed (used(): the rest of the burst is the
+// frame's) and leaves the bursts it hands to TDCEstimator in opin() (npass() of them).  d_state: one sora_cca11a_state that the adapter constructs; Reset() is the brick's
+// __init with cca_state and error_code cleared, as BB11aDemodContext::Reset and RxThread's ResetCarrierSense do it.
+struct CF_11aCCA { uint32_t cca_state = 0, cca_pwr_threshold = 1000 * 1000, cca_pwr_reading = 0, cca_peak_index = 0, error_code = 0; };
+template <size_t N>
+class THip11aCCA {
+public:
+    THip11aCCA(CF_11aCCA& ctx, sora_cca11a_state* d_state, sora_complex16* d_gated, void* d_tab, unsigned flags = 0, void* stream = nullptr)
+        : ctx_(ctx), d_state_(d_state), opin_(d_gated), d_tab_(static_cast<uint32_t*>(d_tab)), flags_(flags), stream_(stream) {}
+    void Flush() {}
+    bool Reset()
+    {
+        sora_cca11a_state s{};                                                                     // words 5 .. 43 are 0 after __init; words 2 .. 4 stand
+        const uint32_t zero[2] = { 0, 0 };
+        if (sora_hip_stream_synchronize(stream_) != SORA_OK || sora_hip_memcpy_h2d(d_state_, zero, 8) != SORA_OK ||
+            sora_hip_memcpy_h2d(&d_state_->sync_state, &s.sync_state, sizeof(s) - 20) != SORA_OK) return false;
+        ctx_.cca_state = 0; ctx_.error_code = 0;                                                   // only once the device record says so too
+        return true;
+    }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            int rc = SORA_OK;
+            if (!constructed_) {
+                sora_cca11a_state s{}; s.cca_pwr_threshold = ctx_.cca_pwr_threshold;
+                rc = sora_hip_memcpy_h2d(d_state_, &s, sizeof(s));
+                constructed_ = rc == SORA_OK;
+            }
+            const uint32_t tab[5] = { 0u, (uint32_t)N, 0u, 0u, 0u };                               // first, n, out_first, used, npass
+            uint32_t head[5] = { 0, 0, 0, 0, 0 }, res[2] = { 0, 0 };
+            if (rc == SORA_OK) rc = sora_hip_stream_synchronize(stream_);
+            if (rc == SORA_OK) rc = sora_hip_memcpy_h2d(d_tab_, tab, sizeof(tab));
+            if (rc == SORA_OK) rc = sora_hip_cca11a(ipin.peek(), d_tab_, d_tab_ + 1, d_tab_ + 2, d_state_, opin_.append(), d_tab_ + 3, d_tab_ + 4, 1, N, flags_, stream_);
+            if (rc == SORA_OK) rc = sora_hip_stream_synchronize(stream_);
+            if (rc == SORA_OK) rc = sora_hip_memcpy_d2h(head, d_state_, sizeof(head));
+            if (rc == SORA_OK) rc = sora_hip_memcpy_d2h(res, d_tab_ + 3, sizeof(res));
+            ipin.pop();
+            if (rc != SORA_OK) { ctx_.error_code = (uint32_t)rc; return false; }
+            ctx_.cca_state = head[0]; ctx_.error_code = head[1]; ctx_.cca_pwr_reading = head[3]; ctx_.cca_peak_index = head[4];
+            used_ = res[0]; npass_ = res[1];
+        }
+        return true;
+    }
+    DevicePin<sora_complex16, 4 * N>& opin() { return opin_; }
+    uint32_t used() const { return used_; }
+    uint32_t npass() const { return npass_; }
+private:
+    CF_11aCCA& ctx_; sora_cca11a_state* d_state_; DevicePin<sora_complex16, 4 * N> opin_; uint32_t* d_tab_; unsigned flags_; void* stream_;
+    uint32_t used_ = 0, npass_ = 0; bool constructed_ = false;
+};
+
+// ------------------------------------------------------------------------------------------------
 // The bricks of the 802.11b modulation graph (kernel/bb/demod11/fb11bmod_config.hpp:28-50) behind TBB11bSrc (sora_hip_ppdu11b, or the host's) and TBB11bMRSelect (the
 // host's: it only routes): one burst = N of the brick's own bursts, one stream per adapter, d_tab as above.  What the bricks keep lies in device records that the entry
 // points read and write back, so the state crosses from Process to Process by itself: the four spreaders share ONE sora_mod11b_state as the bricks share

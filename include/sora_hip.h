@@ -42,7 +42,9 @@ extern "C" {
  * _upsample40to44, _pack16to8, _preamble11a; the 802.11n modulation graphs' -- sora_hip_stream_parse11n, _interleave11n, _map11n, _sig_map11n, _add_pilot11n,
  * _ifft_only11n, _csd11n, _add_gi11n, _preamble11n; the 802.11b modulation graph's -- sora_hip_ppdu11b, _sc741_11b, _dbpsk_spread11b, _dqpsk_spread11b, _cck5_encode11b,
  * _cck11_encode11b, _pulse_shape11b (sora_mod11b_state, sora_shaper11b_state); the bricks that complete the 802.11n receive graph -- sora_hip_cca11n
- * (sora_cca11n_state), _data_symbol11n, _stream_join11n, and the tail it shares with the 802.11a graph, sora_hip_desc11a, _frame_sink11a (sora_sink11a_rec). */
+ * (sora_cca11n_state), _data_symbol11n, _stream_join11n, and the tail it shares with the 802.11a graph, sora_hip_desc11a, _frame_sink11a (sora_sink11a_rec); the front end
+ * of the 802.11a receive graph -- sora_hip_dc_remove11a, _dc_estimate11a (sora_dcest11a_state), _cca11a (sora_cca11a_state), _carrier_sense11a (sora_cs11a_state),
+ * _data_symbol11a, _viterbi_sig11a, _plcp_parse11a (sora_plcp11a_rec). */
 #define SORA_HIP_ABI_VERSION 4
 
 /* COMPLEX16: kernel/core/inc/complex.h */
@@ -752,6 +754,70 @@ int sora_hip_desc11a(const uint8_t* d_dec, const uint32_t* d_off, const uint32_t
  * byte_count with (ulong)(frame_length - 4), which has wrapped, so every byte goes into the CRC and it never decides: the record is 0, 0. */
 typedef struct { uint32_t error_code, frame_crc32; } sora_sink11a_rec;
 int sora_hip_frame_sink11a(const uint8_t* d_bytes, const uint32_t* d_off, const uint32_t* d_len, sora_sink11a_rec* d_rec, size_t n, void* stream);
+
+/* ---- The front end of the 802.11a receive graph (CreateDemodGraph11a_40M, fb11ademod_config.hpp:169-232) as stages: what stands in front of sora_hip_lts11a and the
+ * symbol chain, and the SIGNAL symbol's decoder and parser.  With them the graph reads
+ *     dc_remove11a -> cca11a -> dc_estimate11a  (or carrier_sense11a: the three with the loop closed) | lts11a | data_symbol11a -> freq_comp11a -> fft64 -> equalize11a ->
+ *     phase_comp11a -> pilot11a -> demap11a -> deinterleave11a -> viterbi_sig11a -> plcp_parse11a | .. -> viterbi11a -> desc11a -> frame_sink11a
+ * TBB11bRxSwitch, T11aSymSelEx, TBB11aRxRateSel, TNoInline, TThreadSeparator and TDropAny only route and stay the host's.  The conventions are those stated above
+ * sora_hip_cca11n and sora_hip_dc_remove11b: device pointers, stream order, no allocation, no host wait; a null pointer gives SORA_ERR_INVALID_PARAM before any device work
+ * (sora_hip_last_error() names the function), no device SORA_ERR_NO_DEVICE, a count of 0 is SORA_OK and launches nothing; a stateful brick works on a batch of independent
+ * streams described by the device tables d_first (SAMPLE index, no alignment) / d_n (bursts of 4 samples), max_n bounding every d_n[f] (bursts at or behind it are not
+ * touched; max_n = 0 launches nothing and writes nothing, d_used and d_npass included), with a per-stream record of 32-bit words that is read and written back,
+ * and the same stream cut into two calls gives what one call gives.  Every stage equals tests/rx11a_stage_model.py bit for bit (tests/test_gpu_11a_rx_stages.py).  DESIGN.md section 7, f2b. */
+#define SORA_CCA11A_STOP_ON_TIMEOUT 1u
+/* TDCRemoveEx<4>::Filter (brick/inc/dc.hpp:46-86), 4 -> 4: out = rep_sub(in, DC), 16-bit wrapping, with DC = d_dc[f] in all four elements (what CF_VecDC holds from its Reset
+ * on: TDCEstimator adds the same value to all four).  That is TDCRemove's arithmetic bit for bit, sora_hip_dc_remove11b's; as there, d_out_first[f] is a SAMPLE
+ * index.  The kernel is this entry's own because it stops a stream at max_n, which the 802.11b stage (whole 256-sample chunks) does not.  At most 65535 streams per call. */
+int sora_hip_dc_remove11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const sora_complex16* d_dc,
+                          sora_complex16* d_out, size_t nstreams, size_t max_n, void* stream);
+/* TDCEstimator (dc.hpp:99-165), 4 -> pass-through (not copied): sum_dc += hadd(in >> 5) per burst; the burst that finds update_cnt == 0 adds sum_dc >> 2 to DC, clears
+ * sum_dc and sets update_cnt to 8; every burst then decrements it.  All 16-bit wrapping.  sum_dc and dc are one element of the brick's vectors (the four are equal).
+ *   as constructed / after Reset():  update_cnt = 8, sum_dc = 0; dc stands (CF_VecDC::Reset makes it 0).  Domain: update_cnt 0 .. 8. */
+typedef struct { uint32_t update_cnt; sora_complex16 sum_dc, dc; uint32_t reserved; } sora_dcest11a_state;
+int sora_hip_dc_estimate11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_dcest11a_state* d_state, size_t nstreams, size_t max_n, void* stream);
+/* TCCA11a (Brick11/src/cca.hpp:104-441) alone, over DC-removed bursts at 20 MHz.  The record: the context fields the brick touches -- cca_state (0 power_clear, 1
+ * power_detected), error_code, cca_pwr_threshold (read only), cca_pwr_reading, cca_peak_index --, its members sync_state (0 no_energy, 1 high_energy), auto_count,
+ * sense_count, high_count, peak_corr, peak_index, sample_his as 16 samples in time order, already >> 2, and the three four-deep windows, oldest first, with their
+ * accumulators.  The brick's unused members (ac_norm_his, energy_sqr_his, dc_est) are not part of it.
+ *   as constructed:  every word 0 (a fresh context: cca_pwr_threshold is the host's; the reference harness sets 1000 * 1000)
+ *   after Reset():   __init (cca.hpp:279-295): sync_state, auto_count, sense_count, high_count, peak_corr, peak_index, sample_his and the three windows with their sums 0;
+ *                    the five context words stand (BB11aDemodContext::Reset clears cca_state and error_code)         (sora_amd.cca11a_states / cca11a_reset make both)
+ *   domain:          every record a brick can hold: sync_state 0 / 1, peak_index 0 .. 15, each sum the wrapping sum of its window; otherwise any words -- auto_count > 0,
+ *                    a lock held, a dropped lock's stale peak_corr / peak_index / high_count, a time-out standing.
+ * Stream f consumes bursts until cca_state becomes power_detected or d_n[f] runs out; d_used[f] = the bursts consumed, the deciding one included.  A stream that enters with
+ * power detected consumes nothing.  The gated output -- the bursts behind which sync_state is no_energy, which is what the brick hands to TDCEstimator -- is written
+ * compacted from BURST d_out_first[f] of d_out (room for d_n[f] bursts), their count in d_npass[f].
+ * Time-out, as the brick has it: sense_count >= 84 with no_energy at the end of a burst sets error_code = SORA_E_CS_TIMEOUT, and the walk goes on (the brick never looks at
+ * error_code).  SORA_CCA11A_STOP_ON_TIMEOUT: the stream ends behind the burst that CHANGES error_code to it; a stream that enters with the time-out standing is not stopped
+ * by it again.  Clearing it and applying Reset is the host's, as RxThread does at the end of the source call (fb11a_demod.cpp:47-57). */
+typedef struct {
+    uint32_t cca_state, error_code, cca_pwr_threshold, cca_pwr_reading, cca_peak_index;
+    uint32_t sync_state, auto_count, sense_count, high_count; int32_t peak_corr; uint32_t peak_index, reserved0;
+    sora_complex16 sample_his[16];
+    int32_t ac_re[4], ac_im[4], energy[4], ac_re_sum, ac_im_sum, energy_sum; uint32_t reserved1;
+} sora_cca11a_state;
+int sora_hip_cca11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_cca11a_state* d_state, sora_complex16* d_out,
+                    uint32_t* d_used, uint32_t* d_npass, size_t nstreams, size_t max_n, unsigned flags, void* stream);
+/* The loop TDCRemoveEx -> TCCA11a -> TDCEstimator as ONE entry over RAW bursts: the estimate feeds back into the subtraction every eight gated bursts, so separate calls
+ * have to be cut at each update.  d_used, the time-out and the flag as sora_hip_cca11a; no sample output.  Words 0-39 of the receive handle's continuation record
+ * (sora_rx_stream_record_of) are a function of this record: 0-15 sample_his, 16-19 / 20-23 / 24-27 the windows, 28-30 their sums, 31 sense_count, 32 high_count,
+ * 33 peak_corr, 34 peak_index, 35 update_cnt, 36 / 37 sum_dc re / im and 38 / 39 dc re / im, sign-extended (sora_amd.cs11a_record_words). */
+typedef struct { sora_cca11a_state cca; sora_dcest11a_state dc; } sora_cs11a_state;
+int sora_hip_carrier_sense11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_cs11a_state* d_state, uint32_t* d_used, size_t nstreams,
+                              size_t max_n, unsigned flags, void* stream);
+/* T11aDataSymbol (PHY_11a.hpp:361-430), 80 -> 64: frame f owns d_nsym[f] symbols of 80 samples from SAMPLE d_first[f] of d_in (no alignment beyond a sample's); samples
+ * 8..71 of symbol k (skip_cp = 8) go to SYMBOL d_out_first[f] + k of d_out, 64 samples each: the layout sora_hip_freq_comp11a / sora_hip_fft64 read.  The brick's
+ * remain_symbols count-down and its Flush at zero are the host's.  max_nsym bounds every d_nsym[f]; at most 65535 frames per call. */
+int sora_hip_data_symbol11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_out_first, sora_complex16* d_out, size_t nframes,
+                            size_t max_nsym, void* stream);
+/* T11aViterbiSig (viterbi.hpp:8-49): d_soft[n][48] (sora_hip_deinterleave11a's output at n_bpsc 1) -> d_sig[n] = Viterbi_sig11's 24 decoded bits >> 6 */
+int sora_hip_viterbi_sig11a(const uint8_t* d_soft, uint32_t* d_sig, size_t n, void* stream);
+/* T11aPLCPParser (PHY_11a.hpp:518-604): d_sig[n] -> d_rec[n]: the context fields from 0 as the parser leaves them, with every reject of _parse_plcp in its order.  Reserved
+ * bits (0xFC0010) or parity: nothing written.  Unknown rate code: data_rate_kbps written (0).  Length > 2500: data_rate_kbps, code_rate and frame_length written,
+ * total_symbols not.  error_code is 0 or SORA_E_PLCP_HEADER_FAIL; total_symbols counts the SIGNAL symbol (remain_symbols starts from it). */
+typedef struct { uint32_t error_code, data_rate_kbps, frame_length, code_rate, total_symbols; } sora_plcp11a_rec;
+int sora_hip_plcp_parse11a(const uint32_t* d_sig, sora_plcp11a_rec* d_rec, size_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 802.11n 2x2 receive graph = CreateDemodGraph11n (kernel/bb/demod11/fb11ndemod_config.hpp:166-257) driven by

@@ -14,6 +14,8 @@ from .capi import (Rx, Rx11b, Rx11n, RxHt40, ht40_symbols, HostResults, ROW_DTYP
                    dc_remove11b, energy_detect11b, symtiming11b, barker_sync11b, despread11b, sfd_sync11b, dbpsk_demap11b, dqpsk_demap11b, cck5p5_decode11b,
                    cck11_decode11b, desc741_11b, plcp_parse11b, frame_sink11b, rx11b_by_stages, rx11b_stages, state11b_reset, STATE11B_WORDS,
                    cca11n, cca11n_states, data_symbol11n, stream_join11n, desc11a, frame_sink11a, rx11n_by_stages, rx11n_stages, CCA11N_WORDS, CCA11N_REARM,
+                   dc_remove11a, dc_estimate11a, cca11a, carrier_sense11a, data_symbol11a, viterbi_sig11a, plcp_parse11a, cca11a_states, dcest11a_states, cs11a_states,
+                   cca11a_reset, cs11a_record_words, rx11a_stages, rx11a_by_stages, CCA11A_WORDS, DCEST11A_WORDS, CS11A_WORDS, CCA11A_STOP_ON_TIMEOUT,
                    ppdu11b, sc741_11b, dbpsk_spread11b, dqpsk_spread11b, cck5_encode11b, cck11_encode11b, pulse_shape11b, mod11b_by_stages, Mod11bStages,
                    tx11a, tx11a_samples, tx11n, tx11n_samples, tx_ht40, tx_ht40_samples, tx11b, tx11b_samples, INGEST_RXBLOCK, INGEST_RAW14, INGEST_44TO40, INGEST_DECIMATE2,
                    ht40_symbols_joint, HT40_CODING_PER_STREAM, HT40_CODING_JOINT, tx_ht40_joint, tx_ht40_joint_samples,

@@ -86,7 +86,9 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_hip_tx_ht40_joint", "sora_hip_tx_ht40_joint_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n",
-           "sora_hip_cca11n", "sora_hip_data_symbol11n", "sora_hip_stream_join11n", "sora_hip_desc11a", "sora_hip_frame_sink11a", "sora_rx11b_create",
+           "sora_hip_cca11n", "sora_hip_data_symbol11n", "sora_hip_stream_join11n", "sora_hip_desc11a", "sora_hip_frame_sink11a",
+           "sora_hip_dc_remove11a", "sora_hip_dc_estimate11a", "sora_hip_cca11a", "sora_hip_carrier_sense11a", "sora_hip_data_symbol11a", "sora_hip_viterbi_sig11a",
+           "sora_hip_plcp_parse11a", "sora_rx11b_create",
                       "sora_rx11b_destroy", "sora_rx11b_stream", "sora_rx11b_synchronize", "sora_rx11b_process_dev", "sora_rx11b_process", "sora_rx11b_results", "sora_rx11b_ticket",
                       "sora_rx11b_calls_in_flight", "sora_rx11b_set_single_pass", "sora_rx11b_set_preamble", "sora_rx11b_wait", "sora_rx11b_wait_any", "sora_rx11b_stream_of", "sora_rx11b_results_of",
                       "sora_rx11b_deliver_async", "sora_rx11b_set_stream_mode", "sora_rx11b_stream_consumed", "sora_rx11n_deliver_async",
@@ -310,6 +312,14 @@ def load(build_if_missing=True):
     L.sora_hip_stream_join11n.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_desc11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_frame_sink11a.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]
+    # the front end of the 802.11a receive graph
+    L.sora_hip_dc_remove11a.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_dc_estimate11a.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_cca11a.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p]
+    L.sora_hip_carrier_sense11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p]
+    L.sora_hip_data_symbol11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_viterbi_sig11a.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_plcp_parse11a.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
     L.sora_rx11n_create.argtypes = [ctypes.POINTER(RxCfg), ctypes.POINTER(ctypes.c_void_p)]
     L.sora_rx11n_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11n_process.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
@@ -2076,6 +2086,317 @@ def rx11n_by_stages(d_iq0, d_iq1, descs, mcs_max=10, trace=None):
     A DEMONSTRATION and a test vehicle, not a fast path: between stages it reads counts and records back to the host to build the next tables, and the data field costs
     some ten calls per OFDM symbol.  It does not reproduce the flush of zero-padded symbols at the end of a capture.  The fast path is Rx11n."""
     return rx11n_stages(_Gpu11nOps(d_iq0.device), d_iq0, d_iq1, descs, mcs_max, trace)
+
+
+# ---- the front end of the 802.11a receive graph as stages (include/sora_hip.h, sora_hip_dc_remove11a .. sora_hip_plcp_parse11a)
+# sora_cca11a_state as int32 words [n, 44]: 0 cca_state, 1 error_code, 2 cca_pwr_threshold, 3 cca_pwr_reading, 4 cca_peak_index, 5 sync_state, 6 auto_count, 7 sense_count,
+# 8 high_count, 9 peak_corr, 10 peak_index, 12..27 sample_his (re | im << 16, oldest first, already >> 2), 28..31 / 32..35 / 36..39 the ac_re / ac_im / energy windows,
+# oldest first, 40..42 their sums.  sora_dcest11a_state [n, 4]: 0 update_cnt, 1 sum_dc, 2 dc (packed).  sora_cs11a_state [n, 48]: the two, one behind the other.
+CCA11A_WORDS, DCEST11A_WORDS, CS11A_WORDS = 44, 4, 48
+CCA11A_STOP_ON_TIMEOUT = 1
+E_CS_TIMEOUT = 0x80000007
+
+
+def dcest11a_states(n):
+    """-> int32 numpy [n, 4]: sora_dcest11a_state as constructed, in a fresh context: update_cnt 8, sum_dc 0, dc 0"""
+    s = np.zeros((n, DCEST11A_WORDS), np.int32); s[:, 0] = 8
+    return s
+
+
+def cca11a_states(n, cca_pwr_threshold=1000 * 1000):
+    """-> int32 numpy [n, 44]: sora_cca11a_state as a constructed TCCA11a holds it in a fresh context: all 0 but the threshold (the reference harness's by default)"""
+    s = np.zeros((n, CCA11A_WORDS), np.int32); s[:, 2] = np.uint32(cca_pwr_threshold).astype(np.int32)
+    return s
+
+
+def cs11a_states(n, cca_pwr_threshold=1000 * 1000):
+    """-> int32 numpy [n, 48]: sora_cs11a_state as constructed"""
+    return np.concatenate([cca11a_states(n, cca_pwr_threshold), dcest11a_states(n)], axis=1)
+
+
+def cca11a_reset(state, context=True):
+    """Reset() on records (int32 numpy [n, 44] or [n, 48]), in place: TCCA11a::__init (and TDCEstimator::__init: update_cnt 8, sum_dc 0; dc stands); context: also
+    what BB11aDemodContext::Reset / ResetCarrierSense clear, cca_state and error_code.  -> state"""
+    state[:, 5:44] = 0
+    if state.shape[1] == CS11A_WORDS:
+        state[:, 44] = 8; state[:, 45] = 0
+    if context:
+        state[:, 0:2] = 0
+    return state
+
+
+def cs11a_record_words(state):
+    """One sora_cs11a_state (48 words) -> words 0-39 of the receive handle's 64-word continuation record (Rx.stream_record_of; oracle.cs_trace) as uint32 [40].  Pure:
+    a relabelling, with sum_dc and dc unpacked and sign-extended."""
+    s = (np.asarray(state).astype(np.int64) & 0xFFFFFFFF).astype(np.uint32).reshape(CS11A_WORDS)
+    w = np.zeros(40, np.uint32)
+    w[0:16] = s[12:28]; w[16:28] = s[28:40]; w[28:31] = s[40:43]
+    w[31] = s[7]; w[32] = s[8]; w[33] = s[9]; w[34] = s[10]; w[35] = s[44]
+    for k, v in ((36, s[45]), (38, s[46])):
+        h = np.array([v & 0xFFFF, v >> 16], np.uint16).view(np.int16).astype(np.int32).view(np.uint32)
+        w[k] = h[0]; w[k + 1] = h[1]
+    return w
+
+
+def dc_remove11a(x, first, n, out_first, dc, out, max_n=None, stream=None):
+    """TDCRemoveEx<4>: stream f = n[f] bursts of 4 from sample first[f] of x (int16 CUDA [samples, 2]) minus dc[f] (int16 CUDA [streams, 2]) -> out from sample out_first[f]"""
+    _check(load().sora_hip_dc_remove11a(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(out_first), _dev_ptr(dc), _dev_ptr(out), first.shape[0], _max_n(n, max_n),
+                                        _stream_ptr(stream)))
+    return out
+
+
+def dc_estimate11a(x, first, n, state, max_n=None, stream=None):
+    """TDCEstimator: state int32 CUDA [streams, 4] (in / out) -> state"""
+    _check(load().sora_hip_dc_estimate11a(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(state), first.shape[0], _max_n(n, max_n), _stream_ptr(stream)))
+    return state
+
+
+def cca11a(x, first, n, out_first, state, out, flags=0, max_n=None, stream=None):
+    """TCCA11a over DC-removed bursts: x int16 CUDA [samples, 2] at 20 MHz; first (samples) / n (bursts) / out_first (BURSTS of out) int32 CUDA [streams]; state int32 CUDA
+    [streams, 44] (in / out); out int16 CUDA [samples, 2] receives the gated bursts -> (used, npass) int32 CUDA [streams]"""
+    import torch
+    used = torch.zeros(first.shape[0], dtype=torch.int32, device=x.device); npass = torch.zeros_like(used)
+    _check(load().sora_hip_cca11a(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(out_first), _dev_ptr(state), _dev_ptr(out), _dev_ptr(used), _dev_ptr(npass),
+                                  first.shape[0], _max_n(n, max_n), int(flags), _stream_ptr(stream)))
+    return used, npass
+
+
+def carrier_sense11a(x, first, n, state, flags=0, max_n=None, stream=None):
+    """TDCRemoveEx -> TCCA11a -> TDCEstimator over raw bursts: state int32 CUDA [streams, 48] (in / out) -> used int32 CUDA [streams]"""
+    import torch
+    used = torch.zeros(first.shape[0], dtype=torch.int32, device=x.device)
+    _check(load().sora_hip_carrier_sense11a(_dev_ptr(x), _dev_ptr(first), _dev_ptr(n), _dev_ptr(state), _dev_ptr(used), first.shape[0], _max_n(n, max_n), int(flags),
+                                            _stream_ptr(stream)))
+    return used
+
+
+def data_symbol11a(x, first, nsym, out_first, out, max_nsym=None, stream=None):
+    """T11aDataSymbol: frame f's nsym[f] symbols of 80 samples from sample first[f] of x -> their samples 8..71 at symbol out_first[f] of out (int16 CUDA [symbols * 64, 2])"""
+    _check(load().sora_hip_data_symbol11a(_dev_ptr(x), _dev_ptr(first), _dev_ptr(nsym), _dev_ptr(out_first), _dev_ptr(out), first.shape[0], _max_n(nsym, max_nsym),
+                                          _stream_ptr(stream)))
+    return out
+
+
+def viterbi_sig11a(soft, stream=None):
+    """T11aViterbiSig: soft uint8 CUDA [n, 48] -> int32 CUDA [n]: the decoded SIGNAL bits >> 6"""
+    import torch
+    sig = torch.zeros(soft.shape[0], dtype=torch.int32, device=soft.device)
+    _check(load().sora_hip_viterbi_sig11a(_dev_ptr(soft), _dev_ptr(sig), soft.shape[0], _stream_ptr(stream)))
+    return sig
+
+
+def plcp_parse11a(sig, stream=None):
+    """T11aPLCPParser: sig int32 CUDA [n] -> int32 CUDA [n, 5]: error_code, data_rate_kbps, frame_length, code_rate, total_symbols"""
+    import torch
+    rec = torch.zeros((sig.shape[0], 5), dtype=torch.int32, device=sig.device)
+    _check(load().sora_hip_plcp_parse11a(_dev_ptr(sig), _dev_ptr(rec), sig.shape[0], _stream_ptr(stream)))
+    return rec
+
+
+class _Gpu11aOps:
+    """rx11a_stages' bricks on the GPU: host tables and records (numpy) up, one stage call each, records back.  Buffers are torch CUDA tensors; a frame's context is
+    [sora_lts11a_ctx row, sora_track11a_state row]."""
+
+    def __init__(self, device):
+        import torch
+        self.torch = torch; self.dev = device
+
+    def _up(self, a, dt=np.int32):
+        return self.torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(dt, copy=False))).to(self.dev)
+
+    def downsample2(self, iq):
+        return ingest(iq, INGEST_DECIMATE2)
+
+    def carrier_sense(self, x, first, n, state, flags):
+        st = self._up(state)
+        used = carrier_sense11a(x, self._up(first), self._up(n), st, flags, max_n=int(max(n)))
+        return st.cpu().numpy(), used.cpu().numpy()
+
+    def _take(self, x, starts, length):
+        idx = (self._up(starts, np.int64)[:, None] + self.torch.arange(length, device=self.dev)[None, :]).reshape(-1)
+        return x[idx].contiguous()
+
+    def lts(self, x, starts):
+        ctx = lts11a(self._take(x, starts, 144).reshape(-1, 144, 2))
+        trk = np.zeros((len(starts), 134), np.int16); trk[:, 4] = 127; trk[:, 6::2] = 0x7FFF      # CF_PhaseCompensate / CF_PilotTrack after Reset (pilot.hpp:143-152)
+        trk = self._up(trk, np.int16)
+        return [[ctx[i:i + 1], trk[i:i + 1]] for i in range(len(starts))], ctx[:, 0].cpu().numpy()
+
+    def symbols(self, x, starts, ctxs):
+        n = len(starts)
+        y = self.torch.zeros((n * 64, 2), dtype=self.torch.int16, device=self.dev)
+        data_symbol11a(x, self._up(starts), self._up(np.ones(n)), self._up(np.arange(n)), y, max_nsym=1)
+        ctx = self.torch.cat([c[0] for c in ctxs]).contiguous(); idx = self._up(np.arange(n))
+        return equalize11a(fft64(freq_comp11a(y.reshape(n, 64, 2), ctx, idx)), ctx, idx)
+
+    def track(self, eq, ctxs):
+        n = len(ctxs)
+        st = self.torch.cat([c[1] for c in ctxs]).contiguous(); idx = self._up(np.arange(n))
+        out = pilot11a(phase_comp11a(eq, st, idx), idx, self._up(np.ones(n)), st)
+        for i, c in enumerate(ctxs):
+            c[1] = st[i:i + 1]
+        return out
+
+    def demap_deint(self, x, nb):
+        return deinterleave11a(demap11a(x, nb), nb)
+
+    def rows(self, a, idx):
+        return a[self._up(idx, np.int64)].contiguous()
+
+    def concat(self, parts):
+        return self.torch.cat([p.reshape(-1) for p in parts]).contiguous()
+
+    def viterbi_sig(self, soft):
+        return viterbi_sig11a(soft)
+
+    def plcp_parse(self, sig):
+        return plcp_parse11a(sig).cpu().numpy().view(np.uint32)
+
+    def viterbi(self, soft, soft_off, nsoft, lens, code_rate):
+        return viterbi11a(soft, self._up(soft_off), self._up(nsoft), self._up(lens, np.int16), int(code_rate)).reshape(-1)
+
+    def desc(self, dec, off, lens, out_off, total):
+        out = self.torch.zeros(max(total, 1), dtype=self.torch.uint8, device=self.dev)
+        return desc11a(dec, self._up(off), self._up(lens), out, self._up(out_off))
+
+    def frame_sink(self, x, off, lens):
+        return frame_sink11a(x, self._up(off), self._up(lens)).cpu().numpy().view(np.uint32)
+
+    def host(self, a):
+        return a.cpu().numpy()
+
+
+def rx11a_stages(ops, iq, descs, sample_rate_mhz=40, cca_pwr_threshold=1000 * 1000):
+    """The 802.11a receive graph (CreateDemodGraph11a_40M under RxThread, fb11a_demod.cpp:29-81) composed from the brick stages through `ops` (the GPU's:
+    rx11a_by_stages; the model's: tests/rx11a_stage_model.ModelOps), along the walk of oracle/so_rx11a.c:691-768.  The host plays TMemSamples' source calls (14 samples at
+    the 20 MHz rate, bursts of 4 as they fit), the routing bricks and RxThread: carrier sense runs with SORA_CCA11A_STOP_ON_TIMEOUT; the remaining bursts of the source call
+    that raised the time-out run with it standing; then Reset.  After power_detected 144 samples go to lts11a, the SIGNAL symbol through the symbol stages, demap11a(1),
+    deinterleave11a(1), viterbi_sig11a and plcp_parse11a, the data symbols by rate to viterbi11a, desc11a and frame_sink11a; then the frame reset, with the source's
+    partial burst dropped (the next burst starts on the call grid).  Captures advance in rounds: each round is one call per stage over all captures in that phase.
+    iq: the captures at 40 MHz (even offsets, whole 28-sample source calls) or at 20 MHz (whole 14-sample calls), descs [(first sample, samples)].
+    -> per capture the list of EVERY event, dicts with the fields of the handle's rows: start_sample, end_sample, error_code, rate_kbps, length, nsym, crc32, cfo_est, mpdu.
+    The 44 MHz graph's queue rule (TDownSample44_40 keeps its queue over a frame reset) is out of scope."""
+    if sample_rate_mhz not in (40, 20):
+        raise ValueError("rx11a_stages: 40 or 20 MHz (the 44 MHz graph's queue rule is not composed)")
+    per = 2 if sample_rate_mhz == 40 else 1
+    nc = len(descs)
+    off = np.array([int(d[0]) for d in descs], np.int64); ns = np.array([int(d[1]) for d in descs], np.int64)
+    if nc and ((ns % (14 * per)).any() or (off % per).any()):
+        raise ValueError("rx11a_stages: a capture is whole source calls (28 samples at 40 MHz, 14 at 20) at an even offset")
+    x = ops.downsample2(iq) if per == 2 else iq
+    base = off // per; n20 = np.minimum(ns // per, int(x.shape[0]) - base)
+    u32 = lambda a: np.asarray(a, np.int64).astype(np.uint32).view(np.int32)
+    call_end = lambda p: (p + 13) // 14 * 14
+    st = cs11a_states(nc, cca_pwr_threshold)
+    p = np.zeros(nc, np.int64); phase = ["cs"] * nc; tail = np.zeros(nc, np.int64)
+    events = [[] for _ in range(nc)]; fr = [dict() for _ in range(nc)]
+    nbpsc = {6000: 1, 9000: 1, 12000: 2, 18000: 2, 24000: 4, 36000: 4, 48000: 6, 54000: 6}
+
+    def frame_reset(c, at):
+        p[c] = call_end(at); cca11a_reset(st[c:c + 1]); phase[c] = "cs" if p[c] + 4 <= n20[c] else "done"
+
+    def fits(g, need):
+        """the captures of g with `need(c)` more samples in them; the others end here without an event"""
+        go = [c for c in g if p[c] + need(c) <= n20[c]]
+        for c in g:
+            if c not in go:
+                phase[c] = "done"
+        return go
+
+    def sense(g):                                                                # ---- TDCRemoveEx -> TCCA11a -> TDCEstimator behind TBB11bRxSwitch
+        s, used = ops.carrier_sense(x, u32(base[g] + p[g]), u32((n20[g] - p[g]) // 4), st[g], CCA11A_STOP_ON_TIMEOUT)
+        for i, c in enumerate(g):
+            st[c] = s[i]; p[c] += 4 * int(used[i])
+            if st[c, 0] == 1:
+                fr[c] = {"start": int(p[c])}; phase[c] = "lts"
+            elif np.uint32(st[c, 1]) == E_CS_TIMEOUT:
+                tail[c] = (min(call_end(p[c]), n20[c]) - p[c]) // 4; phase[c] = "tail"
+            else:
+                phase[c] = "done"
+
+    def call_tail(g):                                                            # ---- the rest of the source call with the time-out standing, then ResetCarrierSense + Reset
+        if tail[g].any():
+            s, used = ops.carrier_sense(x, u32(base[g] + p[g]), u32(tail[g]), st[g], 0)
+            for i, c in enumerate(g):
+                st[c] = s[i]; p[c] += 4 * int(used[i])
+        for c in g:
+            cca11a_reset(st[c:c + 1]); phase[c] = "cs"
+
+    def lts(g):                                                                  # ---- T11aSymSelEx -> T11aLTS
+        go = fits(g, lambda c: 144)
+        if go:
+            ctxs, cfo = ops.lts(x, u32(base[go] + p[go]))
+            for i, c in enumerate(go):
+                fr[c]["ctx"] = ctxs[i]; fr[c]["cfo"] = int(cfo[i]); p[c] += 144; phase[c] = "sig"
+
+    def signal(g):                                                               # ---- the SIGNAL symbol
+        go = fits(g, lambda c: 80)
+        if not go:
+            return
+        ctxs = [fr[c]["ctx"] for c in go]
+        trk = ops.track(ops.symbols(x, u32(base[go] + p[go]), ctxs), ctxs)
+        rec = ops.plcp_parse(ops.viterbi_sig(ops.demap_deint(trk, 1)))
+        for i, c in enumerate(go):
+            p[c] += 80
+            if rec[i, 0]:                                                        # RxThread sees it at the end of the source call; the call's last bursts are consumed
+                end = p[c] + (min(call_end(p[c]), n20[c]) - p[c]) // 4 * 4
+                events[c].append({"start_sample": fr[c]["start"], "end_sample": int(end), "error_code": int(rec[i, 0]), "rate_kbps": 0, "length": 0, "nsym": 0,
+                                  "crc32": 0, "cfo_est": fr[c]["cfo"], "mpdu": b""})
+                frame_reset(c, p[c])
+            else:
+                fr[c].update(rate=int(rec[i, 1]), length=int(rec[i, 2]), cr=int(rec[i, 3]), nsym=int(rec[i, 4]) - 1); phase[c] = "data"
+
+    def data(g):                                                                 # ---- the data symbols, by rate to the trellis, T11aDesc, TBB11aFrameSink
+        go = fits(g, lambda c: 80 * fr[c]["nsym"])
+        if not go:
+            return
+        chunks = {c: [] for c in go}
+        for k in range(max(fr[c]["nsym"] for c in go)):
+            al = [c for c in go if fr[c]["nsym"] > k]
+            ctxs = [fr[c]["ctx"] for c in al]
+            trk = ops.track(ops.symbols(x, u32(base[al] + p[al] + 80 * k), ctxs), ctxs)
+            for b in (1, 2, 4, 6):
+                sel = [i for i, c in enumerate(al) if nbpsc[fr[c]["rate"]] == b]
+                if sel:
+                    soft = ops.demap_deint(ops.rows(trk, sel), b)
+                    for j, i in enumerate(sel):
+                        chunks[al[i]].append(soft[j])
+        for rate in (0, 1, 2):
+            js = [c for c in go if fr[c]["cr"] == rate]
+            if not js:
+                continue
+            nsoft = np.array([48 * nbpsc[fr[c]["rate"]] * fr[c]["nsym"] for c in js], np.int64)
+            lens = np.array([fr[c]["length"] for c in js], np.int64)
+            dec = ops.viterbi(ops.concat([q for c in js for q in chunks[c]]), u32(np.concatenate([[0], np.cumsum(nsoft)])[:-1]), u32(nsoft), lens, rate)
+            boff = 2504 * np.arange(len(js))
+            by = ops.desc(dec, u32(2560 * np.arange(len(js))), u32(lens), u32(boff), 2504 * len(js))
+            srec = ops.frame_sink(by, u32(boff), u32(lens)); hb = ops.host(by)
+            for i, c in enumerate(js):
+                end = int(p[c] + 80 * fr[c]["nsym"])
+                events[c].append({"start_sample": fr[c]["start"], "end_sample": end, "error_code": int(srec[i, 0]), "rate_kbps": fr[c]["rate"], "length": fr[c]["length"],
+                                  "nsym": fr[c]["nsym"], "crc32": int(srec[i, 1]), "cfo_est": fr[c]["cfo"], "mpdu": hb[boff[i]:boff[i] + lens[i]].tobytes()})
+                frame_reset(c, end)
+
+    while True:                                                                  # a round: every capture takes the step of its phase, one call per stage over each group
+        for c in range(nc):
+            if phase[c] == "cs" and p[c] + 4 > n20[c]:
+                phase[c] = "done"
+        for name, step in (("cs", sense), ("tail", call_tail), ("lts", lts), ("sig", signal), ("data", data)):
+            g = [c for c in range(nc) if phase[c] == name]
+            if g:
+                step(g)
+        if all(ph == "done" for ph in phase):
+            return events
+
+
+def rx11a_by_stages(d_iq, descs, sample_rate_mhz=40, cca_pwr_threshold=1000 * 1000):
+    """EVERY event of every capture of a batch, through the 802.11a stage entry points alone (rx11a_stages with the GPU's bricks): d_iq int16 CUDA [samples, 2] at 40 or
+    20 MHz, descs [(first sample, samples)] -> per capture a list of dicts with the fields of the handle's rows.
+    A DEMONSTRATION and a test vehicle, not a fast path: every round reads counts and records back to the host to build the next tables -- two carrier-sense calls and
+    two round trips per time-out (every 21 bursts of silence), some eight calls per OFDM symbol.  Measured on 512 captures of one short frame each: 15 to 23 ms of host
+    wall clock against 9 ms for Rx.process_dev + wait on the same batch; the rounds grow with the silence and the symbols of the longest capture.
+    The 44 MHz graph's queue rule is out of scope.  The fast path is Rx."""
+    return rx11a_stages(_Gpu11aOps(d_iq.device), d_iq, descs, sample_rate_mhz, cca_pwr_threshold)
 
 
 def tx11n_samples(mpdu_len_nofcs, mcs):

@@ -163,6 +163,17 @@ __global__ void k_11b_sfd_sync(const uint32_t* in, const uint32_t* first, const 
 __global__ void k_11b_plcp_parse(const uint8_t* hdr, uint32_t* rec, uint32_t nstreams);
 __global__ void k_11b_frame_sink(const uint8_t* bytes, const uint32_t* first, const uint32_t* len, uint32_t* rec, uint32_t nstreams, const uint32_t* crc_tab);
 
+// ---- the 802.11a receive graph's front-end bricks as stages (k_11a.hip): one wave per stream (the three carrier-sense bricks: grid = nstreams), a workgroup row per frame
+// (data_symbol), a wave / a lane per SIGNAL symbol; first[f] in samples, n[f] in bursts of 4 clamped to max_n
+__global__ void k_11a_dc_remove(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, const uint32_t* dc, uint32_t max_n);
+__global__ void k_11a_dc_estimate(const uint32_t* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t max_n);
+__global__ void k_11a_cca(const uint32_t* in, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, uint32_t* state, uint32_t* out, uint32_t* used, uint32_t* npass,
+                          uint32_t max_n, uint32_t flags, const uint32_t* sts);
+__global__ void k_11a_carrier_sense(const uint32_t* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t* used, uint32_t max_n, uint32_t flags, const uint32_t* sts);
+__global__ void k_11a_data_symbol(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* nsym, const uint32_t* out_first, uint32_t max_nsym);
+__global__ void k_11a_viterbi_sig(const uint8_t* soft, uint32_t* sig, uint32_t n);
+__global__ void k_11a_plcp_parse(const uint32_t* sig, uint32_t* rec, uint32_t n);
+
 // ---- 802.11n 2x2 transmitter (k_tx11n.hip)
 struct Tx11nArgs {             // sora_hip_tx11n
     const uint8_t*  mpdu;      // MPDUs without FCS, frame f at mpdu + off[f]
