@@ -686,6 +686,84 @@ public:
 };
 
 // ------------------------------------------------------------------------------------------------
+// The 40 MHz HT 2x2 receiver's stage bricks (sora_hip_*_ht40), one burst = N symbols (or one frame).  Where the reference's bricks of this
+// kind have two ports (two RX chains in, two spatial streams out) the two are the two halves of one burst, as in THip11nMimoComp.  The stages that take device tables
+// (data symbol, tracker) get a small device array d_tab, which the adapter fills once: one frame that owns the burst.  tests/cxx/rx_ht40_chain.cpp runs a frame through them.
+//   THipHt40DataSymbol<N>   IPORT COMPLEX16 x 2 x 160 N -> OPORT COMPLEX16 x 2 x 128 N        (d_tab: 3 words)
+struct CallDataSymbolHt40 {
+    const uint32_t* d_tab; size_t n;
+    int operator()(const sora_complex16* in, sora_complex16* out, void* st) const
+    { return sora_hip_data_symbol_ht40(in, in + 160 * n, d_tab, d_tab + 1, d_tab + 2, out, out + 128 * n, 1, n, st); }
+};
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipHt40DataSymbol : THipStage<sora_complex16, 320 * N, sora_complex16, 256 * N, CallDataSymbolHt40, T_CTX, T_NEXT> {
+    THipHt40DataSymbol(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, uint32_t* d_tab, void* stream = nullptr)
+        : THipStage<sora_complex16, 320 * N, sora_complex16, 256 * N, CallDataSymbolHt40, T_CTX, T_NEXT>(ctx, next, d_out, CallDataSymbolHt40{ d_tab, N }, stream)
+    { const uint32_t t[3] = { 0u, (uint32_t)N, 0u }; this->raise(sora_hip_memcpy_h2d(d_tab, t, sizeof(t))); }
+};
+//   THipHt40MimoEst         IPORT COMPLEX16 x 2 x 256 (HT-LTF 1 | 2 of chain 0, then of chain 1, after FFT<128>) -> OPORT COMPLEX16 x 512: the weights; d_noise_var: one
+//                           float on the device or null (zero forcing); d_h: room for the channel matrix (512) or null
+struct CallMimoEstHt40 {
+    const float* d_noise_var; sora_complex16* d_h;
+    int operator()(const sora_complex16* in, sora_complex16* out, void* st) const { return sora_hip_mimo_est_ht40(in, in + 256, d_noise_var, d_h, out, 1, st); }
+};
+template <class T_CTX, class T_NEXT>
+struct THipHt40MimoEst : THipStage<sora_complex16, 512, sora_complex16, 512, CallMimoEstHt40, T_CTX, T_NEXT> {
+    THipHt40MimoEst(T_CTX& ctx, T_NEXT* next, sora_complex16* d_w, const float* d_noise_var = nullptr, sora_complex16* d_h = nullptr, void* stream = nullptr)
+        : THipStage<sora_complex16, 512, sora_complex16, 512, CallMimoEstHt40, T_CTX, T_NEXT>(ctx, next, d_w, CallMimoEstHt40{ d_noise_var, d_h }, stream) {}
+};
+//   THipHt40MimoComp<N>     IPORT COMPLEX16 x 2 x 128 N (chain 0 symbols, then chain 1) -> OPORT COMPLEX16 x 2 x 128 N (stream 0, then stream 1)
+struct CallMimoCompHt40 {
+    const sora_complex16* d_w; size_t n;
+    int operator()(const sora_complex16* in, sora_complex16* out, void* st) const { return sora_hip_mimo_comp_ht40(d_w, nullptr, in, in + 128 * n, out, out + 128 * n, n, st); }
+};
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipHt40MimoComp : THipStage<sora_complex16, 256 * N, sora_complex16, 256 * N, CallMimoCompHt40, T_CTX, T_NEXT> {
+    THipHt40MimoComp(T_CTX& ctx, T_NEXT* next, const sora_complex16* d_w, sora_complex16* d_out, void* stream = nullptr)
+        : THipStage<sora_complex16, 256 * N, sora_complex16, 256 * N, CallMimoCompHt40, T_CTX, T_NEXT>(ctx, next, d_out, CallMimoCompHt40{ d_w, N }, stream) {}
+};
+//   THipHt40PilotTrack<N>   IPORT COMPLEX16 x 2 x 128 N (stream 0 symbols, then stream 1) -> OPORT int16 x N: theta after each symbol; d_state: the frame's
+//                           CF_FreqOffset_11n record (24 int16), read and written                  (d_tab: 2 words)
+struct CallPilotTrackHt40 {
+    int16_t* d_state; const uint32_t* d_tab; size_t n;
+    int operator()(const sora_complex16* in, int16_t* out, void* st) const { return sora_hip_pilot_track_ht40(in, in + 128 * n, d_tab, d_tab + 1, d_state, out, 1, st); }
+};
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipHt40PilotTrack : THipStage<sora_complex16, 256 * N, int16_t, N, CallPilotTrackHt40, T_CTX, T_NEXT> {
+    THipHt40PilotTrack(T_CTX& ctx, T_NEXT* next, int16_t* d_state, int16_t* d_theta, uint32_t* d_tab, void* stream = nullptr)
+        : THipStage<sora_complex16, 256 * N, int16_t, N, CallPilotTrackHt40, T_CTX, T_NEXT>(ctx, next, d_theta, CallPilotTrackHt40{ d_state, d_tab, N }, stream)
+    { const uint32_t t[2] = { 0u, (uint32_t)N }; this->raise(sora_hip_memcpy_h2d(d_tab, t, sizeof(t))); }
+};
+//   THipHt40Demap<N_BPSC, N>, THipHt40Deinterleave<N_BPSC, SPATIAL_STREAM, N>, THipHt40StreamJoin<N_BPSC, N> (stream 0's symbols, then stream 1's -> the joint job's bytes)
+struct CallDemapHt40 { int nb; size_t n; int operator()(const sora_complex16* in, uint8_t* out, void* st) const { return sora_hip_demap_ht40(in, out, nb, n, st); } };
+template <int N_BPSC, size_t N, class T_CTX, class T_NEXT>
+struct THipHt40Demap : THipStage<sora_complex16, 128 * N, uint8_t, 108 * N_BPSC * N, CallDemapHt40, T_CTX, T_NEXT> {
+    THipHt40Demap(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* stream = nullptr)
+        : THipStage<sora_complex16, 128 * N, uint8_t, 108 * N_BPSC * N, CallDemapHt40, T_CTX, T_NEXT>(ctx, next, d_out, CallDemapHt40{ N_BPSC, N }, stream) {}
+};
+struct CallDeintHt40 { int nb, ss; size_t n; int operator()(const uint8_t* in, uint8_t* out, void* st) const { return sora_hip_deinterleave_ht40(in, out, nb, ss, n, st); } };
+template <int N_BPSC, int SPATIAL_STREAM, size_t N, class T_CTX, class T_NEXT>
+struct THipHt40Deinterleave : THipStage<uint8_t, 108 * N_BPSC * N, uint8_t, 108 * N_BPSC * N, CallDeintHt40, T_CTX, T_NEXT> {
+    THipHt40Deinterleave(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* stream = nullptr)
+        : THipStage<uint8_t, 108 * N_BPSC * N, uint8_t, 108 * N_BPSC * N, CallDeintHt40, T_CTX, T_NEXT>(ctx, next, d_out, CallDeintHt40{ N_BPSC, SPATIAL_STREAM, N }, stream) {}
+};
+struct CallStreamJoinHt40 { int nb; size_t n; int operator()(const uint8_t* in, uint8_t* out, void* st) const { return sora_hip_stream_join_ht40(in, in + 108 * nb * n, out, nb, n, st); } };
+template <int N_BPSC, size_t N, class T_CTX, class T_NEXT>
+struct THipHt40StreamJoin : THipStage<uint8_t, 216 * N_BPSC * N, uint8_t, 216 * N_BPSC * N, CallStreamJoinHt40, T_CTX, T_NEXT> {
+    THipHt40StreamJoin(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* stream = nullptr)
+        : THipStage<uint8_t, 216 * N_BPSC * N, uint8_t, 216 * N_BPSC * N, CallStreamJoinHt40, T_CTX, T_NEXT>(ctx, next, d_out, CallStreamJoinHt40{ N_BPSC, N }, stream) {}
+};
+//   THipHt40NoiseVar        IPORT COMPLEX16 x 2 x 128 (the two L-LTF symbols of chain 0, then of chain 1, after FFT<64>) -> OPORT float x 1; d_S: the integer sum or null
+struct CallNoiseVarHt40 { uint64_t* d_S; int operator()(const sora_complex16* in, float* out, void* st) const { return sora_hip_noise_var_ht40(in, in + 128, d_S, out, 1, st); } };
+template <class T_CTX, class T_NEXT>
+struct THipHt40NoiseVar : THipStage<sora_complex16, 256, float, 1, CallNoiseVarHt40, T_CTX, T_NEXT> {
+    THipHt40NoiseVar(T_CTX& ctx, T_NEXT* next, float* d_out, uint64_t* d_S = nullptr, void* stream = nullptr)
+        : THipStage<sora_complex16, 256, float, 1, CallNoiseVarHt40, T_CTX, T_NEXT>(ctx, next, d_out, CallNoiseVarHt40{ d_S }, stream) {}
+};
+// (sora_hip_downsample_ht40 has no fixed ratio per call -- a stream's parity runs on from call to call -- and stays a plain entry point.)
+
+
+// ------------------------------------------------------------------------------------------------
 // The bricks that complete the 802.11n receive graph (kernel/bb/demod11/fb11ndemod_config.hpp:166-264), each where its SSE brick sits.  The bricks with NSTREAM = 2 ports
 // carry the two chains / spatial streams as the two halves of one burst, as THip11nMimoComp does.  d_tab: 16 bytes of device memory, the adapter's own (its tables).
 // T11nDataSymbol (PHY_11n.hpp:288-356): IPORT COMPLEX16 x 2 x 80 N (chain 0's N symbols, then chain 1's) -> OPORT COMPLEX16 x 2 x 64 N.  remain_symbols and the Flush at

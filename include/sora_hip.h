@@ -41,7 +41,8 @@ extern "C" {
  * Additive since: the 802.11a modulation graph's bricks as stages -- sora_hip_scramble11a, _conv_encode11a, _interleave11a, _map11a, _add_pilot11a (_from), _ifftx11a,
  * _upsample40to44, _pack16to8, _preamble11a; the 802.11n modulation graphs' -- sora_hip_stream_parse11n, _interleave11n, _map11n, _sig_map11n, _add_pilot11n,
  * _ifft_only11n, _csd11n, _add_gi11n, _preamble11n; the 802.11b modulation graph's -- sora_hip_ppdu11b, _sc741_11b, _dbpsk_spread11b, _dqpsk_spread11b, _cck5_encode11b,
- * _cck11_encode11b, _pulse_shape11b (sora_mod11b_state, sora_shaper11b_state); the bricks that complete the 802.11n receive graph -- sora_hip_cca11n
+ * _cck11_encode11b, _pulse_shape11b (sora_mod11b_state, sora_shaper11b_state); the 40 MHz HT receiver's bricks -- sora_hip_data_symbol_ht40, _mimo_est_ht40, _mimo_comp_ht40,
+ * _pilot_track_ht40, _demap_ht40, _deinterleave_ht40, _stream_join_ht40, _downsample_ht40, _noise_var_ht40; the bricks that complete the 802.11n receive graph -- sora_hip_cca11n
  * (sora_cca11n_state), _data_symbol11n, _stream_join11n, and the tail it shares with the 802.11a graph, sora_hip_desc11a, _frame_sink11a (sora_sink11a_rec); the front end
  * of the 802.11a receive graph -- sora_hip_dc_remove11a, _dc_estimate11a (sora_dcest11a_state), _cca11a (sora_cca11a_state), _carrier_sense11a (sora_cs11a_state),
  * _data_symbol11a, _viterbi_sig11a, _plcp_parse11a (sora_plcp11a_rec). */
@@ -818,6 +819,54 @@ int sora_hip_viterbi_sig11a(const uint8_t* d_soft, uint32_t* d_sig, size_t n, vo
  * total_symbols not.  error_code is 0 or SORA_E_PLCP_HEADER_FAIL; total_symbols counts the SIGNAL symbol (remain_symbols starts from it). */
 typedef struct { uint32_t error_code, data_rate_kbps, frame_length, code_rate, total_symbols; } sora_plcp11a_rec;
 int sora_hip_plcp_parse11a(const uint32_t* d_sig, sora_plcp11a_rec* d_rec, size_t n, void* stream);
+
+/* ---- The 40 MHz HT 2x2 receiver (sora_ht40_* below; parity unpinned, see there) as stages: the bricks of its data field and what its front end adds to the 802.11n stages.
+ * With them every receive graph of the library stands as stages, and a host can replace ONE piece of this one -- its own detector in place of the unbiased MMSE, another
+ * pilot tracker, its own noise estimate -- or compose the whole (sora_amd.rx_ht40_by_stages, rx_ht40_front_by_stages):
+ *     downsample_ht40 -> the 802.11n stages cca11n .. sig_decode11n, the HT40 gate on the host | noise_var_ht40                              (front end: raw capture -> descriptor)
+ *     freq_comp11n -> data_symbol_ht40 -> fft128 -> mimo_est_ht40                                                                           (HT-LTF 1 / 2)
+ *     freq_comp11n -> data_symbol_ht40 -> fft128 -> mimo_comp_ht40 -> pilot_track_ht40        (symbol by symbol: theta of symbol d rotates symbol d + 1)
+ *                  -> demap_ht40 -> deinterleave_ht40 (-> stream_join_ht40 in the joint coding) -> viterbi11n_ws -> desc11a -> frame_sink11a
+ * sora_hip_freq_comp11n with d_state[f] = { (n0 + k) cfo | 8 cfo | theta } is the 40 MHz frequency compensation of the burst that starts n0 samples into the frame.  The
+ * conventions are those stated above sora_hip_cca11n: device pointers, stream order, no allocation, no host wait; a null pointer gives SORA_ERR_INVALID_PARAM before any device
+ * work (sora_hip_last_error() names the function), a count of 0 is SORA_OK and launches nothing, no device SORA_ERR_NO_DEVICE.  The layouts are the handle's: weights and
+ * channel matrix [frame][4][128] COMPLEX16 (entries 00, 01, 10, 11 per FFT bin), symbols [symbol][128].  Every stage equals tests/ht40_stage_model.py bit for bit
+ * (tests/test_gpu_ht40_stages.py).  Buffers that are 16-byte (byte streams: 4-byte) aligned take the wide loads and stores; others work, more slowly.  DESIGN.md section 7, g1b. */
+/* 2 x 160 -> 2 x 128, sora_hip_data_symbol11n at 40 MHz: frame f owns d_nsym[f] symbols of 160 samples from SAMPLE d_first[f] of both chains; samples 32..159 of symbol k go
+ * to SYMBOL d_out_first[f] + k of d_out0 / d_out1, 128 samples each: the layout sora_hip_fft128 reads.  max_nsym >= every d_nsym[f]; at most 65535 frames per call. */
+int sora_hip_data_symbol_ht40(const sora_complex16* d_in0, const sora_complex16* d_in1, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_out_first,
+                              sora_complex16* d_out0, sora_complex16* d_out1, size_t nframes, size_t max_nsym, void* stream);
+/* d_ltf_r[f][256] = HT-LTF 1 | HT-LTF 2 of RX chain r after FFT<128>; d_noise_var[f] per carrier in LSB^2 of the FFT output, >= 0 (NULL: 0 for every frame).
+ * d_h[f][4][128] (optional): TMimoChannelEst's P-matrix combination (p - q) / 2, (p + q) / 2 per chain, negated where the 40 MHz HT-LTF is -1.  d_w[f][4][128]: the
+ * detection weights x 2^16 -- at noise_var 0 the brick's own 2x2 inverse (zero forcing), else the handle's unbiased MMSE W = diag((W' H)_ss)^-1 W', W' = (H^H H + s2 I)^-1 H^H
+ * in single precision (+-1 LSB against a float64 evaluation), bit for bit what sora_ht40_process_dev exports as d_weights.  The 14 bins outside the 114 occupied carriers are 0
+ * in both outputs (the handle leaves them meaningless). */
+int sora_hip_mimo_est_ht40(const sora_complex16* d_ltf0, const sora_complex16* d_ltf1, const float* d_noise_var, sora_complex16* d_h, sora_complex16* d_w, size_t nframes,
+                           void* stream);
+/* TMimoChannelComp over 128 bins: x = sat((W y) >> 9); symbol s uses d_w[d_frame_index[s]] (NULL: frame 0); y_r = RX chain r after FFT<128>, x_k = spatial stream k */
+int sora_hip_mimo_comp_ht40(const sora_complex16* d_w, const uint32_t* d_frame_index, const sora_complex16* d_y0, const sora_complex16* d_y1, sora_complex16* d_x0,
+                            sora_complex16* d_x1, size_t nsym, void* stream);
+/* The handle's pilot phase update: frame f owns symbols d_first[f] .. + d_nsym[f] - 1 of the two detected streams; per symbol theta += ((sum of stream 0's six dsp_atan16 at
+ * bins -+53, -+25, -+11) / 6 + (stream 1's) / 6) >> 1, C division, every step through int16.  theta = vfo_theta_i[0..7] of d_state[f][24], the record sora_hip_freq_comp11n
+ * reads: every entry takes the increments and is written back; the other sixteen words are not touched.  d_theta[s] (optional): vfo_theta_i[0] as it stands after symbol s. */
+int sora_hip_pilot_track_ht40(const sora_complex16* d_x0, const sora_complex16* d_x1, const uint32_t* d_first, const uint32_t* d_nsym, int16_t* d_state, int16_t* d_theta,
+                              size_t nframes, void* stream);
+/* T11nDemap{BPSK,QPSK,QAM16,QAM64} over the 108 data carriers (-58..-2, 2..58 without the pilots): d_in[n][128] -> d_soft[n][108 N_BPSC] soft values 0..7, per carrier the I
+ * bits then the Q bits.  n_bpsc 1, 2, 4 or 6, else SORA_ERR_INVALID_PARAM (so for the two stages below). */
+int sora_hip_demap_ht40(const sora_complex16* d_in, uint8_t* d_soft, int n_bpsc, size_t n, void* stream);
+/* The HT interleaver for 40 MHz (N_COL 18, N_ROW 6 N_BPSC, N_ROT 29) inverted: d_in / d_out [n][108 N_BPSC] of spatial stream 0 or 1 */
+int sora_hip_deinterleave_ht40(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, int spatial_stream, size_t n, void* stream);
+/* The joint coding's de-parser (TStreamJoin + TStreamConcat, sora_hip_stream_join11n at 108 carriers): two de-interleaved streams [n][108 N_BPSC] -> d_out[n][216 N_BPSC] in
+ * groups of s = max(1, N_BPSC / 2) bytes alternating stream 0, stream 1: byte for byte one joint job's soft values for sora_hip_viterbi11n_ws. */
+int sora_hip_stream_join_ht40(const uint8_t* d_s0, const uint8_t* d_s1, uint8_t* d_out, int n_bpsc, size_t n, void* stream);
+/* The derotating decimator of the front end, both chains: stream f reads raw samples d_first[f] + 2 m, m = 0 .. d_n[f] - 1 (nothing behind the last of them), and writes kept
+ * sample m at SAMPLE d_out_first[f] + m of d_out0 / d_out1: x[2m], negated with int16 saturation (-(-32768) = 32767) when d_m0[f] + m is odd.  d_m0[f] = the number (only its
+ * parity counts) of the stream's first kept sample, so a stream cut into two calls gives what one call gives.  max_n bounds every d_n[f]; at most 65535 streams per call. */
+int sora_hip_downsample_ht40(const sora_complex16* d_in0, const sora_complex16* d_in1, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_m0,
+                             const uint32_t* d_out_first, sora_complex16* d_out0, sora_complex16* d_out1, size_t nstreams, size_t max_n, void* stream);
+/* The front end's noise estimate: d_lltf_r[f][128] = the two L-LTF symbols of chain r after FFT<64> -> d_S[f] (optional) = the sum over both chains and the 52 occupied
+ * carriers (bins 1..26, 38..63) of |Y1 - Y2|^2, an exact integer, and d_noise_var[f] = S / 416 rounded once to single precision. */
+int sora_hip_noise_var_ht40(const sora_complex16* d_lltf0, const sora_complex16* d_lltf1, uint64_t* d_S, float* d_noise_var, size_t nframes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 802.11n 2x2 receive graph = CreateDemodGraph11n (kernel/bb/demod11/fb11ndemod_config.hpp:166-257) driven by

@@ -88,7 +88,9 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n",
            "sora_hip_cca11n", "sora_hip_data_symbol11n", "sora_hip_stream_join11n", "sora_hip_desc11a", "sora_hip_frame_sink11a",
            "sora_hip_dc_remove11a", "sora_hip_dc_estimate11a", "sora_hip_cca11a", "sora_hip_carrier_sense11a", "sora_hip_data_symbol11a", "sora_hip_viterbi_sig11a",
-           "sora_hip_plcp_parse11a", "sora_rx11b_create",
+           "sora_hip_plcp_parse11a",
+           "sora_hip_data_symbol_ht40", "sora_hip_mimo_est_ht40", "sora_hip_mimo_comp_ht40", "sora_hip_pilot_track_ht40", "sora_hip_demap_ht40", "sora_hip_deinterleave_ht40",
+           "sora_hip_stream_join_ht40", "sora_hip_downsample_ht40", "sora_hip_noise_var_ht40", "sora_rx11b_create",
                       "sora_rx11b_destroy", "sora_rx11b_stream", "sora_rx11b_synchronize", "sora_rx11b_process_dev", "sora_rx11b_process", "sora_rx11b_results", "sora_rx11b_ticket",
                       "sora_rx11b_calls_in_flight", "sora_rx11b_set_single_pass", "sora_rx11b_set_preamble", "sora_rx11b_wait", "sora_rx11b_wait_any", "sora_rx11b_stream_of", "sora_rx11b_results_of",
                       "sora_rx11b_deliver_async", "sora_rx11b_set_stream_mode", "sora_rx11b_stream_consumed", "sora_rx11n_deliver_async",
@@ -320,6 +322,16 @@ def load(build_if_missing=True):
     L.sora_hip_data_symbol11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_viterbi_sig11a.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_plcp_parse11a.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
+    # the 40 MHz HT receiver's bricks as stages
+    L.sora_hip_data_symbol_ht40.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_mimo_est_ht40.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_mimo_comp_ht40.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_pilot_track_ht40.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_demap_ht40.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_deinterleave_ht40.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_stream_join_ht40.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_downsample_ht40.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_noise_var_ht40.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]
     L.sora_rx11n_create.argtypes = [ctypes.POINTER(RxCfg), ctypes.POINTER(ctypes.c_void_p)]
     L.sora_rx11n_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
     L.sora_rx11n_process.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(CaptureDesc), ctypes.c_size_t]
@@ -2948,3 +2960,318 @@ def mod11b_by_stages(mpdus, rates_kbps, phase_in=None, preamble=None, device=0, 
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(None)))
     return out, plan.offsets, [int(v) for v in plan.state[:, 0].cpu().numpy()]
+
+
+# ---- the 40 MHz HT 2x2 receiver's bricks as stages (include/sora_hip.h, sora_hip_data_symbol_ht40 .. sora_hip_noise_var_ht40)
+def data_symbol_ht40(in0, in1, first, nsym, out_first, out0, out1, max_nsym=None, stream=None):
+    """2 x 160 -> 2 x 128: frame f's nsym[f] symbols of 160 samples from sample first[f] of in0 / in1 -> their samples 32..159 at symbol out_first[f] of out0 / out1
+    (int16 CUDA [symbols * 128, 2])"""
+    _check(load().sora_hip_data_symbol_ht40(_dev_ptr(in0), _dev_ptr(in1), _dev_ptr(first), _dev_ptr(nsym), _dev_ptr(out_first), _dev_ptr(out0), _dev_ptr(out1),
+                                            first.shape[0], _max_n(nsym, max_nsym), _stream_ptr(stream)))
+    return out0, out1
+
+
+def mimo_est_ht40(ltf0, ltf1, noise_var=None, want_h=True, stream=None):
+    """ltf0 / ltf1: int16 CUDA [n, 256, 2] (HT-LTF 1 | HT-LTF 2 of RX chain 0 / 1 after FFT<128>); noise_var: float32 CUDA [n] or None (zero forcing)
+    -> (h or None, w) int16 CUDA [n, 4, 128, 2]: the channel matrix and the detection weights x 2^16, entries 00, 01, 10, 11 per bin"""
+    import torch
+    n = ltf0.shape[0]
+    w = torch.empty((n, 4, 128, 2), dtype=torch.int16, device=ltf0.device)
+    h = torch.empty_like(w) if want_h else None
+    _check(load().sora_hip_mimo_est_ht40(_dev_ptr(ltf0), _dev_ptr(ltf1), _dev_ptr(noise_var) if noise_var is not None else None, _dev_ptr(h) if want_h else None,
+                                         _dev_ptr(w), n, _stream_ptr(stream)))
+    return h, w
+
+
+def mimo_comp_ht40(w, y0, y1, frame_index=None, stream=None):
+    """w: int16 CUDA [nframes, 4, 128, 2]; y0 / y1: int16 CUDA [nsym, 128, 2]; frame_index: int32 CUDA [nsym] or None -> (x0, x1), the two spatial streams"""
+    import torch
+    x0 = torch.empty_like(y0); x1 = torch.empty_like(y1)
+    _check(load().sora_hip_mimo_comp_ht40(_dev_ptr(w), _dev_ptr(frame_index) if frame_index is not None else None, _dev_ptr(y0), _dev_ptr(y1), _dev_ptr(x0), _dev_ptr(x1),
+                                          y0.shape[0], _stream_ptr(stream)))
+    return x0, x1
+
+
+def pilot_track_ht40(x0, x1, first, nsym, state, want_theta=True, stream=None):
+    """x0 / x1: int16 CUDA [nsym_total, 128, 2]; first / nsym: int32 CUDA [nframes]; state int16 CUDA [nframes, 24], words 16..23 updated in place
+    -> theta int16 CUDA [nsym_total] (word 16 as it stands after each symbol) or None"""
+    import torch
+    th = torch.zeros(x0.shape[0], dtype=torch.int16, device=x0.device) if want_theta else None
+    _check(load().sora_hip_pilot_track_ht40(_dev_ptr(x0), _dev_ptr(x1), _dev_ptr(first), _dev_ptr(nsym), _dev_ptr(state), _dev_ptr(th) if want_theta else None,
+                                            state.shape[0], _stream_ptr(stream)))
+    return th
+
+
+def demap_ht40(x, n_bpsc, stream=None):
+    """x: int16 CUDA [n, 128, 2] (the detected symbols of one spatial stream) -> uint8 CUDA [n, 108 n_bpsc]"""
+    import torch
+    out = torch.empty((x.shape[0], 108 * n_bpsc), dtype=torch.uint8, device=x.device)
+    _check(load().sora_hip_demap_ht40(_dev_ptr(x), _dev_ptr(out), int(n_bpsc), x.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def deinterleave_ht40(s, n_bpsc, spatial_stream, stream=None):
+    """s: uint8 CUDA [n, 108 n_bpsc] of spatial stream 0 or 1 -> de-interleaved, same shape"""
+    import torch
+    out = torch.empty_like(s)
+    _check(load().sora_hip_deinterleave_ht40(_dev_ptr(s), _dev_ptr(out), int(n_bpsc), int(spatial_stream), s.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def stream_join_ht40(s0, s1, n_bpsc, out=None, stream=None):
+    """s0 / s1 uint8 CUDA [n, 108 n_bpsc] -> uint8 CUDA [n, 216 n_bpsc], groups of max(n_bpsc / 2, 1) bytes alternating stream 0 / 1"""
+    import torch
+    n = s0.shape[0]
+    if out is None:
+        out = torch.empty((n, 216 * n_bpsc), dtype=torch.uint8, device=s0.device)
+    _check(load().sora_hip_stream_join_ht40(_dev_ptr(s0), _dev_ptr(s1), _dev_ptr(out), int(n_bpsc), n, _stream_ptr(stream)))
+    return out
+
+
+def downsample_ht40(in0, in1, first, n, m0, out_first, out0, out1, max_n=None, stream=None):
+    """the derotating decimator: stream f's kept sample m = raw sample first[f] + 2 m of in0 / in1, negated (saturating) when m0[f] + m is odd, at sample out_first[f] + m of
+    out0 / out1; first / n / m0 / out_first int32 CUDA [streams]"""
+    _check(load().sora_hip_downsample_ht40(_dev_ptr(in0), _dev_ptr(in1), _dev_ptr(first), _dev_ptr(n), _dev_ptr(m0), _dev_ptr(out_first), _dev_ptr(out0), _dev_ptr(out1),
+                                           first.shape[0], _max_n(n, max_n), _stream_ptr(stream)))
+    return out0, out1
+
+
+def noise_var_ht40(lltf0, lltf1, stream=None):
+    """lltf0 / lltf1: int16 CUDA [n, 128, 2] (the two L-LTF symbols of chain 0 / 1 after FFT<64>) -> (S int64 CUDA [n], noise_var float32 CUDA [n])"""
+    import torch
+    n = lltf0.shape[0]
+    S = torch.zeros(n, dtype=torch.int64, device=lltf0.device); nv = torch.zeros(n, dtype=torch.float32, device=lltf0.device)
+    _check(load().sora_hip_noise_var_ht40(_dev_ptr(lltf0), _dev_ptr(lltf1), _dev_ptr(S), _dev_ptr(nv), n, _stream_ptr(stream)))
+    return S, nv
+
+
+class _GpuHt40Ops(_Gpu11nOps):
+    """rx_ht40_stages' bricks on the GPU (the 802.11n ones it shares are _Gpu11nOps'); downsample / noise_var are the front end's two own stages"""
+    VOUT = 4352                                                                   # decoded bytes per job: LENGTH <= 4000
+
+    def state(self, rec):
+        return self._up(rec, np.int16)
+
+    def downsample(self, iq0, iq1, first, n, m0, out_first, total):
+        o0 = self.torch.zeros((max(total, 1), 2), dtype=self.torch.int16, device=self.dev); o1 = self.torch.zeros_like(o0)
+        downsample_ht40(iq0, iq1, self._up(first), self._up(n), self._up(m0), self._up(out_first), o0, o1, max_n=int(max(n)))
+        return o0[:total], o1[:total]
+
+    def noise_var(self, l0, l1):
+        S, nv = noise_var_ht40(l0.reshape(-1, 128, 2), l1.reshape(-1, 128, 2))
+        return S.cpu().numpy(), nv.cpu().numpy()
+
+    def data_symbol(self, x0, x1, first, nsym, out_first, total):
+        o0 = self.torch.zeros((max(total, 1) * 128, 2), dtype=self.torch.int16, device=self.dev); o1 = self.torch.zeros_like(o0)
+        data_symbol_ht40(x0, x1, self._up(first), self._up(nsym), self._up(out_first), o0, o1, max_nsym=int(max(nsym)))
+        return o0[:total * 128], o1[:total * 128]
+
+    def fft128(self, x):
+        return fft128(x.reshape(-1, 128, 2)).reshape(-1, 2)
+
+    def mimo_est(self, l0, l1, noise_var):
+        return mimo_est_ht40(l0.reshape(-1, 256, 2), l1.reshape(-1, 256, 2), self._up(noise_var, np.float32))
+
+    def mimo_comp(self, w, y0, y1, frame_index):
+        return mimo_comp_ht40(w, y0.reshape(-1, 128, 2), y1.reshape(-1, 128, 2), self._up(frame_index))
+
+    def pilot_track(self, x0, x1, first, nsym, state):
+        return pilot_track_ht40(x0, x1, self._up(first), self._up(nsym), state).cpu().numpy()
+
+    def demap(self, x, nb):
+        return demap_ht40(x.reshape(-1, 128, 2), nb)
+
+    def deinterleave(self, s, nb, iss):
+        return deinterleave_ht40(s, nb, iss)
+
+    def stream_join(self, s0, s1, nb):
+        return stream_join_ht40(s0, s1, nb)
+
+    def viterbi(self, soft, soft_off, nsoft, lens, code_rate):
+        ws = self.torch.empty(viterbi11n_workspace_bytes(soft.numel(), len(lens)), dtype=self.torch.uint8, device=self.dev)
+        out = viterbi11n_ws(soft, self._up(soft_off), self._up(nsoft), self._up(lens, np.int16), int(code_rate), ws, out_stride=self.VOUT)
+        self.torch.cuda.synchronize(self.dev)
+        return out.reshape(-1)
+
+
+def ht40_frame_symbols(d, coding=0):
+    """data symbols of the described frame d = (offset, n_bpsc, code_rate, length0, length1, ...) in the given coding: ceil((16 + 8 LENGTH + 6) / N_DBPS), N_DBPS = 108 N_BPSC R
+    per stream (sora_ht40_symbols), twice that over the one PSDU of the joint coding (sora_ht40_symbols_joint); 0: a bad descriptor"""
+    nb, cr = int(d[1]), int(d[2])
+    if nb not in (1, 2, 4, 6) or cr not in (0, 1, 2):
+        return 0
+    nd = 108 * nb * (1, 2, 3)[cr] // (2, 3, 4)[cr]
+    if coding == HT40_CODING_JOINT:
+        return (16 + 8 * int(d[3]) + 6 + 2 * nd - 1) // (2 * nd)
+    return (16 + 8 * max(int(d[3]), int(d[4])) + 6 + nd - 1) // nd
+
+
+def rx_ht40_stages(ops, iq0, iq1, frames, coding=0):
+    """The data field of described 40 MHz HT two-stream frames (what sora_ht40_process_dev decodes) composed from the stage entry points through `ops` (the GPU's:
+    rx_ht40_by_stages; the model's: tests/ht40_stage_model.ModelOps).  frames: [(offset, n_bpsc, code_rate, length0, length1, cfo, noise_var[, id])], the handle's
+    descriptors; coding HT40_CODING_PER_STREAM (two PSDUs, two rows per frame) or HT40_CODING_JOINT (length1 = 0, one row).  The host builds the tables; nothing is read back
+    between stages but the tracked phase it reports.
+      1. freq_comp11n over the two HT-LTF symbols (state {k cfo | 8 cfo | 0}: the brick's own advance keeps the phase n cfo - theta running over the frame) ->
+         data_symbol_ht40 -> fft128 -> mimo_est_ht40;
+      2. symbol by symbol over the batch, because theta of symbol d rotates symbol d + 1: freq_comp11n -> data_symbol_ht40 -> fft128 -> mimo_comp_ht40 -> pilot_track_ht40;
+         a frame that has ended takes part with a count of 0;
+      3. over all symbols of a modulation at once: demap_ht40 -> deinterleave_ht40 (-> stream_join_ht40) -> per code rate viterbi11n_ws -> desc11a -> frame_sink11a.
+    -> dict: rows [{frame, stream, error_code, length, crc32, nsym, mpdu}] (frame-major), soft (per frame [stream 0, stream 1] uint8, or the merged bytes in joint coding),
+    theta (per frame int16 [nsym + 1]: theta[d] compensates symbol d, the last entry stands after the last symbol), weights and h (ops buffers [frames, 4, 128, 2]), xs (per
+    frame int16 [nsym, 2, 128, 2], the detected symbols)."""
+    joint = coding == HT40_CODING_JOINT
+    nf = len(frames)
+    if nf == 0:
+        return {"rows": [], "soft": [], "theta": [], "weights": None, "h": None, "xs": []}
+    nsym = np.array([ht40_frame_symbols(d, coding) for d in frames], np.int64)
+    for d, n in zip(frames, nsym):
+        if n == 0 or d[3] > 4000 or d[4] > 4000 or (joint and d[4] != 0) or not (d[6] >= 0):
+            raise ValueError("rx_ht40_stages: bad frame descriptor (n_bpsc 1/2/4/6, code_rate 0..2, PSDU <= 4000 bytes, noise_var >= 0; joint coding: length1 = 0)")
+    off = np.array([int(d[0]) for d in frames], np.int64); nbp = np.array([int(d[1]) for d in frames], np.int64)
+    cfo = np.array([int(d[5]) for d in frames], np.int64)
+    u32 = lambda a: np.asarray(a, np.int64).astype(np.uint32).view(np.int32)
+    i16 = lambda a: ((np.asarray(a, np.int64) + 32768) & 0xFFFF) - 32768
+    rec = np.zeros((nf, 24), np.int16)
+    rec[:, :8] = i16(cfo[:, None] * np.arange(8)[None, :]); rec[:, 8:16] = i16(8 * cfo)[:, None]
+    st = ops.state(rec)
+    # ---- 1. the two HT-LTF symbols
+    c0, c1 = ops.freq_comp(iq0, iq1, u32(off), u32(np.full(nf, 40)), st)
+    y0, y1 = ops.data_symbol(c0, c1, u32(off), u32(np.full(nf, 2)), u32(2 * np.arange(nf)), 2 * nf)
+    h, w = ops.mimo_est(ops.fft128(y0), ops.fft128(y1), np.array([d[6] for d in frames], np.float32))
+    # ---- 2. the data symbols
+    theta = [[0] for _ in range(nf)]
+    xs0 = [[] for _ in range(nf)]; xs1 = [[] for _ in range(nf)]
+    for d in range(int(nsym.max())):
+        al = np.nonzero(nsym > d)[0]
+        nbur = np.zeros(nf, np.int64); nbur[al] = 20
+        c0, c1 = ops.freq_comp(iq0, iq1, u32(off + 320 + 160 * d), u32(nbur), st)
+        y0, y1 = ops.data_symbol(c0, c1, u32(off[al] + 320 + 160 * d), u32(np.ones(len(al))), u32(np.arange(len(al))), len(al))
+        x0, x1 = ops.mimo_comp(w, ops.fft128(y0), ops.fft128(y1), u32(al))
+        pf = np.zeros(nf, np.int64); pn = np.zeros(nf, np.int64); pf[al] = np.arange(len(al)); pn[al] = 1
+        th = ops.pilot_track(x0, x1, u32(pf), u32(pn), st)
+        for i, f in enumerate(al):
+            theta[f].append(int(th[i])); xs0[f].append(x0[i]); xs1[f].append(x1[i])
+    # ---- 3. per modulation: every symbol at once
+    soft = [None] * nf
+    for b in (1, 2, 4, 6):
+        fs = [f for f in range(nf) if nbp[f] == b]
+        if not fs:
+            continue
+        d0 = ops.deinterleave(ops.demap(ops.concat([x for f in fs for x in xs0[f]]), b), b, 0)
+        d1 = ops.deinterleave(ops.demap(ops.concat([x for f in fs for x in xs1[f]]), b), b, 1)
+        jn = ops.stream_join(d0, d1, b) if joint else None
+        at = 0
+        for f in fs:
+            n = int(nsym[f])
+            soft[f] = jn[at:at + n].reshape(-1) if joint else [d0[at:at + n].reshape(-1), d1[at:at + n].reshape(-1)]
+            at += n
+    jobs = [(f, 0) for f in range(nf)] if joint else [(f, s) for f in range(nf) for s in range(2)]
+    rows = [None] * len(jobs)
+    for rate in (0, 1, 2):
+        js = [j for j, (f, s) in enumerate(jobs) if frames[f][2] == rate]
+        if not js:
+            continue
+        parts = [soft[jobs[j][0]] if joint else soft[jobs[j][0]][jobs[j][1]] for j in js]
+        nsoft = np.array([int(p.shape[0]) for p in parts], np.int64)
+        lens = np.array([int(frames[jobs[j][0]][3 + jobs[j][1]]) for j in js], np.int64)
+        dec = ops.viterbi(ops.concat(parts), u32(np.concatenate([[0], np.cumsum(nsoft)])[:-1]), u32(nsoft), lens, rate)
+        boff = 4096 * np.arange(len(js))
+        by = ops.desc(dec, u32(ops.VOUT * np.arange(len(js))), u32(lens), u32(boff), 4096 * len(js))
+        srec = ops.frame_sink(by, u32(boff), u32(lens)); hb = ops.host(by)
+        for i, j in enumerate(js):
+            f, s = jobs[j]
+            rows[j] = {"frame": f, "stream": s, "error_code": int(srec[i, 0]), "length": int(lens[i]), "crc32": int(srec[i, 1]), "nsym": int(nsym[f]),
+                       "mpdu": hb[boff[i]:boff[i] + lens[i]].tobytes()}
+    xs = [np.stack([np.stack([ops.host(a).reshape(128, 2), ops.host(b).reshape(128, 2)]) for a, b in zip(xs0[f], xs1[f])]) for f in range(nf)]
+    return {"rows": rows, "soft": [ops.host(s) if joint else [ops.host(s[0]), ops.host(s[1])] for s in soft], "theta": [np.array(t, np.int16) for t in theta],
+            "weights": w, "h": h, "xs": xs}
+
+
+def rx_ht40_by_stages(d_iq0, d_iq1, frames, coding=0):
+    """sora_ht40_process_dev's result for the described frames through the stage entry points alone (rx_ht40_stages with the GPU's bricks): d_iq0 / d_iq1 int16 CUDA
+    [samples, 2].  A DEMONSTRATION and a test vehicle, not a fast path: five launches per OFDM symbol of the longest frame and every intermediate through HBM, against the
+    handle's one kernel.  The fast path is RxHt40."""
+    return rx_ht40_stages(_GpuHt40Ops(d_iq0.device), d_iq0, d_iq1, frames, coding)
+
+
+def ht40_sig_gate(rec):
+    """The 40 MHz front end's gate on the decoded bits of one sora_hip_sig_decode11n record (words 9..11): T11nSigParser's checks in front of its own gate (L-SIG reserved
+    bits, parity, rate code, LENGTH field; HT-SIG CRC-8), then 8 <= MCS <= 14 && CBW 40 && 4 <= LENGTH <= 4000 -> None (SORA_E_PLCP_HEADER_FAIL) or (mcs, ht_length)"""
+    sig = int(rec[9]) & 0xFFFFFF; ht = int(rec[10]) | (int(rec[11]) << 32)
+    if (sig & 0xFC0010) or (bin(sig).count("1") & 1) or (sig & 0xF) < 8 or ((sig >> 5) & 0xFFF) * 2 > 1500:
+        return None
+    crc = 0xFF
+    for b in range(34):
+        crc ^= (ht >> b) & 1
+        crc = (crc >> 1) ^ 0xE0 if crc & 1 else crc >> 1
+    if ((~crc) & 0xFF) != ((ht >> 34) & 0x3FFF):
+        return None
+    mcs = ht & 0x7F; cbw40 = (ht >> 7) & 1; length = (ht >> 8) & 0xFFFF
+    if mcs < 8 or mcs > 14 or not cbw40 or length < 4 or length > 4000:
+        return None
+    return mcs, length
+
+
+def rx_ht40_front_stages(ops, iq0, iq1, descs, coding=0):
+    """The front end of the 40 MHz HT receiver (what sora_ht40_process_captures_dev does in front of its data field) up to the FIRST event of every capture, composed from
+    stages through `ops`: downsample_ht40 -> the 802.11n stages along rx11n_stages' walk (cca11n | cfo_est11n -> freq_comp11n -> fft64 -> siso_est11n | freq_comp11n ->
+    data_symbol11n -> fft64 -> siso_comp11n -> sig_demap11n -> sig_decode11n) -> ht40_sig_gate on the host -> noise_var_ht40 on the L-LTF's transforms.
+    descs: [(first sample, samples)] over the two chains at 40 MHz, whole 28-sample source calls at offsets that are multiples of 4.
+    -> per capture None (no detection; the capture ends inside the header; a sound header whose frame runs past the capture: no event, as the handle has it) or a
+    sora_ht40_found-shaped dict a20, mcs, ht_len, nsym, cfo, noise_var (numpy float32), S, end_sample, error_code, and, for a recorded frame, "descriptor": the sora_ht40_frame
+    by k_ht40_plan's rule (offset = capture + 2 a20 + 160, cfo / 2 truncated toward zero, each stream LENGTH bytes; joint coding: one PSDU).
+    Carrier-sense time-outs re-arm at the burst that raises them, as in rx11n_stages.  A demonstration and a test vehicle, not a fast path."""
+    nc = len(descs)
+    if nc == 0:
+        return []
+    off = np.array([int(d[0]) for d in descs], np.int64); ns = np.array([int(d[1]) for d in descs], np.int64)
+    if (ns % 28).any() or (off % 4).any():
+        raise ValueError("rx_ht40_front_stages: a capture is whole 28-sample source calls at an offset that is a multiple of 4")
+    u32 = lambda a: np.asarray(a, np.int64).astype(np.uint32).view(np.int32)
+    n20 = ns // 2
+    first = np.concatenate([[0], np.cumsum(n20)])[:-1]
+    x0, x1 = ops.downsample(iq0, iq1, u32(off), u32(n20), u32(np.zeros(nc)), u32(first), int(n20.sum()))
+    nb = n20 // 4
+    st, used = ops.cca(x0, x1, u32(first), u32(nb), cca11n_states(nc), CCA11N_REARM)
+    s0 = first + 4 * used.astype(np.int64); left = 4 * (nb - used.astype(np.int64))
+    events = [None] * nc
+    live = np.array([c for c in range(nc) if st[c, 0] == 1 and left[c] >= 368], np.int64)
+    if len(live) == 0:
+        return events
+    s0 = s0[live]; nl = len(live)
+    vfo = ops.cfo_est(ops.take(x0, s0, 128), ops.take(x1, s0, 128))
+    cfo = np.array(ops.host(vfo)).reshape(nl, 24)[:, 1].astype(np.int64)          # vfo_delta_i[1] = the estimate, before TFreqComp_11n advances the record
+    c0, c1 = ops.freq_comp(x0, x1, u32(s0), u32(np.full(nl, 16)), vfo)
+    l0, l1 = ops.fft64(ops.take(c0, s0, 128)), ops.fft64(ops.take(c1, s0, 128))
+    ch = ops.siso_est(l0, l1)
+    S, nv = ops.noise_var(l0, l1)
+    c0, c1 = ops.freq_comp(x0, x1, u32(s0 + 128), u32(np.full(nl, 30)), vfo)
+    y0, y1 = ops.data_symbol11n(c0, c1, u32(s0 + 128), u32(np.full(nl, 3)), u32(3 * np.arange(nl)), 3 * nl)
+    rec = ops.sig_decode(ops.sig_demap(ops.siso_comp_mrc(ch, ops.fft64(y0), ops.fft64(y1), u32(np.repeat(np.arange(nl), 3)))))
+    call = lambda kept, c: int(min(-(-2 * kept // 28) * 28, ns[c]))             # the source call (28 raw samples) that brings the kept sample in front of position `kept`
+    for j, c in enumerate(live):
+        a20 = int(s0[j] + 368 - first[c])
+        ev = {"a20": a20, "mcs": 0, "ht_len": 0, "nsym": 0, "cfo": int(cfo[j]), "noise_var": np.float32(nv[j]), "S": int(S[j]), "end_sample": call(a20, c),
+              "error_code": E_PLCP_HEADER_FAIL}
+        g = ht40_sig_gate(rec[j])
+        if g is not None:
+            mcs, length = g
+            nbp = {8: 1, 9: 2, 10: 2, 11: 4, 12: 4, 13: 6, 14: 6}[mcs]; cr = 2 if mcs in (10, 12, 14) else 1 if mcs == 13 else 0
+            nsym = ht40_frame_symbols((0, nbp, cr, length, 0 if coding == HT40_CODING_JOINT else length), coding)
+            end = a20 + 80 * (nsym + 3)                                          # HT-STF, two HT-LTFs and the data symbols at the 20 MHz rate
+            if 2 * end > ns[c]:
+                continue                                                        # the frame runs past the capture: no event
+            h = int(cfo[j]); half = -((-h) // 2) if h < 0 else h // 2
+            ev.update({"mcs": mcs, "ht_len": length, "nsym": nsym, "end_sample": call(end, c), "error_code": 0,
+                       "descriptor": (int(off[c]) + 2 * a20 + 160, nbp, cr, length, 0 if coding == HT40_CODING_JOINT else length, half, float(nv[j]), int(c))})
+        events[c] = ev
+    return events
+
+
+def rx_ht40_front_by_stages(d_iq0, d_iq1, descs, coding=0):
+    """The first sora_ht40_found record of every capture of a batch of two-chain 40 MHz captures, and the descriptor k_ht40_plan makes of it, through the stage entry points
+    alone (rx_ht40_front_stages with the GPU's bricks).  A DEMONSTRATION and a test vehicle, not a fast path; the first event only, and no end-of-capture flush."""
+    return rx_ht40_front_stages(_GpuHt40Ops(d_iq0.device), d_iq0, d_iq1, descs, coding)
+
+
+_GpuHt40Ops.data_symbol11n = _Gpu11nOps.data_symbol
