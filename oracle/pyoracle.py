@@ -450,6 +450,30 @@ class ReferenceGraph:
         """The reference's 802.11b receive graph (Test11B_FB_Demod / MAC11b_Receive) over int16 [n,2] @44 MHz."""
         return self._events(self.L.ref_rx11b_capture, iq44, max_frames)
 
+    def has_11a_bricks(self):
+        """True where the library carries the 802.11a per-brick entry points (ref_11a_*)."""
+        return self.L is not None and hasattr(self.L, "ref_11a_lts")
+
+    def lts11a(self, ctx, in144):
+        """T11aLTS: one burst through the reference's own brick; ctx (RxCtx) goes in through the context facades and comes back out."""
+        a = np.ascontiguousarray(in144, np.int16).reshape(144, 2)
+        self.L.ref_11a_lts(ctypes.byref(ctx), _P(a))
+
+    def sym_front11a(self, ctx, in80):
+        """TFreqCompensation -> TFFT64 -> TChannelEqualization on the 64 samples behind the prefix -> eq int16 [64,2]."""
+        a = np.ascontiguousarray(in80, np.int16).reshape(80, 2); o = np.zeros((64, 2), np.int16)
+        self.L.ref_11a_sym_front(ctypes.byref(ctx), _P(a), _P(o)); return o
+
+    def sym_track11a(self, ctx, eq):
+        """TPhaseCompensate -> TPilotTrack: one symbol; ctx is updated.  Bins 0 and 27..37 of the result are undefined."""
+        a = np.ascontiguousarray(eq, np.int16).reshape(64, 2); o = np.zeros((64, 2), np.int16)
+        self.L.ref_11a_pilot_track(ctypes.byref(ctx), _P(a), _P(o)); return o
+
+    def deinterleave11a(self, nbpsc, soft):
+        """T11aDeinterleave{BPSK,QPSK,QAM16,QAM64}: one burst through the reference's own brick."""
+        a = np.ascontiguousarray(soft, np.uint8); o = np.zeros(48 * nbpsc, np.uint8)
+        assert len(a) == 48 * nbpsc and self.L.ref_11a_deinterleave(nbpsc, _P(a), _P(o)) == 48 * nbpsc; return o
+
     def demap11n(self, nbpsc, sym64):
         """T11nDemap{BPSK,QPSK,QAM16,QAM64}: one burst through the reference's own brick."""
         a = np.ascontiguousarray(sym64, np.int16).reshape(64, 2); o = np.zeros(52 * nbpsc, np.uint8)

@@ -521,3 +521,98 @@ EXPORT int ref_11n_cca(const int16_t* iq0, const int16_t* iq1, uint32_t nbursts,
     }
     return n;                                                        // the brick is left to the process (its allocator is not delete's)
 }
+
+// ---------------------------------------------------------------- single 802.11a symbol-chain bricks (stage level): one burst through the reference's own bricks,
+// instantiated once on BB11aDemodCtx, the context facades written before the call and read back after it.  ref_11a_ctx is the layout of so_rx11a_ctx (so_oracle.h).
+struct ref_11a_ctx { int16_t CFO_est, FreqCoeffs[128], ChannelCoeffs[128], CFO_comp, SFO_comp, CompCoeffs[128], CFO_tracker, SFO_tracker; uint32_t symbol_count; };
+static_assert(sizeof(ref_11a_ctx) == 784, "ref_11a_ctx must match so_rx11a_ctx");
+static void ctx11a_put(const ref_11a_ctx* c)
+{
+    BB11aDemodContext& x = BB11aDemodCtx;
+    x.CF_CFOffset::CFO_est() = c->CFO_est;
+    memcpy(x.CF_FreqCompensate::Coeffs(), c->FreqCoeffs, 256); memcpy(x.CF_Channel_11a::ChannelCoeffs(), c->ChannelCoeffs, 256);
+    x.CF_PhaseCompensate::CFO_comp() = c->CFO_comp; x.CF_PhaseCompensate::SFO_comp() = c->SFO_comp;
+    memcpy(x.CF_PhaseCompensate::CompCoeffs(), c->CompCoeffs, 256);
+    x.CF_PilotTrack::CFO_tracker() = c->CFO_tracker; x.CF_PilotTrack::SFO_tracker() = c->SFO_tracker; x.CF_PilotTrack::symbol_count() = c->symbol_count;
+}
+static void ctx11a_get(ref_11a_ctx* c)
+{
+    BB11aDemodContext& x = BB11aDemodCtx;
+    c->CFO_est = x.CF_CFOffset::CFO_est();
+    memcpy(c->FreqCoeffs, x.CF_FreqCompensate::Coeffs(), 256); memcpy(c->ChannelCoeffs, x.CF_Channel_11a::ChannelCoeffs(), 256);
+    c->CFO_comp = x.CF_PhaseCompensate::CFO_comp(); c->SFO_comp = x.CF_PhaseCompensate::SFO_comp();
+    memcpy(c->CompCoeffs, x.CF_PhaseCompensate::CompCoeffs(), 256);
+    c->CFO_tracker = x.CF_PilotTrack::CFO_tracker(); c->SFO_tracker = x.CF_PilotTrack::SFO_tracker(); c->symbol_count = x.CF_PilotTrack::symbol_count();
+}
+struct CSink11a : public TSink<BB11aDemodContext> {                        // keeps the last 64-bin symbol it was handed
+    DEFINE_IPORT(COMPLEX16, 64); COMPLEX16 last[64];
+    CSink11a(BB11aDemodContext& c) : TSink<BB11aDemodContext>(c) { memset(last, 0, sizeof(last)); }
+    template <class P> bool Process(P& ipin) { while (ipin.check_read()) { memcpy(last, ipin.peek(), 256); ipin.pop(); } return true; }
+};
+// T11aLTS (channel_11a.hpp:33-230): the 144 samples the graph hands it (the brick shifts and rotates them in place, so a copy).  ChannelCoeffs bins 28..35 are
+// never written by the brick: they come back as they went in.
+EXPORT void ref_11a_lts(ref_11a_ctx* c, const int16_t* in144)
+{
+    static T11aLTS<BB11aDemodContext>* lts = new T11aLTS<BB11aDemodContext>(BB11aDemodCtx);
+    A16 COMPLEX16 x[144]; memcpy(x, in144, sizeof(x));
+    ctx11a_put(c);
+    OneBurstPin<COMPLEX16, 144> pin = { x, true };
+    lts->Process(pin);
+    ctx11a_get(c);
+}
+// TFreqCompensation -> TFFT64 -> TChannelEqualization (channel_11a.hpp:614-653, fft.hpp:110-135, channel_11a.hpp:534-604) on the 64 samples that T11aDataSymbol
+// passes on (a copy behind the 8-sample prefix: PHY_11a.hpp:393-397; that brick also counts the frame's symbols down and is left out)
+EXPORT void ref_11a_sym_front(const ref_11a_ctx* c, const int16_t* in80, int16_t* eq64)
+{
+    typedef TChannelEqualization<BB11aDemodContext, CSink11a> Eq;
+    typedef TFFT64<BB11aDemodContext, Eq> Fft;
+    typedef TFreqCompensation<BB11aDemodContext, Fft> Fc;
+    static CSink11a* sink = new CSink11a(BB11aDemodCtx);
+    static Eq* eq = new Eq(BB11aDemodCtx, sink);
+    static Fft* fft = new Fft(BB11aDemodCtx, eq);
+    static Fc* fc = new Fc(BB11aDemodCtx, fft);
+    A16 COMPLEX16 x[64]; memcpy(x, in80 + 2 * 8, sizeof(x));
+    ctx11a_put(c);
+    OneBurstPin<COMPLEX16, 64> pin = { x, true };
+    fc->Process(pin);
+    memcpy(eq64, sink->last, 256);
+}
+// TPhaseCompensate -> TPilotTrack (freqoffset.hpp:16-65, pilot.hpp:123-269): one equalised symbol; the context goes in and comes out.  Bins 0 and 27..37 of the
+// output are not defined by the brick (_rotate leaves 28..35 alone, its coefficients for 0 and 27 are an uninitialised local).
+EXPORT void ref_11a_pilot_track(ref_11a_ctx* c, const int16_t* eq64, int16_t* out64)
+{
+    typedef TPilotTrack<BB11aDemodContext, CSink11a> Trk;
+    typedef TPhaseCompensate<BB11aDemodContext, Trk> Pc;
+    static CSink11a* sink = new CSink11a(BB11aDemodCtx);
+    static Trk* trk = new Trk(BB11aDemodCtx, sink);
+    static Pc* pc = new Pc(BB11aDemodCtx, trk);
+    A16 COMPLEX16 x[64]; memcpy(x, eq64, sizeof(x));
+    ctx11a_put(c);
+    OneBurstPin<COMPLEX16, 64> pin = { x, true };
+    pc->Process(pin);
+    ctx11a_get(c);
+    memcpy(out64, sink->last, 256);
+}
+// T11aDeinterleave{BPSK,QPSK,QAM16,QAM64} (deinterleaver.hpp): 48*nbpsc soft values of one symbol
+template <template <class, class> class BRICK, size_t N>
+static void run_deint11a_once(const uint8_t* in, uint8_t* out)
+{
+    typedef TCaptureSink<BB11aDemodContext, N> Sink;
+    typedef BRICK<BB11aDemodContext, Sink> Brick;
+    static Sink* sink = new Sink(BB11aDemodCtx);
+    static Brick* brick = new Brick(BB11aDemodCtx, sink);
+    A16 uchar x[N]; memcpy(x, in, N);
+    OneBurstPin<uchar, N> pin = { x, true };
+    brick->Process(pin);
+    memcpy(out, sink->last, N);
+}
+EXPORT int ref_11a_deinterleave(int nbpsc, const uint8_t* in, uint8_t* out)
+{
+    switch (nbpsc) {
+    case 1: run_deint11a_once<T11aDeinterleaveBPSK, 48>(in, out); return 48;
+    case 2: run_deint11a_once<T11aDeinterleaveQPSK, 96>(in, out); return 96;
+    case 4: run_deint11a_once<T11aDeinterleaveQAM16, 192>(in, out); return 192;
+    case 6: run_deint11a_once<T11aDeinterleaveQAM64, 288>(in, out); return 288;
+    }
+    return -1;
+}
