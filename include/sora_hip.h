@@ -171,7 +171,11 @@ int  sora_rx_stream_consumed(sora_rx_t* rx, int ticket, uint32_t* h_consumed, si
 int  sora_rx_stream_record_of(sora_rx_t* rx, int ticket, uint32_t capture, uint32_t* h_words, size_t cap_words, size_t* n_words);
 
 /* TBB11aFrameSink's frame buffer + CF_Error per frame: copies results of the last process call to the host.
- * h_mpdu may be NULL (descriptors only).  *nout = rows written. Frames appear in (capture, time) order. */
+ * h_mpdu may be NULL (descriptors only).  *nout = rows written. Frames appear in (capture, time) order.
+ * mpdu_offset indexes h_mpdu and counts the bytes COPIED in front of the row: with h_mpdu NULL every row's offset is 0, and a row behind one whose MPDU did
+ * not fit carries the offset that one carries.  A buffer that is short gives SORA_ERR_CAPACITY with what fits delivered: max_out short -- the first max_out
+ * rows, *nout = max_out; mpdu_cap short -- every row, each MPDU that would reach past mpdu_cap skipped (a later, shorter one that fits is still copied).  The
+ * same holds for *_results / *_results_of of the 802.11b and 802.11n handles (tests/deliver_model.py states it, tests/test_gpu_deliver.py holds the handles to it). */
 int  sora_rx_results(sora_rx_t* rx, sora_frame_result* h_out, size_t max_out, size_t* nout, uint8_t* h_mpdu, size_t mpdu_cap);
 
 /* Tickets.  With several calls in flight (sora_rx_set_depth) every process call has a TICKET, a positive number that
@@ -187,7 +191,10 @@ int  sora_rx_results(sora_rx_t* rx, sora_frame_result* h_out, size_t max_out, si
  *   sora_rx_deliver_async   enqueue, behind the call's kernels and without blocking the host, the delivery of its results
  *                           into host memory: the dense rows (capture, time order; at most max_rows are copied), their
  *                           number, and -- h_mpdu != NULL -- the MPDU array (row.mpdu_offset indexes it; mpdu_bytes must be
- *                           at least sora_rx_mpdu_bytes(rx, ticket)).  The buffers should be page-locked
+ *                           at least sora_rx_mpdu_bytes(rx, ticket); a smaller h_mpdu is refused, SORA_ERR_CAPACITY, before anything is enqueued).
+ *                           The array has 32 bytes per symbol slot, a capture's nsamples / 80 + 1 slots (20 MHz-rate samples) behind those of the
+ *                           captures before it, and a frame's MPDU starts at the slot of its SIGNAL symbol, (start_sample + 144) / 80 of its
+ *                           capture; the offsets are the same whether or not h_mpdu is given.  The buffers should be page-locked
  *                           (sora_hip_host_alloc) so that the copies overlap later calls; they are valid after sora_rx_wait.
  *   sora_rx_wait_any        block until SOME call whose delivery has been enqueued has finished, and return its ticket (the oldest
  *                           one if several have).  Calls in flight overtake one another (their streams sit on different dispatch
@@ -1087,7 +1094,8 @@ int   sora_ht40_stream_consumed(sora_ht40_t* rx, int ticket, uint32_t* h_consume
  *   - raw-capture calls and stream mode work as above with ONE row per recorded frame; a frame's extent follows the joint N_SYM;
  *   - sora_ht40_soft_of: `stream` must be 0; the 2 x nsym x 108 x n_bpsc MERGED soft bytes are returned, as the trellis reads them (symbol after symbol, the
  *     symbol's 2 N_CBPSS coded bits in the encoder's order);
- *   - sora_ht40_deliver_async: max_rows as above (the bound is not halved).
+ *   - sora_ht40_deliver_async: raw-capture calls take max_rows as above (the bound is not halved: the event table keeps its two-row pitch); descriptor calls
+ *     need one row per frame.
  * Returns the previous value; a negative argument only queries.  Like sora_ht40_set_stream_mode it first waits for every call in flight and starts every stream
  * afresh.  Calls issued before the switch keep their coding when their results are read. */
 #define SORA_HT40_CODING_PER_STREAM 0
@@ -1192,7 +1200,10 @@ int   sora_rx11b_results_of(sora_rx11b_t* rx, int ticket, sora_frame_result* out
 /* Result delivery without a host wait (as sora_rx_deliver_async): behind the call's kernels, on its stream, the dense rows in (capture, time)
  * order -- h_rows must have room for captures x max_frames_per_capture of them --, h_counts[0] = rows, h_counts[1] = MPDU bytes, and the MPDUs
  * densely packed in row order (the rows' mpdu_offset indexes h_mpdu; an MPDU that would reach past mpdu_cap is left out and h_counts[1] says
- * so).  Page-locked buffers (sora_hip_host_alloc); valid once sora_rx11b_wait(ticket) has returned.  h_mpdu may be NULL.
+ * so).  mpdu_offset is the sum of the MPDU lengths (min(length, 4096) of the FRAME_OK / CRC32_FAIL rows) of all rows in front, whether or not those MPDUs
+ * fitted and whether or not h_mpdu is given (unlike *_results_of, whose offsets count copied bytes); an MPDU is delivered exactly when mpdu_offset + its length
+ * <= mpdu_cap, and h_counts[1] is the total, not what fitted.  A max_rows below captures x max_frames_per_capture is refused (SORA_ERR_CAPACITY) with nothing
+ * enqueued.  Page-locked buffers (sora_hip_host_alloc); valid once sora_rx11b_wait(ticket) has returned.  h_mpdu may be NULL.
  * The copies are enqueued before the call's sizes are known to the host, so they move the WHOLE of what the caller offers -- max
  * captures x frames rows and all mpdu_cap bytes, every call: give mpdu_cap the size the traffic needs (frames x MTU), not a worst case
  * (rows x 4096 costs tens of MB over the host link per call and delivers stale bytes behind h_counts[1]). */
