@@ -316,6 +316,12 @@ int  sora_rx_results_dev_of(sora_rx_t* rx, int ticket, const sora_frame_result**
  * Per-stage entry points with the brick port shapes, batched (n = number of bursts).  All pointers are
  * device pointers; `stream` is a hipStream_t (NULL = default stream).  Each can sit behind a BRICK-shaped
  * adapter (include/sora_brick.hpp) where the SSE brick sits today.
+ *
+ * Every stage entry point of this header -- this block and the stage blocks below, sora_hip_<brick>(..., size_t count, void* stream) -- checks its arguments in one
+ * order: a null pointer that is not optional is refused by name (SORA_ERR_INVALID_PARAM); a count of 0 returns SORA_OK (nothing to launch, with or without a
+ * device); no device gives SORA_ERR_NO_DEVICE; a count of 2^31 or more gives SORA_ERR_CAPACITY (the kernels index with 32 bits: split the batch).  The checks
+ * particular to one entry (n_bpsc, a flag, alignment, its own limits) follow; only sora_hip_stream_join11n and the sora_hip_*_ht40 stages refuse a bad n_bpsc or
+ * spatial_stream earlier, before the count is looked at.
  * ------------------------------------------------------------------------------------------------ */
 /* TFFT64  (Brick11/src/fft.hpp:108-135 -> core/inc/fft_r4dif.h FFT<64>): IPORT COMPLEX16x64 -> OPORT COMPLEX16x64 */
 int sora_hip_fft64(const sora_complex16* d_in, sora_complex16* d_out, size_t n, void* stream);

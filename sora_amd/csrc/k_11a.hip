@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "dev_11n.h"
 #include "dev_cs11a.h"
+#include "host_stage.h"
 
 namespace sora {
 
@@ -177,92 +178,79 @@ __global__ void __launch_bounds__(256) k_11a_plcp_parse(const uint32_t* __restri
 
 using namespace sora;
 
-#define ST11A_ENTRY(who, nullcond, count) \
-    if (nullcond) return sora_internal_fail(SORA_ERR_INVALID_PARAM, who ": null pointer", 0); \
-    if ((count) == 0) return SORA_OK;                       /* (nothing to launch: true with or without a device) */ \
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0); \
-    if ((count) >= (1ull << 31)) return sora_internal_fail(SORA_ERR_CAPACITY, who ": too many for one call", 0);
+// ---- the stage entry points (host_stage.h: the prologue and helpers every stage shares)
 static_assert(sizeof(sora_cca11a_state) == 4 * kCca11aWords && sizeof(sora_dcest11a_state) == 4 * kDcEst11aWords && sizeof(sora_cs11a_state) == 4 * kCs11aWords &&
               sizeof(sora_plcp11a_rec) == 20, "the 802.11a stage records are 32-bit words");
 namespace {
-int launched(const char* what) { const hipError_t e = hipGetLastError(); return e == hipSuccess ? SORA_OK : sora_internal_fail(SORA_ERR_HARDWARE_FAILED, what, (int)e); }
-const uint32_t* sts_table()
-{
-    int dev = 0; Tables T;
-    if (hipGetDevice(&dev) != hipSuccess || sora_internal_tables(dev, &T) != SORA_OK) return nullptr;
-    return T.sts;
-}
 inline uint32_t clamp_n(size_t max_n) { return max_n < (1u << 30) ? (uint32_t)max_n : (1u << 30); }
 }  // namespace
 
 int sora_hip_dc_remove11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const sora_complex16* d_dc,
                           sora_complex16* d_out, size_t nstreams, size_t max_n, void* stream)
 {
-    ST11A_ENTRY("sora_hip_dc_remove11a", !d_in || !d_first || !d_n || !d_out_first || !d_dc || !d_out, nstreams)
+    STAGE_ENTRY("sora_hip_dc_remove11a", !d_in || !d_first || !d_n || !d_out_first || !d_dc || !d_out, nstreams)
     if (max_n == 0) return SORA_OK;
     if (nstreams > 65535 || max_n >= (1u << 29)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_dc_remove11a: at most 65535 streams of 2^29 bursts per call", 0);
     const uint32_t mn = clamp_n(max_n); const unsigned gx = (unsigned)((4ull * mn + 255) / 256);
-    hipLaunchKernelGGL(k_11a_dc_remove, dim3(gx < 64 ? gx : 64, (unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
-                       reinterpret_cast<uint32_t*>(d_out), d_first, d_n, d_out_first, reinterpret_cast<const uint32_t*>(d_dc), mn);
-    return launched("k_11a_dc_remove");
+    hipLaunchKernelGGL(k_11a_dc_remove, dim3(gx < 64 ? gx : 64, (unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, u32(d_in),
+                       u32(d_out), d_first, d_n, d_out_first, u32(d_dc), mn);
+    return launch_result("k_11a_dc_remove");
 }
 
 int sora_hip_dc_estimate11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_dcest11a_state* d_state, size_t nstreams, size_t max_n, void* stream)
 {
-    ST11A_ENTRY("sora_hip_dc_estimate11a", !d_in || !d_first || !d_n || !d_state, nstreams)
+    STAGE_ENTRY("sora_hip_dc_estimate11a", !d_in || !d_first || !d_n || !d_state, nstreams)
     if (max_n == 0) return SORA_OK;
-    hipLaunchKernelGGL(k_11a_dc_estimate, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in), d_first, d_n,
-                       reinterpret_cast<uint32_t*>(d_state), clamp_n(max_n));
-    return launched("k_11a_dc_estimate");
+    hipLaunchKernelGGL(k_11a_dc_estimate, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, u32(d_in), d_first, d_n, u32(d_state), clamp_n(max_n));
+    return launch_result("k_11a_dc_estimate");
 }
 
 int sora_hip_cca11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_cca11a_state* d_state, sora_complex16* d_out,
                     uint32_t* d_used, uint32_t* d_npass, size_t nstreams, size_t max_n, unsigned flags, void* stream)
 {
-    ST11A_ENTRY("sora_hip_cca11a", !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out || !d_used || !d_npass, nstreams)
+    STAGE_ENTRY("sora_hip_cca11a", !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out || !d_used || !d_npass, nstreams)
     if (flags & ~(unsigned)SORA_CCA11A_STOP_ON_TIMEOUT) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_cca11a: unknown flag", 0);
     if (max_n == 0) return SORA_OK;
-    const uint32_t* sts = sts_table(); if (!sts) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "table upload failed", 0);
-    hipLaunchKernelGGL(k_11a_cca, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in), d_first, d_n, d_out_first,
-                       reinterpret_cast<uint32_t*>(d_state), reinterpret_cast<uint32_t*>(d_out), d_used, d_npass, clamp_n(max_n), (uint32_t)flags, sts);
-    return launched("k_11a_cca");
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    hipLaunchKernelGGL(k_11a_cca, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, u32(d_in), d_first, d_n, d_out_first,
+                       u32(d_state), u32(d_out), d_used, d_npass, clamp_n(max_n), (uint32_t)flags, T.sts);
+    return launch_result("k_11a_cca");
 }
 
 int sora_hip_carrier_sense11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_cs11a_state* d_state, uint32_t* d_used, size_t nstreams,
                               size_t max_n, unsigned flags, void* stream)
 {
-    ST11A_ENTRY("sora_hip_carrier_sense11a", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
+    STAGE_ENTRY("sora_hip_carrier_sense11a", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
     if (flags & ~(unsigned)SORA_CCA11A_STOP_ON_TIMEOUT) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_carrier_sense11a: unknown flag", 0);
     if (max_n == 0) return SORA_OK;
-    const uint32_t* sts = sts_table(); if (!sts) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "table upload failed", 0);
-    hipLaunchKernelGGL(k_11a_carrier_sense, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in), d_first, d_n,
-                       reinterpret_cast<uint32_t*>(d_state), d_used, clamp_n(max_n), (uint32_t)flags, sts);
-    return launched("k_11a_carrier_sense");
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    hipLaunchKernelGGL(k_11a_carrier_sense, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, u32(d_in), d_first, d_n,
+                       u32(d_state), d_used, clamp_n(max_n), (uint32_t)flags, T.sts);
+    return launch_result("k_11a_carrier_sense");
 }
 
 int sora_hip_data_symbol11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_out_first, sora_complex16* d_out, size_t nframes,
                             size_t max_nsym, void* stream)
 {
-    ST11A_ENTRY("sora_hip_data_symbol11a", !d_in || !d_first || !d_nsym || !d_out_first || !d_out, nframes)
+    STAGE_ENTRY("sora_hip_data_symbol11a", !d_in || !d_first || !d_nsym || !d_out_first || !d_out, nframes)
     if (max_nsym == 0) return SORA_OK;
     if (nframes > 65535 || max_nsym > (1u << 27)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_data_symbol11a: at most 65535 frames of 2^27 symbols per call", 0);
     const unsigned gx = (unsigned)((max_nsym * 16 + 255) / 256);
-    hipLaunchKernelGGL(k_11a_data_symbol, dim3(gx < 64 ? gx : 64, (unsigned)nframes), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
-                       reinterpret_cast<uint32_t*>(d_out), d_first, d_nsym, d_out_first, (uint32_t)max_nsym);
-    return launched("k_11a_data_symbol");
+    hipLaunchKernelGGL(k_11a_data_symbol, dim3(gx < 64 ? gx : 64, (unsigned)nframes), dim3(256), 0, (hipStream_t)stream, u32(d_in),
+                       u32(d_out), d_first, d_nsym, d_out_first, (uint32_t)max_nsym);
+    return launch_result("k_11a_data_symbol");
 }
 
 int sora_hip_viterbi_sig11a(const uint8_t* d_soft, uint32_t* d_sig, size_t n, void* stream)
 {
-    ST11A_ENTRY("sora_hip_viterbi_sig11a", !d_soft || !d_sig, n)
+    STAGE_ENTRY("sora_hip_viterbi_sig11a", !d_soft || !d_sig, n)
     hipLaunchKernelGGL(k_11a_viterbi_sig, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_soft, d_sig, (uint32_t)n);
-    return launched("k_11a_viterbi_sig");
+    return launch_result("k_11a_viterbi_sig");
 }
 
 int sora_hip_plcp_parse11a(const uint32_t* d_sig, sora_plcp11a_rec* d_rec, size_t n, void* stream)
 {
-    ST11A_ENTRY("sora_hip_plcp_parse11a", !d_sig || !d_rec, n)
-    hipLaunchKernelGGL(k_11a_plcp_parse, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_sig, reinterpret_cast<uint32_t*>(d_rec), (uint32_t)n);
-    return launched("k_11a_plcp_parse");
+    STAGE_ENTRY("sora_hip_plcp_parse11a", !d_sig || !d_rec, n)
+    hipLaunchKernelGGL(k_11a_plcp_parse, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_sig, u32(d_rec), (uint32_t)n);
+    return launch_result("k_11a_plcp_parse");
 }
-#undef ST11A_ENTRY

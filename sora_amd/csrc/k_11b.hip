@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "dev_11b.h"
+#include "host_stage.h"
 
 namespace sora {
 
@@ -416,3 +417,121 @@ __global__ void __launch_bounds__(64) k_11b_frame_sink(const uint8_t* __restrict
 }
 
 }  // namespace sora
+
+using namespace sora;
+
+// ---- the stage entry points (host_stage.h: the prologue and helpers every stage shares)
+static_assert(sizeof(sora_stream11b_state) == 16 && sizeof(sora_energy11b_state) == 68 && sizeof(sora_symtiming11b_state) == 8 && sizeof(sora_barker11b_state) == 60 &&
+              sizeof(sora_sfd11b_state) == 36 && sizeof(sora_plcp11b_rec) == 16 && sizeof(sora_sink11b_rec) == 8, "the 802.11b stage records are 32-bit words");
+
+int sora_hip_dc_remove11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const sora_complex16* d_dc,
+                          sora_complex16* d_out, size_t nstreams, size_t max_n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_dc_remove11b", !d_in || !d_first || !d_n || !d_out_first || !d_dc || !d_out, nstreams)
+    if (max_n == 0) return SORA_OK;
+    uint32_t chunks; unsigned grid;
+    if (max_n >= (1u << 29) || !stage_grid(nstreams, 4 * max_n, &chunks, &grid))
+        return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_dc_remove11b: nstreams x max_n is too large for one call", 0);
+    hipLaunchKernelGGL(k_11b_dc_remove, dim3(grid), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), d_first, d_n, d_out_first, u32(d_dc), (uint32_t)nstreams, chunks);
+    return launch_result("k_11b_dc_remove");
+}
+
+int sora_hip_energy_detect11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_energy11b_state* d_state, uint32_t* d_used,
+                              size_t nstreams, size_t max_n, void* stream)
+{
+    (void)max_n;                                                                 // (a wave per stream walks its own d_n[f])
+    STAGE_ENTRY("sora_hip_energy_detect11b", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
+    hipLaunchKernelGGL(k_11b_energy_detect, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, u32(d_in), d_first, d_n, u32(d_state), d_used, (uint32_t)nstreams);
+    return launch_result("k_11b_energy_detect");
+}
+
+int sora_hip_symtiming11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_symtiming11b_state* d_state,
+                          sora_complex16* d_out, uint32_t* d_nchips, size_t nstreams, size_t max_n, void* stream)
+{
+    (void)max_n;
+    STAGE_ENTRY("sora_hip_symtiming11b", !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out || !d_nchips, nstreams)
+    hipLaunchKernelGGL(k_11b_symtiming, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, u32(d_in), u32(d_out), d_first, d_n, d_out_first,
+                       reinterpret_cast<int*>(d_state), d_nchips, (uint32_t)nstreams);
+    return launch_result("k_11b_symtiming");
+}
+
+int sora_hip_barker_sync11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_barker11b_state* d_state, uint32_t* d_used,
+                            size_t nstreams, size_t max_n, void* stream)
+{
+    (void)max_n;
+    STAGE_ENTRY("sora_hip_barker_sync11b", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
+    hipLaunchKernelGGL(k_11b_barker_sync, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, u32(d_in), d_first, d_n, u32(d_state), d_used, (uint32_t)nstreams);
+    return launch_result("k_11b_barker_sync");
+}
+
+int sora_hip_despread11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_complex16* d_out,
+                         size_t nstreams, size_t max_n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_despread11b", !d_in || !d_first || !d_n || !d_out_first || !d_out, nstreams)
+    if (max_n == 0) return SORA_OK;
+    uint32_t chunks; unsigned grid;
+    if (!stage_grid(nstreams, max_n, &chunks, &grid)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_despread11b: nstreams x max_n is too large for one call", 0);
+    hipLaunchKernelGGL(k_11b_despread, dim3(grid), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), d_first, d_n, d_out_first, (uint32_t)nstreams, chunks);
+    return launch_result("k_11b_despread");
+}
+
+int sora_hip_sfd_sync11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_sfd11b_state* d_state, uint32_t* d_used,
+                         size_t nstreams, size_t max_n, int mode, void* stream)
+{
+    (void)max_n;
+    STAGE_ENTRY("sora_hip_sfd_sync11b", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
+    if (mode != 0 && mode != 1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_sfd_sync11b: mode must be 0 or 1", 0);
+    hipLaunchKernelGGL(k_11b_sfd_sync, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, u32(d_in), d_first, d_n, u32(d_state), d_used, (uint32_t)nstreams, mode);
+    return launch_result("k_11b_sfd_sync");
+}
+
+// the five position-parallel stream stages with a sora_stream11b_state, behind their entry's prologue: the stage's kernel, then the state behind it (kind: k_11b_stream_state)
+static int stream11b_stage(int kind, const char* too_large, const void* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state,
+                           uint8_t* d_out, size_t nstreams, size_t max_n, void* stream)
+{
+    if (max_n == 0) return SORA_OK;
+    uint32_t chunks; unsigned grid;
+    if (!stage_grid(nstreams, max_n, &chunks, &grid)) return sora_internal_fail(SORA_ERR_CAPACITY, too_large, 0);
+    hipStream_t st = (hipStream_t)stream; const uint32_t ns = (uint32_t)nstreams; uint32_t* state = u32(d_state);
+    switch (kind) {
+    case 0: hipLaunchKernelGGL(k_11b_demap<1>, dim3(grid), dim3(256), 0, st, u32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
+    case 1: hipLaunchKernelGGL(k_11b_demap<2>, dim3(grid), dim3(256), 0, st, u32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
+    case 2: hipLaunchKernelGGL(k_11b_cck<5>, dim3(grid), dim3(256), 0, st, u32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
+    case 3: hipLaunchKernelGGL(k_11b_cck<11>, dim3(grid), dim3(256), 0, st, u32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
+    default: hipLaunchKernelGGL(k_11b_desc741, dim3(grid), dim3(256), 0, st, static_cast<const uint8_t*>(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
+    }
+    static const char* const kernel[5] = { "k_11b_demap<1>", "k_11b_demap<2>", "k_11b_cck<5>", "k_11b_cck<11>", "k_11b_desc741" };
+    if (const int rc = launch_result(kernel[kind])) return rc;
+    hipLaunchKernelGGL(k_11b_stream_state, dim3((ns + 255) / 256), dim3(256), 0, st, d_in, d_first, d_n, state, ns, kind);
+    return launch_result("k_11b_stream_state");
+}
+#define STREAM11B(name, kind, in_t) \
+    int name(const in_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state, uint8_t* d_out, size_t nstreams, \
+             size_t max_n, void* stream) \
+    { \
+        STAGE_ENTRY(#name, !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out, nstreams) \
+        return stream11b_stage(kind, #name ": nstreams x max_n is too large for one call", d_in, d_first, d_n, d_out_first, d_state, d_out, nstreams, max_n, stream); \
+    }
+STREAM11B(sora_hip_dbpsk_demap11b, 0, sora_complex16)
+STREAM11B(sora_hip_dqpsk_demap11b, 1, sora_complex16)
+STREAM11B(sora_hip_cck5p5_decode11b, 2, sora_complex16)
+STREAM11B(sora_hip_cck11_decode11b, 3, sora_complex16)
+STREAM11B(sora_hip_desc741_11b, 4, uint8_t)
+#undef STREAM11B
+
+int sora_hip_plcp_parse11b(const uint8_t* d_hdr, sora_plcp11b_rec* d_rec, size_t nstreams, void* stream)
+{
+    STAGE_ENTRY("sora_hip_plcp_parse11b", !d_hdr || !d_rec, nstreams)
+    if (!aligned16(d_rec)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_plcp_parse11b: the records must be 16-byte aligned", 0);
+    hipLaunchKernelGGL(k_11b_plcp_parse, dim3((unsigned)((nstreams + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_hdr, u32(d_rec), (uint32_t)nstreams);
+    return launch_result("k_11b_plcp_parse");
+}
+
+int sora_hip_frame_sink11b(const uint8_t* d_bytes, const uint32_t* d_first, const uint32_t* d_len, sora_sink11b_rec* d_rec, size_t nstreams, void* stream)
+{
+    STAGE_ENTRY("sora_hip_frame_sink11b", !d_bytes || !d_first || !d_len || !d_rec, nstreams)
+    if ((uintptr_t)d_rec & 7) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_frame_sink11b: the records must be 8-byte aligned", 0);
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    hipLaunchKernelGGL(k_11b_frame_sink, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, d_bytes, d_first, d_len, u32(d_rec), (uint32_t)nstreams, T.crc);
+    return launch_result("k_11b_frame_sink");
+}

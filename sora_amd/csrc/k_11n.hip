@@ -11,7 +11,7 @@
 // (N_COL 13, N_ROW 4 N_BPSC, N_ROT 11) inverted, computed per element instead of the reference's unrolled tables.
 #include "kernels.h"
 #include "dev_11n.h"
-#include "../../include/sora_hip.h"
+#include "host_stage.h"
 
 namespace sora {
 
@@ -501,49 +501,39 @@ __global__ void __launch_bounds__(256) k_frame_sink11a(const uint8_t* __restrict
 
 using namespace sora;
 
+// ---- the stage entry points (host_stage.h: the prologue and helpers every stage shares)
 int sora_hip_demap11n(const sora_complex16* d_in, uint8_t* d_soft, int n_bpsc, size_t n, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_in || !d_soft || !(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_demap11n: bad argument", 0);
-    if (n == 0) return SORA_OK;
-    hipLaunchKernelGGL(k_demap11n_batch, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in), d_soft, n_bpsc, (uint32_t)n);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SORA_OK : sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "k_demap11n_batch", (int)e);
+    STAGE_ENTRY("sora_hip_demap11n", !d_in || !d_soft, n)
+    STAGE_NBPSC("sora_hip_demap11n", n_bpsc)
+    hipLaunchKernelGGL(k_demap11n_batch, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_in), d_soft, n_bpsc, (uint32_t)n);
+    return launch_result("k_demap11n_batch");
 }
 
 int sora_hip_deinterleave11n(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, int spatial_stream, size_t n, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_in || !d_out || !(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6) || spatial_stream < 0 || spatial_stream > 1)
-        return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_deinterleave11n: bad argument", 0);
-    if (n == 0) return SORA_OK;
+    STAGE_ENTRY("sora_hip_deinterleave11n", !d_in || !d_out, n)
+    STAGE_NBPSC("sora_hip_deinterleave11n", n_bpsc)
+    if (spatial_stream < 0 || spatial_stream > 1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_deinterleave11n: spatial_stream must be 0 or 1", 0);
     const uint64_t total = (uint64_t)n * 52 * n_bpsc;
     hipLaunchKernelGGL(k_deint11n_batch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_in, d_out, n_bpsc, spatial_stream, (uint32_t)n);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SORA_OK : sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "k_deint11n_batch", (int)e);
+    return launch_result("k_deint11n_batch");
 }
 
 int sora_hip_mimo_est11n(const sora_complex16* d_ltf0, const sora_complex16* d_ltf1, sora_complex16* d_h, sora_complex16* d_hinv, size_t nframes, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_ltf0 || !d_ltf1 || !d_h || !d_hinv) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_mimo_est11n: null argument", 0);
-    if (nframes == 0) return SORA_OK;
-    hipLaunchKernelGGL(k_mimo_est11n_batch, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_ltf0),
-                       reinterpret_cast<const uint32_t*>(d_ltf1), reinterpret_cast<uint32_t*>(d_h), reinterpret_cast<uint32_t*>(d_hinv), (uint32_t)nframes);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SORA_OK : sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "k_mimo_est11n_batch", (int)e);
+    STAGE_ENTRY("sora_hip_mimo_est11n", !d_ltf0 || !d_ltf1 || !d_h || !d_hinv, nframes)
+    hipLaunchKernelGGL(k_mimo_est11n_batch, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_ltf0), u32(d_ltf1), u32(d_h), u32(d_hinv), (uint32_t)nframes);
+    return launch_result("k_mimo_est11n_batch");
 }
 
 int sora_hip_mimo_comp11n(const sora_complex16* d_hinv, const uint32_t* d_frame_index, const sora_complex16* d_y0, const sora_complex16* d_y1,
                           sora_complex16* d_x0, sora_complex16* d_x1, size_t nsym, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_hinv || !d_y0 || !d_y1 || !d_x0 || !d_x1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_mimo_comp11n: null argument", 0);
-    if (nsym == 0) return SORA_OK;
-    hipLaunchKernelGGL(k_mimo_comp11n_batch, dim3((unsigned)((nsym + 3) / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_hinv), d_frame_index,
-                       reinterpret_cast<const uint32_t*>(d_y0), reinterpret_cast<const uint32_t*>(d_y1), reinterpret_cast<uint32_t*>(d_x0), reinterpret_cast<uint32_t*>(d_x1), (uint32_t)nsym);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SORA_OK : sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "k_mimo_comp11n_batch", (int)e);
+    STAGE_ENTRY("sora_hip_mimo_comp11n", !d_hinv || !d_y0 || !d_y1 || !d_x0 || !d_x1, nsym)
+    hipLaunchKernelGGL(k_mimo_comp11n_batch, dim3((unsigned)((nsym + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_hinv), d_frame_index, u32(d_y0), u32(d_y1), u32(d_x0), u32(d_x1),
+                       (uint32_t)nsym);
+    return launch_result("k_mimo_comp11n_batch");
 }
 
 // ---- dsp_math tables (dsp_math.h:215-245): generated once per device with the C library, as the reference generates them at start-up
@@ -586,7 +576,6 @@ const DspTables* dsp_tables()
     }
     return &T;
 }
-int launch_result(const char* what) { const hipError_t e = hipGetLastError(); return e == hipSuccess ? SORA_OK : sora_internal_fail(SORA_ERR_HARDWARE_FAILED, what, (int)e); }
 }  // namespace
 
 int sora_internal_dsp_tables(const uint32_t** sincos, const short** atan)       // current device; used by k_rx11n.hip
@@ -598,26 +587,22 @@ int sora_internal_dsp_tables(const uint32_t** sincos, const short** atan)       
 
 int sora_hip_cfo_est11n(const sora_complex16* d_lltf0, const sora_complex16* d_lltf1, int16_t* d_state, size_t nframes, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_lltf0 || !d_lltf1 || !d_state) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_cfo_est11n: null argument", 0);
-    if (nframes == 0) return SORA_OK;
+    STAGE_ENTRY("sora_hip_cfo_est11n", !d_lltf0 || !d_lltf1 || !d_state, nframes)
     const DspTables* T = dsp_tables(); if (!T) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "dsp_math table upload failed", 0);
-    hipLaunchKernelGGL(k_cfo_est11n_batch, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_lltf0),
-                       reinterpret_cast<const uint32_t*>(d_lltf1), d_state, (uint32_t)nframes, T->atan);
+    hipLaunchKernelGGL(k_cfo_est11n_batch, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_lltf0), u32(d_lltf1), d_state, (uint32_t)nframes, T->atan);
     return launch_result("k_cfo_est11n_batch");
 }
 
 int sora_hip_freq_comp11n(const sora_complex16* d_in0, const sora_complex16* d_in1, sora_complex16* d_out0, sora_complex16* d_out1,
                           const uint32_t* d_first, const uint32_t* d_nbursts, int16_t* d_state, size_t nframes, size_t max_bursts, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_in0 || !d_in1 || !d_out0 || !d_out1 || !d_first || !d_nbursts || !d_state) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_freq_comp11n: null argument", 0);
-    if (nframes == 0 || max_bursts == 0) return SORA_OK;
+    STAGE_ENTRY("sora_hip_freq_comp11n", !d_in0 || !d_in1 || !d_out0 || !d_out1 || !d_first || !d_nbursts || !d_state, nframes)
+    if (max_bursts == 0) return SORA_OK;
     if (nframes > 65535) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_freq_comp11n: at most 65535 frames per call", 0);
     const DspTables* T = dsp_tables(); if (!T) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "dsp_math table upload failed", 0);
     const unsigned gx = (unsigned)((max_bursts * 8 + 255) / 256);
-    hipLaunchKernelGGL(k_freq_comp11n_batch, dim3(gx < 64 ? gx : 64, (unsigned)nframes), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in0),
-                       reinterpret_cast<const uint32_t*>(d_in1), reinterpret_cast<uint32_t*>(d_out0), reinterpret_cast<uint32_t*>(d_out1), d_first, d_nbursts, d_state, T->sincos);
+    hipLaunchKernelGGL(k_freq_comp11n_batch, dim3(gx < 64 ? gx : 64, (unsigned)nframes), dim3(256), 0, (hipStream_t)stream, u32(d_in0),
+                       u32(d_in1), u32(d_out0), u32(d_out1), d_first, d_nbursts, d_state, T->sincos);
     hipLaunchKernelGGL(k_freq_comp11n_advance, dim3((unsigned)((nframes * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_nbursts, d_state, (uint32_t)nframes);
     return launch_result("k_freq_comp11n_batch");
 }
@@ -625,103 +610,76 @@ int sora_hip_freq_comp11n(const sora_complex16* d_in0, const sora_complex16* d_i
 int sora_hip_pilot_track11n(const sora_complex16* d_x0, const sora_complex16* d_x1, const uint32_t* d_first, const uint32_t* d_nsym, int16_t* d_state,
                             int16_t* d_theta, size_t nframes, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_x0 || !d_x1 || !d_first || !d_nsym || !d_state) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_pilot_track11n: null argument", 0);
-    if (nframes == 0) return SORA_OK;
+    STAGE_ENTRY("sora_hip_pilot_track11n", !d_x0 || !d_x1 || !d_first || !d_nsym || !d_state, nframes)
     const DspTables* T = dsp_tables(); if (!T) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "dsp_math table upload failed", 0);
-    hipLaunchKernelGGL(k_pilot_track11n_batch, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_x0),
-                       reinterpret_cast<const uint32_t*>(d_x1), d_first, d_nsym, d_state, d_theta, (uint32_t)nframes, T->atan);
+    hipLaunchKernelGGL(k_pilot_track11n_batch, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_x0),
+                       u32(d_x1), d_first, d_nsym, d_state, d_theta, (uint32_t)nframes, T->atan);
     return launch_result("k_pilot_track11n_batch");
 }
 
 int sora_hip_siso_est11n(const sora_complex16* d_lltf0, const sora_complex16* d_lltf1, sora_complex16* d_ch, size_t nframes, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_lltf0 || !d_lltf1 || !d_ch) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_siso_est11n: null argument", 0);
-    if (nframes == 0) return SORA_OK;
-    hipLaunchKernelGGL(k_siso_est11n_batch, dim3((unsigned)((nframes + 1) / 2)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_lltf0),
-                       reinterpret_cast<const uint32_t*>(d_lltf1), reinterpret_cast<uint32_t*>(d_ch), (uint32_t)nframes);
+    STAGE_ENTRY("sora_hip_siso_est11n", !d_lltf0 || !d_lltf1 || !d_ch, nframes)
+    hipLaunchKernelGGL(k_siso_est11n_batch, dim3((unsigned)((nframes + 1) / 2)), dim3(256), 0, (hipStream_t)stream, u32(d_lltf0), u32(d_lltf1), u32(d_ch), (uint32_t)nframes);
     return launch_result("k_siso_est11n_batch");
 }
 
 int sora_hip_siso_comp11n(const sora_complex16* d_ch, const uint32_t* d_frame_index, const sora_complex16* d_y0, const sora_complex16* d_y1,
                           sora_complex16* d_x0, sora_complex16* d_x1, sora_complex16* d_mrc, size_t nsym, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_ch || !d_y0 || !d_y1 || !(d_x0 || d_x1 || d_mrc)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_siso_comp11n: null argument", 0);
-    if (nsym == 0) return SORA_OK;
-    hipLaunchKernelGGL(k_siso_comp11n_batch, dim3((unsigned)((nsym + 3) / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_ch), d_frame_index,
-                       reinterpret_cast<const uint32_t*>(d_y0), reinterpret_cast<const uint32_t*>(d_y1), reinterpret_cast<uint32_t*>(d_x0),
-                       reinterpret_cast<uint32_t*>(d_x1), reinterpret_cast<uint32_t*>(d_mrc), (uint32_t)nsym);
+    STAGE_ENTRY("sora_hip_siso_comp11n", !d_ch || !d_y0 || !d_y1 || !(d_x0 || d_x1 || d_mrc), nsym)
+    hipLaunchKernelGGL(k_siso_comp11n_batch, dim3((unsigned)((nsym + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_ch), d_frame_index, u32(d_y0), u32(d_y1), u32(d_x0),
+                       u32(d_x1), u32(d_mrc), (uint32_t)nsym);
     return launch_result("k_siso_comp11n_batch");
 }
 
 int sora_hip_sig_demap11n(const sora_complex16* d_sym, uint8_t* d_soft, size_t nframes, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_sym || !d_soft) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_sig_demap11n: null argument", 0);
-    if (nframes == 0) return SORA_OK;
-    hipLaunchKernelGGL(k_sig_demap11n_batch, dim3((unsigned)((nframes * 3 + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-            reinterpret_cast<const uint32_t*>(d_sym), d_soft, (uint32_t)nframes);
+    STAGE_ENTRY("sora_hip_sig_demap11n", !d_sym || !d_soft, nframes)
+    hipLaunchKernelGGL(k_sig_demap11n_batch, dim3((unsigned)((nframes * 3 + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_sym), d_soft, (uint32_t)nframes);
     return launch_result("k_sig_demap11n_batch");
 }
 
 int sora_hip_sig_decode11n(const uint8_t* d_soft, uint32_t* d_rec, size_t nframes, void* stream)
 {
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0);
-    if (!d_soft || !d_rec) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_sig_decode11n: null argument", 0);
-    if (nframes == 0) return SORA_OK;
+    STAGE_ENTRY("sora_hip_sig_decode11n", !d_soft || !d_rec, nframes)
     hipLaunchKernelGGL(k_sig_decode11n_batch, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_soft, d_rec, (uint32_t)nframes);
     return launch_result("k_sig_decode11n_batch");
 }
 
-// ---- the bricks that complete the receive graph (sora_hip_cca11n .. sora_hip_frame_sink11a); the conventions of the 802.11b receive stage block
-#define ST11N_ENTRY(who, nullcond, count) \
-    if (nullcond) return sora_internal_fail(SORA_ERR_INVALID_PARAM, who ": null pointer", 0); \
-    if ((count) == 0) return SORA_OK;                       /* (nothing to launch: true with or without a device) */ \
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0); \
-    if ((count) >= (1ull << 31)) return sora_internal_fail(SORA_ERR_CAPACITY, who ": too many for one call", 0);
+// ---- the bricks that complete the receive graph (sora_hip_cca11n .. sora_hip_frame_sink11a)
 static_assert(sizeof(sora_cca11n_state) == 4 * kCcaWords && sizeof(sora_sink11a_rec) == 8, "the 802.11n stage records are 32-bit words");
-namespace {
-int stage_tables11n(Tables* T)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || sora_internal_tables(dev, T) != SORA_OK) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "table upload failed", 0);
-    return SORA_OK;
-}
-}  // namespace
 
 int sora_hip_cca11n(const sora_complex16* d_in0, const sora_complex16* d_in1, const uint32_t* d_first, const uint32_t* d_n, sora_cca11n_state* d_state, uint32_t* d_used,
                     size_t nstreams, size_t max_n, unsigned flags, void* stream)
 {
     (void)max_n;                                                                 // (a wave per stream walks its own d_n[f])
-    ST11N_ENTRY("sora_hip_cca11n", !d_in0 || !d_in1 || !d_first || !d_n || !d_state || !d_used, nstreams)
+    STAGE_ENTRY("sora_hip_cca11n", !d_in0 || !d_in1 || !d_first || !d_n || !d_state || !d_used, nstreams)
     if (flags & ~(unsigned)SORA_CCA11N_REARM) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_cca11n: unknown flag", 0);
-    hipLaunchKernelGGL(k_cca11n, dim3((unsigned)((nstreams + 3) / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in0),
-                       reinterpret_cast<const uint32_t*>(d_in1), d_first, d_n, reinterpret_cast<uint32_t*>(d_state), d_used, (uint32_t)nstreams, (uint32_t)flags);
+    hipLaunchKernelGGL(k_cca11n, dim3((unsigned)((nstreams + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_in0),
+                       u32(d_in1), d_first, d_n, u32(d_state), d_used, (uint32_t)nstreams, (uint32_t)flags);
     return launch_result("k_cca11n");
 }
 
 int sora_hip_data_symbol11n(const sora_complex16* d_in0, const sora_complex16* d_in1, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_out_first,
                             sora_complex16* d_out0, sora_complex16* d_out1, size_t nframes, size_t max_nsym, void* stream)
 {
-    ST11N_ENTRY("sora_hip_data_symbol11n", !d_in0 || !d_in1 || !d_first || !d_nsym || !d_out_first || !d_out0 || !d_out1, nframes)
+    STAGE_ENTRY("sora_hip_data_symbol11n", !d_in0 || !d_in1 || !d_first || !d_nsym || !d_out_first || !d_out0 || !d_out1, nframes)
     if (max_nsym == 0) return SORA_OK;
     if (nframes > 65535 || max_nsym > (1u << 27)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_data_symbol11n: at most 65535 frames of 2^27 symbols per call", 0);
     const unsigned gx = (unsigned)((max_nsym * 16 + 255) / 256);
-    hipLaunchKernelGGL(k_data_symbol11n, dim3(gx < 64 ? gx : 64, (unsigned)nframes), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in0),
-                       reinterpret_cast<const uint32_t*>(d_in1), reinterpret_cast<uint32_t*>(d_out0), reinterpret_cast<uint32_t*>(d_out1), d_first, d_nsym, d_out_first);
+    hipLaunchKernelGGL(k_data_symbol11n, dim3(gx < 64 ? gx : 64, (unsigned)nframes), dim3(256), 0, (hipStream_t)stream, u32(d_in0),
+                       u32(d_in1), u32(d_out0), u32(d_out1), d_first, d_nsym, d_out_first);
     return launch_result("k_data_symbol11n");
 }
 
 int sora_hip_stream_join11n(const uint8_t* d_s0, const uint8_t* d_s1, uint8_t* d_out, int n_bpsc, size_t n, void* stream)
 {
     if (!d_s0 || !d_s1 || !d_out) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_stream_join11n: null pointer", 0);
-    if (!(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_stream_join11n: n_bpsc must be 1, 2, 4 or 6", 0);
-    ST11N_ENTRY("sora_hip_stream_join11n", false, n)
+    STAGE_NBPSC("sora_hip_stream_join11n", n_bpsc)                                // (before the prologue: refused for a count of 0 too)
+    STAGE_ENTRY("sora_hip_stream_join11n", false, n)
     const uint64_t total = (uint64_t)n * 104 * n_bpsc;
-    const bool aligned = ((((uintptr_t)d_s0 | (uintptr_t)d_s1 | (uintptr_t)d_out) & 15) == 0);
-    const uint64_t chunks = aligned ? total / 96 : 0, tail = total - chunks * 96;
+    const uint64_t chunks = aligned16(d_s0, d_s1, d_out) ? total / 96 : 0, tail = total - chunks * 96;
     const uint64_t threads = chunks + (tail < 65536 ? tail : 65536);            // a thread per chunk, then the tail's bytes strided over up to 65536 more
     const unsigned grid = (unsigned)((threads + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
@@ -735,17 +693,16 @@ int sora_hip_stream_join11n(const uint8_t* d_s0, const uint8_t* d_s1, uint8_t* d
 
 int sora_hip_desc11a(const uint8_t* d_dec, const uint32_t* d_off, const uint32_t* d_len, uint8_t* d_out, const uint32_t* d_out_off, size_t n, void* stream)
 {
-    ST11N_ENTRY("sora_hip_desc11a", !d_dec || !d_off || !d_len || !d_out || !d_out_off, n)
-    Tables T; if (stage_tables11n(&T) != SORA_OK) return SORA_ERR_HARDWARE_FAILED;
+    STAGE_ENTRY("sora_hip_desc11a", !d_dec || !d_off || !d_len || !d_out || !d_out_off, n)
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
     hipLaunchKernelGGL(k_desc11a, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_dec, d_off, d_len, d_out, d_out_off, (uint32_t)n, T);
     return launch_result("k_desc11a");
 }
 
 int sora_hip_frame_sink11a(const uint8_t* d_bytes, const uint32_t* d_off, const uint32_t* d_len, sora_sink11a_rec* d_rec, size_t n, void* stream)
 {
-    ST11N_ENTRY("sora_hip_frame_sink11a", !d_bytes || !d_off || !d_len || !d_rec, n)
-    Tables T; if (stage_tables11n(&T) != SORA_OK) return SORA_ERR_HARDWARE_FAILED;
-    hipLaunchKernelGGL(k_frame_sink11a, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_bytes, d_off, d_len, reinterpret_cast<uint32_t*>(d_rec), (uint32_t)n, T);
+    STAGE_ENTRY("sora_hip_frame_sink11a", !d_bytes || !d_off || !d_len || !d_rec, n)
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    hipLaunchKernelGGL(k_frame_sink11a, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_bytes, d_off, d_len, u32(d_rec), (uint32_t)n, T);
     return launch_result("k_frame_sink11a");
 }
-#undef ST11N_ENTRY

@@ -15,7 +15,7 @@
 #include "kernels.h"
 #include "dev_11n.h"
 #include "dev_ht40.h"
-#include "../../include/sora_hip.h"
+#include "host_stage.h"
 
 namespace sora {
 
@@ -235,91 +235,72 @@ __global__ void __launch_bounds__(256) k_ht40s_noise_var(const uint32_t* __restr
 
 using namespace sora;
 
-#define HT40_ENTRY(who, nullcond, count) \
-    if (nullcond) return sora_internal_fail(SORA_ERR_INVALID_PARAM, who ": null pointer", 0); \
-    if ((count) == 0) return SORA_OK;                       /* (nothing to launch: true with or without a device) */ \
-    if (sora_hip_device_count() <= 0) return sora_internal_fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path", 0); \
-    if ((count) >= (1ull << 31)) return sora_internal_fail(SORA_ERR_CAPACITY, who ": too many for one call", 0);
-#define HT40_NBPSC(who, nb) \
-    if (!((nb) == 1 || (nb) == 2 || (nb) == 4 || (nb) == 6)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, who ": n_bpsc must be 1, 2, 4 or 6", 0);
-namespace {
-int launched(const char* what) { const hipError_t e = hipGetLastError(); return e == hipSuccess ? SORA_OK : sora_internal_fail(SORA_ERR_HARDWARE_FAILED, what, (int)e); }
-template <class... P> bool aligned16(P... p) { return ((... | (uintptr_t)p) & 15) == 0; }
-template <class... P> bool aligned4(P... p) { return ((... | (uintptr_t)p) & 3) == 0; }
-const uint32_t* u32(const sora_complex16* p) { return reinterpret_cast<const uint32_t*>(p); }
-uint32_t* u32(sora_complex16* p) { return reinterpret_cast<uint32_t*>(p); }
-}  // namespace
-
+// ---- the stage entry points (host_stage.h: the prologue and helpers every stage shares).  n_bpsc and spatial_stream are checked before the prologue here
 int sora_hip_data_symbol_ht40(const sora_complex16* d_in0, const sora_complex16* d_in1, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_out_first,
                               sora_complex16* d_out0, sora_complex16* d_out1, size_t nframes, size_t max_nsym, void* stream)
 {
-    HT40_ENTRY("sora_hip_data_symbol_ht40", !d_in0 || !d_in1 || !d_first || !d_nsym || !d_out_first || !d_out0 || !d_out1, nframes)
+    STAGE_ENTRY("sora_hip_data_symbol_ht40", !d_in0 || !d_in1 || !d_first || !d_nsym || !d_out_first || !d_out0 || !d_out1, nframes)
     if (max_nsym == 0) return SORA_OK;
     if (nframes > 65535 || max_nsym > (1u << 26)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_data_symbol_ht40: at most 65535 frames of 2^26 symbols per call", 0);
     const unsigned gx = (unsigned)((max_nsym * 32 + 255) / 256);
     hipLaunchKernelGGL(k_ht40s_data_symbol, dim3(gx < 64 ? gx : 64, (unsigned)nframes), dim3(256), 0, (hipStream_t)stream, u32(d_in0), u32(d_in1), u32(d_out0), u32(d_out1),
                        d_first, d_nsym, d_out_first);
-    return launched("k_ht40s_data_symbol");
+    return launch_result("k_ht40s_data_symbol");
 }
 
 int sora_hip_mimo_est_ht40(const sora_complex16* d_ltf0, const sora_complex16* d_ltf1, const float* d_noise_var, sora_complex16* d_h, sora_complex16* d_w, size_t nframes,
                            void* stream)
 {
-    HT40_ENTRY("sora_hip_mimo_est_ht40", !d_ltf0 || !d_ltf1 || !d_w, nframes)
+    STAGE_ENTRY("sora_hip_mimo_est_ht40", !d_ltf0 || !d_ltf1 || !d_w, nframes)
     hipLaunchKernelGGL(k_ht40s_mimo_est, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_ltf0), u32(d_ltf1), d_noise_var, d_h ? u32(d_h) : nullptr,
                        u32(d_w), (uint32_t)nframes);
-    return launched("k_ht40s_mimo_est");
+    return launch_result("k_ht40s_mimo_est");
 }
 
 int sora_hip_mimo_comp_ht40(const sora_complex16* d_w, const uint32_t* d_frame_index, const sora_complex16* d_y0, const sora_complex16* d_y1, sora_complex16* d_x0,
                             sora_complex16* d_x1, size_t nsym, void* stream)
 {
-    HT40_ENTRY("sora_hip_mimo_comp_ht40", !d_w || !d_y0 || !d_y1 || !d_x0 || !d_x1, nsym)
+    STAGE_ENTRY("sora_hip_mimo_comp_ht40", !d_w || !d_y0 || !d_y1 || !d_x0 || !d_x1, nsym)
     hipLaunchKernelGGL(k_ht40s_mimo_comp, dim3((unsigned)((nsym + 7) / 8)), dim3(256), 0, (hipStream_t)stream, u32(d_w), d_frame_index, u32(d_y0), u32(d_y1), u32(d_x0), u32(d_x1),
                        (uint32_t)nsym, aligned16(d_w, d_y0, d_y1, d_x0, d_x1) ? 1 : 0);
-    return launched("k_ht40s_mimo_comp");
+    return launch_result("k_ht40s_mimo_comp");
 }
 
 int sora_hip_pilot_track_ht40(const sora_complex16* d_x0, const sora_complex16* d_x1, const uint32_t* d_first, const uint32_t* d_nsym, int16_t* d_state, int16_t* d_theta,
                               size_t nframes, void* stream)
 {
-    HT40_ENTRY("sora_hip_pilot_track_ht40", !d_x0 || !d_x1 || !d_first || !d_nsym || !d_state, nframes)
+    STAGE_ENTRY("sora_hip_pilot_track_ht40", !d_x0 || !d_x1 || !d_first || !d_nsym || !d_state, nframes)
     const uint32_t* sincos = nullptr; const short* atan = nullptr;
     if (sora_internal_dsp_tables(&sincos, &atan) != SORA_OK) return sora_internal_fail(SORA_ERR_HARDWARE_FAILED, "dsp_math table upload failed", 0);
     hipLaunchKernelGGL(k_ht40s_pilot_track, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_x0), u32(d_x1), d_first, d_nsym, d_state, d_theta,
                        (uint32_t)nframes, atan);
-    return launched("k_ht40s_pilot_track");
+    return launch_result("k_ht40s_pilot_track");
 }
 
 int sora_hip_demap_ht40(const sora_complex16* d_in, uint8_t* d_soft, int n_bpsc, size_t n, void* stream)
 {
-    HT40_NBPSC("sora_hip_demap_ht40", n_bpsc)
-    HT40_ENTRY("sora_hip_demap_ht40", !d_in || !d_soft, n)
+    STAGE_NBPSC("sora_hip_demap_ht40", n_bpsc)
+    STAGE_ENTRY("sora_hip_demap_ht40", !d_in || !d_soft, n)
     const dim3 grid((unsigned)((n + 7) / 8)); hipStream_t st = (hipStream_t)stream;
     const int vi = aligned16(d_in) ? 1 : 0, vo = aligned4(d_soft) ? 1 : 0;
-    switch (n_bpsc) {
-    case 1: hipLaunchKernelGGL(k_ht40s_demap<1>, grid, dim3(256), 0, st, u32(d_in), d_soft, (uint32_t)n, vi, vo); break;
-    case 2: hipLaunchKernelGGL(k_ht40s_demap<2>, grid, dim3(256), 0, st, u32(d_in), d_soft, (uint32_t)n, vi, vo); break;
-    case 4: hipLaunchKernelGGL(k_ht40s_demap<4>, grid, dim3(256), 0, st, u32(d_in), d_soft, (uint32_t)n, vi, vo); break;
-    default: hipLaunchKernelGGL(k_ht40s_demap<6>, grid, dim3(256), 0, st, u32(d_in), d_soft, (uint32_t)n, vi, vo); break;
-    }
-    return launched("k_ht40s_demap");
+    STAGE_BY_NBPSC(n_bpsc, k_ht40s_demap, grid, st, u32(d_in), d_soft, (uint32_t)n, vi, vo)
+    return launch_result("k_ht40s_demap");
 }
 
 int sora_hip_deinterleave_ht40(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, int spatial_stream, size_t n, void* stream)
 {
-    HT40_NBPSC("sora_hip_deinterleave_ht40", n_bpsc)
+    STAGE_NBPSC("sora_hip_deinterleave_ht40", n_bpsc)
     if (spatial_stream < 0 || spatial_stream > 1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_deinterleave_ht40: spatial_stream must be 0 or 1", 0);
-    HT40_ENTRY("sora_hip_deinterleave_ht40", !d_in || !d_out, n)
+    STAGE_ENTRY("sora_hip_deinterleave_ht40", !d_in || !d_out, n)
     hipLaunchKernelGGL(k_ht40s_deint, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, (hipStream_t)stream, d_in, d_out, n_bpsc, spatial_stream, (uint32_t)n,
                        aligned4(d_in, d_out) ? 1 : 0);
-    return launched("k_ht40s_deint");
+    return launch_result("k_ht40s_deint");
 }
 
 int sora_hip_stream_join_ht40(const uint8_t* d_s0, const uint8_t* d_s1, uint8_t* d_out, int n_bpsc, size_t n, void* stream)
 {
-    HT40_NBPSC("sora_hip_stream_join_ht40", n_bpsc)
-    HT40_ENTRY("sora_hip_stream_join_ht40", !d_s0 || !d_s1 || !d_out, n)
+    STAGE_NBPSC("sora_hip_stream_join_ht40", n_bpsc)
+    STAGE_ENTRY("sora_hip_stream_join_ht40", !d_s0 || !d_s1 || !d_out, n)
     // 108 N_BPSC is a multiple of s for every modulation: the whole call is one interleave of two byte streams, the 802.11n stage's kernel over 216 N_BPSC per symbol
     const uint64_t total = (uint64_t)n * 216 * n_bpsc;
     const uint64_t chunks = aligned16(d_s0, d_s1, d_out) ? total / 96 : 0, tail = total - chunks * 96;
@@ -331,27 +312,25 @@ int sora_hip_stream_join_ht40(const uint8_t* d_s0, const uint8_t* d_s1, uint8_t*
     case 6: hipLaunchKernelGGL(k_stream_join11n<3>, dim3(grid), dim3(256), 0, st, d_s0, d_s1, d_out, total, chunks); break;
     default: hipLaunchKernelGGL(k_stream_join11n<1>, dim3(grid), dim3(256), 0, st, d_s0, d_s1, d_out, total, chunks); break;
     }
-    return launched("k_stream_join11n");
+    return launch_result("k_stream_join11n");
 }
 
 int sora_hip_downsample_ht40(const sora_complex16* d_in0, const sora_complex16* d_in1, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_m0,
                              const uint32_t* d_out_first, sora_complex16* d_out0, sora_complex16* d_out1, size_t nstreams, size_t max_n, void* stream)
 {
-    HT40_ENTRY("sora_hip_downsample_ht40", !d_in0 || !d_in1 || !d_first || !d_n || !d_m0 || !d_out_first || !d_out0 || !d_out1, nstreams)
+    STAGE_ENTRY("sora_hip_downsample_ht40", !d_in0 || !d_in1 || !d_first || !d_n || !d_m0 || !d_out_first || !d_out0 || !d_out1, nstreams)
     if (max_n == 0) return SORA_OK;
     if (nstreams > 65535 || max_n >= (1ull << 31)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_downsample_ht40: at most 65535 streams of 2^31 - 1 kept samples per call", 0);
     const unsigned gx = (unsigned)((max_n / 4 + 256) / 256);
     hipLaunchKernelGGL(k_ht40s_downsample, dim3(gx < 256 ? gx : 256, (unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, u32(d_in0), u32(d_in1), u32(d_out0), u32(d_out1),
                        d_first, d_n, d_m0, d_out_first, (uint32_t)max_n);
-    return launched("k_ht40s_downsample");
+    return launch_result("k_ht40s_downsample");
 }
 
 int sora_hip_noise_var_ht40(const sora_complex16* d_lltf0, const sora_complex16* d_lltf1, uint64_t* d_S, float* d_noise_var, size_t nframes, void* stream)
 {
-    HT40_ENTRY("sora_hip_noise_var_ht40", !d_lltf0 || !d_lltf1 || !d_noise_var, nframes)
+    STAGE_ENTRY("sora_hip_noise_var_ht40", !d_lltf0 || !d_lltf1 || !d_noise_var, nframes)
     hipLaunchKernelGGL(k_ht40s_noise_var, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, u32(d_lltf0), u32(d_lltf1),
                        reinterpret_cast<unsigned long long*>(d_S), d_noise_var, (uint32_t)nframes);
-    return launched("k_ht40s_noise_var");
+    return launch_result("k_ht40s_noise_var");
 }
-#undef HT40_ENTRY
-#undef HT40_NBPSC

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "dev_tx.h"
+#include "host_stage.h"
 
 namespace sora {
 
@@ -320,3 +321,109 @@ __global__ void __launch_bounds__(64) k_mod_preamble(uint32_t* __restrict__ out,
 }
 
 }  // namespace sora
+
+using namespace sora;
+
+// ---- the stage entry points (host_stage.h: the prologue and helpers every stage shares)
+int sora_hip_scramble11a(const uint8_t* d_in, uint8_t* d_out, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_tail, const uint8_t* d_seed,
+                         size_t nframes, size_t max_len, void* stream)
+{
+    STAGE_ENTRY("sora_hip_scramble11a", !d_in || !d_out || !d_off || !d_len || !d_seed, nframes)
+    if (max_len == 0) return SORA_OK;
+    uint32_t chunks; unsigned grid;
+    if (!stage_grid(nframes, max_len, &chunks, &grid)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_scramble11a: nframes x max_len is too large for one call", 0);
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    hipLaunchKernelGGL(k_mod_scramble, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_in, d_out, d_off, d_len, d_tail, d_seed, (uint32_t)nframes, chunks, T);
+    return launch_result("k_mod_scramble");
+}
+
+int sora_hip_conv_encode11a(const uint8_t* d_in, const uint32_t* d_in_off, const uint32_t* d_len, int code_rate, uint8_t* d_out, const uint32_t* d_out_off,
+                            size_t nframes, size_t max_len, void* stream)
+{
+    STAGE_ENTRY("sora_hip_conv_encode11a", !d_in || !d_in_off || !d_len || !d_out || !d_out_off, nframes)
+    if (code_rate != SORA_CR_12 && code_rate != SORA_CR_23 && code_rate != SORA_CR_34) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_conv_encode11a: bad code rate", 0);
+    if (max_len >= (1u << 27)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_conv_encode11a: a frame of 128 MiB or more", 0);
+    const size_t bin = (size_t)code_rate + 1, max_out = max_len / bin * (bin + 1);
+    if (max_out == 0) return SORA_OK;
+    uint32_t chunks; unsigned grid;
+    if (!stage_grid(nframes, max_out, &chunks, &grid)) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_conv_encode11a: nframes x max_len is too large for one call", 0);
+    hipLaunchKernelGGL(k_mod_encode, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_in, d_in_off, d_len, code_rate, d_out, d_out_off, (uint32_t)nframes, chunks);
+    return launch_result("k_mod_encode");
+}
+
+int sora_hip_interleave11a(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, size_t nsym, void* stream)
+{
+    STAGE_ENTRY("sora_hip_interleave11a", !d_in || !d_out, nsym)
+    STAGE_NBPSC("sora_hip_interleave11a", n_bpsc)
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_interleave11a: buffers must be 16-byte aligned", 0);
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    const dim3 grid((unsigned)((nsym + 31) / 32));
+    STAGE_BY_NBPSC(n_bpsc, k_mod_interleave, grid, (hipStream_t)stream, d_in, d_out, (uint32_t)nsym, T)
+    return launch_result("k_mod_interleave");
+}
+
+int sora_hip_map11a(const uint8_t* d_in, sora_complex16* d_out, int n_bpsc, int mod, size_t nsym, void* stream)
+{
+    STAGE_ENTRY("sora_hip_map11a", !d_in || !d_out, nsym)
+    STAGE_NBPSC("sora_hip_map11a", n_bpsc)
+    if (mod < 0 || mod > 32767) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11a: mod must be 0 .. 32767", 0);
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11a: buffers must be 16-byte aligned", 0);
+    if (mod == 0) mod = n_bpsc == 1 ? 10720 : n_bpsc == 2 ? (short)(10720 / 1.414) : n_bpsc == 4 ? (short)(10720 / 3.162) : (short)(10720 / 6.481);   // mapper11a.hpp:8-11
+    const dim3 grid((unsigned)((nsym + 31) / 32));
+    STAGE_BY_NBPSC(n_bpsc, k_mod_map, grid, (hipStream_t)stream, d_in, u32(d_out), mod, (uint32_t)nsym)
+    return launch_result("k_mod_map");
+}
+
+int sora_hip_add_pilot11a_from(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_pos0,
+                               size_t nframes, int bpsk_mod, void* stream)
+{
+    STAGE_ENTRY("sora_hip_add_pilot11a", !d_in || !d_out || !d_first || !d_nsym, nframes)
+    if (bpsk_mod < 0 || bpsk_mod > 32767) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11a: bpsk_mod must be 0 .. 32767", 0);
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11a: buffers must be 16-byte aligned", 0);
+    // the frames' lengths are device memory: a batch of few frames gets several workgroups per frame, each striding over the frame's passes of 16 symbols
+    const unsigned gy = nframes >= 2048 ? 1u : (unsigned)std::min<size_t>(64, 2048 / nframes);
+    hipLaunchKernelGGL(k_mod_add_pilot, dim3((unsigned)nframes, gy), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), d_first, d_nsym, d_pos0, (uint32_t)nframes,
+                       bpsk_mod ? bpsk_mod : 10720);
+    return launch_result("k_mod_add_pilot");
+}
+int sora_hip_add_pilot11a(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, size_t nframes, int bpsk_mod, void* stream)
+{
+    return sora_hip_add_pilot11a_from(d_in, d_out, d_first, d_nsym, nullptr, nframes, bpsk_mod, stream);
+}
+
+int sora_hip_ifftx11a(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream)
+{
+    STAGE_ENTRY("sora_hip_ifftx11a", !d_in || !d_out, nsym)
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_ifftx11a: buffers must be 16-byte aligned", 0);
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    hipLaunchKernelGGL(k_mod_ifftx, dim3((unsigned)((nsym + 31) / 32)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), (uint32_t)nsym, T);
+    return launch_result("k_mod_ifftx");
+}
+
+int sora_hip_upsample40to44(const sora_complex16* d_in, sora_complex16* d_out, const uint8_t* d_sees_next, size_t nblocks, void* stream)
+{
+    STAGE_ENTRY("sora_hip_upsample40to44", !d_in || !d_out, nblocks)
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_upsample40to44: buffers must be 16-byte aligned", 0);
+    hipLaunchKernelGGL(k_mod_upsample, dim3((unsigned)((nblocks + 7) / 8)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), d_sees_next, (uint32_t)nblocks);
+    return launch_result("k_mod_upsample");
+}
+
+int sora_hip_pack16to8(const sora_complex16* d_in, int8_t* d_out, size_t nsamples, void* stream)
+{
+    // (counted in workgroups, 256 bursts of 8 samples each: what one launch is limited by; 0 exactly when nsamples is)
+    STAGE_ENTRY("sora_hip_pack16to8", !d_in || !d_out, (nsamples + 2047) / 2048)
+    if (nsamples % 8) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_pack16to8: nsamples must be a multiple of 8 (the brick's burst)", 0);
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_pack16to8: buffers must be 16-byte aligned", 0);
+    const uint64_t nb = nsamples / 8;
+    hipLaunchKernelGGL(k_mod_pack16to8, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), nb);
+    return launch_result("k_mod_pack16to8");
+}
+
+int sora_hip_preamble11a(sora_complex16* d_out, size_t ncopies, void* stream)
+{
+    STAGE_ENTRY("sora_hip_preamble11a", !d_out, ncopies)
+    if (!aligned16(d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble11a: the buffer must be 16-byte aligned", 0);
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    hipLaunchKernelGGL(k_mod_preamble, dim3((unsigned)std::min<size_t>(ncopies, 2048)), dim3(64), 0, (hipStream_t)stream, u32(d_out), (uint32_t)ncopies, T);
+    return launch_result("k_mod_preamble");
+}

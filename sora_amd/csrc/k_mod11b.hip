@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "dev_tx.h"
 #include "dev_mod11b.h"
+#include "host_stage.h"
 
 namespace sora {
 
@@ -302,3 +303,58 @@ __global__ void __launch_bounds__(kMod11bThreads) k_mod11b_shape(const uint16_t*
 }
 
 }  // namespace sora
+
+using namespace sora;
+
+// ---- the stage entry points (host_stage.h: the prologue and helpers every stage shares): a workgroup per stream
+static_assert(sizeof(sora_mod11b_state) == 16 && sizeof(sora_shaper11b_state) == 64, "the 802.11b modulation stage records are 32-bit words");
+constexpr size_t kMod11bMaxN = (size_t)1 << 24;             // 88 chips a byte: a stream's output offsets stay 32-bit
+
+int sora_hip_ppdu11b(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_preamble, uint8_t* d_out,
+                     const uint32_t* d_out_first, size_t nframes, void* stream)
+{
+    STAGE_ENTRY("sora_hip_ppdu11b", !d_mpdu || !d_off || !d_len || !d_rate_kbps || !d_preamble || !d_out || !d_out_first, nframes)
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    hipLaunchKernelGGL(k_mod11b_ppdu, dim3((unsigned)nframes), dim3(256), 0, (hipStream_t)stream, d_mpdu, d_off, d_len, d_rate_kbps, d_preamble, d_out, d_out_first, T.crc, T.crcz);
+    return launch_result("k_mod11b_ppdu");
+}
+
+int sora_hip_sc741_11b(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, uint32_t* d_reg, uint8_t* d_out,
+                       size_t nstreams, size_t max_n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_sc741_11b", !d_in || !d_first || !d_n || !d_out_first || !d_reg || !d_out, nstreams)
+    if (max_n == 0) return SORA_OK;
+    if (max_n > kMod11bMaxN) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_sc741_11b: max_n is too large for one call", 0);
+    hipLaunchKernelGGL(k_mod11b_sc741, dim3((unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, d_in, d_out, d_first, d_n, d_out_first, d_reg, (uint32_t)max_n);
+    return launch_result("k_mod11b_sc741");
+}
+
+#define MOD11B_SPREAD(name, kernel) \
+    int name(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_mod11b_state* d_state, int8_t* d_out, size_t nstreams, \
+             size_t max_n, void* stream) \
+    { \
+        STAGE_ENTRY(#name, !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out, nstreams) \
+        if (max_n == 0) return SORA_OK; \
+        if (max_n > kMod11bMaxN) return sora_internal_fail(SORA_ERR_CAPACITY, #name ": max_n is too large for one call", 0); \
+        if ((uintptr_t)d_out & 1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, #name ": d_out must be aligned to a COMPLEX8", 0); \
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, d_in, reinterpret_cast<uint16_t*>(d_out), d_first, d_n, d_out_first, \
+                           u32(d_state), (uint32_t)max_n); \
+        return launch_result(#kernel); \
+    }
+MOD11B_SPREAD(sora_hip_dbpsk_spread11b, k_mod11b_dbpsk)
+MOD11B_SPREAD(sora_hip_dqpsk_spread11b, k_mod11b_dqpsk)
+MOD11B_SPREAD(sora_hip_cck5_encode11b, k_mod11b_cck5)
+MOD11B_SPREAD(sora_hip_cck11_encode11b, k_mod11b_cck11)
+#undef MOD11B_SPREAD
+
+int sora_hip_pulse_shape11b(const int8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const uint8_t* d_flush,
+                            sora_shaper11b_state* d_state, sora_complex16* d_out, size_t nstreams, size_t max_n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_pulse_shape11b", !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out, nstreams)
+    if (max_n == 0 && !d_flush) return SORA_OK;
+    if (max_n > kMod11bMaxN) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_hip_pulse_shape11b: max_n is too large for one call", 0);
+    if (((uintptr_t)d_in & 1) || !aligned4(d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_pulse_shape11b: d_in and d_out must be aligned to their elements", 0);
+    hipLaunchKernelGGL(k_mod11b_shape, dim3((unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint16_t*>(d_in), u32(d_out), d_first, d_n, d_out_first,
+                       d_flush, u32(d_state), (uint32_t)max_n);
+    return launch_result("k_mod11b_shape");
+}

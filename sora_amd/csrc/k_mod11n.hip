@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "dev_tx.h"
 #include "dev_11n.h"
+#include "host_stage.h"
 
 namespace sora {
 
@@ -262,3 +263,91 @@ __global__ void __launch_bounds__(256) k_mod11n_preamble(const uint4* __restrict
 }
 
 }  // namespace sora
+
+using namespace sora;
+
+// ---- the stage entry points (host_stage.h: the prologue and helpers every stage shares).  sora_hip_preamble11n stands beside sora_hip_tx11n, whose table it copies
+int sora_hip_stream_parse11n(const uint8_t* d_in, uint8_t* d_out0, uint8_t* d_out1, int n_bpsc, size_t nsym, void* stream)
+{
+    STAGE_ENTRY("sora_hip_stream_parse11n", !d_in || !d_out0 || !d_out1, nsym)
+    STAGE_NBPSC("sora_hip_stream_parse11n", n_bpsc)
+    if (!aligned16(d_in, d_out0, d_out1)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_stream_parse11n: buffers must be 16-byte aligned", 0);
+    const dim3 grid((unsigned)((nsym + 31) / 32));
+    STAGE_BY_NBPSC(n_bpsc, k_mod11n_parse, grid, (hipStream_t)stream, d_in, d_out0, d_out1, (uint32_t)nsym)
+    return launch_result("k_mod11n_parse");
+}
+
+int sora_hip_interleave11n(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, int spatial_stream, size_t nsym, void* stream)
+{
+    STAGE_ENTRY("sora_hip_interleave11n", !d_in || !d_out, nsym)
+    STAGE_NBPSC("sora_hip_interleave11n", n_bpsc)
+    if (spatial_stream < 0 || spatial_stream > 1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_interleave11n: spatial_stream must be 0 or 1", 0);
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_interleave11n: buffers must be 16-byte aligned", 0);
+    const dim3 grid((unsigned)((nsym + 31) / 32));
+    STAGE_BY_NBPSC(n_bpsc, k_mod11n_interleave, grid, (hipStream_t)stream, d_in, d_out, spatial_stream, (uint32_t)nsym)
+    return launch_result("k_mod11n_interleave");
+}
+
+int sora_hip_map11n(const uint8_t* d_in, sora_complex16* d_out, int n_bpsc, int mod, size_t nsym, void* stream)
+{
+    STAGE_ENTRY("sora_hip_map11n", !d_in || !d_out, nsym)
+    STAGE_NBPSC("sora_hip_map11n", n_bpsc)
+    if (mod < 0 || mod > 32767) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11n: mod must be 0 .. 32767", 0);
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11n: buffers must be 16-byte aligned", 0);
+    if (mod == 0) mod = n_bpsc == 1 ? 30339 : n_bpsc == 2 ? 21453 : n_bpsc == 4 ? 9594 : 4681;   // fb11nmod_config.hpp:121-128
+    const dim3 grid((unsigned)((nsym + 31) / 32));
+    STAGE_BY_NBPSC(n_bpsc, k_mod11n_map, grid, (hipStream_t)stream, d_in, u32(d_out), mod, (uint32_t)nsym)
+    return launch_result("k_mod11n_map");
+}
+
+int sora_hip_sig_map11n(const uint8_t* d_in, sora_complex16* d_out, size_t nframes, void* stream)
+{
+    STAGE_ENTRY("sora_hip_sig_map11n", !d_in || !d_out, nframes)
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_sig_map11n: buffers must be 16-byte aligned", 0);
+    hipLaunchKernelGGL(k_mod11n_sig_map, dim3((unsigned)((nframes + 31) / 32)), dim3(256), 0, (hipStream_t)stream, d_in, u32(d_out), (uint32_t)nframes);
+    return launch_result("k_mod11n_sig_map");
+}
+
+int sora_hip_add_pilot11n(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_pos0,
+                          size_t nframes, int spatial_stream, void* stream)
+{
+    STAGE_ENTRY("sora_hip_add_pilot11n", !d_in || !d_out || !d_first || !d_nsym, nframes)
+    if (spatial_stream < 0 || spatial_stream > 1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11n: spatial_stream must be 0 or 1", 0);
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11n: buffers must be 16-byte aligned", 0);
+    // (sora_hip_add_pilot11a's grid: a batch of few frames gets several workgroups per frame, each striding over the frame's passes of 16 symbols)
+    const unsigned gy = nframes >= 2048 ? 1u : (unsigned)std::min<size_t>(64, 2048 / nframes);
+    hipLaunchKernelGGL(k_mod11n_add_pilot, dim3((unsigned)nframes, gy), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), d_first, d_nsym, d_pos0, (uint32_t)nframes,
+                       spatial_stream);
+    return launch_result("k_mod11n_add_pilot");
+}
+
+int sora_hip_ifft_only11n(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream)
+{
+    STAGE_ENTRY("sora_hip_ifft_only11n", !d_in || !d_out, nsym)
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_ifft_only11n: buffers must be 16-byte aligned", 0);
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    hipLaunchKernelGGL(k_mod11n_ifft, dim3((unsigned)((nsym + 31) / 32)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), (uint32_t)nsym, T);
+    return launch_result("k_mod11n_ifft");
+}
+
+int sora_hip_csd11n(const sora_complex16* d_in, sora_complex16* d_out, int ncsd, size_t nsym, void* stream)
+{
+    STAGE_ENTRY("sora_hip_csd11n", !d_in || !d_out, nsym)
+    if (ncsd < 1 || ncsd > 31) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_csd11n: ncsd must be 1 .. 31", 0);
+    if (d_in == d_out) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_csd11n: out of place only", 0);
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_csd11n: buffers must be 16-byte aligned", 0);
+    const uint64_t nwords = (uint64_t)nsym * 32;
+    hipLaunchKernelGGL(k_mod11n_csd, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(d_in),
+                       reinterpret_cast<uint4*>(d_out), ncsd, nwords);
+    return launch_result("k_mod11n_csd");
+}
+
+int sora_hip_add_gi11n(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream)
+{
+    STAGE_ENTRY("sora_hip_add_gi11n", !d_in || !d_out, nsym)
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_gi11n: buffers must be 16-byte aligned", 0);
+    const uint64_t nwords = (uint64_t)nsym * 40;
+    hipLaunchKernelGGL(k_mod11n_add_gi, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(d_in),
+                       reinterpret_cast<uint4*>(d_out), nwords);
+    return launch_result("k_mod11n_add_gi");
+}

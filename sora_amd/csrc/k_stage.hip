@@ -15,6 +15,7 @@
 // Pointers given to these entry points must be 16-byte aligned (any hipMalloc'd buffer is).
 #include "kernels.h"
 #include "dev_sym11a.h"
+#include "host_stage.h"
 
 namespace sora {
 
@@ -436,3 +437,115 @@ __global__ void __launch_bounds__(256) k_ingest_tile(const uint8_t* __restrict__
 }
 
 }  // namespace sora
+
+using namespace sora;
+
+// ---- the stage entry points (host_stage.h: the prologue and helpers every stage shares)
+static_assert(sizeof(sora_lts11a_ctx) == 516 && sizeof(sora_track11a_state) == 268, "the 802.11a symbol chain's records are 32-bit words");
+
+int sora_hip_fft64(const sora_complex16* d_in, sora_complex16* d_out, size_t n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_fft64", !d_in || !d_out, n)
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_fft64: buffers must be 16-byte aligned", 0);
+    hipLaunchKernelGGL(k_fft64_batch, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), (uint32_t)n, T);
+    return launch_result("k_fft64_batch");
+}
+
+int sora_hip_fft128(const sora_complex16* d_in, sora_complex16* d_out, size_t n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_fft128", !d_in || !d_out, n)
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_fft128: buffers must be 16-byte aligned", 0);
+    hipLaunchKernelGGL(k_fft128_batch, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), (uint32_t)n, T);
+    return launch_result("k_fft128_batch");
+}
+
+int sora_hip_lts11a(const sora_complex16* d_in, sora_lts11a_ctx* d_ctx, size_t n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_lts11a", !d_in || !d_ctx, n)
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    hipLaunchKernelGGL(k_lts_batch, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, u32(d_in), u32(d_ctx), (uint32_t)n, T);
+    return launch_result("k_lts_batch");
+}
+
+int sora_hip_symfront11a(const sora_complex16* d_in, const sora_lts11a_ctx* d_ctx, const uint32_t* d_ctx_index, sora_complex16* d_eq, size_t n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_symfront11a", !d_in || !d_ctx || !d_eq, n)
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    if (!aligned16(d_in, d_eq)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_symfront11a: sample and output buffers must be 16-byte aligned", 0);
+    hipLaunchKernelGGL(k_symfront_batch, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_ctx), d_ctx_index, u32(d_eq), (uint32_t)n, T);
+    return launch_result("k_symfront_batch");
+}
+
+// The symbol chain's three one-multiply bricks on their own (k_cmul64_batch), behind their entry's prologue
+static int cmul64_stage(int kind, const sora_complex16* d_in, const void* d_coef, uint32_t cstride_words, uint32_t coff_words, const uint32_t* d_index, sora_complex16* d_out,
+                        size_t n, void* stream)
+{
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "symbol buffers must be 16-byte aligned", 0);
+    const dim3 grid((unsigned)((n + 127) / 128)); const hipStream_t st = (hipStream_t)stream;
+    if (kind == 0)      hipLaunchKernelGGL(k_cmul64_batch<0>, grid, dim3(256), 0, st, u32(d_in), u32(d_coef), cstride_words, coff_words, d_index, u32(d_out), (uint32_t)n);
+    else if (kind == 1) hipLaunchKernelGGL(k_cmul64_batch<1>, grid, dim3(256), 0, st, u32(d_in), u32(d_coef), cstride_words, coff_words, d_index, u32(d_out), (uint32_t)n);
+    else                hipLaunchKernelGGL(k_cmul64_batch<2>, grid, dim3(256), 0, st, u32(d_in), u32(d_coef), cstride_words, coff_words, d_index, u32(d_out), (uint32_t)n);
+    return launch_result("k_cmul64_batch");
+}
+int sora_hip_freq_comp11a(const sora_complex16* d_in, const sora_lts11a_ctx* d_ctx, const uint32_t* d_ctx_index, sora_complex16* d_out, size_t n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_freq_comp11a", !d_in || !d_ctx || !d_out, n)
+    return cmul64_stage(0, d_in, d_ctx, 129u, 1u, d_ctx_index, d_out, n, stream);
+}
+int sora_hip_equalize11a(const sora_complex16* d_in, const sora_lts11a_ctx* d_ctx, const uint32_t* d_ctx_index, sora_complex16* d_out, size_t n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_equalize11a", !d_in || !d_ctx || !d_out, n)
+    return cmul64_stage(1, d_in, d_ctx, 129u, 65u, d_ctx_index, d_out, n, stream);
+}
+int sora_hip_phase_comp11a(const sora_complex16* d_in, const sora_track11a_state* d_state, const uint32_t* d_state_index, sora_complex16* d_out, size_t n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_phase_comp11a", !d_in || !d_state || !d_out, n)
+    return cmul64_stage(2, d_in, d_state, 67u, 3u, d_state_index, d_out, n, stream);
+}
+
+// the pilot tracker with (phase) and without the phase compensation behind it, behind their entry's prologue
+static int ptrack_stage(bool phase, const sora_complex16* d_eq, const uint32_t* d_first, const uint32_t* d_nsym, sora_track11a_state* d_state, sora_complex16* d_out,
+                        size_t nframes, void* stream)
+{
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    const dim3 grid((unsigned)nframes); const hipStream_t st = (hipStream_t)stream;
+    if (phase) hipLaunchKernelGGL(k_ptrack_batch<true>, grid, dim3(64), 0, st, u32(d_eq), d_first, d_nsym, u32(d_state), u32(d_out), (uint32_t)nframes, T);
+    else       hipLaunchKernelGGL(k_ptrack_batch<false>, grid, dim3(64), 0, st, u32(d_eq), d_first, d_nsym, u32(d_state), u32(d_out), (uint32_t)nframes, T);
+    return launch_result("k_ptrack_batch");
+}
+int sora_hip_pilot_track11a(const sora_complex16* d_eq, const uint32_t* d_first, const uint32_t* d_nsym, sora_track11a_state* d_state, sora_complex16* d_out,
+                            size_t nframes, void* stream)
+{
+    STAGE_ENTRY("sora_hip_pilot_track11a", !d_eq || !d_first || !d_nsym || !d_state || !d_out, nframes)
+    return ptrack_stage(true, d_eq, d_first, d_nsym, d_state, d_out, nframes, stream);
+}
+int sora_hip_pilot11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_nsym, sora_track11a_state* d_state, sora_complex16* d_out,
+                      size_t nframes, void* stream)
+{
+    STAGE_ENTRY("sora_hip_pilot11a", !d_in || !d_first || !d_nsym || !d_state || !d_out, nframes)
+    return ptrack_stage(false, d_in, d_first, d_nsym, d_state, d_out, nframes, stream);
+}
+
+int sora_hip_demap11a(const sora_complex16* d_in, uint8_t* d_soft, int n_bpsc, size_t n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_demap11a", !d_in || !d_soft, n)
+    STAGE_NBPSC("sora_hip_demap11a", n_bpsc)
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    if (!aligned16(d_in, d_soft)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_demap11a: buffers must be 16-byte aligned", 0);
+    const dim3 grid((unsigned)((n + 31) / 32));
+    STAGE_BY_NBPSC(n_bpsc, k_demap_batch, grid, (hipStream_t)stream, u32(d_in), d_soft, (uint32_t)n, T)
+    return launch_result("k_demap_batch");
+}
+
+int sora_hip_deinterleave11a(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, size_t n, void* stream)
+{
+    STAGE_ENTRY("sora_hip_deinterleave11a", !d_in || !d_out, n)
+    STAGE_NBPSC("sora_hip_deinterleave11a", n_bpsc)
+    Tables T; if (const int rc = stage_tables(&T)) return rc;
+    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_deinterleave11a: buffers must be 16-byte aligned", 0);
+    const dim3 grid((unsigned)((n + 31) / 32));
+    STAGE_BY_NBPSC(n_bpsc, k_deint_batch, grid, (hipStream_t)stream, d_in, d_out, (uint32_t)n, T)
+    return launch_result("k_deint_batch");
+}

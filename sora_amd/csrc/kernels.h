@@ -113,14 +113,6 @@ __global__ void k_win_redo_finish_pipe(const VitJob* jobs, const uint32_t* hdr, 
 __global__ void k_finish(RxArgs A);
 struct PackedRow;
 __global__ void k_pack(const FrameRow* frames, const uint32_t* nframes, const CapDesc* caps, uint32_t ncaps, uint32_t max_frames, PackedRow* rows, uint32_t* nrows_out);
-__global__ void k_fft64_batch(const uint32_t* in, uint32_t* out, uint32_t n, Tables T);
-template <int NB> __global__ void k_demap_batch(const uint32_t* in, uint8_t* soft, uint32_t n, Tables T);
-template <int NB> __global__ void k_deint_batch(const uint8_t* in, uint8_t* out, uint32_t n, Tables T);
-__global__ void k_lts_batch(const uint32_t* in, uint32_t* ctx, uint32_t n, Tables T);
-__global__ void k_symfront_batch(const uint32_t* in, const uint32_t* ctx, const uint32_t* ctx_index, uint32_t* eq, uint32_t n, Tables T);
-template <bool PHASE> __global__ void k_ptrack_batch(const uint32_t* eq, const uint32_t* first, const uint32_t* nsym, uint32_t* state, uint32_t* out, uint32_t nframes, Tables T);
-template <int KIND> __global__ void k_cmul64_batch(const uint32_t* in, const uint32_t* coef, uint32_t cstride, uint32_t coff, const uint32_t* cindex, uint32_t* out, uint32_t n);
-__global__ void k_fft128_batch(const uint32_t* in, uint32_t* out, uint32_t n, Tables T);
 struct TxArgs {                // sora_hip_tx11a (k_tx.hip)
     const uint8_t*  mpdu;      // MPDUs without FCS, frame f at mpdu + off[f]
     const uint32_t* off;
@@ -134,45 +126,6 @@ struct TxArgs {                // sora_hip_tx11a (k_tx.hip)
 };
 __global__ void k_tx_preamble(int8_t* out8, int8_t* out44, Tables T);   // 640 samples at 40 MHz, 704 at 44 MHz
 template <bool UP44> __global__ void k_tx11a(TxArgs A);                 // UP44: TUpsample40MTo44M in front of the 16 -> 8 bit pack (sora_hip_tx11a44)
-
-// ---- the 802.11a modulation graph's bricks as stages (k_mod.hip)
-__global__ void k_mod_scramble(const uint8_t* in, uint8_t* out, const uint32_t* off, const uint32_t* len, const uint32_t* tail, const uint8_t* seed, uint32_t nframes, uint32_t chunks, Tables T);
-__global__ void k_mod_encode(const uint8_t* in, const uint32_t* in_off, const uint32_t* len, int cr, uint8_t* out, const uint32_t* out_off, uint32_t nframes, uint32_t chunks);
-template <int NB> __global__ void k_mod_interleave(const uint8_t* in, uint8_t* out, uint32_t n, Tables T);
-template <int NB> __global__ void k_mod_map(const uint8_t* in, uint32_t* out, int mod, uint32_t n);
-__global__ void k_mod_add_pilot(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* nsym, const uint32_t* pos0, uint32_t nframes, int mod);
-__global__ void k_mod_ifftx(const uint32_t* in, uint32_t* out, uint32_t n, Tables T);
-__global__ void k_mod_upsample(const uint32_t* in, uint32_t* out, const uint8_t* sees_next, uint32_t nblocks);
-__global__ void k_mod_pack16to8(const uint32_t* in, uint32_t* out, uint64_t nbursts);
-__global__ void k_mod_preamble(uint32_t* out, uint32_t ncopies, Tables T);
-
-// ---- the 802.11b receive graph's bricks as stages (k_11b.hip): stream f = n[f] units from element first[f] of `in`, written from element out_first[f] of `out`; grid = nstreams x chunks
-// workgroups of 256 units (the position-parallel stages), one workgroup (symtiming) or one wave (the searches, the sink) per stream
-__global__ void k_11b_dc_remove(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, const uint32_t* dc, uint32_t nstreams, uint32_t chunks);
-__global__ void k_11b_despread(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, uint32_t nstreams, uint32_t chunks);
-template <int BITS> __global__ void k_11b_demap(const uint32_t* in, uint8_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, const uint32_t* state,
-                                                uint32_t nstreams, uint32_t chunks);
-template <int R> __global__ void k_11b_cck(const uint32_t* in, uint8_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, const uint32_t* state,
-                                           uint32_t nstreams, uint32_t chunks);
-__global__ void k_11b_desc741(const uint8_t* in, uint8_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, const uint32_t* state, uint32_t nstreams, uint32_t chunks);
-__global__ void k_11b_stream_state(const void* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t nstreams, int kind);
-__global__ void k_11b_symtiming(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, int* state, uint32_t* nchips, uint32_t nstreams);
-__global__ void k_11b_energy_detect(const uint32_t* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t* used, uint32_t nstreams);
-__global__ void k_11b_barker_sync(const uint32_t* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t* used, uint32_t nstreams);
-__global__ void k_11b_sfd_sync(const uint32_t* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t* used, uint32_t nstreams, int mode);
-__global__ void k_11b_plcp_parse(const uint8_t* hdr, uint32_t* rec, uint32_t nstreams);
-__global__ void k_11b_frame_sink(const uint8_t* bytes, const uint32_t* first, const uint32_t* len, uint32_t* rec, uint32_t nstreams, const uint32_t* crc_tab);
-
-// ---- the 802.11a receive graph's front-end bricks as stages (k_11a.hip): one wave per stream (the three carrier-sense bricks: grid = nstreams), a workgroup row per frame
-// (data_symbol), a wave / a lane per SIGNAL symbol; first[f] in samples, n[f] in bursts of 4 clamped to max_n
-__global__ void k_11a_dc_remove(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, const uint32_t* dc, uint32_t max_n);
-__global__ void k_11a_dc_estimate(const uint32_t* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t max_n);
-__global__ void k_11a_cca(const uint32_t* in, const uint32_t* first, const uint32_t* n, const uint32_t* out_first, uint32_t* state, uint32_t* out, uint32_t* used, uint32_t* npass,
-                          uint32_t max_n, uint32_t flags, const uint32_t* sts);
-__global__ void k_11a_carrier_sense(const uint32_t* in, const uint32_t* first, const uint32_t* n, uint32_t* state, uint32_t* used, uint32_t max_n, uint32_t flags, const uint32_t* sts);
-__global__ void k_11a_data_symbol(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* nsym, const uint32_t* out_first, uint32_t max_nsym);
-__global__ void k_11a_viterbi_sig(const uint8_t* soft, uint32_t* sig, uint32_t n);
-__global__ void k_11a_plcp_parse(const uint32_t* sig, uint32_t* rec, uint32_t n);
 
 // ---- 802.11n 2x2 transmitter (k_tx11n.hip)
 struct Tx11nArgs {             // sora_hip_tx11n
@@ -224,15 +177,7 @@ __host__ __device__ inline bool tx11n_plan(uint32_t len, uint32_t mcs, Tx11nPlan
 constexpr uint32_t kTx11nPreamble = 1120;                // samples per chain of the table: L-STF + L-LTF + HT-STF + 2 HT-LTF
 __global__ void k_tx11n(Tx11nArgs A);
 
-// ---- the 802.11n modulation graphs' bricks as stages (k_mod11n.hip); symbol counts n, 16-byte words nwords
-template <int NB> __global__ void k_mod11n_parse(const uint8_t* in, uint8_t* out0, uint8_t* out1, uint32_t n);
-template <int NB> __global__ void k_mod11n_interleave(const uint8_t* in, uint8_t* out, int iss, uint32_t n);
-template <int NB> __global__ void k_mod11n_map(const uint8_t* in, uint32_t* out, int mod, uint32_t n);
-__global__ void k_mod11n_sig_map(const uint8_t* in, uint32_t* out, uint32_t n);
-__global__ void k_mod11n_add_pilot(const uint32_t* in, uint32_t* out, const uint32_t* first, const uint32_t* nsym, const uint32_t* pos0, uint32_t nframes, int iss);
-__global__ void k_mod11n_ifft(const uint32_t* in, uint32_t* out, uint32_t n, Tables T);
-__global__ void k_mod11n_csd(const uint4* in, uint4* out, int ncsd, uint64_t nwords);
-__global__ void k_mod11n_add_gi(const uint4* in, uint4* out, uint64_t nwords);
+// k_mod11n.hip: LSrc / HTSrc as a stage, launched beside the transmitter whose table it copies (sora_hip_preamble11n); nwords 16-byte words
 __global__ void k_mod11n_preamble(const uint4* table, uint4* out0, uint4* out1, uint32_t w0, uint32_t nw, uint64_t nwords);
 
 // ---- 40 MHz HT 2x2 transmitter (k_tx_ht40.hip)
@@ -320,17 +265,8 @@ __host__ __device__ inline bool tx11b_plan(uint32_t len, uint32_t rate_kbps, Tx1
 }
 __global__ void k_tx11b(Tx11bArgs A);
 
-// ---- the 802.11b modulation graph's bricks as stages (k_mod11b.hip): a workgroup per stream, in passes of kMod11bT input units (bytes; chips for the shaper)
+// the 802.11b modulation graph's bricks as stages (k_mod11b.hip): a workgroup per stream, in passes of kMod11bT input units (bytes; chips for the shaper)
 constexpr int kMod11bT = 1024;
-__global__ void k_mod11b_ppdu(const uint8_t* mpdu, const uint32_t* off, const uint32_t* len, const uint32_t* rate, const uint8_t* kind, uint8_t* out, const uint32_t* out_first,
-                              const uint32_t* crc, const uint32_t* crcz);
-__global__ void k_mod11b_sc741(const uint8_t* in, uint8_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, uint32_t* reg, uint32_t max_n);
-__global__ void k_mod11b_dbpsk(const uint8_t* in, uint16_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, uint32_t* state, uint32_t max_n);
-__global__ void k_mod11b_dqpsk(const uint8_t* in, uint16_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, uint32_t* state, uint32_t max_n);
-__global__ void k_mod11b_cck5(const uint8_t* in, uint16_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, uint32_t* state, uint32_t max_n);
-__global__ void k_mod11b_cck11(const uint8_t* in, uint16_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, uint32_t* state, uint32_t max_n);
-__global__ void k_mod11b_shape(const uint16_t* in, uint32_t* out, const uint32_t* first, const uint32_t* nn, const uint32_t* out_first, const uint8_t* flush, uint32_t* state,
-                               uint32_t max_n);
 __global__ void k_ingest(const uint8_t* raw, uint32_t* out, uint64_t m0, uint64_t n_out, unsigned flags);
 __global__ void k_ingest_tile(const uint8_t* raw, uint32_t* out, unsigned flags, uint32_t tiles);
 __global__ void k_soft_pack3(const uint8_t* soft8, const uint32_t* off8, const uint32_t* nsoft, const uint16_t* flen, const uint32_t* out_off,

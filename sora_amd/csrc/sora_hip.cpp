@@ -17,6 +17,7 @@
 #include "../../include/sora_hip.h"
 #include "kernels.h"
 #include "host_trellis.h"
+#include "host_stage.h"
 
 using namespace sora;
 
@@ -373,7 +374,7 @@ static void free_dev_tables(DevTables& D) { for (void* p : D.allocs) (void)hipFr
 // per-device tables for the stand-alone stage entry points: created once per device, under a lock (stage calls on
 // different handles / threads are independent, include/sora_hip.h)
 static std::mutex g_stage_mutex;
-static DevTables* stage_tables()
+static DevTables* device_tables()
 {
     static DevTables* tabs[64] = {nullptr};
     int dev = 0;
@@ -391,14 +392,14 @@ int sora_internal_fail(int code, const char* what, int hip_error) { return fail(
 int sora_internal_tables(int device, sora::Tables* out)
 {
     if (hipSetDevice(device) != hipSuccess) return SORA_ERR_HARDWARE_FAILED;
-    DevTables* D = stage_tables();
+    DevTables* D = device_tables();
     if (!D) return SORA_ERR_HARDWARE_FAILED;
     *out = D->T; return SORA_OK;
 }
 const uint32_t* sora_internal_crc_table(int device)
 {
     if (hipSetDevice(device) != hipSuccess) return nullptr;
-    DevTables* D = stage_tables();
+    DevTables* D = device_tables();
     return D ? D->T.crc : nullptr;
 }
 
@@ -573,7 +574,7 @@ int sora_hip_table_digest(const char* name, char hex65[65])
 int sora_hip_table_read(const char* name, void* h_out, size_t cap, size_t* bytes)
 {
     if (!name || !bytes) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_table_read: null argument");
-    DevTables* D = stage_tables();
+    DevTables* D = device_tables();
     if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "sora_hip_table_read: no tables on this device");
     const uint32_t* dsc = nullptr; const short* dat = nullptr;
     if (!strncmp(name, "dsp_", 4) && sora_internal_dsp_tables(&dsc, &dat) != SORA_OK) return fail(SORA_ERR_HARDWARE_FAILED, "sora_hip_table_read: dsp_math tables");
@@ -1523,152 +1524,6 @@ int sora_rx_kernel_times(sora_rx_t* rx, float* ms, size_t cap, size_t* nout)
     return SORA_OK;
 }
 
-// ---- per-stage entry points
-int sora_hip_fft64(const sora_complex16* d_in, sora_complex16* d_out, size_t n, void* stream)
-{
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_in || !d_out) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_fft64: null pointer");
-    if (n == 0) return SORA_OK;
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_fft64: buffers must be 16-byte aligned");
-    hipLaunchKernelGGL(k_fft64_batch, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const uint32_t*>(d_in), reinterpret_cast<uint32_t*>(d_out), (uint32_t)n, D->T);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_fft128(const sora_complex16* d_in, sora_complex16* d_out, size_t n, void* stream)
-{
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_in || !d_out) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_fft128: null pointer");
-    if (n == 0) return SORA_OK;
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_fft128: buffers must be 16-byte aligned");
-    hipLaunchKernelGGL(k_fft128_batch, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const uint32_t*>(d_in), reinterpret_cast<uint32_t*>(d_out), (uint32_t)n, D->T);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_lts11a(const sora_complex16* d_in, sora_lts11a_ctx* d_ctx, size_t n, void* stream)
-{
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_in || !d_ctx) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_lts11a: null pointer");
-    static_assert(sizeof(sora_lts11a_ctx) == 516, "sora_lts11a_ctx layout");
-    if (n == 0) return SORA_OK;
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    hipLaunchKernelGGL(k_lts_batch, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
-            reinterpret_cast<uint32_t*>(d_ctx), (uint32_t)n, D->T);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_symfront11a(const sora_complex16* d_in, const sora_lts11a_ctx* d_ctx, const uint32_t* d_ctx_index, sora_complex16* d_eq, size_t n, void* stream)
-{
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_in || !d_ctx || !d_eq) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_symfront11a: null pointer");
-    if (n == 0) return SORA_OK;
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    if (((uintptr_t)d_in | (uintptr_t)d_eq) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_symfront11a: sample and output buffers must be 16-byte aligned");
-    hipLaunchKernelGGL(k_symfront_batch, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
-                       reinterpret_cast<const uint32_t*>(d_ctx), d_ctx_index, reinterpret_cast<uint32_t*>(d_eq), (uint32_t)n, D->T);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-// The symbol chain's three one-multiply bricks on their own (k_stage.hip: k_cmul64_batch)
-static int cmul64_stage(int kind, const char* who, const sora_complex16* d_in, const void* d_coef, uint32_t cstride_words, uint32_t coff_words,
-        const uint32_t* d_index, sora_complex16* d_out, size_t n, void* stream)
-{
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_in || !d_coef || !d_out) return fail(SORA_ERR_INVALID_PARAM, who);
-    if (n == 0) return SORA_OK;
-    if (n >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, who);
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "symbol buffers must be 16-byte aligned");
-    const dim3 grid((unsigned)((n + 127) / 128)); const hipStream_t st = (hipStream_t)stream;
-    const uint32_t* in = reinterpret_cast<const uint32_t*>(d_in); const uint32_t* cf = reinterpret_cast<const uint32_t*>(d_coef);
-        uint32_t* out = reinterpret_cast<uint32_t*>(d_out);
-    if (kind == 0)      hipLaunchKernelGGL(k_cmul64_batch<0>, grid, dim3(256), 0, st, in, cf, cstride_words, coff_words, d_index, out, (uint32_t)n);
-    else if (kind == 1) hipLaunchKernelGGL(k_cmul64_batch<1>, grid, dim3(256), 0, st, in, cf, cstride_words, coff_words, d_index, out, (uint32_t)n);
-    else                hipLaunchKernelGGL(k_cmul64_batch<2>, grid, dim3(256), 0, st, in, cf, cstride_words, coff_words, d_index, out, (uint32_t)n);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-int sora_hip_freq_comp11a(const sora_complex16* d_in, const sora_lts11a_ctx* d_ctx, const uint32_t* d_ctx_index, sora_complex16* d_out, size_t n, void* stream)
-{
-    static_assert(sizeof(sora_lts11a_ctx) == 516, "sora_lts11a_ctx layout");
-    return cmul64_stage(0, "sora_hip_freq_comp11a: null pointer", d_in, d_ctx, 129u, 1u, d_ctx_index, d_out, n, stream);
-}
-int sora_hip_equalize11a(const sora_complex16* d_in, const sora_lts11a_ctx* d_ctx, const uint32_t* d_ctx_index, sora_complex16* d_out, size_t n, void* stream)
-{
-    return cmul64_stage(1, "sora_hip_equalize11a: null pointer", d_in, d_ctx, 129u, 65u, d_ctx_index, d_out, n, stream);
-}
-int sora_hip_phase_comp11a(const sora_complex16* d_in, const sora_track11a_state* d_state, const uint32_t* d_state_index, sora_complex16* d_out, size_t n, void* stream)
-{
-    static_assert(sizeof(sora_track11a_state) == 268, "sora_track11a_state layout");
-    return cmul64_stage(2, "sora_hip_phase_comp11a: null pointer", d_in, d_state, 67u, 3u, d_state_index, d_out, n, stream);
-}
-
-static int ptrack_stage(bool phase, const char* who, const sora_complex16* d_eq, const uint32_t* d_first, const uint32_t* d_nsym, sora_track11a_state* d_state, sora_complex16* d_out,
-                        size_t nframes, void* stream)
-{
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_eq || !d_first || !d_nsym || !d_state || !d_out) return fail(SORA_ERR_INVALID_PARAM, who);
-    static_assert(sizeof(sora_track11a_state) == 268, "sora_track11a_state layout");
-    if (nframes == 0) return SORA_OK;
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    if (phase)
-        hipLaunchKernelGGL(k_ptrack_batch<true>, dim3((unsigned)nframes), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_eq), d_first, d_nsym,
-                           reinterpret_cast<uint32_t*>(d_state), reinterpret_cast<uint32_t*>(d_out), (uint32_t)nframes, D->T);
-    else
-        hipLaunchKernelGGL(k_ptrack_batch<false>, dim3((unsigned)nframes), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_eq), d_first, d_nsym,
-                           reinterpret_cast<uint32_t*>(d_state), reinterpret_cast<uint32_t*>(d_out), (uint32_t)nframes, D->T);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-int sora_hip_pilot_track11a(const sora_complex16* d_eq, const uint32_t* d_first, const uint32_t* d_nsym, sora_track11a_state* d_state, sora_complex16* d_out,
-        size_t nframes, void* stream)
-{ return ptrack_stage(true, "sora_hip_pilot_track11a: null pointer", d_eq, d_first, d_nsym, d_state, d_out, nframes, stream); }
-int sora_hip_pilot11a(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_nsym, sora_track11a_state* d_state, sora_complex16* d_out,
-        size_t nframes, void* stream)
-{ return ptrack_stage(false, "sora_hip_pilot11a: null pointer", d_in, d_first, d_nsym, d_state, d_out, nframes, stream); }
-
-int sora_hip_demap11a(const sora_complex16* d_in, uint8_t* d_soft, int n_bpsc, size_t n, void* stream)
-{
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_in || !d_soft || !(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_demap11a: bad argument");
-    if (n == 0) return SORA_OK;
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    if (((uintptr_t)d_in | (uintptr_t)d_soft) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_demap11a: buffers must be 16-byte aligned");
-    const dim3 grid((unsigned)((n + 31) / 32)); const uint32_t* in32 = reinterpret_cast<const uint32_t*>(d_in); hipStream_t st = (hipStream_t)stream;
-    switch (n_bpsc) {
-    case 1: hipLaunchKernelGGL(k_demap_batch<1>, grid, dim3(256), 0, st, in32, d_soft, (uint32_t)n, D->T); break;
-    case 2: hipLaunchKernelGGL(k_demap_batch<2>, grid, dim3(256), 0, st, in32, d_soft, (uint32_t)n, D->T); break;
-    case 4: hipLaunchKernelGGL(k_demap_batch<4>, grid, dim3(256), 0, st, in32, d_soft, (uint32_t)n, D->T); break;
-    default: hipLaunchKernelGGL(k_demap_batch<6>, grid, dim3(256), 0, st, in32, d_soft, (uint32_t)n, D->T); break;
-    }
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_deinterleave11a(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, size_t n, void* stream)
-{
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_in || !d_out || !(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_deinterleave11a: bad argument");
-    if (n == 0) return SORA_OK;
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_deinterleave11a: buffers must be 16-byte aligned");
-    const dim3 grid((unsigned)((n + 31) / 32)); hipStream_t st = (hipStream_t)stream;
-    switch (n_bpsc) {
-    case 1: hipLaunchKernelGGL(k_deint_batch<1>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)n, D->T); break;
-    case 2: hipLaunchKernelGGL(k_deint_batch<2>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)n, D->T); break;
-    case 4: hipLaunchKernelGGL(k_deint_batch<4>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)n, D->T); break;
-    default: hipLaunchKernelGGL(k_deint_batch<6>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)n, D->T); break;
-    }
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
 // ---- transmitter (row f2)
 static int tx_params(uint32_t kbps, int* nd)
 {
@@ -1695,7 +1550,7 @@ static int tx11a_launch(bool up44, const char* who, const uint8_t* d_mpdu, const
     if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
     if (!d_mpdu || !d_off || !d_len || !d_rate_kbps || !d_seed || !d_out || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, who);
     if (nframes == 0) return SORA_OK;
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    DevTables* D = device_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     hipStream_t st = (hipStream_t)stream;
     {
         // built once per device, under the lock, and complete before it is published: a call on another stream or thread
@@ -1736,284 +1591,6 @@ int sora_hip_tx11a44(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_
 {
     return tx11a_launch(true, "sora_hip_tx11a44: null pointer", d_mpdu, d_off, d_len, d_rate_kbps, d_seed, nframes, d_out, d_out_off, stream);
 }
-
-// ---- the 802.11a modulation graph's bricks as stages (k_mod.hip)
-#define MOD_STAGE_ENTRY(who, nullcond, count) \
-    if (nullcond) return fail(SORA_ERR_INVALID_PARAM, who ": null pointer"); \
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path"); \
-    if ((count) == 0) return SORA_OK;
-static bool mod_nbpsc_ok(int nb) { return nb == 1 || nb == 2 || nb == 4 || nb == 6; }
-// workgroups of 256 positions per frame, frames x chunks in one grid dimension
-static bool mod_grid(size_t nframes, size_t max_items, uint32_t* chunks, unsigned* grid)
-{
-    const size_t c = (max_items + 255) / 256, g = nframes * c;
-    if (c == 0 || g >= (1ull << 31)) return false;
-    *chunks = (uint32_t)c; *grid = (unsigned)g;
-    return true;
-}
-
-int sora_hip_scramble11a(const uint8_t* d_in, uint8_t* d_out, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_tail, const uint8_t* d_seed,
-                         size_t nframes, size_t max_len, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_scramble11a", !d_in || !d_out || !d_off || !d_len || !d_seed, nframes)
-    if (max_len == 0) return SORA_OK;
-    uint32_t chunks; unsigned grid;
-    if (!mod_grid(nframes, max_len, &chunks, &grid)) return fail(SORA_ERR_CAPACITY, "sora_hip_scramble11a: nframes x max_len is too large for one call");
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    hipLaunchKernelGGL(k_mod_scramble, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_in, d_out, d_off, d_len, d_tail, d_seed, (uint32_t)nframes, chunks, D->T);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_conv_encode11a(const uint8_t* d_in, const uint32_t* d_in_off, const uint32_t* d_len, int code_rate, uint8_t* d_out, const uint32_t* d_out_off,
-                            size_t nframes, size_t max_len, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_conv_encode11a", !d_in || !d_in_off || !d_len || !d_out || !d_out_off, nframes)
-    if (code_rate != SORA_CR_12 && code_rate != SORA_CR_23 && code_rate != SORA_CR_34) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_conv_encode11a: bad code rate");
-    if (max_len >= (1u << 27)) return fail(SORA_ERR_CAPACITY, "sora_hip_conv_encode11a: a frame of 128 MiB or more");
-    const size_t bin = (size_t)code_rate + 1, max_out = max_len / bin * (bin + 1);
-    if (max_out == 0) return SORA_OK;
-    uint32_t chunks; unsigned grid;
-    if (!mod_grid(nframes, max_out, &chunks, &grid)) return fail(SORA_ERR_CAPACITY, "sora_hip_conv_encode11a: nframes x max_len is too large for one call");
-    hipLaunchKernelGGL(k_mod_encode, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_in, d_in_off, d_len, code_rate, d_out, d_out_off, (uint32_t)nframes, chunks);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_interleave11a(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, size_t nsym, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_interleave11a", !d_in || !d_out, nsym)
-    if (!mod_nbpsc_ok(n_bpsc)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_interleave11a: n_bpsc must be 1, 2, 4 or 6");
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_interleave11a: buffers must be 16-byte aligned");
-    if (nsym >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_interleave11a: too many symbols for one call");
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    const dim3 grid((unsigned)((nsym + 31) / 32)); hipStream_t st = (hipStream_t)stream;
-    switch (n_bpsc) {
-    case 1: hipLaunchKernelGGL(k_mod_interleave<1>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)nsym, D->T); break;
-    case 2: hipLaunchKernelGGL(k_mod_interleave<2>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)nsym, D->T); break;
-    case 4: hipLaunchKernelGGL(k_mod_interleave<4>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)nsym, D->T); break;
-    default: hipLaunchKernelGGL(k_mod_interleave<6>, grid, dim3(256), 0, st, d_in, d_out, (uint32_t)nsym, D->T); break;
-    }
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_map11a(const uint8_t* d_in, sora_complex16* d_out, int n_bpsc, int mod, size_t nsym, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_map11a", !d_in || !d_out, nsym)
-    if (!mod_nbpsc_ok(n_bpsc) || mod < 0 || mod > 32767) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11a: n_bpsc must be 1, 2, 4 or 6 and mod 0 .. 32767");
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11a: buffers must be 16-byte aligned");
-    if (nsym >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_map11a: too many symbols for one call");
-    if (mod == 0) mod = n_bpsc == 1 ? 10720 : n_bpsc == 2 ? (short)(10720 / 1.414) : n_bpsc == 4 ? (short)(10720 / 3.162) : (short)(10720 / 6.481);   // mapper11a.hpp:8-11
-    const dim3 grid((unsigned)((nsym + 31) / 32)); hipStream_t st = (hipStream_t)stream; uint32_t* out = reinterpret_cast<uint32_t*>(d_out);
-    switch (n_bpsc) {
-    case 1: hipLaunchKernelGGL(k_mod_map<1>, grid, dim3(256), 0, st, d_in, out, mod, (uint32_t)nsym); break;
-    case 2: hipLaunchKernelGGL(k_mod_map<2>, grid, dim3(256), 0, st, d_in, out, mod, (uint32_t)nsym); break;
-    case 4: hipLaunchKernelGGL(k_mod_map<4>, grid, dim3(256), 0, st, d_in, out, mod, (uint32_t)nsym); break;
-    default: hipLaunchKernelGGL(k_mod_map<6>, grid, dim3(256), 0, st, d_in, out, mod, (uint32_t)nsym); break;
-    }
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_add_pilot11a_from(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_pos0,
-                               size_t nframes, int bpsk_mod, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_add_pilot11a", !d_in || !d_out || !d_first || !d_nsym, nframes)
-    if (bpsk_mod < 0 || bpsk_mod > 32767) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11a: bpsk_mod must be 0 .. 32767");
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11a: buffers must be 16-byte aligned");
-    if (nframes >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_add_pilot11a: too many frames for one call");
-    // the frames' lengths are device memory: a batch of few frames gets several workgroups per frame, each striding over the frame's passes of 16 symbols
-    const unsigned gy = nframes >= 2048 ? 1u : (unsigned)std::min<size_t>(64, 2048 / nframes);
-    hipLaunchKernelGGL(k_mod_add_pilot, dim3((unsigned)nframes, gy), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
-                       reinterpret_cast<uint32_t*>(d_out), d_first, d_nsym, d_pos0, (uint32_t)nframes, bpsk_mod ? bpsk_mod : 10720);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-int sora_hip_add_pilot11a(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, size_t nframes, int bpsk_mod, void* stream)
-{
-    return sora_hip_add_pilot11a_from(d_in, d_out, d_first, d_nsym, nullptr, nframes, bpsk_mod, stream);
-}
-
-int sora_hip_ifftx11a(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_ifftx11a", !d_in || !d_out, nsym)
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_ifftx11a: buffers must be 16-byte aligned");
-    if (nsym >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_ifftx11a: too many symbols for one call");
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    hipLaunchKernelGGL(k_mod_ifftx, dim3((unsigned)((nsym + 31) / 32)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
-                       reinterpret_cast<uint32_t*>(d_out), (uint32_t)nsym, D->T);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_upsample40to44(const sora_complex16* d_in, sora_complex16* d_out, const uint8_t* d_sees_next, size_t nblocks, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_upsample40to44", !d_in || !d_out, nblocks)
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_upsample40to44: buffers must be 16-byte aligned");
-    if (nblocks >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_upsample40to44: too many blocks for one call");
-    hipLaunchKernelGGL(k_mod_upsample, dim3((unsigned)((nblocks + 7) / 8)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
-                       reinterpret_cast<uint32_t*>(d_out), d_sees_next, (uint32_t)nblocks);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_pack16to8(const sora_complex16* d_in, int8_t* d_out, size_t nsamples, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_pack16to8", !d_in || !d_out, nsamples)
-    if (nsamples % 8) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_pack16to8: nsamples must be a multiple of 8 (the brick's burst)");
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_pack16to8: buffers must be 16-byte aligned");
-    const uint64_t nb = nsamples / 8;
-    if ((nb + 255) / 256 >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_pack16to8: too many samples for one call");
-    hipLaunchKernelGGL(k_mod_pack16to8, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
-                       reinterpret_cast<uint32_t*>(d_out), nb);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_preamble11a(sora_complex16* d_out, size_t ncopies, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_preamble11a", !d_out, ncopies)
-    if ((uintptr_t)d_out & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble11a: the buffer must be 16-byte aligned");
-    if (ncopies >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, "sora_hip_preamble11a: too many copies for one call");
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    hipLaunchKernelGGL(k_mod_preamble, dim3((unsigned)std::min<size_t>(ncopies, 2048)), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<uint32_t*>(d_out),
-                       (uint32_t)ncopies, D->T);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-// (MOD_STAGE_ENTRY also opens the 802.11n modulation stages, behind sora_hip_tx11n whose preamble table they share)
-
-// ---- the 802.11b receive graph's bricks as stages (k_11b.hip)
-#define ST11B_ENTRY(who, nullcond, count) \
-    if (nullcond) return fail(SORA_ERR_INVALID_PARAM, who ": null pointer"); \
-    if ((count) == 0) return SORA_OK;                       /* (nothing to launch: true with or without a device) */ \
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path"); \
-    if ((count) >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, who ": too many streams for one call");
-static_assert(sizeof(sora_stream11b_state) == 16 && sizeof(sora_energy11b_state) == 68 && sizeof(sora_symtiming11b_state) == 8 && sizeof(sora_barker11b_state) == 60 &&
-              sizeof(sora_sfd11b_state) == 36 && sizeof(sora_plcp11b_rec) == 16 && sizeof(sora_sink11b_rec) == 8, "the 802.11b stage records are 32-bit words");
-static inline const uint32_t* w32(const void* p) { return static_cast<const uint32_t*>(p); }
-static inline uint32_t* w32(void* p) { return static_cast<uint32_t*>(p); }
-
-int sora_hip_dc_remove11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const sora_complex16* d_dc,
-                          sora_complex16* d_out, size_t nstreams, size_t max_n, void* stream)
-{
-    ST11B_ENTRY("sora_hip_dc_remove11b", !d_in || !d_first || !d_n || !d_out_first || !d_dc || !d_out, nstreams)
-    if (max_n == 0) return SORA_OK;
-    uint32_t chunks; unsigned grid;
-    if (max_n >= (1u << 29) || !mod_grid(nstreams, 4 * max_n, &chunks, &grid)) return fail(SORA_ERR_CAPACITY, "sora_hip_dc_remove11b: nstreams x max_n is too large for one call");
-    hipLaunchKernelGGL(k_11b_dc_remove, dim3(grid), dim3(256), 0, (hipStream_t)stream, w32(d_in), w32(d_out), d_first, d_n, d_out_first, w32(d_dc), (uint32_t)nstreams, chunks);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_energy_detect11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_energy11b_state* d_state, uint32_t* d_used,
-                              size_t nstreams, size_t max_n, void* stream)
-{
-    (void)max_n;                                                                 // (a wave per stream walks its own d_n[f])
-    ST11B_ENTRY("sora_hip_energy_detect11b", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
-    hipLaunchKernelGGL(k_11b_energy_detect, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, w32(d_in), d_first, d_n, w32(d_state), d_used, (uint32_t)nstreams);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_symtiming11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_symtiming11b_state* d_state,
-                          sora_complex16* d_out, uint32_t* d_nchips, size_t nstreams, size_t max_n, void* stream)
-{
-    (void)max_n;
-    ST11B_ENTRY("sora_hip_symtiming11b", !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out || !d_nchips, nstreams)
-    hipLaunchKernelGGL(k_11b_symtiming, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, w32(d_in), w32(d_out), d_first, d_n, d_out_first,
-                       reinterpret_cast<int*>(d_state), d_nchips, (uint32_t)nstreams);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_barker_sync11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_barker11b_state* d_state, uint32_t* d_used,
-                            size_t nstreams, size_t max_n, void* stream)
-{
-    (void)max_n;
-    ST11B_ENTRY("sora_hip_barker_sync11b", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
-    hipLaunchKernelGGL(k_11b_barker_sync, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, w32(d_in), d_first, d_n, w32(d_state), d_used, (uint32_t)nstreams);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_despread11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_complex16* d_out,
-                         size_t nstreams, size_t max_n, void* stream)
-{
-    ST11B_ENTRY("sora_hip_despread11b", !d_in || !d_first || !d_n || !d_out_first || !d_out, nstreams)
-    if (max_n == 0) return SORA_OK;
-    uint32_t chunks; unsigned grid;
-    if (!mod_grid(nstreams, max_n, &chunks, &grid)) return fail(SORA_ERR_CAPACITY, "sora_hip_despread11b: nstreams x max_n is too large for one call");
-    hipLaunchKernelGGL(k_11b_despread, dim3(grid), dim3(256), 0, (hipStream_t)stream, w32(d_in), w32(d_out), d_first, d_n, d_out_first, (uint32_t)nstreams, chunks);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_sfd_sync11b(const sora_complex16* d_in, const uint32_t* d_first, const uint32_t* d_n, sora_sfd11b_state* d_state, uint32_t* d_used,
-                         size_t nstreams, size_t max_n, int mode, void* stream)
-{
-    (void)max_n;
-    ST11B_ENTRY("sora_hip_sfd_sync11b", !d_in || !d_first || !d_n || !d_state || !d_used, nstreams)
-    if (mode != 0 && mode != 1) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_sfd_sync11b: mode must be 0 or 1");
-    hipLaunchKernelGGL(k_11b_sfd_sync, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, w32(d_in), d_first, d_n, w32(d_state), d_used, (uint32_t)nstreams, mode);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-// the five position-parallel stream stages with a sora_stream11b_state: the stage's kernel, then the state behind it (kind: k_11b_stream_state)
-static int stream11b_stage(int kind, const char* who, const void* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state,
-                           uint8_t* d_out, size_t nstreams, size_t max_n, void* stream)
-{
-    if (max_n == 0) return SORA_OK;
-    uint32_t chunks; unsigned grid;
-    if (!mod_grid(nstreams, max_n, &chunks, &grid)) return fail(SORA_ERR_CAPACITY, who);
-    hipStream_t st = (hipStream_t)stream; const uint32_t ns = (uint32_t)nstreams; uint32_t* state = w32(d_state);
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(k_11b_demap<1>, dim3(grid), dim3(256), 0, st, w32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
-    case 1: hipLaunchKernelGGL(k_11b_demap<2>, dim3(grid), dim3(256), 0, st, w32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
-    case 2: hipLaunchKernelGGL(k_11b_cck<5>, dim3(grid), dim3(256), 0, st, w32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
-    case 3: hipLaunchKernelGGL(k_11b_cck<11>, dim3(grid), dim3(256), 0, st, w32(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
-    default: hipLaunchKernelGGL(k_11b_desc741, dim3(grid), dim3(256), 0, st, static_cast<const uint8_t*>(d_in), d_out, d_first, d_n, d_out_first, state, ns, chunks); break;
-    }
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_11b_stream_state, dim3((ns + 255) / 256), dim3(256), 0, st, d_in, d_first, d_n, state, ns, kind);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-#define STREAM11B(name, kind, in_t) \
-    int name(const in_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_stream11b_state* d_state, uint8_t* d_out, size_t nstreams, \
-             size_t max_n, void* stream) \
-    { \
-        ST11B_ENTRY(#name, !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out, nstreams) \
-        return stream11b_stage(kind, #name ": nstreams x max_n is too large for one call", d_in, d_first, d_n, d_out_first, d_state, d_out, nstreams, max_n, stream); \
-    }
-STREAM11B(sora_hip_dbpsk_demap11b, 0, sora_complex16)
-STREAM11B(sora_hip_dqpsk_demap11b, 1, sora_complex16)
-STREAM11B(sora_hip_cck5p5_decode11b, 2, sora_complex16)
-STREAM11B(sora_hip_cck11_decode11b, 3, sora_complex16)
-STREAM11B(sora_hip_desc741_11b, 4, uint8_t)
-#undef STREAM11B
-
-int sora_hip_plcp_parse11b(const uint8_t* d_hdr, sora_plcp11b_rec* d_rec, size_t nstreams, void* stream)
-{
-    ST11B_ENTRY("sora_hip_plcp_parse11b", !d_hdr || !d_rec, nstreams)
-    if ((uintptr_t)d_rec & 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_plcp_parse11b: the records must be 16-byte aligned");
-    hipLaunchKernelGGL(k_11b_plcp_parse, dim3((unsigned)((nstreams + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_hdr, w32(d_rec), (uint32_t)nstreams);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_frame_sink11b(const uint8_t* d_bytes, const uint32_t* d_first, const uint32_t* d_len, sora_sink11b_rec* d_rec, size_t nstreams, void* stream)
-{
-    ST11B_ENTRY("sora_hip_frame_sink11b", !d_bytes || !d_first || !d_len || !d_rec, nstreams)
-    if ((uintptr_t)d_rec & 7) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_frame_sink11b: the records must be 8-byte aligned");
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    hipLaunchKernelGGL(k_11b_frame_sink, dim3((unsigned)nstreams), dim3(64), 0, (hipStream_t)stream, d_bytes, d_first, d_len, w32(d_rec), (uint32_t)nstreams, D->T.crc);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-#undef ST11B_ENTRY
 
 // ---- 802.11n 2x2 transmitter
 // The fixed fields of LSrc / HTSrc (preamble11n.hpp:8-83), per chain: L-STF (320), L-LTF (320), HT-STF, HT-LTF1, HT-LTF2 (160 each).
@@ -2087,7 +1664,7 @@ int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t*
     if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
     if (!d_mpdu || !d_off || !d_len || !d_mcs || !d_out0 || !d_out1 || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_tx11n: null pointer");
     if (nframes == 0) return SORA_OK;
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    DevTables* D = device_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     if (const int rc = tx11n_preamble_ready(D)) return rc;
     Tx11nArgs A{};
     A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.mcs = d_mcs; A.seed = d_seed;
@@ -2098,139 +1675,21 @@ int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t*
     return SORA_OK;
 }
 
-// ---- the 802.11n modulation graphs' bricks as stages (k_mod11n.hip)
-#define MOD11N_ALIGNED(who, bits) \
-    if ((bits) & 15) return fail(SORA_ERR_INVALID_PARAM, who ": buffers must be 16-byte aligned");
-#define MOD11N_COUNT(who, count) \
-    if ((count) >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, who ": too many for one call");
-#define MOD11N_BY_NB(kernel, ...) \
-    switch (n_bpsc) { \
-    case 1: hipLaunchKernelGGL(kernel<1>, grid, dim3(256), 0, st, __VA_ARGS__); break; \
-    case 2: hipLaunchKernelGGL(kernel<2>, grid, dim3(256), 0, st, __VA_ARGS__); break; \
-    case 4: hipLaunchKernelGGL(kernel<4>, grid, dim3(256), 0, st, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL(kernel<6>, grid, dim3(256), 0, st, __VA_ARGS__); break; \
-    }
-
-int sora_hip_stream_parse11n(const uint8_t* d_in, uint8_t* d_out0, uint8_t* d_out1, int n_bpsc, size_t nsym, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_stream_parse11n", !d_in || !d_out0 || !d_out1, nsym)
-    if (!mod_nbpsc_ok(n_bpsc)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_stream_parse11n: n_bpsc must be 1, 2, 4 or 6");
-    MOD11N_ALIGNED("sora_hip_stream_parse11n", (uintptr_t)d_in | (uintptr_t)d_out0 | (uintptr_t)d_out1)
-    MOD11N_COUNT("sora_hip_stream_parse11n", nsym)
-    const dim3 grid((unsigned)((nsym + 31) / 32)); hipStream_t st = (hipStream_t)stream;
-    MOD11N_BY_NB(k_mod11n_parse, d_in, d_out0, d_out1, (uint32_t)nsym)
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_interleave11n(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, int spatial_stream, size_t nsym, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_interleave11n", !d_in || !d_out, nsym)
-    if (!mod_nbpsc_ok(n_bpsc) || spatial_stream < 0 || spatial_stream > 1)
-        return fail(SORA_ERR_INVALID_PARAM, "sora_hip_interleave11n: n_bpsc must be 1, 2, 4 or 6 and spatial_stream 0 or 1");
-    MOD11N_ALIGNED("sora_hip_interleave11n", (uintptr_t)d_in | (uintptr_t)d_out)
-    MOD11N_COUNT("sora_hip_interleave11n", nsym)
-    const dim3 grid((unsigned)((nsym + 31) / 32)); hipStream_t st = (hipStream_t)stream;
-    MOD11N_BY_NB(k_mod11n_interleave, d_in, d_out, spatial_stream, (uint32_t)nsym)
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_map11n(const uint8_t* d_in, sora_complex16* d_out, int n_bpsc, int mod, size_t nsym, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_map11n", !d_in || !d_out, nsym)
-    if (!mod_nbpsc_ok(n_bpsc) || mod < 0 || mod > 32767) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11n: n_bpsc must be 1, 2, 4 or 6 and mod 0 .. 32767");
-    MOD11N_ALIGNED("sora_hip_map11n", (uintptr_t)d_in | (uintptr_t)d_out)
-    MOD11N_COUNT("sora_hip_map11n", nsym)
-    if (mod == 0) mod = n_bpsc == 1 ? 30339 : n_bpsc == 2 ? 21453 : n_bpsc == 4 ? 9594 : 4681;   // fb11nmod_config.hpp:121-128
-    const dim3 grid((unsigned)((nsym + 31) / 32)); hipStream_t st = (hipStream_t)stream; uint32_t* out = reinterpret_cast<uint32_t*>(d_out);
-    MOD11N_BY_NB(k_mod11n_map, d_in, out, mod, (uint32_t)nsym)
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_sig_map11n(const uint8_t* d_in, sora_complex16* d_out, size_t nframes, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_sig_map11n", !d_in || !d_out, nframes)
-    MOD11N_ALIGNED("sora_hip_sig_map11n", (uintptr_t)d_in | (uintptr_t)d_out)
-    MOD11N_COUNT("sora_hip_sig_map11n", nframes)
-    hipLaunchKernelGGL(k_mod11n_sig_map, dim3((unsigned)((nframes + 31) / 32)), dim3(256), 0, (hipStream_t)stream, d_in, reinterpret_cast<uint32_t*>(d_out), (uint32_t)nframes);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_add_pilot11n(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, const uint32_t* d_pos0,
-                          size_t nframes, int spatial_stream, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_add_pilot11n", !d_in || !d_out || !d_first || !d_nsym, nframes)
-    if (spatial_stream < 0 || spatial_stream > 1) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11n: spatial_stream must be 0 or 1");
-    MOD11N_ALIGNED("sora_hip_add_pilot11n", (uintptr_t)d_in | (uintptr_t)d_out)
-    MOD11N_COUNT("sora_hip_add_pilot11n", nframes)
-    // (sora_hip_add_pilot11a's grid: a batch of few frames gets several workgroups per frame, each striding over the frame's passes of 16 symbols)
-    const unsigned gy = nframes >= 2048 ? 1u : (unsigned)std::min<size_t>(64, 2048 / nframes);
-    hipLaunchKernelGGL(k_mod11n_add_pilot, dim3((unsigned)nframes, gy), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
-                       reinterpret_cast<uint32_t*>(d_out), d_first, d_nsym, d_pos0, (uint32_t)nframes, spatial_stream);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_ifft_only11n(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_ifft_only11n", !d_in || !d_out, nsym)
-    MOD11N_ALIGNED("sora_hip_ifft_only11n", (uintptr_t)d_in | (uintptr_t)d_out)
-    MOD11N_COUNT("sora_hip_ifft_only11n", nsym)
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    hipLaunchKernelGGL(k_mod11n_ifft, dim3((unsigned)((nsym + 31) / 32)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_in),
-                       reinterpret_cast<uint32_t*>(d_out), (uint32_t)nsym, D->T);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_csd11n(const sora_complex16* d_in, sora_complex16* d_out, int ncsd, size_t nsym, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_csd11n", !d_in || !d_out, nsym)
-    if (ncsd < 1 || ncsd > 31) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_csd11n: ncsd must be 1 .. 31");
-    if (d_in == d_out) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_csd11n: out of place only");
-    MOD11N_ALIGNED("sora_hip_csd11n", (uintptr_t)d_in | (uintptr_t)d_out)
-    MOD11N_COUNT("sora_hip_csd11n", nsym)
-    const uint64_t nwords = (uint64_t)nsym * 32;
-    hipLaunchKernelGGL(k_mod11n_csd, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(d_in),
-                       reinterpret_cast<uint4*>(d_out), ncsd, nwords);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_add_gi11n(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream)
-{
-    MOD_STAGE_ENTRY("sora_hip_add_gi11n", !d_in || !d_out, nsym)
-    MOD11N_ALIGNED("sora_hip_add_gi11n", (uintptr_t)d_in | (uintptr_t)d_out)
-    MOD11N_COUNT("sora_hip_add_gi11n", nsym)
-    const uint64_t nwords = (uint64_t)nsym * 40;
-    hipLaunchKernelGGL(k_mod11n_add_gi, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(d_in),
-                       reinterpret_cast<uint4*>(d_out), nwords);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
+// LSrc / HTSrc as a stage (the 802.11n modulation graph's other bricks: k_mod11n.hip): it copies the transmitter's table, so it stands here
 int sora_hip_preamble11n(sora_complex16* d_out0, sora_complex16* d_out1, int field, size_t ncopies, void* stream)
 {
-    MOD_STAGE_ENTRY("sora_hip_preamble11n", !d_out0 || !d_out1, ncopies)
+    STAGE_ENTRY("sora_hip_preamble11n", !d_out0 || !d_out1, ncopies)
     if (field != 0 && field != 1) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble11n: field must be 0 (LSrc) or 1 (HTSrc)");
-    MOD11N_ALIGNED("sora_hip_preamble11n", (uintptr_t)d_out0 | (uintptr_t)d_out1)
+    if (!aligned16(d_out0, d_out1)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble11n: buffers must be 16-byte aligned");
     if (ncopies >= (1ull << 24)) return fail(SORA_ERR_CAPACITY, "sora_hip_preamble11n: too many copies for one call");
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    DevTables* D = device_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     if (const int rc = tx11n_preamble_ready(D)) return rc;
     const uint32_t w0 = field ? 160u : 0u, nw = field ? 120u : 160u;             // 16-byte words: samples 0..639 / 640..1119 of a chain's 1120
     const uint64_t nwords = (uint64_t)ncopies * nw;
     hipLaunchKernelGGL(k_mod11n_preamble, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(D->tx11n_preamble),
                        reinterpret_cast<uint4*>(d_out0), reinterpret_cast<uint4*>(d_out1), w0, nw, nwords);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
+    return launch_result("k_mod11n_preamble");
 }
-#undef MOD11N_BY_NB
-#undef MOD11N_COUNT
-#undef MOD11N_ALIGNED
-#undef MOD_STAGE_ENTRY
 
 // ---- 40 MHz HT 2x2 transmitter
 size_t sora_hip_tx_ht40_samples(uint32_t mpdu_len_nofcs, uint32_t mcs)
@@ -2255,7 +1714,7 @@ static int tx_ht40_launch(bool joint, const uint8_t* d_mpdu, const uint32_t* d_o
     if (!d_mpdu || !d_off || !d_len || !d_mcs || !d_out0 || !d_out1 || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, joint ? "sora_hip_tx_ht40_joint: null pointer" :
             "sora_hip_tx_ht40: null pointer");
     if (nframes == 0) return SORA_OK;
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    DevTables* D = device_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     hipStream_t st = (hipStream_t)stream;
     {
         // the fixed fields through the same fixed-point IFFT as every other symbol: built once per device, under the lock, and complete
@@ -2306,7 +1765,7 @@ static int tx11b_launch(const char* who, const uint8_t* d_mpdu, const uint32_t* 
     if (!d_mpdu || !d_off || !d_len || !d_rate_kbps || !d_out || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, (std::string(who) + ": null pointer").c_str());
     if (nframes == 0) return SORA_OK;
     if (nframes > 0x7FFFFFFFu) return fail(SORA_ERR_INVALID_PARAM, (std::string(who) + ": too many frames for one call").c_str());
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    DevTables* D = device_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     Tx11bArgs A{};
     A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.rate = d_rate_kbps; A.phase_in = d_phase_in; A.phase_out = d_phase_out;
     A.out = d_out; A.out_off = d_out_off; A.T = D->T; A.preamble = d_preamble;
@@ -2326,70 +1785,6 @@ int sora_hip_tx11b_pre(const uint8_t* d_mpdu, const uint32_t* d_off, const uint3
 {
     return tx11b_launch("sora_hip_tx11b_pre", d_mpdu, d_off, d_len, d_rate_kbps, d_preamble, d_phase_in, d_phase_out, nframes, d_out, d_out_off, stream);
 }
-
-// ---- the 802.11b modulation graph's bricks as stages (k_mod11b.hip): a workgroup per stream
-#define MOD11B_ENTRY(who, nullcond, count) \
-    if (nullcond) return fail(SORA_ERR_INVALID_PARAM, who ": null pointer"); \
-    if ((count) == 0) return SORA_OK;                       /* (nothing to launch: true with or without a device) */ \
-    if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path"); \
-    if ((count) >= (1ull << 31)) return fail(SORA_ERR_CAPACITY, who ": too many streams for one call");
-static_assert(sizeof(sora_mod11b_state) == 16 && sizeof(sora_shaper11b_state) == 64, "the 802.11b modulation stage records are 32-bit words");
-constexpr size_t kMod11bMaxN = (size_t)1 << 24;             // 88 chips a byte: a stream's output offsets stay 32-bit
-
-int sora_hip_ppdu11b(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_rate_kbps, const uint8_t* d_preamble, uint8_t* d_out,
-                     const uint32_t* d_out_first, size_t nframes, void* stream)
-{
-    MOD11B_ENTRY("sora_hip_ppdu11b", !d_mpdu || !d_off || !d_len || !d_rate_kbps || !d_preamble || !d_out || !d_out_first, nframes)
-    DevTables* D = stage_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
-    hipLaunchKernelGGL(k_mod11b_ppdu, dim3((unsigned)nframes), dim3(256), 0, (hipStream_t)stream, d_mpdu, d_off, d_len, d_rate_kbps, d_preamble, d_out, d_out_first,
-                       D->T.crc, D->T.crcz);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-int sora_hip_sc741_11b(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, uint32_t* d_reg, uint8_t* d_out,
-                       size_t nstreams, size_t max_n, void* stream)
-{
-    MOD11B_ENTRY("sora_hip_sc741_11b", !d_in || !d_first || !d_n || !d_out_first || !d_reg || !d_out, nstreams)
-    if (max_n == 0) return SORA_OK;
-    if (max_n > kMod11bMaxN) return fail(SORA_ERR_CAPACITY, "sora_hip_sc741_11b: max_n is too large for one call");
-    hipLaunchKernelGGL(k_mod11b_sc741, dim3((unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, d_in, d_out, d_first, d_n, d_out_first, d_reg, (uint32_t)max_n);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-
-#define MOD11B_SPREAD(name, kernel) \
-    int name(const uint8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, sora_mod11b_state* d_state, int8_t* d_out, size_t nstreams, \
-             size_t max_n, void* stream) \
-    { \
-        MOD11B_ENTRY(#name, !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out, nstreams) \
-        if (max_n == 0) return SORA_OK; \
-        if (max_n > kMod11bMaxN) return fail(SORA_ERR_CAPACITY, #name ": max_n is too large for one call"); \
-        if ((uintptr_t)d_out & 1) return fail(SORA_ERR_INVALID_PARAM, #name ": d_out must be aligned to a COMPLEX8"); \
-        hipLaunchKernelGGL(kernel, dim3((unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, d_in, reinterpret_cast<uint16_t*>(d_out), d_first, d_n, d_out_first, \
-                           reinterpret_cast<uint32_t*>(d_state), (uint32_t)max_n); \
-        HIPCHK(hipGetLastError()); \
-        return SORA_OK; \
-    }
-MOD11B_SPREAD(sora_hip_dbpsk_spread11b, k_mod11b_dbpsk)
-MOD11B_SPREAD(sora_hip_dqpsk_spread11b, k_mod11b_dqpsk)
-MOD11B_SPREAD(sora_hip_cck5_encode11b, k_mod11b_cck5)
-MOD11B_SPREAD(sora_hip_cck11_encode11b, k_mod11b_cck11)
-#undef MOD11B_SPREAD
-
-int sora_hip_pulse_shape11b(const int8_t* d_in, const uint32_t* d_first, const uint32_t* d_n, const uint32_t* d_out_first, const uint8_t* d_flush,
-                            sora_shaper11b_state* d_state, sora_complex16* d_out, size_t nstreams, size_t max_n, void* stream)
-{
-    MOD11B_ENTRY("sora_hip_pulse_shape11b", !d_in || !d_first || !d_n || !d_out_first || !d_state || !d_out, nstreams)
-    if (max_n == 0 && !d_flush) return SORA_OK;
-    if (max_n > kMod11bMaxN) return fail(SORA_ERR_CAPACITY, "sora_hip_pulse_shape11b: max_n is too large for one call");
-    if (((uintptr_t)d_in & 1) || ((uintptr_t)d_out & 3)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_pulse_shape11b: d_in and d_out must be aligned to their elements");
-    hipLaunchKernelGGL(k_mod11b_shape, dim3((unsigned)nstreams), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint16_t*>(d_in), reinterpret_cast<uint32_t*>(d_out),
-                       d_first, d_n, d_out_first, d_flush, reinterpret_cast<uint32_t*>(d_state), (uint32_t)max_n);
-    HIPCHK(hipGetLastError());
-    return SORA_OK;
-}
-#undef MOD11B_ENTRY
 
 // ---- capture ingest
 size_t sora_hip_ingest_count(size_t raw_bytes, unsigned flags)
