@@ -112,6 +112,7 @@ typedef struct {                    /* one row per frame the reference's RxThrea
 
 #define SORA_ROW_TRUNCATED 1u
 #define SORA_ROW_SHORT_PREAMBLE 2u       /* 802.11b rows: the frame came behind the short preamble (sora_rx11b_set_preamble) */
+#define SORA_ROW_SHORT_GI 4u             /* 40 MHz HT rows: the frame had the short guard interval (SORA_HT40_SHORT_GI, sora_ht40_set_guard) */
 
 /* create/destroy the graph: CreateDemodGraph11a_40M + BB11aDemodCtx.Init  /  IReferenceCounting::Release */
 int  sora_rx_create(const sora_rx_cfg* cfg, sora_rx_t** out);
@@ -584,6 +585,23 @@ int sora_hip_tx_ht40(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_
 size_t sora_hip_tx_ht40_joint_samples(uint32_t mpdu_len_nofcs, uint32_t mcs);
 int sora_hip_tx_ht40_joint(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
                            size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
+/* The SHORT GUARD INTERVAL of the same frames (opt-in; DESIGN.md section 7 "g4"; the library's own definition of IEEE 802.11n-2009's HT-mixed short GI at 40 MHz).  A
+ * short-GI frame equals the long-GI frame of the same PSDUs, MCS and seeds up to and including HT-LTF 2 -- the legacy fields, HT-SIG, HT-STF and both HT-LTFs keep the
+ * 32-sample cyclic prefix and 160-sample symbols -- except that
+ *   - HT-SIG bit 31 (Short GI) is 1, and the CRC-8 over bits 0..33 follows;
+ *   - L-SIG LENGTH follows tx_frame's rule with 4 x N_SYM replaced by 4 x ceil(9 N_SYM / 10): the data field's 3.6 us symbols rounded up to whole 4 us;
+ * and every DATA symbol is 144 samples: the last 16 of the 128 transformed samples, then the 128 (no window, no cyclic shift, as before).  A frame is 1600 + 144 N_SYM
+ * samples per chain; N_SYM, scrambling, coding, puncturing, stream parsing, interleaving, mapping and pilots are unchanged.
+ * sora_hip_tx_ht40_gi has sora_hip_tx_ht40's arguments in its order plus d_gi, a guard-interval kind per frame (the shape of sora_hip_tx11b_pre's d_preamble): 0 = long
+ * (sora_hip_tx_ht40's frame, sample for sample), 1 = short; d_gi NULL: every frame long.  Any other kind is treated like an MCS that is not accepted: _gi_samples
+ * answers 0 and nothing is written for that frame.  sora_hip_tx_ht40_joint_gi is the same for the joint coding.  Sample-exact against tests/tx_ht40_gi_model.py.  The
+ * receiver takes such frames as descriptors that carry SORA_HT40_SHORT_GI, or from raw captures with sora_ht40_set_guard(rx, SORA_HT40_GUARD_SIGNALLED). */
+size_t sora_hip_tx_ht40_gi_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, uint32_t gi);
+int sora_hip_tx_ht40_gi(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed, const uint8_t* d_gi,
+                        size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
+size_t sora_hip_tx_ht40_joint_gi_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, uint32_t gi);
+int sora_hip_tx_ht40_joint_gi(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed, const uint8_t* d_gi,
+                              size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
 
 /* 802.11b transmitter: the reference's modulation graph CreateModGraph (kernel/bb/demod11/fb11bmod_config.hpp:28-50) as
  * Test11B_FB_Mod runs it (fb11b_mod.cpp:40-70): long preamble (SYNC, SFD), PLCP header, MPDU + FCS at 1, 2, 5.5 or 11 Mbps, Barker
@@ -840,6 +858,9 @@ int sora_hip_plcp_parse11a(const uint32_t* d_sig, sora_plcp11a_rec* d_rec, size_
  *     freq_comp11n -> data_symbol_ht40 -> fft128 -> mimo_est_ht40                                                                           (HT-LTF 1 / 2)
  *     freq_comp11n -> data_symbol_ht40 -> fft128 -> mimo_comp_ht40 -> pilot_track_ht40        (symbol by symbol: theta of symbol d rotates symbol d + 1)
  *                  -> demap_ht40 -> deinterleave_ht40 (-> stream_join_ht40 in the joint coding) -> viterbi11n_ws -> desc11a -> frame_sink11a
+ * A SHORT-GI frame (SORA_HT40_SHORT_GI on the descriptor's code rate; sora_ht40_set_guard below) is composed from the same stages, no new one: per data symbol d,
+ * freq_comp11n over 18 bursts (144 samples) at offset + 320 + 144 d, then data_symbol_ht40 with first = offset + 320 + 144 d - 16, one symbol at a time -- the stage's samples
+ * 32..159 are then exactly the symbol's 128 useful samples (sora_amd.rx_ht40_by_stages does this; tests/test_gpu_ht40_gi_stages.py holds it to the handle).
  * sora_hip_freq_comp11n with d_state[f] = { (n0 + k) cfo | 8 cfo | theta } is the 40 MHz frequency compensation of the burst that starts n0 samples into the frame.  The
  * conventions are those stated above sora_hip_cca11n: device pointers, stream order, no allocation, no host wait; a null pointer gives SORA_ERR_INVALID_PARAM before any device
  * work (sora_hip_last_error() names the function), a count of 0 is SORA_OK and launches nothing, no device SORA_ERR_NO_DEVICE.  The layouts are the handle's: weights and
@@ -1108,6 +1129,32 @@ int   sora_ht40_stream_consumed(sora_ht40_t* rx, int ticket, uint32_t* h_consume
 #define SORA_HT40_CODING_JOINT      1
 int      sora_ht40_set_coding(sora_ht40_t* rx, int coding);
 uint32_t sora_ht40_symbols_joint(uint32_t length, uint32_t n_bpsc, uint32_t code_rate);   /* data symbols of a joint-coded frame (0: bad arguments) */
+/* The SHORT GUARD INTERVAL (opt-in; sora_hip_tx_ht40_gi states the format; DESIGN.md section 7 "g4").  A short-GI frame has the same N_SYM and the same soft bytes as
+ * the long-GI frame of its PSDUs; only the data symbols lie elsewhere: symbol d starts 320 + 144 d samples behind `offset` and its 128 useful samples 16 further on (long:
+ * 320 + 160 d, 32).  The compensation phase stays n cfo - theta with n the sample's index in the frame.
+ *   - descriptor calls: sora_ht40_frame.code_rate may carry SORA_HT40_SHORT_GI OR-ed onto SORA_CR_*; the frame is then 2 HT-LTF symbols of 160 samples plus nsym data
+ *     symbols of 144 samples from `offset`.  Any other bit above the SORA_CR_* value stays SORA_ERR_INVALID_PARAM.  This works whatever the handle's guard mode is, in
+ *     both codings, and long and short frames may share a call;
+ *   - raw captures: sora_ht40_set_guard(rx, SORA_HT40_GUARD_SIGNALLED) makes the front end read HT-SIG bit 31 (Short GI; its CRC-8 covers it).  A frame with a sound
+ *     header and the bit set occupies 20 MHz samples [a, a + 240 + 72 nsym) from its first HT-STF sample a, and is an event only if all of that lies inside the
+ *     capture's real samples; end_sample and the origin of the next carrier sense follow the source-call rule above from that end, and the data field takes the short
+ *     geometry from `offset` = capture + 2 a20 + 160 + 16: the front end's a20 lies 21..28 samples in front of the frame's own timing -- inside a 32-sample guard
+ *     interval, in front of a 16-sample one -- so a short-GI frame is taken 16 samples later, HT-LTFs and data alike, which puts every window 5..12 samples inside
+ *     its prefix (fewer than 16 where the capture ends inside them: as far as its samples reach; such a capture cuts the frame's own tail).  A frame with the bit
+ *     clear is handled exactly as in SORA_HT40_GUARD_LONG (the default), where the bit is not looked at: a short-GI frame is then cut at the long
+ *     positions and reported CRC32_FAIL, as before.  Works in both codings and in stream mode (a short-GI frame that runs past the piece is found by the next call,
+ *     as a long one is -- it is taken once those 16 samples behind its extent lie inside the piece too, so that every cut gives the one-call result;
+ *     sora_ht40_stream_consumed means what it meant);
+ *   - results: the rows of a short-GI frame carry SORA_ROW_SHORT_GI in flags (beside SORA_ROW_TRUNCATED where that applies) -- both rows of a per-stream frame, the one
+ *     row of a joint frame, in both call forms and through sora_ht40_deliver_async; rate_kbps is unchanged.  sora_ht40_found.mcs carries SORA_HT40_SHORT_GI OR-ed onto the
+ *     MCS of a recorded short-GI frame.  sora_ht40_soft_of, d_weights and max_soft_values are unchanged.
+ * Calls that cannot hold a short frame -- descriptor calls without the flag, raw-capture calls of a handle in SORA_HT40_GUARD_LONG -- launch the kernels they always
+ * launched.  sora_ht40_set_guard returns the previous mode; a negative argument only queries.  Like sora_ht40_set_coding it first waits for every call in flight and
+ * starts every stream afresh; calls issued before the switch keep their mode when their results are read.  The 20 MHz 802.11n pair has no short GI. */
+#define SORA_HT40_SHORT_GI        0x100u  /* on sora_ht40_frame.code_rate (in) and sora_ht40_found.mcs (out) */
+#define SORA_HT40_GUARD_LONG      0
+#define SORA_HT40_GUARD_SIGNALLED 1
+int      sora_ht40_set_guard(sora_ht40_t* rx, int mode);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU sharding for a C host.  Captures are independent -- the reference resets its context per

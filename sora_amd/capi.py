@@ -84,6 +84,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_hip_ppdu11b", "sora_hip_sc741_11b", "sora_hip_dbpsk_spread11b", "sora_hip_dqpsk_spread11b", "sora_hip_cck5_encode11b", "sora_hip_cck11_encode11b",
            "sora_hip_pulse_shape11b",
            "sora_hip_tx_ht40_joint", "sora_hip_tx_ht40_joint_samples",
+           "sora_hip_tx_ht40_gi", "sora_hip_tx_ht40_gi_samples", "sora_hip_tx_ht40_joint_gi", "sora_hip_tx_ht40_joint_gi_samples",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n",
            "sora_hip_cca11n", "sora_hip_data_symbol11n", "sora_hip_stream_join11n", "sora_hip_desc11a", "sora_hip_frame_sink11a",
@@ -101,7 +102,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_ht40_symbols", "sora_ht40_create", "sora_ht40_destroy", "sora_ht40_stream", "sora_ht40_synchronize", "sora_ht40_set_trellis", "sora_ht40_process_dev",
                       "sora_ht40_process_captures_dev", "sora_ht40_results", "sora_ht40_ticket", "sora_ht40_calls_in_flight", "sora_ht40_wait", "sora_ht40_wait_any",
                       "sora_ht40_stream_of", "sora_ht40_results_of", "sora_ht40_soft_of", "sora_ht40_found_of", "sora_ht40_set_stream_mode", "sora_ht40_stream_consumed",
-                      "sora_ht40_set_coding", "sora_ht40_symbols_joint",
+                      "sora_ht40_set_coding", "sora_ht40_symbols_joint", "sora_ht40_set_guard",
            "sora_shard_unique_id", "sora_shard_create", "sora_shard_destroy", "sora_shard_world", "sora_shard_partition", "sora_shard_gather_rows",
            "sora_shard_reduce_counters", "sora_shard_gather_results", "sora_shard_gather_results_mpdu"]
 
@@ -210,6 +211,7 @@ def load(build_if_missing=True):
     L.sora_ht40_symbols.argtypes = [ctypes.c_uint32] * 4; L.sora_ht40_symbols.restype = ctypes.c_uint32
     L.sora_ht40_symbols_joint.argtypes = [ctypes.c_uint32] * 3; L.sora_ht40_symbols_joint.restype = ctypes.c_uint32
     L.sora_ht40_set_coding.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.sora_ht40_set_guard.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.sora_ht40_create.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
     L.sora_ht40_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Ht40Frame), ctypes.c_size_t, ctypes.c_void_p]
     L.sora_ht40_results.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t]
@@ -285,6 +287,10 @@ def load(build_if_missing=True):
     L.sora_hip_tx_ht40.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
     L.sora_hip_tx_ht40_joint_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx_ht40_joint_samples.restype = ctypes.c_size_t
     L.sora_hip_tx_ht40_joint.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
+    for fn in (L.sora_hip_tx_ht40_gi, L.sora_hip_tx_ht40_joint_gi):
+        fn.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
+    for fn in (L.sora_hip_tx_ht40_gi_samples, L.sora_hip_tx_ht40_joint_gi_samples):
+        fn.argtypes = [ctypes.c_uint32] * 3; fn.restype = ctypes.c_size_t
     L.sora_hip_tx11b_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11b_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11b.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
     L.sora_hip_tx11b_pre_samples.argtypes = [ctypes.c_uint32] * 3; L.sora_hip_tx11b_pre_samples.restype = ctypes.c_size_t
@@ -657,6 +663,9 @@ ROW_DTYPE = np.dtype([("capture_id", "<u4"), ("start_sample", "<u4"), ("end_samp
                       ("length", "<u2"), ("nsym", "<u2"), ("crc32", "<u4"), ("cfo_est", "<i2"), ("flags", "<u2"), ("mpdu_offset", "<u4")])   # = sora_frame_result
 ROW_TRUNCATED = 1
 ROW_SHORT_PREAMBLE = 2        # an 802.11b row whose frame came behind the short preamble (Rx11b.set_preamble(1))
+ROW_SHORT_GI = 4              # a 40 MHz HT row whose frame had the short guard interval (SORA_ROW_SHORT_GI)
+HT40_SHORT_GI = 0x100         # SORA_HT40_SHORT_GI: on a descriptor's code rate (in) and on a found record's mcs (out)
+HT40_GUARD_LONG, HT40_GUARD_SIGNALLED = 0, 1
 
 
 class HostResults:
@@ -838,7 +847,7 @@ class RxHt40(_Handle):
 
     @staticmethod
     def frames(descs):
-        """[(offset, n_bpsc, code_rate, length0, length1, cfo, noise_var[, id])] -> packed descriptor array (reusable)"""
+        """[(offset, n_bpsc, code_rate, length0, length1, cfo, noise_var[, id])] -> packed descriptor array (reusable); code_rate may carry HT40_SHORT_GI"""
         if isinstance(descs, ctypes.Array):
             return descs
         arr = (Ht40Frame * max(1, len(descs)))()
@@ -857,6 +866,13 @@ class RxHt40(_Handle):
         """sora_ht40_set_coding: CODING_PER_STREAM (0, the default) or CODING_JOINT (1: one PSDU per frame, stream-parsed; descriptors carry l1 = 0, one row per
         frame, soft(frame, 0) is the merged stream).  -> the previous value; a negative argument only queries"""
         r = int(self._L.sora_ht40_set_coding(self._h, int(coding)))
+        if r < 0: _check(r)
+        return r
+
+    def set_guard(self, mode=-1):
+        """sora_ht40_set_guard: HT40_GUARD_LONG (0, the default: HT-SIG's Short GI bit is not looked at) or HT40_GUARD_SIGNALLED (1: the front end of
+        process_captures_dev reads it; the rows of a short-GI frame carry ROW_SHORT_GI).  -> the previous mode; a negative argument only queries"""
+        r = int(self._L.sora_ht40_set_guard(self._h, int(mode)))
         if r < 0: _check(r)
         return r
 
@@ -899,7 +915,7 @@ class RxHt40(_Handle):
             _check(self._L.sora_ht40_results_of(self._h, int(ticket), res, n2, ctypes.byref(n), mp.ctypes.data if with_mpdu else None, mp.size))
         out = self._table(res, n.value, mp if with_mpdu else None, every_row=True)
         for d in out:
-            d["stream"] = d["start_sample"]
+            d["stream"] = d["start_sample"]; d["short_gi"] = bool(d["flags"] & ROW_SHORT_GI)
         return out
 
     def soft(self, frame, stream, ticket=None):
@@ -916,7 +932,8 @@ class RxHt40(_Handle):
 
     def found(self, capture, ticket=None):
         """sora_ht40_found_of: the front end's records of capture `capture` (index into the call's captures) of a process_captures_dev call (ticket None: the most
-        recent call), in time order: [{a20, mcs, ht_len, nsym, cfo, noise_var (numpy float32), end_sample, error_code}] -- a diagnostic for tests"""
+        recent call), in time order: [{a20, mcs, ht_len, nsym, cfo, noise_var (numpy float32), end_sample, error_code}] -- a diagnostic for tests; mcs carries
+        HT40_SHORT_GI for a recorded short-GI frame (set_guard(1))"""
         t = self.ticket() if ticket is None else int(ticket)
         n = ctypes.c_size_t(0)
         rc = self._L.sora_ht40_found_of(self._h, t, int(capture), None, 0, ctypes.byref(n))
@@ -2681,20 +2698,39 @@ def tx_ht40_samples(mpdu_len_nofcs, mcs):
     return int(load().sora_hip_tx_ht40_samples(int(mpdu_len_nofcs), int(mcs)))
 
 
-def tx_ht40(mpdus0, mpdus1, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None):
+def tx_ht40_gi_samples(mpdu_len_nofcs, mcs, gi):
+    """Samples per TX chain of one 40 MHz HT 2x2 frame of guard-interval kind gi (sora_hip_tx_ht40_gi_samples): 0 = long, 1600 + 160 N_SYM; 1 = short, 1600 + 144 N_SYM;
+    0 for a kind, MCS or length that is not accepted."""
+    return int(load().sora_hip_tx_ht40_gi_samples(int(mpdu_len_nofcs), int(mcs), int(gi) & 0xFFFFFFFF))
+
+
+def _tx_gi(gi, n, who):
+    """gi=None -> None (the entry point without a kind); else one kind (0 long / 1 short) per frame as a list"""
+    if gi is None:
+        return None
+    g = [int(v) for v in gi] if np.ndim(gi) else [int(gi)] * n
+    if len(g) != n or any(v not in (0, 1) for v in g):
+        raise SoraError(-1, who + ": gi must hold one guard-interval kind per frame, 0 (long) or 1 (short)")
+    return g
+
+
+def tx_ht40(mpdus0, mpdus1, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None, gi=None):
     """Modulate a batch of MPDU pairs (bytes WITHOUT FCS; mpdus0[f] on spatial stream 0, mpdus1[f] on stream 1, of equal length) as HT-mixed
     40 MHz two-stream frames on the GPU (MCS 8..14): what RxHt40 receives.
     -> (out0, out1, offsets): int16 CUDA tensors [total,2] COMPLEX16 @40 MHz for TX chains 0 and 1, and the offsets list.
     Frame f occupies samples offsets[f] .. offsets[f+1] of both (gaps[f] zero samples in front of frame f, if given, included at its start);
     its HT-LTF 1 starts 1280 samples after its first sample.
-    seeds: one (seed0, seed1) pair of scrambler seeds per frame (None: 0x5D, 0x2B).  A frame that is not accepted is refused before any launch."""
+    seeds: one (seed0, seed1) pair of scrambler seeds per frame (None: 0x5D, 0x2B).  A frame that is not accepted is refused before any launch.
+    gi: None -> sora_hip_tx_ht40; else one guard-interval kind per frame (or one for all), 0 = long, 1 = short (data symbols of 144 samples, HT-SIG bit 31) ->
+    sora_hip_tx_ht40_gi."""
     import torch
     n = len(mpdus0)
     mcs = [int(m) for m in mcs] if np.ndim(mcs) else [int(mcs)] * n
     lens = [len(m) for m in mpdus0]
     if len(mpdus1) != n or len(mcs) != n or any(len(b) != l for b, l in zip(mpdus1, lens)):
         raise SoraError(-1, "tx_ht40: one MPDU per stream and frame, both of a frame of the same length")
-    ns = [tx_ht40_samples(l, m) for l, m in zip(lens, mcs)]
+    gi = _tx_gi(gi, n, "tx_ht40")
+    ns = [tx_ht40_samples(l, m) for l, m in zip(lens, mcs)] if gi is None else [tx_ht40_gi_samples(l, m, g) for l, m, g in zip(lens, mcs, gi)]
     if any(v == 0 for v in ns):
         raise SoraError(-1, "tx_ht40: unsupported MCS or length (MCS 8..14, 1..3996 bytes)")
     if seeds is not None and (len(seeds) != n or any(len(p) != 2 for p in seeds)):
@@ -2714,8 +2750,13 @@ def tx_ht40(mpdus0, mpdus1, mcs, seeds=None, device=0, stream=None, sync=True, g
     d_ooff = torch.from_numpy(first.astype(np.int64)).to(dev)
     out0 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
     out1 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
-    _check(load().sora_hip_tx_ht40(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
-                                   _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
+    if gi is None:
+        _check(load().sora_hip_tx_ht40(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
+                                       _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
+    else:
+        d_gi = torch.from_numpy(np.asarray(gi, np.uint8)).to(dev)
+        _check(load().sora_hip_tx_ht40_gi(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None,
+                                          _dev_ptr(d_gi), n, _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     return out0, out1, [int(v) for v in ooff]
@@ -2726,17 +2767,23 @@ def tx_ht40_joint_samples(mpdu_len_nofcs, mcs):
     return int(load().sora_hip_tx_ht40_joint_samples(int(mpdu_len_nofcs), int(mcs)))
 
 
-def tx_ht40_joint(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None):
+def tx_ht40_joint_gi_samples(mpdu_len_nofcs, mcs, gi):
+    """as tx_ht40_gi_samples, for one joint-coded frame (sora_hip_tx_ht40_joint_gi_samples)"""
+    return int(load().sora_hip_tx_ht40_joint_gi_samples(int(mpdu_len_nofcs), int(mcs), int(gi) & 0xFFFFFFFF))
+
+
+def tx_ht40_joint(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None, gi=None):
     """Modulate a batch of MPDUs (bytes WITHOUT FCS), ONE per frame, as joint-coded HT-mixed 40 MHz two-stream frames on the GPU (MCS 8..14): what an RxHt40 in
     CODING_JOINT receives.  -> (out0, out1, offsets) as tx_ht40.  seeds: one scrambler seed per frame (None: 0x5D).  A frame that is not accepted is refused before
-    any launch."""
+    any launch.  gi: as tx_ht40's (None -> sora_hip_tx_ht40_joint; else sora_hip_tx_ht40_joint_gi)."""
     import torch
     n = len(mpdus)
     mcs = [int(m) for m in mcs] if np.ndim(mcs) else [int(mcs)] * n
     lens = [len(m) for m in mpdus]
     if len(mcs) != n:
         raise SoraError(-1, "tx_ht40_joint: one MCS per frame")
-    ns = [tx_ht40_joint_samples(l, m) for l, m in zip(lens, mcs)]
+    gi = _tx_gi(gi, n, "tx_ht40_joint")
+    ns = [tx_ht40_joint_samples(l, m) for l, m in zip(lens, mcs)] if gi is None else [tx_ht40_joint_gi_samples(l, m, g) for l, m, g in zip(lens, mcs, gi)]
     if any(v == 0 for v in ns):
         raise SoraError(-1, "tx_ht40_joint: unsupported MCS or length (MCS 8..14, 1..3996 bytes)")
     if seeds is not None and (len(seeds) != n or any(np.ndim(p) != 0 for p in seeds)):
@@ -2755,8 +2802,13 @@ def tx_ht40_joint(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps
     d_ooff = torch.from_numpy(first.astype(np.int64)).to(dev)
     out0 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
     out1 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
-    _check(load().sora_hip_tx_ht40_joint(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
-                                         _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
+    if gi is None:
+        _check(load().sora_hip_tx_ht40_joint(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
+                                             _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
+    else:
+        d_gi = torch.from_numpy(np.asarray(gi, np.uint8)).to(dev)
+        _check(load().sora_hip_tx_ht40_joint_gi(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None,
+                                                _dev_ptr(d_gi), n, _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     return out0, out1, [int(v) for v in ooff]
@@ -3097,7 +3149,7 @@ class _GpuHt40Ops(_Gpu11nOps):
 def ht40_frame_symbols(d, coding=0):
     """data symbols of the described frame d = (offset, n_bpsc, code_rate, length0, length1, ...) in the given coding: ceil((16 + 8 LENGTH + 6) / N_DBPS), N_DBPS = 108 N_BPSC R
     per stream (sora_ht40_symbols), twice that over the one PSDU of the joint coding (sora_ht40_symbols_joint); 0: a bad descriptor"""
-    nb, cr = int(d[1]), int(d[2])
+    nb, cr = int(d[1]), int(d[2]) & ~HT40_SHORT_GI                                # (the guard interval does not change N_SYM)
     if nb not in (1, 2, 4, 6) or cr not in (0, 1, 2):
         return 0
     nd = 108 * nb * (1, 2, 3)[cr] // (2, 3, 4)[cr]
@@ -3116,6 +3168,9 @@ def rx_ht40_stages(ops, iq0, iq1, frames, coding=0):
       2. symbol by symbol over the batch, because theta of symbol d rotates symbol d + 1: freq_comp11n -> data_symbol_ht40 -> fft128 -> mimo_comp_ht40 -> pilot_track_ht40;
          a frame that has ended takes part with a count of 0;
       3. over all symbols of a modulation at once: demap_ht40 -> deinterleave_ht40 (-> stream_join_ht40) -> per code rate viterbi11n_ws -> desc11a -> frame_sink11a.
+    A descriptor whose code_rate carries HT40_SHORT_GI is a short-GI frame (data symbols of 144 samples, prefix 16), composed from the same stages: in step 2 its
+    freq_comp11n runs over 18 bursts at offset + 320 + 144 d, and its data_symbol_ht40 starts 16 samples EARLIER, at offset + 320 + 144 d - 16, so that the stage's samples
+    32..159 are exactly the symbol's 128 useful ones (the 16 in front are skipped unread by what follows).  Rows of such a frame carry "short_gi": True.
     -> dict: rows [{frame, stream, error_code, length, crc32, nsym, mpdu}] (frame-major), soft (per frame [stream 0, stream 1] uint8, or the merged bytes in joint coding),
     theta (per frame int16 [nsym + 1]: theta[d] compensates symbol d, the last entry stands after the last symbol), weights and h (ops buffers [frames, 4, 128, 2]), xs (per
     frame int16 [nsym, 2, 128, 2], the detected symbols)."""
@@ -3129,6 +3184,9 @@ def rx_ht40_stages(ops, iq0, iq1, frames, coding=0):
             raise ValueError("rx_ht40_stages: bad frame descriptor (n_bpsc 1/2/4/6, code_rate 0..2, PSDU <= 4000 bytes, noise_var >= 0; joint coding: length1 = 0)")
     off = np.array([int(d[0]) for d in frames], np.int64); nbp = np.array([int(d[1]) for d in frames], np.int64)
     cfo = np.array([int(d[5]) for d in frames], np.int64)
+    sgi = np.array([(int(d[2]) & HT40_SHORT_GI) != 0 for d in frames], bool)
+    pitch = np.where(sgi, 144, 160); lead = np.where(sgi, 16, 0)                  # a short symbol: 18 bursts; the stage's 160-sample window starts 16 early
+    rate = [int(d[2]) & ~HT40_SHORT_GI for d in frames]
     u32 = lambda a: np.asarray(a, np.int64).astype(np.uint32).view(np.int32)
     i16 = lambda a: ((np.asarray(a, np.int64) + 32768) & 0xFFFF) - 32768
     rec = np.zeros((nf, 24), np.int16)
@@ -3143,9 +3201,9 @@ def rx_ht40_stages(ops, iq0, iq1, frames, coding=0):
     xs0 = [[] for _ in range(nf)]; xs1 = [[] for _ in range(nf)]
     for d in range(int(nsym.max())):
         al = np.nonzero(nsym > d)[0]
-        nbur = np.zeros(nf, np.int64); nbur[al] = 20
-        c0, c1 = ops.freq_comp(iq0, iq1, u32(off + 320 + 160 * d), u32(nbur), st)
-        y0, y1 = ops.data_symbol(c0, c1, u32(off[al] + 320 + 160 * d), u32(np.ones(len(al))), u32(np.arange(len(al))), len(al))
+        nbur = np.zeros(nf, np.int64); nbur[al] = pitch[al] // 8
+        c0, c1 = ops.freq_comp(iq0, iq1, u32(off + 320 + pitch * d), u32(nbur), st)
+        y0, y1 = ops.data_symbol(c0, c1, u32(off[al] + 320 + pitch[al] * d - lead[al]), u32(np.ones(len(al))), u32(np.arange(len(al))), len(al))
         x0, x1 = ops.mimo_comp(w, ops.fft128(y0), ops.fft128(y1), u32(al))
         pf = np.zeros(nf, np.int64); pn = np.zeros(nf, np.int64); pf[al] = np.arange(len(al)); pn[al] = 1
         th = ops.pilot_track(x0, x1, u32(pf), u32(pn), st)
@@ -3167,21 +3225,21 @@ def rx_ht40_stages(ops, iq0, iq1, frames, coding=0):
             at += n
     jobs = [(f, 0) for f in range(nf)] if joint else [(f, s) for f in range(nf) for s in range(2)]
     rows = [None] * len(jobs)
-    for rate in (0, 1, 2):
-        js = [j for j, (f, s) in enumerate(jobs) if frames[f][2] == rate]
+    for cr in (0, 1, 2):
+        js = [j for j, (f, s) in enumerate(jobs) if rate[f] == cr]
         if not js:
             continue
         parts = [soft[jobs[j][0]] if joint else soft[jobs[j][0]][jobs[j][1]] for j in js]
         nsoft = np.array([int(p.shape[0]) for p in parts], np.int64)
         lens = np.array([int(frames[jobs[j][0]][3 + jobs[j][1]]) for j in js], np.int64)
-        dec = ops.viterbi(ops.concat(parts), u32(np.concatenate([[0], np.cumsum(nsoft)])[:-1]), u32(nsoft), lens, rate)
+        dec = ops.viterbi(ops.concat(parts), u32(np.concatenate([[0], np.cumsum(nsoft)])[:-1]), u32(nsoft), lens, cr)
         boff = 4096 * np.arange(len(js))
         by = ops.desc(dec, u32(ops.VOUT * np.arange(len(js))), u32(lens), u32(boff), 4096 * len(js))
         srec = ops.frame_sink(by, u32(boff), u32(lens)); hb = ops.host(by)
         for i, j in enumerate(js):
             f, s = jobs[j]
             rows[j] = {"frame": f, "stream": s, "error_code": int(srec[i, 0]), "length": int(lens[i]), "crc32": int(srec[i, 1]), "nsym": int(nsym[f]),
-                       "mpdu": hb[boff[i]:boff[i] + lens[i]].tobytes()}
+                       "short_gi": bool(sgi[f]), "mpdu": hb[boff[i]:boff[i] + lens[i]].tobytes()}
     xs = [np.stack([np.stack([ops.host(a).reshape(128, 2), ops.host(b).reshape(128, 2)]) for a, b in zip(xs0[f], xs1[f])]) for f in range(nf)]
     return {"rows": rows, "soft": [ops.host(s) if joint else [ops.host(s[0]), ops.host(s[1])] for s in soft], "theta": [np.array(t, np.int16) for t in theta],
             "weights": w, "h": h, "xs": xs}

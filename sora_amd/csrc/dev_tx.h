@@ -173,6 +173,24 @@ __device__ __forceinline__ void tx_emit160(const uint32_t* s, int e, uint32_t* o
     }
 }
 
+// ---- the short guard interval of the 40 MHz HT pair (k_tx_ht40.hip): 144 COMPLEX16 samples of one chain from the transformed buffer, output
+// sample i = time sample (i + 112) & 127 -- the last 16 of the 128, then the 128; no cyclic shift.  36 16-byte words where the stream allows: lane e stores word e and,
+// for e < 4, the same word once more as word 32 + e (the index is the same modulo 128); word by word otherwise.  144 samples are 576 bytes: a frame that starts
+// 16-byte aligned keeps every data symbol on the vector path.
+template <bool SWZ>
+__device__ __forceinline__ void tx_emit144(const uint32_t* s, int e, uint32_t* o)
+{
+    if ((reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
+        const uint32_t n0 = (uint32_t)(4 * e + 112);
+        uint4 v;
+        v.x = tx_tsample<SWZ>(s, n0); v.y = tx_tsample<SWZ>(s, n0 + 1); v.z = tx_tsample<SWZ>(s, n0 + 2); v.w = tx_tsample<SWZ>(s, n0 + 3);
+        reinterpret_cast<uint4*>(o)[e] = v;
+        if (e < 4) reinterpret_cast<uint4*>(o)[32 + e] = v;
+    } else {
+        for (int i = e; i < 144; i += 32) o[i] = tx_tsample<SWZ>(s, (uint32_t)(i + 112));
+    }
+}
+
 // ---- the fixed fields of an HT-mixed frame from the per-device table [2 chains][1120]: samples 0..639 (L-STF, L-LTF) and 1120..1599 (HT-STF, HT-LTF1,
 // HT-LTF2) of both chains; the three SIG symbols go between them
 static_assert(kTx11nPreamble == 1120 && kTxHt40Preamble == 1120, "one table shape for both HT transmitters");

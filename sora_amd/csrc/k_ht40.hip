@@ -35,7 +35,8 @@ struct Ht40Frame {
     float    noise_var;         // per carrier, in LSB^2 of the FFT output; 0 = zero forcing
     // bytes from the soft base: stream 0's soft values, one byte each (VitJob::soft_bits = 8); stream 1's follow at + round_up(values per stream, 32)
     uint32_t soft_off;
-    uint32_t pad[4];
+    uint32_t gi;                // 1 = short guard interval: data symbols of 144 samples, prefix 16; read by the guard-aware kernels only
+    uint32_t pad[3];
 };
 struct Ht40Args {
     const uint32_t* iq0; const uint32_t* iq1; const Ht40Frame* frames; uint32_t nframes;
@@ -63,7 +64,10 @@ struct Ht40Lds {
 // encoder's output went through the reference's stream parser (k_tx11n.hip: with s = max(1, N_BPSC / 2), coded bit kc of a symbol goes to stream (kc / s) & 1 as that
 // stream's bit (kc / 2s) s + kc % s), so the symbol's 2 N_CBPSS soft bytes leave as one merged stream: position q reads W.soft through one table that composes the
 // de-parser with the stream's de-interleaver.  Every addition sits under "if constexpr (JOINT)": the per-stream kernel is the instruction stream it was.
-template <bool JOINT>
+// GI = true (k_ht40_frame_gi, k_ht40_frame_joint_gi): a frame's guard-interval kind F.gi selects the data symbols' pitch and prefix -- 160 / 32 or
+// 144 / 16, wave-uniform, so the four frames of a workgroup may differ in kind; the HT-LTFs keep 160 / 32, and the phase index stays the sample's index in the frame.
+// Launched only for a call that can hold a short frame; every addition sits under GI, so the kernels without it are the instruction streams they were.
+template <bool JOINT, bool GI = false>
 __device__ __forceinline__ void ht40_frame_body(const Ht40Args& A)
 {
     __shared__ Ht40Lds s_w[4];
@@ -92,11 +96,14 @@ __device__ __forceinline__ void ht40_frame_body(const Ht40Args& A)
     for (int k = lane; k < ncb; k += 64) { W.dtab[0][k] = (uint16_t)deint40_index(nb, 0, k); W.dtab[1][k] = (uint16_t)deint40_index(nb, 1, k); }
     int theta = 0;
     const Fft128TwPk twpk = fft128_twiddles_pk(A.T, lane & 31);
-    // one 160-sample symbol starting at sample `pos` of the frame: TFreqComp_11n, cyclic prefix dropped, FFT<128> per chain (32 lanes each) -> W.y[slot]
-    auto symbol_fft = [&](uint32_t pos, int slot) __attribute__((always_inline)) {
+    [[maybe_unused]] uint32_t pitch = 160, cpd = 32;                                          // GI: the data symbols' pitch and cyclic prefix
+    if constexpr (GI) { if (__builtin_amdgcn_readfirstlane((int)F.gi) != 0) { pitch = 144; cpd = 16; } }
+    // one symbol starting at sample `pos` of the frame (160 samples with a prefix of 32; GI: a prefix of `cp`): TFreqComp_11n, cyclic prefix dropped, FFT<128> per chain
+    // (32 lanes each) -> W.y[slot]
+    auto symbol_fft = [&](uint32_t pos, int slot, [[maybe_unused]] uint32_t cp) __attribute__((always_inline)) {
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-            const uint32_t n = pos + 32 + 64 * h + (uint32_t)lane;
+            const uint32_t n = pos + (GI ? cp : 32u) + 64 * h + (uint32_t)lane;
             const cpx cof = unpack(A.sincos[(unsigned)((int)n * cfo - theta) & 0xFFFFu]);
 #pragma unroll
             for (int r = 0; r < 2; r++) W.buf[r][64 * h + lane] = pack(freq_comp11n(unpack(iq[r][n]), cof));
@@ -111,8 +118,8 @@ __device__ __forceinline__ void ht40_frame_body(const Ht40Args& A)
         for (int q = 0; q < 4; q++) W.y[slot][r][e + 32 * q] = W.fft[r][__brev((unsigned)(e + 32 * q)) >> 25];
         wave_lds_sync();
     };
-    symbol_fft(0, 0);
-    symbol_fft(160, 1);
+    symbol_fft(0, 0, 32);
+    symbol_fft(160, 1, 32);
     // ---- channel matrix per carrier (TMimoChannelEst's combination) and detection weights
 #pragma unroll
     for (int hb = 0; hb < 2; hb++) {
@@ -160,7 +167,7 @@ __device__ __forceinline__ void ht40_frame_body(const Ht40Args& A)
     uint8_t* dst = A.soft + F.soft_off;
     const uint32_t per_pad = (F.nsym * 108u * F.nb + 31u) / 32u * 32u;         // stream 1 starts here (ht40_submit lays the job records out the same way)
     for (uint32_t d = 0; d < F.nsym; d++) {
-        symbol_fft(320 + 160 * d, 0);
+        symbol_fft(320 + (GI ? pitch : 160u) * d, 0, cpd);
 #pragma unroll
         for (int hb = 0; hb < 2; hb++) {                                     // TMimoChannelComp
             const int i = lane + 64 * hb;
@@ -203,6 +210,8 @@ __device__ __forceinline__ void ht40_frame_body(const Ht40Args& A)
 }
 __global__ void __launch_bounds__(256) k_ht40_frame(Ht40Args A) { ht40_frame_body<false>(A); }
 __global__ void __launch_bounds__(256) k_ht40_frame_joint(Ht40Args A) { ht40_frame_body<true>(A); }
+__global__ void __launch_bounds__(256) k_ht40_frame_gi(Ht40Args A) { ht40_frame_body<false, true>(A); }
+__global__ void __launch_bounds__(256) k_ht40_frame_joint_gi(Ht40Args A) { ht40_frame_body<true, true>(A); }
 
 // PER: finish jobs (= rows) per frame: 2 in the per-stream coding, 1 in the joint one
 template <uint32_t PER>
@@ -234,7 +243,8 @@ struct Ht40Geom { uint32_t nb, cr, nsym, per, per_pad; };
 __device__ __forceinline__ Ht40Geom ht40_geom(const Ht40Found& F, uint32_t joint)
 {
     Ht40Geom G;
-    G.nb = nbpsc11n(F.mcs); G.cr = code_rate11n(F.mcs);
+    const uint32_t mcs = F.mcs & ~SORA_HT40_SHORT_GI;                            // (a short-GI record carries the flag on its MCS: a frame holds the same soft bytes)
+    G.nb = nbpsc11n(mcs); G.cr = code_rate11n(mcs);
     const uint32_t nd = ht40_ndbps(G.nb, G.cr) << joint;                         // joint coding: one field over both streams
     G.nsym = (16u + 8u * F.ht_len + 6u + nd - 1u) / nd;                          // sora_ht40_symbols(len, len, nb, cr) / sora_ht40_symbols_joint(len, nb, cr)
     G.per = G.nsym * 108u * G.nb; G.per_pad = (G.per + 31u) / 32u * 32u;
@@ -304,10 +314,20 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
             if (fi >= max_frames || (uint64_t)soft_off + 2u * G.per_pad > max_soft || !(F.noise_var >= 0.0f)) { s_err = 1u; evn[e] = 0u; continue; }
             Ht40Frame H;
             H.offset = caps[c].offset + 2ull * F.a20 + 160ull;                   // HT-STF is 4 us = 160 samples @40 MHz; HT-LTF 1 follows
+            const uint32_t sgi = (F.mcs & SORA_HT40_SHORT_GI) ? 1u : 0u;           // set only by the front end of a handle in SORA_HT40_GUARD_SIGNALLED
+            if (sgi) {
+                // The front end's a20 lies 21..28 samples @40 MHz in front of the frame's own timing: inside the 32-sample guard interval, so a long frame's windows see
+                // one symbol each, but in front of a 16-sample prefix.  A short-GI frame is therefore taken kHt40ShortAdvance samples later, HT-LTFs and data alike (one
+                // timing for the channel estimate and the symbols it detects), which puts every window 5..12 samples inside its prefix -- as far as the capture's
+                // samples reach behind the frame's extent [.., 2 a20 + 480 + 144 nsym) (a capture that ends inside those samples cuts the frame's own tail).
+                const uint64_t end = 2ull * F.a20 + 480ull + (uint64_t)kHt40ShortSym * G.nsym;
+                const uint64_t room = caps[c].nsamples > end ? caps[c].nsamples - end : 0ull;
+                H.offset += room < kHt40ShortAdvance ? room : (uint64_t)kHt40ShortAdvance;
+            }
             // one HT-SIG LENGTH: each stream carries its own PSDU of that length
             H.nsym = G.nsym; H.nb = G.nb; H.code_rate = G.cr; H.length[0] = F.ht_len; H.length[1] = joint ? 0u : F.ht_len;
             H.cfo = F.cfo / 2;                                                   // per 20 MHz sample -> per 40 MHz sample
-            H.noise_var = F.noise_var; H.soft_off = soft_off; H.pad[0] = H.pad[1] = H.pad[2] = H.pad[3] = 0;
+            H.noise_var = F.noise_var; H.soft_off = soft_off; H.gi = sgi; H.pad[0] = H.pad[1] = H.pad[2] = 0;
             frames[fi] = H;
             for (uint32_t k = 0; k < jpf; k++) {
                 VitJob J;
@@ -316,8 +336,8 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
                 jobs[(size_t)G.cr * stride + pos + k] = J;
                 fjobs[jpf * fi + k] = Ht40Job{ J.out_off, F.ht_len, jpf * fi + k, 0u };
                 sora_frame_result o;
-                o.capture_id = caps[c].capture_id; o.start_sample = k; o.end_sample = F.end_sample; o.error_code = 0; o.rate_kbps = F.mcs;
-                o.length = 0; o.nsym = (uint16_t)G.nsym; o.crc32 = 0; o.cfo_est = 0; o.flags = tflag; o.mpdu_offset = 0;
+                o.capture_id = caps[c].capture_id; o.start_sample = k; o.end_sample = F.end_sample; o.error_code = 0; o.rate_kbps = F.mcs & ~SORA_HT40_SHORT_GI;
+                o.length = 0; o.nsym = (uint16_t)G.nsym; o.crc32 = 0; o.cfo_est = 0; o.flags = (uint16_t)(tflag | (sgi ? SORA_ROW_SHORT_GI : 0u)); o.mpdu_offset = 0;
                 tmpl[2u * e + k] = o;
             }
         }
@@ -347,7 +367,7 @@ using namespace sora;
 // kernels.  sora_ht40_results reports the most recent call.
 static constexpr int kHt40Slots = 8;
 // frame: index into the call's described frames, -1 = header failed
-struct Ht40Event { uint32_t capture_id, end_sample, error_code, mcs, length, nsym; int frame; bool truncated; };
+struct Ht40Event { uint32_t capture_id, end_sample, error_code, mcs, length, nsym; int frame; bool truncated, short_gi; };
 struct Ht40Slot : Call {       // the stream, ticket and completion state of the call this slot holds (host_calls.h)
     Ht40Frame* d_frames = nullptr; VitJob* d_jobs = nullptr; uint32_t* d_njobs = nullptr; Ht40Job* d_fjobs = nullptr;
     uint8_t* d_soft = nullptr; uint8_t* d_vout = nullptr; uint8_t* d_mpdu = nullptr; Rx11bRow* d_rows = nullptr;
@@ -357,6 +377,7 @@ struct Ht40Slot : Call {       // the stream, ticket and completion state of the
     uint32_t* d_nfr = nullptr; size_t nfr_bytes = 0; Ht40Found* d_found = nullptr; size_t found_bytes = 0;
     bool capture_mode = false; uint32_t capture_mf = 0; std::vector<Ht40Event> events;
     bool joint = false;         // the coding the call was issued in (sora_ht40_set_coding): one job and one row per frame
+    bool guard = false;         // the call can hold a short-GI frame (a flagged descriptor; a raw-capture call in SORA_HT40_GUARD_SIGNALLED): the guard-aware kernels
     uint32_t ncaps = 0;         // captures of a raw-capture call (sora_ht40_stream_consumed); 0 for a descriptor call
     // ... planned on the device (k_ht40_plan): the records come back asynchronously into page-locked memory and are turned into `events` when the call is collected
     uint32_t* d_plan = nullptr;
@@ -379,6 +400,7 @@ struct sora_ht40 {
     // k_viterbi11n (64 lanes per stream pair; the faster one for a call alone) -- sora_ht40_set_trellis
     Trellis trellis = Trellis::Lanes16;
     int coding = SORA_HT40_CODING_PER_STREAM;                                    // sora_ht40_set_coding
+    int guard = SORA_HT40_GUARD_LONG;                                            // sora_ht40_set_guard
     // sora_ht40_set_stream_mode: the records belong to the handle, not to a slot; sized for max_frames streams when the mode is first enabled
     StreamRecords records{kRec11nWords};
 };
@@ -415,9 +437,11 @@ uint32_t sora_ht40_symbols_joint(uint32_t length, uint32_t n_bpsc, uint32_t code
     return ht40_symbols_joint(length, 2u * ht40_ndbps(n_bpsc, code_rate));       // one field over both streams: N_DBPS = 2 x 108 N_BPSC R
 }
 // data symbols of a described frame in the coding of its call
+static inline uint32_t ht40_frame_cr(const sora_ht40_frame& f) { return f.code_rate & ~SORA_HT40_SHORT_GI; }     // SORA_CR_*; any other bit left standing is refused
+static inline bool ht40_frame_short(const sora_ht40_frame& f) { return (f.code_rate & SORA_HT40_SHORT_GI) != 0; }
 static uint32_t ht40_frame_symbols(const sora_ht40_frame& f, bool joint)
 {
-    return joint ? sora_ht40_symbols_joint(f.length[0], f.n_bpsc, f.code_rate) : sora_ht40_symbols(f.length[0], f.length[1], f.n_bpsc, f.code_rate);
+    return joint ? sora_ht40_symbols_joint(f.length[0], f.n_bpsc, ht40_frame_cr(f)) : sora_ht40_symbols(f.length[0], f.length[1], f.n_bpsc, ht40_frame_cr(f));
 }
 
 int sora_ht40_create(int device, uint32_t max_frames, uint64_t max_soft_values, sora_ht40_t** out)
@@ -490,6 +514,19 @@ int sora_ht40_set_coding(sora_ht40_t* rx, int coding)
     rx->coding = coding;
     return old;
 }
+int sora_ht40_set_guard(sora_ht40_t* rx, int mode)
+{
+    if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_set_guard: null handle", 0);
+    const int old = rx->guard;
+    if (mode < 0) return old;
+    if (mode != SORA_HT40_GUARD_LONG && mode != SORA_HT40_GUARD_SIGNALLED) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
+            "sora_ht40_set_guard: SORA_HT40_GUARD_LONG (0) or SORA_HT40_GUARD_SIGNALLED (1)", 0);
+    { const int rc = sora_ht40_synchronize(rx); if (rc) return rc; }
+    HIPCHK(hipSetDevice(rx->device));
+    { const int rc = rx->records.zero(rx->max_frames); if (rc) return rc; }       // a frame's extent depends on the mode: every stream starts afresh
+    rx->guard = mode;
+    return old;
+}
 int sora_ht40_stream_consumed(sora_ht40_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps)
 {
     if (!rx || !h_consumed) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_stream_consumed: null argument", 0);
@@ -504,7 +541,8 @@ static int ht40_data_field(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d
     Ht40Args A;
     A.iq0 = reinterpret_cast<const uint32_t*>(d_iq0); A.iq1 = reinterpret_cast<const uint32_t*>(d_iq1); A.frames = S.d_frames; A.nframes = nframes;
     A.T = rx->T; A.sincos = rx->sincos; A.atan = rx->atan; A.soft = S.d_soft; A.w_out = reinterpret_cast<uint32_t*>(d_weights); A.plan = plan;
-    hipLaunchKernelGGL(S.joint ? k_ht40_frame_joint : k_ht40_frame, dim3((nframes + 3) / 4), dim3(256), 0, S.stream, A);
+    if (S.guard) hipLaunchKernelGGL(S.joint ? k_ht40_frame_joint_gi : k_ht40_frame_gi, dim3((nframes + 3) / 4), dim3(256), 0, S.stream, A);
+    else hipLaunchKernelGGL(S.joint ? k_ht40_frame_joint : k_ht40_frame, dim3((nframes + 3) / 4), dim3(256), 0, S.stream, A);
     trellis_launch<192>(rx->trellis, trellis_lists(S.d_jobs, S.d_njobs, njobs, 2 * rx->max_frames), S.d_soft, S.d_vout, S.stream);
     Ht40FinishArgs Fi; Fi.jobs = S.d_fjobs; Fi.njobs = njobs; Fi.vout = S.d_vout; Fi.mpdu = S.d_mpdu; Fi.rows = S.d_rows; Fi.T = rx->T; Fi.plan = plan;
     hipLaunchKernelGGL(S.joint ? k_ht40_finish_joint : k_ht40_finish, dim3((njobs + 3) / 4), dim3(256), 0, S.stream, Fi);
@@ -527,28 +565,32 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
     const size_t stride = 2 * (size_t)rx->max_frames;
     const bool joint = S.joint;
     const size_t jpf = joint ? 1 : 2;                                             // decoder jobs, finish jobs and rows per frame
+    bool guard = false;                                                           // a frame with SORA_HT40_SHORT_GI on its code rate: the guard-aware kernel takes the call
     for (size_t i = 0; i < nframes; i++) {
         const sora_ht40_frame& s = frames[i];
+        const uint32_t cr = ht40_frame_cr(s);
+        guard = guard || ht40_frame_short(s);
         if (joint && s.length[1] != 0) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
                 "sora_ht40_process_dev: in joint coding a frame carries one PSDU: length[1] must be 0", 0);
         const uint32_t nsym = ht40_frame_symbols(s, joint);
         if (nsym == 0 || s.length[0] > 4000 || s.length[1] > 4000 || !(s.noise_var >= 0.0f)) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
-                "sora_ht40_process_dev: bad frame descriptor (n_bpsc 1/2/4/6, code_rate 0..2, PSDU <= 4000 bytes, noise_var >= 0)", 0);
+                "sora_ht40_process_dev: bad frame descriptor (n_bpsc 1/2/4/6, code_rate 0..2 with or without SORA_HT40_SHORT_GI, PSDU <= 4000 bytes, noise_var >= 0)", 0);
         Ht40Frame& F = hf[i];
-        F.offset = s.offset; F.nsym = nsym; F.nb = s.n_bpsc; F.code_rate = s.code_rate; F.length[0] = s.length[0]; F.length[1] = s.length[1]; F.cfo = s.cfo;
+        F.offset = s.offset; F.nsym = nsym; F.nb = s.n_bpsc; F.code_rate = cr; F.length[0] = s.length[0]; F.length[1] = s.length[1]; F.cfo = s.cfo;
             F.noise_var = s.noise_var;
         const uint64_t per = (uint64_t)nsym * 108 * s.n_bpsc;                       // soft values per stream
         F.soft_off = (uint32_t)soft;
         for (size_t k = 0; k < jpf; k++) {
             // the two streams of a frame are neighbours in their list: one wave decodes both (joint coding: one job over the frame's merged bytes; two frames share a wave)
-            VitJob& J = hj[s.code_rate * stride + nj[s.code_rate]++];
+            VitJob& J = hj[cr * stride + nj[cr]++];
             J.soft_off = F.soft_off + (uint32_t)k * (uint32_t)((per + 31) / 32 * 32); J.soft_bits = 8; J.nsoft = (uint32_t)(joint ? 2 * per : per); J.length = s.length[k];
-                J.dec_off = 0; J.out_off = (uint32_t)((jpf * i + k) * kVoutStride); J.valid = 1; J.code_rate = s.code_rate;
+                J.dec_off = 0; J.out_off = (uint32_t)((jpf * i + k) * kVoutStride); J.valid = 1; J.code_rate = cr;
             fj[jpf * i + k] = Ht40Job{ J.out_off, s.length[k], (uint32_t)(jpf * i + k), 0 };
         }
         soft += 2 * ((per + 31) / 32 * 32);                                         // bytes: one per soft value, both streams
-        F.pad[0] = F.pad[1] = F.pad[2] = F.pad[3] = 0;
+        F.gi = ht40_frame_short(s) ? 1u : 0u; F.pad[0] = F.pad[1] = F.pad[2] = 0;
     }
+    S.guard = guard;
     if (soft > rx->max_soft) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_process_dev: more soft values than max_soft_values", 0);
     S.h_frames.assign(frames, frames + nframes); S.nframes = (uint32_t)nframes; rx->have_results = true;
     rx->last = rx->next;
@@ -570,7 +612,7 @@ int sora_ht40_process_dev(sora_ht40_t* rx, const sora_complex16* d_iq0, const so
     rx->next = call_next(rx->slot, kHt40Slots);                                   // an unused slot, else a released call's, else the oldest call's
     Ht40Slot& S = rx->slot[rx->next];
     HIPCHK(hipStreamSynchronize(S.stream));                                     // the call that used this slot kHt40Slots calls ago
-    S.events.clear(); S.capture_mode = false; S.events_pending = false; S.plan_error = false; S.ncaps = 0; S.joint = rx->coding == SORA_HT40_CODING_JOINT;
+    S.events.clear(); S.capture_mode = false; S.events_pending = false; S.plan_error = false; S.ncaps = 0; S.joint = rx->coding == SORA_HT40_CODING_JOINT; S.guard = false;
     return ht40_submit(rx, S, d_iq0, d_iq1, frames, nframes, d_weights);
 }
 
@@ -621,7 +663,7 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     for (size_t i = 0; i < ncaps; i++) { CapDesc& h = S.h_capsup[i]; h.offset = caps[i].offset; h.nsamples = caps[i].nsamples;
         h.capture_id = caps[i].capture_id; h.slot_base = 0; h.nslots = 0; }
     S.h_caps.assign(caps, caps + ncaps);
-    S.joint = rx->coding == SORA_HT40_CODING_JOINT;
+    S.joint = rx->coding == SORA_HT40_CODING_JOINT; S.guard = rx->guard == SORA_HT40_GUARD_SIGNALLED;
     S.events.clear(); S.capture_mode = true; S.capture_mf = mf; S.ncaps = (uint32_t)ncaps; S.events_pending = true; S.plan_error = false; S.nframes = 0;
     S.bound_frames = (uint32_t)std::min<uint64_t>(nrows, rx->max_frames); S.bound_events = (uint32_t)nrows;
     rx->have_results = true; rx->last = rx->next;
@@ -633,7 +675,7 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     { const int rc = sora_internal_scan_ht40(reinterpret_cast<const uint32_t*>(d_iq0), reinterpret_cast<const uint32_t*>(d_iq1), S.d_caps, (uint32_t)ncaps, mf,
             S.d_scanrows, S.d_nfr, S.d_found,
                                              rx->T, rx->sincos, rx->atan, S.stream, rx->records.on ? rx->records.d_cont : nullptr,
-                                             rx->records.on ? rx->records.d_consumed : nullptr, S.joint ? 1u : 0u); if (rc) return rc; }
+                                             rx->records.on ? rx->records.d_consumed : nullptr, S.joint ? 1u : 0u, S.guard ? 1u : 0u); if (rc) return rc; }
     const size_t stride = 2 * (size_t)rx->max_frames;
     hipLaunchKernelGGL(k_ht40_plan, dim3(1), dim3(1024), 0, S.stream, (const CapDesc*)S.d_caps, (uint32_t)ncaps, mf, (const uint32_t*)S.d_nfr, (const Ht40Found*)S.d_found,
                        rx->max_frames, (uint64_t)rx->max_soft, kVoutStride, S.d_frames, S.d_jobs, (uint32_t)stride, S.d_njobs, S.d_fjobs, S.d_evtmpl, S.d_plan, S.d_evbase, S.d_evn,
@@ -660,8 +702,8 @@ static int ht40_collect_events(Ht40Slot& S)
         const uint32_t n = std::min(S.h_nfr[c], mf);
         for (uint32_t i = 0; i < n; i++) {
             const Ht40Found& F = S.h_found[c * mf + i];
-            Ht40Event E; E.capture_id = S.h_caps[c].capture_id; E.end_sample = F.end_sample; E.error_code = F.error_code; E.mcs = F.mcs; E.length = F.ht_len;
-                E.nsym = F.nsym; E.frame = -1;
+            Ht40Event E; E.capture_id = S.h_caps[c].capture_id; E.end_sample = F.end_sample; E.error_code = F.error_code; E.mcs = F.mcs & ~SORA_HT40_SHORT_GI; E.length = F.ht_len;
+                E.nsym = F.nsym; E.frame = -1; E.short_gi = (F.mcs & SORA_HT40_SHORT_GI) != 0;
             E.truncated = (i + 1 == mf && S.h_nfr[c] > mf);
             if (F.error_code == 0) E.frame = (int)nf++;                            // (the order k_ht40_plan numbers the frames in)
             S.events.push_back(E);
@@ -691,7 +733,8 @@ static int ht40_slot_results(sora_ht40_t* rx, Ht40Slot& S, sora_frame_result* ou
                 if (n >= max_out) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_results: output buffer too small", 0);
                 sora_frame_result& o = out[n++];
                 memset(&o, 0, sizeof(o));
-                o.capture_id = E.capture_id; o.end_sample = E.end_sample; o.error_code = E.error_code; o.flags = E.truncated ? SORA_ROW_TRUNCATED : 0;
+                o.capture_id = E.capture_id; o.end_sample = E.end_sample; o.error_code = E.error_code;
+                o.flags = (uint16_t)((E.truncated ? SORA_ROW_TRUNCATED : 0u) | (E.short_gi ? SORA_ROW_SHORT_GI : 0u));
                     o.mpdu_offset = (uint32_t)moff;
                 if (E.frame >= 0) {
                     const Rx11bRow& r = rows[jpf * (size_t)E.frame + k];
@@ -722,7 +765,8 @@ static int ht40_slot_results(sora_ht40_t* rx, Ht40Slot& S, sora_frame_result* ou
         memset(&o, 0, sizeof(o));
         const sora_ht40_frame& f = S.h_frames[j / jpf];
         o.capture_id = f.frame_id; o.start_sample = (uint32_t)(j % jpf);                               // start_sample carries the spatial stream (joint coding: 0)
-        o.error_code = rows[j].error_code; o.length = (uint16_t)rows[j].length; o.crc32 = rows[j].crc32; o.rate_kbps = f.n_bpsc * 10 + f.code_rate;
+        o.error_code = rows[j].error_code; o.length = (uint16_t)rows[j].length; o.crc32 = rows[j].crc32; o.rate_kbps = f.n_bpsc * 10 + ht40_frame_cr(f);
+        o.flags = ht40_frame_short(f) ? SORA_ROW_SHORT_GI : 0;
         o.nsym = (uint16_t)ht40_frame_symbols(f, S.joint);
         o.mpdu_offset = (uint32_t)moff;
         if (h_mpdu) {
@@ -784,8 +828,8 @@ int sora_ht40_deliver_async(sora_ht40_t* rx, int ticket, sora_frame_result* h_ro
     for (size_t j = 0; j < S->h_tmpl.size(); j++) {                             // (the same fields sora_ht40_results fills in on the host)
         sora_frame_result& o = S->h_tmpl[j]; const sora_ht40_frame& f = S->h_frames[j / jpf];
         memset(&o, 0, sizeof(o));
-        o.capture_id = f.frame_id; o.start_sample = (uint32_t)(j % jpf); o.rate_kbps = f.n_bpsc * 10 + f.code_rate;
-        o.nsym = (uint16_t)ht40_frame_symbols(f, S->joint);
+        o.capture_id = f.frame_id; o.start_sample = (uint32_t)(j % jpf); o.rate_kbps = f.n_bpsc * 10 + ht40_frame_cr(f);
+        o.nsym = (uint16_t)ht40_frame_symbols(f, S->joint); o.flags = ht40_frame_short(f) ? SORA_ROW_SHORT_GI : 0;
     }
     // two rows per frame, always (one in joint coding): "captures" = frames, max_frames_per_capture = 2 (1), no per-capture counts.  (The template is read by an
     // asynchronous copy: it lives in the slot until the slot's next call.)

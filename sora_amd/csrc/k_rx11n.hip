@@ -89,6 +89,7 @@ struct Scan11nArgs {
     // sora_rx11n_set_mcs_max: the highest MCS the SIG parser accepts (10 = PHY_11n.hpp:497), and the handle's bytes per symbol slot (soft values / decoded bytes)
     uint32_t  mcs_max, soft_per_slot, out_per_slot;
     uint32_t  joint;               // HT40 only: 1 = the handle's coding is the joint one (sora_ht40_set_coding): a frame's N_DBPS spans both streams
+    uint32_t  guard;               // HT40 only: 1 = SORA_HT40_GUARD_SIGNALLED (sora_ht40_set_guard): the host launches the forms that read HT-SIG's Short GI bit
 };
 // A symbol slot of the 802.11n handle: kSoftPerSlot / kOutPerSlot (rx_types.h) while the gate stands at MCS 10 (208 soft values, 19.5 decoded bytes per symbol at
 // most); with the gate raised a symbol brings up to 624 soft values and 58.5 decoded bytes (MCS 14)
@@ -155,7 +156,10 @@ constexpr uint32_t kRec11nMagic = 0x534F314Eu;     // a continuation record hold
 //     copy per detection and nothing per block, and it is exact: nothing but the block's writes moved the rings since the block started;
 //   * the record is written once, at the end of the capture, from the rings or their copy (a zero-length capture leaves it as it was).
 // Every addition sits under "if constexpr (STREAM)": the default kernels are the instruction stream they were.
-template <bool HT40, bool STREAM = false>
+// GI = true (HT40 only: k_scan_ht40_gi / k_scan_ht40_stream_gi, launched for a handle in SORA_HT40_GUARD_SIGNALLED): HT-SIG bit 31 (Short GI) of a
+// sound header is read; a frame that sets it has data symbols of 72 samples at 20 MHz and its record carries SORA_HT40_SHORT_GI on the MCS.  With the bit clear, and in the
+// forms without GI, nothing differs.
+template <bool HT40, bool STREAM = false, bool GI = false>
 __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* found, uint32_t* cont = nullptr, uint32_t* consumed = nullptr)
 {
     __shared__ ScanLds s_w[4];
@@ -379,6 +383,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
         wave_lds_sync();
         // ================================================================ the SIG field: three symbols, theta = 0 (no pilot tracking before the data field)
         uint32_t err = 0, mcs = 0, ht_len = 0, code_rate = 0;
+        [[maybe_unused]] uint32_t sgi = 0;                                   // GI: HT-SIG bit 31 of a header that passed the gate
         bool sig_ok = false, decoded = false;
         uint32_t a = l0 + 128;
         int nsig = 0;
@@ -431,7 +436,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
             // the gate.  HT40: two streams, 40 MHz, a rate this library has a decoder for; else mcs_max (10: the reference's ht_frame_mcs >= 11) and 1500 bytes
             if (HT40) sig_ok = P.ok && P.mcs >= 8 && P.mcs <= 14 && P.cbw40 && P.ht_len <= 4000 && P.ht_len >= 4;
             else sig_ok = P.ok && P.mcs >= 8 && P.mcs <= A.mcs_max && P.ht_len <= 1500;
-            if (sig_ok) { mcs = P.mcs; ht_len = P.ht_len; code_rate = code_rate11n(P.mcs); }
+            if (sig_ok) { mcs = P.mcs; ht_len = P.ht_len; code_rate = code_rate11n(P.mcs); if constexpr (GI) sgi = (uint32_t)(ht >> 31) & 1u; }
             else err = E_PLCP_HEADER_FAIL;
         }
         // ================================================================ what happens to the frame, without looking at its data field
@@ -445,6 +450,14 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
             const uint32_t ndbps = ht40_ndbps(nbpsc11n(mcs), code_rate) << A.joint;
             const uint32_t nsym = (16u + 8u * ht_len + 6u + ndbps - 1u) / ndbps;
             nproc = nsym;
+            if constexpr (GI) {
+                // (Short GI: data symbol d at a + 240 + 72 d, 3.6 us symbols)
+                const uint32_t end = a + 240 + (sgi ? 72u : 80u) * nsym;
+                // (stream form: a short frame is taken when the kHt40ShortAdvance samples k_ht40_plan moves its data field by lie inside the piece too, so that every
+                // cut of a stream gives the one-call result; else the next call finds it)
+                if (end + ((STREAM && sgi) ? kHt40ShortAdvance / 2u : 0u) <= n_real) { event = true; queue = true; last_burst_end = end; }
+            }
+            else
             if (a + 240 + 80 * nsym <= n_real) { event = true; queue = true; last_burst_end = a + 240 + 80 * nsym; }
         }
         else if (decoded && !at_end) {
@@ -482,6 +495,7 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
                 rows[nfr] = r;
                 if (HT40) {
                     Ht40Found F; F.a20 = origin + a; F.mcs = queue ? mcs : 0u; F.ht_len = queue ? ht_len : 0u; F.cfo = cfo; F.noise_var = noise_var;
+                    if constexpr (GI) { if (queue && sgi) F.mcs |= SORA_HT40_SHORT_GI; }
                     F.end_sample = 2 * next; F.error_code = queue ? 0u : err; F.nsym = queue ? nproc : 0u;
                     found[row] = F;
                 } else if (queue) {
@@ -536,17 +550,25 @@ __global__ void __launch_bounds__(256) k_scan_ht40(Scan11nArgs A, Ht40Found* fou
 // its stream form (sora_ht40_set_stream_mode): the records and resume points of k_scan11n_stream (kRec11nWords, 40 MHz samples); a20 and end_sample of the
 // Ht40Found records stay relative to the capture, so what follows the scan (k_ht40_plan, the data field's kernels) is the same in both modes
 __global__ void __launch_bounds__(256) k_scan_ht40_stream(Scan11nArgs A, Ht40Found* found, uint32_t* cont, uint32_t* consumed) { scan11n_body<true, true>(A, found, cont, consumed); }
+// the two forms of a handle in SORA_HT40_GUARD_SIGNALLED (sora_ht40_set_guard): HT-SIG's Short GI bit decides a frame's extent
+__global__ void __launch_bounds__(256) k_scan_ht40_gi(Scan11nArgs A, Ht40Found* found) { scan11n_body<true, false, true>(A, found); }
+__global__ void __launch_bounds__(256) k_scan_ht40_stream_gi(Scan11nArgs A, Ht40Found* found, uint32_t* cont, uint32_t* consumed) { scan11n_body<true, true, true>(A, found, cont, consumed); }
 
 }  // namespace sora
 int sora_internal_scan_ht40(const uint32_t* iq0, const uint32_t* iq1, const sora::CapDesc* d_caps, uint32_t ncaps, uint32_t max_frames, sora::Rx11bRow* d_rows, uint32_t* d_nframes,
                             sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st, uint32_t* d_cont, uint32_t* d_consumed,
-                            uint32_t joint)
+                            uint32_t joint, uint32_t guard)
 {
     using namespace sora;
     Scan11nArgs S{};
     S.iq0 = iq0; S.iq1 = iq1; S.caps = d_caps; S.ncaps = ncaps; S.max_frames = max_frames; S.rows = d_rows; S.nframes = d_nframes; S.T = T; S.sincos = sincos; S.atan = atan;
     S.frames = nullptr; S.jobs = nullptr; S.njobs = nullptr; S.nrows = ncaps * max_frames;
-    S.mcs_max = 14; S.soft_per_slot = 0; S.out_per_slot = 0; S.joint = joint;                     // (the HT40 form has its own gate and queues no 20 MHz data field)
+    S.mcs_max = 14; S.soft_per_slot = 0; S.out_per_slot = 0; S.joint = joint; S.guard = guard;    // (the HT40 form has its own gate and queues no 20 MHz data field)
+    if (guard) {
+        if (d_cont) hipLaunchKernelGGL(k_scan_ht40_stream_gi, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found, d_cont, d_consumed);
+        else hipLaunchKernelGGL(k_scan_ht40_gi, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found);
+    }
+    else
     if (d_cont) hipLaunchKernelGGL(k_scan_ht40_stream, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found, d_cont, d_consumed);
     else hipLaunchKernelGGL(k_scan_ht40, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found);
     const hipError_t e = hipGetLastError();
@@ -936,7 +958,7 @@ int sora_rx11n_process_dev(sora_rx11n_t* rx, const sora_complex16* d_iq0, const 
     Scan11nArgs S;
     S.iq0 = A.iq0; S.iq1 = A.iq1; S.caps = P->d_caps; S.ncaps = (uint32_t)ncaps; S.max_frames = A.max_frames; S.rows = P->d_rows; S.nframes = P->d_nframes;
     S.T = rx->T; S.sincos = rx->sincos; S.atan = rx->atan; S.frames = P->d_frames; S.jobs = P->d_jobs; S.njobs = P->d_njobs; S.nrows = nrows;
-    S.mcs_max = (uint32_t)rx->mcs_max; S.soft_per_slot = rx->soft_per_slot; S.out_per_slot = rx->out_per_slot; S.joint = 0;
+    S.mcs_max = (uint32_t)rx->mcs_max; S.soft_per_slot = rx->soft_per_slot; S.out_per_slot = rx->out_per_slot; S.joint = 0; S.guard = 0;
     if (rx->records.on) hipLaunchKernelGGL(k_scan11n_stream, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S, rx->records.d_cont, rx->records.d_consumed);
     else hipLaunchKernelGGL(k_scan11n, dim3((unsigned)((ncaps + 3) / 4)), dim3(256), 0, P->stream, S);
     Frame11nArgs F;

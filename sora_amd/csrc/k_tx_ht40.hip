@@ -9,7 +9,7 @@
 //   * L-STF, L-LTF, L-SIG, HT-SIG and HT-STF are the 20 MHz legacy spectrum on both halves of the channel (carrier k at bins k - 32 and,
 //     times j, k + 32), identical on both chains, no cyclic shifts; HT-LTFs with P = [[1, -1], [1, 1]]; each spatial stream has its
 //     own scrambler seed, K = 7 encoder, puncturing and HT interleaver (N_COL 18, N_ROW 6 N_BPSC, N_ROT 29) and goes out on its own chain.
-// Frame: L-STF 320, L-LTF 320, L-SIG 160, HT-SIG 2 x 160, HT-STF 160, HT-LTF 2 x 160, data nsym x 160 samples per chain.
+// Frame: L-STF 320, L-LTF 320, L-SIG 160, HT-SIG 2 x 160, HT-STF 160, HT-LTF 2 x 160, data nsym x 160 samples per chain (short guard interval, k_tx_ht40_gi: nsym x 144).
 // One 256-thread block per frame: both streams' scrambled fields and generator words in LDS; eight 32-lane groups, group g carries
 // stream g & 1 of data symbol 4 p + g / 2 in pass p.  FCS, scrambler, encoder, puncturing, mapper, SIG stream, IFFT and emission are dev_tx.h's pieces.
 // LDS layout: the symbol buffers are swizzled (fft128_swz, dev_arith.h) so that no stage of the IFFT, the 16-byte terminal stage and the
@@ -83,7 +83,10 @@ __global__ void __launch_bounds__(128) k_tx_ht40_preamble(uint32_t* tab, Tables 
     }
 }
 
-template <bool JOINT>
+// GI = true (k_tx_ht40_gi, k_tx_ht40_joint_gi; sora_hip_tx_ht40_gi): the frame's guard-interval kind A.gi[f] is read once, is block-uniform and
+// selects the data symbols' pitch and emission (160 / tx_emit160 or 144 / tx_emit144), HT-SIG bit 31 and the L-SIG length; a kind other than 0 / 1 is a frame that is not
+// accepted.  Every addition sits under "if constexpr (GI)": the kernels without it are the instruction streams they were.
+template <bool JOINT, bool GI = false>
 __device__ __forceinline__ void tx_ht40_body(const TxHt40Args& A)
 {
     __shared__ alignas(16) uint8_t s_data[2][kBytes];
@@ -100,6 +103,8 @@ __device__ __forceinline__ void tx_ht40_body(const TxHt40Args& A)
     const uint32_t L = A.len[f], mcs = A.mcs[f];
     TxHt40Plan P;
     if (!(JOINT ? tx_ht40_plan_joint(L, mcs, P) : tx_ht40_plan(L, mcs, P))) return;   // a frame that is not accepted: nothing is written
+    [[maybe_unused]] uint32_t sgi = 0;
+    if constexpr (GI) { sgi = A.gi ? (uint32_t)A.gi[f] : 0u; if (sgi > 1u) return; }
     const int nb = P.nb, nd = P.ndbps;
     const uint32_t nsym = P.nsym;
     const uint32_t nw = (nsym * (uint32_t)nd + 31) / 32;                         // generator words the data symbols read, per stream (joint: of the one field)
@@ -184,7 +189,9 @@ __device__ __forceinline__ void tx_ht40_body(const TxHt40Args& A)
     // bits through the legacy interleaver (coded bit k at position 3 (k mod 16) + k div 16), L-SIG on I, HT-SIG on Q, pilots 1, 1, 1, -1
     if (g < 4) {                                                                 // waves 0 and 1: groups 0..2 carry the three symbols
         // L-SIG LENGTH: the legacy duration that spans the HT frame; HT-SIG: MCS, CBW 40, LENGTH, smoothing, not sounding, reserved
-        const TxSig72 sig = tx_sig72(12u + 3u * nsym, (mcs & 0x7Fu) | (1u << 7) | (((L + 4) & 0xFFFFu) << 8) | (7u << 24));
+        TxSig72 sig;
+        if constexpr (GI) sig = tx_sig72(tx_ht40_lsig_length(nsym, sgi), (mcs & 0x7Fu) | (1u << 7) | (((L + 4) & 0xFFFFu) << 8) | (7u << 24) | (sgi << 31));   // bit 31: Short GI
+        else sig = tx_sig72(12u + 3u * nsym, (mcs & 0x7Fu) | (1u << 7) | (((L + 4) & 0xFFFFu) << 8) | (7u << 24));
         const int s = g;
         for (int i = e; i < 128; i += 32) bins[i] = 0;
         if (s < 3) {
@@ -243,11 +250,18 @@ __device__ __forceinline__ void tx_ht40_body(const TxHt40Args& A)
             }
         }
         tx_ifft128<true>(bins, e, tw);
+        if constexpr (GI) {
+            if (sgi) tx_emit144<true>(bins, e, out + 1600 + kHt40ShortSym * (size_t)s);
+            else tx_emit160<true>(bins, e, out + 1600 + 160 * (size_t)s, 0);
+        }
+        else
         tx_emit160<true>(bins, e, out + 1600 + 160 * (size_t)s, 0);
         wave_lds_sync();
     }
 }
 __global__ void __launch_bounds__(256) k_tx_ht40(TxHt40Args A) { tx_ht40_body<false>(A); }
 __global__ void __launch_bounds__(256) k_tx_ht40_joint(TxHt40Args A) { tx_ht40_body<true>(A); }
+__global__ void __launch_bounds__(256) k_tx_ht40_gi(TxHt40Args A) { tx_ht40_body<false, true>(A); }
+__global__ void __launch_bounds__(256) k_tx_ht40_joint_gi(TxHt40Args A) { tx_ht40_body<true, true>(A); }
 
 }  // namespace sora

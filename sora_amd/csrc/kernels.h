@@ -192,6 +192,7 @@ struct TxHt40Args {            // sora_hip_tx_ht40; sora_hip_tx_ht40_joint: ONE 
     const uint64_t* out_off;   // first sample of frame f in both streams
     const uint32_t* preamble;  // [2][1120]: per chain L-STF, L-LTF (640) then HT-STF, HT-LTF1, HT-LTF2 (480), k_tx_ht40_preamble
     Tables          T;
+    const uint8_t*  gi;        // per frame: 0 = long guard interval, 1 = short; nullptr: all long.  Read by k_tx_ht40_gi / k_tx_ht40_joint_gi only (sora_hip_tx_ht40_gi)
 };
 // N_SYM = ceil((16 + 8 (len + 4) + 6) / N_DBPS) with N_DBPS = 108 N_BPSC R: sora_ht40_symbols(len + 4, len + 4, nb, cr), py_ht40.nsym_for
 struct TxHt40Plan { int nb, cr, ndbps; uint32_t nsym; };
@@ -221,6 +222,16 @@ constexpr int kTxHt40Amp = 16384;                        // A: the bin value of 
 __global__ void k_tx_ht40_preamble(uint32_t* tab, Tables T);
 __global__ void k_tx_ht40(TxHt40Args A);
 __global__ void k_tx_ht40_joint(TxHt40Args A);
+// The short guard interval: a frame's kind (TxHt40Args::gi) selects the data symbols' pitch and emission, HT-SIG bit 31 and the L-SIG length.
+// Samples per chain: the fields up to HT-LTF 2 keep their 160-sample symbols; a short data symbol is the last 16 of its 128 samples, then the 128.
+constexpr uint32_t kHt40ShortSym = 144, kHt40ShortCp = 16;
+// raw captures: how much later than a20 says a short-GI frame's data field is taken (k_ht40_plan), and what a stream piece must hold behind the frame's extent for that
+constexpr uint32_t kHt40ShortAdvance = 16;
+__host__ __device__ inline size_t tx_ht40_frame_samples(uint32_t nsym, uint32_t gi) { return 1600u + (size_t)(gi ? kHt40ShortSym : 160u) * nsym; }
+// L-SIG LENGTH = 3 x (the 4 us symbols behind L-SIG, rounded up) - 3: 3 + nsym data symbols of 4 us, or of 3.6 us rounded up to whole 4 us
+__host__ __device__ inline uint32_t tx_ht40_lsig_length(uint32_t nsym, uint32_t gi) { return 12u + 3u * (gi ? (9u * nsym + 9u) / 10u : nsym); }
+__global__ void k_tx_ht40_gi(TxHt40Args A);
+__global__ void k_tx_ht40_joint_gi(TxHt40Args A);
 
 // ---- 802.11b transmitter (k_tx11b.hip)
 struct Tx11bArgs {             // sora_hip_tx11b
@@ -319,9 +330,10 @@ struct Ht40Found {
 
 // d_cont / d_consumed: the streams' continuation records [ncaps][kRec11nWords] and resume points [ncaps] (k_scan_ht40_stream); null = k_scan_ht40
 // joint: 1 = a frame's extent follows the joint coding's N_SYM (sora_ht40_set_coding)
+// guard: 1 = SORA_HT40_GUARD_SIGNALLED (sora_ht40_set_guard): k_scan_ht40_gi / k_scan_ht40_stream_gi, which read HT-SIG's Short GI bit
 int sora_internal_scan_ht40(const uint32_t* iq0, const uint32_t* iq1, const sora::CapDesc* d_caps, uint32_t ncaps, uint32_t max_frames, sora::Rx11bRow* d_rows, uint32_t* d_nframes,
                             sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st,
-                            uint32_t* d_cont = nullptr, uint32_t* d_consumed = nullptr, uint32_t joint = 0);
+                            uint32_t* d_cont = nullptr, uint32_t* d_consumed = nullptr, uint32_t joint = 0, uint32_t guard = 0);
 
 // k_deliver.hip: dense rows + MPDUs of a call of the Rx11bRow-table handles into page-locked host memory, behind the call's kernels
 struct DenseStage {                  // per slot / pipeline (grow-only device staging)

@@ -1706,12 +1706,28 @@ size_t sora_hip_tx_ht40_joint_samples(uint32_t mpdu_len_nofcs, uint32_t mcs)
     return 1280 + 160 * (2 + (size_t)P.nsym);
 }
 
-// both codings: the per-stream one (two MPDUs and two seeds per frame) and the joint one (one of each)
+size_t sora_hip_tx_ht40_gi_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, uint32_t gi)
+{
+    TxHt40Plan P;
+    if (gi > 1 || !tx_ht40_plan(mpdu_len_nofcs, mcs, P)) return 0;
+    return tx_ht40_frame_samples(P.nsym, gi);
+}
+
+size_t sora_hip_tx_ht40_joint_gi_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, uint32_t gi)
+{
+    TxHt40Plan P;
+    if (gi > 1 || !tx_ht40_plan_joint(mpdu_len_nofcs, mcs, P)) return 0;
+    return tx_ht40_frame_samples(P.nsym, gi);
+}
+
+// both codings: the per-stream one (two MPDUs and two seeds per frame) and the joint one (one of each).  guard: the _gi entry points, which launch the kernels that read
+// a guard-interval kind per frame (d_gi; null: every frame long); the entry points without it launch the kernels they always launched
 static int tx_ht40_launch(bool joint, const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
-                          size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
+                          size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream, bool guard = false, const uint8_t* d_gi = nullptr)
 {
     if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-    if (!d_mpdu || !d_off || !d_len || !d_mcs || !d_out0 || !d_out1 || !d_out_off) return fail(SORA_ERR_INVALID_PARAM, joint ? "sora_hip_tx_ht40_joint: null pointer" :
+    if (!d_mpdu || !d_off || !d_len || !d_mcs || !d_out0 || !d_out1 || !d_out_off) return fail(SORA_ERR_INVALID_PARAM,
+            guard ? (joint ? "sora_hip_tx_ht40_joint_gi: null pointer" : "sora_hip_tx_ht40_gi: null pointer") : joint ? "sora_hip_tx_ht40_joint: null pointer" :
             "sora_hip_tx_ht40: null pointer");
     if (nframes == 0) return SORA_OK;
     DevTables* D = device_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
@@ -1733,8 +1749,9 @@ static int tx_ht40_launch(bool joint, const uint8_t* d_mpdu, const uint32_t* d_o
     TxHt40Args A{};
     A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.mcs = d_mcs; A.seed = d_seed;
     A.out0 = reinterpret_cast<uint32_t*>(d_out0); A.out1 = reinterpret_cast<uint32_t*>(d_out1); A.out_off = d_out_off;
-    A.preamble = D->tx_ht40_preamble; A.T = D->T;
-    hipLaunchKernelGGL(joint ? k_tx_ht40_joint : k_tx_ht40, dim3((unsigned)nframes), dim3(256), 0, st, A);
+    A.preamble = D->tx_ht40_preamble; A.T = D->T; A.gi = d_gi;
+    if (guard) hipLaunchKernelGGL(joint ? k_tx_ht40_joint_gi : k_tx_ht40_gi, dim3((unsigned)nframes), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(joint ? k_tx_ht40_joint : k_tx_ht40, dim3((unsigned)nframes), dim3(256), 0, st, A);
     HIPCHK(hipGetLastError());
     return SORA_OK;
 }
@@ -1747,6 +1764,16 @@ int sora_hip_tx_ht40_joint(const uint8_t* d_mpdu, const uint32_t* d_off, const u
                            size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
 {
     return tx_ht40_launch(true, d_mpdu, d_off, d_len, d_mcs, d_seed, nframes, d_out0, d_out1, d_out_off, stream);
+}
+int sora_hip_tx_ht40_gi(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed, const uint8_t* d_gi,
+                        size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
+{
+    return tx_ht40_launch(false, d_mpdu, d_off, d_len, d_mcs, d_seed, nframes, d_out0, d_out1, d_out_off, stream, true, d_gi);
+}
+int sora_hip_tx_ht40_joint_gi(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed, const uint8_t* d_gi,
+                              size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
+{
+    return tx_ht40_launch(true, d_mpdu, d_off, d_len, d_mcs, d_seed, nframes, d_out0, d_out1, d_out_off, stream, true, d_gi);
 }
 
 // ---- 802.11b transmitter
