@@ -762,6 +762,96 @@ struct THipHt40NoiseVar : THipStage<sora_complex16, 256, float, 1, CallNoiseVarH
 };
 // (sora_hip_downsample_ht40 has no fixed ratio per call -- a stream's parity runs on from call to call -- and stays a plain entry point.)
 
+// ------------------------------------------------------------------------------------------------
+// The bricks of the 40 MHz HT 2x2 modulation graph (include/sora_hip.h: the sora_hip_*_ht40 stages behind sora_hip_tx_ht40) beyond the 802.11a ones above (the
+// scrambler, the encoder and the SIG symbols' BPSK interleaver are THip11aSc, THipConvEncode and THip11aInterleave<1>).  One burst = N symbols; kRowHt40 = N_b40
+// bytes per stream and symbol.  The preamble source (sora_hip_preamble_ht40) and the stream-form interleaver (sora_hip_interleave_ht40_stream: frame tables, bit
+// addresses) have no fixed ratio per burst and stay plain entry points.
+constexpr size_t kRowHt40(int n_bpsc) { return (size_t)(108 * n_bpsc + 7) / 8; }
+
+// the stream parser: IPORT uchar x 27 N_BPSC -> OPORTS 0 and 1 uchar x N_b40, a demux: Next0 and Next1 take the two spatial streams
+template <int N_BPSC, size_t N, class T_CTX, class T_NEXT0, class T_NEXT1>
+class THipHt40StreamParser {
+public:
+    using iport_traits = port_traits<uint8_t, 27 * N_BPSC * N>;
+    using oport_traits = port_traits<uint8_t, kRowHt40(N_BPSC) * N>;
+    THipHt40StreamParser(T_CTX& ctx, T_NEXT0* next0, T_NEXT1* next1, uint8_t* d_out0, uint8_t* d_out1, void* stream = nullptr)
+        : ctx_(ctx), next0_(next0), next1_(next1), opin0_(d_out0), opin1_(d_out1), stream_(stream) {}
+    void Reset() { if (next0_) next0_->Reset(); if (next1_) next1_->Reset(); }
+    void Flush() { if (next0_) next0_->Flush(); if (next1_) next1_->Flush(); }
+    template <class T_IPIN> bool Process(T_IPIN& ipin)
+    {
+        while (ipin.check_read()) {
+            uint8_t* out0 = opin0_.append(); uint8_t* out1 = opin1_.append();
+            const int rc = sora_hip_stream_parse_ht40(ipin.peek(), out0, out1, N_BPSC, N, stream_);
+            if (rc != SORA_OK) { ctx_.error_code = (uint32_t)rc; return false; }
+            ipin.pop();
+            if (next0_ && !next0_->Process(opin0_)) return false;
+            if (next1_ && !next1_->Process(opin1_)) return false;
+        }
+        return true;
+    }
+    DevicePin<uint8_t, kRowHt40(N_BPSC) * N>& opin0() { return opin0_; }
+    DevicePin<uint8_t, kRowHt40(N_BPSC) * N>& opin1() { return opin1_; }
+private:
+    T_CTX& ctx_; T_NEXT0* next0_; T_NEXT1* next1_; DevicePin<uint8_t, kRowHt40(N_BPSC) * N> opin0_, opin1_; void* stream_;
+};
+// the HT interleaver for 40 MHz, SPATIAL_STREAM 0 / 1: IPORT uchar x N_b40 -> OPORT uchar x N_b40
+struct CallInterleaveHt40 { int nb, ss; size_t n; int operator()(const uint8_t* in, uint8_t* out, void* st) const
+    { return sora_hip_interleave_ht40(in, out, nb, ss, n, st); } };
+template <int N_BPSC, int SPATIAL_STREAM, size_t N, class T_CTX, class T_NEXT>
+struct THipHt40Interleave : THipStage<uint8_t, kRowHt40(N_BPSC) * N, uint8_t, kRowHt40(N_BPSC) * N, CallInterleaveHt40, T_CTX, T_NEXT> {
+    THipHt40Interleave(T_CTX& ctx, T_NEXT* next, uint8_t* d_out, void* stream = nullptr)
+        : THipStage<uint8_t, kRowHt40(N_BPSC) * N, uint8_t, kRowHt40(N_BPSC) * N, CallInterleaveHt40, T_CTX, T_NEXT>(ctx, next, d_out,
+              CallInterleaveHt40{ N_BPSC, SPATIAL_STREAM, N }, stream) {}
+};
+// the mapper: IPORT uchar x N_b40 -> OPORT COMPLEX16 x 108
+struct CallMapHt40 { int nb; size_t n; int operator()(const uint8_t* in, sora_complex16* out, void* st) const { return sora_hip_map_ht40(in, out, nb, n, st); } };
+template <int N_BPSC, size_t N, class T_CTX, class T_NEXT>
+struct THipHt40Map : THipStage<uint8_t, kRowHt40(N_BPSC) * N, sora_complex16, 108 * N, CallMapHt40, T_CTX, T_NEXT> {
+    THipHt40Map(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* stream = nullptr)
+        : THipStage<uint8_t, kRowHt40(N_BPSC) * N, sora_complex16, 108 * N, CallMapHt40, T_CTX, T_NEXT>(ctx, next, d_out, CallMapHt40{ N_BPSC, N }, stream) {}
+};
+// L-SIG + HT-SIG: IPORT uchar x 18 -> OPORT COMPLEX16 x 3 x 128, N frames per burst
+struct CallSigMapHt40 { size_t n; int operator()(const uint8_t* in, sora_complex16* out, void* st) const { return sora_hip_sig_map_ht40(in, out, n, st); } };
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipHt40SigMap : THipStage<uint8_t, 18 * N, sora_complex16, 384 * N, CallSigMapHt40, T_CTX, T_NEXT> {
+    THipHt40SigMap(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* stream = nullptr)
+        : THipStage<uint8_t, 18 * N, sora_complex16, 384 * N, CallSigMapHt40, T_CTX, T_NEXT>(ctx, next, d_out, CallSigMapHt40{ N }, stream) {}
+};
+// data carriers and pilots onto the 128 bins: IPORT COMPLEX16 x 108 -> OPORT COMPLEX16 x 128; the pilots do not depend on the symbol's place in its frame, so every
+// burst is one frame of N symbols.  d_tab: 16 bytes of device memory for the call's frame table.
+struct CallAddPilotHt40 {
+    uint32_t* d_tab; size_t n;
+    int operator()(const sora_complex16* in, sora_complex16* out, void* st) const
+    {
+        const uint32_t tab[4] = { 0u, (uint32_t)n, 0u, 0u };                                       // first, nsym
+        if (sora_hip_memcpy_h2d(d_tab, tab, sizeof(tab)) != SORA_OK) return SORA_ERR_HARDWARE_FAILED;
+        return sora_hip_add_pilot_ht40(in, out, d_tab, d_tab + 1, 1, st);
+    }
+};
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipHt40AddPilot : THipStage<sora_complex16, 108 * N, sora_complex16, 128 * N, CallAddPilotHt40, T_CTX, T_NEXT> {
+    THipHt40AddPilot(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* d_tab, void* stream = nullptr)
+        : THipStage<sora_complex16, 108 * N, sora_complex16, 128 * N, CallAddPilotHt40, T_CTX, T_NEXT>(ctx, next, d_out,
+              CallAddPilotHt40{ static_cast<uint32_t*>(d_tab), N }, stream) {}
+};
+// the fixed-point IFFT<128>, natural order: IPORT COMPLEX16 x 128 -> OPORT COMPLEX16 x 128
+struct CallIFFTHt40 { size_t n; int operator()(const sora_complex16* in, sora_complex16* out, void* st) const { return sora_hip_ifft_ht40(in, out, n, st); } };
+template <size_t N, class T_CTX, class T_NEXT>
+struct THipHt40IFFT : THipStage<sora_complex16, 128 * N, sora_complex16, 128 * N, CallIFFTHt40, T_CTX, T_NEXT> {
+    THipHt40IFFT(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* stream = nullptr)
+        : THipStage<sora_complex16, 128 * N, sora_complex16, 128 * N, CallIFFTHt40, T_CTX, T_NEXT>(ctx, next, d_out, CallIFFTHt40{ N }, stream) {}
+};
+// the guard interval, GI 0 (long) / 1 (short): IPORT COMPLEX16 x 128 -> OPORT COMPLEX16 x 160 / 144
+struct CallAddGIHt40 { int gi; size_t n; int operator()(const sora_complex16* in, sora_complex16* out, void* st) const { return sora_hip_add_gi_ht40(in, out, gi, n, st); } };
+template <int GI, size_t N, class T_CTX, class T_NEXT>
+struct THipHt40AddGI : THipStage<sora_complex16, 128 * N, sora_complex16, (GI ? 144 : 160) * N, CallAddGIHt40, T_CTX, T_NEXT> {
+    static_assert(GI == 0 || GI == 1, "0 = long, 1 = short");
+    THipHt40AddGI(T_CTX& ctx, T_NEXT* next, sora_complex16* d_out, void* stream = nullptr)
+        : THipStage<sora_complex16, 128 * N, sora_complex16, (GI ? 144 : 160) * N, CallAddGIHt40, T_CTX, T_NEXT>(ctx, next, d_out, CallAddGIHt40{ GI, N }, stream) {}
+};
+
 
 // ------------------------------------------------------------------------------------------------
 // The bricks that complete the 802.11n receive graph (kernel/bb/demod11/fb11ndemod_config.hpp:166-264), each where its SSE brick sits.  The bricks with NSTREAM = 2 ports

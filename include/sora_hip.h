@@ -45,7 +45,8 @@ extern "C" {
  * _pilot_track_ht40, _demap_ht40, _deinterleave_ht40, _stream_join_ht40, _downsample_ht40, _noise_var_ht40; the bricks that complete the 802.11n receive graph -- sora_hip_cca11n
  * (sora_cca11n_state), _data_symbol11n, _stream_join11n, and the tail it shares with the 802.11a graph, sora_hip_desc11a, _frame_sink11a (sora_sink11a_rec); the front end
  * of the 802.11a receive graph -- sora_hip_dc_remove11a, _dc_estimate11a (sora_dcest11a_state), _cca11a (sora_cca11a_state), _carrier_sense11a (sora_cs11a_state),
- * _data_symbol11a, _viterbi_sig11a, _plcp_parse11a (sora_plcp11a_rec). */
+ * _data_symbol11a, _viterbi_sig11a, _plcp_parse11a (sora_plcp11a_rec); the 40 MHz HT modulation graph's bricks -- sora_hip_stream_parse_ht40, _interleave_ht40,
+ * _interleave_ht40_stream, _map_ht40, _sig_map_ht40, _add_pilot_ht40, _ifft_ht40, _add_gi_ht40, _preamble_ht40. */
 #define SORA_HIP_ABI_VERSION 4
 
 /* COMPLEX16: kernel/core/inc/complex.h */
@@ -602,6 +603,54 @@ int sora_hip_tx_ht40_gi(const uint8_t* d_mpdu, const uint32_t* d_off, const uint
 size_t sora_hip_tx_ht40_joint_gi_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, uint32_t gi);
 int sora_hip_tx_ht40_joint_gi(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed, const uint8_t* d_gi,
                               size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The bricks of the 40 MHz HT 2x2 modulation graph as stage entry points: what sora_hip_tx_ht40, _joint and _gi fuse, brick by brick, so that a host can replace ONE
+ * brick, put its own between two of them, or pair the transmit bricks with the receive stages sora_hip_demap_ht40, _deinterleave_ht40 and _stream_join_ht40:
+ *     preamble_ht40(0)
+ *     SIG:  conv_encode11a (1/2) -> interleave11a (BPSK) -> sig_map_ht40 -> ifft_ht40 -> add_gi_ht40 (long); the same samples on both chains
+ *     preamble_ht40(1)
+ *     data, per-stream coding:  scramble11a -> conv_encode11a -> interleave_ht40_stream (iss) -> map_ht40 -> add_pilot_ht40 -> ifft_ht40 -> add_gi_ht40 (gi)
+ *     data, joint coding:       scramble11a -> conv_encode11a -> stream_parse_ht40 -> interleave_ht40 (iss) -> map_ht40 -> add_pilot_ht40 -> ifft_ht40 -> add_gi_ht40 (gi)
+ * The scrambler, the encoder and the SIG symbols' interleaver are the 802.11a stages above.  The scrambler's register for the transmitter's seed s (seven bits, bit i of
+ * s = x[-1 - i], py_ht40.scramble_seq) is d_seed = bit-reversed-7(s) << 1; its TAIL_SCRAMBLE byte is the tail rule (the six tail bits start a byte).  The source of the
+ * fields -- the 9 SIG bytes with the HT-SIG CRC-8, SERVICE + PSDU + FCS + tail + pad -- is the host's (sora_amd.mod_ht40_fields).
+ * PARITY UNPINNED, as for the transmitter: the reference has no 40 MHz graph.  Each brick is defined by the project's integer model (tests/mod_ht40_model.py, from
+ * tests/tx_ht40_model.py, ht40_joint_model.py and tx_ht40_gi_model.py) and is exact against it and against the fused kernels.
+ * N_b40 = ceil(108 n_bpsc / 8) = 14, 27, 54, 81 bytes per stream and symbol; bits are packed LSB first, rows lie back to back, unpadded; the upper half of BPSK's 14th
+ * byte is 0.  The conventions are those of the stage blocks above: device pointers, stream order, no allocation, no host wait; a null pointer or a symbol buffer that is
+ * not 16-byte aligned gives SORA_ERR_INVALID_PARAM, a count of 0 is SORA_OK and launches nothing, no device SORA_ERR_NO_DEVICE; a bad n_bpsc, spatial_stream, gi or field
+ * is refused before the count is looked at, as by the receive stages of this graph.  Symbols that no frame owns are not written.  DESIGN.md section 7, g2b.
+ * ------------------------------------------------------------------------------------------------ */
+/* The stream parser on the 216 n_bpsc coded bits of a symbol: IPORT uchar x 27 n_bpsc -> OPORTS 0 and 1 uchar x N_b40 per symbol.  With s = max(1, n_bpsc / 2), coded bit k
+ * goes to stream (k / s) & 1 as its bit (k / 2s) s + k % s (sora_hip_stream_parse11n's rule, the inverse of sora_hip_stream_join_ht40). */
+int sora_hip_stream_parse_ht40(const uint8_t* d_in, uint8_t* d_out0, uint8_t* d_out1, int n_bpsc, size_t nsym, void* stream);
+/* The HT interleaver for 40 MHz (N_COL 18, N_ROW 6 n_bpsc, N_ROT 29): uchar x N_b40 -> uchar x N_b40 per symbol; the inverse of sora_hip_deinterleave_ht40's index map.
+ * Input bit k < 108 n_bpsc of a row goes to bit r(k); BPSK's input bits 108..111 are not read. */
+int sora_hip_interleave_ht40(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, int spatial_stream, size_t nsym, void* stream);
+/* The same map reading by bit address, which is what lets sora_hip_conv_encode11a's output feed the per-stream chain: frame f's coded stream begins at byte d_in_off[f] of
+ * d_in (no alignment asked); symbol j < d_nsym[f] of the frame reads bits 108 n_bpsc j onward of that stream (at BPSK odd symbols start mid-byte) and writes row
+ * d_first[f] + j of d_out (16-byte aligned, rows of N_b40).  Rows that no frame owns are not written; a frame of 0 symbols writes nothing. */
+int sora_hip_interleave_ht40_stream(const uint8_t* d_in, const uint32_t* d_in_off, const uint32_t* d_first, const uint32_t* d_nsym, uint8_t* d_out, int n_bpsc,
+                                    int spatial_stream, size_t nframes, void* stream);
+/* The mapper: uchar x N_b40 -> COMPLEX16 x 108 per symbol.  Carrier c takes bits c n_bpsc .. of the row, the first half for I and the second for Q, Gray, first bit = sign;
+ * the odd integers times 6144, 6144, 4000, 2214 (n_bpsc 1, 2, 4, 6); BPSK on I alone. */
+int sora_hip_map_ht40(const uint8_t* d_in, sora_complex16* d_out, int n_bpsc, size_t nsym, void* stream);
+/* L-SIG and HT-SIG: uchar x 18 per frame (three interleaved BPSK symbols of 48 bits) -> COMPLEX16 x 3 x 128 bins per frame, complete: the 48 carriers +-16384 (L-SIG on I,
+ * HT-SIG 1 and 2 on Q) and the pilots +, +, +, - x 16384 on I at legacy carriers -21, -7, 7, 21, all on both halves of the channel (carrier k at bin k - 32 and, times j,
+ * at bin k + 32); every other bin 0. */
+int sora_hip_sig_map_ht40(const uint8_t* d_in, sora_complex16* d_out, size_t nframes, void* stream);
+/* COMPLEX16 x 108 -> COMPLEX16 x 128 bins per symbol: data carrier c at its bin (carriers -58..-2, 2..58 without the pilots'), pilots (12288, 0) at carriers +-11, +-25, +-53,
+ * the 14 other bins 0.  Frame f owns symbols d_first[f] .. d_first[f] + d_nsym[f] - 1 (sora_hip_add_pilot11a's tables). */
+int sora_hip_add_pilot_ht40(const sora_complex16* d_in, sora_complex16* d_out, const uint32_t* d_first, const uint32_t* d_nsym, size_t nframes, void* stream);
+/* The reference's fixed-point IFFT<128> of 128 bins in natural order: COMPLEX16 x 128 -> COMPLEX16 x 128 per symbol, no shift, no guard interval, no window */
+int sora_hip_ifft_ht40(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream);
+/* The guard interval: COMPLEX16 x 128 -> x 160 (gi 0: the last 32 samples, then the 128) or x 144 (gi 1: the last 16, then the 128) per symbol.  Any other gi gives
+ * SORA_ERR_INVALID_PARAM. */
+int sora_hip_add_gi_ht40(const sora_complex16* d_in, sora_complex16* d_out, int gi, size_t nsym, void* stream);
+/* The fixed fields sora_hip_tx_ht40 writes, from the same per-device table: field 0 = L-STF, L-LTF (640 COMPLEX16 per chain), field 1 = HT-STF, HT-LTF1, HT-LTF2 (480 per
+ * chain), ncopies times back to back into d_out0 (TX chain 0) and d_out1 (chain 1).  The first call on a device builds the table and waits for it. */
+int sora_hip_preamble_ht40(sora_complex16* d_out0, sora_complex16* d_out1, int field, size_t ncopies, void* stream);
 
 /* 802.11b transmitter: the reference's modulation graph CreateModGraph (kernel/bb/demod11/fb11bmod_config.hpp:28-50) as
  * Test11B_FB_Mod runs it (fb11b_mod.cpp:40-70): long preamble (SYNC, SFD), PLCP header, MPDU + FCS at 1, 2, 5.5 or 11 Mbps, Barker

@@ -19,6 +19,8 @@ from .capi import (Rx, Rx11b, Rx11n, RxHt40, ht40_symbols, HostResults, ROW_DTYP
                    ppdu11b, sc741_11b, dbpsk_spread11b, dqpsk_spread11b, cck5_encode11b, cck11_encode11b, pulse_shape11b, mod11b_by_stages, Mod11bStages,
                    tx11a, tx11a_samples, tx11n, tx11n_samples, tx_ht40, tx_ht40_samples, tx11b, tx11b_samples, INGEST_RXBLOCK, INGEST_RAW14, INGEST_44TO40, INGEST_DECIMATE2,
                    ht40_symbols_joint, HT40_CODING_PER_STREAM, HT40_CODING_JOINT, tx_ht40_joint, tx_ht40_joint_samples,
+                   stream_parse_ht40, interleave_ht40, interleave_ht40_stream, map_ht40, sig_map_ht40, add_pilot_ht40, ifft_ht40, add_gi_ht40, preamble_ht40,
+                   mod_ht40_by_stages, ModHt40Stages, mod_ht40_fields,
                    tx_ht40_gi_samples, tx_ht40_joint_gi_samples, HT40_SHORT_GI, ROW_SHORT_GI, HT40_GUARD_LONG, HT40_GUARD_SIGNALLED,
                    data_symbol_ht40, mimo_est_ht40, mimo_comp_ht40, pilot_track_ht40, demap_ht40, deinterleave_ht40, stream_join_ht40, downsample_ht40, noise_var_ht40,
                    rx_ht40_stages, rx_ht40_by_stages, ht40_frame_symbols, rx_ht40_front_stages, rx_ht40_front_by_stages, ht40_sig_gate,

@@ -85,6 +85,8 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_hip_pulse_shape11b",
            "sora_hip_tx_ht40_joint", "sora_hip_tx_ht40_joint_samples",
            "sora_hip_tx_ht40_gi", "sora_hip_tx_ht40_gi_samples", "sora_hip_tx_ht40_joint_gi", "sora_hip_tx_ht40_joint_gi_samples",
+           "sora_hip_stream_parse_ht40", "sora_hip_interleave_ht40", "sora_hip_interleave_ht40_stream", "sora_hip_map_ht40", "sora_hip_sig_map_ht40",
+           "sora_hip_add_pilot_ht40", "sora_hip_ifft_ht40", "sora_hip_add_gi_ht40", "sora_hip_preamble_ht40",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
                       "sora_hip_pilot_track11n", "sora_hip_siso_est11n", "sora_hip_siso_comp11n", "sora_hip_sig_demap11n", "sora_hip_sig_decode11n",
            "sora_hip_cca11n", "sora_hip_data_symbol11n", "sora_hip_stream_join11n", "sora_hip_desc11a", "sora_hip_frame_sink11a",
@@ -271,6 +273,15 @@ def load(build_if_missing=True):
     L.sora_hip_csd11n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_add_gi11n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     L.sora_hip_preamble11n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_stream_parse_ht40.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_interleave_ht40.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_interleave_ht40_stream.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_map_ht40.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_sig_map_ht40.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_add_pilot_ht40.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_ifft_ht40.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_add_gi_ht40.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+    L.sora_hip_preamble_ht40.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
     # the 802.11b receive graph's bricks as stages
     L.sora_hip_dc_remove11b.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
     for fn in ("sora_hip_energy_detect11b", "sora_hip_barker_sync11b", "sora_hip_despread11b"):
@@ -2812,6 +2823,275 @@ def tx_ht40_joint(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps
     if sync:
         _check(load().sora_hip_stream_synchronize(_stream_ptr(stream)))
     return out0, out1, [int(v) for v in ooff]
+
+
+# ---- the 40 MHz HT modulation graph's bricks as stages (include/sora_hip.h; bits packed in bytes, LSB first; N_b40 = ceil(108 n_bpsc / 8) bytes per stream and symbol)
+def _row_ht40(n_bpsc):
+    return (108 * int(n_bpsc) + 7) // 8
+
+
+def stream_parse_ht40(s, n_bpsc, out=None, stream=None):
+    """the stream parser: s uint8 CUDA [n, 27 n_bpsc] -> (uint8 CUDA [n, N_b40], the same) for spatial streams 0 and 1; out: a pair of buffers to write into"""
+    import torch
+    n = s.shape[0]
+    o0, o1 = out if out is not None else (torch.empty((n, _row_ht40(n_bpsc)), dtype=torch.uint8, device=s.device) for _ in range(2))
+    _check(load().sora_hip_stream_parse_ht40(_dev_ptr(s), _dev_ptr(o0), _dev_ptr(o1), int(n_bpsc), n, _stream_ptr(stream)))
+    return o0, o1
+
+
+def interleave_ht40(s, n_bpsc, spatial_stream, out=None, stream=None):
+    """the HT interleaver for 40 MHz: s uint8 CUDA [n, N_b40] -> the same shape"""
+    import torch
+    out = torch.empty_like(s) if out is None else out
+    _check(load().sora_hip_interleave_ht40(_dev_ptr(s), _dev_ptr(out), int(n_bpsc), int(spatial_stream), s.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def interleave_ht40_stream(s, in_off, first, nsym, n_bpsc, spatial_stream, out, stream=None):
+    """the same map reading by bit address: s uint8 CUDA [nbytes]; in_off / first / nsym int32 CUDA [nframes]; symbol j of frame f reads bits 108 n_bpsc j onward of
+    s[in_off[f]:] and writes row first[f] + j of out (uint8 CUDA [rows, N_b40], written in place and returned); no other row is touched"""
+    _check(load().sora_hip_interleave_ht40_stream(_dev_ptr(s), _dev_ptr(in_off), _dev_ptr(first), _dev_ptr(nsym), _dev_ptr(out), int(n_bpsc), int(spatial_stream),
+                                                  in_off.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def map_ht40(s, n_bpsc, out=None, stream=None):
+    """the mapper: s uint8 CUDA [n, N_b40] -> int16 CUDA [n, 108, 2]: odd integers times 6144 / 6144 / 4000 / 2214"""
+    import torch
+    out = torch.empty((s.shape[0], 108, 2), dtype=torch.int16, device=s.device) if out is None else out
+    _check(load().sora_hip_map_ht40(_dev_ptr(s), _dev_ptr(out), int(n_bpsc), s.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def sig_map_ht40(s, out=None, stream=None):
+    """L-SIG + HT-SIG: s uint8 CUDA [n, 18] -> int16 CUDA [n, 3, 128, 2]: three complete symbols of bins per frame"""
+    import torch
+    out = torch.empty((s.shape[0], 3, 128, 2), dtype=torch.int16, device=s.device) if out is None else out
+    _check(load().sora_hip_sig_map_ht40(_dev_ptr(s), _dev_ptr(out), s.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def add_pilot_ht40(x, first, nsym, out=None, stream=None):
+    """x int16 CUDA [n, 108, 2]; first / nsym int32 CUDA [nframes] -> int16 CUDA [n, 128, 2]; symbols no frame owns stay as they were (0 in a buffer of the wrapper's)"""
+    import torch
+    out = torch.zeros((x.shape[0], 128, 2), dtype=torch.int16, device=x.device) if out is None else out
+    _check(load().sora_hip_add_pilot_ht40(_dev_ptr(x), _dev_ptr(out), _dev_ptr(first), _dev_ptr(nsym), first.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def ifft_ht40(x, out=None, stream=None):
+    """the fixed-point IFFT<128>, natural order: x int16 CUDA [n, 128, 2] -> the same shape"""
+    import torch
+    out = torch.empty_like(x) if out is None else out
+    _check(load().sora_hip_ifft_ht40(_dev_ptr(x), _dev_ptr(out), x.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def add_gi_ht40(x, gi=0, out=None, stream=None):
+    """the guard interval: x int16 CUDA [n, 128, 2] -> int16 CUDA [n, 160, 2] (gi 0) or [n, 144, 2] (gi 1)"""
+    import torch
+    out = torch.empty((x.shape[0], 144 if int(gi) == 1 else 160, 2), dtype=torch.int16, device=x.device) if out is None else out
+    _check(load().sora_hip_add_gi_ht40(_dev_ptr(x), _dev_ptr(out), int(gi), x.shape[0], _stream_ptr(stream)))
+    return out
+
+
+def preamble_ht40(field, ncopies=1, device=0, stream=None):
+    """field 0: L-STF, L-LTF; field 1: HT-STF, HT-LTF1, HT-LTF2 -> (int16 CUDA [ncopies, 640 or 480, 2] for TX chain 0, the same for chain 1)"""
+    import torch
+    ns = {0: 640, 1: 480}.get(int(field), 640)
+    o0, o1 = (torch.empty((int(ncopies), ns, 2), dtype=torch.int16, device=torch.device("cuda", device)) for _ in range(2))
+    _check(load().sora_hip_preamble_ht40(_dev_ptr(o0), _dev_ptr(o1), int(field), int(ncopies), _stream_ptr(stream)))
+    return o0, o1
+
+
+_MCS_HT40 = {8: (1, CR_12, 54), 9: (2, CR_12, 108), 10: (2, CR_34, 162), 11: (4, CR_12, 216), 12: (4, CR_34, 324), 13: (6, CR_23, 432), 14: (6, CR_34, 486)}
+
+
+def mod_ht40_fields(mpdus, mcs, coding=HT40_CODING_PER_STREAM, gi=0, seeds=None):
+    """The host's share of one frame of the 40 MHz HT modulation chains.  mpdus: (mpdu0, mpdu1) WITHOUT FCS (per-stream coding) or one MPDU (joint).
+    -> (the 9 SIG bytes: L-SIG at 6 Mbps with the LENGTH that spans the HT frame, HT-SIG with the short-GI bit and its CRC-8; a list of one field per encoder: SERVICE +
+    PSDU + FCS + tail + pad up to N_SYM x N_DBPS bits, then zeros up to the encoder stage's whole bursts; the bytes of a field that are scrambled; the index of the tail
+    byte; per field the register sora_hip_scramble11a starts from -- the seed's seven bits reversed, << 1: seed bit i is x[-1 - i]; N_SYM).
+    seeds: (s0, s1) / one seed; None: 0x5D, 0x2B / 0x5D."""
+    import zlib
+    nb, cr, nd = _MCS_HT40[int(mcs)]
+    joint = int(coding) == HT40_CODING_JOINT
+    ms = [bytes(mpdus)] if joint else [bytes(mpdus[0]), bytes(mpdus[1])]
+    if joint:
+        nd *= 2
+    gi = int(gi)
+    ln = len(ms[0]) + 4
+    nsym = -(-(16 + 8 * ln + 6) // nd)
+    lsig = 0xB | ((12 + 3 * ((9 * nsym + 9) // 10 if gi else nsym)) << 5)
+    lsig |= (bin(lsig).count("1") & 1) << 17
+    h4 = (int(mcs) & 0x7F) | (1 << 7) | ((ln & 0xFFFF) << 8) | (7 << 24) | (gi << 31)
+    crc = 0xFF                                                                   # CRC-8 over HT-SIG bits 0..33: reflected, poly 0xE0, complemented
+    for b in range(34):
+        crc ^= (h4 >> b) & 1
+        crc = (crc >> 1) ^ 0xE0 if crc & 1 else crc >> 1
+    sig = lsig | ((h4 | ((~crc & 0xFF) << 34)) << 24)
+    nbytes = (nsym * nd + 7) // 8
+    data = []
+    for mp in ms:
+        d = np.zeros(-(-nbytes // (cr + 1)) * (cr + 1), np.uint8)
+        d[2:2 + len(mp)] = np.frombuffer(mp, np.uint8)
+        d[2 + len(mp):2 + ln] = np.frombuffer(int(zlib.crc32(mp) & 0xFFFFFFFF).to_bytes(4, "little"), np.uint8)
+        data.append(d)
+    if seeds is None:
+        seeds = (0x5D,) if joint else (0x5D, 0x2B)
+    seeds = [seeds] if np.ndim(seeds) == 0 else list(seeds)
+    regs = [int("{:07b}".format(int(s) & 0x7F)[::-1], 2) << 1 for s in seeds]
+    return np.frombuffer(sig.to_bytes(9, "little"), np.uint8).copy(), data, nbytes, 2 + ln, regs, nsym
+
+
+class ModHt40Stages:
+    """sora_amd.tx_ht40's / tx_ht40_joint's frames composed from stage entry points instead of the fused kernels (include/sora_hip.h: the chains of the 40 MHz HT
+    modulation graph).  The constructor plays the source on the host (mod_ht40_fields) and uploads the fields and the frame tables; run() is the stage chain, every
+    intermediate through HBM.  The data symbols are laid out by guard-interval kind, then modulation, so that each stage is one call per kind, modulation, code rate or
+    spatial stream whatever the batch; the SIG symbols and both streams' data symbols share one IFFT call; a last index_select over blocks of 160 samples (of 16 where a batch holds short symbols) puts
+    the fields into frame order.  Joint coding: the encoder stage emits whole bursts, so at MCS 8, 10 and 14 a frame of an odd number of symbols ends one or two coded bytes behind
+    its last symbol's row; such a frame gets one more row, a symbol that no frame owns and nothing reads."""
+
+    def __init__(self, mpdus0, mpdus1, mcs, seeds=None, gi=None, device=0):
+        import torch
+        n = self.n = len(mpdus0)
+        joint = self.joint = mpdus1 is None
+        who = "mod_ht40_by_stages"
+        mcs = [int(m) for m in mcs] if np.ndim(mcs) else [int(mcs)] * n
+        lens = [len(p) for p in mpdus0]
+        if len(mcs) != n or (not joint and (len(mpdus1) != n or any(len(b) != l for b, l in zip(mpdus1, lens)))):
+            raise SoraError(-1, who + ": one MCS per frame; one MPDU per stream and frame, both of a frame of the same length")
+        if any(m not in _MCS_HT40 or not 1 <= l <= 3996 for l, m in zip(lens, mcs)):
+            raise SoraError(-1, who + ": unsupported MCS or length (MCS 8..14, 1..3996 bytes)")
+        if seeds is not None and (len(seeds) != n or any((np.ndim(p) != 0) if joint else (np.ndim(p) != 1 or len(p) != 2) for p in seeds)):
+            raise SoraError(-1, who + ": seeds must hold one seed (joint coding) or one pair (per-stream coding) per frame")
+        g = _tx_gi(gi, n, who) or [0] * n
+        dev = self.dev = torch.device("cuda", device)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
+        i32 = lambda a: up(np.asarray(a, np.int64).astype(np.int32), np.int32)
+        coding = HT40_CODING_JOINT if joint else HT40_CODING_PER_STREAM
+        fields = [mod_ht40_fields(mpdus0[f] if joint else (mpdus0[f], mpdus1[f]), mcs[f], coding, g[f], None if seeds is None else seeds[f]) for f in range(n)]
+        par = [_MCS_HT40[m] for m in mcs]
+        nsym = [fl[5] for fl in fields]
+        nfld = 1 if joint else 2
+        out_len = [len(fl[1][0]) // (p[1] + 1) * (p[1] + 2) for fl, p in zip(fields, par)]      # coded bytes the encoder stage writes per field
+        rows = [-(-o // (27 * p[0])) if joint else k for o, p, k in zip(out_len, par, nsym)]    # data symbol slots a frame takes
+        order = sorted(range(n), key=lambda f: (g[f], par[f][0], f))             # slots: long frames then short ones, each grouped by modulation
+        slot0, at = [0] * n, 0
+        for f in order:
+            slot0[f] = at; at += rows[f]
+        ns = self.nslots = at
+        self.nlong = sum(rows[f] for f in range(n) if g[f] == 0)
+        self.runs, cat, sat = [], 18 * n + (-18 * n) % 16, 0                     # (n_bpsc, first slot, slots, coded base, stream base): bases on 16-byte boundaries
+        for kind in (0, 1):
+            for nb in (1, 2, 4, 6):
+                fs = [f for f in order if g[f] == kind and par[f][0] == nb]
+                cnt = sum(rows[f] for f in fs)
+                if cnt:
+                    self.runs.append((nb, slot0[fs[0]], cnt, cat, sat, fs))
+                    if joint:
+                        cat += (cnt * 27 * nb + 15) // 16 * 16
+                    sat += (cnt * _row_ht40(nb) + 15) // 16 * 16
+        self.stream_bytes = max(sat, 16)
+        coded_off = [[0] * nfld for _ in range(n)]
+        for nb, s0, cnt, cb, sb, fs in self.runs:
+            for f in fs:
+                if joint:
+                    coded_off[f][0] = cb + (slot0[f] - s0) * 27 * nb
+                else:                                                            # per-stream coding: the coded streams lie one behind the other, read by bit address
+                    for s in (0, 1):
+                        coded_off[f][s] = cat; cat += out_len[f]
+        self.coded_bytes = cat + 16
+        # the uncoded bytes: the SIG fields (9 bytes each), then the data fields, each with its zeros up to the encoder's whole bursts
+        flds = [(f, s) for f in range(n) for s in range(nfld)]
+        glen = [len(fields[f][1][s]) for f, s in flds]
+        doff = np.zeros(len(flds) + 1, np.int64); np.cumsum(glen, out=doff[1:]); doff += 9 * n
+        raw = np.zeros(int(doff[-1]), np.uint8)
+        for f, fl in enumerate(fields):
+            raw[9 * f:9 * f + 9] = fl[0]
+        for k, (f, s) in enumerate(flds):
+            raw[doff[k]:doff[k] + glen[k]] = fields[f][1][s]
+        self.d_raw = up(raw, np.uint8)
+        self.scr = (i32(doff[:-1]), i32([fields[f][2] for f, s in flds]), i32([fields[f][3] for f, s in flds]),
+                    up(np.asarray([fields[f][4][s] for f, s in flds], np.uint8), np.uint8), max(fields[f][2] for f in range(n)))
+        # the encoder: the SIG fields at rate 1/2 (18 bytes each from byte 0 of the coded buffer), the data fields by code rate; a fresh register per field
+        self.enc = [(CR_12, i32([9 * f for f in range(n)]), i32([9] * n), i32([18 * f for f in range(n)]), n, 9)]
+        for cr in (CR_12, CR_23, CR_34):
+            ks = [k for k, (f, s) in enumerate(flds) if par[f][1] == cr]
+            if ks:
+                self.enc.append((cr, i32([doff[k] for k in ks]), i32([glen[k] for k in ks]), i32([coded_off[flds[k][0]][flds[k][1]] for k in ks]), len(ks),
+                                 max(glen[k] for k in ks)))
+        if not joint:                                                            # interleave_ht40_stream's tables per run and stream: (byte offsets, first rows, symbols)
+            self.ist = [[(i32([coded_off[f][s] for f in fs]), i32([slot0[f] - s0 for f in fs]), i32([nsym[f] for f in fs])) for s in (0, 1)]
+                        for nb, s0, cnt, cb, sb, fs in self.runs]
+        self.pil = (i32(slot0), i32(nsym))
+        # blocks of a chain's buffer, of 160 samples, or of 16 where a short symbol (144) is among them: n x 640 samples of L-STF + L-LTF, 3 n x 160 of SIG, n x 480 of
+        # HT-STF + HT-LTFs, the long slots x 160, the short slots x 144
+        u = self.block = 16 if any(g) else 160
+        pl, ps, sl, ss = 640 // u, 480 // u, 160 // u, 144 // u
+        blocks, offs = [], [0]
+        for f in range(n):
+            blocks += list(range(pl * f, pl * f + pl)) + list(range(pl * n + ps * f, pl * n + ps * f + ps)) + list(range((pl + ps) * n + ps * f, (pl + ps) * n + ps * f + ps))
+            b0 = (pl + 2 * ps) * n + (sl * slot0[f] if g[f] == 0 else sl * self.nlong + ss * (slot0[f] - self.nlong))
+            blocks += list(range(b0, b0 + (ss if g[f] else sl) * nsym[f]))
+            offs.append(offs[-1] + 1600 + (144 if g[f] else 160) * nsym[f])
+        self.d_blocks = up(np.asarray(blocks, np.int64), np.int64)
+        self.offsets = offs
+
+    def run(self):
+        """-> (out0, out1): int16 CUDA [total, 2] per TX chain; everything in order on torch's current stream (the gather at the end is torch's), nothing waited for"""
+        import torch
+        L = load()
+        st = _stream_ptr(None)
+        n, dev, ns, nl = self.n, self.dev, self.nslots, self.nlong
+        u8 = lambda k: torch.zeros(k, dtype=torch.uint8, device=dev)
+        i16 = lambda *shape: torch.empty(shape + (2,), dtype=torch.int16, device=dev)
+        off, ln, tail, seed, mx = self.scr
+        d_scr = scramble11a(self.d_raw, off, ln, seed, tail=tail, max_len=mx)    # (the SIG bytes and the encoder's pad bytes are in no frame of the call)
+        d_coded = u8(self.coded_bytes)
+        for cr, in_off, ilen, out_off, cnt, mxl in self.enc:
+            _check(L.sora_hip_conv_encode11a(_dev_ptr(d_scr), _dev_ptr(in_off), _dev_ptr(ilen), cr, _dev_ptr(d_coded), _dev_ptr(out_off), cnt, mxl, st))
+        # bins of every symbol that goes through the IFFT: 3 n SIG symbols, the data slots of stream 0, those of stream 1
+        d_bins = i16(3 * n + 2 * ns, 128)
+        d_sig = interleave11a(d_coded[:18 * n].view(3 * n, 6), 1)
+        _check(L.sora_hip_sig_map_ht40(_dev_ptr(d_sig), d_bins.data_ptr(), n, st))
+        d_int = [u8(self.stream_bytes), u8(self.stream_bytes)]
+        d_par = [u8(self.stream_bytes), u8(self.stream_bytes)] if self.joint else None
+        d_car = i16(2 * ns, 108)
+        for r, (nb, s0, cnt, cb, sb, fs) in enumerate(self.runs):
+            if self.joint:
+                _check(L.sora_hip_stream_parse_ht40(d_coded.data_ptr() + cb, d_par[0].data_ptr() + sb, d_par[1].data_ptr() + sb, nb, cnt, st))
+            for iss in (0, 1):
+                if self.joint:
+                    _check(L.sora_hip_interleave_ht40(d_par[iss].data_ptr() + sb, d_int[iss].data_ptr() + sb, nb, iss, cnt, st))
+                else:
+                    io, fi, nsy = self.ist[r][iss]
+                    _check(L.sora_hip_interleave_ht40_stream(d_coded.data_ptr(), _dev_ptr(io), _dev_ptr(fi), _dev_ptr(nsy), d_int[iss].data_ptr() + sb, nb, iss, len(fs), st))
+                _check(L.sora_hip_map_ht40(d_int[iss].data_ptr() + sb, d_car.data_ptr() + (iss * ns + s0) * 432, nb, cnt, st))
+        for iss in (0, 1):
+            _check(L.sora_hip_add_pilot_ht40(d_car.data_ptr() + iss * ns * 432, d_bins.data_ptr() + (3 * n + iss * ns) * 512, _dev_ptr(self.pil[0]), _dev_ptr(self.pil[1]),
+                                             n, st))
+        d_t = ifft_ht40(d_bins)
+        total = 1600 * n + 160 * nl + 144 * (ns - nl)                            # samples of a chain's buffer: L, SIG, HT, long slots, short slots
+        outs = [i16(total), i16(total)]
+        for ch in (0, 1):                                                        # one add_gi call per chain and kind; the SIG symbols are the same on both chains
+            src = d_t.data_ptr() + (3 * n + ch * ns) * 512
+            _check(L.sora_hip_add_gi_ht40(d_t.data_ptr(), outs[ch].data_ptr() + 640 * n * 4, 0, 3 * n, st))
+            _check(L.sora_hip_add_gi_ht40(src, outs[ch].data_ptr() + 1600 * n * 4, 0, nl, st))
+            _check(L.sora_hip_add_gi_ht40(src + nl * 512, outs[ch].data_ptr() + (1600 * n + 160 * nl) * 4, 1, ns - nl, st))
+        _check(L.sora_hip_preamble_ht40(outs[0].data_ptr(), outs[1].data_ptr(), 0, n, st))
+        _check(L.sora_hip_preamble_ht40(outs[0].data_ptr() + 1120 * n * 4, outs[1].data_ptr() + 1120 * n * 4, 1, n, st))
+        return tuple(o.view(-1, self.block, 2).index_select(0, self.d_blocks).reshape(-1, 2) for o in outs)
+
+
+def mod_ht40_by_stages(mpdus0, mpdus1, mcs, seeds=None, gi=None, device=0, sync=True):
+    """Modulate a batch through the stage chain (ModHt40Stages).  mpdus1 a list: per-stream coding, what sora_amd.tx_ht40(mpdus0, mpdus1, mcs, seeds, gi=gi) returns;
+    mpdus1 None: joint coding, what sora_amd.tx_ht40_joint(mpdus0, mcs, seeds, gi=gi) returns.  -> (out0, out1, offsets)"""
+    plan = ModHt40Stages(mpdus0, mpdus1, mcs, seeds, gi, device)
+    out0, out1 = plan.run()
+    if sync:
+        _check(load().sora_hip_stream_synchronize(_stream_ptr(None)))
+    return out0, out1, plan.offsets
 
 
 TX11B_RATES = (1000, 2000, 5500, 11000)

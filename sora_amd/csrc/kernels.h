@@ -232,6 +232,8 @@ __host__ __device__ inline size_t tx_ht40_frame_samples(uint32_t nsym, uint32_t 
 __host__ __device__ inline uint32_t tx_ht40_lsig_length(uint32_t nsym, uint32_t gi) { return 12u + 3u * (gi ? (9u * nsym + 9u) / 10u : nsym); }
 __global__ void k_tx_ht40_gi(TxHt40Args A);
 __global__ void k_tx_ht40_joint_gi(TxHt40Args A);
+// k_mod_ht40.hip: the fixed fields as a stage, launched beside the transmitter whose table it copies (sora_hip_preamble_ht40); nwords 16-byte words
+__global__ void k_mod_ht40_preamble(const uint4* table, uint4* out0, uint4* out1, uint32_t w0, uint32_t nw, uint64_t nwords);
 
 // ---- 802.11b transmitter (k_tx11b.hip)
 struct Tx11bArgs {             // sora_hip_tx11b

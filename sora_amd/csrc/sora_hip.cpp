@@ -1720,6 +1720,23 @@ size_t sora_hip_tx_ht40_joint_gi_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, 
     return tx_ht40_frame_samples(P.nsym, gi);
 }
 
+// the fixed fields through the same fixed-point IFFT as every other symbol (the four transmitters and sora_hip_preamble_ht40): built once per device, under the lock,
+// and complete before it is published
+static int tx_ht40_preamble_ready(DevTables* D, hipStream_t st)
+{
+    std::lock_guard<std::mutex> lock(g_stage_mutex);
+    if (!D->tx_ht40_preamble) {
+        uint32_t* p = nullptr;
+        HIPCHK(hipMalloc((void**)&p, 2 * kTxHt40Preamble * sizeof(uint32_t)));
+        hipLaunchKernelGGL(k_tx_ht40_preamble, dim3(1), dim3(128), 0, st, p, D->T);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { (void)hipFree(p); return fail(SORA_ERR_HARDWARE_FAILED, "k_tx_ht40_preamble", e); }
+        D->tx_ht40_preamble = p; D->allocs.push_back(p);
+    }
+    return SORA_OK;
+}
+
 // both codings: the per-stream one (two MPDUs and two seeds per frame) and the joint one (one of each).  guard: the _gi entry points, which launch the kernels that read
 // a guard-interval kind per frame (d_gi; null: every frame long); the entry points without it launch the kernels they always launched
 static int tx_ht40_launch(bool joint, const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
@@ -1732,20 +1749,7 @@ static int tx_ht40_launch(bool joint, const uint8_t* d_mpdu, const uint32_t* d_o
     if (nframes == 0) return SORA_OK;
     DevTables* D = device_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     hipStream_t st = (hipStream_t)stream;
-    {
-        // the fixed fields through the same fixed-point IFFT as every other symbol: built once per device, under the lock, and complete
-        // before it is published
-        std::lock_guard<std::mutex> lock(g_stage_mutex);
-        if (!D->tx_ht40_preamble) {
-            uint32_t* p = nullptr;
-            HIPCHK(hipMalloc((void**)&p, 2 * kTxHt40Preamble * sizeof(uint32_t)));
-            hipLaunchKernelGGL(k_tx_ht40_preamble, dim3(1), dim3(128), 0, st, p, D->T);
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) { (void)hipFree(p); return fail(SORA_ERR_HARDWARE_FAILED, "k_tx_ht40_preamble", e); }
-            D->tx_ht40_preamble = p; D->allocs.push_back(p);
-        }
-    }
+    if (const int rc = tx_ht40_preamble_ready(D, st)) return rc;
     TxHt40Args A{};
     A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.mcs = d_mcs; A.seed = d_seed;
     A.out0 = reinterpret_cast<uint32_t*>(d_out0); A.out1 = reinterpret_cast<uint32_t*>(d_out1); A.out_off = d_out_off;
@@ -1774,6 +1778,22 @@ int sora_hip_tx_ht40_joint_gi(const uint8_t* d_mpdu, const uint32_t* d_off, cons
                               size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
 {
     return tx_ht40_launch(true, d_mpdu, d_off, d_len, d_mcs, d_seed, nframes, d_out0, d_out1, d_out_off, stream, true, d_gi);
+}
+
+// the fixed fields as a stage (the 40 MHz HT modulation graph's other bricks: k_mod_ht40.hip): it copies the transmitters' table, so it stands here
+int sora_hip_preamble_ht40(sora_complex16* d_out0, sora_complex16* d_out1, int field, size_t ncopies, void* stream)
+{
+    if (field != 0 && field != 1) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble_ht40: field must be 0 (L-STF, L-LTF) or 1 (HT-STF, HT-LTF1, HT-LTF2)");
+    STAGE_ENTRY("sora_hip_preamble_ht40", !d_out0 || !d_out1, ncopies)
+    if (!aligned16(d_out0, d_out1)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble_ht40: buffers must be 16-byte aligned");
+    if (ncopies >= (1ull << 24)) return fail(SORA_ERR_CAPACITY, "sora_hip_preamble_ht40: too many copies for one call");
+    DevTables* D = device_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
+    if (const int rc = tx_ht40_preamble_ready(D, (hipStream_t)stream)) return rc;
+    const uint32_t w0 = field ? 160u : 0u, nw = field ? 120u : 160u;             // 16-byte words: samples 0..639 / 640..1119 of a chain's 1120
+    const uint64_t nwords = (uint64_t)ncopies * nw;
+    hipLaunchKernelGGL(k_mod_ht40_preamble, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(D->tx_ht40_preamble),
+                       reinterpret_cast<uint4*>(d_out0), reinterpret_cast<uint4*>(d_out1), w0, nw, nwords);
+    return launch_result("k_mod_ht40_preamble");
 }
 
 // ---- 802.11b transmitter
