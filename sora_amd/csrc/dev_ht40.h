@@ -37,6 +37,9 @@ __device__ __forceinline__ int pilot_bin40(int k)          // pilot k (0..5) of 
     const int pk = k == 0 ? -53 : k == 1 ? -25 : k == 2 ? -11 : k == 3 ? 11 : k == 4 ? 25 : 53;
     return pk & 127;
 }
+// what the transmitter (k_tx_ht40.hip) and the modulation stages (k_mod_ht40.hip) put on the carriers, in units of kTxHt40Amp / 128 per LEVEL (tests/tx_ht40_model.py)
+__device__ __forceinline__ int level40(int nb) { return nb <= 2 ? 6144 : nb == 4 ? 4000 : 2214; }   // a data carrier's unit d(N_BPSC): rint(A LEVEL / 128), LEVEL = 48, 48, 31.25, 17.3
+constexpr int kPilot40 = 12288;                            // a data pilot: 2 d(1)
 
 
 // ---- what the stage entry points of k_ht40_stages.hip add to the bricks of dev_11n.h

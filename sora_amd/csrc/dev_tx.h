@@ -126,23 +126,6 @@ __device__ __forceinline__ int tx_pilot11n(int iss, uint32_t n, int k)
     return (pilot_sgn((n + 3u) % 127u) ? -psi : psi) * kBpsk11n;
 }
 
-// ---- a tile of nbytes contiguous bytes between 16-byte aligned global memory and LDS (the stages of k_mod.hip and k_mod11n.hip, 256 threads): 16 bytes per lane, the
-// ragged end of a last tile byte by byte
-__device__ __forceinline__ void mod_tile_load(uint32_t* s, const uint8_t* g, int nbytes, int tid)
-{
-    for (int q = tid; q < (nbytes + 15) / 16; q += 256) {
-        if (16 * q + 16 <= nbytes) reinterpret_cast<uint4*>(s)[q] = reinterpret_cast<const uint4*>(g)[q];
-        else for (int b = 16 * q; b < 16 * q + 16; b++) reinterpret_cast<uint8_t*>(s)[b] = b < nbytes ? g[b] : (uint8_t)0;
-    }
-}
-__device__ __forceinline__ void mod_tile_store(uint8_t* g, const uint32_t* s, int nbytes, int tid)
-{
-    for (int q = tid; q < (nbytes + 15) / 16; q += 256) {
-        if (16 * q + 16 <= nbytes) reinterpret_cast<uint4*>(g)[q] = reinterpret_cast<const uint4*>(s)[q];
-        else for (int b = 16 * q; b < nbytes; b++) g[b] = reinterpret_cast<const uint8_t*>(s)[b];
-    }
-}
-
 // ---- IFFT<128> of a group's 128-word symbol buffer in place (ifft128_core_pk: packed COMPLEX16, bit-exact with fft128_core<true>): time sample n is left at
 // word brev7(n), swizzled (fft128_swz) where the buffer is.  The buffer is private to a 32-lane group: wave-level barriers.
 template <bool SWZ>

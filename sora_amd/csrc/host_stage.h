@@ -13,6 +13,11 @@
     if ((count) >= (1ull << 31)) return sora_internal_fail(SORA_ERR_CAPACITY, who ": too many for one call", 0);
 #define STAGE_NBPSC(who, nb) \
     if (!((nb) == 1 || (nb) == 2 || (nb) == 4 || (nb) == 6)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, who ": n_bpsc must be 1, 2, 4 or 6", 0);
+#define STAGE_STREAM01(who, iss) \
+    if ((iss) < 0 || (iss) > 1) return sora_internal_fail(SORA_ERR_INVALID_PARAM, who ": spatial_stream must be 0 or 1", 0);
+// the buffers a stage moves 16 bytes per lane
+#define STAGE_ALIGNED16(who, ...) \
+    if (!aligned16(__VA_ARGS__)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, who ": buffers must be 16-byte aligned", 0);
 // a kernel template's 1 / 2 / 4 / 6 instances, workgroups of 256 (nb has passed STAGE_NBPSC)
 #define STAGE_BY_NBPSC(nb, kernel, grid, st, ...) \
     switch (nb) { \
@@ -46,6 +51,12 @@ inline bool stage_grid(size_t nframes, size_t max_items, uint32_t* chunks, unsig
     *chunks = (uint32_t)c; *grid = (unsigned)g;
     return true;
 }
+
+// workgroups of `per` items each for `count` of them (count has passed STAGE_ENTRY)
+inline unsigned stage_tiles(size_t count, size_t per) { return (unsigned)((count + per - 1) / per); }
+// gridDim.y of the stages whose workgroup (f, y) strides over the passes of frame f: the frames' lengths are device memory, so a batch of few frames gets several
+// workgroups per frame
+inline unsigned stage_frame_grid(size_t nframes) { return nframes >= 2048 ? 1u : (unsigned)std::min<size_t>(64, 2048 / nframes); }
 
 // the current device's look-up tables (uploaded on first use)
 inline int stage_tables(Tables* T)

@@ -10,16 +10,17 @@
 //   k_mod_pack16to8   TPackSample16to8               (brick/inc/stdbrick.hpp:415-445)         COMPLEX16 x 8 -> COMPLEX8 x 8
 //   k_mod_preamble    TTS11aSrc                      (preamble11a.hpp:19-140)                 -> COMPLEX16 x 640
 // The arithmetic is dev_tx.h's (what the fused transmitters run); here are the port formats and the streaming shape of k_stage.hip: a workgroup owns a tile of
-// consecutive symbols, every access to a symbol buffer is a 16-byte-per-lane load or store of a contiguous tile, the reshuffling inside a symbol happens in LDS.
-// The byte-wide stages (scrambler, encoder) are one thread per output byte: every output bit is a closed form of its position.
+// consecutive symbols, every access to a symbol buffer is a 16-byte-per-lane load or store of a contiguous tile, the reshuffling inside a symbol happens in LDS.  The tile
+// shape and the bodies of the interleaver, the mapper, the pilot stage and the IFFT are dev_mod.h's, which the 802.11n and 40 MHz HT graphs instantiate too; here are this
+// graph's widths and policies.  The byte-wide stages (scrambler, encoder) are one thread per output byte: every output bit is a closed form of its position.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "dev_tx.h"
+#include "dev_mod.h"
 #include "host_stage.h"
 
 namespace sora {
 
-// (mod_tile_load / mod_tile_store, a tile between global memory and LDS: dev_tx.h)
 // ---- T11aSc: byte i of frame f = in ^ (the register after i + 1 steps), the register a phase of the period-127 cycle (tx_scramble); the tail byte keeps its two pad bits.
 // chunks = workgroups per frame (the host's bound on the lengths / 256).
 __global__ void __launch_bounds__(256) k_mod_scramble(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const uint32_t* __restrict__ off, const uint32_t* __restrict__ len,
@@ -63,153 +64,56 @@ __global__ void __launch_bounds__(256) k_mod_encode(const uint8_t* __restrict__ 
     out[(size_t)out_off[f] + j] = (uint8_t)o;
 }
 
-// ---- T11aInterleave*: bit k of a symbol goes to bit j(k) (T.deint holds j(k): the receiver's de-interleaver reads it the other way round).  A tile of 32 symbols is
-// staged in LDS; a thread makes whole output bytes through the inverted map.
-constexpr int kModSyms = 32;
+// ---- T11aInterleave*: bit k of a symbol goes to bit j(k) (T.deint holds j(k): the receiver's de-interleaver reads it the other way round): mod_interleave_tile
+struct ModMap11a {
+    static constexpr bool kOrsPadBits = false;                                   // 48 N_BPSC bits fill the row
+    const uint16_t* row;                                                         // Tables::deint, one row of 288 per N_BPSC
+    __device__ __forceinline__ int operator()(int k) const { return row[k]; }
+};
 template <int NB>
 __global__ void __launch_bounds__(256) k_mod_interleave(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n, Tables T)
 {
-    constexpr int NCB = 48 * NB, SB = 6 * NB;                                    // coded bits, bytes per symbol
-    __shared__ alignas(16) uint32_t s_in[kModSyms * SB / 4];
-    __shared__ alignas(16) uint32_t s_out[kModSyms * SB / 4];
-    __shared__ uint16_t s_inv[NCB];
-    const int tid = threadIdx.x;
-    const uint32_t s0 = blockIdx.x * kModSyms;
-    const int ns = (int)min((uint32_t)kModSyms, n - s0), nbytes = ns * SB;
     constexpr int di = NB == 1 ? 0 : NB == 2 ? 1 : NB == 4 ? 2 : 3;
-    for (int k = tid; k < NCB; k += 256) s_inv[T.deint[di * 288 + k]] = (uint16_t)k;
-    mod_tile_load(s_in, in + (size_t)s0 * SB, nbytes, tid);
-    __syncthreads();
-    const uint8_t* b = reinterpret_cast<const uint8_t*>(s_in);
-    for (int q = tid; q < nbytes; q += 256) {
-        const int sym = q / SB, p0 = 8 * (q - sym * SB);
-        unsigned o = 0;
-#pragma unroll
-        for (int t = 0; t < 8; t++) { const int k = s_inv[p0 + t]; o |= ((b[sym * SB + (k >> 3)] >> (k & 7)) & 1u) << t; }
-        reinterpret_cast<uint8_t*>(s_out)[q] = (uint8_t)o;
-    }
-    __syncthreads();
-    mod_tile_store(out + (size_t)s0 * SB, s_out, nbytes, tid);
+    mod_interleave_tile<48, NB>(in, out, n, ModMap11a{ T.deint + di * 288 });
 }
-template __global__ void k_mod_interleave<1>(const uint8_t*, uint8_t*, uint32_t, Tables);
-template __global__ void k_mod_interleave<2>(const uint8_t*, uint8_t*, uint32_t, Tables);
-template __global__ void k_mod_interleave<4>(const uint8_t*, uint8_t*, uint32_t, Tables);
-template __global__ void k_mod_interleave<6>(const uint8_t*, uint8_t*, uint32_t, Tables);
+MOD_INSTANCES(k_mod_interleave, const uint8_t*, uint8_t*, uint32_t, Tables)
 
-// ---- TMap11a*<MOD>: carrier c of a symbol takes bits c N_BPSC .. of its 6 N_BPSC bytes, the first half for I and the second for Q (tx_axis_level; BPSK: +-MOD on I).
-// A thread makes four carriers in a row and stores them as one 16-byte word: 12 per symbol.
+// ---- TMap11a*<MOD>: mod_map_tile on the 48 carriers of a symbol's 6 N_BPSC bytes, 12 words per symbol
 template <int NB>
 __global__ void __launch_bounds__(256) k_mod_map(const uint8_t* __restrict__ in, uint32_t* __restrict__ out, int mod, uint32_t n)
 {
-    constexpr int SB = 6 * NB, M = NB == 1 ? 1 : NB / 2;
-    __shared__ alignas(16) uint32_t s_in[kModSyms * SB / 4];
-    const int tid = threadIdx.x;
-    const uint32_t s0 = blockIdx.x * kModSyms;
-    const int ns = (int)min((uint32_t)kModSyms, n - s0);
-    mod_tile_load(s_in, in + (size_t)s0 * SB, ns * SB, tid);
-    __syncthreads();
-    const int d2 = 2 * mod, lvl0 = -((1 << M) - 1) * mod;
-    const uint32_t off[3] = { 0u, 1u, 2u };
-    uint4* o4 = reinterpret_cast<uint4*>(out + (size_t)s0 * 48);
-    for (int q = tid; q < ns * 12; q += 256) {                                   // carriers 4 q .. 4 q + 3 of the tile; the tile's bits are one string (48 NB per symbol)
-        uint32_t v[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const uint32_t bit0 = (uint32_t)(4 * q + t) * NB;
-            if (NB == 1) v[t] = pack(mk(tx_gen_bit(s_in, bit0) ? mod : -mod, 0));
-            else v[t] = pack(mk(tx_axis_level(s_in, bit0, off, M, d2, lvl0), tx_axis_level(s_in, bit0 + M, off, M, d2, lvl0)));   // (short)(l * kmod): pack wraps
-        }
-        o4[q] = uint4{v[0], v[1], v[2], v[3]};
-    }
+    mod_map_tile<48, NB>(in, out, mod, n);
 }
-template __global__ void k_mod_map<1>(const uint8_t*, uint32_t*, int, uint32_t);
-template __global__ void k_mod_map<2>(const uint8_t*, uint32_t*, int, uint32_t);
-template __global__ void k_mod_map<4>(const uint8_t*, uint32_t*, int, uint32_t);
-template __global__ void k_mod_map<6>(const uint8_t*, uint32_t*, int, uint32_t);
+MOD_INSTANCES(k_mod_map, const uint8_t*, uint32_t*, int, uint32_t)
 
-// ---- T11aAddPilot: 16 lanes per symbol, 16 symbols per pass of a workgroup; the 48 carriers arrive as twelve 16-byte loads, bins 4 e .. 4 e + 3 leave as one store.
-// Workgroup (f, y) takes passes y, y + gridDim.y, .. of frame f.  The symbol at position j of its frame (pos0[f] + its index in the table's range; pos0 null: 0) has
-// polarity PilotSgn[127] for j = 0 and PilotSgn[(j - 1) mod 127] behind it: m_PilotIndex starts at 127 and wraps at 127.
+// ---- T11aAddPilot: mod_pilot_frames, 16 lanes per symbol; the 48 carriers arrive as twelve 16-byte loads.  The symbol at position j of its frame has polarity
+// PilotSgn[127] for j = 0 and PilotSgn[(j - 1) mod 127] behind it: m_PilotIndex starts at 127 and wraps at 127.
+struct ModPilots11a {
+    static constexpr int kCarriers = 48;
+    int mod;
+    static __device__ __forceinline__ int source(int b)                          // -1 = a pilot, -2 = zero
+    {
+        if (b == 7 || b == 21 || b == 43 || b == 57) return -1;
+        if (b >= 1 && b <= 26) return 24 + (b - 1) - (b > 7) - (b > 21);
+        if (b >= 38) return b - 38 - (b > 43) - (b > 57);
+        return -2;
+    }
+    __device__ __forceinline__ uint32_t word(int kind, int b, uint32_t j) const
+    {
+        const int p = pilot_sgn(j == 0 ? 127u : (j - 1u) % 127u) ? -mod : mod;
+        return kind == -1 ? pack(mk(b == 21 ? -p : p, 0)) : 0u;
+    }
+};
 __global__ void __launch_bounds__(256) k_mod_add_pilot(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const uint32_t* __restrict__ first,
         const uint32_t* __restrict__ nsym, const uint32_t* __restrict__ pos0, uint32_t nframes, int mod)
 {
-    __shared__ alignas(16) uint32_t s_all[16][48];
-    const uint32_t f = blockIdx.x;
-    if (f >= nframes) return;
-    const int g = threadIdx.x >> 4, e = threadIdx.x & 15;
-    uint32_t* s = s_all[g];
-    const uint32_t sf = first[f], ns = nsym[f], p0 = pos0 ? pos0[f] : 0u;
-    int src[4];                                                                  // bin 4 e + q: carrier index in the input, -1 = a pilot, -2 = zero
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int b = 4 * e + q;
-        if (b == 7 || b == 21 || b == 43 || b == 57) src[q] = -1;
-        else if (b >= 1 && b <= 26) src[q] = 24 + (b - 1) - (b > 7) - (b > 21);
-        else if (b >= 38) src[q] = b - 38 - (b > 43) - (b > 57);
-        else src[q] = -2;
-    }
-    for (uint32_t t0 = blockIdx.y * 16u; t0 < ns; t0 += gridDim.y * 16u) {      // (uniform per workgroup: every lane keeps the barriers company)
-        const uint32_t t = t0 + (uint32_t)g;
-        const bool active = t < ns;
-        const size_t sym = (size_t)sf + t;
-        uint4 v = uint4{0, 0, 0, 0};
-        if (active && e < 12) v = reinterpret_cast<const uint4*>(in + sym * 48)[e];
-        wave_lds_sync();
-        if (e < 12) reinterpret_cast<uint4*>(s)[e] = v;
-        wave_lds_sync();
-        const uint32_t j = p0 + t;
-        const int p = pilot_sgn(j == 0 ? 127u : (j - 1u) % 127u) ? -mod : mod;
-        uint32_t o[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int b = 4 * e + q;
-            o[q] = src[q] >= 0 ? s[src[q]] : src[q] == -1 ? pack(mk(b == 21 ? -p : p, 0)) : 0u;
-        }
-        if (active) reinterpret_cast<uint4*>(out + sym * 64)[e] = uint4{o[0], o[1], o[2], o[3]};
-    }
+    mod_pilot_frames<16>(in, out, first, nsym, pos0, nframes, ModPilots11a{ mod });
 }
 
-// ---- TIFFTx: 32 lanes per symbol, 8 symbols per tile, 4 tiles per workgroup, every tile's load in flight before the first butterfly (k_fft128_batch's shape).  Lanes
-// 0 .. 15 bring bins 4 e .. 4 e + 3 as one 16-byte load and put them at bins 0 .. 31 / 96 .. 127 of the group's swizzled 128-word buffer, lanes 16 .. 31 clear the 64 bins
-// between; tx_ifft128<true> transforms in place; output sample i is time sample (i + 96) & 127, >> 4, so lane e stores samples 4 e .. 4 e + 3 and, for e < 8, the same
-// four time samples as 128 + 4 e .. (the guard interval is the symbol's last 32 samples in front): each output sample is written once, 16 bytes per lane.  Samples 0, 1, 158
-// and 159 are halved (the window).
-constexpr int kIfftTiles = 4;
-__device__ __forceinline__ uint4 mod_ifftx_quad(const uint32_t* s, int e, int sh01, int sh23)
-{
-    const uint32_t n0 = (uint32_t)(4 * e + 96);
-    return uint4{ pk_sra(tx_tsample<true>(s, n0), sh01), pk_sra(tx_tsample<true>(s, n0 + 1), sh01), pk_sra(tx_tsample<true>(s, n0 + 2), sh23), pk_sra(tx_tsample<true>(s, n0 + 3), sh23) };
-}
+// ---- TIFFTx: mod_ifft_tiles from 64 bins to 160 samples, the guard interval in front and the window on its ends
 __global__ void __launch_bounds__(256) k_mod_ifftx(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n, Tables T)
 {
-    __shared__ alignas(16) uint32_t s_all[8][128];
-    const int g = threadIdx.x >> 5, e = threadIdx.x & 31;
-    const Fft128Tw tw = fft128_twiddles(T, e);
-    uint32_t* s = s_all[g];
-    uint4 v[kIfftTiles];
-#pragma unroll
-    for (int t = 0; t < kIfftTiles; t++) {
-        const uint32_t i = (blockIdx.x * kIfftTiles + t) * 8 + g;
-        v[t] = (i < n && e < 16) ? reinterpret_cast<const uint4*>(in)[(size_t)i * 16 + e] : uint4{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int t = 0; t < kIfftTiles; t++) {
-        const uint32_t i = (blockIdx.x * kIfftTiles + t) * 8 + g;
-        wave_lds_sync();
-        {
-            const int b0 = e < 16 ? bin128(4 * e) : 32 + 4 * (e - 16);               // four bins in a row on the 128-point grid; the swizzle moves them one by one
-            const uint32_t w[4] = { v[t].x, v[t].y, v[t].z, v[t].w };
-#pragma unroll
-            for (int q = 0; q < 4; q++) s[fft128_swz(b0 + q)] = w[q];
-        }
-        tx_ifft128<true>(s, e, tw);
-        wave_lds_sync();
-        if (i < n) {
-            uint4* o = reinterpret_cast<uint4*>(out + (size_t)i * 160);
-            o[e] = mod_ifftx_quad(s, e, e == 0 ? 5 : 4, 4);
-            if (e < 8) o[32 + e] = mod_ifftx_quad(s, e, 4, e == 7 ? 5 : 4);
-        }
-    }
+    mod_ifft_tiles<ModPlace64, ModEmitGiWindow>(in, out, n, T);
 }
 
 // ---- TUpsample40MTo44M: y[11 m + r] = int16(mh(x[10 m + r - 1], S(r)) + mh(x[10 m + r], S(11 - r))) per 160-sample block, nothing carried between blocks (the closed form:
@@ -355,9 +259,9 @@ int sora_hip_interleave11a(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, size
 {
     STAGE_ENTRY("sora_hip_interleave11a", !d_in || !d_out, nsym)
     STAGE_NBPSC("sora_hip_interleave11a", n_bpsc)
-    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_interleave11a: buffers must be 16-byte aligned", 0);
+    STAGE_ALIGNED16("sora_hip_interleave11a", d_in, d_out)
     Tables T; if (const int rc = stage_tables(&T)) return rc;
-    const dim3 grid((unsigned)((nsym + 31) / 32));
+    const dim3 grid(stage_tiles(nsym, kModTile));
     STAGE_BY_NBPSC(n_bpsc, k_mod_interleave, grid, (hipStream_t)stream, d_in, d_out, (uint32_t)nsym, T)
     return launch_result("k_mod_interleave");
 }
@@ -367,9 +271,9 @@ int sora_hip_map11a(const uint8_t* d_in, sora_complex16* d_out, int n_bpsc, int 
     STAGE_ENTRY("sora_hip_map11a", !d_in || !d_out, nsym)
     STAGE_NBPSC("sora_hip_map11a", n_bpsc)
     if (mod < 0 || mod > 32767) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11a: mod must be 0 .. 32767", 0);
-    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_map11a: buffers must be 16-byte aligned", 0);
+    STAGE_ALIGNED16("sora_hip_map11a", d_in, d_out)
     if (mod == 0) mod = n_bpsc == 1 ? 10720 : n_bpsc == 2 ? (short)(10720 / 1.414) : n_bpsc == 4 ? (short)(10720 / 3.162) : (short)(10720 / 6.481);   // mapper11a.hpp:8-11
-    const dim3 grid((unsigned)((nsym + 31) / 32));
+    const dim3 grid(stage_tiles(nsym, kModTile));
     STAGE_BY_NBPSC(n_bpsc, k_mod_map, grid, (hipStream_t)stream, d_in, u32(d_out), mod, (uint32_t)nsym)
     return launch_result("k_mod_map");
 }
@@ -379,10 +283,8 @@ int sora_hip_add_pilot11a_from(const sora_complex16* d_in, sora_complex16* d_out
 {
     STAGE_ENTRY("sora_hip_add_pilot11a", !d_in || !d_out || !d_first || !d_nsym, nframes)
     if (bpsk_mod < 0 || bpsk_mod > 32767) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11a: bpsk_mod must be 0 .. 32767", 0);
-    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_add_pilot11a: buffers must be 16-byte aligned", 0);
-    // the frames' lengths are device memory: a batch of few frames gets several workgroups per frame, each striding over the frame's passes of 16 symbols
-    const unsigned gy = nframes >= 2048 ? 1u : (unsigned)std::min<size_t>(64, 2048 / nframes);
-    hipLaunchKernelGGL(k_mod_add_pilot, dim3((unsigned)nframes, gy), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), d_first, d_nsym, d_pos0, (uint32_t)nframes,
+    STAGE_ALIGNED16("sora_hip_add_pilot11a", d_in, d_out)
+    hipLaunchKernelGGL(k_mod_add_pilot, dim3((unsigned)nframes, stage_frame_grid(nframes)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), d_first, d_nsym, d_pos0, (uint32_t)nframes,
                        bpsk_mod ? bpsk_mod : 10720);
     return launch_result("k_mod_add_pilot");
 }
@@ -394,17 +296,17 @@ int sora_hip_add_pilot11a(const sora_complex16* d_in, sora_complex16* d_out, con
 int sora_hip_ifftx11a(const sora_complex16* d_in, sora_complex16* d_out, size_t nsym, void* stream)
 {
     STAGE_ENTRY("sora_hip_ifftx11a", !d_in || !d_out, nsym)
-    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_ifftx11a: buffers must be 16-byte aligned", 0);
+    STAGE_ALIGNED16("sora_hip_ifftx11a", d_in, d_out)
     Tables T; if (const int rc = stage_tables(&T)) return rc;
-    hipLaunchKernelGGL(k_mod_ifftx, dim3((unsigned)((nsym + 31) / 32)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), (uint32_t)nsym, T);
+    hipLaunchKernelGGL(k_mod_ifftx, dim3(stage_tiles(nsym, kModIfftSyms)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), (uint32_t)nsym, T);
     return launch_result("k_mod_ifftx");
 }
 
 int sora_hip_upsample40to44(const sora_complex16* d_in, sora_complex16* d_out, const uint8_t* d_sees_next, size_t nblocks, void* stream)
 {
     STAGE_ENTRY("sora_hip_upsample40to44", !d_in || !d_out, nblocks)
-    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_upsample40to44: buffers must be 16-byte aligned", 0);
-    hipLaunchKernelGGL(k_mod_upsample, dim3((unsigned)((nblocks + 7) / 8)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), d_sees_next, (uint32_t)nblocks);
+    STAGE_ALIGNED16("sora_hip_upsample40to44", d_in, d_out)
+    hipLaunchKernelGGL(k_mod_upsample, dim3(stage_tiles(nblocks, kUpBlocks)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), d_sees_next, (uint32_t)nblocks);
     return launch_result("k_mod_upsample");
 }
 
@@ -413,9 +315,9 @@ int sora_hip_pack16to8(const sora_complex16* d_in, int8_t* d_out, size_t nsample
     // (counted in workgroups, 256 bursts of 8 samples each: what one launch is limited by; 0 exactly when nsamples is)
     STAGE_ENTRY("sora_hip_pack16to8", !d_in || !d_out, (nsamples + 2047) / 2048)
     if (nsamples % 8) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_pack16to8: nsamples must be a multiple of 8 (the brick's burst)", 0);
-    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_pack16to8: buffers must be 16-byte aligned", 0);
+    STAGE_ALIGNED16("sora_hip_pack16to8", d_in, d_out)
     const uint64_t nb = nsamples / 8;
-    hipLaunchKernelGGL(k_mod_pack16to8, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), nb);
+    hipLaunchKernelGGL(k_mod_pack16to8, dim3(stage_tiles(nb, 256)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), nb);
     return launch_result("k_mod_pack16to8");
 }
 

@@ -447,7 +447,7 @@ int sora_hip_fft64(const sora_complex16* d_in, sora_complex16* d_out, size_t n, 
 {
     STAGE_ENTRY("sora_hip_fft64", !d_in || !d_out, n)
     Tables T; if (const int rc = stage_tables(&T)) return rc;
-    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_fft64: buffers must be 16-byte aligned", 0);
+    STAGE_ALIGNED16("sora_hip_fft64", d_in, d_out)
     hipLaunchKernelGGL(k_fft64_batch, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), (uint32_t)n, T);
     return launch_result("k_fft64_batch");
 }
@@ -456,7 +456,7 @@ int sora_hip_fft128(const sora_complex16* d_in, sora_complex16* d_out, size_t n,
 {
     STAGE_ENTRY("sora_hip_fft128", !d_in || !d_out, n)
     Tables T; if (const int rc = stage_tables(&T)) return rc;
-    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_fft128: buffers must be 16-byte aligned", 0);
+    STAGE_ALIGNED16("sora_hip_fft128", d_in, d_out)
     hipLaunchKernelGGL(k_fft128_batch, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, (hipStream_t)stream, u32(d_in), u32(d_out), (uint32_t)n, T);
     return launch_result("k_fft128_batch");
 }
@@ -533,7 +533,7 @@ int sora_hip_demap11a(const sora_complex16* d_in, uint8_t* d_soft, int n_bpsc, s
     STAGE_ENTRY("sora_hip_demap11a", !d_in || !d_soft, n)
     STAGE_NBPSC("sora_hip_demap11a", n_bpsc)
     Tables T; if (const int rc = stage_tables(&T)) return rc;
-    if (!aligned16(d_in, d_soft)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_demap11a: buffers must be 16-byte aligned", 0);
+    STAGE_ALIGNED16("sora_hip_demap11a", d_in, d_soft)
     const dim3 grid((unsigned)((n + 31) / 32));
     STAGE_BY_NBPSC(n_bpsc, k_demap_batch, grid, (hipStream_t)stream, u32(d_in), d_soft, (uint32_t)n, T)
     return launch_result("k_demap_batch");
@@ -544,7 +544,7 @@ int sora_hip_deinterleave11a(const uint8_t* d_in, uint8_t* d_out, int n_bpsc, si
     STAGE_ENTRY("sora_hip_deinterleave11a", !d_in || !d_out, n)
     STAGE_NBPSC("sora_hip_deinterleave11a", n_bpsc)
     Tables T; if (const int rc = stage_tables(&T)) return rc;
-    if (!aligned16(d_in, d_out)) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_hip_deinterleave11a: buffers must be 16-byte aligned", 0);
+    STAGE_ALIGNED16("sora_hip_deinterleave11a", d_in, d_out)
     const dim3 grid((unsigned)((n + 31) / 32));
     STAGE_BY_NBPSC(n_bpsc, k_deint_batch, grid, (hipStream_t)stream, d_in, d_out, (uint32_t)n, T)
     return launch_result("k_deint_batch");

@@ -34,10 +34,8 @@ constexpr int kBytes = 4096;                // field bytes per stream: SERVICE +
 constexpr int kGen = 1040;                  // generator words per stream and output: nsym * NDBPS input bits are at most 32507 (1016 words)
 constexpr int kAmp = kTxHt40Amp;            // A: an LTF / SIG carrier
 constexpr int kStf = 17053;                 // rint(A sqrt(13 / 12))
-constexpr int kPilot = 12288;               // 2 d(1)
 static_assert(kGen % 32 == 16 && kGen * 32 >= 32507 && kBytes >= 4 * 1016 + 4, "LDS plan");
 static_assert(kGen >= 1026 && 2 * kBytes >= 4 * 1026 + 4, "LDS plan, joint coding: 32832 field bits = 1026 generator words, 4108 field bytes in the two streams' arrays");
-__device__ __forceinline__ int level40(int nb) { return nb <= 2 ? 6144 : nb == 4 ? 4000 : 2214; }   // rint(A LEVEL / 128), LEVEL = 48, 48, 31.25, 17.3
 __device__ __forceinline__ uint32_t pk16(int re, int im) { return (uint32_t)(uint16_t)re | ((uint32_t)(uint16_t)im << 16); }
 static __constant__ int8_t kLLtf[53] = {    // L-LTF, carriers -26..26
     1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 0,
@@ -236,7 +234,7 @@ __device__ __forceinline__ void tx_ht40_body(const TxHt40Args& A)
         const uint32_t ibase = s * (uint32_t)nd;
         // the 14 bins that carry nothing: 127, 0, 1 and 59..69 (the buffer holds the symbol before's samples)
         if (e < 14) bins[fft128_swz(e < 3 ? (e + 127) & 127 : 56 + e)] = 0;
-        if (e < 6) bins[fft128_swz((e == 0 ? -53 : e == 1 ? -25 : e == 2 ? -11 : e == 3 ? 11 : e == 4 ? 25 : 53) & 127)] = pk16(kPilot, 0);
+        if (e < 6) bins[fft128_swz((e == 0 ? -53 : e == 1 ? -25 : e == 2 ? -11 : e == 3 ? 11 : e == 4 ? 25 : 53) & 127)] = pk16(kPilot40, 0);
 #pragma unroll
         for (int t = 0; t < 4; t++) {
             if (e + 32 * t < 108) {

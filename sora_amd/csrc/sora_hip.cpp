@@ -1675,20 +1675,29 @@ int sora_hip_tx11n(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t*
     return SORA_OK;
 }
 
+// What sora_hip_preamble11n and sora_hip_preamble_ht40 share behind their own checks and their table: field 0 / 1 of both chains of a two-chain transmitter's table
+// ([2][1120] samples), ncopies < kPreambleCopies times back to back
+constexpr size_t kPreambleCopies = 1ull << 24;
+static int preamble_copy(void (*kernel)(const uint4*, uint4*, uint4*, uint32_t, uint32_t, uint64_t), const char* name, const uint32_t* table, sora_complex16* d_out0,
+                         sora_complex16* d_out1, int field, size_t ncopies, void* stream)
+{
+    const uint32_t w0 = field ? 160u : 0u, nw = field ? 120u : 160u;             // 16-byte words: samples 0..639 / 640..1119 of a chain's 1120
+    const uint64_t nwords = (uint64_t)ncopies * nw;
+    hipLaunchKernelGGL(kernel, dim3(stage_tiles(nwords, 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(table), reinterpret_cast<uint4*>(d_out0),
+                       reinterpret_cast<uint4*>(d_out1), w0, nw, nwords);
+    return launch_result(name);
+}
+
 // LSrc / HTSrc as a stage (the 802.11n modulation graph's other bricks: k_mod11n.hip): it copies the transmitter's table, so it stands here
 int sora_hip_preamble11n(sora_complex16* d_out0, sora_complex16* d_out1, int field, size_t ncopies, void* stream)
 {
     STAGE_ENTRY("sora_hip_preamble11n", !d_out0 || !d_out1, ncopies)
     if (field != 0 && field != 1) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble11n: field must be 0 (LSrc) or 1 (HTSrc)");
-    if (!aligned16(d_out0, d_out1)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble11n: buffers must be 16-byte aligned");
-    if (ncopies >= (1ull << 24)) return fail(SORA_ERR_CAPACITY, "sora_hip_preamble11n: too many copies for one call");
+    STAGE_ALIGNED16("sora_hip_preamble11n", d_out0, d_out1)
+    if (ncopies >= kPreambleCopies) return fail(SORA_ERR_CAPACITY, "sora_hip_preamble11n: too many copies for one call");
     DevTables* D = device_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     if (const int rc = tx11n_preamble_ready(D)) return rc;
-    const uint32_t w0 = field ? 160u : 0u, nw = field ? 120u : 160u;             // 16-byte words: samples 0..639 / 640..1119 of a chain's 1120
-    const uint64_t nwords = (uint64_t)ncopies * nw;
-    hipLaunchKernelGGL(k_mod11n_preamble, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(D->tx11n_preamble),
-                       reinterpret_cast<uint4*>(d_out0), reinterpret_cast<uint4*>(d_out1), w0, nw, nwords);
-    return launch_result("k_mod11n_preamble");
+    return preamble_copy(k_mod11n_preamble, "k_mod11n_preamble", D->tx11n_preamble, d_out0, d_out1, field, ncopies, stream);
 }
 
 // ---- 40 MHz HT 2x2 transmitter
@@ -1785,15 +1794,11 @@ int sora_hip_preamble_ht40(sora_complex16* d_out0, sora_complex16* d_out1, int f
 {
     if (field != 0 && field != 1) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble_ht40: field must be 0 (L-STF, L-LTF) or 1 (HT-STF, HT-LTF1, HT-LTF2)");
     STAGE_ENTRY("sora_hip_preamble_ht40", !d_out0 || !d_out1, ncopies)
-    if (!aligned16(d_out0, d_out1)) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_preamble_ht40: buffers must be 16-byte aligned");
-    if (ncopies >= (1ull << 24)) return fail(SORA_ERR_CAPACITY, "sora_hip_preamble_ht40: too many copies for one call");
+    STAGE_ALIGNED16("sora_hip_preamble_ht40", d_out0, d_out1)
+    if (ncopies >= kPreambleCopies) return fail(SORA_ERR_CAPACITY, "sora_hip_preamble_ht40: too many copies for one call");
     DevTables* D = device_tables(); if (!D) return fail(SORA_ERR_HARDWARE_FAILED, "table upload failed");
     if (const int rc = tx_ht40_preamble_ready(D, (hipStream_t)stream)) return rc;
-    const uint32_t w0 = field ? 160u : 0u, nw = field ? 120u : 160u;             // 16-byte words: samples 0..639 / 640..1119 of a chain's 1120
-    const uint64_t nwords = (uint64_t)ncopies * nw;
-    hipLaunchKernelGGL(k_mod_ht40_preamble, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(D->tx_ht40_preamble),
-                       reinterpret_cast<uint4*>(d_out0), reinterpret_cast<uint4*>(d_out1), w0, nw, nwords);
-    return launch_result("k_mod_ht40_preamble");
+    return preamble_copy(k_mod_ht40_preamble, "k_mod_ht40_preamble", D->tx_ht40_preamble, d_out0, d_out1, field, ncopies, stream);
 }
 
 // ---- 802.11b transmitter

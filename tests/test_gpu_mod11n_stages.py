@@ -106,7 +106,7 @@ def test_sig_map(env):
     x = np.random.default_rng(11).integers(0, 256, (65, 18)).astype(np.uint8)
     x[0] = 0; x[1] = 0xFF
     want = M.sig_map(x)
-    for n in (1, 2, 65):
+    for n in (1, 2, 31, 32, 33, 65):                                             # the edges of a tile of 32 frames either side
         assert np.array_equal(sora.sig_map11n(dev(torch, x[:n])).cpu().numpy(), want[:n]), n
 
 
@@ -134,7 +134,7 @@ def test_add_pilot(env, iss):
     assert np.array_equal(M.add_pilot(car[:145], iss)[125:], M.add_pilot(car[125:145], iss, 125))
 
 
-NSYM_T = (1, 7, 8, 9, 257)
+NSYM_T = (1, 7, 8, 9, 31, 32, 33, 257)               # a group of 8 symbols' edges, the IFFT workgroup's 32 either side, several workgroups
 
 
 @pytest.fixture(scope="module")

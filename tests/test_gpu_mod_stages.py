@@ -9,7 +9,7 @@ from tx11a44_model import has_rail, up40to44
 
 pytestmark = pytest.mark.gpu
 
-NSYMS = (1, 2, 63, 64, 65, 257)                                                  # one symbol, a part of a tile, a tile's edges either side, several workgroups
+NSYMS = (1, 2, 31, 32, 33, 63, 64, 65, 257)                                      # one symbol, a part of a tile, the edges of one tile of 32 and of two either side, several workgroups
 
 
 @pytest.fixture(scope="module")
