@@ -46,7 +46,8 @@ extern "C" {
  * (sora_cca11n_state), _data_symbol11n, _stream_join11n, and the tail it shares with the 802.11a graph, sora_hip_desc11a, _frame_sink11a (sora_sink11a_rec); the front end
  * of the 802.11a receive graph -- sora_hip_dc_remove11a, _dc_estimate11a (sora_dcest11a_state), _cca11a (sora_cca11a_state), _carrier_sense11a (sora_cs11a_state),
  * _data_symbol11a, _viterbi_sig11a, _plcp_parse11a (sora_plcp11a_rec); the 40 MHz HT modulation graph's bricks -- sora_hip_stream_parse_ht40, _interleave_ht40,
- * _interleave_ht40_stream, _map_ht40, _sig_map_ht40, _add_pilot_ht40, _ifft_ht40, _add_gi_ht40, _preamble_ht40. */
+ * _interleave_ht40_stream, _map_ht40, _sig_map_ht40, _add_pilot_ht40, _ifft_ht40, _add_gi_ht40, _preamble_ht40; the K=7 decoder at code rate 5/6 as a stage --
+ * sora_hip_viterbi56_11n (SORA_CR_56), and MCS 15 on the 40 MHz pair -- sora_ht40_set_mcs_max, sora_hip_tx_ht40_mcs, _joint_mcs and their _samples. */
 #define SORA_HIP_ABI_VERSION 4
 
 /* COMPLEX16: kernel/core/inc/complex.h */
@@ -68,6 +69,12 @@ typedef struct { int16_t re, im; } sora_complex16;
 
 /* code rates: kernel/bb/Brick11/src/ieee80211const.h:14-20 */
 enum { SORA_CR_12 = 0, SORA_CR_23 = 1, SORA_CR_34 = 2 };
+/* Rate 5/6 (BB11nGetCodingRateFromMcsIndex names CR_56; the reference has no encoder or decoder for it, so the definition is this library's, held to an integer
+ * model): per 5 input bits the coded bits sent are A1 B1 A2 B3 A4 B5 (IEEE 802.11n-2009) -- the reference's 3/4 pattern A1 B1 A2 B3 continued by A4 B5.  A puncture
+ * group is 6 soft values and 5 trellis steps of kinds (A,B) (A) (B) (A) (B).  It is taken by sora_hip_viterbi56_11n, by the descriptors of a 40 MHz receive
+ * handle whose gate is 15 (sora_ht40_set_mcs_max) and by sora_ht40_symbols, and it is what sora_hip_tx_ht40_mcs sends at MCS 15; every other entry point that takes a code
+ * rate accepts SORA_CR_12 / _23 / _34 and answers 3 with SORA_ERR_INVALID_PARAM. */
+enum { SORA_CR_56 = 3 };
 
 /* ------------------------------------------------------------------------------------------------
  * Whole-path receiver = the demod graph CreateDemodGraph11a_40M (kernel/bb/demod11/fb11ademod_config.hpp:
@@ -393,6 +400,24 @@ int sora_hip_viterbi11n_ws(const uint8_t* d_soft, size_t soft_span_bytes, const 
  * sora_rx_window_stats's order: out[0] unit boundaries compared, out[1] boundaries whose vectors differed, out[2] jobs decoded again serially
  * because of that, out[3] units.  Waits for `stream` (the stream of that call).  Calls with another lanes_per_pair leave the record as it was. */
 int sora_hip_viterbi_window_stats(const void* d_workspace, unsigned long long out[4], void* stream);
+/* The same decoder at code rate 5/6 (SORA_CR_56), a kernel of its own (k_viterbi56_11n): T11aViterbi<.., 192, 36>::Process with a fourth branch and ONE rule changed.
+ *   - Per puncture group p[0..5]: ACS(A,B)(p0,p1) ACS(A)(p2) ACS(B)(p3) ACS(A)(p4) ACS(B)(p5), then trellis_index += 5, p += 6.
+ *   - The metrics are normalised after every step whose index is a multiple of 8, also inside a group.  (The reference's rule, (trellis_index & 7) == 0 after a group,
+ *     would fire every 40 steps -- up to 8 x 84 units of growth in an 8-bit wrapping metric, which decodes nothing; every 8 steps is rate 1/2's cadence with less growth,
+ *     at most 140 units against 224.)
+ *   - The trace-back schedule is examined after every group with the other rates' expressions: a frame's last trace-back at the first group end with trellis_index >=
+ *     8 length + 22 (look = the excess, 0..4); else, from trellis_index >= ob + 192 + 36 + 6 on, a window of 192 bits with look = 36 + remain, remain =
+ *     (trellis_index - (ob + 234)) % 8 (0..4).  Metric initialisation, tie-breaks, the arg-min key and the 6-bit prefix are unchanged.
+ *   - Soft values short of a whole group at the end of a stream are not decoded; a stream that ends in front of its frame's last trace-back yields the whole windows
+ *     it holds and nothing else.
+ * tests/cxx/viterbi56_model.c states all of it as a program, and the kernel is held to it bit for bit.  One BYTE per soft value, of which only the low three bits are
+ * read (what sora_ht40_soft_of returns); job i reads d_nsoft[i] bytes at d_soft + d_soft_off[i] (any alignment) and writes d_frame_len[i] + 2 decoded bytes at d_out +
+ * d_out_off[i].  Consecutive jobs (2k, 2k + 1) share a wave.  soft_span_bytes = the extent of d_soft: no byte at or behind d_soft + soft_span_bytes is ever read,
+ * whatever the offsets say, so the stage needs no workspace and no slack behind the last stream; 0 is SORA_ERR_INVALID_PARAM, 2^32 or more SORA_ERR_CAPACITY.  No
+ * allocation and no host wait.  Not offered: the sixteen-lane and window-parallel forms, a rate 5/6 encoder stage (sora_hip_conv_encode11a keeps refusing rate 3),
+ * BRICK adapters. */
+int sora_hip_viterbi56_11n(const uint8_t* d_soft, size_t soft_span_bytes, const uint32_t* d_soft_off, const uint32_t* d_nsoft, const uint16_t* d_frame_len,
+                           uint8_t* d_out, const uint32_t* d_out_off, size_t n, void* stream);
 
 /* Capture ingest in front of the receive graph, one streaming pass on the device:
  *   SORA_INGEST_RXBLOCK    the input is a Sora dump: 128-byte RX_BLOCKs = 16-byte descriptor + 28 COMPLEX16
@@ -603,6 +628,18 @@ int sora_hip_tx_ht40_gi(const uint8_t* d_mpdu, const uint32_t* d_off, const uint
 size_t sora_hip_tx_ht40_joint_gi_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, uint32_t gi);
 int sora_hip_tx_ht40_joint_gi(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed, const uint8_t* d_gi,
                               size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream);
+/* MCS 15 (two streams, 64-QAM, rate 5/6: SORA_CR_56 above): the _gi entry points' arguments plus a gate, int mcs_max.  14: the _gi entry
+ * points' output byte for byte -- their kernels are launched, MCS 15 writes nothing and counts 0 samples.  15: MCS 15 is accepted as well, for 1..3996 bytes, in both
+ * codings and both guard intervals: N_BPSC 6, N_DBPS = 540 per stream (1080 over the one field of the joint coding), N_SYM = ceil((16 + 8 (len + 4) + 6) / N_DBPS), the
+ * encoder's output punctured to A1 B1 A2 B3 A4 B5 per five input bits (N_CBPS per stream, 648, is a whole number of such groups), HT-SIG's MCS field 15; everything
+ * else in the header and in the frame is MCS 14's.  Any other gate is SORA_ERR_INVALID_PARAM (the _samples forms: 0).  sora_hip_tx_ht40, _joint and the _gi forms keep
+ * refusing MCS 15.  What takes such frames: a receive handle after sora_ht40_set_mcs_max(rx, 15). */
+size_t sora_hip_tx_ht40_mcs_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, uint32_t gi, int mcs_max);
+int sora_hip_tx_ht40_mcs(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed, const uint8_t* d_gi,
+                         size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, int mcs_max, void* stream);
+size_t sora_hip_tx_ht40_joint_mcs_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, uint32_t gi, int mcs_max);
+int sora_hip_tx_ht40_joint_mcs(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed, const uint8_t* d_gi,
+                               size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, int mcs_max, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The bricks of the 40 MHz HT 2x2 modulation graph as stage entry points: what sora_hip_tx_ht40, _joint and _gi fuse, brick by brick, so that a host can replace ONE
@@ -1204,6 +1241,25 @@ uint32_t sora_ht40_symbols_joint(uint32_t length, uint32_t n_bpsc, uint32_t code
 #define SORA_HT40_GUARD_LONG      0
 #define SORA_HT40_GUARD_SIGNALLED 1
 int      sora_ht40_set_guard(sora_ht40_t* rx, int mode);
+
+/* MCS 15 (two streams, 64-QAM, rate 5/6; 270 / 300 Mbit/s with the long / short guard interval) on the receive handle.  The rate's
+ * definition -- the puncture pattern and the decoder -- is SORA_CR_56's and sora_hip_viterbi56_11n's above: N_CBPS per stream is 108 N_BPSC, a whole number of 6-value
+ * groups for every N_BPSC; N_DBPS is 90 N_BPSC per stream (540 at MCS 15) and twice that in the joint coding (1080).
+ * sora_ht40_set_mcs_max(rx, mcs_max) sets the gate: 14 (the default) or 15, anything else above 0 is SORA_ERR_INVALID_PARAM; returns the previous value; an argument
+ * <= 0 only queries.  Like sora_ht40_set_guard it first waits for every call in flight and starts every stream afresh (a frame the gate now admits changes what a
+ * stream holds).  With the gate at 14 nothing differs: SORA_CR_56 on a descriptor is SORA_ERR_INVALID_PARAM, MCS 15 in HT-SIG is a header failure, every call launches
+ * the kernels it always launched.  With the gate at 15:
+ *   - descriptor calls: sora_ht40_frame.code_rate may be SORA_CR_56, with or without SORA_HT40_SHORT_GI, with any n_bpsc of 1 / 2 / 4 / 6, in both codings; rows of such a
+ *     frame carry rate_kbps = 10 n_bpsc + 3.  sora_ht40_soft_of works unchanged (the soft bytes do not depend on the code rate).
+ *   - raw captures: the front end's gate is 8 <= MCS <= 15; a recorded MCS 15 frame has sora_ht40_found.mcs = 15 and rows with rate_kbps = 15.
+ *   - the frames of rate 5/6 are a FOURTH job list, decoded by k_viterbi56_11n behind the call's trellis kernel: launched for a descriptor call only when the call
+ *     holds such a frame, for a raw-capture or stream-mode call always (on an empty list its waves return at once).  sora_ht40_set_trellis does not apply to that
+ *     list: it has one kernel, 64 lanes per pair -- the two streams of a frame, or two joint frames.
+ * sora_ht40_symbols accepts code_rate SORA_CR_56 whatever a handle's gate is (a pure function); sora_ht40_symbols_joint keeps answering it with 0, as it always has (a
+ * test of the joint coding pins that): a joint rate-5/6 frame has ceil((16 + 8 LENGTH + 6) / (180 N_BPSC)) data symbols, and a gate-15 handle's rows report the count.
+ * Not offered: MCS 15 on the 20 MHz pair (sora_rx11n_*, sora_hip_tx11n: its symbol-slot storage is sized for 3/4), the stage compositions at rate 5/6, BRICK adapters,
+ * the sixteen-lane and window-parallel trellis forms for rate 5/6. */
+int      sora_ht40_set_mcs_max(sora_ht40_t* rx, int mcs_max);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU sharding for a C host.  Captures are independent -- the reference resets its context per

@@ -6,7 +6,7 @@ this package is the thin Python binding used by the tests and bench.py.  There i
 from .capi import (Rx, Rx11b, Rx11n, RxHt40, ht40_symbols, HostResults, ROW_DTYPE, ROW_TRUNCATED, ROW_SHORT_PREAMBLE, SoraError, device_count, load, lib_path, fft64, fft128, lts11a, symfront11a,
     pilot_track11a, pilot11a, set_share_window_us, freq_comp11a, equalize11a, phase_comp11a, demap11a, deinterleave11a, demap11n, deinterleave11n, mimo_est11n, mimo_comp11n,
     cfo_est11n, freq_comp11n, pilot_track11n, siso_est11n, siso_comp11n, sig_demap11n, sig_decode11n, viterbi11a, viterbi11a_ws, viterbi11a_workspace_bytes,  # noqa: F401
-                   viterbi11n_ws, viterbi11n_workspace_bytes, viterbi_window_stats,
+                   viterbi11n_ws, viterbi11n_workspace_bytes, viterbi_window_stats, viterbi56_11n, CR_56,
                    ingest, ingest_count, scramble11a, conv_encode11a, interleave11a, map11a, add_pilot11a, ifftx11a, upsample40to44, pack16to8, preamble11a,
                    mod11a_by_stages, Mod11aStages, mod11a_fields, CR_12, CR_23, CR_34,
                    stream_parse11n, interleave11n, map11n, sig_map11n, add_pilot11n, ifft_only11n, csd11n, add_gi11n, preamble11n,

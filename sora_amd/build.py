@@ -12,10 +12,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "lib", "obj")
 LIB = os.path.join(HERE, "lib", "libsora_hip.so")
-SOURCES = ["k_scan.hip", "k_rx.hip", "k_vit16.hip", "k_vitwin.hip", "k_stage.hip", "k_tx.hip", "k_tx11n.hip", "k_tx_ht40.hip", "k_tx11b.hip", "k_mod.hip", "k_mod11n.hip", "k_mod11b.hip",
-    "k_mod_ht40.hip", "k_11b.hip", "k_rx11b.hip", "k_11n.hip", "k_11a.hip", "k_rx11n.hip", "k_ht40.hip", "k_ht40_stages.hip", "k_deliver.hip", "sora_hip.cpp", "sora_shard.cpp"]
-HEADERS = ["dev_arith.h", "dev_viterbi.h", "dev_vit16.h", "dev_winplan.h", "dev_vitwin.h", "dev_11n.h", "dev_ht40.h", "dev_pilot11a.h", "dev_sym11a.h", "dev_tx.h", "dev_mod.h", "dev_11b.h",
-           "dev_mod11b.h", "dev_cs11a.h", "rx_types.h", "kernels.h", "host_calls.h", "host_trellis.h", "host_stage.h", os.path.join("..", "..", "include", "sora_hip.h")]
+SOURCES = ["k_scan.hip", "k_rx.hip", "k_vit16.hip", "k_vitwin.hip", "k_vit56.hip", "k_stage.hip", "k_tx.hip", "k_tx11n.hip", "k_tx_ht40.hip", "k_tx_ht40_mcs.hip", "k_tx11b.hip",
+    "k_mod.hip", "k_mod11n.hip", "k_mod11b.hip", "k_mod_ht40.hip", "k_11b.hip", "k_rx11b.hip", "k_11n.hip", "k_11a.hip", "k_rx11n.hip", "k_ht40.hip", "k_ht40_stages.hip", "k_deliver.hip",
+    "sora_hip.cpp", "sora_shard.cpp"]
+HEADERS = ["dev_arith.h", "dev_viterbi.h", "dev_vit16.h", "dev_winplan.h", "dev_vitwin.h", "dev_vit56.h", "dev_11n.h", "dev_ht40.h", "dev_pilot11a.h", "dev_sym11a.h", "dev_tx.h", "dev_tx_ht40.h",
+           "dev_mod.h", "dev_11b.h", "dev_mod11b.h", "dev_cs11a.h", "rx_types.h", "kernels.h", "host_calls.h", "host_trellis.h", "host_stage.h", os.path.join("..", "..", "include", "sora_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-x", "hip"]   # hidden: the library exports what include/sora_hip.h declares, nothing else
 
 

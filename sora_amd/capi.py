@@ -71,7 +71,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
                       "sora_rx_kernel_name_fused", "sora_hip_fft64", "sora_hip_fft128", "sora_hip_lts11a", "sora_hip_symfront11a", "sora_hip_pilot_track11a", "sora_hip_pilot11a",
                       "sora_hip_freq_comp11a", "sora_hip_equalize11a", "sora_hip_phase_comp11a", "sora_hip_demap11a", "sora_hip_deinterleave11a", "sora_hip_viterbi11a",
                       "sora_hip_viterbi11a_ws", "sora_hip_viterbi11a_workspace_bytes", "sora_hip_viterbi11n_ws", "sora_hip_viterbi11n_workspace_bytes",
-                      "sora_hip_viterbi_window_stats",
+                      "sora_hip_viterbi_window_stats", "sora_hip_viterbi56_11n",
            "sora_hip_ingest", "sora_hip_ingest_count", "sora_hip_tx11a", "sora_hip_tx11a_samples", "sora_hip_tx11a44", "sora_hip_tx11a44_samples",
            "sora_hip_scramble11a", "sora_hip_conv_encode11a", "sora_hip_interleave11a", "sora_hip_map11a", "sora_hip_add_pilot11a", "sora_hip_add_pilot11a_from",
            "sora_hip_ifftx11a", "sora_hip_upsample40to44", "sora_hip_pack16to8", "sora_hip_preamble11a",
@@ -85,6 +85,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_hip_pulse_shape11b",
            "sora_hip_tx_ht40_joint", "sora_hip_tx_ht40_joint_samples",
            "sora_hip_tx_ht40_gi", "sora_hip_tx_ht40_gi_samples", "sora_hip_tx_ht40_joint_gi", "sora_hip_tx_ht40_joint_gi_samples",
+           "sora_hip_tx_ht40_mcs", "sora_hip_tx_ht40_mcs_samples", "sora_hip_tx_ht40_joint_mcs", "sora_hip_tx_ht40_joint_mcs_samples",
            "sora_hip_stream_parse_ht40", "sora_hip_interleave_ht40", "sora_hip_interleave_ht40_stream", "sora_hip_map_ht40", "sora_hip_sig_map_ht40",
            "sora_hip_add_pilot_ht40", "sora_hip_ifft_ht40", "sora_hip_add_gi_ht40", "sora_hip_preamble_ht40",
            "sora_hip_demap11n", "sora_hip_deinterleave11n", "sora_hip_mimo_est11n", "sora_hip_mimo_comp11n", "sora_hip_cfo_est11n", "sora_hip_freq_comp11n",
@@ -104,7 +105,7 @@ EXPORTS = ["sora_hip_abi_version", "sora_hip_last_error", "sora_hip_device_count
            "sora_ht40_symbols", "sora_ht40_create", "sora_ht40_destroy", "sora_ht40_stream", "sora_ht40_synchronize", "sora_ht40_set_trellis", "sora_ht40_process_dev",
                       "sora_ht40_process_captures_dev", "sora_ht40_results", "sora_ht40_ticket", "sora_ht40_calls_in_flight", "sora_ht40_wait", "sora_ht40_wait_any",
                       "sora_ht40_stream_of", "sora_ht40_results_of", "sora_ht40_soft_of", "sora_ht40_found_of", "sora_ht40_set_stream_mode", "sora_ht40_stream_consumed",
-                      "sora_ht40_set_coding", "sora_ht40_symbols_joint", "sora_ht40_set_guard",
+                      "sora_ht40_set_coding", "sora_ht40_symbols_joint", "sora_ht40_set_guard", "sora_ht40_set_mcs_max",
            "sora_shard_unique_id", "sora_shard_create", "sora_shard_destroy", "sora_shard_world", "sora_shard_partition", "sora_shard_gather_rows",
            "sora_shard_reduce_counters", "sora_shard_gather_results", "sora_shard_gather_results_mpdu"]
 
@@ -214,6 +215,7 @@ def load(build_if_missing=True):
     L.sora_ht40_symbols_joint.argtypes = [ctypes.c_uint32] * 3; L.sora_ht40_symbols_joint.restype = ctypes.c_uint32
     L.sora_ht40_set_coding.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.sora_ht40_set_guard.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.sora_ht40_set_mcs_max.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.sora_ht40_create.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
     L.sora_ht40_process_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Ht40Frame), ctypes.c_size_t, ctypes.c_void_p]
     L.sora_ht40_results.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameResult), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t]
@@ -247,6 +249,8 @@ def load(build_if_missing=True):
     L.sora_hip_viterbi11n_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t]; L.sora_hip_viterbi11n_workspace_bytes.restype = ctypes.c_size_t
     L.sora_hip_viterbi11n_ws.argtypes = L.sora_hip_viterbi11a_ws.argtypes
     L.sora_hip_viterbi_window_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_void_p]
+    L.sora_hip_viterbi56_11n.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                         ctypes.c_void_p]
     L.sora_hip_stream_synchronize.argtypes = [ctypes.c_void_p]
     L.sora_hip_tx11a_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11a_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11a.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -302,6 +306,10 @@ def load(build_if_missing=True):
         fn.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
     for fn in (L.sora_hip_tx_ht40_gi_samples, L.sora_hip_tx_ht40_joint_gi_samples):
         fn.argtypes = [ctypes.c_uint32] * 3; fn.restype = ctypes.c_size_t
+    for fn in (L.sora_hip_tx_ht40_mcs, L.sora_hip_tx_ht40_joint_mcs):
+        fn.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p]
+    for fn in (L.sora_hip_tx_ht40_mcs_samples, L.sora_hip_tx_ht40_joint_mcs_samples):
+        fn.argtypes = [ctypes.c_uint32] * 3 + [ctypes.c_int]; fn.restype = ctypes.c_size_t
     L.sora_hip_tx11b_samples.argtypes = [ctypes.c_uint32, ctypes.c_uint32]; L.sora_hip_tx11b_samples.restype = ctypes.c_size_t
     L.sora_hip_tx11b.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
     L.sora_hip_tx11b_pre_samples.argtypes = [ctypes.c_uint32] * 3; L.sora_hip_tx11b_pre_samples.restype = ctypes.c_size_t
@@ -887,6 +895,13 @@ class RxHt40(_Handle):
         if r < 0: _check(r)
         return r
 
+    def set_mcs_max(self, mcs_max=0):
+        """sora_ht40_set_mcs_max: 14 (the default) or 15 (descriptors may carry CR_56, the front end of process_captures_dev admits MCS 15; such frames are decoded by
+        k_viterbi56_11n).  -> the previous value; an argument <= 0 only queries"""
+        r = int(self._L.sora_ht40_set_mcs_max(self._h, int(mcs_max)))
+        if r < 0: _check(r)
+        return r
+
     def process_dev(self, d_iq0, d_iq1, descs, d_weights=None):
         arr = self.frames(descs); n = getattr(arr, "_n", len(arr))
         _hold(self, (d_iq0, d_iq1, d_weights)); self._n = n
@@ -1219,6 +1234,23 @@ def viterbi11n_ws(soft, soft_off, nsoft, frame_len, code_rate, workspace, out=No
         out_off = (torch.arange(n, device=soft.device, dtype=torch.int32) * out_stride).contiguous()
     _check(load().sora_hip_viterbi11n_ws(_dev_ptr(soft), soft.numel(), _dev_ptr(soft_off), _dev_ptr(nsoft), _dev_ptr(frame_len), code_rate,
                                          _dev_ptr(out), _dev_ptr(out_off), n, _dev_ptr(workspace), workspace.numel(), int(lanes_per_pair), _stream_ptr(stream)))
+    return out
+
+
+CR_56 = 3
+
+
+def viterbi56_11n(soft, soft_off, nsoft, frame_len, out=None, out_off=None, out_stride=2560, stream=None):
+    """The K=7 decoder at code rate 5/6 (SORA_CR_56: A1 B1 A2 B3 A4 B5) with the 802.11n graph's 192 / 36 window schedule, k_viterbi56_11n: soft = uint8 CUDA
+    tensor, one byte per soft value (its low three bits), job i = nsoft[i] bytes at soft_off[i] (uint32 / int32 CUDA tensors), frame_len int16 / uint16.  Nothing at or
+    behind soft.numel() is read; no workspace, no allocation beyond `out`, no host wait.  -> out (uint8 [n, out_stride], or the caller's with its out_off)."""
+    import torch
+    n = soft_off.shape[0]
+    if out is None:
+        out = torch.zeros((n, out_stride), dtype=torch.uint8, device=soft.device)
+        out_off = (torch.arange(n, device=soft.device, dtype=torch.int32) * out_stride).contiguous()
+    _check(load().sora_hip_viterbi56_11n(_dev_ptr(soft), soft.numel(), _dev_ptr(soft_off), _dev_ptr(nsoft), _dev_ptr(frame_len), _dev_ptr(out), _dev_ptr(out_off), n,
+                                         _stream_ptr(stream)))
     return out
 
 
@@ -2704,9 +2736,13 @@ def mod11n_by_stages(mpdus, mcs, seeds=None, device=0, sync=True):
     return out0, out1, plan.offsets
 
 
-def tx_ht40_samples(mpdu_len_nofcs, mcs):
-    """Samples per TX chain of one 40 MHz HT 2x2 frame (sora_hip_tx_ht40_samples): 1280 + 160 (2 + N_SYM); 0 for an MCS or length that is not accepted."""
-    return int(load().sora_hip_tx_ht40_samples(int(mpdu_len_nofcs), int(mcs)))
+def tx_ht40_samples(mpdu_len_nofcs, mcs, mcs_max=14, gi=0, joint=False):
+    """Samples per TX chain of one 40 MHz HT 2x2 frame (sora_hip_tx_ht40_samples): 1280 + 160 (2 + N_SYM); 0 for an MCS or length that is not accepted.
+    mcs_max other than 14, a kind gi or joint=True: sora_hip_tx_ht40_mcs_samples / _joint_mcs_samples (mcs_max=15 accepts MCS 15; gi 1: 1600 + 144 N_SYM)."""
+    if mcs_max == 14 and not gi and not joint:
+        return int(load().sora_hip_tx_ht40_samples(int(mpdu_len_nofcs), int(mcs)))
+    fn = load().sora_hip_tx_ht40_joint_mcs_samples if joint else load().sora_hip_tx_ht40_mcs_samples
+    return int(fn(int(mpdu_len_nofcs), int(mcs), int(gi) & 0xFFFFFFFF, int(mcs_max)))
 
 
 def tx_ht40_gi_samples(mpdu_len_nofcs, mcs, gi):
@@ -2725,7 +2761,7 @@ def _tx_gi(gi, n, who):
     return g
 
 
-def tx_ht40(mpdus0, mpdus1, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None, gi=None):
+def tx_ht40(mpdus0, mpdus1, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None, gi=None, mcs_max=14):
     """Modulate a batch of MPDU pairs (bytes WITHOUT FCS; mpdus0[f] on spatial stream 0, mpdus1[f] on stream 1, of equal length) as HT-mixed
     40 MHz two-stream frames on the GPU (MCS 8..14): what RxHt40 receives.
     -> (out0, out1, offsets): int16 CUDA tensors [total,2] COMPLEX16 @40 MHz for TX chains 0 and 1, and the offsets list.
@@ -2733,7 +2769,8 @@ def tx_ht40(mpdus0, mpdus1, mcs, seeds=None, device=0, stream=None, sync=True, g
     its HT-LTF 1 starts 1280 samples after its first sample.
     seeds: one (seed0, seed1) pair of scrambler seeds per frame (None: 0x5D, 0x2B).  A frame that is not accepted is refused before any launch.
     gi: None -> sora_hip_tx_ht40; else one guard-interval kind per frame (or one for all), 0 = long, 1 = short (data symbols of 144 samples, HT-SIG bit 31) ->
-    sora_hip_tx_ht40_gi."""
+    sora_hip_tx_ht40_gi.  mcs_max: 14, or 15 -> sora_hip_tx_ht40_mcs with that gate (gi None: all long): MCS 15 (64-QAM, rate 5/6) is accepted as well; any other value
+    is refused."""
     import torch
     n = len(mpdus0)
     mcs = [int(m) for m in mcs] if np.ndim(mcs) else [int(mcs)] * n
@@ -2741,9 +2778,16 @@ def tx_ht40(mpdus0, mpdus1, mcs, seeds=None, device=0, stream=None, sync=True, g
     if len(mpdus1) != n or len(mcs) != n or any(len(b) != l for b, l in zip(mpdus1, lens)):
         raise SoraError(-1, "tx_ht40: one MPDU per stream and frame, both of a frame of the same length")
     gi = _tx_gi(gi, n, "tx_ht40")
-    ns = [tx_ht40_samples(l, m) for l, m in zip(lens, mcs)] if gi is None else [tx_ht40_gi_samples(l, m, g) for l, m, g in zip(lens, mcs, gi)]
+    gated = mcs_max != 14
+    if gated:
+        if mcs_max != 15:
+            raise SoraError(-1, "tx_ht40: mcs_max is 14 or 15")
+        gi = [0] * n if gi is None else gi
+        ns = [tx_ht40_samples(l, m, mcs_max, g) for l, m, g in zip(lens, mcs, gi)]
+    else:
+        ns = [tx_ht40_samples(l, m) for l, m in zip(lens, mcs)] if gi is None else [tx_ht40_gi_samples(l, m, g) for l, m, g in zip(lens, mcs, gi)]
     if any(v == 0 for v in ns):
-        raise SoraError(-1, "tx_ht40: unsupported MCS or length (MCS 8..14, 1..3996 bytes)")
+        raise SoraError(-1, "tx_ht40: unsupported MCS or length (MCS 8..14, or ..15 with mcs_max=15; 1..3996 bytes)")
     if seeds is not None and (len(seeds) != n or any(len(p) != 2 for p in seeds)):
         raise SoraError(-1, "tx_ht40: seeds must hold one pair per frame")
     off = np.zeros(2 * n + 1, np.int64); np.cumsum([(l + 3) // 4 * 4 for l in lens for _ in range(2)], out=off[1:])
@@ -2761,7 +2805,11 @@ def tx_ht40(mpdus0, mpdus1, mcs, seeds=None, device=0, stream=None, sync=True, g
     d_ooff = torch.from_numpy(first.astype(np.int64)).to(dev)
     out0 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
     out1 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
-    if gi is None:
+    if gated:
+        d_gi = torch.from_numpy(np.asarray(gi, np.uint8)).to(dev)
+        _check(load().sora_hip_tx_ht40_mcs(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None,
+                                           _dev_ptr(d_gi), n, _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), int(mcs_max), _stream_ptr(stream)))
+    elif gi is None:
         _check(load().sora_hip_tx_ht40(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
                                        _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
     else:
@@ -2783,10 +2831,10 @@ def tx_ht40_joint_gi_samples(mpdu_len_nofcs, mcs, gi):
     return int(load().sora_hip_tx_ht40_joint_gi_samples(int(mpdu_len_nofcs), int(mcs), int(gi) & 0xFFFFFFFF))
 
 
-def tx_ht40_joint(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None, gi=None):
+def tx_ht40_joint(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps=None, gi=None, mcs_max=14):
     """Modulate a batch of MPDUs (bytes WITHOUT FCS), ONE per frame, as joint-coded HT-mixed 40 MHz two-stream frames on the GPU (MCS 8..14): what an RxHt40 in
     CODING_JOINT receives.  -> (out0, out1, offsets) as tx_ht40.  seeds: one scrambler seed per frame (None: 0x5D).  A frame that is not accepted is refused before
-    any launch.  gi: as tx_ht40's (None -> sora_hip_tx_ht40_joint; else sora_hip_tx_ht40_joint_gi)."""
+    any launch.  gi: as tx_ht40's (None -> sora_hip_tx_ht40_joint; else sora_hip_tx_ht40_joint_gi).  mcs_max: as tx_ht40's (15 -> sora_hip_tx_ht40_joint_mcs)."""
     import torch
     n = len(mpdus)
     mcs = [int(m) for m in mcs] if np.ndim(mcs) else [int(mcs)] * n
@@ -2794,9 +2842,16 @@ def tx_ht40_joint(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps
     if len(mcs) != n:
         raise SoraError(-1, "tx_ht40_joint: one MCS per frame")
     gi = _tx_gi(gi, n, "tx_ht40_joint")
-    ns = [tx_ht40_joint_samples(l, m) for l, m in zip(lens, mcs)] if gi is None else [tx_ht40_joint_gi_samples(l, m, g) for l, m, g in zip(lens, mcs, gi)]
+    gated = mcs_max != 14
+    if gated:
+        if mcs_max != 15:
+            raise SoraError(-1, "tx_ht40_joint: mcs_max is 14 or 15")
+        gi = [0] * n if gi is None else gi
+        ns = [tx_ht40_samples(l, m, mcs_max, g, joint=True) for l, m, g in zip(lens, mcs, gi)]
+    else:
+        ns = [tx_ht40_joint_samples(l, m) for l, m in zip(lens, mcs)] if gi is None else [tx_ht40_joint_gi_samples(l, m, g) for l, m, g in zip(lens, mcs, gi)]
     if any(v == 0 for v in ns):
-        raise SoraError(-1, "tx_ht40_joint: unsupported MCS or length (MCS 8..14, 1..3996 bytes)")
+        raise SoraError(-1, "tx_ht40_joint: unsupported MCS or length (MCS 8..14, or ..15 with mcs_max=15; 1..3996 bytes)")
     if seeds is not None and (len(seeds) != n or any(np.ndim(p) != 0 for p in seeds)):
         raise SoraError(-1, "tx_ht40_joint: seeds must hold one seed per frame")
     off = np.zeros(n + 1, np.int64); np.cumsum([(l + 3) // 4 * 4 for l in lens], out=off[1:])
@@ -2813,7 +2868,11 @@ def tx_ht40_joint(mpdus, mcs, seeds=None, device=0, stream=None, sync=True, gaps
     d_ooff = torch.from_numpy(first.astype(np.int64)).to(dev)
     out0 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
     out1 = torch.zeros((int(ooff[-1]), 2), dtype=torch.int16, device=dev)
-    if gi is None:
+    if gated:
+        d_gi = torch.from_numpy(np.asarray(gi, np.uint8)).to(dev)
+        _check(load().sora_hip_tx_ht40_joint_mcs(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None,
+                                                 _dev_ptr(d_gi), n, _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), int(mcs_max), _stream_ptr(stream)))
+    elif gi is None:
         _check(load().sora_hip_tx_ht40_joint(_dev_ptr(d_blob), _dev_ptr(d_off), _dev_ptr(d_len), _dev_ptr(d_mcs), _dev_ptr(d_seed) if d_seed is not None else None, n,
                                              _dev_ptr(out0), _dev_ptr(out1), _dev_ptr(d_ooff), _stream_ptr(stream)))
     else:

@@ -22,7 +22,10 @@ namespace sora {
 __host__ __device__ inline uint32_t nbpsc11n(uint32_t mcs) { return mcs == 8 ? 1u : mcs <= 10 ? 2u : mcs <= 12 ? 4u : 6u; }
 __host__ __device__ inline uint32_t code_rate11n(uint32_t mcs) { return (mcs == 10 || mcs == 12 || mcs == 14) ? 2u : mcs == 13 ? 1u : 0u; }
 __host__ __device__ inline uint32_t data_bits11n(uint32_t coded, uint32_t cr) { return cr == 0 ? coded / 2 : cr == 1 ? coded / 3 * 2 : coded / 4 * 3; }
-__host__ __device__ inline uint32_t ht40_ndbps(uint32_t nb, uint32_t cr) { return data_bits11n(108u * nb, cr); }     // per stream, 108 data carriers
+// per stream, 108 data carriers; rate 5/6 (SORA_CR_56 = 3, the 40 MHz pair only): 90 N_BPSC
+__host__ __device__ inline uint32_t ht40_ndbps(uint32_t nb, uint32_t cr) { return cr == 3 ? 90u * nb : data_bits11n(108u * nb, cr); }
+// the 40 MHz pair's rate table: MCS 15 is 64-QAM, rate 5/6 (a front end whose gate is 14 never asks)
+__host__ __device__ inline uint32_t code_rate_ht40(uint32_t mcs) { return mcs == 15 ? 3u : code_rate11n(mcs); }
 namespace {
 struct Run { uint8_t v, n; };
 static __constant__ Run kRuns[83] = {

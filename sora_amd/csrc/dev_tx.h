@@ -69,6 +69,16 @@ __device__ __forceinline__ uint32_t tx_punct_offset(int cr, int k, uint32_t gen_
     return (uint32_t)il + (uint32_t)which * gen_bits;
 }
 
+// ... with rate 5/6 beside them (cr 3, SORA_CR_56: the 40 MHz pair's MCS 15; the reference has no such encoder): A1 B1 A2 B3 A4 B5 -- coded bit k = 6 q + r is generator
+// A (r even) or B (r odd) at input bit 5 q + (0, 0, 1, 2, 3, 4)[r].  N_CBPS = 108 N_BPSC per stream is a whole number of these periods too.  A function of its own: what
+// calls tx_punct_offset compiles to what it did.
+__device__ __forceinline__ uint32_t tx_punct_offset56(int cr, int k, uint32_t gen_bits)
+{
+    if (cr != 3) return tx_punct_offset(cr, k, gen_bits);
+    const int q6 = k / 6, r = k - 6 * q6;
+    return (uint32_t)(5 * q6 + (r == 0 ? 0 : r - 1)) + (uint32_t)(r & 1) * gen_bits;
+}
+
 // ---- TMap11a* (mapper11a.hpp:16-43): bit idx of the generator words; one axis of a carrier from its M <= 3 bits, first-transmitted = MSB (InitQamMapLut's
 // reversal), Gray -> binary, level bb * 2 d + lvl0 with lvl0 = -(2^M - 1) d
 __device__ __forceinline__ uint32_t tx_gen_bit(const uint32_t* gab, uint32_t idx) { return (gab[idx >> 5] >> (idx & 31u)) & 1u; }

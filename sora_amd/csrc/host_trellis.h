@@ -134,4 +134,12 @@ template <int WIN> inline void trellis_launch(Trellis kind, const TrellisJobs& J
     }
 }
 
+// ---- code rate 5/6 (SORA_CR_56; k_vit56.hip).  A handle's job table may have a FOURTH list: hdr[3] jobs at jobs + 3 * stride.  The three kinds above keep reading
+// hdr[0..2] and never see it; this enqueues k_viterbi56_11n over it -- one kernel, 64 lanes per pair: a handle's *_set_trellis does not apply to the fourth list.  n: the
+// most jobs the list can hold in this call; soft_bytes: the extent of the soft buffer (no byte at or behind it is read).  A launch over an empty list costs its dispatch.
+inline void trellis_launch56(const TrellisJobs& J, const uint8_t* soft, size_t soft_bytes, uint8_t* out, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_viterbi56_11n, dim3((J.n + 7) / 8), dim3(256), 0, st, J.jobs, J.hdr, J.stride, soft, (uint32_t)soft_bytes, out);
+}
+
 }  // namespace sora

@@ -244,7 +244,7 @@ __device__ __forceinline__ Ht40Geom ht40_geom(const Ht40Found& F, uint32_t joint
 {
     Ht40Geom G;
     const uint32_t mcs = F.mcs & ~SORA_HT40_SHORT_GI;                            // (a short-GI record carries the flag on its MCS: a frame holds the same soft bytes)
-    G.nb = nbpsc11n(mcs); G.cr = code_rate11n(mcs);
+    G.nb = nbpsc11n(mcs); G.cr = code_rate_ht40(mcs);
     const uint32_t nd = ht40_ndbps(G.nb, G.cr) << joint;                         // joint coding: one field over both streams
     G.nsym = (16u + 8u * F.ht_len + 6u + nd - 1u) / nd;                          // sora_ht40_symbols(len, len, nb, cr) / sora_ht40_symbols_joint(len, nb, cr)
     G.per = G.nsym * 108u * G.nb; G.per_pad = (G.per + 31u) / 32u * 32u;
@@ -262,38 +262,40 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
     const uint32_t jpf = joint ? 1u : 2u;
     // Besides the data field's tables: the call's EVENT table for sora_ht40_deliver_async, in (capture, time) order like sora_ht40_results_of -- event e has evn[e] rows (two for a
     // recorded frame, one for a header that failed), template rows tmpl[2 e + k], and evbase[e] = the row of the decoder's row table its rows start at (0xFFFFFFFF: no frame).
-    __shared__ uint32_t s_v[6][1024];
-    __shared__ uint32_t s_base[6];
+    constexpr int NC = 7;                                                        // counters per capture (below); kc(cr): the one of code rate cr
+    auto kc = [](uint32_t cr) { return cr < 3u ? 2u + cr : 6u; };
+    __shared__ uint32_t s_v[NC][1024];
+    __shared__ uint32_t s_base[NC];
     __shared__ uint32_t s_err;
     const uint32_t t = threadIdx.x;
-    if (t < 6) s_base[t] = 0;
+    if (t < NC) s_base[t] = 0;
     if (t == 0) s_err = 0;
     __syncthreads();
     for (uint32_t c0 = 0; c0 < ncaps; c0 += 1024) {
         const uint32_t c = c0 + t;
         const uint32_t n = c < ncaps ? min(nfr[c], mf) : 0u;
-        uint32_t mine[6] = { 0, 0, 0, 0, 0, n };                                 // frames, soft bytes, frames of code rate 0 / 1 / 2, events
+        uint32_t mine[NC] = { 0, 0, 0, 0, 0, n, 0 };                             // frames, soft bytes, frames of code rate 0 / 1 / 2, events, frames of code rate 3 (5/6)
         for (uint32_t i = 0; i < n; i++) {
             const Ht40Found& F = found[(size_t)c * mf + i];
             if (F.error_code != 0) continue;
             const Ht40Geom G = ht40_geom(F, joint);
-            mine[0]++; mine[1] += 2u * G.per_pad; mine[2 + G.cr]++;
+            mine[0]++; mine[1] += 2u * G.per_pad; mine[kc(G.cr)]++;
         }
 #pragma unroll
-        for (int k = 0; k < 6; k++) s_v[k][t] = mine[k];
+        for (int k = 0; k < NC; k++) s_v[k][t] = mine[k];
         __syncthreads();
-        for (uint32_t o = 1; o < 1024; o <<= 1) {                                // Hillis-Steele inclusive scans of the six counters
-            uint32_t add[6];
+        for (uint32_t o = 1; o < 1024; o <<= 1) {                                // Hillis-Steele inclusive scans of the seven counters
+            uint32_t add[NC];
 #pragma unroll
-            for (int k = 0; k < 6; k++) add[k] = t >= o ? s_v[k][t - o] : 0u;
+            for (int k = 0; k < NC; k++) add[k] = t >= o ? s_v[k][t - o] : 0u;
             __syncthreads();
 #pragma unroll
-            for (int k = 0; k < 6; k++) s_v[k][t] += add[k];
+            for (int k = 0; k < NC; k++) s_v[k][t] += add[k];
             __syncthreads();
         }
-        uint32_t at[6];
+        uint32_t at[NC];
 #pragma unroll
-        for (int k = 0; k < 6; k++) at[k] = s_base[k] + s_v[k][t] - mine[k];
+        for (int k = 0; k < NC; k++) at[k] = s_base[k] + s_v[k][t] - mine[k];
         for (uint32_t i = 0; i < n; i++) {
             const Ht40Found& F = found[(size_t)c * mf + i];
             const uint32_t e = at[5]++;                                          // the event's index in the call
@@ -307,8 +309,8 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
                 continue;
             }
             const Ht40Geom G = ht40_geom(F, joint);
-            const uint32_t fi = at[0], soft_off = at[1], pos = jpf * at[2 + G.cr];
-            at[0]++; at[1] += 2u * G.per_pad; at[2 + G.cr]++;
+            const uint32_t fi = at[0], soft_off = at[1], pos = jpf * at[kc(G.cr)];
+            at[0]++; at[1] += 2u * G.per_pad; at[kc(G.cr)]++;
             evbase[e] = jpf * fi; evn[e] = jpf;
             // (reported by wait / results: SORA_ERR_CAPACITY)
             if (fi >= max_frames || (uint64_t)soft_off + 2u * G.per_pad > max_soft || !(F.noise_var >= 0.0f)) { s_err = 1u; evn[e] = 0u; continue; }
@@ -344,7 +346,7 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
         __syncthreads();
         if (t == 1023) {
 #pragma unroll
-            for (int k = 0; k < 6; k++) s_base[k] += s_v[k][1023];
+            for (int k = 0; k < NC; k++) s_base[k] += s_v[k][1023];
         }
         __syncthreads();
     }
@@ -352,7 +354,7 @@ __global__ void __launch_bounds__(1024) k_ht40_plan(const CapDesc* __restrict__ 
     if (t == 0) {
         const bool bad = s_err != 0;
         plan[0] = bad ? 0u : s_base[0]; plan[1] = s_base[0]; plan[2] = s_base[1]; plan[3] = s_err; plan[4] = bad ? 0u : s_base[5];
-        njobs[0] = bad ? 0u : jpf * s_base[2]; njobs[1] = bad ? 0u : jpf * s_base[3]; njobs[2] = bad ? 0u : jpf * s_base[4]; njobs[3] = 0;
+        njobs[0] = bad ? 0u : jpf * s_base[2]; njobs[1] = bad ? 0u : jpf * s_base[3]; njobs[2] = bad ? 0u : jpf * s_base[4]; njobs[3] = bad ? 0u : jpf * s_base[6];
     }
 }
 
@@ -378,6 +380,7 @@ struct Ht40Slot : Call {       // the stream, ticket and completion state of the
     bool capture_mode = false; uint32_t capture_mf = 0; std::vector<Ht40Event> events;
     bool joint = false;         // the coding the call was issued in (sora_ht40_set_coding): one job and one row per frame
     bool guard = false;         // the call can hold a short-GI frame (a flagged descriptor; a raw-capture call in SORA_HT40_GUARD_SIGNALLED): the guard-aware kernels
+    bool rate56 = false;        // the call can hold a rate 5/6 frame (such a descriptor; a raw-capture call of a handle whose gate is 15): k_viterbi56_11n behind the trellis
     uint32_t ncaps = 0;         // captures of a raw-capture call (sora_ht40_stream_consumed); 0 for a descriptor call
     // ... planned on the device (k_ht40_plan): the records come back asynchronously into page-locked memory and are turned into `events` when the call is collected
     uint32_t* d_plan = nullptr;
@@ -401,6 +404,7 @@ struct sora_ht40 {
     Trellis trellis = Trellis::Lanes16;
     int coding = SORA_HT40_CODING_PER_STREAM;                                    // sora_ht40_set_coding
     int guard = SORA_HT40_GUARD_LONG;                                            // sora_ht40_set_guard
+    int mcs_max = 14;                                                            // sora_ht40_set_mcs_max: 15 admits MCS 15 / SORA_CR_56
     // sora_ht40_set_stream_mode: the records belong to the handle, not to a slot; sized for max_frames streams when the mode is first enabled
     StreamRecords records{kRec11nWords};
 };
@@ -426,22 +430,26 @@ static void ht40_free(sora_ht40_t* rx)
 
 uint32_t sora_ht40_symbols(uint32_t length0, uint32_t length1, uint32_t n_bpsc, uint32_t code_rate)
 {
-    if (!(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6) || code_rate > 2) return 0;
+    if (!(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6) || code_rate > SORA_CR_56) return 0;
     const uint32_t L = length0 > length1 ? length0 : length1, nd = ht40_ndbps(n_bpsc, code_rate);
     return (16u + 8u * L + 6u + nd - 1) / nd;
 }
 
-uint32_t sora_ht40_symbols_joint(uint32_t length, uint32_t n_bpsc, uint32_t code_rate)
+// one field over both streams: N_DBPS = 2 x 108 N_BPSC R; code_rate 0 .. max_cr
+static uint32_t ht40_joint_symbols(uint32_t length, uint32_t n_bpsc, uint32_t code_rate, uint32_t max_cr)
 {
-    if (!(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6) || code_rate > 2) return 0;
-    return ht40_symbols_joint(length, 2u * ht40_ndbps(n_bpsc, code_rate));       // one field over both streams: N_DBPS = 2 x 108 N_BPSC R
+    if (!(n_bpsc == 1 || n_bpsc == 2 || n_bpsc == 4 || n_bpsc == 6) || code_rate > max_cr) return 0;
+    return ht40_symbols_joint(length, 2u * ht40_ndbps(n_bpsc, code_rate));
 }
+// (this one keeps answering rate 5/6 with 0, as it did before the rate existed: tests/test_ht40_joint_abi_cpu.py pins that.  A joint rate-5/6 frame has
+// ceil((16 + 8 LENGTH + 6) / (180 N_BPSC)) symbols, which a gate-15 handle's rows report)
+uint32_t sora_ht40_symbols_joint(uint32_t length, uint32_t n_bpsc, uint32_t code_rate) { return ht40_joint_symbols(length, n_bpsc, code_rate, SORA_CR_34); }
 // data symbols of a described frame in the coding of its call
 static inline uint32_t ht40_frame_cr(const sora_ht40_frame& f) { return f.code_rate & ~SORA_HT40_SHORT_GI; }     // SORA_CR_*; any other bit left standing is refused
 static inline bool ht40_frame_short(const sora_ht40_frame& f) { return (f.code_rate & SORA_HT40_SHORT_GI) != 0; }
 static uint32_t ht40_frame_symbols(const sora_ht40_frame& f, bool joint)
 {
-    return joint ? sora_ht40_symbols_joint(f.length[0], f.n_bpsc, ht40_frame_cr(f)) : sora_ht40_symbols(f.length[0], f.length[1], f.n_bpsc, ht40_frame_cr(f));
+    return joint ? ht40_joint_symbols(f.length[0], f.n_bpsc, ht40_frame_cr(f), SORA_CR_56) : sora_ht40_symbols(f.length[0], f.length[1], f.n_bpsc, ht40_frame_cr(f));
 }
 
 int sora_ht40_create(int device, uint32_t max_frames, uint64_t max_soft_values, sora_ht40_t** out)
@@ -460,7 +468,7 @@ int sora_ht40_create(int device, uint32_t max_frames, uint64_t max_soft_values, 
     for (Ht40Slot& S : rx->slot) {
         if (e == hipSuccess) e = sora_internal_stream_create(&S.stream, (int)(&S - &rx->slot[0]));
         if (e == hipSuccess) e = hipMalloc((void**)&S.d_frames, sizeof(Ht40Frame) * max_frames);
-        if (e == hipSuccess) e = hipMalloc((void**)&S.d_jobs, 3 * sizeof(VitJob) * nj);
+        if (e == hipSuccess) e = hipMalloc((void**)&S.d_jobs, 4 * sizeof(VitJob) * nj);     // the three code-rate lists and the rate 5/6 list (host_trellis.h)
         if (e == hipSuccess) e = hipMalloc((void**)&S.d_njobs, 16);
         if (e == hipSuccess) e = hipMalloc((void**)&S.d_fjobs, sizeof(Ht40Job) * nj);
         if (e == hipSuccess) e = hipMalloc((void**)&S.d_soft, max_soft_values * 2 + 4096 + 1024);
@@ -468,7 +476,7 @@ int sora_ht40_create(int device, uint32_t max_frames, uint64_t max_soft_values, 
         if (e == hipSuccess) e = hipMalloc((void**)&S.d_mpdu, nj * 4096);
         if (e == hipSuccess) e = hipMalloc((void**)&S.d_rows, sizeof(Rx11bRow) * nj);
         if (e == hipSuccess) e = hipMalloc((void**)&S.d_plan, 32);
-        if (e == hipSuccess) e = hipHostMalloc(&S.h_stage, sizeof(Ht40Frame) * max_frames + 3 * sizeof(VitJob) * nj + sizeof(Ht40Job) * nj + 64, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc(&S.h_stage, sizeof(Ht40Frame) * max_frames + 4 * sizeof(VitJob) * nj + sizeof(Ht40Job) * nj + 64, hipHostMallocDefault);
         if (e == hipSuccess) e = hipMemset(S.d_soft, 0, max_soft_values * 2 + 4096 + 1024);
         if (e == hipSuccess) e = hipMemset(S.d_vout, 0, nj * kVoutStride + 256);
     }
@@ -527,6 +535,18 @@ int sora_ht40_set_guard(sora_ht40_t* rx, int mode)
     rx->guard = mode;
     return old;
 }
+int sora_ht40_set_mcs_max(sora_ht40_t* rx, int mcs_max)
+{
+    if (!rx) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_set_mcs_max: null handle", 0);
+    const int old = rx->mcs_max;
+    if (mcs_max <= 0) return old;
+    if (mcs_max != 14 && mcs_max != 15) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_set_mcs_max: the gate is 14 (the default) or 15", 0);
+    { const int rc = sora_ht40_synchronize(rx); if (rc) return rc; }
+    HIPCHK(hipSetDevice(rx->device));
+    { const int rc = rx->records.zero(rx->max_frames); if (rc) return rc; }       // a frame the gate now admits changes what a stream holds: every stream starts afresh
+    rx->mcs_max = mcs_max;
+    return old;
+}
 int sora_ht40_stream_consumed(sora_ht40_t* rx, int ticket, uint32_t* h_consumed, size_t ncaps)
 {
     if (!rx || !h_consumed) return sora_internal_fail(SORA_ERR_INVALID_PARAM, "sora_ht40_stream_consumed: null argument", 0);
@@ -544,6 +564,8 @@ static int ht40_data_field(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d
     if (S.guard) hipLaunchKernelGGL(S.joint ? k_ht40_frame_joint_gi : k_ht40_frame_gi, dim3((nframes + 3) / 4), dim3(256), 0, S.stream, A);
     else hipLaunchKernelGGL(S.joint ? k_ht40_frame_joint : k_ht40_frame, dim3((nframes + 3) / 4), dim3(256), 0, S.stream, A);
     trellis_launch<192>(rx->trellis, trellis_lists(S.d_jobs, S.d_njobs, njobs, 2 * rx->max_frames), S.d_soft, S.d_vout, S.stream);
+    // rate 5/6 jobs (the table's fourth list) have a kernel of their own behind it: a descriptor call that holds such a frame, every raw-capture call of a gate-15 handle
+    if (S.rate56) trellis_launch56(trellis_lists(S.d_jobs, S.d_njobs, njobs, 2 * rx->max_frames), S.d_soft, (size_t)rx->max_soft * 2 + 4096 + 1024, S.d_vout, S.stream);
     Ht40FinishArgs Fi; Fi.jobs = S.d_fjobs; Fi.njobs = njobs; Fi.vout = S.d_vout; Fi.mpdu = S.d_mpdu; Fi.rows = S.d_rows; Fi.T = rx->T; Fi.plan = plan;
     hipLaunchKernelGGL(S.joint ? k_ht40_finish_joint : k_ht40_finish, dim3((njobs + 3) / 4), dim3(256), 0, S.stream, Fi);
     HIPCHK(hipGetLastError());
@@ -558,7 +580,7 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
     // (the tables are built in the slot's page-locked staging area -- the slot's previous call has finished -- and uploaded asynchronously)
     Ht40Frame* hf = reinterpret_cast<Ht40Frame*>(S.h_stage);
     VitJob* hj = reinterpret_cast<VitJob*>(hf + rx->max_frames);
-    Ht40Job* fj = reinterpret_cast<Ht40Job*>(hj + 3 * 2 * (size_t)rx->max_frames);
+    Ht40Job* fj = reinterpret_cast<Ht40Job*>(hj + 4 * 2 * (size_t)rx->max_frames);
     uint32_t* nj_stage = reinterpret_cast<uint32_t*>(fj + 2 * (size_t)rx->max_frames);
     uint32_t nj[4] = { 0, 0, 0, 0 };
     uint64_t soft = 0;
@@ -572,9 +594,10 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
         guard = guard || ht40_frame_short(s);
         if (joint && s.length[1] != 0) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
                 "sora_ht40_process_dev: in joint coding a frame carries one PSDU: length[1] must be 0", 0);
-        const uint32_t nsym = ht40_frame_symbols(s, joint);
+        const uint32_t nsym = cr > (rx->mcs_max >= 15 ? (uint32_t)SORA_CR_56 : (uint32_t)SORA_CR_34) ? 0u : ht40_frame_symbols(s, joint);   // SORA_CR_56: sora_ht40_set_mcs_max(15) only
         if (nsym == 0 || s.length[0] > 4000 || s.length[1] > 4000 || !(s.noise_var >= 0.0f)) return sora_internal_fail(SORA_ERR_INVALID_PARAM,
-                "sora_ht40_process_dev: bad frame descriptor (n_bpsc 1/2/4/6, code_rate 0..2 with or without SORA_HT40_SHORT_GI, PSDU <= 4000 bytes, noise_var >= 0)", 0);
+                "sora_ht40_process_dev: bad frame descriptor (n_bpsc 1/2/4/6, code_rate 0..2 -- or 3, SORA_CR_56, after sora_ht40_set_mcs_max(rx, 15) -- with or without "
+                "SORA_HT40_SHORT_GI, PSDU <= 4000 bytes, noise_var >= 0)", 0);
         Ht40Frame& F = hf[i];
         F.offset = s.offset; F.nsym = nsym; F.nb = s.n_bpsc; F.code_rate = cr; F.length[0] = s.length[0]; F.length[1] = s.length[1]; F.cfo = s.cfo;
             F.noise_var = s.noise_var;
@@ -590,7 +613,7 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
         soft += 2 * ((per + 31) / 32 * 32);                                         // bytes: one per soft value, both streams
         F.gi = ht40_frame_short(s) ? 1u : 0u; F.pad[0] = F.pad[1] = F.pad[2] = 0;
     }
-    S.guard = guard;
+    S.guard = guard; S.rate56 = nj[3] != 0;
     if (soft > rx->max_soft) return sora_internal_fail(SORA_ERR_CAPACITY, "sora_ht40_process_dev: more soft values than max_soft_values", 0);
     S.h_frames.assign(frames, frames + nframes); S.nframes = (uint32_t)nframes; rx->have_results = true;
     rx->last = rx->next;
@@ -598,7 +621,7 @@ static int ht40_submit(sora_ht40_t* rx, Ht40Slot& S, const sora_complex16* d_iq0
     if (nframes == 0) return SORA_OK;
     for (int r = 0; r < 4; r++) nj_stage[r] = nj[r];
     HIPCHK(hipMemcpyAsync(S.d_frames, hf, sizeof(Ht40Frame) * nframes, hipMemcpyHostToDevice, S.stream));
-    for (int r = 0; r < 3; r++)                                                   // (only the filled part of each code-rate list)
+    for (int r = 0; r < 4; r++)                                                   // (only the filled part of each code-rate list)
         if (nj[r]) HIPCHK(hipMemcpyAsync(S.d_jobs + r * stride, hj + r * stride, sizeof(VitJob) * nj[r], hipMemcpyHostToDevice, S.stream));
     HIPCHK(hipMemcpyAsync(S.d_njobs, nj_stage, 16, hipMemcpyHostToDevice, S.stream));
     HIPCHK(hipMemcpyAsync(S.d_fjobs, fj, sizeof(Ht40Job) * jpf * nframes, hipMemcpyHostToDevice, S.stream));
@@ -663,7 +686,7 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     for (size_t i = 0; i < ncaps; i++) { CapDesc& h = S.h_capsup[i]; h.offset = caps[i].offset; h.nsamples = caps[i].nsamples;
         h.capture_id = caps[i].capture_id; h.slot_base = 0; h.nslots = 0; }
     S.h_caps.assign(caps, caps + ncaps);
-    S.joint = rx->coding == SORA_HT40_CODING_JOINT; S.guard = rx->guard == SORA_HT40_GUARD_SIGNALLED;
+    S.joint = rx->coding == SORA_HT40_CODING_JOINT; S.guard = rx->guard == SORA_HT40_GUARD_SIGNALLED; S.rate56 = rx->mcs_max >= 15;
     S.events.clear(); S.capture_mode = true; S.capture_mf = mf; S.ncaps = (uint32_t)ncaps; S.events_pending = true; S.plan_error = false; S.nframes = 0;
     S.bound_frames = (uint32_t)std::min<uint64_t>(nrows, rx->max_frames); S.bound_events = (uint32_t)nrows;
     rx->have_results = true; rx->last = rx->next;
@@ -675,7 +698,7 @@ int sora_ht40_process_captures_dev(sora_ht40_t* rx, const sora_complex16* d_iq0,
     { const int rc = sora_internal_scan_ht40(reinterpret_cast<const uint32_t*>(d_iq0), reinterpret_cast<const uint32_t*>(d_iq1), S.d_caps, (uint32_t)ncaps, mf,
             S.d_scanrows, S.d_nfr, S.d_found,
                                              rx->T, rx->sincos, rx->atan, S.stream, rx->records.on ? rx->records.d_cont : nullptr,
-                                             rx->records.on ? rx->records.d_consumed : nullptr, S.joint ? 1u : 0u, S.guard ? 1u : 0u); if (rc) return rc; }
+                                             rx->records.on ? rx->records.d_consumed : nullptr, S.joint ? 1u : 0u, S.guard ? 1u : 0u, (uint32_t)rx->mcs_max); if (rc) return rc; }
     const size_t stride = 2 * (size_t)rx->max_frames;
     hipLaunchKernelGGL(k_ht40_plan, dim3(1), dim3(1024), 0, S.stream, (const CapDesc*)S.d_caps, (uint32_t)ncaps, mf, (const uint32_t*)S.d_nfr, (const Ht40Found*)S.d_found,
                        rx->max_frames, (uint64_t)rx->max_soft, kVoutStride, S.d_frames, S.d_jobs, (uint32_t)stride, S.d_njobs, S.d_fjobs, S.d_evtmpl, S.d_plan, S.d_evbase, S.d_evn,

@@ -433,10 +433,10 @@ __device__ __forceinline__ void scan11n_body(const Scan11nArgs& A, Ht40Found* fo
             const unsigned long long ht = uni64(viterbi_sig_wave<48>(W.sigsoft + 48, reinterpret_cast<uint64_t*>(W.dec), lane) >> 6);
             wave_lds_sync();
             const SigFront P = sig_parse_front(lsig, ht);
-            // the gate.  HT40: two streams, 40 MHz, a rate this library has a decoder for; else mcs_max (10: the reference's ht_frame_mcs >= 11) and 1500 bytes
-            if (HT40) sig_ok = P.ok && P.mcs >= 8 && P.mcs <= 14 && P.cbw40 && P.ht_len <= 4000 && P.ht_len >= 4;
+            // the gate.  HT40: two streams, 40 MHz, up to the handle's mcs_max (14, or 15 after sora_ht40_set_mcs_max); else mcs_max (10: the reference's ht_frame_mcs >= 11) and 1500 bytes
+            if (HT40) sig_ok = P.ok && P.mcs >= 8 && P.mcs <= A.mcs_max && P.cbw40 && P.ht_len <= 4000 && P.ht_len >= 4;
             else sig_ok = P.ok && P.mcs >= 8 && P.mcs <= A.mcs_max && P.ht_len <= 1500;
-            if (sig_ok) { mcs = P.mcs; ht_len = P.ht_len; code_rate = code_rate11n(P.mcs); if constexpr (GI) sgi = (uint32_t)(ht >> 31) & 1u; }
+            if (sig_ok) { mcs = P.mcs; ht_len = P.ht_len; code_rate = HT40 ? code_rate_ht40(P.mcs) : code_rate11n(P.mcs); if constexpr (GI) sgi = (uint32_t)(ht >> 31) & 1u; }
             else err = E_PLCP_HEADER_FAIL;
         }
         // ================================================================ what happens to the frame, without looking at its data field
@@ -557,13 +557,13 @@ __global__ void __launch_bounds__(256) k_scan_ht40_stream_gi(Scan11nArgs A, Ht40
 }  // namespace sora
 int sora_internal_scan_ht40(const uint32_t* iq0, const uint32_t* iq1, const sora::CapDesc* d_caps, uint32_t ncaps, uint32_t max_frames, sora::Rx11bRow* d_rows, uint32_t* d_nframes,
                             sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st, uint32_t* d_cont, uint32_t* d_consumed,
-                            uint32_t joint, uint32_t guard)
+                            uint32_t joint, uint32_t guard, uint32_t mcs_max)
 {
     using namespace sora;
     Scan11nArgs S{};
     S.iq0 = iq0; S.iq1 = iq1; S.caps = d_caps; S.ncaps = ncaps; S.max_frames = max_frames; S.rows = d_rows; S.nframes = d_nframes; S.T = T; S.sincos = sincos; S.atan = atan;
     S.frames = nullptr; S.jobs = nullptr; S.njobs = nullptr; S.nrows = ncaps * max_frames;
-    S.mcs_max = 14; S.soft_per_slot = 0; S.out_per_slot = 0; S.joint = joint; S.guard = guard;    // (the HT40 form has its own gate and queues no 20 MHz data field)
+    S.mcs_max = mcs_max; S.soft_per_slot = 0; S.out_per_slot = 0; S.joint = joint; S.guard = guard;    // (the HT40 form: its gate, 14 or 15; it queues no 20 MHz data field)
     if (guard) {
         if (d_cont) hipLaunchKernelGGL(k_scan_ht40_stream_gi, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found, d_cont, d_consumed);
         else hipLaunchKernelGGL(k_scan_ht40_gi, dim3((ncaps + 3) / 4), dim3(256), 0, st, S, d_found);

@@ -89,6 +89,8 @@ __global__ void k_pipe(RxArgs A, PipeArgs P);
 __global__ void k_viterbi(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
 __global__ void k_viterbi_p3(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
 __global__ void k_viterbi11n(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
+// k_vit56.hip: code rate 5/6, a job table's fourth list (njobs[3] jobs at jobs + 3 stride); span = bytes of the soft buffer: nothing at or behind it is read
+__global__ void k_viterbi56_11n(const VitJob* jobs, const uint32_t* njobs, uint32_t stride, const uint8_t* soft, uint32_t span, uint8_t* out);
 // k_vit16.hip
 __global__ void k_viterbi16(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
 __global__ void k_viterbi16_p3(const VitJob* jobs, const uint32_t* njobs3, uint32_t njobs_single, uint32_t stride, const uint8_t* soft, uint8_t* out);
@@ -217,6 +219,17 @@ __host__ __device__ inline bool tx_ht40_plan_joint(uint32_t len, uint32_t mcs, T
     P.nsym = ht40_symbols_joint(len + 4u, (uint32_t)P.ndbps);
     return true;
 }
+// MCS 15: the two plans behind a gate.  mcs_max 14: the plans above, whatever the MCS; 15: MCS 15 is accepted too -- 64-QAM, rate 5/6
+// (SORA_CR_56 = 3), N_DBPS = 540 per stream, 1080 over both in the joint coding; any other gate accepts nothing.
+__host__ __device__ inline bool tx_ht40_plan_mcs(uint32_t len, uint32_t mcs, uint32_t mcs_max, bool joint, TxHt40Plan& P)
+{
+    if (mcs_max != 14 && mcs_max != 15) return false;
+    if (mcs != 15 || mcs_max != 15) return joint ? tx_ht40_plan_joint(len, mcs, P) : tx_ht40_plan(len, mcs, P);
+    if (len < 1 || len > 3996) return false;
+    P.nb = 6; P.cr = 3; P.ndbps = joint ? 1080 : 540;
+    P.nsym = (16u + 8u * (len + 4u) + 6u + (uint32_t)P.ndbps - 1u) / (uint32_t)P.ndbps;
+    return true;
+}
 constexpr uint32_t kTxHt40Preamble = 1120;               // samples per chain of the table: L-STF + L-LTF + HT-STF + 2 HT-LTF
 constexpr int kTxHt40Amp = 16384;                        // A: the bin value of an LTF / SIG carrier (tests/tx_ht40_model.py)
 __global__ void k_tx_ht40_preamble(uint32_t* tab, Tables T);
@@ -232,6 +245,9 @@ __host__ __device__ inline size_t tx_ht40_frame_samples(uint32_t nsym, uint32_t 
 __host__ __device__ inline uint32_t tx_ht40_lsig_length(uint32_t nsym, uint32_t gi) { return 12u + 3u * (gi ? (9u * nsym + 9u) / 10u : nsym); }
 __global__ void k_tx_ht40_gi(TxHt40Args A);
 __global__ void k_tx_ht40_joint_gi(TxHt40Args A);
+// ... and with the gate at 15 (sora_hip_tx_ht40_mcs, sora_hip_tx_ht40_joint_mcs): the guard-aware kernels that also accept MCS 15
+__global__ void k_tx_ht40_mcs(TxHt40Args A);
+__global__ void k_tx_ht40_joint_mcs(TxHt40Args A);
 // k_mod_ht40.hip: the fixed fields as a stage, launched beside the transmitter whose table it copies (sora_hip_preamble_ht40); nwords 16-byte words
 __global__ void k_mod_ht40_preamble(const uint4* table, uint4* out0, uint4* out1, uint32_t w0, uint32_t nw, uint64_t nwords);
 
@@ -335,7 +351,7 @@ struct Ht40Found {
 // guard: 1 = SORA_HT40_GUARD_SIGNALLED (sora_ht40_set_guard): k_scan_ht40_gi / k_scan_ht40_stream_gi, which read HT-SIG's Short GI bit
 int sora_internal_scan_ht40(const uint32_t* iq0, const uint32_t* iq1, const sora::CapDesc* d_caps, uint32_t ncaps, uint32_t max_frames, sora::Rx11bRow* d_rows, uint32_t* d_nframes,
                             sora::Ht40Found* d_found, const sora::Tables& T, const uint32_t* sincos, const short* atan, hipStream_t st,
-                            uint32_t* d_cont = nullptr, uint32_t* d_consumed = nullptr, uint32_t joint = 0, uint32_t guard = 0);
+                            uint32_t* d_cont = nullptr, uint32_t* d_consumed = nullptr, uint32_t joint = 0, uint32_t guard = 0, uint32_t mcs_max = 14);
 
 // k_deliver.hip: dense rows + MPDUs of a call of the Rx11bRow-table handles into page-locked host memory, behind the call's kernels
 struct DenseStage {                  // per slot / pipeline (grow-only device staging)

@@ -1729,6 +1729,20 @@ size_t sora_hip_tx_ht40_joint_gi_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, 
     return tx_ht40_frame_samples(P.nsym, gi);
 }
 
+size_t sora_hip_tx_ht40_mcs_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, uint32_t gi, int mcs_max)
+{
+    TxHt40Plan P;
+    if (gi > 1 || mcs_max < 0 || !tx_ht40_plan_mcs(mpdu_len_nofcs, mcs, (uint32_t)mcs_max, false, P)) return 0;
+    return tx_ht40_frame_samples(P.nsym, gi);
+}
+
+size_t sora_hip_tx_ht40_joint_mcs_samples(uint32_t mpdu_len_nofcs, uint32_t mcs, uint32_t gi, int mcs_max)
+{
+    TxHt40Plan P;
+    if (gi > 1 || mcs_max < 0 || !tx_ht40_plan_mcs(mpdu_len_nofcs, mcs, (uint32_t)mcs_max, true, P)) return 0;
+    return tx_ht40_frame_samples(P.nsym, gi);
+}
+
 // the fixed fields through the same fixed-point IFFT as every other symbol (the four transmitters and sora_hip_preamble_ht40): built once per device, under the lock,
 // and complete before it is published
 static int tx_ht40_preamble_ready(DevTables* D, hipStream_t st)
@@ -1749,7 +1763,8 @@ static int tx_ht40_preamble_ready(DevTables* D, hipStream_t st)
 // both codings: the per-stream one (two MPDUs and two seeds per frame) and the joint one (one of each).  guard: the _gi entry points, which launch the kernels that read
 // a guard-interval kind per frame (d_gi; null: every frame long); the entry points without it launch the kernels they always launched
 static int tx_ht40_launch(bool joint, const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed,
-                          size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream, bool guard = false, const uint8_t* d_gi = nullptr)
+                          size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream, bool guard = false, const uint8_t* d_gi = nullptr,
+                          bool mcs15 = false)
 {
     if (sora_hip_device_count() <= 0) return fail(SORA_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
     if (!d_mpdu || !d_off || !d_len || !d_mcs || !d_out0 || !d_out1 || !d_out_off) return fail(SORA_ERR_INVALID_PARAM,
@@ -1763,7 +1778,8 @@ static int tx_ht40_launch(bool joint, const uint8_t* d_mpdu, const uint32_t* d_o
     A.mpdu = d_mpdu; A.off = d_off; A.len = d_len; A.mcs = d_mcs; A.seed = d_seed;
     A.out0 = reinterpret_cast<uint32_t*>(d_out0); A.out1 = reinterpret_cast<uint32_t*>(d_out1); A.out_off = d_out_off;
     A.preamble = D->tx_ht40_preamble; A.T = D->T; A.gi = d_gi;
-    if (guard) hipLaunchKernelGGL(joint ? k_tx_ht40_joint_gi : k_tx_ht40_gi, dim3((unsigned)nframes), dim3(256), 0, st, A);
+    if (mcs15) hipLaunchKernelGGL(joint ? k_tx_ht40_joint_mcs : k_tx_ht40_mcs, dim3((unsigned)nframes), dim3(256), 0, st, A);   // (the gate at 15: guard-aware too)
+    else if (guard) hipLaunchKernelGGL(joint ? k_tx_ht40_joint_gi : k_tx_ht40_gi, dim3((unsigned)nframes), dim3(256), 0, st, A);
     else hipLaunchKernelGGL(joint ? k_tx_ht40_joint : k_tx_ht40, dim3((unsigned)nframes), dim3(256), 0, st, A);
     HIPCHK(hipGetLastError());
     return SORA_OK;
@@ -1787,6 +1803,20 @@ int sora_hip_tx_ht40_joint_gi(const uint8_t* d_mpdu, const uint32_t* d_off, cons
                               size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, void* stream)
 {
     return tx_ht40_launch(true, d_mpdu, d_off, d_len, d_mcs, d_seed, nframes, d_out0, d_out1, d_out_off, stream, true, d_gi);
+}
+
+// the _gi entry points behind a gate: 14 launches their kernels (the same bytes), 15 the kernels that accept MCS 15 as well
+int sora_hip_tx_ht40_mcs(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed, const uint8_t* d_gi,
+                         size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, int mcs_max, void* stream)
+{
+    if (mcs_max != 14 && mcs_max != 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_tx_ht40_mcs: mcs_max is 14 or 15");
+    return tx_ht40_launch(false, d_mpdu, d_off, d_len, d_mcs, d_seed, nframes, d_out0, d_out1, d_out_off, stream, true, d_gi, mcs_max == 15);
+}
+int sora_hip_tx_ht40_joint_mcs(const uint8_t* d_mpdu, const uint32_t* d_off, const uint32_t* d_len, const uint32_t* d_mcs, const uint8_t* d_seed, const uint8_t* d_gi,
+                               size_t nframes, sora_complex16* d_out0, sora_complex16* d_out1, const uint64_t* d_out_off, int mcs_max, void* stream)
+{
+    if (mcs_max != 14 && mcs_max != 15) return fail(SORA_ERR_INVALID_PARAM, "sora_hip_tx_ht40_joint_mcs: mcs_max is 14 or 15");
+    return tx_ht40_launch(true, d_mpdu, d_off, d_len, d_mcs, d_seed, nframes, d_out0, d_out1, d_out_off, stream, true, d_gi, mcs_max == 15);
 }
 
 // the fixed fields as a stage (the 40 MHz HT modulation graph's other bricks: k_mod_ht40.hip): it copies the transmitters' table, so it stands here
